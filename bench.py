@@ -18,8 +18,13 @@ inside the timed region.  ``device_resident`` is the same cycle with inputs and
 outputs kept in HBM (round 1's headline), ``pageable_boundary`` the cycle with a
 driver that keeps every array in pageable memory.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (``value``, ``ms_per_step`` and what the
+timed steps themselves counted); ``--dump-outputs DIR`` also writes what the last timed step returned.  Everything else --
+the device-resident, pageable and u = 1 legs, the SpMV roofline, PCIe rates, the self-check, configs 2 / 5 / 3, the
+scaling models and the CPU baselines -- runs only with ``--full``, where the ``--no-*`` switches select among them.
 """
 from __future__ import annotations
 
@@ -64,7 +69,32 @@ def parse():
     p.add_argument("--force-morton", action="store_true", help="with --reorder: renumber along the Morton curve regardless")
     p.add_argument("--pc", choices=("bpx", "jacobi"), default="bpx",
                    help="CG preconditioner: bpx = Jacobi + auxiliary-lattice multilevel correction (default)")
+    p.add_argument("--full", action="store_true",
+                   help="everything besides the headline: device-resident / pageable / u = 1 legs, SpMV roofline, PCIe rates, "
+                        "self-check, configs 2 / 5 / 3, scaling models and CPU baselines (the --no-* switches select among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (dJ/df, u, J) as DIR/<name>.npy in float64; arrays of more than "
+                        f"{DUMP_MAX_ENTRIES} entries as a fixed seeded sample of that many (N = 1 only)")
     return p.parse_args()
+
+
+DUMP_MAX_ENTRIES = 3_000_000       # per array: dJ/df and u at most 24 MB each in float64, 48 MB in all
+DUMP_SEED = 20240807
+
+
+def dump_outputs(directory: str, arrays: dict) -> dict:
+    """``DIR/<name>.npy`` (float64) for every array; one of more than DUMP_MAX_ENTRIES entries is replaced by its values at
+    ``np.unique(default_rng(DUMP_SEED).integers(0, size, DUMP_MAX_ENTRIES))`` -- the same sorted indices on every run of
+    the same size, so two builds can be compared entry for entry.  Returns {name: entries written}."""
+    os.makedirs(directory, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > DUMP_MAX_ENTRIES:
+            a = a[np.unique(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_MAX_ENTRIES))]
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+        out[name] = int(a.size)
+    return out
 
 
 def spmv_algorithmic_bytes(nnz: int, n: int) -> int:
@@ -632,14 +662,18 @@ def run_distributed_bench(args, ctx, control, cpu_baseline: bool = True):
     per = len(infos) // K if K else 0
     its_per_step = [i["iterations"] for i in infos[:per]]
     cg_ms = sum(i["solve_ms"] for i in infos) / max(K, 1)
-    A_mat = [w[1] for k, w in utils_hip._WORK.items() if k[1] == "newton_A" and w[0] is mesh][0].mat
-    xv = Vec(ctx, mesh.n_vert).set(np.random.default_rng(rank).standard_normal(mesh.n_vert))
-    yv = Vec(ctx, mesh.n_vert)
-    control.barrier()
-    spmv_ms = min(A_mat.bench_spmv(xv, yv, 50) for _ in range(3))      # local rows only, no halo: the kernel's own rate
+    full = bool(getattr(args, "full", False))                # the SpMV roofline, the self-check and the CPU baseline: --full
+    achieved = spmv_ms = float("nan")
+    if full:
+        A_mat = [w[1] for k, w in utils_hip._WORK.items() if k[1] == "newton_A" and w[0] is mesh][0].mat
+        xv = Vec(ctx, mesh.n_vert).set(np.random.default_rng(rank).standard_normal(mesh.n_vert))
+        yv = Vec(ctx, mesh.n_vert)
+        control.barrier()
+        spmv_ms = min(A_mat.bench_spmv(xv, yv, 50) for _ in range(3))      # local rows only, no halo: the kernel's own rate
     local_nnz = dm.info["nnz"]
     B_A = B.spmv_algorithmic_bytes(local_nnz, mesh.n_owned)
-    achieved = B_A / (spmv_ms * 1e-3) / 1e9
+    if full:
+        achieved = B_A / (spmv_ms * 1e-3) / 1e9
     L = mesh.local
     lat = dm.pc_info()
     hd = dm.halo_direct_info()
@@ -651,7 +685,7 @@ def run_distributed_bench(args, ctx, control, cpu_baseline: bool = True):
     # cycle of the WHOLE mesh (oracle/c_port.py::poisson_cycle_dst, no iterative solve), every rank compares the entries
     # it owns, the largest error over the ranks goes into the record.  Structured cube only.
     check = None
-    if not getattr(args, "no_check", False) and not getattr(args, "jitter", 0.0):
+    if full and not getattr(args, "no_check", False) and not getattr(args, "jitter", 0.0):
         kc = (W + K) % len(f_host)
         g_chk = np.array(E_host_wait(B.one_cycle(sim, fea, f_host[kc], u0)), copy=True)
         u_chk = np.array(sim['u'], copy=True)
@@ -701,7 +735,9 @@ def run_distributed_bench(args, ctx, control, cpu_baseline: bool = True):
             "non_cg_ms_per_step": ms_per_step - cg_ms,
             "setup_s_per_rank": [float(s[9]) for s in stats], "setup_rss_mb_per_rank": [float(s[8]) for s in stats],
         },
-        "roofline": {
+    }
+    if full:
+        result["roofline"] = {
             "bound": "hbm", "achieved": float(stats[0][7]) / (float(stats[0][6]) * 1e-3) / 1e9, "peak": B.HBM_PEAK_GBS, "unit": "GB/s",
             "frac": float(stats[0][7]) / (float(stats[0][6]) * 1e-3) / 1e9 / B.HBM_PEAK_GBS, "traffic": None,
             "achieved_algorithmic": float(stats[0][5]), "frac_algorithmic": float(stats[0][5]) / B.HBM_PEAK_GBS,
@@ -711,11 +747,10 @@ def run_distributed_bench(args, ctx, control, cpu_baseline: bool = True):
             "kernel": "k_spmv_sell<1,true> on rank 0's local rows (per GPU), 150 back-to-back launches",
             "algorithmic_bytes_per_launch": B_A, "avg_launch_ms": float(stats[0][6]), "launches_timed": 150,
             "achieved_per_rank": [float(s[5]) for s in stats],
-        },
-    }
+        }
     if check is not None:
         result["check"] = check
-    if cpu_baseline and not getattr(args, "no_cpu_baseline", False):
+    if full and cpu_baseline and not getattr(args, "no_cpu_baseline", False):
         counts = its_per_step if its_per_step else [0]
         n = args.n
         nnz = n_dof + 2 * (3 * n * (n + 1) ** 2 + 3 * n * n * (n + 1) + n ** 3)
@@ -1201,16 +1236,20 @@ def main():
         result = _run(args)
     if result is not None:
         # every check record of the line carries `passed`; one verdict for the line, and a failing check is said aloud
-        failed = []
+        # (a plain run checks nothing -- the checks are part of --full -- and claims no verdict)
+        failed, checked = [], []
 
         def walk(o, path):
             if isinstance(o, dict):
-                if "passed" in o and o["passed"] is False:
-                    failed.append(path)
+                if "passed" in o:
+                    checked.append(path)
+                    if o["passed"] is False:
+                        failed.append(path)
                 for k, v in o.items():
                     walk(v, f"{path}.{k}" if path else k)
         walk(result, "")
-        result["checks_passed"] = not failed
+        if args.full or checked:
+            result["checks_passed"] = not failed
         if failed:
             print(f"bench.py: CHECK FAILED in {failed}: the numbers of this line are not validated", file=sys.stderr, flush=True)
         print(json.dumps(result), flush=True)
@@ -1234,7 +1273,11 @@ def _run(args):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("bench: --dump-outputs writes the last timed step's outputs and needs --steps >= 1")
     if world > 1 or os.environ.get("FEMO_BENCH_FORCE_DIST", "0") not in ("", "0"):   # the env switch runs the N>1 code path on one rank (tests)
+        if args.dump_outputs:
+            raise SystemExit("bench: --dump-outputs is implemented for the N = 1 path only (each rank holds a share of the arrays)")
         return bench_distributed(args, rank, world, local_rank)
 
     from femo_amd import engine as E
@@ -1284,6 +1327,9 @@ def _run(args):
         raise SystemExit("bench: the host-boundary cycle must return a NumPy gradient")
     infos = list(utils_hip.LAST_KSP_INFO)
     xfer = E.host_stats()
+    if args.dump_outputs:
+        # what the caller of the last timed step holds: the gradient it returned, the state and the functional
+        dump_outputs(args.dump_outputs, {"dJ_df": E.host_wait(g), "u": sim['u'], "J": sim['l2_functional']})
 
     per = len(infos) // K if K else 0                      # linear solves per step: Newton's three + the adjoint
     its_per_step = [i["iterations"] for i in infos[:per]]
@@ -1293,8 +1339,45 @@ def _run(args):
     solves = [i for i in infos if i["spmv_samples"] > 0]
     spmv_in_cg_ms = (sum(i["spmv_ms"] for i in solves) / sum(i["spmv_samples"] for i in solves)) if solves else float("nan")
     n_in_cg = sum(i["spmv_samples"] for i in solves)
+    h2d_bytes = (xfer["h2d_pinned_bytes"] + xfer["h2d_staged_bytes"]) / max(K, 1)
+    d2h_bytes = (xfer["d2h_pinned_bytes"] + xfer["d2h_staged_bytes"] + xfer["d2h_async_bytes"]
+                 + xfer["d2h_device_sum_bytes"]) / max(K, 1)
 
-    # ---- the same cycle with inputs and outputs resident in HBM (no host boundary) ----------------
+    # ---- the headline record: everything in it comes from the timed steps ----------------------------
+    result = {
+        "metric": METRIC, "value": n_dof / (ms_per_step * 1e-3), "unit": "DOFs/s",
+        "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {
+            "workload": (f"3-D linear Poisson, P1 tets, unit cube n={args.n}: {n_dof} DOFs, {mesh.n_cell} cells, "
+                         f"nnz {nnz}; per step, NumPy arrays at the operator boundary (f in; u, J, dJ/df out): "
+                         f"Newton x3 (assemble R, dR/du, A; {PC.upper()}-CG) + J + dJ/du, dJ/df + "
+                         f"dR/du, dR/df, A + transposed {PC.upper()}-CG + dR/df^T lambda; "
+                         + ("CG stops on sqrt(r.M^-1 r) <= 1e-11 sqrt(b.M^-1 b) (energy-equivalent norm)" if PC == "bpx" else
+                            "CG stops on sqrt(r.D^-1 r) <= 1e-14 sqrt(b.D^-1 b)") + "; cold start"),
+            "boundary": "host (NumPy in pinned blocks of femo_host_alloc; H2D + D2H inside the timed region)",
+            "preconditioner": PC, "pc_lattice": dm.pc_info(),
+            "n": args.n, "jitter": args.jitter, "permuted": bool(args.permute), "reordered": bool(args.reorder),
+            "n_dof": n_dof, "n_cell": mesh.n_cell, "nnz": nnz,
+            "sell_slices": dm.info["n_slices"], "regular_slices": dm.info["regular_slices"], "short_slices": dm.info.get("short_slices", 0),
+            "linear_solves_per_step": per, "cg_iterations_per_step": its_per_step, "cg_ms_per_step": cg_ms,
+            "non_cg_ms_per_step": ms_per_step - cg_ms, "setup_s": setup_s,
+            # blocking waits of the host on the device inside the library per cycle (femo_host_sync_stats): each is an idle
+            # device for one host round trip (20-50 us) -- what the cycles of small meshes / of one rank of eight are made of
+            "host_syncs_per_step": host_syncs,
+            "pcie": {"h2d_bytes_per_step": h2d_bytes, "d2h_bytes_per_step": d2h_bytes,
+                     "d2h_async_bytes_per_step": xfer["d2h_async_bytes"] / max(K, 1),
+                     "d2h_device_sum_bytes_per_step": xfer["d2h_device_sum_bytes"] / max(K, 1),
+                     "uploads_elided_per_step": (xfer["h2d_skipped"] + xfer["h2d_as_d2d"]) / max(K, 1),
+                     "upload_bytes_elided_per_step": (xfer["h2d_skipped_bytes"] + xfer["h2d_as_d2d_bytes"]) / max(K, 1),
+                     "host_threads": E._lib.load().femo_host_threads()},
+        },
+    }
+    if not args.full:
+        return result
+
+    # ---- --full: the same cycle with inputs and outputs resident in HBM (no host boundary) ----------
     sim_d, fea_d = build_problem(mesh, device=True)
     f_dev = [DeviceArray(Vec(ctx, mesh.n_cell).set(f)) for f in f_pin]
     Kd = min(K, 5) if K else 0
@@ -1326,67 +1409,35 @@ def _run(args):
     t0 = time.perf_counter(); probe.get(out=out); t_dn = time.perf_counter() - t0
     del probe, out
     nbytes = mesh.n_cell * 8
-    h2d_bytes = (xfer["h2d_pinned_bytes"] + xfer["h2d_staged_bytes"]) / max(K, 1)
-    d2h_bytes = (xfer["d2h_pinned_bytes"] + xfer["d2h_staged_bytes"] + xfer["d2h_async_bytes"]
-                 + xfer["d2h_device_sum_bytes"]) / max(K, 1)
 
-    result = {
-        "metric": METRIC, "value": n_dof / (ms_per_step * 1e-3), "unit": "DOFs/s",
-        "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {
-            "workload": (f"3-D linear Poisson, P1 tets, unit cube n={args.n}: {n_dof} DOFs, {mesh.n_cell} cells, "
-                         f"nnz {nnz}; per step, NumPy arrays at the operator boundary (f in; u, J, dJ/df out): "
-                         f"Newton x3 (assemble R, dR/du, A; {PC.upper()}-CG) + J + dJ/du, dJ/df + "
-                         f"dR/du, dR/df, A + transposed {PC.upper()}-CG + dR/df^T lambda; "
-                         + ("CG stops on sqrt(r.M^-1 r) <= 1e-11 sqrt(b.M^-1 b) (energy-equivalent norm)" if PC == "bpx" else
-                            "CG stops on sqrt(r.D^-1 r) <= 1e-14 sqrt(b.D^-1 b)") + "; cold start"),
-            "boundary": "host (NumPy in pinned blocks of femo_host_alloc; H2D + D2H inside the timed region)",
-            "preconditioner": PC, "pc_lattice": dm.pc_info(),
-            "n": args.n, "jitter": args.jitter, "permuted": bool(args.permute), "reordered": bool(args.reorder),
-            "n_dof": n_dof, "n_cell": mesh.n_cell, "nnz": nnz,
-            "sell_slices": dm.info["n_slices"], "regular_slices": dm.info["regular_slices"], "short_slices": dm.info.get("short_slices", 0),
-            "linear_solves_per_step": per, "cg_iterations_per_step": its_per_step, "cg_ms_per_step": cg_ms,
-            "non_cg_ms_per_step": ms_per_step - cg_ms, "setup_s": setup_s,
-            # blocking waits of the host on the device inside the library per cycle (femo_host_sync_stats): each is an idle
-            # device for one host round trip (20-50 us) -- what the cycles of small meshes / of one rank of eight are made of
-            "host_syncs_per_step": host_syncs,
-            # SURVEY.md section 8(d) split: Newton's linear solves / the transposed (adjoint) solve /
-            # host<->device traffic and host-side passes / the rest (assembly, functional, dR/df^T lambda)
-            "split_ms_per_step": {"forward_solves": fwd_ms, "adjoint_solve": adj_ms,
-                                  "h2d_d2h": ms_per_step - dev_ms,       # the part of the transfers NOT hidden behind kernels
-                                  "assembly_outputs": dev_ms - cg_ms},
-            "pcie": {"h2d_bytes_per_step": h2d_bytes, "d2h_bytes_per_step": d2h_bytes,
-                     "d2h_async_bytes_per_step": xfer["d2h_async_bytes"] / max(K, 1),
-                     "d2h_device_sum_bytes_per_step": xfer["d2h_device_sum_bytes"] / max(K, 1),
-                     "uploads_elided_per_step": (xfer["h2d_skipped"] + xfer["h2d_as_d2d"]) / max(K, 1),
-                     "upload_bytes_elided_per_step": (xfer["h2d_skipped_bytes"] + xfer["h2d_as_d2d_bytes"]) / max(K, 1),
-                     "h2d_pinned_GBs": nbytes / t_up / 1e9, "d2h_pinned_GBs": nbytes / t_dn / 1e9,
-                     "h2d_pageable_staged_GBs": nbytes / t_pg / 1e9, "host_threads": E._lib.load().femo_host_threads()},
-        },
-        "device_resident": {"value": n_dof / (dev_ms * 1e-3) if dev_ms else None, "unit": "DOFs/s", "ms_per_step": dev_ms,
-                            "steps": Kd, "note": "same cycle with DeviceArray inputs/outputs (no PCIe); round 1's headline"},
-        "roofline": {
-            # round 6: `achieved` / `frac` are PHYSICAL -- the bytes the kernel really moves (PMC pass of
-            # this kernel at this size, else the stored format's bytes) over the launch time measured in this run; the SURVEY
-            # 8(d) CSR bytes over the same time are the CSR-equivalent rate `achieved_algorithmic` / `frac_algorithmic`
-            "bound": "hbm", "achieved": physical / (spmv_avg_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": physical / (spmv_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
-            "physical_bytes_per_launch": physical,
-            "physical_bytes_source": f"PMC (2*FETCH_SIZE + WRITE_SIZE, profiles/{pmc_file}, collected at commit {pmc_commit})" if traffic else "stored bytes of the SELL format",
-            "achieved_algorithmic": achieved, "frac_algorithmic": achieved / HBM_PEAK_GBS,
-            "format_compression": B_A / physical,
-            "frac_algorithmic_note": "CSR-equivalent rate: SURVEY.md 8(d) bytes (12 B per entry + 20 B per row) over the measured launch time; the regular-slice SELL format "
-                                     "fetches no column indices and stores no unit diagonal, so the kernel moves format_compression x fewer bytes than the formula counts",
-            "frac_physical": physical / (spmv_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "kernel": "k_spmv_sell<1,true> (SELL-64 SpMV + fused p.Ap, one launch per CG iteration)",
-            "algorithmic_bytes_per_launch": B_A, "avg_launch_ms": spmv_avg_ms, "launches_timed": n_in_cg,
-            "timed": "single launches inside the timed PCG loops (HIP events on the library's stream)",
-            "avg_launch_ms_back_to_back": spmv_loop_ms, "back_to_back_launches_timed": 150,
-            "stored_bytes_per_launch": stored,
-            "whole_cycle": whole_cycle_roofline(mesh.tdim, n_dof, mesh.n_cell, nnz, its_per_step, ms_per_step, dev_ms),
-        },
+    # SURVEY.md section 8(d) split: Newton's linear solves / the transposed (adjoint) solve /
+    # host<->device traffic and host-side passes / the rest (assembly, functional, dR/df^T lambda)
+    result["config"]["split_ms_per_step"] = {"forward_solves": fwd_ms, "adjoint_solve": adj_ms,
+                                             "h2d_d2h": ms_per_step - dev_ms,       # the part of the transfers NOT hidden behind kernels
+                                             "assembly_outputs": dev_ms - cg_ms}
+    result["config"]["pcie"].update({"h2d_pinned_GBs": nbytes / t_up / 1e9, "d2h_pinned_GBs": nbytes / t_dn / 1e9,
+                                     "h2d_pageable_staged_GBs": nbytes / t_pg / 1e9})
+    result["device_resident"] = {"value": n_dof / (dev_ms * 1e-3) if dev_ms else None, "unit": "DOFs/s", "ms_per_step": dev_ms,
+                                 "steps": Kd, "note": "same cycle with DeviceArray inputs/outputs (no PCIe); round 1's headline"}
+    result["roofline"] = {
+        # round 6: `achieved` / `frac` are PHYSICAL -- the bytes the kernel really moves (PMC pass of
+        # this kernel at this size, else the stored format's bytes) over the launch time measured in this run; the SURVEY
+        # 8(d) CSR bytes over the same time are the CSR-equivalent rate `achieved_algorithmic` / `frac_algorithmic`
+        "bound": "hbm", "achieved": physical / (spmv_avg_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": physical / (spmv_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
+        "physical_bytes_per_launch": physical,
+        "physical_bytes_source": f"PMC (2*FETCH_SIZE + WRITE_SIZE, profiles/{pmc_file}, collected at commit {pmc_commit})" if traffic else "stored bytes of the SELL format",
+        "achieved_algorithmic": achieved, "frac_algorithmic": achieved / HBM_PEAK_GBS,
+        "format_compression": B_A / physical,
+        "frac_algorithmic_note": "CSR-equivalent rate: SURVEY.md 8(d) bytes (12 B per entry + 20 B per row) over the measured launch time; the regular-slice SELL format "
+                                 "fetches no column indices and stores no unit diagonal, so the kernel moves format_compression x fewer bytes than the formula counts",
+        "frac_physical": physical / (spmv_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        "kernel": "k_spmv_sell<1,true> (SELL-64 SpMV + fused p.Ap, one launch per CG iteration)",
+        "algorithmic_bytes_per_launch": B_A, "avg_launch_ms": spmv_avg_ms, "launches_timed": n_in_cg,
+        "timed": "single launches inside the timed PCG loops (HIP events on the library's stream)",
+        "avg_launch_ms_back_to_back": spmv_loop_ms, "back_to_back_launches_timed": 150,
+        "stored_bytes_per_launch": stored,
+        "whole_cycle": whole_cycle_roofline(mesh.tdim, n_dof, mesh.n_cell, nnz, its_per_step, ms_per_step, dev_ms),
     }
     # What of the transfers the operator protocol leaves exposed whatever the library does: the gradient is the last thing a
     # cycle produces and must be on the host when the cycle ends (nothing is left to compute under its way down); f must be

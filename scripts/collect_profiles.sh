@@ -5,14 +5,14 @@
 set -u
 R=$(pwd); O=$R/$1; mkdir -p $O
 export TMPDIR=/tmp
-timeout 900 python bench.py --steps 20 --warmup 3 > $O/bench_n1.json 2> $O/bench_n1.err
-timeout 600 python bench.py --steps 5 --warmup 2 --permute --no-cpu-baseline > $O/bench_permuted.json 2> /dev/null
-timeout 600 python bench.py --steps 5 --warmup 2 --jitter 0.2 --no-cpu-baseline --no-pcie > $O/bench_jitter.json 2> /dev/null
-timeout 600 python bench.py --steps 10 --warmup 2 --mesh-n 100 --no-cpu-baseline --no-pcie > $O/bench_c2_n100.json 2> /dev/null
-timeout 600 python bench.py --steps 3 --warmup 1 --pc jacobi --no-cpu-baseline --no-pcie > $O/bench_pc_jacobi.json 2> /dev/null
-FEMO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_forced_dist_1rank.json 2> /dev/null
+timeout 900 python bench.py --full --steps 20 --warmup 3 > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 python bench.py --full --steps 5 --warmup 2 --permute --no-cpu-baseline > $O/bench_permuted.json 2> /dev/null
+timeout 600 python bench.py --full --steps 5 --warmup 2 --jitter 0.2 --no-cpu-baseline --no-pcie > $O/bench_jitter.json 2> /dev/null
+timeout 600 python bench.py --full --steps 10 --warmup 2 --mesh-n 100 --no-cpu-baseline --no-pcie > $O/bench_c2_n100.json 2> /dev/null
+timeout 600 python bench.py --full --steps 3 --warmup 1 --pc jacobi --no-cpu-baseline --no-pcie > $O/bench_pc_jacobi.json 2> /dev/null
+FEMO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_forced_dist_1rank.json 2> /dev/null
 timeout 300 python scripts/run_nonlinear_c5.py > $O/config5_nonlinear_n2236.json 2> /dev/null
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pcie > $O/bench_under_rocprof.json 2> /dev/null)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pcie > $O/bench_under_rocprof.json 2> /dev/null)
 python3 scripts/trace_summary.py $O/trace 5 k_spmv_sell 8 > $O/bench_kernel_stats.csv
 cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats_rocprofv3.csv 2>/dev/null
 rm -rf $O/trace

@@ -6,15 +6,15 @@
 set -u
 R=$(pwd); O=$R/$1; mkdir -p $O
 export TMPDIR=/tmp
-timeout 1200 python bench.py --steps 20 --warmup 3 > $O/bench_n1.json 2> $O/bench_n1.err
-timeout 600 python bench.py --steps 5 --warmup 2 --permute --no-cpu-baseline --no-configs > $O/bench_permuted.json 2> /dev/null
-timeout 600 python bench.py --steps 10 --warmup 2 --permute --reorder --no-cpu-baseline --no-configs --no-pcie > $O/bench_permuted_reordered.json 2> /dev/null
-timeout 600 python bench.py --steps 10 --warmup 2 --reorder --force-morton --no-cpu-baseline --no-configs --no-pcie > $O/bench_morton.json 2> /dev/null
-timeout 600 python bench.py --steps 10 --warmup 2 --jitter 0.2 --no-cpu-baseline --no-configs --no-pcie > $O/bench_jitter.json 2> /dev/null
-timeout 600 python bench.py --steps 3 --warmup 1 --pc jacobi --no-cpu-baseline --no-configs --no-pcie > $O/bench_pc_jacobi.json 2> /dev/null
-FEMO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-configs > $O/bench_forced_dist_1rank.json 2> /dev/null
+timeout 1200 python bench.py --full --steps 20 --warmup 3 > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 600 python bench.py --full --steps 5 --warmup 2 --permute --no-cpu-baseline --no-configs > $O/bench_permuted.json 2> /dev/null
+timeout 600 python bench.py --full --steps 10 --warmup 2 --permute --reorder --no-cpu-baseline --no-configs --no-pcie > $O/bench_permuted_reordered.json 2> /dev/null
+timeout 600 python bench.py --full --steps 10 --warmup 2 --reorder --force-morton --no-cpu-baseline --no-configs --no-pcie > $O/bench_morton.json 2> /dev/null
+timeout 600 python bench.py --full --steps 10 --warmup 2 --jitter 0.2 --no-cpu-baseline --no-configs --no-pcie > $O/bench_jitter.json 2> /dev/null
+timeout 600 python bench.py --full --steps 3 --warmup 1 --pc jacobi --no-cpu-baseline --no-configs --no-pcie > $O/bench_pc_jacobi.json 2> /dev/null
+FEMO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-configs > $O/bench_forced_dist_1rank.json 2> /dev/null
 # kernel traces: the bench command itself (headline leg only: the trace of the other meshes would drown it), C3, C5
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pcie --no-configs > $O/bench_under_rocprof.json 2> /dev/null)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pcie --no-configs > $O/bench_under_rocprof.json 2> /dev/null)
 python3 scripts/trace_summary.py $O/trace 5 k_spmv_sell 8 > $O/bench_kernel_stats.csv
 python3 scripts/trace_gaps.py $O/trace 200 > $O/bench_trace_gaps.txt 2>&1
 cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats_rocprofv3.csv 2>/dev/null

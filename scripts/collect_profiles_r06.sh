@@ -6,17 +6,17 @@
 set -u
 R=$(pwd); O=$R/$1; mkdir -p $O
 export TMPDIR=/tmp
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_cmd.json 2> $O/bench_n1.err
-timeout 300 python bench.py --mesh-n 100 --steps 20 --warmup 3 --no-cpu-baseline --no-configs > $O/bench_c2_n100.json 2> /dev/null
-timeout 600 python bench.py --steps 10 --warmup 2 --jitter 0.2 --no-cpu-baseline --no-configs --no-pcie > $O/bench_jitter.json 2> /dev/null
-FEMO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-configs > $O/bench_forced_dist_1rank.json 2> /dev/null
+timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_cmd.json 2> $O/bench_n1.err
+timeout 300 python bench.py --full --mesh-n 100 --steps 20 --warmup 3 --no-cpu-baseline --no-configs > $O/bench_c2_n100.json 2> /dev/null
+timeout 600 python bench.py --full --steps 10 --warmup 2 --jitter 0.2 --no-cpu-baseline --no-configs --no-pcie > $O/bench_jitter.json 2> /dev/null
+FEMO_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-configs > $O/bench_forced_dist_1rank.json 2> /dev/null
 timeout 900 python scripts/run_emulated_ranks_bench.py 215 8 > $O/emulated_8ranks_n215.json 2> /dev/null
 # kernel traces
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pcie --no-configs > $O/bench_under_rocprof.json 2> /dev/null)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pcie --no-configs > $O/bench_under_rocprof.json 2> /dev/null)
 python3 scripts/trace_summary.py $O/trace 5 k_spmv_sell 7 > $O/bench_kernel_stats.csv
 cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats_rocprofv3.csv 2>/dev/null
 rm -rf $O/trace
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/trace2 -- python3 $R/bench.py --mesh-n 100 --steps 10 --warmup 2 --no-cpu-baseline --no-pcie --no-configs --no-check > /dev/null 2> /dev/null)
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/trace2 -- python3 $R/bench.py --full --mesh-n 100 --steps 10 --warmup 2 --no-cpu-baseline --no-pcie --no-configs --no-check > /dev/null 2> /dev/null)
 python3 scripts/trace_summary.py $O/trace2 3 k_spmv_sell 7 > $O/c2_kernel_stats.csv
 python3 scripts/trace_timeline.py $O/trace2 k_load_walk 8 collapse > $O/c2_cycle_timeline.txt 2>&1
 rm -rf $O/trace2
@@ -30,7 +30,7 @@ python3 scripts/trace_timeline.py $O/trace_sm2 k_load_walk 3 > $O/scaling_model_
 rm -rf $O/trace_sm2
 timeout 300 python scripts/run_scaling_model.py 215 6 --model-only > $O/scaling_model_direct.json 2> /dev/null
 FEMO_HALO_RCCL=1 timeout 300 python scripts/run_scaling_model.py 215 6 --model-only > $O/scaling_model_rccl.json 2> /dev/null
-timeout 600 python bench.py --permute --reorder --steps 10 --warmup 3 --no-cpu-baseline --no-configs --no-pcie > $O/bench_permuted_reordered.json 2> /dev/null
+timeout 600 python bench.py --full --permute --reorder --steps 10 --warmup 3 --no-cpu-baseline --no-configs --no-pcie > $O/bench_permuted_reordered.json 2> /dev/null
 ./scripts/probe_cellcentric/skeleton 215 > $O/cellcentric_skeleton_n215.txt 2>&1
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace3 -- python3 $R/scripts/run_shell_c3.py 362 > $O/config3_shell_roof_n362.json 2> /dev/null)
 python3 scripts/trace_summary.py $O/trace3 5 k_bsell_spmv 12 > $O/config3_shell_kernel_stats.csv

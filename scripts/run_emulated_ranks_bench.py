@@ -18,7 +18,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 215
 world = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 group = EmuGroup(world)
 shared = ThreadControl.Shared(world)
-args = Namespace(n=n, steps=2, warmup=1, pc="bpx", jitter=0.0, cpu_n=0, no_cpu_baseline=True)
+args = Namespace(n=n, steps=2, warmup=1, pc="bpx", jitter=0.0, cpu_n=0, no_cpu_baseline=True, full=True)
 out, err = [None] * world, [None] * world
 
 

@@ -134,3 +134,35 @@ def test_self_check_maps_renumbered_meshes_back():
     ref0 = fo.reference_cycle(fo.OMesh(3, canon.x, canon.conn, n), f0, fo.u_target(canon.x), fo.boundary_vertices_box(canon.x), np.zeros(len(bd)))
     chk0 = bench.self_check(a, canon, f0, ref0["u"], ref0["J"][0], ref0["grad"])
     assert max(chk0["u_rel_err"], chk0["grad_rel_err"], chk0["J_rel_err"]) < 1e-12
+
+
+def test_plain_run_options_and_output_dump(tmp_path, monkeypatch):
+    """`--full` is off by default; `--dump-outputs` writes float64 .npy files, a large array as a fixed seeded sample that is the
+    same on every run and keeps the whole dump under 64 MB."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+
+    big = np.arange(59_630_250, dtype=np.float64) * 0.5            # dJ/df at n = 215: one entry per cell
+    mid = np.linspace(0.0, 1.0, 10_077_696)                         # u at n = 215
+    small = np.arange(2197.0)
+    sizes = bench.dump_outputs(str(tmp_path / "a"), {"dJ_df": big, "u": mid, "J": np.array([1.25]), "s": small})
+    bench.dump_outputs(str(tmp_path / "b"), {"dJ_df": big, "u": mid})
+    total = 0
+    for name in ("dJ_df", "u", "J", "s"):
+        x = np.load(tmp_path / "a" / f"{name}.npy")
+        assert x.dtype == np.float64 and x.ndim == 1 and x.size == sizes[name]
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert total <= 64 * 2 ** 20
+    assert np.array_equal(np.load(tmp_path / "a" / "s.npy"), small) and np.load(tmp_path / "a" / "J.npy").tolist() == [1.25]
+    for name, full in (("dJ_df", big), ("u", mid)):
+        x = np.load(tmp_path / "a" / f"{name}.npy")
+        assert 0.8 * bench.DUMP_MAX_ENTRIES < x.size <= bench.DUMP_MAX_ENTRIES
+        assert np.all(np.diff(x) > 0) and np.isin(x, full).all()      # distinct entries of the array, in index order
+        assert np.array_equal(x, np.load(tmp_path / "b" / f"{name}.npy"))

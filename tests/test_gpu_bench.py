@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(*flags):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags], capture_output=True, text=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *flags], capture_output=True, text=True,
                        timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -52,3 +52,44 @@ def test_bench_permuted_numbering():
     r = _bench("--mesh-n", "10", "--steps", "2", "--warmup", "1", "--permute", "--no-cpu-baseline", "--no-pcie")
     assert r["config"]["permuted"] is True and r["config"]["regular_slices"] == 0
     assert r["config"]["linear_solves_per_step"] == 4
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline and what the timed steps counted, nothing of the other legs; --dump-outputs
+    writes what the last timed step returned, which is the DST-exact cycle of that step's source to round-off, and the same
+    arrays to round-off on a second run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import c_port
+    from oracle import femo_oracle as fo
+    n, K, W = 12, 3, 1
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--mesh-n", str(n), "--steps", str(K),
+                            "--warmup", str(W), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-4000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout
+        r = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in r
+        assert r["steps"] == K and r["warmup"] == W and r["ms_per_step"] > 0 and r["higher_is_better"] is True
+        assert abs(r["value"] - r["config"]["n_dof"] / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+        assert r["config"]["linear_solves_per_step"] == 4
+        for key in ("device_resident", "roofline", "pageable_boundary", "csdl_default_start", "check", "configs", "cpu_baseline",
+                    "checks_passed"):
+            assert key not in r
+        runs.append({name: np.load(d / f"{name}.npy") for name in ("dJ_df", "u", "J")})
+    out = runs[0]
+    assert out["dJ_df"].dtype == np.float64 and out["dJ_df"].size == 6 * n ** 3
+    assert out["u"].size == (n + 1) ** 3 and out["J"].size == 1
+    for name in out:                  # same inputs; the device reductions may round differently from run to run
+        assert np.abs(out[name] - runs[1][name]).max() <= 1e-10 * np.abs(runs[1][name]).max()
+    m = fo.unit_cube_mesh(n)
+    f = bench.source_fields(bench._Centroid(m), min(K + W, 4))[(W + K - 1) % min(K + W, 4)]
+    ref = c_port.poisson_cycle_dst(n, 3, m.x, m.conn, f, fo.u_target(m.x), fo.boundary_vertices_box(m.x), bench.ALPHA)
+    assert np.abs(out["u"] - ref["u"]).max() < 1e-10 * np.abs(ref["u"]).max()
+    assert np.abs(out["dJ_df"] - ref["grad"]).max() < 1e-10 * np.abs(ref["grad"]).max()
+    assert abs(out["J"][0] - float(ref["J"])) < 1e-10 * abs(float(ref["J"]))

@@ -469,7 +469,7 @@ def test_distributed_bench_record_on_eight_emulated_ranks():
     world, n = 8, 48
     group = EmuGroup(world)
     shared = ThreadControl.Shared(world)
-    args = Namespace(n=n, steps=2, warmup=1, pc="bpx", jitter=0.0, cpu_n=0, no_cpu_baseline=True)
+    args = Namespace(n=n, steps=2, warmup=1, pc="bpx", jitter=0.0, cpu_n=0, no_cpu_baseline=True, full=True)
     out, err = [None] * world, [None] * world
 
     def body(rank):

@@ -27,7 +27,7 @@ def test_two_rank_bench_over_rccl(halo):
         env["FEMO_HALO_RCCL"] = "1"
     # n = 48: the smallest cube whose lattice has the four levels the merged loop (one all-reduce per iteration) needs
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--mesh-n", "48", "--steps", "3",
-                        "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--warmup", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -59,7 +59,7 @@ def test_rank_ladder_bench_over_rccl(world):
         pytest.skip(f"needs {world} GPUs")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--mesh-n", "64", "--steps", "3",
-                        "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
+                        "--warmup", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, p.stdout
