@@ -29,6 +29,9 @@ PDE_NL_POISSON = 1
 PDE_MASS = 2
 PDE_EB_BEAM = 3
 J_L2_TRACKING = 0
+ELAST_SIMP = 0
+ELAST_RAMP = 1
+ELAST_INFO_KEYS = ("dim", "n_dof", "nnz", "sell_entries", "spmv_bytes")
 
 
 class SolverOpts(C.Structure):
@@ -187,6 +190,24 @@ PROTOTYPES = {
     "femo_mesh_halo_direct_enable": (C.c_int, [H, C.c_int]),
     "femo_mesh_halo_direct_info": (C.c_int, [H, C.POINTER(C.c_int64)]),
     "femo_allreduce_sum": (C.c_int, [H, c_f64p, C.c_int]),
+    # SIMP topology optimisation: vector CG1 elasticity and the DG0 density filter
+    "femo_elast_create": (C.c_int, [H, C.c_double, C.c_double, C.POINTER(H)]),
+    "femo_elast_destroy": (C.c_int, [H]),
+    "femo_elast_info": (C.c_int, [H, c_i64p]),
+    "femo_elast_set_fixed": (C.c_int, [H, C.c_void_p]),
+    "femo_elast_set_facets": (C.c_int, [H, c_i64, C.c_void_p]),
+    "femo_elast_assemble": (C.c_int, [H, C.c_int, H]),
+    "femo_elast_apply": (C.c_int, [H, C.c_int, C.c_double, H, C.c_double, H, H]),
+    "femo_elast_load": (C.c_int, [H, c_f64p, H]),
+    "femo_elast_drho": (C.c_int, [H, C.c_int, C.c_int, H, H, H, H, C.c_int]),
+    "femo_elast_solve": (C.c_int, [H, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
+    "femo_elast_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "femo_elast_bench_spmv": (C.c_int, [H, H, H, C.c_int, c_f64p]),
+    "femo_filter_create": (C.c_int, [H, C.c_int, c_i64, C.c_void_p, C.c_double, C.POINTER(H)]),
+    "femo_filter_destroy": (C.c_int, [H]),
+    "femo_filter_nnz": (C.c_int, [H, c_i64p]),
+    "femo_filter_apply": (C.c_int, [H, C.c_int, H, H]),
+    "femo_filter_export_csr": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -66,6 +66,7 @@ except Exception:  # ModuleNotFoundError in this image
             self.submodels: List[Tuple[str, "Model"]] = []
             self.operations: List[Any] = []
             self.design_variables: Dict[str, dict] = {}
+            self.constraints: Dict[str, dict] = {}
             self.objective: Optional[dict] = None
             self._defined = False
 
@@ -95,6 +96,9 @@ except Exception:  # ModuleNotFoundError in this image
 
         def add_design_variable(self, name, lower=None, upper=None, scaler=None):
             self.design_variables[name] = dict(lower=lower, upper=upper, scaler=scaler)
+
+        def add_constraint(self, name, lower=None, upper=None, equals=None, scaler=None):
+            self.constraints[name] = dict(lower=lower, upper=upper, equals=equals, scaler=scaler)
 
         def add_objective(self, name, scaler=1.0):
             self.objective = dict(name=name, scaler=scaler)

@@ -206,6 +206,10 @@ class Simulator:
                 inputs = {k: self.values[k] for k in op.input_meta}
                 if isinstance(op, CustomExplicitOperation):
                     if o not in op.output_meta:
+                        # an explicit op between the design variables and the state (a filter): adj[in] += J^T adj[out]
+                        outs = [k for k in op.output_meta if k in adj]
+                        if outs and hasattr(op, "compute_jacvec_product"):
+                            self._explicit_rev(op, inputs, outs, adj)
                         continue
                     derivatives = {}
                     op.compute_derivatives(inputs, derivatives)
@@ -287,6 +291,24 @@ class Simulator:
         if single:
             return result[(self._key(of), self._key(wrt))]
         return result
+
+    def _explicit_rev(self, op, inputs, outs, adj) -> None:
+        """d_inputs = J^T d_outputs of an explicit operation (compute_jacvec_product 'rev'), added to the inputs' adjoints."""
+        d_outputs = {k: adj[k] for k in outs}
+        d_inputs = {k: self._zeros_like(k, 'jvp_in') for k in op.input_meta}
+        op.compute_jacvec_product(inputs, d_inputs, d_outputs, 'rev')
+        for k, v in d_inputs.items():
+            if isinstance(v, DeviceArray):
+                if k not in adj:
+                    adj[k] = self._zeros_like(k, 'adj')
+                adj[k] += v
+            else:
+                v = np.ascontiguousarray(E.host_wait(v), dtype=np.float64).ravel()
+                if k not in adj:
+                    adj[k] = v
+                else:
+                    adj[k] = self._own(adj[k])
+                    E.host_axpby(1.0, v, 1.0, adj[k])
 
     def check_totals(self, of: str, wrt: str, step: float = 1e-6, n_dir: int = 3, seed: int = 0) -> dict:
         """Directional central finite differences vs the adjoint total (the idiom of

@@ -1,0 +1,1107 @@
+// SIMP topology optimisation: vector CG1 linear elasticity with a DG0 density, and the DG0 density filter
+// (examples/beam_topo_opt; C-ABI in include/femo_hip.h, "SIMP topology optimisation").
+//
+// Layout.  The state has d = tdim dofs per vertex (dof = d * vertex + component).  K(rho) lives on the mesh's SCALAR SELL
+// pattern: SELL entry e holds one d x d block at vals[e * d^2 + r * d + c] (r: row component, c: column component), the
+// diagonal blocks at diag[v * d^2 + ...].  Per block one 4-byte column index serves 8 d^2 bytes of values.
+//
+// Assembly walks the vertex -> cell incidence like assemble.hip: the thread of row v visits the cells around v and adds
+// C(rho_c) |T_c| B_v^T D_0 B_w to its blocks (v, w).  No float atomics: every block has one writer, the visits come in
+// ascending cell order, and the cell geometry is formed from `conn` in its own vertex order, so block (v, w) and block
+// (w, v)^T are sums of the same numbers in the same order -- K is symmetric entry for entry.
+#include "femo_internal.h"
+
+#include <algorithm>
+#include <cmath>
+
+struct femo_elast {
+  femo_mesh* mesh = nullptr;
+  int d = 0;
+  double lam0 = 0.0, mu0 = 0.0;
+  double* d_vals = nullptr;     // sell_entries * d^2
+  double* d_diag = nullptr;     // n_rows * d^2
+  double* d_dinv = nullptr;     // n_rows * d^2: inverse of the (masked) diagonal blocks
+  uint8_t* d_fixed = nullptr;   // n_dof, optional
+  bool has_fixed = false;
+  bool assembled = false;
+  // tagged facets: vertex -> facet CSR (vertex ids of the facets, d per facet)
+  int64_t n_facets = 0;
+  int32_t* d_fverts = nullptr;
+  int64_t* d_fptr = nullptr;    // n_vert + 1
+  int32_t* d_flist = nullptr;
+  // PCG work
+  double *w_r = nullptr, *w_z = nullptr, *w_p = nullptr, *w_q = nullptr, *w_part = nullptr, *w_s = nullptr;
+  int32_t* w_flag = nullptr;
+  int32_t* h_flag = nullptr;    // pinned
+  double* h_s = nullptr;        // pinned
+};
+
+struct femo_filter {
+  femo_ctx* ctx = nullptr;
+  int64_t n = 0, nnz = 0;
+  int64_t* d_rowptr = nullptr;
+  int32_t* d_col = nullptr;
+  double* d_val = nullptr;      // W
+  double* d_valT = nullptr;     // W^T on the same (symmetric) pattern
+};
+
+namespace {
+
+constexpr int EB = 256;              // threads per block of the row kernels
+constexpr int PCG_GRID = 512;        // blocks of the PCG reductions (one partial each)
+
+inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
+  int64_t g = (n + EB - 1) / EB;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (unsigned)g;
+}
+
+// gradients of the barycentric coordinates and the volume of a P1 simplex, from the vertices in `conn` order
+template <int D>
+__device__ __forceinline__ void simplex_grads(const double (&p)[D + 1][D], double (&g)[D + 1][D], double& vol) {
+  double m[D][D];          // m[k][i] = p[k+1][i] - p[0][i]
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+#pragma unroll
+    for (int i = 0; i < D; ++i) m[k][i] = p[k + 1][i] - p[0][i];
+  // grad lambda_{k+1} = column k of m^-1
+  if constexpr (D == 2) {
+    const double det = m[0][0] * m[1][1] - m[0][1] * m[1][0];
+    const double id = 1.0 / det;
+    g[1][0] = m[1][1] * id;  g[1][1] = -m[1][0] * id;
+    g[2][0] = -m[0][1] * id; g[2][1] = m[0][0] * id;
+    vol = 0.5 * fabs(det);
+  } else {
+    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1];
+    const double c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2];
+    const double c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+    const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
+    const double id = 1.0 / det;
+    // inverse (adjugate / det): inv[i][k]
+    double inv[3][3];
+    inv[0][0] = c00 * id;
+    inv[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id;
+    inv[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id;
+    inv[1][0] = c01 * id;
+    inv[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id;
+    inv[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id;
+    inv[2][0] = c02 * id;
+    inv[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id;
+    inv[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) g[k + 1][i] = inv[i][k];
+    vol = fabs(det) * (1.0 / 6.0);
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 1; k <= D; ++k) s += g[k][i];
+    g[0][i] = -s;
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void load_cell(const int32_t* __restrict__ conn, const double* __restrict__ x, int64_t c,
+                                          int32_t (&v)[D + 1], double (&p)[D + 1][D]) {
+#pragma unroll
+  for (int b = 0; b <= D; ++b) {
+    v[b] = conn[c * (D + 1) + b];
+#pragma unroll
+    for (int i = 0; i < D; ++i) p[b][i] = x[(int64_t)v[b] * D + i];
+  }
+}
+
+__device__ __forceinline__ double penal(int method, double r) {
+  return method == FEMO_ELAST_SIMP ? r * r * r : r / (1.0 + 8.0 * (1.0 - r));
+}
+__device__ __forceinline__ double penal_d(int method, double r) {
+  if (method == FEMO_ELAST_SIMP) return 3.0 * r * r;
+  const double q = 1.0 + 8.0 * (1.0 - r);
+  return 9.0 / (q * q);
+}
+
+// block (a, b) of the element matrix without the factor C |T|; written symmetrically in (a, r) <-> (b, c)
+template <int D>
+__device__ __forceinline__ double kblock(const double (&g)[D + 1][D], int a, int b, int r, int c, double lam, double mu,
+                                         double gab) {
+  double t = lam * (g[a][r] * g[b][c]) + mu * (g[a][c] * g[b][r]);
+  if (r == c) t += mu * gab;
+  return t;
+}
+
+template <int D>
+__device__ __forceinline__ double dotg(const double (&g)[D + 1][D], int a, int b) {
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) s += g[a][k] * g[b][k];
+  return s;
+}
+
+// in-register inverse of a small SPD block (fixed components: identity row / column)
+template <int D>
+__device__ __forceinline__ void block_inverse(double (&B)[D * D], double (&Bi)[D * D]) {
+  if constexpr (D == 2) {
+    const double det = B[0] * B[3] - B[1] * B[2];
+    const double id = 1.0 / det;
+    Bi[0] = B[3] * id; Bi[1] = -B[1] * id; Bi[2] = -B[2] * id; Bi[3] = B[0] * id;
+  } else {
+    const double c00 = B[4] * B[8] - B[5] * B[7];
+    const double c01 = B[5] * B[6] - B[3] * B[8];
+    const double c02 = B[3] * B[7] - B[4] * B[6];
+    const double det = B[0] * c00 + B[1] * c01 + B[2] * c02;
+    const double id = 1.0 / det;
+    Bi[0] = c00 * id;
+    Bi[1] = (B[2] * B[7] - B[1] * B[8]) * id;
+    Bi[2] = (B[1] * B[5] - B[2] * B[4]) * id;
+    Bi[3] = c01 * id;
+    Bi[4] = (B[0] * B[8] - B[2] * B[6]) * id;
+    Bi[5] = (B[2] * B[3] - B[0] * B[5]) * id;
+    Bi[6] = c02 * id;
+    Bi[7] = (B[1] * B[6] - B[0] * B[7]) * id;
+    Bi[8] = (B[0] * B[4] - B[1] * B[3]) * id;
+  }
+}
+
+__device__ __forceinline__ int slot_pos(uint32_t slots, int a, int b) {
+  const int j = b - (b > a ? 1 : 0);
+  return (int)((slots >> (8 * j)) & 0xFFu);
+}
+
+// ----------------------------------------------------------------------------------------------- assembly ----
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_assemble(
+    int64_t n_rows, const int64_t* __restrict__ vptr, const int32_t* __restrict__ visit_cell,
+    const uint32_t* __restrict__ visit_slots, const int64_t* __restrict__ mptr, const int32_t* __restrict__ rowlen,
+    const int32_t* __restrict__ conn, const double* __restrict__ x, const double* __restrict__ rho, int method,
+    double lam, double mu, const uint8_t* __restrict__ fixed, double* __restrict__ vals, double* __restrict__ diag,
+    double* __restrict__ dinv) {
+  constexpr int DD = D * D;
+  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (row >= n_rows) return;
+  const int64_t slice = row >> 6;
+  const int lane = (int)(row & 63);
+  const int64_t mb = mptr[slice];
+  const int len = rowlen[row];
+  for (int k = 0; k < len; ++k) {
+    const int64_t e = femo_sell_index(mb, k, lane);
+#pragma unroll
+    for (int q = 0; q < DD; ++q) vals[e * DD + q] = 0.0;
+  }
+  double dg[DD];
+#pragma unroll
+  for (int q = 0; q < DD; ++q) dg[q] = 0.0;
+  const int64_t vb = vptr[slice];
+  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
+  for (int s = 0; s < nvis; ++s) {
+    const int64_t vi = vb + (int64_t)s * 64 + lane;
+    const int32_t ca = visit_cell[vi];
+    if (ca < 0) continue;
+    const uint32_t sl = visit_slots[vi];
+    const int64_t c = ca >> 2;
+    const int a = ca & 3;
+    int32_t v[D + 1];
+    double p[D + 1][D], g[D + 1][D], vol;
+    load_cell<D>(conn, x, c, v, p);
+    simplex_grads<D>(p, g, vol);
+    const double coef = penal(method, rho[c]) * vol;
+#pragma unroll
+    for (int b = 0; b <= D; ++b) {
+      const double gab = dotg<D>(g, a, b);
+      if (b == a) {
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+          for (int cc = 0; cc < D; ++cc) dg[r * D + cc] += coef * kblock<D>(g, a, b, r, cc, lam, mu, gab);
+      } else {
+        const int64_t e = femo_sell_index(mb, slot_pos(sl, a, b), lane);
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+          for (int cc = 0; cc < D; ++cc) vals[e * DD + r * D + cc] += coef * kblock<D>(g, a, b, r, cc, lam, mu, gab);
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < DD; ++q) diag[row * DD + q] = dg[q];
+  // block-Jacobi: inverse of the diagonal block, fixed components as identity rows / columns
+  double B[DD], Bi[DD];
+#pragma unroll
+  for (int r = 0; r < D; ++r)
+#pragma unroll
+    for (int cc = 0; cc < D; ++cc) {
+      const bool fr = fixed && fixed[row * D + r], fc = fixed && fixed[row * D + cc];
+      B[r * D + cc] = (fr || fc) ? (r == cc ? 1.0 : 0.0) : dg[r * D + cc];
+    }
+  block_inverse<D>(B, Bi);
+#pragma unroll
+  for (int q = 0; q < DD; ++q) dinv[row * DD + q] = Bi[q];
+}
+
+// y = a Op x + b f (+ partial dot(x, y) per block when part != null).  MASKED: identity rows / columns on fixed dofs.
+template <int D, bool MASKED>
+__global__ __launch_bounds__(EB) void k_elast_spmv(
+    int64_t n_rows, const int64_t* __restrict__ mptr, const int32_t* __restrict__ cols, const int32_t* __restrict__ rowlen,
+    const double* __restrict__ vals, const double* __restrict__ diag, const uint8_t* __restrict__ fixed,
+    double a, const double* __restrict__ x, double b, const double* __restrict__ f, double* __restrict__ y,
+    double* __restrict__ part, const int32_t* __restrict__ done) {
+  constexpr int DD = D * D;
+  __shared__ double lds[EB / 64];
+  if (done && *done) return;
+  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
+  double dotv = 0.0;
+  if (row < n_rows) {
+    const int64_t slice = row >> 6;
+    const int lane = (int)(row & 63);
+    const int64_t mb = mptr[slice];
+    const int len = rowlen[row];
+    double acc[D], xo[D];
+    uint8_t fo[D];
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      xo[r] = x[row * D + r];
+      fo[r] = MASKED ? fixed[row * D + r] : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      double s = 0.0;
+#pragma unroll
+      for (int cc = 0; cc < D; ++cc) s += diag[row * DD + r * D + cc] * (fo[cc] ? 0.0 : xo[cc]);
+      acc[r] = s;
+    }
+    for (int k = 0; k < len; ++k) {
+      const int64_t e = femo_sell_index(mb, k, lane);
+      const int64_t col = cols[e];
+      double xc[D];
+#pragma unroll
+      for (int cc = 0; cc < D; ++cc) {
+        xc[cc] = x[col * D + cc];
+        if (MASKED && fixed[col * D + cc]) xc[cc] = 0.0;
+      }
+#pragma unroll
+      for (int r = 0; r < D; ++r)
+#pragma unroll
+        for (int cc = 0; cc < D; ++cc) acc[r] += vals[e * DD + r * D + cc] * xc[cc];
+    }
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      double o = MASKED && fo[r] ? xo[r] : acc[r];
+      o = a * o;
+      if (f) o += b * f[row * D + r];
+      y[row * D + r] = o;
+      dotv += xo[r] * o;
+    }
+  }
+  if (part) {
+    const double s = femo_block_sum<EB>(dotv, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- dR/drho ----
+// rev: y_c (+)= C'(rho_c) |T| (lam div w div u + 2 mu eps(w) : eps(u)) = C'(rho_c) w_c^T K0_c u_c
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_drho_T(int64_t n_cell, const int32_t* __restrict__ conn,
+                                                     const double* __restrict__ xv, const double* __restrict__ rho, int method,
+                                                     double lam, double mu, const double* __restrict__ u,
+                                                     const double* __restrict__ w, double* __restrict__ y, int accumulate) {
+  const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (c >= n_cell) return;
+  int32_t v[D + 1];
+  double p[D + 1][D], g[D + 1][D], vol;
+  load_cell<D>(conn, xv, c, v, p);
+  simplex_grads<D>(p, g, vol);
+  double Gu[D][D], Gw[D][D];      // G[i][k] = d(field_i)/dx_k
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) { Gu[i][k] = 0.0; Gw[i][k] = 0.0; }
+#pragma unroll
+  for (int b = 0; b <= D; ++b)
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const double ub = u[(int64_t)v[b] * D + i], wb = w[(int64_t)v[b] * D + i];
+#pragma unroll
+      for (int k = 0; k < D; ++k) { Gu[i][k] += ub * g[b][k]; Gw[i][k] += wb * g[b][k]; }
+    }
+  double divu = 0.0, divw = 0.0, ee = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) { divu += Gu[i][i]; divw += Gw[i][i]; }
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) ee += 0.25 * (Gu[i][k] + Gu[k][i]) * (Gw[i][k] + Gw[k][i]);
+  const double val = penal_d(method, rho[c]) * vol * (lam * divu * divw + 2.0 * mu * ee);
+  y[c] = accumulate ? y[c] + val : val;
+}
+
+// fwd: y_v (+)= sum over the cells c around v of C'(rho_c) dr_c |T| sigma_0(u_c) grad(phi_v)
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_drho_N(
+    int64_t n_rows, const int64_t* __restrict__ vptr, const int32_t* __restrict__ visit_cell, const int32_t* __restrict__ conn,
+    const double* __restrict__ xv, const double* __restrict__ rho, int method, double lam, double mu,
+    const double* __restrict__ u, const double* __restrict__ dr, double* __restrict__ y, int accumulate) {
+  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (row >= n_rows) return;
+  const int64_t slice = row >> 6;
+  const int lane = (int)(row & 63);
+  const int64_t vb = vptr[slice];
+  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
+  double acc[D];
+#pragma unroll
+  for (int r = 0; r < D; ++r) acc[r] = 0.0;
+  for (int s = 0; s < nvis; ++s) {
+    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
+    if (ca < 0) continue;
+    const int64_t c = ca >> 2;
+    const int a = ca & 3;
+    int32_t v[D + 1];
+    double p[D + 1][D], g[D + 1][D], vol;
+    load_cell<D>(conn, xv, c, v, p);
+    simplex_grads<D>(p, g, vol);
+    double Gu[D][D];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int k = 0; k < D; ++k) Gu[i][k] = 0.0;
+#pragma unroll
+    for (int b = 0; b <= D; ++b)
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        const double ub = u[(int64_t)v[b] * D + i];
+#pragma unroll
+        for (int k = 0; k < D; ++k) Gu[i][k] += ub * g[b][k];
+      }
+    double divu = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) divu += Gu[i][i];
+    const double coef = penal_d(method, rho[c]) * dr[c] * vol;
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      double sg = lam * divu * g[a][r];
+#pragma unroll
+      for (int k = 0; k < D; ++k) sg += mu * (Gu[r][k] + Gu[k][r]) * g[a][k];
+      acc[r] += coef * sg;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < D; ++r) y[row * D + r] = accumulate ? y[row * D + r] + acc[r] : acc[r];
+}
+
+// ------------------------------------------------------------------------------------------- traction ----
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_load(int64_t n_vert, const int64_t* __restrict__ fptr,
+                                                   const int32_t* __restrict__ flist, const int32_t* __restrict__ fverts,
+                                                   const double* __restrict__ x, double t0, double t1, double t2,
+                                                   double* __restrict__ F) {
+  const int64_t v = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (v >= n_vert) return;
+  double w = 0.0;
+  for (int64_t k = fptr[v]; k < fptr[v + 1]; ++k) {
+    const int64_t f = flist[k];
+    double p[D][D];
+#pragma unroll
+    for (int b = 0; b < D; ++b)
+#pragma unroll
+      for (int i = 0; i < D; ++i) p[b][i] = x[(int64_t)fverts[f * D + b] * D + i];
+    double meas;
+    if constexpr (D == 2) {
+      meas = sqrt((p[1][0] - p[0][0]) * (p[1][0] - p[0][0]) + (p[1][1] - p[0][1]) * (p[1][1] - p[0][1]));
+    } else {
+      const double e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]};
+      const double e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
+      const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+      meas = 0.5 * sqrt(cx * cx + cy * cy + cz * cz);
+    }
+    w += meas / D;
+  }
+  const double t[3] = {t0, t1, t2};
+#pragma unroll
+  for (int i = 0; i < D; ++i) F[v * D + i] = t[i] * w;
+}
+
+// --------------------------------------------------------------------------------------------- export ----
+template <int D>
+__global__ void k_elast_export(int64_t n_rows, const int64_t* __restrict__ mptr, const int32_t* __restrict__ cols,
+                               const int32_t* __restrict__ rowlen, const uint32_t* __restrict__ rowreal,
+                               const double* __restrict__ diag, const double* __restrict__ vals,
+                               const int64_t* __restrict__ rowptr, int32_t* __restrict__ ocol, double* __restrict__ oval) {
+  constexpr int DD = D * D;
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_rows) return;
+  const int64_t base = mptr[row >> 6];
+  const int lane = (int)(row & 63);
+  const int len = rowlen[row];
+  int64_t o = rowptr[row];
+  bool placed = false;
+  const uint32_t real = rowreal[row];
+  for (int k = 0; k < len; ++k) {
+    if (k < 32 && !((real >> k) & 1u)) continue;
+    const int64_t e = femo_sell_index(base, k, lane);
+    const int32_t c = cols[e];
+    if (!placed && c > row) {
+      ocol[o] = (int32_t)row;
+      for (int q = 0; q < DD; ++q) oval[o * DD + q] = diag[row * DD + q];
+      ++o; placed = true;
+    }
+    ocol[o] = c;
+    for (int q = 0; q < DD; ++q) oval[o * DD + q] = vals[e * DD + q];
+    ++o;
+  }
+  if (!placed) {
+    ocol[o] = (int32_t)row;
+    for (int q = 0; q < DD; ++q) oval[o * DD + q] = diag[row * DD + q];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ PCG ----
+// Device scalars s[]: 0 rz, 1 alpha, 2 beta, 3 tol^2, 4 rz0.  flag[]: 0 done, 1 iterations, 2 breakdown, 3 converged.
+enum { S_RZ = 0, S_ALPHA = 1, S_BETA = 2, S_TOL2 = 3, S_RZ0 = 4 };
+
+__global__ void k_pcg_start_x(int64_t n, int zero_guess, const uint8_t* __restrict__ fixed, const double* __restrict__ b,
+                              double* __restrict__ x) {
+  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (i >= n) return;
+  double v = zero_guess ? 0.0 : x[i];
+  if (fixed && fixed[i]) v = b[i];
+  x[i] = v;
+}
+
+// z = Dinv r (block), optional x += alpha p, r -= alpha q first; partial r.z per block; INIT: p = z as well
+template <int D, bool UPDATE, bool INIT>
+__global__ __launch_bounds__(EB) void k_pcg_precond(int64_t n_rows, const double* __restrict__ dinv, double* __restrict__ x,
+                                                    double* __restrict__ r, const double* __restrict__ p,
+                                                    const double* __restrict__ q, double* __restrict__ z,
+                                                    double* __restrict__ pinit, const double* __restrict__ s,
+                                                    double* __restrict__ part, const int32_t* __restrict__ flag) {
+  constexpr int DD = D * D;
+  __shared__ double lds[EB / 64];
+  if (UPDATE && flag[0]) return;
+  double dotv = 0.0;
+  const double alpha = UPDATE ? s[S_ALPHA] : 0.0;
+  for (int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x; row < n_rows; row += (int64_t)gridDim.x * EB) {
+    double rr[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      double ri = r[row * D + i];
+      if (UPDATE) {
+        x[row * D + i] += alpha * p[row * D + i];
+        ri -= alpha * q[row * D + i];
+        r[row * D + i] = ri;
+      }
+      rr[i] = ri;
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      double zi = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) zi += dinv[row * DD + i * D + k] * rr[k];
+      z[row * D + i] = zi;
+      if (INIT) pinit[row * D + i] = zi;
+      dotv += rr[i] * zi;
+    }
+  }
+  const double t = femo_block_sum<EB>(dotv, lds);
+  if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// one block: sum of the partials (fixed order)
+__device__ double sum_partials(const double* __restrict__ part, int np, double* lds) {
+  double v = 0.0;
+  for (int i = threadIdx.x; i < np; i += blockDim.x) v += part[i];
+  return femo_block_sum_all<1024>(v, lds);
+}
+
+// mode 0: initial rz.  mode 1: alpha = rz / pq.  mode 2: rz' -> beta, convergence.
+__global__ __launch_bounds__(1024) void k_pcg_scalar(int mode, const double* __restrict__ part, int np, double rtol2,
+                                                     double atol2, int max_it, double* __restrict__ s,
+                                                     int32_t* __restrict__ flag) {
+  __shared__ double lds[16];
+  if (mode != 0 && flag[0]) return;
+  const double v = sum_partials(part, np, lds);
+  if (threadIdx.x != 0) return;
+  if (mode == 0) {
+    s[S_RZ] = v; s[S_RZ0] = v;
+    const double tol2 = fmax(rtol2 * v, atol2);
+    s[S_TOL2] = tol2;
+    flag[0] = 0; flag[1] = 0; flag[2] = 0; flag[3] = 0;
+    if (!(v == v)) { flag[0] = 1; flag[2] = 1; }
+    else if (v <= tol2) { flag[0] = 1; flag[3] = 1; }
+  } else if (mode == 1) {
+    if (!(v > 0.0) || !(v == v)) { flag[0] = 1; flag[2] = 1; return; }
+    s[S_ALPHA] = s[S_RZ] / v;
+  } else {
+    flag[1] += 1;
+    if (!(v == v)) { flag[0] = 1; flag[2] = 1; return; }
+    s[S_BETA] = v / s[S_RZ];
+    s[S_RZ] = v;
+    if (v <= s[S_TOL2]) { flag[0] = 1; flag[3] = 1; }
+    else if (flag[1] >= max_it) flag[0] = 1;
+  }
+}
+
+__global__ void k_pcg_p(int64_t n, const double* __restrict__ z, double* __restrict__ p, const double* __restrict__ s,
+                        const int32_t* __restrict__ flag) {
+  if (flag[0]) return;
+  const double beta = s[S_BETA];
+  for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) p[i] = z[i] + beta * p[i];
+}
+
+// --------------------------------------------------------------------------------------------- filter ----
+struct Grid {
+  double lo[3];
+  double h;
+  int64_t n[3];
+};
+
+template <int D>
+__device__ __forceinline__ int64_t grid_cell(const Grid& G, const double* p, int64_t (&ijk)[3]) {
+  int64_t id = 0, stride = 1;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    int64_t q = (int64_t)floor((p[k] - G.lo[k]) / G.h);
+    q = q < 0 ? 0 : (q >= G.n[k] ? G.n[k] - 1 : q);
+    ijk[k] = q;
+    id += q * stride;
+    stride *= G.n[k];
+  }
+  return id;
+}
+
+template <int D>
+__global__ void k_f_bin(int64_t n, const double* __restrict__ x, Grid G, int64_t* __restrict__ cid,
+                        unsigned long long* __restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (i >= n) return;
+  int64_t ijk[3];
+  const int64_t c = grid_cell<D>(G, x + i * D, ijk);
+  cid[i] = c;
+  atomicAdd(&count[c], 1ull);
+}
+
+// exclusive scan of n counts into out[0..n] (one workgroup, chunk by chunk; build-time only)
+__global__ __launch_bounds__(1024) void k_scan(int64_t n, const unsigned long long* __restrict__ in, int64_t* __restrict__ out) {
+  __shared__ int64_t buf[1024];
+  __shared__ int64_t carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int64_t base = 0; base < n; base += 1024) {
+    const int64_t i = base + threadIdx.x;
+    const int64_t v = i < n ? (int64_t)in[i] : 0;
+    buf[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const int64_t t = threadIdx.x >= (unsigned)off ? buf[threadIdx.x - off] : 0;
+      __syncthreads();
+      buf[threadIdx.x] += t;
+      __syncthreads();
+    }
+    if (i < n) out[i] = carry + buf[threadIdx.x] - v;
+    __syncthreads();
+    if (threadIdx.x == 1023) carry += buf[1023];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[n] = carry;
+}
+
+__global__ void k_f_fill(int64_t n, const int64_t* __restrict__ cid, const int64_t* __restrict__ start,
+                         unsigned long long* __restrict__ cursor, int32_t* __restrict__ bucket) {
+  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = cid[i];
+  const unsigned long long k = atomicAdd(&cursor[c], 1ull);
+  bucket[start[c] + (int64_t)k] = (int32_t)i;
+}
+
+// each grid cell's points in ascending order: the walks below visit candidates deterministically
+__global__ void k_f_sort_buckets(int64_t ncell, const int64_t* __restrict__ start, int32_t* __restrict__ bucket) {
+  const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (c >= ncell) return;
+  const int64_t b = start[c], e = start[c + 1];
+  for (int64_t i = b + 1; i < e; ++i) {
+    const int32_t v = bucket[i];
+    int64_t j = i - 1;
+    while (j >= b && bucket[j] > v) { bucket[j + 1] = bucket[j]; --j; }
+    bucket[j + 1] = v;
+  }
+}
+
+__device__ __forceinline__ double dist_sym(const double* a, const double* b, int D) {
+  double s = 0.0;
+  for (int k = 0; k < D; ++k) { const double t = a[k] - b[k]; s += t * t; }
+  return sqrt(s);
+}
+
+// PASS 0: count the neighbours of every point.  PASS 1: write (column, r - d) into the row, then sort it by column.
+template <int D, int PASS>
+__global__ void k_f_rows(int64_t n, const double* __restrict__ x, Grid G, double radius, const int64_t* __restrict__ start,
+                         const int32_t* __restrict__ bucket, unsigned long long* __restrict__ rowcnt,
+                         const int64_t* __restrict__ rowptr, int32_t* __restrict__ col, double* __restrict__ rd) {
+  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (i >= n) return;
+  int64_t ijk[3] = {0, 0, 0};
+  grid_cell<D>(G, x + i * D, ijk);
+  int64_t cnt = 0;
+  const int64_t o = PASS == 1 ? rowptr[i] : 0;
+  const int dz = D == 3 ? 1 : 0;
+  for (int oz = -dz; oz <= dz; ++oz)
+    for (int oy = -1; oy <= 1; ++oy)
+      for (int ox = -1; ox <= 1; ++ox) {
+        const int64_t cx = ijk[0] + ox, cy = ijk[1] + oy, cz = ijk[2] + oz;
+        if (cx < 0 || cx >= G.n[0] || cy < 0 || cy >= G.n[1]) continue;
+        if (D == 3 && (cz < 0 || cz >= G.n[2])) continue;
+        const int64_t c = cx + G.n[0] * (cy + (D == 3 ? G.n[1] * cz : 0));
+        for (int64_t k = start[c]; k < start[c + 1]; ++k) {
+          const int32_t j = bucket[k];
+          const double d = dist_sym(x + i * D, x + (int64_t)j * D, D);
+          if (d <= radius) {
+            if (PASS == 1) { col[o + cnt] = j; rd[o + cnt] = radius - d; }
+            ++cnt;
+          }
+        }
+      }
+  if (PASS == 0) {
+    rowcnt[i] = (unsigned long long)cnt;
+  } else {
+    for (int64_t a = o + 1; a < o + cnt; ++a) {
+      const int32_t cj = col[a];
+      const double vj = rd[a];
+      int64_t b = a - 1;
+      while (b >= o && col[b] > cj) { col[b + 1] = col[b]; rd[b + 1] = rd[b]; --b; }
+      col[b + 1] = cj; rd[b + 1] = vj;
+    }
+  }
+}
+
+__global__ void k_f_rowsum(int64_t n, const int64_t* __restrict__ rowptr, const double* __restrict__ rd, double* __restrict__ S) {
+  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) s += rd[e];
+  S[i] = s;
+}
+
+// W_ij = (r - d_ij) / S_i;  (W^T)_ij = W_ji = (r - d_ij) / S_j on the same pattern (d_ij = d_ji bit for bit)
+__global__ void k_f_weights(int64_t n, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                            const double* __restrict__ S, double* __restrict__ val, double* __restrict__ valT) {
+  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (i >= n) return;
+  const double si = S[i];
+  for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+    const double r = valT[e];
+    val[e] = r / si;
+    valT[e] = r / S[col[e]];
+  }
+}
+
+__global__ void k_f_apply(int64_t n, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                          const double* __restrict__ val, const double* __restrict__ x, double* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) s += val[e] * x[col[e]];
+  y[i] = s;
+}
+
+template <typename T>
+int dalloc(T** p, int64_t n) {
+  FEMO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), (size_t)std::max<int64_t>(n, 1) * sizeof(T)));
+  return 0;
+}
+
+}  // namespace
+
+// ===================================================================================================== C-ABI ====
+extern "C" {
+
+int femo_elast_create(femo_mesh* m, double E, double nu, femo_elast** out) {
+  FEMO_REQUIRE(m && out, "null argument");
+  FEMO_REQUIRE(m->tdim == 2 || m->tdim == 3, "elasticity needs a 2-D or 3-D simplex mesh");
+  FEMO_REQUIRE(m->n_nbr == 0 && m->n_rows == m->n_vert,
+               "elasticity runs on one GPU: a partitioned mesh (halo set) is not supported");
+  FEMO_REQUIRE(nu > -1.0 && nu < 0.5 && E > 0.0, "elasticity: need E > 0 and -1 < nu < 1/2");
+  auto* e = new femo_elast();
+  e->mesh = m;
+  e->d = m->tdim;
+  e->lam0 = E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu));
+  e->mu0 = E / (2.0 * (1.0 + nu));
+  const int64_t dd = (int64_t)e->d * e->d, n = m->n_vert * e->d;
+  int rc = 0;
+  rc |= dalloc(&e->d_vals, m->sell_entries * dd);
+  rc |= dalloc(&e->d_diag, m->n_vert * dd);
+  rc |= dalloc(&e->d_dinv, m->n_vert * dd);
+  rc |= dalloc(&e->w_r, n); rc |= dalloc(&e->w_z, n); rc |= dalloc(&e->w_p, n); rc |= dalloc(&e->w_q, n);
+  rc |= dalloc(&e->w_part, std::max<int64_t>(PCG_GRID, (m->n_vert + EB - 1) / EB));
+  rc |= dalloc(&e->w_s, 8);
+  rc |= dalloc(&e->w_flag, 4);
+  if (rc == 0 && hipHostMalloc(reinterpret_cast<void**>(&e->h_flag), 4 * sizeof(int32_t)) != hipSuccess) rc = 1;
+  if (rc == 0 && hipHostMalloc(reinterpret_cast<void**>(&e->h_s), 8 * sizeof(double)) != hipSuccess) rc = 1;
+  if (rc) { femo_elast_destroy(e); femo_set_error("femo_elast_create: device allocation failed"); return 1; }
+  *out = e;
+  return 0;
+}
+
+int femo_elast_destroy(femo_elast* e) {
+  if (!e) return 0;                    // hipFree waits for the device; the mesh may already be gone
+  hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
+  hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
+  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag);
+  if (e->h_flag) hipHostFree(e->h_flag);
+  if (e->h_s) hipHostFree(e->h_s);
+  delete e;
+  return 0;
+}
+
+int femo_elast_info(const femo_elast* e, int64_t info[FEMO_ELAST_INFO_COUNT]) {
+  FEMO_REQUIRE(e && info, "null argument");
+  const femo_mesh* m = e->mesh;
+  const int64_t d = e->d;
+  info[FEMO_ELAST_INFO_DIM] = d;
+  info[FEMO_ELAST_INFO_NDOF] = d * m->n_vert;
+  info[FEMO_ELAST_INFO_NNZ] = m->nnz;
+  info[FEMO_ELAST_INFO_SELL] = m->sell_entries;
+  info[FEMO_ELAST_INFO_SPMV_BYTES] = m->nnz * (4 + 8 * d * d) + m->n_vert * 16 * d + (m->n_slices + 1) * 8 + m->n_vert * 4;
+  return 0;
+}
+
+int femo_elast_set_fixed(femo_elast* e, const uint8_t* mask) {
+  FEMO_REQUIRE(e, "null argument");
+  const int64_t n = e->mesh->n_vert * e->d;
+  hipStream_t st = e->mesh->ctx->stream;
+  if (!mask) { e->has_fixed = false; return 0; }
+  if (!e->d_fixed) FEMO_TRY(dalloc(&e->d_fixed, n));
+  FEMO_HIP_CHECK(hipMemcpyAsync(e->d_fixed, mask, n, hipMemcpyHostToDevice, st));
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  e->has_fixed = true;
+  return 0;
+}
+
+int femo_elast_set_facets(femo_elast* e, int64_t n_facets, const int32_t* fv) {
+  FEMO_REQUIRE(e && (fv || n_facets == 0) && n_facets >= 0, "null argument");
+  const femo_mesh* m = e->mesh;
+  const int d = e->d;
+  std::vector<int64_t> ptr(m->n_vert + 1, 0);
+  for (int64_t f = 0; f < n_facets * d; ++f) {
+    FEMO_REQUIRE(fv[f] >= 0 && fv[f] < m->n_vert, "facet vertex out of range");
+    ++ptr[fv[f] + 1];
+  }
+  for (int64_t v = 0; v < m->n_vert; ++v) ptr[v + 1] += ptr[v];
+  std::vector<int32_t> list(ptr[m->n_vert]);
+  std::vector<int64_t> cur(ptr.begin(), ptr.end() - 1);
+  for (int64_t f = 0; f < n_facets; ++f)               // ascending facet order per vertex
+    for (int b = 0; b < d; ++b) list[cur[fv[f * d + b]]++] = (int32_t)f;
+  hipStream_t st = m->ctx->stream;
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
+  e->d_fverts = nullptr; e->d_fptr = nullptr; e->d_flist = nullptr;
+  FEMO_TRY(dalloc(&e->d_fverts, n_facets * d));
+  FEMO_TRY(dalloc(&e->d_fptr, m->n_vert + 1));
+  FEMO_TRY(dalloc(&e->d_flist, (int64_t)list.size()));
+  if (n_facets) FEMO_HIP_CHECK(hipMemcpyAsync(e->d_fverts, fv, n_facets * d * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(e->d_fptr, ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  if (!list.empty()) FEMO_HIP_CHECK(hipMemcpyAsync(e->d_flist, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  e->n_facets = n_facets;
+  return 0;
+}
+
+int femo_elast_assemble(femo_elast* e, int method, const femo_vec* rho) {
+  FEMO_REQUIRE(e && rho, "null argument");
+  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
+  femo_mesh* m = e->mesh;
+  FEMO_REQUIRE(rho->n >= m->n_cell, "density vector too small");
+  FEMO_TRY(femo_vec_await(rho));
+  hipStream_t st = m->ctx->stream;
+  const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
+  if (e->d == 2)
+    hipLaunchKernelGGL(k_elast_assemble<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell,
+                       m->d_visit_slots, m->d_mptr, m->d_rowlen, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, fx,
+                       e->d_vals, e->d_diag, e->d_dinv);
+  else
+    hipLaunchKernelGGL(k_elast_assemble<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell,
+                       m->d_visit_slots, m->d_mptr, m->d_rowlen, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, fx,
+                       e->d_vals, e->d_diag, e->d_dinv);
+  FEMO_HIP_CHECK(hipGetLastError());
+  e->assembled = true;
+  return 0;
+}
+
+static int elast_spmv(femo_elast* e, bool masked, double a, const double* x, double b, const double* f, double* y,
+                      double* part, const int32_t* done) {
+  femo_mesh* m = e->mesh;
+  hipStream_t st = m->ctx->stream;
+  const unsigned g = grid_of(m->n_rows);
+  const uint8_t* fx = e->d_fixed;
+#define FEMO_ESPMV(D, M) hipLaunchKernelGGL((k_elast_spmv<D, M>), dim3(g), dim3(EB), 0, st, m->n_rows, m->d_mptr, m->d_cols, \
+                                            m->d_rowlen, e->d_vals, e->d_diag, fx, a, x, b, f, y, part, done)
+  if (e->d == 2) { if (masked) FEMO_ESPMV(2, true); else FEMO_ESPMV(2, false); }
+  else { if (masked) FEMO_ESPMV(3, true); else FEMO_ESPMV(3, false); }
+#undef FEMO_ESPMV
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_elast_apply(femo_elast* e, int masked, double a, const femo_vec* x, double b, const femo_vec* f, femo_vec* y) {
+  FEMO_REQUIRE(e && x && y, "null argument");
+  FEMO_REQUIRE(e->assembled, "femo_elast_apply: assemble K first");
+  const int64_t n = e->mesh->n_vert * e->d;
+  FEMO_REQUIRE(x->n >= n && y->n >= n && (!f || f->n >= n), "vector size mismatch in femo_elast_apply");
+  FEMO_REQUIRE(!masked || e->has_fixed, "femo_elast_apply: masked product without a fixed set");
+  FEMO_REQUIRE(x != y, "femo_elast_apply: x and y must differ");
+  FEMO_TRY(femo_vec_await(x));
+  if (f) FEMO_TRY(femo_vec_await(f));
+  femo_vec_touch(y);
+  return elast_spmv(e, masked != 0, a, x->d, b, f ? f->d : nullptr, y->d, nullptr, nullptr);
+}
+
+int femo_elast_load(femo_elast* e, const double* t, femo_vec* F) {
+  FEMO_REQUIRE(e && t && F, "null argument");
+  femo_mesh* m = e->mesh;
+  FEMO_REQUIRE(F->n >= m->n_vert * e->d, "load vector too small");
+  FEMO_REQUIRE(e->d_fptr, "femo_elast_load: no tagged facets (femo_elast_set_facets)");
+  femo_vec_touch(F);
+  hipStream_t st = m->ctx->stream;
+  const double t2 = e->d == 3 ? t[2] : 0.0;
+  if (e->d == 2)
+    hipLaunchKernelGGL(k_elast_load<2>, dim3(grid_of(m->n_vert)), dim3(EB), 0, st, m->n_vert, e->d_fptr, e->d_flist, e->d_fverts, m->d_x, t[0], t[1], t2, F->d);
+  else
+    hipLaunchKernelGGL(k_elast_load<3>, dim3(grid_of(m->n_vert)), dim3(EB), 0, st, m->n_vert, e->d_fptr, e->d_flist, e->d_fverts, m->d_x, t[0], t[1], t2, F->d);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rho, const femo_vec* u, const femo_vec* x,
+                    femo_vec* y, int accumulate) {
+  FEMO_REQUIRE(e && rho && u && x && y, "null argument");
+  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
+  femo_mesh* m = e->mesh;
+  const int64_t n = m->n_vert * e->d;
+  FEMO_REQUIRE(rho->n >= m->n_cell && u->n >= n, "vector size mismatch in femo_elast_drho");
+  FEMO_REQUIRE(transpose ? (x->n >= n && y->n >= m->n_cell) : (x->n >= m->n_cell && y->n >= n), "vector size mismatch in femo_elast_drho");
+  FEMO_REQUIRE(y != x && y != u && y != rho, "femo_elast_drho: output aliases an input");
+  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(x));
+  femo_vec_touch(y);
+  hipStream_t st = m->ctx->stream;
+  if (transpose) {
+    if (e->d == 2)
+      hipLaunchKernelGGL(k_elast_drho_T<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, u->d, x->d, y->d, accumulate);
+    else
+      hipLaunchKernelGGL(k_elast_drho_T<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, u->d, x->d, y->d, accumulate);
+  } else {
+    if (e->d == 2)
+      hipLaunchKernelGGL(k_elast_drho_N<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, u->d, x->d, y->d, accumulate);
+    else
+      hipLaunchKernelGGL(k_elast_drho_N<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, u->d, x->d, y->d, accumulate);
+  }
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info) {
+  FEMO_REQUIRE(e && b && x && opts, "null argument");
+  FEMO_REQUIRE(e->assembled, "femo_elast_solve: assemble K first");
+  femo_mesh* m = e->mesh;
+  const int64_t n = m->n_vert * e->d;
+  FEMO_REQUIRE(b->n >= n && x->n >= n && b != x, "vector size mismatch in femo_elast_solve");
+  FEMO_TRY(femo_vec_await(b));
+  femo_vec_touch(x);
+  hipStream_t st = m->ctx->stream;
+  const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
+  const int check = opts->check_every > 0 ? opts->check_every : 32;
+  const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
+  const double rtol2 = opts->rtol * opts->rtol, atol2 = opts->atol * opts->atol;
+  const unsigned gs = grid_of(m->n_rows);
+  const int nps = (int)gs;
+  hipEvent_t e0 = m->ctx->ev0, e1 = m->ctx->ev1;
+  FEMO_HIP_CHECK(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(k_pcg_start_x, dim3(grid_of(n)), dim3(EB), 0, st, n, opts->zero_guess, fx, b->d, x->d);
+  FEMO_TRY(elast_spmv(e, fx != nullptr, -1.0, x->d, 1.0, b->d, e->w_r, nullptr, nullptr));    // r = b - A x
+  const unsigned gp = (unsigned)PCG_GRID;
+#define FEMO_PRECOND(D, U, I) hipLaunchKernelGGL((k_pcg_precond<D, U, I>), dim3(gp), dim3(EB), 0, st, m->n_rows, e->d_dinv, x->d, \
+                                                 e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, e->w_flag)
+  if (e->d == 2) FEMO_PRECOND(2, false, true); else FEMO_PRECOND(3, false, true);
+  hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 0, e->w_part, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
+  FEMO_HIP_CHECK(hipGetLastError());
+  int it_issued = 0;
+  for (;;) {
+    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_flag, e->w_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FEMO_HIP_CHECK(hipStreamSynchronize(st));
+    if (e->h_flag[0] || it_issued >= max_it) break;
+    for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) {
+      FEMO_TRY(elast_spmv(e, fx != nullptr, 1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, e->w_flag));   // q = A p, p.q
+      hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 1, e->w_part, nps, rtol2, atol2, max_it, e->w_s, e->w_flag);
+      if (e->d == 2) FEMO_PRECOND(2, true, false); else FEMO_PRECOND(3, true, false);
+      hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 2, e->w_part, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
+      hipLaunchKernelGGL(k_pcg_p, dim3(gp), dim3(EB), 0, st, n, e->w_z, e->w_p, e->w_s, e->w_flag);
+    }
+    FEMO_HIP_CHECK(hipGetLastError());
+  }
+#undef FEMO_PRECOND
+  FEMO_HIP_CHECK(hipEventRecord(e1, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(e->h_s, e->w_s, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  if (info) {
+    std::memset(info, 0, sizeof(*info));
+    info->iterations = e->h_flag[1];
+    info->converged = e->h_flag[2] ? -1 : (e->h_flag[3] ? 1 : 0);
+    info->residual_norm = std::sqrt(std::fabs(e->h_s[S_RZ]));
+    info->rhs_norm = std::sqrt(std::fabs(e->h_s[S_RZ0]));
+    info->pc_residual_norm = info->residual_norm;
+    info->pc_rhs_norm = info->rhs_norm;
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) info->solve_ms = ms;
+  }
+  return 0;
+}
+
+int femo_elast_export_csr(const femo_elast* e, int64_t* rowptr, int32_t* col, double* val) {
+  FEMO_REQUIRE(e && rowptr && col && val, "null argument");
+  FEMO_REQUIRE(e->assembled, "femo_elast_export_csr: assemble K first");
+  const femo_mesh* m = e->mesh;
+  FEMO_TRY(femo_mesh_pattern_csr(m, rowptr, col));
+  const int64_t dd = (int64_t)e->d * e->d;
+  hipStream_t st = m->ctx->stream;
+  int64_t* d_rp = nullptr; int32_t* d_col = nullptr; double* d_val = nullptr;
+  FEMO_TRY(dalloc(&d_rp, m->n_rows + 1));
+  FEMO_TRY(dalloc(&d_col, m->nnz));
+  FEMO_TRY(dalloc(&d_val, m->nnz * dd));
+  FEMO_HIP_CHECK(hipMemcpyAsync(d_rp, rowptr, (m->n_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  if (e->d == 2)
+    hipLaunchKernelGGL(k_elast_export<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, m->d_rowreal, e->d_diag, e->d_vals, d_rp, d_col, d_val);
+  else
+    hipLaunchKernelGGL(k_elast_export<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, m->d_rowreal, e->d_diag, e->d_vals, d_rp, d_col, d_val);
+  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_HIP_CHECK(hipMemcpyAsync(col, d_col, m->nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(val, d_val, m->nnz * dd * sizeof(double), hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  hipFree(d_rp); hipFree(d_col); hipFree(d_val);
+  return 0;
+}
+
+int femo_elast_bench_spmv(femo_elast* e, const femo_vec* x, femo_vec* y, int reps, double* ms) {
+  FEMO_REQUIRE(e && x && y && ms && reps > 0, "null argument");
+  FEMO_REQUIRE(e->assembled, "femo_elast_bench_spmv: assemble K first");
+  const int64_t n = e->mesh->n_vert * e->d;
+  FEMO_REQUIRE(x->n >= n && y->n >= n && x != y, "vector size mismatch in femo_elast_bench_spmv");
+  hipStream_t st = e->mesh->ctx->stream;
+  femo_vec_touch(y);
+  FEMO_TRY(elast_spmv(e, false, 1.0, x->d, 0.0, nullptr, y->d, nullptr, nullptr));     // warm-up
+  FEMO_HIP_CHECK(hipEventRecord(e->mesh->ctx->ev0, st));
+  for (int k = 0; k < reps; ++k) FEMO_TRY(elast_spmv(e, false, 1.0, x->d, 0.0, nullptr, y->d, nullptr, nullptr));
+  FEMO_HIP_CHECK(hipEventRecord(e->mesh->ctx->ev1, st));
+  FEMO_HIP_CHECK(hipEventSynchronize(e->mesh->ctx->ev1));
+  float t = 0.0f;
+  FEMO_HIP_CHECK(hipEventElapsedTime(&t, e->mesh->ctx->ev0, e->mesh->ctx->ev1));
+  *ms = t / reps;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ filter ----
+int femo_filter_create(femo_ctx* ctx, int dim, int64_t n, const double* coords, double radius, femo_filter** out) {
+  FEMO_REQUIRE(ctx && coords && out, "null argument");
+  FEMO_REQUIRE(dim == 2 || dim == 3, "filter: dim must be 2 or 3");
+  FEMO_REQUIRE(n > 0 && n < INT32_MAX, "filter: bad point count");
+  FEMO_REQUIRE(radius > 0.0 && std::isfinite(radius), "filter: radius must be positive");
+  // uniform grid, cell size >= r (the 3^d cells around a point hold every neighbour), at most ~ 4 n + 1024 cells
+  Grid G{};
+  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  for (int k = 0; k < dim; ++k) { lo[k] = coords[k]; hi[k] = coords[k]; }
+  for (int64_t i = 0; i < n; ++i)
+    for (int k = 0; k < dim; ++k) { lo[k] = std::min(lo[k], coords[i * dim + k]); hi[k] = std::max(hi[k], coords[i * dim + k]); }
+  double h = radius;
+  for (;;) {
+    double cells = 1.0;
+    for (int k = 0; k < dim; ++k) cells *= std::floor((hi[k] - lo[k]) / h) + 1.0;
+    if (cells <= 4.0 * (double)n + 1024.0) break;
+    h *= 1.25;
+  }
+  G.h = h;
+  int64_t ncell = 1;
+  for (int k = 0; k < 3; ++k) {
+    G.lo[k] = lo[k];
+    G.n[k] = k < dim ? (int64_t)std::floor((hi[k] - lo[k]) / h) + 1 : 1;
+    ncell *= G.n[k];
+  }
+  hipStream_t st = ctx->stream;
+  auto* F = new femo_filter();
+  F->ctx = ctx;
+  F->n = n;
+  double* d_x = nullptr; int64_t* d_cid = nullptr; unsigned long long* d_cnt = nullptr; int64_t* d_start = nullptr;
+  int32_t* d_bucket = nullptr; double* d_S = nullptr;
+  auto fail = [&](int rc) { hipFree(d_x); hipFree(d_cid); hipFree(d_cnt); hipFree(d_start); hipFree(d_bucket); hipFree(d_S);
+                            femo_filter_destroy(F); return rc; };
+  if (dalloc(&d_x, n * dim) || dalloc(&d_cid, n) || dalloc(&d_cnt, std::max(ncell, n)) || dalloc(&d_start, std::max(ncell, n) + 1) ||
+      dalloc(&d_bucket, n) || dalloc(&d_S, n) || dalloc(&F->d_rowptr, n + 1))
+    return fail(1);
+  if (hipMemcpyAsync(d_x, coords, n * dim * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(d_cnt, 0, ncell * sizeof(unsigned long long), st) != hipSuccess) {
+    femo_set_error("femo_filter_create: copy failed"); return fail(1);
+  }
+  const unsigned gn = grid_of(n), gc = grid_of(ncell);
+  if (dim == 2) hipLaunchKernelGGL(k_f_bin<2>, dim3(gn), dim3(EB), 0, st, n, d_x, G, d_cid, d_cnt);
+  else hipLaunchKernelGGL(k_f_bin<3>, dim3(gn), dim3(EB), 0, st, n, d_x, G, d_cid, d_cnt);
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, ncell, d_cnt, d_start);
+  hipMemsetAsync(d_cnt, 0, ncell * sizeof(unsigned long long), st);
+  hipLaunchKernelGGL(k_f_fill, dim3(gn), dim3(EB), 0, st, n, d_cid, d_start, d_cnt, d_bucket);
+  hipLaunchKernelGGL(k_f_sort_buckets, dim3(gc), dim3(EB), 0, st, ncell, d_start, d_bucket);
+  // rows: count, scan, fill + sort
+  unsigned long long* d_rowcnt = d_cnt;      // reused (n entries fit: allocated max(ncell, n))
+  if (dim == 2) hipLaunchKernelGGL((k_f_rows<2, 0>), dim3(gn), dim3(EB), 0, st, n, d_x, G, radius, d_start, d_bucket, d_rowcnt, nullptr, nullptr, nullptr);
+  else hipLaunchKernelGGL((k_f_rows<3, 0>), dim3(gn), dim3(EB), 0, st, n, d_x, G, radius, d_start, d_bucket, d_rowcnt, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, st, n, d_rowcnt, F->d_rowptr);
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(&F->nnz, F->d_rowptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    femo_set_error("femo_filter_create: grid passes failed"); return fail(1);
+  }
+  if (dalloc(&F->d_col, F->nnz) || dalloc(&F->d_val, F->nnz) || dalloc(&F->d_valT, F->nnz)) return fail(1);
+  if (dim == 2) hipLaunchKernelGGL((k_f_rows<2, 1>), dim3(gn), dim3(EB), 0, st, n, d_x, G, radius, d_start, d_bucket, nullptr, F->d_rowptr, F->d_col, F->d_valT);
+  else hipLaunchKernelGGL((k_f_rows<3, 1>), dim3(gn), dim3(EB), 0, st, n, d_x, G, radius, d_start, d_bucket, nullptr, F->d_rowptr, F->d_col, F->d_valT);
+  hipLaunchKernelGGL(k_f_rowsum, dim3(gn), dim3(EB), 0, st, n, F->d_rowptr, F->d_valT, d_S);
+  hipLaunchKernelGGL(k_f_weights, dim3(gn), dim3(EB), 0, st, n, F->d_rowptr, F->d_col, d_S, F->d_val, F->d_valT);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    femo_set_error("femo_filter_create: row passes failed"); return fail(1);
+  }
+  hipFree(d_x); hipFree(d_cid); hipFree(d_cnt); hipFree(d_start); hipFree(d_bucket); hipFree(d_S);
+  *out = F;
+  return 0;
+}
+
+int femo_filter_destroy(femo_filter* f) {
+  if (!f) return 0;
+  hipFree(f->d_rowptr); hipFree(f->d_col); hipFree(f->d_val); hipFree(f->d_valT);
+  delete f;
+  return 0;
+}
+
+int femo_filter_nnz(const femo_filter* f, int64_t* nnz) {
+  FEMO_REQUIRE(f && nnz, "null argument");
+  *nnz = f->nnz;
+  return 0;
+}
+
+int femo_filter_apply(femo_filter* f, int transpose, const femo_vec* x, femo_vec* y) {
+  FEMO_REQUIRE(f && x && y, "null argument");
+  FEMO_REQUIRE(x->n >= f->n && y->n >= f->n && x != y, "vector size mismatch in femo_filter_apply");
+  FEMO_TRY(femo_vec_await(x));
+  femo_vec_touch(y);
+  hipLaunchKernelGGL(k_f_apply, dim3(grid_of(f->n)), dim3(EB), 0, f->ctx->stream, f->n, f->d_rowptr, f->d_col,
+                     transpose ? f->d_valT : f->d_val, x->d, y->d);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_filter_export_csr(const femo_filter* f, int transpose, int64_t* rowptr, int32_t* col, double* val) {
+  FEMO_REQUIRE(f && rowptr && col && val, "null argument");
+  hipStream_t st = f->ctx->stream;
+  FEMO_HIP_CHECK(hipMemcpyAsync(rowptr, f->d_rowptr, (f->n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(col, f->d_col, f->nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(val, transpose ? f->d_valT : f->d_val, f->nnz * sizeof(double), hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  return 0;
+}
+
+}  // extern "C"

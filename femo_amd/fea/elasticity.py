@@ -1,0 +1,508 @@
+"""SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
+handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip).
+
+The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
+own assembly and solves, so `FEA.add_input / add_state / add_output`, `StateOperation`, `OutputOperation` and `FEAModel`
+are used unchanged.
+
+  ElasticityResidual   R(u; rho) = sum_e C(rho_e) int_e sigma_0(u) : eps(v) dx - int_ds(tag) t . v ds   (pdeRes, :85-101)
+                       C = rho^3 (SIMP) or rho / (1 + 8 (1 - rho)) (RAMP); sigma_0 = lambda_0 tr(eps) I + 2 mu_0 eps with
+                       lambda_0 = E nu / ((1 + nu)(1 - 2 nu)), mu_0 = E / (2 (1 + nu)) -- plane strain in 2-D
+  Compliance           J = int_ds(tag) t . u ds = F^T u                                                 (compliance, :108-109)
+  averageFunc          (1/|Omega|) int rho dx as a LinearFunctional with the DG0 coefficient |T_e| / |Omega| (:103-106)
+
+P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from .. import _lib
+from .._lib import check
+from ..engine import Vec, _ptr
+from .forms import BackendForm, LinearFunctional
+from .function import Function, FunctionSpace, VectorFunctionSpace
+from .io import MeshTags
+
+METHODS = {"SIMP": _lib.ELAST_SIMP, "RAMP": _lib.ELAST_RAMP}
+
+
+def _ctx():
+    from .utils_hip import get_context
+    return get_context()
+
+
+# ------------------------------------------------------------------------------------------------ device handles ----
+class DeviceElasticity:
+    """femo_elast: K(rho) as d x d blocks on the mesh's scalar pattern, its products, the traction load, dR/drho and PCG."""
+
+    def __init__(self, ctx, mesh, E: float = 1.0, nu: float = 0.3):
+        self.ctx, self.lib, self.mesh = ctx, ctx.lib, mesh
+        self.dm = mesh.device(ctx)
+        h = _lib.H()
+        check(self.lib.femo_elast_create(self.dm.handle, float(E), float(nu), C.byref(h)))
+        self.handle = h
+        buf = (C.c_int64 * len(_lib.ELAST_INFO_KEYS))()
+        check(self.lib.femo_elast_info(self.handle, buf))
+        self.info = dict(zip(_lib.ELAST_INFO_KEYS, (int(v) for v in buf)))
+        self.d, self.n_dof = self.info["dim"], self.info["n_dof"]
+        self.fixed_key = None
+        self.facets_key = None
+
+    def set_fixed(self, mask: Optional[np.ndarray]) -> None:
+        if mask is None:
+            check(self.lib.femo_elast_set_fixed(self.handle, None))
+            self.fixed_key = None
+            return
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        assert m.size == self.n_dof
+        check(self.lib.femo_elast_set_fixed(self.handle, _ptr(m)))
+        self.fixed_key = hash(m.tobytes())
+
+    def set_facets(self, facets: np.ndarray) -> None:
+        f = np.ascontiguousarray(facets, dtype=np.int32).reshape(-1, self.d)
+        key = hash(f.tobytes())
+        if key != self.facets_key:
+            check(self.lib.femo_elast_set_facets(self.handle, f.shape[0], _ptr(f)))
+            self.facets_key = key
+
+    def assemble(self, method: int, rho: Vec) -> None:
+        check(self.lib.femo_elast_assemble(self.handle, int(method), rho.handle))
+
+    def apply(self, x: Vec, y: Vec, masked: bool = False, a: float = 1.0, b: float = 0.0, f: Optional[Vec] = None) -> Vec:
+        """y = a K x + b f, or with A (identity rows / columns on the fixed dofs) when ``masked``."""
+        check(self.lib.femo_elast_apply(self.handle, int(bool(masked)), float(a), x.handle, float(b),
+                                        None if f is None else f.handle, y.handle))
+        return y
+
+    def load(self, t, out: Vec) -> Vec:
+        tv = (C.c_double * 3)(*([float(v) for v in np.ravel(t)] + [0.0] * 3)[:3])
+        check(self.lib.femo_elast_load(self.handle, tv, out.handle))
+        return out
+
+    def drho(self, method: int, transpose: bool, rho: Vec, u: Vec, x: Vec, y: Vec, accumulate: bool = False) -> Vec:
+        check(self.lib.femo_elast_drho(self.handle, int(method), int(bool(transpose)), rho.handle, u.handle, x.handle,
+                                       y.handle, int(bool(accumulate))))
+        return y
+
+    def solve(self, b: Vec, x: Vec, rtol: float = 1e-15, atol: float = 0.0, max_it: int = 1_000_000,
+              check_every: int = 64, zero_guess: bool = True) -> _lib.SolveInfo:
+        opts = _lib.SolverOpts(rtol=float(rtol), atol=float(atol), max_it=int(max_it), zero_guess=int(bool(zero_guess)),
+                               check_every=int(check_every), pc=0, atol_pc=0.0)
+        info = _lib.SolveInfo()
+        check(self.lib.femo_elast_solve(self.handle, b.handle, x.handle, C.byref(opts), C.byref(info)))
+        return info
+
+    def export_csr(self):
+        """K as a SciPy CSR matrix of size n_dof (host copy; tests and debugging)."""
+        import scipy.sparse as sp
+        nr, nnz, d = self.mesh.n_vert, self.info["nnz"], self.d
+        rowptr = np.zeros(nr + 1, np.int64)
+        col = np.zeros(nnz, np.int32)
+        val = np.zeros(nnz * d * d)
+        check(self.lib.femo_elast_export_csr(self.handle, _ptr(rowptr), _ptr(col), _ptr(val)))
+        return sp.bsr_matrix((val.reshape(nnz, d, d), col, rowptr), shape=(nr * d, nr * d)).tocsr()
+
+    def bench_spmv(self, x: Vec, y: Vec, reps: int = 20) -> float:
+        ms = C.c_double(0.0)
+        check(self.lib.femo_elast_bench_spmv(self.handle, x.handle, y.handle, int(reps), C.byref(ms)))
+        return ms.value
+
+    def __del__(self):
+        try:
+            h, self.handle = getattr(self, "handle", None), None
+            if h and getattr(self.ctx, "handle", None) and getattr(self.dm, "handle", None):
+                self.lib.femo_elast_destroy(h)
+        except Exception:
+            pass
+
+
+def elasticity_handle(mesh, E: float = 1.0, nu: float = 0.3) -> DeviceElasticity:
+    """One handle per (mesh, context, E, nu)."""
+    ctx = _ctx()
+    cache = mesh.__dict__.setdefault("_elast", {})
+    key = (id(ctx), float(E), float(nu))
+    h = cache.get(key)
+    if h is None or h.ctx is not ctx:
+        h = cache[key] = DeviceElasticity(ctx, mesh, E, nu)
+    return h
+
+
+class DeviceFilter:
+    """femo_filter: W_ij = (r - d_ij) / sum_k (r - d_ik) over d_ij <= r, and W^T, built on the device
+    (GeneralFilterOperation.compute_weight_mat, pre_processor/general_filter_model.py)."""
+
+    def __init__(self, ctx, coordinates: np.ndarray, radius: float):
+        self.ctx, self.lib = ctx, ctx.lib
+        x = np.ascontiguousarray(coordinates, dtype=np.float64)
+        if x.ndim != 2 or x.shape[1] not in (2, 3):
+            raise ValueError("filter coordinates must be an (n, 2) or (n, 3) array")
+        self.n, self.dim, self.radius = x.shape[0], x.shape[1], float(radius)
+        h = _lib.H()
+        check(self.lib.femo_filter_create(ctx.handle, self.dim, self.n, _ptr(x), self.radius, C.byref(h)))
+        self.handle = h
+        nnz = C.c_int64(0)
+        check(self.lib.femo_filter_nnz(self.handle, C.byref(nnz)))
+        self.nnz = int(nnz.value)
+
+    def apply(self, x: Vec, y: Vec, transpose: bool = False) -> Vec:
+        check(self.lib.femo_filter_apply(self.handle, int(bool(transpose)), x.handle, y.handle))
+        return y
+
+    def export_csr(self, transpose: bool = False):
+        """(rowptr, col, val) of W (or W^T), rows sorted by column."""
+        rowptr = np.zeros(self.n + 1, np.int64)
+        col = np.zeros(self.nnz, np.int32)
+        val = np.zeros(self.nnz)
+        check(self.lib.femo_filter_export_csr(self.handle, int(bool(transpose)), _ptr(rowptr), _ptr(col), _ptr(val)))
+        return rowptr, col, val
+
+    def __del__(self):
+        try:
+            h, self.handle = getattr(self, "handle", None), None
+            if h and getattr(self.ctx, "handle", None):
+                self.lib.femo_filter_destroy(h)
+        except Exception:
+            pass
+
+
+# ----------------------------------------------------------------------------------------- boundary data / UFL ----
+class Constant:
+    """dolfinx.fem.Constant(mesh, value) [ext]: a spatially constant scalar or vector (run_topo_opt_cantilever_beam.py:73)."""
+
+    def __init__(self, mesh, value):
+        self.mesh = mesh
+        self.value = np.array(value, dtype=np.float64)
+
+    def __array__(self, dtype=None, copy=None):
+        return self.value if dtype is None else self.value.astype(dtype)
+
+
+def meshtags(mesh, dim: int, entities, values) -> MeshTags:
+    """dolfinx.mesh.meshtags [ext]: entities (as returned by locate_entities_boundary, one row of vertices each) with
+    integer tags (run_topo_opt_cantilever_beam.py:46-47)."""
+    ents = np.asarray(entities, dtype=np.int32).reshape(len(np.atleast_1d(values)), -1)
+    if ents.size and ents.shape[1] != dim + 1:
+        raise ValueError(f"entities of dimension {dim} have {dim + 1} vertices")
+    return MeshTags(dim, ents, np.atleast_1d(values))
+
+
+class Measure:
+    """ufl.Measure('ds', domain=mesh, subdomain_data=tags) [ext]; ``ds_(100)`` selects the facets tagged 100
+    (run_topo_opt_cantilever_beam.py:51-52).  Without subdomain data (or tag) it is the whole exterior boundary."""
+
+    def __init__(self, integral_type: str = "ds", domain=None, subdomain_data: Optional[MeshTags] = None,
+                 metadata=None, subdomain_id=None):
+        if integral_type != "ds":
+            raise NotImplementedError("Measure: only exterior facet integrals ('ds') are in the catalogue")
+        self.integral_type, self.mesh, self.subdomain_data = integral_type, domain, subdomain_data
+        self.metadata, self.subdomain_id = metadata, subdomain_id
+
+    def __call__(self, subdomain_id) -> "Measure":
+        return Measure(self.integral_type, self.mesh, self.subdomain_data, self.metadata, subdomain_id)
+
+    def facets(self) -> np.ndarray:
+        """(n, tdim) vertex ids of the facets the measure integrates over."""
+        tags = self.subdomain_data
+        if tags is not None and self.subdomain_id is not None:
+            return tags.entities[tags.find(self.subdomain_id)]
+        from .mesh import locate_entities_boundary
+        return locate_entities_boundary(self.mesh, self.mesh.tdim - 1, lambda x: np.ones(x.shape[1], dtype=bool))
+
+
+def _traction(t, mesh) -> np.ndarray:
+    tv = np.ravel(np.asarray(t.value if isinstance(t, Constant) else t, dtype=np.float64))
+    if tv.size != mesh.tdim:
+        raise ValueError(f"the traction needs {mesh.tdim} components")
+    return tv
+
+
+def _load_vec(mesh, facets: np.ndarray, t: np.ndarray) -> Vec:
+    """F = int_ds t . v ds on the device, cached per (facets, t)."""
+    cache = mesh.__dict__.setdefault("_elast_loads", {})
+    key = (id(_ctx()), hash(np.ascontiguousarray(facets, dtype=np.int32).tobytes()), tuple(t))
+    F = cache.get(key)
+    if F is None:
+        dev = elasticity_handle(mesh)
+        F = Vec(_ctx(), mesh.tdim * mesh.n_vert)
+        dev.set_facets(facets)
+        dev.load(t, F)
+        cache[key] = F
+    return F
+
+
+def _fixed_data(n_dof: int, bcs):
+    """(mask, values) of a bc list (first bc wins on duplicates); (None, None) without bcs."""
+    if not bcs:
+        return None, None
+    mask = np.zeros(n_dof, dtype=np.uint8)
+    vals = np.zeros(n_dof)
+    for bc in reversed(list(bcs)):
+        mask[bc.dofs] = 1
+        vals[bc.dofs] = np.asarray(bc.values(), dtype=np.float64)
+    return mask, vals
+
+
+# ------------------------------------------------------------------------------------------------------ operators ----
+class ElasticityMatrix:
+    """dR/du = K(rho); with ``masked`` the A of state_model.py:149 (identity rows / columns on the fixed dofs)."""
+    symmetric = True
+    pde_kind = None
+
+    def __init__(self, form: "ElasticityResidual", masked: bool = False):
+        self.form, self.masked, self.mesh = form, masked, form.mesh
+        self._row = None
+        self.info = None
+
+    def getSizes(self):
+        n = self.form.n_dof
+        return (n, n)
+
+    size = property(getSizes)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        dev = self.form.stiffness()
+        return dev.apply(x, y, masked=self.masked and dev.fixed_key is not None)
+
+    multTranspose = mult
+
+    def new_row_vec(self) -> Vec:
+        if self._row is None:
+            self._row = Vec(_ctx(), self.form.n_dof)
+        return self._row
+
+    new_col_vec = new_row_vec
+
+    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        o = options or {}
+        dev = self.form.stiffness()
+        self.info = dev.solve(b, x, rtol=o.get("elast_rtol", self.form.rtol), max_it=o.get("elast_max_it", 1_000_000))
+        self.form._record(self.info, "adjoint")
+
+    def to_scipy(self):
+        K = self.form.stiffness().export_csr()
+        if not self.masked or self.form._mask is None:
+            return K
+        import scipy.sparse as sp
+        free = sp.diags((self.form._mask == 0).astype(np.float64))
+        return (free @ K @ free + sp.diags(self.form._mask.astype(np.float64))).tocsr()
+
+
+class _ElasticityDrho:
+    """dR/drho (n_dof x n_cell), matrix free: column e = C'(rho_e) K0_e u_e."""
+
+    def __init__(self, form: "ElasticityResidual"):
+        self.form, self.mesh = form, form.mesh
+        self._row = self._col = None
+
+    def getSizes(self):
+        return (self.form.n_dof, self.mesh.n_cell)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        return F.device().drho(F.method_id, False, F.rho.vec, F.u.vec, x, y)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        return F.device().drho(F.method_id, True, F.rho.vec, F.u.vec, x, y)
+
+    def new_row_vec(self) -> Vec:
+        if self._row is None:
+            self._row = Vec(_ctx(), self.form.n_dof)
+        return self._row
+
+    def new_col_vec(self) -> Vec:
+        if self._col is None:
+            self._col = Vec(_ctx(), self.mesh.n_cell)
+        return self._col
+
+
+# ---------------------------------------------------------------------------------------------------------- forms ----
+class ElasticityResidual(BackendForm):
+    """R(u; rho) = K(rho) u - F(t) with the tagged traction ``ds`` (see the module docstring)."""
+    rank = 1
+    is_linear = True
+    is_symmetric = True
+    constant_partials = False
+
+    def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, E: float = 1.0,
+                 nu: float = 0.3, method: str = "SIMP"):
+        if not isinstance(u.function_space, VectorFunctionSpace):
+            raise NotImplementedError("ElasticityResidual needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
+        if rho.function_space.family != "DG" or rho.function_space.mesh is not u.function_space.mesh:
+            raise NotImplementedError("ElasticityResidual needs a DG0 density on the state's mesh")
+        if method not in METHODS:
+            raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
+        self.u, self.rho, self.mesh = u, rho, u.function_space.mesh
+        self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
+        self.t = _traction(traction, self.mesh)
+        self.ds = ds if ds is not None else Measure("ds", domain=self.mesh)
+        self.n_dof = u.function_space.dim
+        self.rtol = 1e-15
+        self._key = None
+        self._mask = None
+        self._vals = None
+        self._res = None
+        self._rhs_cache = None
+        self.last_info = {}
+
+    def functions(self):
+        return (self.u, self.rho)
+
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
+
+    def load(self) -> Vec:
+        return _load_vec(self.mesh, self.ds.facets(), self.t)
+
+    def _set_bcs(self, bcs) -> None:
+        mask, self._vals = _fixed_data(self.n_dof, bcs)
+        self._mask = mask
+
+    def stiffness(self) -> DeviceElasticity:
+        """The handle with K(rho) of the current density and this form's fixed set: reassembled when either changed."""
+        dev = self.device()
+        want = None if self._mask is None else hash(self._mask.tobytes())
+        if dev.fixed_key != want:
+            dev.set_fixed(self._mask)
+        key = (self.rho.version, id(self.rho.vec), dev.fixed_key, self.method_id, id(self))
+        if getattr(dev, "_owner", None) != key:
+            dev.assemble(self.method_id, self.rho.vec)
+            dev._owner = key
+        return dev
+
+    def _record(self, info, kind: str) -> None:
+        from .utils_hip import LAST_KSP_INFO
+        self.last_info[kind] = dict(iterations=info.iterations, converged=info.converged, solve_ms=info.solve_ms,
+                                    residual_norm=info.residual_norm, rhs_norm=info.rhs_norm)
+        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_" + kind))
+        if info.converged != 1:
+            raise RuntimeError(f"elasticity PCG did not converge ({kind}): {info.iterations} iterations, "
+                               f"sqrt(r.M^-1 r) = {info.residual_norm:.3e} of {info.rhs_norm:.3e}")
+
+    def new_matrix(self) -> ElasticityMatrix:
+        return ElasticityMatrix(self)
+
+    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
+        """R = K u - F, one launch (femo_elast_apply)."""
+        if out is None:
+            if self._res is None:
+                self._res = Vec(_ctx(), self.n_dof)
+            out = self._res
+        return self.stiffness().apply(self.u.vec, out, a=1.0, b=-1.0, f=self.load())
+
+    def partial_matrix(self, wrt: Function, out=None):
+        if wrt is self.u:
+            return out if isinstance(out, ElasticityMatrix) and not out.masked else ElasticityMatrix(self)
+        if wrt is self.rho:
+            return out if isinstance(out, _ElasticityDrho) else _ElasticityDrho(self)
+        raise ValueError("the elasticity residual does not depend on that Function")
+
+    def assemble_system(self, bcs, rhs: bool, out, out_nobc):
+        if rhs:
+            raise NotImplementedError("assembleSystem(rhs=True) for the elasticity form: use solveNonlinear / FEA.solve")
+        self._set_bcs(bcs)
+        self.stiffness()
+        A = out if isinstance(out, ElasticityMatrix) else ElasticityMatrix(self)
+        A.form, A.masked = self, True
+        if isinstance(out_nobc, ElasticityMatrix):
+            out_nobc.form, out_nobc.masked = self, False
+        return A, None
+
+    def _rhs(self, dev: DeviceElasticity) -> Vec:
+        """F with the Dirichlet lifting: b = F - K g, b = g on the fixed dofs."""
+        F = self.load()
+        if self._mask is None:
+            return F
+        nonzero = bool(np.any(self._vals[self._mask == 1] != 0.0))
+        key = (id(F), hash(self._mask.tobytes()))
+        if not nonzero and self._rhs_cache is not None and self._rhs_cache[0] == key:
+            return self._rhs_cache[1]
+        ctx = _ctx()
+        if nonzero:
+            g = Vec(ctx, self.n_dof).set(np.where(self._mask == 1, self._vals, 0.0))
+            b = Vec(ctx, self.n_dof)
+            dev.apply(g, b, a=-1.0, b=1.0, f=F)                   # F - K g
+            bh = np.array(b.get())
+        else:
+            bh = np.array(F.get())
+        bh[self._mask == 1] = self._vals[self._mask == 1]
+        bv = Vec(ctx, self.n_dof).set(bh)
+        if not nonzero:
+            self._rhs_cache = (key, bv)
+        return bv
+
+    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
+        """K(rho) u = F with the strongly imposed dofs: one PCG solve (the form is linear)."""
+        self._set_bcs(bcs)
+        dev = self.stiffness()
+        info = dev.solve(self._rhs(dev), func.vec, rtol=self.rtol)
+        func.version += 1
+        self._record(info, "state")
+        if report:
+            print(f"elasticity solve: {info.iterations} PCG iterations, {info.solve_ms:.1f} ms")
+
+
+class Compliance(BackendForm):
+    """J = int_ds t . u ds = F^T u (compliance, run_topo_opt_cantilever_beam.py:108-109)."""
+    rank = 0
+
+    def __init__(self, u: Function, traction, ds: Optional[Measure] = None):
+        if not isinstance(u.function_space, VectorFunctionSpace):
+            raise NotImplementedError("Compliance needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
+        self.u, self.mesh = u, u.function_space.mesh
+        self.t = _traction(traction, self.mesh)
+        self.ds = ds if ds is not None else Measure("ds", domain=self.mesh)
+        self._grad = None
+
+    def functions(self):
+        return (self.u,)
+
+    def load(self) -> Vec:
+        return _load_vec(self.mesh, self.ds.facets(), self.t)
+
+    def assemble_scalar(self) -> float:
+        return self.load().dot(self.u.vec, self.u.function_space.dim)
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        n = wrt.function_space.dim
+        if out is None:
+            if self._grad is None or self._grad.n != n:
+                self._grad = Vec(_ctx(), n)
+            out = self._grad
+        if wrt is self.u:
+            return out.copy_from(self.load())
+        return out.fill(0.0)
+
+
+def cell_volumes(mesh) -> np.ndarray:
+    """|T_e| of every simplex."""
+    p = mesh.x[mesh.conn]
+    J = p[:, 1:, :] - p[:, :1, :]
+    fact = 2.0 if mesh.tdim == 2 else 6.0
+    return np.abs(np.linalg.det(J)) / fact
+
+
+def averageFunc(func: Function) -> LinearFunctional:
+    """(1/|Omega|) int func dx for a DG0 Function (averageFunc, run_topo_opt_cantilever_beam.py:103-106)."""
+    V = func.function_space
+    if V.family != "DG":
+        raise NotImplementedError("averageFunc needs a DG0 Function")
+    vol = cell_volumes(V.mesh)
+    coeff = Function(FunctionSpace(V.mesh, ("DG", 0)))
+    coeff.vector[:] = vol / vol.sum()
+    return LinearFunctional(coeff, func)
+
+
+# ---------------------------------------------------------------------------- builders of the run script (:85-109) ----
+def pdeRes(u, v, rho_e, f, E: float = 1.0, dss: Optional[Measure] = None, method: str = "SIMP") -> ElasticityResidual:
+    """run_topo_opt_cantilever_beam.py:85-101 (nu = 0.3 as there); ``v`` is implied by the catalogue."""
+    return ElasticityResidual(u, rho_e, f, dss, E=E, nu=0.3, method=method)
+
+
+def compliance(u, f, dss: Optional[Measure] = None) -> Compliance:
+    """run_topo_opt_cantilever_beam.py:108-109"""
+    return Compliance(u, f, dss)

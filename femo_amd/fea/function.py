@@ -45,6 +45,58 @@ class FunctionSpace:
     __hash__ = object.__hash__
 
 
+class VectorFunctionSpace:
+    """dolfinx ``VectorFunctionSpace(mesh, ("CG", 1))`` [ext] on a 2-D or 3-D simplex mesh: d = tdim components per vertex in
+    the blocked layout dolfinx uses (bs = d): dof = d * vertex + component, which is also the order ``getFuncArray``
+    hands to CSDL (run_topo_opt_cantilever_beam.py:108-110).  The scalar ``FunctionSpace`` is left as it is."""
+
+    def __init__(self, mesh, element=("CG", 1)):
+        family, degree = element
+        if (family, degree) not in (("CG", 1), ("Lagrange", 1)):
+            raise NotImplementedError(f"vector function space {element}: only ('CG', 1) is implemented")
+        if getattr(mesh, "tdim", None) not in (2, 3) or getattr(mesh, "gdim", mesh.tdim) != mesh.tdim \
+                or mesh.conn.shape[1] != mesh.tdim + 1:
+            raise NotImplementedError("VectorFunctionSpace needs a 2-D or 3-D simplex Mesh")
+        self.mesh = mesh
+        self.family = "CGV"
+        self.degree = 1
+        self.bs = mesh.tdim
+        self.num_sub_spaces = mesh.tdim
+
+    @property
+    def dim(self) -> int:
+        return self.bs * self.mesh.n_vert
+
+    def tabulate_dof_coordinates(self) -> np.ndarray:
+        """One row per vertex (the block), as dolfinx tabulates a blocked space."""
+        return self.mesh.x
+
+    def sub(self, i: int) -> "_SubSpace":
+        if not 0 <= i < self.bs:
+            raise IndexError(f"component {i} of a {self.bs}-component space")
+        return _SubSpace(self, i)
+
+    def __eq__(self, other):
+        return isinstance(other, VectorFunctionSpace) and other.mesh is self.mesh
+
+    __hash__ = object.__hash__
+
+
+class _SubSpace:
+    """``V.sub(i)``: component i of a VectorFunctionSpace; ``dofs`` are its dofs in the parent's numbering."""
+
+    def __init__(self, parent: VectorFunctionSpace, i: int):
+        self.parent, self.component = parent, int(i)
+        self.mesh = parent.mesh
+
+    @property
+    def dofs(self) -> np.ndarray:
+        return (np.arange(self.mesh.n_vert, dtype=np.int32) * self.parent.bs + self.component).astype(np.int32)
+
+    def tabulate_dof_coordinates(self) -> np.ndarray:
+        return self.mesh.x
+
+
 class _VectorView:
     """PETSc-Vec-flavoured access to a Function's device vector."""
 

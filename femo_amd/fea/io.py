@@ -38,7 +38,17 @@ class XDMFRecorder:
         if self._mesh is None:
             raise RuntimeError("write_mesh must be called before write_function")
         a = np.ascontiguousarray(function.vector.getArray(), dtype="<f8")
-        _, n_vert, n_cell = self._mesh
+        tdim, n_vert, n_cell = self._mesh
+        bs = getattr(getattr(function, "function_space", None), "bs", 1)
+        if bs > 1 and a.size == bs * n_vert:
+            # vector CG1 field (VectorFunctionSpace): one XYZ triple per vertex, padded with zeros in 2-D
+            v = np.zeros((n_vert, 3), dtype="<f8")
+            v[:, :bs] = a.reshape(n_vert, bs)
+            fname = f"{self.stem}_{len(self._steps):05d}.bin"
+            v.tofile(fname)
+            self._steps.append((float(t), getattr(function, "name", None) or "f", os.path.basename(fname), "Node", f"{n_vert} 3"))
+            self._flush()
+            return
         if a.size == n_vert:
             centre = "Node"
         elif a.size == n_cell:
@@ -68,8 +78,9 @@ class XDMFRecorder:
         else:
             out.append('  <Grid Name="TimeSeries" GridType="Collection" CollectionType="Temporal">')
             for t, name, fname, centre, count in self._steps:
+                kind_attr = "Vector" if isinstance(count, str) else "Scalar"
                 out.append(f'   <Grid Name="{name}" GridType="Uniform"><Time Value="{t!r}"/>{topo}{geo}'
-                           f'<Attribute Name="{name}" AttributeType="Scalar" Center="{centre}"><DataItem Format="Binary" '
+                           f'<Attribute Name="{name}" AttributeType="{kind_attr}" Center="{centre}"><DataItem Format="Binary" '
                            f'DataType="Float" Precision="8" Endian="Little" Dimensions="{count}">{fname}</DataItem>'
                            f'</Attribute></Grid>')
             out.append('  </Grid>')

@@ -314,4 +314,30 @@ def locate_dofs_geometrical(V, marker: Callable[[np.ndarray], np.ndarray]) -> np
     x = V.tabulate_dof_coordinates()
     xt = np.zeros((3, x.shape[0]))
     xt[:x.shape[1]] = x.T
-    return np.nonzero(np.asarray(marker(xt), dtype=bool))[0].astype(np.int32)
+    hit = np.nonzero(np.asarray(marker(xt), dtype=bool))[0].astype(np.int32)
+    if hasattr(V, "component"):                      # V.sub(i) of a vector space: that component of the matching vertices
+        return (hit * V.parent.bs + V.component).astype(np.int32)
+    bs = getattr(V, "bs", 1)
+    if bs > 1:                                       # vector space: every component of the matching vertices
+        return (hit[:, None] * bs + np.arange(bs, dtype=np.int32)[None, :]).ravel().astype(np.int32)
+    return hit
+
+
+def locate_entities_boundary(mesh: Mesh, dim: int, marker: Callable[[np.ndarray], np.ndarray]) -> np.ndarray:
+    """dolfinx.mesh.locate_entities_boundary [ext] for the facets (dim = tdim - 1) of a simplex mesh: the exterior facets
+    all of whose vertices satisfy ``marker`` (coordinates as (3, n)).  A facet is named by its vertices: the result is an
+    (n_facets, tdim) int32 array in ascending (cell, local facet) order (run_topo_opt_cantilever_beam.py:44-45)."""
+    if dim != mesh.tdim - 1:
+        raise NotImplementedError("locate_entities_boundary: only facets (dim = tdim - 1) are implemented")
+    xt = np.zeros((3, mesh.n_vert))
+    xt[:mesh.tdim] = mesh.x.T
+    ok = np.asarray(marker(xt), dtype=bool)
+    mask = mesh.boundary_facet_mask()
+    out = []
+    for c in np.nonzero(mask)[0]:
+        for k in range(mesh.tdim + 1):
+            if (mask[c] >> k) & 1:
+                fv = np.delete(mesh.conn[c], k)
+                if ok[fv].all():
+                    out.append(np.sort(fv))
+    return np.asarray(out, dtype=np.int32).reshape(-1, mesh.tdim)

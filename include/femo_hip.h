@@ -41,6 +41,8 @@ typedef struct femo_mesh femo_mesh;  /* P1 simplex mesh + vertex->cell incidence
 typedef struct femo_bc   femo_bc;    /* strong Dirichlet set (fea_dolfinx.py:169-176 add_strong_bc)   */
 typedef struct femo_mat  femo_mat;   /* N x N sparse matrix on the mesh pattern (PETSc Mat)           */
 typedef struct femo_shell femo_shell; /* Reissner-Mindlin shell space CG2^3 x CG1^3 on a triangulated surface (below) */
+typedef struct femo_elast femo_elast; /* vector CG1 linear elasticity with a DG0 density (SIMP / RAMP), below         */
+typedef struct femo_filter femo_filter; /* DG0 density filter W (and W^T) built on the device, below                 */
 
 /* closed catalogue of residual forms (UFL is not available) */
 enum femo_pde_kind {
@@ -572,6 +574,60 @@ int femo_shell_set_partition(femo_shell* s, const uint8_t* owned_points, int n_n
 int femo_shell_set_owned_cells(femo_shell* s, const uint8_t* owned_cells);
 int femo_shell_halo(femo_shell* s, femo_vec* x);
 int femo_shell_mask_unowned(femo_shell* s, femo_vec* x);
+
+/* ---- SIMP topology optimisation (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py) ------------------------------
+ * Linear elasticity on the P1 simplices of a femo_mesh: state u in VectorFunctionSpace(mesh, ("CG", 1)), blocked dofs
+ * dof = d * vertex + component (d = tdim), one DG0 density rho_e per cell.
+ *   R(u; rho) = sum_e C(rho_e) int_e sigma_0(u) : eps(v) dx - int_ds t . v ds            (pdeRes, :85-101)
+ *   C = rho^3 (FEMO_ELAST_SIMP) or rho / (1 + 8 (1 - rho)) (FEMO_ELAST_RAMP); sigma_0 = lambda_0 tr(eps) I + 2 mu_0 eps
+ * K(rho) is stored as one d x d fp64 block per entry of the mesh's scalar SELL pattern (the column index is shared with the
+ * scalar operators), assembled vertex by vertex without atomics, so K is deterministic and symmetric entry for entry.
+ * Single GPU only: a mesh with a halo plan is refused.                                                                   */
+enum { FEMO_ELAST_SIMP = 0, FEMO_ELAST_RAMP = 1 };
+enum { FEMO_ELAST_INFO_DIM = 0, FEMO_ELAST_INFO_NDOF = 1, FEMO_ELAST_INFO_NNZ = 2, FEMO_ELAST_INFO_SELL = 3,
+       FEMO_ELAST_INFO_SPMV_BYTES = 4, FEMO_ELAST_INFO_COUNT = 5 };
+/* FEA(mesh) + VectorFunctionSpace(mesh, ("CG", 1)) with E, nu of pdeRes (:85-93)                                        */
+int femo_elast_create(femo_mesh* mesh, double E, double nu, femo_elast** out);
+int femo_elast_destroy(femo_elast* e);
+/* [dim, n_dof, nnz of the scalar pattern, SELL entries, bytes one block SpMV moves: nnz (4 + 8 d^2) + n_vert 16 d + rowptr] */
+int femo_elast_info(const femo_elast* e, int64_t info[FEMO_ELAST_INFO_COUNT]);
+/* Strong Dirichlet dofs (fea.add_strong_bc, :152-156): mask[n_dof] = 1 on fixed dofs; NULL clears.  Used by the masked
+ * products (identity rows and columns) and by the block-Jacobi inverse of the next femo_elast_assemble.                  */
+int femo_elast_set_fixed(femo_elast* e, const uint8_t* mask);
+/* Tagged boundary facets of ds_(100) (locate_entities_boundary + meshtags, :44-52): d vertex ids per facet.             */
+int femo_elast_set_facets(femo_elast* e, int64_t n_facets, const int32_t* facet_verts);
+/* K(rho) (dolfinx assemble_matrix of derivative(pdeRes, u), fea_dolfinx.py / state_model.py:117-158) and the inverted
+ * diagonal blocks of the preconditioner (rows / columns of fixed dofs replaced by the identity).                         */
+int femo_elast_assemble(femo_elast* e, int method, const femo_vec* rho);
+/* y = a K x + b f  (masked = 0) or  y = a A x + b f  with A = K with identity rows / columns on the fixed dofs (masked = 1,
+ * the A of state_model.py:149).  f may be NULL (b ignored).  a = 1, b = -1 gives the residual R = K u - F of
+ * assembleVector(pdeRes) in the same launch (state_model.py:75-85).                                                     */
+int femo_elast_apply(femo_elast* e, int masked, double a, const femo_vec* x, double b, const femo_vec* f, femo_vec* y);
+/* F = int_ds t . v ds for a constant traction t[d] (Constant(mesh, (0, -1/4)), :73): t |f| / d per facet vertex.       */
+int femo_elast_load(femo_elast* e, const double* t, femo_vec* F);
+/* dR/drho (assemble_matrix of derivative(pdeRes, rho)), column e = C'(rho_e) K0_e u_e, matrix free:
+ *   transpose = 1:  y[n_cell] (+)= C'(rho_e) x_e^T K0_e u_e       (state_model.py:190-200, rev mode)
+ *   transpose = 0:  y[n_dof]  (+)= sum_e C'(rho_e) x_e K0_e u_e   (state_model.py:176-188, fwd mode; vertex walk)     */
+int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rho, const femo_vec* u, const femo_vec* x,
+                    femo_vec* y, int accumulate);
+/* A x = b by device-resident PCG with the block-Jacobi preconditioner (solveKSP_mumps, utils_dolfinx.py:476-493); K is
+ * symmetric, so the adjoint solve is the same call.  Fixed dofs: x = b there.  Stops on sqrt(r^T M^-1 r) <=
+ * max(rtol sqrt(r0^T M^-1 r0), atol); convergence is polled every check_every iterations.  opts->pc is ignored.         */
+int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info);
+/* K as block CSR on the scalar pattern of femo_mesh_pattern_csr: val[nnz * d * d], block (row comp, col comp) row-major. */
+int femo_elast_export_csr(const femo_elast* e, int64_t* rowptr, int32_t* col, double* val);
+/* reps block SpMV launches (unmasked) timed with device events: mean ms per launch.                                      */
+int femo_elast_bench_spmv(femo_elast* e, const femo_vec* x, femo_vec* y, int reps, double* ms);
+/* GeneralFilterOperation (pre_processor/general_filter_model.py): W_ij = (r - d_ij) / sum_k (r - d_ik) over the points j
+ * with d_ij <= r, r = beta h_avg, from n points in dim dimensions (the DG0 dof coordinates).  Built on the device: uniform
+ * hash grid of cell size >= r, count / scan / fill, rows sorted by column; W^T is kept as its own CSR.                   */
+int femo_filter_create(femo_ctx* ctx, int dim, int64_t n, const double* coords, double radius, femo_filter** out);
+int femo_filter_destroy(femo_filter* f);
+int femo_filter_nnz(const femo_filter* f, int64_t* nnz);
+/* y = W x (transpose = 0, compute: weight_mtx.dot) or y = W^T x (transpose = 1, the rev product)                      */
+int femo_filter_apply(femo_filter* f, int transpose, const femo_vec* x, femo_vec* y);
+/* the rows / cols / val that declare_derivatives('density', 'density_unfiltered', ...) is given (CSR of W or W^T)     */
+int femo_filter_export_csr(const femo_filter* f, int transpose, int64_t* rowptr, int32_t* col, double* val);
 
 #ifdef __cplusplus
 }

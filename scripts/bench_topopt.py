@@ -1,0 +1,150 @@
+"""One SIMP design cycle of examples/beam_topo_opt on the HIP engine, timed: filter -> state solve -> compliance ->
+adjoint -> W^T, through FEAModel + GeneralFilterModel + Simulator (host values, like a CSDL backend).  Prints one JSON
+line: ms per cycle (wall clock between two device synchronisations), PCG iterations of the forward and adjoint solves, block-SpMV time
+and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the same size timed beside it.
+
+  python scripts/bench_topopt.py --nelx 640 --nely 320          (2-D cantilever, the reference's driver at that size)
+  python scripts/bench_topopt.py --n3 48                        (3-D unit cube, clamped at x = 0, load on x = 1)
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK_BYTES_PER_S = 8.0e12
+
+
+def build(args):
+    from femo_amd.csdl_opt.fea_model import FEAModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.simulator import Simulator
+    from femo_amd.fea.elasticity import averageFunc, compliance, pdeRes
+    from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, Measure, VectorFunctionSpace,
+                                      createRectangleMesh, createUnitCubeMesh, locate_dofs_geometrical,
+                                      locate_entities_boundary, meshSize, meshtags)
+    if args.n3:
+        mesh = createUnitCubeMesh(args.n3)
+        marker = lambda x: np.logical_and(np.isclose(x[0], 1.0), x[2] < 0.25)
+        t = (0.0, 0.0, -1.0)
+    else:
+        LX, LY = 160.0, 80.0
+        mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([LX, LY]), args.nelx, args.nely)
+        marker = lambda x: np.logical_and(abs(x[1] - LY / 2) < LY / args.nely + 3e-6, abs(x[0] - LX) < 3e-6)
+        t = (0.0, -0.25)
+    d = mesh.tdim
+    facets = locate_entities_boundary(mesh, d - 1, marker)
+    ds_ = Measure("ds", domain=mesh, subdomain_data=meshtags(mesh, d - 1, facets, np.full(len(facets), 100, dtype=np.int32)))
+    fea = FEA(mesh)
+    fea.REPORT = False
+    Q, V = FunctionSpace(mesh, ("DG", 0)), VectorFunctionSpace(mesh, ("CG", 1))
+    rho, u = Function(Q), Function(V)
+    f = Constant(mesh, t)
+    res = pdeRes(u, None, rho, f, dss=ds_(100))
+    fea.add_input("density", rho)
+    fea.add_state(name="displacements", function=u, residual_form=res, arguments=["density"])
+    fea.add_output(name="avg_density", type="scalar", form=averageFunc(rho), arguments=["density"])
+    fea.add_output(name="compliance", type="scalar", form=compliance(u, f, dss=ds_(100)), arguments=["displacements"])
+    ubc = Function(V)
+    ubc.vector.set(0.0)
+    fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), lambda x: np.isclose(x[0], 0.0, atol=1e-6))], V)
+    model = FEAModel(fea=[fea])
+    h = meshSize(mesh)
+    t0 = time.perf_counter()
+    fm = GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2)
+    model.add(fm, name="general_filter_model")
+    model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.random.default_rng(0).random(mesh.n_cell) * 0.86)
+    sim = Simulator(model)                                      # defines the filter operation: W, W^T built here
+    from femo_amd.fea.utils_hip import get_context
+    get_context().sync()
+    filter_build_ms = (time.perf_counter() - t0) * 1e3
+    return sim, mesh, res, facets, t, filter_build_ms
+
+
+def scipy_cycle(mesh, facets, t, x0, radius):
+    """The same cycle with SciPy: KD-tree filter, element-by-element assembly, spsolve forward and adjoint."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+    from scipy.spatial import cKDTree
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import elasticity_ref as ref
+    t0 = time.perf_counter()
+    c = mesh.centroids()
+    pairs = cKDTree(c).query_pairs(radius, output_type="ndarray")
+    i = np.concatenate([pairs[:, 0], pairs[:, 1], np.arange(len(c))])
+    j = np.concatenate([pairs[:, 1], pairs[:, 0], np.arange(len(c))])
+    w = radius - np.linalg.norm(c[i] - c[j], axis=1)
+    W = sp.csr_matrix((w, (i, j)), shape=(len(c),) * 2)
+    W = sp.diags(1.0 / np.asarray(W.sum(axis=1)).ravel()) @ W
+    rho = W @ x0
+    d = mesh.tdim
+    # the element matrix of every cell from the restatement (vectorised over cells by the shape of its formula)
+    K0 = ref.element_matrices(mesh.x, mesh.conn)
+    K = ref.stiffness(mesh.x, mesh.conn, rho, K0=K0)
+    F = ref.traction_load(mesh.x, facets, t)
+    fixed_v = np.nonzero(np.isclose(mesh.x[:, 0], 0.0))[0]
+    fixed = (fixed_v[:, None] * d + np.arange(d)).ravel()
+    free = np.setdiff1d(np.arange(K.shape[0]), fixed)
+    Kff = K[free][:, free].tocsc()
+    u = np.zeros(K.shape[0])
+    u[free] = spla.spsolve(Kff, F[free])
+    lam = np.zeros(K.shape[0])
+    lam[free] = spla.spsolve(Kff, F[free])
+    g = W.T @ (-ref.compliance_gradient(mesh.x, mesh.conn, rho, u, lam, K0=K0))
+    return (time.perf_counter() - t0) * 1e3, float(F @ u), g
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nelx", type=int, default=80)
+    ap.add_argument("--nely", type=int, default=40)
+    ap.add_argument("--n3", type=int, default=0)
+    ap.add_argument("--cycles", type=int, default=3)
+    ap.add_argument("--no-scipy", action="store_true")
+    args = ap.parse_args()
+    from femo_amd import _lib
+    from femo_amd.engine import Context, Vec
+    from femo_amd.fea import utils_hip
+    if _lib.device_count() < 1:
+        raise SystemExit("bench_topopt needs a HIP device")
+    ctx = Context(0)
+    utils_hip.set_context(ctx)
+    sim, mesh, res, facets, t, filter_build_ms = build(args)
+    x0 = np.array(sim["density_unfiltered"])
+    times = []
+    for k in range(args.cycles + 1):
+        sim["density_unfiltered"] = x0 * (1.0 - 1e-3 * k)
+        ctx.sync()
+        t0 = time.perf_counter()
+        sim.run()
+        g = np.asarray(sim.compute_totals("compliance", "density_unfiltered"))
+        ctx.sync()
+        if k > 0:
+            times.append((time.perf_counter() - t0) * 1e3)
+    dev = res.stiffness()
+    xv, yv = Vec(ctx, dev.n_dof).set(np.random.default_rng(1).standard_normal(dev.n_dof)), Vec(ctx, dev.n_dof)
+    spmv_ms = dev.bench_spmv(xv, yv, 50)
+    info = res.last_info
+    out = dict(metric="topopt_cycle", mesh=(f"cube n={args.n3}" if args.n3 else f"rect {args.nelx}x{args.nely}"),
+               n_dof=dev.n_dof, n_cell=mesh.n_cell, cycle_ms=float(np.median(times)), cycle_ms_all=[float(v) for v in times],
+               pcg_iterations_forward=info["state"]["iterations"], pcg_iterations_adjoint=info["adjoint"]["iterations"],
+               spmv_ms=spmv_ms, spmv_bytes=dev.info["spmv_bytes"],
+               spmv_share_of_8TBps=dev.info["spmv_bytes"] / (spmv_ms * 1e-3) / PEAK_BYTES_PER_S,
+               filter_build_ms=filter_build_ms, compliance=float(sim["compliance"][0]))
+    if not args.no_scipy:
+        h = np.asarray(__import__("femo_amd.fea.mesh", fromlist=["meshSize"]).meshSize(mesh))
+        sc_ms, sc_J, sc_g = scipy_cycle(mesh, facets, t, np.array(sim["density_unfiltered"]), 2.0 * (h.max() + h.min()) / 2)
+        out.update(scipy_spsolve_cycle_ms=sc_ms, scipy_rel_diff_compliance=abs(sc_J - out["compliance"]) / abs(sc_J),
+                   scipy_rel_diff_gradient=float(np.abs(sc_g - g).max() / np.abs(sc_g).max()))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

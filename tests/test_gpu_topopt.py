@@ -1,0 +1,291 @@
+"""GPU tests of SIMP topology optimisation (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py on the HIP engine):
+block assembly against the restatement (tests/elasticity_ref.py), answers that need no restatement (rigid-body modes,
+patch test), the 80 x 40 cantilever through FEAModel + GeneralFilterModel + Simulator, the total derivative, exact
+transposes, the device-built filter, and (slow) the full-size meshes."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import elasticity_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+L_X, L_Y = 160.0, 80.0
+
+
+@pytest.fixture
+def gpu(ctx):
+    from femo_amd.fea import utils_hip
+    utils_hip.set_context(ctx)
+    return ctx
+
+
+def _meshes():
+    from femo_amd.fea.mesh import createRectangleMesh, createUnitCubeMesh, createUnitSquareMesh
+    return {"rect8x4": lambda: createRectangleMesh([0.0, 0.0], [2.0, 1.0], 8, 4),
+            "square9j": lambda: createUnitSquareMesh(9, 0.25),
+            "cube4": lambda: createUnitCubeMesh(4),
+            "cube4j": lambda: createUnitCubeMesh(4, 0.2)}
+
+
+def _device_K(mesh, rho, method, E=1.0, nu=0.3):
+    from femo_amd.engine import Vec
+    from femo_amd.fea.elasticity import METHODS, DeviceElasticity
+    from femo_amd.fea.utils_hip import get_context
+    dev = DeviceElasticity(get_context(), mesh, E, nu)
+    rv = Vec(get_context(), mesh.n_cell).set(rho)
+    dev.assemble(METHODS[method], rv)
+    return dev, rv
+
+
+@pytest.mark.parametrize("name", ["rect8x4", "square9j", "cube4", "cube4j"])
+@pytest.mark.parametrize("method", ["SIMP", "RAMP"])
+def test_assembly_parity(gpu, name, method):
+    mesh = _meshes()[name]()
+    rho = np.random.default_rng(7).uniform(1e-3, 1.0, mesh.n_cell)
+    dev, _ = _device_K(mesh, rho, method)
+    K = dev.export_csr()
+    Kr = ref.stiffness(mesh.x, mesh.conn, rho, method)
+    d = mesh.tdim
+    # same block pattern as the scalar operator pattern
+    rowptr, col = mesh.device(gpu).pattern_csr()
+    assert K.nnz == col.size * d * d
+    K.sort_indices(); Kr.sort_indices()
+    assert np.array_equal(K.indptr, Kr.indptr) and np.array_equal(K.indices, Kr.indices)
+    assert abs(K - Kr).max() <= 1e-12 * abs(Kr).max()
+    assert (K != K.T).nnz == 0                                  # symmetric entry for entry
+
+
+@pytest.mark.parametrize("name", ["square9j", "cube4j"])
+def test_rigid_body_modes(gpu, name):
+    from femo_amd.engine import Vec
+    mesh = _meshes()[name]()
+    rho = np.random.default_rng(3).uniform(1e-3, 1.0, mesh.n_cell)
+    dev, _ = _device_K(mesh, rho, "SIMP")
+    R = ref.rigid_body_modes(mesh.x)
+    nK = abs(dev.export_csr()).sum(axis=1).max()
+    x, y = Vec(gpu, dev.n_dof), Vec(gpu, dev.n_dof)
+    for k in range(R.shape[1]):
+        x.set(R[:, k])
+        dev.apply(x, y)
+        assert np.linalg.norm(y.get()) <= 1e-12 * nK * np.linalg.norm(R[:, k])
+
+
+@pytest.mark.parametrize("name", ["square9j", "cube4j"])
+def test_patch_test(gpu, name):
+    """u = A x + b on every boundary vertex: the solved interior is the same linear field.  The density is a random
+    constant: a linear field has constant stress, which is in equilibrium only where C(rho) does not jump."""
+    from femo_amd.fea.elasticity import ElasticityResidual, Measure
+    from femo_amd.fea.function import Function, FunctionSpace, VectorFunctionSpace
+    from femo_amd.fea.utils_hip import dirichletbc
+    mesh = _meshes()[name]()
+    d = mesh.tdim
+    rng = np.random.default_rng(11)
+    A, b = rng.standard_normal((d, d)), rng.standard_normal(d)
+    exact = (mesh.x @ A.T + b).ravel()
+    V, Q = VectorFunctionSpace(mesh), FunctionSpace(mesh, ("DG", 0))
+    u, rho = Function(V), Function(Q)
+    rho.vector[:] = np.full(mesh.n_cell, rng.uniform(1e-2, 1.0))
+    bverts = np.nonzero(np.any((mesh.x < 1e-9) | (mesh.x > 1 - 1e-9), axis=1))[0]
+    dofs = (bverts[:, None] * d + np.arange(d)).ravel()
+    g = Function(V)
+    g.vector[:] = exact
+    form = ElasticityResidual(u, rho, np.zeros(d), Measure("ds", domain=mesh))
+    form.solve_state(u, [dirichletbc(g, dofs, V)])
+    assert np.abs(u.vector.getArray() - exact).max() <= 1e-10 * np.abs(exact).max()
+
+
+def build_cantilever(nelx=80, nely=40, device=False, method="SIMP", seed=0):
+    """run_topo_opt_cantilever_beam.py:30-178 on the HIP mirror (the optimiser itself is out of scope)."""
+    from femo_amd.csdl_opt.fea_model import FEAModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.simulator import Simulator
+    from femo_amd.fea.elasticity import averageFunc, compliance, pdeRes
+    from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, Measure, TestFunction, VectorFunctionSpace,
+                                      createRectangleMesh, locate_dofs_geometrical, locate_entities_boundary, meshSize,
+                                      meshtags)
+    mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([L_X, L_Y]), nelx, nely)
+    DOLFIN_EPS = 3e-16
+
+    def TractionBoundary(x):
+        return np.logical_and(abs(x[1] - L_Y / 2) < L_Y / nely + DOLFIN_EPS * 1e10, abs(x[0] - L_X) < DOLFIN_EPS * 1e10)
+
+    fdim = mesh.tdim - 1
+    traction_facets = locate_entities_boundary(mesh, fdim, TractionBoundary)
+    facet_tag = meshtags(mesh, fdim, traction_facets, np.full(len(traction_facets), 100, dtype=np.int32))
+    ds_ = Measure('ds', domain=mesh, subdomain_data=facet_tag, metadata={"quadrature_degree": 4})
+    fea = FEA(mesh)
+    fea.REPORT = False
+    Q = FunctionSpace(mesh, ('DG', 0))
+    rho_fn = Function(Q)
+    V = VectorFunctionSpace(mesh, ('CG', 1))
+    u_fn = Function(V)
+    f = Constant(mesh, (0, -1 / 4))
+    res = pdeRes(u_fn, TestFunction(V), rho_fn, f, dss=ds_(100), method=method)
+    fea.add_input('density', rho_fn)
+    fea.add_state(name='displacements', function=u_fn, residual_form=res, arguments=['density'])
+    fea.add_output(name='avg_density', type='scalar', form=averageFunc(rho_fn), arguments=['density'])
+    fea.add_output(name='compliance', type='scalar', form=compliance(u_fn, f, dss=ds_(100)), arguments=['displacements'])
+    ubc = Function(V)
+    ubc.vector.set(0.0)
+    fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), lambda x: np.isclose(x[0], 0., atol=1e-6))], V)
+    fea_model = FEAModel(fea=[fea])
+    h = meshSize(mesh)
+    nel = mesh.n_cell
+    fea_model.add(GeneralFilterModel(nel=nel, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
+                  name='general_filter_model')
+    rng = np.random.default_rng(seed)
+    fea_model.create_input('density_unfiltered', shape=nel, val=rng.random(nel) * 0.86)
+    fea_model.add_design_variable('density_unfiltered', upper=1.0, lower=1e-4)
+    fea_model.add_objective('compliance')
+    fea_model.add_constraint('avg_density', upper=0.40)
+    sim = Simulator(fea_model, device=device)
+    return sim, fea, mesh, dict(facets=traction_facets, h_avg=(h.max() + h.min()) / 2, res=res)
+
+
+def _reference_cycle(mesh, facets, h_avg, x0, method="SIMP"):
+    W = ref.filter_matrix(mesh.centroids(), 2.0 * h_avg)
+    rho = W @ x0
+    K0 = ref.element_matrices(mesh.x, mesh.conn)
+    K = ref.stiffness(mesh.x, mesh.conn, rho, method, K0=K0)
+    F = ref.traction_load(mesh.x, facets, (0.0, -0.25))
+    fixed_v = np.nonzero(np.isclose(mesh.x[:, 0], 0.0))[0]
+    fixed = np.concatenate([2 * fixed_v, 2 * fixed_v + 1])
+    u = ref.solve_fixed(K, F, fixed)
+    vol = ref.cell_volumes(mesh.x, mesh.conn)
+    dJ_drho = -ref.compliance_gradient(mesh.x, mesh.conn, rho, u, u, method, K0=K0)
+    return dict(W=W, rho=rho, u=u, J=F @ u, avg=vol @ rho / vol.sum(), grad=W.T @ dJ_drho, K=K, F=F, fixed=fixed)
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_cantilever_cycle(gpu, device):
+    sim, fea, mesh, aux = build_cantilever(device=device)
+    sim.run()
+    x0 = np.array(sim['density_unfiltered'])
+    R = _reference_cycle(mesh, aux['facets'], aux['h_avg'], x0)
+    assert np.abs(np.asarray(sim['density']) - R['rho']).max() <= 1e-14
+    u = np.asarray(sim['displacements'])
+    assert np.abs(u - R['u']).max() <= 1e-9 * np.abs(R['u']).max()
+    assert abs(float(sim['compliance'][0]) - R['J']) <= 1e-9 * abs(R['J'])
+    assert abs(float(sim['avg_density'][0]) - R['avg']) <= 1e-14
+    g = np.asarray(sim.compute_totals('compliance', 'density_unfiltered'))
+    assert np.abs(g - R['grad']).max() <= 1e-8 * np.abs(R['grad']).max()
+    ga = np.asarray(sim.compute_totals('avg_density', 'density_unfiltered'))
+    vol = ref.cell_volumes(mesh.x, mesh.conn)
+    assert np.abs(ga - R['W'].T @ (vol / vol.sum())).max() <= 1e-14 * np.abs(ga).max() * 10
+    info = aux['res'].last_info
+    print(f"80x40 cantilever: state PCG {info['state']['iterations']} it, adjoint {info['adjoint']['iterations']} it")
+    if not device:
+        chk = sim.check_totals('compliance', 'density_unfiltered', step=1e-4, n_dir=3, seed=0)
+        assert max(chk['rel_error']) <= 1e-6, chk
+
+
+def test_transposes(gpu):
+    from femo_amd.engine import Vec
+    from femo_amd.fea.elasticity import METHODS, DeviceFilter
+    from femo_amd.fea.mesh import createUnitCubeMesh, createUnitSquareMesh
+    rng = np.random.default_rng(5)
+    for mesh in (createUnitSquareMesh(12, 0.2), createUnitCubeMesh(4, 0.2)):
+        for method in ("SIMP", "RAMP"):
+            rho = rng.uniform(1e-2, 1.0, mesh.n_cell)
+            dev, rv = _device_K(mesh, rho, method)
+            n = dev.n_dof
+            u, v, w = Vec(gpu, n).set(rng.standard_normal(n)), Vec(gpu, n).set(rng.standard_normal(n)), Vec(gpu, mesh.n_cell).set(rng.standard_normal(mesh.n_cell))
+            Jw, JTv = Vec(gpu, n), Vec(gpu, mesh.n_cell)
+            dev.drho(METHODS[method], False, rv, u, w, Jw)
+            dev.drho(METHODS[method], True, rv, u, v, JTv)
+            a, b = v.dot(Jw), JTv.dot(w)
+            assert abs(a - b) <= 1e-13 * np.linalg.norm(v.get()) * np.linalg.norm(Jw.get())
+            # against the restatement's column formula
+            g = ref.compliance_gradient(mesh.x, mesh.conn, rho, u.get(), v.get(), method)
+            assert np.abs(JTv.get() - g).max() <= 1e-12 * np.abs(g).max()
+        c = mesh.centroids()
+        F = DeviceFilter(gpu, c, 2.5 / mesh.n)
+        x, y = Vec(gpu, mesh.n_cell).set(rng.standard_normal(mesh.n_cell)), Vec(gpu, mesh.n_cell).set(rng.standard_normal(mesh.n_cell))
+        Wx, WTy = Vec(gpu, mesh.n_cell), Vec(gpu, mesh.n_cell)
+        F.apply(x, Wx)
+        F.apply(y, WTy, transpose=True)
+        assert abs(y.dot(Wx) - WTy.dot(x)) <= 1e-13 * np.linalg.norm(y.get()) * np.linalg.norm(Wx.get())
+
+
+@pytest.mark.parametrize("kind", ["permuted2d", "cube3d"])
+def test_filter_matches_brute_force(gpu, kind):
+    from femo_amd.fea.elasticity import DeviceFilter
+    from femo_amd.fea.mesh import createRectangleMesh, createUnitCubeMesh, meshSize
+    mesh = (createRectangleMesh([0.0, 0.0], [160.0, 80.0], 40, 20).permuted(seed=3, cells=True) if kind == "permuted2d"
+            else createUnitCubeMesh(5, 0.2))
+    h = meshSize(mesh)
+    r = 2.0 * (h.max() + h.min()) / 2
+    c = mesh.centroids()
+    F = DeviceFilter(gpu, c, r)
+    rowptr, col, val = F.export_csr()
+    assert np.all(np.diff(col[rowptr[0]:rowptr[1]]) > 0)
+    for i in range(mesh.n_cell):
+        assert np.all(np.diff(col[rowptr[i]:rowptr[i + 1]]) > 0)
+    W = sp.csr_matrix((val, col, rowptr), shape=(mesh.n_cell,) * 2)
+    Wr = ref.filter_matrix(c, r)
+    assert abs(W - Wr).max() <= 1e-14                           # weight-0 entries at d = r may be present or absent
+    rT, cT, vT = F.export_csr(transpose=True)
+    WT = sp.csr_matrix((vT, cT, rT), shape=(mesh.n_cell,) * 2)
+    assert abs(WT - W.T).max() <= 1e-15
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("size", ["rect640x320", "cube48"])
+def test_full_size(gpu, size):
+    from femo_amd.engine import Vec
+    from femo_amd.fea.elasticity import ElasticityResidual, Measure, METHODS
+    from femo_amd.fea.function import Function, FunctionSpace, VectorFunctionSpace
+    from femo_amd.fea.mesh import createRectangleMesh, createUnitCubeMesh, locate_entities_boundary
+    from femo_amd.fea.utils_hip import dirichletbc
+    if size == "rect640x320":
+        mesh = createRectangleMesh([0.0, 0.0], [L_X, L_Y], 640, 320)
+        tmark = lambda x: np.logical_and(abs(x[1] - L_Y / 2) < L_Y / 320 + 3e-6, abs(x[0] - L_X) < 3e-6)
+        t = np.array([0.0, -0.25])
+    else:
+        mesh = createUnitCubeMesh(48)
+        tmark = lambda x: np.logical_and(np.isclose(x[0], 1.0), x[2] < 0.25)
+        t = np.array([0.0, 0.0, -1.0])
+    d = mesh.tdim
+    rng = np.random.default_rng(2)
+    V, Q = VectorFunctionSpace(mesh), FunctionSpace(mesh, ("DG", 0))
+    u, rho = Function(V), Function(Q)
+    rho.vector[:] = rng.uniform(0.3, 1.0, mesh.n_cell)
+    from femo_amd.fea.elasticity import meshtags
+    facets = locate_entities_boundary(mesh, d - 1, tmark)
+    ds = Measure("ds", domain=mesh, subdomain_data=meshtags(mesh, d - 1, facets, np.full(len(facets), 1)))(1)
+    fixed_v = np.nonzero(np.isclose(mesh.x[:, 0], 0.0))[0]
+    dofs = (fixed_v[:, None] * d + np.arange(d)).ravel()
+    form = ElasticityResidual(u, rho, t, ds)
+    bcs = [dirichletbc(0.0, dofs, V)]
+    form.solve_state(u, bcs)
+    info = form.last_info['state']
+    print(f"{size}: {V.dim} dofs, PCG {info['iterations']} iterations, {info['solve_ms']:.1f} ms")
+    assert info['converged'] == 1
+    dev = form.stiffness()
+    F = form.load()
+    Ku = Vec(gpu, V.dim)
+    dev.apply(u.vec, Ku, masked=True)
+    Fh = np.array(F.get()); Fh[dofs] = 0.0
+    r = np.array(Ku.get()) - Fh
+    assert np.linalg.norm(r) <= 1e-8 * np.linalg.norm(Fh)
+    dev.apply(u.vec, Ku)
+    uh = np.array(u.vec.get())
+    J = Fh @ uh
+    assert abs(J - uh @ np.array(Ku.get())) <= 1e-8 * abs(J)
+    # gradient of the compliance w.r.t. rho (adjoint = u) against central differences in 2 directions
+    g = Vec(gpu, mesh.n_cell)
+    dev.drho(METHODS["SIMP"], True, rho.vec, u.vec, u.vec, g)
+    grad = -np.array(g.get())
+    rho0 = np.array(rho.vector.getArray())
+    for _ in range(2):
+        dr = rng.standard_normal(mesh.n_cell)
+        step = 1e-5
+        vals = []
+        for s in (1.0, -1.0):
+            rho.vector[:] = rho0 + s * step * dr
+            form.solve_state(u, bcs)
+            vals.append(Fh @ np.array(u.vec.get()))
+        fd = (vals[0] - vals[1]) / (2 * step)
+        assert abs(fd - grad @ dr) <= 1e-5 * abs(fd)
+    rho.vector[:] = rho0
