@@ -1466,17 +1466,6 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_load_walk(int64_t n_rows, int64_
   if (row < n_rows) out[row] = acc;
 }
 
-__global__ void k_reduce_partials(int nblocks, int nsums, const double* __restrict__ partials,
-                                  double* __restrict__ out) {
-  __shared__ double lds[1024 / 64];
-  for (int j = 0; j < nsums; ++j) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 1024) acc += partials[(int64_t)j * FEMO_MAX_PARTIALS + i];
-    const double s = femo_block_sum<1024>(acc, lds);
-    if (threadIdx.x == 0) out[j] = s;
-  }
-}
-
 inline int cell_grid(int64_t n_cell) {
   int64_t g = (n_cell + FEMO_BLOCK - 1) / FEMO_BLOCK;
   if (g > FEMO_MAX_PARTIALS) g = FEMO_MAX_PARTIALS;
@@ -1861,8 +1850,7 @@ int femo_launch_cell_expr(femo_mesh* m, int kind, const double* params, const do
 
 int femo_reduce_to_host(femo_ctx* ctx, int nblocks, int nsums, double* host_out) {
   FEMO_REQUIRE(nsums <= FEMO_NSCAL && nblocks <= FEMO_MAX_PARTIALS, "reduction too large");
-  hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, nblocks, nsums, ctx->d_partials, ctx->d_scal);
-  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_TRY(femo_launch_fold(1024, nblocks, nsums, ctx->d_partials, ctx->d_scal, ctx->stream));
   if (ctx->nranks > 1)
     FEMO_TRY(femo_coll_allreduce(ctx, ctx->d_scal, nsums, ctx->stream));
   FEMO_HIP_CHECK(hipMemcpyAsync(ctx->h_scal, ctx->d_scal, nsums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

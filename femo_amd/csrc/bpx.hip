@@ -1893,15 +1893,6 @@ __global__ void k_unpack_shared(int64_t n_shared, const int32_t* __restrict__ id
     else g_coarse[i - n_shared] = buf[i];
   }
 }
-__global__ __launch_bounds__(1024) void k_fold_partials(int nb, const double* __restrict__ partials, double* __restrict__ out,
-                                                        const int32_t* __restrict__ done) {
-  if (done != nullptr && *done) return;
-  __shared__ double lds[1024 / 64];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 1024) acc += partials[i];
-  const double t = femo_block_sum<1024>(acc, lds);
-  if (threadIdx.x == 0) out[0] = t;
-}
 
 // resident workgroups of the persistent brick kernel per CU (registers and LDS decide; asked once)
 template <int D, int PF>
@@ -2234,7 +2225,7 @@ int femo_pc_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const do
   const double* dot_global = nullptr;
   if (sparse && mode != 0) {
     // each rank only holds the finest level on the nodes it touches: its weighted dot is a partial sum
-    hipLaunchKernelGGL(k_fold_partials, dim3(1), dim3(1024), 0, st, nb_dot, pc->d_dot_partials, pc->d_dot_scalar, done);
+    FEMO_TRY(femo_launch_fold(1024, nb_dot, 1, pc->d_dot_partials, pc->d_dot_scalar, st, done));
     FEMO_TRY(femo_coll_allreduce(ctx, pc->d_dot_scalar, 1, st));
     dot_global = pc->d_dot_scalar;
     nb_dot = 0;

@@ -508,20 +508,13 @@ __global__ __launch_bounds__(EB) void k_pcg_precond(int64_t n_rows, const double
   if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
-// one block: sum of the partials (fixed order)
-__device__ double sum_partials(const double* __restrict__ part, int np, double* lds) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < np; i += blockDim.x) v += part[i];
-  return femo_block_sum_all<1024>(v, lds);
-}
-
 // mode 0: initial rz.  mode 1: alpha = rz / pq.  mode 2: rz' -> beta, convergence.
 __global__ __launch_bounds__(1024) void k_pcg_scalar(int mode, const double* __restrict__ part, int np, double rtol2,
                                                      double atol2, int max_it, double* __restrict__ s,
                                                      int32_t* __restrict__ flag) {
   __shared__ double lds[16];
   if (mode != 0 && flag[0]) return;
-  const double v = sum_partials(part, np, lds);
+  const double v = femo_fold_partials<1024>(part, np, lds);
   if (threadIdx.x != 0) return;
   if (mode == 0) {
     s[S_RZ] = v; s[S_RZ0] = v;

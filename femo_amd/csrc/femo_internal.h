@@ -200,6 +200,11 @@ int femo_launch_sum(double* out, const double* a, const double* b, int64_t n, hi
 // out = a * x on the stream (api.hip; a host array known to be a * a device vector is "uploaded" this way)
 int femo_launch_scale(double* out, double a, const double* x, int64_t n, hipStream_t st);
 int femo_launch_fill(double* out, double value, int64_t n, hipStream_t st);
+// out[j] = femo_fold_partials over slot j of `partials` (+ slot j of `partials2`, nb2 > 0), j < nsums, slots
+// FEMO_MAX_PARTIALS apart; one workgroup of nt = 1024 or 256 threads (the thread count fixes the summation order).
+// done != null: nothing once *done is set.  (solver.hip)
+int femo_launch_fold(int nt, int nb, int nsums, const double* partials, double* out, hipStream_t st,
+                     const int32_t* done = nullptr, int nb2 = 0, const double* partials2 = nullptr);
 void femo_vec_register(femo_vec* v);     // after creation: assigns uid, enters the live table
 void femo_vec_unregister(femo_vec* v);   // before destruction
 
@@ -449,6 +454,18 @@ __device__ __forceinline__ double femo_block_sum_all(double v, double* lds /* NT
 #pragma unroll
   for (int i = 0; i < NT / 64; ++i) s += lds[i];
   return s;
+}
+
+// The fixed-order sum of nb per-block partials (+ nb2 of a second list, into the same per-thread accumulator) as one
+// block of NT threads folds it: stride NT, then the tree of femo_block_sum_all.  The same value in every thread, and in
+// every block that folds the same partials.
+template <int NT>
+__device__ __forceinline__ double femo_fold_partials(const double* __restrict__ partials, int nb, double* lds /* NT/64 */,
+                                                     const double* __restrict__ partials2 = nullptr, int nb2 = 0) {
+  double a = 0.0;
+  for (int i = threadIdx.x; i < nb; i += NT) a += partials[i];
+  for (int i = threadIdx.x; i < nb2; i += NT) a += partials2[i];
+  return femo_block_sum_all<NT>(a, lds);
 }
 
 // Blocks are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the XCD

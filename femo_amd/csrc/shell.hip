@@ -1063,21 +1063,6 @@ __global__ void k_csr_diag_inv(int64_t n, const int64_t* __restrict__ rowptr, co
   }
 }
 
-// sum of per-block partials, the same value in every thread of every block (fixed order: reproducible)
-__device__ __forceinline__ double fold(const double* __restrict__ partials, int nb, double* lds) {
-  double a = 0.0;
-  for (int i = threadIdx.x; i < nb; i += SH_BLOCK) a += partials[i];
-  a = femo_wave_sum(a);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) lds[w] = a;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < SH_BLOCK / 64; ++i) s += lds[i];
-  return s;
-}
-
 // scal: [0] gamma = r.z, [1] gamma0 (tolerance reference), [2] tol^2 factor
 // r = b - A x0 is prepared by the host code; z = dinv r; p = z; partial r.z
 __global__ __launch_bounds__(SH_BLOCK) void k_scg_init(int64_t n, const double* __restrict__ r, const double* __restrict__ dinv,
@@ -1096,7 +1081,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_scg_init(int64_t n, const double* 
 __global__ __launch_bounds__(SH_BLOCK) void k_scg_gamma0(int nb, const double* __restrict__ partials, double rtol2, double atol2, double* __restrict__ scal,
                                                          int32_t* __restrict__ flag) {
   __shared__ double lds[SH_BLOCK / 64];
-  const double g = fold(partials, nb, lds);
+  const double g = femo_fold_partials<SH_BLOCK>(partials, nb, lds);
   if (threadIdx.x == 0) {
     scal[0] = g; scal[1] = g;
     scal[4] = g;                           // gamma as published by the first SpMV of the loop
@@ -1113,7 +1098,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_scg_xr(int64_t n, int nb_pq, const
                                                      const int32_t* __restrict__ done) {
   if (*done) return;
   __shared__ double lds[SH_BLOCK / 64];
-  const double pq = fold(part_pq, nb_pq, lds);
+  const double pq = femo_fold_partials<SH_BLOCK>(part_pq, nb_pq, lds);
   const double alpha = pq != 0.0 ? scal[0] / pq : 0.0;
   double s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * SH_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * SH_BLOCK) {
@@ -1132,7 +1117,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_scg_p(int64_t n, int it, int nb_rz
                                                     int32_t* __restrict__ flag, double* __restrict__ gamma_out) {
   if (flag[0]) return;
   __shared__ double lds[SH_BLOCK / 64];
-  const double g1 = fold(part_rz, nb_rz, lds);
+  const double g1 = femo_fold_partials<SH_BLOCK>(part_rz, nb_rz, lds);
   const double g0 = scal[0];
   const bool conv = g1 <= scal[2] || !(g1 == g1);
   const double beta = g0 != 0.0 ? g1 / g0 : 0.0;
@@ -3074,7 +3059,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_scg_xr_plain(int64_t n, int nb_pq,
                                                            double* __restrict__ x, double* __restrict__ r, const int32_t* __restrict__ done) {
   if (*done) return;
   __shared__ double lds[SH_BLOCK / 64];
-  const double pq = fold(part_pq, nb_pq, lds);
+  const double pq = femo_fold_partials<SH_BLOCK>(part_pq, nb_pq, lds);
   const double alpha = pq != 0.0 ? scal[0] / pq : 0.0;
   for (int64_t i = (int64_t)blockIdx.x * SH_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * SH_BLOCK) {
     x[i] += alpha * p[i];
@@ -3088,7 +3073,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_scg_p_z(int64_t n, int it, int nb_
                                                       double* __restrict__ gamma_out) {
   if (flag[0]) return;
   __shared__ double lds[SH_BLOCK / 64];
-  const double g1 = fold(part_rz, nb_rz, lds);
+  const double g1 = femo_fold_partials<SH_BLOCK>(part_rz, nb_rz, lds);
   const double g0 = scal[0];
   const bool conv = g1 <= scal[2] || !(g1 == g1);
   const double beta = g0 != 0.0 ? g1 / g0 : 0.0;
@@ -3110,7 +3095,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_scg_xr_pt(int64_t n_pts, int nb_pq
                                                         double* __restrict__ part_rB, const int32_t* __restrict__ done, double* __restrict__ alpha_out = nullptr) {
   if (*done) return;
   __shared__ double lds[SH_BLOCK / 64];
-  const double pq = fold(part_pq, nb_pq, lds);
+  const double pq = femo_fold_partials<SH_BLOCK>(part_pq, nb_pq, lds);
   const double alpha = pq != 0.0 ? scal[0] / pq : 0.0;
   // alpha_out != nullptr: x += alpha p is carried by the preconditioner's first coarse product (ShellXCarry); this kernel
   // then streams q, r and the smoother blocks only
@@ -3153,7 +3138,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_pc_prolong_fused(int64_t n_pts, in
                                                                const float4* __restrict__ fin_w4 = nullptr, int64_t n_unode = 0) {
   if (flag[0]) return;
   __shared__ double lds[SH_BLOCK / 64];
-  const double g1 = fold(part_rB, nb_rB, lds) + fold(part_te, nb_te, lds);
+  const double g1 = femo_fold_partials<SH_BLOCK>(part_rB, nb_rB, lds) + femo_fold_partials<SH_BLOCK>(part_te, nb_te, lds);
   const double g0 = scal[0];
   const bool conv = g1 <= scal[2] || !(g1 == g1);
   const double beta = g0 != 0.0 ? g1 / g0 : 0.0;
@@ -3234,14 +3219,6 @@ __global__ void k_halo_pack(int64_t n, const int32_t* __restrict__ idx, const do
 
 __global__ void k_halo_unpack(int64_t n, const int32_t* __restrict__ idx, const double* __restrict__ buf, double* __restrict__ v) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[idx[i]] = buf[i];
-}
-
-// out[0] = sum of the partials (one workgroup): what the all-reduce between a producer and its consumer works on
-__global__ __launch_bounds__(SH_BLOCK) void k_fold1(int nb, const double* __restrict__ partials, double* __restrict__ out, const int32_t* __restrict__ done) {
-  if (done != nullptr && *done) return;
-  __shared__ double lds[SH_BLOCK / 64];
-  const double g = fold(partials, nb, lds);
-  if (threadIdx.x == 0) out[0] = g;
 }
 
 template <class T>
@@ -4414,8 +4391,7 @@ int femo_shell_solve(femo_shell* s, const femo_vec* vals, const uint8_t* fixed_h
   const bool carry_x = fused && s->cs_ready && s->d_cs_Af != nullptr && !femo_env_flag("FEMO_SHELL_NO_XCARRY");
   const int nb_rz0 = lattice ? (int)gz : (int)gv;
   if (multi) {
-    hipLaunchKernelGGL(k_fold1, dim3(1), dim3(SH_BLOCK), 0, st, nb_rz0, Prz, one_rz, (const int32_t*)nullptr);
-    FEMO_HIP_CHECK(hipGetLastError());
+    FEMO_TRY(femo_launch_fold(SH_BLOCK, nb_rz0, 1, Prz, one_rz, st));
     FEMO_TRY(shell_allreduce(s, one_rz, 1, st));
     hipLaunchKernelGGL(k_scg_gamma0, dim3(1), dim3(SH_BLOCK), 0, st, 1, one_rz, opts->rtol * opts->rtol, opts->atol * opts->atol, s->d_scal, s->d_flag);
   } else {
@@ -4451,20 +4427,17 @@ int femo_shell_solve(femo_shell* s, const femo_vec* vals, const uint8_t* fixed_h
         hipLaunchKernelGGL(k_csr_spmv, dim3(gs), dim3(SH_BLOCK), 0, st, n, s->d_rowptr, s->d_cols, vals->d, d_fixed, 0, s->d_p, s->d_q, Ppq, s->d_flag, s->d_scal, gam);
       if (sample) { FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev + 1], st)); ++n_ev; }
       if (multi) {
-        hipLaunchKernelGGL(k_fold1, dim3(1), dim3(SH_BLOCK), 0, st, (int)gs, Ppq, one_pq, s->d_flag);
-        FEMO_HIP_CHECK(hipGetLastError());
+        FEMO_TRY(femo_launch_fold(SH_BLOCK, (int)gs, 1, Ppq, one_pq, st, s->d_flag));
         FEMO_TRY(shell_allreduce(s, one_pq, 1, st));
         if (lattice) {
           hipLaunchKernelGGL(k_scg_xr_plain, dim3(gv), dim3(SH_BLOCK), 0, st, n, 1, one_pq, s->d_scal, s->d_p, s->d_q, x->d, s->d_r, s->d_flag);
           FEMO_TRY(shell_pc_apply(s, d_fixed, Prz, gz, s->d_flag));
-          hipLaunchKernelGGL(k_fold1, dim3(1), dim3(SH_BLOCK), 0, st, (int)gz, Prz, one_rz, s->d_flag);
-          FEMO_HIP_CHECK(hipGetLastError());
+          FEMO_TRY(femo_launch_fold(SH_BLOCK, (int)gz, 1, Prz, one_rz, st, s->d_flag));
           FEMO_TRY(shell_allreduce(s, one_rz, 1, st));
           hipLaunchKernelGGL(k_scg_p_z, dim3(gv), dim3(SH_BLOCK), 0, st, n, it, 1, one_rz, s->d_scal, s->d_z, s->d_p, s->d_flag, gam);
         } else {
           hipLaunchKernelGGL(k_scg_xr, dim3(gv), dim3(SH_BLOCK), 0, st, n, 1, one_pq, s->d_scal, s->d_p, s->d_q, s->d_dinv, x->d, s->d_r, Prz, s->d_flag);
-          hipLaunchKernelGGL(k_fold1, dim3(1), dim3(SH_BLOCK), 0, st, (int)gv, Prz, one_rz, s->d_flag);
-          FEMO_HIP_CHECK(hipGetLastError());
+          FEMO_TRY(femo_launch_fold(SH_BLOCK, (int)gv, 1, Prz, one_rz, st, s->d_flag));
           FEMO_TRY(shell_allreduce(s, one_rz, 1, st));
           hipLaunchKernelGGL(k_scg_p, dim3(gv), dim3(SH_BLOCK), 0, st, n, it, 1, one_rz, s->d_scal, s->d_r, s->d_dinv, s->d_p, s->d_flag, gam);
         }

@@ -432,25 +432,6 @@ __global__ void k_gather(int64_t n, const int32_t* __restrict__ perm, const doub
 constexpr int S_GAMMA = 0, S_DELTA = 2, S_TOL2 = 3;
 constexpr int P_DELTA = 0, P_GAMMA = 1;
 
-template <int NT>
-__device__ __forceinline__ double femo_block_sum_bcast(double v, double* lds /* NT/64 */) {
-  v = femo_wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) lds[w] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < NT / 64; ++i) s += lds[i];
-  return s;
-}
-
-__device__ __forceinline__ double cg_scalar(const double* __restrict__ partials, int nb, double* lds) {
-  double a = 0.0;
-  for (int i = threadIdx.x; i < nb; i += FEMO_BLOCK) a += partials[i];
-  return femo_block_sum_bcast<FEMO_BLOCK>(a, lds);
-}
-
 __global__ void k_invsqrt_diag(int64_t n, const double* __restrict__ diag, double* __restrict__ s) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     s[i] = 1.0 / sqrt(diag[i]);
@@ -518,8 +499,8 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_cg_update_r(int64_t n, int cur, 
                                                             const int32_t* __restrict__ done) {
   if (*done) return;
   __shared__ double lds[FEMO_BLOCK / 64];
-  const double gamma = cg_scalar(partials + (P_GAMMA + cur) * FEMO_MAX_PARTIALS, nb_g, lds);
-  const double delta = cg_scalar(partials + P_DELTA * FEMO_MAX_PARTIALS, nb_d, lds);
+  const double gamma = femo_fold_partials<FEMO_BLOCK>(partials + (P_GAMMA + cur) * FEMO_MAX_PARTIALS, nb_g, lds);
+  const double delta = femo_fold_partials<FEMO_BLOCK>(partials + P_DELTA * FEMO_MAX_PARTIALS, nb_d, lds);
   const double alpha = delta != 0.0 ? gamma / delta : 0.0;
   double s0 = 0.0;
   const int64_t n2 = n >> 1;
@@ -553,9 +534,9 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_cg_update_xp(int64_t n, int cur,
   if (stamp != 0 && stamp != it + 1) return;
   __shared__ double lds[FEMO_BLOCK / 64];
   const int nxt = cur ^ 1;
-  const double gamma = cg_scalar(partials + (P_GAMMA + cur) * FEMO_MAX_PARTIALS, nb_g, lds);
-  const double gamma1 = cg_scalar(partials + (P_GAMMA + nxt) * FEMO_MAX_PARTIALS, nb_g, lds);
-  const double delta = cg_scalar(partials + P_DELTA * FEMO_MAX_PARTIALS, nb_d, lds);
+  const double gamma = femo_fold_partials<FEMO_BLOCK>(partials + (P_GAMMA + cur) * FEMO_MAX_PARTIALS, nb_g, lds);
+  const double gamma1 = femo_fold_partials<FEMO_BLOCK>(partials + (P_GAMMA + nxt) * FEMO_MAX_PARTIALS, nb_g, lds);
+  const double delta = femo_fold_partials<FEMO_BLOCK>(partials + P_DELTA * FEMO_MAX_PARTIALS, nb_d, lds);
   const double alpha = delta != 0.0 ? gamma / delta : 0.0;
   const bool bad = !(gamma1 == gamma1) || !(alpha == alpha);  // NaN: not SPD or diverged
   const bool converged = gamma1 <= scal[S_TOL2] || bad;
@@ -606,19 +587,6 @@ constexpr int S_RHO = 4;
 constexpr int S_ALPHA = 8;  // alpha of the current iteration (k_pcg_xr with carry_x: the x update runs inside the preconditioner)
 constexpr int S_TOLG = 5;   // rtol^2 * gamma_0: the stopping threshold on gamma = rh.zh (set on the device by the first apply)
 
-// out[0] = sum of `nb` partials (+ `nb2` partials of the next slot pair, overlapped SpMV)
-__global__ __launch_bounds__(1024) void k_pcg_fold(int nb, const double* __restrict__ partials, int nb2,
-                                                   const double* __restrict__ partials2, double* __restrict__ out,
-                                                   const int32_t* __restrict__ done) {
-  if (*done) return;
-  __shared__ double lds[1024 / 64];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 1024) acc += partials[i];
-  for (int i = threadIdx.x; i < nb2; i += 1024) acc += partials2[i];
-  const double t = femo_block_sum<1024>(acc, lds);
-  if (threadIdx.x == 0) out[0] = t;
-}
-
 // xh += alpha ph ; rh -= alpha qh ; partial rh.rh.  nb_d > 0: delta is folded here from the
 // SpMV's per-block partials (single GPU: no fold kernel, no all-reduce), else read from scal.
 __global__ __launch_bounds__(FEMO_BLOCK) void k_pcg_xr(int64_t n, int cur, int nb_d, const double* __restrict__ partials_d,
@@ -631,7 +599,7 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_pcg_xr(int64_t n, int cur, int n
   if (*done) return;
   __shared__ double lds[FEMO_BLOCK / 64];
   const double gamma = scal[S_GAMMA + cur];
-  const double delta = nb_d > 0 ? cg_scalar(partials_d, nb_d, lds) : scal[S_DELTA];
+  const double delta = nb_d > 0 ? femo_fold_partials<FEMO_BLOCK>(partials_d, nb_d, lds) : scal[S_DELTA];
   if (nb_d > 0 && blockIdx.x == 0 && threadIdx.x == 0) scal[S_DELTA] = delta;   // for the breakdown test
   const double alpha = delta != 0.0 ? gamma / delta : 0.0;
   double s0 = 0.0;
@@ -685,12 +653,7 @@ __global__ __launch_bounds__(1024) void k_pcg_check(int it, int nb, const double
                                                     double* __restrict__ scal, int32_t* __restrict__ flags) {
   if (flags[0]) return;
   __shared__ double lds[1024 / 64];
-  double rho = 0.0;
-  if (nb > 0) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nb; i += 1024) acc += partials[i];
-    rho = femo_block_sum<1024>(acc, lds);
-  }
+  double rho = nb > 0 ? femo_fold_partials<1024>(partials, nb, lds) : 0.0;
   if (threadIdx.x != 0) return;
   if (nb > 0) scal[S_RHO] = rho; else rho = scal[S_RHO];
   const double delta = scal[S_DELTA];
@@ -763,21 +726,6 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_cgm_update(int64_t n, int it, do
   }
 }
 
-// fold partial slots 0 (delta) and 1 (gamma) into buf[0], buf[1] = scal + 2*parity
-__global__ __launch_bounds__(1024) void k_cgm_fold(int nblocks, int nblocks2, const double* __restrict__ partials,
-                                                   double* __restrict__ buf, const int32_t* __restrict__ done) {
-  if (*done) return;
-  __shared__ double lds[1024 / 64];
-  for (int j = 0; j < 2; ++j) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 1024) acc += partials[(int64_t)j * FEMO_MAX_PARTIALS + i];
-    // second launch of an overlapped SpMV (boundary slices): slots 2, 3
-    for (int i = threadIdx.x; i < nblocks2; i += 1024) acc += partials[(int64_t)(j + 2) * FEMO_MAX_PARTIALS + i];
-    const double t = femo_block_sum<1024>(acc, lds);
-    if (threadIdx.x == 0) buf[j] = t;                // buf = {delta, gamma}, contiguous for one all-reduce
-  }
-}
-
 // ---- BiCGSTAB on the scaled system (non-symmetric operators) --------------------------
 // van der Vorst's recurrence; S A S keeps a unit diagonal, i.e. Jacobi preconditioning.
 // Scalars live in scal[]; producers write partials, a one-block fold (plus all-reduce when
@@ -800,19 +748,6 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_bi_init(int64_t n, const double*
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
   t = femo_block_sum<FEMO_BLOCK>(s1, lds);
   if (threadIdx.x == 0) partials[FEMO_MAX_PARTIALS + blockIdx.x] = t;
-}
-
-// fold `nsums` consecutive partial slots into scal[dst .. dst+nsums)
-__global__ __launch_bounds__(1024) void k_bi_fold(int nblocks, int nsums, const double* __restrict__ partials, double* __restrict__ dst,
-                                                  const int32_t* __restrict__ done) {
-  if (*done) return;
-  __shared__ double lds[1024 / 64];
-  for (int j = 0; j < nsums; ++j) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 1024) acc += partials[(int64_t)j * FEMO_MAX_PARTIALS + i];
-    const double t = femo_block_sum<1024>(acc, lds);
-    if (threadIdx.x == 0) dst[j] = t;
-  }
 }
 
 // convergence test on (rho, rr) after `it` finished iterations (one thread; every later launch sees the flag)
@@ -910,14 +845,16 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_dot(int64_t n, const double* __r
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
-// out[j] = sum of partial slot j (consecutive slots starting at `partials`)
-__global__ __launch_bounds__(1024) void k_reduce_partials_at(int nblocks, int nsums, const double* __restrict__ partials,
-                                                             double* __restrict__ out) {
-  __shared__ double lds[1024 / 64];
+// the one stand-alone fold (femo_launch_fold): what an all-reduce between a producer and its consumers works on
+template <int NT>
+__global__ __launch_bounds__(NT) void k_fold(int nb, int nsums, const double* __restrict__ partials, int nb2,
+                                             const double* __restrict__ partials2, double* __restrict__ out,
+                                             const int32_t* __restrict__ done) {
+  if (done != nullptr && *done) return;
+  __shared__ double lds[NT / 64];
   for (int j = 0; j < nsums; ++j) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 1024) acc += partials[(int64_t)j * FEMO_MAX_PARTIALS + i];
-    const double t = femo_block_sum<1024>(acc, lds);
+    const int64_t o = (int64_t)j * FEMO_MAX_PARTIALS;
+    const double t = femo_fold_partials<NT>(partials + o, nb, lds, partials2 != nullptr ? partials2 + o : nullptr, nb2);
     if (threadIdx.x == 0) out[j] = t;
   }
 }
@@ -936,6 +873,15 @@ inline int vec_grid(const femo_ctx* ctx, int64_t n) {
 }
 
 }  // namespace
+
+int femo_launch_fold(int nt, int nb, int nsums, const double* partials, double* out, hipStream_t st,
+                     const int32_t* done, int nb2, const double* partials2) {
+  FEMO_REQUIRE(nt == 1024 || nt == 256, "femo_launch_fold: 1024 or 256 threads");
+  if (nt == 1024) hipLaunchKernelGGL(k_fold<1024>, dim3(1), dim3(1024), 0, st, nb, nsums, partials, nb2, partials2, out, done);
+  else hipLaunchKernelGGL(k_fold<256>, dim3(1), dim3(256), 0, st, nb, nsums, partials, nb2, partials2, out, done);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 
 int femo_spmv_grid(const femo_mesh* m) {
   int64_t g = (m->n_slices + 3) / 4;           // one slice per wave if the mesh is small
@@ -1435,6 +1381,140 @@ static int ensure_scaled(femo_mat* A, bool transpose) {
   return 0;
 }
 
+// ---- host side shared by the Krylov drivers --------------------------------------------------------------------------
+// The N-rank code path (folds + all-reduces between producers and consumers): a partitioned run, or FEMO_FORCE_MULTI=1 on
+// a 1-rank communicator (tests)
+static bool multi_path(const femo_ctx* ctx) {
+  return ctx->nranks > 1 || (ctx->comm != nullptr && femo_env_flag("FEMO_FORCE_MULTI"));
+}
+
+// r0 = b - q: a zero guess leaves *q0 null (and clears x when clear_x), any other takes q = A x0 with the unscaled operator
+// `vals`, the ghosts of x refreshed first
+static int initial_guess(femo_mat* A, const double* vals, femo_vec* x, bool zero_guess, bool clear_x, double* q,
+                         const double** q0) {
+  femo_mesh* m = A->mesh;
+  *q0 = nullptr;
+  if (zero_guess) {
+    if (clear_x) FEMO_HIP_CHECK(hipMemsetAsync(x->d, 0, x->n * sizeof(double), m->ctx->stream));
+    return 0;
+  }
+  if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, x->d));
+  FEMO_TRY(launch_spmv(A, vals, x->d, q, nullptr, nullptr));
+  *q0 = q;
+  return 0;
+}
+
+// the two sums an init kernel left in consecutive partial slots, folded into d[0], d[1], all-reduced on the N-rank path
+// and read back with one host synchronisation: r0.r0 and b.b of the scaled system
+static int initial_norms(femo_ctx* ctx, bool multi, int nb, const double* partials, double* d, double* rr0, double* bb) {
+  hipStream_t st = ctx->stream;
+  FEMO_TRY(femo_launch_fold(1024, nb, 2, partials, d, st));
+  if (multi) FEMO_TRY(femo_coll_allreduce(ctx, d, 2, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(ctx->h_scal, d, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  *rr0 = ctx->h_scal[0];
+  *bb = ctx->h_scal[1];
+  return 0;
+}
+
+// x = S xh (+ x0 unless the guess was zero), then ev1, waited for
+static int unscale_x(femo_mat* A, const double* xh, femo_vec* x, bool zero_guess) {
+  femo_ctx* ctx = A->mesh->ctx;
+  const int64_t n = A->mesh->n_rows;
+  if (n > 0) {
+    hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, ctx->stream, n, zero_guess ? 0 : 1, A->d_s, xh, x->d);
+    FEMO_HIP_CHECK(hipGetLastError());
+  }
+  FEMO_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
+  FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev1));
+  return 0;
+}
+
+// what every driver reports; the solve's time runs from ev0 (recorded first thing) to `end`
+static int fill_info(femo_ctx* ctx, hipEvent_t end, femo_solve_info* info, int iters, int conv, double rr) {
+  float ms = 0.f;
+  FEMO_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, end));
+  info->iterations = iters;
+  info->converged = conv;
+  info->residual_norm = std::sqrt(rr);
+  info->solve_ms = ms;
+  return 0;
+}
+
+static int finish_solve(femo_mat* A, const double* xh, femo_vec* x, bool zero_guess, femo_solve_info* info, int iters,
+                        int conv, double rr) {
+  FEMO_TRY(unscale_x(A, xh, x, zero_guess));
+  return fill_info(A->mesh->ctx, A->mesh->ctx->ev1, info, iters, conv, rr);
+}
+
+// Events around the SpMV of iterations [from, from + N) (ev_pool[0 .. 2N)): info->spmv_ms / spmv_samples, the roofline
+// record of bench.py
+struct SpmvSamples {
+  static constexpr int N = 4;
+  femo_ctx* ctx;
+  int from;
+  int n = 0;
+  bool on = false;
+  SpmvSamples(femo_ctx* c, int first) : ctx(c), from(first) {}
+  int begin(int it) {
+    on = it >= from && it < from + N;
+    if (on) FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n], ctx->stream));
+    return 0;
+  }
+  int end() {
+    if (on) { FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n + 1], ctx->stream)); ++n; }
+    return 0;
+  }
+  int report(femo_solve_info* info) const {
+    double acc = 0.0;
+    for (int i = 0; i < n; ++i) {
+      float t = 0.f;
+      FEMO_HIP_CHECK(hipEventElapsedTime(&t, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]));
+      acc += t;
+    }
+    info->spmv_ms = acc;
+    info->spmv_samples = n;
+    return 0;
+  }
+};
+constexpr int POLL_EV = 2 * SpmvSamples::N;   // ev_pool[POLL_EV + slot]: the flag polls
+
+// The host's view of the "done" stamp of a loop enqueued in batches: behind every batch a copy of the four flag words
+// (h_flags: two slots of four) and an event.  Two deep: the host waits for the previous batch's copy while the one just
+// enqueued runs; `sync` waits for the batch just enqueued instead.  A batch that reaches max_it (`last`) ends the loop.
+struct FlagPoll {
+  femo_ctx* ctx;
+  int32_t* h_flags;
+  int polled = 0;
+  bool pending[2] = {false, false};
+  explicit FlagPoll(femo_ctx* c) : ctx(c), h_flags(reinterpret_cast<int32_t*>(c->h_scal + FEMO_NSCAL)) {}
+  int after_batch(bool last, bool sync, bool* done) {
+    hipStream_t st = ctx->stream;
+    const int slot = polled & 1;
+    FEMO_HIP_CHECK(hipMemcpyAsync(h_flags + 4 * slot, ctx->d_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[POLL_EV + slot], st));
+    pending[slot] = true;
+    ++polled;
+    const int prev = polled & 1;
+    if (sync) {
+      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[POLL_EV + slot]));
+      if (h_flags[4 * slot] || last) *done = true;
+      pending[slot] = false;
+      return 0;
+    }
+    if (pending[prev]) {
+      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[POLL_EV + prev]));
+      if (h_flags[4 * prev]) *done = true;
+      pending[prev] = false;
+    }
+    if (!*done && last) {
+      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[POLL_EV + slot]));
+      *done = true;
+    }
+    return 0;
+  }
+};
+
 // ---- merged BPX-PCG (round 4) ---------------------------------------------------------------------------------------
 // One all-reduce + one halo exchange per iteration on N ranks, five launches per iteration on one (SpMV, brick
 // restriction of q = A p, coarse lattice + vector updates, fine lattice, mesh prolongation + direction update), one
@@ -1446,10 +1526,8 @@ __global__ __launch_bounds__(1024) void k_pcg_setup(int nb, const double* __rest
   __shared__ double lds[1024 / 64];
   double rho0, bb;
   if (nb > 0) {
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < nb; i += 1024) { a += partials[i]; b += partials[FEMO_MAX_PARTIALS + i]; }
-    rho0 = femo_block_sum_all<1024>(a, lds);
-    bb = femo_block_sum_all<1024>(b, lds);
+    rho0 = femo_fold_partials<1024>(partials, nb, lds);
+    bb = femo_fold_partials<1024>(partials + FEMO_MAX_PARTIALS, nb, lds);
   } else {
     rho0 = S[MS_RED]; bb = S[MS_RED + 1];
   }
@@ -1497,16 +1575,12 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
   }
   if (opts->zero_guess && x->n > n) { ze.p[ze.count] = x->d + n; ze.n[ze.count++] = x->n - n; }   // ghost tail of the solution, as the classic loop leaves it
   FEMO_TRY(femo_pc_merged_begin(m, A->d_s, mask, &ze));
-  const double* q0 = nullptr;
-  if (!opts->zero_guess) {
-    if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, x->d));
-    FEMO_TRY(launch_spmv(A, A->d_vals, x->d, w.q, nullptr, nullptr));
-    q0 = w.q;
-  }
+  const double* q0;
+  FEMO_TRY(initial_guess(A, A->d_vals, x, opts->zero_guess, /*clear_x=*/false, w.q, &q0));
   hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, b->d, q0, A->d_s, w.r, w.p, w.xh, P, A->has_idrows ? A->d_idrows : nullptr);
   const double atol2 = opts->atol * opts->atol;
   if (multi) {
-    hipLaunchKernelGGL(k_reduce_partials_at, dim3(1), dim3(1024), 0, st, gv, 2, P + FEMO_MAX_PARTIALS, S + MS_RED);
+    FEMO_TRY(femo_launch_fold(1024, gv, 2, P + FEMO_MAX_PARTIALS, S + MS_RED, st));
     FEMO_TRY(femo_coll_allreduce(ctx, S + MS_RED, 2, st));
     hipLaunchKernelGGL(k_pcg_setup, dim3(1), dim3(1024), 0, st, 0, P + FEMO_MAX_PARTIALS, S, opts->rtol * opts->rtol, atol2, ctx->d_flags);
   } else {
@@ -1539,24 +1613,12 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
   info->pc_rhs_norm = std::sqrt(gamma0 * (rho0 > 0.0 ? bb / rho0 : 1.0));
   if (h_flags[0]) {                               // below the absolute tolerance (k_pcg_setup) or below atol_pc (first apply)
     info->pc_residual_norm = std::sqrt(gamma0);
-    if (!spec_x && n > 0) {
-      hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, st, n, 1, A->d_s, w.xh, x->d);
-      FEMO_HIP_CHECK(hipEventRecord(ctx->ev1, st));
-      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev1));
-    }
-    float ms0 = 0.f;
-    FEMO_HIP_CHECK(hipEventElapsedTime(&ms0, ctx->ev0, ctx->ev1));
-    info->iterations = 0;
-    info->loop_allreduces = 0;
-    info->converged = (h_flags[2] || !(rho0 == rho0)) ? -1 : 1;
-    info->residual_norm = std::sqrt(rho0);
-    info->solve_ms = ms0;
-    return 0;
+    if (!spec_x && n > 0) FEMO_TRY(unscale_x(A, w.xh, x, opts->zero_guess));
+    return fill_info(ctx, ctx->ev1, info, 0, (h_flags[2] || !(rho0 == rho0)) ? -1 : 1, rho0);
   }
   FEMO_TRY(ensure_scaled(A, false));
 
-  const int n_sample = 4, sample_from = 2;
-  int n_ev = 0;
+  SpmvSamples spmv(ctx, 2);
   // Batches: with a prediction (the smaller of the last two counts on this mesh) exactly that many iterations first, then
   // 2, 3, 4, 6, 8, 8 ... -- each batch polled synchronously (a solve that follows a short one paid a
   // blocking poll every second iteration).  Without a prediction: 8 at a time.
@@ -1591,8 +1653,7 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
     }
     const int it_end = it + this_batch < max_it ? it + this_batch : max_it;
     for (; it < it_end; ++it) {
-      const bool sample = it >= sample_from && it < sample_from + n_sample;
-      if (sample) FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev], st));
+      FEMO_TRY(spmv.begin(it));
       int g1 = gs, g2 = 0;
       if (multi) {
         if (femo_pc_merged_sends_halo(m)) {
@@ -1606,7 +1667,7 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
       } else {
         FEMO_TRY(launch_spmv(A, A->d_valsS, w.p, w.q, Pq_int, ctx->d_flags, true));
       }
-      if (sample) { FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev + 1], st)); ++n_ev; }
+      FEMO_TRY(spmv.end());
       stop.it = it;
       V.cur = it & 1;
       V.nb_q[0] = g1; V.nb_q[1] = g2; V.Pq[0] = Pq_int; V.Pq[1] = Pq_bnd;
@@ -1621,24 +1682,21 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
     if (femo_halo_direct_ready(m)) FEMO_HIP_CHECK(hipMemcpyAsync(ctx->d_flags + 3, m->hd->d_err, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     FEMO_HIP_CHECK(hipMemcpyAsync(h_flags, ctx->d_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     FEMO_HIP_CHECK(hipMemcpyAsync(ctx->h_scal, S, FEMO_NSCAL * sizeof(double), hipMemcpyDeviceToHost, st));
-    FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_sample], st));
-    FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[2 * n_sample]));
+    FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[POLL_EV], st));
+    FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[POLL_EV]));
     FEMO_REQUIRE(!(femo_halo_direct_ready(m) && h_flags[3] != 0),
                  "ghost refresh: a consumer waited 4 s for a neighbour's stores and gave up (rank %d of %d) -- the solve is void", ctx->rank, ctx->nranks);
     if (h_flags[0] || it >= max_it) done = true;
   }
   info->loop_allreduces = (int32_t)(ctx->n_allreduce - ar0);
-  float ms = 0.f;
-  if (h_flags[0]) {
-    FEMO_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev_pool[2 * n_sample]));
-  } else {
+  const hipEvent_t end = h_flags[0] ? ctx->ev_pool[POLL_EV] : ctx->ev1;
+  if (!h_flags[0]) {
     // not converged within max_it: x of the last iterate, the final scalars and the time with one more synchronisation
     if (n > 0) hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, st, n, opts->zero_guess ? 0 : 1, A->d_s, w.xh, x->d);
     FEMO_HIP_CHECK(hipMemcpyAsync(h_flags, ctx->d_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     FEMO_HIP_CHECK(hipMemcpyAsync(ctx->h_scal, S, FEMO_NSCAL * sizeof(double), hipMemcpyDeviceToHost, st));
     FEMO_HIP_CHECK(hipEventRecord(ctx->ev1, st));
     FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev1));
-    FEMO_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   }
   const int iters = h_flags[1];
   const int conv = h_flags[0] ? (h_flags[2] ? -1 : 1) : 0;
@@ -1647,20 +1705,9 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
     const double g_end = ctx->h_scal[MS_GAMMA + (iters & 1)];
     if (g_end > 0.0 && gamma0 > g_end) m->pcg_rate = std::log(gamma0 / g_end) / iters;
   }
-  double acc = 0.0;
-  for (int i = 0; i < n_ev; ++i) {
-    float t = 0.f;
-    FEMO_HIP_CHECK(hipEventElapsedTime(&t, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]));
-    acc += t;
-  }
-  info->spmv_ms = acc;
-  info->spmv_samples = n_ev;
+  FEMO_TRY(spmv.report(info));
   info->pc_residual_norm = std::sqrt(ctx->h_scal[MS_GAMMA + (iters & 1)]);
-  info->iterations = iters;
-  info->converged = conv;
-  info->residual_norm = std::sqrt(ctx->h_scal[MS_RR]);
-  info->solve_ms = ms;
-  return 0;
+  return fill_info(ctx, end, info, iters, conv, ctx->h_scal[MS_RR]);
 }
 
 extern "C" int femo_mat_prescale(femo_mat* A) {
@@ -1679,17 +1726,19 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   FEMO_REQUIRE(A->bpx_ok, "the BPX preconditioner needs an operator assembled from a Poisson-type form");
   FEMO_REQUIRE(!transpose, "the BPX preconditioner is for symmetric operators");
   hipStream_t st = ctx->stream;
+  // (not multi_path: FEMO_FORCE_MULTI on one rank keeps the classic loop, whose all-reduce path it tests)
   if (!(ctx->comm != nullptr && ctx->nranks == 1 && femo_env_flag("FEMO_FORCE_MULTI")) && femo_pc_merged_ok(m))
     return solve_pcg_bpx_merged(A, b, x, opts, info);
   FEMO_HIP_CHECK(hipEventRecord(ctx->ev0, st));
   FEMO_TRY(ensure_s(A));
   FEMO_TRY(femo_pc_build(m));
   CgWork w;
-  const bool multi = ctx->nranks > 1 || (ctx->comm != nullptr && femo_env_flag("FEMO_FORCE_MULTI"));
+  const bool multi = multi_path(ctx);
   FEMO_TRY(ensure_work(ctx, n, m->n_vert, w, 1));
   const int gv = vec_grid(ctx, n);
   const int gs = femo_spmv_grid(m);
-  int32_t* h_flags = reinterpret_cast<int32_t*>(ctx->h_scal + FEMO_NSCAL);
+  FlagPoll poll(ctx);
+  int32_t* h_flags = poll.h_flags;
   double* P = ctx->d_partials;
   double* S = ctx->d_scal;
   const uint8_t* mask = A->pc_has_mask ? A->d_pcmask : nullptr;
@@ -1700,21 +1749,12 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   };
 
   FEMO_HIP_CHECK(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int32_t), st));
-  const double* q0 = nullptr;
-  if (opts->zero_guess) {
-    FEMO_HIP_CHECK(hipMemsetAsync(x->d, 0, x->n * sizeof(double), st));
-  } else {
-    if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, x->d));
-    FEMO_TRY(launch_spmv(A, A->d_vals, x->d, w.q, nullptr, nullptr));
-    q0 = w.q;
-  }
+  const double* q0;
+  FEMO_TRY(initial_guess(A, A->d_vals, x, opts->zero_guess, /*clear_x=*/true, w.q, &q0));
   hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, b->d, q0, A->d_s, w.r, w.p, w.xh, P, A->has_idrows ? A->d_idrows : nullptr);
-  hipLaunchKernelGGL(k_reduce_partials_at, dim3(1), dim3(1024), 0, st, gv, 2, P + FEMO_MAX_PARTIALS, S);
   FEMO_HIP_CHECK(hipGetLastError());
-  if (multi) FEMO_TRY(femo_coll_allreduce(ctx, S, 2, st));
-  FEMO_HIP_CHECK(hipMemcpyAsync(ctx->h_scal, S, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-  FEMO_HIP_CHECK(hipStreamSynchronize(st));
-  const double rho0 = ctx->h_scal[0], bb = ctx->h_scal[1];
+  double rho0, bb;
+  FEMO_TRY(initial_norms(ctx, multi, gv, P + FEMO_MAX_PARTIALS, S, &rho0, &bb));
   // Stopping rule: relative in the norm of the preconditioner, sqrt(r^T M^-1 r) <= rtol sqrt(b^T M^-1 b)
   // (tested inside femo_pc_apply, where gamma = r^T M^-1 r becomes known), absolute in the Jacobi norm,
   // sqrt(r^T D^-1 r) <= atol (Newton's rounding-floor rule is stated in that norm; tested by k_pcg_check).
@@ -1722,22 +1762,7 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   const double tol = opts->atol;
   info->rhs_norm = bnorm;
   const int max_it = opts->max_it > 0 ? opts->max_it : 10000;
-  auto finish = [&](int iters, int conv, double rho) -> int {
-    if (n > 0) {
-      hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, st, n, opts->zero_guess ? 0 : 1, A->d_s, w.xh, x->d);
-      FEMO_HIP_CHECK(hipGetLastError());
-    }
-    FEMO_HIP_CHECK(hipEventRecord(ctx->ev1, st));
-    FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev1));
-    float ms = 0.f;
-    FEMO_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    info->iterations = iters;
-    info->converged = conv;
-    info->residual_norm = std::sqrt(rho);
-    info->solve_ms = ms;
-    return 0;
-  };
-  if (!(std::sqrt(rho0) > tol) || rho0 == 0.0) return finish(0, rho0 == rho0 ? 1 : -1, rho0);
+  if (!(std::sqrt(rho0) > tol) || rho0 == 0.0) return finish_solve(A, w.xh, x, opts->zero_guess, info, 0, rho0 == rho0 ? 1 : -1, rho0);
 
   double hs[FEMO_NSCAL] = {0};
   hs[S_TOL2] = tol * tol;
@@ -1761,11 +1786,10 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   const double gamma0 = ctx->h_scal[S_GAMMA];
   info->pc_rhs_norm = std::sqrt(gamma0 * (rho0 > 0.0 ? bb / rho0 : 1.0));
   info->pc_residual_norm = std::sqrt(gamma0);
-  if (h_flags[0]) return finish(0, gamma0 == gamma0 ? 1 : -1, rho0);      // below atol_pc before the first iteration
+  if (h_flags[0]) return finish_solve(A, w.xh, x, opts->zero_guess, info, 0, gamma0 == gamma0 ? 1 : -1, rho0);   // below atol_pc before the first iteration
   FEMO_TRY(ensure_scaled(A, false));   // the iteration's operator S A S (the apply above only needed S)
 
-  const int n_sample = 4, sample_from = 2;
-  int n_ev = 0;
+  SpmvSamples spmv(ctx, 2);
   const bool local_scalars = !multi && m->n_nbr == 0;
   const bool piggyback = multi && femo_pc_can_piggyback(m);
   // x += alpha p inside the preconditioner's single-workgroup launch (the first apply, above, has settled whether the
@@ -1785,17 +1809,15 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   // (the smaller of the last two counts: Newton's later solves need far fewer iterations than its first)
   const int last2 = std::min(m->pcg_last_iters, m->pcg_prev_iters);
   const int predicted = last2 > 0 ? last2 : 0;
-  int it = 0, polled = 0;
+  int it = 0;
   bool done = false;
-  int pending[2] = {-1, -1};
   const int64_t ar0 = ctx->n_allreduce;
   while (!done) {
     const int this_batch = predicted > 0 ? (it == 0 ? predicted : 2) : batch;
     const int it_end = it + this_batch < max_it ? it + this_batch : max_it;
     for (; it < it_end; ++it) {
       const int cur = it & 1, nxt = cur ^ 1;
-      const bool sample = it >= sample_from && it < sample_from + n_sample;
-      if (sample) FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev], st));
+      FEMO_TRY(spmv.begin(it));
       int g1 = gs, g2 = 0;
       if (m->n_nbr > 0 && m->d_slices_int != nullptr) {
         FEMO_TRY(halo_spmv_overlapped(A, A->d_valsS, w.p, w.q, P, ctx->d_flags, true, false, &g1, &g2));
@@ -1803,7 +1825,7 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
         if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, w.p));
         FEMO_TRY(launch_spmv(A, A->d_valsS, w.p, w.q, P + P_DELTA * FEMO_MAX_PARTIALS, ctx->d_flags, true));
       }
-      if (sample) { FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev + 1], st)); ++n_ev; }
+      FEMO_TRY(spmv.end());
       double* Pd = P + P_DELTA * FEMO_MAX_PARTIALS;
       double* Pr = P + 1 * FEMO_MAX_PARTIALS;
       double* Pg = P + 2 * FEMO_MAX_PARTIALS;   // boundary-slice partials of the overlapped SpMV
@@ -1825,10 +1847,10 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
           FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, A->d_s, r_cur, w.p, 1, S + S_RHO, S + S_GAMMA + cur, S + S_GAMMA + nxt, ctx->d_flags, gv, false, &stop, gv, Pr));
         }
       } else {
-        hipLaunchKernelGGL(k_pcg_fold, dim3(1), dim3(1024), 0, st, g1, Pd, g2, Pg, S + S_DELTA, ctx->d_flags);
+        FEMO_TRY(femo_launch_fold(1024, g1, 1, Pd, S + S_DELTA, st, ctx->d_flags, g2, Pg));
         FEMO_TRY(allreduce1(S + S_DELTA));
         hipLaunchKernelGGL(k_pcg_xr, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, cur, 0, Pd, S, w.q, w.p, (const double*)w.r, w.r, w.xh, Pr, ctx->d_flags);
-        hipLaunchKernelGGL(k_pcg_fold, dim3(1), dim3(1024), 0, st, gv, Pr, 0, (const double*)nullptr, S + S_RHO, ctx->d_flags);
+        FEMO_TRY(femo_launch_fold(1024, gv, 1, Pr, S + S_RHO, st, ctx->d_flags));
         if (piggyback) {
           // the rank's part of rh.rh rides in the lattice all-reduce of the preconditioner; the stopping
           // test then runs after the apply (one wasted apply in the last iteration, one collective less in all)
@@ -1842,28 +1864,7 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
       }
     }
     FEMO_HIP_CHECK(hipGetLastError());
-    const int slot = polled & 1;
-    FEMO_HIP_CHECK(hipMemcpyAsync(h_flags + 4 * slot, ctx->d_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_sample + slot], st));
-    pending[slot] = it;
-    ++polled;
-    const int prev = polled & 1;
-    const bool last = it >= max_it;
-    if (predicted > 0) {                                  // synchronous poll of the batch just enqueued
-      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[2 * n_sample + slot]));
-      if (h_flags[4 * slot] || last) done = true;
-      pending[slot] = -1;
-      continue;
-    }
-    if (pending[prev] >= 0) {
-      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[2 * n_sample + prev]));
-      if (h_flags[4 * prev]) done = true;
-      pending[prev] = -1;
-    }
-    if (!done && last) {
-      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[2 * n_sample + slot]));
-      done = true;
-    }
+    FEMO_TRY(poll.after_batch(it >= max_it, /*sync=*/predicted > 0, &done));   // with a prediction: the batch just enqueued
   }
   info->loop_allreduces = (int32_t)(ctx->n_allreduce - ar0);
   FEMO_HIP_CHECK(hipMemcpyAsync(h_flags, ctx->d_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1872,16 +1873,9 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   const int iters = h_flags[1];
   const int conv = h_flags[0] ? (h_flags[2] ? -1 : 1) : 0;
   if (conv == 1 && iters > 0) { m->pcg_prev_iters = m->pcg_last_iters; m->pcg_last_iters = iters; }
-  double acc = 0.0;
-  for (int i = 0; i < n_ev; ++i) {
-    float t = 0.f;
-    FEMO_HIP_CHECK(hipEventElapsedTime(&t, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]));
-    acc += t;
-  }
-  info->spmv_ms = acc;
-  info->spmv_samples = n_ev;
+  FEMO_TRY(spmv.report(info));
   info->pc_residual_norm = std::sqrt(ctx->h_scal[S_GAMMA + (iters & 1)]);
-  return finish(iters, conv, ctx->h_scal[S_RHO]);
+  return finish_solve(A, w.xh, x, opts->zero_guess, info, iters, conv, ctx->h_scal[S_RHO]);
 }
 
 // z = M^-1 r with the BPX preconditioner of A, in unscaled variables:
@@ -1931,57 +1925,29 @@ extern "C" int femo_solve_cg(const femo_mat* A_, int transpose, const femo_vec* 
   FEMO_TRY(ensure_s(A));
   if (transpose && !opts->zero_guess) FEMO_TRY(femo_mat_ensure_transpose(A));
   CgWork w;
-  // FEMO_FORCE_MULTI=1 runs the all-reduce code path on a 1-rank communicator (tests)
-  const bool multi = ctx->nranks > 1 || (ctx->comm != nullptr && femo_env_flag("FEMO_FORCE_MULTI"));
+  const bool multi = multi_path(ctx);
   FEMO_TRY(ensure_work(ctx, n, m->n_vert, w, multi ? 1 : 0));
   const int gv = vec_grid(ctx, n);
   const int gs = femo_spmv_grid(m);
-  int32_t* h_flags = reinterpret_cast<int32_t*>(ctx->h_scal + FEMO_NSCAL);  // 2 slots x 4 ints
+  FlagPoll poll(ctx);
   double* P = ctx->d_partials;
 
   FEMO_HIP_CHECK(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int32_t), st));
   // r0 = b - A x0 with the unscaled operator; the iteration then solves for the correction
-  const double* q0 = nullptr;
-  if (opts->zero_guess) {
-    FEMO_HIP_CHECK(hipMemsetAsync(x->d, 0, x->n * sizeof(double), st));
-  } else {
-    if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, x->d));
-    const double* vals = A->d_vals;
-    if (transpose) vals = A->d_valsT;
-    FEMO_TRY(launch_spmv(A, vals, x->d, w.q, nullptr, nullptr));
-    q0 = w.q;
-  }
+  const double* q0;
+  FEMO_TRY(initial_guess(A, transpose ? A->d_valsT : A->d_vals, x, opts->zero_guess, /*clear_x=*/true, w.q, &q0));
   hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, b->d, q0, A->d_s, w.r, w.p, w.xh, P, A->has_idrows ? A->d_idrows : nullptr);
   FEMO_HIP_CHECK(hipGetLastError());
-  // gamma0 and ||S b||^2 (all-reduced when multi): partial slots 1 and 2
-  hipLaunchKernelGGL(k_reduce_partials_at, dim3(1), dim3(1024), 0, st, gv, 2, P + FEMO_MAX_PARTIALS, ctx->d_scal);
-  FEMO_HIP_CHECK(hipGetLastError());
-  if (multi) FEMO_TRY(femo_coll_allreduce(ctx, ctx->d_scal, 2, st));
-  FEMO_HIP_CHECK(hipMemcpyAsync(ctx->h_scal, ctx->d_scal, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-  FEMO_HIP_CHECK(hipStreamSynchronize(st));
-  const double gamma0 = ctx->h_scal[0], bb = ctx->h_scal[1];
+  // gamma0 and ||S b||^2: partial slots 1 and 2
+  double gamma0, bb;
+  FEMO_TRY(initial_norms(ctx, multi, gv, P + FEMO_MAX_PARTIALS, ctx->d_scal, &gamma0, &bb));
   const double bnorm = std::sqrt(bb);
   double tol = opts->rtol * bnorm;
   if (opts->atol > tol) tol = opts->atol;
   info->rhs_norm = bnorm;
   const int max_it = opts->max_it > 0 ? opts->max_it : 10000;
-  auto finish = [&](int iters, int conv, double gamma) -> int {
-    if (n > 0) {
-      hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, st, n, opts->zero_guess ? 0 : 1, A->d_s, w.xh, x->d);
-      FEMO_HIP_CHECK(hipGetLastError());
-    }
-    FEMO_HIP_CHECK(hipEventRecord(ctx->ev1, st));
-    FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev1));
-    float ms = 0.f;
-    FEMO_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    info->iterations = iters;
-    info->converged = conv;
-    info->residual_norm = std::sqrt(gamma);
-    info->solve_ms = ms;
-    return 0;
-  };
   if (!(std::sqrt(gamma0) > tol))   // converged at once, or NaN (reported as breakdown)
-    return finish(0, gamma0 == gamma0 ? 1 : -1, gamma0);
+    return finish_solve(A, w.xh, x, opts->zero_guess, info, 0, gamma0 == gamma0 ? 1 : -1, gamma0);
   FEMO_TRY(ensure_scaled(A, transpose != 0));
 
   double hs[FEMO_NSCAL] = {0};
@@ -1991,65 +1957,48 @@ extern "C" int femo_solve_cg(const femo_mat* A_, int transpose, const femo_vec* 
   FEMO_HIP_CHECK(hipMemcpyAsync(ctx->d_scal, ctx->h_scal, sizeof hs, hipMemcpyHostToDevice, st));
   FEMO_HIP_CHECK(hipStreamSynchronize(st));  // h_scal is reused below
 
-  const int n_sample = 4, sample_from = 4;
-  int n_ev = 0;
-  // w = Ah r with both dots, folded and all-reduced into the (delta, gamma) pair of `parity`
-  auto merged_spmv = [&](int parity, bool sample) -> int {
+  SpmvSamples spmv(ctx, 4);
+  // w = Ah r with both dots, folded and all-reduced into the (delta, gamma) pair of `parity` (it < 0: not sampled)
+  auto merged_spmv = [&](int parity, int it) -> int {
     int g1 = gs, g2 = 0;
-    if (sample) FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev], st));
+    FEMO_TRY(spmv.begin(it));
     if (m->n_nbr > 0 && m->d_slices_int != nullptr) {
       FEMO_TRY(halo_spmv_overlapped(A, A->d_valsS, w.r, w.q, P, ctx->d_flags, true, true, &g1, &g2));
     } else {
       if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, w.r));
       FEMO_TRY(launch_spmv(A, A->d_valsS, w.r, w.q, P, ctx->d_flags, true, true));
     }
-    if (sample) { FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev + 1], st)); ++n_ev; }
-    hipLaunchKernelGGL(k_cgm_fold, dim3(1), dim3(1024), 0, st, g1, g2, P, ctx->d_scal + 2 * parity, ctx->d_flags);
+    FEMO_TRY(spmv.end());
+    FEMO_TRY(femo_launch_fold(1024, g1, 2, P, ctx->d_scal + 2 * parity, st, ctx->d_flags, g2, P + 2 * FEMO_MAX_PARTIALS));
     FEMO_TRY(femo_coll_allreduce(ctx, ctx->d_scal + 2 * parity, 2, st));
     return 0;
   };
-  if (multi) FEMO_TRY(merged_spmv(0, false));
+  if (multi) FEMO_TRY(merged_spmv(0, -1));
 
   const int batch = opts->check_every > 0 ? opts->check_every : 32;
-  int it = 0, polled = 0;
+  int it = 0;
   bool done = false;
-  int pending[2] = {-1, -1};
   while (!done) {
     const int it_end = it + batch < max_it ? it + batch : max_it;
     for (; it < it_end; ++it) {
       const int cur = it & 1, nxt = cur ^ 1;
-      const bool sample = it >= sample_from && it < sample_from + n_sample;
       if (multi) {
         // single-reduction CG: update from the reduced (delta, gamma) of parity cur, then the next SpMV
         hipLaunchKernelGGL(k_cgm_update, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, it, ctx->d_scal, w.q, w.r, w.p, w.sv, w.xh, ctx->d_flags);
-        FEMO_TRY(merged_spmv(nxt, sample));
+        FEMO_TRY(merged_spmv(nxt, it));
       } else {
-        if (sample) FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev], st));
+        FEMO_TRY(spmv.begin(it));
         FEMO_TRY(launch_spmv(A, A->d_valsS, w.p, w.q, P + P_DELTA * FEMO_MAX_PARTIALS, ctx->d_flags, true));
-        if (sample) { FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_ev + 1], st)); ++n_ev; }
+        FEMO_TRY(spmv.end());
         hipLaunchKernelGGL(k_cg_update_r, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, cur, gs, gv, P, ctx->d_scal, w.q, w.r, ctx->d_flags);
         hipLaunchKernelGGL(k_cg_update_xp, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, cur, it, gs, gv, P, ctx->d_scal, w.r, w.p, w.xh, ctx->d_flags);
       }
     }
     FEMO_HIP_CHECK(hipGetLastError());
-    const int slot = polled & 1;
-    FEMO_HIP_CHECK(hipMemcpyAsync(h_flags + 4 * slot, ctx->d_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    FEMO_HIP_CHECK(hipEventRecord(ctx->ev_pool[2 * n_sample + slot], st));
-    pending[slot] = it;
-    ++polled;
-    const int prev = polled & 1;
-    const bool last = it >= max_it;
-    if (pending[prev] >= 0) {
-      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[2 * n_sample + prev]));
-      if (h_flags[4 * prev]) done = true;
-      pending[prev] = -1;
-    }
-    if (!done && last) {
-      FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev_pool[2 * n_sample + slot]));
-      done = true;
-    }
+    FEMO_TRY(poll.after_batch(it >= max_it, /*sync=*/false, &done));
   }
   // final scalars: gamma of the last completed iteration sits in the (iters & 1) slot
+  int32_t* h_flags = poll.h_flags;
   FEMO_HIP_CHECK(hipMemcpyAsync(h_flags, ctx->d_flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   FEMO_HIP_CHECK(hipStreamSynchronize(st));
   const int iters = h_flags[1];
@@ -2060,20 +2009,13 @@ extern "C" int femo_solve_cg(const femo_mat* A_, int transpose, const femo_vec* 
     FEMO_HIP_CHECK(hipStreamSynchronize(st));
     gamma_f = ctx->h_scal[2 * (iters & 1) + 1];
   } else {
-    hipLaunchKernelGGL(k_reduce_partials_at, dim3(1), dim3(1024), 0, st, gv, 1, P + (P_GAMMA + (iters & 1)) * FEMO_MAX_PARTIALS, ctx->d_scal + 8);
+    FEMO_TRY(femo_launch_fold(1024, gv, 1, P + (P_GAMMA + (iters & 1)) * FEMO_MAX_PARTIALS, ctx->d_scal + 8, st));
     FEMO_HIP_CHECK(hipMemcpyAsync(ctx->h_scal, ctx->d_scal + 8, sizeof(double), hipMemcpyDeviceToHost, st));
     FEMO_HIP_CHECK(hipStreamSynchronize(st));
     gamma_f = ctx->h_scal[0];
   }
-  double acc = 0.0;
-  for (int i = 0; i < n_ev; ++i) {
-    float t = 0.f;
-    FEMO_HIP_CHECK(hipEventElapsedTime(&t, ctx->ev_pool[2 * i], ctx->ev_pool[2 * i + 1]));
-    acc += t;
-  }
-  info->spmv_ms = acc;
-  info->spmv_samples = n_ev;
-  return finish(iters, conv, gamma_f);
+  FEMO_TRY(spmv.report(info));
+  return finish_solve(A, w.xh, x, opts->zero_guess, info, iters, conv, gamma_f);
 }
 
 
@@ -2096,7 +2038,7 @@ extern "C" int femo_solve_bicgstab(const femo_mat* A_, int transpose, const femo
   FEMO_TRY(ensure_scaled(A, transpose != 0 && !scatter_T));
   CgWork w;
   FEMO_TRY(ensure_work(ctx, n, m->n_vert, w, 2));
-  const bool multi = ctx->nranks > 1 || (ctx->comm != nullptr && femo_env_flag("FEMO_FORCE_MULTI"));
+  const bool multi = multi_path(ctx);
   const int gv = vec_grid(ctx, n);
   const int gs = femo_spmv_grid(m);
   double* P = ctx->d_partials;
@@ -2104,46 +2046,23 @@ extern "C" int femo_solve_bicgstab(const femo_mat* A_, int transpose, const femo
   int32_t* h_flags = reinterpret_cast<int32_t*>(ctx->h_scal + FEMO_NSCAL);
   FEMO_HIP_CHECK(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int32_t), st));
   FEMO_HIP_CHECK(hipMemsetAsync(w.sv, 0, ctx->cg_n * sizeof(double), st));   // sv, p: gathered incl. ghosts
-  const double* q0 = nullptr;
-  if (opts->zero_guess) {
-    FEMO_HIP_CHECK(hipMemsetAsync(x->d, 0, x->n * sizeof(double), st));
-  } else {
-    if (scatter_T) {
-      FEMO_TRY(spmv_transposed_scatter(A, A->d_vals, false, x->d, w.q, nullptr));
-    } else {
-      if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, x->d));
-      FEMO_TRY(launch_spmv(A, transpose ? A->d_valsT : A->d_vals, x->d, w.q, nullptr, nullptr));
-    }
+  const double* q0;
+  if (scatter_T && !opts->zero_guess) {
+    FEMO_TRY(spmv_transposed_scatter(A, A->d_vals, false, x->d, w.q, nullptr));
     q0 = w.q;
+  } else {
+    FEMO_TRY(initial_guess(A, transpose ? A->d_valsT : A->d_vals, x, opts->zero_guess, /*clear_x=*/true, w.q, &q0));
   }
   hipLaunchKernelGGL(k_bi_init, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, b->d, q0, A->d_s, w.r, w.r0, w.p, w.q, w.xh, P);
   FEMO_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_reduce_partials_at, dim3(1), dim3(1024), 0, st, gv, 2, P, S + 12);
-  if (multi) FEMO_TRY(femo_coll_allreduce(ctx, S + 12, 2, st));
-  FEMO_HIP_CHECK(hipMemcpyAsync(ctx->h_scal, S + 12, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-  FEMO_HIP_CHECK(hipStreamSynchronize(st));
-  const double rr0 = ctx->h_scal[0], bb = ctx->h_scal[1];
+  double rr0, bb;
+  FEMO_TRY(initial_norms(ctx, multi, gv, P, S + 12, &rr0, &bb));
   const double bnorm = std::sqrt(bb);
   double tol = opts->rtol * bnorm;
   if (opts->atol > tol) tol = opts->atol;
   info->rhs_norm = bnorm;
   const int max_it = opts->max_it > 0 ? opts->max_it : 10000;
-  auto finish = [&](int iters, int conv, double rr) -> int {
-    if (n > 0) {
-      hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, st, n, opts->zero_guess ? 0 : 1, A->d_s, w.xh, x->d);
-      FEMO_HIP_CHECK(hipGetLastError());
-    }
-    FEMO_HIP_CHECK(hipEventRecord(ctx->ev1, st));
-    FEMO_HIP_CHECK(hipEventSynchronize(ctx->ev1));
-    float ms = 0.f;
-    FEMO_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    info->iterations = iters;
-    info->converged = conv;
-    info->residual_norm = std::sqrt(rr);
-    info->solve_ms = ms;
-    return 0;
-  };
-  if (!(std::sqrt(rr0) > tol)) return finish(0, rr0 == rr0 ? 1 : -1, rr0);
+  if (!(std::sqrt(rr0) > tol)) return finish_solve(A, w.xh, x, opts->zero_guess, info, 0, rr0 == rr0 ? 1 : -1, rr0);
   double hs[FEMO_NSCAL] = {0};
   hs[B_RHO] = rr0; hs[B_RHO_OLD] = 1.0; hs[B_ALPHA] = 1.0; hs[B_OMEGA] = 1.0; hs[B_RR] = rr0; hs[B_TOL2] = tol * tol;
   memcpy(ctx->h_scal, hs, sizeof hs);
@@ -2165,7 +2084,7 @@ extern "C" int femo_solve_bicgstab(const femo_mat* A_, int transpose, const femo
         if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, w.p));
         FEMO_TRY(launch_spmv(A, A->d_valsS, w.p, w.q, P, ctx->d_flags, true, false, nullptr, 0, nullptr, w.r0));   // v, (r0, v)
       }
-      hipLaunchKernelGGL(k_bi_fold, dim3(1), dim3(1024), 0, st, scatter_T ? gv : gs, 1, P, S + B_R0V, ctx->d_flags);
+      FEMO_TRY(femo_launch_fold(1024, scatter_T ? gv : gs, 1, P, S + B_R0V, st, ctx->d_flags));
       if (multi) FEMO_TRY(femo_coll_allreduce(ctx, S + B_R0V, 1, st));
       hipLaunchKernelGGL(k_bi_s, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, S, w.r, w.q, w.sv, ctx->d_flags);
       if (scatter_T) {
@@ -2176,10 +2095,10 @@ extern "C" int femo_solve_bicgstab(const femo_mat* A_, int transpose, const femo
         if (m->n_nbr > 0) FEMO_TRY(halo_raw(m, w.sv));
         FEMO_TRY(launch_spmv(A, A->d_valsS, w.sv, w.t, P, ctx->d_flags, true, false, nullptr, 0, nullptr, nullptr, true));  // t, (s,t), (t,t)
       }
-      hipLaunchKernelGGL(k_bi_fold, dim3(1), dim3(1024), 0, st, scatter_T ? gv : gs, 2, P, S + B_TS, ctx->d_flags);
+      FEMO_TRY(femo_launch_fold(1024, scatter_T ? gv : gs, 2, P, S + B_TS, st, ctx->d_flags));
       if (multi) FEMO_TRY(femo_coll_allreduce(ctx, S + B_TS, 2, st));
       hipLaunchKernelGGL(k_bi_xr, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, it, S, w.p, w.sv, w.t, w.r0, w.xh, w.r, P, ctx->d_flags);
-      hipLaunchKernelGGL(k_bi_fold, dim3(1), dim3(1024), 0, st, gv, 2, P, S + 12, ctx->d_flags);
+      FEMO_TRY(femo_launch_fold(1024, gv, 2, P, S + 12, st, ctx->d_flags));
       if (multi) FEMO_TRY(femo_coll_allreduce(ctx, S + 12, 2, st));
       hipLaunchKernelGGL(k_bi_set_rho, dim3(1), dim3(1), 0, st, S + 12, S, ctx->d_flags);
     }
@@ -2193,5 +2112,5 @@ extern "C" int femo_solve_bicgstab(const femo_mat* A_, int transpose, const femo
   FEMO_HIP_CHECK(hipStreamSynchronize(st));
   const int conv = h_flags[0] ? (h_flags[2] ? -1 : 1) : 0;
   const int iters = h_flags[0] ? h_flags[1] : it;
-  return finish(iters, conv, ctx->h_scal[B_RR]);
+  return finish_solve(A, w.xh, x, opts->zero_guess, info, iters, conv, ctx->h_scal[B_RR]);
 }
