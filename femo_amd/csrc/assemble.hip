@@ -904,7 +904,7 @@ __global__ __launch_bounds__(64) void k_poisson_system_lds(
     const int32_t* __restrict__ rowlen, const double* __restrict__ x, const double* __restrict__ u,
     const double* __restrict__ load, const uint8_t* __restrict__ bcmask, const double* __restrict__ bcval,
     double* __restrict__ diag0, double* __restrict__ vals0, double* __restrict__ diag1, double* __restrict__ vals1,
-    double* __restrict__ rhs, const uint64_t* __restrict__ bc_rowmask, int debug_skip) {
+    double* __restrict__ rhs, const uint64_t* __restrict__ bc_rowmask) {
   extern __shared__ double lds_row[];
   double* strip = lds_row;                       // [nb][64]
   double* nx = lds_row + nb * 64;                // [nb][D][64]
@@ -914,7 +914,7 @@ __global__ __launch_bounds__(64) void k_poisson_system_lds(
   const int64_t row = (slice << 6) + lane;
   const bool valid = row < n_rows;
   const int64_t vb = vptr[slice], mb = mptr[slice];
-  const int nvis = (debug_skip & 1) ? 0 : (int)((vptr[slice + 1] - vb) >> 6);
+  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
   const int wm = (int)((mptr[slice + 1] - mb) >> 6);
   const int32_t* dl = sdelta + slice * sdelta_stride;
   const bool regular = dl[0] != INT32_MIN;
@@ -928,7 +928,7 @@ __global__ __launch_bounds__(64) void k_poisson_system_lds(
   // indices of a chunk are loaded before the first coordinate gather and all gathers before the first LDS
   // write: two memory round trips per 16 columns instead of two per column.
   constexpr int PC = 16;
-  for (int k0 = 0; k0 < ((debug_skip & 2) ? 0 : wm); k0 += PC) {
+  for (int k0 = 0; k0 < wm; k0 += PC) {
     uint32_t c[PC];
 #pragma unroll
     for (int i = 0; i < PC; ++i) {
@@ -1080,7 +1080,7 @@ __global__ void k_impose_bc(int64_t n, const double* __restrict__ u, const uint8
     out[i] = (bcmask != nullptr && bcmask[i]) ? bcval[i] : u[i];
 }
 
-template <int D, int NB, bool WANT_RHS, bool HAS_V0, bool HAS_V1, bool LDS_ATOMIC, bool HAVE_BC = true>
+template <int D, int NB, bool WANT_RHS, bool HAS_V0, bool HAS_V1, bool HAVE_BC = true>
 __global__ __launch_bounds__(64) void k_poisson_system_pipe(
     int64_t n_rows, int64_t n_slices, const int64_t* __restrict__ vptr, const P1Rec12* __restrict__ visit_rec,
     const int64_t* __restrict__ mptr, const int32_t* __restrict__ cols, const int32_t* __restrict__ rowlen,
@@ -1241,10 +1241,7 @@ __global__ __launch_bounds__(64) void k_poisson_system_pipe(
       double kk[D];
       poisson_pairs<D>(R.xo, V.o, V.wt, kk);
 #pragma unroll
-      for (int j = 0; j < D; ++j) {
-        if constexpr (LDS_ATOMIC) (void)__hip_atomic_fetch_add(&strip[V.pos[j] * 64 + lane], kk[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        else strip[V.pos[j] * 64 + lane] = __dadd_rn(strip[V.pos[j] * 64 + lane], kk[j]);
-      }
+      for (int j = 0; j < D; ++j) (void)__hip_atomic_fetch_add(&strip[V.pos[j] * 64 + lane], kk[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     };
     int base = 0;
     for (; base + CH <= nvis; base += CH) {
@@ -1584,8 +1581,7 @@ int femo_launch_residual(femo_mesh* m, int pde, const double* params, const doub
     // K u - L is the Newton right-hand side without a Dirichlet set: the pipelined system kernel in its
     // rhs-only form (1.3 ms at C4 against 2.2 ms for the per-visit-gather walk below)
     const int nbr = (m->max_rowlen + 1) & ~1;
-    static const bool walk = FEMO_TUNE_ENV("FEMO_RESIDUAL_WALK") != nullptr;
-    if (!walk && nbr <= (m->tdim == 3 ? 16 : 8))
+    if (nbr <= (m->tdim == 3 ? 16 : 8))
       return femo_launch_system(m, pde, params, u, f, aux, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, r, f_uid, f_gen, nullptr);
     FEMO_TRY(ensure_load_vector(m, f, f_uid, f_gen));
     FEMO_ROW_WALK(m, 0, nb, st, u, (const double*)m->d_load, r);
@@ -1680,31 +1676,28 @@ int femo_launch_system(femo_mesh* m, int pde, const double* params, const double
   // rows with up to 64 neighbours: the row neighbourhood fits in LDS (one wave per workgroup)
   const int nbr = (m->max_rowlen + 1) & ~1;
   const size_t lds_row = (size_t)nbr * (m->tdim + 1) * 64 * sizeof(double);
-  static const bool gather_only = FEMO_TUNE_ENV("FEMO_ASSEMBLY_GATHER") != nullptr;
-  if (lds_row <= 128 * 1024 && !gather_only) {
+  if (lds_row <= 128 * 1024) {
     FEMO_TRY(ensure_visit_weights(m));
     const int64_t ns = m->n_slices;
     const P1Rec12* rec = reinterpret_cast<const P1Rec12*>(m->d_visit_rec);
-    static const int dbg = FEMO_TUNE_ENV("FEMO_DEBUG_SKIP") ? atoi(FEMO_TUNE_ENV("FEMO_DEBUG_SKIP")) : 0;     // timing experiments (FEMO_TUNING builds)
 #define FEMO_SYS_LDS(D)                                                                                                       \
     do {                                                                                                                      \
       auto k = k_poisson_system_lds<D, 12>;                                                                                   \
       if (lds_row > 64 * 1024) FEMO_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row)); \
       hipLaunchKernelGGL(k, dim3(ns), dim3(64), lds_row, m->ctx->stream, m->n_rows, ns, nbr, m->d_vptr, rec, m->d_mptr, m->d_cols,    \
-                         m->d_sdelta, m->sdelta_stride, m->d_rowlen, m->d_x, u, load, bcmask, bcval, diag0, vals0, diag1, vals1, rhs, bcmask ? bc_rowmask : nullptr, dbg); \
+                         m->d_sdelta, m->sdelta_stride, m->d_rowlen, m->d_x, u, load, bcmask, bcval, diag0, vals0, diag1, vals1, rhs, bcmask ? bc_rowmask : nullptr); \
     } while (0)
     // persistent pipelined kernel: rows of up to 16 entries, a Dirichlet set with its row masks, and one of the
-    // three combinations the operators ask for: A + rhs, dR/du + A, rhs only
-    // 1 (default): persistent waves, one per SIMD; 2: the same without LDS atomics; 0: the LDS kernel.  Round 5 tried a third
-    // form -- half-slice waves, two per SIMD, the two lanes of a row splitting its visits (commit 8f1a594, DESIGN_LOG.md) --
-    // which produced the same off-diagonal bits and the same time: the kernel is bound by neither latency nor the LDS atomics
-    // but by its instruction stream (57 fp64 instructions per visit at 8 cycles each on the half-rate fp64 pipe of gfx950,
-    // plus 9 LDS gathers), i.e. by the 12 pair evaluations per cell of the owner-computes formulation.
-    static const int pipe_mode = FEMO_TUNE_ENV("FEMO_ASSEMBLY_PIPE") ? atoi(FEMO_TUNE_ENV("FEMO_ASSEMBLY_PIPE")) : 1;
+    // three combinations the operators ask for: A + rhs, dR/du + A, rhs only.  Persistent waves, one per SIMD; round 5
+    // tried a second form -- half-slice waves, two per SIMD, the two lanes of a row splitting its visits (commit 8f1a594,
+    // DESIGN_LOG.md) -- which produced the same off-diagonal bits and the same time: the kernel is bound by neither
+    // latency nor the LDS atomics but by its instruction stream (57 fp64 instructions per visit at 8 cycles each on the
+    // half-rate fp64 pipe of gfx950, plus 9 LDS gathers), i.e. by the 12 pair evaluations per cell of the owner-computes
+    // formulation.
     const int NBp = m->tdim == 3 ? (nbr <= 14 ? 14 : 16) : 8;
     const bool combo_a = rhs && !vals0 && vals1, combo_b = !rhs && vals0 && vals1, combo_c = rhs && !vals0 && !vals1;
     const bool no_bc_residual = combo_c && bcmask == nullptr;          // evaluate_residuals: K u - L, no Dirichlet treatment
-    if (pipe_mode != 0 && nbr <= NBp && ((bcmask != nullptr && bc_rowmask != nullptr && (combo_a || combo_b || combo_c)) || no_bc_residual)) {
+    if (nbr <= NBp && ((bcmask != nullptr && bc_rowmask != nullptr && (combo_a || combo_b || combo_c)) || no_bc_residual)) {
       hipStream_t st = m->ctx->stream;
       if (!m->d_pipe_dummy) {
         FEMO_HIP_CHECK(hipMalloc(&m->d_pipe_dummy, 64 * 2 * sizeof(double)));
@@ -1712,21 +1705,16 @@ int femo_launch_system(femo_mesh* m, int pde, const double* params, const double
       }
       if (rhs && !no_bc_residual) hipLaunchKernelGGL(k_impose_bc, dim3(cell_grid(m->n_vert)), dim3(FEMO_BLOCK), 0, st, m->n_vert, u, bcmask, bcval, m->d_ubc);
       const double* ubc = no_bc_residual ? u : m->d_ubc;
-      static const int waves_per_cu = FEMO_TUNE_ENV("FEMO_ASSEMBLY_WAVES") ? std::max(1, atoi(FEMO_TUNE_ENV("FEMO_ASSEMBLY_WAVES"))) : 4;
-      // one wave per SIMD: the LDS request is raised so that a fifth workgroup cannot land on a CU (it would share a
-      // SIMD with another persistent wave and both would take twice as long)
-      const size_t lds_need = (size_t)NBp * (m->tdim + 1) * 64 * sizeof(double);
-      const size_t lds_pipe = waves_per_cu <= 4 ? std::max<size_t>(lds_need, 34 * 1024) : lds_need;
-      const unsigned grid = (unsigned)std::min<int64_t>(ns, (int64_t)m->ctx->n_cu * waves_per_cu);
-#define FEMO_SYS_PIPE(D, NB, R, V0, V1, AT)                                                                                      \
-      hipLaunchKernelGGL((k_poisson_system_pipe<D, NB, R, V0, V1, AT>), dim3(grid), dim3(64), lds_pipe, st, m->n_rows, ns, m->d_vptr, rec, \
+      // one wave per SIMD (4 per CU): the LDS request is raised so that a fifth workgroup cannot land on a CU (it would
+      // share a SIMD with another persistent wave and both would take twice as long)
+      const size_t lds_pipe = std::max<size_t>((size_t)NBp * (m->tdim + 1) * 64 * sizeof(double), 34 * 1024);
+      const unsigned grid = (unsigned)std::min<int64_t>(ns, (int64_t)m->ctx->n_cu * 4);
+#define FEMO_SYS_PIPE(D, NB, R, V0, V1, BC)                                                                                      \
+      hipLaunchKernelGGL((k_poisson_system_pipe<D, NB, R, V0, V1, BC>), dim3(grid), dim3(64), lds_pipe, st, m->n_rows, ns, m->d_vptr, rec, \
                          m->d_mptr, m->d_cols, m->d_rowlen, m->d_x, u, ubc, load, bcval, diag0, vals0, diag1, vals1, rhs,        \
                          bc_rowmask, m->d_pipe_dummy)
 #define FEMO_SYS_PIPE_COMBO(D, NB)                                                                                           \
-      do { if (no_bc_residual) hipLaunchKernelGGL((k_poisson_system_pipe<D, NB, true, false, false, true, false>), dim3(grid), dim3(64), lds_pipe, st, m->n_rows, ns, m->d_vptr, rec, \
-                         m->d_mptr, m->d_cols, m->d_rowlen, m->d_x, u, ubc, load, bcval, diag0, vals0, diag1, vals1, rhs, bc_rowmask, m->d_pipe_dummy); \
-           else if (pipe_mode == 2) { if (combo_a) FEMO_SYS_PIPE(D, NB, true, false, true, false); else if (combo_b) FEMO_SYS_PIPE(D, NB, false, true, true, false);  \
-           else FEMO_SYS_PIPE(D, NB, true, false, false, false); }                                                             \
+      do { if (no_bc_residual) FEMO_SYS_PIPE(D, NB, true, false, false, false);                                                   \
            else if (combo_a) FEMO_SYS_PIPE(D, NB, true, false, true, true); else if (combo_b) FEMO_SYS_PIPE(D, NB, false, true, true, true);  \
            else FEMO_SYS_PIPE(D, NB, true, false, false, true); } while (0)
       if (m->tdim == 3) { if (NBp == 14) FEMO_SYS_PIPE_COMBO(3, 14); else FEMO_SYS_PIPE_COMBO(3, 16); }

@@ -1199,7 +1199,10 @@ struct MergedCarry {
   int64_t n_intc; const int32_t* int_idx;
   double* gs_c; double* h_c; const double* coef_c;
   int64_t n_top_buf;                // nodes of level T-1 (the dense part of the buffer)
-  int dbg;                          // timing experiments (FEMO_TUNING builds): 1 = workgroup 0 returns early, 2 = the carriers do
+  // Always 0, so the early exits it guards below are never taken.  Kept because the kernel sits at the 128-VGPR cap of
+  // 1024-thread workgroups and spills: without these tests the register allocator moves spills into workgroup 0's path
+  // (the critical one) and the launch takes 77.0 us instead of 74.5 (bench cube, measured).
+  int dbg;
   int64_t sep_off;                  // LDS offset (doubles) of the scratch of lattice_restrict3_sep, -1: the 27-tap restrictions
   int flat;                         // 3-D, 1 <= levels below T-1 <= 4, scratch fits: the chain below level T-1 in ONE down and ONE up step (below)
 };
@@ -1656,7 +1659,6 @@ struct PackArgs {
   int nb_q[2]; const double* Pq[2];
   int nb_rr; const double* Prr;
   double* buf;
-  int dbg;
 };
 __global__ __launch_bounds__(256) void k_pack_merged(PackArgs a, const int32_t* __restrict__ done) {
   if (done != nullptr && *done) return;
@@ -1683,15 +1685,13 @@ __global__ __launch_bounds__(256) void k_pack_merged(PackArgs a, const int32_t* 
     return;
   }
   for (int64_t i = t0; i < a.n_shared; i += stride) a.buf[i] = a.h[a.shared_idx[i]];
-  if (!(a.dbg & 2))
-    for (int64_t i = t0; i < a.n_top; i += stride) a.buf[a.n_shared + i] = lattice_restrict_node32((int)i, a.nc, a.nf, a.dim, a.h);
+  for (int64_t i = t0; i < a.n_top; i += stride) a.buf[a.n_shared + i] = lattice_restrict_node32((int)i, a.nc, a.nf, a.dim, a.h);
   double gg = 0.0, gh = 0.0, hh = 0.0;
-  if (!(a.dbg & 1))
-    for (int64_t i = t0; i < a.n_int; i += stride) {
-      const int32_t j = a.int_idx[i];
-      const double c = a.coef[j], g = a.gs[j], h = a.h[j];
-      gg += c * g * g; gh += c * g * h; hh += c * h * h;
-    }
+  for (int64_t i = t0; i < a.n_int; i += stride) {
+    const int32_t j = a.int_idx[i];
+    const double c = a.coef[j], g = a.gs[j], h = a.h[j];
+    gg += c * g * g; gh += c * g * h; hh += c * h * h;
+  }
   if (t0 - threadIdx.x < a.n_int) {                  // workgroups that saw entries of the list (wave-uniform)
     t = femo_block_sum<256>(gg, red); if (threadIdx.x == 0) atomicAdd(&tail[4], t);
     t = femo_block_sum<256>(gh, red); if (threadIdx.x == 0) atomicAdd(&tail[5], t);
@@ -1815,7 +1815,6 @@ int femo_pc_build(femo_mesh* m) {
     int64_t fullest = 0;
     for (size_t b = 0; b + 1 < P.brick_ptr.size(); ++b) fullest = std::max<int64_t>(fullest, P.brick_ptr[b + 1] - P.brick_ptr[b]);
     pc->brick_pf = fullest <= 2 * FEMO_BLOCK ? 2 : (fullest <= 3 * FEMO_BLOCK ? 3 : 4);
-    if (const char* env = FEMO_TUNE_ENV("FEMO_BRICK_PF")) pc->brick_pf = std::min(4, std::max(2, atoi(env)));
   }
   FEMO_TRY(upload(&pc->d_bin_ptr, P.bin_ptr));
   FEMO_TRY(upload(&pc->d_brick_base, P.brick_base));
@@ -1908,7 +1907,6 @@ static int bricks_per_cu(int dim, int pf) {
   if (c == 0) {
     if (dim == 3) c = pf == 2 ? bricks_per_cu_of<3, 2>() : (pf == 3 ? bricks_per_cu_of<3, 3>() : bricks_per_cu_of<3, 4>());
     else c = pf == 2 ? bricks_per_cu_of<2, 2>() : (pf == 3 ? bricks_per_cu_of<2, 3>() : bricks_per_cu_of<2, 4>());
-    if (const char* env = FEMO_TUNE_ENV("FEMO_BRICKS_PER_CU")) c = std::max(1, atoi(env));
   }
   return c;
 }
@@ -2124,7 +2122,7 @@ int femo_pc_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const do
   int64_t below = 0;
   for (int l = 0; l + 1 < T; ++l) below += pc->L[l].nodes;
   const bool fused_cycle = nf >= 2 && T >= 2 && T < FEMO_PC_MAX_LEVELS - 1 && below * 2 * (int64_t)sizeof(double) <= 144 * 1024 &&
-                           pc->L[T - 1].nodes <= FEMO_COARSE_TOP_MAX && FEMO_TUNE_ENV("FEMO_BPX_UNFUSED_LATTICE") == nullptr;
+                           pc->L[T - 1].nodes <= FEMO_COARSE_TOP_MAX;
   pc->fused_cycle_seen = fused_cycle;
   FEMO_REQUIRE(xupdate == nullptr || fused_cycle, "femo_pc_apply: the x update rides in the fused lattice cycle only");
   if (fused_cycle) {
@@ -2279,7 +2277,7 @@ static bool merged_shape_ok(const femo_pc* pc, bool multi) {
 
 bool femo_pc_merged_ok(femo_mesh* m) {
   // FEMO_PCG_CLASSIC: A/B switch and the tests of the classic loop (read per solve, never per launch)
-  if (femo_env_flag("FEMO_PCG_CLASSIC") || femo_env_flag("FEMO_BPX_DENSE_ALLREDUCE") || femo_env_flag("FEMO_BPX_UNFUSED_LATTICE")) return false;
+  if (femo_env_flag("FEMO_PCG_CLASSIC") || femo_env_flag("FEMO_BPX_DENSE_ALLREDUCE")) return false;
   if (femo_pc_build(m) != 0) return false;
   return merged_shape_ok(m->pc, m->ctx->nranks > 1);
 }
@@ -2358,8 +2356,6 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
     for (int l = 0; l < 2; ++l) { a.nb_q[l] = init ? 0 : V.nb_q[l]; a.Pq[l] = V.Pq[l]; }
     a.nb_rr = init ? 0 : std::max(1, ctx->n_cu - 1); a.Prr = pc->d_rr_partials;
     a.buf = pc->d_mbuf;
-    static const int dbg_pack = FEMO_TUNE_ENV("FEMO_DEBUG_PACK") ? atoi(FEMO_TUNE_ENV("FEMO_DEBUG_PACK")) : 0;
-    a.dbg = dbg_pack;
     const int64_t work = std::max(std::max(a.n_shared, a.n_int), n_top);
     const unsigned gp = 1u + (unsigned)std::min<int64_t>(PACK_GRID, std::max<int64_t>(1, (work + 255) / 256));
     hipLaunchKernelGGL(k_pack_merged, dim3(gp), dim3(256), 0, st, a, done);
@@ -2399,14 +2395,13 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
   mc.n_intc = multi ? pc->n_mint_coarse : 0; mc.int_idx = pc->d_mint_idx;
   mc.gs_c = GS(T); mc.h_c = H(T, par); mc.coef_c = pc->L[T].coef;
   mc.n_top_buf = n_top;
-  static const int dbg_coarse = FEMO_TUNE_ENV("FEMO_DEBUG_COARSE") ? atoi(FEMO_TUNE_ENV("FEMO_DEBUG_COARSE")) : 0;
-  mc.dbg = dbg_coarse;
+  mc.dbg = 0;
   // scratch of the separable restrictions (3-D): the largest of the top restriction (one rank: level T -> T-1, + its output)
   // and the LDS-resident ones; behind the levels when it fits
   size_t lds_all = lds;
   mc.sep_off = -1;
   mc.flat = 0;
-  if (pc->dim == 3 && !femo_env_flag("FEMO_BPX_TAPS27")) {
+  if (pc->dim == 3) {
     auto need = [&](const int* nc, const int* nfn, bool with_out) -> int64_t {
       const int64_t s1 = (int64_t)(nc[0] + 1) * (nfn[1] + 1) * (nfn[2] + 1), s2 = (int64_t)(nc[0] + 1) * (nc[1] + 1) * (nfn[2] + 1);
       return s1 + s2 + (with_out ? (int64_t)(nc[0] + 1) * (nc[1] + 1) * (nc[2] + 1) : 0);
@@ -2419,7 +2414,7 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
     // (the z-pass of the flattened chain reads the prefetched coefficient of node `tid`: one trip per level, i.e. every level
     // below T-1 must have at most 1024 nodes -- true for the m0 in {2, 3} doubling lattices with TOP_MAX = 5120; checked here)
     const bool one_trip = top >= 1 && pc->L[top - 1].nodes <= 1024;
-    if (top >= 1 && top <= 4 && one_trip && !femo_env_flag("FEMO_BPX_CHAIN")) {
+    if (top >= 1 && top <= 4 && one_trip) {
       const int* nt = pc->L[top].n;
       for (int k = 1; k <= top; ++k) {
         const int* nc = pc->L[top - k].n;
@@ -2461,8 +2456,7 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
   const int32_t* tile_list = pc->n_my_tiles < tiles ? pc->d_my_tiles : nullptr;      // all of them: walk the plain range
   if (tile_list != nullptr) tiles = pc->n_my_tiles;
   // 128 threads per tile when 256-thread workgroups would not all be resident at once (see the kernel)
-  static const int bt_env = FEMO_TUNE_ENV("FEMO_PROLONG3_BT") ? atoi(FEMO_TUNE_ENV("FEMO_PROLONG3_BT")) : 0;
-  const bool small_blocks = bt_env ? bt_env == 128 : tiles > 2048;      // (1.03 M rows, 1000 tiles: 7.7 us with 256 threads, 8.5 with 128)
+  const bool small_blocks = tiles > 2048;      // (1.03 M rows, 1000 tiles: 7.7 us with 256 threads, 8.5 with 128)
   const int grid3 = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, small_blocks ? 4096 : 2048));
   const int nb_dot = multi ? 0 : grid3;
   if (pc->dim == 3) {

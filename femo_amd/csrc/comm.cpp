@@ -133,13 +133,12 @@ int femo_coll_neighbors(femo_ctx* ctx, int n_nbr, const int32_t* nbr, const int6
   }
   if (ctx->emu != nullptr) return emu_neighbors(ctx, n_nbr, nbr, send_ptr, d_send, recv_ptr, d_recv, st);
   FEMO_REQUIRE(ctx->comm != nullptr, "halo exchange before femo_comm_init");
-  const ncclComm_t comm = ctx->comm_halo != nullptr ? ctx->comm_halo : ctx->comm;
   FEMO_NCCL_CHECK(ncclGroupStart());
   for (int k = 0; k < n_nbr; ++k) {
     const int64_t sc = send_ptr[k + 1] - send_ptr[k];
     const int64_t rc = recv_ptr[k + 1] - recv_ptr[k];
-    if (sc > 0) FEMO_NCCL_CHECK(ncclSend(d_send + send_ptr[k], (size_t)sc, ncclDouble, nbr[k], comm, st));
-    if (rc > 0) FEMO_NCCL_CHECK(ncclRecv(d_recv + recv_ptr[k], (size_t)rc, ncclDouble, nbr[k], comm, st));
+    if (sc > 0) FEMO_NCCL_CHECK(ncclSend(d_send + send_ptr[k], (size_t)sc, ncclDouble, nbr[k], ctx->comm, st));
+    if (rc > 0) FEMO_NCCL_CHECK(ncclRecv(d_recv + recv_ptr[k], (size_t)rc, ncclDouble, nbr[k], ctx->comm, st));
   }
   FEMO_NCCL_CHECK(ncclGroupEnd());
   return 0;

@@ -66,14 +66,9 @@ inline hipError_t femo_counted_device_sync() { femo_host_sync_count.fetch_add(1,
     if (rc__ != 0) return rc__;                                                     \
   } while (0)
 
-// Tuning / timing switches read from the environment exist only in builds with -DFEMO_TUNING (make TUNING=1): the
-// product library never calls getenv on a launch path.  Functional options that tests select
-// (FEMO_FORCE_MULTI, FEMO_HOST_VERIFY, FEMO_BPX_DENSE_ALLREDUCE, FEMO_BPX_FUSED, FEMO_SHELL_NO_*) are read once.
-#if defined(FEMO_TUNING)
-#define FEMO_TUNE_ENV(name) getenv(name)
-#else
-#define FEMO_TUNE_ENV(name) (static_cast<const char*>(nullptr))
-#endif
+// Options read from the environment ("Environment switches") are read once per solve or set-up, never
+// per launch: the fall-backs and comparison paths that tests and bench.py select (FEMO_FORCE_MULTI, FEMO_HOST_VERIFY,
+// FEMO_BPX_DENSE_ALLREDUCE, FEMO_BPX_FUSED, FEMO_PCG_CLASSIC, FEMO_SHELL_TRILINEAR, FEMO_SHELL_NO_*, ...).
 inline bool femo_env_flag(const char* name) { return getenv(name) != nullptr; }
 
 // ------------------------------------------------------------- constants ----
@@ -134,13 +129,8 @@ struct femo_ctx {
   double* h_scal = nullptr;      // pinned mirror: FEMO_NSCAL doubles + 4 int32
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<hipEvent_t> ev_pool;
+  // all collectives, the neighbour exchanges on the comm stream included: RCCL orders the two streams' operations itself
   ncclComm_t comm = nullptr;
-  // The neighbour exchanges (ncclSend/ncclRecv on the comm stream, overlapped with the interior SpMV) have a communicator
-  // of their own (ncclCommSplit of `comm`, round 5): RCCL serialises the operations of ONE communicator, so on a shared
-  // one the halo exchange of iteration k+1 and the all-reduce of iteration k could not be in flight together.  Opt-in
-  // (FEMO_SPLIT_COMM=1, round 6) and agreed on collectively in femo_comm_init: null on EVERY rank unless the split worked on
-  // every rank; the default is the single communicator.
-  ncclComm_t comm_halo = nullptr;
   struct femo_emu_group* emu = nullptr;      // in-process rank emulation (tests; comm.cpp)
   bool model = false;                        // femo_comm_model: N-rank code paths, collectives complete without moving data
   int rank = 0, nranks = 1;

@@ -33,7 +33,6 @@
 #include <unistd.h>
 
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cstdlib>
 #include <fstream>
@@ -237,17 +236,6 @@ int ensure_copy_stream(femo_ctx* c) {
   return 0;
 }
 
-// FEMO_HOST_TRACE=1: one line per host-side operation on stderr (what, MB, ms)
-struct Trace {
-  const char* what; int64_t bytes; std::chrono::steady_clock::time_point t0; bool on;
-  Trace(const char* w, int64_t b) : what(w), bytes(b), on(FEMO_TUNE_ENV("FEMO_HOST_TRACE") != nullptr) { if (on) t0 = std::chrono::steady_clock::now(); }
-  ~Trace() {
-    if (!on) return;
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    fprintf(stderr, "[femo host] %-28s %9.2f MB %8.3f ms\n", what, bytes / 1e6, ms);
-  }
-};
-
 // staging ring of the context -------------------------------------------------------
 constexpr int64_t STAGE_DOUBLES = int64_t(1) << 20;     // 8 MiB per slot
 
@@ -357,7 +345,6 @@ int femo_host_alloc(int64_t bytes, void** out) {
     }
   }
   void* p = nullptr;
-  Trace tr("hipHostMalloc", (int64_t)need);
   FEMO_HIP_CHECK(hipHostMalloc(&p, need, hipHostMallocDefault));
   HostBlock b;
   b.base = static_cast<char*>(p); b.bytes = need; b.pooled = true;
@@ -466,7 +453,6 @@ int femo_host_fill(double* p, int64_t n, double value) {
   FEMO_REQUIRE(p || n == 0, "null argument");
   if (n == 0) return 0;
   FEMO_TRY(wait_block(p));
-  Trace tr("host_fill", n * 8);
   HostPool& P = HostPool::get();
   const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(P.threads(), n >> 16));
   P.run(parts, [&](int k) {
@@ -486,7 +472,6 @@ int femo_host_copy(double* dst, const double* src, int64_t n) {
   FEMO_REQUIRE((dst && src) || n == 0, "null argument");
   FEMO_TRY(wait_block(src));
   FEMO_TRY(wait_block(dst));
-  Trace tr("host_copy", n * 8);
   par_stream(dst, src, n, 0);
   femo_host_touch(dst);
   return 0;
@@ -536,7 +521,6 @@ int femo_host_axpby(int64_t n, double a, const double* x, double b, double* y) {
     }
     if (uid != 0) {
       if (x_pending && y_ready != nullptr) {
-        Trace tr("host_axpby (deferred)", n * 8);
         FEMO_HIP_CHECK(hipSetDevice(pctx->device));
         FEMO_HIP_CHECK(hipLaunchHostFunc(pctx->copy_stream, run_deferred_scale, new DeferredScale{y, x, n, a}));
         FEMO_HIP_CHECK(hipEventRecord(y_ready, pctx->copy_stream));
@@ -544,7 +528,6 @@ int femo_host_axpby(int64_t n, double a, const double* x, double b, double* y) {
         if (x_ready != nullptr) FEMO_HIP_CHECK(hipEventRecord(x_ready, pctx->copy_stream));
       } else {
         FEMO_TRY(wait_block(x));
-        Trace tr("host_axpby", n * 8);
         par_stream(y, x, n, 2, a, 0.0);
       }
       std::lock_guard<std::mutex> lk(g_mu);
@@ -556,7 +539,6 @@ int femo_host_axpby(int64_t n, double a, const double* x, double b, double* y) {
     }
   }
   FEMO_TRY(wait_block(x));
-  Trace tr("host_axpby", n * 8);
   par_stream(y, x, n, 2, a, b);
   femo_host_touch(y);
   return 0;
@@ -599,7 +581,6 @@ int femo_vec_set_host(femo_vec* v, const double* host, int64_t n) {
       }
     }
   }
-  Trace tr(src == v && src ? "set_host (skipped)" : (src ? "set_host (d2d)" : (pinned ? "set_host (pinned)" : "set_host (staged)")), n * 8);
   int elided = 0;
   if (src != nullptr && src == v && src_scale == 1.0) {
     elided = 1;                                          // v still holds exactly this content
@@ -674,7 +655,6 @@ int femo_vec_set_host_deferred(femo_vec* v, const double* host, int64_t n) {
   FEMO_TRY(ensure_copy_stream(c));
   femo_vec_touch(v);                                     // earlier copy-outs / uploads of v first; new generation
   if (v->h2d_ev == nullptr) FEMO_HIP_CHECK(hipEventCreateWithFlags(&v->h2d_ev, hipEventDisableTiming));
-  Trace tr("set_host (deferred)", n * 8);
   hipEvent_t ready = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -739,7 +719,6 @@ static int get_host_impl(const femo_vec* v, double* host, int64_t n, int op, boo
   }
   if (op == 1 && mirror != nullptr) {
     // host holds exactly mirror's content: host + v = mirror + v, formed on the device and copied out at DMA rate
-    Trace tr("add_to_host (device sum)", n * 8);
     if (verify_enabled()) {
       std::vector<double> chk((size_t)n);
       FEMO_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -762,7 +741,6 @@ static int get_host_impl(const femo_vec* v, double* host, int64_t n, int op, boo
     return 0;
   }
   if (lazy && pinned && op == 0) {
-    Trace tr("get_host (async)", n * 8);
     FEMO_TRY(ensure_copy_stream(c));
     femo_vec* vv = const_cast<femo_vec*>(v);
     if (vv->d2h_ev == nullptr) FEMO_HIP_CHECK(hipEventCreateWithFlags(&vv->d2h_ev, hipEventDisableTiming));
@@ -789,10 +767,7 @@ static int get_host_impl(const femo_vec* v, double* host, int64_t n, int op, boo
     }
     return 0;
   }
-  {
-    Trace tr(op ? "add_to_host" : (pinned ? "get_host (pinned)" : "get_host (staged)"), n * 8);
-    FEMO_TRY(d2h(v, host, n, pinned, op));
-  }
+  FEMO_TRY(d2h(v, host, n, pinned, op));
   std::lock_guard<std::mutex> lk(g_mu);
   if (pinned && op == 0) { ++g_stats.d2h_pinned; g_stats.d2h_pinned_bytes += n * 8; }
   else { ++g_stats.d2h_staged; g_stats.d2h_staged_bytes += n * 8; }

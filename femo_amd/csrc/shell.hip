@@ -17,7 +17,6 @@
 //   * partials and outputs: (dR/dh)^T lambda element by element from the strains of w and lambda, load and its
 //     transpose, compliance, mass, elastic energy, the aggregated von Mises stress and its projection onto the vertices.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2297,56 +2296,10 @@ __global__ __launch_bounds__(256) void k_chol_update(int64_t N, int kb, double* 
   tile_foreach(acc, [&](int r, int c, double v) { g[(int64_t)r * N + c] -= v; });
 }
 
-// row of tiles i of W = L^-1: W_ij = -dinv_i sum_{k = j}^{i - 1} L_ik W_kj for j = blockIdx.x < i, with W_jj = dinv_j and
-// W_kj (k > j) read from where the earlier rows put it: transposed, in tile (j, k) of the upper triangle; W_ij goes to
-// tile (j, i) the same way
-__global__ __launch_bounds__(256) void k_trinv_row(int64_t N, int i, double* __restrict__ A, const double* __restrict__ dinv) {
-  __shared__ double sa[DT][DP];
-  __shared__ double sb[DT][DP];
-  const int j = blockIdx.x;
-  TileAcc acc;
-  // the two tiles of step k + 1 travel from global memory to registers while step k multiplies
-  double ra[16], rb[16];
-  auto fetch = [&](int k) {
-    const double* ga = A + ((int64_t)i * DT) * N + (int64_t)k * DT;                              // L_ik [r][m]
-    const double* gb = k == j ? dinv + (int64_t)j * DT * DT : A + ((int64_t)j * DT) * N + (int64_t)k * DT;
-    const int64_t ldb = k == j ? DT : N;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = threadIdx.x + 256 * q, r = idx / DT, c = idx % DT;
-      ra[q] = ga[(int64_t)r * N + c];
-      rb[q] = gb[(int64_t)r * ldb + c];
-    }
-  };
-  fetch(j);
-  for (int k = j; k < i; ++k) {
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int idx = threadIdx.x + 256 * q, r = idx / DT, c = idx % DT;
-      sa[r][c] = ra[q];
-      if (k == j) sb[c][r] = rb[q];                        // sb[c][m] = W_jj[m][c]: the diagonal tile is stored untransposed
-      else sb[r][c] = rb[q];                               // tile (j, k)[c][m] = W_kj[m][c]
-    }
-    __syncthreads();
-    if (k + 1 < i) fetch(k + 1);
-    tile_mma(acc, sa, sb);
-  }
-  __syncthreads();
-  // S (in acc) transposed into sb: sb[c][m] = S[m][c]; then W_ij[r][c] = -sum_m dinv_i[r][m] S[m][c]
-  tile_foreach(acc, [&](int r, int c, double v) { sb[c][r] = v; });
-  tile_load(sa, dinv + (int64_t)i * DT * DT, DT, false);
-  __syncthreads();
-  TileAcc out;
-  tile_mma(out, sa, sb);
-  double* g = A + ((int64_t)j * DT) * N + (int64_t)i * DT;                                       // tile (j, i), transposed store
-  tile_foreach(out, [&](int r, int c, double v) { g[(int64_t)c * N + r] = -v; });
-}
-
 // W = L^-1 by recursive doubling (round 4): with the diagonal tiles inverted (dinv), level s joins pairs of inverted diagonal
 // blocks of 2^s tiles, [W_CC 0; W_RC W_RR] with W_RC = -W_RR (L_RC W_CC) -- two launches of independent tile products per
-// level, 2 x 6 launches for 48 tiles, where the row-by-row version (k_trinv_row) is 47 dependent launches whose last ones
-// loop over 47 tile products per workgroup (4.5 ms at n = 3060).  phase 0: T_ij = sum_{k = j .. c1 - 1} L_ik W_kj, stored
+// level, 2 x 6 launches for 48 tiles, where the row-by-row version it replaced was 47 dependent launches whose last ones
+// looped over 47 tile products per workgroup (4.5 ms at n = 3060).  phase 0: T_ij = sum_{k = j .. c1 - 1} L_ik W_kj, stored
 // TRANSPOSED in T (what phase 1 reads as its B operand); phase 1: W_ij = -sum_{k = r0 .. i} W_ik T_kj, stored transposed in
 // the upper triangle of A like every finished tile of W.  Operands: L below the diagonal of A, finished W tiles (k, j), k > j,
 // at tile (j, k) of A transposed, diagonal ones in dinv.
@@ -2442,8 +2395,7 @@ struct ShellXCarry {
   int row_blocks;        // workgroups [0, row_blocks) do the product, the rest carry
 };
 
-template <class T>
-__global__ __launch_bounds__(SH_BLOCK) void k_pc_coarse_apply(int64_t n, int64_t N, int lower, const T* __restrict__ W, const double* __restrict__ x,
+__global__ __launch_bounds__(SH_BLOCK) void k_pc_coarse_apply(int64_t n, int64_t N, int lower, const float* __restrict__ W, const double* __restrict__ x,
                                                               double* __restrict__ y, const int32_t* __restrict__ done, ShellXCarry xc = {nullptr, nullptr, nullptr, 0, 0}) {
   if (done != nullptr && *done) return;
   if (xc.x != nullptr && (int)blockIdx.x >= xc.row_blocks) {
@@ -2458,7 +2410,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_pc_coarse_apply(int64_t n, int64_t
   for (int h = 0; h < 2; ++h) {
     const int64_t r = h == 0 ? pair : n - 1 - pair;
     if (h == 1 && r <= pair) break;
-    const T* row = W + r * N;
+    const float* row = W + r * N;
     const int64_t k0 = lower ? 0 : r, k1 = lower ? r + 1 : n;
     double s = 0.0;
     for (int64_t k = k0 + threadIdx.x; k < k1; k += SH_BLOCK) s += (double)row[k] * x[k];
@@ -3457,13 +3409,10 @@ static int shell_pc_coarse_setup(femo_shell* s, const femo_vec* vals, const uint
   hipStream_t st = s->ctx->stream;
   const int64_t n = s->cs_n, N = s->cs_N;
   const int nblk = (int)(N / DT);
-  static const bool dbg = FEMO_TUNE_ENV("FEMO_DEBUG_COARSE") != nullptr;
-  auto now = [&] { if (dbg) (void)hipStreamSynchronize(st); return std::chrono::steady_clock::now(); };
-  auto t0 = now();
   FEMO_HIP_CHECK(hipMemsetAsync(s->d_cs_A, 0, N * N * sizeof(double), st));
   FEMO_HIP_CHECK(hipMemsetAsync(s->d_cs_info, 0, 4 * sizeof(int32_t), st));
   if (s->hermite && s->d_lvl_node != nullptr && !femo_env_flag("FEMO_SHELL_TRILINEAR") && !femo_env_flag("FEMO_SHELL_NO_BLOCKS")) {
-    if (femo_env_flag("FEMO_SHELL_CG_ATOMIC") || s->cs_max_item > MM_ITEM) {      // (items above 256 points: only with FEMO_SHELL_CG_CHUNK)
+    if (femo_env_flag("FEMO_SHELL_CG_ATOMIC") || s->cs_max_item > MM_ITEM) {      // (items above 256 points: callers of the C ABI may pass them)
       for (int pass = 0; pass < 2; ++pass)
         hipLaunchKernelGGL(k_pc_coarse_galerkin_h, dim3((unsigned)s->cs_items), dim3(256), CGH_LDS, st, pass, s->cs_level, s->pc_width, s->level_off[s->cs_level], N,
                            s->n_unode, s->d_cs_ptr, s->d_cs_pts, s->d_cs_nbr, s->d_cs_pcell, s->d_brow, s->d_bcols, vals->d, d_fixed, s->d_ell_idx,
@@ -3489,7 +3438,6 @@ static int shell_pc_coarse_setup(femo_shell* s, const femo_vec* vals, const uint
   // (the prototype used 1e-8; the iteration counts do not move)
   hipLaunchKernelGGL(k_pc_coarse_fix_diag, dim3(sgrid(N, 256)), dim3(256), 0, st, N, s->d_cs_A, s->hermite_on ? 1e-9 : 1e-13);
   FEMO_HIP_CHECK(hipGetLastError());
-  auto t1 = now();
   for (int kb = 0; kb < nblk; ++kb) {
     if (kb == 0) hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), 0, st, N, kb, s->d_cs_A, s->d_cs_dinv, s->d_cs_info);
     const int m = nblk - kb - 1;
@@ -3498,19 +3446,14 @@ static int shell_pc_coarse_setup(femo_shell* s, const femo_vec* vals, const uint
       hipLaunchKernelGGL(k_chol_update, dim3(m * (m + 1) / 2), dim3(256), 0, st, N, kb, s->d_cs_A, s->d_cs_dinv, s->d_cs_info);   // also factorises tile kb + 1
     }
   }
-  auto t2 = now();
-  if (s->d_cs_T != nullptr && !femo_env_flag("FEMO_SHELL_TRINV_ROWS")) {
-    for (int B = 1; B < nblk; B *= 2) {
-      const int nb = (nblk + 2 * B - 1) / (2 * B);
-      for (int phase = 0; phase < 2; ++phase)
-        hipLaunchKernelGGL(k_trinv_level, dim3((unsigned)(nb * B * B)), dim3(256), 0, st, N, nblk, B, phase, s->d_cs_A, s->d_cs_dinv, s->d_cs_T);
-    }
-  } else {
-    for (int i = 1; i < nblk; ++i) hipLaunchKernelGGL(k_trinv_row, dim3(i), dim3(256), 0, st, N, i, s->d_cs_A, s->d_cs_dinv);
+  for (int B = 1; B < nblk; B *= 2) {
+    const int nb = (nblk + 2 * B - 1) / (2 * B);
+    for (int phase = 0; phase < 2; ++phase)
+      hipLaunchKernelGGL(k_trinv_level, dim3((unsigned)(nb * B * B)), dim3(256), 0, st, N, nblk, B, phase, s->d_cs_A, s->d_cs_dinv, s->d_cs_T);
   }
   hipLaunchKernelGGL(k_trinv_diag, dim3(nblk), dim3(256), 0, st, N, s->d_cs_A, s->d_cs_dinv);
   hipLaunchKernelGGL(k_pc_coarse_mirror, dim3(sgrid(N, 256), (unsigned)N), dim3(256), 0, st, N, s->d_cs_A);
-  if (s->d_cs_Af != nullptr) hipLaunchKernelGGL(k_pc_coarse_to_float, dim3(2048), dim3(256), 0, st, N * N, s->d_cs_A, s->d_cs_Af, std::sqrt(shell_coarse_weight(s)));
+  hipLaunchKernelGGL(k_pc_coarse_to_float, dim3(2048), dim3(256), 0, st, N * N, s->d_cs_A, s->d_cs_Af, std::sqrt(shell_coarse_weight(s)));
   FEMO_HIP_CHECK(hipGetLastError());
   int32_t info[4] = {0, 0, 0, 0};
   FEMO_HIP_CHECK(hipMemcpyAsync(info, s->d_cs_info, sizeof info, hipMemcpyDeviceToHost, st));
@@ -3534,12 +3477,6 @@ static int shell_pc_coarse_setup(femo_shell* s, const femo_vec* vals, const uint
     // whose dense operator is formed now (the preconditioner changes, the solution does not)
     s->hermite = false;
     return shell_pc_coarse_setup(s, vals, d_fixed);
-  }
-  if (dbg) {
-    auto t3 = now();
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    fprintf(stderr, "[femo] coarse solve: level %d, %lld unknowns (padded %lld), %lld items; Galerkin %.2f ms, Cholesky %.2f ms, inverse %.2f ms; far %d, pivot %d\n",
-            s->cs_level, (long long)n, (long long)N, (long long)s->cs_items, ms(t0, t1), ms(t1, t2), ms(t2, t3), info[1], info[2]);
   }
   return 0;
 }
@@ -3606,21 +3543,13 @@ static int shell_pc_apply(femo_shell* s, const uint8_t* d_fixed, double* Prz, un
       }
     }
     const unsigned gp = (unsigned)((s->cs_n + 1) / 2);
-    FEMO_REQUIRE(carry == nullptr || s->d_cs_Af != nullptr, "the carried x update rides in the single-precision coarse product");
-    if (s->d_cs_Af != nullptr) {
-      ShellXCarry xc = {nullptr, nullptr, nullptr, 0, 0};
-      unsigned g1 = gp;
-      if (carry != nullptr) { xc = *carry; xc.row_blocks = (int)gp; g1 = gp + 1024u; }
-      hipLaunchKernelGGL(k_pc_coarse_apply<float>, dim3(g1), dim3(SH_BLOCK), 0, st, s->cs_n, s->cs_N, 1, (const float*)s->d_cs_Af,
-                         s->d_t + 6 * s->level_off[cs], s->d_cs_tmp, done, xc);
-      hipLaunchKernelGGL(k_pc_coarse_apply<float>, dim3(gp), dim3(SH_BLOCK), 0, st, s->cs_n, s->cs_N, 0, (const float*)s->d_cs_Af, s->d_cs_tmp,
-                         s->d_e + 6 * s->level_off[cs], done);
-    } else {
-      hipLaunchKernelGGL(k_pc_coarse_apply<double>, dim3(gp), dim3(SH_BLOCK), 0, st, s->cs_n, s->cs_N, 1, (const double*)s->d_cs_A,
-                         s->d_t + 6 * s->level_off[cs], s->d_cs_tmp, done);
-      hipLaunchKernelGGL(k_pc_coarse_apply<double>, dim3(gp), dim3(SH_BLOCK), 0, st, s->cs_n, s->cs_N, 0, (const double*)s->d_cs_A, s->d_cs_tmp,
-                         s->d_e + 6 * s->level_off[cs], done);
-    }
+    ShellXCarry xc = {nullptr, nullptr, nullptr, 0, 0};
+    unsigned g1 = gp;
+    if (carry != nullptr) { xc = *carry; xc.row_blocks = (int)gp; g1 = gp + 1024u; }
+    hipLaunchKernelGGL(k_pc_coarse_apply, dim3(g1), dim3(SH_BLOCK), 0, st, s->cs_n, s->cs_N, 1, (const float*)s->d_cs_Af,
+                       s->d_t + 6 * s->level_off[cs], s->d_cs_tmp, done, xc);
+    hipLaunchKernelGGL(k_pc_coarse_apply, dim3(gp), dim3(SH_BLOCK), 0, st, s->cs_n, s->cs_N, 0, (const float*)s->d_cs_Af, s->d_cs_tmp,
+                       s->d_e + 6 * s->level_off[cs], done);
     for (int l = cs + 1; l < L; ++l) level_up(l, s->blk_ready ? s->d_cblk : (const double*)nullptr);
   } else {
   // levels 0 .. kc (at most 256 nodes each, never the finest: with 4096 the one workgroup took 244 us, with 768 still 71) go through the fused single-workgroup kernel
@@ -3670,7 +3599,7 @@ int femo_shell_pc_coarse(femo_shell* s, int level, const int32_t* node_xyz, int6
   FEMO_TRY(to_device(&s->d_cs_nbr, item_nbr, n_items * 64, st));
   const int64_t N = (n + DT - 1) / DT * DT;
   FEMO_HIP_CHECK(hipMalloc(&s->d_cs_A, N * N * sizeof(double)));
-  if (!femo_env_flag("FEMO_SHELL_COARSE_FP64")) FEMO_HIP_CHECK(hipMalloc(&s->d_cs_Af, N * N * sizeof(float)));
+  FEMO_HIP_CHECK(hipMalloc(&s->d_cs_Af, N * N * sizeof(float)));
   FEMO_HIP_CHECK(hipMalloc(&s->d_cs_tmp, N * sizeof(double)));
   FEMO_HIP_CHECK(hipMalloc(&s->d_cs_dinv, N * DT * sizeof(double)));
   FEMO_HIP_CHECK(hipMalloc(&s->d_cs_T, N * N * sizeof(double)));
@@ -4378,8 +4307,6 @@ int femo_shell_solve(femo_shell* s, const femo_vec* vals, const uint8_t* fixed_h
   const unsigned gz = std::min<unsigned>(sgrid(n / 3, SH_BLOCK / 8), SH_MAXPART);     // k_pc_prolong: 8 lanes per point
   const unsigned gx = std::min<unsigned>(sgrid(n / 3), 1024u);                        // k_scg_xr_pt: a thread per point, few partials
   double* Pte = s->d_part + 2 * SH_MAXPART;
-  // direction update fused into the prolongation (dofs numbered 3 point + component: every shell pattern of fea/shell.py)
-  const bool fused = opts->pc == 1 && n % 3 == 0 && !multi && !femo_env_flag("FEMO_SHELL_UNFUSED");
   if (lattice) {
     FEMO_TRY(shell_pc_setup(s, vals, mask_hash, d_fixed));
     FEMO_TRY(shell_pc_apply(s, d_fixed, Prz, gz, nullptr));
@@ -4387,8 +4314,8 @@ int femo_shell_solve(femo_shell* s, const femo_vec* vals, const uint8_t* fixed_h
   } else {
     hipLaunchKernelGGL(k_scg_init, dim3(gv), dim3(SH_BLOCK), 0, st, n, s->d_r, s->d_dinv, s->d_p, Prz);
   }
-  // x += alpha p inside the preconditioner's first coarse product (fused loop, one rank, coarse solve in single precision)
-  const bool carry_x = fused && s->cs_ready && s->d_cs_Af != nullptr && !femo_env_flag("FEMO_SHELL_NO_XCARRY");
+  // x += alpha p inside the preconditioner's first coarse product (fused loop, one rank, with the coarse solve)
+  const bool carry_x = lattice && !multi && s->cs_ready;
   const int nb_rz0 = lattice ? (int)gz : (int)gv;
   if (multi) {
     FEMO_TRY(femo_launch_fold(SH_BLOCK, nb_rz0, 1, Prz, one_rz, st));
@@ -4441,10 +4368,11 @@ int femo_shell_solve(femo_shell* s, const femo_vec* vals, const uint8_t* fixed_h
           FEMO_TRY(shell_allreduce(s, one_rz, 1, st));
           hipLaunchKernelGGL(k_scg_p, dim3(gv), dim3(SH_BLOCK), 0, st, n, it, 1, one_rz, s->d_scal, s->d_r, s->d_dinv, s->d_p, s->d_flag, gam);
         }
-      } else if (lattice && fused) {
+      } else if (lattice) {
+        // One rank: the direction update is fused into the prolongation (dofs numbered 3 point + component).
         // r . z = r . B r + (P^T r) . e is known before z is: the update emits the first part, the finest lattice level
         // the second, and the prolongation writes p = z + beta p at once (9 launches and 3 vector streams fewer
-        // per iteration than the unfused form below)
+        // per iteration than the unfused form above)
         int nb_te = 0;
         if (carry_x) {
           const ShellXCarry xc = {x->d, s->d_p, s->d_scal + 5, n, 0};
@@ -4463,10 +4391,6 @@ int femo_shell_solve(femo_shell* s, const femo_vec* vals, const uint8_t* fixed_h
         hipLaunchKernelGGL(k_pc_prolong_fused, dim3(gzf), dim3(SH_BLOCK), 0, st, n / 3, it, (int)gx, Prz, nb_te, Pte, s->d_scal, s->d_fin_idx, s->d_fin_w,
                            d_fixed, s->d_dinv, s->dinv3_ready ? s->d_dinv3 : (const float*)nullptr, s->d_r, s->d_e, s->d_p, s->d_flag, gam,
                            (s->hermite_on && s->cs_ready && s->blk_ready) ? s->d_fin_w4 : (const float4*)nullptr, s->n_unode);
-      } else if (lattice) {
-        hipLaunchKernelGGL(k_scg_xr_plain, dim3(gv), dim3(SH_BLOCK), 0, st, n, (int)gs, Ppq, s->d_scal, s->d_p, s->d_q, x->d, s->d_r, s->d_flag);
-        FEMO_TRY(shell_pc_apply(s, d_fixed, Prz, gz, s->d_flag));
-        hipLaunchKernelGGL(k_scg_p_z, dim3(gv), dim3(SH_BLOCK), 0, st, n, it, (int)gz, Prz, s->d_scal, s->d_z, s->d_p, s->d_flag, gam);
       } else {
         hipLaunchKernelGGL(k_scg_xr, dim3(gv), dim3(SH_BLOCK), 0, st, n, (int)gs, Ppq, s->d_scal, s->d_p, s->d_q, s->d_dinv, x->d, s->d_r, Prz, s->d_flag);
         hipLaunchKernelGGL(k_scg_p, dim3(gv), dim3(SH_BLOCK), 0, st, n, it, (int)gv, Prz, s->d_scal, s->d_r, s->d_dinv, s->d_p, s->d_flag, gam);
