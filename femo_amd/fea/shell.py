@@ -1,4 +1,5 @@
-"""Reissner-Mindlin shell on the GPU engine: host side of `csrc/shell.hip`.
+"""Reissner-Mindlin shell on the GPU engine: host side of the shell units of `csrc` (`shell_internal.h`;
+SURVEY.md section 8(f) row 3).
 
 Mirrors the surface of `examples/test_shell_m3l/shell_pde.py:219-332` (``ShellPDE``: function spaces W / VT / VF,
 ``pdeRes``, ``compliance``, ``mass``, ``volume``, ``elastic_energy``) for the CG2^3 x CG1^3 element; the weak form the
@@ -879,7 +880,7 @@ class DeviceShell:
             assert mask.size == self.n_dof
         check(self.lib.femo_shell_solve(self.handle, vals.handle, C.c_void_p(mask.ctypes.data) if mask is not None else None,
                                         xfix.handle if xfix is not None else None, b.handle, x.handle, C.byref(opts), C.byref(info)))
-        if info.converged not in (1, 2):           # 2: stalled at the attainable accuracy, below 1e-9 relative (shell.hip)
+        if info.converged not in (1, 2):           # 2: stalled at the attainable accuracy, below 1e-9 relative (shell_solve.hip)
             raise E.FemoError(f"shell CG did not converge: {info.iterations} iterations, residual {info.residual_norm:.3e} "
                               f"(rhs {info.rhs_norm:.3e})")
         return info

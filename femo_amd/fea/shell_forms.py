@@ -1,6 +1,6 @@
 """Shell forms for the FEA / FEAModel operator stack: the objects `examples/test_shell_m3l/shell_pde.py:219-332`
 builds (``ShellPDE`` with its spaces W / VT / VF, ``pdeRes``, ``compliance``, ``mass``, ``volume``,
-``elastic_energy``) on the HIP shell kernels (`csrc/shell.hip`, host side `fea/shell.py`).
+``elastic_energy``) on the HIP shell kernels (`csrc/shell_forms.hip`, solves in `csrc/shell_solve.hip`; host side `fea/shell.py`).
 
 They are ``BackendForm``s: `utils_hip.assemble*`, `solveNonlinear`, `KSP` hand them their own assembly and solves,
 so `FEA.add_input / add_state / add_output`, `StateOperation`, `OutputOperation` and `FEAModel` are used unchanged

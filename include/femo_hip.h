@@ -494,7 +494,7 @@ int femo_shell_pc_create(femo_shell* s, int width, int64_t n_nodes, int n_levels
                          const int64_t* chi_rowptr, const int32_t* chi_cols, const double* chi_vals);
 /* Exact coarse solve for the lattice preconditioner (optional, after femo_shell_pc_create): on lattice level `level`
  * (not the finest; 6 x nodes <= 8192 unknowns) the Galerkin operator P^T K P is formed as a dense matrix on the device,
- * factorised by the library's own blocked Cholesky + triangular inverse on the fp64 matrix cores (shell.hip) whenever
+ * factorised by the library's own blocked Cholesky + triangular inverse on the fp64 matrix cores (shell_coarse.hip) whenever
  * the stiffness or the Dirichlet set change, and A^-1 = L^-T L^-1 applied in place
  * of the diagonal levels 0 .. level: M^-1 = D^-1 + sum_{l > level} P_l C_l P_l^T + P_c (P_c^T K P_c)^-1 P_c^T.  What
  * the reference's direct solver (MUMPS, utils_dolfinx.py:476-512) does for the whole matrix is done here for the

@@ -1,4 +1,4 @@
-"""Reissner-Mindlin shell kernels (csrc/shell.hip through femo_amd/fea/shell.py) against oracle/shell_oracle.py:
+"""Reissner-Mindlin shell kernels (csrc/shell_forms.hip, csrc/shell_solve.hip through femo_amd/fea/shell.py) against oracle/shell_oracle.py:
 element couplings, load, residual, forward / adjoint solves on the Scordelis-Lo roof, thickness sensitivities."""
 import numpy as np
 import pytest

@@ -1,6 +1,6 @@
 """Hermite-type lattice spaces in the shell's preconditioner (round 4): csrc/shell.hip (k_pc_restrict_h, k_lat_level_h,
-k_lat_down_composite_h, the Hermite branch of the prolongations, k_pc_galerkin_blocks_h, k_pc_coarse_galerkin_h) through
-femo_amd/fea/shell.py against oracle/shell_oracle.py::LatticePreconditioner -- the dense coarse operator entry by entry,
+k_lat_down_composite_h, the Hermite branch of the prolongations, k_pc_galerkin_blocks_h) and csrc/shell_coarse.hip
+(k_pc_coarse_galerkin_h) through femo_amd/fea/shell.py against oracle/shell_oracle.py::LatticePreconditioner -- the dense coarse operator entry by entry,
 M^-1 r, the iteration counts, and the solution against the direct solve."""
 import numpy as np
 import pytest
@@ -171,7 +171,7 @@ def test_set_up_kernels_on_a_high_valence_mesh(ctx, monkeypatch):
 
 def test_dirichlet_mask_kept_on_the_device_follows_the_callers_array(ctx):
     """Round 5: the shell keeps the Dirichlet mask of the last solve on the device behind a hash of the caller's array
-    (`shell_mask`, shell.hip) instead of uploading it per solve.  Another mask must replace it -- state, preconditioner
+    (`shell_mask`, shell_solve.hip) instead of uploading it per solve.  Another mask must replace it -- state, preconditioner
     set-up and imposed dofs all follow --, and coming back to the first mask gives the first result again."""
     from femo_amd.engine import Vec
     prob, V0, fixed = _problem(ctx, 16)
