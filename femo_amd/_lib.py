@@ -32,6 +32,8 @@ J_L2_TRACKING = 0
 ELAST_SIMP = 0
 ELAST_RAMP = 1
 ELAST_INFO_KEYS = ("dim", "n_dof", "nnz", "sell_entries", "spmv_bytes")
+ELAST_PC = {"jacobi": 0, "multilevel": 1}
+ELAST_PC_INFO_COUNT = 16           # [levels, lattice bytes, block builds, last build us, nodes per level ...]
 
 
 class SolverOpts(C.Structure):
@@ -202,6 +204,10 @@ PROTOTYPES = {
     "femo_elast_drho": (C.c_int, [H, C.c_int, C.c_int, H, H, H, H, C.c_int]),
     "femo_elast_solve": (C.c_int, [H, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
     "femo_elast_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "femo_elast_pc_setup": (C.c_int, [H, C.c_double]),
+    "femo_elast_pc_info": (C.c_int, [H, c_i64p]),
+    "femo_elast_pc_export_level": (C.c_int, [H, C.c_int, C.c_void_p]),
+    "femo_elast_pc_apply": (C.c_int, [H, H, H]),
     "femo_elast_bench_spmv": (C.c_int, [H, H, H, C.c_int, c_f64p]),
     "femo_filter_create": (C.c_int, [H, C.c_int, c_i64, C.c_void_p, C.c_double, C.POINTER(H)]),
     "femo_filter_destroy": (C.c_int, [H]),

@@ -1,0 +1,162 @@
+// Shared by elasticity.hip (assembly, products, PCG loop) and elast_pc.hip (multilevel preconditioner).  Not part of the ABI.
+#pragma once
+
+#include "femo_internal.h"
+
+struct femo_elast_pc;   // lattice hierarchy of the multilevel preconditioner (elast_pc.hip)
+
+struct femo_elast {
+  femo_mesh* mesh = nullptr;
+  int d = 0;
+  double lam0 = 0.0, mu0 = 0.0;
+  double* d_vals = nullptr;     // sell_entries * d^2
+  double* d_diag = nullptr;     // n_rows * d^2
+  double* d_dinv = nullptr;     // n_rows * d^2: inverse of the (masked) diagonal blocks
+  uint8_t* d_fixed = nullptr;   // n_dof, optional
+  bool has_fixed = false;
+  bool assembled = false;
+  // tagged facets: vertex -> facet CSR (vertex ids of the facets, d per facet)
+  int64_t n_facets = 0;
+  int32_t* d_fverts = nullptr;
+  int64_t* d_fptr = nullptr;    // n_vert + 1
+  int32_t* d_flist = nullptr;
+  // PCG work
+  double *w_r = nullptr, *w_z = nullptr, *w_p = nullptr, *w_q = nullptr, *w_part = nullptr, *w_s = nullptr;
+  int32_t* w_flag = nullptr;
+  int32_t* h_flag = nullptr;    // pinned
+  double* h_s = nullptr;        // pinned
+  // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
+  femo_elast_pc* pc = nullptr;
+  bool pc_dirty = true;
+  int method = 0;                    // of the last femo_elast_assemble ...
+  uint64_t rho_uid = 0, rho_gen = 0; // ... and its density vector: looked up in the live table at the lazy build (never a
+                                     // pointer: the caller may have destroyed it); uid 0 = wrapped memory, built at once
+};
+
+constexpr int EB = 256;              // threads per block of the row kernels
+constexpr int PCG_GRID = 512;        // blocks of the PCG reductions (one partial each)
+
+// PCG device scalars s[]: 0 rz, 1 alpha, 2 beta, 3 tol^2, 4 rz0.  flag[]: 0 done, 1 iterations, 2 breakdown, 3 converged.
+enum { S_RZ = 0, S_ALPHA = 1, S_BETA = 2, S_TOL2 = 3, S_RZ0 = 4 };
+
+// elast_pc.hip ------------------------------------------------------------------------------------------------------
+void femo_elast_pc_free(femo_elast* e);
+// Rebuilds the Galerkin blocks when K or the fixed set changed since the last build (no-op otherwise).
+int femo_elast_pc_ensure(femo_elast* e);
+// The build itself, from the density the current K was assembled with.
+int femo_elast_pc_build(femo_elast* e, const double* rho);
+// The preconditioner step of the PCG loop: what k_pcg_precond does with z = M^-1 r of the multilevel form.
+// update: x += alpha p, r -= alpha q first (alpha = s[S_ALPHA]; nothing once flag[0] is set).  pinit != null: p = z as well.
+int femo_elast_pc_step(femo_elast* e, bool update, double* x, double* r, const double* p, const double* q, double* z,
+                       double* pinit, const double* s, double* part, const int32_t* flag);
+
+#if defined(__HIPCC__)
+// gradients of the barycentric coordinates and the volume of a P1 simplex, from the vertices in `conn` order
+template <int D>
+__device__ __forceinline__ void simplex_grads(const double (&p)[D + 1][D], double (&g)[D + 1][D], double& vol) {
+  double m[D][D];          // m[k][i] = p[k+1][i] - p[0][i]
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+#pragma unroll
+    for (int i = 0; i < D; ++i) m[k][i] = p[k + 1][i] - p[0][i];
+  // grad lambda_{k+1} = column k of m^-1
+  if constexpr (D == 2) {
+    const double det = m[0][0] * m[1][1] - m[0][1] * m[1][0];
+    const double id = 1.0 / det;
+    g[1][0] = m[1][1] * id;  g[1][1] = -m[1][0] * id;
+    g[2][0] = -m[0][1] * id; g[2][1] = m[0][0] * id;
+    vol = 0.5 * fabs(det);
+  } else {
+    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1];
+    const double c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2];
+    const double c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+    const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
+    const double id = 1.0 / det;
+    // inverse (adjugate / det): inv[i][k]
+    double inv[3][3];
+    inv[0][0] = c00 * id;
+    inv[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id;
+    inv[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id;
+    inv[1][0] = c01 * id;
+    inv[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id;
+    inv[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id;
+    inv[2][0] = c02 * id;
+    inv[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id;
+    inv[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) g[k + 1][i] = inv[i][k];
+    vol = fabs(det) * (1.0 / 6.0);
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 1; k <= D; ++k) s += g[k][i];
+    g[0][i] = -s;
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void load_cell(const int32_t* __restrict__ conn, const double* __restrict__ x, int64_t c,
+                                          int32_t (&v)[D + 1], double (&p)[D + 1][D]) {
+#pragma unroll
+  for (int b = 0; b <= D; ++b) {
+    v[b] = conn[c * (D + 1) + b];
+#pragma unroll
+    for (int i = 0; i < D; ++i) p[b][i] = x[(int64_t)v[b] * D + i];
+  }
+}
+
+__device__ __forceinline__ double penal(int method, double r) {
+  return method == FEMO_ELAST_SIMP ? r * r * r : r / (1.0 + 8.0 * (1.0 - r));
+}
+__device__ __forceinline__ double penal_d(int method, double r) {
+  if (method == FEMO_ELAST_SIMP) return 3.0 * r * r;
+  const double q = 1.0 + 8.0 * (1.0 - r);
+  return 9.0 / (q * q);
+}
+
+// block (a, b) of the element matrix without the factor C |T|; written symmetrically in (a, r) <-> (b, c)
+template <int D>
+__device__ __forceinline__ double kblock(const double (&g)[D + 1][D], int a, int b, int r, int c, double lam, double mu,
+                                         double gab) {
+  double t = lam * (g[a][r] * g[b][c]) + mu * (g[a][c] * g[b][r]);
+  if (r == c) t += mu * gab;
+  return t;
+}
+
+template <int D>
+__device__ __forceinline__ double dotg(const double (&g)[D + 1][D], int a, int b) {
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) s += g[a][k] * g[b][k];
+  return s;
+}
+
+// in-register inverse of a small SPD block (fixed components: identity row / column)
+template <int D>
+__device__ __forceinline__ void block_inverse(double (&B)[D * D], double (&Bi)[D * D]) {
+  if constexpr (D == 2) {
+    const double det = B[0] * B[3] - B[1] * B[2];
+    const double id = 1.0 / det;
+    Bi[0] = B[3] * id; Bi[1] = -B[1] * id; Bi[2] = -B[2] * id; Bi[3] = B[0] * id;
+  } else {
+    const double c00 = B[4] * B[8] - B[5] * B[7];
+    const double c01 = B[5] * B[6] - B[3] * B[8];
+    const double c02 = B[3] * B[7] - B[4] * B[6];
+    const double det = B[0] * c00 + B[1] * c01 + B[2] * c02;
+    const double id = 1.0 / det;
+    Bi[0] = c00 * id;
+    Bi[1] = (B[2] * B[7] - B[1] * B[8]) * id;
+    Bi[2] = (B[1] * B[5] - B[2] * B[4]) * id;
+    Bi[3] = c01 * id;
+    Bi[4] = (B[0] * B[8] - B[2] * B[6]) * id;
+    Bi[5] = (B[2] * B[3] - B[0] * B[5]) * id;
+    Bi[6] = c02 * id;
+    Bi[7] = (B[1] * B[6] - B[0] * B[7]) * id;
+    Bi[8] = (B[0] * B[4] - B[1] * B[3]) * id;
+  }
+}
+#endif

@@ -9,32 +9,10 @@
 // C(rho_c) |T_c| B_v^T D_0 B_w to its blocks (v, w).  No float atomics: every block has one writer, the visits come in
 // ascending cell order, and the cell geometry is formed from `conn` in its own vertex order, so block (v, w) and block
 // (w, v)^T are sums of the same numbers in the same order -- K is symmetric entry for entry.
-#include "femo_internal.h"
+#include "elast_internal.h"
 
 #include <algorithm>
 #include <cmath>
-
-struct femo_elast {
-  femo_mesh* mesh = nullptr;
-  int d = 0;
-  double lam0 = 0.0, mu0 = 0.0;
-  double* d_vals = nullptr;     // sell_entries * d^2
-  double* d_diag = nullptr;     // n_rows * d^2
-  double* d_dinv = nullptr;     // n_rows * d^2: inverse of the (masked) diagonal blocks
-  uint8_t* d_fixed = nullptr;   // n_dof, optional
-  bool has_fixed = false;
-  bool assembled = false;
-  // tagged facets: vertex -> facet CSR (vertex ids of the facets, d per facet)
-  int64_t n_facets = 0;
-  int32_t* d_fverts = nullptr;
-  int64_t* d_fptr = nullptr;    // n_vert + 1
-  int32_t* d_flist = nullptr;
-  // PCG work
-  double *w_r = nullptr, *w_z = nullptr, *w_p = nullptr, *w_q = nullptr, *w_part = nullptr, *w_s = nullptr;
-  int32_t* w_flag = nullptr;
-  int32_t* h_flag = nullptr;    // pinned
-  double* h_s = nullptr;        // pinned
-};
 
 struct femo_filter {
   femo_ctx* ctx = nullptr;
@@ -47,123 +25,11 @@ struct femo_filter {
 
 namespace {
 
-constexpr int EB = 256;              // threads per block of the row kernels
-constexpr int PCG_GRID = 512;        // blocks of the PCG reductions (one partial each)
-
 inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
   int64_t g = (n + EB - 1) / EB;
   if (g < 1) g = 1;
   if (g > cap) g = cap;
   return (unsigned)g;
-}
-
-// gradients of the barycentric coordinates and the volume of a P1 simplex, from the vertices in `conn` order
-template <int D>
-__device__ __forceinline__ void simplex_grads(const double (&p)[D + 1][D], double (&g)[D + 1][D], double& vol) {
-  double m[D][D];          // m[k][i] = p[k+1][i] - p[0][i]
-#pragma unroll
-  for (int k = 0; k < D; ++k)
-#pragma unroll
-    for (int i = 0; i < D; ++i) m[k][i] = p[k + 1][i] - p[0][i];
-  // grad lambda_{k+1} = column k of m^-1
-  if constexpr (D == 2) {
-    const double det = m[0][0] * m[1][1] - m[0][1] * m[1][0];
-    const double id = 1.0 / det;
-    g[1][0] = m[1][1] * id;  g[1][1] = -m[1][0] * id;
-    g[2][0] = -m[0][1] * id; g[2][1] = m[0][0] * id;
-    vol = 0.5 * fabs(det);
-  } else {
-    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1];
-    const double c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2];
-    const double c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
-    const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
-    const double id = 1.0 / det;
-    // inverse (adjugate / det): inv[i][k]
-    double inv[3][3];
-    inv[0][0] = c00 * id;
-    inv[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id;
-    inv[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id;
-    inv[1][0] = c01 * id;
-    inv[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id;
-    inv[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id;
-    inv[2][0] = c02 * id;
-    inv[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id;
-    inv[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) g[k + 1][i] = inv[i][k];
-    vol = fabs(det) * (1.0 / 6.0);
-  }
-#pragma unroll
-  for (int i = 0; i < D; ++i) {
-    double s = 0.0;
-#pragma unroll
-    for (int k = 1; k <= D; ++k) s += g[k][i];
-    g[0][i] = -s;
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void load_cell(const int32_t* __restrict__ conn, const double* __restrict__ x, int64_t c,
-                                          int32_t (&v)[D + 1], double (&p)[D + 1][D]) {
-#pragma unroll
-  for (int b = 0; b <= D; ++b) {
-    v[b] = conn[c * (D + 1) + b];
-#pragma unroll
-    for (int i = 0; i < D; ++i) p[b][i] = x[(int64_t)v[b] * D + i];
-  }
-}
-
-__device__ __forceinline__ double penal(int method, double r) {
-  return method == FEMO_ELAST_SIMP ? r * r * r : r / (1.0 + 8.0 * (1.0 - r));
-}
-__device__ __forceinline__ double penal_d(int method, double r) {
-  if (method == FEMO_ELAST_SIMP) return 3.0 * r * r;
-  const double q = 1.0 + 8.0 * (1.0 - r);
-  return 9.0 / (q * q);
-}
-
-// block (a, b) of the element matrix without the factor C |T|; written symmetrically in (a, r) <-> (b, c)
-template <int D>
-__device__ __forceinline__ double kblock(const double (&g)[D + 1][D], int a, int b, int r, int c, double lam, double mu,
-                                         double gab) {
-  double t = lam * (g[a][r] * g[b][c]) + mu * (g[a][c] * g[b][r]);
-  if (r == c) t += mu * gab;
-  return t;
-}
-
-template <int D>
-__device__ __forceinline__ double dotg(const double (&g)[D + 1][D], int a, int b) {
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) s += g[a][k] * g[b][k];
-  return s;
-}
-
-// in-register inverse of a small SPD block (fixed components: identity row / column)
-template <int D>
-__device__ __forceinline__ void block_inverse(double (&B)[D * D], double (&Bi)[D * D]) {
-  if constexpr (D == 2) {
-    const double det = B[0] * B[3] - B[1] * B[2];
-    const double id = 1.0 / det;
-    Bi[0] = B[3] * id; Bi[1] = -B[1] * id; Bi[2] = -B[2] * id; Bi[3] = B[0] * id;
-  } else {
-    const double c00 = B[4] * B[8] - B[5] * B[7];
-    const double c01 = B[5] * B[6] - B[3] * B[8];
-    const double c02 = B[3] * B[7] - B[4] * B[6];
-    const double det = B[0] * c00 + B[1] * c01 + B[2] * c02;
-    const double id = 1.0 / det;
-    Bi[0] = c00 * id;
-    Bi[1] = (B[2] * B[7] - B[1] * B[8]) * id;
-    Bi[2] = (B[1] * B[5] - B[2] * B[4]) * id;
-    Bi[3] = c01 * id;
-    Bi[4] = (B[0] * B[8] - B[2] * B[6]) * id;
-    Bi[5] = (B[2] * B[3] - B[0] * B[5]) * id;
-    Bi[6] = c02 * id;
-    Bi[7] = (B[1] * B[6] - B[0] * B[7]) * id;
-    Bi[8] = (B[0] * B[4] - B[1] * B[3]) * id;
-  }
 }
 
 __device__ __forceinline__ int slot_pos(uint32_t slots, int a, int b) {
@@ -458,8 +324,7 @@ __global__ void k_elast_export(int64_t n_rows, const int64_t* __restrict__ mptr,
 }
 
 // ------------------------------------------------------------------------------------------------ PCG ----
-// Device scalars s[]: 0 rz, 1 alpha, 2 beta, 3 tol^2, 4 rz0.  flag[]: 0 done, 1 iterations, 2 breakdown, 3 converged.
-enum { S_RZ = 0, S_ALPHA = 1, S_BETA = 2, S_TOL2 = 3, S_RZ0 = 4 };
+// Device scalars s[] and flag[]: elast_internal.h
 
 __global__ void k_pcg_start_x(int64_t n, int zero_guess, const uint8_t* __restrict__ fixed, const double* __restrict__ b,
                               double* __restrict__ x) {
@@ -739,6 +604,7 @@ int femo_elast_create(femo_mesh* m, double E, double nu, femo_elast** out) {
 
 int femo_elast_destroy(femo_elast* e) {
   if (!e) return 0;                    // hipFree waits for the device; the mesh may already be gone
+  femo_elast_pc_free(e);
   hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
   hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag);
@@ -764,6 +630,7 @@ int femo_elast_set_fixed(femo_elast* e, const uint8_t* mask) {
   FEMO_REQUIRE(e, "null argument");
   const int64_t n = e->mesh->n_vert * e->d;
   hipStream_t st = e->mesh->ctx->stream;
+  e->pc_dirty = true;
   if (!mask) { e->has_fixed = false; return 0; }
   if (!e->d_fixed) FEMO_TRY(dalloc(&e->d_fixed, n));
   FEMO_HIP_CHECK(hipMemcpyAsync(e->d_fixed, mask, n, hipMemcpyHostToDevice, st));
@@ -819,6 +686,12 @@ int femo_elast_assemble(femo_elast* e, int method, const femo_vec* rho) {
                        e->d_vals, e->d_diag, e->d_dinv);
   FEMO_HIP_CHECK(hipGetLastError());
   e->assembled = true;
+  e->pc_dirty = true;
+  e->method = method;
+  e->rho_uid = rho->uid;
+  e->rho_gen = rho->gen;
+  // wrapped memory cannot be recognised later: with a lattice plan in place its blocks are built now
+  if (e->pc && rho->uid == 0) FEMO_TRY(femo_elast_pc_build(e, rho->d));
   return 0;
 }
 
@@ -903,7 +776,10 @@ int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_s
   femo_vec_touch(x);
   hipStream_t st = m->ctx->stream;
   const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
-  const int check = opts->check_every > 0 ? opts->check_every : 32;
+  const bool ml = opts->pc == FEMO_ELAST_PC_MULTILEVEL;
+  FEMO_REQUIRE(!ml || e->pc, "femo_elast_solve: pc = multilevel without femo_elast_pc_setup");
+  if (ml) FEMO_TRY(femo_elast_pc_ensure(e));
+  const int check = opts->check_every > 0 ? opts->check_every : (ml ? 8 : 32);
   const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
   const double rtol2 = opts->rtol * opts->rtol, atol2 = opts->atol * opts->atol;
   const unsigned gs = grid_of(m->n_rows);
@@ -915,7 +791,8 @@ int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_s
   const unsigned gp = (unsigned)PCG_GRID;
 #define FEMO_PRECOND(D, U, I) hipLaunchKernelGGL((k_pcg_precond<D, U, I>), dim3(gp), dim3(EB), 0, st, m->n_rows, e->d_dinv, x->d, \
                                                  e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, e->w_flag)
-  if (e->d == 2) FEMO_PRECOND(2, false, true); else FEMO_PRECOND(3, false, true);
+  if (ml) FEMO_TRY(femo_elast_pc_step(e, false, x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, e->w_flag));
+  else if (e->d == 2) FEMO_PRECOND(2, false, true); else FEMO_PRECOND(3, false, true);
   hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 0, e->w_part, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
   FEMO_HIP_CHECK(hipGetLastError());
   int it_issued = 0;
@@ -926,7 +803,8 @@ int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_s
     for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) {
       FEMO_TRY(elast_spmv(e, fx != nullptr, 1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, e->w_flag));   // q = A p, p.q
       hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 1, e->w_part, nps, rtol2, atol2, max_it, e->w_s, e->w_flag);
-      if (e->d == 2) FEMO_PRECOND(2, true, false); else FEMO_PRECOND(3, true, false);
+      if (ml) FEMO_TRY(femo_elast_pc_step(e, true, x->d, e->w_r, e->w_p, e->w_q, e->w_z, nullptr, e->w_s, e->w_part, e->w_flag));
+      else if (e->d == 2) FEMO_PRECOND(2, true, false); else FEMO_PRECOND(3, true, false);
       hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 2, e->w_part, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
       hipLaunchKernelGGL(k_pcg_p, dim3(gp), dim3(EB), 0, st, n, e->w_z, e->w_p, e->w_s, e->w_flag);
     }

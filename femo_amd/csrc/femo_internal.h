@@ -197,6 +197,7 @@ int femo_launch_fold(int nt, int nb, int nsums, const double* partials, double* 
                      const int32_t* done = nullptr, int nb2 = 0, const double* partials2 = nullptr);
 void femo_vec_register(femo_vec* v);     // after creation: assigns uid, enters the live table
 void femo_vec_unregister(femo_vec* v);   // before destruction
+femo_vec* femo_vec_live(uint64_t uid);   // the live owned vector with this uid, or null (destroyed, or uid 0 = wrapped memory)
 
 struct femo_pc;   // auxiliary-lattice BPX hierarchy (bpx.hip)
 

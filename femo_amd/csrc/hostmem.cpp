@@ -324,6 +324,13 @@ void femo_vec_unregister(femo_vec* v) {
   g_live.erase(v->uid);
 }
 
+femo_vec* femo_vec_live(uint64_t uid) {
+  if (!uid) return nullptr;
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_live.find(uid);
+  return it == g_live.end() ? nullptr : it->second;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------ pinned blocks ----

@@ -28,6 +28,7 @@ from .function import Function, FunctionSpace, VectorFunctionSpace
 from .io import MeshTags
 
 METHODS = {"SIMP": _lib.ELAST_SIMP, "RAMP": _lib.ELAST_RAMP}
+PRECONDITIONERS = _lib.ELAST_PC           # "jacobi" (block diagonal) | "multilevel" (csrc/elast_pc.hip)
 
 
 def _ctx():
@@ -51,6 +52,8 @@ class DeviceElasticity:
         self.d, self.n_dof = self.info["dim"], self.info["n_dof"]
         self.fixed_key = None
         self.facets_key = None
+        self.pc_plan = None                # set by pc_setup: dict(levels, bytes, nodes)
+        self._rho = None
 
     def set_fixed(self, mask: Optional[np.ndarray]) -> None:
         if mask is None:
@@ -71,6 +74,7 @@ class DeviceElasticity:
 
     def assemble(self, method: int, rho: Vec) -> None:
         check(self.lib.femo_elast_assemble(self.handle, int(method), rho.handle))
+        self._rho = rho                    # the multilevel blocks are rebuilt from this vector on the next solve
 
     def apply(self, x: Vec, y: Vec, masked: bool = False, a: float = 1.0, b: float = 0.0, f: Optional[Vec] = None) -> Vec:
         """y = a K x + b f, or with A (identity rows / columns on the fixed dofs) when ``masked``."""
@@ -88,10 +92,42 @@ class DeviceElasticity:
                                        y.handle, int(bool(accumulate))))
         return y
 
+    def pc_setup(self, spacing_factor: float = 0.0) -> dict:
+        """Lattice plan of the multilevel preconditioner (once per mesh); 0 selects the default spacing factor."""
+        check(self.lib.femo_elast_pc_setup(self.handle, float(spacing_factor)))
+        self.pc_plan = {k: v for k, v in self.pc_info().items() if k in ("levels", "bytes", "nodes")}
+        return self.pc_plan
+
+    def pc_info(self) -> dict:
+        """levels, lattice bytes, block builds so far, device ms of the last block build, nodes per level."""
+        buf = (C.c_int64 * _lib.ELAST_PC_INFO_COUNT)()
+        check(self.lib.femo_elast_pc_info(self.handle, buf))
+        nl = int(buf[0])
+        return dict(levels=nl, bytes=int(buf[1]), builds=int(buf[2]), build_ms=int(buf[3]) * 1e-3,
+                    nodes=[int(buf[4 + l]) for l in range(nl)])
+
+    def pc_level(self, level: int) -> np.ndarray:
+        """(nodes, d, d): the Galerkin blocks blockdiag(P_l^T A P_l) of lattice ``level``, before inversion."""
+        nodes = self.pc_info()["nodes"][level]
+        out = np.zeros((nodes, self.d, self.d))
+        check(self.lib.femo_elast_pc_export_level(self.handle, int(level), _ptr(out)))
+        return out
+
+    def pc_apply(self, r: Vec, z: Vec) -> Vec:
+        """z = M^-1 r with the multilevel preconditioner."""
+        check(self.lib.femo_elast_pc_apply(self.handle, r.handle, z.handle))
+        return z
+
     def solve(self, b: Vec, x: Vec, rtol: float = 1e-15, atol: float = 0.0, max_it: int = 1_000_000,
-              check_every: int = 64, zero_guess: bool = True) -> _lib.SolveInfo:
+              check_every: Optional[int] = None, zero_guess: bool = True, pc: str = "jacobi") -> _lib.SolveInfo:
+        """PCG; ``pc`` = "jacobi" or "multilevel" (needs `pc_setup`).  Polls every 64 iterations with Jacobi, and every 8
+        (the library's default) with the multilevel preconditioner, unless ``check_every`` says otherwise."""
+        if pc not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
+        if check_every is None:
+            check_every = 64 if pc == "jacobi" else 0
         opts = _lib.SolverOpts(rtol=float(rtol), atol=float(atol), max_it=int(max_it), zero_guess=int(bool(zero_guess)),
-                               check_every=int(check_every), pc=0, atol_pc=0.0)
+                               check_every=int(check_every), pc=PRECONDITIONERS[pc], atol_pc=0.0)
         info = _lib.SolveInfo()
         check(self.lib.femo_elast_solve(self.handle, b.handle, x.handle, C.byref(opts), C.byref(info)))
         return info
@@ -279,7 +315,8 @@ class ElasticityMatrix:
     def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
         o = options or {}
         dev = self.form.stiffness()
-        self.info = dev.solve(b, x, rtol=o.get("elast_rtol", self.form.rtol), max_it=o.get("elast_max_it", 1_000_000))
+        self.info = dev.solve(b, x, rtol=o.get("elast_rtol", self.form.rtol), max_it=o.get("elast_max_it", 1_000_000),
+                              pc=self.form.preconditioner)
         self.form._record(self.info, "adjoint")
 
     def to_scipy(self):
@@ -329,13 +366,16 @@ class ElasticityResidual(BackendForm):
     constant_partials = False
 
     def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, E: float = 1.0,
-                 nu: float = 0.3, method: str = "SIMP"):
+                 nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi"):
         if not isinstance(u.function_space, VectorFunctionSpace):
             raise NotImplementedError("ElasticityResidual needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
         if rho.function_space.family != "DG" or rho.function_space.mesh is not u.function_space.mesh:
             raise NotImplementedError("ElasticityResidual needs a DG0 density on the state's mesh")
         if method not in METHODS:
             raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
+        if preconditioner not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {preconditioner!r} (jacobi or multilevel)")
+        self.preconditioner = preconditioner
         self.u, self.rho, self.mesh = u, rho, u.function_space.mesh
         self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
         self.t = _traction(traction, self.mesh)
@@ -372,12 +412,15 @@ class ElasticityResidual(BackendForm):
         if getattr(dev, "_owner", None) != key:
             dev.assemble(self.method_id, self.rho.vec)
             dev._owner = key
+        if self.preconditioner == "multilevel" and dev.pc_plan is None:
+            dev.pc_setup()
         return dev
 
     def _record(self, info, kind: str) -> None:
         from .utils_hip import LAST_KSP_INFO
         self.last_info[kind] = dict(iterations=info.iterations, converged=info.converged, solve_ms=info.solve_ms,
-                                    residual_norm=info.residual_norm, rhs_norm=info.rhs_norm)
+                                    residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
+                                    preconditioner=self.preconditioner)
         LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_" + kind))
         if info.converged != 1:
             raise RuntimeError(f"elasticity PCG did not converge ({kind}): {info.iterations} iterations, "
@@ -439,7 +482,7 @@ class ElasticityResidual(BackendForm):
         """K(rho) u = F with the strongly imposed dofs: one PCG solve (the form is linear)."""
         self._set_bcs(bcs)
         dev = self.stiffness()
-        info = dev.solve(self._rhs(dev), func.vec, rtol=self.rtol)
+        info = dev.solve(self._rhs(dev), func.vec, rtol=self.rtol, pc=self.preconditioner)
         func.version += 1
         self._record(info, "state")
         if report:
@@ -498,9 +541,10 @@ def averageFunc(func: Function) -> LinearFunctional:
 
 
 # ---------------------------------------------------------------------------- builders of the run script (:85-109) ----
-def pdeRes(u, v, rho_e, f, E: float = 1.0, dss: Optional[Measure] = None, method: str = "SIMP") -> ElasticityResidual:
+def pdeRes(u, v, rho_e, f, E: float = 1.0, dss: Optional[Measure] = None, method: str = "SIMP",
+           preconditioner: str = "jacobi") -> ElasticityResidual:
     """run_topo_opt_cantilever_beam.py:85-101 (nu = 0.3 as there); ``v`` is implied by the catalogue."""
-    return ElasticityResidual(u, rho_e, f, dss, E=E, nu=0.3, method=method)
+    return ElasticityResidual(u, rho_e, f, dss, E=E, nu=0.3, method=method, preconditioner=preconditioner)
 
 
 def compliance(u, f, dss: Optional[Measure] = None) -> Compliance:

@@ -612,8 +612,35 @@ int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rh
                     femo_vec* y, int accumulate);
 /* A x = b by device-resident PCG with the block-Jacobi preconditioner (solveKSP_mumps, utils_dolfinx.py:476-493); K is
  * symmetric, so the adjoint solve is the same call.  Fixed dofs: x = b there.  Stops on sqrt(r^T M^-1 r) <=
- * max(rtol sqrt(r0^T M^-1 r0), atol); convergence is polled every check_every iterations.  opts->pc is ignored.         */
+ * max(rtol sqrt(r0^T M^-1 r0), atol); convergence is polled every check_every iterations (0 = 32, or 8 with the
+ * multilevel preconditioner).  opts->pc: FEMO_ELAST_PC_MULTILEVEL selects the preconditioner below (an error unless
+ * femo_elast_pc_setup was called); every other value is block-Jacobi (M = the diagonal blocks), as before the field was read. */
+enum { FEMO_ELAST_PC_JACOBI = 0, FEMO_ELAST_PC_MULTILEVEL = 1 };
 int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info);
+/* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
+ *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
+ * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices
+ * (the same weights for all d components, zero rows on fixed dofs).  The coarsest lattice has one bin along the shortest
+ * axis of the box; every finer one halves the spacing; there are 1 + round(log2(shortest extent / (spacing_factor * mean
+ * edge length))) of them (spacing_factor 0 = the default, 2).  The plan is built once per mesh; the d x d blocks are rebuilt
+ * inside femo_elast_solve / femo_elast_pc_apply / femo_elast_pc_export_level whenever femo_elast_assemble or
+ * femo_elast_set_fixed ran since the last build.  The rebuild reads the density vector of the last femo_elast_assemble,
+ * which must still exist and be unchanged (an error otherwise: assemble again); a wrapped vector (femo_vec_wrap) cannot be
+ * recognised later, so its blocks are built inside femo_elast_assemble when the plan exists.  femo_elast_pc_setup refuses a
+ * mesh whose second-finest lattice exceeds 2^18 nodes: the lattices below the finest are swept by one workgroup.        */
+enum { FEMO_ELAST_PC_INFO_LEVELS = 0,      /* number of lattices                                                      */
+       FEMO_ELAST_PC_INFO_BYTES = 1,       /* device bytes of the lattices: blocks, their inverses, work vectors      */
+       FEMO_ELAST_PC_INFO_BUILDS = 2,      /* block builds so far                                                     */
+       FEMO_ELAST_PC_INFO_BUILD_US = 3,    /* device time of the last block build, microseconds                       */
+       FEMO_ELAST_PC_INFO_NODES = 4,       /* [4 + l]: nodes of lattice l, coarsest first (FEMO_ELAST_PC_MAX_LEVELS)   */
+       FEMO_ELAST_PC_MAX_LEVELS = 12, FEMO_ELAST_PC_INFO_COUNT = 16 };
+int femo_elast_pc_setup(femo_elast* e, double spacing_factor);
+int femo_elast_pc_info(const femo_elast* e, int64_t info[FEMO_ELAST_PC_INFO_COUNT]);
+/* blocks[nodes(level) * d * d]: the Galerkin blocks blockdiag_d(P_l^T A P_l) BEFORE inversion, row-major per node
+ * (node index: x fastest); zero where no free dof touches the node.  Rebuilds the blocks first if they are out of date. */
+int femo_elast_pc_export_level(femo_elast* e, int level, double* blocks);
+/* z = M^-1 r outside the solver (tests); on fixed dofs z = r, as the block-Jacobi inverse maps them.                    */
+int femo_elast_pc_apply(femo_elast* e, const femo_vec* r, femo_vec* z);
 /* K as block CSR on the scalar pattern of femo_mesh_pattern_csr: val[nnz * d * d], block (row comp, col comp) row-major. */
 int femo_elast_export_csr(const femo_elast* e, int64_t* rowptr, int32_t* col, double* val);
 /* reps block SpMV launches (unmasked) timed with device events: mean ms per launch.                                      */

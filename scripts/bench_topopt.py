@@ -5,6 +5,7 @@ and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the
 
   python scripts/bench_topopt.py --nelx 640 --nely 320          (2-D cantilever, the reference's driver at that size)
   python scripts/bench_topopt.py --n3 48                        (3-D unit cube, clamped at x = 0, load on x = 1)
+  ... --pc multilevel                                           (the lattice preconditioner of csrc/elast_pc.hip; default jacobi)
 """
 from __future__ import annotations
 
@@ -47,7 +48,7 @@ def build(args):
     Q, V = FunctionSpace(mesh, ("DG", 0)), VectorFunctionSpace(mesh, ("CG", 1))
     rho, u = Function(Q), Function(V)
     f = Constant(mesh, t)
-    res = pdeRes(u, None, rho, f, dss=ds_(100))
+    res = pdeRes(u, None, rho, f, dss=ds_(100), preconditioner=args.pc)
     fea.add_input("density", rho)
     fea.add_state(name="displacements", function=u, residual_form=res, arguments=["density"])
     fea.add_output(name="avg_density", type="scalar", form=averageFunc(rho), arguments=["density"])
@@ -108,6 +109,7 @@ def main():
     ap.add_argument("--n3", type=int, default=0)
     ap.add_argument("--cycles", type=int, default=3)
     ap.add_argument("--no-scipy", action="store_true")
+    ap.add_argument("--pc", choices=("jacobi", "multilevel"), default="jacobi", help="preconditioner of the PCG solves")
     args = ap.parse_args()
     from femo_amd import _lib
     from femo_amd.engine import Context, Vec
@@ -137,7 +139,12 @@ def main():
                pcg_iterations_forward=info["state"]["iterations"], pcg_iterations_adjoint=info["adjoint"]["iterations"],
                spmv_ms=spmv_ms, spmv_bytes=dev.info["spmv_bytes"],
                spmv_share_of_8TBps=dev.info["spmv_bytes"] / (spmv_ms * 1e-3) / PEAK_BYTES_PER_S,
-               filter_build_ms=filter_build_ms, compliance=float(sim["compliance"][0]))
+               filter_build_ms=filter_build_ms, compliance=float(sim["compliance"][0]), pc=args.pc, pc_levels=0,
+               pc_build_ms=0.0,
+               pcg_iteration_us=1e3 * info["state"]["solve_ms"] / max(info["state"]["iterations"], 1))
+    if args.pc == "multilevel":
+        pci = dev.pc_info()
+        out.update(pc_levels=pci["levels"], pc_build_ms=pci["build_ms"], pc_nodes=pci["nodes"], pc_lattice_bytes=pci["bytes"])
     if not args.no_scipy:
         h = np.asarray(__import__("femo_amd.fea.mesh", fromlist=["meshSize"]).meshSize(mesh))
         sc_ms, sc_J, sc_g = scipy_cycle(mesh, facets, t, np.array(sim["density_unfiltered"]), 2.0 * (h.max() + h.min()) / 2)

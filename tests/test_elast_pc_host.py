@@ -1,0 +1,95 @@
+"""Host checks of the multilevel elasticity preconditioner: the restatement (tests/elast_pc_ref.py) against its own
+definitions, the caps of the GPU count tests met by the restatement alone, and the binding of the new entry points."""
+import numpy as np
+import pytest
+
+import elast_pc_ref as pr
+import elasticity_ref as ref
+
+def _case(name, method="SIMP"):
+    mesh = pr.small_meshes()[name]()
+    rho = np.random.default_rng(7).uniform(1e-3, 1.0, mesh.n_cell)
+    mask = pr.clamped_face(mesh)
+    return mesh, rho, mask, pr.Multilevel(mesh.x, mesh.conn, rho, method, mask)
+
+
+@pytest.mark.parametrize("name", ["rect8x4", "square9j", "cube4j"])
+def test_plan(name):
+    mesh = pr.small_meshes()[name]()
+    plan = pr.lattice_plan(mesh.x, mesh.conn)
+    assert min(plan["n"][0]) == 1                                    # one bin along the shortest axis
+    for l in range(1, plan["n_levels"]):
+        assert np.array_equal(plan["n"][l], 2 * plan["n"][l - 1]) and plan["H"][l] == plan["H"][l - 1] / 2
+    h = pr.mean_edge_length(mesh.x, mesh.conn)
+    assert 2.0 ** -0.5 <= plan["H"][-1] / (2.0 * h) <= 2.0 ** 0.5 or plan["n_levels"] == 1
+    if name == "rect8x4":
+        assert plan["nodes"][0] == 6
+
+
+@pytest.mark.parametrize("name", ["rect8x4", "square9j", "cube4j"])
+def test_symmetric_positive(name):
+    mesh, rho, mask, M = _case(name)
+    rng = np.random.default_rng(3)
+    n = mesh.tdim * mesh.n_vert
+    for _ in range(4):
+        x, y = rng.standard_normal(n), rng.standard_normal(n)
+        Mx, My = M.apply(x), M.apply(y)
+        assert abs(x @ My - y @ Mx) <= 1e-13 * np.linalg.norm(x) * np.linalg.norm(My)
+        assert x @ Mx > 0.0
+    # fixed dofs map as the block-Jacobi inverse maps them: z = r there
+    x = rng.standard_normal(n)
+    assert np.array_equal(M.apply(x)[mask == 1], x[mask == 1])
+
+
+@pytest.mark.parametrize("name", ["rect8x4", "square9j", "cube4j"])
+def test_lattices_are_nested(name):
+    mesh = pr.small_meshes()[name]()
+    plan = pr.lattice_plan(mesh.x, mesh.conn)
+    last = plan["n_levels"] - 1
+    assert last >= 1
+    PL = pr.interpolation(plan, mesh.x, last)
+    assert abs(PL.sum(axis=1) - 1.0).max() <= 1e-14                  # partition of unity
+    for l in range(last):
+        P = pr.interpolation(plan, mesh.x, l)
+        assert abs(P - PL @ pr.lattice_transfer(plan, last, l)).max() <= 1e-14
+
+
+@pytest.mark.parametrize("name", ["rect8x4", "square9j", "cube4j"])
+@pytest.mark.parametrize("method", ["SIMP", "RAMP"])
+def test_cell_formula_matches_sparse_product(name, method):
+    mesh, rho, mask, M = _case(name, method)
+    coef = ref.penal(rho, method)
+    for l in range(M.plan["n_levels"]):
+        B = pr.cell_blocks(M.plan, mesh.x, mesh.conn, coef, l, mask)
+        assert np.abs(B - M.G[l]).max() <= 1e-13 * np.abs(M.G[l]).max()
+
+
+def reference_counts(nelx, nely, kind):
+    mesh, rho, mask, facets, F = pr.count_case(nelx, nely, kind)
+    M = pr.Multilevel(mesh.x, mesh.conn, rho, "SIMP", mask)
+    _, nj, cj = pr.pcg(M.A, F, M.jacobi, mask)
+    _, nm, cm = pr.pcg(M.A, F, M.apply, mask)
+    assert cj and cm
+    return nj, nm
+
+
+@pytest.mark.parametrize("kind", ["uniform", "truss"])
+def test_reference_counts_meet_the_caps(kind):
+    """The caps of tests/test_gpu_elast_pc.py::test_counts hold for the restatement itself on the same inputs:
+    Jacobi >= 4 x multilevel at 80 x 40 and >= 10 x at 320 x 160, and count(320 x 160) <= 1.3 count(80 x 40)."""
+    j80, m80 = reference_counts(80, 40, kind)
+    j320, m320 = reference_counts(320, 160, kind)
+    print(f"{kind}: 80x40 jacobi {j80} multilevel {m80}; 320x160 jacobi {j320} multilevel {m320}")
+    assert j80 >= 4 * m80
+    assert j320 >= 10 * m320
+    assert m320 <= 1.3 * m80
+
+
+def test_lib_binds_the_entry_points():
+    from femo_amd import _lib
+    lib = _lib.load()
+    for name in ("femo_elast_pc_setup", "femo_elast_pc_info", "femo_elast_pc_export_level", "femo_elast_pc_apply"):
+        assert name in _lib.PROTOTYPES
+        assert getattr(lib, name).argtypes == _lib.PROTOTYPES[name][1]
+    assert _lib.ELAST_PC == {"jacobi": 0, "multilevel": 1}
+
