@@ -202,6 +202,8 @@ PROTOTYPES = {
     "femo_elast_apply": (C.c_int, [H, C.c_int, C.c_double, H, C.c_double, H, H]),
     "femo_elast_load": (C.c_int, [H, c_f64p, H]),
     "femo_elast_drho": (C.c_int, [H, C.c_int, C.c_int, H, H, H, H, C.c_int]),
+    "femo_elast_pnorm_stress": (C.c_int, [H, H, H, C.c_double, C.c_double, C.c_double, C.c_double, c_f64p, H, H, C.c_int]),
+    "femo_elast_von_mises": (C.c_int, [H, H, H, C.c_double, H]),
     "femo_elast_solve": (C.c_int, [H, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
     "femo_elast_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "femo_elast_pc_setup": (C.c_int, [H, C.c_double]),

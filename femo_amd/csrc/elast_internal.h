@@ -25,6 +25,8 @@ struct femo_elast {
   int32_t* w_flag = nullptr;
   int32_t* h_flag = nullptr;    // pinned
   double* h_s = nullptr;        // pinned
+  // stress aggregate (femo_elast_pnorm_stress): one partial per cell block and the folded value behind them, on first use
+  double* w_spart = nullptr;
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
   femo_elast_pc* pc = nullptr;
   bool pc_dirty = true;

@@ -257,6 +257,124 @@ __global__ __launch_bounds__(EB) void k_elast_drho_N(
   for (int r = 0; r < D; ++r) y[row * D + r] = accumulate ? y[row * D + r] + acc[r] : acc[r];
 }
 
+// ------------------------------------------------------------------------------------------------ stress ----
+// Solid-material stress sigma_0(u) of a P1 cell as a 3 x 3 tensor (plane strain in 2-D: sigma_zz = lam tr eps, no
+// out-of-plane shear).  Its deviator does not see lam: s = 2 mu (eps - tr(eps) / 3 I), so s_zz = -2 mu tr(eps) / 3 in
+// 2-D.  Returns sigma_vm = sqrt(3/2 s : s); s holds the d x d block of the deviator.
+template <int D>
+__device__ __forceinline__ double cell_von_mises(const double (&g)[D + 1][D], const int32_t (&v)[D + 1],
+                                                 const double* __restrict__ u, double mu, double (&s)[D][D]) {
+  double Gu[D][D];      // Gu[i][k] = du_i/dx_k
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) Gu[i][k] = 0.0;
+#pragma unroll
+  for (int b = 0; b <= D; ++b)
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const double ub = u[(int64_t)v[b] * D + i];
+#pragma unroll
+      for (int k = 0; k < D; ++k) Gu[i][k] += ub * g[b][k];
+    }
+  double tr = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) tr += Gu[i][i];
+  const double hyd = (2.0 / 3.0) * mu * tr;
+  double ss = D == 2 ? hyd * hyd : 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const double t = mu * (Gu[i][k] + Gu[k][i]) - (i == k ? hyd : 0.0);
+      s[i][k] = t;
+      ss += t * t;
+    }
+  return sqrt(1.5 * ss);
+}
+
+// One thread per cell, every output optional by null pointer:
+//   field[c] = rho_c^q sigma_vm                                       (the relaxed cell stress)
+//   part[block] = sum over the block of J_c = |T_c| / alpha (m rho_c^q sigma_vm)^p
+//   drho[c] (+)= p q / rho_c J_c
+// rho == null reads as q = 0.  A cell with sigma_vm = 0 gives 0 everywhere (pow(0, p) = 0 for p >= 1; no division by it).
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_stress_cell(int64_t n_cell, const int32_t* __restrict__ conn,
+                                                          const double* __restrict__ xv, const double* __restrict__ rho,
+                                                          const double* __restrict__ u, double mu, double m, double p, double q,
+                                                          double inv_alpha, double* __restrict__ field,
+                                                          double* __restrict__ part, double* __restrict__ drho, int accumulate) {
+  __shared__ double lds[EB / 64];
+  const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
+  double Jc = 0.0;
+  if (c < n_cell) {
+    int32_t v[D + 1];
+    double pt[D + 1][D], g[D + 1][D], s[D][D], vol;
+    load_cell<D>(conn, xv, c, v, pt);
+    simplex_grads<D>(pt, g, vol);
+    const double vm = cell_von_mises<D>(g, v, u, mu, s);
+    const double r = rho ? rho[c] : 1.0;
+    const double relaxed = (rho && q != 0.0 ? pow(r, q) : 1.0) * vm;
+    if (field) field[c] = relaxed;
+    if (part || drho) {
+      Jc = vm > 0.0 ? vol * inv_alpha * pow(m * relaxed, p) : 0.0;
+      if (drho) {
+        const double d = q != 0.0 && Jc != 0.0 ? p * q / r * Jc : 0.0;
+        drho[c] = accumulate ? drho[c] + d : d;
+      }
+    }
+  }
+  if (part) {
+    const double t = femo_block_sum<EB>(Jc, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+  }
+}
+
+// dJ/du, the walk of k_elast_drho_N: y_(v, r) (+)= sum over the cells c around v of (tau_c grad phi_v)_r with
+// tau = 2 mu S + lam tr(S) I and S = dJ_c/dsigma = |T| / alpha p (m rho^q)^p sigma_vm^(p-2) 3/2 s.  S is a deviator, so the lam
+// term is zero and tau = 2 mu S; only its d x d block meets grad phi.  Written as w (s / sigma_vm) with
+// w = 3 mu p J_c / sigma_vm = 3 mu p |T| / alpha (m rho^q)^p sigma_vm^(p-1): no negative power of sigma_vm for p >= 1, and the cell is
+// skipped when sigma_vm = 0.  One writer per vertex, cells in ascending order: no float atomics, the same bits every call.
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_stress_du(
+    int64_t n_rows, const int64_t* __restrict__ vptr, const int32_t* __restrict__ visit_cell, const int32_t* __restrict__ conn,
+    const double* __restrict__ xv, const double* __restrict__ rho, const double* __restrict__ u, double mu, double m, double p,
+    double q, double inv_alpha, double* __restrict__ y, int accumulate) {
+  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (row >= n_rows) return;
+  const int64_t slice = row >> 6;
+  const int lane = (int)(row & 63);
+  const int64_t vb = vptr[slice];
+  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
+  double acc[D];
+#pragma unroll
+  for (int r = 0; r < D; ++r) acc[r] = 0.0;
+  for (int k = 0; k < nvis; ++k) {
+    const int32_t ca = visit_cell[vb + (int64_t)k * 64 + lane];
+    if (ca < 0) continue;
+    const int64_t c = ca >> 2;
+    const int a = ca & 3;
+    int32_t v[D + 1];
+    double pt[D + 1][D], g[D + 1][D], s[D][D], vol;
+    load_cell<D>(conn, xv, c, v, pt);
+    simplex_grads<D>(pt, g, vol);
+    const double vm = cell_von_mises<D>(g, v, u, mu, s);
+    if (!(vm > 0.0)) continue;
+    const double mr = m * (q != 0.0 ? pow(rho[c], q) : 1.0);
+    const double w = 3.0 * mu * p * vol * inv_alpha * mr * pow(mr * vm, p - 1.0);
+    if (w == 0.0) continue;
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      double t = 0.0;
+#pragma unroll
+      for (int j = 0; j < D; ++j) t += (s[r][j] / vm) * g[a][j];
+      acc[r] += w * t;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < D; ++r) y[row * D + r] = accumulate ? y[row * D + r] + acc[r] : acc[r];
+}
+
 // ------------------------------------------------------------------------------------------- traction ----
 template <int D>
 __global__ __launch_bounds__(EB) void k_elast_load(int64_t n_vert, const int64_t* __restrict__ fptr,
@@ -607,7 +725,7 @@ int femo_elast_destroy(femo_elast* e) {
   femo_elast_pc_free(e);
   hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
-  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag);
+  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_spart);
   if (e->h_flag) hipHostFree(e->h_flag);
   if (e->h_s) hipHostFree(e->h_s);
   delete e;
@@ -764,6 +882,75 @@ int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rh
   }
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ stress ----
+static int stress_cell_launch(femo_elast* e, const double* rho, const double* u, double m, double p, double q, double inv_alpha,
+                              double* field, double* part, double* drho, int accumulate) {
+  femo_mesh* mh = e->mesh;
+  const unsigned g = grid_of(mh->n_cell);
+  FEMO_REQUIRE((int64_t)g * EB >= mh->n_cell, "too many cells for one launch");
+  if (e->d == 2)
+    hipLaunchKernelGGL(k_elast_stress_cell<2>, dim3(g), dim3(EB), 0, mh->ctx->stream, mh->n_cell, mh->d_conn, mh->d_x, rho, u,
+                       e->mu0, m, p, q, inv_alpha, field, part, drho, accumulate);
+  else
+    hipLaunchKernelGGL(k_elast_stress_cell<3>, dim3(g), dim3(EB), 0, mh->ctx->stream, mh->n_cell, mh->d_conn, mh->d_x, rho, u,
+                       e->mu0, m, p, q, inv_alpha, field, part, drho, accumulate);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_elast_pnorm_stress(femo_elast* e, const femo_vec* rho, const femo_vec* u, double m, double p, double q, double alpha,
+                            double* value, femo_vec* grad_u, femo_vec* grad_rho, int accumulate) {
+  FEMO_REQUIRE(e && rho && u, "null argument");
+  femo_mesh* mh = e->mesh;
+  const int64_t n = mh->n_vert * e->d;
+  FEMO_REQUIRE(rho->n >= mh->n_cell && u->n >= n && (!grad_u || grad_u->n >= n) && (!grad_rho || grad_rho->n >= mh->n_cell),
+               "vector size mismatch in femo_elast_pnorm_stress");
+  FEMO_REQUIRE(m > 0.0 && p >= 1.0 && q >= 0.0 && alpha > 0.0 && std::isfinite(m) && std::isfinite(p) && std::isfinite(q) &&
+               std::isfinite(alpha), "bad parameters of the stress aggregate: need m > 0, p >= 1, q >= 0, alpha > 0");
+  FEMO_REQUIRE(grad_u != u && grad_u != rho && grad_rho != rho && grad_rho != u && (!grad_u || grad_u != grad_rho),
+               "femo_elast_pnorm_stress: output aliases an input");
+  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u));
+  hipStream_t st = mh->ctx->stream;
+  const int nb = (int)grid_of(mh->n_cell);
+  if (value && !e->w_spart) FEMO_TRY(dalloc(&e->w_spart, (int64_t)nb + 1));
+  if (grad_rho) femo_vec_touch(grad_rho);
+  if (value || grad_rho)
+    FEMO_TRY(stress_cell_launch(e, rho->d, u->d, m, p, q, 1.0 / alpha, nullptr, value ? e->w_spart : nullptr,
+                                grad_rho ? grad_rho->d : nullptr, accumulate));
+  if (grad_u) {
+    femo_vec_touch(grad_u);
+    const unsigned g = grid_of(mh->n_rows);
+    if (e->d == 2)
+      hipLaunchKernelGGL(k_elast_stress_du<2>, dim3(g), dim3(EB), 0, st, mh->n_rows, mh->d_vptr, mh->d_visit_cell, mh->d_conn,
+                         mh->d_x, rho->d, u->d, e->mu0, m, p, q, 1.0 / alpha, grad_u->d, accumulate);
+    else
+      hipLaunchKernelGGL(k_elast_stress_du<3>, dim3(g), dim3(EB), 0, st, mh->n_rows, mh->d_vptr, mh->d_visit_cell, mh->d_conn,
+                         mh->d_x, rho->d, u->d, e->mu0, m, p, q, 1.0 / alpha, grad_u->d, accumulate);
+    FEMO_HIP_CHECK(hipGetLastError());
+  }
+  if (value) {
+    FEMO_TRY(femo_launch_fold(1024, nb, 1, e->w_spart, e->w_spart + nb, st));
+    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_s, e->w_spart + nb, sizeof(double), hipMemcpyDeviceToHost, st));
+    FEMO_HIP_CHECK(hipStreamSynchronize(st));
+    *value = e->h_s[0];
+  }
+  return 0;
+}
+
+int femo_elast_von_mises(femo_elast* e, const femo_vec* rho, const femo_vec* u, double q, femo_vec* out_cells) {
+  FEMO_REQUIRE(e && u && out_cells, "null argument");
+  FEMO_REQUIRE(q >= 0.0 && std::isfinite(q), "femo_elast_von_mises: need q >= 0");
+  FEMO_REQUIRE(rho || q == 0.0, "femo_elast_von_mises: q > 0 needs the density");
+  femo_mesh* mh = e->mesh;
+  FEMO_REQUIRE(u->n >= mh->n_vert * e->d && out_cells->n >= mh->n_cell && (!rho || rho->n >= mh->n_cell),
+               "vector size mismatch in femo_elast_von_mises");
+  FEMO_REQUIRE(out_cells != u && out_cells != rho, "femo_elast_von_mises: output aliases an input");
+  FEMO_TRY(femo_vec_await(u));
+  if (rho) FEMO_TRY(femo_vec_await(rho));
+  femo_vec_touch(out_cells);
+  return stress_cell_launch(e, rho ? rho->d : nullptr, u->d, 1.0, 1.0, q, 1.0, out_cells->d, nullptr, nullptr, 0);
 }
 
 int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info) {

@@ -10,6 +10,11 @@ are used unchanged.
                        lambda_0 = E nu / ((1 + nu)(1 - 2 nu)), mu_0 = E / (2 (1 + nu)) -- plane strain in 2-D
   Compliance           J = int_ds(tag) t . u ds = F^T u                                                 (compliance, :108-109)
   averageFunc          (1/|Omega|) int rho dx as a LinearFunctional with the DG0 coefficient |T_e| / |Omega| (:103-106)
+  ElasticityPnormStress  J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p, the aggregated von Mises stress of the solid
+                       material: sigma_vm = sqrt(3/2 s : s), s the deviator of sigma_0(u) as a 3 x 3 tensor (plane strain in
+                       2-D: sigma_zz = lambda_0 tr eps); rho^q sigma_vm is the qp-relaxed cell stress.  Not in the reference's
+                       script: the solid counterpart of the shell's pnorm_stress (shell_pde.py:297-313)
+  ElasticityVonMises   the cell field rho_e^q sigma_vm,e for `project` / FEA.add_field_output
 
 P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
 """
@@ -91,6 +96,21 @@ class DeviceElasticity:
         check(self.lib.femo_elast_drho(self.handle, int(method), int(bool(transpose)), rho.handle, u.handle, x.handle,
                                        y.handle, int(bool(accumulate))))
         return y
+
+    def pnorm_stress(self, rho: Vec, u: Vec, m: float, p: float, q: float, alpha: float, value: bool = True,
+                     grad_u: Optional[Vec] = None, grad_rho: Optional[Vec] = None, accumulate: bool = False):
+        """J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p (returned when ``value``), dJ/du into ``grad_u`` and dJ/drho
+        into ``grad_rho`` (added onto them with ``accumulate``)."""
+        val = C.c_double(0.0)
+        check(self.lib.femo_elast_pnorm_stress(self.handle, rho.handle, u.handle, float(m), float(p), float(q), float(alpha),
+                                               C.byref(val) if value else None, None if grad_u is None else grad_u.handle,
+                                               None if grad_rho is None else grad_rho.handle, int(bool(accumulate))))
+        return val.value if value else None
+
+    def von_mises(self, u: Vec, out: Vec, rho: Optional[Vec] = None, q: float = 0.0) -> Vec:
+        """out[n_cell] = rho_e^q sigma_vm,e; the solid stress (q = 0) needs no density."""
+        check(self.lib.femo_elast_von_mises(self.handle, None if rho is None else rho.handle, u.handle, float(q), out.handle))
+        return out
 
     def pc_setup(self, spacing_factor: float = 0.0) -> dict:
         """Lattice plan of the multilevel preconditioner (once per mesh); 0 selects the default spacing factor."""
@@ -529,6 +549,88 @@ def cell_volumes(mesh) -> np.ndarray:
     return np.abs(np.linalg.det(J)) / fact
 
 
+def _check_stress_spaces(name: str, u: Function, rho: Optional[Function]) -> None:
+    if not isinstance(u.function_space, VectorFunctionSpace):
+        raise NotImplementedError(f"{name} needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
+    if rho is not None and (rho.function_space.family != "DG" or rho.function_space.mesh is not u.function_space.mesh):
+        raise NotImplementedError(f"{name} needs a DG0 density on the state's mesh")
+
+
+class ElasticityPnormStress(BackendForm):
+    """J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p with the solid-material von Mises stress (module docstring);
+    alpha = |Omega| unless given.  dJ/du is not a multiple of the load: its adjoint solve is a solve of its own."""
+    rank = 0
+
+    def __init__(self, u: Function, rho: Function, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0,
+                 q: float = 0.5, alpha: Optional[float] = None):
+        _check_stress_spaces("ElasticityPnormStress", u, rho)
+        if not (m > 0.0 and p >= 1.0 and q >= 0.0) or (alpha is not None and not alpha > 0.0):
+            raise ValueError("the stress aggregate needs m > 0, p >= 1, q >= 0 and alpha > 0")
+        self.u, self.rho, self.mesh = u, rho, u.function_space.mesh
+        self.E, self.nu, self.m, self.p, self.q = float(E), float(nu), float(m), float(p), float(q)
+        self.alpha = float(cell_volumes(self.mesh).sum() if alpha is None else alpha)
+        self._grad = {}
+
+    def functions(self):
+        return (self.u, self.rho)
+
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
+
+    def assemble_scalar(self) -> float:
+        return self.device().pnorm_stress(self.rho.vec, self.u.vec, self.m, self.p, self.q, self.alpha)
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:                                            # one buffer per argument: both partials may be pending
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        if wrt is self.u:
+            self.device().pnorm_stress(self.rho.vec, self.u.vec, self.m, self.p, self.q, self.alpha, value=False, grad_u=out)
+        elif wrt is self.rho:
+            self.device().pnorm_stress(self.rho.vec, self.u.vec, self.m, self.p, self.q, self.alpha, value=False, grad_rho=out)
+        else:
+            out.fill(0.0)
+        return out
+
+
+class ElasticityVonMises(BackendForm):
+    """The cell field rho_e^q sigma_vm,e (q = 0: the stress of the solid material, no density needed).  `project` hands the
+    projection over: onto a DG0 target the cell values themselves, onto CG1 the L2 projection of a cell-wise constant."""
+    rank = 0
+
+    def __init__(self, u: Function, rho: Optional[Function] = None, E: float = 1.0, nu: float = 0.3, q: float = 0.0):
+        _check_stress_spaces("ElasticityVonMises", u, rho)
+        if not q >= 0.0 or (q > 0.0 and rho is None):
+            raise ValueError("the relaxed von Mises stress needs q >= 0, and the density when q > 0")
+        self.u, self.rho, self.mesh = u, rho, u.function_space.mesh
+        self.E, self.nu, self.q = float(E), float(nu), float(q)
+        self._cells = None
+
+    def functions(self):
+        return (self.u,) if self.rho is None else (self.u, self.rho)
+
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
+
+    def project_field(self, target: Function, lump_mass: bool = False) -> Function:
+        V = target.function_space
+        if V.mesh is not self.mesh or isinstance(V, VectorFunctionSpace) or V.family not in ("DG", "CG"):
+            raise NotImplementedError("the von Mises stress is projected onto the DG0 or the CG1 space of the state's mesh")
+        rho = None if self.rho is None else self.rho.vec
+        if V.family == "DG":
+            self.device().von_mises(self.u.vec, target.vec, rho, self.q)
+            target.version += 1
+            return target
+        if self._cells is None:
+            self._cells = Function(FunctionSpace(self.mesh, ("DG", 0)))
+        self.device().von_mises(self.u.vec, self._cells.vec, rho, self.q)
+        self._cells.version += 1
+        from .utils_hip import project
+        project(self._cells, target, lump_mass=lump_mass)           # the cell-constant path PowerExpr takes
+        return target
+
+
 def averageFunc(func: Function) -> LinearFunctional:
     """(1/|Omega|) int func dx for a DG0 Function (averageFunc, run_topo_opt_cantilever_beam.py:103-106)."""
     V = func.function_space
@@ -550,3 +652,14 @@ def pdeRes(u, v, rho_e, f, E: float = 1.0, dss: Optional[Measure] = None, method
 def compliance(u, f, dss: Optional[Measure] = None) -> Compliance:
     """run_topo_opt_cantilever_beam.py:108-109"""
     return Compliance(u, f, dss)
+
+
+def pnorm_stress(u, rho_e, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0, q: float = 0.5,
+                 alpha: Optional[float] = None) -> ElasticityPnormStress:
+    """The aggregated von Mises stress as a scalar output, named after the shell's builder (shell_pde.py:297-313)."""
+    return ElasticityPnormStress(u, rho_e, E=E, nu=nu, m=m, p=p, q=q, alpha=alpha)
+
+
+def von_Mises_stress(u, rho_e=None, E: float = 1.0, nu: float = 0.3, q: float = 0.0) -> ElasticityVonMises:
+    """The (relaxed) von Mises stress as a field output."""
+    return ElasticityVonMises(u, rho_e, E=E, nu=nu, q=q)

@@ -25,7 +25,7 @@ from .function import Function, FunctionSpace, VectorFunctionSpace
 from .io import XDMFRecorder
 from .mesh import (BeamMesh, Mesh, createIntervalMesh, createRectangleMesh, createUnitCubeMesh, createUnitSquareMesh,
                    findNodeIndices, locate_dofs_geometrical, locate_entities_boundary, meshSize)
-from .elasticity import Constant, Measure, meshtags
+from .elasticity import Constant, Measure, meshtags, pnorm_stress, von_Mises_stress
 
 
 class AbstractFEA(object):

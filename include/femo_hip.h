@@ -610,6 +610,19 @@ int femo_elast_load(femo_elast* e, const double* t, femo_vec* F);
  *   transpose = 0:  y[n_dof]  (+)= sum_e C'(rho_e) x_e K0_e u_e   (state_model.py:176-188, fwd mode; vertex walk)     */
 int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rho, const femo_vec* u, const femo_vec* x,
                     femo_vec* y, int accumulate);
+/* Aggregated von Mises stress of the SOLID material (a stress constraint beside the volume constraint):
+ *   J = 1/alpha sum_e |T_e| (m rho_e^q sigma_vm,e)^p,   sigma_vm = sqrt(3/2 s : s),  s = dev sigma_0(u) as a 3 x 3 tensor
+ * (plane strain in 2-D: sigma_zz = lambda_0 tr eps), lambda_0, mu_0 from femo_elast_create.  rho_e^q sigma_vm is the
+ * qp-relaxed cell stress (q = 0: the solid stress).  Any of the outputs may be NULL:
+ *   value             J, folded on the device in a fixed order (the call waits for it)
+ *   grad_u[n_dof]     (+)= dJ/du, vertex walk without float atomics: the same bits every call
+ *   grad_rho[n_cell]  (+)= dJ/drho_e = p q / rho_e J_e
+ * accumulate = 1 adds onto both gradients.  A cell with sigma_vm = 0 contributes 0 to all three.  Needs m > 0, p >= 1,
+ * q >= 0, alpha > 0; rho_e > 0 is the caller's contract when q > 0.                                                     */
+int femo_elast_pnorm_stress(femo_elast* e, const femo_vec* rho, const femo_vec* u, double m, double p, double q, double alpha,
+                            double* value, femo_vec* grad_u, femo_vec* grad_rho, int accumulate);
+/* out_cells[n_cell] = rho_e^q sigma_vm,e, the cell field of the aggregate above; rho may be NULL when q == 0.           */
+int femo_elast_von_mises(femo_elast* e, const femo_vec* rho, const femo_vec* u, double q, femo_vec* out_cells);
 /* A x = b by device-resident PCG with the block-Jacobi preconditioner (solveKSP_mumps, utils_dolfinx.py:476-493); K is
  * symmetric, so the adjoint solve is the same call.  Fixed dofs: x = b there.  Stops on sqrt(r^T M^-1 r) <=
  * max(rtol sqrt(r0^T M^-1 r0), atol); convergence is polled every check_every iterations (0 = 32, or 8 with the

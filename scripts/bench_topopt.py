@@ -6,6 +6,9 @@ and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the
   python scripts/bench_topopt.py --nelx 640 --nely 320          (2-D cantilever, the reference's driver at that size)
   python scripts/bench_topopt.py --n3 48                        (3-D unit cube, clamped at x = 0, load on x = 1)
   ... --pc multilevel                                           (the lattice preconditioner of csrc/elast_pc.hip; default jacobi)
+  ... --stress                                                  (adds the aggregated von Mises stress as a second scalar output and its
+                                                                 total derivative to the cycle: one more adjoint solve, whose right-hand
+                                                                 side is not the load; reported as extra keys of the JSON line)
 """
 from __future__ import annotations
 
@@ -53,6 +56,12 @@ def build(args):
     fea.add_state(name="displacements", function=u, residual_form=res, arguments=["density"])
     fea.add_output(name="avg_density", type="scalar", form=averageFunc(rho), arguments=["density"])
     fea.add_output(name="compliance", type="scalar", form=compliance(u, f, dss=ds_(100)), arguments=["displacements"])
+    stress = None
+    if args.stress:
+        from femo_amd.fea.elasticity import pnorm_stress
+        stress = pnorm_stress(u, rho, p=8.0, q=0.5)                 # m is set from the first state (main)
+        fea.add_output(name="stress", type="scalar", form=stress, arguments=["displacements", "density"])
+        fea.consistent_bc_partials = True                           # dJ/du is not zero on the clamped dofs
     ubc = Function(V)
     ubc.vector.set(0.0)
     fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), lambda x: np.isclose(x[0], 0.0, atol=1e-6))], V)
@@ -66,7 +75,7 @@ def build(args):
     from femo_amd.fea.utils_hip import get_context
     get_context().sync()
     filter_build_ms = (time.perf_counter() - t0) * 1e3
-    return sim, mesh, res, facets, t, filter_build_ms
+    return sim, mesh, res, facets, t, filter_build_ms, stress
 
 
 def scipy_cycle(mesh, facets, t, x0, radius):
@@ -110,6 +119,7 @@ def main():
     ap.add_argument("--cycles", type=int, default=3)
     ap.add_argument("--no-scipy", action="store_true")
     ap.add_argument("--pc", choices=("jacobi", "multilevel"), default="jacobi", help="preconditioner of the PCG solves")
+    ap.add_argument("--stress", action="store_true", help="add the p-norm von Mises stress output and its total derivative")
     args = ap.parse_args()
     from femo_amd import _lib
     from femo_amd.engine import Context, Vec
@@ -118,7 +128,7 @@ def main():
         raise SystemExit("bench_topopt needs a HIP device")
     ctx = Context(0)
     utils_hip.set_context(ctx)
-    sim, mesh, res, facets, t, filter_build_ms = build(args)
+    sim, mesh, res, facets, t, filter_build_ms, stress = build(args)
     x0 = np.array(sim["density_unfiltered"])
     times = []
     for k in range(args.cycles + 1):
@@ -127,6 +137,13 @@ def main():
         t0 = time.perf_counter()
         sim.run()
         g = np.asarray(sim.compute_totals("compliance", "density_unfiltered"))
+        if stress is not None:
+            it_compliance_adjoint = res.last_info["adjoint"]["iterations"]
+            if k == 0:                                              # scale of the aggregate, fixed from the first state
+                cells = Vec(ctx, mesh.n_cell)
+                stress.m = 1.0 / float(np.max(stress.device().von_mises(stress.u.vec, cells, stress.rho.vec, stress.q).get()))
+                sim.run()
+            gs = np.asarray(sim.compute_totals("stress", "density_unfiltered"))
         ctx.sync()
         if k > 0:
             times.append((time.perf_counter() - t0) * 1e3)
@@ -142,6 +159,10 @@ def main():
                filter_build_ms=filter_build_ms, compliance=float(sim["compliance"][0]), pc=args.pc, pc_levels=0,
                pc_build_ms=0.0,
                pcg_iteration_us=1e3 * info["state"]["solve_ms"] / max(info["state"]["iterations"], 1))
+    if stress is not None:
+        out.update(pcg_iterations_adjoint=it_compliance_adjoint, pcg_iterations_stress_adjoint=info["adjoint"]["iterations"],
+                   stress=float(sim["stress"][0]), stress_m=stress.m, stress_p=stress.p, stress_q=stress.q,
+                   stress_gradient_norm=float(np.linalg.norm(gs)))
     if args.pc == "multilevel":
         pci = dev.pc_info()
         out.update(pc_levels=pci["levels"], pc_build_ms=pci["build_ms"], pc_nodes=pci["nodes"], pc_lattice_bytes=pci["bytes"])
