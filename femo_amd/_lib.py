@@ -165,6 +165,7 @@ PROTOTYPES = {
     "femo_assemble_system": (C.c_int, [H, C.c_int, C.c_void_p, H, H, H, H, H, H, H]),
     "femo_bc_apply_rhs": (C.c_int, [H, H, H]),
     "femo_newton_rhs": (C.c_int, [H, H, H, H, H]),
+    "femo_newton_rhs_linear": (C.c_int, [H, H, H, H, H]),
     "femo_mat_spmv": (C.c_int, [H, C.c_int, H, H]),
     "femo_dRdf_apply": (C.c_int, [H, H, C.c_int, H, H, C.c_int]),
     "femo_assemble_dRdf_cell": (C.c_int, [H, C.c_int, C.c_void_p, H]),

@@ -20,7 +20,7 @@ from femo_amd.fea.fea_hip import FEA
 from femo_amd.fea.forms import BackendForm
 from femo_amd.fea.utils_hip import (DeviceArray, SparseMatrix, addMatVecProductBwd, addMatVecProductFwd,
                                     assembleMatrix, assembleSystem, assembleVector, computePartials,
-                                    createFunction, getFuncArray, setUpKSP_MUMPS, update,
+                                    createFunction, cycle_linearisation, getFuncArray, setUpKSP_MUMPS, update,
                                     KSP_OPTIONS)
 
 
@@ -109,8 +109,8 @@ class StateOperation(CustomImplicitOperation):
         # runs under the transfer.  Forms with a backend of their own (shell) and recorders read the inputs through other
         # entry points: they keep the synchronous upload.
         recording = any(self.args_dict[name]['record'] for name in inputs)
-        defer = (fea.async_results and not isinstance(res, BackendForm) and not recording
-                 and fea.custom_solve is None and getattr(fea, "deferred_uploads", True))
+        plain = not isinstance(res, BackendForm) and not recording and fea.custom_solve is None
+        defer = fea.async_results and plain and getattr(fea, "deferred_uploads", True)
         update(self.state['function'], outputs[self.state_name])
         with deferred_uploads(defer):
             push_functions(self.args_dict, inputs)
@@ -126,15 +126,25 @@ class StateOperation(CustomImplicitOperation):
             # (a backend that declared it honours asynchronous arrays) and never twice: a compute_derivatives without a
             # solve before it assembles as always.  Round 6: only once this operation HAS been asked for
             # its derivatives -- a forward-only evaluation (no compute_derivatives ever) neither assembles nor keeps them.
+            # With DeviceArrays at the boundary there is no upload to hide, but the Newton solve below runs on these matrices
+            # either way (one linearisation per cycle), so the same order is kept there.
             self._early_done = False
-            if defer and getattr(res, 'constant_partials', False) and getattr(fea, 'early_linearisation', _EARLY_DEFAULT) \
+            if (defer or (plain and stays_on_device(inputs))) and getattr(res, 'constant_partials', False) \
+                    and getattr(fea, 'early_linearisation', _EARLY_DEFAULT) \
                     and getattr(self, '_derivatives_requested', False) \
                     and self.state['dR_du'] is None and self.state['dR_df_list'] is None:
                 self._linearise()
                 if hasattr(self.A, 'mat') and KSP_OPTIONS.get('pc') in ('bpx', 'jacobi'):
                     self.A.mat.prescale()
                 self._early_done = True
-            fea.solve(res, self.state['function'], self.bcs)
+            if self._early_done and isinstance(self.dRdu, SparseMatrix) and isinstance(self.A, SparseMatrix):
+                # one linearisation per cycle: the Newton solve runs on the matrices just assembled -- one dR/du + A pass, one
+                # S A S and one set of preconditioner weights serve the forward and the adjoint solve (the offer ends with the
+                # block: the next solve_residual_equations assembles again)
+                with cycle_linearisation(res, self.bcs, self.dRdu, self.A):
+                    fea.solve(res, self.state['function'], self.bcs)
+            else:
+                fea.solve(res, self.state['function'], self.bcs)
         with lazy_results(fea.async_results):
             outputs[self.state_name] = getFuncArray(self.state['function'], device=stays_on_device(inputs))
         if fea.record:

@@ -679,6 +679,24 @@ int femo_newton_rhs(const femo_mat* K, const femo_vec* F, const femo_vec* u, con
   return 0;
 }
 
+int femo_newton_rhs_linear(const femo_mat* K, const femo_vec* f, const femo_vec* u, const femo_bc* bc, femo_vec* b) {
+  FEMO_REQUIRE(K && f && u && b, "null argument");
+  femo_mesh* m = K->mesh;
+  FEMO_REQUIRE(bc == nullptr || bc->mesh == m, "Dirichlet set belongs to another mesh");
+  FEMO_REQUIRE(u->n >= m->n_vert && f->n >= m->n_cell && b->n >= m->n_rows, "vector size mismatch in newton_rhs_linear");
+  FEMO_REQUIRE(b->d != u->d, "newton_rhs_linear cannot run in place");
+  FEMO_TRY(femo_vec_await(u));          // before the halo exchange packs it
+  if (m->n_nbr > 0) FEMO_TRY(femo_halo_exchange(m, const_cast<femo_vec*>(u)));
+  femo_vec_touch(b);
+  // the product reads u' = u with the prescribed values imposed, ghost entries included: K u' = K u + K[:,bc](g - u)
+  const double* x = u->d;
+  if (bc != nullptr) FEMO_TRY(femo_launch_impose_bc(m, u->d, bc->d_mask, bc->d_dense, &x));
+  FEMO_TRY(femo_vec_await(f));          // a deferred upload of f: everything above was enqueued in front of the wait
+  const double* load = nullptr;
+  FEMO_TRY(femo_poisson_load_vector(m, f, &load));
+  return femo_launch_newton_rhs_linear(K, x, u->d, load, bc ? bc->d_mask : nullptr, bc ? bc->d_dense : nullptr, b->d);
+}
+
 int femo_dRdf_apply(femo_mesh* m, const femo_vec* vals, int transpose, const femo_vec* x, femo_vec* y, int accumulate) {
   FEMO_REQUIRE(m && vals && x && y, "null argument");
   FEMO_REQUIRE(vals->n >= m->n_cell * (m->tdim + 1), "dRdf value buffer too small");

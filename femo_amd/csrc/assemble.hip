@@ -1699,10 +1699,8 @@ int femo_launch_system(femo_mesh* m, int pde, const double* params, const double
     const bool no_bc_residual = combo_c && bcmask == nullptr;          // evaluate_residuals: K u - L, no Dirichlet treatment
     if (nbr <= NBp && ((bcmask != nullptr && bc_rowmask != nullptr && (combo_a || combo_b || combo_c)) || no_bc_residual)) {
       hipStream_t st = m->ctx->stream;
-      if (!m->d_pipe_dummy) {
-        FEMO_HIP_CHECK(hipMalloc(&m->d_pipe_dummy, 64 * 2 * sizeof(double)));
-        FEMO_HIP_CHECK(hipMalloc(&m->d_ubc, (std::max<int64_t>(m->n_vert, 1) + 2) * sizeof(double)));
-      }
+      if (!m->d_pipe_dummy) FEMO_HIP_CHECK(hipMalloc(&m->d_pipe_dummy, 64 * 2 * sizeof(double)));
+      if (!m->d_ubc) FEMO_HIP_CHECK(hipMalloc(&m->d_ubc, (std::max<int64_t>(m->n_vert, 1) + 2) * sizeof(double)));
       if (rhs && !no_bc_residual) hipLaunchKernelGGL(k_impose_bc, dim3(cell_grid(m->n_vert)), dim3(FEMO_BLOCK), 0, st, m->n_vert, u, bcmask, bcval, m->d_ubc);
       const double* ubc = no_bc_residual ? u : m->d_ubc;
       // one wave per SIMD (4 per CU): the LDS request is raised so that a fifth workgroup cannot land on a CU (it would
@@ -1732,6 +1730,24 @@ int femo_launch_system(femo_mesh* m, int pde, const double* params, const double
   if (m->tdim == 3) FEMO_TRY((launch_system_t<3, FEMO_PDE_POISSON>(m, nb, lds, u, f, load, beta, sgn, bcmask, bcval, diag0, vals0, diag1, vals1, rhs)));
   else FEMO_TRY((launch_system_t<2, FEMO_PDE_POISSON>(m, nb, lds, u, f, load, beta, sgn, bcmask, bcval, diag0, vals0, diag1, vals1, rhs)));
   return finish_deferred();
+}
+
+// What the Newton right-hand side of a linear form needs besides the product with its operator (femo_newton_rhs_linear):
+// the load vector of f -- cached per content of f like every other user of it -- and u with the prescribed values imposed.
+int femo_poisson_load_vector(femo_mesh* m, const femo_vec* f, const double** load) {
+  FEMO_TRY(ensure_load_vector(m, f->d, f->uid, f->gen));
+  *load = m->d_load;
+  return 0;
+}
+
+int femo_launch_impose_bc(femo_mesh* m, const double* u, const uint8_t* bcmask, const double* bcval, const double** ubc) {
+  if (!m->d_ubc) FEMO_HIP_CHECK(hipMalloc(&m->d_ubc, (std::max<int64_t>(m->n_vert, 1) + 2) * sizeof(double)));
+  if (m->n_vert > 0) {
+    hipLaunchKernelGGL(k_impose_bc, dim3(cell_grid(m->n_vert)), dim3(FEMO_BLOCK), 0, m->ctx->stream, m->n_vert, u, bcmask, bcval, m->d_ubc);
+    FEMO_HIP_CHECK(hipGetLastError());
+  }
+  *ubc = m->d_ubc;
+  return 0;
 }
 
 int femo_launch_dRdf(femo_mesh* m, int pde, const double* params, const double* u,

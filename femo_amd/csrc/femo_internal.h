@@ -497,6 +497,12 @@ int femo_launch_functional_grad_f(femo_mesh* m, int kind, const double* params, 
                                   const double* f, const double* ud, double* g);
 int femo_launch_spmv(const femo_mat* A, const double* vals, const double* x, double* y,
                      double* partials /* or null: fused dot(x,y) partials */);
+// y = K x - load outside the Dirichlet set, u - bcval on it (bcmask null: no set), one launch (solver.hip); its two inputs
+// besides the operator: the cached load vector of f, and u with the prescribed values imposed (assemble.hip)
+int femo_launch_newton_rhs_linear(const femo_mat* K, const double* x, const double* u, const double* load,
+                                  const uint8_t* bcmask, const double* bcval, double* y);
+int femo_poisson_load_vector(femo_mesh* m, const femo_vec* f, const double** load);
+int femo_launch_impose_bc(femo_mesh* m, const double* u, const uint8_t* bcmask, const double* bcval, const double** ubc);
 int femo_spmv_grid(const femo_mesh* m);
 int femo_halo_exchange_on(femo_mesh* m, femo_vec* x, hipStream_t st);
 int femo_mesh_classify_slices(femo_mesh* m);

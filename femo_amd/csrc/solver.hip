@@ -336,6 +336,49 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_spmv_sell(
   }
 }
 
+// Newton right-hand side of a LINEAR form from its assembled operator (femo_newton_rhs_linear): the product K x of
+// k_spmv_sell<0, false> -- same slice walk, same three slice classes, same order of accumulation -- with the rest of the
+// right-hand side in its epilogue:  y_i = (K x)_i - load_i  outside the Dirichlet set,  y_i = u_i - g_i  on it
+// (bcmask == null: no set, y = K x - load).  x is u with the prescribed values imposed, so that K x carries the lifting.
+// A kernel of its own, not a further flag of k_spmv_sell: the CG loop's instantiations keep their registers.
+template <bool NT>
+__global__ __launch_bounds__(FEMO_BLOCK) void k_spmv_sell_rhs(
+    int64_t n_rows, int64_t n_slices, const int64_t* __restrict__ mptr,
+    const int32_t* __restrict__ cols, const int16_t* __restrict__ cols16, const int32_t* __restrict__ sdelta, int sdelta_stride,
+    const double* __restrict__ vals, const double* __restrict__ diag, const double* __restrict__ x,
+    const double* __restrict__ u, const double* __restrict__ load, const uint8_t* __restrict__ bcmask,
+    const double* __restrict__ bcval, double* __restrict__ y) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int xcd = blockIdx.x & 7;                    // (XCD-aware walk: see k_spmv_sell)
+  const int64_t blk_in_xcd = blockIdx.x >> 3;
+  const int64_t waves_per_xcd = (int64_t)(gridDim.x >> 3) * (FEMO_BLOCK / 64);
+  const int64_t s_lo = n_slices * xcd / 8, s_hi = n_slices * (xcd + 1) / 8;
+  for (int64_t slice = s_lo + blk_in_xcd * (FEMO_BLOCK / 64) + wave; slice < s_hi; slice += waves_per_xcd) {
+    const int64_t base = mptr[slice];
+    const int npair = (int)((mptr[slice + 1] - base) >> 7);
+    const int64_t row = (slice << 6) + lane;
+    const int64_t rc = row < n_rows ? row : 0;       // lanes beyond n_rows compute on row 0 and store nothing
+    const double xr = x[rc];
+    double acc = diag[row] * xr;
+    const double2* __restrict__ v2 = reinterpret_cast<const double2*>(vals + base) + lane;
+    const int32_t* __restrict__ dl = sdelta + slice * sdelta_stride;
+    if (dl[0] != INT32_MIN) {  // wave-uniform (scalar load)
+      acc = row_sum_regular<NT>(npair, v2, dl, x + row, acc);
+    } else if (dl[1] == 1) {   // 16-bit column deltas
+      const int* __restrict__ c16 = reinterpret_cast<const int*>(cols16) + (base >> 1) + lane;
+      acc = row_sum_short<NT>(npair, v2, c16, x + row, acc);
+    } else {
+      const int2* __restrict__ c2 = reinterpret_cast<const int2*>(cols + base) + lane;
+      acc = row_sum<NT>(npair, v2, c2, x, acc);
+    }
+    if (row < n_rows) {
+      const bool on_set = bcmask != nullptr && bcmask[row];
+      y[row] = on_set ? u[row] - bcval[row] : acc - load[row];
+    }
+  }
+}
+
 // y += A^T x by scatter (partitioned, structurally non-symmetric-valued operators): the transposed entry of a
 // ghost column lives in a row of another rank, so the explicit transposed values cannot be formed locally.
 // Row i adds a_ij x_i to y_j for all its entries, ghost columns included; the ghost tail of y then travels back
@@ -1007,6 +1050,20 @@ static int halo_spmv_inflight(const femo_mat* A, const double* vals, double* x, 
 
 int femo_launch_spmv(const femo_mat* A, const double* vals, const double* x, double* y, double* partials) {
   return launch_spmv(A, vals, x, y, partials, nullptr);
+}
+
+int femo_launch_newton_rhs_linear(const femo_mat* K, const double* x, const double* u, const double* load,
+                                  const uint8_t* bcmask, const double* bcval, double* y) {
+  const femo_mesh* m = K->mesh;
+  if (m->n_slices == 0) return 0;
+  const int64_t g = femo_spmv_grid(m);
+  const bool nt = (int64_t)m->sell_entries * (int64_t)sizeof(double) > FEMO_LLC_MATRIX_BYTES;
+#define FEMO_RHS_ARGS m->n_rows, m->n_slices, m->d_mptr, m->d_cols, m->d_cols16, m->d_sdelta, m->sdelta_stride, K->d_vals, K->d_diag, x, u, load, bcmask, bcval, y
+  if (nt) hipLaunchKernelGGL((k_spmv_sell_rhs<true>), dim3(g), dim3(FEMO_BLOCK), 0, m->ctx->stream, FEMO_RHS_ARGS);
+  else hipLaunchKernelGGL((k_spmv_sell_rhs<false>), dim3(g), dim3(FEMO_BLOCK), 0, m->ctx->stream, FEMO_RHS_ARGS);
+#undef FEMO_RHS_ARGS
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 int femo_mat_ensure_transpose(femo_mat* A) {

@@ -775,6 +775,13 @@ def newton_rhs(K: Mat, F: Vec, u: Vec, bc: DirichletSet, b: Vec) -> Vec:
     return b
 
 
+def newton_rhs_linear(K: Mat, f: Vec, u: Vec, bc: Optional[DirichletSet], b: Vec) -> Vec:
+    """Newton right-hand side of a linear form from its assembled operator K (no BCs): b = K u' - L outside the set,
+    u - g on it; ``bc=None``: the residual K u - L (include/femo_hip.h)."""
+    check(K.lib.femo_newton_rhs_linear(K.handle, f.handle, u.handle, _h(bc), b.handle))
+    return b
+
+
 def dRdf_apply(mesh: DeviceMesh, vals: Vec, x: Vec, y: Vec, transpose: bool, accumulate: bool = False) -> Vec:
     check(mesh.lib.femo_dRdf_apply(mesh.handle, vals.handle, int(transpose), x.handle, y.handle, int(accumulate)))
     return y

@@ -588,6 +588,31 @@ def setUpKSP_MUMPS(A, options: Optional[dict] = None) -> KSP:
 
 
 # ---------------------------------------------------------- nonlinear solves ----
+class cycle_linearisation:
+    """``with cycle_linearisation(res, bcs, dRdu, A):`` a Newton solve of ``res`` with ``bcs`` inside the block runs on these
+    matrices -- dR/du without and A with the Dirichlet set eliminated, assembled by the caller in THIS cycle -- instead of
+    assembling its own (forms with constant partials only, `_NewtonBase.linear_reuse`).  Per thread, and gone with the block:
+    a linearisation is never carried into a later solve."""
+
+    def __init__(self, res: Form, bcs, K: "SparseMatrix", A: "SparseMatrix"):
+        self.entry = (res, list(bcs), K, A)
+
+    def __enter__(self):
+        _TLS.linearisation = self.entry
+        return self
+
+    def __exit__(self, *exc):
+        _TLS.linearisation = None
+        return False
+
+
+def _offered_linearisation(F: Form, bcs):
+    entry = getattr(_TLS, "linearisation", None)
+    if entry is None or entry[0] is not F or len(entry[1]) != len(bcs) or any(a is not b for a, b in zip(entry[1], bcs)):
+        return None
+    return entry[2], entry[3]
+
+
 class _NewtonBase:
     def __init__(self, F: Form, w: Function, bcs, abs_tol, rel_tol, max_it, report, error_on_nonconvergence):
         if not isinstance(F, _RESIDUALS):
@@ -608,6 +633,12 @@ class _NewtonBase:
     # Newton reads rho_0 of the next solve with its own reduction and skips a solve the solver would not iterate on (round 6;
     # False leaves the decision to the solver: tests compare the two)
     newton_probe = True
+    # A form whose partials are constant (`constant_partials`: linear Poisson) has ONE operator per solve: dR/du and A are
+    # assembled once, in one pass over the mesh -- or taken from the caller's linearisation of this cycle
+    # (`cycle_linearisation`) -- and every right-hand side is a product with dR/du (engine.newton_rhs_linear) instead of another
+    # pass.  Same iterations, same reductions, same rules.  False: a pass per residual, as for every other form (tests
+    # compare the two)
+    linear_reuse = True
 
     def solve(self, func: Function):
         """dolfinx.nls.petsc.NewtonSolver.solve [ext]: F; while not converged and
@@ -619,12 +650,34 @@ class _NewtonBase:
         n = mesh.n_vert
         b = _work(mesh, "newton_b", lambda: Vec(ctx, n))
         dx = _work(mesh, "newton_dx", lambda: Vec(ctx, n))
-        A = _work(mesh, "newton_A", lambda: SparseMatrix(mesh, symmetric=F.is_symmetric))
-        A.pde_kind = F.pde_kind
         ds = _dirichlet_set(mesh, self.bcs)
         aux = _aux(F)
+        reuse = self.linear_reuse and getattr(F, "constant_partials", False) and F.pde_kind == _lib.PDE_POISSON
+        offered = _offered_linearisation(F, self.bcs) if reuse else None
+        if offered is not None:
+            K, A = offered
+        else:
+            A = _work(mesh, "newton_A", lambda: SparseMatrix(mesh, symmetric=F.is_symmetric))
+            A.pde_kind = F.pde_kind
+        if reuse:
+            if offered is None:
+                K = _work(mesh, "newton_K", lambda: SparseMatrix(mesh, symmetric=F.is_symmetric))
+                K.pde_kind = F.pde_kind
+                # the operator of this solve: needs neither f nor u, so it runs under an upload of f that is still in flight,
+                # and so does S A S (one rank: as in the library's deferred pass, whether to scale early is not a decision
+                # ranks may take differently)
+                E.assemble_system(dm, F.pde_kind, F.params, F.u.vec, F.f.vec, ds, K.mat, A.mat, None, aux=aux)
+                if ctx.nranks == 1 and A.symmetric and KSP_OPTIONS.get("pc") in ("bpx", "jacobi"):
+                    A.mat.prescale()
+
+            def residual_pass(with_matrix):
+                E.newton_rhs_linear(K.mat, F.f.vec, F.u.vec, ds, b)
+        else:
+            def residual_pass(with_matrix):
+                E.assemble_system(dm, F.pde_kind, F.params, F.u.vec, F.f.vec, ds, None, A.mat if with_matrix else None, b,
+                                  aux=aux)
         # F (with Dirichlet lifting) and J at the current iterate, one pass over the mesh
-        E.assemble_system(dm, F.pde_kind, F.params, F.u.vec, F.f.vec, ds, None, A.mat, b, aux=aux)
+        residual_pass(True)
         n_own = dm.n_rows          # dots run over owned rows (all-reduced across ranks in the library)
         r0 = r = float(np.sqrt(b.dot(b, n_own)))
         self.residual_norms = [r]
@@ -697,8 +750,7 @@ class _NewtonBase:
             # next pass: residual for the convergence test and, in the same launch, the Jacobian the
             # next iteration will use.  After the last allowed iteration nothing consumes a Jacobian
             # (the reference assembles J only when it iterates again), so that pass is residual-only.
-            E.assemble_system(dm, F.pde_kind, F.params, F.u.vec, F.f.vec, ds, None,
-                              A.mat if it < self.max_it else None, b, aux=aux)
+            residual_pass(it < self.max_it)
             pairs = [(b, b)]
             more = it < self.max_it
             want_energy = more and bpx_energy and (energy_scale is None or self.ksp_iterations[-1] > 0)

@@ -297,6 +297,11 @@ int femo_bc_apply_rhs(const femo_bc* bc, const femo_vec* u, femo_vec* b);
  * [ext] as driven by utils_dolfinx.py:431:  b = F + K[:,bc](g-u); b[bc] = u-g. */
 int femo_newton_rhs(const femo_mat* K_nobc, const femo_vec* F, const femo_vec* u,
                     const femo_bc* bc, femo_vec* b);
+/* The same right-hand side for a LINEAR form (linear Poisson), from its assembled operator instead of a pass over
+ * the mesh:  b = K u' - L  outside the set (u' = u with g on the set, L = the load vector of f),  b[bc] = u - g;
+ * bc == NULL: the plain residual K u - L.  One product with K (no BCs), the rest in its epilogue.                  */
+int femo_newton_rhs_linear(const femo_mat* K_nobc, const femo_vec* f, const femo_vec* u,
+                           const femo_bc* bc, femo_vec* b);
 
 /* ---- operator application (state_model.py:161-200) -------------------------
  * mat_spmv:   utils_dolfinx.py:256-264 (A*x) / :275-287 (A^T*R).
