@@ -33,6 +33,7 @@ ELAST_SIMP = 0
 ELAST_RAMP = 1
 ELAST_INFO_KEYS = ("dim", "n_dof", "nnz", "sell_entries", "spmv_bytes")
 ELAST_PC = {"jacobi": 0, "multilevel": 1}
+ELAST_MAX_COLS = 8                # FEMO_ELAST_MAX_COLS: load cases of one batched product / solve
 ELAST_PC_INFO_COUNT = 16           # [levels, lattice bytes, block builds, last build us, nodes per level ...]
 
 
@@ -206,6 +207,9 @@ PROTOTYPES = {
     "femo_elast_pnorm_stress": (C.c_int, [H, H, H, C.c_double, C.c_double, C.c_double, C.c_double, c_f64p, H, H, C.c_int]),
     "femo_elast_von_mises": (C.c_int, [H, H, H, C.c_double, H]),
     "femo_elast_solve": (C.c_int, [H, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
+    "femo_elast_apply_multi": (C.c_int, [H, C.c_int, C.c_int, C.c_double, H, C.c_double, H, H]),
+    "femo_elast_solve_multi": (C.c_int, [H, C.c_int, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
+    "femo_elast_drho_multi": (C.c_int, [H, C.c_int, C.c_int, C.c_int, H, H, H, H, C.c_int]),
     "femo_elast_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "femo_elast_pc_setup": (C.c_int, [H, C.c_double]),
     "femo_elast_pc_info": (C.c_int, [H, c_i64p]),

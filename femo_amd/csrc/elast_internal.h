@@ -30,6 +30,14 @@ struct femo_elast {
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
   femo_elast_pc* pc = nullptr;
   bool pc_dirty = true;
+  // batched PCG (femo_elast_solve_multi): m_cols columns of r, z, p, q, one column after the other; per column
+  // EMS_STRIDE scalars, EMF_STRIDE flags and m_pstride partials.  Allocated on the first batched solve, grown on demand.
+  int m_cols = 0;
+  int64_t m_pstride = 0;
+  double *m_r = nullptr, *m_z = nullptr, *m_p = nullptr, *m_q = nullptr, *m_part = nullptr, *m_s = nullptr;
+  int32_t* m_flag = nullptr;
+  int32_t* hm_flag = nullptr;   // pinned, FEMO_ELAST_MAX_COLS columns
+  double* hm_s = nullptr;       // pinned
   int method = 0;                    // of the last femo_elast_assemble ...
   uint64_t rho_uid = 0, rho_gen = 0; // ... and its density vector: looked up in the live table at the lazy build (never a
                                      // pointer: the caller may have destroyed it); uid 0 = wrapped memory, built at once
@@ -40,6 +48,8 @@ constexpr int PCG_GRID = 512;        // blocks of the PCG reductions (one partia
 
 // PCG device scalars s[]: 0 rz, 1 alpha, 2 beta, 3 tol^2, 4 rz0.  flag[]: 0 done, 1 iterations, 2 breakdown, 3 converged.
 enum { S_RZ = 0, S_ALPHA = 1, S_BETA = 2, S_TOL2 = 3, S_RZ0 = 4 };
+// Batched PCG: column l keeps its own s[] at s + l * EMS_STRIDE and its own flag[] at flag + l * EMF_STRIDE.
+constexpr int EMS_STRIDE = 8, EMF_STRIDE = 4;
 
 // elast_pc.hip ------------------------------------------------------------------------------------------------------
 void femo_elast_pc_free(femo_elast* e);
@@ -51,6 +61,19 @@ int femo_elast_pc_build(femo_elast* e, const double* rho);
 // update: x += alpha p, r -= alpha q first (alpha = s[S_ALPHA]; nothing once flag[0] is set).  pinit != null: p = z as well.
 int femo_elast_pc_step(femo_elast* e, bool update, double* x, double* r, const double* p, const double* q, double* z,
                        double* pinit, const double* s, double* part, const int32_t* flag);
+// The same step for n_cols columns in the same four launches (a column dimension in every grid; k_pc_coarse: one
+// workgroup per column).  Vectors: column l at + l * n_dof; s, flag: EMS_STRIDE / EMF_STRIDE apart; part: part_stride
+// apart.  Every column goes through the arithmetic of femo_elast_pc_step in the same order; a column whose flag[0] is
+// set is skipped (update only).  The L copies of the lattice work vectors are allocated here on first use.
+int femo_elast_pc_step_multi(femo_elast* e, bool update, int n_cols, double* x, double* r, const double* p, const double* q,
+                             double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag);
+
+// elasticity.hip ----------------------------------------------------------------------------------------------------
+// The launches of femo_elast_drho on raw pointers (femo_elast_drho_multi loops them over the columns).
+int femo_elast_drho_launch(femo_elast* e, int method, int transpose, const double* rho, const double* u, const double* x,
+                           double* y, int accumulate);
+// elast_multi.hip ---------------------------------------------------------------------------------------------------
+void femo_elast_multi_free(femo_elast* e);
 
 #if defined(__HIPCC__)
 // gradients of the barycentric coordinates and the volume of a P1 simplex, from the vertices in `conn` order

@@ -690,6 +690,25 @@ int dalloc(T** p, int64_t n) {
 
 }  // namespace
 
+int femo_elast_drho_launch(femo_elast* e, int method, int transpose, const double* rho, const double* u, const double* x,
+                           double* y, int accumulate) {
+  femo_mesh* m = e->mesh;
+  hipStream_t st = m->ctx->stream;
+  if (transpose) {
+    if (e->d == 2)
+      hipLaunchKernelGGL(k_elast_drho_T<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
+    else
+      hipLaunchKernelGGL(k_elast_drho_T<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
+  } else {
+    if (e->d == 2)
+      hipLaunchKernelGGL(k_elast_drho_N<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
+    else
+      hipLaunchKernelGGL(k_elast_drho_N<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
+  }
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // ===================================================================================================== C-ABI ====
 extern "C" {
 
@@ -723,6 +742,7 @@ int femo_elast_create(femo_mesh* m, double E, double nu, femo_elast** out) {
 int femo_elast_destroy(femo_elast* e) {
   if (!e) return 0;                    // hipFree waits for the device; the mesh may already be gone
   femo_elast_pc_free(e);
+  femo_elast_multi_free(e);
   hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
   hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_spart);
@@ -868,19 +888,27 @@ int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rh
   FEMO_REQUIRE(y != x && y != u && y != rho, "femo_elast_drho: output aliases an input");
   FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(x));
   femo_vec_touch(y);
-  hipStream_t st = m->ctx->stream;
-  if (transpose) {
-    if (e->d == 2)
-      hipLaunchKernelGGL(k_elast_drho_T<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, u->d, x->d, y->d, accumulate);
-    else
-      hipLaunchKernelGGL(k_elast_drho_T<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, u->d, x->d, y->d, accumulate);
-  } else {
-    if (e->d == 2)
-      hipLaunchKernelGGL(k_elast_drho_N<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, u->d, x->d, y->d, accumulate);
-    else
-      hipLaunchKernelGGL(k_elast_drho_N<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, u->d, x->d, y->d, accumulate);
+  return femo_elast_drho_launch(e, method, transpose, rho->d, u->d, x->d, y->d, accumulate);
+}
+
+int femo_elast_drho_multi(femo_elast* e, int method, int transpose, int n_cols, const femo_vec* rho, const femo_vec* u,
+                          const femo_vec* x, femo_vec* y, int accumulate) {
+  FEMO_REQUIRE(e && rho && u && x && y, "null argument");
+  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
+  FEMO_REQUIRE(n_cols >= 1 && n_cols <= FEMO_ELAST_MAX_COLS, "femo_elast_drho_multi: %d columns (1 to %d)", n_cols,
+               FEMO_ELAST_MAX_COLS);
+  femo_mesh* m = e->mesh;
+  const int64_t n = m->n_vert * e->d, nl = n * n_cols;
+  FEMO_REQUIRE(rho->n >= m->n_cell && u->n >= nl, "vector size mismatch in femo_elast_drho_multi");
+  FEMO_REQUIRE(transpose ? (x->n >= nl && y->n >= m->n_cell) : (x->n >= m->n_cell && y->n >= nl),
+               "vector size mismatch in femo_elast_drho_multi");
+  FEMO_REQUIRE(y != x && y != u && y != rho, "femo_elast_drho_multi: output aliases an input");
+  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(x));
+  femo_vec_touch(y);
+  for (int l = 0; l < n_cols; ++l) {
+    if (transpose) FEMO_TRY(femo_elast_drho_launch(e, method, 1, rho->d, u->d + l * n, x->d + l * n, y->d, accumulate || l > 0));
+    else FEMO_TRY(femo_elast_drho_launch(e, method, 0, rho->d, u->d + l * n, x->d, y->d + l * n, accumulate));
   }
-  FEMO_HIP_CHECK(hipGetLastError());
   return 0;
 }
 

@@ -15,6 +15,10 @@ are used unchanged.
                        2-D: sigma_zz = lambda_0 tr eps); rho^q sigma_vm is the qp-relaxed cell stress.  Not in the reference's
                        script: the solid counterpart of the shell's pnorm_stress (shell_pde.py:297-313)
   ElasticityVonMises   the cell field rho_e^q sigma_vm,e for `project` / FEA.add_field_output
+  MultiLoadElasticityResidual, MultiLoadCompliance
+                       L load cases on one K(rho): the state is a Function(LoadCaseSpace(V, L)), column l solves
+                       K(rho) u_l = F_l, and J = sum_l w_l F_l . u_l.  Every solve of the cycle -- state, adjoint, forward
+                       mode -- is one batched PCG over all columns (csrc/elast_multi.hip)
 
 P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
 """
@@ -29,7 +33,7 @@ from .. import _lib
 from .._lib import check
 from ..engine import Vec, _ptr
 from .forms import BackendForm, LinearFunctional
-from .function import Function, FunctionSpace, VectorFunctionSpace
+from .function import Function, FunctionSpace, LoadCaseSpace, VectorFunctionSpace
 from .io import MeshTags
 
 METHODS = {"SIMP": _lib.ELAST_SIMP, "RAMP": _lib.ELAST_RAMP}
@@ -151,6 +155,43 @@ class DeviceElasticity:
         info = _lib.SolveInfo()
         check(self.lib.femo_elast_solve(self.handle, b.handle, x.handle, C.byref(opts), C.byref(info)))
         return info
+
+    # ---- several load cases in one vector: column l at l * n_dof (csrc/elast_multi.hip) ----
+    def _cols(self, n_cols: int, *vecs: Vec) -> int:
+        n_cols = int(n_cols)
+        for v in vecs:
+            if v is not None and v.n < n_cols * self.n_dof:
+                raise _lib.FemoError(f"{n_cols} load cases need vectors of {n_cols * self.n_dof} entries, got {v.n}")
+        return n_cols
+
+    def apply_multi(self, n_cols: int, x: Vec, y: Vec, masked: bool = False, a: float = 1.0, b: float = 0.0,
+                    f: Optional[Vec] = None) -> Vec:
+        """y_l = a K x_l + b f_l (or with the masked A) for all ``n_cols`` columns in one launch."""
+        check(self.lib.femo_elast_apply_multi(self.handle, int(bool(masked)), self._cols(n_cols, x, y, f), float(a), x.handle,
+                                              float(b), None if f is None else f.handle, y.handle))
+        return y
+
+    def solve_multi(self, n_cols: int, b: Vec, x: Vec, rtol: float = 1e-15, atol: float = 0.0, max_it: int = 1_000_000,
+                    check_every: Optional[int] = None, zero_guess: bool = True, pc: str = "jacobi") -> list:
+        """`solve` for ``n_cols`` right-hand sides in one batched PCG; one `SolveInfo` per column (``solve_ms`` is that of the
+        whole batched solve in each).  A column that has converged is frozen while the others go on."""
+        if pc not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
+        if check_every is None:
+            check_every = 64 if pc == "jacobi" else 0
+        opts = _lib.SolverOpts(rtol=float(rtol), atol=float(atol), max_it=int(max_it), zero_guess=int(bool(zero_guess)),
+                               check_every=int(check_every), pc=PRECONDITIONERS[pc], atol_pc=0.0)
+        info = (_lib.SolveInfo * _lib.ELAST_MAX_COLS)()
+        check(self.lib.femo_elast_solve_multi(self.handle, self._cols(n_cols, b, x), b.handle, x.handle, C.byref(opts), info))
+        return [info[l] for l in range(int(n_cols))]
+
+    def drho_multi(self, method: int, transpose: bool, n_cols: int, rho: Vec, u: Vec, x: Vec, y: Vec,
+                   accumulate: bool = False) -> Vec:
+        """transpose: y[n_cell] (+)= sum_l C'(rho) x_l^T K0 u_l; otherwise column l of y (+)= the forward product with u_l."""
+        n_cols = self._cols(n_cols, u, x if transpose else y)
+        check(self.lib.femo_elast_drho_multi(self.handle, int(method), int(bool(transpose)), n_cols, rho.handle, u.handle,
+                                             x.handle, y.handle, int(bool(accumulate))))
+        return y
 
     def export_csr(self):
         """K as a SciPy CSR matrix of size n_dof (host copy; tests and debugging)."""
@@ -541,6 +582,264 @@ class Compliance(BackendForm):
         return out.fill(0.0)
 
 
+# ------------------------------------------------------------------------------------------- several load cases ----
+def _multi_load_vec(mesh, facets_list, tractions, weights=None) -> Vec:
+    """Column l = w_l F_l (w = 1 without weights): the single loads of `_load_vec`, placed through the host once and cached."""
+    cache = mesh.__dict__.setdefault("_elast_multi_loads", {})
+    w = np.ones(len(tractions)) if weights is None else np.asarray(weights, dtype=np.float64)
+    key = (id(_ctx()), tuple(hash(np.ascontiguousarray(f, dtype=np.int32).tobytes()) for f in facets_list),
+           tuple(tuple(t) for t in tractions), tuple(w))
+    F = cache.get(key)
+    if F is None:
+        cols = [w[l] * np.array(_load_vec(mesh, facets_list[l], tractions[l]).get(), dtype=np.float64)
+                for l in range(len(tractions))]
+        F = cache[key] = Vec(_ctx(), len(cols) * cols[0].size).set(np.concatenate(cols))
+    return F
+
+
+def _multi_arguments(name: str, u: Function, tractions, measures):
+    V = u.function_space
+    if not isinstance(V, LoadCaseSpace):
+        raise NotImplementedError(f"{name} needs a Function(LoadCaseSpace(V, n_cases)) state")
+    if getattr(V.mesh, "local", None) is not None and V.mesh.local.nranks > 1:
+        raise NotImplementedError(f"{name}: partitioned meshes are out of scope")
+    tractions = list(tractions)
+    measures = [None] * len(tractions) if measures is None else list(measures)
+    if len(tractions) != V.n_cases or len(measures) != V.n_cases:
+        raise ValueError(f"{name}: {V.n_cases} load cases need as many tractions and measures")
+    ts = [_traction(t, V.mesh) for t in tractions]
+    dss = [ds if ds is not None else Measure("ds", domain=V.mesh) for ds in measures]
+    return V, ts, dss
+
+
+class MultiLoadElasticityMatrix:
+    """dR/du of the multi-load residual: K(rho) (masked: A) on every column.  One `mult` is one batched product, one
+    `backend_solve` one batched PCG over all columns."""
+    symmetric = True
+    pde_kind = None
+
+    def __init__(self, form: "MultiLoadElasticityResidual", masked: bool = False):
+        self.form, self.masked, self.mesh = form, masked, form.mesh
+        self._row = None
+        self.info = None
+
+    def getSizes(self):
+        n = self.form.n_cases * self.form.n_dof
+        return (n, n)
+
+    size = property(getSizes)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        dev = self.form.stiffness()
+        return dev.apply_multi(self.form.n_cases, x, y, masked=self.masked and dev.fixed_key is not None)
+
+    multTranspose = mult
+
+    def new_row_vec(self) -> Vec:
+        if self._row is None:
+            self._row = Vec(_ctx(), self.getSizes()[0])
+        return self._row
+
+    new_col_vec = new_row_vec
+
+    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        o = options or {}
+        F = self.form
+        self.info = F.stiffness().solve_multi(F.n_cases, b, x, rtol=o.get("elast_rtol", F.rtol),
+                                              max_it=o.get("elast_max_it", 1_000_000), pc=F.preconditioner)
+        F._record(self.info, "adjoint")
+
+    def to_scipy(self):
+        import scipy.sparse as sp
+        K = self.form.stiffness().export_csr()
+        if self.masked and self.form._mask is not None:
+            free = sp.diags((self.form._mask == 0).astype(np.float64))
+            K = free @ K @ free + sp.diags(self.form._mask.astype(np.float64))
+        return sp.block_diag([K] * self.form.n_cases, format="csr")
+
+
+class _MultiLoadDrho:
+    """dR/drho ((n_cases n_dof) x n_cell), matrix free: block l of column e = C'(rho_e) K0_e u_{l,e}."""
+
+    def __init__(self, form: "MultiLoadElasticityResidual"):
+        self.form, self.mesh = form, form.mesh
+        self._row = self._col = None
+
+    def getSizes(self):
+        return (self.form.n_cases * self.form.n_dof, self.mesh.n_cell)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        return F.device().drho_multi(F.method_id, False, F.n_cases, F.rho.vec, F.u.vec, x, y)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        return F.device().drho_multi(F.method_id, True, F.n_cases, F.rho.vec, F.u.vec, x, y)
+
+    def new_row_vec(self) -> Vec:
+        if self._row is None:
+            self._row = Vec(_ctx(), self.getSizes()[0])
+        return self._row
+
+    def new_col_vec(self) -> Vec:
+        if self._col is None:
+            self._col = Vec(_ctx(), self.mesh.n_cell)
+        return self._col
+
+
+class MultiLoadElasticityResidual(ElasticityResidual):
+    """Column l of the residual is K(rho) u_l - F_l, with F_l the traction ``tractions[l]`` on ``measures[l]``: L load cases
+    on one stiffness matrix, one fixed set and one preconditioner.  ``u`` is a Function(LoadCaseSpace(V, L)).  The state
+    solve, the adjoint solve (`apply_inverse_jacobian`) and the forward-mode solve are each ONE batched PCG over all columns
+    (`DeviceElasticity.solve_multi`): a converged column is frozen while the others iterate.
+
+    Boundary conditions are given in the numbering of the base space V, exactly as for `ElasticityResidual`
+    (``fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), ...)], V)``), and hold for every column: the same fixed set,
+    the same values, and the lifting b_l = F_l - K g.
+
+    Out of scope: supports that differ between the load cases; `ElasticityPnormStress` / `ElasticityVonMises` on a
+    multi-column state; partitioned meshes; ``fea.consistent_bc_partials`` (StateOperation filters the multiplier in the
+    numbering of the bc list, which reaches the first column only).  ``last_info[kind]`` keeps, per kind of solve ("state", "adjoint"), the record
+    of the last batched solve with one entry per column under ``columns``; ``solve_counts[kind]`` counts the batched
+    solves."""
+
+    def __init__(self, u: Function, rho: Function, tractions, measures=None, E: float = 1.0, nu: float = 0.3,
+                 method: str = "SIMP", preconditioner: str = "jacobi"):
+        V, self.tractions, self.measures = _multi_arguments("MultiLoadElasticityResidual", u, tractions, measures)
+        if rho.function_space.family != "DG" or rho.function_space.mesh is not V.mesh:
+            raise NotImplementedError("MultiLoadElasticityResidual needs a DG0 density on the state's mesh")
+        if method not in METHODS:
+            raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
+        if preconditioner not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {preconditioner!r} (jacobi or multilevel)")
+        self.preconditioner = preconditioner
+        self.u, self.rho, self.mesh = u, rho, V.mesh
+        self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
+        self.n_cases, self.n_dof = V.n_cases, V.base.dim           # n_dof: of one column (the numbering of the bcs)
+        self.rtol = 1e-15
+        self._key = None
+        self._mask = None
+        self._vals = None
+        self._res = None
+        self._rhs_cache = None
+        self.last_info = {}
+        self.solve_counts = {"state": 0, "adjoint": 0}
+
+    def load(self) -> Vec:
+        return _multi_load_vec(self.mesh, [ds.facets() for ds in self.measures], self.tractions)
+
+    def _record(self, infos, kind: str) -> None:
+        from .utils_hip import LAST_KSP_INFO
+        cols = [dict(iterations=i.iterations, converged=i.converged, residual_norm=i.residual_norm, rhs_norm=i.rhs_norm)
+                for i in infos]
+        self.solve_counts[kind] = self.solve_counts.get(kind, 0) + 1
+        self.last_info[kind] = dict(columns=cols, n_cases=self.n_cases, iterations=[c["iterations"] for c in cols],
+                                    converged=[c["converged"] for c in cols], solve_ms=infos[0].solve_ms,
+                                    preconditioner=self.preconditioner)
+        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_multiload_" + kind))
+        for l, c in enumerate(cols):
+            if c["converged"] != 1:
+                raise RuntimeError(f"elasticity PCG did not converge ({kind}, load case {l} of {self.n_cases}): "
+                                   f"{c['iterations']} iterations, sqrt(r.M^-1 r) = {c['residual_norm']:.3e} of "
+                                   f"{c['rhs_norm']:.3e}")
+
+    def new_matrix(self) -> MultiLoadElasticityMatrix:
+        return MultiLoadElasticityMatrix(self)
+
+    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
+        """Column l: K u_l - F_l; one launch for all columns (femo_elast_apply_multi)."""
+        if out is None:
+            if self._res is None:
+                self._res = Vec(_ctx(), self.n_cases * self.n_dof)
+            out = self._res
+        return self.stiffness().apply_multi(self.n_cases, self.u.vec, out, a=1.0, b=-1.0, f=self.load())
+
+    def partial_matrix(self, wrt: Function, out=None):
+        if wrt is self.u:
+            return out if isinstance(out, MultiLoadElasticityMatrix) and not out.masked else MultiLoadElasticityMatrix(self)
+        if wrt is self.rho:
+            return out if isinstance(out, _MultiLoadDrho) else _MultiLoadDrho(self)
+        raise ValueError("the elasticity residual does not depend on that Function")
+
+    def assemble_system(self, bcs, rhs: bool, out, out_nobc):
+        if rhs:
+            raise NotImplementedError("assembleSystem(rhs=True) for the elasticity form: use solveNonlinear / FEA.solve")
+        self._set_bcs(bcs)
+        self.stiffness()
+        A = out if isinstance(out, MultiLoadElasticityMatrix) else MultiLoadElasticityMatrix(self)
+        A.form, A.masked = self, True
+        if isinstance(out_nobc, MultiLoadElasticityMatrix):
+            out_nobc.form, out_nobc.masked = self, False
+        return A, None
+
+    def _rhs(self, dev: DeviceElasticity) -> Vec:
+        """Column l: F_l with the Dirichlet lifting, b_l = F_l - K g, b_l = g on the fixed dofs."""
+        F = self.load()
+        if self._mask is None:
+            return F
+        fixed = self._mask == 1
+        nonzero = bool(np.any(self._vals[fixed] != 0.0))
+        key = (id(F), hash(self._mask.tobytes()))
+        if not nonzero and self._rhs_cache is not None and self._rhs_cache[0] == key:
+            return self._rhs_cache[1]
+        ctx = _ctx()
+        bh = np.array(F.get(), dtype=np.float64).reshape(self.n_cases, self.n_dof)
+        if nonzero:
+            g = Vec(ctx, self.n_dof).set(np.where(fixed, self._vals, 0.0))
+            Kg = Vec(ctx, self.n_dof)
+            dev.apply(g, Kg)
+            bh -= np.array(Kg.get())[None, :]
+        bh[:, fixed] = self._vals[fixed]
+        bv = Vec(ctx, self.n_cases * self.n_dof).set(bh.ravel())
+        if not nonzero:
+            self._rhs_cache = (key, bv)
+        return bv
+
+    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
+        """K(rho) u_l = F_l for every load case with the strongly imposed dofs: ONE batched PCG solve."""
+        self._set_bcs(bcs)
+        dev = self.stiffness()
+        infos = dev.solve_multi(self.n_cases, self._rhs(dev), func.vec, rtol=self.rtol, pc=self.preconditioner)
+        func.version += 1
+        self._record(infos, "state")
+        if report:
+            print(f"elasticity solve, {self.n_cases} load cases: {[i.iterations for i in infos]} PCG iterations, "
+                  f"{infos[0].solve_ms:.1f} ms")
+
+
+class MultiLoadCompliance(BackendForm):
+    """J = sum_l w_l F_l . u_l over the load cases of a Function(LoadCaseSpace(V, L)) (w = 1 without ``weights``)."""
+    rank = 0
+
+    def __init__(self, u: Function, tractions, measures=None, weights=None):
+        V, self.tractions, self.measures = _multi_arguments("MultiLoadCompliance", u, tractions, measures)
+        self.u, self.mesh = u, V.mesh
+        self.weights = np.ones(V.n_cases) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
+        if self.weights.size != V.n_cases:
+            raise ValueError(f"MultiLoadCompliance: {V.n_cases} load cases need as many weights")
+        self._grad = None
+
+    def functions(self):
+        return (self.u,)
+
+    def load(self) -> Vec:
+        """Column l = w_l F_l."""
+        return _multi_load_vec(self.mesh, [ds.facets() for ds in self.measures], self.tractions, self.weights)
+
+    def assemble_scalar(self) -> float:
+        return self.load().dot(self.u.vec, self.u.function_space.dim)
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        n = wrt.function_space.dim
+        if out is None:
+            if self._grad is None or self._grad.n != n:
+                self._grad = Vec(_ctx(), n)
+            out = self._grad
+        if wrt is self.u:
+            return out.copy_from(self.load())
+        return out.fill(0.0)
+
+
 def cell_volumes(mesh) -> np.ndarray:
     """|T_e| of every simplex."""
     p = mesh.x[mesh.conn]
@@ -652,6 +951,17 @@ def pdeRes(u, v, rho_e, f, E: float = 1.0, dss: Optional[Measure] = None, method
 def compliance(u, f, dss: Optional[Measure] = None) -> Compliance:
     """run_topo_opt_cantilever_beam.py:108-109"""
     return Compliance(u, f, dss)
+
+
+def pdeRes_multiload(u, v, rho_e, fs, dss_list=None, E: float = 1.0, method: str = "SIMP",
+                     preconditioner: str = "jacobi") -> MultiLoadElasticityResidual:
+    """`pdeRes` for the load cases ``fs[l]`` on ``dss_list[l]``; ``u`` is a Function(LoadCaseSpace(V, len(fs)))."""
+    return MultiLoadElasticityResidual(u, rho_e, fs, dss_list, E=E, nu=0.3, method=method, preconditioner=preconditioner)
+
+
+def compliance_multiload(u, fs, dss_list=None, weights=None) -> MultiLoadCompliance:
+    """sum_l w_l int_ds(l) f_l . u_l ds"""
+    return MultiLoadCompliance(u, fs, dss_list, weights)
 
 
 def pnorm_stress(u, rho_e, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0, q: float = 0.5,

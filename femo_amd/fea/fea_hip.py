@@ -21,11 +21,12 @@ from .utils_hip import (DeviceArray, DirichletBC, KSP, dirichletbc, getFuncArray
 from .forms import (ALPHA, BeamResidual, DerivativeForm, FieldExpression, Form, FunctionExpr, GradientMagnitude,
                     L2TrackingFunctional, LinearFunctional, NonlinearPoissonResidual, PoissonResidual, PowerExpr,
                     TestFunction, derivative, interiorResidual, outputForm, pdeRes)
-from .function import Function, FunctionSpace, VectorFunctionSpace
+from .function import Function, FunctionSpace, LoadCaseSpace, VectorFunctionSpace
 from .io import XDMFRecorder
 from .mesh import (BeamMesh, Mesh, createIntervalMesh, createRectangleMesh, createUnitCubeMesh, createUnitSquareMesh,
                    findNodeIndices, locate_dofs_geometrical, locate_entities_boundary, meshSize)
-from .elasticity import Constant, Measure, meshtags, pnorm_stress, von_Mises_stress
+from .elasticity import (Constant, Measure, compliance_multiload, meshtags, pdeRes_multiload, pnorm_stress,
+                         von_Mises_stress)
 
 
 class AbstractFEA(object):

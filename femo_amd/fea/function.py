@@ -97,6 +97,43 @@ class _SubSpace:
         return self.mesh.x
 
 
+class LoadCaseSpace:
+    """``n_cases`` copies of a VectorFunctionSpace in one vector, one per load case of the SIMP elasticity: column l holds the
+    dofs of ``base`` in its blocked layout and starts at ``l * base.dim`` (the layout of femo_elast_solve_multi).  A
+    ``Function(LoadCaseSpace(V, L))`` is an ordinary Function of dimension ``L * V.dim``."""
+
+    def __init__(self, base: VectorFunctionSpace, n_cases: int):
+        from .. import _lib
+        if not isinstance(base, VectorFunctionSpace):
+            raise NotImplementedError("LoadCaseSpace needs a VectorFunctionSpace(mesh, ('CG', 1)) base")
+        if not 1 <= int(n_cases) <= _lib.ELAST_MAX_COLS:
+            raise ValueError(f"LoadCaseSpace: {n_cases} load cases (1 to {_lib.ELAST_MAX_COLS})")
+        self.base, self.n_cases, self.mesh = base, int(n_cases), base.mesh
+        self.family = "CGV_CASES"
+        self.degree = 1
+        self.bs = base.bs
+        self.num_sub_spaces = 0
+
+    @property
+    def dim(self) -> int:
+        return self.n_cases * self.base.dim
+
+    def column(self, l: int) -> slice:
+        """The entries of load case ``l`` in a vector of this space."""
+        if not 0 <= l < self.n_cases:
+            raise IndexError(f"load case {l} of {self.n_cases}")
+        return slice(l * self.base.dim, (l + 1) * self.base.dim)
+
+    def tabulate_dof_coordinates(self) -> np.ndarray:
+        """The base space's: one row per vertex, the same for every load case."""
+        return self.base.tabulate_dof_coordinates()
+
+    def __eq__(self, other):
+        return isinstance(other, LoadCaseSpace) and other.base == self.base and other.n_cases == self.n_cases
+
+    __hash__ = object.__hash__
+
+
 class _VectorView:
     """PETSc-Vec-flavoured access to a Function's device vector."""
 

@@ -635,6 +635,30 @@ int femo_elast_von_mises(femo_elast* e, const femo_vec* rho, const femo_vec* u, 
  * femo_elast_pc_setup was called); every other value is block-Jacobi (M = the diagonal blocks), as before the field was read. */
 enum { FEMO_ELAST_PC_JACOBI = 0, FEMO_ELAST_PC_MULTILEVEL = 1 };
 int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info);
+/* Several load cases at once (csrc/elast_multi.hip).  n_cols columns, 1 <= n_cols <= FEMO_ELAST_MAX_COLS, lie one after
+ * the other in ONE femo_vec of length n_cols * n_dof: column l starts at l * n_dof and keeps the blocked layout
+ * d * vertex + component.  All columns share K(rho), the fixed set and the preconditioner.                               */
+enum { FEMO_ELAST_MAX_COLS = 8 };
+/* y_l = a Op x_l + b f_l for every column in one launch (Op = K or the masked A, as femo_elast_apply; f may be NULL).
+ * A thread keeps the accumulators of up to 4 columns and reads each d x d block, column index and fixed byte
+ * once for them; more columns take further passes inside the same launch.                                               */
+int femo_elast_apply_multi(femo_elast* e, int masked, int n_cols, double a, const femo_vec* x, double b, const femo_vec* f,
+                           femo_vec* y);
+/* femo_elast_solve for n_cols right-hand sides in one PCG loop: every launch of an iteration carries all columns, so an
+ * iteration costs the launches of a single-column one (5 with block-Jacobi, 8 with the multilevel preconditioner).  Each
+ * column has its own scalars and its own stopping test sqrt(r_l^T M^-1 r_l) <= max(rtol sqrt(r0_l^T M^-1 r0_l), atol); a
+ * column that converged, broke down (NaN) or met the test at iteration 0 (a zero right-hand side) is frozen: its x is not
+ * touched again while the others go on.  The host polls all columns every check_every iterations and stops when every
+ * column is finished or max_it is reached.  info[l]: iterations, converged, residual and rhs norm of column l; solve_ms
+ * is the device time of the whole batched solve, in every info[l].  Within a column the sums run in the order of
+ * femo_elast_solve: no float atomics, the same bits every call.                                                         */
+int femo_elast_solve_multi(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts,
+                           femo_solve_info* info /* [n_cols] */);
+/* femo_elast_drho with n_cols states u_l (u: n_cols * n_dof):
+ *   transpose = 1:  y[n_cell] (+)= sum_l C'(rho_e) x_{l,e}^T K0_e u_{l,e}      (x: n_cols * n_dof)
+ *   transpose = 0:  y_l[n_dof] (+)= sum_e C'(rho_e) x_e K0_e u_{l,e}           (x: n_cell, y: n_cols * n_dof)             */
+int femo_elast_drho_multi(femo_elast* e, int method, int transpose, int n_cols, const femo_vec* rho, const femo_vec* u,
+                          const femo_vec* x, femo_vec* y, int accumulate);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
  *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
  * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices

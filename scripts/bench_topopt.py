@@ -9,6 +9,13 @@ and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the
   ... --stress                                                  (adds the aggregated von Mises stress as a second scalar output and its
                                                                  total derivative to the cycle: one more adjoint solve, whose right-hand
                                                                  side is not the load; reported as extra keys of the JSON line)
+  ... --load-cases L                                            (2 <= L <= 8: L load cases on one K(rho) through pdeRes_multiload /
+                                                                 compliance_multiload, every solve of the cycle one batched PCG;
+                                                                 the loads are listed under `load_cases` below.  Adds to the JSON
+                                                                 line load_cases, the iteration counts per column, and the
+                                                                 batched solve timed against L sequential single-column solves of
+                                                                 the same right-hand sides: solve_ms_batched, solve_ms_sequential,
+                                                                 and the spread of their 5 alternated repeats)
 """
 from __future__ import annotations
 
@@ -78,6 +85,139 @@ def build(args):
     return sim, mesh, res, facets, t, filter_build_ms, stress
 
 
+def load_cases(d, n_cases, nely=None):
+    """(marker, traction) of the first ``n_cases`` loads.  Load 0 is the tip load of the single-load cycle; the others act
+    on further pieces of the boundary away from the clamped face x = 0:
+
+      2-D, the 160 x 80 cantilever                          3-D, the unit cube
+      0  right edge at mid-height (one cell up and down), t = (0, -1/4)    face x = 1 below z = 1/4, t = (0, 0, -1)
+      1  top edge beyond x = 3/4 L_X,    t = (0, -1/4)      face z = 1 beyond x = 3/4, t = (0, 0, -1)
+      2  the whole right edge,           t = (1/4, 0)       the whole face x = 1,      t = (1, 0, 0)
+      3  bottom edge beyond x = 3/4 L_X, t = (0, 1/4)       face z = 0 beyond x = 3/4, t = (0, 0, 1)
+      4  top edge, x in (1/2, 3/4) L_X,  t = (0, -1/4)      face y = 1 beyond x = 3/4, t = (0, -1, 0)
+      5  bottom edge, same piece,        t = (0, 1/4)       face y = 0 beyond x = 3/4, t = (0, 1, 0)
+      6  top edge beyond x = 3/4 L_X,    t = (1/4, 0)       face x = 1 below y = 1/4,  t = (0, -1, 0)
+      7  the whole right edge,           t = (0, -1/4)      face x = 1 above z = 3/4,  t = (0, 0, 1)"""
+    e = 3e-6
+    if d == 2:
+        LX, LY = 160.0, 80.0
+        right = lambda x: abs(x[0] - LX) < e
+        top = lambda lo, hi: (lambda x: np.logical_and(abs(x[1] - LY) < e, np.logical_and(x[0] > lo * LX - e, x[0] < hi * LX + e)))
+        bot = lambda lo, hi: (lambda x: np.logical_and(abs(x[1]) < e, np.logical_and(x[0] > lo * LX - e, x[0] < hi * LX + e)))
+        cases = [(lambda x: np.logical_and(abs(x[1] - LY / 2) < LY / nely + e, abs(x[0] - LX) < e), (0.0, -0.25)),
+                 (top(0.75, 1.0), (0.0, -0.25)), (right, (0.25, 0.0)), (bot(0.75, 1.0), (0.0, 0.25)),
+                 (top(0.5, 0.75), (0.0, -0.25)), (bot(0.5, 0.75), (0.0, 0.25)), (top(0.75, 1.0), (0.25, 0.0)),
+                 (right, (0.0, -0.25))]
+    else:
+        on = lambda k, v: (lambda x: np.isclose(x[k], v))
+        both = lambda a, b: (lambda x: np.logical_and(a(x), b(x)))
+        far = lambda x: x[0] > 0.75 - e
+        cases = [(both(on(0, 1.0), lambda x: x[2] < 0.25), (0.0, 0.0, -1.0)), (both(on(2, 1.0), far), (0.0, 0.0, -1.0)),
+                 (on(0, 1.0), (1.0, 0.0, 0.0)), (both(on(2, 0.0), far), (0.0, 0.0, 1.0)),
+                 (both(on(1, 1.0), far), (0.0, -1.0, 0.0)), (both(on(1, 0.0), far), (0.0, 1.0, 0.0)),
+                 (both(on(0, 1.0), lambda x: x[1] < 0.25), (0.0, -1.0, 0.0)),
+                 (both(on(0, 1.0), lambda x: x[2] > 0.75), (0.0, 0.0, 1.0))]
+    return cases[:n_cases]
+
+
+def build_multi(args):
+    """The model of `build` with ``args.load_cases`` loads: the state is a Function(LoadCaseSpace(V, L))."""
+    from femo_amd.csdl_opt.fea_model import FEAModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.simulator import Simulator
+    from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, LoadCaseSpace, Measure, VectorFunctionSpace,
+                                      compliance_multiload, createRectangleMesh, createUnitCubeMesh,
+                                      locate_dofs_geometrical, locate_entities_boundary, meshSize, meshtags, pdeRes_multiload)
+    if args.n3:
+        mesh = createUnitCubeMesh(args.n3)
+    else:
+        mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([160.0, 80.0]), args.nelx, args.nely)
+    d = mesh.tdim
+    dss, fs = [], []
+    for l, (marker, t) in enumerate(load_cases(d, args.load_cases, args.nely)):
+        facets = locate_entities_boundary(mesh, d - 1, marker)
+        if len(facets) == 0:
+            raise SystemExit(f"load case {l} has no facets on this mesh")
+        dss.append(Measure("ds", domain=mesh, subdomain_data=meshtags(mesh, d - 1, facets, np.full(len(facets), 100 + l, dtype=np.int32)))(100 + l))
+        fs.append(Constant(mesh, t))
+    fea = FEA(mesh)
+    fea.REPORT = False
+    Q, V = FunctionSpace(mesh, ("DG", 0)), VectorFunctionSpace(mesh, ("CG", 1))
+    rho, u = Function(Q), Function(LoadCaseSpace(V, args.load_cases))
+    res = pdeRes_multiload(u, None, rho, fs, dss, preconditioner=args.pc)
+    fea.add_input("density", rho)
+    fea.add_state(name="displacements", function=u, residual_form=res, arguments=["density"])
+    fea.add_output(name="compliance", type="scalar", form=compliance_multiload(u, fs, dss), arguments=["displacements"])
+    ubc = Function(V)
+    ubc.vector.set(0.0)
+    fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), lambda x: np.isclose(x[0], 0.0, atol=1e-6))], V)
+    model = FEAModel(fea=[fea])
+    h = meshSize(mesh)
+    model.add(GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
+              name="general_filter_model")
+    model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.random.default_rng(0).random(mesh.n_cell) * 0.86)
+    return Simulator(model), mesh, res
+
+
+def main_multi(args, ctx):
+    """The cycle with L load cases, then the batched solve against L sequential single-column solves of the same
+    right-hand sides on the same handle: a warm-up of both, then 5 alternated repeats, wall clock around calls that end in
+    a device synchronisation."""
+    from femo_amd.engine import Vec
+    L = args.load_cases
+    sim, mesh, res = build_multi(args)
+    x0 = np.array(sim["density_unfiltered"])
+    times = []
+    for k in range(args.cycles + 1):
+        sim["density_unfiltered"] = x0 * (1.0 - 1e-3 * k)
+        ctx.sync()
+        t0 = time.perf_counter()
+        sim.run()
+        np.asarray(sim.compute_totals("compliance", "density_unfiltered"))
+        ctx.sync()
+        if k > 0:
+            times.append((time.perf_counter() - t0) * 1e3)
+    info = res.last_info
+    dev = res.stiffness()
+    n = dev.n_dof
+    B = np.array(res._rhs(dev).get()).reshape(L, n)
+    bm, xm = Vec(ctx, L * n).set(B.ravel()), Vec(ctx, L * n)
+    bs, xs = [Vec(ctx, n).set(B[l]) for l in range(L)], Vec(ctx, n)
+
+    def batched():
+        ctx.sync()
+        t0 = time.perf_counter()
+        infos = dev.solve_multi(L, bm, xm, pc=args.pc)
+        return (time.perf_counter() - t0) * 1e3, infos
+
+    def sequential():
+        ctx.sync()
+        t0 = time.perf_counter()
+        infos = [dev.solve(bs[l], xs, pc=args.pc) for l in range(L)]
+        return (time.perf_counter() - t0) * 1e3, infos
+
+    batched(); sequential()
+    tb, ts = [], []
+    for _ in range(5):
+        t, ib = batched(); tb.append(t)
+        t, isq = sequential(); ts.append(t)
+    spread = max(max(tb) - min(tb), max(ts) - min(ts))
+    out = dict(metric="topopt_cycle_multiload", mesh=(f"cube n={args.n3}" if args.n3 else f"rect {args.nelx}x{args.nely}"),
+               n_dof=n, n_cell=mesh.n_cell, load_cases=L, pc=args.pc, cycle_ms=float(np.median(times)),
+               cycle_ms_all=[float(v) for v in times], pcg_iterations_forward=info["state"]["iterations"],
+               pcg_iterations_adjoint=info["adjoint"]["iterations"], compliance=float(sim["compliance"][0]),
+               solve_ms_batched=float(np.median(tb)), solve_ms_sequential=float(np.median(ts)),
+               solve_ms_batched_all=[float(v) for v in tb], solve_ms_sequential_all=[float(v) for v in ts], spread=float(spread),
+               batched_faster_than_spread=bool(np.median(ts) - np.median(tb) > spread),
+               device_ms_batched=float(ib[0].solve_ms), device_ms_sequential=float(sum(i.solve_ms for i in isq)),
+               iterations_batched=[i.iterations for i in ib], iterations_sequential=[i.iterations for i in isq],
+               converged=[i.converged for i in ib])
+    if args.pc == "multilevel":
+        pci = dev.pc_info()
+        out.update(pc_levels=pci["levels"], pc_nodes=pci["nodes"], pc_lattice_bytes=pci["bytes"])
+    print(json.dumps(out))
+
+
 def scipy_cycle(mesh, facets, t, x0, radius):
     """The same cycle with SciPy: KD-tree filter, element-by-element assembly, spsolve forward and adjoint."""
     import scipy.sparse as sp
@@ -120,7 +260,16 @@ def main():
     ap.add_argument("--no-scipy", action="store_true")
     ap.add_argument("--pc", choices=("jacobi", "multilevel"), default="jacobi", help="preconditioner of the PCG solves")
     ap.add_argument("--stress", action="store_true", help="add the p-norm von Mises stress output and its total derivative")
+    ap.add_argument("--load-cases", type=int, default=1,
+                    help="number of load cases, 1 to 8; more than 1: the tip load plus loads on further pieces of the boundary "
+                         "(top, bottom and right edge in 2-D; the faces z = 1, z = 0, y = 1, y = 0 beyond x = 3/4 and pieces of "
+                         "x = 1 in 3-D; `load_cases` in this script lists them), solved as one batched PCG and timed against "
+                         "sequential single-column solves")
     args = ap.parse_args()
+    if not 1 <= args.load_cases <= 8:
+        ap.error("--load-cases: 1 to 8")
+    if args.load_cases > 1 and args.stress:
+        ap.error("--stress is not available with several load cases")
     from femo_amd import _lib
     from femo_amd.engine import Context, Vec
     from femo_amd.fea import utils_hip
@@ -128,6 +277,8 @@ def main():
         raise SystemExit("bench_topopt needs a HIP device")
     ctx = Context(0)
     utils_hip.set_context(ctx)
+    if args.load_cases > 1:
+        return main_multi(args, ctx)
     sim, mesh, res, facets, t, filter_build_ms, stress = build(args)
     x0 = np.array(sim["density_unfiltered"])
     times = []
