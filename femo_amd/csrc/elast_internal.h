@@ -1,4 +1,5 @@
-// Shared by elasticity.hip (assembly, products, PCG loop) and elast_pc.hip (multilevel preconditioner).  Not part of the ABI.
+// Shared by elasticity.hip (assembly, products, PCG loop, stress), elast_pc.hip (multilevel preconditioner), elast_multi.hip
+// (batched PCG) and elast_stress_multi.hip (stress over several load cases).  Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -27,6 +28,9 @@ struct femo_elast {
   double* h_s = nullptr;        // pinned
   // stress aggregate (femo_elast_pnorm_stress): one partial per cell block and the folded value behind them, on first use
   double* w_spart = nullptr;
+  // the same for several load cases (femo_elast_pnorm_stress_multi): FEMO_ELAST_MAX_COLS slabs of partials, one per column,
+  // and the folded values behind them, on first use
+  double* w_smpart = nullptr;
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
   femo_elast_pc* pc = nullptr;
   bool pc_dirty = true;
@@ -132,6 +136,41 @@ __device__ __forceinline__ void load_cell(const int32_t* __restrict__ conn, cons
 #pragma unroll
     for (int i = 0; i < D; ++i) p[b][i] = x[(int64_t)v[b] * D + i];
   }
+}
+
+// Solid-material stress sigma_0(u) of a P1 cell as a 3 x 3 tensor (plane strain in 2-D: sigma_zz = lam tr eps, no
+// out-of-plane shear).  Its deviator does not see lam: s = 2 mu (eps - tr(eps) / 3 I), so s_zz = -2 mu tr(eps) / 3 in
+// 2-D.  Returns sigma_vm = sqrt(3/2 s : s); s holds the d x d block of the deviator.
+template <int D>
+__device__ __forceinline__ double cell_von_mises(const double (&g)[D + 1][D], const int32_t (&v)[D + 1],
+                                                 const double* __restrict__ u, double mu, double (&s)[D][D]) {
+  double Gu[D][D];      // Gu[i][k] = du_i/dx_k
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) Gu[i][k] = 0.0;
+#pragma unroll
+  for (int b = 0; b <= D; ++b)
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const double ub = u[(int64_t)v[b] * D + i];
+#pragma unroll
+      for (int k = 0; k < D; ++k) Gu[i][k] += ub * g[b][k];
+    }
+  double tr = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) tr += Gu[i][i];
+  const double hyd = (2.0 / 3.0) * mu * tr;
+  double ss = D == 2 ? hyd * hyd : 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const double t = mu * (Gu[i][k] + Gu[k][i]) - (i == k ? hyd : 0.0);
+      s[i][k] = t;
+      ss += t * t;
+    }
+  return sqrt(1.5 * ss);
 }
 
 __device__ __forceinline__ double penal(int method, double r) {

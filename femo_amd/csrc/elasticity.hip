@@ -258,41 +258,7 @@ __global__ __launch_bounds__(EB) void k_elast_drho_N(
 }
 
 // ------------------------------------------------------------------------------------------------ stress ----
-// Solid-material stress sigma_0(u) of a P1 cell as a 3 x 3 tensor (plane strain in 2-D: sigma_zz = lam tr eps, no
-// out-of-plane shear).  Its deviator does not see lam: s = 2 mu (eps - tr(eps) / 3 I), so s_zz = -2 mu tr(eps) / 3 in
-// 2-D.  Returns sigma_vm = sqrt(3/2 s : s); s holds the d x d block of the deviator.
-template <int D>
-__device__ __forceinline__ double cell_von_mises(const double (&g)[D + 1][D], const int32_t (&v)[D + 1],
-                                                 const double* __restrict__ u, double mu, double (&s)[D][D]) {
-  double Gu[D][D];      // Gu[i][k] = du_i/dx_k
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int k = 0; k < D; ++k) Gu[i][k] = 0.0;
-#pragma unroll
-  for (int b = 0; b <= D; ++b)
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      const double ub = u[(int64_t)v[b] * D + i];
-#pragma unroll
-      for (int k = 0; k < D; ++k) Gu[i][k] += ub * g[b][k];
-    }
-  double tr = 0.0;
-#pragma unroll
-  for (int i = 0; i < D; ++i) tr += Gu[i][i];
-  const double hyd = (2.0 / 3.0) * mu * tr;
-  double ss = D == 2 ? hyd * hyd : 0.0;
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const double t = mu * (Gu[i][k] + Gu[k][i]) - (i == k ? hyd : 0.0);
-      s[i][k] = t;
-      ss += t * t;
-    }
-  return sqrt(1.5 * ss);
-}
-
+// cell_von_mises<D>: elast_internal.h (shared with elast_stress_multi.hip).
 // One thread per cell, every output optional by null pointer:
 //   field[c] = rho_c^q sigma_vm                                       (the relaxed cell stress)
 //   part[block] = sum over the block of J_c = |T_c| / alpha (m rho_c^q sigma_vm)^p
@@ -745,7 +711,7 @@ int femo_elast_destroy(femo_elast* e) {
   femo_elast_multi_free(e);
   hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
-  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_spart);
+  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_spart); hipFree(e->w_smpart);
   if (e->h_flag) hipHostFree(e->h_flag);
   if (e->h_s) hipHostFree(e->h_s);
   delete e;

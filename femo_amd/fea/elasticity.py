@@ -19,6 +19,12 @@ are used unchanged.
                        L load cases on one K(rho): the state is a Function(LoadCaseSpace(V, L)), column l solves
                        K(rho) u_l = F_l, and J = sum_l w_l F_l . u_l.  Every solve of the cycle -- state, adjoint, forward
                        mode -- is one batched PCG over all columns (csrc/elast_multi.hip)
+  MultiLoadPnormStress J = sum_l w_l J_l with one aggregate J_l = (1/alpha) sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p per
+                       load case of a LoadCaseSpace state: the values, dJ/du (column l = w_l dJ_l/du_l) and dJ/drho of all
+                       load cases in one pass over the mesh (csrc/elast_stress_multi.hip).  Its adjoint is one batched PCG
+                       whose right-hand sides are not loads: they are non-zero on the clamped dofs of every column
+  MultiLoadVonMises    the cell field max_l s_l rho_e^q sigma_vm,e(u_l) (the envelope over the load cases), or that of one
+                       load case, for `project` / FEA.add_field_output
 
 P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
 """
@@ -192,6 +198,39 @@ class DeviceElasticity:
         check(self.lib.femo_elast_drho_multi(self.handle, int(method), int(bool(transpose)), n_cols, rho.handle, u.handle,
                                              x.handle, y.handle, int(bool(accumulate))))
         return y
+
+    def pnorm_stress_multi(self, n_cols: int, rho: Vec, u: Vec, m, p: float, q: float, alpha: float, weights=None,
+                           value: bool = True, grad_u: Optional[Vec] = None, grad_rho: Optional[Vec] = None,
+                           accumulate: bool = False):
+        """J_l = (1/alpha) sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p for every column (the array of the ``n_cols`` unweighted
+        values is returned when ``value``), column l of ``grad_u`` (+)= w_l dJ_l/du_l, ``grad_rho`` (+)= sum_l w_l dJ_l/drho.
+        ``m``: a scalar or one scale per column; ``weights``: one per column, 1 without."""
+        n_cols = self._cols(n_cols, u, grad_u)
+        mv = np.ascontiguousarray(m, dtype=np.float64).ravel()
+        if np.ndim(m) == 0:
+            mv = np.full(max(n_cols, 0), float(m))
+        wv = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        if mv.size != n_cols or (wv is not None and wv.size != n_cols):
+            raise _lib.FemoError(f"pnorm_stress_multi: {n_cols} columns need as many scales and weights")
+        vals = np.zeros(max(n_cols, 1))
+        f64 = lambda a: a.ctypes.data_as(_lib.c_f64p)
+        check(self.lib.femo_elast_pnorm_stress_multi(self.handle, n_cols, rho.handle, u.handle, f64(mv),
+                                                     None if wv is None else f64(wv), float(p), float(q), float(alpha),
+                                                     f64(vals) if value else None, None if grad_u is None else grad_u.handle,
+                                                     None if grad_rho is None else grad_rho.handle, int(bool(accumulate))))
+        return vals[:n_cols] if value else None
+
+    def von_mises_multi(self, n_cols: int, u: Vec, out: Vec, rho: Optional[Vec] = None, q: float = 0.0, scales=None,
+                        column: Optional[int] = None) -> Vec:
+        """out[n_cell] = max_l s_l rho_e^q sigma_vm,e(u_l), or s_column rho_e^q sigma_vm,e(u_column) with ``column``."""
+        n_cols = self._cols(n_cols, u)
+        sv = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64).ravel()
+        if sv is not None and sv.size != n_cols:
+            raise _lib.FemoError(f"von_mises_multi: {n_cols} columns need as many scales")
+        check(self.lib.femo_elast_von_mises_multi(self.handle, n_cols, None if rho is None else rho.handle, u.handle,
+                                                  None if sv is None else sv.ctypes.data_as(_lib.c_f64p), float(q),
+                                                  -1 if column is None else int(column), out.handle))
+        return out
 
     def export_csr(self):
         """K as a SciPy CSR matrix of size n_dof (host copy; tests and debugging)."""
@@ -697,11 +736,10 @@ class MultiLoadElasticityResidual(ElasticityResidual):
     (``fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), ...)], V)``), and hold for every column: the same fixed set,
     the same values, and the lifting b_l = F_l - K g.
 
-    Out of scope: supports that differ between the load cases; `ElasticityPnormStress` / `ElasticityVonMises` on a
-    multi-column state; partitioned meshes; ``fea.consistent_bc_partials`` (StateOperation filters the multiplier in the
-    numbering of the bc list, which reaches the first column only).  ``last_info[kind]`` keeps, per kind of solve ("state", "adjoint"), the record
-    of the last batched solve with one entry per column under ``columns``; ``solve_counts[kind]`` counts the batched
-    solves."""
+    Out of scope: supports that differ between the load cases; partitioned meshes.  The stress outputs of a multi-column
+    state are `MultiLoadPnormStress` / `MultiLoadVonMises`.  ``last_info[kind]`` keeps, per kind of solve ("state",
+    "adjoint"), the record of the last batched solve with one entry per column under ``columns``; ``solve_counts[kind]``
+    counts the batched solves."""
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, E: float = 1.0, nu: float = 0.3,
                  method: str = "SIMP", preconditioner: str = "jacobi"):
@@ -849,6 +887,9 @@ def cell_volumes(mesh) -> np.ndarray:
 
 
 def _check_stress_spaces(name: str, u: Function, rho: Optional[Function]) -> None:
+    if isinstance(u.function_space, LoadCaseSpace):
+        raise NotImplementedError(f"{name} needs a VectorFunctionSpace(mesh, ('CG', 1)) state; for the load cases of a "
+                                  "LoadCaseSpace use MultiLoadPnormStress / MultiLoadVonMises")
     if not isinstance(u.function_space, VectorFunctionSpace):
         raise NotImplementedError(f"{name} needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
     if rho is not None and (rho.function_space.family != "DG" or rho.function_space.mesh is not u.function_space.mesh):
@@ -930,6 +971,143 @@ class ElasticityVonMises(BackendForm):
         return target
 
 
+def _check_multi_stress_spaces(name: str, u: Function, rho: Optional[Function]) -> LoadCaseSpace:
+    V = u.function_space
+    if not isinstance(V, LoadCaseSpace):
+        raise NotImplementedError(f"{name} needs a Function(LoadCaseSpace(V, n_cases)) state")
+    if getattr(V.mesh, "local", None) is not None and V.mesh.local.nranks > 1:
+        raise NotImplementedError(f"{name}: partitioned meshes are out of scope")
+    if rho is not None and (rho.function_space.family != "DG" or rho.function_space.mesh is not V.mesh):
+        raise NotImplementedError(f"{name} needs a DG0 density on the state's mesh")
+    return V
+
+
+def _per_case(name: str, what: str, values, n_cases: int) -> np.ndarray:
+    """A scalar (the same for every load case) or one value per load case, as a float array of length n_cases."""
+    a = np.asarray(values, dtype=np.float64).ravel()
+    if a.size == 1 and np.ndim(values) == 0:
+        a = np.full(n_cases, float(a[0]))
+    if a.size != n_cases:
+        raise ValueError(f"{name}: {n_cases} load cases need as many {what}")
+    return a.copy()
+
+
+class MultiLoadPnormStress(BackendForm):
+    """J = sum_l w_l J_l, J_l = (1/alpha) sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p, over the load cases of a
+    Function(LoadCaseSpace(V, L)): the worst stress over all load cases as one p-norm constraint.  ``m``: a scalar or one
+    scale per load case (the loads differ in magnitude); ``weights`` >= 0, 1 without; p, q, alpha shared, alpha = |Omega|
+    unless given.  Value, dJ/du (column l = w_l dJ_l/du_l) and dJ/drho each take one pass over the mesh for all load cases
+    (`DeviceElasticity.pnorm_stress_multi`).  dJ/du is non-zero on the clamped dofs of every column: the exact reduced
+    gradient needs ``fea.consistent_bc_partials``."""
+    rank = 0
+
+    def __init__(self, u: Function, rho: Function, E: float = 1.0, nu: float = 0.3, m=1.0, p: float = 8.0, q: float = 0.5,
+                 alpha: Optional[float] = None, weights=None):
+        V = _check_multi_stress_spaces("MultiLoadPnormStress", u, rho)
+        self.n_cases = V.n_cases
+        self.m = _per_case("MultiLoadPnormStress", "scales m", m, V.n_cases)
+        self.weights = np.ones(V.n_cases) if weights is None else _per_case("MultiLoadPnormStress", "weights", weights, V.n_cases)
+        if not (np.all(self.m > 0.0) and p >= 1.0 and q >= 0.0) or (alpha is not None and not alpha > 0.0):
+            raise ValueError("the stress aggregate needs m > 0, p >= 1, q >= 0 and alpha > 0")
+        if not np.all(self.weights >= 0.0):
+            raise ValueError("the stress aggregate needs weights >= 0")
+        self.u, self.rho, self.mesh = u, rho, V.mesh
+        self.E, self.nu, self.p, self.q = float(E), float(nu), float(p), float(q)
+        self.alpha = float(cell_volumes(self.mesh).sum() if alpha is None else alpha)
+        self._grad = {}
+        self._values = None
+
+    def functions(self):
+        return (self.u, self.rho)
+
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
+
+    def _call(self, **kw):
+        return self.device().pnorm_stress_multi(self.n_cases, self.rho.vec, self.u.vec, self.m, self.p, self.q, self.alpha,
+                                                weights=self.weights, **kw)
+
+    def values(self) -> Optional[np.ndarray]:
+        """The J_l of the last `assemble_scalar` (unweighted), or None before the first."""
+        return None if self._values is None else self._values.copy()
+
+    def assemble_scalar(self) -> float:
+        self._values = self._call()
+        return float(self.weights @ self._values)
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:                                            # one buffer per argument: both partials may be pending
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        if wrt is self.u:
+            self._call(value=False, grad_u=out)
+        elif wrt is self.rho:
+            self._call(value=False, grad_rho=out)
+        else:
+            out.fill(0.0)
+        return out
+
+    def set_scales_from_state(self) -> np.ndarray:
+        """m_l = 1 / max_e rho_e^q sigma_vm,e(u_l) from the current state and density, so that the terms of every aggregate
+        are O(1).  A load case without stress keeps its scale."""
+        cells = Vec(_ctx(), self.mesh.n_cell)
+        for l in range(self.n_cases):
+            peak = float(np.max(self.device().von_mises_multi(self.n_cases, self.u.vec, cells, self.rho.vec, self.q,
+                                                              column=l).get()))
+            if peak > 0.0:
+                self.m[l] = 1.0 / peak
+        return self.m.copy()
+
+
+class MultiLoadVonMises(BackendForm):
+    """The cell field max_l s_l rho_e^q sigma_vm,e(u_l) over the load cases of a Function(LoadCaseSpace(V, L)) -- the envelope
+    -- or, with ``load_case``, s_l rho_e^q sigma_vm,e(u_l) of that load case alone.  ``scales`` > 0: one per load case, 1
+    without.  Projected onto DG0 and CG1 as `ElasticityVonMises` is."""
+    rank = 0
+
+    def __init__(self, u: Function, rho: Optional[Function] = None, E: float = 1.0, nu: float = 0.3, q: float = 0.0,
+                 scales=None, load_case: Optional[int] = None):
+        V = _check_multi_stress_spaces("MultiLoadVonMises", u, rho)
+        if not q >= 0.0 or (q > 0.0 and rho is None):
+            raise ValueError("the relaxed von Mises stress needs q >= 0, and the density when q > 0")
+        if load_case is not None and not 0 <= int(load_case) < V.n_cases:
+            raise ValueError(f"MultiLoadVonMises: load case {load_case} of {V.n_cases}")
+        self.scales = None if scales is None else _per_case("MultiLoadVonMises", "scales", scales, V.n_cases)
+        if self.scales is not None and not np.all(self.scales > 0.0):
+            raise ValueError("MultiLoadVonMises needs scales > 0")
+        self.u, self.rho, self.mesh, self.n_cases = u, rho, V.mesh, V.n_cases
+        self.E, self.nu, self.q = float(E), float(nu), float(q)
+        self.load_case = None if load_case is None else int(load_case)
+        self._cells = None
+
+    def functions(self):
+        return (self.u,) if self.rho is None else (self.u, self.rho)
+
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
+
+    def _field(self, out: Vec) -> Vec:
+        return self.device().von_mises_multi(self.n_cases, self.u.vec, out, None if self.rho is None else self.rho.vec, self.q,
+                                             scales=self.scales, column=self.load_case)
+
+    def project_field(self, target: Function, lump_mass: bool = False) -> Function:
+        V = target.function_space
+        if V.mesh is not self.mesh or isinstance(V, (VectorFunctionSpace, LoadCaseSpace)) or V.family not in ("DG", "CG"):
+            raise NotImplementedError("the von Mises stress is projected onto the DG0 or the CG1 space of the state's mesh")
+        if V.family == "DG":
+            self._field(target.vec)
+            target.version += 1
+            return target
+        if self._cells is None:
+            self._cells = Function(FunctionSpace(self.mesh, ("DG", 0)))
+        self._field(self._cells.vec)
+        self._cells.version += 1
+        from .utils_hip import project
+        project(self._cells, target, lump_mass=lump_mass)
+        return target
+
+
 def averageFunc(func: Function) -> LinearFunctional:
     """(1/|Omega|) int func dx for a DG0 Function (averageFunc, run_topo_opt_cantilever_beam.py:103-106)."""
     V = func.function_space
@@ -973,3 +1151,15 @@ def pnorm_stress(u, rho_e, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: f
 def von_Mises_stress(u, rho_e=None, E: float = 1.0, nu: float = 0.3, q: float = 0.0) -> ElasticityVonMises:
     """The (relaxed) von Mises stress as a field output."""
     return ElasticityVonMises(u, rho_e, E=E, nu=nu, q=q)
+
+
+def pnorm_stress_multiload(u, rho_e, E: float = 1.0, nu: float = 0.3, m=1.0, p: float = 8.0, q: float = 0.5,
+                           alpha: Optional[float] = None, weights=None) -> MultiLoadPnormStress:
+    """`pnorm_stress` over the load cases of a Function(LoadCaseSpace(V, L)): sum_l w_l J_l with one scale m_l per load case."""
+    return MultiLoadPnormStress(u, rho_e, E=E, nu=nu, m=m, p=p, q=q, alpha=alpha, weights=weights)
+
+
+def von_Mises_stress_multiload(u, rho_e=None, E: float = 1.0, nu: float = 0.3, q: float = 0.0, scales=None,
+                               load_case: Optional[int] = None) -> MultiLoadVonMises:
+    """The envelope of the (relaxed) von Mises stress over the load cases, or the field of one load case, as a field output."""
+    return MultiLoadVonMises(u, rho_e, E=E, nu=nu, q=q, scales=scales, load_case=load_case)

@@ -659,6 +659,24 @@ int femo_elast_solve_multi(femo_elast* e, int n_cols, const femo_vec* b, femo_ve
  *   transpose = 0:  y_l[n_dof] (+)= sum_e C'(rho_e) x_e K0_e u_{l,e}           (x: n_cell, y: n_cols * n_dof)             */
 int femo_elast_drho_multi(femo_elast* e, int method, int transpose, int n_cols, const femo_vec* rho, const femo_vec* u,
                           const femo_vec* x, femo_vec* y, int accumulate);
+/* femo_elast_pnorm_stress for n_cols states u_l in one pass (csrc/elast_stress_multi.hip): one aggregate per load case,
+ *   J_l = 1/alpha sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p,     J = sum_l w_l J_l
+ * with one scale m_l > 0 per load case, weights w_l >= 0 (NULL = 1), and p, q, alpha shared.  The cell geometry and rho^q
+ * are computed once per cell (and once per cell visit of the vertex walk) for all columns.  Any output may be NULL:
+ *   values[n_cols]          the UNWEIGHTED J_l, folded on the device in a fixed order (one copy, one wait per call)
+ *   grad_u[n_cols * n_dof]  column l (+)= w_l dJ_l/du_l; without accumulate a column with w_l = 0 is written as zeros
+ *   grad_rho[n_cell]        (+)= sum_l w_l p q / rho_e J_{l,e}, summed in ascending l
+ * The zero-stress guard holds per (cell, column): a column with u_l = 0 gives exact zeros.  No float atomics: the same bits
+ * every call.                                                                                                             */
+int femo_elast_pnorm_stress_multi(femo_elast* e, int n_cols, const femo_vec* rho, const femo_vec* u,
+                                  const double* m /* [n_cols] */, const double* w /* [n_cols] or NULL */, double p, double q,
+                                  double alpha, double* values /* [n_cols] or NULL */, femo_vec* grad_u, femo_vec* grad_rho,
+                                  int accumulate);
+/* out_cells[n_cell] = max_l scale_l rho_e^q sigma_vm,e(u_l), the envelope over the load cases (column = -1), or
+ * scale_column rho_e^q sigma_vm,e(u_column) (0 <= column < n_cols).  scale > 0 per load case, NULL = 1; rho may be NULL
+ * when q == 0.                                                                                                            */
+int femo_elast_von_mises_multi(femo_elast* e, int n_cols, const femo_vec* rho, const femo_vec* u,
+                               const double* scale /* [n_cols] or NULL */, double q, int column, femo_vec* out_cells);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
  *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
  * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices

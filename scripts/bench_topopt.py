@@ -16,6 +16,14 @@ and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the
                                                                  batched solve timed against L sequential single-column solves of
                                                                  the same right-hand sides: solve_ms_batched, solve_ms_sequential,
                                                                  and the spread of their 5 alternated repeats)
+  ... --load-cases L --stress                                   (adds sum_l J_l, the aggregated von Mises stress of every load case
+                                                                 (pnorm_stress_multiload, scales m_l from the first state), and its
+                                                                 total derivative to the timed cycle: one more batched adjoint solve,
+                                                                 whose right-hand sides are live on the clamped dofs.  Adds stress,
+                                                                 stress_values, stress_m, the iterations per column of that solve,
+                                                                 and the batched stress evaluation (value + dJ/du + dJ/drho in one
+                                                                 call) timed against L single-column calls on the same columns:
+                                                                 stress_ms_batched, stress_ms_sequential and their spread)
 """
 from __future__ import annotations
 
@@ -148,6 +156,12 @@ def build_multi(args):
     fea.add_input("density", rho)
     fea.add_state(name="displacements", function=u, residual_form=res, arguments=["density"])
     fea.add_output(name="compliance", type="scalar", form=compliance_multiload(u, fs, dss), arguments=["displacements"])
+    stress = None
+    if args.stress:
+        from femo_amd.fea.fea_hip import pnorm_stress_multiload
+        stress = pnorm_stress_multiload(u, rho, p=8.0, q=0.5)       # the m_l are set from the first state (main_multi)
+        fea.add_output(name="stress", type="scalar", form=stress, arguments=["displacements", "density"])
+        fea.consistent_bc_partials = True                           # dJ/du is not zero on the clamped dofs of any column
     ubc = Function(V)
     ubc.vector.set(0.0)
     fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), lambda x: np.isclose(x[0], 0.0, atol=1e-6))], V)
@@ -156,7 +170,46 @@ def build_multi(args):
     model.add(GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
               name="general_filter_model")
     model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.random.default_rng(0).random(mesh.n_cell) * 0.86)
-    return Simulator(model), mesh, res
+    return Simulator(model), mesh, res, stress
+
+
+def time_stress_multi(ctx, stress, L):
+    """The batched stress evaluation (value, dJ/du and dJ/drho in one call) against L calls of the single-column
+    `pnorm_stress` on the same columns with the same m_l: a warm-up of both, then 5 alternated repeats, each between two
+    device synchronisations."""
+    from femo_amd.engine import Vec
+    dev, rho = stress.device(), stress.rho.vec
+    n, nc = dev.n_dof, stress.mesh.n_cell
+    U = np.array(stress.u.vec.get()).reshape(L, n)
+    us = [Vec(ctx, n).set(U[l]) for l in range(L)]
+    gm, gr = Vec(ctx, L * n), Vec(ctx, nc)
+    g1, r1 = Vec(ctx, n), Vec(ctx, nc)
+
+    def batched():
+        ctx.sync()
+        t0 = time.perf_counter()
+        dev.pnorm_stress_multi(L, rho, stress.u.vec, stress.m, stress.p, stress.q, stress.alpha, weights=stress.weights,
+                               grad_u=gm, grad_rho=gr)
+        ctx.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def sequential():
+        ctx.sync()
+        t0 = time.perf_counter()
+        for l in range(L):
+            dev.pnorm_stress(rho, us[l], stress.m[l], stress.p, stress.q, stress.alpha, grad_u=g1, grad_rho=r1, accumulate=l > 0)
+        ctx.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    batched(); sequential()
+    tb, ts = [], []
+    for _ in range(5):
+        tb.append(batched())
+        ts.append(sequential())
+    spread = max(max(tb) - min(tb), max(ts) - min(ts))
+    return dict(stress_ms_batched=float(np.median(tb)), stress_ms_sequential=float(np.median(ts)),
+                stress_ms_batched_all=[float(v) for v in tb], stress_ms_sequential_all=[float(v) for v in ts],
+                stress_ms_spread=float(spread), stress_batched_faster_than_spread=bool(np.median(ts) - np.median(tb) > spread))
 
 
 def main_multi(args, ctx):
@@ -165,7 +218,7 @@ def main_multi(args, ctx):
     a device synchronisation."""
     from femo_amd.engine import Vec
     L = args.load_cases
-    sim, mesh, res = build_multi(args)
+    sim, mesh, res, stress = build_multi(args)
     x0 = np.array(sim["density_unfiltered"])
     times = []
     for k in range(args.cycles + 1):
@@ -174,6 +227,12 @@ def main_multi(args, ctx):
         t0 = time.perf_counter()
         sim.run()
         np.asarray(sim.compute_totals("compliance", "density_unfiltered"))
+        if stress is not None:
+            it_compliance_adjoint = res.last_info["adjoint"]["iterations"]
+            if k == 0:                                              # scales of the aggregates, fixed from the first state
+                stress.set_scales_from_state()
+                sim.run()
+            gs = np.asarray(sim.compute_totals("stress", "density_unfiltered"))
         ctx.sync()
         if k > 0:
             times.append((time.perf_counter() - t0) * 1e3)
@@ -212,6 +271,12 @@ def main_multi(args, ctx):
                device_ms_batched=float(ib[0].solve_ms), device_ms_sequential=float(sum(i.solve_ms for i in isq)),
                iterations_batched=[i.iterations for i in ib], iterations_sequential=[i.iterations for i in isq],
                converged=[i.converged for i in ib])
+    if stress is not None:
+        out.update(pcg_iterations_adjoint=it_compliance_adjoint, pcg_iterations_stress_adjoint=info["adjoint"]["iterations"],
+                   stress=float(sim["stress"][0]), stress_values=[float(v) for v in stress.values()],
+                   stress_m=[float(v) for v in stress.m], stress_p=stress.p, stress_q=stress.q,
+                   stress_gradient_norm=float(np.linalg.norm(gs)))
+        out.update(time_stress_multi(ctx, stress, L))
     if args.pc == "multilevel":
         pci = dev.pc_info()
         out.update(pc_levels=pci["levels"], pc_nodes=pci["nodes"], pc_lattice_bytes=pci["bytes"])
@@ -268,8 +333,6 @@ def main():
     args = ap.parse_args()
     if not 1 <= args.load_cases <= 8:
         ap.error("--load-cases: 1 to 8")
-    if args.load_cases > 1 and args.stress:
-        ap.error("--stress is not available with several load cases")
     from femo_amd import _lib
     from femo_amd.engine import Context, Vec
     from femo_amd.fea import utils_hip
