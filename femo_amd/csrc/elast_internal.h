@@ -1,5 +1,6 @@
-// Shared by elasticity.hip (assembly, products, PCG loop, stress), elast_pc.hip (multilevel preconditioner), elast_multi.hip
-// (batched PCG) and elast_stress_multi.hip (stress over several load cases).  Not part of the ABI.
+// Shared by elasticity.hip (assembly, dR/drho, load, stress, export, filter), elast_solve.hip (block product and PCG, for one
+// or several load cases), elast_pc.hip (multilevel preconditioner) and elast_stress_multi.hip (stress over several load
+// cases).  Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -21,11 +22,15 @@ struct femo_elast {
   int32_t* d_fverts = nullptr;
   int64_t* d_fptr = nullptr;    // n_vert + 1
   int32_t* d_flist = nullptr;
-  // PCG work
+  // PCG work: w_cols columns of r, z, p, q, one column after the other, and w_pstride partials per column; one column from
+  // femo_elast_create, grown on demand (femo_elast_work_reserve).  Per column EMS_STRIDE scalars and EMF_STRIDE flags,
+  // always for FEMO_ELAST_MAX_COLS columns, like their pinned mirrors.
+  int w_cols = 0;
+  int64_t w_pstride = 0;
   double *w_r = nullptr, *w_z = nullptr, *w_p = nullptr, *w_q = nullptr, *w_part = nullptr, *w_s = nullptr;
   int32_t* w_flag = nullptr;
   int32_t* h_flag = nullptr;    // pinned
-  double* h_s = nullptr;        // pinned
+  double* h_s = nullptr;        // pinned; the stress aggregates come back through it as well
   // stress aggregate (femo_elast_pnorm_stress): one partial per cell block and the folded value behind them, on first use
   double* w_spart = nullptr;
   // the same for several load cases (femo_elast_pnorm_stress_multi): FEMO_ELAST_MAX_COLS slabs of partials, one per column,
@@ -34,14 +39,6 @@ struct femo_elast {
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
   femo_elast_pc* pc = nullptr;
   bool pc_dirty = true;
-  // batched PCG (femo_elast_solve_multi): m_cols columns of r, z, p, q, one column after the other; per column
-  // EMS_STRIDE scalars, EMF_STRIDE flags and m_pstride partials.  Allocated on the first batched solve, grown on demand.
-  int m_cols = 0;
-  int64_t m_pstride = 0;
-  double *m_r = nullptr, *m_z = nullptr, *m_p = nullptr, *m_q = nullptr, *m_part = nullptr, *m_s = nullptr;
-  int32_t* m_flag = nullptr;
-  int32_t* hm_flag = nullptr;   // pinned, FEMO_ELAST_MAX_COLS columns
-  double* hm_s = nullptr;       // pinned
   int method = 0;                    // of the last femo_elast_assemble ...
   uint64_t rho_uid = 0, rho_gen = 0; // ... and its density vector: looked up in the live table at the lazy build (never a
                                      // pointer: the caller may have destroyed it); uid 0 = wrapped memory, built at once
@@ -52,7 +49,7 @@ constexpr int PCG_GRID = 512;        // blocks of the PCG reductions (one partia
 
 // PCG device scalars s[]: 0 rz, 1 alpha, 2 beta, 3 tol^2, 4 rz0.  flag[]: 0 done, 1 iterations, 2 breakdown, 3 converged.
 enum { S_RZ = 0, S_ALPHA = 1, S_BETA = 2, S_TOL2 = 3, S_RZ0 = 4 };
-// Batched PCG: column l keeps its own s[] at s + l * EMS_STRIDE and its own flag[] at flag + l * EMF_STRIDE.
+// Column l keeps its own s[] at s + l * EMS_STRIDE and its own flag[] at flag + l * EMF_STRIDE.
 constexpr int EMS_STRIDE = 8, EMF_STRIDE = 4;
 
 // elast_pc.hip ------------------------------------------------------------------------------------------------------
@@ -61,23 +58,25 @@ void femo_elast_pc_free(femo_elast* e);
 int femo_elast_pc_ensure(femo_elast* e);
 // The build itself, from the density the current K was assembled with.
 int femo_elast_pc_build(femo_elast* e, const double* rho);
-// The preconditioner step of the PCG loop: what k_pcg_precond does with z = M^-1 r of the multilevel form.
-// update: x += alpha p, r -= alpha q first (alpha = s[S_ALPHA]; nothing once flag[0] is set).  pinit != null: p = z as well.
-int femo_elast_pc_step(femo_elast* e, bool update, double* x, double* r, const double* p, const double* q, double* z,
-                       double* pinit, const double* s, double* part, const int32_t* flag);
-// The same step for n_cols columns in the same four launches (a column dimension in every grid; k_pc_coarse: one
-// workgroup per column).  Vectors: column l at + l * n_dof; s, flag: EMS_STRIDE / EMF_STRIDE apart; part: part_stride
-// apart.  Every column goes through the arithmetic of femo_elast_pc_step in the same order; a column whose flag[0] is
-// set is skipped (update only).  The L copies of the lattice work vectors are allocated here on first use.
-int femo_elast_pc_step_multi(femo_elast* e, bool update, int n_cols, double* x, double* r, const double* p, const double* q,
-                             double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag);
+// The preconditioner step of the PCG loop for n_cols columns in four launches (a column dimension in every grid;
+// k_pc_coarse: one workgroup per column): what k_pcg_precond does with z = M^-1 r of the multilevel form.
+// update: x += alpha p, r -= alpha q first (alpha = s[S_ALPHA]; a column whose flag[0] is set is skipped).  pinit != null:
+// p = z as well.  Vectors: column l at + l * n_dof; s, flag: EMS_STRIDE / EMF_STRIDE apart; part: part_stride apart.  The
+// lattice work vectors grow here when n_cols exceeds what they hold.
+int femo_elast_pc_step(femo_elast* e, bool update, int n_cols, double* x, double* r, const double* p, const double* q,
+                       double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag);
 
 // elasticity.hip ----------------------------------------------------------------------------------------------------
 // The launches of femo_elast_drho on raw pointers (femo_elast_drho_multi loops them over the columns).
 int femo_elast_drho_launch(femo_elast* e, int method, int transpose, const double* rho, const double* u, const double* x,
                            double* y, int accumulate);
-// elast_multi.hip ---------------------------------------------------------------------------------------------------
-void femo_elast_multi_free(femo_elast* e);
+// elast_solve.hip ---------------------------------------------------------------------------------------------------
+// y_l = a Op x_l + b f_l for n_cols columns (+ partial dot(x_l, y_l) per block and column, part_stride apart, when part !=
+// null).  masked: identity rows / columns on fixed dofs.  done != null: a column whose done[l * EMF_STRIDE] is set is skipped.
+int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const double* x, double b, const double* f, double* y,
+                    double* part, int64_t part_stride, const int32_t* done);
+// PCG work vectors for at least n_cols columns.  who: the entry point, for the error text.
+int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who);
 
 #if defined(__HIPCC__)
 // gradients of the barycentric coordinates and the volume of a P1 simplex, from the vertices in `conn` order

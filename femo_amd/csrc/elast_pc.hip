@@ -14,9 +14,9 @@
 //   z = D^-1 r + P_L s_L + P_L-1 e    k_pc_final           the x / r update, p = z on the first call and the partial r.z of
 //                                                          k_pcg_precond, plus two multilinear gathers per vertex
 //
-// The four kernels are thin wrappers around __forceinline__ bodies (pc_*_body); the batched step of several load cases
-// (femo_elast_pc_step_multi, k_pc_*_multi) calls the same bodies with a column in the grid -- blockIdx.y, for k_pc_coarse one
-// workgroup per column -- and L copies of the lattice work vectors.  The Galerkin blocks are shared.
+// The four kernels carry a column in the grid -- blockIdx.y, for k_pc_coarse one workgroup per column -- so one step serves
+// the L load cases of a batched solve (femo_elast_pc_step) on L copies of the lattice work vectors; a single solve and
+// femo_elast_pc_apply are the step with L = 1.  The Galerkin blocks are shared.
 //
 // A vertex keeps its finest-lattice bin (int32 per axis) and fraction (fp64 per axis); the bin and fraction on level L - 1
 // follow exactly (bin >> 1, (frac + (bin & 1)) / 2).  The restriction CSR carries the products of the same fractions, so
@@ -57,11 +57,9 @@ struct femo_elast_pc {
   double H[PC_ML] = {};
   double* d_G = nullptr;        // total nodes * d^2: Galerkin blocks
   double* d_C = nullptr;        // total nodes * d^2: their inverses
-  double* d_g = nullptr;        // total nodes * d: restricted residual
-  double* d_e = nullptr;        // total nodes * d: corrections
-  double* d_gm = nullptr;       // m_cols copies of d_g and d_e for the batched step, on its first use
-  double* d_em = nullptr;
-  int m_cols = 0;
+  double* d_g = nullptr;        // cols * total nodes * d: restricted residual, one column after the other
+  double* d_e = nullptr;        // cols * total nodes * d: corrections
+  int cols = 0;                 // one from femo_elast_pc_setup, grown by the step
   int32_t* d_vbin = nullptr;    // n_vert * d
   double* d_vfrac = nullptr;    // n_vert * d
   int64_t* d_rptr = nullptr;    // finest nodes + 1
@@ -216,13 +214,19 @@ __global__ __launch_bounds__(EB) void k_pc_invert(int64_t n_nodes, double* __res
 }
 
 // ------------------------------------------------------------------------------------------------- apply ----
+// blockIdx.y of the kernels below is the column (k_pc_coarse: blockIdx.x).  vs: column stride of the mesh vectors, ls: of
+// the lattice vectors, ps: of the partials.
 // g_L[node] = sum over the vertices under the node's hat of w (r - alpha q), fixed dofs skipped.  GL lanes per node.
 template <int D, int GL, bool UPDATE>
-__device__ __forceinline__ void pc_restrict_mesh_body(int64_t nodes, const int64_t* __restrict__ rptr,
-                                                      const int32_t* __restrict__ rvert, const double* __restrict__ rw,
-                                                      const double* __restrict__ r, const double* __restrict__ q,
-                                                      const double* __restrict__ s, const uint8_t* __restrict__ fixed,
-                                                      const int32_t* __restrict__ flag, double* __restrict__ g) {
+__global__ __launch_bounds__(EB) void k_pc_restrict_mesh(int64_t nodes, const int64_t* __restrict__ rptr,
+                                                         const int32_t* __restrict__ rvert, const double* __restrict__ rw,
+                                                         const double* __restrict__ r, const double* __restrict__ q,
+                                                         const double* __restrict__ s, const uint8_t* __restrict__ fixed,
+                                                         const int32_t* __restrict__ flag, double* __restrict__ g,
+                                                         int64_t vs, int64_t ls) {
+  const int64_t col = blockIdx.y;
+  r += col * vs; s += col * EMS_STRIDE; flag += col * EMF_STRIDE; g += col * ls;
+  if (UPDATE) q += col * vs;
   if (UPDATE && flag[0]) return;
   const double alpha = UPDATE ? s[S_ALPHA] : 0.0;
   const int lane = threadIdx.x % GL;
@@ -256,28 +260,6 @@ __device__ __forceinline__ void pc_restrict_mesh_body(int64_t nodes, const int64
     for (int c = 0; c < D; ++c) g[node * D + c] = acc[c];
   }
   }
-}
-
-template <int D, int GL, bool UPDATE>
-__global__ __launch_bounds__(EB) void k_pc_restrict_mesh(int64_t nodes, const int64_t* __restrict__ rptr,
-                                                         const int32_t* __restrict__ rvert, const double* __restrict__ rw,
-                                                         const double* __restrict__ r, const double* __restrict__ q,
-                                                         const double* __restrict__ s, const uint8_t* __restrict__ fixed,
-                                                         const int32_t* __restrict__ flag, double* __restrict__ g) {
-  pc_restrict_mesh_body<D, GL, UPDATE>(nodes, rptr, rvert, rw, r, q, s, fixed, flag, g);
-}
-
-// The batched kernels: blockIdx.y is the column.  vs: column stride of the mesh vectors, ls: of the lattice vectors.
-template <int D, int GL, bool UPDATE>
-__global__ __launch_bounds__(EB) void k_pc_restrict_mesh_multi(int64_t nodes, const int64_t* __restrict__ rptr,
-                                                               const int32_t* __restrict__ rvert, const double* __restrict__ rw,
-                                                               const double* __restrict__ r, const double* __restrict__ q,
-                                                               const double* __restrict__ s, const uint8_t* __restrict__ fixed,
-                                                               const int32_t* __restrict__ flag, double* __restrict__ g,
-                                                               int64_t vs, int64_t ls) {
-  const int64_t col = blockIdx.y;
-  pc_restrict_mesh_body<D, GL, UPDATE>(nodes, rptr, rvert, rw, r + col * vs, UPDATE ? q + col * vs : q, s + col * EMS_STRIDE,
-                                       fixed, flag + col * EMF_STRIDE, g + col * ls);
 }
 
 template <int D>
@@ -348,10 +330,12 @@ __device__ __forceinline__ void pc_prolong_node(const PcLat& F, const PcLat& Cc,
 
 // finest level: s_L = C_L g_L (into e_L) and g_L-1 = T^T g_L
 template <int D, bool UPDATE>
-__device__ __forceinline__ void pc_lat_restrict_body(const PcLat& F, const PcLat& Cc, int has_coarse,
-                                                     const double* __restrict__ CF, const double* __restrict__ gF,
-                                                     double* __restrict__ sF, double* __restrict__ gC,
-                                                     const int32_t* __restrict__ flag) {
+__global__ __launch_bounds__(EB) void k_pc_lat_restrict(PcLat F, PcLat Cc, int has_coarse, const double* __restrict__ CF,
+                                                        const double* __restrict__ gF, double* __restrict__ sF,
+                                                        double* __restrict__ gC, const int32_t* __restrict__ flag, int64_t ls) {
+  const int64_t col = blockIdx.y;
+  gF += col * ls; sF += col * ls; flag += col * EMF_STRIDE;
+  if (has_coarse) gC += col * ls;
   if (UPDATE && flag[0]) return;
   for (int64_t idx = (int64_t)blockIdx.x * EB + threadIdx.x; idx < F.nodes; idx += (int64_t)gridDim.x * EB) {
     pc_prolong_node<D>(F, Cc, idx, CF, gF, nullptr, sF);
@@ -359,28 +343,14 @@ __device__ __forceinline__ void pc_lat_restrict_body(const PcLat& F, const PcLat
   }
 }
 
+// levels top .. 0 in one workgroup: restrict down from g_top, e_0 = C_0 g_0, e_l = C_l g_l + T e_l-1 up to top.  One
+// workgroup per column (blockIdx.x), all of them at once; the Galerkin blocks C are shared
 template <int D, bool UPDATE>
-__global__ __launch_bounds__(EB) void k_pc_lat_restrict(PcLat F, PcLat Cc, int has_coarse, const double* __restrict__ CF,
-                                                        const double* __restrict__ gF, double* __restrict__ sF,
-                                                        double* __restrict__ gC, const int32_t* __restrict__ flag) {
-  pc_lat_restrict_body<D, UPDATE>(F, Cc, has_coarse, CF, gF, sF, gC, flag);
-}
-
-template <int D, bool UPDATE>
-__global__ __launch_bounds__(EB) void k_pc_lat_restrict_multi(PcLat F, PcLat Cc, int has_coarse, const double* __restrict__ CF,
-                                                              const double* __restrict__ gF, double* __restrict__ sF,
-                                                              double* __restrict__ gC, const int32_t* __restrict__ flag,
-                                                              int64_t ls) {
-  const int64_t col = blockIdx.y;
-  pc_lat_restrict_body<D, UPDATE>(F, Cc, has_coarse, CF, gF + col * ls, sF + col * ls, has_coarse ? gC + col * ls : gC,
-                                  flag + col * EMF_STRIDE);
-}
-
-// levels top .. 0 in one workgroup: restrict down from g_top, e_0 = C_0 g_0, e_l = C_l g_l + T e_l-1 up to top
-template <int D, bool UPDATE>
-__device__ __forceinline__ void pc_coarse_body(const PcLevels& P, int top, const double* __restrict__ C, double* g, double* e,
-                                               const int32_t* __restrict__ flag) {
+__global__ __launch_bounds__(PC_COARSE_NT) void k_pc_coarse(PcLevels P, int top, const double* __restrict__ C, double* g, double* e,
+                                                            const int32_t* __restrict__ flag, int64_t ls) {
   constexpr int DD = D * D;
+  const int64_t col = blockIdx.x;
+  g += col * ls; e += col * ls; flag += col * EMF_STRIDE;
   if (UPDATE && flag[0]) return;
   for (int l = top - 1; l >= 0; --l) {
     for (int64_t idx = threadIdx.x; idx < P.lat[l].nodes; idx += PC_COARSE_NT)
@@ -393,20 +363,6 @@ __device__ __forceinline__ void pc_coarse_body(const PcLevels& P, int top, const
                          l > 0 ? e + P.off[l - 1] * D : nullptr, e + P.off[l] * D);
     __syncthreads();
   }
-}
-
-template <int D, bool UPDATE>
-__global__ __launch_bounds__(PC_COARSE_NT) void k_pc_coarse(PcLevels P, int top, const double* __restrict__ C, double* g, double* e,
-                                                            const int32_t* __restrict__ flag) {
-  pc_coarse_body<D, UPDATE>(P, top, C, g, e, flag);
-}
-
-// one workgroup per column (blockIdx.x), all of them at once; the Galerkin blocks C are shared
-template <int D, bool UPDATE>
-__global__ __launch_bounds__(PC_COARSE_NT) void k_pc_coarse_multi(PcLevels P, int top, const double* __restrict__ C, double* g,
-                                                                  double* e, const int32_t* __restrict__ flag, int64_t ls) {
-  const int64_t col = blockIdx.x;
-  pc_coarse_body<D, UPDATE>(P, top, C, g + col * ls, e + col * ls, flag + col * EMF_STRIDE);
 }
 
 template <int D>
@@ -429,15 +385,21 @@ __device__ __forceinline__ void pc_gather(const PcLat& L, const int (&b)[D], con
 
 // k_pcg_precond with z = D^-1 r + P_L s_L + P_L-1 e_L-1 (free dofs)
 template <int D, bool UPDATE, bool INIT>
-__device__ __forceinline__ void pc_final_body(int64_t n_rows, const double* __restrict__ dinv, double* __restrict__ x,
-                                              double* __restrict__ r, const double* __restrict__ p,
-                                              const double* __restrict__ q, double* __restrict__ z, double* __restrict__ pinit,
-                                              const double* __restrict__ s, double* __restrict__ part,
-                                              const int32_t* __restrict__ flag, const uint8_t* __restrict__ fixed,
-                                              const int32_t* __restrict__ vbin, const double* __restrict__ vfrac, const PcLat& F,
-                                              const double* __restrict__ sF, const PcLat& Cc, const double* __restrict__ eC,
-                                              double* lds /* EB / 64 */) {
+__global__ __launch_bounds__(EB) void k_pc_final(int64_t n_rows, const double* __restrict__ dinv, double* __restrict__ x,
+                                                 double* __restrict__ r, const double* __restrict__ p,
+                                                 const double* __restrict__ q, double* __restrict__ z, double* __restrict__ pinit,
+                                                 const double* __restrict__ s, double* __restrict__ part,
+                                                 const int32_t* __restrict__ flag, const uint8_t* __restrict__ fixed,
+                                                 const int32_t* __restrict__ vbin, const double* __restrict__ vfrac, PcLat F,
+                                                 const double* __restrict__ sF, PcLat Cc, const double* __restrict__ eC,
+                                                 int64_t vs, int64_t ls, int64_t ps) {
   constexpr int DD = D * D;
+  __shared__ double lds[EB / 64];
+  const int64_t col = blockIdx.y;
+  r += col * vs; z += col * vs; s += col * EMS_STRIDE; part += col * ps; flag += col * EMF_STRIDE; sF += col * ls;
+  if (UPDATE) { x += col * vs; p += col * vs; q += col * vs; }
+  if (INIT) pinit += col * vs;
+  if (eC) eC += col * ls;
   if (UPDATE && flag[0]) return;
   double dotv = 0.0;
   const double alpha = UPDATE ? s[S_ALPHA] : 0.0;
@@ -478,36 +440,6 @@ __device__ __forceinline__ void pc_final_body(int64_t n_rows, const double* __re
   if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
-template <int D, bool UPDATE, bool INIT>
-__global__ __launch_bounds__(EB) void k_pc_final(int64_t n_rows, const double* __restrict__ dinv, double* __restrict__ x,
-                                                 double* __restrict__ r, const double* __restrict__ p,
-                                                 const double* __restrict__ q, double* __restrict__ z, double* __restrict__ pinit,
-                                                 const double* __restrict__ s, double* __restrict__ part,
-                                                 const int32_t* __restrict__ flag, const uint8_t* __restrict__ fixed,
-                                                 const int32_t* __restrict__ vbin, const double* __restrict__ vfrac, PcLat F,
-                                                 const double* __restrict__ sF, PcLat Cc, const double* __restrict__ eC) {
-  __shared__ double lds[EB / 64];
-  pc_final_body<D, UPDATE, INIT>(n_rows, dinv, x, r, p, q, z, pinit, s, part, flag, fixed, vbin, vfrac, F, sF, Cc, eC, lds);
-}
-
-// ps: column stride of the partials
-template <int D, bool UPDATE, bool INIT>
-__global__ __launch_bounds__(EB) void k_pc_final_multi(int64_t n_rows, const double* __restrict__ dinv, double* __restrict__ x,
-                                                       double* __restrict__ r, const double* __restrict__ p,
-                                                       const double* __restrict__ q, double* __restrict__ z,
-                                                       double* __restrict__ pinit, const double* __restrict__ s,
-                                                       double* __restrict__ part, const int32_t* __restrict__ flag,
-                                                       const uint8_t* __restrict__ fixed, const int32_t* __restrict__ vbin,
-                                                       const double* __restrict__ vfrac, PcLat F, const double* __restrict__ sF,
-                                                       PcLat Cc, const double* __restrict__ eC, int64_t vs, int64_t ls, int64_t ps) {
-  __shared__ double lds[EB / 64];
-  const int64_t col = blockIdx.y;
-  pc_final_body<D, UPDATE, INIT>(n_rows, dinv, UPDATE ? x + col * vs : x, r + col * vs, UPDATE ? p + col * vs : p,
-                                 UPDATE ? q + col * vs : q, z + col * vs, INIT ? pinit + col * vs : pinit, s + col * EMS_STRIDE,
-                                 part + col * ps, flag + col * EMF_STRIDE, fixed, vbin, vfrac, F, sF + col * ls, Cc,
-                                 eC ? eC + col * ls : eC, lds);
-}
-
 template <int D>
 int pc_build_blocks(femo_elast* e, const double* rho) {
   constexpr int DD = D * D;
@@ -538,40 +470,8 @@ int pc_build_blocks(femo_elast* e, const double* rho) {
 }
 
 template <int D, bool UPDATE>
-int pc_step(femo_elast* e, double* x, double* r, const double* p, const double* q, double* z, double* pinit, const double* s,
-            double* part, const int32_t* flag) {
-  constexpr int GL = D == 2 ? 8 : 64;
-  femo_elast_pc* pc = e->pc;
-  femo_mesh* m = e->mesh;
-  hipStream_t st = m->ctx->stream;
-  const PcLevels& P = pc->P;
-  const int L = P.n_levels - 1;
-  const PcLat& F = P.lat[L];
-  const PcLat& Cc = P.lat[L > 0 ? L - 1 : 0];
-  const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
-  double* gF = pc->d_g + P.off[L] * D;
-  double* sF = pc->d_e + P.off[L] * D;
-  double* gC = L > 0 ? pc->d_g + P.off[L - 1] * D : nullptr;
-  const double* eC = L > 0 ? pc->d_e + P.off[L - 1] * D : nullptr;
-  hipLaunchKernelGGL((k_pc_restrict_mesh<D, GL, UPDATE>), dim3(pc_grid(F.nodes * GL)), dim3(EB), 0, st, F.nodes, pc->d_rptr,
-                     pc->d_rvert, pc->d_rw, r, q, s, fx, flag, gF);
-  hipLaunchKernelGGL((k_pc_lat_restrict<D, UPDATE>), dim3(pc_grid(F.nodes)), dim3(EB), 0, st, F, Cc, L > 0 ? 1 : 0,
-                     pc->d_C + P.off[L] * D * D, gF, sF, gC, flag);
-  if (L > 0)
-    hipLaunchKernelGGL((k_pc_coarse<D, UPDATE>), dim3(1), dim3(PC_COARSE_NT), 0, st, P, L - 1, pc->d_C, pc->d_g, pc->d_e, flag);
-  if (pinit)
-    hipLaunchKernelGGL((k_pc_final<D, UPDATE, true>), dim3(PCG_GRID), dim3(EB), 0, st, m->n_rows, e->d_dinv, x, r, p, q, z, pinit,
-                       s, part, flag, fx, pc->d_vbin, pc->d_vfrac, F, sF, Cc, eC);
-  else
-    hipLaunchKernelGGL((k_pc_final<D, UPDATE, false>), dim3(PCG_GRID), dim3(EB), 0, st, m->n_rows, e->d_dinv, x, r, p, q, z, pinit,
-                       s, part, flag, fx, pc->d_vbin, pc->d_vfrac, F, sF, Cc, eC);
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-template <int D, bool UPDATE>
-int pc_step_multi(femo_elast* e, int nc, double* x, double* r, const double* p, const double* q, double* z, double* pinit,
-                  const double* s, double* part, int64_t ps, const int32_t* flag) {
+int pc_step(femo_elast* e, int nc, double* x, double* r, const double* p, const double* q, double* z, double* pinit,
+            const double* s, double* part, int64_t ps, const int32_t* flag) {
   constexpr int GL = D == 2 ? 8 : 64;
   femo_elast_pc* pc = e->pc;
   femo_mesh* m = e->mesh;
@@ -582,23 +482,23 @@ int pc_step_multi(femo_elast* e, int nc, double* x, double* r, const double* p, 
   const PcLat& Cc = P.lat[L > 0 ? L - 1 : 0];
   const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
   const int64_t vs = m->n_rows * D, ls = P.off[P.n_levels] * D;
-  double* gF = pc->d_gm + P.off[L] * D;
-  double* sF = pc->d_em + P.off[L] * D;
-  double* gC = L > 0 ? pc->d_gm + P.off[L - 1] * D : nullptr;
-  const double* eC = L > 0 ? pc->d_em + P.off[L - 1] * D : nullptr;
+  double* gF = pc->d_g + P.off[L] * D;
+  double* sF = pc->d_e + P.off[L] * D;
+  double* gC = L > 0 ? pc->d_g + P.off[L - 1] * D : nullptr;
+  const double* eC = L > 0 ? pc->d_e + P.off[L - 1] * D : nullptr;
   const unsigned cols = (unsigned)nc;
-  hipLaunchKernelGGL((k_pc_restrict_mesh_multi<D, GL, UPDATE>), dim3(pc_grid(F.nodes * GL), cols), dim3(EB), 0, st, F.nodes,
+  hipLaunchKernelGGL((k_pc_restrict_mesh<D, GL, UPDATE>), dim3(pc_grid(F.nodes * GL), cols), dim3(EB), 0, st, F.nodes,
                      pc->d_rptr, pc->d_rvert, pc->d_rw, r, q, s, fx, flag, gF, vs, ls);
-  hipLaunchKernelGGL((k_pc_lat_restrict_multi<D, UPDATE>), dim3(pc_grid(F.nodes), cols), dim3(EB), 0, st, F, Cc, L > 0 ? 1 : 0,
+  hipLaunchKernelGGL((k_pc_lat_restrict<D, UPDATE>), dim3(pc_grid(F.nodes), cols), dim3(EB), 0, st, F, Cc, L > 0 ? 1 : 0,
                      pc->d_C + P.off[L] * D * D, gF, sF, gC, flag, ls);
   if (L > 0)
-    hipLaunchKernelGGL((k_pc_coarse_multi<D, UPDATE>), dim3(cols), dim3(PC_COARSE_NT), 0, st, P, L - 1, pc->d_C, pc->d_gm,
-                       pc->d_em, flag, ls);
+    hipLaunchKernelGGL((k_pc_coarse<D, UPDATE>), dim3(cols), dim3(PC_COARSE_NT), 0, st, P, L - 1, pc->d_C, pc->d_g,
+                       pc->d_e, flag, ls);
   if (pinit)
-    hipLaunchKernelGGL((k_pc_final_multi<D, UPDATE, true>), dim3(PCG_GRID, cols), dim3(EB), 0, st, m->n_rows, e->d_dinv, x, r, p, q,
+    hipLaunchKernelGGL((k_pc_final<D, UPDATE, true>), dim3(PCG_GRID, cols), dim3(EB), 0, st, m->n_rows, e->d_dinv, x, r, p, q,
                        z, pinit, s, part, flag, fx, pc->d_vbin, pc->d_vfrac, F, sF, Cc, eC, vs, ls, ps);
   else
-    hipLaunchKernelGGL((k_pc_final_multi<D, UPDATE, false>), dim3(PCG_GRID, cols), dim3(EB), 0, st, m->n_rows, e->d_dinv, x, r, p, q,
+    hipLaunchKernelGGL((k_pc_final<D, UPDATE, false>), dim3(PCG_GRID, cols), dim3(EB), 0, st, m->n_rows, e->d_dinv, x, r, p, q,
                        z, pinit, s, part, flag, fx, pc->d_vbin, pc->d_vfrac, F, sF, Cc, eC, vs, ls, ps);
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
@@ -610,7 +510,6 @@ void femo_elast_pc_free(femo_elast* e) {
   femo_elast_pc* pc = e ? e->pc : nullptr;
   if (!pc) return;
   hipFree(pc->d_G); hipFree(pc->d_C); hipFree(pc->d_g); hipFree(pc->d_e); hipFree(pc->d_vbin); hipFree(pc->d_vfrac);
-  hipFree(pc->d_gm); hipFree(pc->d_em);
   hipFree(pc->d_rptr); hipFree(pc->d_rvert); hipFree(pc->d_rw);
   if (pc->ev0) hipEventDestroy(pc->ev0);
   if (pc->ev1) hipEventDestroy(pc->ev1);
@@ -635,32 +534,24 @@ int femo_elast_pc_build(femo_elast* e, const double* rho) {
   return 0;
 }
 
-int femo_elast_pc_step(femo_elast* e, bool update, double* x, double* r, const double* p, const double* q, double* z,
-                       double* pinit, const double* s, double* part, const int32_t* flag) {
-  if (e->d == 2) return update ? pc_step<2, true>(e, x, r, p, q, z, pinit, s, part, flag) : pc_step<2, false>(e, x, r, p, q, z, pinit, s, part, flag);
-  return update ? pc_step<3, true>(e, x, r, p, q, z, pinit, s, part, flag) : pc_step<3, false>(e, x, r, p, q, z, pinit, s, part, flag);
-}
-
-int femo_elast_pc_step_multi(femo_elast* e, bool update, int n_cols, double* x, double* r, const double* p, const double* q,
-                             double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag) {
+int femo_elast_pc_step(femo_elast* e, bool update, int n_cols, double* x, double* r, const double* p, const double* q,
+                       double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag) {
   femo_elast_pc* pc = e->pc;
-  FEMO_REQUIRE(pc && n_cols >= 1 && n_cols <= FEMO_ELAST_MAX_COLS, "femo_elast_pc_step_multi: bad column count %d", n_cols);
-  if (pc->m_cols < n_cols) {
+  FEMO_REQUIRE(pc && n_cols >= 1 && n_cols <= FEMO_ELAST_MAX_COLS, "femo_elast_pc_step: bad column count %d", n_cols);
+  if (pc->cols < n_cols) {                       // the old pair stays until the new one exists
     const int64_t per = pc->P.off[pc->P.n_levels] * e->d;
+    double *g = nullptr, *c = nullptr;
+    if (pc_alloc(&g, per * n_cols) || pc_alloc(&c, per * n_cols)) { hipFree(g); return 1; }
     FEMO_HIP_CHECK(hipStreamSynchronize(e->mesh->ctx->stream));
-    hipFree(pc->d_gm); hipFree(pc->d_em);
-    pc->d_gm = pc->d_em = nullptr;
-    pc->bytes -= 2 * per * pc->m_cols * (int64_t)sizeof(double);
-    pc->m_cols = 0;
-    FEMO_TRY(pc_alloc(&pc->d_gm, per * n_cols));
-    FEMO_TRY(pc_alloc(&pc->d_em, per * n_cols));
-    pc->m_cols = n_cols;
-    pc->bytes += 2 * per * n_cols * (int64_t)sizeof(double);
+    hipFree(pc->d_g); hipFree(pc->d_e);
+    pc->d_g = g; pc->d_e = c;
+    pc->bytes += 2 * per * (n_cols - pc->cols) * (int64_t)sizeof(double);
+    pc->cols = n_cols;
   }
-#define FEMO_PC_STEP_MULTI(D, U) pc_step_multi<D, U>(e, n_cols, x, r, p, q, z, pinit, s, part, part_stride, flag)
-  if (e->d == 2) return update ? FEMO_PC_STEP_MULTI(2, true) : FEMO_PC_STEP_MULTI(2, false);
-  return update ? FEMO_PC_STEP_MULTI(3, true) : FEMO_PC_STEP_MULTI(3, false);
-#undef FEMO_PC_STEP_MULTI
+#define FEMO_PC_STEP(D, U) pc_step<D, U>(e, n_cols, x, r, p, q, z, pinit, s, part, part_stride, flag)
+  if (e->d == 2) return update ? FEMO_PC_STEP(2, true) : FEMO_PC_STEP(2, false);
+  return update ? FEMO_PC_STEP(3, true) : FEMO_PC_STEP(3, false);
+#undef FEMO_PC_STEP
 }
 
 // ===================================================================================================== C-ABI ====
@@ -794,6 +685,7 @@ int femo_elast_pc_setup(femo_elast* e, double spacing_factor) {
   femo_elast_pc_free(e);
   e->pc = pc;
   e->pc_dirty = true;
+  pc->cols = 1;
   pc->bytes = total * (2 * dd + 2 * d) * (int64_t)sizeof(double);
   FEMO_HIP_CHECK(hipMemcpyAsync(pc->d_vbin, vbin.data(), vbin.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
   FEMO_HIP_CHECK(hipMemcpyAsync(pc->d_vfrac, vfrac.data(), vfrac.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -843,7 +735,7 @@ int femo_elast_pc_apply(femo_elast* e, const femo_vec* r, femo_vec* z) {
   FEMO_TRY(femo_elast_pc_ensure(e));
   FEMO_TRY(femo_vec_await(r));
   femo_vec_touch(z);
-  return femo_elast_pc_step(e, false, nullptr, const_cast<double*>(r->d) /* read only without the update */, nullptr, nullptr, z->d, nullptr, e->w_s, e->w_part, e->w_flag);
+  return femo_elast_pc_step(e, false, 1, nullptr, const_cast<double*>(r->d) /* read only without the update */, nullptr, nullptr, z->d, nullptr, e->w_s, e->w_part, e->w_pstride, e->w_flag);
 }
 
 }  // extern "C"

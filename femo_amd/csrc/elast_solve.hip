@@ -1,0 +1,404 @@
+// Block product and PCG of the SIMP elasticity, for one right-hand side or several load cases in one batched loop (C-ABI in
+// include/femo_hip.h: femo_elast_solve, femo_elast_solve_multi, femo_elast_apply_multi; femo_elast_spmv serves the rest).
+//
+// Layout.  L columns (1 <= L <= FEMO_ELAST_MAX_COLS) one after the other in one vector: column l starts at l * n_dof and
+// keeps the blocked layout d * vertex + component.  K(rho), the fixed set and the preconditioner are shared.  The
+// single-column entry points are this loop with L = 1.
+//
+// An iteration issues these launches, each with a column dimension in its grid:
+//
+//   q_l = A p_l, partial p_l.q_l       k_elast_spmv_multi   up to MC columns per thread: a d x d block, its column index
+//                                                           and the fixed bytes are read once for them; pass blockIdx.y
+//                                                           covers columns MC * blockIdx.y ...  One column runs the MC = 1
+//                                                           instantiation, several run MultiChunk<D>::value
+//   alpha_l                            k_pcg_scalar         one workgroup per column
+//   x, r update, z_l = M^-1 r_l        k_pcg_precond, or the four launches of femo_elast_pc_step
+//   beta_l, convergence of column l    k_pcg_scalar
+//   p_l = z_l + beta_l p_l             k_pcg_p
+//
+// Column l owns s[] at s + l * EMS_STRIDE, flag[] at flag + l * EMF_STRIDE and its own slab of partials.  Once flag[0] of
+// a column is set (converged, breakdown, or the stopping test met at iteration 0) every block of that column returns
+// early, so its x, r and p are never written again and a stale alpha does no harm.  Within a column every sum runs in the
+// same order whatever L is: no float atomics, the same bits on every call.
+#include "elast_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace {
+
+constexpr int EMC = FEMO_ELAST_MAX_COLS;
+
+// columns per thread of the batched product
+template <int D>
+struct MultiChunk { static constexpr int value = 4; };
+
+inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
+  int64_t g = (n + EB - 1) / EB;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (unsigned)g;
+}
+
+// y_l = a Op x_l + b f_l (+ partial dot(x_l, y_l) per block and column when part != null) for the columns
+// c0 = MC * blockIdx.y ... min(c0 + MC, n_cols) - 1.  done != null: a column whose done[l * EMF_STRIDE] is set is skipped.
+// vs: column stride of the vectors, ps: of the partials.
+template <int D, bool MASKED, int MC>
+__global__ __launch_bounds__(EB) void k_elast_spmv_multi(
+    int64_t n_rows, const int64_t* __restrict__ mptr, const int32_t* __restrict__ cols, const int32_t* __restrict__ rowlen,
+    const double* __restrict__ vals, const double* __restrict__ diag, const uint8_t* __restrict__ fixed, int n_cols, int64_t vs,
+    double a, const double* __restrict__ x, double b, const double* __restrict__ f, double* __restrict__ y,
+    double* __restrict__ part, int64_t ps, const int32_t* __restrict__ done) {
+  constexpr int DD = D * D;
+  __shared__ double lds[EB / 64];
+  const int c0 = (int)blockIdx.y * MC;
+  bool on[MC];          // uniform over the block
+  bool any = false;
+#pragma unroll
+  for (int c = 0; c < MC; ++c) {
+    on[c] = c0 + c < n_cols && !(done && done[(c0 + c) * EMF_STRIDE]);
+    any = any || on[c];
+  }
+  if (!any) return;
+  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
+  double dotv[MC];
+#pragma unroll
+  for (int c = 0; c < MC; ++c) dotv[c] = 0.0;
+  if (row < n_rows) {
+    const int64_t slice = row >> 6;
+    const int lane = (int)(row & 63);
+    const int64_t mb = mptr[slice];
+    const int len = rowlen[row];
+    double acc[MC][D], xo[MC][D];
+    uint8_t fo[D];
+#pragma unroll
+    for (int r = 0; r < D; ++r) fo[r] = MASKED ? fixed[row * D + r] : 0;
+#pragma unroll
+    for (int c = 0; c < MC; ++c)
+#pragma unroll
+      for (int r = 0; r < D; ++r) xo[c][r] = on[c] ? x[(c0 + c) * vs + row * D + r] : 0.0;
+    {
+      double dg[DD];
+#pragma unroll
+      for (int q = 0; q < DD; ++q) dg[q] = diag[row * DD + q];
+#pragma unroll
+      for (int c = 0; c < MC; ++c)
+#pragma unroll
+        for (int r = 0; r < D; ++r) {
+          double s = 0.0;
+#pragma unroll
+          for (int cc = 0; cc < D; ++cc) s += dg[r * D + cc] * (fo[cc] ? 0.0 : xo[c][cc]);
+          acc[c][r] = s;
+        }
+    }
+    for (int k = 0; k < len; ++k) {
+      const int64_t e = femo_sell_index(mb, k, lane);
+      const int64_t col = cols[e];
+      double blk[DD];
+#pragma unroll
+      for (int q = 0; q < DD; ++q) blk[q] = vals[e * DD + q];
+      uint8_t fc[D];
+#pragma unroll
+      for (int cc = 0; cc < D; ++cc) fc[cc] = MASKED ? fixed[col * D + cc] : 0;
+#pragma unroll
+      for (int c = 0; c < MC; ++c) {
+        if (!on[c]) continue;
+        double xc[D];
+#pragma unroll
+        for (int cc = 0; cc < D; ++cc) {
+          xc[cc] = x[(c0 + c) * vs + col * D + cc];
+          if (MASKED && fc[cc]) xc[cc] = 0.0;
+        }
+#pragma unroll
+        for (int r = 0; r < D; ++r)
+#pragma unroll
+          for (int cc = 0; cc < D; ++cc) acc[c][r] += blk[r * D + cc] * xc[cc];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+      if (!on[c]) continue;
+#pragma unroll
+      for (int r = 0; r < D; ++r) {
+        double o = MASKED && fo[r] ? xo[c][r] : acc[c][r];
+        o = a * o;
+        if (f) o += b * f[(c0 + c) * vs + row * D + r];
+        y[(c0 + c) * vs + row * D + r] = o;
+        dotv[c] += xo[c][r] * o;
+      }
+    }
+  }
+  if (part) {
+#pragma unroll
+    for (int c = 0; c < MC; ++c) {
+      if (!on[c]) continue;
+      const double s = femo_block_sum<EB>(dotv[c], lds);
+      if (threadIdx.x == 0) part[(c0 + c) * ps + blockIdx.x] = s;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ PCG ----
+// Device scalars s[] and flag[]: elast_internal.h.  blockIdx.y (k_pcg_scalar: blockIdx.x) is the column.
+__global__ void k_pcg_start_x(int64_t n, int zero_guess, const uint8_t* __restrict__ fixed, const double* __restrict__ b,
+                              double* __restrict__ x) {
+  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (i >= n) return;
+  b += blockIdx.y * n; x += blockIdx.y * n;
+  double v = zero_guess ? 0.0 : x[i];
+  if (fixed && fixed[i]) v = b[i];
+  x[i] = v;
+}
+
+// z = Dinv r (block), optional x += alpha p, r -= alpha q first; partial r.z per block; INIT: p = z as well
+template <int D, bool UPDATE, bool INIT>
+__global__ __launch_bounds__(EB) void k_pcg_precond(int64_t n_rows, const double* __restrict__ dinv, double* __restrict__ x,
+                                                    double* __restrict__ r, const double* __restrict__ p,
+                                                    const double* __restrict__ q, double* __restrict__ z,
+                                                    double* __restrict__ pinit, const double* __restrict__ s,
+                                                    double* __restrict__ part, int64_t ps, const int32_t* __restrict__ flag) {
+  constexpr int DD = D * D;
+  __shared__ double lds[EB / 64];
+  flag += blockIdx.y * EMF_STRIDE;
+  s += blockIdx.y * EMS_STRIDE;
+  if (UPDATE && flag[0]) return;
+  const int64_t colv = (int64_t)blockIdx.y * n_rows * D;
+  x += colv; r += colv; p += colv; q += colv; z += colv; part += blockIdx.y * ps;
+  if (INIT) pinit += colv;
+  double dotv = 0.0;
+  const double alpha = UPDATE ? s[S_ALPHA] : 0.0;
+  for (int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x; row < n_rows; row += (int64_t)gridDim.x * EB) {
+    double rr[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const int64_t o = row * D + i;
+      double ri = r[o];
+      if (UPDATE) {
+        x[o] += alpha * p[o];
+        ri -= alpha * q[o];
+        r[o] = ri;
+      }
+      rr[i] = ri;
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      double zi = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) zi += dinv[row * DD + i * D + k] * rr[k];
+      z[row * D + i] = zi;
+      if (INIT) pinit[row * D + i] = zi;
+      dotv += rr[i] * zi;
+    }
+  }
+  const double t = femo_block_sum<EB>(dotv, lds);
+  if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// mode 0: initial rz.  mode 1: alpha = rz / pq.  mode 2: rz' -> beta, convergence.  One workgroup per column.
+__global__ __launch_bounds__(1024) void k_pcg_scalar(int mode, const double* __restrict__ part, int64_t ps, int np,
+                                                     double rtol2, double atol2, int max_it, double* __restrict__ s,
+                                                     int32_t* __restrict__ flag) {
+  __shared__ double lds[16];
+  part += blockIdx.x * ps;
+  s += blockIdx.x * EMS_STRIDE;
+  flag += blockIdx.x * EMF_STRIDE;
+  if (mode != 0 && flag[0]) return;
+  const double v = femo_fold_partials<1024>(part, np, lds);
+  if (threadIdx.x != 0) return;
+  if (mode == 0) {
+    s[S_RZ] = v; s[S_RZ0] = v;
+    const double tol2 = fmax(rtol2 * v, atol2);
+    s[S_TOL2] = tol2;
+    flag[0] = 0; flag[1] = 0; flag[2] = 0; flag[3] = 0;
+    if (!(v == v)) { flag[0] = 1; flag[2] = 1; }
+    else if (v <= tol2) { flag[0] = 1; flag[3] = 1; }
+  } else if (mode == 1) {
+    if (!(v > 0.0) || !(v == v)) { flag[0] = 1; flag[2] = 1; return; }
+    s[S_ALPHA] = s[S_RZ] / v;
+  } else {
+    flag[1] += 1;
+    if (!(v == v)) { flag[0] = 1; flag[2] = 1; return; }
+    s[S_BETA] = v / s[S_RZ];
+    s[S_RZ] = v;
+    if (v <= s[S_TOL2]) { flag[0] = 1; flag[3] = 1; }
+    else if (flag[1] >= max_it) flag[0] = 1;
+  }
+}
+
+__global__ void k_pcg_p(int64_t n, const double* __restrict__ z, double* __restrict__ p, const double* __restrict__ s,
+                        const int32_t* __restrict__ flag) {
+  if (flag[blockIdx.y * EMF_STRIDE]) return;
+  const double beta = s[blockIdx.y * EMS_STRIDE + S_BETA];
+  z += blockIdx.y * n; p += blockIdx.y * n;
+  for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) p[i] = z[i] + beta * p[i];
+}
+
+template <typename T>
+int dalloc(T** p, int64_t n) {
+  FEMO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), (size_t)std::max<int64_t>(n, 1) * sizeof(T)));
+  return 0;
+}
+
+template <int D, bool MASKED, int MC>
+void spmv_launch(femo_elast* e, int nc, double a, const double* x, double b, const double* f, double* y, double* part,
+                 int64_t ps, const int32_t* done) {
+  femo_mesh* m = e->mesh;
+  hipLaunchKernelGGL((k_elast_spmv_multi<D, MASKED, MC>), dim3(grid_of(m->n_rows), (unsigned)((nc + MC - 1) / MC)), dim3(EB), 0,
+                     m->ctx->stream, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_fixed, nc,
+                     m->n_rows * D, a, x, b, f, y, part, ps, done);
+}
+
+// one column: the MC = 1 instantiation, which carries no accumulators of absent columns
+template <int D, bool MASKED>
+void spmv_chunk(femo_elast* e, int nc, double a, const double* x, double b, const double* f, double* y, double* part,
+                int64_t ps, const int32_t* done) {
+  if (nc == 1) spmv_launch<D, MASKED, 1>(e, nc, a, x, b, f, y, part, ps, done);
+  else spmv_launch<D, MASKED, MultiChunk<D>::value>(e, nc, a, x, b, f, y, part, ps, done);
+}
+
+// the PCG of femo_elast_solve (one column) and femo_elast_solve_multi, which have checked their arguments; who: the entry
+// point, for the error texts.  info: n_cols records, or null.
+int pcg_solve(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
+              const char* who) {
+  femo_mesh* m = e->mesh;
+  const int64_t n = m->n_vert * e->d;
+  const bool ml = opts->pc == FEMO_ELAST_PC_MULTILEVEL;
+  FEMO_REQUIRE(!ml || e->pc, "%s: pc = multilevel without femo_elast_pc_setup", who);
+  FEMO_TRY(femo_vec_await(b));
+  femo_vec_touch(x);
+  hipStream_t st = m->ctx->stream;
+  const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
+  if (ml) FEMO_TRY(femo_elast_pc_ensure(e));
+  FEMO_TRY(femo_elast_work_reserve(e, n_cols, who));
+  const int check = opts->check_every > 0 ? opts->check_every : (ml ? 8 : 32);
+  const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
+  const double rtol2 = opts->rtol * opts->rtol, atol2 = opts->atol * opts->atol;
+  const int nps = (int)grid_of(m->n_rows);
+  const int64_t ps = e->w_pstride;
+  const unsigned L = (unsigned)n_cols, gp = (unsigned)PCG_GRID;
+  hipEvent_t e0 = m->ctx->ev0, e1 = m->ctx->ev1;
+  FEMO_HIP_CHECK(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(k_pcg_start_x, dim3(grid_of(n), L), dim3(EB), 0, st, n, opts->zero_guess, fx, b->d, x->d);
+  FEMO_TRY(femo_elast_spmv(e, fx != nullptr, n_cols, -1.0, x->d, 1.0, b->d, e->w_r, nullptr, 0, nullptr));    // r = b - A x
+#define FEMO_PRECOND(D, U, I) hipLaunchKernelGGL((k_pcg_precond<D, U, I>), dim3(gp, L), dim3(EB), 0, st, m->n_rows, e->d_dinv, \
+                                                 x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, ps, e->w_flag)
+  if (ml) FEMO_TRY(femo_elast_pc_step(e, false, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, ps, e->w_flag));
+  else if (e->d == 2) FEMO_PRECOND(2, false, true); else FEMO_PRECOND(3, false, true);
+  hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 0, e->w_part, ps, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
+  FEMO_HIP_CHECK(hipGetLastError());
+  int it_issued = 0;
+  for (;;) {
+    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_flag, e->w_flag, (size_t)n_cols * EMF_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FEMO_HIP_CHECK(hipStreamSynchronize(st));
+    bool all_done = true;
+    for (int l = 0; l < n_cols; ++l) all_done = all_done && e->h_flag[l * EMF_STRIDE] != 0;
+    if (all_done || it_issued >= max_it) break;
+    for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) {
+      FEMO_TRY(femo_elast_spmv(e, fx != nullptr, n_cols, 1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, ps, e->w_flag));   // q = A p, p.q
+      hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 1, e->w_part, ps, nps, rtol2, atol2, max_it, e->w_s, e->w_flag);
+      if (ml) FEMO_TRY(femo_elast_pc_step(e, true, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, nullptr, e->w_s, e->w_part, ps, e->w_flag));
+      else if (e->d == 2) FEMO_PRECOND(2, true, false); else FEMO_PRECOND(3, true, false);
+      hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 2, e->w_part, ps, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
+      hipLaunchKernelGGL(k_pcg_p, dim3(gp, L), dim3(EB), 0, st, n, e->w_z, e->w_p, e->w_s, e->w_flag);
+    }
+    FEMO_HIP_CHECK(hipGetLastError());
+  }
+#undef FEMO_PRECOND
+  FEMO_HIP_CHECK(hipEventRecord(e1, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(e->h_s, e->w_s, (size_t)n_cols * EMS_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  if (info) {
+    float ms = 0.0f;
+    const bool timed = hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+    for (int l = 0; l < n_cols; ++l) {
+      const int32_t* fl = e->h_flag + l * EMF_STRIDE;
+      const double* s = e->h_s + l * EMS_STRIDE;
+      femo_solve_info* o = info + l;
+      std::memset(o, 0, sizeof(*o));
+      o->iterations = fl[1];
+      o->converged = fl[2] ? -1 : (fl[3] ? 1 : 0);
+      o->residual_norm = std::sqrt(std::fabs(s[S_RZ]));
+      o->rhs_norm = std::sqrt(std::fabs(s[S_RZ0]));
+      o->pc_residual_norm = o->residual_norm;
+      o->pc_rhs_norm = o->rhs_norm;
+      if (timed) o->solve_ms = ms;
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+
+int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const double* x, double b, const double* f, double* y,
+                    double* part, int64_t part_stride, const int32_t* done) {
+  if (e->d == 2) {
+    if (masked) spmv_chunk<2, true>(e, n_cols, a, x, b, f, y, part, part_stride, done);
+    else spmv_chunk<2, false>(e, n_cols, a, x, b, f, y, part, part_stride, done);
+  } else {
+    if (masked) spmv_chunk<3, true>(e, n_cols, a, x, b, f, y, part, part_stride, done);
+    else spmv_chunk<3, false>(e, n_cols, a, x, b, f, y, part, part_stride, done);
+  }
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who) {
+  if (e->w_cols >= n_cols) return 0;
+  femo_mesh* m = e->mesh;
+  const int64_t n = m->n_vert * e->d, ps = std::max<int64_t>(PCG_GRID, grid_of(m->n_rows));
+  double* w[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // r, z, p, q, part: the old ones stay until all five exist
+  int rc = 0;
+  for (int k = 0; k < 5; ++k) rc |= dalloc(&w[k], (k < 4 ? n : ps) * n_cols);
+  if (rc) {
+    for (double* v : w) hipFree(v);
+    femo_set_error("%s: device allocation failed", who);
+    return 1;
+  }
+  FEMO_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part);
+  e->w_r = w[0]; e->w_z = w[1]; e->w_p = w[2]; e->w_q = w[3]; e->w_part = w[4];
+  e->w_pstride = ps;
+  e->w_cols = n_cols;
+  return 0;
+}
+
+// ===================================================================================================== C-ABI ====
+extern "C" {
+
+int femo_elast_apply_multi(femo_elast* e, int masked, int n_cols, double a, const femo_vec* x, double b, const femo_vec* f,
+                           femo_vec* y) {
+  FEMO_REQUIRE(e && x && y, "null argument");
+  FEMO_REQUIRE(n_cols >= 1 && n_cols <= EMC, "femo_elast_apply_multi: %d columns (1 to %d)", n_cols, EMC);
+  FEMO_REQUIRE(e->assembled, "femo_elast_apply_multi: assemble K first");
+  const int64_t n = e->mesh->n_vert * e->d * n_cols;
+  FEMO_REQUIRE(x->n >= n && y->n >= n && (!f || f->n >= n), "vector size mismatch in femo_elast_apply_multi: %d columns need %lld entries",
+               n_cols, (long long)n);
+  FEMO_REQUIRE(!masked || e->has_fixed, "femo_elast_apply_multi: masked product without a fixed set");
+  FEMO_REQUIRE(x != y, "femo_elast_apply_multi: x and y must differ");
+  FEMO_TRY(femo_vec_await(x));
+  if (f) FEMO_TRY(femo_vec_await(f));
+  femo_vec_touch(y);
+  return femo_elast_spmv(e, masked != 0, n_cols, a, x->d, b, f ? f->d : nullptr, y->d, nullptr, 0, nullptr);
+}
+
+int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info) {
+  FEMO_REQUIRE(e && b && x && opts, "null argument");
+  FEMO_REQUIRE(e->assembled, "femo_elast_solve: assemble K first");
+  const int64_t n = e->mesh->n_vert * e->d;
+  FEMO_REQUIRE(b->n >= n && x->n >= n && b != x, "vector size mismatch in femo_elast_solve");
+  return pcg_solve(e, 1, b, x, opts, info, "femo_elast_solve");
+}
+
+int femo_elast_solve_multi(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts,
+                           femo_solve_info* info) {
+  FEMO_REQUIRE(e && b && x && opts, "null argument");
+  FEMO_REQUIRE(n_cols >= 1 && n_cols <= EMC, "femo_elast_solve_multi: %d columns (1 to %d)", n_cols, EMC);
+  FEMO_REQUIRE(e->assembled, "femo_elast_solve_multi: assemble K first");
+  const int64_t n = e->mesh->n_vert * e->d * n_cols;
+  FEMO_REQUIRE(b->n >= n && x->n >= n && b != x, "vector size mismatch in femo_elast_solve_multi: %d columns need %lld entries",
+               n_cols, (long long)n);
+  return pcg_solve(e, n_cols, b, x, opts, info, "femo_elast_solve_multi");
+}
+
+}  // extern "C"

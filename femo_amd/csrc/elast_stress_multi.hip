@@ -3,7 +3,7 @@
 //
 //   J_l = 1/alpha sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p,     J = sum_l w_l J_l
 //
-// Layout as in elast_multi.hip: L columns (1 <= L <= FEMO_ELAST_MAX_COLS), column l of the state and of dJ/du at l * n_dof.
+// Layout as in elast_solve.hip: L columns (1 <= L <= FEMO_ELAST_MAX_COLS), column l of the state and of dJ/du at l * n_dof.
 // The arithmetic of a column is that of k_elast_stress_cell / k_elast_stress_du (elasticity.hip); what the columns share
 // -- the cell's vertices, the gradients of its barycentric coordinates, its volume and rho^q -- is computed once per cell
 // (cell kernel) and once per cell visit (dJ/du kernel), not once per column.  m, w and the field scales travel as

@@ -107,66 +107,6 @@ __global__ __launch_bounds__(EB) void k_elast_assemble(
   for (int q = 0; q < DD; ++q) dinv[row * DD + q] = Bi[q];
 }
 
-// y = a Op x + b f (+ partial dot(x, y) per block when part != null).  MASKED: identity rows / columns on fixed dofs.
-template <int D, bool MASKED>
-__global__ __launch_bounds__(EB) void k_elast_spmv(
-    int64_t n_rows, const int64_t* __restrict__ mptr, const int32_t* __restrict__ cols, const int32_t* __restrict__ rowlen,
-    const double* __restrict__ vals, const double* __restrict__ diag, const uint8_t* __restrict__ fixed,
-    double a, const double* __restrict__ x, double b, const double* __restrict__ f, double* __restrict__ y,
-    double* __restrict__ part, const int32_t* __restrict__ done) {
-  constexpr int DD = D * D;
-  __shared__ double lds[EB / 64];
-  if (done && *done) return;
-  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
-  double dotv = 0.0;
-  if (row < n_rows) {
-    const int64_t slice = row >> 6;
-    const int lane = (int)(row & 63);
-    const int64_t mb = mptr[slice];
-    const int len = rowlen[row];
-    double acc[D], xo[D];
-    uint8_t fo[D];
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-      xo[r] = x[row * D + r];
-      fo[r] = MASKED ? fixed[row * D + r] : 0;
-    }
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-      double s = 0.0;
-#pragma unroll
-      for (int cc = 0; cc < D; ++cc) s += diag[row * DD + r * D + cc] * (fo[cc] ? 0.0 : xo[cc]);
-      acc[r] = s;
-    }
-    for (int k = 0; k < len; ++k) {
-      const int64_t e = femo_sell_index(mb, k, lane);
-      const int64_t col = cols[e];
-      double xc[D];
-#pragma unroll
-      for (int cc = 0; cc < D; ++cc) {
-        xc[cc] = x[col * D + cc];
-        if (MASKED && fixed[col * D + cc]) xc[cc] = 0.0;
-      }
-#pragma unroll
-      for (int r = 0; r < D; ++r)
-#pragma unroll
-        for (int cc = 0; cc < D; ++cc) acc[r] += vals[e * DD + r * D + cc] * xc[cc];
-    }
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-      double o = MASKED && fo[r] ? xo[r] : acc[r];
-      o = a * o;
-      if (f) o += b * f[row * D + r];
-      y[row * D + r] = o;
-      dotv += xo[r] * o;
-    }
-  }
-  if (part) {
-    const double s = femo_block_sum<EB>(dotv, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- dR/drho ----
 // rev: y_c (+)= C'(rho_c) |T| (lam div w div u + 2 mu eps(w) : eps(u)) = C'(rho_c) w_c^T K0_c u_c
 template <int D>
@@ -407,91 +347,6 @@ __global__ void k_elast_export(int64_t n_rows, const int64_t* __restrict__ mptr,
   }
 }
 
-// ------------------------------------------------------------------------------------------------ PCG ----
-// Device scalars s[] and flag[]: elast_internal.h
-
-__global__ void k_pcg_start_x(int64_t n, int zero_guess, const uint8_t* __restrict__ fixed, const double* __restrict__ b,
-                              double* __restrict__ x) {
-  const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
-  if (i >= n) return;
-  double v = zero_guess ? 0.0 : x[i];
-  if (fixed && fixed[i]) v = b[i];
-  x[i] = v;
-}
-
-// z = Dinv r (block), optional x += alpha p, r -= alpha q first; partial r.z per block; INIT: p = z as well
-template <int D, bool UPDATE, bool INIT>
-__global__ __launch_bounds__(EB) void k_pcg_precond(int64_t n_rows, const double* __restrict__ dinv, double* __restrict__ x,
-                                                    double* __restrict__ r, const double* __restrict__ p,
-                                                    const double* __restrict__ q, double* __restrict__ z,
-                                                    double* __restrict__ pinit, const double* __restrict__ s,
-                                                    double* __restrict__ part, const int32_t* __restrict__ flag) {
-  constexpr int DD = D * D;
-  __shared__ double lds[EB / 64];
-  if (UPDATE && flag[0]) return;
-  double dotv = 0.0;
-  const double alpha = UPDATE ? s[S_ALPHA] : 0.0;
-  for (int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x; row < n_rows; row += (int64_t)gridDim.x * EB) {
-    double rr[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      double ri = r[row * D + i];
-      if (UPDATE) {
-        x[row * D + i] += alpha * p[row * D + i];
-        ri -= alpha * q[row * D + i];
-        r[row * D + i] = ri;
-      }
-      rr[i] = ri;
-    }
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      double zi = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) zi += dinv[row * DD + i * D + k] * rr[k];
-      z[row * D + i] = zi;
-      if (INIT) pinit[row * D + i] = zi;
-      dotv += rr[i] * zi;
-    }
-  }
-  const double t = femo_block_sum<EB>(dotv, lds);
-  if (threadIdx.x == 0) part[blockIdx.x] = t;
-}
-
-// mode 0: initial rz.  mode 1: alpha = rz / pq.  mode 2: rz' -> beta, convergence.
-__global__ __launch_bounds__(1024) void k_pcg_scalar(int mode, const double* __restrict__ part, int np, double rtol2,
-                                                     double atol2, int max_it, double* __restrict__ s,
-                                                     int32_t* __restrict__ flag) {
-  __shared__ double lds[16];
-  if (mode != 0 && flag[0]) return;
-  const double v = femo_fold_partials<1024>(part, np, lds);
-  if (threadIdx.x != 0) return;
-  if (mode == 0) {
-    s[S_RZ] = v; s[S_RZ0] = v;
-    const double tol2 = fmax(rtol2 * v, atol2);
-    s[S_TOL2] = tol2;
-    flag[0] = 0; flag[1] = 0; flag[2] = 0; flag[3] = 0;
-    if (!(v == v)) { flag[0] = 1; flag[2] = 1; }
-    else if (v <= tol2) { flag[0] = 1; flag[3] = 1; }
-  } else if (mode == 1) {
-    if (!(v > 0.0) || !(v == v)) { flag[0] = 1; flag[2] = 1; return; }
-    s[S_ALPHA] = s[S_RZ] / v;
-  } else {
-    flag[1] += 1;
-    if (!(v == v)) { flag[0] = 1; flag[2] = 1; return; }
-    s[S_BETA] = v / s[S_RZ];
-    s[S_RZ] = v;
-    if (v <= s[S_TOL2]) { flag[0] = 1; flag[3] = 1; }
-    else if (flag[1] >= max_it) flag[0] = 1;
-  }
-}
-
-__global__ void k_pcg_p(int64_t n, const double* __restrict__ z, double* __restrict__ p, const double* __restrict__ s,
-                        const int32_t* __restrict__ flag) {
-  if (flag[0]) return;
-  const double beta = s[S_BETA];
-  for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) p[i] = z[i] + beta * p[i];
-}
-
 // --------------------------------------------------------------------------------------------- filter ----
 struct Grid {
   double lo[3];
@@ -689,17 +544,16 @@ int femo_elast_create(femo_mesh* m, double E, double nu, femo_elast** out) {
   e->d = m->tdim;
   e->lam0 = E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu));
   e->mu0 = E / (2.0 * (1.0 + nu));
-  const int64_t dd = (int64_t)e->d * e->d, n = m->n_vert * e->d;
+  const int64_t dd = (int64_t)e->d * e->d;
   int rc = 0;
   rc |= dalloc(&e->d_vals, m->sell_entries * dd);
   rc |= dalloc(&e->d_diag, m->n_vert * dd);
   rc |= dalloc(&e->d_dinv, m->n_vert * dd);
-  rc |= dalloc(&e->w_r, n); rc |= dalloc(&e->w_z, n); rc |= dalloc(&e->w_p, n); rc |= dalloc(&e->w_q, n);
-  rc |= dalloc(&e->w_part, std::max<int64_t>(PCG_GRID, (m->n_vert + EB - 1) / EB));
-  rc |= dalloc(&e->w_s, 8);
-  rc |= dalloc(&e->w_flag, 4);
-  if (rc == 0 && hipHostMalloc(reinterpret_cast<void**>(&e->h_flag), 4 * sizeof(int32_t)) != hipSuccess) rc = 1;
-  if (rc == 0 && hipHostMalloc(reinterpret_cast<void**>(&e->h_s), 8 * sizeof(double)) != hipSuccess) rc = 1;
+  rc |= femo_elast_work_reserve(e, 1, "femo_elast_create");
+  rc |= dalloc(&e->w_s, (int64_t)EMS_STRIDE * FEMO_ELAST_MAX_COLS);
+  rc |= dalloc(&e->w_flag, (int64_t)EMF_STRIDE * FEMO_ELAST_MAX_COLS);
+  if (rc == 0 && hipHostMalloc(reinterpret_cast<void**>(&e->h_flag), EMF_STRIDE * FEMO_ELAST_MAX_COLS * sizeof(int32_t)) != hipSuccess) rc = 1;
+  if (rc == 0 && hipHostMalloc(reinterpret_cast<void**>(&e->h_s), EMS_STRIDE * FEMO_ELAST_MAX_COLS * sizeof(double)) != hipSuccess) rc = 1;
   if (rc) { femo_elast_destroy(e); femo_set_error("femo_elast_create: device allocation failed"); return 1; }
   *out = e;
   return 0;
@@ -708,7 +562,6 @@ int femo_elast_create(femo_mesh* m, double E, double nu, femo_elast** out) {
 int femo_elast_destroy(femo_elast* e) {
   if (!e) return 0;                    // hipFree waits for the device; the mesh may already be gone
   femo_elast_pc_free(e);
-  femo_elast_multi_free(e);
   hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
   hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_spart); hipFree(e->w_smpart);
@@ -799,21 +652,6 @@ int femo_elast_assemble(femo_elast* e, int method, const femo_vec* rho) {
   return 0;
 }
 
-static int elast_spmv(femo_elast* e, bool masked, double a, const double* x, double b, const double* f, double* y,
-                      double* part, const int32_t* done) {
-  femo_mesh* m = e->mesh;
-  hipStream_t st = m->ctx->stream;
-  const unsigned g = grid_of(m->n_rows);
-  const uint8_t* fx = e->d_fixed;
-#define FEMO_ESPMV(D, M) hipLaunchKernelGGL((k_elast_spmv<D, M>), dim3(g), dim3(EB), 0, st, m->n_rows, m->d_mptr, m->d_cols, \
-                                            m->d_rowlen, e->d_vals, e->d_diag, fx, a, x, b, f, y, part, done)
-  if (e->d == 2) { if (masked) FEMO_ESPMV(2, true); else FEMO_ESPMV(2, false); }
-  else { if (masked) FEMO_ESPMV(3, true); else FEMO_ESPMV(3, false); }
-#undef FEMO_ESPMV
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
 int femo_elast_apply(femo_elast* e, int masked, double a, const femo_vec* x, double b, const femo_vec* f, femo_vec* y) {
   FEMO_REQUIRE(e && x && y, "null argument");
   FEMO_REQUIRE(e->assembled, "femo_elast_apply: assemble K first");
@@ -824,7 +662,7 @@ int femo_elast_apply(femo_elast* e, int masked, double a, const femo_vec* x, dou
   FEMO_TRY(femo_vec_await(x));
   if (f) FEMO_TRY(femo_vec_await(f));
   femo_vec_touch(y);
-  return elast_spmv(e, masked != 0, a, x->d, b, f ? f->d : nullptr, y->d, nullptr, nullptr);
+  return femo_elast_spmv(e, masked != 0, 1, a, x->d, b, f ? f->d : nullptr, y->d, nullptr, 0, nullptr);
 }
 
 int femo_elast_load(femo_elast* e, const double* t, femo_vec* F) {
@@ -947,68 +785,6 @@ int femo_elast_von_mises(femo_elast* e, const femo_vec* rho, const femo_vec* u, 
   return stress_cell_launch(e, rho ? rho->d : nullptr, u->d, 1.0, 1.0, q, 1.0, out_cells->d, nullptr, nullptr, 0);
 }
 
-int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info) {
-  FEMO_REQUIRE(e && b && x && opts, "null argument");
-  FEMO_REQUIRE(e->assembled, "femo_elast_solve: assemble K first");
-  femo_mesh* m = e->mesh;
-  const int64_t n = m->n_vert * e->d;
-  FEMO_REQUIRE(b->n >= n && x->n >= n && b != x, "vector size mismatch in femo_elast_solve");
-  FEMO_TRY(femo_vec_await(b));
-  femo_vec_touch(x);
-  hipStream_t st = m->ctx->stream;
-  const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
-  const bool ml = opts->pc == FEMO_ELAST_PC_MULTILEVEL;
-  FEMO_REQUIRE(!ml || e->pc, "femo_elast_solve: pc = multilevel without femo_elast_pc_setup");
-  if (ml) FEMO_TRY(femo_elast_pc_ensure(e));
-  const int check = opts->check_every > 0 ? opts->check_every : (ml ? 8 : 32);
-  const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
-  const double rtol2 = opts->rtol * opts->rtol, atol2 = opts->atol * opts->atol;
-  const unsigned gs = grid_of(m->n_rows);
-  const int nps = (int)gs;
-  hipEvent_t e0 = m->ctx->ev0, e1 = m->ctx->ev1;
-  FEMO_HIP_CHECK(hipEventRecord(e0, st));
-  hipLaunchKernelGGL(k_pcg_start_x, dim3(grid_of(n)), dim3(EB), 0, st, n, opts->zero_guess, fx, b->d, x->d);
-  FEMO_TRY(elast_spmv(e, fx != nullptr, -1.0, x->d, 1.0, b->d, e->w_r, nullptr, nullptr));    // r = b - A x
-  const unsigned gp = (unsigned)PCG_GRID;
-#define FEMO_PRECOND(D, U, I) hipLaunchKernelGGL((k_pcg_precond<D, U, I>), dim3(gp), dim3(EB), 0, st, m->n_rows, e->d_dinv, x->d, \
-                                                 e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, e->w_flag)
-  if (ml) FEMO_TRY(femo_elast_pc_step(e, false, x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, e->w_flag));
-  else if (e->d == 2) FEMO_PRECOND(2, false, true); else FEMO_PRECOND(3, false, true);
-  hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 0, e->w_part, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
-  FEMO_HIP_CHECK(hipGetLastError());
-  int it_issued = 0;
-  for (;;) {
-    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_flag, e->w_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    FEMO_HIP_CHECK(hipStreamSynchronize(st));
-    if (e->h_flag[0] || it_issued >= max_it) break;
-    for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) {
-      FEMO_TRY(elast_spmv(e, fx != nullptr, 1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, e->w_flag));   // q = A p, p.q
-      hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 1, e->w_part, nps, rtol2, atol2, max_it, e->w_s, e->w_flag);
-      if (ml) FEMO_TRY(femo_elast_pc_step(e, true, x->d, e->w_r, e->w_p, e->w_q, e->w_z, nullptr, e->w_s, e->w_part, e->w_flag));
-      else if (e->d == 2) FEMO_PRECOND(2, true, false); else FEMO_PRECOND(3, true, false);
-      hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(1024), 0, st, 2, e->w_part, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
-      hipLaunchKernelGGL(k_pcg_p, dim3(gp), dim3(EB), 0, st, n, e->w_z, e->w_p, e->w_s, e->w_flag);
-    }
-    FEMO_HIP_CHECK(hipGetLastError());
-  }
-#undef FEMO_PRECOND
-  FEMO_HIP_CHECK(hipEventRecord(e1, st));
-  FEMO_HIP_CHECK(hipMemcpyAsync(e->h_s, e->w_s, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-  FEMO_HIP_CHECK(hipStreamSynchronize(st));
-  if (info) {
-    std::memset(info, 0, sizeof(*info));
-    info->iterations = e->h_flag[1];
-    info->converged = e->h_flag[2] ? -1 : (e->h_flag[3] ? 1 : 0);
-    info->residual_norm = std::sqrt(std::fabs(e->h_s[S_RZ]));
-    info->rhs_norm = std::sqrt(std::fabs(e->h_s[S_RZ0]));
-    info->pc_residual_norm = info->residual_norm;
-    info->pc_rhs_norm = info->rhs_norm;
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) info->solve_ms = ms;
-  }
-  return 0;
-}
-
 int femo_elast_export_csr(const femo_elast* e, int64_t* rowptr, int32_t* col, double* val) {
   FEMO_REQUIRE(e && rowptr && col && val, "null argument");
   FEMO_REQUIRE(e->assembled, "femo_elast_export_csr: assemble K first");
@@ -1040,9 +816,9 @@ int femo_elast_bench_spmv(femo_elast* e, const femo_vec* x, femo_vec* y, int rep
   FEMO_REQUIRE(x->n >= n && y->n >= n && x != y, "vector size mismatch in femo_elast_bench_spmv");
   hipStream_t st = e->mesh->ctx->stream;
   femo_vec_touch(y);
-  FEMO_TRY(elast_spmv(e, false, 1.0, x->d, 0.0, nullptr, y->d, nullptr, nullptr));     // warm-up
+  FEMO_TRY(femo_elast_spmv(e, false, 1, 1.0, x->d, 0.0, nullptr, y->d, nullptr, 0, nullptr));     // warm-up
   FEMO_HIP_CHECK(hipEventRecord(e->mesh->ctx->ev0, st));
-  for (int k = 0; k < reps; ++k) FEMO_TRY(elast_spmv(e, false, 1.0, x->d, 0.0, nullptr, y->d, nullptr, nullptr));
+  for (int k = 0; k < reps; ++k) FEMO_TRY(femo_elast_spmv(e, false, 1, 1.0, x->d, 0.0, nullptr, y->d, nullptr, 0, nullptr));
   FEMO_HIP_CHECK(hipEventRecord(e->mesh->ctx->ev1, st));
   FEMO_HIP_CHECK(hipEventSynchronize(e->mesh->ctx->ev1));
   float t = 0.0f;

@@ -1,5 +1,6 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
-handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip).
+handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
+product and PCG in csrc/elast_solve.hip).
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
 own assembly and solves, so `FEA.add_input / add_state / add_output`, `StateOperation`, `OutputOperation` and `FEAModel`
@@ -18,7 +19,7 @@ are used unchanged.
   MultiLoadElasticityResidual, MultiLoadCompliance
                        L load cases on one K(rho): the state is a Function(LoadCaseSpace(V, L)), column l solves
                        K(rho) u_l = F_l, and J = sum_l w_l F_l . u_l.  Every solve of the cycle -- state, adjoint, forward
-                       mode -- is one batched PCG over all columns (csrc/elast_multi.hip)
+                       mode -- is one batched PCG over all columns (csrc/elast_solve.hip)
   MultiLoadPnormStress J = sum_l w_l J_l with one aggregate J_l = (1/alpha) sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p per
                        load case of a LoadCaseSpace state: the values, dJ/du (column l = w_l dJ_l/du_l) and dJ/drho of all
                        load cases in one pass over the mesh (csrc/elast_stress_multi.hip).  Its adjoint is one batched PCG
@@ -148,21 +149,25 @@ class DeviceElasticity:
         check(self.lib.femo_elast_pc_apply(self.handle, r.handle, z.handle))
         return z
 
-    def solve(self, b: Vec, x: Vec, rtol: float = 1e-15, atol: float = 0.0, max_it: int = 1_000_000,
-              check_every: Optional[int] = None, zero_guess: bool = True, pc: str = "jacobi") -> _lib.SolveInfo:
-        """PCG; ``pc`` = "jacobi" or "multilevel" (needs `pc_setup`).  Polls every 64 iterations with Jacobi, and every 8
-        (the library's default) with the multilevel preconditioner, unless ``check_every`` says otherwise."""
+    @staticmethod
+    def _solver_opts(rtol, atol, max_it, check_every, zero_guess, pc) -> _lib.SolverOpts:
         if pc not in PRECONDITIONERS:
             raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
         if check_every is None:
             check_every = 64 if pc == "jacobi" else 0
-        opts = _lib.SolverOpts(rtol=float(rtol), atol=float(atol), max_it=int(max_it), zero_guess=int(bool(zero_guess)),
+        return _lib.SolverOpts(rtol=float(rtol), atol=float(atol), max_it=int(max_it), zero_guess=int(bool(zero_guess)),
                                check_every=int(check_every), pc=PRECONDITIONERS[pc], atol_pc=0.0)
+
+    def solve(self, b: Vec, x: Vec, rtol: float = 1e-15, atol: float = 0.0, max_it: int = 1_000_000,
+              check_every: Optional[int] = None, zero_guess: bool = True, pc: str = "jacobi") -> _lib.SolveInfo:
+        """PCG; ``pc`` = "jacobi" or "multilevel" (needs `pc_setup`).  Polls every 64 iterations with Jacobi, and every 8
+        (the library's default) with the multilevel preconditioner, unless ``check_every`` says otherwise."""
+        opts = self._solver_opts(rtol, atol, max_it, check_every, zero_guess, pc)
         info = _lib.SolveInfo()
         check(self.lib.femo_elast_solve(self.handle, b.handle, x.handle, C.byref(opts), C.byref(info)))
         return info
 
-    # ---- several load cases in one vector: column l at l * n_dof (csrc/elast_multi.hip) ----
+    # ---- several load cases in one vector: column l at l * n_dof (csrc/elast_solve.hip) ----
     def _cols(self, n_cols: int, *vecs: Vec) -> int:
         n_cols = int(n_cols)
         for v in vecs:
@@ -181,12 +186,7 @@ class DeviceElasticity:
                     check_every: Optional[int] = None, zero_guess: bool = True, pc: str = "jacobi") -> list:
         """`solve` for ``n_cols`` right-hand sides in one batched PCG; one `SolveInfo` per column (``solve_ms`` is that of the
         whole batched solve in each).  A column that has converged is frozen while the others go on."""
-        if pc not in PRECONDITIONERS:
-            raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
-        if check_every is None:
-            check_every = 64 if pc == "jacobi" else 0
-        opts = _lib.SolverOpts(rtol=float(rtol), atol=float(atol), max_it=int(max_it), zero_guess=int(bool(zero_guess)),
-                               check_every=int(check_every), pc=PRECONDITIONERS[pc], atol_pc=0.0)
+        opts = self._solver_opts(rtol, atol, max_it, check_every, zero_guess, pc)
         info = (_lib.SolveInfo * _lib.ELAST_MAX_COLS)()
         check(self.lib.femo_elast_solve_multi(self.handle, self._cols(n_cols, b, x), b.handle, x.handle, C.byref(opts), info))
         return [info[l] for l in range(int(n_cols))]

@@ -635,7 +635,7 @@ int femo_elast_von_mises(femo_elast* e, const femo_vec* rho, const femo_vec* u, 
  * femo_elast_pc_setup was called); every other value is block-Jacobi (M = the diagonal blocks), as before the field was read. */
 enum { FEMO_ELAST_PC_JACOBI = 0, FEMO_ELAST_PC_MULTILEVEL = 1 };
 int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info);
-/* Several load cases at once (csrc/elast_multi.hip).  n_cols columns, 1 <= n_cols <= FEMO_ELAST_MAX_COLS, lie one after
+/* Several load cases at once (csrc/elast_solve.hip).  n_cols columns, 1 <= n_cols <= FEMO_ELAST_MAX_COLS, lie one after
  * the other in ONE femo_vec of length n_cols * n_dof: column l starts at l * n_dof and keeps the blocked layout
  * d * vertex + component.  All columns share K(rho), the fixed set and the preconditioner.                               */
 enum { FEMO_ELAST_MAX_COLS = 8 };

@@ -1,4 +1,4 @@
-"""NumPy / SciPy restatement of the batched multi-load path of the SIMP elasticity (csrc/elast_multi.hip,
+"""NumPy / SciPy restatement of the batched multi-load path of the SIMP elasticity (csrc/elast_solve.hip,
 femo_amd/fea/elasticity.py: MultiLoadElasticityResidual / MultiLoadCompliance), on top of tests/elasticity_ref.py and
 tests/elast_pc_ref.py:
 

@@ -1,6 +1,6 @@
-"""GPU tests of the batched multi-load path of the SIMP elasticity (csrc/elast_multi.hip, the batched step of
-csrc/elast_pc.hip, MultiLoadElasticityResidual / MultiLoadCompliance) against the single-column device path and the
-restatements (tests/elasticity_ref.py, tests/elast_pc_ref.py, tests/elast_multi_ref.py).
+"""GPU tests of the batched multi-load path of the SIMP elasticity (csrc/elast_solve.hip, the step of csrc/elast_pc.hip
+with several columns, MultiLoadElasticityResidual / MultiLoadCompliance) against the one-column launches of the same
+kernels and the restatements (tests/elasticity_ref.py, tests/elast_pc_ref.py, tests/elast_multi_ref.py).
 
 The meshes are small on purpose: less than one wave of rows (rect8x4), the three meshes of the preconditioner tests, and
 two with more than one block of 256 rows (rect24x12: 325 vertices, cube6j: 343), so that the per-column folds of the
@@ -353,6 +353,55 @@ def test_single_column_unchanged(gpu):
         assert after.iterations == before.iterations
         assert np.array_equal(np.array(x1.get()), xb)
         assert dev.pc_info()["builds"] == builds == (1 if pc == "multilevel" else 0)   # built lazily, once, by dev.solve
+
+
+@pytest.mark.parametrize("name", ["square9j", "cube4j"])
+def test_work_vectors_grow(gpu, name):
+    """One set of PCG and lattice work vectors serves every column count: it grows at 3 and at 5 columns, serves 3 again
+    below its capacity, and the one-column solves and preconditioner applications in between keep their bits."""
+    from femo_amd.engine import Vec
+    c = case(name)
+    dev, _ = _device(gpu, name)
+    n = dev.n_dof
+    bytes_setup = dev.pc_plan["bytes"]
+    per = sum(dev.pc_plan["nodes"]) * dev.d
+    b1, x1 = Vec(gpu, n).set(c["B"][1]), Vec(gpu, n)
+    rv, zv = Vec(gpu, n).set(np.random.default_rng(11).standard_normal(n)), Vec(gpu, n)
+    bv, xv = Vec(gpu, 5 * n).set(c["B"].ravel()), Vec(gpu, 5 * n)
+    PCS = ("jacobi", "multilevel")
+
+    def single():
+        out = []
+        for pc in PCS:
+            i = dev.solve(b1, x1, rtol=1e-15, pc=pc)
+            assert i.converged == 1
+            out.append((np.array(x1.get()), i.iterations))
+        return out
+
+    def apply():
+        return np.array(dev.pc_apply(rv, zv).get())
+
+    def multi(L):
+        out = []
+        for pc in PCS:
+            infos = dev.solve_multi(L, bv, xv, rtol=1e-15, pc=pc)
+            assert all(i.converged == 1 for i in infos)
+            out.append((np.array(xv.get())[:L * n].reshape(L, n), [i.iterations for i in infos]))
+        return out
+
+    def same(a, b):
+        return all(np.array_equal(xa, xb) and ia == ib for (xa, ia), (xb, ib) in zip(a, b))
+
+    s1 = single()
+    z1 = apply()
+    m3 = multi(3)
+    assert same(single(), s1)
+    multi(5)
+    assert dev.pc_info()["bytes"] == bytes_setup + 4 * 2 * per * 8   # five columns of g and e where one was
+    assert same(multi(3), m3)
+    assert same(single(), s1)
+    assert np.array_equal(apply(), z1)
+    assert dev.pc_info()["builds"] == 1
 
 
 @pytest.mark.slow
