@@ -1,6 +1,6 @@
-// Shared by elasticity.hip (assembly, dR/drho, load, stress, export, filter), elast_solve.hip (block product and PCG, for one
-// or several load cases), elast_pc.hip (multilevel preconditioner) and elast_stress_multi.hip (stress over several load
-// cases).  Not part of the ABI.
+// Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product and PCG), elast_pc.hip
+// (multilevel preconditioner) and elast_stress.hip (stress aggregate), each for one or several load cases.  Not part of
+// the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -31,10 +31,8 @@ struct femo_elast {
   int32_t* w_flag = nullptr;
   int32_t* h_flag = nullptr;    // pinned
   double* h_s = nullptr;        // pinned; the stress aggregates come back through it as well
-  // stress aggregate (femo_elast_pnorm_stress): one partial per cell block and the folded value behind them, on first use
-  double* w_spart = nullptr;
-  // the same for several load cases (femo_elast_pnorm_stress_multi): FEMO_ELAST_MAX_COLS slabs of partials, one per column,
-  // and the folded values behind them, on first use
+  // stress aggregate (femo_elast_pnorm_stress, femo_elast_pnorm_stress_multi): FEMO_ELAST_MAX_COLS slabs of partials, one per
+  // column, and the folded values behind them, on first use
   double* w_smpart = nullptr;
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
   femo_elast_pc* pc = nullptr;
@@ -52,6 +50,21 @@ enum { S_RZ = 0, S_ALPHA = 1, S_BETA = 2, S_TOL2 = 3, S_RZ0 = 4 };
 // Column l keeps its own s[] at s + l * EMS_STRIDE and its own flag[] at flag + l * EMF_STRIDE.
 constexpr int EMS_STRIDE = 8, EMF_STRIDE = 4;
 
+// blocks of EB threads for n items
+inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
+  int64_t g = (n + EB - 1) / EB;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (unsigned)g;
+}
+
+// device array of n entries (at least one)
+template <typename T>
+int dalloc(T** p, int64_t n) {
+  FEMO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), (size_t)(n > 1 ? n : 1) * sizeof(T)));
+  return 0;
+}
+
 // elast_pc.hip ------------------------------------------------------------------------------------------------------
 void femo_elast_pc_free(femo_elast* e);
 // Rebuilds the Galerkin blocks when K or the fixed set changed since the last build (no-op otherwise).
@@ -66,10 +79,6 @@ int femo_elast_pc_build(femo_elast* e, const double* rho);
 int femo_elast_pc_step(femo_elast* e, bool update, int n_cols, double* x, double* r, const double* p, const double* q,
                        double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag);
 
-// elasticity.hip ----------------------------------------------------------------------------------------------------
-// The launches of femo_elast_drho on raw pointers (femo_elast_drho_multi loops them over the columns).
-int femo_elast_drho_launch(femo_elast* e, int method, int transpose, const double* rho, const double* u, const double* x,
-                           double* y, int accumulate);
 // elast_solve.hip ---------------------------------------------------------------------------------------------------
 // y_l = a Op x_l + b f_l for n_cols columns (+ partial dot(x_l, y_l) per block and column, part_stride apart, when part !=
 // null).  masked: identity rows / columns on fixed dofs.  done != null: a column whose done[l * EMF_STRIDE] is set is skipped.

@@ -34,13 +34,6 @@ constexpr int EMC = FEMO_ELAST_MAX_COLS;
 template <int D>
 struct MultiChunk { static constexpr int value = 4; };
 
-inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
-  int64_t g = (n + EB - 1) / EB;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (unsigned)g;
-}
-
 // y_l = a Op x_l + b f_l (+ partial dot(x_l, y_l) per block and column when part != null) for the columns
 // c0 = MC * blockIdx.y ... min(c0 + MC, n_cols) - 1.  done != null: a column whose done[l * EMF_STRIDE] is set is skipped.
 // vs: column stride of the vectors, ps: of the partials.
@@ -234,12 +227,6 @@ __global__ void k_pcg_p(int64_t n, const double* __restrict__ z, double* __restr
   for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) p[i] = z[i] + beta * p[i];
 }
 
-template <typename T>
-int dalloc(T** p, int64_t n) {
-  FEMO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), (size_t)std::max<int64_t>(n, 1) * sizeof(T)));
-  return 0;
-}
-
 template <int D, bool MASKED, int MC>
 void spmv_launch(femo_elast* e, int nc, double a, const double* x, double b, const double* f, double* y, double* part,
                  int64_t ps, const int32_t* done) {
@@ -328,6 +315,14 @@ int pcg_solve(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const f
   return 0;
 }
 
+// the product of femo_elast_apply (one column) and femo_elast_apply_multi, which have checked their arguments
+int apply_cols(femo_elast* e, int masked, int n_cols, double a, const femo_vec* x, double b, const femo_vec* f, femo_vec* y) {
+  FEMO_TRY(femo_vec_await(x));
+  if (f) FEMO_TRY(femo_vec_await(f));
+  femo_vec_touch(y);
+  return femo_elast_spmv(e, masked != 0, n_cols, a, x->d, b, f ? f->d : nullptr, y->d, nullptr, 0, nullptr);
+}
+
 }  // namespace
 
 int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const double* x, double b, const double* f, double* y,
@@ -366,6 +361,16 @@ int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who) {
 // ===================================================================================================== C-ABI ====
 extern "C" {
 
+int femo_elast_apply(femo_elast* e, int masked, double a, const femo_vec* x, double b, const femo_vec* f, femo_vec* y) {
+  FEMO_REQUIRE(e && x && y, "null argument");
+  FEMO_REQUIRE(e->assembled, "femo_elast_apply: assemble K first");
+  const int64_t n = e->mesh->n_vert * e->d;
+  FEMO_REQUIRE(x->n >= n && y->n >= n && (!f || f->n >= n), "vector size mismatch in femo_elast_apply");
+  FEMO_REQUIRE(!masked || e->has_fixed, "femo_elast_apply: masked product without a fixed set");
+  FEMO_REQUIRE(x != y, "femo_elast_apply: x and y must differ");
+  return apply_cols(e, masked, 1, a, x, b, f, y);
+}
+
 int femo_elast_apply_multi(femo_elast* e, int masked, int n_cols, double a, const femo_vec* x, double b, const femo_vec* f,
                            femo_vec* y) {
   FEMO_REQUIRE(e && x && y, "null argument");
@@ -376,10 +381,7 @@ int femo_elast_apply_multi(femo_elast* e, int masked, int n_cols, double a, cons
                n_cols, (long long)n);
   FEMO_REQUIRE(!masked || e->has_fixed, "femo_elast_apply_multi: masked product without a fixed set");
   FEMO_REQUIRE(x != y, "femo_elast_apply_multi: x and y must differ");
-  FEMO_TRY(femo_vec_await(x));
-  if (f) FEMO_TRY(femo_vec_await(f));
-  femo_vec_touch(y);
-  return femo_elast_spmv(e, masked != 0, n_cols, a, x->d, b, f ? f->d : nullptr, y->d, nullptr, 0, nullptr);
+  return apply_cols(e, masked, n_cols, a, x, b, f, y);
 }
 
 int femo_elast_solve(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info) {

@@ -5,6 +5,8 @@
 // pattern: SELL entry e holds one d x d block at vals[e * d^2 + r * d + c] (r: row component, c: column component), the
 // diagonal blocks at diag[v * d^2 + ...].  Per block one 4-byte column index serves 8 d^2 bytes of values.
 //
+// The stress aggregate is in elast_stress.hip, the product and the solve in elast_solve.hip.
+//
 // Assembly walks the vertex -> cell incidence like assemble.hip: the thread of row v visits the cells around v and adds
 // C(rho_c) |T_c| B_v^T D_0 B_w to its blocks (v, w).  No float atomics: every block has one writer, the visits come in
 // ascending cell order, and the cell geometry is formed from `conn` in its own vertex order, so block (v, w) and block
@@ -24,13 +26,6 @@ struct femo_filter {
 };
 
 namespace {
-
-inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
-  int64_t g = (n + EB - 1) / EB;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (unsigned)g;
-}
 
 __device__ __forceinline__ int slot_pos(uint32_t slots, int a, int b) {
   const int j = b - (b > a ? 1 : 0);
@@ -191,90 +186,6 @@ __global__ __launch_bounds__(EB) void k_elast_drho_N(
 #pragma unroll
       for (int k = 0; k < D; ++k) sg += mu * (Gu[r][k] + Gu[k][r]) * g[a][k];
       acc[r] += coef * sg;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < D; ++r) y[row * D + r] = accumulate ? y[row * D + r] + acc[r] : acc[r];
-}
-
-// ------------------------------------------------------------------------------------------------ stress ----
-// cell_von_mises<D>: elast_internal.h (shared with elast_stress_multi.hip).
-// One thread per cell, every output optional by null pointer:
-//   field[c] = rho_c^q sigma_vm                                       (the relaxed cell stress)
-//   part[block] = sum over the block of J_c = |T_c| / alpha (m rho_c^q sigma_vm)^p
-//   drho[c] (+)= p q / rho_c J_c
-// rho == null reads as q = 0.  A cell with sigma_vm = 0 gives 0 everywhere (pow(0, p) = 0 for p >= 1; no division by it).
-template <int D>
-__global__ __launch_bounds__(EB) void k_elast_stress_cell(int64_t n_cell, const int32_t* __restrict__ conn,
-                                                          const double* __restrict__ xv, const double* __restrict__ rho,
-                                                          const double* __restrict__ u, double mu, double m, double p, double q,
-                                                          double inv_alpha, double* __restrict__ field,
-                                                          double* __restrict__ part, double* __restrict__ drho, int accumulate) {
-  __shared__ double lds[EB / 64];
-  const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
-  double Jc = 0.0;
-  if (c < n_cell) {
-    int32_t v[D + 1];
-    double pt[D + 1][D], g[D + 1][D], s[D][D], vol;
-    load_cell<D>(conn, xv, c, v, pt);
-    simplex_grads<D>(pt, g, vol);
-    const double vm = cell_von_mises<D>(g, v, u, mu, s);
-    const double r = rho ? rho[c] : 1.0;
-    const double relaxed = (rho && q != 0.0 ? pow(r, q) : 1.0) * vm;
-    if (field) field[c] = relaxed;
-    if (part || drho) {
-      Jc = vm > 0.0 ? vol * inv_alpha * pow(m * relaxed, p) : 0.0;
-      if (drho) {
-        const double d = q != 0.0 && Jc != 0.0 ? p * q / r * Jc : 0.0;
-        drho[c] = accumulate ? drho[c] + d : d;
-      }
-    }
-  }
-  if (part) {
-    const double t = femo_block_sum<EB>(Jc, lds);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
-  }
-}
-
-// dJ/du, the walk of k_elast_drho_N: y_(v, r) (+)= sum over the cells c around v of (tau_c grad phi_v)_r with
-// tau = 2 mu S + lam tr(S) I and S = dJ_c/dsigma = |T| / alpha p (m rho^q)^p sigma_vm^(p-2) 3/2 s.  S is a deviator, so the lam
-// term is zero and tau = 2 mu S; only its d x d block meets grad phi.  Written as w (s / sigma_vm) with
-// w = 3 mu p J_c / sigma_vm = 3 mu p |T| / alpha (m rho^q)^p sigma_vm^(p-1): no negative power of sigma_vm for p >= 1, and the cell is
-// skipped when sigma_vm = 0.  One writer per vertex, cells in ascending order: no float atomics, the same bits every call.
-template <int D>
-__global__ __launch_bounds__(EB) void k_elast_stress_du(
-    int64_t n_rows, const int64_t* __restrict__ vptr, const int32_t* __restrict__ visit_cell, const int32_t* __restrict__ conn,
-    const double* __restrict__ xv, const double* __restrict__ rho, const double* __restrict__ u, double mu, double m, double p,
-    double q, double inv_alpha, double* __restrict__ y, int accumulate) {
-  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
-  if (row >= n_rows) return;
-  const int64_t slice = row >> 6;
-  const int lane = (int)(row & 63);
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
-  double acc[D];
-#pragma unroll
-  for (int r = 0; r < D; ++r) acc[r] = 0.0;
-  for (int k = 0; k < nvis; ++k) {
-    const int32_t ca = visit_cell[vb + (int64_t)k * 64 + lane];
-    if (ca < 0) continue;
-    const int64_t c = ca >> 2;
-    const int a = ca & 3;
-    int32_t v[D + 1];
-    double pt[D + 1][D], g[D + 1][D], s[D][D], vol;
-    load_cell<D>(conn, xv, c, v, pt);
-    simplex_grads<D>(pt, g, vol);
-    const double vm = cell_von_mises<D>(g, v, u, mu, s);
-    if (!(vm > 0.0)) continue;
-    const double mr = m * (q != 0.0 ? pow(rho[c], q) : 1.0);
-    const double w = 3.0 * mu * p * vol * inv_alpha * mr * pow(mr * vm, p - 1.0);
-    if (w == 0.0) continue;
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-      double t = 0.0;
-#pragma unroll
-      for (int j = 0; j < D; ++j) t += (s[r][j] / vm) * g[a][j];
-      acc[r] += w * t;
     }
   }
 #pragma unroll
@@ -503,16 +414,9 @@ __global__ void k_f_apply(int64_t n, const int64_t* __restrict__ rowptr, const i
   y[i] = s;
 }
 
-template <typename T>
-int dalloc(T** p, int64_t n) {
-  FEMO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), (size_t)std::max<int64_t>(n, 1) * sizeof(T)));
-  return 0;
-}
-
-}  // namespace
-
-int femo_elast_drho_launch(femo_elast* e, int method, int transpose, const double* rho, const double* u, const double* x,
-                           double* y, int accumulate) {
+// The launches of dR/drho for one column on raw pointers.
+int drho_launch(femo_elast* e, int method, int transpose, const double* rho, const double* u, const double* x, double* y,
+                int accumulate) {
   femo_mesh* m = e->mesh;
   hipStream_t st = m->ctx->stream;
   if (transpose) {
@@ -529,6 +433,24 @@ int femo_elast_drho_launch(femo_elast* e, int method, int transpose, const doubl
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
 }
+
+// dR/drho of femo_elast_drho (one column) and femo_elast_drho_multi, which have checked their sizes; who: the entry point,
+// for the error texts.  The transpose sums the columns into y in ascending order.
+int drho_cols(femo_elast* e, int method, int transpose, int n_cols, const femo_vec* rho, const femo_vec* u, const femo_vec* x,
+              femo_vec* y, int accumulate, const char* who) {
+  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
+  FEMO_REQUIRE(y != x && y != u && y != rho, "%s: output aliases an input", who);
+  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(x));
+  femo_vec_touch(y);
+  const int64_t n = e->mesh->n_vert * e->d;
+  for (int l = 0; l < n_cols; ++l) {
+    if (transpose) FEMO_TRY(drho_launch(e, method, 1, rho->d, u->d + l * n, x->d + l * n, y->d, accumulate || l > 0));
+    else FEMO_TRY(drho_launch(e, method, 0, rho->d, u->d + l * n, x->d, y->d + l * n, accumulate));
+  }
+  return 0;
+}
+
+}  // namespace
 
 // ===================================================================================================== C-ABI ====
 extern "C" {
@@ -564,7 +486,7 @@ int femo_elast_destroy(femo_elast* e) {
   femo_elast_pc_free(e);
   hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
-  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_spart); hipFree(e->w_smpart);
+  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_smpart);
   if (e->h_flag) hipHostFree(e->h_flag);
   if (e->h_s) hipHostFree(e->h_s);
   delete e;
@@ -652,19 +574,6 @@ int femo_elast_assemble(femo_elast* e, int method, const femo_vec* rho) {
   return 0;
 }
 
-int femo_elast_apply(femo_elast* e, int masked, double a, const femo_vec* x, double b, const femo_vec* f, femo_vec* y) {
-  FEMO_REQUIRE(e && x && y, "null argument");
-  FEMO_REQUIRE(e->assembled, "femo_elast_apply: assemble K first");
-  const int64_t n = e->mesh->n_vert * e->d;
-  FEMO_REQUIRE(x->n >= n && y->n >= n && (!f || f->n >= n), "vector size mismatch in femo_elast_apply");
-  FEMO_REQUIRE(!masked || e->has_fixed, "femo_elast_apply: masked product without a fixed set");
-  FEMO_REQUIRE(x != y, "femo_elast_apply: x and y must differ");
-  FEMO_TRY(femo_vec_await(x));
-  if (f) FEMO_TRY(femo_vec_await(f));
-  femo_vec_touch(y);
-  return femo_elast_spmv(e, masked != 0, 1, a, x->d, b, f ? f->d : nullptr, y->d, nullptr, 0, nullptr);
-}
-
 int femo_elast_load(femo_elast* e, const double* t, femo_vec* F) {
   FEMO_REQUIRE(e && t && F, "null argument");
   femo_mesh* m = e->mesh;
@@ -684,21 +593,16 @@ int femo_elast_load(femo_elast* e, const double* t, femo_vec* F) {
 int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rho, const femo_vec* u, const femo_vec* x,
                     femo_vec* y, int accumulate) {
   FEMO_REQUIRE(e && rho && u && x && y, "null argument");
-  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
   femo_mesh* m = e->mesh;
   const int64_t n = m->n_vert * e->d;
   FEMO_REQUIRE(rho->n >= m->n_cell && u->n >= n, "vector size mismatch in femo_elast_drho");
   FEMO_REQUIRE(transpose ? (x->n >= n && y->n >= m->n_cell) : (x->n >= m->n_cell && y->n >= n), "vector size mismatch in femo_elast_drho");
-  FEMO_REQUIRE(y != x && y != u && y != rho, "femo_elast_drho: output aliases an input");
-  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(x));
-  femo_vec_touch(y);
-  return femo_elast_drho_launch(e, method, transpose, rho->d, u->d, x->d, y->d, accumulate);
+  return drho_cols(e, method, transpose, 1, rho, u, x, y, accumulate, "femo_elast_drho");
 }
 
 int femo_elast_drho_multi(femo_elast* e, int method, int transpose, int n_cols, const femo_vec* rho, const femo_vec* u,
                           const femo_vec* x, femo_vec* y, int accumulate) {
   FEMO_REQUIRE(e && rho && u && x && y, "null argument");
-  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
   FEMO_REQUIRE(n_cols >= 1 && n_cols <= FEMO_ELAST_MAX_COLS, "femo_elast_drho_multi: %d columns (1 to %d)", n_cols,
                FEMO_ELAST_MAX_COLS);
   femo_mesh* m = e->mesh;
@@ -706,83 +610,7 @@ int femo_elast_drho_multi(femo_elast* e, int method, int transpose, int n_cols, 
   FEMO_REQUIRE(rho->n >= m->n_cell && u->n >= nl, "vector size mismatch in femo_elast_drho_multi");
   FEMO_REQUIRE(transpose ? (x->n >= nl && y->n >= m->n_cell) : (x->n >= m->n_cell && y->n >= nl),
                "vector size mismatch in femo_elast_drho_multi");
-  FEMO_REQUIRE(y != x && y != u && y != rho, "femo_elast_drho_multi: output aliases an input");
-  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(x));
-  femo_vec_touch(y);
-  for (int l = 0; l < n_cols; ++l) {
-    if (transpose) FEMO_TRY(femo_elast_drho_launch(e, method, 1, rho->d, u->d + l * n, x->d + l * n, y->d, accumulate || l > 0));
-    else FEMO_TRY(femo_elast_drho_launch(e, method, 0, rho->d, u->d + l * n, x->d, y->d + l * n, accumulate));
-  }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ stress ----
-static int stress_cell_launch(femo_elast* e, const double* rho, const double* u, double m, double p, double q, double inv_alpha,
-                              double* field, double* part, double* drho, int accumulate) {
-  femo_mesh* mh = e->mesh;
-  const unsigned g = grid_of(mh->n_cell);
-  FEMO_REQUIRE((int64_t)g * EB >= mh->n_cell, "too many cells for one launch");
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_elast_stress_cell<2>, dim3(g), dim3(EB), 0, mh->ctx->stream, mh->n_cell, mh->d_conn, mh->d_x, rho, u,
-                       e->mu0, m, p, q, inv_alpha, field, part, drho, accumulate);
-  else
-    hipLaunchKernelGGL(k_elast_stress_cell<3>, dim3(g), dim3(EB), 0, mh->ctx->stream, mh->n_cell, mh->d_conn, mh->d_x, rho, u,
-                       e->mu0, m, p, q, inv_alpha, field, part, drho, accumulate);
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-int femo_elast_pnorm_stress(femo_elast* e, const femo_vec* rho, const femo_vec* u, double m, double p, double q, double alpha,
-                            double* value, femo_vec* grad_u, femo_vec* grad_rho, int accumulate) {
-  FEMO_REQUIRE(e && rho && u, "null argument");
-  femo_mesh* mh = e->mesh;
-  const int64_t n = mh->n_vert * e->d;
-  FEMO_REQUIRE(rho->n >= mh->n_cell && u->n >= n && (!grad_u || grad_u->n >= n) && (!grad_rho || grad_rho->n >= mh->n_cell),
-               "vector size mismatch in femo_elast_pnorm_stress");
-  FEMO_REQUIRE(m > 0.0 && p >= 1.0 && q >= 0.0 && alpha > 0.0 && std::isfinite(m) && std::isfinite(p) && std::isfinite(q) &&
-               std::isfinite(alpha), "bad parameters of the stress aggregate: need m > 0, p >= 1, q >= 0, alpha > 0");
-  FEMO_REQUIRE(grad_u != u && grad_u != rho && grad_rho != rho && grad_rho != u && (!grad_u || grad_u != grad_rho),
-               "femo_elast_pnorm_stress: output aliases an input");
-  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u));
-  hipStream_t st = mh->ctx->stream;
-  const int nb = (int)grid_of(mh->n_cell);
-  if (value && !e->w_spart) FEMO_TRY(dalloc(&e->w_spart, (int64_t)nb + 1));
-  if (grad_rho) femo_vec_touch(grad_rho);
-  if (value || grad_rho)
-    FEMO_TRY(stress_cell_launch(e, rho->d, u->d, m, p, q, 1.0 / alpha, nullptr, value ? e->w_spart : nullptr,
-                                grad_rho ? grad_rho->d : nullptr, accumulate));
-  if (grad_u) {
-    femo_vec_touch(grad_u);
-    const unsigned g = grid_of(mh->n_rows);
-    if (e->d == 2)
-      hipLaunchKernelGGL(k_elast_stress_du<2>, dim3(g), dim3(EB), 0, st, mh->n_rows, mh->d_vptr, mh->d_visit_cell, mh->d_conn,
-                         mh->d_x, rho->d, u->d, e->mu0, m, p, q, 1.0 / alpha, grad_u->d, accumulate);
-    else
-      hipLaunchKernelGGL(k_elast_stress_du<3>, dim3(g), dim3(EB), 0, st, mh->n_rows, mh->d_vptr, mh->d_visit_cell, mh->d_conn,
-                         mh->d_x, rho->d, u->d, e->mu0, m, p, q, 1.0 / alpha, grad_u->d, accumulate);
-    FEMO_HIP_CHECK(hipGetLastError());
-  }
-  if (value) {
-    FEMO_TRY(femo_launch_fold(1024, nb, 1, e->w_spart, e->w_spart + nb, st));
-    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_s, e->w_spart + nb, sizeof(double), hipMemcpyDeviceToHost, st));
-    FEMO_HIP_CHECK(hipStreamSynchronize(st));
-    *value = e->h_s[0];
-  }
-  return 0;
-}
-
-int femo_elast_von_mises(femo_elast* e, const femo_vec* rho, const femo_vec* u, double q, femo_vec* out_cells) {
-  FEMO_REQUIRE(e && u && out_cells, "null argument");
-  FEMO_REQUIRE(q >= 0.0 && std::isfinite(q), "femo_elast_von_mises: need q >= 0");
-  FEMO_REQUIRE(rho || q == 0.0, "femo_elast_von_mises: q > 0 needs the density");
-  femo_mesh* mh = e->mesh;
-  FEMO_REQUIRE(u->n >= mh->n_vert * e->d && out_cells->n >= mh->n_cell && (!rho || rho->n >= mh->n_cell),
-               "vector size mismatch in femo_elast_von_mises");
-  FEMO_REQUIRE(out_cells != u && out_cells != rho, "femo_elast_von_mises: output aliases an input");
-  FEMO_TRY(femo_vec_await(u));
-  if (rho) FEMO_TRY(femo_vec_await(rho));
-  femo_vec_touch(out_cells);
-  return stress_cell_launch(e, rho ? rho->d : nullptr, u->d, 1.0, 1.0, q, 1.0, out_cells->d, nullptr, nullptr, 0);
+  return drho_cols(e, method, transpose, n_cols, rho, u, x, y, accumulate, "femo_elast_drho_multi");
 }
 
 int femo_elast_export_csr(const femo_elast* e, int64_t* rowptr, int32_t* col, double* val) {

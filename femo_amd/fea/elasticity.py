@@ -1,6 +1,7 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
-product and PCG in csrc/elast_solve.hip).
+product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip).  One load case is the L = 1 case of several:
+each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
 own assembly and solves, so `FEA.add_input / add_state / add_output`, `StateOperation`, `OutputOperation` and `FEAModel`
@@ -22,7 +23,7 @@ are used unchanged.
                        mode -- is one batched PCG over all columns (csrc/elast_solve.hip)
   MultiLoadPnormStress J = sum_l w_l J_l with one aggregate J_l = (1/alpha) sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p per
                        load case of a LoadCaseSpace state: the values, dJ/du (column l = w_l dJ_l/du_l) and dJ/drho of all
-                       load cases in one pass over the mesh (csrc/elast_stress_multi.hip).  Its adjoint is one batched PCG
+                       load cases in one pass over the mesh (csrc/elast_stress.hip).  Its adjoint is one batched PCG
                        whose right-hand sides are not loads: they are non-zero on the clamped dofs of every column
   MultiLoadVonMises    the cell field max_l s_l rho_e^q sigma_vm,e(u_l) (the envelope over the load cases), or that of one
                        load case, for `project` / FEA.add_field_output
@@ -383,8 +384,12 @@ def _fixed_data(n_dof: int, bcs):
 
 
 # ------------------------------------------------------------------------------------------------------ operators ----
+# One load case is the L = 1 case: every form below is written once for the ``n_cases`` columns of its state (1 for a plain
+# VectorFunctionSpace state) and calls the batched entry points.  The ``MultiLoad...`` names adapt the constructor
+# arguments and how the solves are recorded and reported.
 class ElasticityMatrix:
-    """dR/du = K(rho); with ``masked`` the A of state_model.py:149 (identity rows / columns on the fixed dofs)."""
+    """dR/du = K(rho) on every column; with ``masked`` the A of state_model.py:149 (identity rows / columns on the fixed
+    dofs).  One `mult` is one batched product, one `backend_solve` one batched PCG over all columns."""
     symmetric = True
     pde_kind = None
 
@@ -394,61 +399,65 @@ class ElasticityMatrix:
         self.info = None
 
     def getSizes(self):
-        n = self.form.n_dof
+        n = self.form.n_cases * self.form.n_dof
         return (n, n)
 
     size = property(getSizes)
 
     def mult(self, x: Vec, y: Vec) -> Vec:
         dev = self.form.stiffness()
-        return dev.apply(x, y, masked=self.masked and dev.fixed_key is not None)
+        return dev.apply_multi(self.form.n_cases, x, y, masked=self.masked and dev.fixed_key is not None)
 
     multTranspose = mult
 
     def new_row_vec(self) -> Vec:
         if self._row is None:
-            self._row = Vec(_ctx(), self.form.n_dof)
+            self._row = Vec(_ctx(), self.getSizes()[0])
         return self._row
 
     new_col_vec = new_row_vec
 
     def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
         o = options or {}
-        dev = self.form.stiffness()
-        self.info = dev.solve(b, x, rtol=o.get("elast_rtol", self.form.rtol), max_it=o.get("elast_max_it", 1_000_000),
-                              pc=self.form.preconditioner)
-        self.form._record(self.info, "adjoint")
+        F = self.form
+        infos = F.stiffness().solve_multi(F.n_cases, b, x, rtol=o.get("elast_rtol", F.rtol),
+                                          max_it=o.get("elast_max_it", 1_000_000), pc=F.preconditioner)
+        self.info = F._record(infos, "adjoint")
 
     def to_scipy(self):
-        K = self.form.stiffness().export_csr()
-        if not self.masked or self.form._mask is None:
-            return K
         import scipy.sparse as sp
-        free = sp.diags((self.form._mask == 0).astype(np.float64))
-        return (free @ K @ free + sp.diags(self.form._mask.astype(np.float64))).tocsr()
+        K = self.form.stiffness().export_csr()
+        if self.masked and self.form._mask is not None:
+            free = sp.diags((self.form._mask == 0).astype(np.float64))
+            K = (free @ K @ free + sp.diags(self.form._mask.astype(np.float64))).tocsr()
+        return K if self.form.n_cases == 1 else sp.block_diag([K] * self.form.n_cases, format="csr")
+
+
+class MultiLoadElasticityMatrix(ElasticityMatrix):
+    """`ElasticityMatrix` of a `MultiLoadElasticityResidual`."""
 
 
 class _ElasticityDrho:
-    """dR/drho (n_dof x n_cell), matrix free: column e = C'(rho_e) K0_e u_e."""
+    """dR/drho ((n_cases n_dof) x n_cell), matrix free: block l of column e = C'(rho_e) K0_e u_{l,e}."""
 
     def __init__(self, form: "ElasticityResidual"):
         self.form, self.mesh = form, form.mesh
         self._row = self._col = None
 
     def getSizes(self):
-        return (self.form.n_dof, self.mesh.n_cell)
+        return (self.form.n_cases * self.form.n_dof, self.mesh.n_cell)
 
     def mult(self, x: Vec, y: Vec) -> Vec:
         F = self.form
-        return F.device().drho(F.method_id, False, F.rho.vec, F.u.vec, x, y)
+        return F.device().drho_multi(F.method_id, False, F.n_cases, F.rho.vec, F.u.vec, x, y)
 
     def multTranspose(self, x: Vec, y: Vec) -> Vec:
         F = self.form
-        return F.device().drho(F.method_id, True, F.rho.vec, F.u.vec, x, y)
+        return F.device().drho_multi(F.method_id, True, F.n_cases, F.rho.vec, F.u.vec, x, y)
 
     def new_row_vec(self) -> Vec:
         if self._row is None:
-            self._row = Vec(_ctx(), self.form.n_dof)
+            self._row = Vec(_ctx(), self.getSizes()[0])
         return self._row
 
     def new_col_vec(self) -> Vec:
@@ -458,172 +467,11 @@ class _ElasticityDrho:
 
 
 # ---------------------------------------------------------------------------------------------------------- forms ----
-class ElasticityResidual(BackendForm):
-    """R(u; rho) = K(rho) u - F(t) with the tagged traction ``ds`` (see the module docstring)."""
-    rank = 1
-    is_linear = True
-    is_symmetric = True
-    constant_partials = False
-
-    def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, E: float = 1.0,
-                 nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi"):
-        if not isinstance(u.function_space, VectorFunctionSpace):
-            raise NotImplementedError("ElasticityResidual needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
-        if rho.function_space.family != "DG" or rho.function_space.mesh is not u.function_space.mesh:
-            raise NotImplementedError("ElasticityResidual needs a DG0 density on the state's mesh")
-        if method not in METHODS:
-            raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
-        if preconditioner not in PRECONDITIONERS:
-            raise ValueError(f"unknown preconditioner {preconditioner!r} (jacobi or multilevel)")
-        self.preconditioner = preconditioner
-        self.u, self.rho, self.mesh = u, rho, u.function_space.mesh
-        self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
-        self.t = _traction(traction, self.mesh)
-        self.ds = ds if ds is not None else Measure("ds", domain=self.mesh)
-        self.n_dof = u.function_space.dim
-        self.rtol = 1e-15
-        self._key = None
-        self._mask = None
-        self._vals = None
-        self._res = None
-        self._rhs_cache = None
-        self.last_info = {}
-
-    def functions(self):
-        return (self.u, self.rho)
-
-    def device(self) -> DeviceElasticity:
-        return elasticity_handle(self.mesh, self.E, self.nu)
-
-    def load(self) -> Vec:
-        return _load_vec(self.mesh, self.ds.facets(), self.t)
-
-    def _set_bcs(self, bcs) -> None:
-        mask, self._vals = _fixed_data(self.n_dof, bcs)
-        self._mask = mask
-
-    def stiffness(self) -> DeviceElasticity:
-        """The handle with K(rho) of the current density and this form's fixed set: reassembled when either changed."""
-        dev = self.device()
-        want = None if self._mask is None else hash(self._mask.tobytes())
-        if dev.fixed_key != want:
-            dev.set_fixed(self._mask)
-        key = (self.rho.version, id(self.rho.vec), dev.fixed_key, self.method_id, id(self))
-        if getattr(dev, "_owner", None) != key:
-            dev.assemble(self.method_id, self.rho.vec)
-            dev._owner = key
-        if self.preconditioner == "multilevel" and dev.pc_plan is None:
-            dev.pc_setup()
-        return dev
-
-    def _record(self, info, kind: str) -> None:
-        from .utils_hip import LAST_KSP_INFO
-        self.last_info[kind] = dict(iterations=info.iterations, converged=info.converged, solve_ms=info.solve_ms,
-                                    residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
-                                    preconditioner=self.preconditioner)
-        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_" + kind))
-        if info.converged != 1:
-            raise RuntimeError(f"elasticity PCG did not converge ({kind}): {info.iterations} iterations, "
-                               f"sqrt(r.M^-1 r) = {info.residual_norm:.3e} of {info.rhs_norm:.3e}")
-
-    def new_matrix(self) -> ElasticityMatrix:
-        return ElasticityMatrix(self)
-
-    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
-        """R = K u - F, one launch (femo_elast_apply)."""
-        if out is None:
-            if self._res is None:
-                self._res = Vec(_ctx(), self.n_dof)
-            out = self._res
-        return self.stiffness().apply(self.u.vec, out, a=1.0, b=-1.0, f=self.load())
-
-    def partial_matrix(self, wrt: Function, out=None):
-        if wrt is self.u:
-            return out if isinstance(out, ElasticityMatrix) and not out.masked else ElasticityMatrix(self)
-        if wrt is self.rho:
-            return out if isinstance(out, _ElasticityDrho) else _ElasticityDrho(self)
-        raise ValueError("the elasticity residual does not depend on that Function")
-
-    def assemble_system(self, bcs, rhs: bool, out, out_nobc):
-        if rhs:
-            raise NotImplementedError("assembleSystem(rhs=True) for the elasticity form: use solveNonlinear / FEA.solve")
-        self._set_bcs(bcs)
-        self.stiffness()
-        A = out if isinstance(out, ElasticityMatrix) else ElasticityMatrix(self)
-        A.form, A.masked = self, True
-        if isinstance(out_nobc, ElasticityMatrix):
-            out_nobc.form, out_nobc.masked = self, False
-        return A, None
-
-    def _rhs(self, dev: DeviceElasticity) -> Vec:
-        """F with the Dirichlet lifting: b = F - K g, b = g on the fixed dofs."""
-        F = self.load()
-        if self._mask is None:
-            return F
-        nonzero = bool(np.any(self._vals[self._mask == 1] != 0.0))
-        key = (id(F), hash(self._mask.tobytes()))
-        if not nonzero and self._rhs_cache is not None and self._rhs_cache[0] == key:
-            return self._rhs_cache[1]
-        ctx = _ctx()
-        if nonzero:
-            g = Vec(ctx, self.n_dof).set(np.where(self._mask == 1, self._vals, 0.0))
-            b = Vec(ctx, self.n_dof)
-            dev.apply(g, b, a=-1.0, b=1.0, f=F)                   # F - K g
-            bh = np.array(b.get())
-        else:
-            bh = np.array(F.get())
-        bh[self._mask == 1] = self._vals[self._mask == 1]
-        bv = Vec(ctx, self.n_dof).set(bh)
-        if not nonzero:
-            self._rhs_cache = (key, bv)
-        return bv
-
-    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
-        """K(rho) u = F with the strongly imposed dofs: one PCG solve (the form is linear)."""
-        self._set_bcs(bcs)
-        dev = self.stiffness()
-        info = dev.solve(self._rhs(dev), func.vec, rtol=self.rtol, pc=self.preconditioner)
-        func.version += 1
-        self._record(info, "state")
-        if report:
-            print(f"elasticity solve: {info.iterations} PCG iterations, {info.solve_ms:.1f} ms")
-
-
-class Compliance(BackendForm):
-    """J = int_ds t . u ds = F^T u (compliance, run_topo_opt_cantilever_beam.py:108-109)."""
-    rank = 0
-
-    def __init__(self, u: Function, traction, ds: Optional[Measure] = None):
-        if not isinstance(u.function_space, VectorFunctionSpace):
-            raise NotImplementedError("Compliance needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
-        self.u, self.mesh = u, u.function_space.mesh
-        self.t = _traction(traction, self.mesh)
-        self.ds = ds if ds is not None else Measure("ds", domain=self.mesh)
-        self._grad = None
-
-    def functions(self):
-        return (self.u,)
-
-    def load(self) -> Vec:
-        return _load_vec(self.mesh, self.ds.facets(), self.t)
-
-    def assemble_scalar(self) -> float:
-        return self.load().dot(self.u.vec, self.u.function_space.dim)
-
-    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        n = wrt.function_space.dim
-        if out is None:
-            if self._grad is None or self._grad.n != n:
-                self._grad = Vec(_ctx(), n)
-            out = self._grad
-        if wrt is self.u:
-            return out.copy_from(self.load())
-        return out.fill(0.0)
-
-
-# ------------------------------------------------------------------------------------------- several load cases ----
-def _multi_load_vec(mesh, facets_list, tractions, weights=None) -> Vec:
-    """Column l = w_l F_l (w = 1 without weights): the single loads of `_load_vec`, placed through the host once and cached."""
+def _loads_vec(mesh, facets_list, tractions, weights=None) -> Vec:
+    """Column l = w_l F_l (w = 1 without weights).  One unweighted column is the load of `_load_vec` itself; several are
+    placed through the host once and cached."""
+    if len(tractions) == 1 and weights is None:
+        return _load_vec(mesh, facets_list[0], tractions[0])
     cache = mesh.__dict__.setdefault("_elast_multi_loads", {})
     w = np.ones(len(tractions)) if weights is None else np.asarray(weights, dtype=np.float64)
     key = (id(_ctx()), tuple(hash(np.ascontiguousarray(f, dtype=np.int32).tobytes()) for f in facets_list),
@@ -651,79 +499,152 @@ def _multi_arguments(name: str, u: Function, tractions, measures):
     return V, ts, dss
 
 
-class MultiLoadElasticityMatrix:
-    """dR/du of the multi-load residual: K(rho) (masked: A) on every column.  One `mult` is one batched product, one
-    `backend_solve` one batched PCG over all columns."""
-    symmetric = True
-    pde_kind = None
+class ElasticityResidual(BackendForm):
+    """R(u; rho) = K(rho) u - F(t) with the tagged traction ``ds`` (see the module docstring).  ``n_cases`` columns (one
+    here), ``n_dof`` dofs per column; every product and solve is the batched one over all columns."""
+    rank = 1
+    is_linear = True
+    is_symmetric = True
+    constant_partials = False
+    matrix_class = ElasticityMatrix
 
-    def __init__(self, form: "MultiLoadElasticityResidual", masked: bool = False):
-        self.form, self.masked, self.mesh = form, masked, form.mesh
-        self._row = None
-        self.info = None
+    def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, E: float = 1.0,
+                 nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi"):
+        V = u.function_space
+        if not isinstance(V, VectorFunctionSpace):
+            raise NotImplementedError("ElasticityResidual needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
+        self.t = _traction(traction, V.mesh)
+        self.ds = ds if ds is not None else Measure("ds", domain=V.mesh)
+        self._setup(u, rho, V, 1, [self.t], [self.ds], E, nu, method, preconditioner)
 
-    def getSizes(self):
-        n = self.form.n_cases * self.form.n_dof
-        return (n, n)
+    def _setup(self, u, rho, V, n_cases, tractions, measures, E, nu, method, preconditioner) -> None:
+        """``V``: the space of one column (the numbering of the bcs)."""
+        if rho.function_space.family != "DG" or rho.function_space.mesh is not V.mesh:
+            raise NotImplementedError(f"{type(self).__name__} needs a DG0 density on the state's mesh")
+        if method not in METHODS:
+            raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
+        if preconditioner not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {preconditioner!r} (jacobi or multilevel)")
+        self.preconditioner = preconditioner
+        self.u, self.rho, self.mesh = u, rho, V.mesh
+        self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
+        self.n_cases, self.n_dof = n_cases, V.dim
+        self.tractions, self.measures = tractions, measures
+        self.rtol = 1e-15
+        self._key = None
+        self._mask = None
+        self._vals = None
+        self._res = None
+        self._rhs_cache = None
+        self.last_info = {}
 
-    size = property(getSizes)
+    def functions(self):
+        return (self.u, self.rho)
 
-    def mult(self, x: Vec, y: Vec) -> Vec:
-        dev = self.form.stiffness()
-        return dev.apply_multi(self.form.n_cases, x, y, masked=self.masked and dev.fixed_key is not None)
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
 
-    multTranspose = mult
+    def load(self) -> Vec:
+        return _loads_vec(self.mesh, [ds.facets() for ds in self.measures], self.tractions)
 
-    def new_row_vec(self) -> Vec:
-        if self._row is None:
-            self._row = Vec(_ctx(), self.getSizes()[0])
-        return self._row
+    def _set_bcs(self, bcs) -> None:
+        mask, self._vals = _fixed_data(self.n_dof, bcs)
+        self._mask = mask
 
-    new_col_vec = new_row_vec
+    def stiffness(self) -> DeviceElasticity:
+        """The handle with K(rho) of the current density and this form's fixed set: reassembled when either changed."""
+        dev = self.device()
+        want = None if self._mask is None else hash(self._mask.tobytes())
+        if dev.fixed_key != want:
+            dev.set_fixed(self._mask)
+        key = (self.rho.version, id(self.rho.vec), dev.fixed_key, self.method_id, id(self))
+        if getattr(dev, "_owner", None) != key:
+            dev.assemble(self.method_id, self.rho.vec)
+            dev._owner = key
+        if self.preconditioner == "multilevel" and dev.pc_plan is None:
+            dev.pc_setup()
+        return dev
 
-    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
-        o = options or {}
-        F = self.form
-        self.info = F.stiffness().solve_multi(F.n_cases, b, x, rtol=o.get("elast_rtol", F.rtol),
-                                              max_it=o.get("elast_max_it", 1_000_000), pc=F.preconditioner)
-        F._record(self.info, "adjoint")
+    def _record(self, infos, kind: str):
+        """Keeps the record of a solve (``infos``: one per column) and raises when it did not converge; returns what
+        the matrix shows as its ``info``."""
+        from .utils_hip import LAST_KSP_INFO
+        info = infos[0]
+        self.last_info[kind] = dict(iterations=info.iterations, converged=info.converged, solve_ms=info.solve_ms,
+                                    residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
+                                    preconditioner=self.preconditioner)
+        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_" + kind))
+        if info.converged != 1:
+            raise RuntimeError(f"elasticity PCG did not converge ({kind}): {info.iterations} iterations, "
+                               f"sqrt(r.M^-1 r) = {info.residual_norm:.3e} of {info.rhs_norm:.3e}")
+        return info
 
-    def to_scipy(self):
-        import scipy.sparse as sp
-        K = self.form.stiffness().export_csr()
-        if self.masked and self.form._mask is not None:
-            free = sp.diags((self.form._mask == 0).astype(np.float64))
-            K = free @ K @ free + sp.diags(self.form._mask.astype(np.float64))
-        return sp.block_diag([K] * self.form.n_cases, format="csr")
+    def _report(self, infos) -> str:
+        return f"elasticity solve: {infos[0].iterations} PCG iterations, {infos[0].solve_ms:.1f} ms"
 
+    def new_matrix(self) -> ElasticityMatrix:
+        return self.matrix_class(self)
 
-class _MultiLoadDrho:
-    """dR/drho ((n_cases n_dof) x n_cell), matrix free: block l of column e = C'(rho_e) K0_e u_{l,e}."""
+    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
+        """Column l: K u_l - F_l; one launch for all columns (femo_elast_apply_multi)."""
+        if out is None:
+            if self._res is None:
+                self._res = Vec(_ctx(), self.n_cases * self.n_dof)
+            out = self._res
+        return self.stiffness().apply_multi(self.n_cases, self.u.vec, out, a=1.0, b=-1.0, f=self.load())
 
-    def __init__(self, form: "MultiLoadElasticityResidual"):
-        self.form, self.mesh = form, form.mesh
-        self._row = self._col = None
+    def partial_matrix(self, wrt: Function, out=None):
+        if wrt is self.u:
+            return out if isinstance(out, self.matrix_class) and not out.masked else self.matrix_class(self)
+        if wrt is self.rho:
+            return out if isinstance(out, _ElasticityDrho) else _ElasticityDrho(self)
+        raise ValueError("the elasticity residual does not depend on that Function")
 
-    def getSizes(self):
-        return (self.form.n_cases * self.form.n_dof, self.mesh.n_cell)
+    def assemble_system(self, bcs, rhs: bool, out, out_nobc):
+        if rhs:
+            raise NotImplementedError("assembleSystem(rhs=True) for the elasticity form: use solveNonlinear / FEA.solve")
+        self._set_bcs(bcs)
+        self.stiffness()
+        A = out if isinstance(out, self.matrix_class) else self.matrix_class(self)
+        A.form, A.masked = self, True
+        if isinstance(out_nobc, self.matrix_class):
+            out_nobc.form, out_nobc.masked = self, False
+        return A, None
 
-    def mult(self, x: Vec, y: Vec) -> Vec:
-        F = self.form
-        return F.device().drho_multi(F.method_id, False, F.n_cases, F.rho.vec, F.u.vec, x, y)
+    def _rhs(self, dev: DeviceElasticity) -> Vec:
+        """Column l: F_l with the Dirichlet lifting, b_l = F_l - K g, b_l = g on the fixed dofs (the same fixed set and
+        the same values for every column)."""
+        F = self.load()
+        if self._mask is None:
+            return F
+        fixed = self._mask == 1
+        nonzero = bool(np.any(self._vals[fixed] != 0.0))
+        key = (id(F), hash(self._mask.tobytes()))
+        if not nonzero and self._rhs_cache is not None and self._rhs_cache[0] == key:
+            return self._rhs_cache[1]
+        ctx, L, n = _ctx(), self.n_cases, self.n_dof
+        if nonzero:
+            g = Vec(ctx, L * n).set(np.tile(np.where(fixed, self._vals, 0.0), L))
+            b = Vec(ctx, L * n)
+            dev.apply_multi(L, g, b, a=-1.0, b=1.0, f=F)            # F_l - K g
+            bh = np.array(b.get()).reshape(L, n)
+        else:
+            bh = np.array(F.get()).reshape(L, n)
+        bh[:, fixed] = self._vals[fixed]
+        bv = Vec(ctx, L * n).set(bh.ravel())
+        if not nonzero:
+            self._rhs_cache = (key, bv)
+        return bv
 
-    def multTranspose(self, x: Vec, y: Vec) -> Vec:
-        F = self.form
-        return F.device().drho_multi(F.method_id, True, F.n_cases, F.rho.vec, F.u.vec, x, y)
-
-    def new_row_vec(self) -> Vec:
-        if self._row is None:
-            self._row = Vec(_ctx(), self.getSizes()[0])
-        return self._row
-
-    def new_col_vec(self) -> Vec:
-        if self._col is None:
-            self._col = Vec(_ctx(), self.mesh.n_cell)
-        return self._col
+    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
+        """K(rho) u_l = F_l for every column with the strongly imposed dofs: ONE batched PCG solve (the form is linear)."""
+        self._set_bcs(bcs)
+        dev = self.stiffness()
+        infos = dev.solve_multi(self.n_cases, self._rhs(dev), func.vec, rtol=self.rtol, pc=self.preconditioner)
+        func.version += 1
+        self._record(infos, "state")
+        if report:
+            print(self._report(infos))
 
 
 class MultiLoadElasticityResidual(ElasticityResidual):
@@ -740,33 +661,15 @@ class MultiLoadElasticityResidual(ElasticityResidual):
     state are `MultiLoadPnormStress` / `MultiLoadVonMises`.  ``last_info[kind]`` keeps, per kind of solve ("state",
     "adjoint"), the record of the last batched solve with one entry per column under ``columns``; ``solve_counts[kind]``
     counts the batched solves."""
+    matrix_class = MultiLoadElasticityMatrix
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, E: float = 1.0, nu: float = 0.3,
                  method: str = "SIMP", preconditioner: str = "jacobi"):
-        V, self.tractions, self.measures = _multi_arguments("MultiLoadElasticityResidual", u, tractions, measures)
-        if rho.function_space.family != "DG" or rho.function_space.mesh is not V.mesh:
-            raise NotImplementedError("MultiLoadElasticityResidual needs a DG0 density on the state's mesh")
-        if method not in METHODS:
-            raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
-        if preconditioner not in PRECONDITIONERS:
-            raise ValueError(f"unknown preconditioner {preconditioner!r} (jacobi or multilevel)")
-        self.preconditioner = preconditioner
-        self.u, self.rho, self.mesh = u, rho, V.mesh
-        self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
-        self.n_cases, self.n_dof = V.n_cases, V.base.dim           # n_dof: of one column (the numbering of the bcs)
-        self.rtol = 1e-15
-        self._key = None
-        self._mask = None
-        self._vals = None
-        self._res = None
-        self._rhs_cache = None
-        self.last_info = {}
+        V, ts, dss = _multi_arguments("MultiLoadElasticityResidual", u, tractions, measures)
+        self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner)
         self.solve_counts = {"state": 0, "adjoint": 0}
 
-    def load(self) -> Vec:
-        return _multi_load_vec(self.mesh, [ds.facets() for ds in self.measures], self.tractions)
-
-    def _record(self, infos, kind: str) -> None:
+    def _record(self, infos, kind: str):
         from .utils_hip import LAST_KSP_INFO
         cols = [dict(iterations=i.iterations, converged=i.converged, residual_norm=i.residual_norm, rhs_norm=i.rhs_norm)
                 for i in infos]
@@ -780,81 +683,25 @@ class MultiLoadElasticityResidual(ElasticityResidual):
                 raise RuntimeError(f"elasticity PCG did not converge ({kind}, load case {l} of {self.n_cases}): "
                                    f"{c['iterations']} iterations, sqrt(r.M^-1 r) = {c['residual_norm']:.3e} of "
                                    f"{c['rhs_norm']:.3e}")
+        return infos
 
-    def new_matrix(self) -> MultiLoadElasticityMatrix:
-        return MultiLoadElasticityMatrix(self)
-
-    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
-        """Column l: K u_l - F_l; one launch for all columns (femo_elast_apply_multi)."""
-        if out is None:
-            if self._res is None:
-                self._res = Vec(_ctx(), self.n_cases * self.n_dof)
-            out = self._res
-        return self.stiffness().apply_multi(self.n_cases, self.u.vec, out, a=1.0, b=-1.0, f=self.load())
-
-    def partial_matrix(self, wrt: Function, out=None):
-        if wrt is self.u:
-            return out if isinstance(out, MultiLoadElasticityMatrix) and not out.masked else MultiLoadElasticityMatrix(self)
-        if wrt is self.rho:
-            return out if isinstance(out, _MultiLoadDrho) else _MultiLoadDrho(self)
-        raise ValueError("the elasticity residual does not depend on that Function")
-
-    def assemble_system(self, bcs, rhs: bool, out, out_nobc):
-        if rhs:
-            raise NotImplementedError("assembleSystem(rhs=True) for the elasticity form: use solveNonlinear / FEA.solve")
-        self._set_bcs(bcs)
-        self.stiffness()
-        A = out if isinstance(out, MultiLoadElasticityMatrix) else MultiLoadElasticityMatrix(self)
-        A.form, A.masked = self, True
-        if isinstance(out_nobc, MultiLoadElasticityMatrix):
-            out_nobc.form, out_nobc.masked = self, False
-        return A, None
-
-    def _rhs(self, dev: DeviceElasticity) -> Vec:
-        """Column l: F_l with the Dirichlet lifting, b_l = F_l - K g, b_l = g on the fixed dofs."""
-        F = self.load()
-        if self._mask is None:
-            return F
-        fixed = self._mask == 1
-        nonzero = bool(np.any(self._vals[fixed] != 0.0))
-        key = (id(F), hash(self._mask.tobytes()))
-        if not nonzero and self._rhs_cache is not None and self._rhs_cache[0] == key:
-            return self._rhs_cache[1]
-        ctx = _ctx()
-        bh = np.array(F.get(), dtype=np.float64).reshape(self.n_cases, self.n_dof)
-        if nonzero:
-            g = Vec(ctx, self.n_dof).set(np.where(fixed, self._vals, 0.0))
-            Kg = Vec(ctx, self.n_dof)
-            dev.apply(g, Kg)
-            bh -= np.array(Kg.get())[None, :]
-        bh[:, fixed] = self._vals[fixed]
-        bv = Vec(ctx, self.n_cases * self.n_dof).set(bh.ravel())
-        if not nonzero:
-            self._rhs_cache = (key, bv)
-        return bv
-
-    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
-        """K(rho) u_l = F_l for every load case with the strongly imposed dofs: ONE batched PCG solve."""
-        self._set_bcs(bcs)
-        dev = self.stiffness()
-        infos = dev.solve_multi(self.n_cases, self._rhs(dev), func.vec, rtol=self.rtol, pc=self.preconditioner)
-        func.version += 1
-        self._record(infos, "state")
-        if report:
-            print(f"elasticity solve, {self.n_cases} load cases: {[i.iterations for i in infos]} PCG iterations, "
-                  f"{infos[0].solve_ms:.1f} ms")
+    def _report(self, infos) -> str:
+        return (f"elasticity solve, {self.n_cases} load cases: {[i.iterations for i in infos]} PCG iterations, "
+                f"{infos[0].solve_ms:.1f} ms")
 
 
-class MultiLoadCompliance(BackendForm):
-    """J = sum_l w_l F_l . u_l over the load cases of a Function(LoadCaseSpace(V, L)) (w = 1 without ``weights``)."""
+class Compliance(BackendForm):
+    """J = int_ds t . u ds = F^T u (compliance, run_topo_opt_cantilever_beam.py:108-109); over several columns
+    J = sum_l w_l F_l . u_l."""
     rank = 0
 
-    def __init__(self, u: Function, tractions, measures=None, weights=None):
-        V, self.tractions, self.measures = _multi_arguments("MultiLoadCompliance", u, tractions, measures)
-        self.u, self.mesh = u, V.mesh
-        self.weights = np.ones(V.n_cases) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
-        if self.weights.size != V.n_cases:
-            raise ValueError(f"MultiLoadCompliance: {V.n_cases} load cases need as many weights")
+    def __init__(self, u: Function, traction, ds: Optional[Measure] = None):
+        if not isinstance(u.function_space, VectorFunctionSpace):
+            raise NotImplementedError("Compliance needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
+        self.u, self.mesh = u, u.function_space.mesh
+        self.t = _traction(traction, self.mesh)
+        self.ds = ds if ds is not None else Measure("ds", domain=self.mesh)
+        self.tractions, self.measures, self.weights = [self.t], [self.ds], None
         self._grad = None
 
     def functions(self):
@@ -862,7 +709,7 @@ class MultiLoadCompliance(BackendForm):
 
     def load(self) -> Vec:
         """Column l = w_l F_l."""
-        return _multi_load_vec(self.mesh, [ds.facets() for ds in self.measures], self.tractions, self.weights)
+        return _loads_vec(self.mesh, [ds.facets() for ds in self.measures], self.tractions, self.weights)
 
     def assemble_scalar(self) -> float:
         return self.load().dot(self.u.vec, self.u.function_space.dim)
@@ -876,6 +723,18 @@ class MultiLoadCompliance(BackendForm):
         if wrt is self.u:
             return out.copy_from(self.load())
         return out.fill(0.0)
+
+
+class MultiLoadCompliance(Compliance):
+    """J = sum_l w_l F_l . u_l over the load cases of a Function(LoadCaseSpace(V, L)) (w = 1 without ``weights``)."""
+
+    def __init__(self, u: Function, tractions, measures=None, weights=None):
+        V, self.tractions, self.measures = _multi_arguments("MultiLoadCompliance", u, tractions, measures)
+        self.u, self.mesh = u, V.mesh
+        self.weights = np.ones(V.n_cases) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
+        if self.weights.size != V.n_cases:
+            raise ValueError(f"MultiLoadCompliance: {V.n_cases} load cases need as many weights")
+        self._grad = None
 
 
 def cell_volumes(mesh) -> np.ndarray:
@@ -894,81 +753,6 @@ def _check_stress_spaces(name: str, u: Function, rho: Optional[Function]) -> Non
         raise NotImplementedError(f"{name} needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
     if rho is not None and (rho.function_space.family != "DG" or rho.function_space.mesh is not u.function_space.mesh):
         raise NotImplementedError(f"{name} needs a DG0 density on the state's mesh")
-
-
-class ElasticityPnormStress(BackendForm):
-    """J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p with the solid-material von Mises stress (module docstring);
-    alpha = |Omega| unless given.  dJ/du is not a multiple of the load: its adjoint solve is a solve of its own."""
-    rank = 0
-
-    def __init__(self, u: Function, rho: Function, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0,
-                 q: float = 0.5, alpha: Optional[float] = None):
-        _check_stress_spaces("ElasticityPnormStress", u, rho)
-        if not (m > 0.0 and p >= 1.0 and q >= 0.0) or (alpha is not None and not alpha > 0.0):
-            raise ValueError("the stress aggregate needs m > 0, p >= 1, q >= 0 and alpha > 0")
-        self.u, self.rho, self.mesh = u, rho, u.function_space.mesh
-        self.E, self.nu, self.m, self.p, self.q = float(E), float(nu), float(m), float(p), float(q)
-        self.alpha = float(cell_volumes(self.mesh).sum() if alpha is None else alpha)
-        self._grad = {}
-
-    def functions(self):
-        return (self.u, self.rho)
-
-    def device(self) -> DeviceElasticity:
-        return elasticity_handle(self.mesh, self.E, self.nu)
-
-    def assemble_scalar(self) -> float:
-        return self.device().pnorm_stress(self.rho.vec, self.u.vec, self.m, self.p, self.q, self.alpha)
-
-    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:                                            # one buffer per argument: both partials may be pending
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
-        if wrt is self.u:
-            self.device().pnorm_stress(self.rho.vec, self.u.vec, self.m, self.p, self.q, self.alpha, value=False, grad_u=out)
-        elif wrt is self.rho:
-            self.device().pnorm_stress(self.rho.vec, self.u.vec, self.m, self.p, self.q, self.alpha, value=False, grad_rho=out)
-        else:
-            out.fill(0.0)
-        return out
-
-
-class ElasticityVonMises(BackendForm):
-    """The cell field rho_e^q sigma_vm,e (q = 0: the stress of the solid material, no density needed).  `project` hands the
-    projection over: onto a DG0 target the cell values themselves, onto CG1 the L2 projection of a cell-wise constant."""
-    rank = 0
-
-    def __init__(self, u: Function, rho: Optional[Function] = None, E: float = 1.0, nu: float = 0.3, q: float = 0.0):
-        _check_stress_spaces("ElasticityVonMises", u, rho)
-        if not q >= 0.0 or (q > 0.0 and rho is None):
-            raise ValueError("the relaxed von Mises stress needs q >= 0, and the density when q > 0")
-        self.u, self.rho, self.mesh = u, rho, u.function_space.mesh
-        self.E, self.nu, self.q = float(E), float(nu), float(q)
-        self._cells = None
-
-    def functions(self):
-        return (self.u,) if self.rho is None else (self.u, self.rho)
-
-    def device(self) -> DeviceElasticity:
-        return elasticity_handle(self.mesh, self.E, self.nu)
-
-    def project_field(self, target: Function, lump_mass: bool = False) -> Function:
-        V = target.function_space
-        if V.mesh is not self.mesh or isinstance(V, VectorFunctionSpace) or V.family not in ("DG", "CG"):
-            raise NotImplementedError("the von Mises stress is projected onto the DG0 or the CG1 space of the state's mesh")
-        rho = None if self.rho is None else self.rho.vec
-        if V.family == "DG":
-            self.device().von_mises(self.u.vec, target.vec, rho, self.q)
-            target.version += 1
-            return target
-        if self._cells is None:
-            self._cells = Function(FunctionSpace(self.mesh, ("DG", 0)))
-        self.device().von_mises(self.u.vec, self._cells.vec, rho, self.q)
-        self._cells.version += 1
-        from .utils_hip import project
-        project(self._cells, target, lump_mass=lump_mass)           # the cell-constant path PowerExpr takes
-        return target
 
 
 def _check_multi_stress_spaces(name: str, u: Function, rho: Optional[Function]) -> LoadCaseSpace:
@@ -992,26 +776,26 @@ def _per_case(name: str, what: str, values, n_cases: int) -> np.ndarray:
     return a.copy()
 
 
-class MultiLoadPnormStress(BackendForm):
-    """J = sum_l w_l J_l, J_l = (1/alpha) sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p, over the load cases of a
-    Function(LoadCaseSpace(V, L)): the worst stress over all load cases as one p-norm constraint.  ``m``: a scalar or one
-    scale per load case (the loads differ in magnitude); ``weights`` >= 0, 1 without; p, q, alpha shared, alpha = |Omega|
-    unless given.  Value, dJ/du (column l = w_l dJ_l/du_l) and dJ/drho each take one pass over the mesh for all load cases
-    (`DeviceElasticity.pnorm_stress_multi`).  dJ/du is non-zero on the clamped dofs of every column: the exact reduced
-    gradient needs ``fea.consistent_bc_partials``."""
+class ElasticityPnormStress(BackendForm):
+    """J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p with the solid-material von Mises stress (module docstring);
+    alpha = |Omega| unless given.  dJ/du is not a multiple of the load: its adjoint solve is a solve of its own.  Over
+    several columns J = sum_l w_l J_l; value, dJ/du (column l = w_l dJ_l/du_l) and dJ/drho each take one pass over the mesh
+    for all of them (`DeviceElasticity.pnorm_stress_multi`).  ``m`` is a float here and may be assigned to."""
     rank = 0
 
-    def __init__(self, u: Function, rho: Function, E: float = 1.0, nu: float = 0.3, m=1.0, p: float = 8.0, q: float = 0.5,
-                 alpha: Optional[float] = None, weights=None):
-        V = _check_multi_stress_spaces("MultiLoadPnormStress", u, rho)
-        self.n_cases = V.n_cases
-        self.m = _per_case("MultiLoadPnormStress", "scales m", m, V.n_cases)
-        self.weights = np.ones(V.n_cases) if weights is None else _per_case("MultiLoadPnormStress", "weights", weights, V.n_cases)
-        if not (np.all(self.m > 0.0) and p >= 1.0 and q >= 0.0) or (alpha is not None and not alpha > 0.0):
+    def __init__(self, u: Function, rho: Function, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0,
+                 q: float = 0.5, alpha: Optional[float] = None):
+        _check_stress_spaces("ElasticityPnormStress", u, rho)
+        self._setup(u, rho, u.function_space.mesh, 1, m, np.ones(1), E, nu, p, q, alpha)
+        self.m = float(m)
+
+    def _setup(self, u, rho, mesh, n_cases, m, weights, E, nu, p, q, alpha) -> None:
+        if not (np.all(np.asarray(m) > 0.0) and p >= 1.0 and q >= 0.0) or (alpha is not None and not alpha > 0.0):
             raise ValueError("the stress aggregate needs m > 0, p >= 1, q >= 0 and alpha > 0")
-        if not np.all(self.weights >= 0.0):
+        if not np.all(weights >= 0.0):
             raise ValueError("the stress aggregate needs weights >= 0")
-        self.u, self.rho, self.mesh = u, rho, V.mesh
+        self.u, self.rho, self.mesh, self.n_cases = u, rho, mesh, n_cases
+        self.m, self.weights = m, weights
         self.E, self.nu, self.p, self.q = float(E), float(nu), float(p), float(q)
         self.alpha = float(cell_volumes(self.mesh).sum() if alpha is None else alpha)
         self._grad = {}
@@ -1048,6 +832,21 @@ class MultiLoadPnormStress(BackendForm):
             out.fill(0.0)
         return out
 
+
+class MultiLoadPnormStress(ElasticityPnormStress):
+    """J = sum_l w_l J_l, J_l = (1/alpha) sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p, over the load cases of a
+    Function(LoadCaseSpace(V, L)): the worst stress over all load cases as one p-norm constraint.  ``m``: a scalar or one
+    scale per load case (the loads differ in magnitude); ``weights`` >= 0, 1 without; p, q, alpha shared, alpha = |Omega|
+    unless given.  dJ/du is non-zero on the clamped dofs of every column: the exact reduced gradient needs
+    ``fea.consistent_bc_partials``."""
+
+    def __init__(self, u: Function, rho: Function, E: float = 1.0, nu: float = 0.3, m=1.0, p: float = 8.0, q: float = 0.5,
+                 alpha: Optional[float] = None, weights=None):
+        V = _check_multi_stress_spaces("MultiLoadPnormStress", u, rho)
+        m = _per_case("MultiLoadPnormStress", "scales m", m, V.n_cases)
+        weights = np.ones(V.n_cases) if weights is None else _per_case("MultiLoadPnormStress", "weights", weights, V.n_cases)
+        self._setup(u, rho, V.mesh, V.n_cases, m, weights, E, nu, p, q, alpha)
+
     def set_scales_from_state(self) -> np.ndarray:
         """m_l = 1 / max_e rho_e^q sigma_vm,e(u_l) from the current state and density, so that the terms of every aggregate
         are O(1).  A load case without stress keeps its scale."""
@@ -1060,25 +859,22 @@ class MultiLoadPnormStress(BackendForm):
         return self.m.copy()
 
 
-class MultiLoadVonMises(BackendForm):
-    """The cell field max_l s_l rho_e^q sigma_vm,e(u_l) over the load cases of a Function(LoadCaseSpace(V, L)) -- the envelope
-    -- or, with ``load_case``, s_l rho_e^q sigma_vm,e(u_l) of that load case alone.  ``scales`` > 0: one per load case, 1
-    without.  Projected onto DG0 and CG1 as `ElasticityVonMises` is."""
+class ElasticityVonMises(BackendForm):
+    """The cell field rho_e^q sigma_vm,e (q = 0: the stress of the solid material, no density needed); over several columns
+    max_l s_l rho_e^q sigma_vm,e(u_l), or the field of one of them.  `project` hands the projection over: onto a DG0 target
+    the cell values themselves, onto CG1 the L2 projection of a cell-wise constant."""
     rank = 0
 
-    def __init__(self, u: Function, rho: Optional[Function] = None, E: float = 1.0, nu: float = 0.3, q: float = 0.0,
-                 scales=None, load_case: Optional[int] = None):
-        V = _check_multi_stress_spaces("MultiLoadVonMises", u, rho)
+    def __init__(self, u: Function, rho: Optional[Function] = None, E: float = 1.0, nu: float = 0.3, q: float = 0.0):
+        _check_stress_spaces("ElasticityVonMises", u, rho)
+        self._setup(u, rho, u.function_space.mesh, 1, None, None, E, nu, q)
+
+    def _setup(self, u, rho, mesh, n_cases, scales, load_case, E, nu, q) -> None:
         if not q >= 0.0 or (q > 0.0 and rho is None):
             raise ValueError("the relaxed von Mises stress needs q >= 0, and the density when q > 0")
-        if load_case is not None and not 0 <= int(load_case) < V.n_cases:
-            raise ValueError(f"MultiLoadVonMises: load case {load_case} of {V.n_cases}")
-        self.scales = None if scales is None else _per_case("MultiLoadVonMises", "scales", scales, V.n_cases)
-        if self.scales is not None and not np.all(self.scales > 0.0):
-            raise ValueError("MultiLoadVonMises needs scales > 0")
-        self.u, self.rho, self.mesh, self.n_cases = u, rho, V.mesh, V.n_cases
+        self.u, self.rho, self.mesh, self.n_cases = u, rho, mesh, n_cases
+        self.scales, self.load_case = scales, load_case
         self.E, self.nu, self.q = float(E), float(nu), float(q)
-        self.load_case = None if load_case is None else int(load_case)
         self._cells = None
 
     def functions(self):
@@ -1104,8 +900,24 @@ class MultiLoadVonMises(BackendForm):
         self._field(self._cells.vec)
         self._cells.version += 1
         from .utils_hip import project
-        project(self._cells, target, lump_mass=lump_mass)
+        project(self._cells, target, lump_mass=lump_mass)           # the cell-constant path PowerExpr takes
         return target
+
+
+class MultiLoadVonMises(ElasticityVonMises):
+    """The cell field max_l s_l rho_e^q sigma_vm,e(u_l) over the load cases of a Function(LoadCaseSpace(V, L)) -- the envelope
+    -- or, with ``load_case``, s_l rho_e^q sigma_vm,e(u_l) of that load case alone.  ``scales`` > 0: one per load case, 1
+    without.  Projected onto DG0 and CG1 as `ElasticityVonMises` is."""
+
+    def __init__(self, u: Function, rho: Optional[Function] = None, E: float = 1.0, nu: float = 0.3, q: float = 0.0,
+                 scales=None, load_case: Optional[int] = None):
+        V = _check_multi_stress_spaces("MultiLoadVonMises", u, rho)
+        if load_case is not None and not 0 <= int(load_case) < V.n_cases:
+            raise ValueError(f"MultiLoadVonMises: load case {load_case} of {V.n_cases}")
+        scales = None if scales is None else _per_case("MultiLoadVonMises", "scales", scales, V.n_cases)
+        if scales is not None and not np.all(scales > 0.0):
+            raise ValueError("MultiLoadVonMises needs scales > 0")
+        self._setup(u, rho, V.mesh, V.n_cases, scales, None if load_case is None else int(load_case), E, nu, q)
 
 
 def averageFunc(func: Function) -> LinearFunctional:

@@ -626,7 +626,10 @@ int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rh
  * q >= 0, alpha > 0; rho_e > 0 is the caller's contract when q > 0.                                                     */
 int femo_elast_pnorm_stress(femo_elast* e, const femo_vec* rho, const femo_vec* u, double m, double p, double q, double alpha,
                             double* value, femo_vec* grad_u, femo_vec* grad_rho, int accumulate);
-/* out_cells[n_cell] = rho_e^q sigma_vm,e, the cell field of the aggregate above; rho may be NULL when q == 0.           */
+/* out_cells[n_cell] = rho_e^q sigma_vm,e, the cell field of the aggregate above; rho may be NULL when q == 0.  The value is
+ * written as it is: a non-finite state gives a non-finite stress in the cells it touches.  Both entry points are the
+ * one-column case (m, w = 1, scale = 1) of the _multi forms below and run one-column instantiations of the same kernels
+ * (csrc/elast_stress.hip); femo_elast_apply and femo_elast_drho likewise share one body each with their _multi forms.    */
 int femo_elast_von_mises(femo_elast* e, const femo_vec* rho, const femo_vec* u, double q, femo_vec* out_cells);
 /* A x = b by device-resident PCG with the block-Jacobi preconditioner (solveKSP_mumps, utils_dolfinx.py:476-493); K is
  * symmetric, so the adjoint solve is the same call.  Fixed dofs: x = b there.  Stops on sqrt(r^T M^-1 r) <=
@@ -659,7 +662,7 @@ int femo_elast_solve_multi(femo_elast* e, int n_cols, const femo_vec* b, femo_ve
  *   transpose = 0:  y_l[n_dof] (+)= sum_e C'(rho_e) x_e K0_e u_{l,e}           (x: n_cell, y: n_cols * n_dof)             */
 int femo_elast_drho_multi(femo_elast* e, int method, int transpose, int n_cols, const femo_vec* rho, const femo_vec* u,
                           const femo_vec* x, femo_vec* y, int accumulate);
-/* femo_elast_pnorm_stress for n_cols states u_l in one pass (csrc/elast_stress_multi.hip): one aggregate per load case,
+/* femo_elast_pnorm_stress for n_cols states u_l in one pass (csrc/elast_stress.hip): one aggregate per load case,
  *   J_l = 1/alpha sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p,     J = sum_l w_l J_l
  * with one scale m_l > 0 per load case, weights w_l >= 0 (NULL = 1), and p, q, alpha shared.  The cell geometry and rho^q
  * are computed once per cell (and once per cell visit of the vertex walk) for all columns.  Any output may be NULL:
@@ -674,7 +677,7 @@ int femo_elast_pnorm_stress_multi(femo_elast* e, int n_cols, const femo_vec* rho
                                   int accumulate);
 /* out_cells[n_cell] = max_l scale_l rho_e^q sigma_vm,e(u_l), the envelope over the load cases (column = -1), or
  * scale_column rho_e^q sigma_vm,e(u_column) (0 <= column < n_cols).  scale > 0 per load case, NULL = 1; rho may be NULL
- * when q == 0.                                                                                                            */
+ * when q == 0.  With n_cols > 1 a NaN stress reads as 0 in the maximum; one column is written as it is.                */
 int femo_elast_von_mises_multi(femo_elast* e, int n_cols, const femo_vec* rho, const femo_vec* u,
                                const double* scale /* [n_cols] or NULL */, double q, int column, femo_vec* out_cells);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):

@@ -1,5 +1,5 @@
 """NumPy restatement of the aggregated von Mises stress over several load cases (femo_amd/fea/elasticity.py:
-MultiLoadPnormStress / MultiLoadVonMises; kernels in csrc/elast_stress_multi.hip), on top of tests/elast_stress_ref.py:
+MultiLoadPnormStress / MultiLoadVonMises; kernels in csrc/elast_stress.hip), on top of tests/elast_stress_ref.py:
 
   J_l = (1/alpha) sum_e |T_e| (m_l rho_e^q sigma_vm,e(u_l))^p       elast_stress_ref.pnorm_stress of column l with scale m_l
   J   = sum_l w_l J_l

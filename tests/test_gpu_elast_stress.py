@@ -1,6 +1,7 @@
-"""GPU tests of the aggregated von Mises stress of the SIMP elasticity (csrc/elasticity.hip: k_elast_stress_cell,
-k_elast_stress_du; femo_elast_pnorm_stress / femo_elast_von_mises) against the restatement tests/elast_stress_ref.py:
-kernel parity, closed forms, the zero-stress guard, bitwise reproducibility, the projected field, and the 16 x 8 cantilever
+"""GPU tests of the aggregated von Mises stress of the SIMP elasticity (csrc/elast_stress.hip: the one-column instantiations
+of k_elast_stress_cell_multi and k_elast_stress_du_multi; femo_elast_pnorm_stress / femo_elast_von_mises) against the
+restatement tests/elast_stress_ref.py: kernel parity, closed forms, the zero-stress guard, a non-finite state, bitwise
+reproducibility, the projected field, and the 16 x 8 cantilever
 through FEAModel + GeneralFilterModel + Simulator with the first adjoint right-hand side that is not the load."""
 import numpy as np
 import pytest
@@ -101,6 +102,29 @@ def test_zero_displacement(gpu, name):
         J, du, drho = _all_three(gpu, dev, rv, uv, 2.0, p, q, 1.0)
         assert J == 0.0
         assert np.all(np.isfinite(du)) and np.all(du == 0.0) and np.all(np.isfinite(drho)) and np.all(drho == 0.0)
+
+
+@pytest.mark.parametrize("name", ["square9j", "cube4j"])
+def test_non_finite_state_shows_in_the_field(gpu, name):
+    """One NaN entry of the state: NaN in exactly the cells that touch that vertex (the field is written as it is, not
+    through a maximum that would turn it into 0), finite values elsewhere, and the handle still works afterwards."""
+    from femo_amd.engine import Vec
+    mesh = _meshes()[name]()
+    u, rho, m = sref.random_inputs(mesh.x, mesh.conn, seed=5)
+    good = sref.pnorm_stress(mesh.x, mesh.conn, rho, u, m, 8.0, 0.5)
+    vertex = mesh.n_vert // 2
+    bad = u.copy()
+    bad[vertex * mesh.tdim + 1] = np.nan
+    touching = np.any(mesh.conn == vertex, axis=1)
+    assert 0 < touching.sum() < mesh.n_cell
+    dev, rv, uv = _device(gpu, mesh, rho, bad)
+    cells = Vec(gpu, mesh.n_cell)
+    for field in (np.array(dev.von_mises(uv, cells, rv, 0.5).get()), np.array(dev.von_mises(uv, cells).get())):
+        assert np.array_equal(np.isnan(field), touching) and np.all(np.isfinite(field[~touching]))
+    uv.set(u)
+    field = np.array(dev.von_mises(uv, cells, rv, 0.5).get())
+    assert np.abs(field - good["field"]).max() <= 1e-12 * np.abs(good["field"]).max()
+    assert abs(dev.pnorm_stress(rv, uv, m, 8.0, 0.5, good["alpha"]) - good["value"]) <= 1e-12 * good["value"]
 
 
 def test_reproducible_bit_for_bit(gpu):

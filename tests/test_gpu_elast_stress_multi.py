@@ -1,8 +1,8 @@
-"""GPU tests of the aggregated von Mises stress over several load cases (csrc/elast_stress_multi.hip:
+"""GPU tests of the aggregated von Mises stress over several load cases (csrc/elast_stress.hip:
 k_elast_stress_cell_multi, k_elast_stress_du_multi; femo_elast_pnorm_stress_multi / femo_elast_von_mises_multi;
 MultiLoadPnormStress / MultiLoadVonMises) against the restatement tests/elast_stress_multi_ref.py and the single-column
 entry points: kernel parity, accumulate, one output at a time, zero columns and zero weights, bitwise reproducibility,
-limits, the batched solve with right-hand sides that are live on the fixed dofs, the projected fields, and the 16 x 8
+the partials buffer shared with the single-column entry point, limits, the batched solve with right-hand sides that are live on the fixed dofs, the projected fields, and the 16 x 8
 cantilever with three loads through FEAModel + GeneralFilterModel + Simulator with the Dirichlet filter in every column.
 
 L = 1, 3, 5, 8: one column, a chunk of the dJ/du kernel that is not full, a ragged second chunk (4 + 1), the maximum."""
@@ -101,7 +101,7 @@ def test_kernel_parity(gpu, name, L, p, q):
 @pytest.mark.parametrize("name", MESHES)
 def test_matches_single_column(gpu, name, L):
     """Column by column against femo_elast_pnorm_stress / femo_elast_von_mises with m_l, and dJ/drho against their
-    accumulated calls in ascending l."""
+    accumulated calls in ascending l: the chunked instantiations of the two kernels against the one-column ones."""
     from femo_amd.engine import Vec
     mesh, U, rho, m, w = inputs(name, L)
     p, q = 8.0, 0.5
@@ -193,6 +193,28 @@ def test_reproducible_bit_for_bit(gpu):
     J1, du1, dr1 = _all_three(gpu, dev, 5, rv, uv, m, 8.0, 0.5, 1.0, w)
     J2, du2, dr2 = _all_three(gpu, dev, 5, rv, uv, m, 8.0, 0.5, 1.0, w)
     assert np.array_equal(J1, J2) and np.array_equal(du1, du2) and np.array_equal(dr1, dr2)
+
+
+def test_partials_buffer_shared_with_single_column(gpu):
+    """The single-column and the batched aggregate fold through one partials buffer, sized for all columns by whichever call
+    allocates it: one column, eight, one again on one handle, and eight first on a fresh one, give the same bits."""
+    name, L, p, q = "cube6j", 8, 8.0, 0.5
+    mesh, U, rho, m, w = inputs(name, L)
+    assert (mesh.n_cell + 255) // 256 == 6
+    R = restated(name, L, p, q)
+    dev, rv, uv = _device(gpu, mesh, rho, U)
+    from femo_amd.engine import Vec
+    u0 = Vec(gpu, U.shape[1]).set(U[0])
+    first = dev.pnorm_stress(rv, u0, m[0], p, q, R["alpha"])
+    eight = dev.pnorm_stress_multi(L, rv, uv, m, p, q, R["alpha"])
+    again = dev.pnorm_stress(rv, u0, m[0], p, q, R["alpha"])
+    fresh, rv2, uv2 = _device(gpu, mesh, rho, U)
+    eight_first = fresh.pnorm_stress_multi(L, rv2, uv2, m, p, q, R["alpha"])
+    u02 = Vec(gpu, U.shape[1]).set(U[0])
+    then_one = fresh.pnorm_stress(rv2, u02, m[0], p, q, R["alpha"])
+    print(f"one column {first!r}, eight {eight!r}")
+    assert first == again == then_one and np.array_equal(eight, eight_first)
+    assert max(abs(eight[l] - R["values"][l]) / R["values"][l] for l in range(L)) <= 1e-12
 
 
 def test_limits(gpu):
