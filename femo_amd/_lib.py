@@ -213,6 +213,7 @@ PROTOTYPES = {
     "femo_elast_pnorm_stress_multi": (C.c_int, [H, C.c_int, H, H, c_f64p, c_f64p, C.c_double, C.c_double, C.c_double, c_f64p,
                                                 H, H, C.c_int]),
     "femo_elast_von_mises_multi": (C.c_int, [H, C.c_int, H, H, c_f64p, C.c_double, C.c_int, H]),
+    "femo_elast_body_apply": (C.c_int, [H, C.c_int, c_f64p, C.c_int, C.c_double, H, H, C.c_int, H, C.c_int]),
     "femo_elast_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "femo_elast_pc_setup": (C.c_int, [H, C.c_double]),
     "femo_elast_pc_info": (C.c_int, [H, c_i64p]),

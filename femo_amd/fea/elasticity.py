@@ -1,6 +1,6 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
-product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip).  One load case is the L = 1 case of several:
+product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
@@ -11,6 +11,14 @@ are used unchanged.
                        C = rho^3 (SIMP) or rho / (1 + 8 (1 - rho)) (RAMP); sigma_0 = lambda_0 tr(eps) I + 2 mu_0 eps with
                        lambda_0 = E nu / ((1 + nu)(1 - 2 nu)), mu_0 = E / (2 (1 + nu)) -- plane strain in 2-D
   Compliance           J = int_ds(tag) t . u ds = F^T u                                                 (compliance, :108-109)
+  body forces          ``body_force`` / ``body_forces`` of the residuals and compliances: self-weight and inertial load cases
+                       (gravity, pull-up, lateral manoeuvres).  b = mass density times acceleration, constant per load case;
+                       the mass is linear in rho, so F(rho) = T + G_b rho with (G_b rho)[d v + i] = b_i sum_{e around v}
+                       rho_e |T_e| / (d + 1).  R = K(rho) u - F(rho), dR/drho = C'(rho) K0 u - G_b, J = sum_l w_l F_l(rho) . u_l
+                       with dJ/drho = G_{wB}^T u: one launch each for all load cases (csrc/elast_body.hip).  Not in the
+                       reference's script.  RAMP is the usual stiffness law here (SIMP's rho^3 against the linear mass gives
+                       large displacements at low density), and the exact reduced gradient needs
+                       ``fea.consistent_bc_partials = True``: F(rho) is non-zero on clamped vertices
   averageFunc          (1/|Omega|) int rho dx as a LinearFunctional with the DG0 coefficient |T_e| / |Omega| (:103-106)
   ElasticityPnormStress  J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p, the aggregated von Mises stress of the solid
                        material: sigma_vm = sqrt(3/2 s : s), s the deviator of sigma_0(u) as a 3 x 3 tensor (plane strain in
@@ -200,6 +208,23 @@ class DeviceElasticity:
                                              x.handle, y.handle, int(bool(accumulate))))
         return y
 
+    def body_apply(self, n_cols: int, b, x: Vec, y: Vec, transpose: bool = False, a: float = 1.0, base: Optional[Vec] = None,
+                   zero_fixed: bool = False, accumulate: bool = False) -> Vec:
+        """The body-load operator G_B of the ``n_cols`` body forces ``b`` (n_cols x d) in one launch (csrc/elast_body.hip):
+        column l of y = [y if ``accumulate``, else ``base`` or 0] + a b_l sum_{c around v} x_c |T_c| / (d + 1) from the cell
+        vector x, with 0 on the dofs of the fixed set when ``zero_fixed``; ``transpose``: y[n_cell] (+)= a G_B^T x from the
+        n_cols columns of x."""
+        bv = np.asarray(b, dtype=np.float64).reshape(-1, self.d) if np.size(b) else np.zeros((0, self.d))
+        n_cols = self._cols(n_cols, x if transpose else y, base)
+        if bv.shape[0] != n_cols:
+            raise _lib.FemoError(f"body_apply: {n_cols} columns need as many body forces")
+        b3 = np.zeros((max(n_cols, 1), 3))
+        b3[:n_cols, :self.d] = bv
+        check(self.lib.femo_elast_body_apply(self.handle, n_cols, b3.ctypes.data_as(_lib.c_f64p), int(bool(transpose)),
+                                             float(a), x.handle, None if base is None else base.handle,
+                                             int(bool(zero_fixed)), y.handle, int(bool(accumulate))))
+        return y
+
     def pnorm_stress_multi(self, n_cols: int, rho: Vec, u: Vec, m, p: float, q: float, alpha: float, weights=None,
                            value: bool = True, grad_u: Optional[Vec] = None, grad_rho: Optional[Vec] = None,
                            accumulate: bool = False):
@@ -350,11 +375,39 @@ class Measure:
         return locate_entities_boundary(self.mesh, self.mesh.tdim - 1, lambda x: np.ones(x.shape[1], dtype=bool))
 
 
-def _traction(t, mesh) -> np.ndarray:
+def _traction(t, mesh) -> Optional[np.ndarray]:
+    """None: no traction (a load case that carries a body force alone)."""
+    if t is None:
+        return None
     tv = np.ravel(np.asarray(t.value if isinstance(t, Constant) else t, dtype=np.float64))
     if tv.size != mesh.tdim:
         raise ValueError(f"the traction needs {mesh.tdim} components")
     return tv
+
+
+def _body_forces(name: str, body_forces, n_cases: int, mesh) -> Optional[np.ndarray]:
+    """(n_cases, tdim) body forces, a None entry being the zero vector; None when there is no body force at all."""
+    if body_forces is None:
+        return None
+    body_forces = list(body_forces)
+    if len(body_forces) != n_cases:
+        raise ValueError(f"{name}: {n_cases} load cases need as many body forces")
+    if all(b is None for b in body_forces):
+        return None
+    B = np.zeros((n_cases, mesh.tdim))
+    for l, b in enumerate(body_forces):
+        if b is None:
+            continue
+        bv = np.ravel(np.asarray(b.value if isinstance(b, Constant) else b, dtype=np.float64))
+        if bv.size != mesh.tdim:
+            raise ValueError(f"{name}: the body force needs {mesh.tdim} components")
+        B[l] = bv
+    return B
+
+
+def _facets_of(measures, tractions) -> list:
+    """The tagged facets of every load case that has a traction (None for the others: they need none)."""
+    return [None if t is None else ds.facets() for ds, t in zip(measures, tractions)]
 
 
 def _load_vec(mesh, facets: np.ndarray, t: np.ndarray) -> Vec:
@@ -438,7 +491,8 @@ class MultiLoadElasticityMatrix(ElasticityMatrix):
 
 
 class _ElasticityDrho:
-    """dR/drho ((n_cases n_dof) x n_cell), matrix free: block l of column e = C'(rho_e) K0_e u_{l,e}."""
+    """dR/drho ((n_cases n_dof) x n_cell), matrix free: block l of column e = C'(rho_e) K0_e u_{l,e}, minus the body-load
+    operator G_B of a form with body forces (F depends on the density there), added onto the stiffness term."""
 
     def __init__(self, form: "ElasticityResidual"):
         self.form, self.mesh = form, form.mesh
@@ -449,11 +503,17 @@ class _ElasticityDrho:
 
     def mult(self, x: Vec, y: Vec) -> Vec:
         F = self.form
-        return F.device().drho_multi(F.method_id, False, F.n_cases, F.rho.vec, F.u.vec, x, y)
+        F.device().drho_multi(F.method_id, False, F.n_cases, F.rho.vec, F.u.vec, x, y)
+        if F.body is not None:
+            F.device().body_apply(F.n_cases, F.body, x, y, a=-1.0, accumulate=True)
+        return y
 
     def multTranspose(self, x: Vec, y: Vec) -> Vec:
         F = self.form
-        return F.device().drho_multi(F.method_id, True, F.n_cases, F.rho.vec, F.u.vec, x, y)
+        F.device().drho_multi(F.method_id, True, F.n_cases, F.rho.vec, F.u.vec, x, y)
+        if F.body is not None:
+            F.device().body_apply(F.n_cases, F.body, x, y, transpose=True, a=-1.0, accumulate=True)
+        return y
 
     def new_row_vec(self) -> Vec:
         if self._row is None:
@@ -467,24 +527,49 @@ class _ElasticityDrho:
 
 
 # ---------------------------------------------------------------------------------------------------------- forms ----
-def _loads_vec(mesh, facets_list, tractions, weights=None) -> Vec:
+def _loads_vec(mesh, facets_list, tractions, weights=None) -> Optional[Vec]:
     """Column l = w_l F_l (w = 1 without weights).  One unweighted column is the load of `_load_vec` itself; several are
-    placed through the host once and cached."""
+    placed through the host once and cached.  A load case without a traction (None) is a zero column; None when no load
+    case has one."""
+    if all(t is None for t in tractions):
+        return None
     if len(tractions) == 1 and weights is None:
         return _load_vec(mesh, facets_list[0], tractions[0])
     cache = mesh.__dict__.setdefault("_elast_multi_loads", {})
     w = np.ones(len(tractions)) if weights is None else np.asarray(weights, dtype=np.float64)
-    key = (id(_ctx()), tuple(hash(np.ascontiguousarray(f, dtype=np.int32).tobytes()) for f in facets_list),
-           tuple(tuple(t) for t in tractions), tuple(w))
+    key = (id(_ctx()), tuple(None if f is None else hash(np.ascontiguousarray(f, dtype=np.int32).tobytes()) for f in facets_list),
+           tuple(None if t is None else tuple(t) for t in tractions), tuple(w))
     F = cache.get(key)
     if F is None:
-        cols = [w[l] * np.array(_load_vec(mesh, facets_list[l], tractions[l]).get(), dtype=np.float64)
+        n = mesh.tdim * mesh.n_vert
+        cols = [np.zeros(n) if tractions[l] is None else
+                w[l] * np.array(_load_vec(mesh, facets_list[l], tractions[l]).get(), dtype=np.float64)
                 for l in range(len(tractions))]
-        F = cache[key] = Vec(_ctx(), len(cols) * cols[0].size).set(np.concatenate(cols))
+        F = cache[key] = Vec(_ctx(), len(cols) * n).set(np.concatenate(cols))
     return F
 
 
-def _multi_arguments(name: str, u: Function, tractions, measures):
+class _BodyLoad:
+    """The total load T + G_B rho of a form with body forces, in a Vec of the form's own: rebuilt by one G_B launch whenever
+    the density (its version or its vector) or the traction columns changed.  ``B``: (n_cases, tdim), weights included."""
+
+    def __init__(self, mesh, rho: Function, B: np.ndarray):
+        self.mesh, self.rho, self.B = mesh, rho, B
+        self.vec = None
+        self.key = None
+
+    def total(self, dev: "DeviceElasticity", traction: Optional[Vec], zero_fixed: bool = False) -> Vec:
+        key = (self.rho.version, id(self.rho.vec), id(traction), dev.fixed_key if zero_fixed else None)
+        if key != self.key:
+            L = self.B.shape[0]
+            if self.vec is None:
+                self.vec = Vec(_ctx(), L * dev.n_dof)
+            dev.body_apply(L, self.B, self.rho.vec, self.vec, base=traction, zero_fixed=zero_fixed)
+            self.key = key
+        return self.vec
+
+
+def _multi_arguments(name: str, u: Function, tractions, measures, body_forces=None):
     V = u.function_space
     if not isinstance(V, LoadCaseSpace):
         raise NotImplementedError(f"{name} needs a Function(LoadCaseSpace(V, n_cases)) state")
@@ -494,14 +579,23 @@ def _multi_arguments(name: str, u: Function, tractions, measures):
     measures = [None] * len(tractions) if measures is None else list(measures)
     if len(tractions) != V.n_cases or len(measures) != V.n_cases:
         raise ValueError(f"{name}: {V.n_cases} load cases need as many tractions and measures")
+    if any(t is None for t in tractions) and _body_forces(name, body_forces, V.n_cases, V.mesh) is None:
+        raise ValueError(f"{name}: a load case without a traction needs a body force")
     ts = [_traction(t, V.mesh) for t in tractions]
     dss = [ds if ds is not None else Measure("ds", domain=V.mesh) for ds in measures]
-    return V, ts, dss
+    return V, ts, dss, _body_forces(name, body_forces, V.n_cases, V.mesh)
 
 
 class ElasticityResidual(BackendForm):
-    """R(u; rho) = K(rho) u - F(t) with the tagged traction ``ds`` (see the module docstring).  ``n_cases`` columns (one
-    here), ``n_dof`` dofs per column; every product and solve is the batched one over all columns."""
+    """R(u; rho) = K(rho) u - F(rho) with F = the tagged traction ``ds`` (see the module docstring) plus, with
+    ``body_force`` b (mass density times acceleration, constant), the self-weight G_b rho: rho_e |T_e| b / (d + 1) at every
+    vertex of cell e.  ``traction`` may be None with a body force.  ``n_cases`` columns (one here), ``n_dof`` dofs per
+    column; every product and solve is the batched one over all columns.
+
+    With a body force `load` is the total F(rho), rebuilt in one launch when the density changes, and dR/drho gains
+    -G_b.  RAMP is the usual stiffness law with self-weight: SIMP's rho^3 against the linear mass gives large displacements
+    at low density.  F(rho) is non-zero on clamped vertices, so the adjoint is non-zero on fixed dofs: the exact reduced
+    gradient needs ``fea.consistent_bc_partials = True``, as for `MultiLoadPnormStress`."""
     rank = 1
     is_linear = True
     is_symmetric = True
@@ -509,16 +603,19 @@ class ElasticityResidual(BackendForm):
     matrix_class = ElasticityMatrix
 
     def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, E: float = 1.0,
-                 nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi"):
+                 nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None):
         V = u.function_space
         if not isinstance(V, VectorFunctionSpace):
             raise NotImplementedError("ElasticityResidual needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
         self.t = _traction(traction, V.mesh)
         self.ds = ds if ds is not None else Measure("ds", domain=V.mesh)
-        self._setup(u, rho, V, 1, [self.t], [self.ds], E, nu, method, preconditioner)
+        body = _body_forces("ElasticityResidual", None if body_force is None else [body_force], 1, V.mesh)
+        if self.t is None and body is None:
+            raise ValueError("ElasticityResidual: without a traction the load needs a body force")
+        self._setup(u, rho, V, 1, [self.t], [self.ds], E, nu, method, preconditioner, body)
 
-    def _setup(self, u, rho, V, n_cases, tractions, measures, E, nu, method, preconditioner) -> None:
-        """``V``: the space of one column (the numbering of the bcs)."""
+    def _setup(self, u, rho, V, n_cases, tractions, measures, E, nu, method, preconditioner, body=None) -> None:
+        """``V``: the space of one column (the numbering of the bcs); ``body``: (n_cases, tdim) body forces or None."""
         if rho.function_space.family != "DG" or rho.function_space.mesh is not V.mesh:
             raise NotImplementedError(f"{type(self).__name__} needs a DG0 density on the state's mesh")
         if method not in METHODS:
@@ -530,6 +627,10 @@ class ElasticityResidual(BackendForm):
         self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
         self.n_cases, self.n_dof = n_cases, V.dim
         self.tractions, self.measures = tractions, measures
+        self.body = body
+        self._body_load = self._body_rhs = None
+        if body is not None:
+            self._body_load, self._body_rhs = _BodyLoad(V.mesh, rho, body), _BodyLoad(V.mesh, rho, body)
         self.rtol = 1e-15
         self._key = None
         self._mask = None
@@ -544,8 +645,13 @@ class ElasticityResidual(BackendForm):
     def device(self) -> DeviceElasticity:
         return elasticity_handle(self.mesh, self.E, self.nu)
 
+    def _traction_load(self) -> Optional[Vec]:
+        return _loads_vec(self.mesh, _facets_of(self.measures, self.tractions), self.tractions)
+
     def load(self) -> Vec:
-        return _loads_vec(self.mesh, [ds.facets() for ds in self.measures], self.tractions)
+        """Column l: the total load F_l(rho)."""
+        T = self._traction_load()
+        return T if self.body is None else self._body_load.total(self.device(), T)
 
     def _set_bcs(self, bcs) -> None:
         mask, self._vals = _fixed_data(self.n_dof, bcs)
@@ -613,12 +719,15 @@ class ElasticityResidual(BackendForm):
 
     def _rhs(self, dev: DeviceElasticity) -> Vec:
         """Column l: F_l with the Dirichlet lifting, b_l = F_l - K g, b_l = g on the fixed dofs (the same fixed set and
-        the same values for every column)."""
-        F = self.load()
+        the same values for every column).  With body forces and homogeneous values it is built on the device in the launch
+        that forms the body load (the traction columns as its base, zeros on the fixed dofs), once per density."""
         if self._mask is None:
-            return F
+            return self.load()
         fixed = self._mask == 1
         nonzero = bool(np.any(self._vals[fixed] != 0.0))
+        if self.body is not None and not nonzero:
+            return self._body_rhs.total(dev, self._traction_load(), zero_fixed=True)
+        F = self.load()
         key = (id(F), hash(self._mask.tobytes()))
         if not nonzero and self._rhs_cache is not None and self._rhs_cache[0] == key:
             return self._rhs_cache[1]
@@ -648,7 +757,9 @@ class ElasticityResidual(BackendForm):
 
 
 class MultiLoadElasticityResidual(ElasticityResidual):
-    """Column l of the residual is K(rho) u_l - F_l, with F_l the traction ``tractions[l]`` on ``measures[l]``: L load cases
+    """Column l of the residual is K(rho) u_l - F_l, with F_l the traction ``tractions[l]`` on ``measures[l]`` plus, with
+    ``body_forces`` (one per load case, None = none), the inertial load G_{b_l} rho of `ElasticityResidual` -- gravity, a
+    pull-up, a lateral manoeuvre; a load case with a body force may have None as its traction: L load cases
     on one stiffness matrix, one fixed set and one preconditioner.  ``u`` is a Function(LoadCaseSpace(V, L)).  The state
     solve, the adjoint solve (`apply_inverse_jacobian`) and the forward-mode solve are each ONE batched PCG over all columns
     (`DeviceElasticity.solve_multi`): a converged column is frozen while the others iterate.
@@ -664,9 +775,9 @@ class MultiLoadElasticityResidual(ElasticityResidual):
     matrix_class = MultiLoadElasticityMatrix
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, E: float = 1.0, nu: float = 0.3,
-                 method: str = "SIMP", preconditioner: str = "jacobi"):
-        V, ts, dss = _multi_arguments("MultiLoadElasticityResidual", u, tractions, measures)
-        self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner)
+                 method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None):
+        V, ts, dss, body = _multi_arguments("MultiLoadElasticityResidual", u, tractions, measures, body_forces)
+        self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner, body)
         self.solve_counts = {"state": 0, "adjoint": 0}
 
     def _record(self, infos, kind: str):
@@ -692,49 +803,69 @@ class MultiLoadElasticityResidual(ElasticityResidual):
 
 class Compliance(BackendForm):
     """J = int_ds t . u ds = F^T u (compliance, run_topo_opt_cantilever_beam.py:108-109); over several columns
-    J = sum_l w_l F_l . u_l."""
+    J = sum_l w_l F_l . u_l.  With ``body_force`` the load is the total F(rho) = T + G_b rho of `ElasticityResidual`: the
+    density ``rho`` is then required, the form depends on (u, rho), and dJ/drho = G_{wB}^T u (one launch)."""
     rank = 0
 
-    def __init__(self, u: Function, traction, ds: Optional[Measure] = None):
+    def __init__(self, u: Function, traction, ds: Optional[Measure] = None, body_force=None, rho: Optional[Function] = None):
         if not isinstance(u.function_space, VectorFunctionSpace):
             raise NotImplementedError("Compliance needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
         self.u, self.mesh = u, u.function_space.mesh
         self.t = _traction(traction, self.mesh)
         self.ds = ds if ds is not None else Measure("ds", domain=self.mesh)
         self.tractions, self.measures, self.weights = [self.t], [self.ds], None
-        self._grad = None
+        self._set_body("Compliance", _body_forces("Compliance", None if body_force is None else [body_force], 1, self.mesh), rho)
+        self._grad = {}
+
+    def _set_body(self, name: str, body: Optional[np.ndarray], rho: Optional[Function]) -> None:
+        """``body``: (n_cases, tdim) or None; kept with the weights folded in (column l = w_l b_l)."""
+        if body is None and any(t is None for t in self.tractions):
+            raise ValueError(f"{name}: a load case without a traction needs a body force")
+        if body is not None:
+            if rho is None:
+                raise ValueError(f"{name}: the load of a body force depends on the density: pass rho")
+            if rho.function_space.family != "DG" or rho.function_space.mesh is not self.mesh:
+                raise NotImplementedError(f"{name} needs a DG0 density on the state's mesh")
+            if self.weights is not None:
+                body = body * np.asarray(self.weights, dtype=np.float64)[:, None]
+        self.body, self.rho = body, rho if body is not None else None
+        self._body_load = None if body is None else _BodyLoad(self.mesh, rho, body)
 
     def functions(self):
-        return (self.u,)
+        return (self.u,) if self.body is None else (self.u, self.rho)
 
     def load(self) -> Vec:
-        """Column l = w_l F_l."""
-        return _loads_vec(self.mesh, [ds.facets() for ds in self.measures], self.tractions, self.weights)
+        """Column l = w_l F_l, the total load with body forces."""
+        T = _loads_vec(self.mesh, _facets_of(self.measures, self.tractions), self.tractions, self.weights)
+        return T if self.body is None else self._body_load.total(elasticity_handle(self.mesh), T)
 
     def assemble_scalar(self) -> float:
         return self.load().dot(self.u.vec, self.u.function_space.dim)
 
     def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        n = wrt.function_space.dim
-        if out is None:
-            if self._grad is None or self._grad.n != n:
-                self._grad = Vec(_ctx(), n)
-            out = self._grad
+        if out is None:                                            # one buffer per argument: both partials may be pending
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
         if wrt is self.u:
             return out.copy_from(self.load())
+        if self.body is not None and wrt is self.rho:
+            return elasticity_handle(self.mesh).body_apply(self.body.shape[0], self.body, self.u.vec, out, transpose=True)
         return out.fill(0.0)
 
 
 class MultiLoadCompliance(Compliance):
-    """J = sum_l w_l F_l . u_l over the load cases of a Function(LoadCaseSpace(V, L)) (w = 1 without ``weights``)."""
+    """J = sum_l w_l F_l . u_l over the load cases of a Function(LoadCaseSpace(V, L)) (w = 1 without ``weights``); with
+    ``body_forces`` (and the density ``rho``) F_l is the total load of `MultiLoadElasticityResidual`."""
 
-    def __init__(self, u: Function, tractions, measures=None, weights=None):
-        V, self.tractions, self.measures = _multi_arguments("MultiLoadCompliance", u, tractions, measures)
+    def __init__(self, u: Function, tractions, measures=None, weights=None, body_forces=None, rho: Optional[Function] = None):
+        V, self.tractions, self.measures, body = _multi_arguments("MultiLoadCompliance", u, tractions, measures, body_forces)
         self.u, self.mesh = u, V.mesh
         self.weights = np.ones(V.n_cases) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
         if self.weights.size != V.n_cases:
             raise ValueError(f"MultiLoadCompliance: {V.n_cases} load cases need as many weights")
-        self._grad = None
+        self._set_body("MultiLoadCompliance", body, rho)
+        self._grad = {}
 
 
 def cell_volumes(mesh) -> np.ndarray:
@@ -933,25 +1064,29 @@ def averageFunc(func: Function) -> LinearFunctional:
 
 # ---------------------------------------------------------------------------- builders of the run script (:85-109) ----
 def pdeRes(u, v, rho_e, f, E: float = 1.0, dss: Optional[Measure] = None, method: str = "SIMP",
-           preconditioner: str = "jacobi") -> ElasticityResidual:
-    """run_topo_opt_cantilever_beam.py:85-101 (nu = 0.3 as there); ``v`` is implied by the catalogue."""
-    return ElasticityResidual(u, rho_e, f, dss, E=E, nu=0.3, method=method, preconditioner=preconditioner)
+           preconditioner: str = "jacobi", body_force=None) -> ElasticityResidual:
+    """run_topo_opt_cantilever_beam.py:85-101 (nu = 0.3 as there); ``v`` is implied by the catalogue.  ``body_force``: the
+    self-weight rho b dx (not in the reference's script); ``f`` may then be None."""
+    return ElasticityResidual(u, rho_e, f, dss, E=E, nu=0.3, method=method, preconditioner=preconditioner,
+                              body_force=body_force)
 
 
-def compliance(u, f, dss: Optional[Measure] = None) -> Compliance:
-    """run_topo_opt_cantilever_beam.py:108-109"""
-    return Compliance(u, f, dss)
+def compliance(u, f, dss: Optional[Measure] = None, body_force=None, rho_e=None) -> Compliance:
+    """run_topo_opt_cantilever_beam.py:108-109; with ``body_force`` (and the density ``rho_e``) the work of the total load."""
+    return Compliance(u, f, dss, body_force=body_force, rho=rho_e)
 
 
 def pdeRes_multiload(u, v, rho_e, fs, dss_list=None, E: float = 1.0, method: str = "SIMP",
-                     preconditioner: str = "jacobi") -> MultiLoadElasticityResidual:
-    """`pdeRes` for the load cases ``fs[l]`` on ``dss_list[l]``; ``u`` is a Function(LoadCaseSpace(V, len(fs)))."""
-    return MultiLoadElasticityResidual(u, rho_e, fs, dss_list, E=E, nu=0.3, method=method, preconditioner=preconditioner)
+                     preconditioner: str = "jacobi", body_forces=None) -> MultiLoadElasticityResidual:
+    """`pdeRes` for the load cases ``fs[l]`` on ``dss_list[l]`` with the body forces ``body_forces[l]`` (None = none);
+    ``u`` is a Function(LoadCaseSpace(V, len(fs)))."""
+    return MultiLoadElasticityResidual(u, rho_e, fs, dss_list, E=E, nu=0.3, method=method, preconditioner=preconditioner,
+                                       body_forces=body_forces)
 
 
-def compliance_multiload(u, fs, dss_list=None, weights=None) -> MultiLoadCompliance:
-    """sum_l w_l int_ds(l) f_l . u_l ds"""
-    return MultiLoadCompliance(u, fs, dss_list, weights)
+def compliance_multiload(u, fs, dss_list=None, weights=None, body_forces=None, rho_e=None) -> MultiLoadCompliance:
+    """sum_l w_l F_l . u_l with F_l = int_ds(l) f_l . v ds + the body load of ``body_forces[l]`` (needs ``rho_e``)"""
+    return MultiLoadCompliance(u, fs, dss_list, weights, body_forces=body_forces, rho=rho_e)
 
 
 def pnorm_stress(u, rho_e, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0, q: float = 0.5,

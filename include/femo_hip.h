@@ -680,6 +680,20 @@ int femo_elast_pnorm_stress_multi(femo_elast* e, int n_cols, const femo_vec* rho
  * when q == 0.  With n_cols > 1 a NaN stress reads as 0 in the maximum; one column is written as it is.                */
 int femo_elast_von_mises_multi(femo_elast* e, int n_cols, const femo_vec* rho, const femo_vec* u,
                                const double* scale /* [n_cols] or NULL */, double q, int column, femo_vec* out_cells);
+/* Body loads: self-weight and inertial load cases (csrc/elast_body.hip).  A body force b_l in R^d (mass density times
+ * acceleration) is constant per load case; the mass is linear in the density, so the load is F_l(rho) = T_l + (G_B rho)_l
+ * with the linear operator G_B of B = (b_0 ... b_{n_cols-1}), b: n_cols * 3 doubles, unused components 0:
+ *   transpose = 0:  y[l n_dof + d v + i] = [accumulate ? y : (base ? base : 0)] + a b_l[i] sum_{c around v} x_c |T_c| / (d+1)
+ *                   (x: n_cell, y and base: n_cols * n_dof; base may be NULL).  zero_fixed = 1 writes 0 on the dofs of the
+ *                   fixed set of every column instead (needs femo_elast_set_fixed): with base = the traction columns that is
+ *                   the right-hand side for homogeneous supports in the same launch.
+ *   transpose = 1:  y[c] = (accumulate ? y[c] : 0) + a |T_c| / (d+1) sum_l b_l . sum_{v in c} x_l[v]
+ *                   (x: n_cols * n_dof, y: n_cell; base NULL and zero_fixed 0), summed in ascending l.
+ * dR/drho of R_l = K(rho) u_l - F_l(rho) is femo_elast_drho_multi - G_B, and d/drho of sum_l w_l F_l(rho) . u_l is G_{wB}^T u.
+ * One launch for all columns either way; the vertex sum and the cell volume are formed once for all of them.  No float
+ * atomics: the same bits every call, and column l does not depend on n_cols.                                             */
+int femo_elast_body_apply(femo_elast* e, int n_cols, const double* b /* [n_cols * 3] */, int transpose, double a,
+                          const femo_vec* x, const femo_vec* base /* or NULL */, int zero_fixed, femo_vec* y, int accumulate);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
  *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
  * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices
