@@ -497,7 +497,45 @@ int femo_launch_functional_grad_f(femo_mesh* m, int kind, const double* params, 
                                   const double* f, const double* ud, double* g);
 int femo_launch_spmv(const femo_mat* A, const double* vals, const double* x, double* y,
                      double* partials /* or null: fused dot(x,y) partials */);
-// y = K x - load outside the Dirichlet set, u - bcval on it (bcmask null: no set), one launch (solver.hip); its two inputs
+// One launch of the SELL product y = A x (spmv.hip), described by an aggregate built with designated initialisers at the
+// call site.  The values of FemoSpmvDots are the DOT template argument of k_spmv_sell; d = dvec, or x when dvec is null.
+enum FemoSpmvDots : int {
+  FEMO_DOTS_NONE = 0,
+  FEMO_DOTS_DAX = 1,        // d.Ax
+  FEMO_DOTS_DAX_XX = 2,     // d.Ax | x.x
+  FEMO_DOTS_DAX_AXAX = 3,   // d.Ax | Ax.Ax
+  FEMO_DOTS_TRIPLE = 4,     // x.Ax | Ax.Ax | dvec.Ax (merged BPX-PCG)
+};
+// slots of FEMO_MAX_PARTIALS doubles a variant writes behind `partials`
+constexpr int femo_spmv_dot_slots(FemoSpmvDots d) { return d == FEMO_DOTS_TRIPLE ? 3 : d >= FEMO_DOTS_DAX_XX ? 2 : d == FEMO_DOTS_DAX ? 1 : 0; }
+// ... and where the boundary launch of a two-launch product puts its own: that many slots behind the interior launch's, but
+// never nearer than the slot pair the classic BPX-PCG loop has always used (d.Ax alone: its slot 1 holds rho's partials)
+constexpr int femo_spmv_bnd_slots(FemoSpmvDots d) { return femo_spmv_dot_slots(d) > 2 ? femo_spmv_dot_slots(d) : 2; }
+struct FemoSpmv {
+  const double* vals;                   // d_vals, d_valsT or d_valsS of A
+  bool unit = false;                    // unit diagonal (S A S)
+  FemoSpmvDots dots = FEMO_DOTS_NONE;
+  double* partials = nullptr;           // per-block partials of `dots`
+  const double* dvec = nullptr;
+  const int32_t* done = nullptr;        // nothing once *done is set
+  const int32_t* slices = nullptr;      // walk this subset of the slices (n_slices of them) instead of all
+  int64_t n_slices = 0;
+  hipStream_t stream = nullptr;         // null: the context's compute stream
+  bool ghost = false;                   // slice list with flagged ghost slices: wait for the neighbours' counters, read the inbox
+};
+int femo_launch_spmv(const femo_mat* A, const double* x, double* y, const FemoSpmv& d);
+// y = A x with the ghosts of x refreshed first, by the route this mesh has: overlapped with the interior slices where the
+// mesh has interior / boundary lists, else refresh then multiply.  inflight: the refresh is already under way
+// (femo_pc_merged_sends_halo).  *g_int, *g_bnd: the block counts to fold (partials of the boundary launch, if there is
+// one, femo_spmv_bnd_slots further on)
+int femo_halo_spmv(const femo_mat* A, double* x, double* y, const FemoSpmv& d, int* g_int, int* g_bnd, bool inflight = false);
+int femo_halo_raw(femo_mesh* m, double* x, hipStream_t st);     // ghost refresh of a bare device array of n_vert entries
+// y = A^T x on a partitioned mesh by scatter + reverse halo add, A given by its own (untransposed) values
+int femo_spmv_transposed_scatter(const femo_mat* A, const double* vals, bool unit, const double* x, double* y, const int32_t* done);
+inline bool femo_transpose_is_local(const femo_mesh* m) { return m->n_nbr == 0; }   // can A^T's values be formed on this rank?
+int femo_mat_ensure_s(femo_mat* A);                        // S = diag^-1/2 of the current assembly
+int femo_mat_ensure_scaled(femo_mat* A, bool transpose);   // ... and S A S (or S A^T S)
+// y = K x - load outside the Dirichlet set, u - bcval on it (bcmask null: no set), one launch (spmv.hip); its two inputs
 // besides the operator: the cached load vector of f, and u with the prescribed values imposed (assemble.hip)
 int femo_launch_newton_rhs_linear(const femo_mat* K, const double* x, const double* u, const double* load,
                                   const uint8_t* bcmask, const double* bcval, double* y);
@@ -562,7 +600,7 @@ int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, con
 int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const FemoMergedVecs& V, double* S,
                          const int32_t* done, const struct FemoPcgStop* stop);
 // N > 1: does femo_pc_merged_apply start the halo exchange of the direction it produces (interface vertices first, send buffer
-// filled by the prolongation itself)?  Then the loop's SpMV must not exchange again: femo_halo_spmv_inflight.
+// filled by the prolongation itself)?  Then the loop's SpMV must not exchange again: femo_halo_spmv(inflight).
 bool femo_pc_merged_sends_halo(const femo_mesh* m);
 int femo_pc_merged_collectives(const femo_mesh* m);   // all-reduces per iteration of the merged loop on this mesh (0 on one rank)
 // nb_rho > 0: rho = rh.rh is folded from rho_partials[0:nb_rho] inside the apply (and stored to *rho)
