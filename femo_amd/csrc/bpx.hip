@@ -42,6 +42,30 @@ struct LatticeLevel {
   double* coef = nullptr;  // C_l * keep mask
 };
 
+// How the lattice kernels of a hierarchy are launched: everything below is fixed by the level sizes, n_fused and whether the
+// context has more than one rank, so femo_pc_build works it out once (pc_plan_launches) and the applies only read it.
+struct LaunchPlan {
+  int T = 0;                    // coarsest level the brick kernel fills
+  int64_t below = 0;            // nodes of levels 0 .. T-2
+  // classic apply: the fused cycle (k_lattice_coarse up to level T-1 + k_lattice_prolong3), or level by level with the
+  // levels 0 .. cut-1 in the single-workgroup kernel (coarse_total nodes; cut == 0: no such launch)
+  bool fused_cycle = false;
+  int cut = 0;
+  int64_t coarse_total = 0;
+  int top_in_lds = 0;           // k_lattice_coarse of either branch: g of its top level fits in LDS behind the levels below
+  size_t lds_coarse = 0;        // ... and its dynamic LDS bytes
+  int fine_grid = 0;            // k_lattice_prolong3: one workgroup per tile of 8^3 / 16^2 finest nodes, at most 2048
+  // merged loop
+  bool merged_ok = false;       // the shape the merged kernels are written for (pc_plan_launches)
+  size_t lds_merged = 0;        // k_lattice_coarse_m: levels 0 .. T-2, g of T-1, scratch of the separable restrictions
+  int64_t sep_off = -1;         // MergedCarry::sep_off
+  int flat = 0;                 // MergedCarry::flat
+  int64_t m_tiles = 0;          // k_lattice_prolong3_m: tiles walked (the rank's own where those are fewer: m_tile_list) ...
+  const int32_t* m_tile_list = nullptr;
+  bool m_small = false;         // ... with 128 threads each when 256-thread workgroups would not all be resident at once
+  int m_grid = 0;
+};
+
 }  // namespace
 
 struct femo_pc {
@@ -57,8 +81,8 @@ struct femo_pc {
   int parity = 0;
   int n_fused = 0;          // coarser levels the brick kernel restricts to directly (besides the finest)
   int brick_pf = 4;         // staging depth of the brick kernel: smallest of 2..4 with 256 x brick_pf >= the fullest brick
-  bool fused_cycle_seen = false;   // the last apply ran the fused lattice cycle (femo_pc_carries_xupdate)
-  bool coarse_lds_set = false;
+  LaunchPlan plan;
+  bool coarse_lds_set = false;     // k_lattice_coarse's dynamic-LDS limit raised for this hierarchy (raise_lds)
   // owned vertices sorted by brick (BRICK^dim bins of the finest lattice), for the restriction
   int64_t n_bricks = 0;
   int32_t* d_perm = nullptr;        // sorted position -> vertex
@@ -107,6 +131,10 @@ struct femo_pc {
   int32_t* d_my_tiles = nullptr;
   std::vector<uint8_t> tile_mine;     // host copy of the tile mask (from the brick list: every node a local vertex touches lies in one of them)
   double* coef_all = nullptr;         // the coef arrays of all levels, coarsest first, contiguous (like g_all)
+  // accumulators of level l: first copy, or (levels >= T, which != 0) the second, see g_alt
+  double* acc(int l, int which) const { return (l < plan.T || which == 0) ? L[l].g : g_alt + (L[l].g - L[plan.T].g); }
+  // merged loop: the state of level l >= T-1
+  double* state(int l) const { return gs + (L[l].g - L[plan.T - 1].g); }
 };
 
 namespace {
@@ -515,13 +543,6 @@ __global__ __launch_bounds__(FEMO_BLOCK, FEMO_BRICK_WAVES) void k_restrict_brick
 // 10 % from the third iteration on), independently of the mesh size -- unlike r^T D^-1 r, whose ratio to the
 // error grows like cond(D^-1 A) ~ n^2.  mode 2 stores tol^2 = rtol^2 * factor * gamma_0, mode 1 compares; every
 // block takes the same decision from the same numbers, block 0 publishes it.
-struct PcgStop {
-  double rtol2_factor;     // rtol^2 (x b.D^-1 b / r0.D^-1 r0 for a non-zero initial guess)
-  double atol_pc2;         // absolute threshold on gamma
-  double* tolg2;           // device scalar: rtol^2 * gamma_0
-  int32_t* flags;          // [0] stamp (it + 1) once converged, [1] iterations, [2] breakdown
-  int it;
-};
 // merged BPX-PCG: where gamma' = r.r + sum_l C g^2 comes from (S == nullptr: the classic apply)
 struct MergedScal {
   const double* S;
@@ -555,7 +576,7 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_prolong_mesh(int64_t n_rows, Lat
                                                              const double* __restrict__ dot_partials, const double* __restrict__ dot_global,
                                                              int nb_rho, const double* __restrict__ rho_partials, double* __restrict__ rho,
                                                              const double* __restrict__ gamma_cur, double* __restrict__ gamma_nxt,
-                                                             const int32_t* __restrict__ done, PcgStop st, MergedScal ms, HaloFirst hf) {
+                                                             const int32_t* __restrict__ done, FemoPcgStop st, MergedScal ms, HaloFirst hf) {
   const bool both = hf.n_send_blocks > 0;
   const bool role_send = both ? (int)blockIdx.x < hf.n_send_blocks : hf.n_verts > 0;   // this workgroup walks the send list
   const int bid = (both && !role_send) ? (int)blockIdx.x - hf.n_send_blocks : (int)blockIdx.x;
@@ -1745,6 +1766,8 @@ Lat make_lat(const femo_pc* pc, const LatticeLevel& l) {
 
 }  // namespace
 
+static void pc_plan_launches(femo_pc* pc, bool multi);
+
 // -------------------------------------------------------------------------------------
 int femo_pc_build(femo_mesh* m) {
   if (m->pc) return 0;
@@ -1846,6 +1869,7 @@ int femo_pc_build(femo_mesh* m) {
   FEMO_HIP_CHECK(hipMalloc(&pc->d_w_sorted, std::max<size_t>(P.perm.size(), 1) * sizeof(float)));
   FEMO_HIP_CHECK(hipMalloc(&pc->d_sinv, std::max<size_t>(P.perm.size(), 1) * sizeof(float)));
   FEMO_HIP_CHECK(hipMalloc(&pc->d_dot_partials, 4096 * sizeof(double)));
+  pc_plan_launches(pc, ctx->nranks > 1);
   m->pc = pc;
   return 0;
 }
@@ -1863,6 +1887,95 @@ void femo_pc_destroy(femo_mesh* m) {
   (void)hipFree(m->pc->d_mshared_idx); (void)hipFree(m->pc->d_mint_idx); (void)hipFree(m->pc->d_mbuf);
   delete m->pc;
   m->pc = nullptr;
+}
+
+// ---- template dispatch and the launch plan ---------------------------------------------------------------------------
+// f is a generic lambda that receives the mesh dimension (by_dim) or the staging depth of the brick kernel (by_brick_pf) as
+// a std::integral_constant: every templated kernel is instantiated for exactly the values listed here.
+template <class F>
+static auto by_dim(int dim, F&& f) { return dim == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 2>{}); }
+template <class F>
+static auto by_brick_pf(int pf, F&& f) {
+  return pf == 2 ? f(std::integral_constant<int, 2>{}) : pf == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 4>{});
+}
+
+// Dynamic LDS of a single-workgroup coarse kernel whose top level is `top`: g and e of the levels below it, and g of the top
+// level behind them where it fits (*top_in_lds: at most FEMO_COARSE_TOP_MAX nodes and 150 KiB in all).
+static size_t coarse_lds(const femo_pc* pc, int top, int* top_in_lds) {
+  int64_t under = 0;
+  for (int l = 0; l < top; ++l) under += pc->L[l].nodes;
+  const size_t lds = (size_t)under * 2 * sizeof(double), top_bytes = (size_t)pc->L[top].nodes * sizeof(double);
+  *top_in_lds = (pc->L[top].nodes <= FEMO_COARSE_TOP_MAX && lds + top_bytes <= 150 * 1024) ? 1 : 0;
+  return *top_in_lds ? lds + top_bytes : lds;
+}
+
+// Fills femo_pc::plan; called once by femo_pc_build, when the levels, n_fused and the rank's tiles are known.
+// multi: the context has more than one rank (the merged kernel then gets R h_T from the all-reduce and needs no scratch for it).
+static void pc_plan_launches(femo_pc* pc, bool multi) {
+  LaunchPlan& P = pc->plan;
+  const int nl = pc->n_levels, nf = pc->n_fused, D = pc->dim;
+  const int T = P.T = nl - 1 - nf;
+  for (int l = 0; l + 1 < T; ++l) P.below += pc->L[l].nodes;
+  // Fused lattice cycle, 3 launches instead of 6 (3-D): the restriction from the coarsest level the bricks filled
+  // (multi-block: a single workgroup gathering 27 values per node of a 15 k-node level took 20 us), one workgroup
+  // for everything below it, and one launch for the three finest levels.  It and the merged loop need level T-1 small
+  // enough for the single workgroup's registers and the levels below it in LDS.
+  const bool top_fits = T >= 1 && T < FEMO_PC_MAX_LEVELS - 1 && pc->L[T - 1].nodes <= FEMO_COARSE_TOP_MAX &&
+                        P.below * 2 * (int64_t)sizeof(double) <= 144 * 1024;
+  P.fused_cycle = nf >= 2 && T >= 2 && top_fits;
+  if (P.fused_cycle) {
+    P.lds_coarse = coarse_lds(pc, T - 1, &P.top_in_lds);
+  } else {
+    // levels 0 .. cut-1 go through the single-workgroup kernel, which reads g of level `cut` from
+    // global memory: one CU gathers 27 values per coarse node, so that level must stay small (with
+    // 15.6 k nodes the phase alone took 25 us at C4); `cut` = first level handled by multi-block launches
+    while (P.cut < T && P.cut < FEMO_PC_MAX_LEVELS - 1 && pc->L[P.cut + 1].nodes <= FEMO_COARSE_TOP_MAX) P.coarse_total += pc->L[P.cut++].nodes;
+    if (P.cut > 0) P.lds_coarse = coarse_lds(pc, P.cut, &P.top_in_lds);
+  }
+  const LatticeLevel& F = pc->L[nl - 1];
+  const int TF = D == 3 ? 8 : 16;
+  int64_t tiles = 1;
+  for (int k = 0; k < D; ++k) tiles *= (F.n[k] + TF) / TF;
+  P.fine_grid = (int)std::min<int64_t>(tiles, 2048);
+  P.m_tile_list = pc->n_my_tiles < tiles ? pc->d_my_tiles : nullptr;      // all of them: walk the plain range
+  P.m_tiles = P.m_tile_list != nullptr ? pc->n_my_tiles : tiles;
+  P.m_small = P.m_tiles > 2048;      // (1.03 M rows, 1000 tiles: 7.7 us with 256 threads, 8.5 with 128)
+  P.m_grid = (int)std::max<int64_t>(1, std::min<int64_t>(P.m_tiles, P.m_small ? 4096 : 2048));
+  // the shape the merged kernels are written for: two brick-fused levels, everything below level T-1 (and g_{T-1}) in LDS
+  // (two fused levels in 3-D, three in 2-D: the carriers' loops and the node lists are generic over the brick-filled levels; in
+  // 2-D the level between T-1 and the tile kernel's three gets its correction from a k_lattice_prolong launch on the state)
+  int top_in_lds = 0;
+  if ((nf == 2 || (nf == 3 && D == 2)) && top_fits) P.lds_merged = coarse_lds(pc, T - 1, &top_in_lds);
+  P.merged_ok = top_in_lds != 0;
+  if (!P.merged_ok || D != 3) return;
+  // scratch of the separable restrictions (3-D): the largest of the top restriction (one rank: level T -> T-1, + its output)
+  // and the LDS-resident ones; behind the levels when it fits
+  auto need = [](const int* nc, const int* nfn, bool with_out) -> int64_t {
+    const int64_t s1 = (int64_t)(nc[0] + 1) * (nfn[1] + 1) * (nfn[2] + 1), s2 = (int64_t)(nc[0] + 1) * (nc[1] + 1) * (nfn[2] + 1);
+    return s1 + s2 + (with_out ? (int64_t)(nc[0] + 1) * (nc[1] + 1) * (nc[2] + 1) : 0);
+  };
+  int64_t scratch = multi ? 0 : need(pc->L[T - 1].n, pc->L[T].n, true);
+  for (int l = 0; l + 1 <= T - 1; ++l) scratch = std::max(scratch, need(pc->L[l].n, pc->L[l + 1].n, false));
+  // the flattened chain (k_lattice_coarse_m: mc.flat): x- and y-pass outputs of ALL levels below T-1 at once
+  int64_t flat_need = 0;
+  const int top = T - 1;
+  // (the z-pass of the flattened chain reads the prefetched coefficient of node `tid`: one trip per level, i.e. every level
+  // below T-1 must have at most 1024 nodes -- true for the m0 in {2, 3} doubling lattices with TOP_MAX = 5120; checked here)
+  const bool one_trip = top >= 1 && pc->L[top - 1].nodes <= 1024;
+  if (top >= 1 && top <= 4 && one_trip) {
+    const int* nt = pc->L[top].n;
+    for (int k = 1; k <= top; ++k) {
+      const int* nc = pc->L[top - k].n;
+      flat_need += (int64_t)(nc[0] + 1) * (nt[1] + 1) * (nt[2] + 1) + (int64_t)(nc[0] + 1) * (nc[1] + 1) * (nt[2] + 1);
+    }
+  }
+  const int64_t off = (int64_t)(P.lds_merged / sizeof(double));
+  if (flat_need > 0 && (off + std::max(scratch, flat_need)) * (int64_t)sizeof(double) <= 158 * 1024) {
+    P.flat = 1;
+    scratch = std::max(scratch, flat_need);
+  }
+  if ((off + scratch) * (int64_t)sizeof(double) <= 158 * 1024) { P.sep_off = off; P.lds_merged = (size_t)(off + scratch) * sizeof(double); }
+  else P.flat = 0;
 }
 
 // ---- sparse exchange of the finest lattice on partitioned meshes ---------------------------
@@ -1894,36 +2007,103 @@ __global__ void k_unpack_shared(int64_t n_shared, const int32_t* __restrict__ id
 }
 
 // resident workgroups of the persistent brick kernel per CU (registers and LDS decide; asked once)
-template <int D, int PF>
-static int bricks_per_cu_of() {
-  int nb = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_restrict_bricks<D, PF>, FEMO_BLOCK, 0);
-  return (e == hipSuccess && nb > 0) ? nb : 3;
-}
-
 static int bricks_per_cu(int dim, int pf) {
   static int cached[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
   int& c = cached[dim == 3 ? 1 : 0][pf];
-  if (c == 0) {
-    if (dim == 3) c = pf == 2 ? bricks_per_cu_of<3, 2>() : (pf == 3 ? bricks_per_cu_of<3, 3>() : bricks_per_cu_of<3, 4>());
-    else c = pf == 2 ? bricks_per_cu_of<2, 2>() : (pf == 3 ? bricks_per_cu_of<2, 3>() : bricks_per_cu_of<2, 4>());
-  }
+  if (c != 0) return c;
+  const hipError_t e = by_dim(dim, [&](auto D) {
+    return by_brick_pf(pf, [&](auto PF) { return hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, k_restrict_bricks<decltype(D)::value, decltype(PF)::value>, FEMO_BLOCK, 0); });
+  });
+  if (e != hipSuccess || c <= 0) c = 3;
   return c;
 }
 
-// the brick restriction for the mesh's dimension and staging depth
-#define FEMO_LAUNCH_BRICKS(pc, gb, st, ...)                                                                                        \
-  do {                                                                                                                             \
-    if ((pc)->dim == 3) {                                                                                                          \
-      if ((pc)->brick_pf == 2) hipLaunchKernelGGL((k_restrict_bricks<3, 2>), dim3(gb), dim3(FEMO_BLOCK), 0, st, __VA_ARGS__);      \
-      else if ((pc)->brick_pf == 3) hipLaunchKernelGGL((k_restrict_bricks<3, 3>), dim3(gb), dim3(FEMO_BLOCK), 0, st, __VA_ARGS__); \
-      else hipLaunchKernelGGL((k_restrict_bricks<3, 4>), dim3(gb), dim3(FEMO_BLOCK), 0, st, __VA_ARGS__);                          \
-    } else {                                                                                                                       \
-      if ((pc)->brick_pf == 2) hipLaunchKernelGGL((k_restrict_bricks<2, 2>), dim3(gb), dim3(FEMO_BLOCK), 0, st, __VA_ARGS__);      \
-      else if ((pc)->brick_pf == 3) hipLaunchKernelGGL((k_restrict_bricks<2, 3>), dim3(gb), dim3(FEMO_BLOCK), 0, st, __VA_ARGS__); \
-      else hipLaunchKernelGGL((k_restrict_bricks<2, 4>), dim3(gb), dim3(FEMO_BLOCK), 0, st, __VA_ARGS__);                          \
-    }                                                                                                                              \
-  } while (0)
+// the brick restriction of `src` (with the weights d_w_sorted) into `dst`, the finest level's accumulators -- and, through
+// the fused restrictions, into the n_fused levels in front of them -- for the mesh's dimension and staging depth
+static void launch_bricks(femo_mesh* m, const double* src, double* dst, const int32_t* done) {
+  const femo_pc* pc = m->pc;
+  if (pc->n_bricks <= 0) return;
+  const Lat lat = make_lat(pc, pc->L.back());
+  const unsigned gb = (unsigned)std::min<int64_t>(pc->n_bricks, (int64_t)m->ctx->n_cu * bricks_per_cu(pc->dim, pc->brick_pf));
+  by_dim(pc->dim, [&](auto D) {
+    by_brick_pf(pc->brick_pf, [&](auto PF) {
+      hipLaunchKernelGGL((k_restrict_bricks<decltype(D)::value, decltype(PF)::value>), dim3(gb), dim3(FEMO_BLOCK), 0, m->ctx->stream, pc->n_bricks, pc->d_brick_ptr,
+                         pc->d_brick_base, pc->d_bin_ptr, pc->d_perm, pc->d_pk_sorted, lat, src, pc->d_w_sorted, dst, pc->n_fused, done);
+    });
+  });
+}
+
+// level l <- level l + 1 (src: that level's accumulators), a launch of its own
+static void launch_lattice_restrict(const femo_pc* pc, int l, const double* src, hipStream_t st, const int32_t* done) {
+  const LatticeLevel &C = pc->L[l], &Fi = pc->L[l + 1];
+  hipLaunchKernelGGL(k_lattice_restrict, dim3(lat_grid(C.nodes)), dim3(256), 0, st, C.n[0], C.n[1], C.n[2], Fi.n[0], Fi.n[1], Fi.n[2], pc->dim, src, C.g, done);
+}
+
+// e_l = coef_l g + I e_{l-1}, a launch of its own (zero_g: g is cleared behind the read; dots / dotw: the finest level's g.e)
+static void launch_lattice_prolong(const femo_pc* pc, int l, double* g, int zero_g, double* dots, const double* dotw, hipStream_t st,
+                                   const int32_t* done) {
+  const LatticeLevel& Fi = pc->L[l];
+  const double* ec = l > 0 ? pc->L[l - 1].e : nullptr;
+  const int* nc = l > 0 ? pc->L[l - 1].n : Fi.n;
+  hipLaunchKernelGGL(k_lattice_prolong, dim3(lat_grid(Fi.nodes)), dim3(256), 0, st, Fi.n[0], Fi.n[1], Fi.n[2], nc[0], nc[1], nc[2], pc->dim, ec, Fi.coef, g, zero_g, Fi.e, dots, dotw, done);
+}
+
+// a launch with more than 64 KiB of dynamic LDS needs the kernel's limit raised first: once per hierarchy (*raised)
+static int raise_lds(const void* kernel, size_t lds, int limit, bool* raised) {
+  if (lds <= 64 * 1024 || *raised) return 0;
+  FEMO_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, limit));
+  *raised = true;
+  return 0;
+}
+
+// Levels 0 .. top of a single-workgroup coarse kernel, with the accumulators of parity `which`.  emit_top: level top + 1 is
+// the coarsest one the bricks filled (finer_g; g_top is restricted from it where the caller sets restrict_top).
+static CoarseLevels coarse_levels(const femo_pc* pc, int top, int which, int emit_top) {
+  CoarseLevels CL = {};
+  CL.n_levels = top;
+  CL.emit_top = emit_top;
+  for (int l = 0; l <= top; ++l) {
+    for (int k = 0; k < 3; ++k) CL.n[l][k] = pc->L[l].n[k];
+    CL.g[l] = pc->acc(l, which); CL.e[l] = pc->L[l].e; CL.coef[l] = pc->L[l].coef;
+    CL.nodes[l] = pc->L[l].nodes;
+    CL.off[l] = l == 0 ? 0 : CL.off[l - 1] + 2 * CL.nodes[l - 1];
+  }
+  if (emit_top) {
+    CL.finer_g = pc->acc(top + 1, which);
+    for (int k = 0; k < 3; ++k) CL.finer_n[k] = pc->L[top + 1].n[k];
+  }
+  return CL;
+}
+
+// The three finest levels of the tile kernels: g_c, g_m, g_f are what they prolong from (accumulators or the merged loop's
+// state); the accumulators of parity `other` on the two coarser ones are cleared for the restriction after the next.
+static FineLevels fine_levels(const femo_pc* pc, double* g_c, double* g_m, double* g_f, int other, double* dot_partials, const double* dot_weight) {
+  const int nl = pc->n_levels;
+  const LatticeLevel &Lcc = pc->L[nl - 4], &Lc = pc->L[nl - 3], &Lm = pc->L[nl - 2], &F = pc->L[nl - 1];
+  FineLevels FL;
+  for (int k = 0; k < 3; ++k) { FL.ncc[k] = Lcc.n[k]; FL.nc[k] = Lc.n[k]; FL.nm[k] = Lm.n[k]; FL.nf[k] = F.n[k]; }
+  FL.e_cc = Lcc.e;
+  FL.coef_c = Lc.coef; FL.g_c = g_c; FL.g_c_other = pc->acc(nl - 3, other);
+  FL.coef_m = Lm.coef; FL.g_m = g_m; FL.g_m_other = pc->acc(nl - 2, other);
+  FL.coef_f = F.coef; FL.g_f = g_f; FL.e_f = F.e;
+  FL.dot_partials = dot_partials;
+  FL.dot_weight = dot_weight;
+  return FL;
+}
+
+// The mesh prolongation of either loop.  a: vectors, mode and scalars as femo_pc_apply takes them (the merged loop fills one
+// in); nb_dot / dot_global: the lattice dot as per-block partials or as one reduced scalar.
+static void launch_prolong_mesh(femo_mesh* m, const uint8_t* mask, const FemoPcApply& a, unsigned grid, int nb_dot, const double* dot_global,
+                                const MergedScal& ms, const HaloFirst& hf) {
+  const femo_pc* pc = m->pc;
+  const Lat lat = make_lat(pc, pc->L.back());
+  const FemoPcgStop stop = a.stop != nullptr ? *a.stop : FemoPcgStop{};
+  by_dim(pc->dim, [&](auto D) {
+    hipLaunchKernelGGL(k_prolong_mesh<decltype(D)::value>, dim3(grid), dim3(FEMO_BLOCK), 0, m->ctx->stream, m->n_rows, lat, pc->d_pk, a.rh, pc->d_sinv, mask,
+                       pc->L.back().e, a.out, a.mode, nb_dot, pc->d_dot_partials, dot_global, a.nb_rho, a.rho_partials, a.rho, a.gamma_cur, a.gamma_nxt,
+                       a.done, stop, ms, hf);
+  });
+}
 
 // Which lattice nodes do several ranks touch?  A rank's restriction only reaches the nodes around its own vertices (on
 // the finest lattice and, through the fused restrictions of the brick kernel, on the next coarser ones) and its
@@ -1931,16 +2111,13 @@ static int bricks_per_cu(int dim, int pf) {
 // rank touches (the layers along the partition interfaces).  Collective, once per mesh.  Two sets of lists:
 //   classic loop (femo_pc_apply): the finest level's shared nodes; the coarser fused levels travel whole;
 //   merged loop (femo_pc_merged_apply, round 5): shared / single-rank nodes of ALL brick-filled levels (femo_pc::d_mshared_idx).
-static bool merged_shape_ok(const femo_pc* pc, bool multi);
 static int pc_setup_shared(femo_mesh* m) {
   femo_pc* pc = m->pc;
   if (pc->shared_ready) return 0;
   femo_ctx* ctx = m->ctx;
   hipStream_t st = ctx->stream;
-  const int nl = pc->n_levels, nf = pc->n_fused;
-  const int T = nl - 1 - nf;
+  const int nl = pc->n_levels, T = pc->plan.T;
   LatticeLevel& F = pc->L[nl - 1];
-  const Lat lat = make_lat(pc, F);
   double* first = pc->L[T].g;                                // accumulators of levels T .. L (first copy), contiguous
   const int64_t n_all = (F.g + F.nodes) - first;
   const int64_t off_F = F.g - first;
@@ -1951,10 +2128,7 @@ static int pc_setup_shared(femo_mesh* m) {
   hipLaunchKernelGGL(k_fill_ones<double>, dim3(lat_grid(m->n_vert)), dim3(256), 0, st, m->n_vert, ones);
   hipLaunchKernelGGL(k_fill_ones<float>, dim3(lat_grid(m->n_rows)), dim3(256), 0, st, std::max<int64_t>(m->n_rows, 0), pc->d_w_sorted);
   FEMO_HIP_CHECK(hipMemsetAsync(first, 0, n_all * sizeof(double), st));
-  if (pc->n_bricks > 0) {
-    const unsigned gb = (unsigned)std::min<int64_t>(pc->n_bricks, (int64_t)ctx->n_cu * bricks_per_cu(pc->dim, pc->brick_pf));
-    FEMO_LAUNCH_BRICKS(pc, gb, st, pc->n_bricks, pc->d_brick_ptr, pc->d_brick_base, pc->d_bin_ptr, pc->d_perm, pc->d_pk_sorted, lat, ones, pc->d_w_sorted, F.g, nf, (const int32_t*)nullptr);
-  }
+  launch_bricks(m, ones, F.g, nullptr);
   hipLaunchKernelGGL(k_mark_touched, dim3(lat_grid(n_all)), dim3(256), 0, st, n_all, first, tmp);
   FEMO_HIP_CHECK(hipGetLastError());
   std::vector<double> mine((size_t)n_all), cnt((size_t)n_all);
@@ -2001,7 +2175,7 @@ static int pc_setup_shared(femo_mesh* m) {
     if (!v.empty()) FEMO_HIP_CHECK(hipMemcpy(*dst, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return 0;
   };
-  if (merged_shape_ok(pc, true)) {
+  if (pc->plan.merged_ok) {
     FEMO_REQUIRE(n_all < (int64_t(1) << 31), "lattice too large for 32-bit node lists");
     std::vector<int32_t> msh, mint;
     const int64_t n_coarse_nodes = off_F;                     // levels T and L-1 lead the range
@@ -2041,13 +2215,10 @@ static int pc_prepare(femo_mesh* m, const uint8_t* mask, uint64_t key) {
   FEMO_HIP_CHECK(hipMemsetAsync(F.e, 0, F.nodes * sizeof(double), st));
   const Lat lat = make_lat(pc, F);
   const double* none = nullptr;
-  if (pc->dim == 3) {
-    hipLaunchKernelGGL(k_restrict_mesh<3>, dim3(gv), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, m->d_x, none, none, mask, 0, F.g, (const int32_t*)nullptr);
-    if (mask) hipLaunchKernelGGL(k_restrict_mesh<3>, dim3(gv), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, m->d_x, none, none, mask, 1, F.e, (const int32_t*)nullptr);
-  } else {
-    hipLaunchKernelGGL(k_restrict_mesh<2>, dim3(gv), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, m->d_x, none, none, mask, 0, F.g, (const int32_t*)nullptr);
-    if (mask) hipLaunchKernelGGL(k_restrict_mesh<2>, dim3(gv), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, m->d_x, none, none, mask, 1, F.e, (const int32_t*)nullptr);
-  }
+  by_dim(pc->dim, [&](auto D) {
+    hipLaunchKernelGGL(k_restrict_mesh<decltype(D)::value>, dim3(gv), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, m->d_x, none, none, mask, 0, F.g, (const int32_t*)nullptr);
+    if (mask) hipLaunchKernelGGL(k_restrict_mesh<decltype(D)::value>, dim3(gv), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, m->d_x, none, none, mask, 1, F.e, (const int32_t*)nullptr);
+  });
   if (ctx->nranks > 1) {
     FEMO_TRY(femo_coll_allreduce(ctx, F.g, F.nodes, st));
     FEMO_TRY(femo_coll_allreduce(ctx, F.e, F.nodes, st));
@@ -2069,175 +2240,84 @@ static int pc_prepare(femo_mesh* m, const uint8_t* mask, uint64_t key) {
   return 0;
 }
 
-// zh = M^-1 rh in scaled variables; partials[block] = rh.zh per block (gv blocks)
-int femo_pc_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const double* s, const double* rh, double* out,
-                  int mode, double* rho, const double* gamma_cur, double* gamma_nxt, const int32_t* done, int gv,
-                  bool rho_is_partial, const FemoPcgStop* stop, int nb_rho, const double* rho_partials, const FemoXUpdate* xupdate) {
+// zh = M^-1 rh in scaled variables (FemoPcApply, femo_internal.h)
+int femo_pc_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const FemoPcApply& a) {
   femo_pc* pc = m->pc;
   femo_ctx* ctx = m->ctx;
+  const LaunchPlan& P = pc->plan;
+  const bool sparse = ctx->nranks > 1 && pc->shared_ready;
+  FEMO_REQUIRE(!a.rho_is_partial || sparse, "femo_pc_apply: a partial rho needs the sparse exchange (femo_pc_can_piggyback)");
+  FEMO_REQUIRE(a.xupdate == nullptr || P.fused_cycle, "femo_pc_apply: the x update rides in the fused lattice cycle only");
+  FEMO_REQUIRE(a.mode == 0 || (a.rho != nullptr && a.gamma_cur != nullptr && a.gamma_nxt != nullptr), "femo_pc_apply: modes 1 and 2 need rho, gamma_cur and gamma_nxt");
+  FEMO_REQUIRE(a.nb_rho <= 0 || a.rho_partials != nullptr, "femo_pc_apply: nb_rho > 0 needs rho_partials");
   FEMO_TRY(pc_prepare(m, mask, mask_key));
   const hipStream_t st = ctx->stream;
-  const double* rsrc = rh;
-  const int nl = pc->n_levels, nf = pc->n_fused;
-  const int T = nl - 1 - nf;                                   // coarsest level the brick kernel fills
+  const int32_t* done = a.done;
+  const int nl = pc->n_levels, nf = pc->n_fused, T = P.T;
   LatticeLevel& F = pc->L[nl - 1];
-  const Lat lat = make_lat(pc, F);
   // accumulators of this apply / of the next one (levels >= T exist twice, see femo_pc::g_alt)
   const int par = pc->parity;
-  auto G = [&](int l, int which) -> double* {
-    if (l < T || which == 0) return pc->L[l].g;
-    return pc->g_alt + (pc->L[l].g - pc->L[T].g);
-  };
-  double* gF = G(nl - 1, par);
+  double* gF = pc->acc(nl - 1, par);
   // g of the finest nf+1 levels: zero on entry (femo_pc_begin, then the prolongation kernels clean up)
-  if (pc->n_bricks > 0) {
-    const unsigned gb = (unsigned)std::min<int64_t>(pc->n_bricks, (int64_t)ctx->n_cu * bricks_per_cu(pc->dim, pc->brick_pf));
-    FEMO_LAUNCH_BRICKS(pc, gb, st, pc->n_bricks, pc->d_brick_ptr, pc->d_brick_base, pc->d_bin_ptr, pc->d_perm, pc->d_pk_sorted, lat, rsrc, pc->d_w_sorted, gF, nf, done);
-  }
-  const bool sparse = ctx->nranks > 1 && pc->shared_ready;
+  launch_bricks(m, a.rh, gF, done);
   if (sparse) {
     // one all-reduce per apply: the finest-level nodes several ranks touch + the whole coarser fused levels
-    double* gc = nf >= 1 ? G(T, par) : nullptr;
+    double* gc = nf >= 1 ? pc->acc(T, par) : nullptr;
     const int64_t n_coarse = nf >= 1 ? gF - gc : 0;
     const int64_t count = pc->n_shared + n_coarse;
     // rho_is_partial: *rho holds this rank's part of rh.rh; it rides in the same all-reduce
-    double* piggy = rho_is_partial ? rho : nullptr;
+    double* piggy = a.rho_is_partial ? a.rho : nullptr;
     if (count > 0 || piggy != nullptr) {
       hipLaunchKernelGGL(k_pack_shared, dim3(lat_grid(std::max<int64_t>(count, 1))), dim3(256), 0, st, pc->n_shared, pc->d_shared_idx, gF, n_coarse, gc, piggy, pc->d_xbuf, done);
       FEMO_TRY(femo_coll_allreduce(ctx, pc->d_xbuf, count + (piggy ? 1 : 0), st));
       hipLaunchKernelGGL(k_unpack_shared, dim3(lat_grid(std::max<int64_t>(count, 1))), dim3(256), 0, st, pc->n_shared, pc->d_shared_idx, gF, n_coarse, gc, piggy, pc->d_xbuf, done);
     }
-  } else if (rho_is_partial) {
-    FEMO_REQUIRE(false, "femo_pc_apply: a partial rho needs the sparse exchange (femo_pc_can_piggyback)");
   } else if (ctx->nranks > 1) {   // dense: the contiguous accumulators of the finest nf+1 levels
-    double* first = G(T, par);
-    const int64_t count = (gF + F.nodes) - first;
-    FEMO_TRY(femo_coll_allreduce(ctx, first, count, st));
+    double* first = pc->acc(T, par);
+    FEMO_TRY(femo_coll_allreduce(ctx, first, (gF + F.nodes) - first, st));
   }
   const double* dotw = sparse ? pc->d_dot_weight : nullptr;
-  int nb_dot = (int)lat_grid(F.nodes);
-  // Fused lattice cycle, 3 launches instead of 6 (3-D): the restriction from the coarsest level the bricks filled
-  // (multi-block: a single workgroup gathering 27 values per node of a 15 k-node level took 20 us), one workgroup
-  // for everything below it, and one launch for the three finest levels.
-  int64_t below = 0;
-  for (int l = 0; l + 1 < T; ++l) below += pc->L[l].nodes;
-  const bool fused_cycle = nf >= 2 && T >= 2 && T < FEMO_PC_MAX_LEVELS - 1 && below * 2 * (int64_t)sizeof(double) <= 144 * 1024 &&
-                           pc->L[T - 1].nodes <= FEMO_COARSE_TOP_MAX;
-  pc->fused_cycle_seen = fused_cycle;
-  FEMO_REQUIRE(xupdate == nullptr || fused_cycle, "femo_pc_apply: the x update rides in the fused lattice cycle only");
-  if (fused_cycle) {
-    CoarseLevels CL;
-    CL.n_levels = T - 1;                                           // levels 0 .. T-2 in LDS, e_{T-1} emitted
-    CL.emit_top = 1;
-    for (int l = 0; l <= T - 1; ++l) {
-      for (int k = 0; k < 3; ++k) CL.n[l][k] = pc->L[l].n[k];
-      CL.g[l] = pc->L[l].g; CL.e[l] = pc->L[l].e; CL.coef[l] = pc->L[l].coef;
-      CL.nodes[l] = pc->L[l].nodes;
-      CL.off[l] = l == 0 ? 0 : CL.off[l - 1] + 2 * CL.nodes[l - 1];
-    }
-    size_t lds = (size_t)below * 2 * sizeof(double);
-    CL.top_in_lds = (CL.nodes[T - 1] <= FEMO_COARSE_TOP_MAX && lds + (size_t)CL.nodes[T - 1] * sizeof(double) <= 150 * 1024) ? 1 : 0;
-    if (CL.top_in_lds) lds += (size_t)CL.nodes[T - 1] * sizeof(double);
-    CL.restrict_top = CL.top_in_lds;
-    CL.finer_g = G(T, par);
-    for (int k = 0; k < 3; ++k) CL.finer_n[k] = pc->L[T].n[k];
-    if (!CL.restrict_top) {                                     // no room for g_top in LDS: restrict it with a launch of its own
-      LatticeLevel& C = pc->L[T - 1];
-      const LatticeLevel& Fi = pc->L[T];
-      hipLaunchKernelGGL(k_lattice_restrict, dim3(lat_grid(C.nodes)), dim3(256), 0, st, C.n[0], C.n[1], C.n[2], Fi.n[0], Fi.n[1], Fi.n[2], pc->dim, G(T, par), C.g, done);
-    }
-    if (lds > 64 * 1024 && !pc->coarse_lds_set) {
-      FEMO_HIP_CHECK(hipFuncSetAttribute((const void*)k_lattice_coarse, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      pc->coarse_lds_set = true;
-    }
-    {
-      // one workgroup does the lattice work; with an x update to carry, one more per remaining compute unit
-      FemoXUpdate xu = {nullptr, nullptr, nullptr, 0};
-      unsigned grid = 1;
-      if (xupdate != nullptr && xupdate->n > 0) { xu = *xupdate; grid = (unsigned)std::max(2, ctx->n_cu); }
-      hipLaunchKernelGGL(k_lattice_coarse, dim3(grid), dim3(1024), lds, st, CL, pc->dim, done, xu);
-    }
-    for (int l = T; l <= nl - 4; ++l) {                         // 2-D only (three fused levels): the level in between
-      LatticeLevel& Fi = pc->L[l];
-      hipLaunchKernelGGL(k_lattice_prolong, dim3(lat_grid(Fi.nodes)), dim3(256), 0, st, Fi.n[0], Fi.n[1], Fi.n[2], pc->L[l - 1].n[0], pc->L[l - 1].n[1], pc->L[l - 1].n[2], pc->dim, pc->L[l - 1].e, Fi.coef, G(l, par), 1, Fi.e, (double*)nullptr, (const double*)nullptr, done);
-    }
-    FineLevels FL;
-    const LatticeLevel &Lcc = pc->L[nl - 4], &Lc = pc->L[nl - 3], &Lm = pc->L[nl - 2];
-    for (int k = 0; k < 3; ++k) { FL.ncc[k] = Lcc.n[k]; FL.nc[k] = Lc.n[k]; FL.nm[k] = Lm.n[k]; FL.nf[k] = F.n[k]; }
-    FL.e_cc = Lcc.e;
-    FL.coef_c = Lc.coef; FL.g_c = G(nl - 3, par); FL.g_c_other = G(nl - 3, par ^ 1);
-    FL.coef_m = Lm.coef; FL.g_m = G(nl - 2, par); FL.g_m_other = G(nl - 2, par ^ 1);
-    FL.coef_f = F.coef; FL.g_f = gF; FL.e_f = F.e;
-    FL.dot_partials = mode != 0 ? pc->d_dot_partials : nullptr;
-    FL.dot_weight = dotw;
-    const int TF = pc->dim == 3 ? 8 : 16;
-    int64_t tiles = 1;
-    for (int k = 0; k < pc->dim; ++k) tiles *= (F.n[k] + TF) / TF;
-    nb_dot = (int)std::min<int64_t>(tiles, 2048);
-    if (pc->dim == 3) hipLaunchKernelGGL(k_lattice_prolong3<3>, dim3(nb_dot), dim3(256), 0, st, FL, done);
-    else hipLaunchKernelGGL(k_lattice_prolong3<2>, dim3(nb_dot), dim3(256), 0, st, FL, done);
+  double* dots = a.mode != 0 ? pc->d_dot_partials : nullptr;
+  int nb_dot;
+  if (P.fused_cycle) {
+    CoarseLevels CL = coarse_levels(pc, T - 1, par, 1);            // levels 0 .. T-2 in LDS, e_{T-1} emitted
+    CL.top_in_lds = CL.restrict_top = P.top_in_lds;
+    if (!CL.restrict_top) launch_lattice_restrict(pc, T - 1, pc->acc(T, par), st, done);   // no room for g_top in LDS
+    FEMO_TRY(raise_lds((const void*)k_lattice_coarse, P.lds_coarse, 160 * 1024, &pc->coarse_lds_set));
+    // one workgroup does the lattice work; with an x update to carry, one more per remaining compute unit
+    FemoXUpdate xu = {nullptr, nullptr, nullptr, 0};
+    unsigned grid = 1;
+    if (a.xupdate != nullptr && a.xupdate->n > 0) { xu = *a.xupdate; grid = (unsigned)std::max(2, ctx->n_cu); }
+    hipLaunchKernelGGL(k_lattice_coarse, dim3(grid), dim3(1024), P.lds_coarse, st, CL, pc->dim, done, xu);
+    for (int l = T; l <= nl - 4; ++l)                              // 2-D only (three fused levels): the level in between
+      launch_lattice_prolong(pc, l, pc->acc(l, par), 1, nullptr, nullptr, st, done);
+    const FineLevels FL = fine_levels(pc, pc->acc(nl - 3, par), pc->acc(nl - 2, par), gF, par ^ 1, dots, dotw);
+    nb_dot = P.fine_grid;
+    by_dim(pc->dim, [&](auto D) { hipLaunchKernelGGL(k_lattice_prolong3<decltype(D)::value>, dim3(nb_dot), dim3(256), 0, st, FL, done); });
     pc->parity ^= 1;
   } else {
-    // levels with at most COARSE_NODES nodes (and below the brick-fused ones) go through the
-    // single-workgroup kernel; `cut` = first level handled by multi-block launches
-    // levels 0 .. cut-1 go through the single-workgroup kernel, which reads g of level `cut` from
-    // global memory: one CU gathers 27 values per coarse node, so that level must stay small (with
-    // 15.6 k nodes the phase alone took 25 us at C4)
-    constexpr int64_t COARSE_TOP_NODES = FEMO_COARSE_TOP_MAX;
-    int cut = 0;
-    int64_t coarse_total = 0;
-    while (cut < nl - 1 - nf && cut < FEMO_PC_MAX_LEVELS - 1 && pc->L[cut + 1].nodes <= COARSE_TOP_NODES) coarse_total += pc->L[cut++].nodes;
-    for (int l = nl - 2 - nf; l >= cut; --l) {
-      LatticeLevel& C = pc->L[l];
-      const LatticeLevel& Fi = pc->L[l + 1];
-      hipLaunchKernelGGL(k_lattice_restrict, dim3(lat_grid(C.nodes)), dim3(256), 0, st, C.n[0], C.n[1], C.n[2], Fi.n[0], Fi.n[1], Fi.n[2], pc->dim, G(l + 1, par), C.g, done);
+    // level by level: multi-block restrictions down to level `cut`, the single-workgroup kernel for the levels below it
+    // (LaunchPlan), multi-block prolongations from `cut` up
+    for (int l = T - 1; l >= P.cut; --l) launch_lattice_restrict(pc, l, pc->acc(l + 1, par), st, done);
+    if (P.cut > 0) {
+      CoarseLevels CL = coarse_levels(pc, P.cut, par, 0);
+      CL.top_in_lds = P.top_in_lds;
+      FEMO_TRY(raise_lds((const void*)k_lattice_coarse, P.lds_coarse, 160 * 1024, &pc->coarse_lds_set));
+      hipLaunchKernelGGL(k_lattice_coarse, dim3(1), dim3(1024), P.lds_coarse, st, CL, pc->dim, done, FemoXUpdate{nullptr, nullptr, nullptr, 0});
     }
-    if (cut > 0) {
-      CoarseLevels CL;
-      CL.n_levels = cut;
-      CL.emit_top = 0;
-      for (int l = 0; l <= cut; ++l) {
-        for (int k = 0; k < 3; ++k) CL.n[l][k] = pc->L[l].n[k];
-        CL.g[l] = G(l, par); CL.e[l] = pc->L[l].e; CL.coef[l] = pc->L[l].coef;
-        CL.nodes[l] = pc->L[l].nodes;
-        CL.off[l] = l == 0 ? 0 : CL.off[l - 1] + 2 * CL.nodes[l - 1];
-      }
-      size_t lds = (size_t)coarse_total * 2 * sizeof(double);
-      CL.top_in_lds = (CL.nodes[cut] <= FEMO_COARSE_TOP_MAX && lds + (size_t)CL.nodes[cut] * sizeof(double) <= 150 * 1024) ? 1 : 0;
-      if (CL.top_in_lds) lds += (size_t)CL.nodes[cut] * sizeof(double);
-      CL.restrict_top = 0; CL.finer_g = nullptr; CL.finer_n[0] = CL.finer_n[1] = CL.finer_n[2] = 0;
-      if (lds > 64 * 1024 && !pc->coarse_lds_set) {
-        FEMO_HIP_CHECK(hipFuncSetAttribute((const void*)k_lattice_coarse, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        pc->coarse_lds_set = true;
-      }
-      hipLaunchKernelGGL(k_lattice_coarse, dim3(1), dim3(1024), lds, st, CL, pc->dim, done, FemoXUpdate{nullptr, nullptr, nullptr, 0});
-    }
-    for (int l = cut; l < nl; ++l) {
-      LatticeLevel& Fi = pc->L[l];
-      const double* ec = l > 0 ? pc->L[l - 1].e : nullptr;
-      const int* nc = l > 0 ? pc->L[l - 1].n : Fi.n;
-      double* dots = (l == nl - 1 && mode != 0) ? pc->d_dot_partials : nullptr;
-      hipLaunchKernelGGL(k_lattice_prolong, dim3(lat_grid(Fi.nodes)), dim3(256), 0, st, Fi.n[0], Fi.n[1], Fi.n[2], nc[0], nc[1], nc[2], pc->dim, ec, Fi.coef, G(l, par), l >= T ? 1 : 0, Fi.e, dots, l == nl - 1 ? dotw : (const double*)nullptr, done);
-    }
+    for (int l = P.cut; l < nl; ++l)
+      launch_lattice_prolong(pc, l, pc->acc(l, par), l >= T ? 1 : 0, l == nl - 1 ? dots : nullptr, l == nl - 1 ? dotw : nullptr, st, done);
+    nb_dot = (int)lat_grid(F.nodes);
   }
   const double* dot_global = nullptr;
-  if (sparse && mode != 0) {
+  if (sparse && a.mode != 0) {
     // each rank only holds the finest level on the nodes it touches: its weighted dot is a partial sum
     FEMO_TRY(femo_launch_fold(1024, nb_dot, 1, pc->d_dot_partials, pc->d_dot_scalar, st, done));
     FEMO_TRY(femo_coll_allreduce(ctx, pc->d_dot_scalar, 1, st));
     dot_global = pc->d_dot_scalar;
     nb_dot = 0;
   }
-  PcgStop ps;
-  ps.rtol2_factor = stop ? stop->rtol2_factor : 0.0;
-  ps.atol_pc2 = stop ? stop->atol_pc2 : 0.0;
-  ps.tolg2 = stop ? stop->tolg2 : nullptr;
-  ps.flags = stop ? stop->flags : nullptr;
-  ps.it = stop ? stop->it : 0;
-  if (pc->dim == 3)
-    hipLaunchKernelGGL(k_prolong_mesh<3>, dim3(gv), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, pc->d_pk, rh, pc->d_sinv, mask, F.e, out, mode, nb_dot, pc->d_dot_partials, dot_global, nb_rho, rho_partials, rho, gamma_cur, gamma_nxt, done, ps, MergedScal{}, HaloFirst{});
-  else
-    hipLaunchKernelGGL(k_prolong_mesh<2>, dim3(gv), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, pc->d_pk, rh, pc->d_sinv, mask, F.e, out, mode, nb_dot, pc->d_dot_partials, dot_global, nb_rho, rho_partials, rho, gamma_cur, gamma_nxt, done, ps, MergedScal{}, HaloFirst{});
+  launch_prolong_mesh(m, mask, a, (unsigned)a.gv, nb_dot, dot_global, MergedScal{}, HaloFirst{});
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -2251,7 +2331,7 @@ int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask) {
     FEMO_HIP_CHECK(hipGetLastError());
   }
   const int nl = pc->n_levels;
-  double* first = pc->L[nl - 1 - pc->n_fused].g;
+  double* first = pc->L[pc->plan.T].g;
   const int64_t count = (pc->L[nl - 1].g + pc->L[nl - 1].nodes) - first;
   FEMO_HIP_CHECK(hipMemsetAsync(first, 0, count * sizeof(double), m->ctx->stream));
   FEMO_HIP_CHECK(hipMemsetAsync(pc->g_alt, 0, count * sizeof(double), m->ctx->stream));
@@ -2259,27 +2339,12 @@ int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask) {
   return 0;
 }
 
-
 // ---- merged BPX-PCG: host side ---------------------------------------------------------------------------------------
-// the shape the merged kernels are written for: two brick-fused levels, everything below level T-1 (and g_{T-1}) in LDS
-// (two fused levels in 3-D, three in 2-D: the carriers' loops and the node lists are generic over the brick-filled levels; in
-// 2-D the level between T-1 and the tile kernel's three gets its correction from a k_lattice_prolong launch on the state)
-static bool merged_shape_ok(const femo_pc* pc, bool multi) {
-  const int nl = pc->n_levels, nf = pc->n_fused;
-  const int T = nl - 1 - nf;
-  (void)multi;
-  if (!(nf == 2 || (nf == 3 && pc->dim == 2)) || T < 1 || T >= FEMO_PC_MAX_LEVELS - 1) return false;
-  int64_t below = 0;
-  for (int l = 0; l + 1 < T; ++l) below += pc->L[l].nodes;
-  const int64_t lds = below * 2 * (int64_t)sizeof(double) + pc->L[T - 1].nodes * (int64_t)sizeof(double);
-  return pc->L[T - 1].nodes <= FEMO_COARSE_TOP_MAX && below * 2 * (int64_t)sizeof(double) <= 144 * 1024 && lds <= 150 * 1024;
-}
-
 bool femo_pc_merged_ok(femo_mesh* m) {
   // FEMO_PCG_CLASSIC: A/B switch and the tests of the classic loop (read per solve, never per launch)
   if (femo_env_flag("FEMO_PCG_CLASSIC") || femo_env_flag("FEMO_BPX_DENSE_ALLREDUCE")) return false;
   if (femo_pc_build(m) != 0) return false;
-  return merged_shape_ok(m->pc, m->ctx->nranks > 1);
+  return m->pc->plan.merged_ok;
 }
 
 int femo_pc_merged_collectives(const femo_mesh* m) { return m->ctx->nranks > 1 ? 1 : 0; }
@@ -2290,7 +2355,7 @@ int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, con
   femo_ctx* ctx = m->ctx;
   const hipStream_t st = ctx->stream;
   if (ctx->nranks > 1) FEMO_TRY(pc_setup_shared(m));   // once; collective
-  const int nl = pc->n_levels, T = nl - 1 - pc->n_fused;
+  const int nl = pc->n_levels, T = pc->plan.T;
   if (!pc->gs) {
     pc->gs_n = (pc->L[nl - 1].g + pc->L[nl - 1].nodes) - pc->L[T - 1].g;
     FEMO_HIP_CHECK(hipMalloc(&pc->gs, pc->gs_n * sizeof(double)));
@@ -2328,31 +2393,24 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
                          const int32_t* done, const FemoPcgStop* stop) {
   femo_pc* pc = m->pc;
   femo_ctx* ctx = m->ctx;
+  const LaunchPlan& P = pc->plan;
   FEMO_TRY(pc_prepare(m, mask, mask_key));
   const hipStream_t st = ctx->stream;
-  const int nl = pc->n_levels, nf = pc->n_fused;
-  const int T = nl - 1 - nf;
-  FEMO_REQUIRE(merged_shape_ok(pc, ctx->nranks > 1) && pc->gs != nullptr, "femo_pc_merged_apply: lattice shape not supported / begin not called");
-  LatticeLevel& F = pc->L[nl - 1];
-  const Lat lat = make_lat(pc, F);
+  const int nl = pc->n_levels, T = P.T;
+  FEMO_REQUIRE(P.merged_ok && pc->gs != nullptr, "femo_pc_merged_apply: lattice shape not supported / begin not called");
   const int par = pc->parity;
-  auto H = [&](int l, int which) -> double* { return which == 0 ? pc->L[l].g : pc->g_alt + (pc->L[l].g - pc->L[T].g); };
-  auto GS = [&](int l) -> double* { return pc->gs + (pc->L[l].g - pc->L[T - 1].g); };
   const bool init = V.q == nullptr;
   const bool multi = ctx->nranks > 1;
-  double* hF = H(nl - 1, par);
-  if (pc->n_bricks > 0) {
-    const unsigned gb = (unsigned)std::min<int64_t>(pc->n_bricks, (int64_t)ctx->n_cu * bricks_per_cu(pc->dim, pc->brick_pf));
-    FEMO_LAUNCH_BRICKS(pc, gb, st, pc->n_bricks, pc->d_brick_ptr, pc->d_brick_base, pc->d_bin_ptr, pc->d_perm, pc->d_pk_sorted, lat, init ? (const double*)V.r : V.q, pc->d_w_sorted, hF, nf, done);
-  }
+  double* hF = pc->acc(nl - 1, par);
+  launch_bricks(m, init ? V.r : V.q, hF, done);
   const int64_t n_top = pc->L[T - 1].nodes;
   if (multi) {
     FEMO_REQUIRE(pc->shared_ready && pc->d_mbuf != nullptr, "femo_pc_merged_apply: the sparse lattice exchange is not set up");
     PackArgs a;
-    a.n_shared = pc->n_mshared; a.shared_idx = pc->d_mshared_idx; a.h = H(T, par);
+    a.n_shared = pc->n_mshared; a.shared_idx = pc->d_mshared_idx; a.h = pc->acc(T, par);
     a.n_top = n_top; a.dim = pc->dim;
     for (int k = 0; k < 3; ++k) { a.nc[k] = pc->L[T - 1].n[k]; a.nf[k] = pc->L[T].n[k]; }
-    a.n_int = pc->n_mint; a.int_idx = pc->d_mint_idx; a.gs = GS(T); a.coef = pc->L[T].coef;
+    a.n_int = pc->n_mint; a.int_idx = pc->d_mint_idx; a.gs = pc->state(T); a.coef = pc->L[T].coef;
     for (int l = 0; l < 2; ++l) { a.nb_q[l] = init ? 0 : V.nb_q[l]; a.Pq[l] = V.Pq[l]; }
     a.nb_rr = init ? 0 : std::max(1, ctx->n_cu - 1); a.Prr = pc->d_rr_partials;
     a.buf = pc->d_mbuf;
@@ -2362,138 +2420,55 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
     FEMO_TRY(femo_coll_allreduce(ctx, pc->d_mbuf, a.n_shared + n_top + MS_NRED, st));
   }
   // workgroup 0: the LDS-resident levels; the others: vector and lattice updates
-  CoarseLevels CL;
-  CL.n_levels = T - 1;
-  CL.emit_top = 1;
-  int64_t below = 0;
-  for (int l = 0; l <= T - 1; ++l) {
-    for (int k = 0; k < 3; ++k) CL.n[l][k] = pc->L[l].n[k];
-    CL.g[l] = pc->L[l].g; CL.e[l] = pc->L[l].e; CL.coef[l] = pc->L[l].coef;
-    CL.nodes[l] = pc->L[l].nodes;
-    CL.off[l] = l == 0 ? 0 : CL.off[l - 1] + 2 * CL.nodes[l - 1];
-    if (l + 1 < T) below += pc->L[l].nodes;
-  }
-  const size_t lds = (size_t)below * 2 * sizeof(double) + (size_t)CL.nodes[T - 1] * sizeof(double);
-  CL.top_in_lds = 1; CL.restrict_top = 1;
-  CL.finer_g = H(T, par);
-  for (int k = 0; k < 3; ++k) CL.finer_n[k] = pc->L[T].n[k];
-  if (lds > 64 * 1024 && !pc->coarse_lds_set) {
-    FEMO_HIP_CHECK(hipFuncSetAttribute((const void*)k_lattice_coarse, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    pc->coarse_lds_set = true;
-  }
+  CoarseLevels CL = coarse_levels(pc, T - 1, par, 1);
+  CL.top_in_lds = CL.restrict_top = 1;
   const int n_carry = std::max(1, ctx->n_cu - 1);
   MergedCarry mc;
   mc.S = S; mc.cur = V.cur; mc.multi = multi ? 1 : 0; mc.init = init ? 1 : 0;
   mc.nb_pq = V.nb_q[0]; mc.nb_pq2 = V.nb_q[1]; mc.pq_partials = V.Pq[0]; mc.pq_partials2 = V.Pq[1];
   mc.x = V.x; mc.r = V.r; mc.p = V.p; mc.q = V.q; mc.n = V.n;
   mc.rr_partials = pc->d_rr_partials; mc.lat_partials = pc->d_lat_partials;
-  mc.h_c_other = H(T, par ^ 1);
-  mc.n_dense = hF - H(T, par);
-  mc.gs_top = GS(T - 1);
+  mc.h_c_other = pc->acc(T, par ^ 1);
+  mc.n_dense = hF - pc->acc(T, par);
+  mc.gs_top = pc->state(T - 1);
   mc.buf = multi ? pc->d_mbuf : nullptr;
   mc.n_shared = multi ? pc->n_mshared : 0; mc.shared_idx = pc->d_mshared_idx;
   mc.n_intc = multi ? pc->n_mint_coarse : 0; mc.int_idx = pc->d_mint_idx;
-  mc.gs_c = GS(T); mc.h_c = H(T, par); mc.coef_c = pc->L[T].coef;
+  mc.gs_c = pc->state(T); mc.h_c = pc->acc(T, par); mc.coef_c = pc->L[T].coef;
   mc.n_top_buf = n_top;
-  mc.dbg = 0;
-  // scratch of the separable restrictions (3-D): the largest of the top restriction (one rank: level T -> T-1, + its output)
-  // and the LDS-resident ones; behind the levels when it fits
-  size_t lds_all = lds;
-  mc.sep_off = -1;
-  mc.flat = 0;
-  if (pc->dim == 3) {
-    auto need = [&](const int* nc, const int* nfn, bool with_out) -> int64_t {
-      const int64_t s1 = (int64_t)(nc[0] + 1) * (nfn[1] + 1) * (nfn[2] + 1), s2 = (int64_t)(nc[0] + 1) * (nc[1] + 1) * (nfn[2] + 1);
-      return s1 + s2 + (with_out ? (int64_t)(nc[0] + 1) * (nc[1] + 1) * (nc[2] + 1) : 0);
-    };
-    int64_t scratch = multi ? 0 : need(pc->L[T - 1].n, pc->L[T].n, true);
-    for (int l = 0; l + 1 <= T - 1; ++l) scratch = std::max(scratch, need(pc->L[l].n, pc->L[l + 1].n, false));
-    // the flattened chain (k_lattice_coarse_m: mc.flat): x- and y-pass outputs of ALL levels below T-1 at once
-    int64_t flat_need = 0;
-    const int top = T - 1;
-    // (the z-pass of the flattened chain reads the prefetched coefficient of node `tid`: one trip per level, i.e. every level
-    // below T-1 must have at most 1024 nodes -- true for the m0 in {2, 3} doubling lattices with TOP_MAX = 5120; checked here)
-    const bool one_trip = top >= 1 && pc->L[top - 1].nodes <= 1024;
-    if (top >= 1 && top <= 4 && one_trip) {
-      const int* nt = pc->L[top].n;
-      for (int k = 1; k <= top; ++k) {
-        const int* nc = pc->L[top - k].n;
-        flat_need += (int64_t)(nc[0] + 1) * (nt[1] + 1) * (nt[2] + 1) + (int64_t)(nc[0] + 1) * (nc[1] + 1) * (nt[2] + 1);
-      }
-    }
-    const int64_t off = (int64_t)(lds / sizeof(double));
-    mc.flat = 0;
-    if (flat_need > 0 && (off + std::max(scratch, flat_need)) * (int64_t)sizeof(double) <= 158 * 1024) {
-      mc.flat = 1;
-      scratch = std::max(scratch, flat_need);
-    }
-    if ((off + scratch) * (int64_t)sizeof(double) <= 158 * 1024) { mc.sep_off = off; lds_all = (size_t)(off + scratch) * sizeof(double); }
-    else mc.flat = 0;
-  }
-  if (lds_all > 64 * 1024 && !pc->merged_lds_set) {
-    FEMO_HIP_CHECK(hipFuncSetAttribute((const void*)k_lattice_coarse_m, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-    pc->merged_lds_set = true;
-  }
-  hipLaunchKernelGGL(k_lattice_coarse_m, dim3(1 + n_carry), dim3(1024), lds_all, st, CL, pc->dim, done, mc);
-  for (int l = T; l <= nl - 4; ++l) {            // N ranks, 2-D (three fused levels): the level between T-1 and the tile kernel's three
-    LatticeLevel& Fi = pc->L[l];
-    hipLaunchKernelGGL(k_lattice_prolong, dim3(lat_grid(Fi.nodes)), dim3(256), 0, st, Fi.n[0], Fi.n[1], Fi.n[2], pc->L[l - 1].n[0], pc->L[l - 1].n[1], pc->L[l - 1].n[2], pc->dim, pc->L[l - 1].e, Fi.coef, GS(l), 0, Fi.e, (double*)nullptr, (const double*)nullptr, done);
-  }
-  FineLevels FL;
-  const LatticeLevel &Lcc = pc->L[nl - 4], &Lc = pc->L[nl - 3], &Lm = pc->L[nl - 2];
-  for (int k = 0; k < 3; ++k) { FL.ncc[k] = Lcc.n[k]; FL.nc[k] = Lc.n[k]; FL.nm[k] = Lm.n[k]; FL.nf[k] = F.n[k]; }
-  FL.e_cc = Lcc.e;
-  FL.coef_c = Lc.coef; FL.g_c = GS(nl - 3); FL.g_c_other = H(nl - 3, par ^ 1);
-  FL.coef_m = Lm.coef; FL.g_m = GS(nl - 2); FL.g_m_other = H(nl - 2, par ^ 1);
-  FL.coef_f = F.coef; FL.g_f = GS(nl - 1); FL.e_f = F.e;
+  mc.dbg = 0;                                    // (read by the kernel only, see MergedCarry)
+  mc.sep_off = P.sep_off;
+  mc.flat = P.flat;
+  FEMO_TRY(raise_lds((const void*)k_lattice_coarse_m, P.lds_merged, 159 * 1024, &pc->merged_lds_set));
+  hipLaunchKernelGGL(k_lattice_coarse_m, dim3(1 + n_carry), dim3(1024), P.lds_merged, st, CL, pc->dim, done, mc);
+  for (int l = T; l <= nl - 4; ++l)              // 2-D (three fused levels): the level between T-1 and the tile kernel's three
+    launch_lattice_prolong(pc, l, pc->state(l), 0, nullptr, nullptr, st, done);
   // N > 1: the shared nodes' part of the dot comes from the carriers (replicated), the single-rank nodes' part from the
-  // reduced scalars; this launch adds nothing and walks the rank's own tiles only
-  FL.dot_partials = multi ? nullptr : pc->d_dot_partials;
-  FL.dot_weight = nullptr;
-  const int TF = pc->dim == 3 ? 8 : 16;
-  int64_t tiles = 1;
-  for (int k = 0; k < pc->dim; ++k) tiles *= (F.n[k] + TF) / TF;
-  const int32_t* tile_list = pc->n_my_tiles < tiles ? pc->d_my_tiles : nullptr;      // all of them: walk the plain range
-  if (tile_list != nullptr) tiles = pc->n_my_tiles;
-  // 128 threads per tile when 256-thread workgroups would not all be resident at once (see the kernel)
-  const bool small_blocks = tiles > 2048;      // (1.03 M rows, 1000 tiles: 7.7 us with 256 threads, 8.5 with 128)
-  const int grid3 = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, small_blocks ? 4096 : 2048));
-  const int nb_dot = multi ? 0 : grid3;
-  if (pc->dim == 3) {
-    if (small_blocks) hipLaunchKernelGGL((k_lattice_prolong3_m<3, 128>), dim3(grid3), dim3(128), 0, st, FL, hF, (const double*)S, init ? 1 : 0, tile_list, tiles, done);
-    else hipLaunchKernelGGL((k_lattice_prolong3_m<3, 256>), dim3(grid3), dim3(256), 0, st, FL, hF, (const double*)S, init ? 1 : 0, tile_list, tiles, done);
-  } else {
-    if (small_blocks) hipLaunchKernelGGL((k_lattice_prolong3_m<2, 128>), dim3(grid3), dim3(128), 0, st, FL, hF, (const double*)S, init ? 1 : 0, tile_list, tiles, done);
-    else hipLaunchKernelGGL((k_lattice_prolong3_m<2, 256>), dim3(grid3), dim3(256), 0, st, FL, hF, (const double*)S, init ? 1 : 0, tile_list, tiles, done);
-  }
+  // reduced scalars; the tile launch adds nothing and walks the rank's own tiles only
+  const FineLevels FL = fine_levels(pc, pc->state(nl - 3), pc->state(nl - 2), pc->state(nl - 1), par ^ 1, multi ? nullptr : pc->d_dot_partials, nullptr);
+  by_dim(pc->dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    if (P.m_small) hipLaunchKernelGGL((k_lattice_prolong3_m<DIM, 128>), dim3(P.m_grid), dim3(128), 0, st, FL, hF, (const double*)S, init ? 1 : 0, P.m_tile_list, P.m_tiles, done);
+    else hipLaunchKernelGGL((k_lattice_prolong3_m<DIM, 256>), dim3(P.m_grid), dim3(256), 0, st, FL, hF, (const double*)S, init ? 1 : 0, P.m_tile_list, P.m_tiles, done);
+  });
   pc->parity ^= 1;
-  PcgStop ps;
-  ps.rtol2_factor = stop ? stop->rtol2_factor : 0.0;
-  ps.atol_pc2 = stop ? stop->atol_pc2 : 0.0;
-  ps.tolg2 = stop ? stop->tolg2 : nullptr;
-  ps.flags = stop ? stop->flags : nullptr;
-  ps.it = stop ? stop->it : 0;
   MergedScal ms;
   ms.S = S; ms.multi = multi ? 1 : 0; ms.init = init ? 1 : 0;
   ms.nb_lat = n_carry; ms.lat_partials = pc->d_lat_partials;
   ms.nb_rr = (multi || init) ? 0 : n_carry; ms.rr_partials = pc->d_rr_partials;
   ms.atol2 = V.atol2;
-  const int mode = init ? 2 : 1;
-  double* gamma_cur = S + MS_GAMMA + V.cur;
-  double* gamma_nxt = init ? S + MS_GAMMA + V.cur : S + MS_GAMMA + (V.cur ^ 1);
-  auto prolong = [&](unsigned grid, const HaloFirst& hf) {
-    if (pc->dim == 3)
-      hipLaunchKernelGGL(k_prolong_mesh<3>, dim3(grid), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, pc->d_pk, (const double*)V.r, pc->d_sinv, mask, F.e, V.p, mode, nb_dot, pc->d_dot_partials, (const double*)nullptr, 0, (const double*)nullptr, S + MS_RR, (const double*)gamma_cur, gamma_nxt, done, ps, ms, hf);
-    else
-      hipLaunchKernelGGL(k_prolong_mesh<2>, dim3(grid), dim3(FEMO_BLOCK), 0, st, m->n_rows, lat, pc->d_pk, (const double*)V.r, pc->d_sinv, mask, F.e, V.p, mode, nb_dot, pc->d_dot_partials, (const double*)nullptr, 0, (const double*)nullptr, S + MS_RR, (const double*)gamma_cur, gamma_nxt, done, ps, ms, hf);
-  };
+  // the new direction: p = zh (first apply) or zh + beta p, gamma' to the other parity's scalar
+  const FemoPcApply a = {.rh = V.r, .out = V.p, .mode = init ? 2 : 1, .rho = S + MS_RR, .gamma_cur = S + MS_GAMMA + V.cur,
+                         .gamma_nxt = S + MS_GAMMA + (init ? V.cur : V.cur ^ 1), .done = done, .stop = stop};
+  const int nb_dot = multi ? 0 : P.m_grid;
+  auto prolong = [&](unsigned grid, const HaloFirst& hf) { launch_prolong_mesh(m, mask, a, grid, nb_dot, nullptr, ms, hf); };
   if (femo_pc_merged_sends_halo(m)) {
     // the interface vertices first, straight into the send buffer; the exchange of the new direction then travels on the
-    // communication stream under the bulk of the prolongation and the interior slices of the next SpMV (solver.hip:
-    // femo_halo_spmv_inflight waits for it before the boundary slices)
+    // communication stream under the bulk of the prolongation and the interior slices of the next SpMV (spmv.hip:
+    // halo_spmv_inflight waits for it before the boundary slices)
     if (femo_halo_direct_ready(m)) {
       // device-initiated (round 6): the stores go to the neighbours' inboxes, the workgroups bump their counters; the
-      // consumer is the small pull launch in front of the next product's boundary slices (solver.hip: halo_spmv_inflight)
+      // consumer is the small pull launch in front of the next product's boundary slices (spmv.hip: halo_spmv_inflight)
       ++ctx->n_neighbor; ctx->neighbor_doubles += m->send_ptr[m->n_nbr];
       const unsigned long long epoch = femo_halo_direct_begin(m);
       m->hd->loop_epoch = epoch;
@@ -2524,13 +2499,13 @@ bool femo_pc_merged_sends_halo(const femo_mesh* m) {
          m->ctx->comm_stream != nullptr;
 }
 
-// can the PCG loop hand its partial rh.rh to femo_pc_apply instead of all-reducing it itself?
-
+// x += alpha p in the classic loop's coarse launch (FemoXUpdate): where the fused lattice cycle runs, on one rank
 bool femo_pc_carries_xupdate(const femo_mesh* m) {
   const bool off = femo_env_flag("FEMO_PCG_NO_XCARRY");        // read per solve (a test switches it), never per launch
-  return !off && m->pc != nullptr && m->pc->fused_cycle_seen && m->ctx->nranks == 1;
+  return !off && m->pc != nullptr && m->pc->plan.fused_cycle && m->ctx->nranks == 1;
 }
 
+// can the PCG loop hand its partial rh.rh to femo_pc_apply instead of all-reducing it itself?
 bool femo_pc_can_piggyback(const femo_mesh* m) { return m->pc != nullptr && m->ctx->nranks > 1 && m->pc->shared_ready; }
 
 int femo_pc_levels(const femo_mesh* m, int* n_levels, int64_t* finest_nodes) {

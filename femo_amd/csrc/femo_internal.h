@@ -550,14 +550,12 @@ int femo_coll_neighbors(femo_ctx* ctx, int n_nbr, const int32_t* nbr, const int6
                         const int64_t* recv_ptr, double* d_recv, hipStream_t st);
 int femo_pc_build(femo_mesh* m);
 void femo_pc_destroy(femo_mesh* m);
-// mode 0: out = M^-1 rh (scaled variables).  mode 1: out = M^-1 rh + beta out with beta = gamma'/(*gamma_cur),
-// gamma' = rh.M^-1 rh = *rho + g_L.e_L, written to *gamma_nxt.  mode 2: like 1 with beta = 0.
-// stopping test of the BPX-PCG loop, evaluated inside the preconditioner apply (see k_prolong_mesh)
+// stopping test of the BPX-PCG loop, evaluated inside the preconditioner apply (see k_prolong_mesh, which takes it by value)
 struct FemoPcgStop {
-  double rtol2_factor;
-  double atol_pc2;
-  double* tolg2;
-  int32_t* flags;
+  double rtol2_factor;     // rtol^2 (x b.D^-1 b / r0.D^-1 r0 for a non-zero initial guess)
+  double atol_pc2;         // absolute threshold on gamma
+  double* tolg2;           // device scalar: rtol^2 * gamma_0
+  int32_t* flags;          // [0] stamp (it + 1) once converged, [1] iterations, [2] breakdown
   int it;
 };
 // The solver's x += alpha p, carried by the idle compute units of the single-workgroup coarse-lattice kernel (round 3): the
@@ -598,17 +596,27 @@ bool femo_pc_merged_ok(femo_mesh* m);                 // the fused lattice cycle
 struct FemoZeroExtra { double* p[3]; int64_t n[3]; int count; };     // small regions the caller wants cleared by the same launch
 int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra = nullptr);
 int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const FemoMergedVecs& V, double* S,
-                         const int32_t* done, const struct FemoPcgStop* stop);
+                         const int32_t* done, const FemoPcgStop* stop);
 // N > 1: does femo_pc_merged_apply start the halo exchange of the direction it produces (interface vertices first, send buffer
 // filled by the prolongation itself)?  Then the loop's SpMV must not exchange again: femo_halo_spmv(inflight).
 bool femo_pc_merged_sends_halo(const femo_mesh* m);
 int femo_pc_merged_collectives(const femo_mesh* m);   // all-reduces per iteration of the merged loop on this mesh (0 on one rank)
-// nb_rho > 0: rho = rh.rh is folded from rho_partials[0:nb_rho] inside the apply (and stored to *rho)
-int femo_pc_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const double* s, const double* rh, double* out,
-                  int mode, double* rho, const double* gamma_cur, double* gamma_nxt, const int32_t* done, int gv,
-                  bool rho_is_partial = false, const FemoPcgStop* stop = nullptr, int nb_rho = 0,
-                  const double* rho_partials = nullptr, const FemoXUpdate* xupdate = nullptr);
-bool femo_pc_carries_xupdate(const femo_mesh* m);   // after the first apply on the mesh: the fused lattice cycle runs
+// One application of the preconditioner in scaled variables (bpx.hip), described by an aggregate built with designated
+// initialisers at the call site.  mode 0: out = M^-1 rh.  mode 1: out = M^-1 rh + beta out with beta = gamma'/(*gamma_cur),
+// gamma' = rh.M^-1 rh = *rho + g_L.e_L, written to *gamma_nxt.  mode 2: like 1 with beta = 0.
+struct FemoPcApply {
+  const double* rh; double* out;
+  int mode = 0;
+  double* rho = nullptr; const double* gamma_cur = nullptr; double* gamma_nxt = nullptr;   // modes 1 and 2 (rho: read, or folded and stored: nb_rho)
+  const int32_t* done = nullptr;         // nothing once *done is set
+  int gv = 0;                            // grid of the mesh-sized launch
+  bool rho_is_partial = false;           // *rho is this rank's part: it rides in the lattice all-reduce (femo_pc_can_piggyback)
+  const FemoPcgStop* stop = nullptr;
+  int nb_rho = 0; const double* rho_partials = nullptr;   // nb_rho > 0: rho is folded from rho_partials[0:nb_rho] inside the apply (and stored to *rho)
+  const FemoXUpdate* xupdate = nullptr;  // only where femo_pc_carries_xupdate()
+};
+int femo_pc_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const FemoPcApply& a);
+bool femo_pc_carries_xupdate(const femo_mesh* m);   // once the hierarchy is built: the fused lattice cycle runs on this mesh
 bool femo_pc_can_piggyback(const femo_mesh* m);
 int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask);
 int femo_pc_levels(const femo_mesh* m, int* n_levels, int64_t* finest_nodes);

@@ -988,7 +988,10 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   stop.tolg2 = S + S_TOLG;
   stop.flags = ctx->d_flags;
   stop.it = -1;
-  FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, A->d_s, w.r, w.p, 2, S + S_RHO, S + S_GAMMA + 1, S + S_GAMMA, ctx->d_flags, gv, false, &stop));
+  FemoPcApply pc = {.rh = w.r, .out = w.p, .mode = 2, .rho = S + S_RHO, .gamma_cur = S + S_GAMMA + 1, .gamma_nxt = S + S_GAMMA,
+                    .done = ctx->d_flags, .gv = gv, .stop = &stop};
+  FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, pc));
+  pc.mode = 1;                                  // from here on: the next direction, zh + beta ph
   FEMO_TRY(read_back(ctx, nullptr));
   const double gamma0 = ctx->h_scal[S_GAMMA];
   info->pc_rhs_norm = std::sqrt(gamma0 * (rho0 > 0.0 ? bb / rho0 : 1.0));
@@ -1033,6 +1036,8 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
       double* Pr = P + 1 * FEMO_MAX_PARTIALS;
       double* Pg = P + 2 * FEMO_MAX_PARTIALS;   // boundary-slice partials of the overlapped SpMV
       stop.it = it;
+      FemoPcApply a = pc;                         // this iteration's apply: the branches below add what differs
+      a.gamma_cur = S + S_GAMMA + cur; a.gamma_nxt = S + S_GAMMA + nxt;
       if (local_scalars) {
         // single GPU: the consumers fold the per-block partials themselves
         // ph = M^-1 rh + beta ph in one pass: rh.zh = rho + g_L.e_L is known before the mesh prolongation, and
@@ -1040,14 +1045,16 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
         if (use_atol) {
           hipLaunchKernelGGL(k_pcg_xr, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, cur, g1, Pd, S, w.q, w.p, (const double*)r_cur, r_cur, w.xh, Pr, ctx->d_flags);
           hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(1024), 0, st, it, gv, Pr, S, ctx->d_flags);
-          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, A->d_s, r_cur, w.p, 1, S + S_RHO, S + S_GAMMA + cur, S + S_GAMMA + nxt, ctx->d_flags, gv, false, &stop));
+          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, a));
         } else if (carry_x) {
           hipLaunchKernelGGL(k_pcg_xr, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, cur, g1, Pd, S, w.q, w.p, (const double*)r_cur, r_cur, w.xh, Pr, ctx->d_flags, 1);
           const FemoXUpdate xu = {w.xh, w.p, S + S_ALPHA, n};
-          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, A->d_s, r_cur, w.p, 1, S + S_RHO, S + S_GAMMA + cur, S + S_GAMMA + nxt, ctx->d_flags, gv, false, &stop, gv, Pr, &xu));
+          a.nb_rho = gv; a.rho_partials = Pr; a.xupdate = &xu;
+          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, a));
         } else {
           hipLaunchKernelGGL(k_pcg_xr, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, cur, g1, Pd, S, w.q, w.p, (const double*)r_cur, r_cur, w.xh, Pr, ctx->d_flags);
-          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, A->d_s, r_cur, w.p, 1, S + S_RHO, S + S_GAMMA + cur, S + S_GAMMA + nxt, ctx->d_flags, gv, false, &stop, gv, Pr));
+          a.nb_rho = gv; a.rho_partials = Pr;
+          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, a));
         }
       } else {
         FEMO_TRY(femo_launch_fold(1024, g1, 1, Pd, S + S_DELTA, st, ctx->d_flags, g2, Pg));
@@ -1057,12 +1064,13 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
         if (piggyback) {
           // the rank's part of rh.rh rides in the lattice all-reduce of the preconditioner; the stopping
           // test then runs after the apply (one wasted apply in the last iteration, one collective less in all)
-          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, A->d_s, w.r, w.p, 1, S + S_RHO, S + S_GAMMA + cur, S + S_GAMMA + nxt, ctx->d_flags, gv, true, &stop));
+          a.rho_is_partial = true;
+          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, a));
           if (use_atol) hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(1024), 0, st, it, 0, Pr, S, ctx->d_flags);
         } else {
           FEMO_TRY(allreduce1(S + S_RHO));
           if (use_atol) hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(1024), 0, st, it, 0, Pr, S, ctx->d_flags);
-          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, A->d_s, w.r, w.p, 1, S + S_RHO, S + S_GAMMA + cur, S + S_GAMMA + nxt, ctx->d_flags, gv, false, &stop));
+          FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, a));
         }
       }
     }
@@ -1102,7 +1110,7 @@ extern "C" int femo_mat_pc_apply(const femo_mat* A_, const femo_vec* r, femo_vec
   if (n == 0) return 0;
   // rh = S r, zh = Mh^-1 rh, z = S zh
   hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, r->d, (const double*)nullptr, A->d_s, w.r, w.p, w.xh, ctx->d_partials, (const uint8_t*)nullptr);
-  FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, A->d_s, w.r, w.sv, 0, nullptr, nullptr, nullptr, ctx->d_flags, gv));
+  FEMO_TRY(femo_pc_apply(m, mask, A->pc_key, FemoPcApply{.rh = w.r, .out = w.sv, .done = ctx->d_flags, .gv = gv}));
   hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, st, n, 0, A->d_s, w.sv, z->d);
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;

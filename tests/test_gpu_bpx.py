@@ -181,10 +181,11 @@ def test_operator_stack_with_bpx_matches_jacobi(ctx, d, n):
     assert max(itb) < max(itj)
 
 
-@pytest.mark.parametrize("d,n,jit", [(2, 37, 0.2), (2, 64, 0.0), (3, 9, 0.25), (3, 20, 0.2), (3, 32, 0.0)])
+@pytest.mark.parametrize("d,n,jit", [(2, 37, 0.2), (2, 64, 0.0), (3, 9, 0.25), (3, 20, 0.2), (3, 32, 0.0), (2, 110, 0.2)])
 def test_pc_apply_matches_the_oracle_operator(ctx, d, n, jit):
     """femo_mat_pc_apply = the operator oracle/bpx_oracle.py writes down (lattice choice, packed
-    coordinates, keep rule, level weights, nested transfers), to rounding error; and it is symmetric."""
+    coordinates, keep rule, level weights, nested transfers), to rounding error; and it is symmetric.
+    (2, 110): the smallest mesh on which the apply runs its fused lattice cycle (six levels, three of them brick-fused)."""
     from femo_amd import engine as E
     from oracle import bpx_oracle as bo
     m = fo.unit_square_mesh(n, jit) if d == 2 else fo.unit_cube_mesh(n, jit)
