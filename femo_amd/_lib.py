@@ -34,6 +34,7 @@ ELAST_RAMP = 1
 ELAST_INFO_KEYS = ("dim", "n_dof", "nnz", "sell_entries", "spmv_bytes")
 ELAST_PC = {"jacobi": 0, "multilevel": 1}
 ELAST_MAX_COLS = 8                # FEMO_ELAST_MAX_COLS: load cases of one batched product / solve
+ELAST_MASS_LAWS = {"linear": 0, "du_olhoff": 1}    # FEMO_ELAST_MASS_LINEAR, FEMO_ELAST_MASS_DU_OLHOFF
 ELAST_PC_INFO_COUNT = 16           # [levels, lattice bytes, block builds, last build us, nodes per level ...]
 
 
@@ -48,6 +49,16 @@ class SolveInfo(C.Structure):
                 ("rhs_norm", C.c_double),
                 ("solve_ms", C.c_double), ("spmv_ms", C.c_double),
                 ("spmv_samples", C.c_int32), ("loop_allreduces", C.c_int32)]
+
+
+class EigOpts(C.Structure):
+    _fields_ = [("rtol", C.c_double), ("pcg_rtol", C.c_double), ("max_outer", C.c_int32), ("pcg_max_it", C.c_int32),
+                ("pc", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EigInfo(C.Structure):
+    _fields_ = [("outer_iterations", C.c_int32), ("pcg_iterations", C.c_int32), ("converged", C.c_int32),
+                ("reserved", C.c_int32), ("residual", C.c_double * ELAST_MAX_COLS), ("solve_ms", C.c_double)]
 
 
 class HostStats(C.Structure):
@@ -214,6 +225,12 @@ PROTOTYPES = {
                                                 H, H, C.c_int]),
     "femo_elast_von_mises_multi": (C.c_int, [H, C.c_int, H, H, c_f64p, C.c_double, C.c_int, H]),
     "femo_elast_body_apply": (C.c_int, [H, C.c_int, c_f64p, C.c_int, C.c_double, H, H, C.c_int, H, C.c_int]),
+    "femo_elast_mass_apply_multi": (C.c_int, [H, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, H, H, H]),
+    "femo_elast_block_gram": (C.c_int, [H, C.c_int, H, C.c_int, H, c_f64p]),
+    "femo_elast_block_rotate": (C.c_int, [H, C.c_int, c_f64p, H, H]),
+    "femo_elast_eig_drho": (C.c_int, [H, C.c_int, C.c_int, C.c_double, C.c_int, H, H, c_f64p, c_f64p, H, C.c_int]),
+    "femo_elast_eigs": (C.c_int, [H, C.c_int, C.c_double, H, C.c_int, C.c_int, H, C.POINTER(EigOpts), c_f64p,
+                                  C.POINTER(EigInfo)]),
     "femo_elast_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "femo_elast_pc_setup": (C.c_int, [H, C.c_double]),
     "femo_elast_pc_info": (C.c_int, [H, c_i64p]),

@@ -18,24 +18,6 @@ constexpr int EMC = FEMO_ELAST_MAX_COLS;
 
 struct BodyForces { double v[EMC][3]; };
 
-// |T| of a P1 simplex from the vertices in `conn` order (the volume of simplex_grads without the gradients)
-template <int D>
-__device__ __forceinline__ double simplex_volume(const double (&p)[D + 1][D]) {
-  double m[D][D];
-#pragma unroll
-  for (int k = 0; k < D; ++k)
-#pragma unroll
-    for (int i = 0; i < D; ++i) m[k][i] = p[k + 1][i] - p[0][i];
-  if constexpr (D == 2) {
-    return 0.5 * fabs(m[0][0] * m[1][1] - m[0][1] * m[1][0]);
-  } else {
-    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1];
-    const double c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2];
-    const double c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
-    return fabs(m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02) * (1.0 / 6.0);
-  }
-}
-
 // N: one thread per vertex row, the visit walk of k_elast_drho_N.  s_v once, then every column and component:
 //   y = [accumulate ? y : (base ? base : 0)] + a s_v b_l[i],   or 0 on a fixed dof (fixed != null: the same set per column)
 template <int D>

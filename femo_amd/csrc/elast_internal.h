@@ -1,6 +1,6 @@
 // Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product and PCG), elast_pc.hip
-// (multilevel preconditioner) and elast_stress.hip (stress aggregate), each for one or several load cases.  Not part of
-// the ABI.
+// (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, and elast_eig.hip
+// (mass product, block linear algebra and the eigen solve).  Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -34,6 +34,12 @@ struct femo_elast {
   // stress aggregate (femo_elast_pnorm_stress, femo_elast_pnorm_stress_multi): FEMO_ELAST_MAX_COLS slabs of partials, one per
   // column, and the folded values behind them, on first use
   double* w_smpart = nullptr;
+  // eigen solve (elast_eig.hip), on first use: the right-hand sides B = M X of w_eig_cols columns; the Gram partials and
+  // their folded values, with their pinned mirror
+  double* w_eig = nullptr;
+  int w_eig_cols = 0;
+  double* w_gram = nullptr;
+  double* h_gram = nullptr;     // pinned
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
   femo_elast_pc* pc = nullptr;
   bool pc_dirty = true;
@@ -86,6 +92,10 @@ int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const doub
                     double* part, int64_t part_stride, const int32_t* done);
 // PCG work vectors for at least n_cols columns.  who: the entry point, for the error text.
 int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who);
+// The batched PCG of femo_elast_solve_multi for a caller that has checked its arguments (the eigen solve): info: n_cols
+// records, or null.
+int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
+                   const char* who);
 
 #if defined(__HIPCC__)
 // gradients of the barycentric coordinates and the volume of a P1 simplex, from the vertices in `conn` order
@@ -132,6 +142,24 @@ __device__ __forceinline__ void simplex_grads(const double (&p)[D + 1][D], doubl
 #pragma unroll
     for (int k = 1; k <= D; ++k) s += g[k][i];
     g[0][i] = -s;
+  }
+}
+
+// |T| of a P1 simplex from the vertices in `conn` order (the volume of simplex_grads without the gradients)
+template <int D>
+__device__ __forceinline__ double simplex_volume(const double (&p)[D + 1][D]) {
+  double m[D][D];
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+#pragma unroll
+    for (int i = 0; i < D; ++i) m[k][i] = p[k + 1][i] - p[0][i];
+  if constexpr (D == 2) {
+    return 0.5 * fabs(m[0][0] * m[1][1] - m[0][1] * m[1][0]);
+  } else {
+    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1];
+    const double c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2];
+    const double c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+    return fabs(m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02) * (1.0 / 6.0);
   }
 }
 
@@ -188,6 +216,19 @@ __device__ __forceinline__ double penal_d(int method, double r) {
   if (method == FEMO_ELAST_SIMP) return 3.0 * r * r;
   const double q = 1.0 + 8.0 * (1.0 - r);
   return 9.0 / (q * q);
+}
+
+// mass per unit of solid mass at density r: linear, or Du & Olhoff's law -- r for r >= 0.1, 6e5 r^6 - 5e6 r^7 below (value 0.1
+// and slope 1 at the joint), which keeps low-density regions from carrying spurious localised modes
+__device__ __forceinline__ double mass_law(int law, double r) {
+  if (law == FEMO_ELAST_MASS_LINEAR || r >= 0.1) return r;
+  const double r2 = r * r, r6 = r2 * r2 * r2;
+  return 6e5 * r6 - 5e6 * (r6 * r);
+}
+__device__ __forceinline__ double mass_law_d(int law, double r) {
+  if (law == FEMO_ELAST_MASS_LINEAR || r >= 0.1) return 1.0;
+  const double r2 = r * r, r5 = r2 * r2 * r;
+  return 36e5 * r5 - 35e6 * (r5 * r);
 }
 
 // block (a, b) of the element matrix without the factor C |T|; written symmetrically in (a, r) <-> (b, c)

@@ -338,6 +338,11 @@ int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const doub
   return 0;
 }
 
+int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
+                   const char* who) {
+  return pcg_solve(e, n_cols, b, x, opts, info, who);
+}
+
 int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who) {
   if (e->w_cols >= n_cols) return 0;
   femo_mesh* m = e->mesh;

@@ -1,6 +1,6 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
-product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip).  One load case is the L = 1 case of several:
+product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
@@ -35,6 +35,14 @@ are used unchanged.
                        whose right-hand sides are not loads: they are non-zero on the clamped dofs of every column
   MultiLoadVonMises    the cell field max_l s_l rho_e^q sigma_vm,e(u_l) (the envelope over the load cases), or that of one
                        load case, for `project` / FEA.add_field_output
+  ElasticityEigenvalues  the lowest eigenpairs of K(rho) phi = lambda M(rho) phi on the free dofs, M = density sum_e m(rho_e)
+                       M0_e the consistent P1 mass with m = rho or Du & Olhoff's C^1 cut-off below rho = 0.1: block inverse
+                       iteration with Rayleigh-Ritz, every inner solve one batched PCG over the block (csrc/elast_eig.hip),
+                       warm-started from the previous modes.  Not in the reference's script
+  EigenvalueAggregate  J = ((1/n) sum_{k<n} lambda_k^-p)^(-1/p), a smooth stand-in for the fundamental eigenvalue that is
+                       symmetric within a cluster, as a scalar output of the density alone: dJ/drho = sum_k c_k (C'(rho_e)
+                       phi_k^T K0_e phi_k - lambda_k density m'(rho_e) phi_k^T M0_e phi_k) in one launch, no adjoint solve.
+                       ``n_modes`` should not split a cluster of (nearly) equal eigenvalues
 
 P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
 """
@@ -53,6 +61,7 @@ from .function import Function, FunctionSpace, LoadCaseSpace, VectorFunctionSpac
 from .io import MeshTags
 
 METHODS = {"SIMP": _lib.ELAST_SIMP, "RAMP": _lib.ELAST_RAMP}
+MASS_LAWS = _lib.ELAST_MASS_LAWS          # "linear" (m = rho) | "du_olhoff" (C^1 cut-off below rho = 0.1)
 PRECONDITIONERS = _lib.ELAST_PC           # "jacobi" (block diagonal) | "multilevel" (csrc/elast_pc.hip)
 
 
@@ -224,6 +233,72 @@ class DeviceElasticity:
                                              float(a), x.handle, None if base is None else base.handle,
                                              int(bool(zero_fixed)), y.handle, int(bool(accumulate))))
         return y
+
+    # ---- eigenfrequencies: K phi = lambda M(rho) phi on the free dofs (csrc/elast_eig.hip) ----
+    @staticmethod
+    def _mass_law(mass_law: str) -> int:
+        if mass_law not in MASS_LAWS:
+            raise _lib.FemoError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
+        return MASS_LAWS[mass_law]
+
+    def mass_apply_multi(self, n_cols: int, rho: Vec, x: Vec, y: Vec, masked: bool = False, a: float = 1.0,
+                         density: float = 1.0, mass_law: str = "linear") -> Vec:
+        """y_l = a M(rho) x_l with the consistent P1 mass M = density sum_e m(rho_e) M0_e, matrix free, for all ``n_cols``
+        columns in one launch; ``masked``: M_ff (fixed entries of x read as 0, exact zeros on the fixed dofs of y)."""
+        check(self.lib.femo_elast_mass_apply_multi(self.handle, self._mass_law(mass_law), float(density), int(bool(masked)),
+                                                   self._cols(n_cols, x, y), float(a), rho.handle, x.handle, y.handle))
+        return y
+
+    def block_gram(self, n_a: int, a: Vec, n_b: int, b: Vec) -> np.ndarray:
+        """(n_a, n_b): G[i, j] = a_i . b_j, all pairs in one pass."""
+        n_a, n_b = self._cols(n_a, a), self._cols(n_b, b)
+        G = np.zeros(max(n_a, 1) * max(n_b, 1))
+        check(self.lib.femo_elast_block_gram(self.handle, n_a, a.handle, n_b, b.handle, G.ctypes.data_as(_lib.c_f64p)))
+        return G.reshape(n_a, n_b)
+
+    def block_rotate(self, n_cols: int, Q, x: Vec, y: Vec) -> Vec:
+        """y_j = sum_i x_i Q[i, j] for the ``n_cols`` columns; ``y`` may be ``x``."""
+        n_cols = self._cols(n_cols, x, y)
+        Qa = np.ascontiguousarray(Q, dtype=np.float64)
+        if Qa.shape != (n_cols, n_cols):
+            raise _lib.FemoError(f"block_rotate: {n_cols} columns need a {n_cols} x {n_cols} matrix")
+        check(self.lib.femo_elast_block_rotate(self.handle, n_cols, Qa.ctypes.data_as(_lib.c_f64p), x.handle, y.handle))
+        return y
+
+    def eig_drho(self, method: int, n_modes: int, rho: Vec, phi: Vec, lam, c, y: Vec, density: float = 1.0,
+                 mass_law: str = "linear", accumulate: bool = False) -> Vec:
+        """y[n_cell] (+)= sum_k c_k [C'(rho) phi_k^T K0 phi_k - lam_k density m'(rho) phi_k^T M0 phi_k] in one launch: with
+        M-orthonormal modes the bracket is d lambda_k / d rho."""
+        n_modes = self._cols(n_modes, phi)
+        lv, cv = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (lam, c))
+        if lv.size != n_modes or cv.size != n_modes:
+            raise _lib.FemoError(f"eig_drho: {n_modes} modes need as many eigenvalues and weights")
+        f64 = lambda a: a.ctypes.data_as(_lib.c_f64p)
+        check(self.lib.femo_elast_eig_drho(self.handle, int(method), self._mass_law(mass_law), float(density), n_modes,
+                                           rho.handle, phi.handle, f64(lv), f64(cv), y.handle, int(bool(accumulate))))
+        return y
+
+    def eigs(self, n_modes: int, rho: Vec, X: Vec, block: Optional[int] = None, density: float = 1.0,
+             mass_law: str = "linear", rtol: float = 1e-9, max_outer: int = 200, pcg_rtol: float = 1e-12,
+             pcg_max_it: int = 0, pc: str = "jacobi"):
+        """The ``n_modes`` lowest eigenpairs of the assembled K and M(rho) on the free dofs by block inverse iteration with
+        Rayleigh-Ritz; every inner solve is one batched PCG over the ``block`` columns of ``X`` (the start block on entry,
+        the M-orthonormal modes on return; the last block - n_modes columns are guard vectors).  Returns (lambda[block]
+        ascending, info) with info = dict(outer_iterations, pcg_iterations, converged, residual, solve_ms)."""
+        if pc not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
+        n_modes = int(n_modes)
+        block = min(_lib.ELAST_MAX_COLS, n_modes + 2) if block is None else int(block)
+        block = self._cols(block, X)
+        opts = _lib.EigOpts(rtol=float(rtol), pcg_rtol=float(pcg_rtol), max_outer=int(max_outer), pcg_max_it=int(pcg_max_it),
+                            pc=PRECONDITIONERS[pc], reserved=0)
+        info = _lib.EigInfo()
+        lam = np.zeros(_lib.ELAST_MAX_COLS)
+        check(self.lib.femo_elast_eigs(self.handle, self._mass_law(mass_law), float(density), rho.handle, n_modes, block,
+                                       X.handle, C.byref(opts), lam.ctypes.data_as(_lib.c_f64p), C.byref(info)))
+        return lam[:block].copy(), dict(outer_iterations=info.outer_iterations, pcg_iterations=info.pcg_iterations,
+                                        converged=info.converged, residual=np.array(info.residual[:block]),
+                                        solve_ms=info.solve_ms, preconditioner=pc)
 
     def pnorm_stress_multi(self, n_cols: int, rho: Vec, u: Vec, m, p: float, q: float, alpha: float, weights=None,
                            value: bool = True, grad_u: Optional[Vec] = None, grad_rho: Optional[Vec] = None,
@@ -1051,6 +1126,143 @@ class MultiLoadVonMises(ElasticityVonMises):
         self._setup(u, rho, V.mesh, V.n_cases, scales, None if load_case is None else int(load_case), E, nu, q)
 
 
+class ElasticityEigenvalues:
+    """The ``n_modes`` lowest eigenpairs of K(rho) phi = lambda M(rho) phi with the supports ``bcs`` (homogeneous; at least
+    one: a free-free structure needs a shift, which is out of scope), by `DeviceElasticity.eigs` in a block of ``block``
+    columns (the block - n_modes last ones are guard vectors).  M is the consistent P1 mass, density ``density`` times
+    m(rho): ``mass_law`` "linear" or "du_olhoff".
+
+    ``modes`` is a Function(LoadCaseSpace(V, block)): M-orthonormal, zeros on the fixed dofs, the entry of largest
+    magnitude of each column positive.  `eigenvalues` re-solves only when the density (its version or its vector) or the
+    fixed set changed, from the previous modes (a seeded random block the first time).  K is reassembled the way
+    `ElasticityResidual.stiffness` does it, on the same handle and with the same ownership key, so a static residual on the
+    same mesh keeps working beside it.  ``last_info`` keeps the record of the last solve; a solve that does not converge
+    raises.
+
+    Out of scope: partitioned meshes, lumped non-structural masses, buckling."""
+
+    def __init__(self, rho: Function, V: VectorFunctionSpace, bcs, n_modes: int, block: Optional[int] = None, E: float = 1.0,
+                 nu: float = 0.3, method: str = "SIMP", density: float = 1.0, mass_law: str = "linear",
+                 preconditioner: str = "jacobi", rtol: float = 1e-9, seed: int = 0):
+        name = type(self).__name__
+        if isinstance(V, LoadCaseSpace) or not isinstance(V, VectorFunctionSpace):
+            raise NotImplementedError(f"{name} needs the VectorFunctionSpace(mesh, ('CG', 1)) of one displacement field")
+        if getattr(V.mesh, "local", None) is not None and V.mesh.local.nranks > 1:
+            raise NotImplementedError(f"{name}: partitioned meshes are out of scope")
+        if rho.function_space.family != "DG" or rho.function_space.mesh is not V.mesh:
+            raise NotImplementedError(f"{name} needs a DG0 density on the mesh of V")
+        if method not in METHODS:
+            raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
+        if mass_law not in MASS_LAWS:
+            raise ValueError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
+        if preconditioner not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {preconditioner!r} (jacobi or multilevel)")
+        n_modes = int(n_modes)
+        block = min(_lib.ELAST_MAX_COLS, n_modes + 2) if block is None else int(block)
+        if not 1 <= n_modes <= block <= _lib.ELAST_MAX_COLS:
+            raise ValueError(f"{name}: {n_modes} modes in a block of {block} (1 <= n_modes <= block <= {_lib.ELAST_MAX_COLS})")
+        mask, vals = _fixed_data(V.dim, bcs)
+        if mask is None or not mask.any():
+            raise NotImplementedError(f"{name}: without supports K is singular (free-free structures need a shift)")
+        if np.any(vals != 0.0):
+            raise NotImplementedError(f"{name}: the supports of an eigenproblem are homogeneous")
+        self.rho, self.V, self.mesh, self._mask = rho, V, V.mesh, mask
+        self.n_modes, self.block, self.n_dof = n_modes, block, V.dim
+        self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
+        self.density, self.mass_law, self.preconditioner = float(density), mass_law, preconditioner
+        self.rtol, self.pcg_rtol, self.max_outer, self.seed = float(rtol), 1e-12, 200, int(seed)
+        self.modes = Function(LoadCaseSpace(V, block))
+        self._lam = None
+        self._key = None
+        self._started = False
+        self.last_info = {}
+
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
+
+    def stiffness(self) -> DeviceElasticity:
+        """`ElasticityResidual.stiffness`: the handle with K(rho) of the current density and this object's fixed set."""
+        dev = self.device()
+        want = hash(self._mask.tobytes())
+        if dev.fixed_key != want:
+            dev.set_fixed(self._mask)
+        key = (self.rho.version, id(self.rho.vec), dev.fixed_key, self.method_id, id(self))
+        if getattr(dev, "_owner", None) != key:
+            dev.assemble(self.method_id, self.rho.vec)
+            dev._owner = key
+        if self.preconditioner == "multilevel" and dev.pc_plan is None:
+            dev.pc_setup()
+        return dev
+
+    def eigenvalues(self) -> np.ndarray:
+        """lambda_0 <= ... <= lambda_{n_modes-1} of the current density."""
+        key = (self.rho.version, id(self.rho.vec), hash(self._mask.tobytes()))
+        if key == self._key:
+            return self._lam[:self.n_modes].copy()
+        from .utils_hip import LAST_KSP_INFO
+        dev = self.stiffness()
+        if not self._started:                                          # afterwards: the previous modes
+            free = self._mask == 0
+            X = np.zeros((self.block, self.n_dof))
+            X[:, free] = np.random.default_rng(self.seed).standard_normal((int(free.sum()), self.block)).T
+            self.modes.vector[:] = X.ravel()
+            self._started = True
+        lam, info = dev.eigs(self.n_modes, self.rho.vec, self.modes.vec, block=self.block, density=self.density,
+                             mass_law=self.mass_law, rtol=self.rtol, max_outer=self.max_outer, pcg_rtol=self.pcg_rtol,
+                             pc=self.preconditioner)
+        self.modes.version += 1
+        self.last_info = dict(info, eigenvalues=lam.copy(), n_modes=self.n_modes, block=self.block)
+        LAST_KSP_INFO.append(dict(self.last_info, kind="elasticity_eigs"))
+        if info["converged"] != 1:
+            raise RuntimeError(f"elasticity eigen solve did not converge: {info['outer_iterations']} outer steps, residuals "
+                               f"{info['residual'][:self.n_modes]} above {self.rtol:.1e}")
+        self._lam, self._key = lam, key
+        return lam[:self.n_modes].copy()
+
+
+class EigenvalueAggregate(BackendForm):
+    """J = ((1/n) sum_{k<n} lambda_k^-p)^(-1/p), p >= 1, over the ``n_modes`` lowest eigenvalues of an
+    `ElasticityEigenvalues`: a smooth stand-in for lambda_1 (lambda_1 <= J <= n^(1/p) lambda_1, so J >= c bounds lambda_1
+    from below by c n^(-1/p)) that is symmetric in the eigenvalues, so it is differentiable where the modes of a cluster swap -- provided
+    the cluster lies inside: ``n_modes`` should not split a group of (nearly) equal eigenvalues, since the derivative of a
+    single eigenvalue inside a cluster does not exist.  A rank-0 output of the density alone: no state, no adjoint solve.
+    dJ/drho is one launch, sum_k c_k dlambda_k/drho with c_k = (1/n) lambda_k^(-p-1) J^(p+1)."""
+    rank = 0
+
+    def __init__(self, eigen: ElasticityEigenvalues, p: float = 8.0):
+        if not isinstance(eigen, ElasticityEigenvalues):
+            raise NotImplementedError("EigenvalueAggregate needs an ElasticityEigenvalues")
+        if not p >= 1.0:
+            raise ValueError("EigenvalueAggregate needs p >= 1")
+        self.eigen, self.rho, self.mesh, self.p = eigen, eigen.rho, eigen.mesh, float(p)
+        self._grad = None
+
+    def functions(self):
+        return (self.rho,)
+
+    def _value(self):
+        lam = self.eigen.eigenvalues()
+        lo = lam.min()
+        J = lo * np.mean((lam / lo) ** -self.p) ** (-1.0 / self.p)
+        return J, lam
+
+    def assemble_scalar(self) -> float:
+        return float(self._value()[0])
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:
+            if self._grad is None:
+                self._grad = Vec(_ctx(), self.mesh.n_cell)
+            out = self._grad
+        if wrt is not self.rho:
+            return out.fill(0.0)
+        J, lam = self._value()
+        c = (lam / J) ** (-self.p - 1.0) / lam.size
+        g = self.eigen
+        return g.device().eig_drho(g.method_id, g.n_modes, self.rho.vec, g.modes.vec, lam, c, out, density=g.density,
+                                   mass_law=g.mass_law)
+
+
 def averageFunc(func: Function) -> LinearFunctional:
     """(1/|Omega|) int func dx for a DG0 Function (averageFunc, run_topo_opt_cantilever_beam.py:103-106)."""
     V = func.function_space
@@ -1110,3 +1322,13 @@ def von_Mises_stress_multiload(u, rho_e=None, E: float = 1.0, nu: float = 0.3, q
                                load_case: Optional[int] = None) -> MultiLoadVonMises:
     """The envelope of the (relaxed) von Mises stress over the load cases, or the field of one load case, as a field output."""
     return MultiLoadVonMises(u, rho_e, E=E, nu=nu, q=q, scales=scales, load_case=load_case)
+
+
+def eigenvalue_aggregate(rho_e, V, bcs, n_modes: int = 3, p: float = 8.0, block: Optional[int] = None, E: float = 1.0,
+                         nu: float = 0.3, method: str = "SIMP", density: float = 1.0, mass_law: str = "linear",
+                         preconditioner: str = "jacobi", rtol: float = 1e-9, seed: int = 0) -> EigenvalueAggregate:
+    """The smooth lower bound of the fundamental eigenvalue as a scalar output of the density:
+    ``fea.add_output(name, 'scalar', eigenvalue_aggregate(rho_e, V, bcs, n_modes=3), ['density'])``."""
+    return EigenvalueAggregate(ElasticityEigenvalues(rho_e, V, bcs, n_modes, block=block, E=E, nu=nu, method=method,
+                                                     density=density, mass_law=mass_law, preconditioner=preconditioner,
+                                                     rtol=rtol, seed=seed), p=p)

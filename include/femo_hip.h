@@ -694,6 +694,53 @@ int femo_elast_von_mises_multi(femo_elast* e, int n_cols, const femo_vec* rho, c
  * atomics: the same bits every call, and column l does not depend on n_cols.                                             */
 int femo_elast_body_apply(femo_elast* e, int n_cols, const double* b /* [n_cols * 3] */, int transpose, double a,
                           const femo_vec* x, const femo_vec* base /* or NULL */, int zero_fixed, femo_vec* y, int accumulate);
+/* Lowest eigenfrequencies (csrc/elast_eig.hip): K(rho) phi = lambda M(rho) phi on the free dofs, with the consistent P1 mass
+ *   M(rho) = density sum_e m(rho_e) M0_e,   M0_e[(a,i),(b,j)] = delta_ij |T_e| (1 + delta_ab) / ((d+1)(d+2)),
+ *   m = rho (FEMO_ELAST_MASS_LINEAR) or rho for rho >= 0.1 and 6e5 rho^6 - 5e6 rho^7 below (FEMO_ELAST_MASS_DU_OLHOFF, C^1 at
+ *   0.1: the usual cure for spurious localised modes in low-density regions).
+ * Columns as above (column l at l * n_dof, 1 <= n_cols <= FEMO_ELAST_MAX_COLS).  No float atomics anywhere: the same bits
+ * every call; a column of the mass product and an entry of a Gram matrix do not depend on how many columns go with them. */
+enum { FEMO_ELAST_MASS_LINEAR = 0, FEMO_ELAST_MASS_DU_OLHOFF = 1 };
+/* y_l = a M(rho) x_l, matrix free (vertex walk).  masked = 1: M_ff -- fixed entries of x read as 0, y exactly 0 on the fixed
+ * dofs (needs femo_elast_set_fixed).                                                                                      */
+int femo_elast_mass_apply_multi(femo_elast* e, int mass_law, double density, int masked, int n_cols, double a,
+                                const femo_vec* rho, const femo_vec* x, femo_vec* y);
+/* G[i * n_b + j] = a_i . b_j over n_dof entries for all n_a x n_b pairs in one pass, folded on the device in a fixed order
+ * (the call waits for it).                                                                                                */
+int femo_elast_block_gram(femo_elast* e, int n_a, const femo_vec* a, int n_b, const femo_vec* b, double* G /* [n_a * n_b] */);
+/* y_j = sum_i x_i Q[i * n_cols + j], summed in ascending i; y may be x.                                                 */
+int femo_elast_block_rotate(femo_elast* e, int n_cols, const double* Q /* [n_cols * n_cols] */, const femo_vec* x, femo_vec* y);
+/* y[n_cell] (+)= sum_k c_k [ C'(rho_e) phi_k,e^T K0_e phi_k,e - lambda_k density m'(rho_e) phi_k,e^T M0_e phi_k,e ]: with
+ * M-orthonormal modes the bracket is d lambda_k / d rho_e.  One launch for all n_modes columns of phi, ascending k.       */
+int femo_elast_eig_drho(femo_elast* e, int method, int mass_law, double density, int n_modes, const femo_vec* rho,
+                        const femo_vec* phi, const double* lambda /* [n_modes] */, const double* c /* [n_modes] */, femo_vec* y,
+                        int accumulate);
+typedef struct femo_eig_opts {
+  double rtol;          /* every mode k < n_modes: |K phi_k - lambda_k M phi_k|_2 <= rtol lambda_k |M phi_k|_2               */
+  double pcg_rtol;      /* the inner solves, relative to their first residual as in femo_elast_solve                         */
+  int32_t max_outer;    /* 0 = 200                                                                                           */
+  int32_t pcg_max_it;   /* 0 = the default of femo_elast_solve                                                               */
+  int32_t pc;           /* FEMO_ELAST_PC_JACOBI | FEMO_ELAST_PC_MULTILEVEL                                                   */
+  int32_t reserved;
+} femo_eig_opts;
+typedef struct femo_eig_info {
+  int32_t outer_iterations;
+  int32_t pcg_iterations;                  /* iterations of the batched loop, summed over the outer steps                    */
+  int32_t converged;                       /* 1: every tested mode met rtol                                                  */
+  int32_t reserved;
+  double residual[FEMO_ELAST_MAX_COLS];    /* |K phi_k - lambda_k M phi_k| / (lambda_k |M phi_k|), guard columns included     */
+  double solve_ms;                         /* device time of the inner solves                                                */
+} femo_eig_info;
+/* The n_modes lowest eigenpairs by block inverse iteration with Rayleigh-Ritz on the assembled K of the handle and its fixed
+ * set (an error without one: K is singular on a free-free structure; a shift is out of scope).  X: block columns, the start
+ * block on entry (any block of full rank; fixed entries are ignored), the modes on return -- ascending lambda, X^T M X = I,
+ * exact zeros on the fixed dofs, the entry of largest magnitude of each column positive.  The block - n_modes last columns
+ * are guard vectors: they speed up the others and are not tested.  An outer step is B = M_ff X, one batched PCG K Y = B
+ * from the previous block, the two Gram matrices Y^T M Y and Y^T K Y, their block x block eigenproblem on the host (Cholesky
+ * and cyclic Jacobi) and X = Y Q.  lambda[block].  An inner solve that does not converge is an error; an outer iteration
+ * that runs out of steps returns with info->converged = 0.                                                                 */
+int femo_elast_eigs(femo_elast* e, int mass_law, double density, const femo_vec* rho, int n_modes, int block, femo_vec* X,
+                    const femo_eig_opts* opts, double* lambda, femo_eig_info* info);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
  *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
  * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices
