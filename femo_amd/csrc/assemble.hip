@@ -1584,6 +1584,7 @@ int femo_launch_residual(femo_mesh* m, int pde, const double* params, const doub
     if (nbr <= (m->tdim == 3 ? 16 : 8))
       return femo_launch_system(m, pde, params, u, f, aux, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, r, f_uid, f_gen, nullptr);
     FEMO_TRY(ensure_load_vector(m, f, f_uid, f_gen));
+    FEMO_TRY(ensure_visit_weights(m));               // the walk reads the visit records: this may be the mesh's first pass
     FEMO_ROW_WALK(m, 0, nb, st, u, (const double*)m->d_load, r);
   }
   FEMO_HIP_CHECK(hipGetLastError());
@@ -1628,7 +1629,14 @@ int femo_launch_system(femo_mesh* m, int pde, const double* params, const double
   int cap = 16;
   while (cap < m->max_rowlen) cap *= 2;
   const size_t lds = (size_t)cap * FEMO_BLOCK * sizeof(double);
-  FEMO_REQUIRE(lds <= 160 * 1024, "row length %d exceeds the LDS strip capacity", m->max_rowlen);
+  // Two capacities, both checked here, before anything is launched.  The linear Poisson form keeps a row's neighbourhood
+  // in LDS, one wave per workgroup (k_poisson_system_lds): 128 KiB hold 64 entries in 3-D and 84 in 2-D.  Every other
+  // form -- and linear Poisson beyond that -- accumulates in k_jacobian's strip of cap entries for each of FEMO_BLOCK
+  // threads: cap = 64 is 128 KiB, cap = 128 would be 256 KiB, more than the 160 KiB of a CU.
+  const int nbr = (m->max_rowlen + 1) & ~1;
+  const size_t lds_row = (size_t)nbr * (m->tdim + 1) * 64 * sizeof(double);
+  const bool row_in_lds = pde == FEMO_PDE_POISSON && lds_row <= 128 * 1024;
+  FEMO_REQUIRE(row_in_lds || lds <= 160 * 1024, "row length %d exceeds the LDS strip capacity", m->max_rowlen);
   const double beta = params ? params[0] : 0.0;
   const double sgn = (params && params[1] != 0.0) ? params[1] : 1.0;
   if (pde == FEMO_PDE_EB_BEAM) {
@@ -1674,9 +1682,7 @@ int femo_launch_system(femo_mesh* m, int pde, const double* params, const double
     return 0;
   };
   // rows with up to 64 neighbours: the row neighbourhood fits in LDS (one wave per workgroup)
-  const int nbr = (m->max_rowlen + 1) & ~1;
-  const size_t lds_row = (size_t)nbr * (m->tdim + 1) * 64 * sizeof(double);
-  if (lds_row <= 128 * 1024) {
+  if (row_in_lds) {
     FEMO_TRY(ensure_visit_weights(m));
     const int64_t ns = m->n_slices;
     const P1Rec12* rec = reinterpret_cast<const P1Rec12*>(m->d_visit_rec);

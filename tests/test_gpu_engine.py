@@ -138,7 +138,8 @@ def test_cg_parity(ctx, d, n, jit):
 def test_spmv_column_encodings(ctx):
     """The three column encodings of the SELL SpMV on one mesh: per-slice deltas (structured numbering, boundary rows
     completed with structural zeros), 16-bit deltas (Morton numbering: every column within +-32767 of its row), 32-bit
-    indices (random numbering) -- same product, and the Jacobian stays bitwise symmetric in each."""
+    indices (random numbering) -- same product, and the Jacobian stays bitwise symmetric in each.
+    Rows of more than 14 entries in each of the three encodings: tests/test_gpu_wide_rows.py."""
     from femo_amd import engine as E
     from femo_amd.fea.mesh import createUnitCubeMesh
     base = createUnitCubeMesh(44, 0.2)
