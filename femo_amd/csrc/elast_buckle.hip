@@ -1,0 +1,523 @@
+// SIMP topology optimisation: linearised buckling load factors of the linear elasticity, (K + lambda K_G(u, rho)) phi = 0 on
+// the free dofs (C-ABI in include/femo_hip.h: femo_elast_geom_stress, femo_elast_geom_stress_get,
+// femo_elast_geom_apply_multi, femo_elast_buckle_du, femo_elast_buckle_drho, femo_elast_buckle).
+//
+//   sigma_e = C(rho_e) sigma_0(u_e),   sigma_0 = lam0 tr(eps) I + 2 mu0 eps (the d x d in-plane block)
+//   K_G,e[(a,i),(b,j)] = delta_ij |T_e| g_a . sigma_e g_b,   g_a the barycentric gradients
+//
+// Layout as in elast_solve.hip: column l at l * n_dof.  K_G is never stored: the product walks the cells around a vertex row
+// like k_elast_mass, and reads the cell stress from a buffer of the handle that femo_elast_geom_stress fills once per
+// solve, so the product touches neither u nor rho.  No float atomics: one writer per dof and per cell; the cells around a
+// vertex, the columns and the modes are summed in a fixed order, so every call gives the same bits, and a column of the
+// product does not depend on how many columns travel with it.
+//
+// femo_elast_buckle is femo_elast_eigs with the roles changed: the pencil is (-K_G) phi = mu K phi, mu = 1 / lambda, K
+// positive definite and -K_G indefinite, for the largest positive mu.  An outer step issues
+//
+//   B = (-K_G)_ff X                          k_elast_geom            one launch for the block
+//   K Y = B, first guess 0                   the batched PCG of elast_solve.hip (Y overwrites X); the stopping level is
+//                                            relative to |B|
+//   KY = A Y, GY = (-K_G)_ff Y               k_elast_spmv_multi, k_elast_geom
+//   G_K = Y^T KY, G_G = Y^T GY               k_block_gram twice, one fold, one copy to the pinned mirror
+//   host: Cholesky of G_K, cyclic Jacobi on C^-1 G_G C^-T  ->  mu, taken in descending order, Q = C^-T V
+//   X = Y Q, KX = KY Q, R = GY Q - KX diag(mu)   k_block_rotate three times (X in place)
+//   |R_k|^2, |KX_k|^2                        k_block_gram twice, one fold, one copy
+//
+// and stops when |R_k| <= rtol mu_k |KX_k| and mu_k > 0 for every k < n_modes.  The block converges to the modes of largest
+// |mu| of either sign (negative mu: buckling under the reversed load): when one of the n_modes largest Ritz values is still
+// not positive at the last outer step, the block is too small for this load and the call fails.
+#include "elast_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace elast_block;
+
+namespace {
+
+constexpr int EMC = FEMO_ELAST_MAX_COLS;
+
+struct ModeWeights { double w1[EMC], w2[EMC]; };
+
+// component of the symmetric d x d tensor at (i, k): the diagonal first, then 01[, 02, 12]
+template <int D>
+__device__ __forceinline__ constexpr int sym_at(int i, int k) {
+  return i == k ? i : (D == 2 ? 2 : (i + k + 2));
+}
+
+// Gu[i][k] = d x_i / d x_k of the P1 field x in a cell
+template <int D>
+__device__ __forceinline__ void cell_gradient(const double (&g)[D + 1][D], const int32_t (&v)[D + 1],
+                                              const double* __restrict__ x, double (&Gu)[D][D]) {
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) Gu[i][k] = 0.0;
+#pragma unroll
+  for (int b = 0; b <= D; ++b)
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const double xb = x[(int64_t)v[b] * D + i];
+#pragma unroll
+      for (int k = 0; k < D; ++k) Gu[i][k] += xb * g[b][k];
+    }
+}
+
+// sigma_0 = lam tr(eps) I + 2 mu eps of the gradient Gu
+template <int D>
+__device__ __forceinline__ void solid_stress(const double (&Gu)[D][D], double lam, double mu, double (&s)[D][D]) {
+  double tr = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) tr += Gu[i][i];
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) s[i][k] = mu * (Gu[i][k] + Gu[k][i]) + (i == k ? lam * tr : 0.0);
+}
+
+// H (+)= w (grad phi)^T (grad phi): H[k][l] += w sum_i d_k phi_i d_l phi_i
+template <int D>
+__device__ __forceinline__ void add_gram(const double (&G)[D][D], double w, double (&H)[D][D]) {
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+#pragma unroll
+    for (int l = 0; l < D; ++l) {
+      double s = 0.0;
+#pragma unroll
+      for (int i = 0; i < D; ++i) s += G[i][k] * G[i][l];
+      H[k][l] += w * s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------- cell stress ----
+// One thread per cell: the d (d+1) / 2 components of C(rho_c) sigma_0(u_c), component-major.
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_cell_stress(int64_t n_cell, const int32_t* __restrict__ conn,
+                                                          const double* __restrict__ xv, const double* __restrict__ rho,
+                                                          int method, double lam, double mu, const double* __restrict__ u,
+                                                          double* __restrict__ sig) {
+  const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (c >= n_cell) return;
+  int32_t v[D + 1];
+  double p[D + 1][D], g[D + 1][D], vol, Gu[D][D], s[D][D];
+  load_cell<D>(conn, xv, c, v, p);
+  simplex_grads<D>(p, g, vol);
+  cell_gradient<D>(g, v, u, Gu);
+  solid_stress<D>(Gu, lam, mu, s);
+  const double C = penal(method, rho[c]);
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = i; k < D; ++k) sig[(int64_t)sym_at<D>(i, k) * n_cell + c] = C * s[i][k];
+}
+
+// ------------------------------------------------------------------------------------- geometric stiffness ----
+// One thread per vertex row, the visit walk of k_elast_mass.  A visit of cell c as its vertex a adds, per column and
+// component i, |T_c| sum_k (sigma_c g_a)_k d_k x_i = sum_b w_b x_i[v_b] with w_b = |T_c| (sigma_c g_a) . g_b; y = a * that.
+// MASKED: fixed entries of x read as 0 and fixed entries of y are 0.  The geometry, the stress, the weights and the fixed
+// bytes of a visit (one bit per dof of the cell) serve all columns.
+template <int D, bool MASKED>
+__global__ __launch_bounds__(EB) void k_elast_geom(
+    int64_t n_rows, int64_t n_cell, const int64_t* __restrict__ vptr, const int32_t* __restrict__ visit_cell,
+    const int32_t* __restrict__ conn, const double* __restrict__ xv, const double* __restrict__ sig,
+    const uint8_t* __restrict__ fixed, int n_cols, double a, const double* __restrict__ x, double* __restrict__ y) {
+  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (row >= n_rows) return;
+  const int64_t slice = row >> 6;
+  const int lane = (int)(row & 63);
+  const int64_t vb = vptr[slice];
+  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
+  const int64_t n_dof = n_rows * D;
+  double acc[EMC][D];
+#pragma unroll
+  for (int l = 0; l < EMC; ++l)
+#pragma unroll
+    for (int i = 0; i < D; ++i) acc[l][i] = 0.0;
+  for (int s = 0; s < nvis; ++s) {
+    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
+    if (ca < 0) continue;
+    const int64_t c = ca >> 2;
+    const int va = ca & 3;
+    int32_t v[D + 1];
+    double w[D + 1];
+    {
+      double p[D + 1][D], g[D + 1][D], vol, t[D];
+      load_cell<D>(conn, xv, c, v, p);
+      simplex_grads<D>(p, g, vol);
+      double ga[D];
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        ga[k] = 0.0;
+#pragma unroll
+        for (int b = 0; b <= D; ++b) ga[k] = b == va ? g[b][k] : ga[k];
+      }
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        double tk = 0.0;
+#pragma unroll
+        for (int m = 0; m < D; ++m) tk += sig[(int64_t)sym_at<D>(k < m ? k : m, k < m ? m : k) * n_cell + c] * ga[m];
+        t[k] = vol * tk;
+      }
+#pragma unroll
+      for (int b = 0; b <= D; ++b) {
+        double wb = 0.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) wb += t[k] * g[b][k];
+        w[b] = wb;
+      }
+    }
+    unsigned fx = 0u;                                                 // bit b * D + i: dof (v_b, i) is fixed
+    if (MASKED) {
+#pragma unroll
+      for (int b = 0; b <= D; ++b)
+#pragma unroll
+        for (int i = 0; i < D; ++i) fx |= fixed[(int64_t)v[b] * D + i] ? 1u << (b * D + i) : 0u;
+    }
+#pragma unroll
+    for (int l = 0; l < EMC; ++l) {
+      if (l >= n_cols) break;
+      const double* __restrict__ xl = x + (int64_t)l * n_dof;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        double sx = 0.0;
+#pragma unroll
+        for (int b = 0; b <= D; ++b) {
+          const double t = xl[(int64_t)v[b] * D + i];                 // loaded whatever the mask says: a select, no branch
+          sx += w[b] * ((fx >> (b * D + i)) & 1u ? 0.0 : t);
+        }
+        acc[l][i] += sx;
+      }
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < EMC; ++l) {
+    if (l >= n_cols) break;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const bool f = MASKED && fixed[row * D + i];
+      y[(int64_t)l * n_dof + row * D + i] = f ? 0.0 : a * acc[l][i];
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------- d lambda / d u ----
+// One thread per vertex row, the same walk: out[(v,j)] = sum_{c around v} C(rho_c) |T_c| (Sigma_H g_a)_j with
+// Sigma_H = lam0 tr(H) I + 2 mu0 H and H = sum_k w_k (grad phi_k)^T (grad phi_k), the modes in ascending order.
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_buckle_du(
+    int64_t n_rows, const int64_t* __restrict__ vptr, const int32_t* __restrict__ visit_cell, const int32_t* __restrict__ conn,
+    const double* __restrict__ xv, const double* __restrict__ rho, int method, double lam, double mu, int n_modes,
+    ModeWeights mw, const double* __restrict__ phi, double* __restrict__ out) {
+  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (row >= n_rows) return;
+  const int64_t slice = row >> 6;
+  const int lane = (int)(row & 63);
+  const int64_t vb = vptr[slice];
+  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
+  const int64_t n_dof = n_rows * D;
+  double acc[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) acc[j] = 0.0;
+  for (int s = 0; s < nvis; ++s) {
+    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
+    if (ca < 0) continue;
+    const int64_t c = ca >> 2;
+    const int va = ca & 3;
+    int32_t v[D + 1];
+    double p[D + 1][D], g[D + 1][D], vol, H[D][D];
+    load_cell<D>(conn, xv, c, v, p);
+    simplex_grads<D>(p, g, vol);
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+#pragma unroll
+      for (int l = 0; l < D; ++l) H[k][l] = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < n_modes; ++k) {
+      double G[D][D];
+      cell_gradient<D>(g, v, phi + (int64_t)k * n_dof, G);
+      add_gram<D>(G, mw.w1[k], H);
+    }
+    double tr = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) tr += H[k][k];
+    const double cw = penal(method, rho[c]) * vol;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      double t = 0.0;
+#pragma unroll
+      for (int m = 0; m < D; ++m) {
+        double gam = 0.0;
+#pragma unroll
+        for (int b = 0; b <= D; ++b) gam = b == va ? g[b][m] : gam;
+        t += (2.0 * mu * H[j][m] + (j == m ? lam * tr : 0.0)) * gam;
+      }
+      acc[j] += cw * t;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < D; ++j) out[row * D + j] = acc[j];
+}
+
+// ------------------------------------------------------------------------------------- d lambda / d rho ----
+// One thread per cell, the modes in ascending order:
+//   y_c (+)= C'(rho_c) |T_c| sum_k [ w1_k (lam0 (div phi_k)^2 + 2 mu0 eps(phi_k) : eps(phi_k)) + w2_k sigma_0(u_c) : H_c(phi_k) ]
+// The first bracket is the arithmetic of k_elast_eig_drho.
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_buckle_drho(int64_t n_cell, int64_t n_dof, const int32_t* __restrict__ conn,
+                                                          const double* __restrict__ xv, const double* __restrict__ rho,
+                                                          int method, double lam, double mu, int n_modes, ModeWeights mw,
+                                                          const double* __restrict__ u, const double* __restrict__ phi,
+                                                          double* __restrict__ y, int accumulate) {
+  const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (c >= n_cell) return;
+  int32_t v[D + 1];
+  double p[D + 1][D], g[D + 1][D], vol, Gu[D][D], s0[D][D];
+  load_cell<D>(conn, xv, c, v, p);
+  simplex_grads<D>(p, g, vol);
+  cell_gradient<D>(g, v, u, Gu);
+  solid_stress<D>(Gu, lam, mu, s0);
+  const double dC = penal_d(method, rho[c]) * vol;
+  double acc = 0.0;
+#pragma unroll 1
+  for (int k = 0; k < n_modes; ++k) {
+    double G[D][D];
+    cell_gradient<D>(g, v, phi + (int64_t)k * n_dof, G);
+    double div = 0.0, ee = 0.0, sh = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) div += G[i][i];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+      for (int j = 0; j < D; ++j) { const double t = G[i][j] + G[j][i]; ee += 0.25 * t * t; }
+#pragma unroll
+    for (int m = 0; m < D; ++m)
+#pragma unroll
+      for (int l = 0; l < D; ++l) {
+        double h = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) h += G[i][m] * G[i][l];
+        sh += s0[m][l] * h;
+      }
+    acc += mw.w1[k] * (dC * (lam * div * div + 2.0 * mu * ee)) + mw.w2[k] * (dC * sh);
+  }
+  y[c] = accumulate ? y[c] + acc : acc;
+}
+
+// ----------------------------------------------------------------------------------------------- launches ----
+int stress_launch(femo_elast* e, int method, const double* rho, const double* u) {
+  femo_mesh* m = e->mesh;
+  if (!e->w_gstress) FEMO_TRY(dalloc(&e->w_gstress, (int64_t)(e->d * (e->d + 1) / 2) * m->n_cell));
+  hipStream_t st = m->ctx->stream;
+  if (e->d == 2)
+    hipLaunchKernelGGL(k_elast_cell_stress<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho, method,
+                       e->lam0, e->mu0, u, e->w_gstress);
+  else
+    hipLaunchKernelGGL(k_elast_cell_stress<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho, method,
+                       e->lam0, e->mu0, u, e->w_gstress);
+  FEMO_HIP_CHECK(hipGetLastError());
+  e->has_gstress = true;
+  return 0;
+}
+
+int geom_launch(femo_elast* e, bool masked, int n_cols, double a, const double* x, double* y) {
+  femo_mesh* m = e->mesh;
+  hipStream_t st = m->ctx->stream;
+#define FEMO_GEOM(D, MK) hipLaunchKernelGGL((k_elast_geom<D, MK>), dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->n_cell, \
+                                            m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, e->w_gstress, e->d_fixed, n_cols, a, x, y)
+  if (e->d == 2) { if (masked) FEMO_GEOM(2, true); else FEMO_GEOM(2, false); }
+  else { if (masked) FEMO_GEOM(3, true); else FEMO_GEOM(3, false); }
+#undef FEMO_GEOM
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+// ===================================================================================================== C-ABI ====
+extern "C" {
+
+int femo_elast_geom_stress(femo_elast* e, int method, const femo_vec* rho, const femo_vec* u) {
+  FEMO_REQUIRE(e && rho && u, "null argument");
+  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
+  femo_mesh* m = e->mesh;
+  FEMO_REQUIRE(rho->n >= m->n_cell && u->n >= m->n_vert * e->d, "vector size mismatch in femo_elast_geom_stress: need %lld cells and %lld dofs",
+               (long long)m->n_cell, (long long)(m->n_vert * e->d));
+  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u));
+  return stress_launch(e, method, rho->d, u->d);
+}
+
+int femo_elast_geom_stress_get(femo_elast* e, femo_vec* out) {
+  FEMO_REQUIRE(e && out, "null argument");
+  FEMO_REQUIRE(e->has_gstress, "femo_elast_geom_stress_get: no cell stress -- call femo_elast_geom_stress first");
+  const int64_t n = (int64_t)(e->d * (e->d + 1) / 2) * e->mesh->n_cell;
+  FEMO_REQUIRE(out->n >= n, "vector size mismatch in femo_elast_geom_stress_get: need %lld entries", (long long)n);
+  femo_vec_touch(out);
+  FEMO_HIP_CHECK(hipMemcpyAsync(out->d, e->w_gstress, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, e->mesh->ctx->stream));
+  return 0;
+}
+
+int femo_elast_geom_apply_multi(femo_elast* e, int masked, int n_cols, double a, const femo_vec* x, femo_vec* y) {
+  FEMO_REQUIRE(e && x && y, "null argument");
+  FEMO_REQUIRE(n_cols >= 1 && n_cols <= EMC, "femo_elast_geom_apply_multi: %d columns (1 to %d)", n_cols, EMC);
+  const int64_t nl = e->mesh->n_vert * e->d * n_cols;
+  FEMO_REQUIRE(x->n >= nl && y->n >= nl, "vector size mismatch in femo_elast_geom_apply_multi: %d columns need %lld entries", n_cols,
+               (long long)nl);
+  FEMO_REQUIRE(e->has_gstress, "femo_elast_geom_apply_multi: no cell stress -- call femo_elast_geom_stress first");
+  FEMO_REQUIRE(!masked || e->has_fixed, "femo_elast_geom_apply_multi: masked product without a fixed set");
+  FEMO_REQUIRE(y != x, "femo_elast_geom_apply_multi: output aliases an input");
+  FEMO_TRY(femo_vec_await(x));
+  femo_vec_touch(y);
+  return geom_launch(e, masked != 0, n_cols, a, x->d, y->d);
+}
+
+int femo_elast_buckle_du(femo_elast* e, int method, int n_modes, const femo_vec* rho, const femo_vec* phi, const double* w,
+                         femo_vec* out) {
+  FEMO_REQUIRE(e && rho && phi && w && out, "null argument");
+  FEMO_REQUIRE(n_modes >= 1 && n_modes <= EMC, "femo_elast_buckle_du: %d columns (1 to %d)", n_modes, EMC);
+  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
+  femo_mesh* m = e->mesh;
+  const int64_t n = m->n_vert * e->d;
+  FEMO_REQUIRE(rho->n >= m->n_cell && out->n >= n && phi->n >= n * n_modes,
+               "vector size mismatch in femo_elast_buckle_du: %d columns need %lld entries", n_modes, (long long)(n * n_modes));
+  FEMO_REQUIRE(out != rho && out != phi, "femo_elast_buckle_du: output aliases an input");
+  ModeWeights mw;
+  for (int k = 0; k < EMC; ++k) { mw.w1[k] = k < n_modes ? w[k] : 0.0; mw.w2[k] = 0.0; }
+  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(phi));
+  femo_vec_touch(out);
+  hipStream_t st = m->ctx->stream;
+  if (e->d == 2)
+    hipLaunchKernelGGL(k_elast_buckle_du<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn,
+                       m->d_x, rho->d, method, e->lam0, e->mu0, n_modes, mw, phi->d, out->d);
+  else
+    hipLaunchKernelGGL(k_elast_buckle_du<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn,
+                       m->d_x, rho->d, method, e->lam0, e->mu0, n_modes, mw, phi->d, out->d);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_elast_buckle_drho(femo_elast* e, int method, int n_modes, const femo_vec* rho, const femo_vec* u, const femo_vec* phi,
+                           const double* w1, const double* w2, femo_vec* y, int accumulate) {
+  FEMO_REQUIRE(e && rho && u && phi && w1 && w2 && y, "null argument");
+  FEMO_REQUIRE(n_modes >= 1 && n_modes <= EMC, "femo_elast_buckle_drho: %d columns (1 to %d)", n_modes, EMC);
+  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
+  femo_mesh* m = e->mesh;
+  const int64_t n = m->n_vert * e->d;
+  FEMO_REQUIRE(rho->n >= m->n_cell && y->n >= m->n_cell && u->n >= n && phi->n >= n * n_modes,
+               "vector size mismatch in femo_elast_buckle_drho: %d columns need %lld entries", n_modes, (long long)(n * n_modes));
+  FEMO_REQUIRE(y != rho && y != u && y != phi, "femo_elast_buckle_drho: output aliases an input");
+  ModeWeights mw;
+  for (int k = 0; k < EMC; ++k) { mw.w1[k] = k < n_modes ? w1[k] : 0.0; mw.w2[k] = k < n_modes ? w2[k] : 0.0; }
+  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(phi));
+  femo_vec_touch(y);
+  hipStream_t st = m->ctx->stream;
+  if (e->d == 2)
+    hipLaunchKernelGGL(k_elast_buckle_drho<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, n, m->d_conn, m->d_x, rho->d, method,
+                       e->lam0, e->mu0, n_modes, mw, u->d, phi->d, y->d, accumulate);
+  else
+    hipLaunchKernelGGL(k_elast_buckle_drho<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, n, m->d_conn, m->d_x, rho->d, method,
+                       e->lam0, e->mu0, n_modes, mw, u->d, phi->d, y->d, accumulate);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_elast_buckle(femo_elast* e, int method, const femo_vec* rho, const femo_vec* u, int n_modes, int block, femo_vec* X,
+                      const femo_eig_opts* opts, double* lambda, femo_eig_info* info) {
+  FEMO_REQUIRE(e && rho && u && X && opts && lambda, "null argument");
+  FEMO_REQUIRE(block >= 1 && block <= EMC, "femo_elast_buckle: %d columns (1 to %d)", block, EMC);
+  FEMO_REQUIRE(n_modes >= 1 && n_modes <= block, "femo_elast_buckle: %d modes in a block of %d (1 <= n_modes <= block)", n_modes, block);
+  FEMO_REQUIRE(method == FEMO_ELAST_SIMP || method == FEMO_ELAST_RAMP, "unknown penalisation method %d", method);
+  FEMO_REQUIRE(e->assembled, "femo_elast_buckle: assemble K first");
+  FEMO_REQUIRE(e->has_fixed, "femo_elast_buckle: no fixed set -- K is singular on a free-free structure");
+  FEMO_REQUIRE(opts->rtol > 0.0 && opts->pcg_rtol > 0.0, "femo_elast_buckle: need rtol > 0 and pcg_rtol > 0");
+  femo_mesh* m = e->mesh;
+  femo_ctx* ctx = m->ctx;
+  const int64_t n = m->n_vert * e->d, nl = n * block;
+  FEMO_REQUIRE(rho->n >= m->n_cell && u->n >= n && X->n >= nl, "vector size mismatch in femo_elast_buckle: %d columns need %lld entries",
+               block, (long long)nl);
+  FEMO_REQUIRE(X != rho && X != u, "femo_elast_buckle: the block aliases the density or the state");
+  FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(X));
+  femo_vec_touch(X);
+  FEMO_TRY(femo_elast_work_reserve(e, block, "femo_elast_buckle"));
+  FEMO_TRY(gram_reserve(e));
+  if (e->w_eig_cols < block) {
+    double* b = nullptr;
+    FEMO_TRY(dalloc(&b, nl));
+    FEMO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    hipFree(e->w_eig);
+    e->w_eig = b;
+    e->w_eig_cols = block;
+  }
+  FEMO_TRY(stress_launch(e, method, rho->d, u->d));
+  femo_solver_opts so;
+  std::memset(&so, 0, sizeof(so));
+  so.rtol = opts->pcg_rtol;
+  so.max_it = opts->pcg_max_it;
+  so.zero_guess = 1;                                                  // the stopping level is relative to |B|
+  so.pc = opts->pc;
+  const int max_outer = opts->max_outer > 0 ? opts->max_outer : 400;
+  femo_vec Bv = wrap(ctx, e->w_eig, nl);
+  femo_solve_info si[EMC];
+  femo_eig_info out;
+  std::memset(&out, 0, sizeof(out));
+  double mu[EMC] = {};
+  const int L = block, LL = EMC * EMC;
+  int positive = 0;                                                   // tested columns with mu > 0 at the last outer step
+  for (int outer = 1; outer <= max_outer; ++outer) {
+    FEMO_TRY(geom_launch(e, true, L, -1.0, X->d, e->w_eig));                                        // B = (-K_G)_ff X
+    FEMO_TRY(femo_elast_pcg(e, L, &Bv, X, &so, si, "femo_elast_buckle"));                            // K Y = B, Y in X
+    int its = 0;
+    for (int l = 0; l < L; ++l) {
+      FEMO_REQUIRE(si[l].converged == 1, "femo_elast_buckle: the inner PCG did not converge (outer step %d, column %d: %d iterations)",
+                   outer, l, si[l].iterations);
+      its = std::max(its, (int)si[l].iterations);
+      out.solve_ms += l == 0 ? si[l].solve_ms : 0.0;
+    }
+    out.pcg_iterations += its;
+    out.outer_iterations = outer;
+    double *GY = e->w_z, *KY = e->w_q, *KX = e->w_p, *R = e->w_r;      // the PCG work vectors are free until the next solve
+    FEMO_TRY(femo_elast_spmv(e, true, L, 1.0, X->d, 0.0, nullptr, KY, nullptr, 0, nullptr));
+    FEMO_TRY(geom_launch(e, true, L, -1.0, X->d, GY));
+    FEMO_TRY(gram_launch(e, 0, n, L, X->d, L, KY));
+    FEMO_TRY(gram_launch(e, 1, n, L, X->d, L, GY));
+    FEMO_TRY(gram_fetch(e, n, L * L, L * L));
+    double GK[EMC][EMC] = {}, GG[EMC][EMC] = {}, Qa[EMC][EMC] = {}, asc[EMC] = {};
+    for (int i = 0; i < L; ++i)
+      for (int j = 0; j < L; ++j) { GK[i][j] = e->h_gram[i * L + j]; GG[i][j] = e->h_gram[LL + i * L + j]; }
+    FEMO_REQUIRE(small_eigs(L, GK, GG, asc, Qa),
+                 "femo_elast_buckle: the block lost rank (Y^T K Y is not positive definite at outer step %d): start from another block",
+                 outer);
+    BlockMatrix Q, QT;                                                // the columns in descending mu
+    std::memset(&Q, 0, sizeof(Q)); std::memset(&QT, 0, sizeof(QT));
+    for (int j = 0; j < L; ++j) {
+      mu[j] = asc[L - 1 - j];
+      for (int i = 0; i < L; ++i) { Q.v[i][j] = Qa[i][L - 1 - j]; QT.v[i][j] = -Q.v[i][j] * mu[j]; }
+    }
+    FEMO_TRY(rotate_launch(e, n, L, Q, X->d, nullptr, nullptr, X->d));          // X = Y Q
+    FEMO_TRY(rotate_launch(e, n, L, Q, GY, &QT, KY, R));                        // R = GY Q - KY Q diag(mu)
+    FEMO_TRY(rotate_launch(e, n, L, Q, KY, nullptr, nullptr, KX));              // KX = KY Q
+    FEMO_TRY(gram_launch(e, 0, n, L, R, L, R));
+    FEMO_TRY(gram_launch(e, 1, n, L, KX, L, KX));
+    FEMO_TRY(gram_fetch(e, n, L * L, L * L));
+    bool ok = true;
+    positive = 0;
+    for (int k = 0; k < L; ++k) {
+      const double rn = std::sqrt(std::fabs(e->h_gram[k * L + k])), kn = std::sqrt(std::fabs(e->h_gram[LL + k * L + k]));
+      out.residual[k] = rn / (std::fabs(mu[k]) * kn);
+      if (k < n_modes && mu[k] > 0.0) ++positive;
+      if (k < n_modes && !(out.residual[k] <= opts->rtol && mu[k] > 0.0)) ok = false;
+    }
+    if (ok) { out.converged = 1; break; }
+  }
+  FEMO_TRY(sign_launch(e, n, L, X->d));
+  FEMO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  FEMO_REQUIRE(out.converged == 1 || positive == n_modes,
+               "femo_elast_buckle: the block is too small for this load -- no positive load factor for %d of the %d modes after %d "
+               "outer steps (the block of %d columns fills up with negative mu, buckling under the reversed load): raise block",
+               n_modes - positive, n_modes, out.outer_iterations, L);
+  for (int k = 0; k < L; ++k) lambda[k] = 1.0 / mu[k];
+  if (info) *info = out;
+  return 0;
+}
+
+}  // extern "C"

@@ -28,12 +28,13 @@
 #include <cmath>
 #include <cstring>
 
+using namespace elast_block;
+
 namespace {
 
 constexpr int EMC = FEMO_ELAST_MAX_COLS;
 constexpr int GRAM_GRID = 512;       // blocks of the Gram kernel at the most (one partial per block and pair)
 
-struct BlockMatrix { double v[EMC][EMC]; };
 struct ModeScalars { double lam[EMC], c[EMC]; };
 
 // ------------------------------------------------------------------------------------------- mass product ----
@@ -262,6 +263,11 @@ inline int gram_grid(int64_t n) { return (int)grid_of(n, GRAM_GRID); }
 // The Gram partials: two slabs of EMC * EMC slots of FEMO_MAX_PARTIALS, and the 2 * EMC * EMC folded values behind them.
 constexpr int64_t GRAM_SLAB = (int64_t)EMC * EMC * FEMO_MAX_PARTIALS;
 
+}  // namespace
+
+// ------------------------------------------------------------- shared with elast_buckle.hip (elast_internal.h) ----
+namespace elast_block {
+
 int gram_reserve(femo_elast* e) {
   if (e->w_gram) return 0;
   FEMO_TRY(dalloc(&e->w_gram, 2 * GRAM_SLAB + 2 * EMC * EMC));
@@ -386,7 +392,13 @@ femo_vec wrap(femo_ctx* ctx, double* d, int64_t n) {
   return v;
 }
 
-}  // namespace
+int sign_launch(femo_elast* e, int64_t n, int n_cols, double* x) {
+  hipLaunchKernelGGL(k_eig_sign, dim3((unsigned)n_cols), dim3(1024), 0, e->mesh->ctx->stream, n, x);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace elast_block
 
 // ===================================================================================================== C-ABI ====
 extern "C" {
@@ -546,8 +558,7 @@ int femo_elast_eigs(femo_elast* e, int mass_law, double density, const femo_vec*
     }
     if (ok) { out.converged = 1; break; }
   }
-  hipLaunchKernelGGL(k_eig_sign, dim3((unsigned)L), dim3(1024), 0, ctx->stream, n, X->d);
-  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_TRY(sign_launch(e, n, L, X->d));
   FEMO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   for (int k = 0; k < L; ++k) lambda[k] = theta[k];
   if (info) *info = out;

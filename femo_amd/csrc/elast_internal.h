@@ -1,6 +1,7 @@
 // Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product and PCG), elast_pc.hip
-// (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, and elast_eig.hip
-// (mass product, block linear algebra and the eigen solve).  Not part of the ABI.
+// (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, elast_eig.hip
+// (mass product, block linear algebra and the eigen solve) and elast_buckle.hip (geometric stiffness and the buckling
+// solve, on the block linear algebra of elast_eig.hip).  Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -40,6 +41,10 @@ struct femo_elast {
   int w_eig_cols = 0;
   double* w_gram = nullptr;
   double* h_gram = nullptr;     // pinned
+  // buckling (elast_buckle.hip), on first use: the cell stress C(rho) sigma_0(u) of femo_elast_geom_stress, component-major
+  // (d (d+1) / 2 components of n_cell entries: the diagonal first, then 01[, 02, 12])
+  double* w_gstress = nullptr;
+  bool has_gstress = false;
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
   femo_elast_pc* pc = nullptr;
   bool pc_dirty = true;
@@ -96,6 +101,29 @@ int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who);
 // records, or null.
 int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
                    const char* who);
+
+// elast_eig.hip: the block linear algebra of the eigen solves ----------------------------------------------------------
+namespace elast_block {
+struct BlockMatrix { double v[FEMO_ELAST_MAX_COLS][FEMO_ELAST_MAX_COLS]; };
+// The Gram partials and their pinned mirror h_gram, on first use.
+int gram_reserve(femo_elast* e);
+// slab s (0 or 1) <- partials of A^T B (n entries per column); folded by gram_fetch
+int gram_launch(femo_elast* e, int slab, int64_t n, int n_a, const double* A, int n_b, const double* B);
+// folds the first `sums0` pairs of slab 0 and `sums1` of slab 1 and waits for them in h_gram[0 ...] and
+// h_gram[FEMO_ELAST_MAX_COLS^2 ...]
+int gram_fetch(femo_elast* e, int64_t n, int sums0, int sums1);
+// y_j = sum_i x_i Q[i][j] (+ sum_i x2_i Q2[i][j] with Q2), ascending i; y may be x (or x2)
+int rotate_launch(femo_elast* e, int64_t n, int n_cols, const BlockMatrix& Q, const double* x, const BlockMatrix* Q2,
+                  const double* x2, double* y);
+// G_K q = theta G_M q, G_M positive definite (false when it is not): theta ascending, Q^T G_M Q = I, Q^T G_K Q = Theta
+bool small_eigs(int L, const double (&GM)[FEMO_ELAST_MAX_COLS][FEMO_ELAST_MAX_COLS],
+                const double (&GK)[FEMO_ELAST_MAX_COLS][FEMO_ELAST_MAX_COLS], double (&theta)[FEMO_ELAST_MAX_COLS],
+                double (&Q)[FEMO_ELAST_MAX_COLS][FEMO_ELAST_MAX_COLS]);
+// the entry of largest magnitude (the first of equals) of each of the n_cols columns of x becomes positive
+int sign_launch(femo_elast* e, int64_t n, int n_cols, double* x);
+// a femo_vec over memory it does not own
+femo_vec wrap(femo_ctx* ctx, double* d, int64_t n);
+}  // namespace elast_block
 
 #if defined(__HIPCC__)
 // gradients of the barycentric coordinates and the volume of a P1 simplex, from the vertices in `conn` order

@@ -487,7 +487,7 @@ int femo_elast_destroy(femo_elast* e) {
   hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
   hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_smpart);
-  hipFree(e->w_eig); hipFree(e->w_gram);
+  hipFree(e->w_eig); hipFree(e->w_gram); hipFree(e->w_gstress);
   if (e->h_gram) hipHostFree(e->h_gram);
   if (e->h_flag) hipHostFree(e->h_flag);
   if (e->h_s) hipHostFree(e->h_s);

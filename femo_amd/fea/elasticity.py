@@ -1,6 +1,7 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
-product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip).  One load case is the L = 1 case of several:
+product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip,
+buckling in csrc/elast_buckle.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
@@ -43,6 +44,15 @@ are used unchanged.
                        symmetric within a cluster, as a scalar output of the density alone: dJ/drho = sum_k c_k (C'(rho_e)
                        phi_k^T K0_e phi_k - lambda_k density m'(rho_e) phi_k^T M0_e phi_k) in one launch, no adjoint solve.
                        ``n_modes`` should not split a cluster of (nearly) equal eigenvalues
+  ElasticityBuckling   the smallest positive load factors of (K(rho) + lambda K_G(u, rho)) phi = 0 on the free dofs for the
+                       state u of an `ElasticityResidual`: K_G the geometric stiffness of the cell stress C(rho_e) sigma_0(u_e),
+                       matrix free.  Solved as (-K_G) phi = mu K phi, mu = 1 / lambda, for the largest positive mu by the block
+                       iteration of the eigenfrequencies with the roles changed (csrc/elast_buckle.hip), on the residual's
+                       own K.  Not in the reference's script
+  BucklingAggregate    J = ((1/n) sum_{k<n} lambda_k^-p)^(-1/p) of the load factors, the aggregate of `EigenvalueAggregate`, as a
+                       scalar output of (u, rho): dJ/du and dJ/drho are one launch each, and the framework's adjoint solve
+                       K w = dJ/du does the rest.  dJ/du is non-zero on clamped dofs: the exact reduced gradient needs
+                       ``fea.consistent_bc_partials = True``
 
 P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
 """
@@ -300,6 +310,74 @@ class DeviceElasticity:
                                         converged=info.converged, residual=np.array(info.residual[:block]),
                                         solve_ms=info.solve_ms, preconditioner=pc)
 
+    # ---- buckling: (K + lambda K_G(u, rho)) phi = 0 on the free dofs (csrc/elast_buckle.hip) ----
+    def geom_stress(self, method: int, rho: Vec, u: Vec, out: Optional[Vec] = None) -> Optional[Vec]:
+        """Fills the handle's cell stress C(rho_e) sigma_0(u_e), which `geom_apply_multi` reads; with ``out`` a copy of it:
+        d (d+1) / 2 components of n_cell entries, component-major (the diagonal first, then 01[, 02, 12])."""
+        check(self.lib.femo_elast_geom_stress(self.handle, int(method), rho.handle, u.handle))
+        if out is not None:
+            check(self.lib.femo_elast_geom_stress_get(self.handle, out.handle))
+        return out
+
+    def geom_apply_multi(self, n_cols: int, x: Vec, y: Vec, masked: bool = False, a: float = 1.0) -> Vec:
+        """y_l = a K_G x_l with the geometric stiffness of the last `geom_stress`, matrix free, for all ``n_cols`` columns in one
+        launch; ``masked``: (K_G)_ff (fixed entries of x read as 0, exact zeros on the fixed dofs of y)."""
+        check(self.lib.femo_elast_geom_apply_multi(self.handle, int(bool(masked)), self._cols(n_cols, x, y), float(a), x.handle,
+                                                   y.handle))
+        return y
+
+    def _mode_weights(self, who: str, n_modes: int, *weights):
+        ws = [np.ascontiguousarray(w, dtype=np.float64).ravel() for w in weights]
+        if any(w.size != n_modes for w in ws):
+            raise _lib.FemoError(f"{who}: {n_modes} modes need as many weights")
+        return ws
+
+    def buckle_du(self, method: int, n_modes: int, rho: Vec, phi: Vec, w, out: Vec) -> Vec:
+        """out[(v, j)] = sum_{e around v} C(rho_e) |T_e| (Sigma_H g_v)_j with Sigma_H = lam0 tr(H) I + 2 mu0 H and
+        H = sum_k w_k (grad phi_k)^T (grad phi_k), in one launch: with K-orthonormal modes and w_k = lambda_k^2 it is
+        d lambda_k / du."""
+        n_modes = self._cols(n_modes, phi)
+        (wv,) = self._mode_weights("buckle_du", n_modes, w)
+        check(self.lib.femo_elast_buckle_du(self.handle, int(method), n_modes, rho.handle, phi.handle,
+                                            wv.ctypes.data_as(_lib.c_f64p), out.handle))
+        return out
+
+    def buckle_drho(self, method: int, n_modes: int, rho: Vec, u: Vec, phi: Vec, w1, w2, y: Vec,
+                    accumulate: bool = False) -> Vec:
+        """y[n_cell] (+)= C'(rho_e) |T_e| sum_k [w1_k (lam0 (div phi_k)^2 + 2 mu0 eps(phi_k) : eps(phi_k)) + w2_k sigma_0(u_e) :
+        H_e(phi_k)] in one launch: with K-orthonormal modes, w1_k = lambda_k and w2_k = lambda_k^2 it is d lambda_k / d rho at
+        fixed u."""
+        n_modes = self._cols(n_modes, phi)
+        w1v, w2v = self._mode_weights("buckle_drho", n_modes, w1, w2)
+        f64 = lambda a: a.ctypes.data_as(_lib.c_f64p)
+        check(self.lib.femo_elast_buckle_drho(self.handle, int(method), n_modes, rho.handle, u.handle, phi.handle, f64(w1v),
+                                              f64(w2v), y.handle, int(bool(accumulate))))
+        return y
+
+    def buckle(self, n_modes: int, rho: Vec, u: Vec, X: Vec, block: Optional[int] = None, method: int = _lib.ELAST_SIMP,
+               rtol: float = 1e-9, max_outer: int = 400, pcg_rtol: float = 1e-12, pcg_max_it: int = 0, pc: str = "jacobi"):
+        """The ``n_modes`` smallest positive load factors of (K + lambda K_G(u, rho)) phi = 0 on the free dofs, with the
+        assembled K of the handle: the block iteration of `eigs` on (-K_G) phi = mu K phi for the largest positive
+        mu = 1 / lambda, every inner solve one batched PCG over the ``block`` columns of ``X`` from a zero first guess (the
+        start block on entry, the K-orthonormal modes in descending mu on return; the last block - n_modes columns are guard
+        vectors).  The block converges to the largest |mu| of either sign: when it fills up with negative mu (buckling under
+        the reversed load) before ``n_modes`` positive ones are found, the call fails -- raise ``block``.  Returns
+        (lambda[block] = 1 / mu, info) with info as that of `eigs`; ``residual`` is |(-K_G) x - mu K x| / (mu |K x|)."""
+        if pc not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
+        n_modes = int(n_modes)
+        block = _lib.ELAST_MAX_COLS if block is None else int(block)
+        block = self._cols(block, X)
+        opts = _lib.EigOpts(rtol=float(rtol), pcg_rtol=float(pcg_rtol), max_outer=int(max_outer), pcg_max_it=int(pcg_max_it),
+                            pc=PRECONDITIONERS[pc], reserved=0)
+        info = _lib.EigInfo()
+        lam = np.zeros(_lib.ELAST_MAX_COLS)
+        check(self.lib.femo_elast_buckle(self.handle, int(method), rho.handle, u.handle, n_modes, block, X.handle,
+                                         C.byref(opts), lam.ctypes.data_as(_lib.c_f64p), C.byref(info)))
+        return lam[:block].copy(), dict(outer_iterations=info.outer_iterations, pcg_iterations=info.pcg_iterations,
+                                        converged=info.converged, residual=np.array(info.residual[:block]),
+                                        solve_ms=info.solve_ms, preconditioner=pc)
+
     def pnorm_stress_multi(self, n_cols: int, rho: Vec, u: Vec, m, p: float, q: float, alpha: float, weights=None,
                            value: bool = True, grad_u: Optional[Vec] = None, grad_rho: Optional[Vec] = None,
                            accumulate: bool = False):
@@ -497,6 +575,31 @@ def _load_vec(mesh, facets: np.ndarray, t: np.ndarray) -> Vec:
         dev.load(t, F)
         cache[key] = F
     return F
+
+
+def _owned_stiffness(owner, mask: Optional[np.ndarray]) -> DeviceElasticity:
+    """The handle of ``owner`` (its ``device()``, ``rho``, ``method_id``, ``preconditioner``) with K(rho) of the current density
+    and the fixed set ``mask``: reassembled when the density (its version or its vector), the fixed set, the method or the
+    owner changed since the last assembly on this handle."""
+    dev = owner.device()
+    want = None if mask is None else hash(mask.tobytes())
+    if dev.fixed_key != want:
+        dev.set_fixed(mask)
+    key = (owner.rho.version, id(owner.rho.vec), dev.fixed_key, owner.method_id, id(owner))
+    if getattr(dev, "_owner", None) != key:
+        dev.assemble(owner.method_id, owner.rho.vec)
+        dev._owner = key
+    if owner.preconditioner == "multilevel" and dev.pc_plan is None:
+        dev.pc_setup()
+    return dev
+
+
+def _reciprocal_power_mean(lam: np.ndarray, p: float):
+    """J = ((1/n) sum_k lambda_k^-p)^(-1/p) of positive values and c_k = dJ/dlambda_k = (1/n) lambda_k^(-p-1) J^(p+1)."""
+    lam = np.asarray(lam, dtype=np.float64)
+    lo = lam.min()
+    J = lo * np.mean((lam / lo) ** -p) ** (-1.0 / p)
+    return J, (lam / J) ** (-p - 1.0) / lam.size
 
 
 def _fixed_data(n_dof: int, bcs):
@@ -734,17 +837,7 @@ class ElasticityResidual(BackendForm):
 
     def stiffness(self) -> DeviceElasticity:
         """The handle with K(rho) of the current density and this form's fixed set: reassembled when either changed."""
-        dev = self.device()
-        want = None if self._mask is None else hash(self._mask.tobytes())
-        if dev.fixed_key != want:
-            dev.set_fixed(self._mask)
-        key = (self.rho.version, id(self.rho.vec), dev.fixed_key, self.method_id, id(self))
-        if getattr(dev, "_owner", None) != key:
-            dev.assemble(self.method_id, self.rho.vec)
-            dev._owner = key
-        if self.preconditioner == "multilevel" and dev.pc_plan is None:
-            dev.pc_setup()
-        return dev
+        return _owned_stiffness(self, self._mask)
 
     def _record(self, infos, kind: str):
         """Keeps the record of a solve (``infos``: one per column) and raises when it did not converge; returns what
@@ -1139,7 +1232,7 @@ class ElasticityEigenvalues:
     same mesh keeps working beside it.  ``last_info`` keeps the record of the last solve; a solve that does not converge
     raises.
 
-    Out of scope: partitioned meshes, lumped non-structural masses, buckling."""
+    Out of scope: partitioned meshes, lumped non-structural masses.  Buckling load factors are `ElasticityBuckling`."""
 
     def __init__(self, rho: Function, V: VectorFunctionSpace, bcs, n_modes: int, block: Optional[int] = None, E: float = 1.0,
                  nu: float = 0.3, method: str = "SIMP", density: float = 1.0, mass_law: str = "linear",
@@ -1182,17 +1275,7 @@ class ElasticityEigenvalues:
 
     def stiffness(self) -> DeviceElasticity:
         """`ElasticityResidual.stiffness`: the handle with K(rho) of the current density and this object's fixed set."""
-        dev = self.device()
-        want = hash(self._mask.tobytes())
-        if dev.fixed_key != want:
-            dev.set_fixed(self._mask)
-        key = (self.rho.version, id(self.rho.vec), dev.fixed_key, self.method_id, id(self))
-        if getattr(dev, "_owner", None) != key:
-            dev.assemble(self.method_id, self.rho.vec)
-            dev._owner = key
-        if self.preconditioner == "multilevel" and dev.pc_plan is None:
-            dev.pc_setup()
-        return dev
+        return _owned_stiffness(self, self._mask)
 
     def eigenvalues(self) -> np.ndarray:
         """lambda_0 <= ... <= lambda_{n_modes-1} of the current density."""
@@ -1242,9 +1325,7 @@ class EigenvalueAggregate(BackendForm):
 
     def _value(self):
         lam = self.eigen.eigenvalues()
-        lo = lam.min()
-        J = lo * np.mean((lam / lo) ** -self.p) ** (-1.0 / self.p)
-        return J, lam
+        return _reciprocal_power_mean(lam, self.p)[0], lam
 
     def assemble_scalar(self) -> float:
         return float(self._value()[0])
@@ -1256,11 +1337,139 @@ class EigenvalueAggregate(BackendForm):
             out = self._grad
         if wrt is not self.rho:
             return out.fill(0.0)
-        J, lam = self._value()
-        c = (lam / J) ** (-self.p - 1.0) / lam.size
+        lam = self.eigen.eigenvalues()
+        c = _reciprocal_power_mean(lam, self.p)[1]
         g = self.eigen
         return g.device().eig_drho(g.method_id, g.n_modes, self.rho.vec, g.modes.vec, lam, c, out, density=g.density,
                                    mass_law=g.mass_law)
+
+
+class ElasticityBuckling:
+    """The ``n_modes`` smallest positive load factors lambda of (K(rho) + lambda K_G(u, rho)) phi = 0 on the free dofs, for the
+    state u of ``residual``, an `ElasticityResidual` of one load case: the load lambda F is the linearised buckling load.
+    K_G is the geometric stiffness of the cell stress sigma_e = C(rho_e) sigma_0(u_e) with the residual's own stiffness law,
+    K_G,e[(a,i),(b,j)] = delta_ij |T_e| g_a . sigma_e g_b.  Density, state, method, E, nu, preconditioner and the fixed set
+    are the residual's; K comes from ``residual.stiffness()``, so it is not assembled again and the handle stays the
+    residual's (the state must have been solved: before that the residual has no fixed set, and `load_factors` raises).
+
+    Solved by `DeviceElasticity.buckle` in a block of ``block`` columns (all FEMO_ELAST_MAX_COLS unless given: the spectra
+    of (-K_G, K) are dense, and 5 columns take 2-3 times the outer steps of 8).  ``modes`` is a Function(LoadCaseSpace(V,
+    block)): K-orthonormal, zeros on the fixed dofs, the entry of largest magnitude of each column positive.  `load_factors`
+    re-solves only when the density or the state (their versions or vectors) or the fixed set changed, from the previous
+    modes (a seeded random block the first time).  ``last_info`` keeps the record of the last solve; a solve that does not
+    converge raises.
+
+    Limitation: the block converges to the modes of largest |1 / lambda| of EITHER sign, and a negative lambda is buckling
+    under the reversed load.  A load whose negative spectrum dominates (a member in tension) fills the block with those
+    before ``n_modes`` positive factors are found; the solve then fails and says so: raise ``block``.
+
+    Out of scope: a stress interpolation of its own or a cut-off against low-density pseudo-modes (the stress carries the
+    stiffness law C), several load cases or supports that differ per case, shifted or sign-selective iterations for loads
+    whose negative spectrum dominates, partitioned meshes, inhomogeneous supports, nonlinear pre-buckling."""
+
+    def __init__(self, residual: "ElasticityResidual", n_modes: int, block: Optional[int] = None, rtol: float = 1e-9,
+                 seed: int = 0):
+        name = type(self).__name__
+        if not isinstance(residual, ElasticityResidual):
+            raise NotImplementedError(f"{name} needs the ElasticityResidual whose state carries the load")
+        if isinstance(residual, MultiLoadElasticityResidual) or residual.n_cases != 1:
+            raise NotImplementedError(f"{name}: several load cases are out of scope (one ElasticityResidual, one load)")
+        if getattr(residual.mesh, "local", None) is not None and residual.mesh.local.nranks > 1:
+            raise NotImplementedError(f"{name}: partitioned meshes are out of scope")
+        n_modes = int(n_modes)
+        block = _lib.ELAST_MAX_COLS if block is None else int(block)
+        if not 1 <= n_modes <= block <= _lib.ELAST_MAX_COLS:
+            raise ValueError(f"{name}: {n_modes} modes in a block of {block} (1 <= n_modes <= block <= {_lib.ELAST_MAX_COLS})")
+        self.residual, self.u, self.rho, self.mesh = residual, residual.u, residual.rho, residual.mesh
+        self.n_modes, self.block, self.n_dof = n_modes, block, residual.n_dof
+        self.rtol, self.pcg_rtol, self.max_outer, self.seed = float(rtol), 1e-12, 400, int(seed)
+        self.modes = Function(LoadCaseSpace(residual.u.function_space, block))
+        self._lam = None
+        self._key = None
+        self._started = False
+        self.last_info = {}
+
+    def device(self) -> DeviceElasticity:
+        return self.residual.device()
+
+    def _fixed_mask(self) -> np.ndarray:
+        R = self.residual
+        if R._mask is None or not R._mask.any():
+            raise RuntimeError(f"{type(self).__name__}: the residual has no fixed set yet -- solve the state first (the supports "
+                               "reach the residual with the solve, and without supports K is singular)")
+        if np.any(R._vals[R._mask == 1] != 0.0):
+            raise NotImplementedError(f"{type(self).__name__}: inhomogeneous supports are out of scope")
+        return R._mask
+
+    def load_factors(self) -> np.ndarray:
+        """0 < lambda_0 <= ... <= lambda_{n_modes-1} of the current density and state."""
+        mask = self._fixed_mask()
+        key = (self.rho.version, id(self.rho.vec), self.u.version, id(self.u.vec), hash(mask.tobytes()))
+        if key == self._key:
+            return self._lam[:self.n_modes].copy()
+        from .utils_hip import LAST_KSP_INFO
+        R = self.residual
+        dev = R.stiffness()                                            # the residual's K and ownership key: no assembly of our own
+        if not self._started:                                          # afterwards: the previous modes
+            free = mask == 0
+            X = np.zeros((self.block, self.n_dof))
+            X[:, free] = np.random.default_rng(self.seed).standard_normal((int(free.sum()), self.block)).T
+            self.modes.vector[:] = X.ravel()
+            self._started = True
+        lam, info = dev.buckle(self.n_modes, self.rho.vec, self.u.vec, self.modes.vec, block=self.block, method=R.method_id,
+                               rtol=self.rtol, max_outer=self.max_outer, pcg_rtol=self.pcg_rtol, pc=R.preconditioner)
+        self.modes.version += 1
+        self.last_info = dict(info, load_factors=lam.copy(), n_modes=self.n_modes, block=self.block)
+        LAST_KSP_INFO.append(dict(self.last_info, kind="elasticity_buckling"))
+        if info["converged"] != 1:
+            raise RuntimeError(f"elasticity buckling solve did not converge: {info['outer_iterations']} outer steps, residuals "
+                               f"{info['residual'][:self.n_modes]} above {self.rtol:.1e}")
+        self._lam, self._key = lam, key
+        return lam[:self.n_modes].copy()
+
+
+class BucklingAggregate(BackendForm):
+    """J = ((1/n) sum_{k<n} lambda_k^-p)^(-1/p), p >= 1, over the ``n_modes`` smallest positive load factors of an
+    `ElasticityBuckling`: the aggregate of `EigenvalueAggregate` (lambda_1 <= J <= n^(1/p) lambda_1, symmetric within a
+    cluster, so ``n_modes`` should not split one).  A rank-0 output of (u, rho).  With K-orthonormal modes and
+    c_k = dJ/dlambda_k,
+
+      dJ/drho_e = sum_k c_k lambda_k C'(rho_e) [phi_k,e^T K0_e phi_k,e + lambda_k |T_e| sigma_0(u_e) : H_e(phi_k)]
+      dJ/du_(b,j) = sum_k c_k lambda_k^2 sum_{e around b} C(rho_e) |T_e| (Sigma_H,e(phi_k) g_b)_j
+
+    with H = (grad phi)^T (grad phi) and Sigma_H = lambda_0 tr(H) I + 2 mu_0 H: one launch each.  The framework's adjoint
+    solves K w = dJ/du and applies dR/drho^T (the body-load term included).  dJ/du is non-zero on clamped dofs: the exact
+    reduced gradient needs ``fea.consistent_bc_partials = True``, as for `ElasticityPnormStress`."""
+    rank = 0
+
+    def __init__(self, buckling: ElasticityBuckling, p: float = 8.0):
+        if not isinstance(buckling, ElasticityBuckling):
+            raise NotImplementedError("BucklingAggregate needs an ElasticityBuckling")
+        if not p >= 1.0:
+            raise ValueError("BucklingAggregate needs p >= 1")
+        self.buckling, self.u, self.rho, self.mesh, self.p = buckling, buckling.u, buckling.rho, buckling.mesh, float(p)
+        self._grad = {}
+
+    def functions(self):
+        return (self.u, self.rho)
+
+    def assemble_scalar(self) -> float:
+        return float(_reciprocal_power_mean(self.buckling.load_factors(), self.p)[0])
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:                                            # one buffer per argument: both partials may be pending
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        if wrt is not self.u and wrt is not self.rho:
+            return out.fill(0.0)
+        b = self.buckling
+        lam = b.load_factors()
+        c = _reciprocal_power_mean(lam, self.p)[1]
+        dev, method = b.device(), b.residual.method_id
+        if wrt is self.u:
+            return dev.buckle_du(method, b.n_modes, self.rho.vec, b.modes.vec, c * lam * lam, out)
+        return dev.buckle_drho(method, b.n_modes, self.rho.vec, self.u.vec, b.modes.vec, c * lam, c * lam * lam, out)
 
 
 def averageFunc(func: Function) -> LinearFunctional:
@@ -1332,3 +1541,11 @@ def eigenvalue_aggregate(rho_e, V, bcs, n_modes: int = 3, p: float = 8.0, block:
     return EigenvalueAggregate(ElasticityEigenvalues(rho_e, V, bcs, n_modes, block=block, E=E, nu=nu, method=method,
                                                      density=density, mass_law=mass_law, preconditioner=preconditioner,
                                                      rtol=rtol, seed=seed), p=p)
+
+
+def buckling_aggregate(residual: ElasticityResidual, n_modes: int = 2, p: float = 8.0, block: Optional[int] = None,
+                       rtol: float = 1e-9, seed: int = 0) -> BucklingAggregate:
+    """The smooth lower bound of the critical buckling load factor of the state of ``residual`` as a scalar output:
+    ``fea.add_output('buckling', 'scalar', buckling_aggregate(res), ['u', 'density'])`` with
+    ``fea.consistent_bc_partials = True``."""
+    return BucklingAggregate(ElasticityBuckling(residual, n_modes, block=block, rtol=rtol, seed=seed), p=p)

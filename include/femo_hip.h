@@ -741,6 +741,44 @@ typedef struct femo_eig_info {
  * that runs out of steps returns with info->converged = 0.                                                                 */
 int femo_elast_eigs(femo_elast* e, int mass_law, double density, const femo_vec* rho, int n_modes, int block, femo_vec* X,
                     const femo_eig_opts* opts, double* lambda, femo_eig_info* info);
+/* Linearised buckling (csrc/elast_buckle.hip): (K(rho) + lambda K_G(u, rho)) phi = 0 on the free dofs for the state u of ONE
+ * load case, with the geometric stiffness of the cell stress sigma_e = C(rho_e) sigma_0(u_e) (the stiffness law itself: no
+ * separate stress interpolation; sigma_0 = lam0 tr(eps) I + 2 mu0 eps, its d x d in-plane block):
+ *   K_G,e[(a,i),(b,j)] = delta_ij |T_e| g_a . sigma_e g_b,   g_a the barycentric gradients.
+ * The critical load factor is the smallest positive lambda.  Columns as above; no float atomics anywhere: the same bits every
+ * call, and a column of the product does not depend on how many columns go with it.
+ *
+ * femo_elast_geom_stress fills the cell stress buffer of the handle (d (d+1) / 2 components of n_cell entries, component-major:
+ * the diagonal first, then 01[, 02, 12]; allocated on first use), so that the product touches neither u nor rho;
+ * femo_elast_geom_stress_get copies it into out (tests, output).                                                           */
+int femo_elast_geom_stress(femo_elast* e, int method, const femo_vec* rho, const femo_vec* u);
+int femo_elast_geom_stress_get(femo_elast* e, femo_vec* out /* d (d+1) / 2 * n_cell */);
+/* y_l = a K_G x_l with the stress of the last femo_elast_geom_stress, matrix free (vertex walk), one launch for all columns.
+ * masked = 1: (K_G)_ff -- fixed entries of x read as 0, y exactly 0 on the fixed dofs (needs femo_elast_set_fixed).         */
+int femo_elast_geom_apply_multi(femo_elast* e, int masked, int n_cols, double a, const femo_vec* x, femo_vec* y);
+/* out[(v,j)] = sum_{e around v} C(rho_e) |T_e| (Sigma_H g_v)_j,  Sigma_H = lam0 tr(H) I + 2 mu0 H,
+ * H = sum_k w_k (grad phi_k)^T (grad phi_k): with K-orthonormal modes and w_k = lambda_k^2 this is d lambda_k / d u, non-zero on
+ * clamped dofs.  One launch for all n_modes columns of phi, ascending k.                                                   */
+int femo_elast_buckle_du(femo_elast* e, int method, int n_modes, const femo_vec* rho, const femo_vec* phi,
+                         const double* w /* [n_modes] */, femo_vec* out);
+/* y[n_cell] (+)= C'(rho_e) |T_e| sum_k [ w1_k (lam0 (div phi_k)^2 + 2 mu0 eps(phi_k) : eps(phi_k)) + w2_k sigma_0(u_e) : H_e(phi_k) ]:
+ * with K-orthonormal modes, w1_k = lambda_k and w2_k = lambda_k^2 this is d lambda_k / d rho_e at fixed u.                   */
+int femo_elast_buckle_drho(femo_elast* e, int method, int n_modes, const femo_vec* rho, const femo_vec* u, const femo_vec* phi,
+                           const double* w1 /* [n_modes] */, const double* w2 /* [n_modes] */, femo_vec* y, int accumulate);
+/* The n_modes smallest positive load factors on the assembled K of the handle and its fixed set, solved as
+ * (-K_G) phi = mu K phi, mu = 1 / lambda, for the largest positive mu: femo_elast_eigs with the roles changed.  The call fills
+ * the stress buffer itself.  X: block columns, the start block on entry, the modes on return -- descending mu, X^T K X = I,
+ * exact zeros on the fixed dofs, the entry of largest magnitude of each column positive.  An outer step is B = (-K_G)_ff X, one
+ * batched PCG K Y = B from a zero first guess (so that its stopping level is relative to |B|), the Gram matrices Y^T K Y and
+ * Y^T (-K_G) Y, their block x block eigenproblem on the host and X = Y Q.  It stops when |(-K_G) x_k - mu_k K x_k| <= rtol mu_k
+ * |K x_k| (info->residual) and mu_k > 0 for every k < n_modes.  opts: max_outer 0 = 400.  lambda[block] = 1 / mu: ascending over
+ * the positive ones; a guard column may carry a negative value.
+ * The block converges to the modes of largest |mu| of EITHER sign; negative mu is buckling under the reversed load.  When one
+ * of the n_modes largest Ritz values is still not positive at the last outer step, the block is too small for this load and
+ * the call fails: raise block.  (With n_modes positive ones that merely miss rtol it returns with info->converged = 0.)  Shifted or sign-selective iterations are out of scope, as are several load cases, a stress
+ * interpolation of its own against low-density pseudo-modes, and nonlinear pre-buckling.                                    */
+int femo_elast_buckle(femo_elast* e, int method, const femo_vec* rho, const femo_vec* u, int n_modes, int block, femo_vec* X,
+                      const femo_eig_opts* opts, double* lambda, femo_eig_info* info);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
  *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
  * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices
