@@ -229,6 +229,7 @@ int femo_ctx_destroy(femo_ctx* c) {
   if (c->ev_comm) hipEventDestroy(c->ev_comm);
   hipFree(c->d_partials); hipFree(c->d_scal); hipFree(c->d_flags);
   hipFree(c->cg_r); hipFree(c->cg_p); hipFree(c->cg_q); hipFree(c->cg_dinv); hipFree(c->cg_s); hipFree(c->cg_t); hipFree(c->cg_r0);
+  hipFree(c->cg_ring); hipFree(c->cg_alpha_hist);
   hipHostFree(c->h_scal);
   for (int k = 0; k < FEMO_STAGE_SLOTS; ++k) {
     if (c->stage[k]) hipHostFree(c->stage[k]);
@@ -431,6 +432,13 @@ int femo_mesh_pc_info(const femo_mesh* m, int32_t* n_levels, int64_t* finest_nod
   int nl = 0;
   FEMO_TRY(femo_pc_levels(m, &nl, finest_nodes));
   *n_levels = nl;
+  return 0;
+}
+
+int femo_mesh_pcg_info(femo_mesh* m, int64_t* out, int count) {
+  FEMO_REQUIRE(m && out && count >= 0, "bad argument");
+  const int64_t v[4] = {femo_pc_merged_ok(m) ? 1 : 0, m->ctx->pcg_last_ring, m->ctx->pcg_last_flushes, m->ctx->pcg_ring_short};
+  for (int k = 0; k < count && k < 4; ++k) out[k] = v[k];
   return 0;
 }
 

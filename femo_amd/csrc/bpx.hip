@@ -125,6 +125,7 @@ struct femo_pc {
   int32_t* d_mint_idx = nullptr;
   double* d_mbuf = nullptr;           // [shared nodes of T, L-1, L | R h_T on level T-1 | MS_NRED scalars]: the one all-reduce per iteration
   bool merged_lds_set = false;        // k_lattice_coarse_m's LDS limit raised on this context's device (was a process-wide static)
+  bool merged_kept_lds_set = false;   // ... and that of its KEPT instantiation
   // ... and the part of the finest three levels this rank needs: the 8^3 (16^2) tiles of k_lattice_prolong3_m that hold a
   // node it touches (1/N of the lattice plus the interface layers)
   int64_t n_my_tiles = 0;
@@ -572,7 +573,7 @@ template <int D>
 __global__ __launch_bounds__(FEMO_BLOCK) void k_prolong_mesh(int64_t n_rows, Lat lat, const uint32_t* __restrict__ pk,
                                                              const double* __restrict__ rh, const float* __restrict__ sinv,
                                                              const uint8_t* __restrict__ mask, const double* __restrict__ e,
-                                                             double* __restrict__ out, int mode, int nb_dot,
+                                                             const double* prev, double* out, int mode, int nb_dot,
                                                              const double* __restrict__ dot_partials, const double* __restrict__ dot_global,
                                                              int nb_rho, const double* __restrict__ rho_partials, double* __restrict__ rho,
                                                              const double* __restrict__ gamma_cur, double* __restrict__ gamma_nxt,
@@ -681,7 +682,7 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_prolong_mesh(int64_t n_rows, Lat
     }
     const float si = sinv[v];                               // the same rounded 1/s the restriction multiplies with (k_pc_weights)
     const double z = si == 0.0f ? rh[v] : rh[v] + sum * (double)si;   // pinned rows stay r even if the correction is not finite
-    return mode == 1 ? z + beta * out[v] : z;
+    return mode == 1 ? z + beta * prev[v] : z;                // (prev == out unless the solver keeps its directions)
   };
   const int64_t stride = (int64_t)nblk * FEMO_BLOCK;
   for (int64_t w_i = (int64_t)bid * FEMO_BLOCK + threadIdx.x; w_i < n_walk; w_i += stride) {
@@ -1198,8 +1199,9 @@ struct MergedCarry {
   int cur, multi, init;
   int nb_pq, nb_pq2;
   const double *pq_partials, *pq_partials2;
-  double *x, *r;
-  const double *p, *q;
+  double *x, *r;              // x == nullptr: the solver keeps the directions and forms x itself (FemoMergedVecs::p_next);
+  const double *p, *q;        // the carriers then stream r and q only and workgroup 0 records alpha in *alpha_out
+  double* alpha_out;
   int64_t n;
   double* rr_partials;
   // one rank: the brick-filled levels below the finest as ONE contiguous range of n_dense nodes (state gs_c, this apply's
@@ -1228,6 +1230,9 @@ struct MergedCarry {
   int flat;                         // 3-D, 1 <= levels below T-1 <= 4, scratch fits: the chain below level T-1 in ONE down and ONE up step (below)
 };
 
+// KEPT: the solver keeps the directions (mc.x == nullptr).  A template parameter and not a test of mc.x: the kernel sits at the
+// register cap, and the instantiation small meshes run -- where workgroup 0 is the critical path -- stays the code it was.
+template <bool KEPT>
 __global__ __launch_bounds__(1024) void k_lattice_coarse_m(CoarseLevels L, int dim, const int32_t* __restrict__ done, MergedCarry mc) {
   // every load the scalars need is issued before the first one is used: the exit flag, gamma and the partials were three
   // dependent round trips to L2 (~3 us at the head of a 14-30 us kernel that is the critical path of small iterations)
@@ -1288,23 +1293,52 @@ __global__ __launch_bounds__(1024) void k_lattice_coarse_m(CoarseLevels L, int d
     if (mc.init) {
       // first apply: nothing to update, but r.r of the initial residual is what the next iteration's all-reduce carries
       for (int64_t i = (int64_t)b * 1024 + threadIdx.x; i < mc.n; i += (int64_t)nc * 1024) rr += mc.r[i] * mc.r[i];
+    } else if constexpr (KEPT) {
+      // r alone, two pairs per lane and trip: as many bytes in flight as the x and r pairs of the branch below
+      const int64_t n2 = mc.n >> 1, step = (int64_t)nc * 1024;
+      double2* r2 = reinterpret_cast<double2*>(mc.r);
+      const double2* q2 = reinterpret_cast<const double2*>(mc.q);
+      int64_t i = (int64_t)b * 1024 + threadIdx.x;
+      for (; i + step < n2; i += 2 * step) {
+        double2 r0 = r2[i], r1 = r2[i + step];
+        const double2 q0 = q2[i], q1 = q2[i + step];
+        r0.x -= alpha * q0.x; r0.y -= alpha * q0.y;
+        r1.x -= alpha * q1.x; r1.y -= alpha * q1.y;
+        r2[i] = r0; r2[i + step] = r1;
+        rr += r0.x * r0.x + r0.y * r0.y;
+        rr += r1.x * r1.x + r1.y * r1.y;
+      }
+      if (i < n2) {
+        double2 ri = r2[i];
+        const double2 qi = q2[i];
+        ri.x -= alpha * qi.x; ri.y -= alpha * qi.y;
+        r2[i] = ri;
+        rr += ri.x * ri.x + ri.y * ri.y;
+      }
+      if ((mc.n & 1) && b == 0 && threadIdx.x == 0) {
+        const int64_t j = mc.n - 1;
+        const double ri = mc.r[j] - alpha * mc.q[j];
+        mc.r[j] = ri;
+        rr += ri * ri;
+      }
     } else {
       const int64_t n2 = mc.n >> 1;
       double2* x2 = reinterpret_cast<double2*>(mc.x);
       double2* r2 = reinterpret_cast<double2*>(mc.r);
       const double2* p2 = reinterpret_cast<const double2*>(mc.p);
       const double2* q2 = reinterpret_cast<const double2*>(mc.q);
+      // (x with an explicit fma: the solver's flush of kept directions, k_pcg_flush, rounds the same way)
       for (int64_t i = (int64_t)b * 1024 + threadIdx.x; i < n2; i += (int64_t)nc * 1024) {
         double2 xi = x2[i], ri = r2[i];
         const double2 pi = p2[i], qi = q2[i];
-        xi.x += alpha * pi.x; xi.y += alpha * pi.y;
+        xi.x = fma(alpha, pi.x, xi.x); xi.y = fma(alpha, pi.y, xi.y);
         ri.x -= alpha * qi.x; ri.y -= alpha * qi.y;
         x2[i] = xi; r2[i] = ri;
         rr += ri.x * ri.x + ri.y * ri.y;
       }
       if ((mc.n & 1) && b == 0 && threadIdx.x == 0) {
         const int64_t i = mc.n - 1;
-        mc.x[i] += alpha * mc.p[i];
+        mc.x[i] = fma(alpha, mc.p[i], mc.x[i]);
         const double ri = mc.r[i] - alpha * mc.q[i];
         mc.r[i] = ri;
         rr += ri * ri;
@@ -1338,7 +1372,10 @@ __global__ __launch_bounds__(1024) void k_lattice_coarse_m(CoarseLevels L, int d
     if (threadIdx.x == 0) mc.lat_partials[b] = t1;
     return;
   }
-  if (threadIdx.x == 0) { mc.S[MS_ALPHA] = alpha; mc.S[MS_PQ] = pq; }
+  if (threadIdx.x == 0) {
+    mc.S[MS_ALPHA] = alpha; mc.S[MS_PQ] = pq;
+    if constexpr (KEPT) *mc.alpha_out = alpha;
+  }
   // N ranks: the reduced scalars where k_prolong_mesh looks for them
   // (and the three sums the next pack launch accumulates with atomics are left zeroed)
   if (mc.multi && threadIdx.x < MS_NRED) {
@@ -2100,7 +2137,7 @@ static void launch_prolong_mesh(femo_mesh* m, const uint8_t* mask, const FemoPcA
   const FemoPcgStop stop = a.stop != nullptr ? *a.stop : FemoPcgStop{};
   by_dim(pc->dim, [&](auto D) {
     hipLaunchKernelGGL(k_prolong_mesh<decltype(D)::value>, dim3(grid), dim3(FEMO_BLOCK), 0, m->ctx->stream, m->n_rows, lat, pc->d_pk, a.rh, pc->d_sinv, mask,
-                       pc->L.back().e, a.out, a.mode, nb_dot, pc->d_dot_partials, dot_global, a.nb_rho, a.rho_partials, a.rho, a.gamma_cur, a.gamma_nxt,
+                       pc->L.back().e, a.prev != nullptr ? a.prev : a.out, a.out, a.mode, nb_dot, pc->d_dot_partials, dot_global, a.nb_rho, a.rho_partials, a.rho, a.gamma_cur, a.gamma_nxt,
                        a.done, stop, ms, hf);
   });
 }
@@ -2426,7 +2463,10 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
   MergedCarry mc;
   mc.S = S; mc.cur = V.cur; mc.multi = multi ? 1 : 0; mc.init = init ? 1 : 0;
   mc.nb_pq = V.nb_q[0]; mc.nb_pq2 = V.nb_q[1]; mc.pq_partials = V.Pq[0]; mc.pq_partials2 = V.Pq[1];
-  mc.x = V.x; mc.r = V.r; mc.p = V.p; mc.q = V.q; mc.n = V.n;
+  const bool kept = V.p_next != nullptr && !init;  // the solver keeps the directions: no x stream, the new direction to the next slot
+  FEMO_REQUIRE(V.p_next == nullptr || (!multi && V.alpha_out != nullptr), "femo_pc_merged_apply: kept directions are for one rank and need alpha_out");
+  mc.x = kept ? nullptr : V.x; mc.r = V.r; mc.p = V.p; mc.q = V.q; mc.n = V.n;
+  mc.alpha_out = kept ? V.alpha_out : nullptr;
   mc.rr_partials = pc->d_rr_partials; mc.lat_partials = pc->d_lat_partials;
   mc.h_c_other = pc->acc(T, par ^ 1);
   mc.n_dense = hF - pc->acc(T, par);
@@ -2439,8 +2479,13 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
   mc.dbg = 0;                                    // (read by the kernel only, see MergedCarry)
   mc.sep_off = P.sep_off;
   mc.flat = P.flat;
-  FEMO_TRY(raise_lds((const void*)k_lattice_coarse_m, P.lds_merged, 159 * 1024, &pc->merged_lds_set));
-  hipLaunchKernelGGL(k_lattice_coarse_m, dim3(1 + n_carry), dim3(1024), P.lds_merged, st, CL, pc->dim, done, mc);
+  if (kept) {
+    FEMO_TRY(raise_lds((const void*)k_lattice_coarse_m<true>, P.lds_merged, 159 * 1024, &pc->merged_kept_lds_set));
+    hipLaunchKernelGGL(k_lattice_coarse_m<true>, dim3(1 + n_carry), dim3(1024), P.lds_merged, st, CL, pc->dim, done, mc);
+  } else {
+    FEMO_TRY(raise_lds((const void*)k_lattice_coarse_m<false>, P.lds_merged, 159 * 1024, &pc->merged_lds_set));
+    hipLaunchKernelGGL(k_lattice_coarse_m<false>, dim3(1 + n_carry), dim3(1024), P.lds_merged, st, CL, pc->dim, done, mc);
+  }
   for (int l = T; l <= nl - 4; ++l)              // 2-D (three fused levels): the level between T-1 and the tile kernel's three
     launch_lattice_prolong(pc, l, pc->state(l), 0, nullptr, nullptr, st, done);
   // N > 1: the shared nodes' part of the dot comes from the carriers (replicated), the single-rank nodes' part from the
@@ -2458,7 +2503,7 @@ int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, c
   ms.nb_rr = (multi || init) ? 0 : n_carry; ms.rr_partials = pc->d_rr_partials;
   ms.atol2 = V.atol2;
   // the new direction: p = zh (first apply) or zh + beta p, gamma' to the other parity's scalar
-  const FemoPcApply a = {.rh = V.r, .out = V.p, .mode = init ? 2 : 1, .rho = S + MS_RR, .gamma_cur = S + MS_GAMMA + V.cur,
+  const FemoPcApply a = {.rh = V.r, .out = kept ? V.p_next : V.p, .prev = V.p, .mode = init ? 2 : 1, .rho = S + MS_RR, .gamma_cur = S + MS_GAMMA + V.cur,
                          .gamma_nxt = S + MS_GAMMA + (init ? V.cur : V.cur ^ 1), .done = done, .stop = stop};
   const int nb_dot = multi ? 0 : P.m_grid;
   auto prolong = [&](unsigned grid, const HaloFirst& hf) { launch_prolong_mesh(m, mask, a, grid, nb_dot, nullptr, ms, hf); };

@@ -153,6 +153,14 @@ struct femo_ctx {
   double *cg_r = nullptr, *cg_p = nullptr, *cg_q = nullptr, *cg_dinv = nullptr, *cg_s = nullptr;
   double *cg_t = nullptr, *cg_r0 = nullptr;
   int64_t cg_n = 0;
+  // kept search directions of the one-rank merged BPX-PCG (solver.hip: ensure_ring): cg_ring_slots vectors of cg_n doubles (256-B stride)
+  // and one alpha per slot, allocated on the first merged solve of that size and freed with the vectors above
+  double* cg_ring = nullptr;
+  double* cg_alpha_hist = nullptr;
+  int cg_ring_slots = 0, cg_ring_want = 0;    // slots held / the count they were allocated for (FEMO_PCG_RING after clamping)
+  // femo_mesh_pcg_info: slots and flush launches of the last merged solve, solves whose ring came out smaller than asked for
+  int pcg_last_ring = 0, pcg_last_flushes = 0;
+  int64_t pcg_ring_short = 0;
 };
 
 struct femo_vec {
@@ -591,6 +599,11 @@ struct FemoMergedVecs {
   int nb_q[2]; const double* Pq[2];                    // SpMV partial triples [p.q | q.q | r.q] (one or two launches), FEMO_MAX_PARTIALS apart
   int gv;                                              // grid of the mesh-sized kernels
   double atol2;                                        // absolute threshold on r.r (0: none)
+  // One rank, kept directions (solver.hip: ensure_ring): p is the slot this iteration multiplied from, the new direction goes to
+  // p_next (the next slot of the ring) and alpha to *alpha_out; x is not touched -- the solver forms it from the slots.
+  // Both null: the update in place, x += alpha p in the carriers.
+  double* p_next = nullptr;
+  double* alpha_out = nullptr;
 };
 bool femo_pc_merged_ok(femo_mesh* m);                 // the fused lattice cycle with two brick-fused levels runs on this mesh
 struct FemoZeroExtra { double* p[3]; int64_t n[3]; int count; };     // small regions the caller wants cleared by the same launch
@@ -606,6 +619,7 @@ int femo_pc_merged_collectives(const femo_mesh* m);   // all-reduces per iterati
 // gamma' = rh.M^-1 rh = *rho + g_L.e_L, written to *gamma_nxt.  mode 2: like 1 with beta = 0.
 struct FemoPcApply {
   const double* rh; double* out;
+  const double* prev = nullptr;          // mode 1: the old direction beta multiplies (null: out, the update in place)
   int mode = 0;
   double* rho = nullptr; const double* gamma_cur = nullptr; double* gamma_nxt = nullptr;   // modes 1 and 2 (rho: read, or folded and stored: nb_rho)
   const int32_t* done = nullptr;         // nothing once *done is set

@@ -414,6 +414,34 @@ __global__ void k_unscale_done(int64_t n, int add, const double* __restrict__ s,
     x[i] = (add ? x[i] : 0.0) + s[i] * xh[i];
 }
 
+// Kept search directions of the one-rank merged BPX-PCG (ensure_ring): x^ += sum_j alpha_j p_j over j = base .. flags[1] - 1,
+// one fma per direction in the order of the iterations -- what the carriers' per-iteration x^ = fma(alpha, p, x^) leaves.
+// Direction j sits in slot j % slots of `ring` (slots `stride` doubles apart), alpha_j in alpha_hist[j % slots].  flags[1]
+// counts the iterations DONE, not those enqueued (launches behind the converging one return at once), and the direction of
+// the converging iteration belongs in x^: no early exit on flags[0] unless only_done asks for the opposite (the batch poll:
+// nothing to do while the loop runs).  Nothing to add: x^ is not written.  s != nullptr: x = (add ? x : 0) + s .* x^ as
+// k_unscale, from the sum in registers.
+__global__ __launch_bounds__(256) void k_pcg_flush(int64_t n, double* __restrict__ xh, const double* __restrict__ ring, int64_t stride,
+                                                   int slots, const double* __restrict__ alpha_hist, int base,
+                                                   const int32_t* __restrict__ flags, int only_done, int add,
+                                                   const double* __restrict__ s, double* __restrict__ x) {
+  if (only_done && flags[0] == 0) return;
+  const int count = min(flags[1], base + slots);          // (the host flushes before a slot is reused: never more than `slots`)
+  if (count <= base && s == nullptr) return;
+  const int k0 = base % slots;                            // slot of direction `base`; the walk below wraps without a division
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    double acc = xh[i];
+    int k = k0;
+#pragma unroll 4
+    for (int j = base; j < count; ++j) {
+      acc = fma(alpha_hist[k], ring[(int64_t)k * stride + i], acc);
+      k = k + 1 == slots ? 0 : k + 1;
+    }
+    if (count > base) xh[i] = acc;
+    if (s != nullptr) x[i] = (add ? x[i] : 0.0) + s[i] * acc;
+  }
+}
+
 __global__ __launch_bounds__(FEMO_BLOCK) void k_dot(int64_t n, const double* __restrict__ a, const double* __restrict__ b,
                                                     double* __restrict__ partials) {
   __shared__ double lds[FEMO_BLOCK / 64];
@@ -569,9 +597,9 @@ int ensure_work(femo_ctx* ctx, int64_t n_rows, int64_t n_vert, CgWork& w, int ne
   const int64_t len = std::max(n_rows, n_vert) + 2;
   if (ctx->cg_n < len) {
     hipFree(ctx->cg_r); hipFree(ctx->cg_p); hipFree(ctx->cg_q); hipFree(ctx->cg_dinv); hipFree(ctx->cg_s);
-    hipFree(ctx->cg_t); hipFree(ctx->cg_r0);
-    ctx->cg_r = ctx->cg_p = ctx->cg_q = ctx->cg_dinv = ctx->cg_s = ctx->cg_t = ctx->cg_r0 = nullptr;
-    ctx->cg_n = 0;
+    hipFree(ctx->cg_t); hipFree(ctx->cg_r0); hipFree(ctx->cg_ring);
+    ctx->cg_r = ctx->cg_p = ctx->cg_q = ctx->cg_dinv = ctx->cg_s = ctx->cg_t = ctx->cg_r0 = ctx->cg_ring = nullptr;
+    ctx->cg_n = 0; ctx->cg_ring_slots = ctx->cg_ring_want = 0;
     FEMO_HIP_CHECK(hipMalloc(&ctx->cg_r, len * sizeof(double)));
     FEMO_HIP_CHECK(hipMalloc(&ctx->cg_p, len * sizeof(double)));
     FEMO_HIP_CHECK(hipMalloc(&ctx->cg_q, len * sizeof(double)));
@@ -589,6 +617,54 @@ int ensure_work(femo_ctx* ctx, int64_t n_rows, int64_t n_vert, CgWork& w, int ne
   }
   w.r = ctx->cg_r; w.p = ctx->cg_p; w.q = ctx->cg_q; w.xh = ctx->cg_dinv; w.sv = ctx->cg_s;
   w.t = ctx->cg_t; w.r0 = ctx->cg_r0;
+  return 0;
+}
+
+// Ring of kept search directions for the one-rank merged BPX-PCG (after ensure_work: slots of ctx->cg_n doubles).  Nothing
+// in that loop reads x^, so instead of streaming it through the carriers of k_lattice_coarse_m every iteration (24 of their
+// 48 B per row) the loop leaves p_k in slot k % R -- k_prolong_mesh reads the old direction and writes the new one anyway --
+// and k_pcg_flush adds alpha_k p_k to x^ in the order of the iterations when the ring is full and at the end of the solve.
+// The rule for R (returned; 0: the per-iteration update):
+//   FEMO_PCG_RING unset -> 32 on meshes of at least FEMO_RING_MIN_ROWS rows, 0 below; "0" -> 0; any other value, on any
+//   mesh, clamped to 2 .. 64; then halved while the ring exceeds one eighth of the device's memory or hipMalloc fails; a
+//   result below 2 -> 0, counted in femo_ctx::pcg_ring_short like every solve that got fewer slots than it asked for.
+//   The ring is allocated on the first solve that asks for this R at this vector length and kept until the CG vectors are
+//   reallocated or the context goes: a warmed-up cycle allocates nothing.
+// FEMO_RING_MIN_ROWS: the carriers run beside workgroup 0 of their launch (the LDS-resident lattice levels, W = 14-21 us); per
+// million rows they take 7.6 us with the x^ stream and 4.1 without, a flush 1.5 per iteration, so the ring gains 6.1 us x M rows
+// - W per iteration once the carriers outlast workgroup 0 and only costs below (DESIGN_LOG R14: measured at 1.03 M and 10.08 M rows).
+constexpr int64_t FEMO_RING_MIN_ROWS = 3000000;
+// doubles from one slot to the next: cg_n rounded up to 256 B, so that every slot starts on a cache line like a vector of its own
+int64_t ring_stride(const femo_ctx* ctx) { return (ctx->cg_n + 31) & ~int64_t(31); }
+int ensure_ring(femo_ctx* ctx, int64_t n_rows, int* slots) {
+  *slots = 0;
+  const char* env = getenv("FEMO_PCG_RING");              // read once per solve (the tests switch it), never per launch
+  int want = n_rows >= FEMO_RING_MIN_ROWS ? 32 : 0;
+  if (env != nullptr) {
+    want = atoi(env);
+    if (want != 0) want = std::min(64, std::max(2, want));
+  }
+  if (want == 0 || n_rows <= 0) return 0;
+  if (!ctx->cg_alpha_hist) FEMO_HIP_CHECK(hipMalloc(&ctx->cg_alpha_hist, 64 * sizeof(double)));   // one per slot of the largest ring
+  if (ctx->cg_ring_want != want) {
+    hipFree(ctx->cg_ring);
+    ctx->cg_ring = nullptr;
+    ctx->cg_ring_slots = 0;
+    size_t free_b = 0, total_b = 0;
+    FEMO_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    (void)free_b;                                          // (the rule is on the device's size, not on what happens to be free)
+    const size_t slot_b = (size_t)ring_stride(ctx) * sizeof(double);
+    bool refused = false;
+    for (int r = want; r >= 2 && ctx->cg_ring_slots == 0; r /= 2) {
+      if ((size_t)r * slot_b > total_b / 8) continue;
+      if (hipMalloc(&ctx->cg_ring, (size_t)r * slot_b) == hipSuccess) ctx->cg_ring_slots = r;
+      else { (void)hipGetLastError(); ctx->cg_ring = nullptr; refused = true; }
+    }
+    // the outcome is remembered (no attempt per solve) unless hipMalloc refused every size: that may pass, the next solve asks again
+    ctx->cg_ring_want = (ctx->cg_ring_slots > 0 || !refused) ? want : 0;
+  }
+  if (ctx->cg_ring_slots < want) ++ctx->pcg_ring_short;   // visible through femo_mesh_pcg_info
+  *slots = ctx->cg_ring_slots;
   return 0;
 }
 }  // namespace
@@ -788,6 +864,20 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
   // k_cg_init writes every owned entry of r, p and x^; only the ghost tails have to be defined (zero) -- they and the ghost
   // tail of the solution are cleared by the preconditioner's own clearing launch (round 6; round 5: three memsets)
   FEMO_TRY(ensure_work(ctx, n, m->n_vert, w, 0, /*zero=*/false));
+  // one rank without ghost entries: the directions are kept in a ring and x^ is formed from them (ensure_ring); direction k in
+  // slot(k), alpha_k beside it
+  int R = 0;
+  if (!multi && m->n_vert <= n) FEMO_TRY(ensure_ring(ctx, n, &R));
+  const int64_t stride = ring_stride(ctx);
+  auto slot = [&](int k) -> double* { return ctx->cg_ring + (int64_t)(k % R) * stride; };
+  int flushed = 0;                                               // directions below this one are in x^
+  ctx->pcg_last_ring = R; ctx->pcg_last_flushes = 0;
+  auto flush = [&](bool only_done, bool unscale) {
+    ++ctx->pcg_last_flushes;
+    hipLaunchKernelGGL(k_pcg_flush, dim3(2048), dim3(256), 0, ctx->stream, n, w.xh, (const double*)ctx->cg_ring, stride, R,
+                       (const double*)ctx->cg_alpha_hist, flushed, (const int32_t*)ctx->d_flags, only_done ? 1 : 0, opts->zero_guess ? 0 : 1,
+                       unscale ? (const double*)A->d_s : (const double*)nullptr, x->d);
+  };
   const int gv = vec_grid(ctx, n);
   const int gs = femo_spmv_grid(m);
   int32_t* h_flags = FlagPoll::host_words(ctx);
@@ -805,7 +895,8 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
   FEMO_TRY(femo_pc_merged_begin(m, A->d_s, mask, &ze));
   const double* q0;
   FEMO_TRY(initial_guess(A, A->d_vals, x, opts->zero_guess, /*clear_x=*/false, w.q, &q0));
-  hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, b->d, q0, A->d_s, w.r, w.p, w.xh, P, A->has_idrows ? A->d_idrows : nullptr);
+  double* const p0 = R ? slot(0) : w.p;
+  hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(FEMO_BLOCK), 0, st, n, b->d, q0, A->d_s, w.r, p0, w.xh, P, A->has_idrows ? A->d_idrows : nullptr);
   const double atol2 = opts->atol * opts->atol;
   if (multi) {
     FEMO_TRY(femo_launch_fold(1024, gv, 2, P + FEMO_MAX_PARTIALS, S + MS_RED, st));
@@ -821,7 +912,7 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
   stop.flags = ctx->d_flags;
   stop.it = -1;
   FemoMergedVecs V;
-  V.x = w.xh; V.r = w.r; V.p = w.p; V.q = nullptr; V.n = n; V.cur = 0; V.gv = gv; V.atol2 = 0.0;
+  V.x = w.xh; V.r = w.r; V.p = p0; V.q = nullptr; V.n = n; V.cur = 0; V.gv = gv; V.atol2 = 0.0;
   V.nb_q[0] = V.nb_q[1] = 0; V.Pq[0] = V.Pq[1] = nullptr;
   FEMO_TRY(femo_pc_merged_apply(m, mask, A->pc_key, V, S, ctx->d_flags, &stop));
   FEMO_HIP_CHECK(hipGetLastError());
@@ -883,10 +974,16 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
     }
     const int it_end = it + this_batch < max_it ? it + this_batch : max_it;
     for (; it < it_end; ++it) {
+      if (R) {
+        // the ring is full: this iteration's prolongation writes the slot of direction `flushed` -- directions up to it - 1
+        // (their alphas are known) go to x^ first
+        if (it + 1 - flushed == R) { flush(false, false); flushed = it; }
+        V.p = slot(it); V.p_next = slot(it + 1); V.alpha_out = ctx->cg_alpha_hist + it % R;
+      }
       FEMO_TRY(spmv.begin(it));
       int g1 = gs, g2 = 0;
       if (multi) FEMO_TRY(femo_halo_spmv(A, w.p, w.q, Ap_multi, &g1, &g2, inflight));
-      else FEMO_TRY(femo_launch_spmv(A, w.p, w.q, Ap_one));
+      else FEMO_TRY(femo_launch_spmv(A, V.p, w.q, Ap_one));
       FEMO_TRY(spmv.end());
       stop.it = it;
       V.cur = it & 1;
@@ -896,7 +993,9 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
     FEMO_HIP_CHECK(hipGetLastError());
     // the poll carries everything the end of a converged solve needs: x (unscaled on the device only if the flag is set),
     // the flags and the scalars -- the batch that converges costs ONE host round trip, not two (round 6)
-    if (n > 0) hipLaunchKernelGGL(k_unscale_done, dim3(2048), dim3(256), 0, st, n, opts->zero_guess ? 0 : 1, A->d_s, w.xh, x->d, ctx->d_flags);
+    // (kept directions: the same launch adds those not yet in x^ first -- like k_unscale_done, nothing unless the flag is set)
+    if (R) flush(true, true);
+    else if (n > 0) hipLaunchKernelGGL(k_unscale_done, dim3(2048), dim3(256), 0, st, n, opts->zero_guess ? 0 : 1, A->d_s, w.xh, x->d, ctx->d_flags);
     // a consumer of the device-initiated ghost refresh that gave up waiting (4 s) must not pass for a result: its flag
     // travels in the spare word of the poll
     if (femo_halo_direct_ready(m)) FEMO_HIP_CHECK(hipMemcpyAsync(ctx->d_flags + 3, m->hd->d_err, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -909,7 +1008,8 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
   const hipEvent_t end = h_flags[0] ? ctx->ev_pool[POLL_EV] : ctx->ev1;
   if (!h_flags[0]) {
     // not converged within max_it: x of the last iterate, the final scalars and the time with one more synchronisation
-    if (n > 0) hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, st, n, opts->zero_guess ? 0 : 1, A->d_s, w.xh, x->d);
+    if (R) flush(false, true);
+    else if (n > 0) hipLaunchKernelGGL(k_unscale, dim3(2048), dim3(256), 0, st, n, opts->zero_guess ? 0 : 1, A->d_s, w.xh, x->d);
     FEMO_TRY(read_back(ctx, ctx->ev1));
   }
   const int iters = h_flags[1];

@@ -576,6 +576,14 @@ class DeviceMesh:
         check(self.lib.femo_mesh_pc_info(self.handle, C.byref(nl), C.byref(nodes)))
         return {"levels": nl.value, "finest_nodes": nodes.value}
 
+    def pcg_info(self):
+        """Which BPX-PCG loop runs on this mesh and what the last merged solve on its context did (femo_hip_test.h)."""
+        if not hasattr(self.lib, "femo_mesh_pcg_info"):
+            raise FemoError("femo_mesh_pcg_info: not exported by this build of libfemo_hip.so")
+        v = (C.c_int64 * 4)()
+        check(self.lib.femo_mesh_pcg_info(self.handle, v, 4))
+        return {"merged": bool(v[0]), "ring_slots": int(v[1]), "flushes": int(v[2]), "ring_short": int(v[3])}
+
     def set_halo(self, nbr, send_ptr, send_idx, recv_ptr) -> None:
         nbr = _i32(nbr)
         send_ptr = np.ascontiguousarray(send_ptr, np.int64)

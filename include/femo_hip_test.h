@@ -32,6 +32,15 @@ int femo_comm_emulate(femo_ctx* ctx, femo_emu_group* group, int rank);
  * are those of the rank's block solved on its own (zero ghost values), not of the global problem.           */
 int femo_comm_model(femo_ctx* ctx, int rank, int nranks);
 
+/* ---- merged BPX-PCG: which loop ran, and on how many kept directions (tests) -----------------------------
+ * out[0] = 1 if BPX-PCG solves on this mesh take the merged loop (builds the lattice hierarchy if need be; honours
+ *          the environment switches that select the classic loop), else 0;
+ * out[1] = ring slots the last merged solve on this mesh's context used (0: x += alpha p every iteration);
+ * out[2] = flush launches that solve enqueued (ring full, batch polls, max_it);
+ * out[3] = merged solves on this context that asked for a ring and got fewer slots than asked for, or none.
+ * Entries beyond `count` are not written.                                                                   */
+int femo_mesh_pcg_info(femo_mesh* mesh, int64_t* out, int count);
+
 #ifdef __cplusplus
 }
 #endif
