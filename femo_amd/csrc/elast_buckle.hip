@@ -11,26 +11,16 @@
 // vertex, the columns and the modes are summed in a fixed order, so every call gives the same bits, and a column of the
 // product does not depend on how many columns travel with it.
 //
-// femo_elast_buckle is femo_elast_eigs with the roles changed: the pencil is (-K_G) phi = mu K phi, mu = 1 / lambda, K
-// positive definite and -K_G indefinite, for the largest positive mu.  An outer step issues
-//
-//   B = (-K_G)_ff X                          k_elast_geom            one launch for the block
-//   K Y = B, first guess 0                   the batched PCG of elast_solve.hip (Y overwrites X); the stopping level is
-//                                            relative to |B|
-//   KY = A Y, GY = (-K_G)_ff Y               k_elast_spmv_multi, k_elast_geom
-//   G_K = Y^T KY, G_G = Y^T GY               k_block_gram twice, one fold, one copy to the pinned mirror
-//   host: Cholesky of G_K, cyclic Jacobi on C^-1 G_G C^-T  ->  mu, taken in descending order, Q = C^-T V
-//   X = Y Q, KX = KY Q, R = GY Q - KX diag(mu)   k_block_rotate three times (X in place)
-//   |R_k|^2, |KX_k|^2                        k_block_gram twice, one fold, one copy
-//
-// and stops when |R_k| <= rtol mu_k |KX_k| and mu_k > 0 for every k < n_modes.  The block converges to the modes of largest
-// |mu| of either sign (negative mu: buckling under the reversed load): when one of the n_modes largest Ritz values is still
-// not positive at the last outer step, the block is too small for this load and the call fails.
+// femo_elast_buckle is the block iteration of elast_block.hip on the pencil (-K_G) phi = mu K phi, mu = 1 / lambda, K
+// positive definite and -K_G indefinite, for the largest positive mu: the operator product is (-K_G)_ff (k_elast_geom, one
+// launch for the block), the modes come back K-orthonormal with mu descending, and the inner PCG K Y = (-K_G) X starts from
+// zero (its stopping level is relative to |B|).  It stops when |(-K_G) x_k - mu_k K x_k| <= rtol mu_k |K x_k| and mu_k > 0
+// for every k < n_modes.  The block converges to the modes of largest |mu| of either sign (negative mu: buckling under the
+// reversed load): when one of the n_modes largest Ritz values is still not positive at the last outer step, the block is
+// too small for this load and the call fails.
 #include "elast_internal.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
 
 using namespace elast_block;
 
@@ -431,93 +421,20 @@ int femo_elast_buckle(femo_elast* e, int method, const femo_vec* rho, const femo
   FEMO_REQUIRE(e->has_fixed, "femo_elast_buckle: no fixed set -- K is singular on a free-free structure");
   FEMO_REQUIRE(opts->rtol > 0.0 && opts->pcg_rtol > 0.0, "femo_elast_buckle: need rtol > 0 and pcg_rtol > 0");
   femo_mesh* m = e->mesh;
-  femo_ctx* ctx = m->ctx;
   const int64_t n = m->n_vert * e->d, nl = n * block;
   FEMO_REQUIRE(rho->n >= m->n_cell && u->n >= n && X->n >= nl, "vector size mismatch in femo_elast_buckle: %d columns need %lld entries",
                block, (long long)nl);
   FEMO_REQUIRE(X != rho && X != u, "femo_elast_buckle: the block aliases the density or the state");
   FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(X));
   femo_vec_touch(X);
-  FEMO_TRY(femo_elast_work_reserve(e, block, "femo_elast_buckle"));
-  FEMO_TRY(gram_reserve(e));
-  if (e->w_eig_cols < block) {
-    double* b = nullptr;
-    FEMO_TRY(dalloc(&b, nl));
-    FEMO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    hipFree(e->w_eig);
-    e->w_eig = b;
-    e->w_eig_cols = block;
-  }
   FEMO_TRY(stress_launch(e, method, rho->d, u->d));
-  femo_solver_opts so;
-  std::memset(&so, 0, sizeof(so));
-  so.rtol = opts->pcg_rtol;
-  so.max_it = opts->pcg_max_it;
-  so.zero_guess = 1;                                                  // the stopping level is relative to |B|
-  so.pc = opts->pc;
-  const int max_outer = opts->max_outer > 0 ? opts->max_outer : 400;
-  femo_vec Bv = wrap(ctx, e->w_eig, nl);
-  femo_solve_info si[EMC];
-  femo_eig_info out;
-  std::memset(&out, 0, sizeof(out));
-  double mu[EMC] = {};
-  const int L = block, LL = EMC * EMC;
-  int positive = 0;                                                   // tested columns with mu > 0 at the last outer step
-  for (int outer = 1; outer <= max_outer; ++outer) {
-    FEMO_TRY(geom_launch(e, true, L, -1.0, X->d, e->w_eig));                                        // B = (-K_G)_ff X
-    FEMO_TRY(femo_elast_pcg(e, L, &Bv, X, &so, si, "femo_elast_buckle"));                            // K Y = B, Y in X
-    int its = 0;
-    for (int l = 0; l < L; ++l) {
-      FEMO_REQUIRE(si[l].converged == 1, "femo_elast_buckle: the inner PCG did not converge (outer step %d, column %d: %d iterations)",
-                   outer, l, si[l].iterations);
-      its = std::max(its, (int)si[l].iterations);
-      out.solve_ms += l == 0 ? si[l].solve_ms : 0.0;
-    }
-    out.pcg_iterations += its;
-    out.outer_iterations = outer;
-    double *GY = e->w_z, *KY = e->w_q, *KX = e->w_p, *R = e->w_r;      // the PCG work vectors are free until the next solve
-    FEMO_TRY(femo_elast_spmv(e, true, L, 1.0, X->d, 0.0, nullptr, KY, nullptr, 0, nullptr));
-    FEMO_TRY(geom_launch(e, true, L, -1.0, X->d, GY));
-    FEMO_TRY(gram_launch(e, 0, n, L, X->d, L, KY));
-    FEMO_TRY(gram_launch(e, 1, n, L, X->d, L, GY));
-    FEMO_TRY(gram_fetch(e, n, L * L, L * L));
-    double GK[EMC][EMC] = {}, GG[EMC][EMC] = {}, Qa[EMC][EMC] = {}, asc[EMC] = {};
-    for (int i = 0; i < L; ++i)
-      for (int j = 0; j < L; ++j) { GK[i][j] = e->h_gram[i * L + j]; GG[i][j] = e->h_gram[LL + i * L + j]; }
-    FEMO_REQUIRE(small_eigs(L, GK, GG, asc, Qa),
-                 "femo_elast_buckle: the block lost rank (Y^T K Y is not positive definite at outer step %d): start from another block",
-                 outer);
-    BlockMatrix Q, QT;                                                // the columns in descending mu
-    std::memset(&Q, 0, sizeof(Q)); std::memset(&QT, 0, sizeof(QT));
-    for (int j = 0; j < L; ++j) {
-      mu[j] = asc[L - 1 - j];
-      for (int i = 0; i < L; ++i) { Q.v[i][j] = Qa[i][L - 1 - j]; QT.v[i][j] = -Q.v[i][j] * mu[j]; }
-    }
-    FEMO_TRY(rotate_launch(e, n, L, Q, X->d, nullptr, nullptr, X->d));          // X = Y Q
-    FEMO_TRY(rotate_launch(e, n, L, Q, GY, &QT, KY, R));                        // R = GY Q - KY Q diag(mu)
-    FEMO_TRY(rotate_launch(e, n, L, Q, KY, nullptr, nullptr, KX));              // KX = KY Q
-    FEMO_TRY(gram_launch(e, 0, n, L, R, L, R));
-    FEMO_TRY(gram_launch(e, 1, n, L, KX, L, KX));
-    FEMO_TRY(gram_fetch(e, n, L * L, L * L));
-    bool ok = true;
-    positive = 0;
-    for (int k = 0; k < L; ++k) {
-      const double rn = std::sqrt(std::fabs(e->h_gram[k * L + k])), kn = std::sqrt(std::fabs(e->h_gram[LL + k * L + k]));
-      out.residual[k] = rn / (std::fabs(mu[k]) * kn);
-      if (k < n_modes && mu[k] > 0.0) ++positive;
-      if (k < n_modes && !(out.residual[k] <= opts->rtol && mu[k] > 0.0)) ok = false;
-    }
-    if (ok) { out.converged = 1; break; }
-  }
-  FEMO_TRY(sign_launch(e, n, L, X->d));
-  FEMO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  FEMO_REQUIRE(out.converged == 1 || positive == n_modes,
-               "femo_elast_buckle: the block is too small for this load -- no positive load factor for %d of the %d modes after %d "
-               "outer steps (the block of %d columns fills up with negative mu, buckling under the reversed load): raise block",
-               n_modes - positive, n_modes, out.outer_iterations, L);
-  for (int k = 0; k < L; ++k) lambda[k] = 1.0 / mu[k];
-  if (info) *info = out;
-  return 0;
+  // (-K_G) phi = mu K phi: K is the positive definite side; mu descending and positive, lambda = 1 / mu; the PCG from zero, so
+  // that its stopping level is relative to |B|
+  const Pencil pencil = {"femo_elast_buckle", "K", [=](int n_cols, const double* x, double* y) {
+                           return geom_launch(e, true, n_cols, -1.0, x, y); },
+                         /*p_is_op*/ false, /*descending*/ true, /*zero_guess*/ 1, /*max_outer*/ 400, /*positive_only*/ true,
+                         /*reciprocal*/ true};
+  return block_iteration(e, pencil, n_modes, block, X, opts, lambda, info);
 }
 
 }  // extern "C"

@@ -1,10 +1,12 @@
 // Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product and PCG), elast_pc.hip
-// (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, elast_eig.hip
-// (mass product, block linear algebra and the eigen solve) and elast_buckle.hip (geometric stiffness and the buckling
-// solve, on the block linear algebra of elast_eig.hip).  Not part of the ABI.
+// (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, elast_block.hip
+// (block linear algebra and the block iteration of the eigen solves), elast_eig.hip (mass product and the eigenfrequency
+// pencil) and elast_buckle.hip (geometric stiffness and the buckling pencil).  Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
+
+#include <functional>
 
 struct femo_elast_pc;   // lattice hierarchy of the multilevel preconditioner (elast_pc.hip)
 
@@ -35,8 +37,8 @@ struct femo_elast {
   // stress aggregate (femo_elast_pnorm_stress, femo_elast_pnorm_stress_multi): FEMO_ELAST_MAX_COLS slabs of partials, one per
   // column, and the folded values behind them, on first use
   double* w_smpart = nullptr;
-  // eigen solve (elast_eig.hip), on first use: the right-hand sides B = M X of w_eig_cols columns; the Gram partials and
-  // their folded values, with their pinned mirror
+  // block iteration (elast_block.hip), on first use: the right-hand sides B = Op X of w_eig_cols columns; the Gram partials
+  // and their folded values, with their pinned mirror
   double* w_eig = nullptr;
   int w_eig_cols = 0;
   double* w_gram = nullptr;
@@ -102,11 +104,13 @@ int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who);
 int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
                    const char* who);
 
-// elast_eig.hip: the block linear algebra of the eigen solves ----------------------------------------------------------
+// elast_block.hip: the block linear algebra and the block iteration of the eigen solves --------------------------------
 namespace elast_block {
 struct BlockMatrix { double v[FEMO_ELAST_MAX_COLS][FEMO_ELAST_MAX_COLS]; };
 // The Gram partials and their pinned mirror h_gram, on first use.
 int gram_reserve(femo_elast* e);
+// The right-hand sides w_eig of the block iteration for at least n_cols columns.
+int rhs_reserve(femo_elast* e, int n_cols);
 // slab s (0 or 1) <- partials of A^T B (n entries per column); folded by gram_fetch
 int gram_launch(femo_elast* e, int slab, int64_t n, int n_a, const double* A, int n_b, const double* B);
 // folds the first `sums0` pairs of slab 0 and `sums1` of slab 1 and waits for them in h_gram[0 ...] and
@@ -123,6 +127,24 @@ bool small_eigs(int L, const double (&GM)[FEMO_ELAST_MAX_COLS][FEMO_ELAST_MAX_CO
 int sign_launch(femo_elast* e, int64_t n, int n_cols, double* x);
 // a femo_vec over memory it does not own
 femo_vec wrap(femo_ctx* ctx, double* d, int64_t n);
+
+// The Ritz pencil N phi = theta P phi of one block iteration: K is one side, the masked product `apply` the other.
+struct Pencil {
+  const char* who;          // the entry point, for the error texts
+  const char* p_name;       // P in the error texts ("Y^T P Y is not positive definite")
+  std::function<int(int n_cols, const double* x, double* y)> apply;   // y_l = Op_ff x_l for n_cols columns, one launch
+  bool p_is_op;             // P (the positive definite side) is Op and N is K; otherwise P is K and N is Op
+  bool descending;          // the modes in descending theta (ascending otherwise)
+  int zero_guess;           // the inner PCG starts from zero (1) or from the previous block (0)
+  int max_outer;            // outer steps at the most when the options say 0
+  bool positive_only;       // a mode counts only with theta > 0, and the call fails when fewer than n_modes ever do
+  bool reciprocal;          // the reported values are 1 / theta
+};
+// Block inverse iteration with Rayleigh-Ritz for the n_modes first modes of the pencil in a block of `block` columns of X
+// (the start block on entry, the P-orthonormal modes on return), for a caller that has checked its arguments.  lambda:
+// `block` values; info may be null.
+int block_iteration(femo_elast* e, const Pencil& pencil, int n_modes, int block, femo_vec* X, const femo_eig_opts* opts,
+                    double* lambda, femo_eig_info* info);
 }  // namespace elast_block
 
 #if defined(__HIPCC__)

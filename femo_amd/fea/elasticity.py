@@ -1,7 +1,7 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
 product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip,
-buckling in csrc/elast_buckle.hip).  One load case is the L = 1 case of several:
+buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
@@ -38,7 +38,7 @@ are used unchanged.
                        load case, for `project` / FEA.add_field_output
   ElasticityEigenvalues  the lowest eigenpairs of K(rho) phi = lambda M(rho) phi on the free dofs, M = density sum_e m(rho_e)
                        M0_e the consistent P1 mass with m = rho or Du & Olhoff's C^1 cut-off below rho = 0.1: block inverse
-                       iteration with Rayleigh-Ritz, every inner solve one batched PCG over the block (csrc/elast_eig.hip),
+                       iteration with Rayleigh-Ritz, every inner solve one batched PCG over the block (csrc/elast_block.hip),
                        warm-started from the previous modes.  Not in the reference's script
   EigenvalueAggregate  J = ((1/n) sum_{k<n} lambda_k^-p)^(-1/p), a smooth stand-in for the fundamental eigenvalue that is
                        symmetric within a cluster, as a scalar output of the density alone: dJ/drho = sum_k c_k (C'(rho_e)
@@ -47,7 +47,7 @@ are used unchanged.
   ElasticityBuckling   the smallest positive load factors of (K(rho) + lambda K_G(u, rho)) phi = 0 on the free dofs for the
                        state u of an `ElasticityResidual`: K_G the geometric stiffness of the cell stress C(rho_e) sigma_0(u_e),
                        matrix free.  Solved as (-K_G) phi = mu K phi, mu = 1 / lambda, for the largest positive mu by the block
-                       iteration of the eigenfrequencies with the roles changed (csrc/elast_buckle.hip), on the residual's
+                       iteration of the eigenfrequencies on another pencil (csrc/elast_block.hip), on the residual's
                        own K.  Not in the reference's script
   BucklingAggregate    J = ((1/n) sum_{k<n} lambda_k^-p)^(-1/p) of the load factors, the aggregate of `EigenvalueAggregate`, as a
                        scalar output of (u, rho): dJ/du and dJ/drho are one launch each, and the framework's adjoint solve
@@ -244,7 +244,7 @@ class DeviceElasticity:
                                              int(bool(zero_fixed)), y.handle, int(bool(accumulate))))
         return y
 
-    # ---- eigenfrequencies: K phi = lambda M(rho) phi on the free dofs (csrc/elast_eig.hip) ----
+    # ---- eigenfrequencies: K phi = lambda M(rho) phi on the free dofs (csrc/elast_eig.hip, csrc/elast_block.hip) ----
     @staticmethod
     def _mass_law(mass_law: str) -> int:
         if mass_law not in MASS_LAWS:
@@ -295,17 +295,23 @@ class DeviceElasticity:
         Rayleigh-Ritz; every inner solve is one batched PCG over the ``block`` columns of ``X`` (the start block on entry,
         the M-orthonormal modes on return; the last block - n_modes columns are guard vectors).  Returns (lambda[block]
         ascending, info) with info = dict(outer_iterations, pcg_iterations, converged, residual, solve_ms)."""
+        block = min(_lib.ELAST_MAX_COLS, int(n_modes) + 2) if block is None else block
+        return self._block_solve(lambda *tail: self.lib.femo_elast_eigs(self.handle, self._mass_law(mass_law), float(density),
+                                                                        rho.handle, *tail),
+                                 n_modes, block, X, rtol, max_outer, pcg_rtol, pcg_max_it, pc)
+
+    def _block_solve(self, call, n_modes: int, block: int, X: Vec, rtol: float, max_outer: int, pcg_rtol: float,
+                     pcg_max_it: int, pc: str):
+        """The marshalling of `eigs` and `buckle`: ``call(n_modes, block, X, opts, lambda, info)`` is the library's entry point
+        behind its leading arguments.  Returns (lambda[block], info)."""
         if pc not in PRECONDITIONERS:
             raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
-        n_modes = int(n_modes)
-        block = min(_lib.ELAST_MAX_COLS, n_modes + 2) if block is None else int(block)
-        block = self._cols(block, X)
+        block = self._cols(int(block), X)
         opts = _lib.EigOpts(rtol=float(rtol), pcg_rtol=float(pcg_rtol), max_outer=int(max_outer), pcg_max_it=int(pcg_max_it),
                             pc=PRECONDITIONERS[pc], reserved=0)
         info = _lib.EigInfo()
         lam = np.zeros(_lib.ELAST_MAX_COLS)
-        check(self.lib.femo_elast_eigs(self.handle, self._mass_law(mass_law), float(density), rho.handle, n_modes, block,
-                                       X.handle, C.byref(opts), lam.ctypes.data_as(_lib.c_f64p), C.byref(info)))
+        check(call(int(n_modes), block, X.handle, C.byref(opts), lam.ctypes.data_as(_lib.c_f64p), C.byref(info)))
         return lam[:block].copy(), dict(outer_iterations=info.outer_iterations, pcg_iterations=info.pcg_iterations,
                                         converged=info.converged, residual=np.array(info.residual[:block]),
                                         solve_ms=info.solve_ms, preconditioner=pc)
@@ -363,20 +369,9 @@ class DeviceElasticity:
         vectors).  The block converges to the largest |mu| of either sign: when it fills up with negative mu (buckling under
         the reversed load) before ``n_modes`` positive ones are found, the call fails -- raise ``block``.  Returns
         (lambda[block] = 1 / mu, info) with info as that of `eigs`; ``residual`` is |(-K_G) x - mu K x| / (mu |K x|)."""
-        if pc not in PRECONDITIONERS:
-            raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
-        n_modes = int(n_modes)
-        block = _lib.ELAST_MAX_COLS if block is None else int(block)
-        block = self._cols(block, X)
-        opts = _lib.EigOpts(rtol=float(rtol), pcg_rtol=float(pcg_rtol), max_outer=int(max_outer), pcg_max_it=int(pcg_max_it),
-                            pc=PRECONDITIONERS[pc], reserved=0)
-        info = _lib.EigInfo()
-        lam = np.zeros(_lib.ELAST_MAX_COLS)
-        check(self.lib.femo_elast_buckle(self.handle, int(method), rho.handle, u.handle, n_modes, block, X.handle,
-                                         C.byref(opts), lam.ctypes.data_as(_lib.c_f64p), C.byref(info)))
-        return lam[:block].copy(), dict(outer_iterations=info.outer_iterations, pcg_iterations=info.pcg_iterations,
-                                        converged=info.converged, residual=np.array(info.residual[:block]),
-                                        solve_ms=info.solve_ms, preconditioner=pc)
+        block = _lib.ELAST_MAX_COLS if block is None else block
+        return self._block_solve(lambda *tail: self.lib.femo_elast_buckle(self.handle, int(method), rho.handle, u.handle, *tail),
+                                 n_modes, block, X, rtol, max_outer, pcg_rtol, pcg_max_it, pc)
 
     def pnorm_stress_multi(self, n_cols: int, rho: Vec, u: Vec, m, p: float, q: float, alpha: float, weights=None,
                            value: bool = True, grad_u: Optional[Vec] = None, grad_rho: Optional[Vec] = None,
@@ -1219,7 +1214,52 @@ class MultiLoadVonMises(ElasticityVonMises):
         self._setup(u, rho, V.mesh, V.n_cases, scales, None if load_case is None else int(load_case), E, nu, q)
 
 
-class ElasticityEigenvalues:
+class _BlockModes:
+    """What `ElasticityEigenvalues` and `ElasticityBuckling` share: a block of modes solved by the block iteration of
+    csrc/elast_block.hip, re-solved only when the key of its inputs changed, from the previous modes (a seeded random block
+    the first time).  A subclass names its values (``_values_name``: the key of them in ``last_info``), its record in
+    LAST_KSP_INFO (``_kind``) and its solve in the error text (``_solve_name``)."""
+
+    @staticmethod
+    def _check_block(name: str, n_modes: int, block: int):
+        if not 1 <= n_modes <= block <= _lib.ELAST_MAX_COLS:
+            raise ValueError(f"{name}: {n_modes} modes in a block of {block} (1 <= n_modes <= block <= {_lib.ELAST_MAX_COLS})")
+
+    def _setup_block(self, V: VectorFunctionSpace, n_modes: int, block: int, rtol: float, max_outer: int, seed: int):
+        self.n_modes, self.block, self.n_dof = n_modes, block, V.dim
+        self.rtol, self.pcg_rtol, self.max_outer, self.seed = float(rtol), 1e-12, max_outer, int(seed)
+        self.modes = Function(LoadCaseSpace(V, block))
+        self._lam = None
+        self._key = None
+        self._started = False
+        self.last_info = {}
+
+    def _solved_values(self, mask: np.ndarray, key: tuple, handle, solve) -> np.ndarray:
+        """The first n_modes values: cached while ``key`` and the fixed set ``mask`` stand, otherwise ``solve(handle())``, the
+        device call on the handle with K assembled, from the previous modes."""
+        key += (hash(mask.tobytes()),)
+        if key == self._key:
+            return self._lam[:self.n_modes].copy()
+        from .utils_hip import LAST_KSP_INFO
+        dev = handle()
+        if not self._started:                                          # afterwards: the previous modes
+            free = mask == 0
+            X = np.zeros((self.block, self.n_dof))
+            X[:, free] = np.random.default_rng(self.seed).standard_normal((int(free.sum()), self.block)).T
+            self.modes.vector[:] = X.ravel()
+            self._started = True
+        lam, info = solve(dev)
+        self.modes.version += 1
+        self.last_info = dict(info, **{self._values_name: lam.copy()}, n_modes=self.n_modes, block=self.block)
+        LAST_KSP_INFO.append(dict(self.last_info, kind=self._kind))
+        if info["converged"] != 1:
+            raise RuntimeError(f"elasticity {self._solve_name} solve did not converge: {info['outer_iterations']} outer steps, "
+                               f"residuals {info['residual'][:self.n_modes]} above {self.rtol:.1e}")
+        self._lam, self._key = lam, key
+        return lam[:self.n_modes].copy()
+
+
+class ElasticityEigenvalues(_BlockModes):
     """The ``n_modes`` lowest eigenpairs of K(rho) phi = lambda M(rho) phi with the supports ``bcs`` (homogeneous; at least
     one: a free-free structure needs a shift, which is out of scope), by `DeviceElasticity.eigs` in a block of ``block``
     columns (the block - n_modes last ones are guard vectors).  M is the consistent P1 mass, density ``density`` times
@@ -1252,23 +1292,18 @@ class ElasticityEigenvalues:
             raise ValueError(f"unknown preconditioner {preconditioner!r} (jacobi or multilevel)")
         n_modes = int(n_modes)
         block = min(_lib.ELAST_MAX_COLS, n_modes + 2) if block is None else int(block)
-        if not 1 <= n_modes <= block <= _lib.ELAST_MAX_COLS:
-            raise ValueError(f"{name}: {n_modes} modes in a block of {block} (1 <= n_modes <= block <= {_lib.ELAST_MAX_COLS})")
+        self._check_block(name, n_modes, block)
         mask, vals = _fixed_data(V.dim, bcs)
         if mask is None or not mask.any():
             raise NotImplementedError(f"{name}: without supports K is singular (free-free structures need a shift)")
         if np.any(vals != 0.0):
             raise NotImplementedError(f"{name}: the supports of an eigenproblem are homogeneous")
         self.rho, self.V, self.mesh, self._mask = rho, V, V.mesh, mask
-        self.n_modes, self.block, self.n_dof = n_modes, block, V.dim
         self.E, self.nu, self.method, self.method_id = float(E), float(nu), method, METHODS[method]
         self.density, self.mass_law, self.preconditioner = float(density), mass_law, preconditioner
-        self.rtol, self.pcg_rtol, self.max_outer, self.seed = float(rtol), 1e-12, 200, int(seed)
-        self.modes = Function(LoadCaseSpace(V, block))
-        self._lam = None
-        self._key = None
-        self._started = False
-        self.last_info = {}
+        self._setup_block(V, n_modes, block, rtol, 200, seed)
+
+    _values_name, _kind, _solve_name = "eigenvalues", "elasticity_eigs", "eigen"
 
     def device(self) -> DeviceElasticity:
         return elasticity_handle(self.mesh, self.E, self.nu)
@@ -1279,28 +1314,11 @@ class ElasticityEigenvalues:
 
     def eigenvalues(self) -> np.ndarray:
         """lambda_0 <= ... <= lambda_{n_modes-1} of the current density."""
-        key = (self.rho.version, id(self.rho.vec), hash(self._mask.tobytes()))
-        if key == self._key:
-            return self._lam[:self.n_modes].copy()
-        from .utils_hip import LAST_KSP_INFO
-        dev = self.stiffness()
-        if not self._started:                                          # afterwards: the previous modes
-            free = self._mask == 0
-            X = np.zeros((self.block, self.n_dof))
-            X[:, free] = np.random.default_rng(self.seed).standard_normal((int(free.sum()), self.block)).T
-            self.modes.vector[:] = X.ravel()
-            self._started = True
-        lam, info = dev.eigs(self.n_modes, self.rho.vec, self.modes.vec, block=self.block, density=self.density,
-                             mass_law=self.mass_law, rtol=self.rtol, max_outer=self.max_outer, pcg_rtol=self.pcg_rtol,
-                             pc=self.preconditioner)
-        self.modes.version += 1
-        self.last_info = dict(info, eigenvalues=lam.copy(), n_modes=self.n_modes, block=self.block)
-        LAST_KSP_INFO.append(dict(self.last_info, kind="elasticity_eigs"))
-        if info["converged"] != 1:
-            raise RuntimeError(f"elasticity eigen solve did not converge: {info['outer_iterations']} outer steps, residuals "
-                               f"{info['residual'][:self.n_modes]} above {self.rtol:.1e}")
-        self._lam, self._key = lam, key
-        return lam[:self.n_modes].copy()
+        return self._solved_values(
+            self._mask, (self.rho.version, id(self.rho.vec)), self.stiffness,
+            lambda dev: dev.eigs(self.n_modes, self.rho.vec, self.modes.vec, block=self.block, density=self.density,
+                                 mass_law=self.mass_law, rtol=self.rtol, max_outer=self.max_outer, pcg_rtol=self.pcg_rtol,
+                                 pc=self.preconditioner))
 
 
 class EigenvalueAggregate(BackendForm):
@@ -1344,7 +1362,7 @@ class EigenvalueAggregate(BackendForm):
                                    mass_law=g.mass_law)
 
 
-class ElasticityBuckling:
+class ElasticityBuckling(_BlockModes):
     """The ``n_modes`` smallest positive load factors lambda of (K(rho) + lambda K_G(u, rho)) phi = 0 on the free dofs, for the
     state u of ``residual``, an `ElasticityResidual` of one load case: the load lambda F is the linearised buckling load.
     K_G is the geometric stiffness of the cell stress sigma_e = C(rho_e) sigma_0(u_e) with the residual's own stiffness law,
@@ -1378,16 +1396,11 @@ class ElasticityBuckling:
             raise NotImplementedError(f"{name}: partitioned meshes are out of scope")
         n_modes = int(n_modes)
         block = _lib.ELAST_MAX_COLS if block is None else int(block)
-        if not 1 <= n_modes <= block <= _lib.ELAST_MAX_COLS:
-            raise ValueError(f"{name}: {n_modes} modes in a block of {block} (1 <= n_modes <= block <= {_lib.ELAST_MAX_COLS})")
+        self._check_block(name, n_modes, block)
         self.residual, self.u, self.rho, self.mesh = residual, residual.u, residual.rho, residual.mesh
-        self.n_modes, self.block, self.n_dof = n_modes, block, residual.n_dof
-        self.rtol, self.pcg_rtol, self.max_outer, self.seed = float(rtol), 1e-12, 400, int(seed)
-        self.modes = Function(LoadCaseSpace(residual.u.function_space, block))
-        self._lam = None
-        self._key = None
-        self._started = False
-        self.last_info = {}
+        self._setup_block(residual.u.function_space, n_modes, block, rtol, 400, seed)
+
+    _values_name, _kind, _solve_name = "load_factors", "elasticity_buckling", "buckling"
 
     def device(self) -> DeviceElasticity:
         return self.residual.device()
@@ -1403,29 +1416,11 @@ class ElasticityBuckling:
 
     def load_factors(self) -> np.ndarray:
         """0 < lambda_0 <= ... <= lambda_{n_modes-1} of the current density and state."""
-        mask = self._fixed_mask()
-        key = (self.rho.version, id(self.rho.vec), self.u.version, id(self.u.vec), hash(mask.tobytes()))
-        if key == self._key:
-            return self._lam[:self.n_modes].copy()
-        from .utils_hip import LAST_KSP_INFO
-        R = self.residual
-        dev = R.stiffness()                                            # the residual's K and ownership key: no assembly of our own
-        if not self._started:                                          # afterwards: the previous modes
-            free = mask == 0
-            X = np.zeros((self.block, self.n_dof))
-            X[:, free] = np.random.default_rng(self.seed).standard_normal((int(free.sum()), self.block)).T
-            self.modes.vector[:] = X.ravel()
-            self._started = True
-        lam, info = dev.buckle(self.n_modes, self.rho.vec, self.u.vec, self.modes.vec, block=self.block, method=R.method_id,
-                               rtol=self.rtol, max_outer=self.max_outer, pcg_rtol=self.pcg_rtol, pc=R.preconditioner)
-        self.modes.version += 1
-        self.last_info = dict(info, load_factors=lam.copy(), n_modes=self.n_modes, block=self.block)
-        LAST_KSP_INFO.append(dict(self.last_info, kind="elasticity_buckling"))
-        if info["converged"] != 1:
-            raise RuntimeError(f"elasticity buckling solve did not converge: {info['outer_iterations']} outer steps, residuals "
-                               f"{info['residual'][:self.n_modes]} above {self.rtol:.1e}")
-        self._lam, self._key = lam, key
-        return lam[:self.n_modes].copy()
+        R = self.residual                                              # its K and ownership key: no assembly of our own
+        return self._solved_values(
+            self._fixed_mask(), (self.rho.version, id(self.rho.vec), self.u.version, id(self.u.vec)), R.stiffness,
+            lambda dev: dev.buckle(self.n_modes, self.rho.vec, self.u.vec, self.modes.vec, block=self.block, method=R.method_id,
+                                   rtol=self.rtol, max_outer=self.max_outer, pcg_rtol=self.pcg_rtol, pc=R.preconditioner))
 
 
 class BucklingAggregate(BackendForm):

@@ -28,6 +28,7 @@ MEASURED on the MI355X (SIMP and RAMP, all meshes and both preconditioners; the 
   total dJ/drho against the restated total  1.5e-10 at the most (cube4j; 8.5e-14 with the body force); bound 1e-6
   directional central differences of J      1.9e-9 on rect24x12; bound 1e-5
   tensile load, (3, 3), 40 outer steps      all three Ritz values negative: raises "block is too small ... no positive load factor"
+  buckle, eigs, buckle on one handle        the bits of fresh handles (rect8x4, cube4j; block-Jacobi)
 """
 import functools
 
@@ -261,6 +262,46 @@ def test_buckle(gpu, name, pc, method, n_modes, block):
     for k in range(n_modes):
         assert 0.5 * res[k] <= info["residual"][k] <= 2.0 * res[k] or max(res[k], info["residual"][k]) <= 1e-13, (k, res, info)
     assert info["outer_iterations"] <= R["outer"] + max(2.0, 0.1 * R["outer"])
+
+
+@pytest.mark.parametrize("name", ["rect8x4", "cube4j"])
+def test_solves_leave_no_trace(gpu, name):
+    """`buckle` and `eigs` run through one block iteration on the handle's shared reserves (the right-hand-side block, the
+    Gram partials, the PCG work vectors): buckle (1, 3), eigs (3, 5) and buckle (1, 3) again, interleaved on one handle, give
+    the bits of the same calls on fresh handles -- lambda, the residuals, both iteration counts and the modes.  Block-Jacobi
+    only: the multilevel preconditioner adds with fp64 atomics and is not bit-repeatable.  MEASURED on the MI355X: equal bits
+    on both meshes, with the library of the commit before the two loops became one as well."""
+    from femo_amd.engine import Vec
+    from femo_amd.fea.elasticity import METHODS
+    P = problem(name, "SIMP")
+    mesh, mask = P["mesh"], P["mask"]
+
+    def handle():
+        dev, rv = _device(gpu, mesh, "SIMP", P["rho"])
+        return dev, rv, Vec(gpu, dev.n_dof).set(P["u"])
+
+    def buckle(dev, rv, uv):
+        xv = Vec(gpu, 3 * dev.n_dof).set(er.start_block(mask, 3).ravel())
+        lam, info = dev.buckle(1, rv, uv, xv, block=3, method=METHODS["SIMP"], rtol=RTOL, pcg_rtol=PCG_RTOL, pc="jacobi")
+        return lam, info, _columns(xv, 3)
+
+    def eigs(dev, rv):
+        xv = Vec(gpu, 5 * dev.n_dof).set(er.start_block(mask, 5).ravel())
+        lam, info = dev.eigs(3, rv, xv, block=5, rtol=RTOL, pcg_rtol=PCG_RTOL, pc="jacobi")
+        return lam, info, _columns(xv, 5)
+
+    fresh_buckle = buckle(*handle())
+    fresh_eigs = eigs(*handle()[:2])
+    dev, rv, uv = handle()
+    mixed = [buckle(dev, rv, uv), eigs(dev, rv), buckle(dev, rv, uv)]
+    for what, (lam, info, Phi), (lam0, info0, Phi0) in zip(("buckle", "eigs", "buckle again"), mixed,
+                                                           (fresh_buckle, fresh_eigs, fresh_buckle)):
+        print(f"{name} {what}: lambda {lam}, fresh {lam0}; outer steps {info['outer_iterations']} / {info0['outer_iterations']}, "
+              f"PCG iterations {info['pcg_iterations']} / {info0['pcg_iterations']}, modes differ by {np.abs(Phi - Phi0).max():.1e}")
+        assert info["converged"] == 1 and info0["converged"] == 1
+        assert np.array_equal(lam, lam0) and np.array_equal(info["residual"], info0["residual"])
+        assert info["outer_iterations"] == info0["outer_iterations"] and info["pcg_iterations"] == info0["pcg_iterations"]
+        assert np.array_equal(Phi, Phi0)
 
 
 def _setup(mesh, method="SIMP", pc="multilevel", body=None, sign=-1.0):
