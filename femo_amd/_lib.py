@@ -66,7 +66,10 @@ class HostStats(C.Structure):
                                          "h2d_skipped", "h2d_skipped_bytes", "h2d_as_d2d", "h2d_as_d2d_bytes",
                                          "d2h_pinned", "d2h_pinned_bytes", "d2h_staged", "d2h_staged_bytes",
                                          "d2h_async", "d2h_async_bytes", "d2h_device_sum", "d2h_device_sum_bytes",
-                                         "h2d_deferred", "h2d_deferred_bytes")]
+                                         "h2d_deferred", "h2d_deferred_bytes",
+                                         # appended with femo_mesh_head_info: a build without it leaves the field at 0 (the
+                                         # library fills the struct it knows; engine.host_stats reports the field only when bound)
+                                         "h2d_chunks")]
 
 
 # name -> (restype, argtypes); every symbol include/femo_hip.h declares
@@ -125,6 +128,7 @@ PROTOTYPES = {
     "femo_comm_model": (C.c_int, [H, C.c_int, C.c_int]),
     "femo_comm_stats": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
     "femo_mesh_pcg_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
+    "femo_mesh_head_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
     # Reissner-Mindlin shell
     "femo_shell_create": (C.c_int, [H, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(H)]),
     "femo_shell_destroy": (C.c_int, [H]),
@@ -254,7 +258,7 @@ PROTOTYPES = {
 
 # test-only entry points that an older build selected through FEMO_LIB (A/B measurements against a parent commit) may lack:
 # they stay unbound there and their wrappers raise
-OPTIONAL = frozenset({"femo_mesh_pcg_info"})
+OPTIONAL = frozenset({"femo_mesh_pcg_info", "femo_mesh_head_info"})
 
 
 class FemoError(RuntimeError):

@@ -287,6 +287,7 @@ int femo_vec_destroy(femo_vec* v) {
     hipEventSynchronize(v->h2d_ev);                    // ... or a deferred upload still writing it
     hipEventDestroy(v->h2d_ev);
   }
+  for (hipEvent_t e : v->h2d_chunk_ev) hipEventDestroy(e);   // (recorded before h2d_ev on the same stream)
   if (v->owned && v->d) {
     hipStreamSynchronize(v->ctx->stream);
     hipFree(v->d);
@@ -438,6 +439,13 @@ int femo_mesh_pc_info(const femo_mesh* m, int32_t* n_levels, int64_t* finest_nod
 int femo_mesh_pcg_info(femo_mesh* m, int64_t* out, int count) {
   FEMO_REQUIRE(m && out && count >= 0, "bad argument");
   const int64_t v[4] = {femo_pc_merged_ok(m) ? 1 : 0, m->ctx->pcg_last_ring, m->ctx->pcg_last_flushes, m->ctx->pcg_ring_short};
+  for (int k = 0; k < count && k < 4; ++k) out[k] = v[k];
+  return 0;
+}
+
+int femo_mesh_head_info(femo_mesh* m, int64_t* out, int count) {
+  FEMO_REQUIRE(m && out && count >= 0, "bad argument");
+  const int64_t v[4] = {(m->n_slices * FEMO_WAVE + FEMO_BLOCK - 1) / FEMO_BLOCK, m->head_blocks_early, m->head_streamed, m->load_builds};
   for (int k = 0; k < count && k < 4; ++k) out[k] = v[k];
   return 0;
 }
@@ -699,6 +707,19 @@ int femo_newton_rhs_linear(const femo_mat* K, const femo_vec* f, const femo_vec*
   // the product reads u' = u with the prescribed values imposed, ghost entries included: K u' = K u + K[:,bc](g - u)
   const double* x = u->d;
   if (bc != nullptr) FEMO_TRY(femo_launch_impose_bc(m, u->d, bc->d_mask, bc->d_dense, &x));
+  // A deferred upload of f that travels in chunks: the load vector and this right-hand side are formed range by range, on
+  // the rows whose cells have landed, while the rest of f is still on its way (the device has nothing else to do at the
+  // head of a cycle).  The same kernels on the same rows as below; every other case is the single launch.
+  const uint8_t* mask = bc ? bc->d_mask : nullptr;
+  const double* dense = bc ? bc->d_dense : nullptr;
+  int n_ranges = 0;
+  FEMO_TRY(femo_poisson_load_stream_begin(m, f, &n_ranges));
+  for (int k = 0; k < n_ranges; ++k) {
+    int64_t slice0 = 0, n_range = 0;
+    FEMO_TRY(femo_poisson_load_stream_range(m, f, k, &slice0, &n_range));
+    FEMO_TRY(femo_launch_newton_rhs_linear(K, x, u->d, m->d_load, mask, dense, b->d, slice0, n_range));   // (no rows: no launch)
+  }
+  if (n_ranges > 0) return 0;
   FEMO_TRY(femo_vec_await(f));          // a deferred upload of f: everything above was enqueued in front of the wait
   const double* load = nullptr;
   FEMO_TRY(femo_poisson_load_vector(m, f, &load));

@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "femo_internal.h"
+#include "head_order.h"
 
 namespace {
 
@@ -1436,10 +1437,12 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_cell_fvol(int64_t n_cell, double
 // load_i = sum over the cells around vertex i of t_c (t_c = f_c |T_c| / (D+1), formed by k_cell_fvol<0>): the walk reads
 // the 4-byte cell ids of the incidence instead of the 16-byte visit records of k_p1_row_walk<D, 2> (round 2: 1.15 ms and
 // 4.9 GB of counted traffic at C4 for 1.5 GB algorithmic)
+// The grid walks row blocks [blk0, blk0 + n_blocks): all of them (blk0 = 0), or the range that became complete with a chunk
+// of f (streamed head, below); the XCD partition applies within the range.
 __global__ __launch_bounds__(FEMO_BLOCK) void k_load_walk(int64_t n_rows, int64_t n_blocks, const int64_t* __restrict__ vptr,
                                                           const int32_t* __restrict__ visit_cell, const double* __restrict__ t,
-                                                          double* __restrict__ out) {
-  const int64_t blk = femo_xcd_block(blockIdx.x, n_blocks);
+                                                          double* __restrict__ out, int64_t blk0 = 0) {
+  const int64_t blk = blk0 + femo_xcd_block(blockIdx.x, n_blocks);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t slice = blk * (FEMO_BLOCK / 64) + wave;
   const int lane = threadIdx.x & 63;
@@ -1534,6 +1537,13 @@ static int ensure_cell_volumes(femo_mesh* m) {
   return 0;
 }
 
+// The residual K u - L of the linear form comes from the pipelined system kernel while the rows fit its strip; wider
+// meshes take the visit-record row walk (FEMO_ROW_WALK).  One predicate for femo_launch_residual and the streamed head.
+static bool residual_is_pipelined(const femo_mesh* m) {
+  const int nbr = (m->max_rowlen + 1) & ~1;
+  return nbr <= (m->tdim == 3 ? 16 : 8);
+}
+
 static int ensure_load_vector(femo_mesh* m, const double* f, uint64_t f_uid, uint64_t f_gen) {
   if (m->d_load && f_uid != 0 && m->load_uid == f_uid && m->load_gen == f_gen) return 0;
   FEMO_TRY(ensure_cell_volumes(m));
@@ -1547,6 +1557,93 @@ static int ensure_load_vector(femo_mesh* m, const double* f, uint64_t f_uid, uin
     FEMO_HIP_CHECK(hipGetLastError());
   }
   m->load_uid = f_uid; m->load_gen = f_gen;
+  ++m->load_builds;
+  return 0;
+}
+
+// maxcell[b] = the largest cell id among the visits of row block b (FEMO_BLOCK rows: slices 4b .. 4b+3), -1 without visits
+__global__ __launch_bounds__(FEMO_BLOCK) void k_block_maxcell(int64_t n_slices, const int64_t* __restrict__ vptr,
+                                                              const int32_t* __restrict__ visit_cell, int32_t* __restrict__ maxcell) {
+  __shared__ int32_t best;
+  if (threadIdx.x == 0) best = -1;
+  __syncthreads();
+  const int64_t s0 = (int64_t)blockIdx.x * (FEMO_BLOCK / 64), s1 = s0 + FEMO_BLOCK / 64 < n_slices ? s0 + FEMO_BLOCK / 64 : n_slices;
+  int32_t mine = -1;
+  for (int64_t k = vptr[s0] + threadIdx.x; k < vptr[s1]; k += FEMO_BLOCK) {
+    const int32_t c = visit_cell[k];
+    if (c >= 0 && (c >> 2) > mine) mine = c >> 2;
+  }
+  if (mine >= 0) atomicMax(&best, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) maxcell[blockIdx.x] = best;
+}
+
+// Topology only, like the visit records: built with the first streamed head of a mesh, gone with the mesh.
+static int ensure_head_order(femo_mesh* m) {
+  if (m->head_ready_built) return 0;
+  const int64_t nb = row_blocks(m);
+  std::vector<int32_t> h((size_t)nb);
+  if (nb > 0) {
+    hipStream_t st = m->ctx->stream;
+    int32_t* d = nullptr;
+    FEMO_HIP_CHECK(hipMalloc(&d, nb * sizeof(int32_t)));
+    hipLaunchKernelGGL(k_block_maxcell, dim3(nb), dim3(FEMO_BLOCK), 0, st, m->n_slices, m->d_vptr, m->d_visit_cell, d);
+    FEMO_HIP_CHECK(hipGetLastError());
+    FEMO_HIP_CHECK(hipMemcpyAsync(h.data(), d, nb * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FEMO_HIP_CHECK(hipStreamSynchronize(st));            // once per mesh
+    FEMO_HIP_CHECK(hipFree(d));
+  }
+  femo_head_running_max(h.data(), nb, m->head_ready);
+  m->head_ready_built = true;
+  return 0;
+}
+
+// The streamed head of a cycle (femo_newton_rhs_linear): while f is still arriving in chunks, the load vector is formed on
+// the rows whose cells have all landed.  femo_poisson_load_stream_begin says how many ranges there are (0: not applicable --
+// no chunked upload in flight, wrapped memory, a partitioned mesh, a mesh whose residual takes the row walk -- and nothing
+// is done: the caller takes the single launches); femo_poisson_load_stream_range(k) waits for chunk k, forms t_c on its
+// cells and walks the row blocks that became complete with it, and returns their slices so that the caller can follow
+// with whatever else is row-wise.  The same kernels on the same data as ensure_load_vector, range by range: every row's
+// arithmetic and its order are unchanged and the vector is bit-equal.  After the last range the vector is complete and
+// cached under f's (uid, generation) like any other.
+// One rank only: no measurement covers the streamed head on a partitioned mesh, so those keep the single launches.
+int femo_poisson_load_stream_begin(femo_mesh* m, const femo_vec* f, int* n_ranges) {
+  *n_ranges = 0;
+  if (row_blocks(m) == 0 || f->uid == 0 || m->n_nbr > 0 || m->ctx->nranks > 1 || !residual_is_pipelined(m)) return 0;
+  if (femo_vec_upload_chunks(f, m->head_ends) <= 1) return 0;
+  FEMO_TRY(ensure_cell_volumes(m));
+  FEMO_TRY(ensure_head_order(m));
+  if (!m->d_load) FEMO_HIP_CHECK(hipMalloc(&m->d_load, (std::max<int64_t>(m->n_slices * FEMO_WAVE, 1) + 2) * sizeof(double)));
+  m->head_c0 = 0; m->head_b0 = 0; m->head_blocks_early = 0;
+  *n_ranges = (int)m->head_ends.size();
+  return 0;
+}
+
+int femo_poisson_load_stream_range(femo_mesh* m, const femo_vec* f, int k, int64_t* slice0, int64_t* n_slices) {
+  *slice0 = 0; *n_slices = 0;
+  hipStream_t st = m->ctx->stream;
+  const int64_t nb = row_blocks(m);
+  const bool last = k + 1 == (int)m->head_ends.size();
+  const int64_t c0 = m->head_c0, b0 = m->head_b0;
+  const int64_t e = last ? m->n_cell : std::min(m->head_ends[(size_t)k], m->n_cell);
+  if (!last && e <= c0) return 0;                        // (f longer than the mesh has cells: nothing new in this chunk)
+  FEMO_TRY(femo_vec_await_prefix(f, m->head_ends[(size_t)k]));
+  if (e > c0)
+    hipLaunchKernelGGL((k_cell_fvol<0>), dim3(cell_grid(e - c0)), dim3(FEMO_BLOCK), 0, st, e - c0, 1.0 / (m->tdim + 1), f->d + c0, m->d_cellvol + c0, m->d_cell_t + c0);
+  const int64_t b1 = last ? nb : std::max(b0, femo_head_blocks_ready(m->head_ready, e));
+  if (b1 > b0) {
+    hipLaunchKernelGGL(k_load_walk, dim3(b1 - b0), dim3(FEMO_BLOCK), 0, st, m->n_rows, b1 - b0, m->d_vptr, m->d_visit_cell, m->d_cell_t, m->d_load, b0);
+    *slice0 = b0 * (FEMO_BLOCK / 64);
+    *n_slices = std::min(b1 * (FEMO_BLOCK / 64), m->n_slices) - *slice0;
+  }
+  FEMO_HIP_CHECK(hipGetLastError());
+  m->head_c0 = std::max(c0, e); m->head_b0 = b1;
+  if (!last) {
+    m->head_blocks_early = b1;
+  } else {
+    m->load_uid = f->uid; m->load_gen = f->gen;          // complete: a second call with the same f finds it
+    ++m->load_builds; ++m->head_streamed;
+  }
   return 0;
 }
 
@@ -1580,8 +1677,7 @@ int femo_launch_residual(femo_mesh* m, int pde, const double* params, const doub
   else {
     // K u - L is the Newton right-hand side without a Dirichlet set: the pipelined system kernel in its
     // rhs-only form (1.3 ms at C4 against 2.2 ms for the per-visit-gather walk below)
-    const int nbr = (m->max_rowlen + 1) & ~1;
-    if (nbr <= (m->tdim == 3 ? 16 : 8))
+    if (residual_is_pipelined(m))
       return femo_launch_system(m, pde, params, u, f, aux, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, r, f_uid, f_gen, nullptr);
     FEMO_TRY(ensure_load_vector(m, f, f_uid, f_gen));
     FEMO_TRY(ensure_visit_weights(m));               // the walk reads the visit records: this may be the mesh's first pass

@@ -184,9 +184,23 @@ struct femo_vec {
   // assembly pass, S A S and the preconditioner weights run under the upload of f)
   hipEvent_t h2d_ev = nullptr;
   bool h2d_pending = false;
+  // the upload in flight travels as h2d_chunks copies of h2d_chunk_n entries, the last one of what remains:
+  // h2d_chunk_ev[k] follows copy k < h2d_chunks - 1, h2d_ev the last.  The events stay with the vector from
+  // upload to upload.  h2d_chunks <= 1: one copy, no prefix to wait for (femo_vec_await_prefix)
+  // (the last chunk takes the remainder: the copies end at k * h2d_chunk_n, a multiple of 256 entries, and at n)
+  std::vector<hipEvent_t> h2d_chunk_ev;
+  int64_t h2d_chunk_n = 0;
+  int h2d_chunks = 0;
 };
 void femo_vec_wait_readers(femo_vec* v);   // hostmem.cpp
 extern "C" int femo_vec_await(const femo_vec* v);     // hostmem.cpp: compute stream waits for a deferred upload of v (no-op otherwise)
+// hostmem.cpp: the compute stream waits until entries [0, n_entries) of a chunked deferred upload of v have landed -- the
+// event of the chunk that holds entry n_entries - 1.  The upload stays pending unless that chunk is the last; without
+// chunk events this is femo_vec_await.
+extern "C" int femo_vec_await_prefix(const femo_vec* v, int64_t n_entries);
+// entries [0, ends[k]) have landed after chunk k of the upload of v in flight; returns the number of chunks (0: none in
+// flight, or a single copy)
+int femo_vec_upload_chunks(const femo_vec* v, std::vector<int64_t>& ends);
 inline void femo_vec_touch(femo_vec* v) {
   if (!v) return;
   ++v->gen;
@@ -261,6 +275,16 @@ struct femo_mesh {
   double* d_load = nullptr;      // load vector of the Poisson residual for the f identified by (load_uid, load_gen)
   double* d_zero_load = nullptr; // zeros of the same length (deferred-upload path of femo_launch_system)
   uint64_t load_uid = 0, load_gen = 0;
+  // streamed head (femo_newton_rhs_linear under a chunked upload of f): head_ready[b] = the largest cell id that row
+  // blocks 0..b visit (running maximum, -1 before the first visit; topology only, built with the first streamed head), so
+  // that the row blocks complete once cells [0, e) have landed are the prefix [0, femo_head_blocks_ready(head_ready, e))
+  std::vector<int64_t> head_ready;
+  bool head_ready_built = false;
+  std::vector<int64_t> head_ends;          // the streamed head in progress: chunk ends of f, cells and row blocks done so far
+  int64_t head_c0 = 0, head_b0 = 0;
+  // test queries (femo_mesh_head_info): load vectors formed on this mesh, streamed heads among them, and the row blocks
+  // the last streamed head walked before its last range
+  int64_t load_builds = 0, head_streamed = 0, head_blocks_early = 0;
   int pcg_last_iters = 0, pcg_prev_iters = 0;   // iterations of the last two converged BPX-PCG solves on this mesh (size the first batch)
   double pcg_rate = 0.0;                        // ln(gamma_0 / gamma_end) / iterations of the last converged merged BPX-PCG solve with >= 4 iterations
   struct femo_mat* mass = nullptr;  // P1 mass matrix on the operator pattern (geometry only; built on first use): dJ/du = M (u - u_d)
@@ -545,9 +569,14 @@ int femo_mat_ensure_s(femo_mat* A);                        // S = diag^-1/2 of t
 int femo_mat_ensure_scaled(femo_mat* A, bool transpose);   // ... and S A S (or S A^T S)
 // y = K x - load outside the Dirichlet set, u - bcval on it (bcmask null: no set), one launch (spmv.hip); its two inputs
 // besides the operator: the cached load vector of f, and u with the prescribed values imposed (assemble.hip)
+// (n_range >= 0: the rows of slices [slice0, slice0 + n_range) only -- a range of the streamed head)
 int femo_launch_newton_rhs_linear(const femo_mat* K, const double* x, const double* u, const double* load,
-                                  const uint8_t* bcmask, const double* bcval, double* y);
+                                  const uint8_t* bcmask, const double* bcval, double* y, int64_t slice0 = 0, int64_t n_range = -1);
 int femo_poisson_load_vector(femo_mesh* m, const femo_vec* f, const double** load);
+// the same vector formed range by range under a chunked upload of f (assemble.hip): _begin gives the number of ranges
+// (0: not applicable, nothing done), _range(k) forms range k and returns the slices whose rows became complete with it
+int femo_poisson_load_stream_begin(femo_mesh* m, const femo_vec* f, int* n_ranges);
+int femo_poisson_load_stream_range(femo_mesh* m, const femo_vec* f, int k, int64_t* slice0, int64_t* n_slices);
 int femo_launch_impose_bc(femo_mesh* m, const double* u, const uint8_t* bcmask, const double* bcval, const double** ubc);
 int femo_spmv_grid(const femo_mesh* m);
 int femo_halo_exchange_on(femo_mesh* m, femo_vec* x, hipStream_t st);

@@ -203,6 +203,21 @@ HostBlock* find_block(const void* p, size_t bytes) {     // g_mu held
 
 bool verify_enabled() { return getenv("FEMO_HOST_VERIFY") != nullptr; }
 
+// Entries per chunk of a deferred upload (femo_vec_set_host_deferred), a multiple of 256; 0: one copy.  FEMO_H2D_CHUNK_MB
+// in MiB, fractions allowed (the tests cut an 8 MB array into 1 MiB pieces); read once per upload, never per chunk.
+constexpr double H2D_CHUNK_MB_DEFAULT = 64.0;             // the best of 16 / 32 / 64 at n = 215 (DESIGN_LOG.md R16)
+int64_t h2d_chunk_entries() {
+  double mb = H2D_CHUNK_MB_DEFAULT;
+  if (const char* e = getenv("FEMO_H2D_CHUNK_MB")) {
+    char* end = nullptr;
+    const double v = strtod(e, &end);
+    if (end != e && v >= 0.0 && v <= 65536.0) mb = v;
+  }
+  if (mb == 0.0) return 0;
+  const int64_t n = (int64_t)(mb * 1048576.0 / sizeof(double)) / 256 * 256;
+  return std::max<int64_t>(n, 256);
+}
+
 // events of blocks that left the registry, kept for the next block that needs one
 std::vector<hipEvent_t> g_ev_free;
 
@@ -662,6 +677,17 @@ int femo_vec_set_host_deferred(femo_vec* v, const double* host, int64_t n) {
   FEMO_TRY(ensure_copy_stream(c));
   femo_vec_touch(v);                                     // earlier copy-outs / uploads of v first; new generation
   if (v->h2d_ev == nullptr) FEMO_HIP_CHECK(hipEventCreateWithFlags(&v->h2d_ev, hipEventDisableTiming));
+  // The copy travels in chunks, each followed by an event of its own, so that a reader which needs only a prefix of v can
+  // start on it (femo_vec_await_prefix: the streamed head of femo_newton_rhs_linear).  The last chunk's event is h2d_ev:
+  // femo_vec_await, the block's `ready` event and the provenance below see one upload that is over when all of it is.
+  int64_t chunk_n = h2d_chunk_entries();
+  if (chunk_n > 0) chunk_n = std::max(chunk_n, ((n + 1023) / 1024 + 255) / 256 * 256);   // at most 1024 chunks
+  const int n_chunks = chunk_n > 0 ? (int)((n + chunk_n - 1) / chunk_n) : 1;
+  while ((int)v->h2d_chunk_ev.size() < n_chunks - 1) {   // kept with the vector: none is created in a warmed-up cycle
+    hipEvent_t e = nullptr;
+    FEMO_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    v->h2d_chunk_ev.push_back(e);
+  }
   hipEvent_t ready = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -672,13 +698,19 @@ int femo_vec_set_host_deferred(femo_vec* v, const double* host, int64_t n) {
   FEMO_REQUIRE(ready != nullptr, "could not create an event");
   FEMO_HIP_CHECK(hipEventRecord(c->ev_copy, c->stream));           // kernels enqueued so far may still read v
   FEMO_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, c->ev_copy, 0));
-  FEMO_HIP_CHECK(hipMemcpyAsync(v->d, host, n * sizeof(double), hipMemcpyHostToDevice, c->copy_stream));
+  for (int k = 0; k < n_chunks; ++k) {
+    const int64_t lo = k * chunk_n, hi = k == n_chunks - 1 ? n : lo + chunk_n;
+    FEMO_HIP_CHECK(hipMemcpyAsync(v->d + lo, host + lo, (hi - lo) * sizeof(double), hipMemcpyHostToDevice, c->copy_stream));
+    if (k < n_chunks - 1) FEMO_HIP_CHECK(hipEventRecord(v->h2d_chunk_ev[k], c->copy_stream));
+  }
   FEMO_HIP_CHECK(hipEventRecord(ready, c->copy_stream));
   FEMO_HIP_CHECK(hipEventRecord(v->h2d_ev, c->copy_stream));
+  v->h2d_chunks = n_chunks; v->h2d_chunk_n = n_chunks > 1 ? chunk_n : 0;
   v->h2d_pending = true;
   std::lock_guard<std::mutex> lk(g_mu);
   ++g_stats.h2d_pinned; g_stats.h2d_pinned_bytes += n * 8;
   ++g_stats.h2d_deferred; g_stats.h2d_deferred_bytes += n * 8;
+  g_stats.h2d_chunks += n_chunks;
   if (HostBlock* b = find_block(host, (size_t)n * sizeof(double))) {
     b->pending = true; b->pend_ctx = c;
     if (v->uid != 0) { b->src_uid = v->uid; b->src_gen = v->gen; b->src_n = n; b->src_scale = 1.0; }
@@ -691,6 +723,15 @@ int femo_vec_await(const femo_vec* v_) {
   if (!v || !v->h2d_pending) return 0;
   v->h2d_pending = false;
   FEMO_HIP_CHECK(hipStreamWaitEvent(v->ctx->stream, v->h2d_ev, 0));
+  return 0;
+}
+
+int femo_vec_await_prefix(const femo_vec* v_, int64_t n_entries) {
+  femo_vec* v = const_cast<femo_vec*>(v_);
+  if (!v || !v->h2d_pending || n_entries <= 0) return 0;
+  const int64_t k = v->h2d_chunks > 1 ? (n_entries - 1) / v->h2d_chunk_n : 0;
+  if (k >= v->h2d_chunks - 1) return femo_vec_await(v);  // the last chunk, or a single copy: all of it
+  FEMO_HIP_CHECK(hipStreamWaitEvent(v->ctx->stream, v->h2d_chunk_ev[(size_t)k], 0));
   return 0;
 }
 
@@ -807,3 +848,10 @@ int femo_host_sync(void) {
 }
 
 }  // extern "C"
+
+int femo_vec_upload_chunks(const femo_vec* v, std::vector<int64_t>& ends) {
+  ends.clear();
+  if (!v || !v->h2d_pending || v->h2d_chunks <= 1) return 0;
+  for (int k = 0; k < v->h2d_chunks; ++k) ends.push_back(k == v->h2d_chunks - 1 ? v->n : (k + 1) * v->h2d_chunk_n);
+  return v->h2d_chunks;
+}

@@ -339,13 +339,14 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_spmv_sell_rhs(
     const int32_t* __restrict__ cols, const int16_t* __restrict__ cols16, const int32_t* __restrict__ sdelta, int sdelta_stride,
     const double* __restrict__ vals, const double* __restrict__ diag, const double* __restrict__ x,
     const double* __restrict__ u, const double* __restrict__ load, const uint8_t* __restrict__ bcmask,
-    const double* __restrict__ bcval, double* __restrict__ y) {
+    const double* __restrict__ bcval, double* __restrict__ y, int64_t slice0) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int xcd = blockIdx.x & 7;                    // (XCD-aware walk: see k_spmv_sell)
   const int64_t blk_in_xcd = blockIdx.x >> 3;
   const int64_t waves_per_xcd = (int64_t)(gridDim.x >> 3) * (FEMO_BLOCK / 64);
-  const int64_t s_lo = n_slices * xcd / 8, s_hi = n_slices * (xcd + 1) / 8;
+  // the n_slices slices from slice0 on: all of them, or a range of the streamed head (the XCD eighths are those of the range)
+  const int64_t s_lo = slice0 + n_slices * xcd / 8, s_hi = slice0 + n_slices * (xcd + 1) / 8;
   for (int64_t slice = s_lo + blk_in_xcd * (FEMO_BLOCK / 64) + wave; slice < s_hi; slice += waves_per_xcd) {
     const int64_t base = mptr[slice];
     const int npair = (int)((mptr[slice + 1] - base) >> 7);
@@ -634,12 +635,15 @@ int femo_launch_spmv(const femo_mat* A, const double* vals, const double* x, dou
 }
 
 int femo_launch_newton_rhs_linear(const femo_mat* K, const double* x, const double* u, const double* load,
-                                  const uint8_t* bcmask, const double* bcval, double* y) {
+                                  const uint8_t* bcmask, const double* bcval, double* y, int64_t slice0, int64_t n_range) {
   const femo_mesh* m = K->mesh;
-  if (m->n_slices == 0) return 0;
-  const int64_t g = femo_spmv_grid(m);
+  const int64_t n_walk = n_range >= 0 ? n_range : m->n_slices;
+  if (n_walk == 0) return 0;                          // (ranges of zero rows launch nothing)
+  FEMO_REQUIRE(slice0 >= 0 && slice0 + n_walk <= m->n_slices, "slice range [%lld, %lld) outside the mesh's %lld slices",
+               (long long)slice0, (long long)(slice0 + n_walk), (long long)m->n_slices);
+  const int64_t g = n_range >= 0 ? subset_grid(m, n_walk) : femo_spmv_grid(m);
   const bool nt = matrix_streams(m);
-#define FEMO_RHS_ARGS m->n_rows, m->n_slices, m->d_mptr, m->d_cols, m->d_cols16, m->d_sdelta, m->sdelta_stride, K->d_vals, K->d_diag, x, u, load, bcmask, bcval, y
+#define FEMO_RHS_ARGS m->n_rows, n_walk, m->d_mptr, m->d_cols, m->d_cols16, m->d_sdelta, m->sdelta_stride, K->d_vals, K->d_diag, x, u, load, bcmask, bcval, y, slice0
   if (nt) hipLaunchKernelGGL((k_spmv_sell_rhs<true>), dim3(g), dim3(FEMO_BLOCK), 0, m->ctx->stream, FEMO_RHS_ARGS);
   else hipLaunchKernelGGL((k_spmv_sell_rhs<false>), dim3(g), dim3(FEMO_BLOCK), 0, m->ctx->stream, FEMO_RHS_ARGS);
 #undef FEMO_RHS_ARGS

@@ -280,7 +280,10 @@ def host_stats(reset: bool = False) -> Dict[str, int]:
     check(lib.femo_host_get_stats(C.byref(st)))
     if reset:
         check(lib.femo_host_reset_stats())
-    return {k: int(getattr(st, k)) for k, _ in _lib.HostStats._fields_}
+    out = {k: int(getattr(st, k)) for k, _ in _lib.HostStats._fields_}
+    if not hasattr(lib, "femo_mesh_head_info"):        # a build from before the chunked upload: its struct ends earlier
+        del out["h2d_chunks"]
+    return out
 
 
 class EmuGroup:
@@ -583,6 +586,14 @@ class DeviceMesh:
         v = (C.c_int64 * 4)()
         check(self.lib.femo_mesh_pcg_info(self.handle, v, 4))
         return {"merged": bool(v[0]), "ring_slots": int(v[1]), "flushes": int(v[2]), "ring_short": int(v[3])}
+
+    def head_info(self):
+        """What the load vector of the Poisson forms did on this mesh: streamed heads and their ranges (femo_hip_test.h)."""
+        if not hasattr(self.lib, "femo_mesh_head_info"):
+            raise FemoError("femo_mesh_head_info: not exported by this build of libfemo_hip.so")
+        v = (C.c_int64 * 4)()
+        check(self.lib.femo_mesh_head_info(self.handle, v, 4))
+        return {"row_blocks": int(v[0]), "blocks_early": int(v[1]), "streamed": int(v[2]), "load_builds": int(v[3])}
 
     def set_halo(self, nbr, send_ptr, send_idx, recv_ptr) -> None:
         nbr = _i32(nbr)

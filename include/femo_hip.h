@@ -191,6 +191,7 @@ typedef struct femo_host_stats {
   int64_t d2h_async, d2h_async_bytes;       /* femo_vec_get_host_async                   */
   int64_t d2h_device_sum, d2h_device_sum_bytes; /* accumulate formed on the device      */
   int64_t h2d_deferred, h2d_deferred_bytes; /* of the h2d_pinned ones: femo_vec_set_host_deferred, on the copy stream */
+  int64_t h2d_chunks;                       /* copies those travelled as (FEMO_H2D_CHUNK_MB; one per upload when it is 0) */
 } femo_host_stats;
 int femo_host_alloc(int64_t bytes, void** out);
 int femo_host_free(void* p);

@@ -41,6 +41,17 @@ int femo_comm_model(femo_ctx* ctx, int rank, int nranks);
  * Entries beyond `count` are not written.                                                                   */
 int femo_mesh_pcg_info(femo_mesh* mesh, int64_t* out, int count);
 
+/* ---- streamed head: what the load vector of the Poisson forms did on this mesh (tests) --------------------
+ * Under a deferred upload of f that travels in chunks (FEMO_H2D_CHUNK_MB) the first Newton right-hand side of a cycle
+ * forms the load vector and K u' - L range by range, on the row blocks (256 rows) whose cells have landed.
+ * out[0] = row blocks of the mesh;
+ * out[1] = row blocks the last streamed head walked BEFORE the range of its last chunk;
+ * out[2] = streamed heads on this mesh so far;
+ * out[3] = load vectors formed on this mesh so far, streamed or in one launch (a cached one is not formed again).
+ * Entries beyond `count` are not written.  A library that exports this entry point also fills the h2d_chunks
+ * field at the end of femo_host_stats.                                                                      */
+int femo_mesh_head_info(femo_mesh* mesh, int64_t* out, int count);
+
 #ifdef __cplusplus
 }
 #endif
