@@ -1,7 +1,8 @@
 // Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product and PCG), elast_pc.hip
 // (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, elast_block.hip
 // (block linear algebra and the block iteration of the eigen solves), elast_eig.hip (mass product and the eigenfrequency
-// pencil) and elast_buckle.hip (geometric stiffness and the buckling pencil).  Not part of the ABI.
+// pencil), elast_buckle.hip (geometric stiffness and the buckling pencil) and elast_harm.hip (assembled mass, shifted
+// product and MINRES of the harmonic response).  Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -47,6 +48,15 @@ struct femo_elast {
   // (d (d+1) / 2 components of n_cell entries: the diagonal first, then 01[, 02, 12])
   double* w_gstress = nullptr;
   bool has_gstress = false;
+  // harmonic response (elast_harm.hip), on first use: the scalar mass matrix on the SELL pattern (sell_entries values in the
+  // slots of K, n_rows diagonal values); the three extra vectors of the MINRES loop (r1, w1, w2, w_harm_cols columns each), its
+  // scalars per column and their pinned mirror
+  double *d_mvals = nullptr, *d_mdiag = nullptr;
+  bool mass_assembled = false;
+  double* w_harm = nullptr;
+  int w_harm_cols = 0;
+  double* w_ms = nullptr;
+  double* h_ms = nullptr;       // pinned
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
   femo_elast_pc* pc = nullptr;
   bool pc_dirty = true;
@@ -99,6 +109,8 @@ int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const doub
                     double* part, int64_t part_stride, const int32_t* done);
 // PCG work vectors for at least n_cols columns.  who: the entry point, for the error text.
 int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who);
+// The first guess of a Krylov loop for n_cols columns (k_pcg_start_x): x = 0 with zero_guess, and x = b on the fixed dofs.
+int femo_elast_start_x(femo_elast* e, int n_cols, int zero_guess, const double* b, double* x);
 // The batched PCG of femo_elast_solve_multi for a caller that has checked its arguments (the eigen solve): info: n_cols
 // records, or null.
 int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
@@ -257,6 +269,12 @@ __device__ __forceinline__ double cell_von_mises(const double (&g)[D + 1][D], co
       ss += t * t;
     }
   return sqrt(1.5 * ss);
+}
+
+// SELL slot of the entry (a, b), b != a, of a visit: visit_slots packs the slots of the cell's other vertices, 8 bits each
+__device__ __forceinline__ int slot_pos(uint32_t slots, int a, int b) {
+  const int j = b - (b > a ? 1 : 0);
+  return (int)((slots >> (8 * j)) & 0xFFu);
 }
 
 __device__ __forceinline__ double penal(int method, double r) {

@@ -343,6 +343,14 @@ int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, co
   return pcg_solve(e, n_cols, b, x, opts, info, who);
 }
 
+int femo_elast_start_x(femo_elast* e, int n_cols, int zero_guess, const double* b, double* x) {
+  const int64_t n = e->mesh->n_vert * e->d;
+  hipLaunchKernelGGL(k_pcg_start_x, dim3(grid_of(n), (unsigned)n_cols), dim3(EB), 0, e->mesh->ctx->stream, n, zero_guess,
+                     e->has_fixed ? e->d_fixed : nullptr, b, x);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who) {
   if (e->w_cols >= n_cols) return 0;
   femo_mesh* m = e->mesh;

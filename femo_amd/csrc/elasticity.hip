@@ -27,11 +27,6 @@ struct femo_filter {
 
 namespace {
 
-__device__ __forceinline__ int slot_pos(uint32_t slots, int a, int b) {
-  const int j = b - (b > a ? 1 : 0);
-  return (int)((slots >> (8 * j)) & 0xFFu);
-}
-
 // ----------------------------------------------------------------------------------------------- assembly ----
 template <int D>
 __global__ __launch_bounds__(EB) void k_elast_assemble(
@@ -488,6 +483,8 @@ int femo_elast_destroy(femo_elast* e) {
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
   hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_smpart);
   hipFree(e->w_eig); hipFree(e->w_gram); hipFree(e->w_gstress);
+  hipFree(e->d_mvals); hipFree(e->d_mdiag); hipFree(e->w_harm); hipFree(e->w_ms);
+  if (e->h_ms) hipHostFree(e->h_ms);
   if (e->h_gram) hipHostFree(e->h_gram);
   if (e->h_flag) hipHostFree(e->h_flag);
   if (e->h_s) hipHostFree(e->h_s);

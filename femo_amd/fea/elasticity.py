@@ -1,7 +1,7 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
 product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip,
-buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip).  One load case is the L = 1 case of several:
+buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip, the harmonic response in csrc/elast_harm.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
@@ -53,6 +53,14 @@ are used unchanged.
                        scalar output of (u, rho): dJ/du and dJ/drho are one launch each, and the framework's adjoint solve
                        K w = dJ/du does the rest.  dJ/du is non-zero on clamped dofs: the exact reduced gradient needs
                        ``fea.consistent_bc_partials = True``
+  HarmonicElasticityResidual  the undamped harmonic response (K(rho) - omega_l^2 M(rho)) u_l = F_l in real arithmetic: one
+                       K, one consistent mass M (that of `ElasticityEigenvalues`, assembled once per density as a scalar matrix
+                       on the pattern of K), one fixed set; column l of a Function(LoadCaseSpace(V, L)) carries its own
+                       frequency omega_l and its own load -- a frequency sweep is one state.  State, adjoint and forward-mode
+                       solves are each ONE batched preconditioned MINRES (csrc/elast_harm.hip): above the first resonance the
+                       matrix is indefinite, where PCG breaks down.  Not in the reference's script
+  DynamicCompliance    J = sum_l w_l |F_l . u_l| (Ma, Kikuchi & Cheng 1995; Olhoff & Du 2005), or sum_l w_l (F_l . u_l)^2, of a
+                       harmonic state: the usual companion of an eigenfrequency constraint
 
 P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
 """
@@ -372,6 +380,55 @@ class DeviceElasticity:
         block = _lib.ELAST_MAX_COLS if block is None else block
         return self._block_solve(lambda *tail: self.lib.femo_elast_buckle(self.handle, int(method), rho.handle, u.handle, *tail),
                                  n_modes, block, X, rtol, max_outer, pcg_rtol, pcg_max_it, pc)
+
+    # ---- harmonic response: (K - sigma_l M(rho)) u_l = F_l, sigma_l = omega_l^2 (csrc/elast_harm.hip) ----
+    def _per_column(self, who: str, what: str, n_cols: int, values) -> np.ndarray:
+        a = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        if a.size != n_cols:
+            raise _lib.FemoError(f"{who}: {n_cols} columns need as many {what}")
+        return a
+
+    def mass_assemble(self, rho: Vec, density: float = 1.0, mass_law: str = "linear") -> None:
+        """M(rho) = density sum_e m(rho_e) M0_e as a scalar matrix on the pattern of K (one double per entry, one per row);
+        `dyn_apply_multi` and `dyn_solve_multi` read it."""
+        check(self.lib.femo_elast_mass_assemble(self.handle, self._mass_law(mass_law), float(density), rho.handle))
+
+    def dyn_apply_multi(self, n_cols: int, shifts, x: Vec, y: Vec, masked: bool = False, a: float = 1.0, b: float = 0.0,
+                        f: Optional[Vec] = None) -> Vec:
+        """y_l = a (K - shifts[l] M) x_l + b f_l with the assembled K and M in one pass over the pattern (or with identity rows
+        and columns on the fixed dofs when ``masked``); shifts[l] = 0 gives the bits of `apply_multi`."""
+        n_cols = self._cols(n_cols, x, y, f)
+        sv = self._per_column("dyn_apply_multi", "shifts", n_cols, shifts)
+        check(self.lib.femo_elast_dyn_apply_multi(self.handle, int(bool(masked)), n_cols, sv.ctypes.data_as(_lib.c_f64p),
+                                                  float(a), x.handle, float(b), None if f is None else f.handle, y.handle))
+        return y
+
+    def dyn_solve_multi(self, n_cols: int, shifts, b: Vec, x: Vec, rtol: float = 1e-12, atol: float = 0.0,
+                        max_it: int = 1_000_000, check_every: Optional[int] = None, zero_guess: bool = True,
+                        pc: str = "jacobi") -> list:
+        """(K - shifts[l] M) x_l = b_l for ``n_cols`` right-hand sides in one batched MINRES with the preconditioner of
+        `solve_multi` (built from the unshifted K); one `SolveInfo` per column: ``converged`` 1, 0 (max_it) or -1 (a
+        non-finite value), ``residual_norm`` the recurrence's estimate of sqrt(r . M^-1 r), ``rhs_norm`` that of the first
+        residual.  A finished column is frozen while the others go on."""
+        opts = self._solver_opts(rtol, atol, max_it, check_every, zero_guess, pc)
+        n_cols = self._cols(n_cols, b, x)
+        sv = self._per_column("dyn_solve_multi", "shifts", n_cols, shifts)
+        info = (_lib.SolveInfo * _lib.ELAST_MAX_COLS)()
+        check(self.lib.femo_elast_dyn_solve_multi(self.handle, n_cols, sv.ctypes.data_as(_lib.c_f64p), b.handle, x.handle,
+                                                  C.byref(opts), info))
+        return [info[l] for l in range(n_cols)]
+
+    def mass_drho_multi(self, transpose: bool, n_cols: int, scales, rho: Vec, u: Vec, x: Vec, y: Vec, density: float = 1.0,
+                        mass_law: str = "linear", accumulate: bool = False) -> Vec:
+        """transpose: y[n_cell] (+)= sum_l scales[l] density m'(rho) x_l^T M0 u_l; otherwise column l of y (+)= scales[l] times
+        the forward product of the cell vector x with u_l.  With scales = -shifts and ``accumulate`` on top of `drho_multi` it
+        is dR/drho of the harmonic residual."""
+        n_cols = self._cols(n_cols, u, x if transpose else y)
+        sv = self._per_column("mass_drho_multi", "scales", n_cols, scales)
+        check(self.lib.femo_elast_mass_drho_multi(self.handle, self._mass_law(mass_law), float(density), int(bool(transpose)),
+                                                  n_cols, sv.ctypes.data_as(_lib.c_f64p), rho.handle, u.handle, x.handle,
+                                                  y.handle, int(bool(accumulate))))
+        return y
 
     def pnorm_stress_multi(self, n_cols: int, rho: Vec, u: Vec, m, p: float, q: float, alpha: float, weights=None,
                            value: bool = True, grad_u: Optional[Vec] = None, grad_rho: Optional[Vec] = None,
@@ -1467,6 +1524,218 @@ class BucklingAggregate(BackendForm):
         return dev.buckle_drho(method, b.n_modes, self.rho.vec, self.u.vec, b.modes.vec, c * lam, c * lam * lam, out)
 
 
+# ------------------------------------------------------------------------------------------- harmonic response ----
+def _host_mass(mesh, rho: np.ndarray, mass_law: str, density: float):
+    """M(rho) as a SciPy CSR matrix (host copy; tests and debugging)."""
+    import scipy.sparse as sp
+    d, nv = mesh.tdim, mesh.tdim + 1
+    m = rho if mass_law == "linear" else np.where(rho >= 0.1, rho, 6e5 * rho ** 6 - 5e6 * rho ** 7)
+    w = density * m * cell_volumes(mesh) / ((d + 1) * (d + 2))
+    S = (np.ones((nv, nv)) + np.eye(nv))[None, :, :] * w[:, None, None]
+    Ms = sp.csr_matrix((S.ravel(), (np.repeat(mesh.conn, nv, axis=1).ravel(), np.tile(mesh.conn, (1, nv)).ravel())),
+                       shape=(mesh.n_vert, mesh.n_vert))
+    return sp.kron(Ms, sp.identity(d), format="csr")
+
+
+class HarmonicElasticityMatrix(MultiLoadElasticityMatrix):
+    """dR/du of a `HarmonicElasticityResidual`: K(rho) - omega_l^2 M(rho) on column l, symmetric; with ``masked`` identity
+    rows / columns on the fixed dofs.  One `mult` is one fused product over all columns, one `backend_solve` one batched
+    MINRES."""
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        dev = F.dynamic()
+        return dev.dyn_apply_multi(F.n_cases, F.shifts, x, y, masked=self.masked and dev.fixed_key is not None)
+
+    multTranspose = mult
+
+    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        o = options or {}
+        F = self.form
+        infos = F.dynamic().dyn_solve_multi(F.n_cases, F.shifts, b, x, rtol=o.get("elast_rtol", F.rtol),
+                                            max_it=o.get("elast_max_it", F.max_it), pc=F.preconditioner)
+        self.info = F._record(infos, "adjoint")
+
+    def to_scipy(self):
+        import scipy.sparse as sp
+        F = self.form
+        K = F.dynamic().export_csr()
+        M = _host_mass(F.mesh, np.array(F.rho.vec.get(), dtype=np.float64), F.mass_law, F.density)
+        blocks = []
+        for sg in F.shifts:
+            S = (K - sg * M).tocsr()
+            if self.masked and F._mask is not None:
+                free = sp.diags((F._mask == 0).astype(np.float64))
+                S = (free @ S @ free + sp.diags(F._mask.astype(np.float64))).tocsr()
+            blocks.append(S)
+        return sp.block_diag(blocks, format="csr")
+
+
+class _HarmonicDrho(_ElasticityDrho):
+    """dR/drho of a `HarmonicElasticityResidual`: block l of column e = C'(rho_e) K0_e u_{l,e} - omega_l^2 density m'(rho_e)
+    M0_e u_{l,e}; the mass term is one launch for all columns, added onto the stiffness term."""
+
+    def _mass(self, transpose: bool, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        return F.device().mass_drho_multi(transpose, F.n_cases, -F.shifts, F.rho.vec, F.u.vec, x, y, density=F.density,
+                                          mass_law=F.mass_law, accumulate=True)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        return self._mass(False, x, super().mult(x, y))
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        return self._mass(True, x, super().multTranspose(x, y))
+
+
+class HarmonicElasticityResidual(MultiLoadElasticityResidual):
+    """Column l of the residual is (K(rho) - omega_l^2 M(rho)) u_l - F_l: the undamped response to the time-harmonic load
+    F_l cos(omega_l t), in real arithmetic.  ``u`` is a Function(LoadCaseSpace(V, L)); ``omegas``: one angular frequency
+    >= 0 per column (a frequency sweep under one load repeats the traction); M = ``density`` sum_e m(rho_e) M0_e is the
+    consistent P1 mass of `ElasticityEigenvalues` with ``mass_law`` "linear" or "du_olhoff".  One K, one M, one fixed set
+    and one preconditioner (block-Jacobi or multilevel, of the unshifted K) serve all columns.
+
+    A `MultiLoadElasticityResidual` in everything else: the state solve, the adjoint solve and the forward-mode solve are
+    each ONE batched MINRES (`DeviceElasticity.dyn_solve_multi`) -- K - omega^2 M is indefinite above the first resonance,
+    where PCG breaks down -- and dR/drho = C'(rho) K0 u - omega^2 density m'(rho) M0 u.  M is reassembled only when the density
+    (its version or its vector), ``density`` or ``mass_law`` changed.  ``rtol`` is 1e-12, not the 1e-15 of the PCG forms:
+    MINRES stops on a recurrence estimate of the residual, which parts from the true residual near eps cond; ``max_it``
+    bounds the iterations of a solve.  A column that does not converge raises, naming the column and its omega.  Close to a resonance the iteration count grows and
+    the response is large: keep the frequencies away from the eigenfrequencies of the design (`ElasticityEigenvalues`).
+
+    Out of scope: damping (complex arithmetic), shifted or deflated preconditioners, frequency-band integrals, body forces,
+    inhomogeneous supports, partitioned meshes."""
+    matrix_class = HarmonicElasticityMatrix
+
+    def __init__(self, u: Function, rho: Function, tractions, measures=None, omegas=None, density: float = 1.0,
+                 mass_law: str = "linear", E: float = 1.0, nu: float = 0.3, method: str = "SIMP",
+                 preconditioner: str = "jacobi", body_forces=None):
+        name = "HarmonicElasticityResidual"
+        if body_forces is not None:
+            raise NotImplementedError(f"{name}: body forces are out of scope")
+        if any(t is None for t in list(tractions)):
+            raise ValueError(f"{name}: every column needs a traction (body forces are out of scope)")
+        V, ts, dss, _ = _multi_arguments(name, u, tractions, measures)
+        if omegas is None:
+            raise ValueError(f"{name}: one angular frequency per column (omegas)")
+        om = _per_case(name, "frequencies omega", omegas, V.n_cases)
+        if not np.all(np.isfinite(om)) or np.any(om < 0.0):
+            raise ValueError(f"{name}: the frequencies omega must be finite and >= 0")
+        if mass_law not in MASS_LAWS:
+            raise ValueError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
+        if not (np.isfinite(density) and density >= 0.0):
+            raise ValueError(f"{name}: the mass density must be finite and >= 0")
+        self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner, None)
+        self.omegas, self.shifts = om, om * om
+        self.density, self.mass_law = float(density), mass_law
+        self.rtol, self.max_it = 1e-12, 1_000_000
+        self.solve_counts = {"state": 0, "adjoint": 0}
+
+    def _set_bcs(self, bcs) -> None:
+        super()._set_bcs(bcs)
+        if self._mask is not None and np.any(self._vals[self._mask == 1] != 0.0):
+            raise NotImplementedError("HarmonicElasticityResidual: inhomogeneous supports are out of scope")
+
+    def dynamic(self) -> DeviceElasticity:
+        """`stiffness()` with M(rho) of the current density as well: reassembled when the density (its version or its
+        vector), the mass density or the mass law changed since the last mass assembly on this handle."""
+        dev = self.stiffness()
+        key = (self.rho.version, id(self.rho.vec), self.density, self.mass_law)
+        if getattr(dev, "_mass_owner", None) != key:
+            dev.mass_assemble(self.rho.vec, density=self.density, mass_law=self.mass_law)
+            dev._mass_owner = key
+        return dev
+
+    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
+        """Column l: (K - omega_l^2 M) u_l - F_l; one launch for all columns (femo_elast_dyn_apply_multi)."""
+        if out is None:
+            if self._res is None:
+                self._res = Vec(_ctx(), self.n_cases * self.n_dof)
+            out = self._res
+        return self.dynamic().dyn_apply_multi(self.n_cases, self.shifts, self.u.vec, out, a=1.0, b=-1.0, f=self.load())
+
+    def partial_matrix(self, wrt: Function, out=None):
+        if wrt is self.rho:
+            return out if isinstance(out, _HarmonicDrho) else _HarmonicDrho(self)
+        return super().partial_matrix(wrt, out)
+
+    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
+        """(K - omega_l^2 M) u_l = F_l for every column with the clamped dofs: ONE batched MINRES (the form is linear)."""
+        self._set_bcs(bcs)
+        dev = self.dynamic()
+        infos = dev.dyn_solve_multi(self.n_cases, self.shifts, self._rhs(dev), func.vec, rtol=self.rtol, max_it=self.max_it,
+                                    pc=self.preconditioner)
+        func.version += 1
+        self._record(infos, "state")
+        if report:
+            print(self._report(infos))
+
+    def _record(self, infos, kind: str):
+        from .utils_hip import LAST_KSP_INFO
+        cols = [dict(iterations=i.iterations, converged=i.converged, residual_norm=i.residual_norm, rhs_norm=i.rhs_norm)
+                for i in infos]
+        self.solve_counts[kind] = self.solve_counts.get(kind, 0) + 1
+        self.last_info[kind] = dict(columns=cols, n_cases=self.n_cases, iterations=[c["iterations"] for c in cols],
+                                    converged=[c["converged"] for c in cols], solve_ms=infos[0].solve_ms,
+                                    preconditioner=self.preconditioner, omegas=self.omegas.copy())
+        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_harmonic_" + kind))
+        for l, c in enumerate(cols):
+            if c["converged"] != 1:
+                raise RuntimeError(f"harmonic elasticity MINRES did not converge ({kind}, column {l} of {self.n_cases}, "
+                                   f"omega = {self.omegas[l]:.6g}): {c['iterations']} iterations, estimated sqrt(r.M^-1 r) = "
+                                   f"{c['residual_norm']:.3e} of {c['rhs_norm']:.3e}")
+        return infos
+
+    def _report(self, infos) -> str:
+        return (f"harmonic elasticity solve, {self.n_cases} frequencies: {[i.iterations for i in infos]} MINRES iterations, "
+                f"{infos[0].solve_ms:.1f} ms")
+
+
+class DynamicCompliance(BackendForm):
+    """J = sum_l w_l |c_l|, or sum_l w_l c_l^2 with ``squared``, over the columns of a harmonic state, c_l = F_l . u_l the
+    dynamic compliance of column l (w = 1 without ``weights``).  Below the first resonance c_l > 0; above it the response
+    may be in antiphase with the load and c_l < 0, hence the absolute value (Ma, Kikuchi & Cheng 1995) or the square, which
+    is smooth where c_l changes sign.  dJ/du_l = w_l sgn(c_l) F_l, or 2 w_l c_l F_l; the form has no partial in the density --
+    the framework's adjoint solve (one batched MINRES) and dR/drho of `HarmonicElasticityResidual` give the total."""
+    rank = 0
+
+    def __init__(self, u: Function, tractions, measures=None, weights=None, squared: bool = False):
+        name = "DynamicCompliance"
+        if any(t is None for t in list(tractions)):
+            raise ValueError(f"{name}: every column needs a traction")
+        V, self.tractions, self.measures, _ = _multi_arguments(name, u, tractions, measures)
+        self.u, self.mesh, self.n_cases = u, V.mesh, V.n_cases
+        self.weights = np.ones(V.n_cases) if weights is None else _per_case(name, "weights", weights, V.n_cases)
+        self.squared = bool(squared)
+        self._grad = {}
+
+    def functions(self):
+        return (self.u,)
+
+    def load(self) -> Vec:
+        """Column l = F_l, unweighted."""
+        return _loads_vec(self.mesh, _facets_of(self.measures, self.tractions), self.tractions)
+
+    def responses(self) -> np.ndarray:
+        """c_l = F_l . u_l of the current state, all columns in one pass."""
+        L = self.n_cases
+        return np.diag(elasticity_handle(self.mesh).block_gram(L, self.load(), L, self.u.vec)).copy()
+
+    def assemble_scalar(self) -> float:
+        c = self.responses()
+        return float(self.weights @ (c * c if self.squared else np.abs(c)))
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        if wrt is not self.u:
+            return out.fill(0.0)
+        c = self.responses()
+        coef = self.weights * (2.0 * c if self.squared else np.sign(c))
+        return elasticity_handle(self.mesh).block_rotate(self.n_cases, np.diag(coef), self.load(), out)
+
+
 def averageFunc(func: Function) -> LinearFunctional:
     """(1/|Omega|) int func dx for a DG0 Function (averageFunc, run_topo_opt_cantilever_beam.py:103-106)."""
     V = func.function_space
@@ -1503,6 +1772,19 @@ def pdeRes_multiload(u, v, rho_e, fs, dss_list=None, E: float = 1.0, method: str
 def compliance_multiload(u, fs, dss_list=None, weights=None, body_forces=None, rho_e=None) -> MultiLoadCompliance:
     """sum_l w_l F_l . u_l with F_l = int_ds(l) f_l . v ds + the body load of ``body_forces[l]`` (needs ``rho_e``)"""
     return MultiLoadCompliance(u, fs, dss_list, weights, body_forces=body_forces, rho=rho_e)
+
+
+def pdeRes_harmonic(u, v, rho_e, fs, dss_list=None, omegas=None, density: float = 1.0, mass_law: str = "linear", E: float = 1.0,
+                    method: str = "SIMP", preconditioner: str = "jacobi") -> HarmonicElasticityResidual:
+    """`pdeRes_multiload` for the harmonic loads ``fs[l]`` cos(omegas[l] t) on ``dss_list[l]`` (nu = 0.3 as there); ``u`` is a
+    Function(LoadCaseSpace(V, len(fs)))."""
+    return HarmonicElasticityResidual(u, rho_e, fs, dss_list, omegas=omegas, density=density, mass_law=mass_law, E=E, nu=0.3,
+                                      method=method, preconditioner=preconditioner)
+
+
+def dynamic_compliance(u, fs, dss_list=None, weights=None, squared: bool = False) -> DynamicCompliance:
+    """sum_l w_l |F_l . u_l| (or its squared form) of a harmonic state as a scalar output."""
+    return DynamicCompliance(u, fs, dss_list, weights=weights, squared=squared)
 
 
 def pnorm_stress(u, rho_e, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0, q: float = 0.5,

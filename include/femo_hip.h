@@ -780,6 +780,36 @@ int femo_elast_buckle_drho(femo_elast* e, int method, int n_modes, const femo_ve
  * interpolation of its own against low-density pseudo-modes, and nonlinear pre-buckling.                                    */
 int femo_elast_buckle(femo_elast* e, int method, const femo_vec* rho, const femo_vec* u, int n_modes, int block, femo_vec* X,
                       const femo_eig_opts* opts, double* lambda, femo_eig_info* info);
+/* Harmonic response (csrc/elast_harm.hip): (K(rho) - omega_l^2 M(rho)) u_l = F_l, undamped, in real arithmetic, with the mass
+ * matrix of femo_elast_mass_apply_multi.  Columns as above; column l carries its own shift sigma_l = omega_l^2 >= 0
+ * (shifts[n_cols]).  No float atomics anywhere: the same bits every call, and a column does not depend on n_cols.
+ *
+ * femo_elast_mass_assemble stores M as a scalar matrix on the mesh's SELL pattern (one double per pattern entry in the slots
+ * of K and one per row; M = that times I_d), allocated on first use and freed with the handle.  Symmetric bit for bit.      */
+int femo_elast_mass_assemble(femo_elast* e, int mass_law, double density, const femo_vec* rho);
+/* y_l = a (K - sigma_l M) x_l + b f_l (f may be NULL) with the assembled K and M in ONE pass over the pattern.  masked = 1:
+ * identity rows / columns on the fixed dofs, exactly as the masked femo_elast_apply_multi.  sigma_l = 0 gives the bits of
+ * femo_elast_apply_multi.                                                                                                 */
+int femo_elast_dyn_apply_multi(femo_elast* e, int masked, int n_cols, const double* shifts /* [n_cols] */, double a,
+                               const femo_vec* x, double b, const femo_vec* f /* or NULL */, femo_vec* y);
+/* (K - sigma_l M) x_l = b_l with the fixed set of the handle (x = b on the fixed dofs) by ONE batched preconditioned MINRES
+ * (Paige & Saunders): the matrix is indefinite above the first resonance, where the PCG of femo_elast_solve_multi breaks
+ * down.  opts as for femo_elast_solve_multi; opts->pc selects block-Jacobi or the multilevel preconditioner, both of the
+ * UNSHIFTED masked K (symmetric positive definite).  It stops on phibar_l <= max(rtol beta1_l, atol), beta1 = sqrt(r0 . M^-1 r0)
+ * -- the norm of the PCG's test; phibar is the recurrence's estimate of sqrt(r . M^-1 r), which parts from the true residual
+ * near eps cond.  info[n_cols]: converged 1 (also for a zero right-hand side, at iteration 0, and for an invariant subspace),
+ * 0 (max_it reached) or -1 (a non-finite value); residual_norm = phibar, rhs_norm = beta1.  A finished column is frozen
+ * while the others go on.  Shifted or deflated preconditioners and damping are out of scope.                             */
+int femo_elast_dyn_solve_multi(femo_elast* e, int n_cols, const double* shifts /* [n_cols] */, const femo_vec* b, femo_vec* x,
+                               const femo_solver_opts* opts, femo_solve_info* info /* [n_cols] or NULL */);
+/* The mass part of dR/drho for R_l = (K - sigma_l M) u_l - F_l, called with scales s_l = -sigma_l and accumulate = 1 on top of
+ * femo_elast_drho_multi:
+ *   transpose = 1:  y[c] (+)= sum_l s_l density m'(rho_c) x_{l,c}^T M0_c u_{l,c}            (x: n_cols * n_dof, y: n_cell)
+ *   transpose = 0:  y_l (+)= s_l sum_{c around v} density m'(rho_c) x_c M0_c u_{l,c}        (x: n_cell, y: n_cols * n_dof)
+ * exact transposes of one another; one launch for all columns either way.                                                 */
+int femo_elast_mass_drho_multi(femo_elast* e, int mass_law, double density, int transpose, int n_cols,
+                               const double* scales /* [n_cols] */, const femo_vec* rho, const femo_vec* u, const femo_vec* x,
+                               femo_vec* y, int accumulate);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
  *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
  * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices

@@ -24,6 +24,15 @@ and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the
                                                                  and the batched stress evaluation (value + dJ/du + dJ/drho in one
                                                                  call) timed against L single-column calls on the same columns:
                                                                  stress_ms_batched, stress_ms_sequential and their spread)
+  ... --harmonic N                                              (1 <= N <= 8: the harmonic response (K - omega_l^2 M) u_l = F of the tip
+                                                                 load at N frequencies through pdeRes_harmonic / dynamic_compliance,
+                                                                 every solve of the cycle one batched MINRES.  The frequencies are
+                                                                 spread below and between the first eigenfrequencies of the start
+                                                                 design (`harmonic_frequencies`).  Adds the MINRES iterations per
+                                                                 column next to the PCG counts of the static solve of the same load,
+                                                                 and the fused product (K - sigma M) x timed against apply_multi
+                                                                 followed by mass_apply_multi on the same vectors: a warm-up, then
+                                                                 5 alternated repeats, medians and spread)
 """
 from __future__ import annotations
 
@@ -283,6 +292,129 @@ def main_multi(args, ctx):
     print(json.dumps(out))
 
 
+def harmonic_frequencies(lam, n):
+    """``n`` shifts sigma = omega^2 from the ascending eigenvalues ``lam``: lambda_1 / 2 first, then the geometric means of the
+    consecutive pairs that lie at least 10 % apart (a pair closer than that is a cluster: its mean would sit on a resonance),
+    and, when those run out, further fractions of lambda_1 below the first one."""
+    lam = np.asarray(lam, dtype=np.float64)
+    between = [float(np.sqrt(a * b)) for a, b in zip(lam[:-1], lam[1:]) if b >= 1.1 * a][:max(n - 1, 0)]
+    below = [0.5 * lam[0] * (k + 1) / (n - len(between)) for k in range(n - len(between))]
+    return np.array(sorted(below + between))
+
+
+def time_products(ctx, dev, rho, shifts, density):
+    """One fused product (K - sigma_l M) x_l against `apply_multi` followed by `mass_apply_multi` on the same vectors (both
+    masked), and the static product alone beside them: a warm-up, then 5 alternated repeats, each a window of about 0.2 s of
+    launches between two device synchronisations."""
+    from femo_amd.engine import Vec
+    L, n = len(shifts), dev.n_dof
+    xv = Vec(ctx, L * n).set(np.random.default_rng(1).standard_normal(L * n))
+    y, yk, ym = Vec(ctx, L * n), Vec(ctx, L * n), Vec(ctx, L * n)
+
+    def timed(body, reps):
+        ctx.sync()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            body()
+        ctx.sync()
+        return (time.perf_counter() - t0) * 1e3 / reps
+
+    fused = lambda: dev.dyn_apply_multi(L, shifts, xv, y, masked=True)
+    split = lambda: (dev.apply_multi(L, xv, yk, masked=True), dev.mass_apply_multi(L, rho, xv, ym, masked=True, density=density))
+    static = lambda: dev.apply_multi(L, xv, yk, masked=True)
+    timed(fused, 20); timed(split, 20)
+    reps = max(20, int(200.0 / timed(static, 20)))                    # windows of about 0.2 s of the static product
+    tf, ts, tk = [], [], []
+    for _ in range(5):
+        tf.append(timed(fused, reps)); ts.append(timed(split, reps)); tk.append(timed(static, reps))
+    spread = max(max(tf) - min(tf), max(ts) - min(ts))
+    return dict(product_ms_fused=float(np.median(tf)), product_ms_two_pass=float(np.median(ts)),
+                product_ms_static=float(np.median(tk)), product_ms_fused_all=[float(v) for v in tf],
+                product_ms_two_pass_all=[float(v) for v in ts], product_ms_static_all=[float(v) for v in tk],
+                product_reps=reps, product_ms_spread=float(spread), fused_faster_than_spread=bool(np.median(ts) - np.median(tf) > spread))
+
+
+def main_harmonic(args, ctx):
+    """The cycle filter -> batched MINRES state -> dynamic compliance -> batched MINRES adjoint -> W^T at N frequencies."""
+    from femo_amd.csdl_opt.fea_model import FEAModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.simulator import Simulator
+    from femo_amd.engine import Vec
+    from femo_amd.fea.elasticity import ElasticityEigenvalues
+    from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, LoadCaseSpace, Measure, VectorFunctionSpace,
+                                      createRectangleMesh, createUnitCubeMesh, dirichletbc, dynamic_compliance,
+                                      locate_dofs_geometrical, locate_entities_boundary, meshSize, meshtags, pdeRes_harmonic)
+    N, density = args.harmonic, 1.0
+    mesh = createUnitCubeMesh(args.n3) if args.n3 else createRectangleMesh(np.array([0.0, 0.0]), np.array([160.0, 80.0]), args.nelx, args.nely)
+    d = mesh.tdim
+    marker, t = load_cases(d, 1, args.nely)[0]
+    facets = locate_entities_boundary(mesh, d - 1, marker)
+    ds = Measure("ds", domain=mesh, subdomain_data=meshtags(mesh, d - 1, facets, np.full(len(facets), 100, dtype=np.int32)))(100)
+    fs, dss = [Constant(mesh, t)] * N, [ds] * N
+    fea = FEA(mesh)
+    fea.REPORT = False
+    Q, V = FunctionSpace(mesh, ("DG", 0)), VectorFunctionSpace(mesh, ("CG", 1))
+    rho, u = Function(Q), Function(LoadCaseSpace(V, N))
+    res = pdeRes_harmonic(u, None, rho, fs, dss, omegas=np.zeros(N), density=density, preconditioner=args.pc)
+    fea.add_input("density", rho)
+    fea.add_state(name="displacements", function=u, residual_form=res, arguments=["density"])
+    fea.add_output(name="dynamic_compliance", type="scalar", form=dynamic_compliance(u, fs, dss), arguments=["displacements"])
+    ubc = Function(V)
+    ubc.vector.set(0.0)
+    clamped = locate_dofs_geometrical((V, V), lambda x: np.isclose(x[0], 0.0, atol=1e-6))
+    fea.add_strong_bc(ubc, [clamped], V)
+    model = FEAModel(fea=[fea])
+    h = meshSize(mesh)
+    model.add(GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
+              name="general_filter_model")
+    model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.random.default_rng(0).random(mesh.n_cell) * 0.86)
+    sim = Simulator(model)
+    x0 = np.array(sim["density_unfiltered"])
+    sim.run()                                                         # omega = 0: the filtered start design reaches `rho`
+    # the first eigenfrequencies of the start design place the frequencies
+    n_modes = min(N + 2, 8)
+    eig = ElasticityEigenvalues(rho, V, [dirichletbc(0.0, clamped, V)], n_modes, block=8, density=density, preconditioner=args.pc,
+                                rtol=1e-6)                      # enough to place the frequencies
+    t0 = time.perf_counter()
+    lam = eig.eigenvalues()
+    eig_ms = (time.perf_counter() - t0) * 1e3
+    shifts = harmonic_frequencies(lam, N)
+    res.omegas, res.shifts = np.sqrt(shifts), shifts
+    times = []
+    for k in range(args.cycles + 1):
+        sim["density_unfiltered"] = x0 * (1.0 - 1e-3 * k)
+        ctx.sync()
+        t0 = time.perf_counter()
+        sim.run()
+        g = np.asarray(sim.compute_totals("dynamic_compliance", "density_unfiltered"))
+        ctx.sync()
+        if k > 0:
+            times.append((time.perf_counter() - t0) * 1e3)
+    info = res.last_info
+    dev = res.dynamic()
+    n = dev.n_dof
+    # the static PCG of the same load, for the iteration counts
+    b = res._rhs(dev)
+    static = dev.solve_multi(N, b, Vec(ctx, N * n), rtol=res.rtol, pc=args.pc)
+    minres_static = dev.dyn_solve_multi(N, np.zeros(N), b, Vec(ctx, N * n), rtol=res.rtol, pc=args.pc)
+    out = dict(metric="topopt_cycle_harmonic", mesh=(f"cube n={args.n3}" if args.n3 else f"rect {args.nelx}x{args.nely}"),
+               n_dof=n, n_cell=mesh.n_cell, frequencies=N, pc=args.pc, cycle_ms=float(np.median(times)),
+               cycle_ms_all=[float(v) for v in times], eigenvalues=[float(v) for v in lam], eig_ms=eig_ms,
+               shifts=[float(v) for v in shifts], shift_over_lambda1=[float(v / lam[0]) for v in shifts],
+               minres_iterations_forward=info["state"]["iterations"], minres_iterations_adjoint=info["adjoint"]["iterations"],
+               minres_solve_ms_forward=info["state"]["solve_ms"], minres_solve_ms_adjoint=info["adjoint"]["solve_ms"],
+               minres_iteration_us=1e3 * info["state"]["solve_ms"] / max(max(info["state"]["iterations"]), 1),
+               pcg_iterations_static=[i.iterations for i in static], pcg_solve_ms_static=float(static[0].solve_ms),
+               minres_iterations_static=[i.iterations for i in minres_static], minres_solve_ms_static=float(minres_static[0].solve_ms),
+               dynamic_compliance=float(sim["dynamic_compliance"][0]), responses=[float(v) for v in fea.outputs_dict["dynamic_compliance"]["form"].responses()],
+               gradient_norm=float(np.linalg.norm(g)))
+    out.update(time_products(ctx, dev, rho.vec, shifts, density))
+    if args.pc == "multilevel":
+        pci = dev.pc_info()
+        out.update(pc_levels=pci["levels"], pc_nodes=pci["nodes"], pc_lattice_bytes=pci["bytes"])
+    print(json.dumps(out))
+
+
 def scipy_cycle(mesh, facets, t, x0, radius):
     """The same cycle with SciPy: KD-tree filter, element-by-element assembly, spsolve forward and adjoint."""
     import scipy.sparse as sp
@@ -330,9 +462,14 @@ def main():
                          "(top, bottom and right edge in 2-D; the faces z = 1, z = 0, y = 1, y = 0 beyond x = 3/4 and pieces of "
                          "x = 1 in 3-D; `load_cases` in this script lists them), solved as one batched PCG and timed against "
                          "sequential single-column solves")
+    ap.add_argument("--harmonic", type=int, default=0,
+                    help="N harmonic responses of the tip load, 1 to 8, at frequencies below and between the first eigenfrequencies "
+                         "of the start design: every solve one batched MINRES; prints the iterations per column and the cycle time")
     args = ap.parse_args()
     if not 1 <= args.load_cases <= 8:
         ap.error("--load-cases: 1 to 8")
+    if not 0 <= args.harmonic <= 8 or (args.harmonic and (args.load_cases > 1 or args.stress)):
+        ap.error("--harmonic: 1 to 8, without --load-cases and --stress")
     from femo_amd import _lib
     from femo_amd.engine import Context, Vec
     from femo_amd.fea import utils_hip
@@ -342,6 +479,8 @@ def main():
     utils_hip.set_context(ctx)
     if args.load_cases > 1:
         return main_multi(args, ctx)
+    if args.harmonic:
+        return main_harmonic(args, ctx)
     sim, mesh, res, facets, t, filter_build_ms, stress = build(args)
     x0 = np.array(sim["density_unfiltered"])
     times = []
