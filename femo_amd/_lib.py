@@ -116,6 +116,10 @@ PROTOTYPES = {
     "femo_vec_dots": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i64, c_f64p]),
     "femo_vec_dots_rhs": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i64, c_f64p, H, H]),
     "femo_mat_identity_solve": (C.c_int, [H, H, H]),
+    "femo_mat_identity_solve_flag": (C.c_int, [H, H, H]),
+    "femo_vec_axpy_if": (C.c_int, [H, C.c_double, H]),
+    "femo_newton_rhs_linear_if": (C.c_int, [H, H, H, H, H]),
+    "femo_ctx_newton_flag_info": (C.c_int, [H, c_i64p, C.c_int]),
     "femo_mesh_create": (C.c_int, [H, C.c_int, c_i64, c_i64, C.c_void_p, c_i64, C.c_void_p, C.POINTER(H)]),
     "femo_mesh_destroy": (C.c_int, [H]),
     "femo_mesh_info": (C.c_int, [H, c_i64p]),
@@ -262,7 +266,9 @@ PROTOTYPES = {
 
 # test-only entry points that an older build selected through FEMO_LIB (A/B measurements against a parent commit) may lack:
 # they stay unbound there and their wrappers raise
-OPTIONAL = frozenset({"femo_mesh_pcg_info", "femo_mesh_head_info"})
+# (and Newton's flagged passes: without them utils_hip takes the plain entry points, as under FEMO_NEWTON_FLAG=0)
+OPTIONAL = frozenset({"femo_mesh_pcg_info", "femo_mesh_head_info", "femo_mat_identity_solve_flag", "femo_vec_axpy_if",
+                      "femo_newton_rhs_linear_if", "femo_ctx_newton_flag_info"})
 
 
 class FemoError(RuntimeError):

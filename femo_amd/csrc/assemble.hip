@@ -1075,8 +1075,10 @@ __global__ __launch_bounds__(64) void k_poisson_system_lds(
 // Off-diagonals are accumulated with ds_add_f64 (per-lane addresses: conflict-free, nothing to wait for).
 // Same arithmetic and order of accumulation as the other two kernels; the right-hand side sums K u' in one sum
 // instead of K u and the lifting separately (differs in the last bits).
+// (run_if: Newton's flag -- the product that reads `out` leaves early on the same word, femo_newton_rhs_linear_if)
 __global__ void k_impose_bc(int64_t n, const double* __restrict__ u, const uint8_t* __restrict__ bcmask,
-                            const double* __restrict__ bcval, double* __restrict__ out) {
+                            const double* __restrict__ bcval, double* __restrict__ out, const int32_t* __restrict__ run_if = nullptr) {
+  if (run_if != nullptr && *run_if == 0) return;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = (bcmask != nullptr && bcmask[i]) ? bcval[i] : u[i];
 }
@@ -1539,10 +1541,7 @@ static int ensure_cell_volumes(femo_mesh* m) {
 
 // The residual K u - L of the linear form comes from the pipelined system kernel while the rows fit its strip; wider
 // meshes take the visit-record row walk (FEMO_ROW_WALK).  One predicate for femo_launch_residual and the streamed head.
-static bool residual_is_pipelined(const femo_mesh* m) {
-  const int nbr = (m->max_rowlen + 1) & ~1;
-  return nbr <= (m->tdim == 3 ? 16 : 8);
-}
+static bool residual_is_pipelined(const femo_mesh* m) { return femo_residual_is_pipelined(m); }
 
 static int ensure_load_vector(femo_mesh* m, const double* f, uint64_t f_uid, uint64_t f_gen) {
   if (m->d_load && f_uid != 0 && m->load_uid == f_uid && m->load_gen == f_gen) return 0;
@@ -1803,7 +1802,7 @@ int femo_launch_system(femo_mesh* m, int pde, const double* params, const double
       hipStream_t st = m->ctx->stream;
       if (!m->d_pipe_dummy) FEMO_HIP_CHECK(hipMalloc(&m->d_pipe_dummy, 64 * 2 * sizeof(double)));
       if (!m->d_ubc) FEMO_HIP_CHECK(hipMalloc(&m->d_ubc, (std::max<int64_t>(m->n_vert, 1) + 2) * sizeof(double)));
-      if (rhs && !no_bc_residual) hipLaunchKernelGGL(k_impose_bc, dim3(cell_grid(m->n_vert)), dim3(FEMO_BLOCK), 0, st, m->n_vert, u, bcmask, bcval, m->d_ubc);
+      if (rhs && !no_bc_residual) hipLaunchKernelGGL(k_impose_bc, dim3(cell_grid(m->n_vert)), dim3(FEMO_BLOCK), 0, st, m->n_vert, u, bcmask, bcval, m->d_ubc, nullptr);
       const double* ubc = no_bc_residual ? u : m->d_ubc;
       // one wave per SIMD (4 per CU): the LDS request is raised so that a fifth workgroup cannot land on a CU (it would
       // share a SIMD with another persistent wave and both would take twice as long)
@@ -1842,10 +1841,11 @@ int femo_poisson_load_vector(femo_mesh* m, const femo_vec* f, const double** loa
   return 0;
 }
 
-int femo_launch_impose_bc(femo_mesh* m, const double* u, const uint8_t* bcmask, const double* bcval, const double** ubc) {
+int femo_launch_impose_bc(femo_mesh* m, const double* u, const uint8_t* bcmask, const double* bcval, const double** ubc,
+                          const int32_t* run_if) {
   if (!m->d_ubc) FEMO_HIP_CHECK(hipMalloc(&m->d_ubc, (std::max<int64_t>(m->n_vert, 1) + 2) * sizeof(double)));
   if (m->n_vert > 0) {
-    hipLaunchKernelGGL(k_impose_bc, dim3(cell_grid(m->n_vert)), dim3(FEMO_BLOCK), 0, m->ctx->stream, m->n_vert, u, bcmask, bcval, m->d_ubc);
+    hipLaunchKernelGGL(k_impose_bc, dim3(cell_grid(m->n_vert)), dim3(FEMO_BLOCK), 0, m->ctx->stream, m->n_vert, u, bcmask, bcval, m->d_ubc, run_if);
     FEMO_HIP_CHECK(hipGetLastError());
   }
   *ubc = m->d_ubc;

@@ -93,6 +93,12 @@ struct femo_pc {
   // preconditioner's scaling by 6e-8 relative, the solution not at all)
   float* d_w_sorted = nullptr;
   float* d_sinv = nullptr;
+  // what the two arrays above were last formed from (k_pc_weights): the operator content (femo_mat::gen, 0 = unknown: never
+  // matches), its scaling vector and its pinned-vertex mask.  One rank: a solve whose key still holds does not form them again
+  // (femo_pc_weights_early; round 18)
+  uint64_t w_key = 0;
+  const double* w_s = nullptr;
+  const uint8_t* w_mask = nullptr;
   double* d_dot_partials = nullptr; // per-block partials of g_L.e_L (4096)
   // partitioned meshes: only the finest-lattice nodes that several ranks touch are exchanged
   bool shared_ready = false;
@@ -2164,6 +2170,7 @@ static int pc_setup_shared(femo_mesh* m) {
   FEMO_HIP_CHECK(hipMalloc(&tmp, n_all * sizeof(double)));
   hipLaunchKernelGGL(k_fill_ones<double>, dim3(lat_grid(m->n_vert)), dim3(256), 0, st, m->n_vert, ones);
   hipLaunchKernelGGL(k_fill_ones<float>, dim3(lat_grid(m->n_rows)), dim3(256), 0, st, std::max<int64_t>(m->n_rows, 0), pc->d_w_sorted);
+  pc->w_key = 0;
   FEMO_HIP_CHECK(hipMemsetAsync(first, 0, n_all * sizeof(double), st));
   launch_bricks(m, ones, F.g, nullptr);
   hipLaunchKernelGGL(k_mark_touched, dim3(lat_grid(n_all)), dim3(256), 0, st, n_all, first, tmp);
@@ -2359,14 +2366,31 @@ int femo_pc_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const Fe
   return 0;
 }
 
-// start of a solve: per-vertex weights of the current operator; the atomically accumulated g arrays must be zero
-int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask) {
+// The per-vertex weights of an operator depend on its scaling vector and its pinned vertices only.  wkey != 0 (one rank,
+// solver.hip: weights_key) names the operator content they are formed from: a later call with the same key, s and mask finds
+// them in place and launches nothing.  wkey == 0: formed now, as always.
+static int pc_weights(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey) {
   femo_pc* pc = m->pc;
-  if (m->ctx->nranks > 1 && getenv("FEMO_BPX_DENSE_ALLREDUCE") == nullptr) FEMO_TRY(pc_setup_shared(m));   // once; uses d_w_sorted as scratch
+  if (wkey != 0 && pc->w_key == wkey && pc->w_s == s && pc->w_mask == mask) { ++m->ctx->pc_weights_reused; return 0; }
   if (m->n_rows > 0) {
     hipLaunchKernelGGL(k_pc_weights, dim3(lat_grid(m->n_rows)), dim3(256), 0, m->ctx->stream, m->n_rows, pc->d_perm, s, mask, pc->d_w_sorted, pc->d_sinv);
     FEMO_HIP_CHECK(hipGetLastError());
   }
+  pc->w_key = wkey; pc->w_s = s; pc->w_mask = mask;
+  return 0;
+}
+// ... issued with the prescale of the operator (femo_mat_prescale), under an upload still in flight; only on a mesh whose
+// hierarchy a solve has already built
+int femo_pc_weights_early(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey) {
+  if (m->pc == nullptr || wkey == 0) return 0;
+  return pc_weights(m, s, mask, wkey);
+}
+
+// start of a solve: per-vertex weights of the current operator; the atomically accumulated g arrays must be zero
+int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey) {
+  femo_pc* pc = m->pc;
+  if (m->ctx->nranks > 1 && getenv("FEMO_BPX_DENSE_ALLREDUCE") == nullptr) FEMO_TRY(pc_setup_shared(m));   // once; uses d_w_sorted as scratch
+  FEMO_TRY(pc_weights(m, s, mask, wkey));
   const int nl = pc->n_levels;
   double* first = pc->L[pc->plan.T].g;
   const int64_t count = (pc->L[nl - 1].g + pc->L[nl - 1].nodes) - first;
@@ -2387,7 +2411,7 @@ bool femo_pc_merged_ok(femo_mesh* m) {
 int femo_pc_merged_collectives(const femo_mesh* m) { return m->ctx->nranks > 1 ? 1 : 0; }
 
 // start of a solve with the merged loop: weights of the current operator, clean accumulators, zero state
-int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra) {
+int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra, uint64_t wkey) {
   femo_pc* pc = m->pc;
   femo_ctx* ctx = m->ctx;
   const hipStream_t st = ctx->stream;
@@ -2399,7 +2423,7 @@ int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, con
     FEMO_HIP_CHECK(hipMalloc(&pc->d_lat_partials, FEMO_MAX_PARTIALS * sizeof(double)));
     FEMO_HIP_CHECK(hipMalloc(&pc->d_rr_partials, FEMO_MAX_PARTIALS * sizeof(double)));
   }
-  if (m->n_rows > 0) hipLaunchKernelGGL(k_pc_weights, dim3(lat_grid(m->n_rows)), dim3(256), 0, st, m->n_rows, pc->d_perm, s, mask, pc->d_w_sorted, pc->d_sinv);
+  FEMO_TRY(pc_weights(m, s, mask, wkey));
   double* first = pc->L[T].g;
   const int64_t count = (pc->L[nl - 1].g + pc->L[nl - 1].nodes) - first;
   ZeroRegions z;

@@ -161,6 +161,20 @@ struct femo_ctx {
   // femo_mesh_pcg_info: slots and flush launches of the last merged solve, solves whose ring came out smaller than asked for
   int pcg_last_ring = 0, pcg_last_flushes = 0;
   int64_t pcg_ring_short = 0;
+  // Newton's flagged passes (api.hip: newton_flag_*; round 18).  d_newton[0] is the flag k_identity_solve raises when it
+  // stores an entry of dx that is not +0.0; [1..4] count the flagged launches of k_axpy / k_spmv_sell_rhs that left early
+  // and that ran (femo_ctx_newton_flag_info).  `newton` is the host-side precondition of passing the flag to a launch:
+  // which right-hand side is in place, from which inputs, and whether the flag speaks about it.
+  int32_t* d_newton = nullptr;
+  struct FemoNewtonKey {
+    bool rhs_valid = false;       // b (uid, gen) holds K u' - L of exactly these inputs
+    const struct femo_mat* K = nullptr;
+    uint64_t K_gen = 0, f_uid = 0, f_gen = 0, u_uid = 0, u_gen = 0, b_uid = 0, b_gen = 0, bc_uid = 0;
+    bool live = false;            // the flag is that of an identity solve of this very b, into dx (uid, gen)
+    uint64_t dx_uid = 0, dx_gen = 0;
+    int64_t flagged = 0;          // launches that were handed the flag
+  } newton;
+  int64_t pc_weights_reused = 0;  // BPX solves that found their weights in place (bpx.hip: pc_weights)
 };
 
 struct femo_vec {
@@ -439,7 +453,10 @@ struct femo_mat {
   uint8_t* d_pcmask = nullptr;  // n_vert bytes, valid when pc_key != 0 and pc_has_mask
   bool pc_has_mask = false;
   uint64_t pc_key = 0;
+  // content generation: process-unique, renewed by every assembly into this matrix (femo_mat_touch); 0 = never assembled
+  uint64_t gen = 0;
 };
+void femo_mat_touch(femo_mat* A);   // api.hip
 
 // ------------------------------------------------------ device utilities ----
 #if defined(__HIPCC__)
@@ -570,14 +587,23 @@ int femo_mat_ensure_scaled(femo_mat* A, bool transpose);   // ... and S A S (or 
 // y = K x - load outside the Dirichlet set, u - bcval on it (bcmask null: no set), one launch (spmv.hip); its two inputs
 // besides the operator: the cached load vector of f, and u with the prescribed values imposed (assemble.hip)
 // (n_range >= 0: the rows of slices [slice0, slice0 + n_range) only -- a range of the streamed head)
+// (run_if != null: nothing unless *run_if is non-zero -- Newton's flag, whole-mesh launches only; count[0] / count[1] are
+// bumped by workgroup 0 of a launch that left early / that ran)
 int femo_launch_newton_rhs_linear(const femo_mat* K, const double* x, const double* u, const double* load,
-                                  const uint8_t* bcmask, const double* bcval, double* y, int64_t slice0 = 0, int64_t n_range = -1);
+                                  const uint8_t* bcmask, const double* bcval, double* y, int64_t slice0 = 0, int64_t n_range = -1,
+                                  const int32_t* run_if = nullptr, int32_t* count = nullptr);
 int femo_poisson_load_vector(femo_mesh* m, const femo_vec* f, const double** load);
 // the same vector formed range by range under a chunked upload of f (assemble.hip): _begin gives the number of ranges
 // (0: not applicable, nothing done), _range(k) forms range k and returns the slices whose rows became complete with it
 int femo_poisson_load_stream_begin(femo_mesh* m, const femo_vec* f, int* n_ranges);
 int femo_poisson_load_stream_range(femo_mesh* m, const femo_vec* f, int k, int64_t* slice0, int64_t* n_slices);
-int femo_launch_impose_bc(femo_mesh* m, const double* u, const uint8_t* bcmask, const double* bcval, const double** ubc);
+int femo_launch_impose_bc(femo_mesh* m, const double* u, const uint8_t* bcmask, const double* bcval, const double** ubc,
+                          const int32_t* run_if = nullptr);
+// the residual K u - L of the linear form comes from the pipelined system kernel while the rows fit its strip (assemble.hip)
+inline bool femo_residual_is_pipelined(const femo_mesh* m) {
+  const int nbr = (m->max_rowlen + 1) & ~1;
+  return nbr <= (m->tdim == 3 ? 16 : 8);
+}
 int femo_spmv_grid(const femo_mesh* m);
 int femo_halo_exchange_on(femo_mesh* m, femo_vec* x, hipStream_t st);
 int femo_mesh_classify_slices(femo_mesh* m);
@@ -636,7 +662,8 @@ struct FemoMergedVecs {
 };
 bool femo_pc_merged_ok(femo_mesh* m);                 // the fused lattice cycle with two brick-fused levels runs on this mesh
 struct FemoZeroExtra { double* p[3]; int64_t n[3]; int count; };     // small regions the caller wants cleared by the same launch
-int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra = nullptr);
+// (wkey: see femo_pc_begin)
+int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra = nullptr, uint64_t wkey = 0);
 int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const FemoMergedVecs& V, double* S,
                          const int32_t* done, const FemoPcgStop* stop);
 // N > 1: does femo_pc_merged_apply start the halo exchange of the direction it produces (interface vertices first, send buffer
@@ -661,6 +688,18 @@ struct FemoPcApply {
 int femo_pc_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const FemoPcApply& a);
 bool femo_pc_carries_xupdate(const femo_mesh* m);   // once the hierarchy is built: the fused lattice cycle runs on this mesh
 bool femo_pc_can_piggyback(const femo_mesh* m);
-int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask);
+// wkey != 0: the operator content (femo_mat::gen) the weights are formed from -- a begin that finds the weights of the same
+// key, s and mask in place does not form them again (one rank; bpx.hip: pc_weights).  femo_pc_weights_early forms them ahead
+// of the solve, with the prescale, on a mesh whose hierarchy exists.
+int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey = 0);
+int femo_pc_weights_early(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey);
+// the key a solve or a prescale of A passes: A's content generation on one rank with Newton's flag switched on, else 0
+// (FEMO_NEWTON_FLAG=0: the weights at every solve; read once per solve / prescale)
+inline uint64_t femo_pc_weights_key(const femo_mat* A) {
+  const femo_mesh* m = A->mesh;
+  if (m->ctx->nranks > 1 || m->n_nbr > 0) return 0;
+  const char* e = getenv("FEMO_NEWTON_FLAG");
+  return (e != nullptr && e[0] == '0' && e[1] == 0) ? 0 : A->gen;
+}
 int femo_pc_levels(const femo_mesh* m, int* n_levels, int64_t* finest_nodes);
 int femo_reduce_to_host(femo_ctx* ctx, int nblocks, int nsums, double* host_out);

@@ -532,25 +532,42 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_dots(int64_t n, DotPairs d, doub
 
 // x = what a Krylov solve of A x = b returns when it decides not to iterate from the zero guess: b_i / diag_i on the identity
 // rows of the last assembly (the loops solve them up front, k_cg_init), 0 elsewhere
+// flag != null (Newton's flagged passes): raised when an entry stored to x is anything but +0.0 in its bits (-0.0 and NaN
+// count as non-zero: y += a x may change y's bits with them).  Cleared on the stream before this launch.
 __global__ void k_identity_solve(int64_t n, int64_t n_all, const double* __restrict__ b, const double* __restrict__ diag,
-                                 const uint8_t* __restrict__ idrow, double* __restrict__ x) {
+                                 const uint8_t* __restrict__ idrow, double* __restrict__ x, int32_t* __restrict__ flag) {
+  bool nz = false;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_all; i += (int64_t)gridDim.x * blockDim.x) {
     double v = 0.0;
     if (i < n && idrow != nullptr && idrow[i]) { const double si = 1.0 / sqrt(diag[i]); v = si * (si * b[i]); }
     x[i] = v;
+    nz = nz || __double_as_longlong(v) != 0;
   }
+  if (flag != nullptr && nz) atomicOr(flag, 1);
 }
-extern "C" int femo_mat_identity_solve(const femo_mat* A, const femo_vec* b, femo_vec* x) {
+static int identity_solve(const femo_mat* A, const femo_vec* b, femo_vec* x, bool flagged) {
   FEMO_REQUIRE(A && b && x, "null argument");
   const femo_mesh* m = A->mesh;
   FEMO_REQUIRE(b->n >= m->n_rows && x->n >= m->n_rows, "vector size mismatch");
   FEMO_TRY(femo_vec_await(b));
   femo_vec_touch(x);
+  auto& nk = m->ctx->newton;
+  if (flagged) {
+    // the flag speaks about the right-hand side in place only if this b IS that right-hand side; x becomes the dx it describes.
+    // Otherwise nobody will be handed the flag: the plain launch
+    nk.live = nk.rhs_valid && b->uid != 0 && b->uid == nk.b_uid && b->gen == nk.b_gen && x->uid != 0 && x->ctx == m->ctx && x->n > 0;
+    nk.dx_uid = x->uid; nk.dx_gen = x->gen;
+    flagged = nk.live;
+    if (flagged) FEMO_HIP_CHECK(hipMemsetAsync(m->ctx->d_newton, 0, sizeof(int32_t), m->ctx->stream));
+  }
   if (x->n == 0) return 0;
-  hipLaunchKernelGGL(k_identity_solve, dim3(2048), dim3(256), 0, m->ctx->stream, m->n_rows, x->n, b->d, A->d_diag, A->has_idrows ? A->d_idrows : nullptr, x->d);
+  hipLaunchKernelGGL(k_identity_solve, dim3(2048), dim3(256), 0, m->ctx->stream, m->n_rows, x->n, b->d, A->d_diag, A->has_idrows ? A->d_idrows : nullptr, x->d,
+                     flagged ? m->ctx->d_newton : nullptr);
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
 }
+extern "C" int femo_mat_identity_solve(const femo_mat* A, const femo_vec* b, femo_vec* x) { return identity_solve(A, b, x, false); }
+extern "C" int femo_mat_identity_solve_flag(const femo_mat* A, const femo_vec* b, femo_vec* x) { return identity_solve(A, b, x, true); }
 
 static int vec_dots(int k, const femo_vec* const* x, const femo_vec* const* y, int64_t n, double* out, const femo_mat* A, const femo_vec* rb);
 extern "C" int femo_vec_dots(int k, const femo_vec* const* x, const femo_vec* const* y, int64_t n, double* out) {
@@ -892,7 +909,7 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
     ze.p[ze.count] = w.r + n; ze.n[ze.count++] = tail;
   }
   if (opts->zero_guess && x->n > n) { ze.p[ze.count] = x->d + n; ze.n[ze.count++] = x->n - n; }   // ghost tail of the solution, as the classic loop leaves it
-  FEMO_TRY(femo_pc_merged_begin(m, A->d_s, mask, &ze));
+  FEMO_TRY(femo_pc_merged_begin(m, A->d_s, mask, &ze, femo_pc_weights_key(A)));
   const double* q0;
   FEMO_TRY(initial_guess(A, A->d_vals, x, opts->zero_guess, /*clear_x=*/false, w.q, &q0));
   double* const p0 = R ? slot(0) : w.p;
@@ -1051,7 +1068,7 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   double* P = ctx->d_partials;
   double* S = ctx->d_scal;
   const uint8_t* mask = A->pc_has_mask ? A->d_pcmask : nullptr;
-  FEMO_TRY(femo_pc_begin(m, A->d_s, mask));
+  FEMO_TRY(femo_pc_begin(m, A->d_s, mask, femo_pc_weights_key(A)));
   auto allreduce1 = [&](double* d) -> int {
     if (multi) FEMO_TRY(femo_coll_allreduce(ctx, d, 1, st));
     return 0;
@@ -1204,7 +1221,7 @@ extern "C" int femo_mat_pc_apply(const femo_mat* A_, const femo_vec* r, femo_vec
   CgWork w;
   FEMO_TRY(ensure_work(ctx, n, m->n_vert, w, 1));
   const uint8_t* mask = A->pc_has_mask ? A->d_pcmask : nullptr;
-  FEMO_TRY(femo_pc_begin(m, A->d_s, mask));
+  FEMO_TRY(femo_pc_begin(m, A->d_s, mask, femo_pc_weights_key(A)));
   const int gv = vec_grid(ctx, n);
   FEMO_HIP_CHECK(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int32_t), st));
   if (n == 0) return 0;

@@ -333,13 +333,21 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_spmv_sell(
 // right-hand side in its epilogue:  y_i = (K x)_i - load_i  outside the Dirichlet set,  y_i = u_i - g_i  on it
 // (bcmask == null: no set, y = K x - load).  x is u with the prescribed values imposed, so that K x carries the lifting.
 // A kernel of its own, not a further flag of k_spmv_sell: the CG loop's instantiations keep their registers.
+// run_if != null (Newton's flag, round 18): y already holds this very right-hand side unless *run_if is set -- the launch
+// leaves as the loop kernels leave on `done`; workgroup 0 counts the launches that left (count[0]) and that ran (count[1]).
 template <bool NT>
 __global__ __launch_bounds__(FEMO_BLOCK) void k_spmv_sell_rhs(
     int64_t n_rows, int64_t n_slices, const int64_t* __restrict__ mptr,
     const int32_t* __restrict__ cols, const int16_t* __restrict__ cols16, const int32_t* __restrict__ sdelta, int sdelta_stride,
     const double* __restrict__ vals, const double* __restrict__ diag, const double* __restrict__ x,
     const double* __restrict__ u, const double* __restrict__ load, const uint8_t* __restrict__ bcmask,
-    const double* __restrict__ bcval, double* __restrict__ y, int64_t slice0) {
+    const double* __restrict__ bcval, double* __restrict__ y, int64_t slice0, const int32_t* __restrict__ run_if,
+    int32_t* __restrict__ count) {
+  if (run_if != nullptr) {
+    const bool leave = *run_if == 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(count + (leave ? 0 : 1), 1);
+    if (leave) return;
+  }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int xcd = blockIdx.x & 7;                    // (XCD-aware walk: see k_spmv_sell)
@@ -635,15 +643,17 @@ int femo_launch_spmv(const femo_mat* A, const double* vals, const double* x, dou
 }
 
 int femo_launch_newton_rhs_linear(const femo_mat* K, const double* x, const double* u, const double* load,
-                                  const uint8_t* bcmask, const double* bcval, double* y, int64_t slice0, int64_t n_range) {
+                                  const uint8_t* bcmask, const double* bcval, double* y, int64_t slice0, int64_t n_range,
+                                  const int32_t* run_if, int32_t* count) {
   const femo_mesh* m = K->mesh;
+  FEMO_REQUIRE(run_if == nullptr || (n_range < 0 && count != nullptr), "a range of the streamed head takes no flag");
   const int64_t n_walk = n_range >= 0 ? n_range : m->n_slices;
   if (n_walk == 0) return 0;                          // (ranges of zero rows launch nothing)
   FEMO_REQUIRE(slice0 >= 0 && slice0 + n_walk <= m->n_slices, "slice range [%lld, %lld) outside the mesh's %lld slices",
                (long long)slice0, (long long)(slice0 + n_walk), (long long)m->n_slices);
   const int64_t g = n_range >= 0 ? subset_grid(m, n_walk) : femo_spmv_grid(m);
   const bool nt = matrix_streams(m);
-#define FEMO_RHS_ARGS m->n_rows, n_walk, m->d_mptr, m->d_cols, m->d_cols16, m->d_sdelta, m->sdelta_stride, K->d_vals, K->d_diag, x, u, load, bcmask, bcval, y, slice0
+#define FEMO_RHS_ARGS m->n_rows, n_walk, m->d_mptr, m->d_cols, m->d_cols16, m->d_sdelta, m->sdelta_stride, K->d_vals, K->d_diag, x, u, load, bcmask, bcval, y, slice0, run_if, count
   if (nt) hipLaunchKernelGGL((k_spmv_sell_rhs<true>), dim3(g), dim3(FEMO_BLOCK), 0, m->ctx->stream, FEMO_RHS_ARGS);
   else hipLaunchKernelGGL((k_spmv_sell_rhs<false>), dim3(g), dim3(FEMO_BLOCK), 0, m->ctx->stream, FEMO_RHS_ARGS);
 #undef FEMO_RHS_ARGS
@@ -870,7 +880,12 @@ extern "C" int femo_bench_spmv(const femo_mat* A, const femo_vec* x, femo_vec* y
   return 0;
 }
 
+// ... and the BPX weights of the operator, which depend on S and the pinned vertices only: the 85 us at C4 that stood behind
+// the wait for f at the head of a cycle.  One rank, a mesh whose hierarchy a BPX solve has built (a mesh that is only ever
+// solved with another preconditioner never has one); otherwise the prescale alone.
 extern "C" int femo_mat_prescale(femo_mat* A) {
   FEMO_REQUIRE(A != nullptr, "null argument");
-  return femo_mat_ensure_scaled(A, false);
+  FEMO_TRY(femo_mat_ensure_scaled(A, false));
+  if (!A->bpx_ok) return 0;
+  return femo_pc_weights_early(A->mesh, A->d_s, A->pc_has_mask ? A->d_pcmask : nullptr, femo_pc_weights_key(A));
 }

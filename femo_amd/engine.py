@@ -324,6 +324,16 @@ class Context:
     def sync(self) -> None:
         check(self.lib.femo_ctx_sync(self.handle))
 
+    def newton_flag_info(self):
+        """(axpys that left early, axpys that ran, products that left early, products that ran, launches handed the flag,
+        the flag, BPX solves that found their weights in place): Newton's flagged passes on this context so far
+        (include/femo_hip_test.h; tests)."""
+        if not hasattr(self.lib, "femo_ctx_newton_flag_info"):
+            raise FemoError("femo_ctx_newton_flag_info: not exported by this build of libfemo_hip.so")
+        v = (C.c_int64 * 7)()
+        check(self.lib.femo_ctx_newton_flag_info(self.handle, v, 7))
+        return tuple(int(x) for x in v)
+
     @property
     def stream(self) -> int:
         return int(self.lib.femo_ctx_stream(self.handle) or 0)
@@ -436,8 +446,10 @@ class Vec:
         check(self.lib.femo_vec_copy(self.handle, other.handle))
         return self
 
-    def axpy(self, a: float, x: "Vec") -> "Vec":
-        check(self.lib.femo_vec_axpy(self.handle, float(a), x.handle))
+    def axpy(self, a: float, x: "Vec", flagged: bool = False) -> "Vec":
+        """self += a x.  ``flagged``: x is the dx of ``Mat.identity_solve(..., flagged=True)`` -- the launch is handed Newton's
+        flag and leaves early while dx is all +0.0 (femo_vec_axpy_if, include/femo_hip.h)."""
+        check((self.lib.femo_vec_axpy_if if flagged else self.lib.femo_vec_axpy)(self.handle, float(a), x.handle))
         return self
 
     def dot(self, other: "Vec", n: Optional[int] = None) -> float:
@@ -677,10 +689,11 @@ class Mat:
         check(self.lib.femo_mat_spmv(self.handle, int(transpose), x.handle, y.handle))
         return y
 
-    def identity_solve(self, b: Vec, x: Vec) -> Vec:
+    def identity_solve(self, b: Vec, x: Vec, flagged: bool = False) -> Vec:
         """x = the result of a solve that decides not to iterate from the zero guess: b_i / diag_i on the identity rows of the
-        last assembly, 0 elsewhere (femo_mat_identity_solve)."""
-        check(self.lib.femo_mat_identity_solve(self.handle, b.handle, x.handle))
+        last assembly, 0 elsewhere (femo_mat_identity_solve).  ``flagged``: the launch also raises Newton's device-side flag
+        when an entry of x is not +0.0 (femo_mat_identity_solve_flag)."""
+        check((self.lib.femo_mat_identity_solve_flag if flagged else self.lib.femo_mat_identity_solve)(self.handle, b.handle, x.handle))
         return x
 
     def prescale(self) -> "Mat":
@@ -794,11 +807,18 @@ def newton_rhs(K: Mat, F: Vec, u: Vec, bc: DirichletSet, b: Vec) -> Vec:
     return b
 
 
-def newton_rhs_linear(K: Mat, f: Vec, u: Vec, bc: Optional[DirichletSet], b: Vec) -> Vec:
+def newton_rhs_linear(K: Mat, f: Vec, u: Vec, bc: Optional[DirichletSet], b: Vec, flagged: bool = False) -> Vec:
     """Newton right-hand side of a linear form from its assembled operator K (no BCs): b = K u' - L outside the set,
-    u - g on it; ``bc=None``: the residual K u - L (include/femo_hip.h)."""
-    check(K.lib.femo_newton_rhs_linear(K.handle, f.handle, u.handle, _h(bc), b.handle))
+    u - g on it; ``bc=None``: the residual K u - L (include/femo_hip.h).  ``flagged``: behind a flagged identity solve and
+    axpy -- the launches leave early while b already holds this right-hand side (femo_newton_rhs_linear_if)."""
+    fn = K.lib.femo_newton_rhs_linear_if if flagged else K.lib.femo_newton_rhs_linear
+    check(fn(K.handle, f.handle, u.handle, _h(bc), b.handle))
     return b
+
+
+def has_newton_flag() -> bool:
+    """Does the loaded library export Newton's flagged entry points (a parent build selected through FEMO_LIB does not)?"""
+    return hasattr(_lib.load(), "femo_newton_rhs_linear_if")
 
 
 def dRdf_apply(mesh: DeviceMesh, vals: Vec, x: Vec, y: Vec, transpose: bool, accumulate: bool = False) -> Vec:

@@ -670,10 +670,10 @@ class _NewtonBase:
                 if ctx.nranks == 1 and A.symmetric and KSP_OPTIONS.get("pc") in ("bpx", "jacobi"):
                     A.mat.prescale()
 
-            def residual_pass(with_matrix):
-                E.newton_rhs_linear(K.mat, F.f.vec, F.u.vec, ds, b)
+            def residual_pass(with_matrix, flagged=False):
+                E.newton_rhs_linear(K.mat, F.f.vec, F.u.vec, ds, b, flagged=flagged)
         else:
-            def residual_pass(with_matrix):
+            def residual_pass(with_matrix, flagged=False):
                 E.assemble_system(dm, F.pde_kind, F.params, F.u.vec, F.f.vec, ds, None, A.mat if with_matrix else None, b,
                                   aux=aux)
         # F (with Dirichlet lifting) and J at the current iterate, one pass over the mesh
@@ -694,6 +694,13 @@ class _NewtonBase:
         unorm = uAu = None
         g2 = None
         rho_b = None               # rho_0 of the NEXT solve, when the last reduction carried it (round 6)
+        # A pass that does not solve (below) leaves dx = 0 off the Dirichlet rows and b_i = u_i - g_i on them: once the state
+        # carries its boundary values exactly, dx is all +0.0, the update writes back the u it read and the next right-hand side
+        # is, bit for bit, the one in place.  The identity solve says so in a device-side flag, and the update and the product
+        # behind it are handed that flag and leave early while it is down (LOG R18).  Every launch and every record stays; the
+        # host never looks at the flag, and the library hands it on only while b provably is the right-hand side of this very
+        # u.  One rank, linear form; FEMO_NEWTON_FLAG=0 (read here, once per solve): the plain launches.
+        use_flag = (reuse and ctx.nranks == 1 and os.environ.get("FEMO_NEWTON_FLAG", "1") != "0" and E.has_newton_flag())
         while not converged and it < self.max_it:
             if it > 0:
                 opts["atol"] = max(KSP_OPTIONS["atol"], KSP_OPTIONS["rtol"] * z0, self.NOISE_FACTOR * eps * unorm)
@@ -733,7 +740,7 @@ class _NewtonBase:
             skip = (rho_b is not None and A.symmetric and not hasattr(A, "backend_solve")
                     and (rho_b == 0.0 or not (np.sqrt(rho_b) > opts["atol"])))
             if skip:
-                A.mat.identity_solve(b, dx)
+                A.mat.identity_solve(b, dx, flagged=use_flag)
                 ksp_its = 0
                 LAST_KSP_INFO.append(dict(thread=threading.get_ident(), iterations=0, converged=1, residual_norm=float(np.sqrt(rho_b)),
                                           rhs_norm=float(np.sqrt(rho_b)), pc_residual_norm=0.0, pc_rhs_norm=0.0, solve_ms=0.0, spmv_ms=0.0,
@@ -745,12 +752,13 @@ class _NewtonBase:
                     z0 = ksp.info.rhs_norm
                 ksp_its = ksp.info.iterations
             self.ksp_iterations.append(ksp_its)
-            func.vec.axpy(-1.0, dx)
+            flagged = skip and use_flag
+            func.vec.axpy(-1.0, dx, flagged=flagged)
             it += 1
             # next pass: residual for the convergence test and, in the same launch, the Jacobian the
             # next iteration will use.  After the last allowed iteration nothing consumes a Jacobian
             # (the reference assembles J only when it iterates again), so that pass is residual-only.
-            residual_pass(it < self.max_it)
+            residual_pass(it < self.max_it, flagged)
             pairs = [(b, b)]
             more = it < self.max_it
             want_energy = more and bpx_energy and (energy_scale is None or self.ksp_iterations[-1] > 0)

@@ -163,6 +163,16 @@ int     femo_vec_dots_rhs(int k, const femo_vec* const* x, const femo_vec* const
 /* ... and what such a solve returns when it does not iterate from the zero guess: x_i = b_i / diag_i on the identity rows of A's
  * last assembly, 0 elsewhere (one small launch, no synchronisation).                                                    */
 int     femo_mat_identity_solve(const femo_mat* A, const femo_vec* b, femo_vec* x);
+/* Newton's flagged passes (one rank, linear form; utils_hip.py `_NewtonBase.solve`, FEMO_NEWTON_FLAG).  The identity solve
+ * also raises a device-side flag when any entry it stores to x is not +0.0 in its bits.  femo_vec_axpy_if (y += a x with that
+ * x, a < 0) and femo_newton_rhs_linear_if are the same launches as the plain entry points, handed that flag: while it is down,
+ * y and the right-hand side already in place are what the launches would write, bit for bit, and the kernels leave at once.
+ * The host never reads the flag.  It is handed on only while the library can show that b still holds the right-hand side of
+ * this very operator content, f, u, Dirichlet set and b (generations unchanged since the launch that wrote b, except by
+ * these entry points themselves); otherwise, and for partitioned meshes, rows wider than the pipelined residual takes and the
+ * streamed head, the calls ARE the plain ones.                                                                            */
+int     femo_mat_identity_solve_flag(const femo_mat* A, const femo_vec* b, femo_vec* x);
+int     femo_vec_axpy_if(femo_vec* y, double a, const femo_vec* x);
 
 /* ---- host memory of the array boundary (csrc/hostmem.cpp) -------------------------------------
  * The CSDL operators exchange NumPy arrays with the FE layer in every method (state_model.py:81-84,
@@ -303,6 +313,9 @@ int femo_newton_rhs(const femo_mat* K_nobc, const femo_vec* F, const femo_vec* u
  * bc == NULL: the plain residual K u - L.  One product with K (no BCs), the rest in its epilogue.                  */
 int femo_newton_rhs_linear(const femo_mat* K_nobc, const femo_vec* f, const femo_vec* u,
                            const femo_bc* bc, femo_vec* b);
+/* ... behind femo_mat_identity_solve_flag and femo_vec_axpy_if (see there) */
+int femo_newton_rhs_linear_if(const femo_mat* K_nobc, const femo_vec* f, const femo_vec* u,
+                              const femo_bc* bc, femo_vec* b);
 
 /* ---- operator application (state_model.py:161-200) -------------------------
  * mat_spmv:   utils_dolfinx.py:256-264 (A*x) / :275-287 (A^T*R).
@@ -319,6 +332,10 @@ int femo_mat_diagonal(const femo_mat* A, femo_vec* d);
  * idle time before the solve -- the operator layer assembles and scales the adjoint system of a linear form while the
  * input of the forward solve is still on its way to the device (state_model.py:117-158 reordered, same work).           */
 int femo_mat_prescale(femo_mat* A);
+/* On one rank, for a matrix of a form BPX takes and a mesh whose lattice hierarchy an earlier BPX solve has built, the
+ * preconditioner's per-vertex weights of this operator are formed here too (they depend on S and the pinned vertices only);
+ * the solves that find them in place do not form them again.  FEMO_NEWTON_FLAG=0: the weights at every solve.          */
+
 /* ---- linear solve (fea_dolfinx.py:192-222; utils_dolfinx.py:476-512) --------
  * Jacobi-preconditioned CG on A (transpose=0) or A^T (transpose=1).  The
  * reference factorises with MUMPS; CG+Jacobi is the BASELINE.json design.

@@ -52,6 +52,16 @@ int femo_mesh_pcg_info(femo_mesh* mesh, int64_t* out, int count);
  * field at the end of femo_host_stats.                                                                      */
 int femo_mesh_head_info(femo_mesh* mesh, int64_t* out, int count);
 
+/* ---- Newton's flagged passes: what the launches that were handed the flag did (tests) -----------------------
+ * Synchronises the context's stream, then
+ * out[0] / out[1] = flagged launches of the axpy that left early / that ran (a device counter, bumped by workgroup 0);
+ * out[2] / out[3] = the same for the product of femo_newton_rhs_linear_if;
+ * out[4] = launches that were handed the flag at all (host side; the rest ran as the plain entry points);
+ * out[5] = the flag as the last identity solve left it;
+ * out[6] = BPX solves on this context that found the preconditioner's weights in place (femo_mat_prescale).
+ * Counters run from the creation of the context.  Entries beyond `count` are not written.                    */
+int femo_ctx_newton_flag_info(femo_ctx* ctx, int64_t* out, int count);
+
 #ifdef __cplusplus
 }
 #endif
