@@ -249,6 +249,9 @@ PROTOTYPES = {
     "femo_elast_mass_assemble": (C.c_int, [H, C.c_int, C.c_double, H]),
     "femo_elast_dyn_apply_multi": (C.c_int, [H, C.c_int, C.c_int, c_f64p, C.c_double, H, C.c_double, H, H]),
     "femo_elast_dyn_solve_multi": (C.c_int, [H, C.c_int, c_f64p, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
+    "femo_elast_cdyn_apply_multi": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_f64p, c_f64p, c_f64p, C.c_double, H, C.c_double, H, H]),
+    "femo_elast_cdyn_solve_multi": (C.c_int, [H, C.c_int, C.c_int, c_f64p, c_f64p, c_f64p, H, H, C.POINTER(SolverOpts),
+                                              C.POINTER(SolveInfo)]),
     "femo_elast_mass_drho_multi": (C.c_int, [H, C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, H, H, H, H, C.c_int]),
     "femo_elast_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "femo_elast_pc_setup": (C.c_int, [H, C.c_double]),

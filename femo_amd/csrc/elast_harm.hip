@@ -59,7 +59,7 @@ struct DynChunk { static constexpr int value = 4; };
 // MINRES device scalars of a column
 enum { MS_BETA1 = 0, MS_BETA, MS_OLDB, MS_ALFA, MS_DBAR, MS_EPSLN, MS_OLDEPS, MS_DELTA, MS_GAMMA, MS_CS, MS_SN, MS_PHI,
        MS_PHIBAR, MS_TOL };
-constexpr int MS_STRIDE = 16;
+constexpr int MS_STRIDE = FEMO_ELAST_HARM_SCALARS;
 
 // neither NaN nor infinite.  (x - x == 0 would do as well, were it not that with x = a * b the compiler contracts x - x into
 // fma(a, b, -x), the rounding error of the product.)
@@ -470,24 +470,6 @@ int dyn_spmv(femo_elast* e, bool masked, int n_cols, const ColScalars& sig, doub
   return 0;
 }
 
-// the three extra vectors of the MINRES loop (r1, w1, w2) for at least n_cols columns, its scalars and their pinned mirror
-int harm_reserve(femo_elast* e, int n_cols, const char* who) {
-  if (!e->w_ms) FEMO_TRY(dalloc(&e->w_ms, (int64_t)MS_STRIDE * EMC));
-  if (!e->h_ms) FEMO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_ms), MS_STRIDE * EMC * sizeof(double)));
-  if (e->w_harm_cols >= n_cols) return 0;
-  const int64_t n = e->mesh->n_vert * e->d;
-  double* w = nullptr;
-  if (dalloc(&w, 3 * n * n_cols)) {
-    femo_set_error("%s: device allocation failed", who);
-    return 1;
-  }
-  FEMO_HIP_CHECK(hipStreamSynchronize(e->mesh->ctx->stream));
-  hipFree(e->w_harm);
-  e->w_harm = w;
-  e->w_harm_cols = n_cols;
-  return 0;
-}
-
 bool shifts_ok(int n_cols, const double* shifts, ColScalars& sig) {
   for (int l = 0; l < EMC; ++l) {
     sig.v[l] = l < n_cols ? shifts[l] : 0.0;
@@ -509,7 +491,7 @@ int minres_solve(femo_elast* e, int n_cols, const ColScalars& sig, const femo_ve
   const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
   if (ml) FEMO_TRY(femo_elast_pc_ensure(e));
   FEMO_TRY(femo_elast_work_reserve(e, n_cols, who));
-  FEMO_TRY(harm_reserve(e, n_cols, who));
+  FEMO_TRY(femo_elast_harm_reserve(e, n_cols, who));
   const int check = opts->check_every > 0 ? opts->check_every : (ml ? 8 : 32);
   const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
   const int nps = (int)grid_of(m->n_rows);
@@ -582,6 +564,24 @@ int minres_solve(femo_elast* e, int n_cols, const ColScalars& sig, const femo_ve
 }
 
 }  // namespace
+
+// the three extra vectors of the MINRES loop (r1, w1, w2) for at least n_cols columns, its scalars and their pinned mirror
+int femo_elast_harm_reserve(femo_elast* e, int n_cols, const char* who) {
+  if (!e->w_ms) FEMO_TRY(dalloc(&e->w_ms, (int64_t)MS_STRIDE * EMC));
+  if (!e->h_ms) FEMO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&e->h_ms), MS_STRIDE * EMC * sizeof(double)));
+  if (e->w_harm_cols >= n_cols) return 0;
+  const int64_t n = e->mesh->n_vert * e->d;
+  double* w = nullptr;
+  if (dalloc(&w, 3 * n * n_cols)) {
+    femo_set_error("%s: device allocation failed", who);
+    return 1;
+  }
+  FEMO_HIP_CHECK(hipStreamSynchronize(e->mesh->ctx->stream));
+  hipFree(e->w_harm);
+  e->w_harm = w;
+  e->w_harm_cols = n_cols;
+  return 0;
+}
 
 // ===================================================================================================== C-ABI ====
 extern "C" {

@@ -1,8 +1,9 @@
 // Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product and PCG), elast_pc.hip
 // (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, elast_block.hip
 // (block linear algebra and the block iteration of the eigen solves), elast_eig.hip (mass product and the eigenfrequency
-// pencil), elast_buckle.hip (geometric stiffness and the buckling pencil) and elast_harm.hip (assembled mass, shifted
-// product and MINRES of the harmonic response).  Not part of the ABI.
+// pencil), elast_buckle.hip (geometric stiffness and the buckling pencil), elast_harm.hip (assembled mass, shifted
+// product and MINRES of the harmonic response) and elast_damp.hip (complex product and COCR of the damped response).  Not
+// part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -50,7 +51,8 @@ struct femo_elast {
   bool has_gstress = false;
   // harmonic response (elast_harm.hip), on first use: the scalar mass matrix on the SELL pattern (sell_entries values in the
   // slots of K, n_rows diagonal values); the three extra vectors of the MINRES loop (r1, w1, w2, w_harm_cols columns each), its
-  // scalars per column and their pinned mirror
+  // scalars per column and their pinned mirror.  The COCR of the damped response (elast_damp.hip) reads the same M and keeps
+  // two of its vectors and its scalars in w_harm and w_ms
   double *d_mvals = nullptr, *d_mdiag = nullptr;
   bool mass_assembled = false;
   double* w_harm = nullptr;
@@ -115,6 +117,13 @@ int femo_elast_start_x(femo_elast* e, int n_cols, int zero_guess, const double* 
 // records, or null.
 int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
                    const char* who);
+
+// elast_harm.hip ----------------------------------------------------------------------------------------------------
+// scalars per column in w_ms / h_ms, always for FEMO_ELAST_MAX_COLS columns
+constexpr int FEMO_ELAST_HARM_SCALARS = 16;
+// The three extra vectors of the MINRES loop in w_harm (w_harm_cols columns each, one behind the other) for at least n_cols
+// columns, the scalars and their pinned mirror.  The COCR of elast_damp.hip keeps two vectors and its scalars there.
+int femo_elast_harm_reserve(femo_elast* e, int n_cols, const char* who);
 
 // elast_block.hip: the block linear algebra and the block iteration of the eigen solves --------------------------------
 namespace elast_block {

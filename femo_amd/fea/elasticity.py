@@ -1,7 +1,7 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
 product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip,
-buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip, the harmonic response in csrc/elast_harm.hip).  One load case is the L = 1 case of several:
+buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip, the harmonic response in csrc/elast_harm.hip, its damped form in csrc/elast_damp.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
@@ -61,6 +61,13 @@ are used unchanged.
                        matrix is indefinite, where PCG breaks down.  Not in the reference's script
   DynamicCompliance    J = sum_l w_l |F_l . u_l| (Ma, Kikuchi & Cheng 1995; Olhoff & Du 2005), or sum_l w_l (F_l . u_l)^2, of a
                        harmonic state: the usual companion of an eigenfrequency constraint
+  DampedHarmonicElasticityResidual, DampedDynamicCompliance
+                       the damped response (K - omega_l^2 M + i (c_K,l K + c_M,l M)) u_l = F_l in complex arithmetic, c_K = eta +
+                       omega beta, c_M = omega alpha for a structural loss factor eta and Rayleigh damping alpha M + beta K; the
+                       state is a Function(LoadCaseSpace(V, 2L)) with Re u_l in column 2 l and Im u_l in column 2 l + 1.  State,
+                       adjoint (conj(Z)) and forward-mode solves are each ONE batched preconditioned COCR (Sogabe & Zhang
+                       2007; csrc/elast_damp.hip), which converges at a resonance, where the undamped MINRES does not, and
+                       J = sum_l w_l |F_l . u_l| (or its square) of the complex compliance is finite and differentiable there
 
 P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
 """
@@ -416,6 +423,40 @@ class DeviceElasticity:
         info = (_lib.SolveInfo * _lib.ELAST_MAX_COLS)()
         check(self.lib.femo_elast_dyn_solve_multi(self.handle, n_cols, sv.ctypes.data_as(_lib.c_f64p), b.handle, x.handle,
                                                   C.byref(opts), info))
+        return [info[l] for l in range(n_cols)]
+
+    # ---- damped harmonic response: Z_l = (K - sigma_l M) + i (ck_l K + cm_l M); complex column l = real columns 2 l, 2 l + 1
+    # (csrc/elast_damp.hip) ----
+    def _damping(self, who: str, n_cols: int, shifts, ck, cm, *vecs: Vec):
+        n_cols = int(n_cols)
+        if not 1 <= n_cols <= _lib.ELAST_MAX_COLS // 2:
+            raise _lib.FemoError(f"{who}: {n_cols} complex columns (1 to {_lib.ELAST_MAX_COLS // 2})")
+        self._cols(2 * n_cols, *vecs)
+        arrays = [self._per_column(who, what, n_cols, v) for what, v in (("shifts", shifts), ("ck", ck), ("cm", cm))]
+        return n_cols, [a.ctypes.data_as(_lib.c_f64p) for a in arrays], arrays
+
+    def cdyn_apply_multi(self, n_cols: int, shifts, ck, cm, x: Vec, y: Vec, masked: bool = False, conj: bool = False,
+                         a: float = 1.0, b: float = 0.0, f: Optional[Vec] = None) -> Vec:
+        """y_l = a Z_l x_l + b f_l with Z_l = (K - shifts[l] M) + i (ck[l] K + cm[l] M) (conj(Z_l) with ``conj``) for ``n_cols``
+        complex columns, Re in real column 2 l and Im in 2 l + 1, in one pass over the pattern; ck = cm = 0 gives the bits of
+        `dyn_apply_multi` on both parts."""
+        n_cols, ptrs, _keep = self._damping("cdyn_apply_multi", n_cols, shifts, ck, cm, x, y, f)
+        check(self.lib.femo_elast_cdyn_apply_multi(self.handle, int(bool(masked)), int(bool(conj)), n_cols, *ptrs, float(a),
+                                                   x.handle, float(b), None if f is None else f.handle, y.handle))
+        return y
+
+    def cdyn_solve_multi(self, n_cols: int, shifts, ck, cm, b: Vec, x: Vec, conj: bool = False, rtol: float = 1e-12,
+                         atol: float = 0.0, max_it: int = 1_000_000, check_every: Optional[int] = None, zero_guess: bool = True,
+                         pc: str = "jacobi") -> list:
+        """Z_l x_l = b_l (conj(Z_l) with ``conj``) for ``n_cols`` complex right-hand sides in one batched preconditioned COCR
+        with the preconditioner of `solve_multi` on both parts; one `SolveInfo` per complex column: ``converged`` 1, 0
+        (max_it) or -1 (a non-finite value or a zero denominator), ``residual_norm`` = sqrt(Re(r^H M^-1 r)), ``rhs_norm`` that
+        of the first residual.  A finished column is frozen while the others go on."""
+        opts = self._solver_opts(rtol, atol, max_it, check_every, zero_guess, pc)
+        n_cols, ptrs, _keep = self._damping("cdyn_solve_multi", n_cols, shifts, ck, cm, b, x)
+        info = (_lib.SolveInfo * _lib.ELAST_MAX_COLS)()
+        check(self.lib.femo_elast_cdyn_solve_multi(self.handle, int(bool(conj)), n_cols, *ptrs, b.handle, x.handle,
+                                                   C.byref(opts), info))
         return [info[l] for l in range(n_cols)]
 
     def mass_drho_multi(self, transpose: bool, n_cols: int, scales, rho: Vec, u: Vec, x: Vec, y: Vec, density: float = 1.0,
@@ -1602,8 +1643,8 @@ class HarmonicElasticityResidual(MultiLoadElasticityResidual):
     bounds the iterations of a solve.  A column that does not converge raises, naming the column and its omega.  Close to a resonance the iteration count grows and
     the response is large: keep the frequencies away from the eigenfrequencies of the design (`ElasticityEigenvalues`).
 
-    Out of scope: damping (complex arithmetic), shifted or deflated preconditioners, frequency-band integrals, body forces,
-    inhomogeneous supports, partitioned meshes."""
+    Damping: `DampedHarmonicElasticityResidual`.  Out of scope: shifted or deflated preconditioners, frequency-band integrals,
+    viscous dampers at points, body forces, inhomogeneous supports, partitioned meshes."""
     matrix_class = HarmonicElasticityMatrix
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, omegas=None, density: float = 1.0,
@@ -1736,6 +1777,287 @@ class DynamicCompliance(BackendForm):
         return elasticity_handle(self.mesh).block_rotate(self.n_cases, np.diag(coef), self.load(), out)
 
 
+# ------------------------------------------------------------------------------------ damped harmonic response ----
+class DampedHarmonicElasticityMatrix(MultiLoadElasticityMatrix):
+    """dR/du of a `DampedHarmonicElasticityResidual` as the real operator on the 2L columns: [[A_l, -B_l], [B_l, A_l]] on
+    the pair (2 l, 2 l + 1), A = K - omega^2 M, B = c_K K + c_M M -- not symmetric.  `mult` is Z, `multTranspose` conj(Z) (the
+    transpose of the real operator); `backend_solve` is one batched COCR with Z (forward mode), `backend_solve_transpose`
+    one with conj(Z) (the adjoint)."""
+    symmetric = False
+
+    def _apply(self, conj: bool, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        dev = F.dynamic()
+        return dev.cdyn_apply_multi(F.n_freq, F.shifts, F.ck, F.cm, x, y, conj=conj,
+                                    masked=self.masked and dev.fixed_key is not None)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        return self._apply(False, x, y)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        return self._apply(True, x, y)
+
+    def _solve(self, conj: bool, kind: str, b: Vec, x: Vec, options: Optional[dict]) -> None:
+        o = options or {}
+        F = self.form
+        infos = F.dynamic().cdyn_solve_multi(F.n_freq, F.shifts, F.ck, F.cm, b, x, conj=conj, rtol=o.get("elast_rtol", F.rtol),
+                                             max_it=o.get("elast_max_it", F.max_it), pc=F.preconditioner)
+        self.info = F._record(infos, kind)
+
+    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        self._solve(False, "forward", b, x, options)
+
+    def backend_solve_transpose(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        self._solve(True, "adjoint", b, x, options)
+
+    def to_scipy(self):
+        import scipy.sparse as sp
+        F = self.form
+        K = F.dynamic().export_csr()
+        M = _host_mass(F.mesh, np.array(F.rho.vec.get(), dtype=np.float64), F.mass_law, F.density)
+        blocks = []
+        for sg, ck, cm in zip(F.shifts, F.ck, F.cm):
+            A, B = (K - sg * M).tocsr(), (ck * K + cm * M).tocsr()
+            if self.masked and F._mask is not None:
+                free = sp.diags((F._mask == 0).astype(np.float64))
+                A = (free @ A @ free + sp.diags(F._mask.astype(np.float64))).tocsr()
+                B = (free @ B @ free).tocsr()
+            blocks.append(sp.bmat([[A, -B], [B, A]], format="csr"))
+        return sp.block_diag(blocks, format="csr")
+
+
+class _DampedHarmonicDrho(_ElasticityDrho):
+    """dR/drho of a `DampedHarmonicElasticityResidual`, matrix free: block l of column e is C'(rho_e) K0_e u_{l,e} (1 + i c_K)
+    - density m'(rho_e) M0_e u_{l,e} (omega_l^2 - i c_M), split into its parts.  The stiffness and the mass launches of the
+    undamped form on two rotated copies of the state: (1 + i c_K) u and (omega^2 - i c_M) u."""
+
+    def __init__(self, form):
+        super().__init__(form)
+        self._uk = self._um = None
+        self._key = None
+
+    def _states(self):
+        F = self.form
+        key = (F.u.version, id(F.u.vec), tuple(F.shifts), tuple(F.ck), tuple(F.cm))
+        if key != self._key:
+            n2 = F.n_cases
+            if self._uk is None:
+                self._uk, self._um = Vec(_ctx(), n2 * F.n_dof), Vec(_ctx(), n2 * F.n_dof)
+            QK, QM = np.zeros((n2, n2)), np.zeros((n2, n2))
+            for l in range(F.n_freq):
+                r, i = 2 * l, 2 * l + 1
+                QK[r, r] = QK[i, i] = 1.0
+                QK[i, r], QK[r, i] = -F.ck[l], F.ck[l]
+                QM[r, r] = QM[i, i] = F.shifts[l]
+                QM[i, r], QM[r, i] = F.cm[l], -F.cm[l]
+            dev = F.device()
+            dev.block_rotate(n2, QK, F.u.vec, self._uk)
+            dev.block_rotate(n2, QM, F.u.vec, self._um)
+            self._key = key
+        return self._uk, self._um
+
+    def _both(self, transpose: bool, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        uk, um = self._states()
+        dev = F.device()
+        dev.drho_multi(F.method_id, transpose, F.n_cases, F.rho.vec, uk, x, y)
+        return dev.mass_drho_multi(transpose, F.n_cases, -np.ones(F.n_cases), F.rho.vec, um, x, y, density=F.density,
+                                   mass_law=F.mass_law, accumulate=True)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        return self._both(False, x, y)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        return self._both(True, x, y)
+
+
+def _damped_arguments(name: str, u: Function, tractions, measures):
+    """(V, L, tractions, measures) of a state of 2L real columns, the lists interleaved with None for the imaginary columns:
+    the load of column 2 l is F_l, that of column 2 l + 1 zero."""
+    V = u.function_space
+    if not isinstance(V, LoadCaseSpace):
+        raise NotImplementedError(f"{name} needs a Function(LoadCaseSpace(V, 2 n_frequencies)) state")
+    if getattr(V.mesh, "local", None) is not None and V.mesh.local.nranks > 1:
+        raise NotImplementedError(f"{name}: partitioned meshes are out of scope")
+    if V.n_cases % 2:
+        raise ValueError(f"{name}: the state needs an even number of columns (Re and Im of every frequency), got {V.n_cases}")
+    L = V.n_cases // 2
+    if L > _lib.ELAST_MAX_COLS // 2:
+        raise ValueError(f"{name}: {L} frequencies ({_lib.ELAST_MAX_COLS // 2} at the most)")
+    tractions = list(tractions)
+    measures = [None] * len(tractions) if measures is None else list(measures)
+    if len(tractions) != L or len(measures) != L:
+        raise ValueError(f"{name}: {L} frequencies need as many tractions and measures")
+    if any(t is None for t in tractions):
+        raise ValueError(f"{name}: every frequency needs a traction (body forces are out of scope)")
+    ts, dss = [], []
+    for t, ds in zip(tractions, measures):
+        ds = ds if ds is not None else Measure("ds", domain=V.mesh)
+        ts += [_traction(t, V.mesh), None]
+        dss += [ds, ds]
+    return V, L, ts, dss
+
+
+class DampedHarmonicElasticityResidual(HarmonicElasticityResidual):
+    """The damped harmonic response Z_l u_l = F_l in complex arithmetic,
+
+        Z_l = K(rho) - omega_l^2 M(rho) + i (c_K,l K(rho) + c_M,l M(rho)),   c_K = loss_factor + omega beta,   c_M = omega alpha,
+
+    with a structural ``loss_factor`` eta and Rayleigh damping ``rayleigh`` = (alpha, beta), C = alpha M + beta K.  ``u`` is a
+    Function(LoadCaseSpace(V, 2L)): column 2 l is Re u_l, column 2 l + 1 is Im u_l; ``tractions``, ``measures`` and ``omegas``
+    are per frequency, L <= 4 of them.  The residual is Z_l u_l - F_l split into its parts (the load is real).  K, M, the fixed
+    set, the preconditioner, the load caches and the recording are those of `HarmonicElasticityResidual`.
+
+    With damping the response is bounded at every frequency, and J of `DampedDynamicCompliance` is finite and differentiable
+    across the resonances that an optimiser moves through the excitation frequencies.  The state solve, the forward-mode
+    solve and the adjoint solve are each ONE batched preconditioned COCR (`DeviceElasticity.cdyn_solve_multi`; Sogabe &
+    Zhang 2007), the adjoint with conj(Z), the transpose of the real operator: `KSP.solve` hands a transposed solve to
+    `backend_solve_transpose`.  (A cached solver object of ``fea.linear_problem = True`` solves with the matrix itself and is
+    not for this form.)  ``solve_counts`` has "state", "adjoint" and "forward".  dR/drho is matrix free, composed of the
+    launches of the undamped form on two rotated copies of the state.
+
+    Out of scope: frequency-band integrals, shifted preconditioners, viscous dampers at points, body forces, inhomogeneous
+    supports, partitioned meshes."""
+    matrix_class = DampedHarmonicElasticityMatrix
+    is_symmetric = False
+
+    def __init__(self, u: Function, rho: Function, tractions, measures=None, omegas=None, loss_factor: float = 0.0,
+                 rayleigh=(0.0, 0.0), density: float = 1.0, mass_law: str = "linear", E: float = 1.0, nu: float = 0.3,
+                 method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None):
+        name = "DampedHarmonicElasticityResidual"
+        if body_forces is not None:
+            raise NotImplementedError(f"{name}: body forces are out of scope")
+        V, L, ts, dss = _damped_arguments(name, u, tractions, measures)
+        if omegas is None:
+            raise ValueError(f"{name}: one angular frequency per column (omegas)")
+        om = _per_case(name, "frequencies omega", omegas, L)
+        if not np.all(np.isfinite(om)) or np.any(om < 0.0):
+            raise ValueError(f"{name}: the frequencies omega must be finite and >= 0")
+        damping = np.array([float(loss_factor)] + [float(v) for v in np.ravel(rayleigh)])
+        if damping.size != 3 or not np.all(np.isfinite(damping)) or np.any(damping < 0.0):
+            raise ValueError(f"{name}: the damping (loss_factor, rayleigh = (alpha, beta)) must be finite and >= 0")
+        if mass_law not in MASS_LAWS:
+            raise ValueError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
+        if not (np.isfinite(density) and density >= 0.0):
+            raise ValueError(f"{name}: the mass density must be finite and >= 0")
+        self._setup(u, rho, V.base, 2 * L, ts, dss, E, nu, method, preconditioner, None)
+        self.n_freq = L
+        self.loss_factor, self.rayleigh = float(damping[0]), (float(damping[1]), float(damping[2]))
+        self.omegas = om
+        self.density, self.mass_law = float(density), mass_law
+        self.rtol, self.max_it = 1e-12, 1_000_000
+        self.solve_counts = {"state": 0, "adjoint": 0, "forward": 0}
+
+    @property
+    def omegas(self) -> np.ndarray:
+        return self._omegas
+
+    @omegas.setter
+    def omegas(self, om) -> None:
+        """The shifts and the damping coefficients follow the frequencies."""
+        self._omegas = np.array(om, dtype=np.float64)
+        self.shifts = self._omegas * self._omegas
+        self.ck = self.loss_factor + self._omegas * self.rayleigh[1]
+        self.cm = self._omegas * self.rayleigh[0]
+
+    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
+        """Columns 2 l, 2 l + 1: Re and Im of Z_l u_l - F_l; one launch (femo_elast_cdyn_apply_multi)."""
+        if out is None:
+            if self._res is None:
+                self._res = Vec(_ctx(), self.n_cases * self.n_dof)
+            out = self._res
+        return self.dynamic().cdyn_apply_multi(self.n_freq, self.shifts, self.ck, self.cm, self.u.vec, out, a=1.0, b=-1.0,
+                                               f=self.load())
+
+    def partial_matrix(self, wrt: Function, out=None):
+        if wrt is self.rho:
+            return out if isinstance(out, _DampedHarmonicDrho) else _DampedHarmonicDrho(self)
+        return MultiLoadElasticityResidual.partial_matrix(self, wrt, out)
+
+    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
+        """Z_l u_l = F_l for every frequency with the clamped dofs: ONE batched COCR (the form is linear)."""
+        self._set_bcs(bcs)
+        dev = self.dynamic()
+        infos = dev.cdyn_solve_multi(self.n_freq, self.shifts, self.ck, self.cm, self._rhs(dev), func.vec, rtol=self.rtol,
+                                     max_it=self.max_it, pc=self.preconditioner)
+        func.version += 1
+        self._record(infos, "state")
+        if report:
+            print(self._report(infos))
+
+    def _record(self, infos, kind: str):
+        from .utils_hip import LAST_KSP_INFO
+        cols = [dict(iterations=i.iterations, converged=i.converged, residual_norm=i.residual_norm, rhs_norm=i.rhs_norm)
+                for i in infos]
+        self.solve_counts[kind] = self.solve_counts.get(kind, 0) + 1
+        self.last_info[kind] = dict(columns=cols, n_cases=self.n_freq, iterations=[c["iterations"] for c in cols],
+                                    converged=[c["converged"] for c in cols], solve_ms=infos[0].solve_ms,
+                                    preconditioner=self.preconditioner, omegas=self.omegas.copy())
+        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_damped_harmonic_" + kind))
+        for l, c in enumerate(cols):
+            if c["converged"] != 1:
+                raise RuntimeError(f"damped harmonic elasticity COCR did not converge ({kind}, column {l} of {self.n_freq}, "
+                                   f"omega = {self.omegas[l]:.6g}): {c['iterations']} iterations, sqrt(Re(r^H M^-1 r)) = "
+                                   f"{c['residual_norm']:.3e} of {c['rhs_norm']:.3e}")
+        return infos
+
+    def _report(self, infos) -> str:
+        return (f"damped harmonic elasticity solve, {self.n_freq} frequencies: {[i.iterations for i in infos]} COCR iterations, "
+                f"{infos[0].solve_ms:.1f} ms")
+
+
+class DampedDynamicCompliance(BackendForm):
+    """J = sum_l w_l |c_l|, or sum_l w_l |c_l|^2 with ``squared``, over the frequencies of a damped harmonic state, c_l =
+    F_l . u_l the complex dynamic compliance (unconjugated; the load is real).  dJ/du: the real column of frequency l is
+    w_l (Re c_l / |c_l|) F_l and the imaginary one w_l (Im c_l / |c_l|) F_l; 2 w_l Re c_l F_l and 2 w_l Im c_l F_l for the square.
+    No partial in the density: the adjoint solve (one batched COCR with conj(Z)) and dR/drho of
+    `DampedHarmonicElasticityResidual` give the total,
+    dJ/drho = sum_l w_l Re(conj(c_l) / |c_l| dc_l/drho), dc_l/drho_e = -u_e^T [C'(rho_e) K0_e (1 + i c_K) - density m'(rho_e) M0_e
+    (omega_l^2 - i c_M)] u_e."""
+    rank = 0
+
+    def __init__(self, u: Function, tractions, measures=None, weights=None, squared: bool = False):
+        name = "DampedDynamicCompliance"
+        V, L, self.tractions, self.measures = _damped_arguments(name, u, tractions, measures)
+        self.u, self.mesh, self.n_cases, self.n_freq = u, V.mesh, V.n_cases, L
+        self.weights = np.ones(L) if weights is None else _per_case(name, "weights", weights, L)
+        self.squared = bool(squared)
+        self._grad = {}
+
+    def functions(self):
+        return (self.u,)
+
+    def load(self) -> Vec:
+        """Column 2 l = F_l, unweighted; column 2 l + 1 = 0."""
+        return _loads_vec(self.mesh, _facets_of(self.measures, self.tractions), self.tractions)
+
+    def responses(self) -> np.ndarray:
+        """The complex c_l = F_l . u_l of the current state, all frequencies in one pass."""
+        n2 = self.n_cases
+        G = elasticity_handle(self.mesh).block_gram(n2, self.load(), n2, self.u.vec)
+        r = 2 * np.arange(self.n_freq)
+        return G[r, r] + 1j * G[r, r + 1]
+
+    def assemble_scalar(self) -> float:
+        a = np.abs(self.responses())
+        return float(self.weights @ (a * a if self.squared else a))
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        if wrt is not self.u:
+            return out.fill(0.0)
+        c = self.responses()
+        a = np.abs(c)
+        coef = self.weights * (2.0 * c if self.squared else np.where(a > 0.0, c / np.where(a > 0.0, a, 1.0), 0.0))
+        Q = np.zeros((self.n_cases, self.n_cases))
+        r = 2 * np.arange(self.n_freq)
+        Q[r, r], Q[r, r + 1] = coef.real, coef.imag
+        return elasticity_handle(self.mesh).block_rotate(self.n_cases, Q, self.load(), out)
+
+
 def averageFunc(func: Function) -> LinearFunctional:
     """(1/|Omega|) int func dx for a DG0 Function (averageFunc, run_topo_opt_cantilever_beam.py:103-106)."""
     V = func.function_space
@@ -1785,6 +2107,21 @@ def pdeRes_harmonic(u, v, rho_e, fs, dss_list=None, omegas=None, density: float 
 def dynamic_compliance(u, fs, dss_list=None, weights=None, squared: bool = False) -> DynamicCompliance:
     """sum_l w_l |F_l . u_l| (or its squared form) of a harmonic state as a scalar output."""
     return DynamicCompliance(u, fs, dss_list, weights=weights, squared=squared)
+
+
+def pdeRes_harmonic_damped(u, v, rho_e, fs, dss_list=None, omegas=None, loss_factor: float = 0.0, rayleigh=(0.0, 0.0),
+                           density: float = 1.0, mass_law: str = "linear", E: float = 1.0, method: str = "SIMP",
+                           preconditioner: str = "jacobi") -> DampedHarmonicElasticityResidual:
+    """`pdeRes_harmonic` with a structural loss factor and Rayleigh damping (alpha, beta); ``u`` is a
+    Function(LoadCaseSpace(V, 2 len(fs))): Re and Im of every frequency."""
+    return DampedHarmonicElasticityResidual(u, rho_e, fs, dss_list, omegas=omegas, loss_factor=loss_factor, rayleigh=rayleigh,
+                                            density=density, mass_law=mass_law, E=E, nu=0.3, method=method,
+                                            preconditioner=preconditioner)
+
+
+def dynamic_compliance_damped(u, fs, dss_list=None, weights=None, squared: bool = False) -> DampedDynamicCompliance:
+    """sum_l w_l |F_l . u_l| (or its squared form) of a damped harmonic state, c_l complex, as a scalar output."""
+    return DampedDynamicCompliance(u, fs, dss_list, weights=weights, squared=squared)
 
 
 def pnorm_stress(u, rho_e, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0, q: float = 0.5,

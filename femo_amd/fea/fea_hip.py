@@ -25,8 +25,9 @@ from .function import Function, FunctionSpace, LoadCaseSpace, VectorFunctionSpac
 from .io import XDMFRecorder
 from .mesh import (BeamMesh, Mesh, createIntervalMesh, createRectangleMesh, createUnitCubeMesh, createUnitSquareMesh,
                    findNodeIndices, locate_dofs_geometrical, locate_entities_boundary, meshSize)
-from .elasticity import (Constant, Measure, buckling_aggregate, compliance_multiload, dynamic_compliance, eigenvalue_aggregate,
-                         meshtags, pdeRes_harmonic, pdeRes_multiload, pnorm_stress, pnorm_stress_multiload, von_Mises_stress,
+from .elasticity import (Constant, Measure, buckling_aggregate, compliance_multiload, dynamic_compliance,
+                         dynamic_compliance_damped, eigenvalue_aggregate, meshtags, pdeRes_harmonic, pdeRes_harmonic_damped,
+                         pdeRes_multiload, pnorm_stress, pnorm_stress_multiload, von_Mises_stress,
                          von_Mises_stress_multiload)
 
 

@@ -542,6 +542,10 @@ class KSP:
 
     def solve(self, b, x) -> None:
         """Symmetric operators: Jacobi-CG; otherwise BiCGSTAB on A or its explicit transpose."""
+        if self.transposed and hasattr(self.A, "backend_solve_transpose"):    # an operator that is not symmetric solves A^T itself
+            self.A.backend_solve_transpose(_as_vec(b), _as_vec(x), self.options)
+            self.info = self.A.info
+            return
         if hasattr(self.A, "backend_solve"):               # operators of a BackendForm bring their own solver
             self.A.backend_solve(_as_vec(b), _as_vec(x), self.options)
             self.info = self.A.info

@@ -816,7 +816,8 @@ int femo_elast_dyn_apply_multi(femo_elast* e, int masked, int n_cols, const doub
  * -- the norm of the PCG's test; phibar is the recurrence's estimate of sqrt(r . M^-1 r), which parts from the true residual
  * near eps cond.  info[n_cols]: converged 1 (also for a zero right-hand side, at iteration 0, and for an invariant subspace),
  * 0 (max_it reached) or -1 (a non-finite value); residual_norm = phibar, rhs_norm = beta1.  A finished column is frozen
- * while the others go on.  Shifted or deflated preconditioners and damping are out of scope.                             */
+ * while the others go on.  Damping: femo_elast_cdyn_solve_multi below.  Shifted or deflated preconditioners are out of
+ * scope.                                                                                                                  */
 int femo_elast_dyn_solve_multi(femo_elast* e, int n_cols, const double* shifts /* [n_cols] */, const femo_vec* b, femo_vec* x,
                                const femo_solver_opts* opts, femo_solve_info* info /* [n_cols] or NULL */);
 /* The mass part of dR/drho for R_l = (K - sigma_l M) u_l - F_l, called with scales s_l = -sigma_l and accumulate = 1 on top of
@@ -827,6 +828,30 @@ int femo_elast_dyn_solve_multi(femo_elast* e, int n_cols, const double* shifts /
 int femo_elast_mass_drho_multi(femo_elast* e, int mass_law, double density, int transpose, int n_cols,
                                const double* scales /* [n_cols] */, const femo_vec* rho, const femo_vec* u, const femo_vec* x,
                                femo_vec* y, int accumulate);
+/* Damped harmonic response (csrc/elast_damp.hip): Z_l u_l = F_l in complex arithmetic with the complex SYMMETRIC
+ *   Z_l = (K - sigma_l M) + i (cK_l K + cM_l M),   sigma_l = omega_l^2 >= 0, cK_l >= 0, cM_l >= 0
+ * (a structural loss factor eta and Rayleigh damping alpha M + beta K give cK = eta + omega beta, cM = omega alpha), K and M
+ * as for femo_elast_dyn_apply_multi.  Complex column l is the pair of real columns 2 l (Re) and 2 l + 1 (Im) of the layout
+ * above: 1 <= n_cols <= FEMO_ELAST_MAX_COLS / 2, vectors of 2 n_cols n_dof entries; shifts, ck, cm: n_cols values each.
+ * conj = 1 takes conj(Z_l), the transpose of the real operator on the 2 n_cols columns (adjoint solves).  No float atomics.
+ *
+ * y_l = a Z_l x_l + b f_l (f may be NULL) in ONE pass over the pattern: an entry of K and M is read once for both parts of
+ * the complex columns of a chunk.  masked = 1: identity rows / columns on the fixed dofs of both parts.  With ck = cm = 0
+ * each part has the bits of femo_elast_dyn_apply_multi on that real column.                                               */
+int femo_elast_cdyn_apply_multi(femo_elast* e, int masked, int conj, int n_cols, const double* shifts /* [n_cols] */,
+                                const double* ck /* [n_cols] */, const double* cm /* [n_cols] */, double a, const femo_vec* x,
+                                double b, const femo_vec* f /* or NULL */, femo_vec* y);
+/* Z_l x_l = b_l with the fixed set of the handle (x = b on the fixed dofs of both parts) by ONE batched preconditioned COCR
+ * (Sogabe & Zhang 2007: conjugate residuals in the unconjugated form x^T y), with the real preconditioners of
+ * femo_elast_dyn_solve_multi applied to both parts: one product and one preconditioner application per iteration.  With
+ * damping it converges at and next to a resonance, where the undamped MINRES does not.  It stops on sqrt(Re(r^H M^-1 r)) <=
+ * max(rtol beta1, atol), beta1 that of the first residual.  info[n_cols]: converged 1 (also for a zero right-hand side), 0
+ * (max_it reached) or -1 (a non-finite value, or a zero denominator of alpha or beta); residual_norm and rhs_norm as for the
+ * MINRES.  A finished column is frozen while the others go on, and a column has the same bits whatever n_cols is.  Out of
+ * scope: frequency-band integrals, shifted preconditioners, viscous dampers at points.                                  */
+int femo_elast_cdyn_solve_multi(femo_elast* e, int conj, int n_cols, const double* shifts /* [n_cols] */,
+                                const double* ck /* [n_cols] */, const double* cm /* [n_cols] */, const femo_vec* b, femo_vec* x,
+                                const femo_solver_opts* opts, femo_solve_info* info /* [n_cols] or NULL */);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
  *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
  * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices

@@ -33,6 +33,12 @@ and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the
                                                                  and the fused product (K - sigma M) x timed against apply_multi
                                                                  followed by mass_apply_multi on the same vectors: a warm-up, then
                                                                  5 alternated repeats, medians and spread)
+  ... --harmonic N --loss-factor X                              (N <= 4: the same frequencies through pdeRes_harmonic_damped /
+                                                                 dynamic_compliance_damped with the structural loss factor X as
+                                                                 well, every solve one batched COCR in complex arithmetic.  Adds
+                                                                 the COCR iterations and ms per column, and the time per iteration
+                                                                 of the COCR and the MINRES state solves, alternated: a warm-up of
+                                                                 both, then 5 pairs, medians)
 """
 from __future__ import annotations
 
@@ -409,10 +415,48 @@ def main_harmonic(args, ctx):
                dynamic_compliance=float(sim["dynamic_compliance"][0]), responses=[float(v) for v in fea.outputs_dict["dynamic_compliance"]["form"].responses()],
                gradient_norm=float(np.linalg.norm(g)))
     out.update(time_products(ctx, dev, rho.vec, shifts, density))
+    if args.loss_factor is not None:
+        out.update(damped_solves(ctx, res, u, fs, dss, fea.bc, args.loss_factor))
     if args.pc == "multilevel":
         pci = dev.pc_info()
         out.update(pc_levels=pci["levels"], pc_nodes=pci["nodes"], pc_lattice_bytes=pci["bytes"])
     print(json.dumps(out))
+
+
+def damped_solves(ctx, res, u, fs, dss, bcs, loss_factor, repeats=5):
+    """The frequencies of the undamped cycle through the damped forms with the structural loss factor ``loss_factor``: the
+    state solve of `pdeRes_harmonic_damped` and the adjoint solve of `dynamic_compliance_damped`, one batched COCR each, on
+    the density the undamped cycle ended with; beside them the undamped MINRES state solve of ``res`` again, alternated
+    with the damped one (``repeats`` pairs after a warm-up of both), for the time per iteration of the two loops."""
+    from femo_amd.engine import Vec
+    from femo_amd.fea.fea_hip import Function, LoadCaseSpace, dynamic_compliance_damped, pdeRes_harmonic_damped
+    N = res.n_cases
+    V = u.function_space.base
+    ud = Function(LoadCaseSpace(V, 2 * N))
+    dres = pdeRes_harmonic_damped(ud, None, res.rho, fs, dss, omegas=res.omegas, loss_factor=loss_factor, density=res.density,
+                                  mass_law=res.mass_law, method=res.method, preconditioner=res.preconditioner)
+    J = dynamic_compliance_damped(ud, fs, dss)
+    us = Function(u.function_space)
+    t_cocr, t_minres = [], []
+    for k in range(repeats + 1):
+        dres.solve_state(ud, bcs)
+        res.solve_state(us, bcs)
+        if k > 0:
+            t_cocr.append(dres.last_info["state"]["solve_ms"] / max(max(dres.last_info["state"]["iterations"]), 1))
+            t_minres.append(res.last_info["state"]["solve_ms"] / max(max(res.last_info["state"]["iterations"]), 1))
+    A = dres.matrix_class(dres, masked=True)
+    g = np.array(J.assemble_derivative(ud).get())
+    g[np.tile(dres._mask, 2 * N) == 1] = 0.0
+    A.backend_solve_transpose(Vec(ctx, g.size).set(g), Vec(ctx, g.size))
+    st, ad = dres.last_info["state"], dres.last_info["adjoint"]
+    return dict(loss_factor=loss_factor, cocr_iterations_forward=st["iterations"], cocr_iterations_adjoint=ad["iterations"],
+                cocr_solve_ms_forward=st["solve_ms"], cocr_solve_ms_adjoint=ad["solve_ms"],
+                cocr_iteration_us=1e3 * float(np.median(t_cocr)), cocr_iteration_us_all=[1e3 * float(v) for v in t_cocr],
+                minres_iteration_us_alternated=1e3 * float(np.median(t_minres)),
+                minres_iteration_us_alternated_all=[1e3 * float(v) for v in t_minres],
+                minres_iterations_alternated=res.last_info["state"]["iterations"],
+                cocr_over_minres_iteration=float(np.median(t_cocr) / np.median(t_minres)),
+                damped_dynamic_compliance=float(J.assemble_scalar()), damped_responses_abs=[float(abs(c)) for c in J.responses()])
 
 
 def scipy_cycle(mesh, facets, t, x0, radius):
@@ -462,12 +506,17 @@ def main():
                          "(top, bottom and right edge in 2-D; the faces z = 1, z = 0, y = 1, y = 0 beyond x = 3/4 and pieces of "
                          "x = 1 in 3-D; `load_cases` in this script lists them), solved as one batched PCG and timed against "
                          "sequential single-column solves")
+    ap.add_argument("--loss-factor", type=float, default=None,
+                    help="with --harmonic N <= 4: the same frequencies through the damped forms with this structural loss factor as "
+                         "well (complex arithmetic, one batched COCR per solve); adds the COCR iterations and ms beside the MINRES fields")
     ap.add_argument("--harmonic", type=int, default=0,
                     help="N harmonic responses of the tip load, 1 to 8, at frequencies below and between the first eigenfrequencies "
                          "of the start design: every solve one batched MINRES; prints the iterations per column and the cycle time")
     args = ap.parse_args()
     if not 1 <= args.load_cases <= 8:
         ap.error("--load-cases: 1 to 8")
+    if args.loss_factor is not None and not (1 <= args.harmonic <= 4 and np.isfinite(args.loss_factor) and args.loss_factor >= 0.0):
+        ap.error("--loss-factor: a finite value >= 0, with --harmonic 1 to 4")
     if not 0 <= args.harmonic <= 8 or (args.harmonic and (args.load_cases > 1 or args.stress)):
         ap.error("--harmonic: 1 to 8, without --load-cases and --stress")
     from femo_amd import _lib
