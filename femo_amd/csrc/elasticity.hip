@@ -12,6 +12,7 @@
 // ascending cell order, and the cell geometry is formed from `conn` in its own vertex order, so block (v, w) and block
 // (w, v)^T are sums of the same numbers in the same order -- K is symmetric entry for entry.
 #include "elast_internal.h"
+#include "filter_grid.h"
 
 #include <algorithm>
 #include <cmath>
@@ -254,11 +255,7 @@ __global__ void k_elast_export(int64_t n_rows, const int64_t* __restrict__ mptr,
 }
 
 // --------------------------------------------------------------------------------------------- filter ----
-struct Grid {
-  double lo[3];
-  double h;
-  int64_t n[3];
-};
+using Grid = FilterGrid;      // filter_grid.h: the host plans it, the kernels below index with it
 
 template <int D>
 __device__ __forceinline__ int64_t grid_cell(const Grid& G, const double* p, int64_t (&ijk)[3]) {
@@ -662,24 +659,8 @@ int femo_filter_create(femo_ctx* ctx, int dim, int64_t n, const double* coords, 
   FEMO_REQUIRE(radius > 0.0 && std::isfinite(radius), "filter: radius must be positive");
   // uniform grid, cell size >= r (the 3^d cells around a point hold every neighbour), at most ~ 4 n + 1024 cells
   Grid G{};
-  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  for (int k = 0; k < dim; ++k) { lo[k] = coords[k]; hi[k] = coords[k]; }
-  for (int64_t i = 0; i < n; ++i)
-    for (int k = 0; k < dim; ++k) { lo[k] = std::min(lo[k], coords[i * dim + k]); hi[k] = std::max(hi[k], coords[i * dim + k]); }
-  double h = radius;
-  for (;;) {
-    double cells = 1.0;
-    for (int k = 0; k < dim; ++k) cells *= std::floor((hi[k] - lo[k]) / h) + 1.0;
-    if (cells <= 4.0 * (double)n + 1024.0) break;
-    h *= 1.25;
-  }
-  G.h = h;
   int64_t ncell = 1;
-  for (int k = 0; k < 3; ++k) {
-    G.lo[k] = lo[k];
-    G.n[k] = k < dim ? (int64_t)std::floor((hi[k] - lo[k]) / h) + 1 : 1;
-    ncell *= G.n[k];
-  }
+  FEMO_REQUIRE(filter_grid_plan(dim, n, coords, radius, &G, &ncell) == FILTER_GRID_OK, "filter: coordinates must be finite");
   hipStream_t st = ctx->stream;
   auto* F = new femo_filter();
   F->ctx = ctx;

@@ -201,6 +201,17 @@ HostBlock* find_block(const void* p, size_t bytes) {     // g_mu held
   return nullptr;
 }
 
+// Does [p, p + bytes) share a byte with any known block?  (Blocks never intersect, so the only candidates are the first
+// block that starts at or after p and the one before it.)
+bool overlaps_block(const void* p, size_t bytes) {       // g_mu held
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  auto it = g_blocks.lower_bound(a);
+  if (it != g_blocks.end() && it->first < a + bytes) return true;          // starts inside the range (or at its base)
+  if (it == g_blocks.begin()) return false;
+  --it;
+  return a < reinterpret_cast<uintptr_t>(it->second.base) + it->second.bytes;   // the block before reaches into it
+}
+
 bool verify_enabled() { return getenv("FEMO_HOST_VERIFY") != nullptr; }
 
 // Entries per chunk of a deferred upload (femo_vec_set_host_deferred), a multiple of 256; 0: one copy.  FEMO_H2D_CHUNK_MB
@@ -431,7 +442,7 @@ int femo_host_register(void* p, int64_t bytes) {
   FEMO_REQUIRE(p != nullptr && bytes > 0, "bad argument");
   {
     std::lock_guard<std::mutex> lk(g_mu);
-    FEMO_REQUIRE(find_block(p, (size_t)bytes) == nullptr, "femo_host_register: range is already pinned");
+    FEMO_REQUIRE(!overlaps_block(p, (size_t)bytes), "femo_host_register: range is already pinned");
   }
   FEMO_HIP_CHECK(hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault));
   HostBlock b;
@@ -446,13 +457,17 @@ int femo_host_unregister(void* p) {
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_blocks.find(reinterpret_cast<uintptr_t>(p));
     FEMO_REQUIRE(it != g_blocks.end() && !it->second.pooled, "femo_host_unregister: not a registered range");
-    if (it->second.ready != nullptr) {
-      if (it->second.pending) (void)hipEventSynchronize(it->second.ready);
-      g_ev_free.push_back(it->second.ready);
-    }
+    if (it->second.ready != nullptr && it->second.pending) (void)hipEventSynchronize(it->second.ready);
+  }
+  // The record goes only once the runtime has let go of the range: if it refuses, the range is still pinned for it, and a
+  // registry that had forgotten it would hand the next array at this address to the staged path as if it were pageable.
+  FEMO_HIP_CHECK(hipHostUnregister(p));
+  std::lock_guard<std::mutex> lk(g_mu);
+  auto it = g_blocks.find(reinterpret_cast<uintptr_t>(p));
+  if (it != g_blocks.end() && !it->second.pooled) {
+    if (it->second.ready != nullptr) g_ev_free.push_back(it->second.ready);
     g_blocks.erase(it);
   }
-  FEMO_HIP_CHECK(hipHostUnregister(p));
   return 0;
 }
 

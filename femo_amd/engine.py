@@ -133,15 +133,45 @@ def auto_register(enabled: bool) -> None:
 _REG_LOCK = threading.RLock()       # emulated ranks are threads of one process: the two tables and the register call are one critical section
 
 
+# Ranges whose unpinning the library refused: the runtime may still hold them pinned although their arrays are gone.  A
+# later array that NumPy places on such a range is never pinned again (it stays on the staged path), and pin_stats() shows
+# the count -- a pin that outlives its array must not go unseen.
+_STALE: List[tuple] = []             # (address, nbytes)
+_PIN_COUNTS = dict(register_refused=0, unregister_failed=0)
+
+
 def _forget_owner(key: int) -> None:
     with _REG_LOCK:
         _SEEN.pop(key, None)
         rec = _REGISTERED.pop(key, None)
         if rec is not None:
             try:
-                _lib.load().femo_host_unregister(C.c_void_p(rec[0]))     # by the RECORDED address: the owner may have moved
+                status = _lib.load().femo_host_unregister(C.c_void_p(rec[0]))     # by the RECORDED address: the owner may have moved
             except Exception:
-                pass
+                status = -1
+            if status != 0:                      # runs from a finalizer: nobody to raise to, so keep the evidence
+                _STALE.append(rec)
+                _PIN_COUNTS["unregister_failed"] += 1
+
+
+def _intersects_stale(addr: int, nb: int) -> bool:
+    return any(addr < s + sn and s < addr + nb for s, sn in _STALE)
+
+
+def _try_register(key: int, addr: int, nb: int) -> bool:     # _REG_LOCK held
+    if _lib.load().femo_host_register(C.c_void_p(addr), nb) == 0:
+        _REGISTERED[key] = (addr, nb)
+        return True
+    _PIN_COUNTS["register_refused"] += 1
+    return False
+
+
+def pin_stats() -> dict:
+    """The state of the in-place pinning of caller arrays: owners seen and pinned now, registrations the library refused,
+    unpinnings it refused, and the ranges those left behind (never pinned again)."""
+    with _REG_LOCK:
+        return dict(seen=len(_SEEN), registered=len(_REGISTERED), register_refused=_PIN_COUNTS["register_refused"],
+                    unregister_failed=_PIN_COUNTS["unregister_failed"], stale=len(_STALE))
 
 
 def _owner_of(a: np.ndarray):
@@ -155,8 +185,9 @@ def _owner_of(a: np.ndarray):
 
 def _note_caller_array(a: np.ndarray) -> None:
     """Called with every caller-owned array a transfer entry point is handed (``Vec.set`` / ``get(out=)`` / ``add_to_host``).
-    ``ndarray.resize`` (an in-place realloc) of an array that was handed over is not supported: the old range would stay
-    pinned until the array is seen again."""
+    ``ndarray.resize`` (an in-place realloc) cannot move an array that was handed over: the first sight leaves a weak
+    reference on the owner, and NumPy refuses to resize an array that carries one.  Should an owner be met at another
+    address all the same, its old range is unpinned, by the recorded address, before anything else."""
     if not _AUTO_REGISTER or a.nbytes < AUTO_REGISTER_MIN_BYTES:
         return
     owner = _owner_of(a)
@@ -169,15 +200,16 @@ def _note_caller_array(a: np.ndarray) -> None:
             if rec == (addr, nb):
                 return
             _forget_owner(key)                   # resized in place: unpin the old range (by its recorded address) first
+        if _STALE and _intersects_stale(addr, nb):
+            _SEEN.pop(key, None)
+            return                               # the runtime may still hold part of this range: staged path, for good
         if _SEEN.get(key) != (addr, nb):
             if key not in _SEEN:
                 import weakref
                 weakref.finalize(owner, _forget_owner, key)
             _SEEN[key] = (addr, nb)
             return                               # first sight: staged path
-        if _lib.load().femo_host_register(C.c_void_p(addr), nb) == 0:
-            _REGISTERED[key] = (addr, nb)
-        else:
+        if not _try_register(key, addr, nb):
             _SEEN.pop(key, None)                 # could not pin (limits, overlap): stay on the staged path
 
 
@@ -195,13 +227,16 @@ def register(a: np.ndarray) -> bool:
             return True
         if rec is not None:
             _forget_owner(key)
+        if _STALE and _intersects_stale(addr, nb):
+            _SEEN.pop(key, None)
+            return False
         if key not in _SEEN:
             import weakref
             weakref.finalize(owner, _forget_owner, key)
         _SEEN[key] = (addr, nb)
-        if _lib.load().femo_host_register(C.c_void_p(addr), nb) == 0:
-            _REGISTERED[key] = (addr, nb)
+        if _try_register(key, addr, nb):
             return True
+        _SEEN.pop(key, None)                     # as after a refused second sight: the next two sights try again
         return False
 
 

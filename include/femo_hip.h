@@ -206,8 +206,8 @@ typedef struct femo_host_stats {
 int femo_host_alloc(int64_t bytes, void** out);
 int femo_host_free(void* p);
 int femo_host_trim(void);                    /* release the recycled blocks            */
-int femo_host_register(void* p, int64_t bytes);
-int femo_host_unregister(void* p);
+int femo_host_register(void* p, int64_t bytes);   /* refused when [p, p + bytes) shares a byte with any known block    */
+int femo_host_unregister(void* p);                 /* the record goes only after the runtime has let go of the range  */
 int femo_host_touch(void* p);                /* the block containing p was written on the host */
 int femo_host_is_pinned(const void* p, int64_t bytes);
 int femo_host_threads(void);
@@ -882,7 +882,8 @@ int femo_elast_export_csr(const femo_elast* e, int64_t* rowptr, int32_t* col, do
 int femo_elast_bench_spmv(femo_elast* e, const femo_vec* x, femo_vec* y, int reps, double* ms);
 /* GeneralFilterOperation (pre_processor/general_filter_model.py): W_ij = (r - d_ij) / sum_k (r - d_ik) over the points j
  * with d_ij <= r, r = beta h_avg, from n points in dim dimensions (the DG0 dof coordinates).  Built on the device: uniform
- * hash grid of cell size >= r, count / scan / fill, rows sorted by column; W^T is kept as its own CSR.                   */
+ * hash grid of cell size >= r, count / scan / fill, rows sorted by column; W^T is kept as its own CSR.  A coordinate
+ * that is NaN or +-inf is an error ("filter: coordinates must be finite"), found on the host before any device work.    */
 int femo_filter_create(femo_ctx* ctx, int dim, int64_t n, const double* coords, double radius, femo_filter** out);
 int femo_filter_destroy(femo_filter* f);
 int femo_filter_nnz(const femo_filter* f, int64_t* nnz);

@@ -569,3 +569,131 @@ def test_early_linearisation_is_the_same_cycle(ctx):
     ru, rg = rel(out[True][0], out[False][0]), rel(out[True][1], out[False][1])
     assert ru < 1e-10 and rg < 1e-10, (ru, rg)
     assert abs(out[True][2] - out[False][2]) <= 1e-10 * abs(out[False][2])
+
+
+def _runtime_query():
+    """``known(address)``: does the HIP runtime itself hold this host address as registered memory?  Asked through
+    hipPointerGetAttributes of the runtime library this process has loaded already (no second copy is opened)."""
+    import ctypes as C
+    path = None
+    with open("/proc/self/maps") as maps:
+        for line in maps:
+            if "libamdhip64.so" in line:
+                path = line.split()[-1]
+                break
+    assert path is not None, "the HIP runtime is not loaded"
+    hip = C.CDLL(path)
+
+    class Attr(C.Structure):                                 # hipPointerAttribute_t
+        _fields_ = [("type", C.c_int), ("device", C.c_int), ("devicePointer", C.c_void_p), ("hostPointer", C.c_void_p),
+                    ("isManaged", C.c_int), ("allocationFlags", C.c_uint)]
+
+    hip.hipPointerGetAttributes.argtypes = [C.POINTER(Attr), C.c_void_p]
+    hip.hipPointerGetAttributes.restype = C.c_int
+    hip.hipGetLastError.restype = C.c_int
+
+    def known(addr):
+        at = Attr()
+        rc = hip.hipPointerGetAttributes(C.byref(at), C.c_void_p(addr))
+        hip.hipGetLastError()                                # an unknown pointer may be reported as an error: not ours to keep
+        return rc == 0 and at.type == 1                      # hipMemoryTypeHost (0: unregistered)
+
+    known.hip = hip
+    return known
+
+
+def test_no_pin_outlives_its_array(ctx):
+    """Eight rounds of: pin an array in place, free it, and look at the array NumPy allocates next (usually at the same
+    address) BEFORE any copy touches it.  The library's registry, the runtime itself (hipPointerGetAttributes, with the
+    pinned array as the positive control) and the engine's counters must all say that nothing is pinned there; a pin that
+    outlived its array then fails an assertion here and not a DMA into memory the runtime only believes pinned."""
+    from femo_amd import engine as E
+    lib = E._lib.load()
+    known = _runtime_query()
+    n = 200_003
+    rng = np.random.default_rng(21)
+    v = E.Vec(ctx, n)
+    same = 0
+    for rnd in range(8):
+        a = rng.standard_normal(n)
+        ref = a.copy()
+        v.set(a); v.set(a)
+        v.get(out=a)
+        addr, nb = a.ctypes.data, a.nbytes
+        assert E.is_pinned(a) and np.array_equal(a, ref)
+        assert known(addr) and known(addr + nb - 8)          # positive control: the runtime holds the range
+        del a
+        gc.collect()
+        b = np.zeros(n)
+        same += int(b.ctypes.data == addr)
+        for p, size in ((addr, nb), (b.ctypes.data, b.nbytes)):
+            assert lib.femo_host_is_pinned(p, size) == 0 and lib.femo_host_is_pinned(p + size - 8, 8) == 0
+            assert not known(p) and not known(p + size - 8)
+        st = E.pin_stats()
+        assert st["unregister_failed"] == 0 and st["stale"] == 0
+        v.get(out=b)                                         # first sight of b: the staged path
+        assert np.array_equal(b, ref) and not E.is_pinned(b)
+        del b
+    print("no_pin_outlives_its_array: the next array took the freed address in %d of 8 rounds" % same)
+
+
+def test_register_refuses_every_overlap(ctx):
+    """With an array pinned in place, femo_host_register refuses -- before it asks the runtime -- a range that reaches into
+    it from below, one that starts inside it and ends behind it, one that encloses it, and one at the same base but longer
+    (a containment check alone lets all four through; the last one then overwrote the record).  The array stays pinned
+    and unpins cleanly."""
+    import ctypes as C
+    from femo_amd import engine as E
+    lib = E._lib.load()
+    n = 200_003
+    a = np.random.default_rng(22).standard_normal(n)
+    v = E.Vec(ctx, n)
+    v.set(a); v.set(a)
+    assert E.is_pinned(a)
+    addr, nb = a.ctypes.data, a.nbytes
+    for p, size in ((addr - 4096, 8192),                     # reaches in from below
+                    (addr + nb - 4096, 8192),                # starts inside, ends behind
+                    (addr - 4096, nb + 8192),                # encloses
+                    (addr, nb + 4096),                       # same base, longer
+                    (addr, nb), (addr + 4096, 4096)):        # the range itself and a part of it: refused before as well
+        with pytest.raises(E.FemoError, match="already pinned"):
+            E.check(lib.femo_host_register(C.c_void_p(p), size))
+        assert E.is_pinned(a) and lib.femo_host_is_pinned(addr, nb) == 1
+        assert lib.femo_host_is_pinned(addr - 4096, 4096) == 0 and lib.femo_host_is_pinned(addr + nb, 4096) == 0
+    out = np.empty(n)
+    v.get(out=out)
+    assert np.array_equal(out, a)                            # the pin still serves
+    del a
+    gc.collect()
+    assert lib.femo_host_is_pinned(addr, nb) == 0
+    st = E.pin_stats()
+    assert st["unregister_failed"] == 0 and st["stale"] == 0
+
+
+def test_a_refused_unregister_keeps_its_record(ctx):
+    """If the runtime refuses to let go of a range, the library must go on knowing it (it erased the record first and asked
+    second: the two then disagreed about what is pinned, and nobody could tell).  The refusal is arranged without harm:
+    the runtime's pin of a live array is taken away behind the library's back, so hipHostUnregister has nothing to release;
+    afterwards the runtime gets its pin back and the range is released in the ordinary way."""
+    import ctypes as C
+    from femo_amd import engine as E
+    lib = E._lib.load()
+    known = _runtime_query()
+    hip = known.hip
+    hip.hipHostRegister.argtypes = [C.c_void_p, C.c_size_t, C.c_uint]
+    hip.hipHostUnregister.argtypes = [C.c_void_p]
+    a = np.zeros(200_003)                                    # alive until the end of the test
+    addr, nb = a.ctypes.data, a.nbytes
+    E.check(lib.femo_host_register(C.c_void_p(addr), nb))
+    assert known(addr)
+    assert hip.hipHostUnregister(C.c_void_p(addr)) == 0      # behind the library's back
+    try:
+        assert not known(addr)
+        with pytest.raises(E.FemoError, match="hipHostUnregister"):
+            E.check(lib.femo_host_unregister(C.c_void_p(addr)))
+        hip.hipGetLastError()
+        assert lib.femo_host_is_pinned(addr, nb) == 1        # the record stays with the status
+    finally:
+        assert hip.hipHostRegister(C.c_void_p(addr), nb, 0) == 0
+    E.check(lib.femo_host_unregister(C.c_void_p(addr)))
+    assert lib.femo_host_is_pinned(addr, nb) == 0 and not known(addr)
