@@ -92,6 +92,8 @@ PROTOTYPES = {
     "femo_vec_get_host": (C.c_int, [H, C.c_void_p, c_i64]),
     "femo_vec_add_to_host": (C.c_int, [H, C.c_void_p, c_i64]),
     "femo_vec_get_host_async": (C.c_int, [H, C.c_void_p, c_i64]),
+    "femo_vec_get_host_promised": (C.c_int, [H, C.c_void_p, c_i64]),
+    "femo_host_forget": (C.c_int, [C.c_void_p]),
     "femo_vec_set_host_deferred": (C.c_int, [H, C.c_void_p, c_i64]),
     "femo_vec_await_upload": (C.c_int, [H]),
     "femo_host_wait": (C.c_int, [C.c_void_p]),
@@ -133,6 +135,7 @@ PROTOTYPES = {
     "femo_comm_stats": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
     "femo_mesh_pcg_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
     "femo_mesh_head_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
+    "femo_mesh_tail_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
     # Reissner-Mindlin shell
     "femo_shell_create": (C.c_int, [H, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(H)]),
     "femo_shell_destroy": (C.c_int, [H]),
@@ -191,6 +194,7 @@ PROTOTYPES = {
     "femo_dRdf_apply": (C.c_int, [H, H, C.c_int, H, H, C.c_int]),
     "femo_assemble_dRdf_cell": (C.c_int, [H, C.c_int, C.c_void_p, H]),
     "femo_dRdf_cell_apply": (C.c_int, [H, H, C.c_int, H, H, C.c_int]),
+    "femo_dRdf_cell_apply_T_add_to_host": (C.c_int, [H, H, H, H, C.c_void_p, c_i64]),
     "femo_mat_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "femo_mat_diagonal": (C.c_int, [H, H]),
     "femo_mat_prescale": (C.c_int, [H]),
@@ -269,9 +273,11 @@ PROTOTYPES = {
 
 # test-only entry points that an older build selected through FEMO_LIB (A/B measurements against a parent commit) may lack:
 # they stay unbound there and their wrappers raise
-# (and Newton's flagged passes: without them utils_hip takes the plain entry points, as under FEMO_NEWTON_FLAG=0)
+# (and Newton's flagged passes: without them utils_hip takes the plain entry points, as under FEMO_NEWTON_FLAG=0; the
+# streamed tail and results on demand: without them the product + add_to_host and the eager asynchronous copy-out)
 OPTIONAL = frozenset({"femo_mesh_pcg_info", "femo_mesh_head_info", "femo_mat_identity_solve_flag", "femo_vec_axpy_if",
-                      "femo_newton_rhs_linear_if", "femo_ctx_newton_flag_info"})
+                      "femo_newton_rhs_linear_if", "femo_ctx_newton_flag_info", "femo_mesh_tail_info",
+                      "femo_dRdf_cell_apply_T_add_to_host", "femo_vec_get_host_promised", "femo_host_forget"})
 
 
 class FemoError(RuntimeError):

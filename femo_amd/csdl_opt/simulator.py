@@ -276,6 +276,8 @@ class Simulator:
                             else:
                                 d_inputs[k] = np.zeros(np.size(self.values[k]))
                         op.compute_jacvec_product(inputs, outputs, d_inputs, {}, d_residuals, 'rev')
+                        if isinstance(d_residuals[state], np.ndarray):
+                            E.host_forget(d_residuals[state])    # the multiplier is never read here: a promised copy-out stays home
                         for v in d_inputs.values():
                             if self.pinned:
                                 E.host_touch(v)           # whatever wrote it: it mirrors no device vector now

@@ -252,6 +252,7 @@ int femo_ctx_destroy(femo_ctx* c) {
   }
   if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
   if (c->ev_copy) hipEventDestroy(c->ev_copy);
+  for (hipEvent_t e : c->d2h_chunk_ev) hipEventDestroy(e);
   hipFree(c->d_accum);
   hipEventDestroy(c->ev0); hipEventDestroy(c->ev1);
   for (auto& e : c->ev_pool) hipEventDestroy(e);
@@ -293,6 +294,7 @@ int femo_vec_wrap(femo_ctx* ctx, void* device_ptr, int64_t n, femo_vec** out) {
 
 int femo_vec_destroy(femo_vec* v) {
   if (!v) return 0;
+  if (v->promises > 0) femo_vec_resolve_promises(v);   // blocks that were promised this content get it now (waited for below)
   femo_vec_unregister(v);
   if (v->d2h_ev) {
     hipEventSynchronize(v->d2h_ev);                    // a copy-out may still be reading the vector
@@ -484,6 +486,13 @@ int femo_mesh_head_info(femo_mesh* m, int64_t* out, int count) {
   FEMO_REQUIRE(m && out && count >= 0, "bad argument");
   const int64_t v[4] = {(m->n_slices * FEMO_WAVE + FEMO_BLOCK - 1) / FEMO_BLOCK, m->head_blocks_early, m->head_streamed, m->load_builds};
   for (int k = 0; k < count && k < 4; ++k) out[k] = v[k];
+  return 0;
+}
+
+int femo_mesh_tail_info(femo_mesh* m, int64_t* out, int count) {
+  FEMO_REQUIRE(m && out && count >= 0, "bad argument");
+  const int64_t v[3] = {m->tail_streamed, m->tail_ranges, m->tail_plain};
+  for (int k = 0; k < count && k < 3; ++k) out[k] = v[k];
   return 0;
 }
 

@@ -1900,6 +1900,26 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_dRdf_cell_apply_T(int64_t n_cell
   }
 }
 
+// The streamed tail's range of the same product, fused with the sum of femo_vec_add_to_host: out = e + A^T x on n_cell cells
+// from the pointers' origin (the caller offsets conn, cv, e and out to the range's first cell; xin is gathered whole).  The sum
+// over the vertices runs in the order above, the product is rounded and then the sum: the bits of k_dRdf_cell_apply_T
+// followed by k_sum, which a contracted fma would not give (contraction is off in the body; __dmul_rn / __dadd_rn are
+// inline functions of a header compiled with contraction allowed, and the compiler fused the pair into one v_fmac_f64).
+template <int D>
+__global__ __launch_bounds__(FEMO_BLOCK) void k_dRdf_cell_apply_T_sum(int64_t n_cell, const int32_t* __restrict__ conn, const double* __restrict__ cv,
+                                                                      const double* __restrict__ xin, const double* __restrict__ e, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  for (int64_t c = (int64_t)blockIdx.x * FEMO_BLOCK + threadIdx.x; c < n_cell; c += (int64_t)gridDim.x * FEMO_BLOCK) {
+    int32_t v[D + 1];
+    load_conn<D>(conn, c, v);
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a <= D; ++a) s += xin[v[a]];
+    const double t = s * cv[c];                          // rounded here ...
+    out[c] = e[c] + t;                                   // ... and here
+  }
+}
+
 __global__ void k_scale_copy(int64_t n, double a, const double* __restrict__ x, double* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = a * x[i];
 }
@@ -1939,6 +1959,14 @@ int femo_launch_dRdf_cell_apply(femo_mesh* m, const double* cvals, int transpose
       hipLaunchKernelGGL(k_load_walk, dim3(nb), dim3(FEMO_BLOCK), 0, st, m->n_rows, nb, m->d_vptr, m->d_visit_cell, m->d_cell_t, y);
     }
   }
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_launch_dRdf_cell_apply_T_sum(femo_mesh* m, const double* cvals, const double* x, const double* e, double* out, int64_t c0, int64_t c1) {
+  FEMO_REQUIRE(0 <= c0 && c0 <= c1 && c1 <= m->n_cell, "cell range [%lld, %lld) outside the mesh", (long long)c0, (long long)c1);
+  if (c1 == c0) return 0;
+  FEMO_LAUNCH_D(m, k_dRdf_cell_apply_T_sum, cell_grid(c1 - c0), 0, m->ctx->stream, c1 - c0, m->d_conn + c0 * (m->tdim + 1), cvals + c0, x, e + c0, out + c0);
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
 }

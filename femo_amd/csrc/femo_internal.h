@@ -149,6 +149,9 @@ struct femo_ctx {
   hipEvent_t ev_copy = nullptr;
   double* d_accum = nullptr;
   int64_t accum_n = 0;
+  // streamed tail (femo_dRdf_cell_apply_T_add_to_host): d2h_chunk_ev[k] follows the kernel of range k on the compute stream and
+  // the copy stream waits for it before that range's copy.  The events stay with the context from call to call.
+  std::vector<hipEvent_t> d2h_chunk_ev;
   // CG workspace, grown on demand and reused across solves
   double *cg_r = nullptr, *cg_p = nullptr, *cg_q = nullptr, *cg_dinv = nullptr, *cg_s = nullptr;
   double *cg_t = nullptr, *cg_r0 = nullptr;
@@ -193,6 +196,9 @@ struct femo_vec {
   // makes the compute stream wait for it (every writing entry point calls femo_vec_touch BEFORE it launches)
   hipEvent_t d2h_ev = nullptr;
   bool d2h_pending = false;
+  // pinned blocks that were promised this vector's content (femo_vec_get_host_promised) and have not been sent it yet: the
+  // next writer sends it first (femo_vec_touch), so does femo_vec_destroy
+  int promises = 0;
   // a deferred upload of this vector (femo_vec_set_host_deferred) is (or was) in flight on the copy stream: the first
   // reader or writer on the compute stream waits for it (femo_vec_await; round 4: the f-independent half of the first
   // assembly pass, S A S and the preconditioner weights run under the upload of f)
@@ -207,6 +213,7 @@ struct femo_vec {
   int h2d_chunks = 0;
 };
 void femo_vec_wait_readers(femo_vec* v);   // hostmem.cpp
+void femo_vec_resolve_promises(femo_vec* v);   // hostmem.cpp: enqueue the copy-out of every block promised v's content
 extern "C" int femo_vec_await(const femo_vec* v);     // hostmem.cpp: compute stream waits for a deferred upload of v (no-op otherwise)
 // hostmem.cpp: the compute stream waits until entries [0, n_entries) of a chunked deferred upload of v have landed -- the
 // event of the chunk that holds entry n_entries - 1.  The upload stays pending unless that chunk is the last; without
@@ -217,6 +224,7 @@ extern "C" int femo_vec_await_prefix(const femo_vec* v, int64_t n_entries);
 int femo_vec_upload_chunks(const femo_vec* v, std::vector<int64_t>& ends);
 inline void femo_vec_touch(femo_vec* v) {
   if (!v) return;
+  if (v->promises > 0) femo_vec_resolve_promises(v);   // the old content leaves before the writer runs (d2h_pending below)
   ++v->gen;
   if (v->d2h_pending) femo_vec_wait_readers(v);
   if (v->h2d_pending) femo_vec_await(v);
@@ -296,6 +304,8 @@ struct femo_mesh {
   bool head_ready_built = false;
   std::vector<int64_t> head_ends;          // the streamed head in progress: chunk ends of f, cells and row blocks done so far
   int64_t head_c0 = 0, head_b0 = 0;
+  // test queries (femo_mesh_tail_info): streamed tails on this mesh, their ranges in all, and calls that took the product + add_to_host path
+  int64_t tail_streamed = 0, tail_ranges = 0, tail_plain = 0;
   // test queries (femo_mesh_head_info): load vectors formed on this mesh, streamed heads among them, and the row blocks
   // the last streamed head walked before its last range
   int64_t load_builds = 0, head_streamed = 0, head_blocks_early = 0;
@@ -537,6 +547,9 @@ int femo_launch_dRdf_apply(femo_mesh* m, const double* vals, int transpose, cons
                            double* y, int accumulate);
 int femo_launch_dRdf_cell(femo_mesh* m, double* cvals);
 int femo_launch_dRdf_cell_apply(femo_mesh* m, const double* cvals, int transpose, const double* x, double* y, int accumulate);
+// out[c] = e[c] + (sum_a x[v_a]) cvals[c] for the cells [c0, c1), product and sum rounded one after the other: what
+// femo_launch_dRdf_cell_apply (transposed, not accumulating) followed by femo_launch_sum(out, e, y) stores there
+int femo_launch_dRdf_cell_apply_T_sum(femo_mesh* m, const double* cvals, const double* x, const double* e, double* out, int64_t c0, int64_t c1);
 // key (optional): uid / generation of u and u_d -- M (u - u_d) formed for the value is kept for the gradient
 int femo_launch_functional_value(femo_mesh* m, int kind, const double* params, const double* u,
                                  const double* f, const double* ud, double* host_value, const uint64_t* key = nullptr);

@@ -29,6 +29,14 @@
 //  5. Accumulate on the device.  femo_vec_add_to_host into a block that still mirrors a live vector G forms
 //     G + v in a scratch vector and copies the sum out at DMA rate, instead of adding on the host while the
 //     chunks arrive (same bits: one IEEE addition per entry either way).
+//  6. The streamed tail (femo_dRdf_cell_apply_T_add_to_host).  The last statement of a reverse sweep, dJ/df += (dR/df)^T psi
+//     into such a block, forms the sum range by range -- product and addition in one kernel, no round trip of the product
+//     through HBM -- and sends each range down on the copy stream while the next one is computed.
+//  7. Promised results (femo_vec_get_host_promised).  A block is recorded as the copy of a vector and marked pending, but
+//     nothing travels until somebody asks for the bytes (femo_host_wait, femo_host_sync, any entry that reads the block) or
+//     the vector is about to change.  Handed back to femo_vec_set_host it is elided like any mirror; femo_host_forget drops
+//     it.  The multiplier of the adjoint solve is consumed on the device and never read on the host: its 8 n_vert bytes
+//     stay off the link that carries the gradient.
 #include <sched.h>
 #include <unistd.h>
 
@@ -180,6 +188,9 @@ struct HostBlock {
   hipEvent_t ready = nullptr;
   bool pending = false;
   femo_ctx* pend_ctx = nullptr;
+  // promised (femo_vec_get_host_promised): pending, recorded as the mirror of (src_uid, src_gen, src_n), and the copy is
+  // not enqueued yet -- `ready` has not been recorded for it.  Whoever needs the bytes sends it first (send_promised).
+  bool promised = false;
 };
 
 std::mutex g_mu;
@@ -229,6 +240,33 @@ int64_t h2d_chunk_entries() {
   return std::max<int64_t>(n, 256);
 }
 
+// The same for the streamed tail (femo_dRdf_cell_apply_T_add_to_host): FEMO_D2H_CHUNK_MB, read once per call; 0: the product
+// and femo_vec_add_to_host as two steps.
+constexpr double D2H_CHUNK_MB_DEFAULT = 64.0;
+int64_t d2h_chunk_entries() {
+  double mb = D2H_CHUNK_MB_DEFAULT;
+  if (const char* e = getenv("FEMO_D2H_CHUNK_MB")) {
+    char* end = nullptr;
+    const double v = strtod(e, &end);
+    if (end != e && v >= 0.0 && v <= 65536.0) mb = v;
+  }
+  if (mb == 0.0) return 0;
+  const int64_t n = (int64_t)(mb * 1048576.0 / sizeof(double)) / 256 * 256;
+  return std::max<int64_t>(n, 256);
+}
+
+// A copy-out is promised only from this size on.  Below it the copy costs no more than its own launch (1 MiB takes 19 us at
+// the link's 56 GB/s), so keeping it off the link saves nothing, while a promise that has to be kept in front of a writer
+// would put the copy and a wait of the compute stream where the eager copy had long landed; and a small result keeps
+// arriving by itself for a caller that reads it at once.  (The threshold of the in-place pinning of caller arrays,
+// engine.AUTO_REGISTER_MIN_BYTES; the deferred upload has one of its own, 8 MiB.)
+constexpr int64_t PROMISE_MIN_BYTES = int64_t(1) << 20;
+
+bool on_demand_enabled() {
+  const char* e = getenv("FEMO_D2H_ON_DEMAND");
+  return e == nullptr || strcmp(e, "0") != 0;
+}
+
 // events of blocks that left the registry, kept for the next block that needs one
 std::vector<hipEvent_t> g_ev_free;
 
@@ -239,8 +277,70 @@ hipEvent_t take_event() {                                // g_mu held
   return e;
 }
 
+int ensure_copy_stream(femo_ctx* c) {
+  if (c->copy_stream) return 0;
+  FEMO_HIP_CHECK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  FEMO_HIP_CHECK(hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
+  return 0;
+}
+
+// promised copy-outs ------------------------------------------------------------------
+struct PromisedCopy { double* host; femo_vec* v; int64_t n; hipEvent_t ready; };
+
+// The promise leaves block b: its copy is about to be enqueued (out != null) or will never be.  g_mu held.
+bool take_promise(HostBlock& b, PromisedCopy* out) {
+  if (!b.promised) return false;
+  b.promised = false;
+  auto it = g_live.find(b.src_uid);
+  femo_vec* v = it != g_live.end() ? it->second : nullptr;
+  if (v != nullptr && v->promises > 0) --v->promises;
+  if (out != nullptr) *out = PromisedCopy{reinterpret_cast<double*>(b.base), v, b.src_n, b.ready};
+  return true;
+}
+
+// Nobody will read the block under p: the promise is dropped, the block holds nothing the library knows of.
+void drop_promise(const void* p) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  HostBlock* b = p ? find_block(p, 1) : nullptr;
+  if (b != nullptr && take_promise(*b, nullptr)) { b->pending = false; b->src_uid = 0; }
+}
+
+// Exactly the copy the lazy branch of get_host_impl enqueues: behind everything on the compute stream so far, on the copy
+// stream, followed by the block's and the vector's events.  The block stays pending; not under g_mu.
+int send_promised(const PromisedCopy& pc) {
+  femo_vec* v = pc.v;
+  // every writer and femo_vec_destroy send a vector's promises first, so the vector of a promise is live and unchanged
+  FEMO_REQUIRE(v != nullptr && pc.ready != nullptr, "a promised copy-out has lost its vector");
+  femo_ctx* c = v->ctx;
+  FEMO_HIP_CHECK(hipSetDevice(c->device));
+  FEMO_TRY(ensure_copy_stream(c));
+  FEMO_TRY(femo_vec_await(v));
+  if (v->d2h_ev == nullptr) FEMO_HIP_CHECK(hipEventCreateWithFlags(&v->d2h_ev, hipEventDisableTiming));
+  FEMO_HIP_CHECK(hipEventRecord(c->ev_copy, c->stream));
+  FEMO_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, c->ev_copy, 0));
+  FEMO_HIP_CHECK(hipMemcpyAsync(pc.host, v->d, pc.n * sizeof(double), hipMemcpyDeviceToHost, c->copy_stream));
+  FEMO_HIP_CHECK(hipEventRecord(pc.ready, c->copy_stream));
+  FEMO_HIP_CHECK(hipEventRecord(v->d2h_ev, c->copy_stream));
+  v->d2h_pending = true;
+  std::lock_guard<std::mutex> lk(g_mu);
+  ++g_stats.d2h_async; g_stats.d2h_async_bytes += pc.n * 8;
+  return 0;
+}
+
+// The bytes of the block under p are needed: if they were only promised, they leave now.
+int resolve_block(const void* p) {
+  PromisedCopy pc{};
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    HostBlock* b = p ? find_block(p, 1) : nullptr;
+    if (b == nullptr || !take_promise(*b, &pc)) return 0;
+  }
+  return send_promised(pc);
+}
+
 // Wait until the asynchronous copy-out into the block containing p (if any) has landed.
 int wait_block(const void* p) {
+  FEMO_TRY(resolve_block(p));
   hipEvent_t ev = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -252,13 +352,6 @@ int wait_block(const void* p) {
   std::lock_guard<std::mutex> lk(g_mu);
   HostBlock* b = find_block(p, 1);
   if (b != nullptr && b->ready == ev && hipEventQuery(ev) == hipSuccess) b->pending = false;
-  return 0;
-}
-
-int ensure_copy_stream(femo_ctx* c) {
-  if (c->copy_stream) return 0;
-  FEMO_HIP_CHECK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  FEMO_HIP_CHECK(hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
   return 0;
 }
 
@@ -344,6 +437,21 @@ void femo_vec_wait_readers(femo_vec* v) {
   v->d2h_pending = false;
 }
 
+void femo_vec_resolve_promises(femo_vec* v) {
+  // called by femo_vec_touch in front of a writer of v and by femo_vec_destroy: the content the blocks were promised leaves
+  // first (the writer then waits for the copies through d2h_pending like for any copy-out in flight)
+  std::vector<PromisedCopy> todo;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (auto& kv : g_blocks) {
+      PromisedCopy pc{};
+      if (kv.second.promised && kv.second.src_uid == v->uid && take_promise(kv.second, &pc)) todo.push_back(pc);
+    }
+    v->promises = 0;
+  }
+  for (const PromisedCopy& pc : todo) (void)send_promised(pc);
+}
+
 void femo_vec_unregister(femo_vec* v) {
   if (!v->uid) return;
   std::lock_guard<std::mutex> lk(g_mu);
@@ -397,6 +505,7 @@ int femo_host_free(void* p) {
     auto it = g_blocks.find(reinterpret_cast<uintptr_t>(p));
     FEMO_REQUIRE(it != g_blocks.end() && it->second.pooled, "femo_host_free: not a block of femo_host_alloc");
     bytes = it->second.bytes;
+    if (take_promise(it->second, nullptr)) it->second.pending = false;   // nobody can read the block any more
     if (it->second.ready != nullptr) {
       if (it->second.pending) (void)hipEventSynchronize(it->second.ready);   // the DMA still owns the block
       g_ev_free.push_back(it->second.ready);
@@ -527,6 +636,7 @@ int femo_host_axpby(int64_t n, double a, const double* x, double b, double* y) {
   FEMO_REQUIRE((x && y) || n == 0, "null argument");
   if (n == 0) return 0;
   FEMO_TRY(wait_block(y));
+  FEMO_TRY(resolve_block(x));                            // x is read below, at once or behind its copy
   // y = a x with x a block that mirrors a device vector: y is then known to be a * that vector without its bytes
   // (femo_vec_set_host from y becomes a device-side scale).  If x is still on its way down the host pass is queued
   // behind the copy on the same stream instead of waiting for it here -- the reverse sweep negates dJ/du this way
@@ -658,7 +768,8 @@ int femo_vec_set_host(femo_vec* v, const double* host, int64_t n) {
   else { ++g_stats.h2d_staged; g_stats.h2d_staged_bytes += n * 8; }
   if (exact_base && v->uid != 0) {                       // the block is now an exact copy of v
     if (HostBlock* b = find_block(host, (size_t)n * sizeof(double))) {
-      if (reinterpret_cast<const char*>(host) == b->base && b->pooled) { b->src_uid = v->uid; b->src_gen = v->gen; b->src_n = n; b->src_scale = 1.0; }
+      // (a promised block keeps the vector that owes it the bytes)
+      if (reinterpret_cast<const char*>(host) == b->base && b->pooled && !b->promised) { b->src_uid = v->uid; b->src_gen = v->gen; b->src_n = n; b->src_scale = 1.0; }
     }
   }
   return 0;
@@ -763,6 +874,7 @@ static int get_host_impl(const femo_vec* v, double* host, int64_t n, int op, boo
   femo_ctx* c = v->ctx;
   FEMO_HIP_CHECK(hipSetDevice(c->device));
   FEMO_TRY(femo_vec_await(v));                           // a deferred upload of v must have landed before it is read back
+  if (op == 0) drop_promise(host);                       // overwritten whole: what it was promised need not travel
   FEMO_TRY(wait_block(host));                            // an earlier copy-out into the block must not land after this one
   bool pinned = false, exact_base = false;
   femo_vec* mirror = nullptr;                            // live vector the block is an exact copy of (op 1)
@@ -848,9 +960,124 @@ int femo_vec_get_host_async(const femo_vec* v, double* host, int64_t n) { return
 
 int femo_vec_add_to_host(const femo_vec* v, double* host, int64_t n) { return get_host_impl(v, host, n, 1, false); }
 
+// host = v, but only on demand: the block is recorded as the copy of v at its present generation and marked pending, and the
+// copy itself is enqueued by whoever first needs the bytes (wait_block, femo_host_sync) or is about to change v
+// (femo_vec_touch, femo_vec_destroy).  Only into a whole pooled block from an owned vector, from PROMISE_MIN_BYTES on; anything
+// else, and FEMO_D2H_ON_DEMAND=0, is femo_vec_get_host_async.
+int femo_vec_get_host_promised(const femo_vec* v, double* host, int64_t n) {
+  FEMO_REQUIRE(v && host, "null argument");
+  FEMO_REQUIRE(n <= v->n, "size mismatch: vector has %lld entries, host array %lld", (long long)v->n, (long long)n);
+  if (n == 0) return 0;
+  bool ok = v->uid != 0 && on_demand_enabled() && n * (int64_t)sizeof(double) >= PROMISE_MIN_BYTES;
+  if (ok) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    HostBlock* b = find_block(host, (size_t)n * sizeof(double));
+    ok = b != nullptr && b->pooled && reinterpret_cast<char*>(host) == b->base;
+  }
+  if (!ok) return get_host_impl(v, host, n, 0, true);
+  drop_promise(host);                                    // the target of another copy-out: what it was promised before need not travel
+  FEMO_TRY(wait_block(host));                            // an earlier copy-out into the block must not land after this one
+  femo_vec* vv = const_cast<femo_vec*>(v);
+  std::lock_guard<std::mutex> lk(g_mu);
+  HostBlock* b = find_block(host, (size_t)n * sizeof(double));
+  FEMO_REQUIRE(b != nullptr, "the block left the registry");
+  if (b->ready == nullptr) b->ready = take_event();
+  FEMO_REQUIRE(b->ready != nullptr, "could not create an event");
+  b->src_uid = v->uid; b->src_gen = v->gen; b->src_n = n; b->src_scale = 1.0; b->const_n = 0;
+  b->pending = true; b->pend_ctx = v->ctx; b->promised = true;
+  ++vv->promises;
+  return 0;
+}
+
+int femo_host_forget(const void* p) {
+  drop_promise(p);
+  return 0;
+}
+
 int femo_host_wait(const void* p) { return wait_block(p); }
 
+// host += (dR/df)^T x for the one-value-per-cell dR/df (femo_dRdf_cell_apply, transposed), the statement that ends a reverse
+// sweep.  Where host is a whole pooled block that is the unscaled exact copy of a live vector e of this context -- the condition
+// of the device sum in get_host_impl -- and the mesh lives on one rank, the cells are walked in ranges of FEMO_D2H_CHUNK_MB:
+// one launch forms e + (dR/df)^T x for a range in d_accum, an event follows it on the compute stream, and the range's
+// copy goes out on the copy stream behind that event while the next range is computed.  One wait at the end.  Everything
+// else is the product into y followed by femo_vec_add_to_host, as before; y is scratch either way.
+int femo_dRdf_cell_apply_T_add_to_host(femo_mesh* m, const femo_vec* cvals, const femo_vec* x, femo_vec* y, double* host, int64_t n) {
+  FEMO_REQUIRE(m && cvals && x && y && host, "null argument");
+  FEMO_REQUIRE(n == m->n_cell && cvals->n >= n && y->n >= n && x->n >= m->n_vert, "vector size mismatch in dRdf^T apply");
+  femo_ctx* c = m->ctx;
+  const int64_t chunk_env = d2h_chunk_entries();         // read once per call
+  femo_vec* mirror = nullptr;
+  if (chunk_env > 0 && n > 0 && c->nranks == 1 && m->n_nbr == 0 && cvals->ctx == c && x->ctx == c) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    HostBlock* b = find_block(host, (size_t)n * sizeof(double));
+    if (b != nullptr && b->pooled && reinterpret_cast<char*>(host) == b->base && b->src_uid != 0 && b->src_n >= n && b->src_scale == 1.0) {
+      auto it = g_live.find(b->src_uid);
+      if (it != g_live.end() && it->second->gen == b->src_gen && it->second->ctx == c) mirror = it->second;
+    }
+  }
+  if (mirror == nullptr) {
+    ++m->tail_plain;
+    FEMO_TRY(femo_dRdf_cell_apply(m, cvals, 1, x, y, 0));
+    return femo_vec_add_to_host(y, host, n);
+  }
+  FEMO_HIP_CHECK(hipSetDevice(c->device));
+  FEMO_TRY(femo_vec_await(cvals));
+  FEMO_TRY(femo_vec_await(x));
+  FEMO_TRY(femo_vec_await(mirror));
+  drop_promise(host);                                    // its content is read from the vector it mirrors, never from the block
+  FEMO_TRY(wait_block(host));                            // an earlier copy-out into the block must not land after this one
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (HostBlock* b = find_block(host, (size_t)n * sizeof(double))) { b->src_uid = 0; b->const_n = 0; }   // being overwritten
+  }
+  if (verify_enabled()) {
+    std::vector<double> chk((size_t)n);
+    FEMO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    FEMO_HIP_CHECK(hipMemcpy(chk.data(), mirror->d, n * sizeof(double), hipMemcpyDeviceToHost));
+    FEMO_REQUIRE(memcmp(chk.data(), host, (size_t)n * sizeof(double)) == 0,
+                 "FEMO_HOST_VERIFY: the block no longer holds the vector it is recorded to mirror");
+  }
+  if (c->accum_n < n) {
+    FEMO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (c->d_accum) FEMO_HIP_CHECK(hipFree(c->d_accum));
+    c->d_accum = nullptr; c->accum_n = 0;
+    FEMO_HIP_CHECK(hipMalloc(&c->d_accum, (size_t)n * sizeof(double)));
+    c->accum_n = n;
+  }
+  FEMO_TRY(ensure_copy_stream(c));
+  const int64_t chunk_n = std::max(chunk_env, ((n + 1023) / 1024 + 255) / 256 * 256);   // at most 1024 ranges
+  const int n_ranges = (int)((n + chunk_n - 1) / chunk_n);
+  while ((int)c->d2h_chunk_ev.size() < n_ranges) {       // kept with the context: none is created in a warmed-up cycle
+    hipEvent_t e = nullptr;
+    FEMO_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    c->d2h_chunk_ev.push_back(e);
+  }
+  for (int k = 0; k < n_ranges; ++k) {
+    const int64_t lo = k * chunk_n, hi = std::min(n, lo + chunk_n);
+    FEMO_TRY(femo_launch_dRdf_cell_apply_T_sum(m, cvals->d, x->d, mirror->d, c->d_accum, lo, hi));
+    FEMO_HIP_CHECK(hipEventRecord(c->d2h_chunk_ev[(size_t)k], c->stream));
+    FEMO_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, c->d2h_chunk_ev[(size_t)k], 0));
+    FEMO_HIP_CHECK(hipMemcpyAsync(host + lo, c->d_accum + lo, (hi - lo) * sizeof(double), hipMemcpyDeviceToHost, c->copy_stream));
+  }
+  // the one wait: every range has landed, and d_accum may be rewritten by the next call
+  FEMO_HIP_CHECK(hipStreamSynchronize(c->copy_stream));
+  ++m->tail_streamed; m->tail_ranges += n_ranges;
+  std::lock_guard<std::mutex> lk(g_mu);
+  ++g_stats.d2h_device_sum; g_stats.d2h_device_sum_bytes += n * 8;
+  return 0;
+}
+
 int femo_host_sync(void) {
+  std::vector<PromisedCopy> todo;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (auto& kv : g_blocks) {
+      PromisedCopy pc{};
+      if (take_promise(kv.second, &pc)) todo.push_back(pc);
+    }
+  }
+  for (const PromisedCopy& pc : todo) FEMO_TRY(send_promised(pc));
   std::vector<hipEvent_t> evs;
   {
     std::lock_guard<std::mutex> lk(g_mu);

@@ -100,6 +100,14 @@ def host_wait(a: np.ndarray) -> np.ndarray:
     return a
 
 
+def host_forget(a: np.ndarray) -> None:
+    """The caller will never read ``a``: a copy-out it was only promised (``Vec.get`` under ``lazy_results(on_demand=True)``)
+    is dropped instead of sent.  No-op for any other array."""
+    lib = _lib.load()
+    if hasattr(lib, "femo_host_forget"):
+        check(lib.femo_host_forget(C.c_void_p(a.ctypes.data)))
+
+
 def host_trim() -> None:
     """Release the recycled pinned blocks (femo_host_trim): between workloads of different sizes."""
     check(_lib.load().femo_host_trim())
@@ -244,17 +252,23 @@ _LAZY = threading.local()
 
 
 @contextlib.contextmanager
-def lazy_results(enabled: bool = True):
+def lazy_results(enabled: bool = True, on_demand: bool = False):
     """Inside the block ``Vec.get()`` (without ``out``) returns its pinned array before the bytes have landed:
     the copy runs on the context's copy stream while later kernels execute.  The caller promises that whoever
     reads the array with code of its own calls ``host_wait`` / ``host_sync`` first (the operator classes hand
-    such arrays only to a backend that set ``fea.async_results``)."""
-    prev = getattr(_LAZY, "on", False)
+    such arrays only to a backend that set ``fea.async_results``).
+
+    ``on_demand``: the copy is only promised (femo_vec_get_host_promised).  It leaves at the first ``host_wait`` /
+    ``host_sync`` / library call that reads the array, or in front of the next write of the vector; handed back to
+    ``Vec.set`` the array is elided without being read, and ``host_forget`` drops the promise.  For results that are
+    usually consumed on the device (the multiplier of an adjoint solve).  Results below 1 MiB leave at once all the same."""
+    prev, prev_od = getattr(_LAZY, "on", False), getattr(_LAZY, "on_demand", False)
     _LAZY.on = bool(enabled) or prev
+    _LAZY.on_demand = bool(enabled) and bool(on_demand)
     try:
         yield
     finally:
-        _LAZY.on = prev
+        _LAZY.on, _LAZY.on_demand = prev, prev_od
 
 
 _DEFER = threading.local()
@@ -459,7 +473,8 @@ class Vec:
             return out
         out = pinned_empty(n)
         if getattr(_LAZY, "on", False):
-            check(self.lib.femo_vec_get_host_async(self.handle, _ptr(out), n))
+            promised = getattr(_LAZY, "on_demand", False) and hasattr(self.lib, "femo_vec_get_host_promised")
+            check((self.lib.femo_vec_get_host_promised if promised else self.lib.femo_vec_get_host_async)(self.handle, _ptr(out), n))
         else:
             check(self.lib.femo_vec_get_host(self.handle, _ptr(out), n))
         out.flags.writeable = False
@@ -633,6 +648,14 @@ class DeviceMesh:
         v = (C.c_int64 * 4)()
         check(self.lib.femo_mesh_pcg_info(self.handle, v, 4))
         return {"merged": bool(v[0]), "ring_slots": int(v[1]), "flushes": int(v[2]), "ring_short": int(v[3])}
+
+    def tail_info(self):
+        """What ``dRdf_cell_apply_T_add_to_host`` did on this mesh: streamed calls, their ranges, plain calls (femo_hip_test.h)."""
+        if not hasattr(self.lib, "femo_mesh_tail_info"):
+            raise FemoError("femo_mesh_tail_info: not exported by this build of libfemo_hip.so")
+        v = (C.c_int64 * 3)()
+        check(self.lib.femo_mesh_tail_info(self.handle, v, 3))
+        return {"streamed": int(v[0]), "ranges": int(v[1]), "plain": int(v[2])}
 
     def head_info(self):
         """What the load vector of the Poisson forms did on this mesh: streamed heads and their ranges (femo_hip_test.h)."""
@@ -835,6 +858,18 @@ def assemble_dRdf_cell(mesh: DeviceMesh, pde: int, params, cvals: Vec) -> Vec:
 def dRdf_cell_apply(mesh: DeviceMesh, cvals: Vec, x: Vec, y: Vec, transpose: bool, accumulate: bool = False) -> Vec:
     check(mesh.lib.femo_dRdf_cell_apply(mesh.handle, cvals.handle, int(transpose), x.handle, y.handle, int(accumulate)))
     return y
+
+
+def dRdf_cell_apply_T_add_to_host(mesh: DeviceMesh, cvals: Vec, x: Vec, y: Vec, host: np.ndarray, n: int) -> np.ndarray:
+    """host[:n] += (dR/df)^T x with ``y`` as scratch: the product and ``y.add_to_host(host, n)``, streamed range by range where
+    the sum is formed on the device (femo_dRdf_cell_apply_T_add_to_host)."""
+    assert host.dtype == np.float64 and host.flags.c_contiguous and host.flags.writeable and host.size >= n
+    if not hasattr(mesh.lib, "femo_dRdf_cell_apply_T_add_to_host"):
+        dRdf_cell_apply(mesh, cvals, x, y, transpose=True)
+        return y.add_to_host(host, n)
+    _note_caller_array(host)
+    check(mesh.lib.femo_dRdf_cell_apply_T_add_to_host(mesh.handle, cvals.handle, x.handle, y.handle, _ptr(host), int(n)))
+    return host
 
 
 def newton_rhs(K: Mat, F: Vec, u: Vec, bc: DirichletSet, b: Vec) -> Vec:

@@ -151,14 +151,16 @@ class FEA(object):
         else:
             solveNonlinear(res, func, bc, self.PDE_SOLVER, self.REPORT, self.initialize)
 
-    def _linear_solve(self, operator, rhs_fn, rhs_values, sol_fn, ksp, device):
+    def _linear_solve(self, operator, rhs_fn, rhs_values, sol_fn, ksp, device, on_demand=False):
         setFuncArray(rhs_fn, rhs_values)
         sol_fn.vector.set(0.0)
         if ksp is None:
             solveKSP_mumps(operator, rhs_fn.vector, sol_fn.vector)
         else:
             ksp.solve(rhs_fn.vector, sol_fn.vector)
-        with E.lazy_results(self.async_results):
+        # on_demand: the solution is usually handed straight back to the library (the multiplier goes into the products of
+        # compute_jacvec_product): its copy-out is promised, and leaves only if somebody reads the array (engine.lazy_results)
+        with E.lazy_results(self.async_results, on_demand=on_demand):
             return getFuncArray(sol_fn, device=device)
 
     def solveLinearFwd(self, du, A, dR, dR_array, ksp=None, device=False):
@@ -174,7 +176,7 @@ class FEA(object):
     def solveLinearBwd(self, dR, A, du, du_array, ksp=None, device=False):
         """dR = A^-T du (fea_dolfinx.py:208-222).  With a cached ``ksp`` (linear_problem) the
         reference solves with A itself; here the cached object solves the same (symmetric) system."""
-        return self._linear_solve(transpose(A), du, du_array, dR, ksp, device)
+        return self._linear_solve(transpose(A), du, du_array, dR, ksp, device, on_demand=True)
 
     def projectFieldOutput(self, form, func):
         """fea_dolfinx.py:224-225"""

@@ -502,8 +502,12 @@ def _add_product(target, A, x, transposed: bool):
     ``d_inputs[arg] += ...`` statements of state_model.py:176-200.  For a NumPy target the sum is
     formed while the product is copied out of the device (no second pass over the host array)."""
     y = A.new_col_vec() if transposed else A.new_row_vec()
-    (A.multTranspose if transposed else A.mult)(_as_vec(x), y)
     n = A.getSizes()[1 if transposed else 0]
+    if (transposed and isinstance(A, CellMatrix) and A.uniform and isinstance(target, np.ndarray) and target.dtype == np.float64
+            and target.flags.c_contiguous and target.flags.writeable and target.size == n):
+        # the tail of a reverse sweep: product, sum and copy-out in one call, streamed where the sum is formed on the device
+        return E.dRdf_cell_apply_T_add_to_host(A.dmesh, A.vals, _as_vec(x), y, target, n)
+    (A.multTranspose if transposed else A.mult)(_as_vec(x), y)
     if isinstance(target, DeviceArray):
         target += DeviceArray(y, n)
         return target

@@ -220,6 +220,14 @@ int femo_host_axpby(int64_t n, double a, const double* x, double b, double* y);
  * block on its own calls femo_host_wait(p) (one block) or femo_host_sync() (all) first.                       */
 int femo_host_wait(const void* p);
 int femo_host_sync(void);
+/* Results on demand: femo_vec_get_host_promised records the block at `host` (a whole block of femo_host_alloc) as the copy of v
+ * and marks it in flight, but enqueues nothing.  The copy of femo_vec_get_host_async leaves when somebody needs the bytes
+ * (femo_host_wait, femo_host_sync, any entry point that reads the block) or v is about to be written or destroyed; handed
+ * back to femo_vec_set_host the block is elided like any mirror and is never read.  femo_host_forget(p): the caller will
+ * never read the block under p -- a copy it was promised is dropped.  Any other `host`, a wrapped vector, less than 1 MiB, or
+ * FEMO_D2H_ON_DEMAND=0 in the environment: femo_vec_get_host_async.                                                   */
+int femo_vec_get_host_promised(const femo_vec* v, double* host, int64_t n);
+int femo_host_forget(const void* p);
 int femo_host_get_stats(femo_host_stats* out);
 int femo_host_reset_stats(void);
 
@@ -295,6 +303,13 @@ int femo_assemble_dRdf(femo_mesh* mesh, int pde, const double* params,
 int femo_assemble_dRdf_cell(femo_mesh* mesh, int pde, const double* params, femo_vec* cvals);
 int femo_dRdf_cell_apply(femo_mesh* mesh, const femo_vec* cvals, int transpose,
                          const femo_vec* x, femo_vec* y, int accumulate);
+/* host[0:n] += (dR/df)^T x, n = n_cell: femo_dRdf_cell_apply(transpose) into the scratch vector y followed by
+ * femo_vec_add_to_host(y, host, n) -- and where that sum would be formed on the device (host is a whole pinned block that is
+ * the exact copy of a live vector, one rank), product, sum and copy-out run range by range of FEMO_D2H_CHUNK_MB MiB
+ * (default 64, fractions allowed, 0: the two steps above) with the copies on the copy stream under the next range's
+ * kernel.  The same bits either way.  y holds the product or is left untouched.                                       */
+int femo_dRdf_cell_apply_T_add_to_host(femo_mesh* mesh, const femo_vec* cvals, const femo_vec* x, femo_vec* y,
+                                       double* host, int64_t n);
 /* One pass over the mesh for any subset of: J_nobc (state_model.py:132), A_bc
  * (state_model.py:149) and the Newton right-hand side  rhs = F + K[:,bc](g-u),
  * rhs[bc] = u-g  (dolfinx NonlinearProblem.F/J [ext], utils_dolfinx.py:431).

@@ -52,6 +52,13 @@ int femo_mesh_pcg_info(femo_mesh* mesh, int64_t* out, int count);
  * field at the end of femo_host_stats.                                                                      */
 int femo_mesh_head_info(femo_mesh* mesh, int64_t* out, int count);
 
+/* ---- streamed tail: what femo_dRdf_cell_apply_T_add_to_host did on this mesh (tests) ----------------------------
+ * out[0] = calls that streamed product, sum and copy-out range by range;
+ * out[1] = ranges of those calls in all;
+ * out[2] = calls that took the product followed by femo_vec_add_to_host.
+ * Entries beyond `count` are not written.                                                                   */
+int femo_mesh_tail_info(femo_mesh* mesh, int64_t* out, int count);
+
 /* ---- Newton's flagged passes: what the launches that were handed the flag did (tests) -----------------------
  * Synchronises the context's stream, then
  * out[0] / out[1] = flagged launches of the axpy that left early / that ran (a device counter, bumped by workgroup 0);
