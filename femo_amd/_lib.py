@@ -136,6 +136,9 @@ PROTOTYPES = {
     "femo_mesh_pcg_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
     "femo_mesh_head_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
     "femo_mesh_tail_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
+    "femo_mat_compact_info": (C.c_int, [H, C.POINTER(C.c_int64), C.c_int]),
+    "femo_mat_spmv_scaled": (C.c_int, [H, C.c_int, H, H, c_f64p, C.POINTER(C.c_int)]),
+    "femo_mat_import_csr": (C.c_int, [H, C.c_void_p]),
     # Reissner-Mindlin shell
     "femo_shell_create": (C.c_int, [H, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(H)]),
     "femo_shell_destroy": (C.c_int, [H]),
@@ -277,7 +280,8 @@ PROTOTYPES = {
 # streamed tail and results on demand: without them the product + add_to_host and the eager asynchronous copy-out)
 OPTIONAL = frozenset({"femo_mesh_pcg_info", "femo_mesh_head_info", "femo_mat_identity_solve_flag", "femo_vec_axpy_if",
                       "femo_newton_rhs_linear_if", "femo_ctx_newton_flag_info", "femo_mesh_tail_info",
-                      "femo_dRdf_cell_apply_T_add_to_host", "femo_vec_get_host_promised", "femo_host_forget"})
+                      "femo_dRdf_cell_apply_T_add_to_host", "femo_vec_get_host_promised", "femo_host_forget",
+                      "femo_mat_compact_info", "femo_mat_spmv_scaled", "femo_mat_import_csr"})
 
 
 class FemoError(RuntimeError):

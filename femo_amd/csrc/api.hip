@@ -583,6 +583,7 @@ int femo_mat_destroy(femo_mat* A) {
   hipStreamSynchronize(A->mesh->ctx->stream);
   hipFree(A->d_diag); hipFree(A->d_vals); hipFree(A->d_valsT); hipFree(A->d_valsS); hipFree(A->d_s);
   hipFree(A->d_pcmask); hipFree(A->d_idrows);
+  femo_mat_compact_free(A);
   delete A;
   return 0;
 }
@@ -844,6 +845,48 @@ int femo_mat_export_csr(const femo_mat* A, int64_t* rowptr, int32_t* col, double
   FEMO_HIP_CHECK(hipMemcpyAsync(val, d_val, m->nnz * sizeof(double), hipMemcpyDeviceToHost, st));
   FEMO_HIP_CHECK(hipStreamSynchronize(st));
   hipFree(d_rp); hipFree(d_col); hipFree(d_val);
+  return 0;
+}
+
+// the inverse of k_export_rows: values in the order of femo_mat_export_csr into diag / vals (structural zeros stay zero)
+__global__ void k_import_rows(int64_t n_rows, const int64_t* __restrict__ mptr, const int32_t* __restrict__ cols,
+                              const int32_t* __restrict__ rowlen, const uint32_t* __restrict__ rowreal, double* __restrict__ diag,
+                              double* __restrict__ vals, const int64_t* __restrict__ rowptr, const double* __restrict__ ival) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_rows) return;
+  const int64_t base = mptr[row >> 6];
+  const int lane = (int)(row & 63);
+  const int len = rowlen[row];
+  int64_t o = rowptr[row];
+  bool placed = false;
+  const uint32_t real = rowreal[row];
+  for (int k = 0; k < len; ++k) {
+    if (k < 32 && !((real >> k) & 1u)) continue;
+    const int64_t e = femo_sell_index(base, k, lane);
+    if (!placed && cols[e] > row) { diag[row] = ival[o]; ++o; placed = true; }
+    vals[e] = ival[o]; ++o;
+  }
+  if (!placed) diag[row] = ival[o];
+}
+
+int femo_mat_import_csr(femo_mat* A, const double* val) {
+  FEMO_REQUIRE(A && val, "null argument");
+  const femo_mesh* m = A->mesh;
+  hipStream_t st = m->ctx->stream;
+  A->valsT_valid = false; A->scaled_valid = false; A->s_valid = false; femo_mat_touch(A);    // as an assembly into A
+  if (m->n_rows == 0) return 0;
+  std::vector<int64_t> rp;
+  FEMO_TRY(pattern_rowptr(m, rp));
+  int64_t* d_rp = nullptr; double* d_val = nullptr;
+  FEMO_HIP_CHECK(hipMalloc(&d_rp, rp.size() * sizeof(int64_t)));
+  FEMO_HIP_CHECK(hipMalloc(&d_val, m->nnz * sizeof(double)));
+  FEMO_HIP_CHECK(hipMemcpyAsync(d_rp, rp.data(), rp.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(d_val, val, m->nnz * sizeof(double), hipMemcpyHostToDevice, st));
+  FEMO_HIP_CHECK(hipMemsetAsync(A->d_vals, 0, std::max<int64_t>(m->sell_entries, 1) * sizeof(double), st));
+  hipLaunchKernelGGL(k_import_rows, dim3((unsigned)((m->n_rows + 255) / 256)), dim3(256), 0, st, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, m->d_rowreal, A->d_diag, A->d_vals, d_rp, d_val);
+  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  hipFree(d_rp); hipFree(d_val);
   return 0;
 }
 

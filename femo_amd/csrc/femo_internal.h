@@ -454,6 +454,19 @@ struct femo_mat {
   double* d_s = nullptr;      // S, n_vert entries (ghosts filled by halo exchange)
   bool scaled_valid = false, scaled_transposed = false;
   bool s_valid = false;       // d_s matches the current diagonal (set before the values are scaled)
+  // Compacted copy of S A S (spmv.hip: k_scale_sell, femo_launch_spmv): in every regular slice the slots whose 64 values are
+  // all zero are dropped and the live ones packed to the front, same slice offsets as d_valsS.  Built with S A S on one rank
+  // while the gate holds (femo_mat_compact_settle); valid only while scaled_valid is.
+  double* d_valsC = nullptr;    // sell_entries: live slots first in every regular slice's block, other slices verbatim
+  int32_t* d_cdelta = nullptr;  // n_slices x sdelta_stride: the live slots' deltas (other slices: a copy of the sdelta row)
+  int32_t* d_cpairs = nullptr;  // n_slices: pairs the product walks
+  unsigned long long* d_ccount = nullptr;   // [0] live pairs, [1] full pairs, [2] regular slices packed, [3] waves through: zero between builds
+  unsigned long long* h_ccount = nullptr;   // pinned host memory: the totals of the last build, stored by its last wave
+  bool compact_valid = false;   // the three arrays describe d_valsS as it stands (together with scaled_valid)
+  bool compact_off = false;     // the gate has fired, or the arrays could not be allocated: this handle builds no more
+  bool compact_pending = false; // a build has been enqueued whose counters the host has not looked at
+  mutable int64_t products_compact = 0, products_full = 0;   // S A S products launched on d_valsC / on d_valsS
+  int64_t compact_live = 0, compact_full = 0, compact_slices = 0;   // the counters of the last build the host has seen
   // identity rows of the last assembly (strong Dirichlet set): the Krylov loops solve them up front
   uint8_t* d_idrows = nullptr;  // n_vert bytes (own copy: the femo_bc may be destroyed before the matrix)
   bool has_idrows = false;
@@ -597,6 +610,10 @@ int femo_spmv_transposed_scatter(const femo_mat* A, const double* vals, bool uni
 inline bool femo_transpose_is_local(const femo_mesh* m) { return m->n_nbr == 0; }   // can A^T's values be formed on this rank?
 int femo_mat_ensure_s(femo_mat* A);                        // S = diag^-1/2 of the current assembly
 int femo_mat_ensure_scaled(femo_mat* A, bool transpose);   // ... and S A S (or S A^T S)
+// the gate of the compacted copy: looks at the counters of the last build.  Only where the host has just waited for
+// everything enqueued on the context's stream (the end of a solve with A): no synchronisation of its own
+void femo_mat_compact_settle(femo_mat* A);
+void femo_mat_compact_free(femo_mat* A);
 // y = K x - load outside the Dirichlet set, u - bcval on it (bcmask null: no set), one launch (spmv.hip); its two inputs
 // besides the operator: the cached load vector of f, and u with the prescribed values imposed (assemble.hip)
 // (n_range >= 0: the rows of slices [slice0, slice0 + n_range) only -- a range of the streamed head)

@@ -749,6 +749,7 @@ static int fill_info(femo_ctx* ctx, hipEvent_t end, femo_solve_info* info, int i
 static int finish_solve(femo_mat* A, const double* xh, femo_vec* x, bool zero_guess, femo_solve_info* info, int iters,
                         int conv, double rr) {
   FEMO_TRY(unscale_x(A, xh, x, zero_guess));
+  femo_mat_compact_settle(A);                    // (the host has just waited for the stream)
   return fill_info(A->mesh->ctx, A->mesh->ctx->ev1, info, iters, conv, rr);
 }
 
@@ -947,6 +948,7 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
   if (h_flags[0]) {                               // below the absolute tolerance (k_pcg_setup) or below atol_pc (first apply)
     info->pc_residual_norm = std::sqrt(gamma0);
     if (!spec_x && n > 0) FEMO_TRY(unscale_x(A, w.xh, x, opts->zero_guess));
+    femo_mat_compact_settle(A);
     return fill_info(ctx, ctx->ev1, info, 0, (h_flags[2] || !(rho0 == rho0)) ? -1 : 1, rho0);
   }
   FEMO_TRY(femo_mat_ensure_scaled(A, false));
@@ -1037,6 +1039,7 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
     if (g_end > 0.0 && gamma0 > g_end) m->pcg_rate = std::log(gamma0 / g_end) / iters;
   }
   FEMO_TRY(spmv.report(info));
+  femo_mat_compact_settle(A);                    // (the last poll waited for everything this solve enqueued)
   info->pc_residual_norm = std::sqrt(ctx->h_scal[MS_GAMMA + (iters & 1)]);
   return fill_info(ctx, end, info, iters, conv, ctx->h_scal[MS_RR]);
 }

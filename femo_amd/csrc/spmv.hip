@@ -10,6 +10,14 @@
 // (8 B/lane), fully coalesced.  Consecutive lanes are consecutive rows, so for
 // any bandwidth-reducing vertex order the x-gathers of one instruction fall in
 // a few cache lines.  Row sums are sequential per lane: deterministic.
+//
+// Compacted copy of S A S (k_scale_sell<true>, k_spmv_sell<.., CP = true>): on one rank the scaling also writes a copy in
+// which every regular slice keeps only the slots that are not zero in all 64 rows, packed to the front in their order; the
+// products of the Krylov loops walk it (femo_launch_spmv decides).  On a structured simplicial grid that is 6 of 14 slots in
+// 3-D and 4 of 6 in 2-D: the P1 stiffness is the 7- / 5-point stencil and the diagonal couplings cancel bit for bit.  A dead
+// slot contributed acc += 0 * x and the live ones keep their order, so for finite x the product is the same bits.  Two edge
+// cases differ: a non-finite x entry under a dead slot no longer turns the row into NaN, and a row
+// whose every term is -0.0 keeps -0.0 where the full product's + 0 * x made it +0.0.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -253,13 +261,16 @@ __device__ __forceinline__ double row_sum_gh(int npair, const double2* __restric
 // DOT: 0 none; 1 partial d.Ax into partials[block] (d = dvec or x); 2 additionally partial x.x,
 // 3 additionally partial Ax.Ax, into the next slot; 4 (merged BPX-PCG): x.Ax, Ax.Ax and dvec.Ax into three
 // consecutive slots (p.q, q.q, r.q: everything the single all-reduce of an iteration carries besides the lattice)
-template <int DOT, bool UNIT, bool NT = true, bool GH = false>
+// CP: `vals` is the compacted copy of S A S (femo_mat::d_valsC) with its cdelta / cpairs; a parameter of its own, so that
+// every other product is the code it was
+template <int DOT, bool UNIT, bool NT = true, bool GH = false, bool CP = false>
 __global__ __launch_bounds__(FEMO_BLOCK) void k_spmv_sell(
     int64_t n_rows, int64_t n_slices, const int64_t* __restrict__ mptr,
     const int32_t* __restrict__ cols, const int16_t* __restrict__ cols16, const int32_t* __restrict__ sdelta, int sdelta_stride,
     const double* __restrict__ vals, const double* __restrict__ diag, const double* __restrict__ x,
     double* __restrict__ y, double* __restrict__ partials, const int32_t* __restrict__ done,
-    const int32_t* __restrict__ slice_list, int64_t n_list, const double* __restrict__ dvec, SpmvGhost gh = SpmvGhost{}) {
+    const int32_t* __restrict__ slice_list, int64_t n_list, const double* __restrict__ dvec,
+    const int32_t* __restrict__ cdelta, const int32_t* __restrict__ cpairs, SpmvGhost gh = SpmvGhost{}) {
   if (done != nullptr && *done) return;
   bool waited = false;
   __shared__ double lds[FEMO_BLOCK / 64];
@@ -282,13 +293,15 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_spmv_sell(
     const bool bnd = GH && entry < 0;                      // sign bit: the slice has ghost columns (wave-uniform)
     const int64_t slice = GH ? (int64_t)(entry & 0x7FFFFFFF) : (slice_list ? (int64_t)entry : si);
     const int64_t base = mptr[slice];
-    const int npair = (int)((mptr[slice + 1] - base) >> 7);
+    // CP: a regular slice holds cpairs[slice] pairs of live slots at the front of its block, their deltas in cdelta; every
+    // other slice is as in the full copy (scalar loads, like the offsets)
+    const int npair = CP ? cpairs[slice] : (int)((mptr[slice + 1] - base) >> 7);
     const int64_t row = (slice << 6) + lane;
     if (GH && bnd && !waited) { spmv_halo_wait_wave(gh, lane); waited = true; }
     const double xr = x[row < n_rows ? row : 0];
     double acc = UNIT ? xr : diag[row] * xr;   // UNIT: symmetrically scaled operator, diagonal == 1
     const double2* __restrict__ v2 = reinterpret_cast<const double2*>(vals + base) + lane;
-    const int32_t* __restrict__ dl = sdelta + slice * sdelta_stride;
+    const int32_t* __restrict__ dl = (CP ? cdelta : sdelta) + slice * sdelta_stride;
     if (GH && bnd) {           // 32-bit columns whatever the slice's class; ghost columns come from the inbox
       const int2* __restrict__ c2 = reinterpret_cast<const int2*>(cols + base) + lane;
       acc = row_sum_gh<NT>(npair, v2, c2, x, gh.ghost - gh.n_own, (int)gh.n_own, acc);
@@ -460,12 +473,23 @@ __global__ void k_invsqrt_diag(int64_t n, const double* __restrict__ diag, doubl
 }
 
 // valsS[row][k] = s[row] * vals[row][k] * s[col]   (one wave per slice)
+// PACK: the same pass also writes the compacted copy (femo_mat::d_valsC, d_cdelta, d_cpairs).  In a regular slice a slot is
+// dead when the scaled value of all 64 lanes compares == 0.0 (+-0 both; NaN is live); the live slots go to the front of the
+// slice's block of outC in their order, pair-interleaved as in `out` (position p at base + (p >> 1) * 128 + lane * 2 + (p & 1)),
+// their deltas to cdelta; an odd count is padded with value 0.0 and delta 0 (the padding convention of the topology).  Every
+// other slice is copied verbatim, its sdelta row with its flags too.  count[0..2] += live pairs, full pairs, regular slices
+// (count[3]: waves that are through); hcount[0..2] receive the totals.
+template <bool PACK>
 __global__ __launch_bounds__(FEMO_BLOCK) void k_scale_sell(int64_t n_slices, const int64_t* __restrict__ mptr,
                                                            const int32_t* __restrict__ cols, const int32_t* __restrict__ sdelta,
                                                            int sdelta_stride, const double* __restrict__ vals,
-                                                           const double* __restrict__ s, int64_t n_vert, double* __restrict__ out) {
+                                                           const double* __restrict__ s, int64_t n_vert, double* __restrict__ out,
+                                                           double* __restrict__ outC, int32_t* __restrict__ cdelta,
+                                                           int32_t* __restrict__ cpairs, unsigned long long* __restrict__ count,
+                                                           unsigned long long* __restrict__ hcount) {
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * (FEMO_BLOCK / 64);
+  unsigned long long n_live = 0, n_full = 0, n_reg = 0;       // of this wave's slices (wave-uniform)
   for (int64_t slice = (int64_t)blockIdx.x * (FEMO_BLOCK / 64) + (threadIdx.x >> 6); slice < n_slices; slice += nw) {
     const int64_t base = mptr[slice];
     const int wm = (int)((mptr[slice + 1] - base) >> 6);
@@ -473,6 +497,10 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_scale_sell(int64_t n_slices, con
     const double si = s[row < n_vert ? row : 0];
     const int32_t* dl = sdelta + slice * sdelta_stride;
     const bool regular = dl[0] != INT32_MIN;
+    int32_t* cd = PACK ? cdelta + slice * sdelta_stride : nullptr;
+    int p = 0;                 // live slots so far (wave-uniform)
+    double2 pend;              // the pair being filled
+    pend.x = 0.0; pend.y = 0.0;
     for (int k = 0; k < wm; k += 2) {
       const int64_t idx = base + (int64_t)(k >> 1) * 128 + lane * 2;
       const double2 v = *reinterpret_cast<const double2*>(vals + idx);
@@ -483,6 +511,57 @@ __global__ __launch_bounds__(FEMO_BLOCK) void k_scale_sell(int64_t n_slices, con
       o.x = si * v.x * s[c0];
       o.y = si * v.y * s[c1];
       *reinterpret_cast<double2*>(out + idx) = o;
+      if (PACK) {
+        if (!regular) {
+          *reinterpret_cast<double2*>(outC + idx) = o;
+        } else {
+          // a slot at a time; `live` and p are wave-uniform, so each `if` is one branch of the whole wave
+          if (__ballot(!(o.x == 0.0)) != 0ull) {
+            if (p & 1) { pend.y = o.x; *reinterpret_cast<double2*>(outC + base + (int64_t)(p >> 1) * 128 + lane * 2) = pend; }
+            else pend.x = o.x;
+            if (lane == 0) cd[p] = dl[k];
+            ++p;
+          }
+          if (__ballot(!(o.y == 0.0)) != 0ull) {
+            if (p & 1) { pend.y = o.y; *reinterpret_cast<double2*>(outC + base + (int64_t)(p >> 1) * 128 + lane * 2) = pend; }
+            else pend.x = o.y;
+            if (lane == 0) cd[p] = dl[k + 1];
+            ++p;
+          }
+        }
+      }
+    }
+    if (PACK) {
+      if (regular) {
+        if (p & 1) {           // odd: the last half is padding (value 0.0, delta 0: the row itself)
+          pend.y = 0.0;
+          *reinterpret_cast<double2*>(outC + base + (int64_t)(p >> 1) * 128 + lane * 2) = pend;
+          if (lane == 0) cd[p] = 0;
+          ++p;
+        }
+        for (int i = p + lane; i < sdelta_stride; i += 64) cd[i] = 0;
+        ++n_reg;
+      } else {
+        for (int i = lane; i < sdelta_stride; i += 64) cd[i] = dl[i];
+        p = wm;
+      }
+      if (lane == 0) cpairs[slice] = p >> 1;
+      n_live += (unsigned long long)(p >> 1);
+      n_full += (unsigned long long)(wm >> 1);
+    }
+  }
+  if (PACK && lane == 0) {
+    if (n_live) atomicAdd(count, n_live);
+    if (n_full) atomicAdd(count + 1, n_full);
+    if (n_reg) atomicAdd(count + 2, n_reg);
+    // the wave that finishes last hands the totals to the host's copy (pinned memory: no copy is enqueued, so nothing of
+    // this queues behind an upload) and leaves the device counters at zero for the next build
+    __threadfence();
+    if (atomicAdd(count + 3, 1ull) == (unsigned long long)gridDim.x * (FEMO_BLOCK / 64) - 1ull) {
+      __threadfence();
+      for (int i = 0; i < 3; ++i)
+        __hip_atomic_store(hcount + i, atomicExch(count + i, 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      atomicExch(count + 3, 0ull);
     }
   }
 }
@@ -523,11 +602,22 @@ int femo_launch_spmv(const femo_mat* A, const double* x, double* y, const FemoSp
   if (n_walk == 0 && d.dots == FEMO_DOTS_NONE) return 0;
   const int g = d.slices ? subset_grid(m, n_walk) : femo_spmv_grid(m);
   hipStream_t st = d.stream ? d.stream : m->ctx->stream;
-#define FEMO_SPMV_ARGS m->n_rows, m->n_slices, m->d_mptr, m->d_cols, m->d_cols16, m->d_sdelta, m->sdelta_stride, d.vals, A->d_diag, x, y, d.partials, d.done, d.slices, d.n_slices, d.dvec
+  // The one place that decides for the compacted copy of S A S: a product on d_valsS over all slices of a mesh without
+  // ghosts, while the copy describes the values as they stand.  Slice lists, the ghost-aware walk, the transposed scatter
+  // and the products on K keep the full array.
+  const bool compact = d.vals == A->d_valsS && d.unit && A->scaled_valid && A->compact_valid && d.slices == nullptr && !d.ghost;
+  const double* vals = compact ? A->d_valsC : d.vals;
+  const int32_t* cdelta = compact ? A->d_cdelta : nullptr;
+  const int32_t* cpairs = compact ? A->d_cpairs : nullptr;
+  if (d.vals == A->d_valsS) ++(compact ? A->products_compact : A->products_full);
+#define FEMO_SPMV_ARGS m->n_rows, m->n_slices, m->d_mptr, m->d_cols, m->d_cols16, m->d_sdelta, m->sdelta_stride, vals, A->d_diag, x, y, d.partials, d.done, d.slices, d.n_slices, d.dvec, cdelta, cpairs
   const bool nt = matrix_streams(m);
 #define FEMO_SPMV_LAUNCH(DOT, UNIT)                                                                                     \
   do {                                                                                                                  \
-    if (nt) hipLaunchKernelGGL((k_spmv_sell<DOT, UNIT, true>), dim3(g), dim3(FEMO_BLOCK), 0, st, FEMO_SPMV_ARGS);        \
+    if (compact) {                                                                                                      \
+      if (nt) hipLaunchKernelGGL((k_spmv_sell<DOT, true, true, false, true>), dim3(g), dim3(FEMO_BLOCK), 0, st, FEMO_SPMV_ARGS);   \
+      else hipLaunchKernelGGL((k_spmv_sell<DOT, true, false, false, true>), dim3(g), dim3(FEMO_BLOCK), 0, st, FEMO_SPMV_ARGS);     \
+    } else if (nt) hipLaunchKernelGGL((k_spmv_sell<DOT, UNIT, true>), dim3(g), dim3(FEMO_BLOCK), 0, st, FEMO_SPMV_ARGS);  \
     else hipLaunchKernelGGL((k_spmv_sell<DOT, UNIT, false>), dim3(g), dim3(FEMO_BLOCK), 0, st, FEMO_SPMV_ARGS);          \
   } while (0)
   switch (d.dots) {
@@ -839,6 +929,62 @@ int femo_mat_ensure_s(femo_mat* A) {
   return 0;
 }
 
+// ---- the compacted copy of S A S: when it is built -------------------------------------------------------------------
+// One rank on a mesh without ghosts (the N-rank products walk slice lists and keep the full array), FEMO_SPMV_COMPACT not
+// "0" (read here, once per scaling -- the tests switch it -- never per launch), at least half of the mesh's slices regular
+// (only regular slices are packed), and a handle whose gate has not fired.
+static bool compact_wanted(const femo_mat* A) {
+  const femo_mesh* m = A->mesh;
+  if (A->compact_off || m->ctx->nranks > 1 || m->n_nbr > 0 || m->n_slices == 0) return false;
+  const char* e = getenv("FEMO_SPMV_COMPACT");
+  if (e != nullptr && e[0] == '0' && e[1] == 0) return false;
+  return 2 * m->n_regular >= m->n_slices;
+}
+
+// first use: the three arrays and the counters.  A device that has no room for a second copy of the values goes on with the
+// full one, and the handle does not ask again.
+static bool compact_alloc(femo_mat* A) {
+  const femo_mesh* m = A->mesh;
+  if (A->d_valsC != nullptr) return true;
+  const size_t nv = (size_t)std::max<int64_t>(m->sell_entries, 1) * sizeof(double) + 64;
+  const size_t nd = (size_t)m->n_slices * (size_t)m->sdelta_stride * sizeof(int32_t);
+  const bool ok = hipMalloc(&A->d_valsC, nv) == hipSuccess && hipMalloc(&A->d_cdelta, nd) == hipSuccess &&
+                  hipMalloc(&A->d_cpairs, (size_t)m->n_slices * sizeof(int32_t)) == hipSuccess &&
+                  hipMalloc(&A->d_ccount, 4 * sizeof(unsigned long long)) == hipSuccess &&
+                  hipHostMalloc(&A->h_ccount, 3 * sizeof(unsigned long long)) == hipSuccess &&
+                  hipMemsetAsync(A->d_ccount, 0, 4 * sizeof(unsigned long long), m->ctx->stream) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    femo_mat_compact_free(A);
+    A->compact_off = true;
+  }
+  return ok;
+}
+
+void femo_mat_compact_free(femo_mat* A) {
+  hipFree(A->d_valsC); hipFree(A->d_cdelta); hipFree(A->d_cpairs); hipFree(A->d_ccount);
+  if (A->h_ccount) hipHostFree(A->h_ccount);
+  A->d_valsC = nullptr; A->d_cdelta = nullptr; A->d_cpairs = nullptr; A->d_ccount = nullptr; A->h_ccount = nullptr;
+  A->compact_valid = false; A->compact_pending = false;
+}
+
+// The gate.  The rule: a handle whose last build found fewer than one pair in eight dead stops building the compaction, and
+// the decision is remembered for the handle (compact_off) -- below that the second write of the values per assembly, as
+// large as S A S itself, costs more than the shorter products return in any leg that does not hide it under an upload.
+// The build left its counters in pinned host memory; they are looked at here, where the host has just waited for the
+// stream anyway (the end of a solve with A), so the gate adds no synchronisation.  Nothing is in flight on the arrays then:
+// they are freed.
+void femo_mat_compact_settle(femo_mat* A) {
+  if (!A->compact_pending) return;
+  A->compact_pending = false;
+  const unsigned long long live = A->h_ccount[0], full = A->h_ccount[1];
+  A->compact_live = (int64_t)live; A->compact_full = (int64_t)full; A->compact_slices = (int64_t)A->h_ccount[2];
+  if ((full - live) * 8ull < full) {
+    femo_mat_compact_free(A);
+    A->compact_off = true;
+  }
+}
+
 // ... and the scaled values S A S (or S A^T S): what the Krylov loops iterate on.  Kept apart
 // from femo_mat_ensure_s because a solve that stops on its initial residual never needs them.
 int femo_mat_ensure_scaled(femo_mat* A, bool transpose) {
@@ -852,8 +998,20 @@ int femo_mat_ensure_scaled(femo_mat* A, bool transpose) {
   }
   FEMO_TRY(femo_mat_ensure_s(A));
   if (!A->d_valsS) FEMO_HIP_CHECK(hipMalloc(&A->d_valsS, std::max<int64_t>(m->sell_entries, 1) * sizeof(double) + 64));
+  A->compact_valid = false;
+  const bool pack = compact_wanted(A) && compact_alloc(A);
   if (m->n_slices > 0) {
-    hipLaunchKernelGGL(k_scale_sell, dim3(2048), dim3(FEMO_BLOCK), 0, ctx->stream, m->n_slices, m->d_mptr, m->d_cols, m->d_sdelta, m->sdelta_stride, src, A->d_s, m->n_vert, A->d_valsS);
+#define FEMO_SCALE_ARGS m->n_slices, m->d_mptr, m->d_cols, m->d_sdelta, m->sdelta_stride, src, A->d_s, m->n_vert, A->d_valsS
+    if (pack) {
+      // the packing is redone with every S A S (nothing is kept across assemblies); the kernel leaves the counters of this
+      // build in h_ccount, where the end of a solve looks at them (femo_mat_compact_settle)
+      hipLaunchKernelGGL((k_scale_sell<true>), dim3(2048), dim3(FEMO_BLOCK), 0, ctx->stream, FEMO_SCALE_ARGS, A->d_valsC, A->d_cdelta, A->d_cpairs, A->d_ccount, A->h_ccount);
+      A->compact_pending = true;
+      A->compact_valid = true;
+    } else {
+      hipLaunchKernelGGL((k_scale_sell<false>), dim3(2048), dim3(FEMO_BLOCK), 0, ctx->stream, FEMO_SCALE_ARGS, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (unsigned long long*)nullptr, (unsigned long long*)nullptr);
+    }
+#undef FEMO_SCALE_ARGS
     FEMO_HIP_CHECK(hipGetLastError());
   }
   A->scaled_valid = true;
@@ -888,4 +1046,38 @@ extern "C" int femo_mat_prescale(femo_mat* A) {
   FEMO_TRY(femo_mat_ensure_scaled(A, false));
   if (!A->bpx_ok) return 0;
   return femo_pc_weights_early(A->mesh, A->d_s, A->pc_has_mask ? A->d_pcmask : nullptr, femo_pc_weights_key(A));
+}
+
+// ---- test hooks (include/femo_hip_test.h) ------------------------------------------------------------------------------
+extern "C" int femo_mat_compact_info(femo_mat* A, int64_t* out, int count) {
+  FEMO_REQUIRE(A && out, "null argument");
+  FEMO_HIP_CHECK(hipStreamSynchronize(A->mesh->ctx->stream));
+  if (A->compact_pending) {                      // (the counters of the last build have landed; the gate is the solvers')
+    A->compact_live = (int64_t)A->h_ccount[0]; A->compact_full = (int64_t)A->h_ccount[1]; A->compact_slices = (int64_t)A->h_ccount[2];
+  }
+  const int64_t v[6] = {(A->scaled_valid && A->compact_valid) ? 1 : 0, A->compact_slices, A->compact_live, A->compact_full,
+                        A->products_compact, A->products_full};
+  for (int i = 0; i < 6 && i < count; ++i) out[i] = v[i];
+  return 0;
+}
+
+extern "C" int femo_mat_spmv_scaled(femo_mat* A, int dots, const femo_vec* x, femo_vec* y, double* partials, int* nblocks) {
+  FEMO_REQUIRE(A && x && y, "null argument");
+  FEMO_REQUIRE(dots >= FEMO_DOTS_NONE && dots <= FEMO_DOTS_DAX_AXAX, "dots %d: 0 .. 3", dots);
+  FEMO_REQUIRE(dots == FEMO_DOTS_NONE || (partials && nblocks), "product with dots: no room for the partials");
+  femo_mesh* m = A->mesh;
+  femo_ctx* ctx = m->ctx;
+  FEMO_REQUIRE(m->n_nbr == 0, "one rank only");
+  FEMO_REQUIRE(x->n >= m->n_vert && y->n >= m->n_rows && x->d != y->d, "vector size mismatch");
+  FEMO_TRY(femo_vec_await(x));
+  femo_vec_touch(y);
+  FEMO_TRY(femo_mat_ensure_scaled(A, false));
+  double* P = ctx->d_partials + 3 * FEMO_MAX_PARTIALS;
+  FEMO_TRY(femo_launch_spmv(A, x->d, y->d, {.vals = A->d_valsS, .unit = true, .dots = (FemoSpmvDots)dots, .partials = dots ? P : nullptr}));
+  const int g = femo_spmv_grid(m);
+  for (int k = 0; k < femo_spmv_dot_slots((FemoSpmvDots)dots); ++k)
+    FEMO_HIP_CHECK(hipMemcpyAsync(partials + (size_t)k * g, P + (size_t)k * FEMO_MAX_PARTIALS, (size_t)g * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  FEMO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  if (nblocks) *nblocks = g;
+  return 0;
 }

@@ -798,6 +798,29 @@ class Mat:
         check(self.lib.femo_solve_bicgstab(self.handle, int(transpose), b.handle, x.handle, C.byref(opts), C.byref(info)))
         return info
 
+    def compact_info(self) -> Dict[str, int]:
+        """The compacted copy of S A S (femo_mat_compact_info of femo_hip_test.h): whether it is valid, what the last build
+        packed and how many products read it / the full array."""
+        out = (C.c_int64 * 6)()
+        check(self.lib.femo_mat_compact_info(self.handle, out, 6))
+        return dict(zip(("valid", "slices", "live_pairs", "full_pairs", "products_compact", "products_full"), (int(v) for v in out)))
+
+    def spmv_scaled(self, dots: int, x: Vec, y: Vec):
+        """y = (S A S) x as the Krylov loops launch it (femo_mat_spmv_scaled, tests): returns the per-block partial sums of
+        variant ``dots`` as an array of shape (sums, blocks)."""
+        part = np.zeros(2 * 2048, np.float64)
+        nb = C.c_int(0)
+        check(self.lib.femo_mat_spmv_scaled(self.handle, int(dots), x.handle, y.handle, part.ctypes.data_as(C.POINTER(C.c_double)), C.byref(nb)))
+        sums = {0: 0, 1: 1, 2: 2, 3: 2}[int(dots)]
+        return part[:sums * nb.value].reshape(sums, nb.value).copy()
+
+    def import_csr(self, val) -> "Mat":
+        """Chosen values, in the order of ``export_csr`` (femo_mat_import_csr, tests): counts as an assembly."""
+        val = _f64(val)
+        assert val.size == self.mesh.info["nnz"]
+        check(self.lib.femo_mat_import_csr(self.handle, _ptr(val)))
+        return self
+
     def bench_spmv(self, x: Vec, y: Vec, reps: int = 50) -> float:
         ms = C.c_double(0.0)
         check(self.lib.femo_bench_spmv(self.handle, x.handle, y.handle, reps, C.byref(ms)))

@@ -69,6 +69,28 @@ int femo_mesh_tail_info(femo_mesh* mesh, int64_t* out, int count);
  * Counters run from the creation of the context.  Entries beyond `count` are not written.                    */
 int femo_ctx_newton_flag_info(femo_ctx* ctx, int64_t* out, int count);
 
+/* ---- compacted copy of S A S: what the scaling built and which copy the products read (tests) ------------------
+ * The scaling S A S of a matrix also writes a copy in which every regular slice keeps only the slots that are not zero
+ * in all 64 rows (one rank, FEMO_SPMV_COMPACT not 0, at least half of the slices regular); the products of the Krylov
+ * loops read it while it is valid.  Synchronises the context's stream, then
+ * out[0] = 1 if the copy describes the scaled values as they stand, else 0;
+ * out[1] = regular slices the last build packed;
+ * out[2] / out[3] = pairs the product walks in the copy / in the full array, over all slices, of the last build;
+ * out[4] / out[5] = products on S A S launched on the copy / on the full array, from the creation of the matrix.
+ * A handle whose build finds fewer than one pair in eight dead stops building the copy at the end of the first solve
+ * that follows (out[0] = 0 from then on; out[1..3] keep the figures of that build).  Entries beyond `count` are not
+ * written.                                                                                                   */
+int femo_mat_compact_info(femo_mat* A, int64_t* out, int count);
+
+/* y = (S A S) x: the launch the Krylov loops issue (scaling the matrix first if need be), with the fused partial sums
+ * of variant `dots` (0 none, 1 x.Ax, 2 x.Ax | x.x, 3 x.Ax | Ax.Ax) copied to `partials` (host; *nblocks per sum, one
+ * sum after the other; room for 2 x 2048).  One rank.                                                        */
+int femo_mat_spmv_scaled(femo_mat* A, int dots, const femo_vec* x, femo_vec* y, double* partials, int* nblocks);
+
+/* Chosen values in a matrix: `val` in the order of femo_mat_export_csr (nnz entries, the diagonal among them).
+ * Counts as an assembly into A: everything derived from the old values is invalid.                           */
+int femo_mat_import_csr(femo_mat* A, const double* val);
+
 #ifdef __cplusplus
 }
 #endif
