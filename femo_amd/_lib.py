@@ -43,6 +43,10 @@ class SolverOpts(C.Structure):
                 ("zero_guess", C.c_int32), ("check_every", C.c_int32), ("pc", C.c_int32), ("atol_pc", C.c_double)]
 
 
+class NewmarkParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("c_m", C.c_double), ("c_k", C.c_double)]
+
+
 class SolveInfo(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32),
                 ("residual_norm", C.c_double), ("pc_residual_norm", C.c_double), ("pc_rhs_norm", C.c_double),
@@ -260,6 +264,14 @@ PROTOTYPES = {
     "femo_elast_cdyn_solve_multi": (C.c_int, [H, C.c_int, C.c_int, c_f64p, c_f64p, c_f64p, H, H, C.POINTER(SolverOpts),
                                               C.POINTER(SolveInfo)]),
     "femo_elast_mass_drho_multi": (C.c_int, [H, C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, H, H, H, H, C.c_int]),
+    "femo_elast_newmark_rhs": (C.c_int, [H, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, H, H, H]),
+    "femo_elast_newmark_march": (C.c_int, [H, C.POINTER(NewmarkParams), C.c_int, C.c_int, H, H, c_f64p, H, C.POINTER(SolverOpts),
+                                           C.c_int, C.POINTER(SolveInfo), C.POINTER(C.c_int32)]),
+    "femo_elast_newmark_apply": (C.c_int, [H, C.POINTER(NewmarkParams), C.c_int, C.c_int, C.c_int, H, H]),
+    "femo_elast_newmark_drho": (C.c_int, [H, C.POINTER(NewmarkParams), C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, H, H, H, H, C.c_int]),
+    "femo_elast_newmark_dots": (C.c_int, [H, C.c_int, H, H, c_f64p]),
+    "femo_elast_newmark_outer": (C.c_int, [H, C.c_int, c_f64p, H, H]),
     "femo_elast_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "femo_elast_pc_setup": (C.c_int, [H, C.c_double]),
     "femo_elast_pc_info": (C.c_int, [H, c_i64p]),

@@ -18,7 +18,7 @@ from femo_amd.csdl_opt._csdl_compat import CustomImplicitOperation, Model, custo
 from femo_amd.engine import deferred_uploads, host_wait, lazy_results
 from femo_amd.fea.fea_hip import FEA
 from femo_amd.fea.forms import BackendForm
-from femo_amd.fea.function import LoadCaseSpace
+from femo_amd.fea.function import LoadCaseSpace, TimeHistorySpace
 from femo_amd.fea.utils_hip import (DeviceArray, SparseMatrix, addMatVecProductBwd, addMatVecProductFwd,
                                     assembleMatrix, assembleSystem, assembleVector, computePartials,
                                     createFunction, cycle_linearisation, getFuncArray, setUpKSP_MUMPS, update,
@@ -79,13 +79,15 @@ class StateOperation(CustomImplicitOperation):
         """Only with ``fea.consistent_bc_partials`` (not reference behaviour): zero the Dirichlet
         entries of the multiplier before the products, which turns the adjoint total into the exact
         reduced gradient (used to check against finite differences).  In every column of a
-        ``LoadCaseSpace`` state."""
+        ``LoadCaseSpace`` state and every step of a ``TimeHistorySpace`` one."""
         if not (self.fea.consistent_bc_partials and self.bcs):
             return values
         dofs = np.unique(np.concatenate([bc.dofs for bc in self.bcs]))
         space = self.state['function'].function_space
         if isinstance(space, LoadCaseSpace):               # bcs are numbered in the base space and hold for every column
             dofs = (dofs[None, :] + space.base.dim * np.arange(space.n_cases)[:, None]).ravel()
+        elif isinstance(space, TimeHistorySpace):          # ... and for every step of a time history
+            dofs = (dofs[None, :] + space.base.dim * np.arange(space.n_steps)[:, None]).ravel()
         if isinstance(values, np.ndarray):
             host_wait(values)          # apply_inverse_jacobian may have returned it while its copy-out is in flight
         # a DeviceArray's own conversion hands out the read-only array of Vec.get: copy that

@@ -458,7 +458,7 @@ int cocr_solve(femo_elast* e, int n_cols, const Damping& zd, const femo_vec* b, 
     if (ml) {
       if (step) { if (e->d == 2) FEMO_COCR_DIR(2, true, false, z, mq); else FEMO_COCR_DIR(3, true, false, z, mq); }
       FEMO_TRY(femo_elast_pc_step(e, false, nr, nullptr, step ? q : r, nullptr, nullptr, step ? mq : z, nullptr, e->w_s, e->w_part,
-                                  ps, e->w_flag));
+                                  ps, e->w_flag, e->d_dinv));
       if (step) hipLaunchKernelGGL(k_cocr_dot<false>, dim3(gp, L), dim3(EB), 0, st, n, q, mq, e->w_part, ps, e->w_flag);
       else hipLaunchKernelGGL(k_cocr_dot<true>, dim3(gp, L), dim3(EB), 0, st, n, r, z, e->w_part, ps, e->w_flag);
       return 0;

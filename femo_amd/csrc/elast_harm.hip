@@ -510,7 +510,8 @@ int minres_solve(femo_elast* e, int n_cols, const ColScalars& sig, const femo_ve
   auto precond = [&](bool step) -> int {
     if (ml) {
       if (step) { if (e->d == 2) FEMO_LANCZOS(2, true, false); else FEMO_LANCZOS(3, true, false); }
-      return femo_elast_pc_step(e, false, n_cols, nullptr, r2, nullptr, nullptr, z, nullptr, e->w_s, e->w_part, ps, e->w_flag);
+      return femo_elast_pc_step(e, false, n_cols, nullptr, r2, nullptr, nullptr, z, nullptr, e->w_s, e->w_part, ps, e->w_flag,
+                                e->d_dinv);
     }
     if (e->d == 2) { if (step) FEMO_LANCZOS(2, true, true); else FEMO_LANCZOS(2, false, true); }
     else { if (step) FEMO_LANCZOS(3, true, true); else FEMO_LANCZOS(3, false, true); }
@@ -564,6 +565,13 @@ int minres_solve(femo_elast* e, int n_cols, const ColScalars& sig, const femo_ve
 }
 
 }  // namespace
+
+int femo_elast_dyn_spmv(femo_elast* e, bool masked, int n_cols, double shift, double a, const double* x, double b, const double* f,
+                        double* y, double* part, int64_t part_stride, const int32_t* done) {
+  ColScalars sig;
+  for (int l = 0; l < EMC; ++l) sig.v[l] = shift;
+  return dyn_spmv(e, masked, n_cols, sig, a, x, b, f, y, part, part_stride, done);
+}
 
 // the three extra vectors of the MINRES loop (r1, w1, w2) for at least n_cols columns, its scalars and their pinned mirror
 int femo_elast_harm_reserve(femo_elast* e, int n_cols, const char* who) {

@@ -2,8 +2,8 @@
 // (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, elast_block.hip
 // (block linear algebra and the block iteration of the eigen solves), elast_eig.hip (mass product and the eigenfrequency
 // pencil), elast_buckle.hip (geometric stiffness and the buckling pencil), elast_harm.hip (assembled mass, shifted
-// product and MINRES of the harmonic response) and elast_damp.hip (complex product and COCR of the damped response).  Not
-// part of the ABI.
+// product and MINRES of the harmonic response), elast_damp.hip (complex product and COCR of the damped response) and
+// elast_transient.hip (Newmark march, its banded product and dR/drho).  Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -60,6 +60,10 @@ struct femo_elast {
   double* w_ms = nullptr;
   double* h_ms = nullptr;       // pinned
   // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
+  // Newmark march (elast_transient.hip), on first use: the step's right-hand side, the two windows of FEMO_ELAST_MAX_COLS
+  // combined columns of dR/drho (w_nm: 1 + 2 FEMO_ELAST_MAX_COLS vectors) and the inverse diagonal blocks of K + sigma M
+  double* w_nm = nullptr;
+  double* d_nm_dinv = nullptr;
   femo_elast_pc* pc = nullptr;
   bool pc_dirty = true;
   int method = 0;                    // of the last femo_elast_assemble ...
@@ -100,9 +104,11 @@ int femo_elast_pc_build(femo_elast* e, const double* rho);
 // k_pc_coarse: one workgroup per column): what k_pcg_precond does with z = M^-1 r of the multilevel form.
 // update: x += alpha p, r -= alpha q first (alpha = s[S_ALPHA]; a column whose flag[0] is set is skipped).  pinit != null:
 // p = z as well.  Vectors: column l at + l * n_dof; s, flag: EMS_STRIDE / EMF_STRIDE apart; part: part_stride apart.  The
-// lattice work vectors grow here when n_cols exceeds what they hold.
+// lattice work vectors grow here when n_cols exceeds what they hold.  dinv: the inverse diagonal blocks of the Jacobi term
+// (e->d_dinv for K itself).
 int femo_elast_pc_step(femo_elast* e, bool update, int n_cols, double* x, double* r, const double* p, const double* q,
-                       double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag);
+                       double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag,
+                       const double* dinv);
 
 // elast_solve.hip ---------------------------------------------------------------------------------------------------
 // y_l = a Op x_l + b f_l for n_cols columns (+ partial dot(x_l, y_l) per block and column, part_stride apart, when part !=
@@ -113,10 +119,16 @@ int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const doub
 int femo_elast_work_reserve(femo_elast* e, int n_cols, const char* who);
 // The first guess of a Krylov loop for n_cols columns (k_pcg_start_x): x = 0 with zero_guess, and x = b on the fixed dofs.
 int femo_elast_start_x(femo_elast* e, int n_cols, int zero_guess, const double* b, double* x);
-// The batched PCG of femo_elast_solve_multi for a caller that has checked its arguments (the eigen solve): info: n_cols
-// records, or null.
+// The operator of femo_elast_pcg other than K: K + sigma M (sigma >= 0, M assembled) through the shifted product, with the
+// inverse diagonal blocks of K + sigma M for the Jacobi term (the lattice term of the multilevel form stays that of K).
+struct femo_elast_op {
+  double sigma;
+  const double* dinv;
+};
+// The batched PCG of femo_elast_solve_multi for a caller that has checked its arguments (the eigen solve, the Newmark
+// march): info: n_cols records, or null.  op == null: K.
 int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
-                   const char* who);
+                   const char* who, const femo_elast_op* op = nullptr);
 
 // elast_harm.hip ----------------------------------------------------------------------------------------------------
 // scalars per column in w_ms / h_ms, always for FEMO_ELAST_MAX_COLS columns
@@ -124,6 +136,9 @@ constexpr int FEMO_ELAST_HARM_SCALARS = 16;
 // The three extra vectors of the MINRES loop in w_harm (w_harm_cols columns each, one behind the other) for at least n_cols
 // columns, the scalars and their pinned mirror.  The COCR of elast_damp.hip keeps two vectors and its scalars there.
 int femo_elast_harm_reserve(femo_elast* e, int n_cols, const char* who);
+// y_l = a (Op - shift M) x_l + b f_l on raw pointers with one shift for all columns (any sign), as femo_elast_spmv
+int femo_elast_dyn_spmv(femo_elast* e, bool masked, int n_cols, double shift, double a, const double* x, double b, const double* f,
+                        double* y, double* part, int64_t part_stride, const int32_t* done);
 
 // elast_block.hip: the block linear algebra and the block iteration of the eigen solves --------------------------------
 namespace elast_block {

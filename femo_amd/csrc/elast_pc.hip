@@ -471,7 +471,7 @@ int pc_build_blocks(femo_elast* e, const double* rho) {
 
 template <int D, bool UPDATE>
 int pc_step(femo_elast* e, int nc, double* x, double* r, const double* p, const double* q, double* z, double* pinit,
-            const double* s, double* part, int64_t ps, const int32_t* flag) {
+            const double* s, double* part, int64_t ps, const int32_t* flag, const double* dinv) {
   constexpr int GL = D == 2 ? 8 : 64;
   femo_elast_pc* pc = e->pc;
   femo_mesh* m = e->mesh;
@@ -495,10 +495,10 @@ int pc_step(femo_elast* e, int nc, double* x, double* r, const double* p, const 
     hipLaunchKernelGGL((k_pc_coarse<D, UPDATE>), dim3(cols), dim3(PC_COARSE_NT), 0, st, P, L - 1, pc->d_C, pc->d_g,
                        pc->d_e, flag, ls);
   if (pinit)
-    hipLaunchKernelGGL((k_pc_final<D, UPDATE, true>), dim3(PCG_GRID, cols), dim3(EB), 0, st, m->n_rows, e->d_dinv, x, r, p, q,
+    hipLaunchKernelGGL((k_pc_final<D, UPDATE, true>), dim3(PCG_GRID, cols), dim3(EB), 0, st, m->n_rows, dinv, x, r, p, q,
                        z, pinit, s, part, flag, fx, pc->d_vbin, pc->d_vfrac, F, sF, Cc, eC, vs, ls, ps);
   else
-    hipLaunchKernelGGL((k_pc_final<D, UPDATE, false>), dim3(PCG_GRID, cols), dim3(EB), 0, st, m->n_rows, e->d_dinv, x, r, p, q,
+    hipLaunchKernelGGL((k_pc_final<D, UPDATE, false>), dim3(PCG_GRID, cols), dim3(EB), 0, st, m->n_rows, dinv, x, r, p, q,
                        z, pinit, s, part, flag, fx, pc->d_vbin, pc->d_vfrac, F, sF, Cc, eC, vs, ls, ps);
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
@@ -535,7 +535,8 @@ int femo_elast_pc_build(femo_elast* e, const double* rho) {
 }
 
 int femo_elast_pc_step(femo_elast* e, bool update, int n_cols, double* x, double* r, const double* p, const double* q,
-                       double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag) {
+                       double* z, double* pinit, const double* s, double* part, int64_t part_stride, const int32_t* flag,
+                       const double* dinv) {
   femo_elast_pc* pc = e->pc;
   FEMO_REQUIRE(pc && n_cols >= 1 && n_cols <= FEMO_ELAST_MAX_COLS, "femo_elast_pc_step: bad column count %d", n_cols);
   if (pc->cols < n_cols) {                       // the old pair stays until the new one exists
@@ -548,7 +549,7 @@ int femo_elast_pc_step(femo_elast* e, bool update, int n_cols, double* x, double
     pc->bytes += 2 * per * (n_cols - pc->cols) * (int64_t)sizeof(double);
     pc->cols = n_cols;
   }
-#define FEMO_PC_STEP(D, U) pc_step<D, U>(e, n_cols, x, r, p, q, z, pinit, s, part, part_stride, flag)
+#define FEMO_PC_STEP(D, U) pc_step<D, U>(e, n_cols, x, r, p, q, z, pinit, s, part, part_stride, flag, dinv)
   if (e->d == 2) return update ? FEMO_PC_STEP(2, true) : FEMO_PC_STEP(2, false);
   return update ? FEMO_PC_STEP(3, true) : FEMO_PC_STEP(3, false);
 #undef FEMO_PC_STEP
@@ -735,7 +736,7 @@ int femo_elast_pc_apply(femo_elast* e, const femo_vec* r, femo_vec* z) {
   FEMO_TRY(femo_elast_pc_ensure(e));
   FEMO_TRY(femo_vec_await(r));
   femo_vec_touch(z);
-  return femo_elast_pc_step(e, false, 1, nullptr, const_cast<double*>(r->d) /* read only without the update */, nullptr, nullptr, z->d, nullptr, e->w_s, e->w_part, e->w_pstride, e->w_flag);
+  return femo_elast_pc_step(e, false, 1, nullptr, const_cast<double*>(r->d) /* read only without the update */, nullptr, nullptr, z->d, nullptr, e->w_s, e->w_part, e->w_pstride, e->w_flag, e->d_dinv);
 }
 
 }  // extern "C"

@@ -246,8 +246,9 @@ void spmv_chunk(femo_elast* e, int nc, double a, const double* x, double b, cons
 
 // the PCG of femo_elast_solve (one column) and femo_elast_solve_multi, which have checked their arguments; who: the entry
 // point, for the error texts.  info: n_cols records, or null.
+// op: K (null), or K + sigma M with its own inverse diagonal blocks for the Jacobi term.
 int pcg_solve(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
-              const char* who) {
+              const char* who, const femo_elast_op* op = nullptr) {
   femo_mesh* m = e->mesh;
   const int64_t n = m->n_vert * e->d;
   const bool ml = opts->pc == FEMO_ELAST_PC_MULTILEVEL;
@@ -265,12 +266,18 @@ int pcg_solve(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const f
   const int64_t ps = e->w_pstride;
   const unsigned L = (unsigned)n_cols, gp = (unsigned)PCG_GRID;
   hipEvent_t e0 = m->ctx->ev0, e1 = m->ctx->ev1;
+  const double* dinv = op ? op->dinv : e->d_dinv;
+  // y = a A x + b f of the chosen operator: the block product of K, or the shifted product with the shift -sigma
+  auto product = [&](double a, const double* xx, double bb, const double* f, double* y, double* part, const int32_t* done) -> int {
+    if (op) return femo_elast_dyn_spmv(e, fx != nullptr, n_cols, -op->sigma, a, xx, bb, f, y, part, ps, done);
+    return femo_elast_spmv(e, fx != nullptr, n_cols, a, xx, bb, f, y, part, ps, done);
+  };
   FEMO_HIP_CHECK(hipEventRecord(e0, st));
   hipLaunchKernelGGL(k_pcg_start_x, dim3(grid_of(n), L), dim3(EB), 0, st, n, opts->zero_guess, fx, b->d, x->d);
-  FEMO_TRY(femo_elast_spmv(e, fx != nullptr, n_cols, -1.0, x->d, 1.0, b->d, e->w_r, nullptr, 0, nullptr));    // r = b - A x
-#define FEMO_PRECOND(D, U, I) hipLaunchKernelGGL((k_pcg_precond<D, U, I>), dim3(gp, L), dim3(EB), 0, st, m->n_rows, e->d_dinv, \
+  FEMO_TRY(product(-1.0, x->d, 1.0, b->d, e->w_r, nullptr, nullptr));                                           // r = b - A x
+#define FEMO_PRECOND(D, U, I) hipLaunchKernelGGL((k_pcg_precond<D, U, I>), dim3(gp, L), dim3(EB), 0, st, m->n_rows, dinv, \
                                                  x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, ps, e->w_flag)
-  if (ml) FEMO_TRY(femo_elast_pc_step(e, false, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, ps, e->w_flag));
+  if (ml) FEMO_TRY(femo_elast_pc_step(e, false, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, ps, e->w_flag, dinv));
   else if (e->d == 2) FEMO_PRECOND(2, false, true); else FEMO_PRECOND(3, false, true);
   hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 0, e->w_part, ps, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
   FEMO_HIP_CHECK(hipGetLastError());
@@ -282,9 +289,9 @@ int pcg_solve(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const f
     for (int l = 0; l < n_cols; ++l) all_done = all_done && e->h_flag[l * EMF_STRIDE] != 0;
     if (all_done || it_issued >= max_it) break;
     for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) {
-      FEMO_TRY(femo_elast_spmv(e, fx != nullptr, n_cols, 1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, ps, e->w_flag));   // q = A p, p.q
+      FEMO_TRY(product(1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, e->w_flag));                               // q = A p, p.q
       hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 1, e->w_part, ps, nps, rtol2, atol2, max_it, e->w_s, e->w_flag);
-      if (ml) FEMO_TRY(femo_elast_pc_step(e, true, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, nullptr, e->w_s, e->w_part, ps, e->w_flag));
+      if (ml) FEMO_TRY(femo_elast_pc_step(e, true, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, nullptr, e->w_s, e->w_part, ps, e->w_flag, dinv));
       else if (e->d == 2) FEMO_PRECOND(2, true, false); else FEMO_PRECOND(3, true, false);
       hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 2, e->w_part, ps, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
       hipLaunchKernelGGL(k_pcg_p, dim3(gp, L), dim3(EB), 0, st, n, e->w_z, e->w_p, e->w_s, e->w_flag);
@@ -339,8 +346,8 @@ int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const doub
 }
 
 int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
-                   const char* who) {
-  return pcg_solve(e, n_cols, b, x, opts, info, who);
+                   const char* who, const femo_elast_op* op) {
+  return pcg_solve(e, n_cols, b, x, opts, info, who, op);
 }
 
 int femo_elast_start_x(femo_elast* e, int n_cols, int zero_guess, const double* b, double* x) {

@@ -481,6 +481,7 @@ int femo_elast_destroy(femo_elast* e) {
   hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_smpart);
   hipFree(e->w_eig); hipFree(e->w_gram); hipFree(e->w_gstress);
   hipFree(e->d_mvals); hipFree(e->d_mdiag); hipFree(e->w_harm); hipFree(e->w_ms);
+  hipFree(e->w_nm); hipFree(e->d_nm_dinv);
   if (e->h_ms) hipHostFree(e->h_ms);
   if (e->h_gram) hipHostFree(e->h_gram);
   if (e->h_flag) hipHostFree(e->h_flag);

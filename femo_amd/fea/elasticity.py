@@ -1,7 +1,7 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
 product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip,
-buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip, the harmonic response in csrc/elast_harm.hip, its damped form in csrc/elast_damp.hip).  One load case is the L = 1 case of several:
+buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip, the harmonic response in csrc/elast_harm.hip, its damped form in csrc/elast_damp.hip, the transient response in csrc/elast_transient.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
 The forms are ``BackendForm``s, like the shell forms: `utils_hip.assemble*`, `solveNonlinear` and `KSP` hand them their
@@ -68,6 +68,13 @@ are used unchanged.
                        adjoint (conj(Z)) and forward-mode solves are each ONE batched preconditioned COCR (Sogabe & Zhang
                        2007; csrc/elast_damp.hip), which converges at a resonance, where the undamped MINRES does not, and
                        J = sum_l w_l |F_l . u_l| (or its square) of the complex compliance is finite and differentiable there
+  TransientElasticityResidual, TransientCompliance
+                       the time-domain response by Newmark(beta, gamma) with Rayleigh damping, as the two-step recurrence in the
+                       displacements from rest; the state is a Function(TimeHistorySpace(V, N)) holding u_1 ... u_N, the whole
+                       history one state of the operator surface.  The history solves a block lower-banded block-Toeplitz
+                       system with symmetric blocks, so the adjoint is the SAME march run backwards: state, forward-mode and
+                       adjoint solves are one device-resident loop (csrc/elast_transient.hip), each step one fused
+                       right-hand-side launch and one PCG on K + sigma M.  J = sum_n w_n F . u_n (or its squared form)
 
 P1 simplices only: the quadrilaterals of the reference's createRectangleMesh are split into triangles (fea/mesh.py).
 """
@@ -82,7 +89,7 @@ from .. import _lib
 from .._lib import check
 from ..engine import Vec, _ptr
 from .forms import BackendForm, LinearFunctional
-from .function import Function, FunctionSpace, LoadCaseSpace, VectorFunctionSpace
+from .function import Function, FunctionSpace, LoadCaseSpace, TimeHistorySpace, VectorFunctionSpace
 from .io import MeshTags
 
 METHODS = {"SIMP": _lib.ELAST_SIMP, "RAMP": _lib.ELAST_RAMP}
@@ -470,6 +477,82 @@ class DeviceElasticity:
                                                   n_cols, sv.ctypes.data_as(_lib.c_f64p), rho.handle, u.handle, x.handle,
                                                   y.handle, int(bool(accumulate))))
         return y
+
+    # ---- transient response: Newmark march on a history of n_steps columns, column t = u_{t+1} (csrc/elast_transient.hip) ----
+    @staticmethod
+    def _newmark(params) -> _lib.NewmarkParams:
+        dt, beta, gamma, c_m, c_k = (float(v) for v in params)
+        return _lib.NewmarkParams(dt=dt, beta=beta, gamma=gamma, c_m=c_m, c_k=c_k)
+
+    def _steps(self, n_steps: int, *vecs: Vec) -> int:
+        n_steps = int(n_steps)
+        for v in vecs:
+            if v is not None and v.n < n_steps * self.n_dof:
+                raise _lib.FemoError(f"{n_steps} steps need vectors of {n_steps * self.n_dof} entries, got {v.n}")
+        return n_steps
+
+    def newmark_rhs(self, u: Vec, y: Vec, m0: float, k0: float, mm: float, km: float, rhs: Optional[Vec] = None,
+                    cr: float = 1.0, crf: float = 1.0, masked: bool = False) -> Vec:
+        """y = cr rhs - (m0 M + k0 K) u_n - (mm M + km K) u_{n-1} in one pass over the pattern; ``u`` holds u_n then u_{n-1}.
+        ``masked``: fixed entries of u read as 0, a fixed row gives crf rhs."""
+        check(self.lib.femo_elast_newmark_rhs(self.handle, int(bool(masked)), float(cr), float(crf), float(m0), float(k0),
+                                              float(mm), float(km), None if rhs is None else rhs.handle, u.handle, y.handle))
+        return y
+
+    def newmark_march(self, params, n_steps: int, U: Vec, rhs: Optional[Vec] = None, F: Optional[Vec] = None, signal=None,
+                      reverse: bool = False, extrapolate: bool = True, rtol: float = 1e-13, atol: float = 0.0,
+                      max_it: int = 1_000_000, check_every: Optional[int] = None, pc: str = "jacobi"):
+        """All ``n_steps`` steps of L U = B (L^T U = B with ``reverse``) in one call: B is the history ``rhs`` or comes from the
+        load pattern ``F`` and the n_steps + 1 samples ``signal``.  ``params`` = (dt, beta, gamma, c_m, c_k).  Returns (one
+        `SolveInfo` per step, the column the march stopped at or -1)."""
+        n_steps = self._steps(n_steps, U, rhs)
+        opts = self._solver_opts(rtol, atol, max_it, check_every, False, pc)
+        g = None
+        if signal is not None:
+            g = np.ascontiguousarray(signal, dtype=np.float64).ravel()
+            if g.size != n_steps + 1:
+                raise _lib.FemoError(f"newmark_march: {n_steps} steps need {n_steps + 1} samples of the signal, got {g.size}")
+        info = (_lib.SolveInfo * n_steps)()
+        stopped = C.c_int32(-1)
+        par = self._newmark(params)
+        check(self.lib.femo_elast_newmark_march(self.handle, C.byref(par), n_steps, int(bool(reverse)),
+                                                None if rhs is None else rhs.handle, None if F is None else F.handle,
+                                                None if g is None else g.ctypes.data_as(_lib.c_f64p), U.handle, C.byref(opts),
+                                                int(bool(extrapolate)), info, C.byref(stopped)))
+        return [info[t] for t in range(n_steps)], int(stopped.value)
+
+    def newmark_apply(self, params, n_steps: int, X: Vec, Y: Vec, transpose: bool = False, masked: bool = False) -> Vec:
+        """Y = L X, or L^T X, for a history; FEMO_ELAST_MAX_COLS time steps per launch."""
+        par = self._newmark(params)
+        check(self.lib.femo_elast_newmark_apply(self.handle, C.byref(par), self._steps(n_steps, X, Y), int(bool(transpose)),
+                                                int(bool(masked)), X.handle, Y.handle))
+        return Y
+
+    def newmark_drho(self, params, method: int, transpose: bool, n_steps: int, rho: Vec, U: Vec, x: Vec, y: Vec,
+                     density: float = 1.0, mass_law: str = "linear", accumulate: bool = False, first: int = 0,
+                     count: Optional[int] = None) -> Vec:
+        """dR/drho of the march's residual for the columns first ... first + count - 1 (all by default).  transpose:
+        y[n_cell] (+)= sum_t (dR_t/drho)^T x_t; otherwise column t of y (+)= dR_t/drho x.  Windows of FEMO_ELAST_MAX_COLS columns
+        in ascending order."""
+        n_steps = self._steps(n_steps, U, x if transpose else y)
+        par = self._newmark(params)
+        check(self.lib.femo_elast_newmark_drho(self.handle, C.byref(par), int(method), self._mass_law(mass_law), float(density),
+                                               int(bool(transpose)), n_steps, int(first),
+                                               n_steps - int(first) if count is None else int(count), rho.handle, U.handle,
+                                               x.handle, y.handle, int(bool(accumulate))))
+        return y
+
+    def newmark_dots(self, n_steps: int, f: Vec, U: Vec) -> np.ndarray:
+        """(n_steps,): f . U_t for every column, through the Gram kernel in windows."""
+        out = np.zeros(self._steps(n_steps, U))
+        check(self.lib.femo_elast_newmark_dots(self.handle, int(n_steps), f.handle, U.handle, out.ctypes.data_as(_lib.c_f64p)))
+        return out
+
+    def newmark_outer(self, n_steps: int, a, f: Vec, Y: Vec) -> Vec:
+        """Y_t = a[t] f for every column."""
+        av = self._per_column("newmark_outer", "coefficients", self._steps(n_steps, Y), a)
+        check(self.lib.femo_elast_newmark_outer(self.handle, int(n_steps), av.ctypes.data_as(_lib.c_f64p), f.handle, Y.handle))
+        return Y
 
     def pnorm_stress_multi(self, n_cols: int, rho: Vec, u: Vec, m, p: float, q: float, alpha: float, weights=None,
                            value: bool = True, grad_u: Optional[Vec] = None, grad_rho: Optional[Vec] = None,
@@ -2058,6 +2141,289 @@ class DampedDynamicCompliance(BackendForm):
         return elasticity_handle(self.mesh).block_rotate(self.n_cases, Q, self.load(), out)
 
 
+# ------------------------------------------------------------------------------------------ transient response ----
+class TransientElasticityMatrix(ElasticityMatrix):
+    """dR/dU of a `TransientElasticityResidual`: the block lower-banded, block-Toeplitz L of the Newmark recurrence on the
+    history -- not symmetric, but with symmetric blocks, so `backend_solve_transpose` (the adjoint) is the march of
+    `backend_solve` (forward mode) run from the last step to the first.  With ``masked`` the diagonal blocks carry identity
+    rows / columns on the fixed dofs and the sub-diagonal blocks zero ones.  `mult` / `multTranspose` are the banded product,
+    8 time steps per launch."""
+    symmetric = False
+
+    def getSizes(self):
+        n = self.form.n_steps * self.form.n_dof
+        return (n, n)
+
+    size = property(getSizes)
+
+    def _apply(self, transpose: bool, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        dev = F.dynamic()
+        return dev.newmark_apply(F.params, F.n_steps, x, y, transpose=transpose,
+                                 masked=self.masked and dev.fixed_key is not None)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        return self._apply(False, x, y)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        return self._apply(True, x, y)
+
+    def _solve(self, reverse: bool, kind: str, b: Vec, x: Vec, options: Optional[dict]) -> None:
+        o = options or {}
+        F = self.form
+        infos, stopped = F.dynamic().newmark_march(F.params, F.n_steps, x, rhs=b, reverse=reverse, extrapolate=F.extrapolate,
+                                                   rtol=o.get("elast_rtol", F.rtol), max_it=o.get("elast_max_it", F.max_it),
+                                                   pc=F.preconditioner)
+        self.info = F._record((infos, stopped), kind)
+
+    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        self._solve(False, "forward", b, x, options)
+
+    def backend_solve_transpose(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        self._solve(True, "adjoint", b, x, options)
+
+    def to_scipy(self):
+        import scipy.sparse as sp
+        F = self.form
+        K = F.dynamic().export_csr()
+        M = _host_mass(F.mesh, np.array(F.rho.vec.get(), dtype=np.float64), F.mass_law, F.density)
+        A = [(m * M + k * K).tocsr() for m, k in zip(F.blocks["m"], F.blocks["k"])]
+        if self.masked and F._mask is not None:
+            free = sp.diags((F._mask == 0).astype(np.float64))
+            A = [(free @ A[0] @ free + sp.diags(F._mask.astype(np.float64))).tocsr(), (free @ A[1] @ free).tocsr(),
+                 (free @ A[2] @ free).tocsr()]
+        N = F.n_steps
+        sub = lambda k: sp.csr_matrix((np.ones(max(N - k, 0)), (np.arange(k, N), np.arange(0, max(N - k, 0)))), shape=(N, N))
+        return (sp.kron(sp.identity(N), A[0]) + sp.kron(sub(1), A[1]) + sp.kron(sub(2), A[2])).tocsr()
+
+
+class _TransientDrho(_ElasticityDrho):
+    """dR/drho of a `TransientElasticityResidual` ((n_steps n_dof) x n_cell), matrix free: block t of column e is C'(rho_e) K0_e
+    uK_t,e + density m'(rho_e) M0_e uM_t,e with the banded combinations uK_t = sum_j k_j u_{t+j}, uM_t = sum_j m_j u_{t+j}; the
+    existing batched products in windows of 8 time steps, in ascending order."""
+
+    def getSizes(self):
+        return (self.form.n_steps * self.form.n_dof, self.mesh.n_cell)
+
+    def _both(self, transpose: bool, x: Vec, y: Vec) -> Vec:
+        F = self.form
+        return F.device().newmark_drho(F.params, F.method_id, transpose, F.n_steps, F.rho.vec, F.u.vec, x, y, density=F.density,
+                                       mass_law=F.mass_law)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        return self._both(False, x, y)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        return self._both(True, x, y)
+
+
+def _transient_space(name: str, u: Function) -> TimeHistorySpace:
+    V = u.function_space
+    if not isinstance(V, TimeHistorySpace):
+        raise NotImplementedError(f"{name} needs a Function(TimeHistorySpace(V, n_steps)) state")
+    if getattr(V.mesh, "local", None) is not None and V.mesh.local.nranks > 1:
+        raise NotImplementedError(f"{name}: partitioned meshes are out of scope")
+    return V
+
+
+class TransientElasticityResidual(ElasticityResidual):
+    """The time-domain response M u'' + C u' + K(rho) u = g(t) F from rest, C = c_m M + c_k K (``rayleigh`` = (c_m, c_k)), by
+    Newmark(``beta``, ``gamma``) with the step ``dt``, written as its two-step recurrence in the displacements:
+
+        A1 u_{n+1} + A0 u_n + A- u_{n-1} = dt^2 (beta g_{n+1} + b0 g_n + b- g_{n-1}) F,   A_j = m_j M + k_j K,   n = 0 ... N - 1
+
+    (the scalars in csrc/elast_transient.hip; u_0 = u_-1 = 0, g_-1 = 0).  ``u`` is a Function(TimeHistorySpace(V, N)) holding
+    u_1 ... u_N; ``traction`` on ``ds`` is the one spatial load pattern F, ``signal`` the N + 1 samples g_0 ... g_N of its time
+    signal; M = ``density`` sum_e m(rho_e) M0_e as for `HarmonicElasticityResidual`, reassembled under the same rule.
+
+    The residual of the whole history is R = L U - B with L block lower-banded and block-Toeplitz with symmetric blocks:
+    L^T is the same march on the time-reversed sequence.  The state solve, the forward-mode solve (`backend_solve` of
+    `new_matrix()`) and the adjoint solve (`backend_solve_transpose`) are ONE device-resident loop
+    (`DeviceElasticity.newmark_march`): per step one fused right-hand-side launch and one PCG on K + (m1 / k1) M with the
+    block-Jacobi (diagonal blocks of K + (m1 / k1) M) or multilevel preconditioner, from the extrapolated first guess
+    2 u_n - u_{n-1} (``extrapolate``, on by default).  The guess buys accuracy, not speed: the PCG stops relative to the residual
+    of its first guess, so a better guess lowers the level it stops at and leaves the iteration count where it was (measured:
+    1-6 % more iterations, a lower error).  A step that does not converge raises, naming the step.
+
+    Refused: beta <= 0, gamma < 1/2, partitioned meshes, inhomogeneous supports, body forces, n_steps < 1,
+    len(signal) != n_steps + 1, non-finite inputs.  Out of scope: several load patterns in one march, non-zero initial
+    conditions, checkpointing, HHT-alpha and generalised-alpha, point dampers."""
+    matrix_class = TransientElasticityMatrix
+    is_symmetric = False
+
+    def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, signal=None, dt: float = None,
+                 beta: float = 0.25, gamma: float = 0.5, rayleigh=(0.0, 0.0), density: float = 1.0, mass_law: str = "linear",
+                 E: float = 1.0, nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None):
+        name = "TransientElasticityResidual"
+        if body_force is not None:
+            raise NotImplementedError(f"{name}: body forces are out of scope")
+        V = _transient_space(name, u)
+        if traction is None:
+            raise ValueError(f"{name}: the load pattern needs a traction (body forces are out of scope)")
+        self.t = _traction(traction, V.mesh)
+        self.ds = ds if ds is not None else Measure("ds", domain=V.mesh)
+        if signal is None:
+            raise ValueError(f"{name}: the time signal needs n_steps + 1 samples (signal)")
+        g = np.array(signal, dtype=np.float64).ravel()
+        if g.size != V.n_steps + 1:
+            raise ValueError(f"{name}: {V.n_steps} steps need {V.n_steps + 1} samples of the signal, got {g.size}")
+        if not np.all(np.isfinite(g)):
+            raise ValueError(f"{name}: the signal must be finite")
+        if dt is None or not (np.isfinite(dt) and dt > 0.0):
+            raise ValueError(f"{name}: the time step dt must be finite and > 0")
+        if not (np.isfinite(beta) and beta > 0.0):
+            raise ValueError(f"{name}: beta must be finite and > 0 (the step matrix must be positive definite)")
+        if not (np.isfinite(gamma) and gamma >= 0.5):
+            raise ValueError(f"{name}: gamma must be finite and >= 1/2")
+        ray = np.array(rayleigh, dtype=np.float64).ravel()
+        if ray.size != 2 or not np.all(np.isfinite(ray)) or np.any(ray < 0.0):
+            raise ValueError(f"{name}: rayleigh = (c_m, c_k) must be two finite values >= 0")
+        if mass_law not in MASS_LAWS:
+            raise ValueError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
+        if not (np.isfinite(density) and density >= 0.0):
+            raise ValueError(f"{name}: the mass density must be finite and >= 0")
+        self._setup(u, rho, V.base, 1, [self.t], [self.ds], E, nu, method, preconditioner, None)
+        self.n_steps, self.signal = V.n_steps, g
+        self.dt, self.beta, self.gamma, self.rayleigh = float(dt), float(beta), float(gamma), (float(ray[0]), float(ray[1]))
+        self.params = (self.dt, self.beta, self.gamma, self.rayleigh[0], self.rayleigh[1])
+        dt2 = self.dt * self.dt
+        b0, bm = 0.5 + self.gamma - 2.0 * self.beta, 0.5 - self.gamma + self.beta
+        cm, ck = self.rayleigh
+        self.blocks = dict(m=(1.0 + self.gamma * self.dt * cm, -2.0 + (1.0 - 2.0 * self.gamma) * self.dt * cm,
+                              1.0 - (1.0 - self.gamma) * self.dt * cm),
+                           k=(self.gamma * self.dt * ck + self.beta * dt2, (1.0 - 2.0 * self.gamma) * self.dt * ck + b0 * dt2,
+                              -(1.0 - self.gamma) * self.dt * ck + bm * dt2), b0=b0, bm=bm)
+        self.density, self.mass_law = float(density), mass_law
+        self.rtol, self.max_it, self.extrapolate = 1e-13, 1_000_000, True
+        self.solve_counts = {"state": 0, "adjoint": 0, "forward": 0}
+        self._B = None
+
+    def signal_coefficients(self) -> np.ndarray:
+        """(n_steps,): dt^2 (beta g_{t+1} + b0 g_t + b- g_{t-1}), the factor of F in the right-hand side of step t."""
+        g = self.signal
+        gm = np.concatenate([[0.0], g[:-2]])
+        return self.dt ** 2 * (self.beta * g[1:] + self.blocks["b0"] * g[:-1] + self.blocks["bm"] * gm)
+
+    def _set_bcs(self, bcs) -> None:
+        super()._set_bcs(bcs)
+        if self._mask is not None and np.any(self._vals[self._mask == 1] != 0.0):
+            raise NotImplementedError("TransientElasticityResidual: inhomogeneous supports are out of scope")
+
+    def dynamic(self) -> DeviceElasticity:
+        """`stiffness()` with M(rho) of the current density as well, under the key rule of
+        `HarmonicElasticityResidual.dynamic`."""
+        dev = self.stiffness()
+        key = (self.rho.version, id(self.rho.vec), self.density, self.mass_law)
+        if getattr(dev, "_mass_owner", None) != key:
+            dev.mass_assemble(self.rho.vec, density=self.density, mass_law=self.mass_law)
+            dev._mass_owner = key
+        return dev
+
+    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
+        """R = L U - B of the whole history, without any Dirichlet treatment: the banded product and one launch for B."""
+        n = self.n_steps * self.n_dof
+        if out is None:
+            if self._res is None:
+                self._res = Vec(_ctx(), n)
+            out = self._res
+        dev = self.dynamic()
+        if self._B is None:
+            self._B = Vec(_ctx(), n)
+        dev.newmark_outer(self.n_steps, self.signal_coefficients(), self.load(), self._B)
+        dev.newmark_apply(self.params, self.n_steps, self.u.vec, out)
+        return out.axpy(-1.0, self._B)
+
+    def partial_matrix(self, wrt: Function, out=None):
+        if wrt is self.rho:
+            return out if isinstance(out, _TransientDrho) else _TransientDrho(self)
+        return super().partial_matrix(wrt, out)
+
+    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
+        """The whole history in one call: N steps on the device, each one fused right-hand side and one PCG."""
+        self._set_bcs(bcs)
+        dev = self.dynamic()
+        out = dev.newmark_march(self.params, self.n_steps, func.vec, F=self.load(), signal=self.signal,
+                                extrapolate=self.extrapolate, rtol=self.rtol, max_it=self.max_it, pc=self.preconditioner)
+        func.version += 1
+        self._record(out, "state")
+        if report:
+            print(self._report(out))
+
+    def _record(self, out, kind: str):
+        from .utils_hip import LAST_KSP_INFO
+        infos, stopped = out
+        taken = [i for i in infos if i.iterations > 0 or i.converged != 0]
+        self.solve_counts[kind] = self.solve_counts.get(kind, 0) + 1
+        self.last_info[kind] = dict(n_steps=self.n_steps, iterations=[i.iterations for i in infos],
+                                    converged=[i.converged for i in infos], stopped_at=stopped,
+                                    solve_ms=float(sum(i.solve_ms for i in taken)), preconditioner=self.preconditioner)
+        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_transient_" + kind))
+        if stopped >= 0:
+            i = infos[stopped]
+            raise RuntimeError(f"transient elasticity PCG did not converge ({kind}, step {stopped} of {self.n_steps}): "
+                               f"{i.iterations} iterations, sqrt(r.M^-1 r) = {i.residual_norm:.3e} of {i.rhs_norm:.3e}; the later "
+                               f"steps were not taken")
+        return infos
+
+    def _report(self, out) -> str:
+        infos = out[0]
+        its = [i.iterations for i in infos]
+        return (f"transient elasticity march, {self.n_steps} steps: {sum(its)} PCG iterations ({min(its)} to {max(its)} per step), "
+                f"{sum(i.solve_ms for i in infos):.1f} ms in the solves")
+
+
+class TransientCompliance(BackendForm):
+    """J = sum_n w_n c_n, or sum_n w_n c_n^2 with ``squared``, over the steps of a transient state, c_n = F . u_n the work of
+    the load pattern on step n (n = 1 ... N).  Without ``weights`` they are ``dt`` each -- the rectangle rule of int F . u dt --
+    and ``dt``, the time step of the residual, must be given: the state's space does not know it.  dJ/du_n = w_n F or 2 w_n c_n F; the form has no partial in the density -- the reversed
+    march of `TransientElasticityResidual` and its dR/drho give the total."""
+    rank = 0
+
+    def __init__(self, u: Function, traction, ds: Optional[Measure] = None, weights=None, squared: bool = False,
+                 dt: Optional[float] = None):
+        name = "TransientCompliance"
+        V = _transient_space(name, u)
+        if traction is None:
+            raise ValueError(f"{name}: the load pattern needs a traction")
+        self.t = _traction(traction, V.mesh)
+        self.ds = ds if ds is not None else Measure("ds", domain=V.mesh)
+        self.u, self.mesh, self.n_steps = u, V.mesh, V.n_steps
+        if weights is None:
+            if dt is None or not (np.isfinite(dt) and dt > 0.0):
+                raise ValueError(f"{name}: without weights the default w_n = dt needs the time step dt")
+            self.weights = np.full(V.n_steps, float(dt))
+        else:
+            self.weights = np.array(weights, dtype=np.float64).ravel()
+            if self.weights.size != V.n_steps or not np.all(np.isfinite(self.weights)):
+                raise ValueError(f"{name}: {V.n_steps} steps need as many finite weights")
+        self.squared = bool(squared)
+        self._grad = {}
+
+    def functions(self):
+        return (self.u,)
+
+    def load(self) -> Vec:
+        return _load_vec(self.mesh, self.ds.facets(), self.t)
+
+    def responses(self) -> np.ndarray:
+        """c_n = F . u_n of the current history, through the Gram kernel in windows of 8 steps."""
+        return elasticity_handle(self.mesh).newmark_dots(self.n_steps, self.load(), self.u.vec)
+
+    def assemble_scalar(self) -> float:
+        c = self.responses()
+        return float(self.weights @ (c * c if self.squared else c))
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        if wrt is not self.u:
+            return out.fill(0.0)
+        coef = self.weights * (2.0 * self.responses() if self.squared else 1.0)
+        return elasticity_handle(self.mesh).newmark_outer(self.n_steps, coef, self.load(), out)
+
+
 def averageFunc(func: Function) -> LinearFunctional:
     """(1/|Omega|) int func dx for a DG0 Function (averageFunc, run_topo_opt_cantilever_beam.py:103-106)."""
     V = func.function_space
@@ -2122,6 +2488,23 @@ def pdeRes_harmonic_damped(u, v, rho_e, fs, dss_list=None, omegas=None, loss_fac
 def dynamic_compliance_damped(u, fs, dss_list=None, weights=None, squared: bool = False) -> DampedDynamicCompliance:
     """sum_l w_l |F_l . u_l| (or its squared form) of a damped harmonic state, c_l complex, as a scalar output."""
     return DampedDynamicCompliance(u, fs, dss_list, weights=weights, squared=squared)
+
+
+def pdeRes_transient(u, v, rho_e, f, dss: Optional[Measure] = None, signal=None, dt: float = None, beta: float = 0.25,
+                     gamma: float = 0.5, rayleigh=(0.0, 0.0), density: float = 1.0, mass_law: str = "linear", E: float = 1.0,
+                     method: str = "SIMP", preconditioner: str = "jacobi") -> TransientElasticityResidual:
+    """`pdeRes` in the time domain: the Newmark march under the load pattern ``f`` on ``dss`` with the time signal ``signal``
+    (nu = 0.3 as there); ``u`` is a Function(TimeHistorySpace(V, len(signal) - 1))."""
+    return TransientElasticityResidual(u, rho_e, f, dss, signal=signal, dt=dt, beta=beta, gamma=gamma, rayleigh=rayleigh,
+                                       density=density, mass_law=mass_law, E=E, nu=0.3, method=method,
+                                       preconditioner=preconditioner)
+
+
+def transient_compliance(u, f, dss: Optional[Measure] = None, weights=None, squared: bool = False,
+                         dt: Optional[float] = None) -> TransientCompliance:
+    """sum_n w_n F . u_n (or its squared form) of a transient state as a scalar output; without ``weights`` w_n = ``dt``, the
+    time step given to `pdeRes_transient`."""
+    return TransientCompliance(u, f, dss, weights=weights, squared=squared, dt=dt)
 
 
 def pnorm_stress(u, rho_e, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0, q: float = 0.5,

@@ -21,14 +21,14 @@ from .utils_hip import (DeviceArray, DirichletBC, KSP, dirichletbc, getFuncArray
 from .forms import (ALPHA, BeamResidual, DerivativeForm, FieldExpression, Form, FunctionExpr, GradientMagnitude,
                     L2TrackingFunctional, LinearFunctional, NonlinearPoissonResidual, PoissonResidual, PowerExpr,
                     TestFunction, derivative, interiorResidual, outputForm, pdeRes)
-from .function import Function, FunctionSpace, LoadCaseSpace, VectorFunctionSpace
+from .function import Function, FunctionSpace, LoadCaseSpace, TimeHistorySpace, VectorFunctionSpace
 from .io import XDMFRecorder
 from .mesh import (BeamMesh, Mesh, createIntervalMesh, createRectangleMesh, createUnitCubeMesh, createUnitSquareMesh,
                    findNodeIndices, locate_dofs_geometrical, locate_entities_boundary, meshSize)
-from .elasticity import (Constant, Measure, buckling_aggregate, compliance_multiload, dynamic_compliance,
-                         dynamic_compliance_damped, eigenvalue_aggregate, meshtags, pdeRes_harmonic, pdeRes_harmonic_damped,
-                         pdeRes_multiload, pnorm_stress, pnorm_stress_multiload, von_Mises_stress,
-                         von_Mises_stress_multiload)
+from .elasticity import (Constant, Measure, TransientCompliance, TransientElasticityResidual, buckling_aggregate,
+                         compliance_multiload, dynamic_compliance, dynamic_compliance_damped, eigenvalue_aggregate, meshtags,
+                         pdeRes_harmonic, pdeRes_harmonic_damped, pdeRes_multiload, pdeRes_transient, pnorm_stress,
+                         pnorm_stress_multiload, transient_compliance, von_Mises_stress, von_Mises_stress_multiload)
 
 
 class AbstractFEA(object):

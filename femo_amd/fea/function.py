@@ -134,6 +134,43 @@ class LoadCaseSpace:
     __hash__ = object.__hash__
 
 
+class TimeHistorySpace:
+    """``n_steps`` copies of a VectorFunctionSpace in one vector, one per time step of a transient response of the SIMP
+    elasticity: step n + 1 of the march holds the dofs of ``base`` in its blocked layout and starts at ``n * base.dim`` (the
+    layout of femo_elast_newmark_march).  Any number of steps: the 8-column limit of a `LoadCaseSpace` does not apply.  A
+    ``Function(TimeHistorySpace(V, N))`` is an ordinary Function of dimension ``N * V.dim``."""
+
+    def __init__(self, base: VectorFunctionSpace, n_steps: int):
+        if not isinstance(base, VectorFunctionSpace):
+            raise NotImplementedError("TimeHistorySpace needs a VectorFunctionSpace(mesh, ('CG', 1)) base")
+        if int(n_steps) < 1:
+            raise ValueError(f"TimeHistorySpace: {n_steps} steps (at least 1)")
+        self.base, self.n_steps, self.mesh = base, int(n_steps), base.mesh
+        self.family = "CGV_STEPS"
+        self.degree = 1
+        self.bs = base.bs
+        self.num_sub_spaces = 0
+
+    @property
+    def dim(self) -> int:
+        return self.n_steps * self.base.dim
+
+    def step(self, n: int) -> slice:
+        """The entries of u_{n+1} in a vector of this space."""
+        if not 0 <= n < self.n_steps:
+            raise IndexError(f"step {n} of {self.n_steps}")
+        return slice(n * self.base.dim, (n + 1) * self.base.dim)
+
+    def tabulate_dof_coordinates(self) -> np.ndarray:
+        """The base space's: one row per vertex, the same for every step."""
+        return self.base.tabulate_dof_coordinates()
+
+    def __eq__(self, other):
+        return isinstance(other, TimeHistorySpace) and other.base == self.base and other.n_steps == self.n_steps
+
+    __hash__ = object.__hash__
+
+
 class _VectorView:
     """PETSc-Vec-flavoured access to a Function's device vector."""
 

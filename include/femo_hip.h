@@ -867,6 +867,52 @@ int femo_elast_cdyn_apply_multi(femo_elast* e, int masked, int conj, int n_cols,
 int femo_elast_cdyn_solve_multi(femo_elast* e, int conj, int n_cols, const double* shifts /* [n_cols] */,
                                 const double* ck /* [n_cols] */, const double* cm /* [n_cols] */, const femo_vec* b, femo_vec* x,
                                 const femo_solver_opts* opts, femo_solve_info* info /* [n_cols] or NULL */);
+/* Transient response (csrc/elast_transient.hip): Newmark(beta, gamma) with Rayleigh damping C = c_m M + c_k K, as its two-step
+ * recurrence in the displacements, from rest (u_0 = u_-1 = 0, g_-1 = 0), for n = 0 ... N - 1:
+ *   A1 u_{n+1} + A0 u_n + A- u_{n-1} = dt^2 (beta g_{n+1} + b0 g_n + b- g_{n-1}) F,    A_j = m_j M + k_j K,
+ *   m1 =  1 + gamma dt c_m,          k1 = gamma dt c_k + beta dt^2,
+ *   m0 = -2 + (1 - 2 gamma) dt c_m,  k0 = (1 - 2 gamma) dt c_k + b0 dt^2,    b0 = 1/2 + gamma - 2 beta,
+ *   m- =  1 - (1 - gamma) dt c_m,    k- = -(1 - gamma) dt c_k + b- dt^2,     b- = 1/2 - gamma + beta,
+ * with K of femo_elast_assemble and M of femo_elast_mass_assemble.  A history holds N columns of n_dof entries, column t =
+ * u_{t+1} at t * n_dof (any N: no column limit).  It solves L U = B with L block lower-banded and block-Toeplitz with
+ * symmetric blocks, so L^T is the same recurrence from the last column to the first.  With a fixed set (homogeneous
+ * supports) A1 has identity rows / columns on the fixed dofs and A0, A- zero ones: L is the identity there.  Needs dt > 0,
+ * beta > 0, gamma >= 1/2, c_m >= 0, c_k >= 0.  No float atomics: the same inputs give the same bits.                      */
+typedef struct femo_newmark_params {
+  double dt, beta, gamma, c_m, c_k;
+} femo_newmark_params;
+/* y = cr rhs - (m0 M + k0 K) u_n - (mm M + km K) u_{n-1} in ONE pass over the pattern (u: 2 n_dof entries, u_n then u_{n-1};
+ * rhs may be NULL): the right-hand side of a step.  masked = 1: fixed entries of u read as 0 and a fixed row gives crf rhs.   */
+int femo_elast_newmark_rhs(femo_elast* e, int masked, double cr, double crf, double m0, double k0, double mm, double km,
+                           const femo_vec* rhs /* or NULL */, const femo_vec* u, femo_vec* y);
+/* All n_steps steps in one call on the context's stream: L U = B (reverse = 0) or L^T U = B (reverse = 1), B either the
+ * history rhs (n_steps columns) or, forward only, dt^2 (beta g_{t+1} + b0 g_t + b- g_{t-1}) F from one load pattern F and the
+ * n_steps + 1 samples g of its signal (F is read as 0 on the fixed dofs).  Each step is one fused right-hand-side launch and
+ * one PCG on K + (m1 / k1) M -- the loop of femo_elast_solve, opts as there, the Jacobi term from the diagonal blocks of
+ * K + (m1 / k1) M -- from the first guess 2 u_prev - u_prev2 (extrapolate = 1) or zero.  The host waits only where the PCG polls
+ * its flag; nothing is allocated after the first step.  info[n_steps] (or NULL): the record of every step taken, indexed by
+ * column; zeroed on entry, so a step that was not taken reads as zeros.  A step that does not converge stops the march: *stopped_at = its column (-1: all steps converged), the columns of
+ * the later steps are not written.                                                                                           */
+int femo_elast_newmark_march(femo_elast* e, const femo_newmark_params* p, int n_steps, int reverse,
+                             const femo_vec* rhs /* or NULL */, const femo_vec* F /* or NULL */, const double* g /* or NULL */,
+                             femo_vec* U, const femo_solver_opts* opts, int extrapolate, femo_solve_info* info /* or NULL */,
+                             int32_t* stopped_at);
+/* Y = L X (transpose = 0) or L^T X for a history, FEMO_ELAST_MAX_COLS columns per launch.  masked as above.                  */
+int femo_elast_newmark_apply(femo_elast* e, const femo_newmark_params* p, int n_steps, int transpose, int masked,
+                             const femo_vec* X, femo_vec* Y);
+/* dR/drho of R = L U - B at fixed B, for the columns first ... first + count - 1 of the history U of n_steps columns:
+ * column t is C'(rho) K0 uK_t + density m'(rho) M0 uM_t with uK_t = k1 u_{t+1} + k0 u_t + k- u_{t-1}, uM_t likewise with m_j.
+ *   transpose = 1:  y[n_cell] (+)= sum_t (dR_t/drho)^T x_t      (x: n_steps columns)
+ *   transpose = 0:  y_t (+)= dR_t/drho x                        (x: n_cell, y: n_steps columns)
+ * through femo_elast_drho_multi and femo_elast_mass_drho_multi in windows of FEMO_ELAST_MAX_COLS columns from `first`, in
+ * ascending order: the whole history gives the bits of its windows accumulated one after the other.  Unmasked.            */
+int femo_elast_newmark_drho(femo_elast* e, const femo_newmark_params* p, int method, int mass_law, double density, int transpose,
+                            int n_steps, int first, int count, const femo_vec* rho, const femo_vec* U, const femo_vec* x,
+                            femo_vec* y, int accumulate);
+/* out[t] = f . U_t for every column, in windows through the Gram kernel (the call waits for them).                          */
+int femo_elast_newmark_dots(femo_elast* e, int n_steps, const femo_vec* f, const femo_vec* U, double* out /* [n_steps] */);
+/* Y_t = a[t] f for every column.                                                                                            */
+int femo_elast_newmark_outer(femo_elast* e, int n_steps, const double* a /* [n_steps] */, const femo_vec* f, femo_vec* Y);
 /* Additive multilevel preconditioner on nested auxiliary lattices over the mesh's bounding box (csrc/elast_pc.hip):
  *   M^-1 = D_blk^-1 + sum_l P_l C_l P_l^T,   C_l = blockdiag_d(P_l^T A P_l)^-1
  * A = K(rho) with identity rows / columns on the fixed dofs, P_l = multilinear interpolation from lattice l to the vertices
