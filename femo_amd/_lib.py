@@ -65,6 +65,19 @@ class EigInfo(C.Structure):
                 ("reserved", C.c_int32), ("residual", C.c_double * ELAST_MAX_COLS), ("solve_ms", C.c_double)]
 
 
+MMA_MAX_M = 8                     # FEMO_MMA_MAX_M: general constraints of one MMA handle
+
+
+class MmaParams(C.Structure):
+    _fields_ = [("move", C.c_double), ("sub_tol", C.c_double), ("c", C.c_double * MMA_MAX_M), ("d", C.c_double * MMA_MAX_M)]
+
+
+class MmaInfo(C.Structure):
+    _fields_ = [("converged", C.c_int32), ("step", C.c_int32), ("stages", C.c_int32), ("newton_steps", C.c_int32),
+                ("halvings", C.c_int32), ("blocking_copies", C.c_int32), ("residual_max", C.c_double), ("max_dx", C.c_double),
+                ("max_dx_rel", C.c_double), ("update_ms", C.c_double), ("lam", C.c_double * MMA_MAX_M), ("y", C.c_double * MMA_MAX_M)]
+
+
 class HostStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("h2d_pinned", "h2d_pinned_bytes", "h2d_staged", "h2d_staged_bytes",
                                          "h2d_skipped", "h2d_skipped_bytes", "h2d_as_d2d", "h2d_as_d2d_bytes",
@@ -283,6 +296,13 @@ PROTOTYPES = {
     "femo_filter_nnz": (C.c_int, [H, c_i64p]),
     "femo_filter_apply": (C.c_int, [H, C.c_int, H, H]),
     "femo_filter_export_csr": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # Method of Moving Asymptotes (csrc/mma.hip)
+    "femo_mma_create": (C.c_int, [H, c_i64, C.c_int, H, H, C.POINTER(MmaParams), C.POINTER(H)]),
+    "femo_mma_update": (C.c_int, [H, H, C.c_double, H, c_f64p, H, C.POINTER(MmaInfo)]),
+    "femo_mma_reset": (C.c_int, [H]),
+    "femo_mma_destroy": (C.c_int, [H]),
+    "femo_mma_get": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p]),
+    "femo_mma_solve_subproblem": (C.c_int, [H] + [C.c_void_p] * 11 + [C.POINTER(MmaInfo)]),
 }
 
 

@@ -29,6 +29,7 @@ from .elasticity import (Constant, Measure, TransientCompliance, TransientElasti
                          compliance_multiload, dynamic_compliance, dynamic_compliance_damped, eigenvalue_aggregate, meshtags,
                          pdeRes_harmonic, pdeRes_harmonic_damped, pdeRes_multiload, pdeRes_transient, pnorm_stress,
                          pnorm_stress_multiload, transient_compliance, von_Mises_stress, von_Mises_stress_multiload)
+from ..opt import CSDLProblem, MMA          # noqa: F401  the drivers' last lines (modopt.CSDLProblem + an optimiser)
 
 
 class AbstractFEA(object):

@@ -953,6 +953,65 @@ int femo_filter_apply(femo_filter* f, int transpose, const femo_vec* x, femo_vec
 /* the rows / cols / val that declare_derivatives('density', 'density_unfiltered', ...) is given (CSR of W or W^T)     */
 int femo_filter_export_csr(const femo_filter* f, int transpose, int64_t* rowptr, int32_t* col, double* val);
 
+/* ---- Method of Moving Asymptotes (csrc/mma.hip) -------------------------------------------------------------------------
+ * What the reference's drivers hand to modopt (run_topo_opt_cantilever_beam.py: modopt.CSDLProblem + SLSQP / SNOPT), as a
+ * device-resident update: minimise f_0(x) subject to f_i(x) <= 0, i = 1..m, xmin <= x <= xmax (Svanberg 1987; Svanberg 2007,
+ * "MMA and GCMMA -- two methods for nonlinear optimization", his defaults).  n variables, 0 <= m <= FEMO_MMA_MAX_M general
+ * constraints, finite bounds with xmax > xmin everywhere, fp64.  Per design step k = 1, 2, ...
+ *   asymptotes   k <= 2: L = x - 0.5 range, U = x + 0.5 range, range = xmax - xmin;  k >= 3: z = (x - x1)(x1 - x2) with the two
+ *                previous iterates, gamma = 1.2 / 0.7 / 1 for z > 0 / < 0 / = 0, L = x - gamma (x1 - L_old),
+ *                U = x + gamma (U_old - x1), then L into [x - 10 range, x - 0.01 range], U into [x + 0.01 range, x + 10 range];
+ *   move limits  alpha = max(xmin, L + 0.1 (x - L), x - move range), beta = min(xmax, U - 0.1 (U - x), x + move range);
+ *   p_ij = (U - x)^2 (1.001 g+ + 0.001 g- + rho), q_ij = (x - L)^2 (0.001 g+ + 1.001 g- + rho), g+- = max(+-df_i/dx_j, 0),
+ *                rho = 1e-5 / range;  b_i = sum_j (p_ij / (U - x) + q_ij / (x - L)) - f_i;
+ *   subproblem   min sum_j p_0j / (U_j - x_j) + q_0j / (x_j - L_j) + sum_i (c_i y_i + d_i y_i^2 / 2)
+ *                s.t. sum_j p_ij / (U_j - x_j) + q_ij / (x_j - L_j) - y_i <= b_i, alpha <= x <= beta, y >= 0
+ *                (Svanberg's z and a_i are dropped: a_i = 0 makes z = 0 at the optimum);
+ *   solver       his primal-dual interior-point Newton iteration on (x, y, lambda, xi, eta, mu, s): barrier 10^0 ... 10^-K,
+ *                K = ceil(-log10(sub_tol)) counted by an integer; per barrier Newton steps until the max-norm of the residual
+ *                is <= 0.9 barrier (at most 200); step 1 / max(1, 1.01 max(-delta / variable)) over the positive unknowns and
+ *                both bound distances of x, halved until the residual's 2-norm does not exceed the previous one (at most 50
+ *                times).  m = 0: x_j = clamp((sqrt(p_0) L + sqrt(q_0) U) / (sqrt(p_0) + sqrt(q_0)), alpha, beta), no iteration.
+ * Per variable the handle keeps x1, x2, L, U, alpha, beta, xi, eta and p, q for i = 0..m; the Newton direction of x, xi, eta is
+ * recomputed in registers from the m values of delta lambda.  The m x m Newton system is folded from per-block partial sums
+ * in a fixed order and solved on the host inside the call (small_solve.h); three blocking copies of at most 64 doubles per
+ * Newton step.  No float atomics: the same inputs give the same bits.  One rank.  Out of scope: GCMMA's inner conservative
+ * loop, equality constraints, passive cells (xmax = xmin), m > FEMO_MMA_MAX_M.                                            */
+#define FEMO_MMA_MAX_M 8
+typedef struct femo_mma femo_mma;
+typedef struct femo_mma_params {
+  double move;                   /* move limit as a fraction of the range, > 0 (Svanberg: 0.5)                 */
+  double sub_tol;                /* the last barrier value is the first 10^-K <= sub_tol; in (0, 1] (1e-7)      */
+  double c[FEMO_MMA_MAX_M];      /* c_i >= 0 (1000: presumes an objective of order one)                        */
+  double d[FEMO_MMA_MAX_M];      /* d_i > 0 (1)                                                                */
+} femo_mma_params;
+typedef struct femo_mma_info {
+  int32_t converged;             /* 1; 0 when a cap was hit (200 Newton steps in a stage, 50 halvings) or the iteration
+                                    left the finite numbers -- x then holds the last iterate                    */
+  int32_t step;                  /* k of this update, from 1                                                    */
+  int32_t stages;                /* barrier values gone through (0 for m = 0)                                   */
+  int32_t newton_steps;          /* in all stages                                                               */
+  int32_t halvings;              /* step halvings in all                                                        */
+  int32_t blocking_copies;       /* times the host waited for folded sums                                       */
+  double residual_max;           /* max-norm of the perturbed KKT rows at the last barrier value                */
+  double max_dx;                 /* max_j |x^{k+1} - x^k|                                                        */
+  double max_dx_rel;             /* max_j |x^{k+1} - x^k| / range_j                                              */
+  double update_ms;              /* host time of the call                                                       */
+  double lam[FEMO_MMA_MAX_M];    /* multipliers of the general constraints                                      */
+  double y[FEMO_MMA_MAX_M];
+} femo_mma_info;
+/* xmin, xmax: n entries each, copied.  params NULL: the defaults above.  Refused: a bound that is not finite, xmax <= xmin
+ * anywhere, m outside 0..FEMO_MMA_MAX_M, move <= 0, sub_tol outside (0, 1], c_i < 0, d_i <= 0.                             */
+int femo_mma_create(femo_ctx* ctx, int64_t n, int m, const femo_vec* xmin, const femo_vec* xmax, const femo_mma_params* params,
+                    femo_mma** out);
+/* One design step: x <- x^{k+1} in place.  df0: n entries; f: m values on the host; df: m stacked columns of n entries
+ * (NULL for m = 0).  Refused before anything changes: a value or gradient entry that is not finite, x outside its bounds.  */
+int femo_mma_update(femo_mma* h, femo_vec* x, double f0, const femo_vec* df0, const double* f, const femo_vec* df,
+                    femo_mma_info* info);
+/* Forget the history: the next update is step 1 again.                                                                   */
+int femo_mma_reset(femo_mma* h);
+int femo_mma_destroy(femo_mma* h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,18 @@ int femo_mat_spmv_scaled(femo_mat* A, int dots, const femo_vec* x, femo_vec* y, 
  * Counts as an assembly into A: everything derived from the old values is invalid.                           */
 int femo_mat_import_csr(femo_mat* A, const double* val);
 
+/* ---- MMA: what the last update built, and one subproblem from given arrays (tests) ------------------------------------------
+ * femo_mma_get copies to the host what the last femo_mma_update (or femo_mma_solve_subproblem) left in the handle:
+ * what = 0 L, 1 U, 2 alpha, 3 beta (n doubles each), 4 p_i, 5 q_i (n doubles, i = 0..m), 6 b (m doubles), 7 the sums
+ * b_i + f_i (m doubles), 8 xi, 9 eta (n doubles each).                                                                    */
+int femo_mma_get(femo_mma* h, int what, int i, double* out);
+/* Solves the subproblem given by host arrays (p, q: m + 1 rows of n; b: m values) with the handle's c, d and sub_tol.  x, xi,
+ * eta: n doubles each; small: 4 m doubles, y | lambda | mu | s.  The handle's history is left alone, its L ... q are
+ * overwritten.                                                                                                           */
+int femo_mma_solve_subproblem(femo_mma* h, const double* L, const double* U, const double* alpha, const double* beta,
+                              const double* p, const double* q, const double* b, double* x, double* xi, double* eta,
+                              double* small, femo_mma_info* info);
+
 #ifdef __cplusplus
 }
 #endif

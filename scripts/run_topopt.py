@@ -1,0 +1,175 @@
+"""The reference's cantilever driver to its end (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py): the SIMP design
+loop with the device-resident MMA update in the place of modopt's SLSQP / SNOPT.
+
+  python scripts/run_topopt.py --nelx 640 --nely 320 --pc multilevel --device --iters 20
+  python scripts/run_topopt.py --n3 48 --pc multilevel --device --iters 20 --host-update
+  ... --stress        a second constraint: the p-norm von Mises stress at most 0.9 times its value at the start design
+  ... --host          Simulator(device=False): NumPy arrays at the operator boundary, uploaded for the update
+  ... --host-update   also run the NumPy restatement's update (tests/mma_ref.py) on the same data, step by step
+
+Minimises the compliance under avg_density <= 0.40 from x = 0.4.  Prints one JSON line: per step the objective, the
+constraint values and the inner (Newton) iterations; the ms of the MMA update against the ms of the design cycle (the first
+step is the warm-up and left out of the statistics: median, minimum, maximum over the others); the bytes a Newton step moves
+by the count of DESIGN.md section 10 and the GB/s that gives; with --host-update the restatement's ms beside the device's,
+alternating with it step by step, and the largest difference between the two updates.  Writes the final filtered density
+to --out (XDMF)."""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def build(args):
+    from femo_amd.csdl_opt.fea_model import FEAModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.simulator import Simulator
+    from femo_amd.fea.elasticity import averageFunc, compliance, pdeRes
+    from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, Measure, VectorFunctionSpace,
+                                      createRectangleMesh, createUnitCubeMesh, locate_dofs_geometrical,
+                                      locate_entities_boundary, meshSize, meshtags)
+    if args.n3:
+        mesh = createUnitCubeMesh(args.n3)
+        marker = lambda x: np.logical_and(np.isclose(x[0], 1.0), x[2] < 0.25)
+        t = (0.0, 0.0, -1.0)
+    else:
+        LX, LY = 160.0, 80.0
+        mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([LX, LY]), args.nelx, args.nely)
+        marker = lambda x: np.logical_and(abs(x[1] - LY / 2) < LY / args.nely + 3e-6, abs(x[0] - LX) < 3e-6)
+        t = (0.0, -0.25)
+    d = mesh.tdim
+    facets = locate_entities_boundary(mesh, d - 1, marker)
+    ds_ = Measure("ds", domain=mesh, subdomain_data=meshtags(mesh, d - 1, facets, np.full(len(facets), 100, dtype=np.int32)))
+    fea = FEA(mesh)
+    fea.REPORT = False
+    Q, V = FunctionSpace(mesh, ("DG", 0)), VectorFunctionSpace(mesh, ("CG", 1))
+    rho, u = Function(Q), Function(V)
+    f = Constant(mesh, t)
+    res = pdeRes(u, None, rho, f, dss=ds_(100), preconditioner=args.pc)
+    fea.add_input("density", rho)
+    fea.add_state(name="displacements", function=u, residual_form=res, arguments=["density"])
+    fea.add_output(name="avg_density", type="scalar", form=averageFunc(rho), arguments=["density"])
+    fea.add_output(name="compliance", type="scalar", form=compliance(u, f, dss=ds_(100)), arguments=["displacements"])
+    stress = None
+    if args.stress:
+        from femo_amd.fea.elasticity import pnorm_stress
+        stress = pnorm_stress(u, rho, p=8.0, q=0.5)
+        fea.add_output(name="stress", type="scalar", form=stress, arguments=["displacements", "density"])
+        fea.consistent_bc_partials = True
+    ubc = Function(V)
+    ubc.vector.set(0.0)
+    fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), lambda x: np.isclose(x[0], 0.0, atol=1e-6))], V)
+    model = FEAModel(fea=[fea])
+    h = meshSize(mesh)
+    model.add(GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
+              name="general_filter_model")
+    model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.full(mesh.n_cell, 0.4))
+    model.add_design_variable("density_unfiltered", upper=1.0, lower=1e-4)
+    model.add_objective("compliance")
+    model.add_constraint("avg_density", upper=0.40)
+    sim = Simulator(model, device=args.device)
+    return sim, model, mesh, stress
+
+
+def newton_step_bytes(n, m):
+    """Bytes one Newton step without halvings moves ("Optimiser"): the three reading passes and the
+    commit each read x, xi, eta, L, U, alpha, beta and p, q of the m + 1 functions; the commit writes x, xi, eta."""
+    return (4 * (7 + 2 * (m + 1)) + 3) * 8 * n
+
+
+def stats(v):
+    v = np.asarray(v[1:] if len(v) > 1 else v, dtype=float)
+    return dict(median=float(np.median(v)), min=float(v.min()), max=float(v.max()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nelx", type=int, default=80)
+    ap.add_argument("--nely", type=int, default=40)
+    ap.add_argument("--n3", type=int, default=0)
+    ap.add_argument("--pc", choices=("jacobi", "multilevel"), default="jacobi")
+    ap.add_argument("--iters", type=int, default=20)
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--device", dest="device", action="store_true", default=True)
+    mode.add_argument("--host", dest="device", action="store_false")
+    ap.add_argument("--stress", action="store_true")
+    ap.add_argument("--host-update", action="store_true")
+    ap.add_argument("--out", default=os.path.join("topopt_out", "density.xdmf"))
+    args = ap.parse_args()
+    from femo_amd import _lib
+    from femo_amd.engine import Context, Vec
+    from femo_amd.fea import utils_hip
+    from femo_amd.fea.io import XDMFRecorder
+    from femo_amd.opt import MMA, CSDLProblem
+    if _lib.device_count() < 1:
+        raise SystemExit("run_topopt needs a HIP device")
+    ctx = Context(0)
+    utils_hip.set_context(ctx)
+    sim, model, mesh, stress = build(args)
+    n = mesh.n_cell
+    if stress is not None:
+        # the aggregate's scale from the start design, and its bound: 0.9 times its value there
+        sim.run()
+        cells = Vec(ctx, n)
+        stress.m = 1.0 / float(np.max(stress.device().von_mises(stress.u.vec, cells, stress.rho.vec, stress.q).get()))
+        sim.run()
+        model.add_constraint("stress", upper=0.9 * float(np.asarray(sim["stress"]).ravel()[0]))
+    prob = CSDLProblem(problem_name="beam_topo_opt", simulator=sim)
+    optimizer = MMA(prob, max_iter=args.iters, move=0.5, tol=0.0, sub_tol=1e-7, normalize=True).setup()
+    host = dict(ms=[], dx=[], newton=[])
+    if args.host_update:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import mma_ref
+        ref = mma_ref.MMA(prob.xmin, prob.xmax, prob.m)
+        pending = []
+
+        def on_update(x, f0, df0, f, df):
+            xh, g0 = np.array(x.get()), np.array(df0.get())
+            g = np.array(df.get()).reshape(prob.m, n) if prob.m else np.zeros((0, n))
+            t0 = time.perf_counter()
+            xn = ref.update(xh, g0, f, g)
+            host["ms"].append((time.perf_counter() - t0) * 1e3)
+            host["newton"].append(ref.last["rec"]["newton"])
+            # the restatement keeps its own history; it is handed the device's iterate every step, so that both update the same data
+            pending.append((x, xn))
+        optimizer.callback = on_update
+    res = optimizer.solve()
+    if args.host_update:
+        # the device's x^{k+1} is the next step's x^k: compare the last pair (the earlier ones were overwritten in place)
+        x, xn = pending[-1]
+        host["dx"] = float(np.abs(np.array(x.get()) - xn).max())
+    optimizer.print_results()
+    sim.run()
+    if os.path.dirname(args.out):
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    rec = XDMFRecorder(args.out)
+    rec.write_mesh(mesh)
+    rho = np.array(np.asarray(sim["density"]), dtype=np.float64)
+    rec.write_function(types.SimpleNamespace(vector=types.SimpleNamespace(getArray=lambda: rho), name="density"), t=len(res["objective"]))
+    upd, cyc = stats(res["update_ms"]), stats(res["cycle_ms"])
+    inner = res["inner"][1:] if len(res["inner"]) > 1 else res["inner"]
+    trials = np.add(res["inner"], res["halvings"]) + np.asarray(res["stages"])
+    passes = 3 * np.asarray(res["inner"]) + trials                      # assemble, stepmax, commit + every trial
+    step_bytes = newton_step_bytes(n, prob.m)
+    update_bytes = passes * (7 + 2 * (prob.m + 1)) * 8 * n + 3 * 8 * n * np.asarray(res["inner"])
+    gbps = update_bytes / (np.asarray(res["update_ms"]) * 1e-3) / 1e9
+    out = dict(metric="topopt_mma", mesh=(f"cube n={args.n3}" if args.n3 else f"rect {args.nelx}x{args.nely}"), n_cell=n,
+               m=prob.m, pc=args.pc, device=bool(args.device), steps=len(res["objective"]), objective=res["objective"],
+               constraints=res["constraints"], inner=res["inner"], halvings=res["halvings"], converged=res["converged"],
+               max_dx=res["max_dx"], update_ms=upd, cycle_ms=cyc, update_share=upd["median"] / (upd["median"] + cyc["median"]),
+               newton_per_update=float(np.mean(inner)), newton_step_bytes=step_bytes,
+               update_GBps=stats(list(gbps)), density_file=args.out,
+               avg_density=float(np.asarray(sim["avg_density"]).ravel()[0]), final_compliance=float(np.asarray(sim["compliance"]).ravel()[0]))
+    if args.host_update:
+        out.update(host_update_ms=stats(host["ms"]), host_newton=host["newton"], host_vs_device_last_dx=host["dx"])
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
