@@ -364,4 +364,25 @@ __device__ __forceinline__ void block_inverse(double (&B)[D * D], double (&Bi)[D
     Bi[8] = (B[0] * B[4] - B[1] * B[3]) * id;
   }
 }
+
+// block-Jacobi inverse of the diagonal block B of a vertex: the components flagged in fx[0 .. D) (null: none) are identity
+// rows / columns of B and of the inverse, exactly.  The closed form alone gives them det * (1 / det), which is 1 only to a
+// rounding where some but not all components of the vertex are fixed.
+template <int D>
+__device__ __forceinline__ void block_inverse_fixed(double (&B)[D * D], const uint8_t* __restrict__ fx, double (&Bi)[D * D]) {
+  bool f[D];
+#pragma unroll
+  for (int r = 0; r < D; ++r) f[r] = fx && fx[r];
+#pragma unroll
+  for (int r = 0; r < D; ++r)
+#pragma unroll
+    for (int c = 0; c < D; ++c)
+      if (f[r] || f[c]) B[r * D + c] = r == c ? 1.0 : 0.0;
+  block_inverse<D>(B, Bi);
+#pragma unroll
+  for (int r = 0; r < D; ++r)
+#pragma unroll
+    for (int c = 0; c < D; ++c)
+      if (f[r] || f[c]) Bi[r * D + c] = r == c ? 1.0 : 0.0;
+}
 #endif

@@ -179,11 +179,8 @@ __global__ __launch_bounds__(EB) void k_newmark_dinv(int64_t n_rows, const doubl
 #pragma unroll
   for (int r = 0; r < D; ++r)
 #pragma unroll
-    for (int cc = 0; cc < D; ++cc) {
-      const bool fr = fixed && fixed[row * D + r], fc = fixed && fixed[row * D + cc];
-      B[r * D + cc] = (fr || fc) ? (r == cc ? 1.0 : 0.0) : diag[row * DD + r * D + cc] + (r == cc ? md : 0.0);
-    }
-  block_inverse<D>(B, Bi);
+    for (int cc = 0; cc < D; ++cc) B[r * D + cc] = diag[row * DD + r * D + cc] + (r == cc ? md : 0.0);
+  block_inverse_fixed<D>(B, fixed ? fixed + row * D : nullptr, Bi);
 #pragma unroll
   for (int q = 0; q < DD; ++q) dinv[row * DD + q] = Bi[q];
 }

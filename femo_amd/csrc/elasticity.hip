@@ -87,13 +87,8 @@ __global__ __launch_bounds__(EB) void k_elast_assemble(
   // block-Jacobi: inverse of the diagonal block, fixed components as identity rows / columns
   double B[DD], Bi[DD];
 #pragma unroll
-  for (int r = 0; r < D; ++r)
-#pragma unroll
-    for (int cc = 0; cc < D; ++cc) {
-      const bool fr = fixed && fixed[row * D + r], fc = fixed && fixed[row * D + cc];
-      B[r * D + cc] = (fr || fc) ? (r == cc ? 1.0 : 0.0) : dg[r * D + cc];
-    }
-  block_inverse<D>(B, Bi);
+  for (int q = 0; q < DD; ++q) B[q] = dg[q];
+  block_inverse_fixed<D>(B, fixed ? fixed + row * D : nullptr, Bi);
 #pragma unroll
   for (int q = 0; q < DD; ++q) dinv[row * DD + q] = Bi[q];
 }

@@ -182,6 +182,7 @@ class Multilevel:
 
     def __init__(self, x, conn, rho, method="SIMP", fixed_mask=None, spacing_factor=0.0, E=1.0, nu=0.3, K=None):
         self.d = d = x.shape[1]
+        self._x = x
         self.plan = lattice_plan(x, conn, spacing_factor)
         self.mask = None if fixed_mask is None else np.asarray(fixed_mask, dtype=np.uint8)
         K = ref.stiffness(x, conn, rho, method, E, nu) if K is None else K
@@ -199,6 +200,35 @@ class Multilevel:
         for P, C in zip(self.P, self.C):
             z += P @ np.einsum("nij,nj->ni", C, (P.T @ r).reshape(-1, self.d)).ravel()
         return z
+
+    def apply_abs(self, r):
+        """a = |D^-1| |r| + sum_l |P_l| |C_l| |P_l^T| |r|: what the rounding errors of one application are measured in."""
+        r = np.abs(r)
+        a = np.einsum("nij,nj->ni", np.abs(self.Dinv), r.reshape(-1, self.d)).ravel()
+        for P, C in zip(self.P, self.C):
+            Pa = abs(P)
+            a += Pa @ np.einsum("nij,nj->ni", np.abs(C), (Pa.T @ r).reshape(-1, self.d)).ravel()
+        return a
+
+    def apply_long(self, r):
+        """`apply` with the same fp64 D^-1, P_l and C_l, every product and sum in np.longdouble."""
+        ld, d = np.longdouble, self.d
+        r = np.asarray(r, dtype=ld)
+        z = np.einsum("nij,nj->ni", self.Dinv.astype(ld), r.reshape(-1, d)).ravel()
+        for P, C in zip(self.P, self.C):
+            P = P.tocoo()
+            w = P.data.astype(ld)
+            g = np.zeros(P.shape[1], dtype=ld)
+            np.add.at(g, P.col, w * r[P.row])
+            e = np.einsum("nij,nj->ni", C.astype(ld), g.reshape(-1, d)).ravel()
+            np.add.at(z, P.row, w * e[P.col])
+        return z
+
+    def longest_restriction_list(self):
+        """n_hat: the most vertices under the hat of one node of the finest lattice."""
+        S = scalar_interpolation(self.plan, self._x, self.plan["n_levels"] - 1).tocsc()
+        S.eliminate_zeros()
+        return int(np.diff(S.indptr).max())
 
 
 def pcg(A, b, precond, fixed_mask=None, rtol=1e-15, atol=0.0, max_it=100000):
@@ -274,6 +304,165 @@ def small_meshes():
             "square9j": lambda: createUnitSquareMesh(9, 0.25),
             "cube4j": lambda: createUnitCubeMesh(4, 0.2)}
 
+
+LDS_DOUBLES = 2048          # a level of more than LDS_DOUBLES / d^2 nodes adds its blocks with global atomics
+COARSE_THREADS = 1024       # a lattice below the finest with more nodes takes the one-workgroup sweep more than one trip
+
+
+def path_meshes():
+    """name -> (mesh factory, spacing factor): the cases on which the other paths of csrc/elast_pc.hip engage.  What each
+    is for stands in PATH_PLANS below and is asserted from the plan by the tests that use it."""
+    import wide_meshes as W
+    from femo_amd.fea.mesh import Mesh, createRectangleMesh, createUnitCubeMesh
+
+    def box8j():
+        m = createUnitCubeMesh(8, 0.2)
+        return Mesh(m.x * np.array([1.0, 1.0, 2.0]), m.conn)
+
+    return {"rect52x26": (lambda: createRectangleMesh([0.0, 0.0], [2.0, 1.0], 52, 26), 0.0),
+            "rect30x20_wide": (lambda: createRectangleMesh([0.0, 0.0], [1.5, 1.0], 30, 20), 1.0),
+            "rect64x32_fine": (lambda: createRectangleMesh([0.0, 0.0], [2.0, 1.0], 64, 32), 0.5),
+            "fan64x24_random": (lambda: Mesh(*W.renumber(*W.fan(64, 24), W.random_numbering(1537, 11))), 1.0),
+            "cube8j": (lambda: createUnitCubeMesh(8, 0.2), 1.0),
+            "cube5_8": (lambda: Mesh(*W.cube5(8)), 1.0),
+            "box8j_fine": (box8j, 0.25),
+            "fan40x8": (lambda: Mesh(*W.fan(40, 8)), 1.0)}                  # host tests only: small enough for cell_blocks
+
+
+# vertices, cells, nodes per level (coarsest first) of path_meshes(), as lattice_plan gave them when the cases were chosen
+PATH_PLANS = {"rect52x26": (1431, 2704, [6, 15, 45, 153, 561]),
+              "rect30x20_wide": (651, 1200, [6, 15, 45, 153, 561]),
+              "rect64x32_fine": (2145, 4096, [6, 15, 45, 153, 561, 2145, 8385]),
+              "fan64x24_random": (1537, 3008, [4, 9, 25, 81, 289, 1089]),
+              "cube8j": (729, 3072, [8, 27, 125, 729]),
+              "cube5_8": (729, 2560, [8, 27, 125, 729]),
+              "box8j_fine": (729, 3072, [12, 45, 225, 1377, 9537]),
+              "fan40x8": (321, 600, [4, 9, 25, 81, 289])}
+# levels on the global-atomic block path, levels below the finest that the one-workgroup sweep takes in several trips
+PATH_LEVELS = {"rect52x26": ([4], []), "rect30x20_wide": ([4], []), "rect64x32_fine": ([4, 5, 6], [5]),
+               "fan64x24_random": ([5], []), "cube8j": ([3], []), "cube5_8": ([3], []), "box8j_fine": ([3, 4], [3]),
+               "fan40x8": ([], [])}
+# per level under path_mask: nodes with an all-zero block, nodes with some but not all diagonal entries zero (the
+# restatement's counts; the lattice nodes no vertex reaches are 0, 3, 10, 36, 136 on rect30x20_wide, 6240 of the finest on
+# rect64x32_fine, 4, 32, 184 on the fan, 132 and 6764 on the stretched box)
+PATH_DEAD = {"rect52x26": ([0, 0, 0, 0, 0], [0, 3, 10, 36, 136]),
+             "rect30x20_wide": ([0, 3, 10, 36, 136], [0, 0, 5, 27, 102]),
+             "rect64x32_fine": ([0, 0, 0, 0, 0, 33, 6273], [0, 3, 10, 36, 136, 528, 528]),
+             "fan64x24_random": ([0, 0, 0, 4, 32, 184], [0, 0, 5, 16, 52, 178]),
+             "cube8j": ([0, 0, 0, 29], [0, 0, 25, 165]),
+             "cube5_8": ([0, 0, 0, 81], [0, 0, 25, 162]),
+             "box8j_fine": ([0, 0, 0, 180, 6845], [0, 0, 45, 291, 666]),
+             "fan40x8": ([0, 0, 0, 4, 41], [0, 0, 5, 16, 48])}
+PATH_GPU_CASES = ["rect52x26", "rect30x20_wide", "rect64x32_fine", "fan64x24_random", "cube8j", "cube5_8", "box8j_fine"]
+
+
+def path_mask(mesh):
+    """The fixed set of the path cases: the clamped face x = 0 (where the mesh has no such face, as the fan, all dofs of
+    the vertex with the smallest x), then component 1 of every vertex in the quarter x > x_min + 0.75 (x_max - x_min): a
+    region of rollers, under which lattice nodes keep some components and lose the others."""
+    d, xs = mesh.tdim, mesh.x[:, 0]
+    if np.isclose(xs.min(), 0.0):
+        mask = clamped_face(mesh)
+    else:
+        mask = np.zeros(d * mesh.n_vert, dtype=np.uint8)
+        mask[d * int(np.argmin(xs)):d * (int(np.argmin(xs)) + 1)] = 1
+    mask[d * np.nonzero(xs > xs.min() + 0.75 * (xs.max() - xs.min()))[0] + 1] = 1
+    return mask
+
+
+_PATH_CASES = {}
+
+
+def path_case(name, method="SIMP"):
+    """(mesh, spacing factor, rho, mask, Multilevel) of one path case, built once per process and shared: read only."""
+    if (name, method) not in _PATH_CASES:
+        make, f = path_meshes()[name]
+        mesh = make()
+        rho = np.random.default_rng(7).uniform(1e-3, 1.0, mesh.n_cell)
+        mask = path_mask(mesh)
+        _PATH_CASES[name, method] = (mesh, f, rho, mask, Multilevel(mesh.x, mesh.conn, rho, method, mask, spacing_factor=f))
+    return _PATH_CASES[name, method]
+
+
+def path_levels(nodes, d):
+    """(levels on the atomic block path, levels below the finest above COARSE_THREADS nodes) of a list of node counts."""
+    return ([l for l, n in enumerate(nodes) if n * d * d > LDS_DOUBLES],
+            [l for l, n in enumerate(nodes[:-1]) if n > COARSE_THREADS])
+
+
+def max_valence(conn):
+    """(vertex, its number of distinct neighbours) of the longest row."""
+    nv = conn.shape[1]
+    e = np.concatenate([conn[:, [a, b]] for a in range(nv) for b in range(nv) if a != b])
+    e = np.unique(e, axis=0)
+    cnt = np.bincount(e[:, 0])
+    return int(cnt.argmax()), int(cnt.max())
+
+
+def is_lexicographic(x):
+    """Vertices numbered by ascending (z, y, x), x fastest, as the structured constructors number them."""
+    return bool(np.array_equal(np.lexsort(x.T), np.arange(len(x))))
+
+
+def dead_counts(G):
+    """(nodes with an all-zero diagonal, nodes with some but not all diagonal entries zero) of one level's blocks."""
+    z = (np.diagonal(G, axis1=1, axis2=2) == 0.0).sum(axis=1)
+    return int((z == G.shape[1]).sum()), int(((z > 0) & (z < G.shape[1])).sum())
+
+
+def lame_ratio(E=1.0, nu=0.3):
+    lam, mu = ref.lame(E, nu)
+    return (lam + mu) / mu
+
+
+def block_bound(G, n_cell, E=1.0, nu=0.3):
+    """(nodes,): the most an entry of a node's block may differ between two fp64 evaluations.  An entry is a sum of at
+    most n_cell cell terms (plus the flushes of the workgroups that accumulate in LDS, 64 covers them with the roundings of
+    a term); the diagonal terms are non-negative with t_rr >= mu0 |g_r|^2, so |t_rc| <= (lam0 + mu0) |g_r| |g_c| <=
+    ((lam0 + mu0) / mu0) max(t_rr, t_cc); the leading 2 covers the sparse products of this file."""
+    return 2.0 * (n_cell + 64) * 2.0 ** -53 * lame_ratio(E, nu) * np.diagonal(G, axis1=1, axis2=2).max(axis=1)
+
+
+def block_entry_bound(G, n_cell, E=1.0, nu=0.3):
+    """(nodes, d, d): block_bound entry by entry.  |t_rc| <= ((lam0 + mu0) / mu0) sqrt(t_rr t_cc) cell by cell, and
+    sum_e sqrt(t_rr t_cc) <= sqrt(G_rr G_cc) by Cauchy-Schwarz, so entry (r, c) carries sqrt(G_rr G_cc) where block_bound
+    has the node's largest diagonal entry: never more, and far less on a component that only weakly weighted free
+    vertices reach beside one that is reached in full."""
+    dg = np.diagonal(G, axis1=1, axis2=2)
+    return 2.0 * (n_cell + 64) * 2.0 ** -53 * lame_ratio(E, nu) * np.sqrt(dg[:, :, None] * dg[:, None, :])
+
+
+def block_conditions(G):
+    """Condition number of the live part of every block after scaling it to a unit diagonal (nan for an all-zero block).
+    This is the number that carries block_entry_bound to the inverse: with S = diag(G)^-1/2 the error of S G S is at most
+    the relative bound in every entry, C = S (S G S)^-1 S, and the scaling cancels from error and inverse alike.  (The
+    unscaled condition number reaches 5e6 where rollers leave a node one strongly and one weakly reached component.)"""
+    d = G.shape[1]
+    dg = np.diagonal(G, axis1=1, axis2=2)
+    live = dg != 0.0
+    s = np.where(live, 1.0 / np.sqrt(np.where(live, dg, 1.0)), 0.0)
+    Gs = G * s[:, :, None] * s[:, None, :]
+    out = np.full(G.shape[0], np.nan)
+    for pat in itertools.product((False, True), repeat=d):
+        k = np.nonzero(pat)[0]
+        sel = np.nonzero((live == np.array(pat)).all(axis=1))[0]
+        if len(k) and len(sel):
+            out[sel] = np.linalg.cond(Gs[sel][:, k][:, :, k])
+    return out
+
+
+def apply_gamma(M):
+    """gamma_s of one application: unit round-off times the length of its longest chain of sums, n_hat terms of the mesh
+    restriction, 3^d down and 2^d <= 3^d up per level, d-term block products and the two gathers of the last kernel."""
+    d = M.d
+    return 2.0 ** -53 * (M.longest_restriction_list() + 2 * 3 ** d * M.plan["n_levels"] + 8 * d)
+
+
+def apply_bound(M, n_cell, r, E=1.0, nu=0.3):
+    """Per entry: (gamma_s + 4 beta) a, beta the relative block error of block_bound without its leading 2, times 4 for the
+    condition number of a live block (block_conditions <= 4 is asserted beside every use)."""
+    beta = (n_cell + 64) * 2.0 ** -53 * lame_ratio(E, nu)
+    return (apply_gamma(M) + 4.0 * beta) * M.apply_abs(r)
 
 
 

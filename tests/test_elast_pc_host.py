@@ -1,5 +1,6 @@
 """Host checks of the multilevel elasticity preconditioner: the restatement (tests/elast_pc_ref.py) against its own
-definitions, the caps of the GPU count tests met by the restatement alone, and the binding of the new entry points."""
+definitions, the caps of the GPU count tests met by the restatement alone, the plans, dead nodes and bounds of the path
+cases (tests/test_gpu_elast_pc_paths.py) met by the restatement alone, and the binding of the new entry points."""
 import numpy as np
 import pytest
 
@@ -83,6 +84,85 @@ def test_reference_counts_meet_the_caps(kind):
     assert j80 >= 4 * m80
     assert j320 >= 10 * m320
     assert m320 <= 1.3 * m80
+
+
+# ------------------------------------------------------------------------------ the path cases (pr.path_meshes) ----
+# The bounds of tests/test_gpu_elast_pc_paths.py are met by the restatement alone, before any device number is read.
+@pytest.mark.parametrize("name", sorted(pr.PATH_PLANS))
+def test_path_plan(name):
+    """The plan each case was chosen for: levels, nodes, the levels beyond LDS_DOUBLES / d^2 nodes (global-atomic block
+    path) and the levels below the finest beyond COARSE_THREADS nodes (several trips of the one-workgroup sweep)."""
+    make, f = pr.path_meshes()[name]
+    mesh = make()
+    plan = pr.lattice_plan(mesh.x, mesh.conn, f)
+    n_vert, n_cell, nodes = pr.PATH_PLANS[name]
+    assert (mesh.n_vert, mesh.n_cell) == (n_vert, n_cell)
+    assert plan["n_levels"] == len(nodes) and plan["nodes"] == nodes
+    assert pr.path_levels(plan["nodes"], mesh.tdim) == pr.PATH_LEVELS[name]
+    if name.startswith("fan"):
+        hub, rows = pr.max_valence(mesh.conn)
+        assert rows == int(name[3:5])                                # the hub row
+        if name == "fan64x24_random":
+            assert hub != 0 and not pr.is_lexicographic(mesh.x)
+    if name == "cube5_8":
+        assert pr.max_valence(mesh.conn)[1] == 18
+    if name == "rect30x20_wide":                                     # the lattice sticks out of the bounding box
+        assert (plan["n"][0] * plan["H"][0] > mesh.x.max(axis=0) - mesh.x.min(axis=0) + 0.25).any()
+    if name == "box8j_fine":                                         # the largest of 0.5, 0.25 with > 1024 nodes below the finest
+        assert pr.path_levels(pr.lattice_plan(mesh.x, mesh.conn, 0.5)["nodes"], 3)[1] == []
+
+
+@pytest.mark.parametrize("name", sorted(pr.PATH_DEAD))
+def test_path_dead_nodes(name):
+    mesh, f, rho, mask, M = pr.path_case(name)
+    dead, partly = zip(*(pr.dead_counts(G) for G in M.G))
+    print(f"{name}: all-zero blocks {list(dead)}, partly dead {list(partly)}")
+    assert (list(dead), list(partly)) == pr.PATH_DEAD[name]
+    assert sum(partly) > 0                                           # every case has the region of rollers
+    # a dead component has an exactly zero row and column in the block and in its inverse
+    for G, Ci in zip(M.G, M.C):
+        z = np.diagonal(G, axis1=1, axis2=2) == 0.0
+        assert not G[z].any() and not np.transpose(G, (0, 2, 1))[z].any()
+        assert not Ci[z].any() and not np.transpose(Ci, (0, 2, 1))[z].any()
+
+
+@pytest.mark.parametrize("name", ["fan40x8", "rect30x20_wide"])
+def test_path_block_bound(name):
+    """The two derivations of the blocks (sparse products, cell by cell) within a quarter of block_bound, and of the
+    entry-wise block_entry_bound, at every node of every level."""
+    mesh, f, rho, mask, M = pr.path_case(name)
+    coef = ref.penal(rho, "SIMP")
+    for l, G in enumerate(M.G):
+        B = pr.cell_blocks(M.plan, mesh.x, mesh.conn, coef, l, mask)
+        assert np.array_equal(np.diagonal(B, axis1=1, axis2=2) == 0.0, np.diagonal(G, axis1=1, axis2=2) == 0.0)
+        bn, be = pr.block_bound(G, mesh.n_cell), pr.block_entry_bound(G, mesh.n_cell)
+        err = np.abs(B - G)
+        live = bn > 0.0
+        rn = (err[live].max(axis=(1, 2)) / bn[live]).max()
+        re = (err[be > 0.0] / be[be > 0.0]).max()
+        print(f"{name} level {l}: |cell - product| / bound: per node {rn:.4f}, per entry {re:.4f}")
+        assert not err[~live].any() and not err[be == 0.0].any()
+        assert rn <= 0.25 and re <= 0.25
+
+
+@pytest.mark.parametrize("name", sorted(pr.PATH_PLANS))
+def test_path_apply_bound(name):
+    """fp64 application against the same one in np.longdouble: a tenth of gamma_s a entry by entry."""
+    mesh, f, rho, mask, M = pr.path_case(name)
+    x = np.random.default_rng(5).standard_normal(mesh.tdim * mesh.n_vert)
+    z, zl, a = M.apply(x), M.apply_long(x), M.apply_abs(x)
+    assert (a > 0.0).all()
+    ratio = float((np.abs(z - zl) / (pr.apply_gamma(M) * a)).max())
+    print(f"{name}: |fp64 - longdouble| / (gamma_s a) = {ratio:.4f}, {float(np.abs(z - zl).max() / np.abs(z).max()):.2e} of max |z|")
+    assert ratio <= 0.1
+
+
+@pytest.mark.parametrize("name", sorted(pr.PATH_PLANS))
+def test_path_block_conditioning(name):
+    mesh, f, rho, mask, M = pr.path_case(name)
+    worst = [float(np.nanmax(pr.block_conditions(G))) for G in M.G]
+    print(f"{name}: largest condition number of a live block, level by level: {[round(w, 2) for w in worst]}")
+    assert max(worst) <= 4.0
 
 
 def test_lib_binds_the_entry_points():
