@@ -78,6 +78,14 @@ class MmaInfo(C.Structure):
                 ("max_dx_rel", C.c_double), ("update_ms", C.c_double), ("lam", C.c_double * MMA_MAX_M), ("y", C.c_double * MMA_MAX_M)]
 
 
+PROJECT_FIXED, PROJECT_VOLUME = 0, 1     # FEMO_PROJECT_FIXED / FEMO_PROJECT_VOLUME
+
+
+class ProjectInfo(C.Structure):
+    _fields_ = [("eta", C.c_double), ("vol_in", C.c_double), ("vol_out", C.c_double), ("s_v", C.c_double), ("ms", C.c_double),
+                ("flat", C.c_int32), ("mode", C.c_int32), ("launches", C.c_int32), ("reserved", C.c_int32)]
+
+
 class HostStats(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("h2d_pinned", "h2d_pinned_bytes", "h2d_staged", "h2d_staged_bytes",
                                          "h2d_skipped", "h2d_skipped_bytes", "h2d_as_d2d", "h2d_as_d2d_bytes",
@@ -303,6 +311,16 @@ PROTOTYPES = {
     "femo_mma_destroy": (C.c_int, [H]),
     "femo_mma_get": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p]),
     "femo_mma_solve_subproblem": (C.c_int, [H] + [C.c_void_p] * 11 + [C.POINTER(MmaInfo)]),
+    # Heaviside projection, passive cells, volume-preserving threshold (csrc/project.hip)
+    "femo_project_create": (C.c_int, [H, c_i64, C.c_void_p, c_i64, C.c_void_p, c_i64, C.c_void_p, C.c_double, C.c_double,
+                                      C.c_double, C.c_int, C.POINTER(H)]),
+    "femo_project_destroy": (C.c_int, [H]),
+    "femo_project_set": (C.c_int, [H, C.c_double, C.c_double, C.c_int]),
+    "femo_project_forward": (C.c_int, [H, H, H, C.POINTER(ProjectInfo)]),
+    "femo_filter_project": (C.c_int, [H, H, H, H, H, C.POINTER(ProjectInfo)]),
+    "femo_project_reverse": (C.c_int, [H, H, H, H]),
+    "femo_project_tangent": (C.c_int, [H, H, H, H]),
+    "femo_project_grayness": (C.c_int, [H, H, C.POINTER(C.c_double)]),
 }
 
 

@@ -9,12 +9,14 @@ W and W^T are built once on the device (csrc/elasticity.hip: hash grid, count / 
 Jacobian-vector products are gathers on the GPU.  Values may be NumPy arrays or ``DeviceArray``.  With the real
 ``csdl`` the sparse partials (rows, cols, val) are declared as a CSDL backend expects, exported once from the device.
 """
+import time
+
 import numpy as np
 
 from femo_amd import engine as E
 from femo_amd.csdl_opt._csdl_compat import HAVE_CSDL, CustomExplicitOperation, Model, custom
 from femo_amd.engine import DeviceArray, Vec
-from femo_amd.fea.elasticity import DeviceFilter
+from femo_amd.fea.elasticity import DeviceFilter, DeviceProjection, check_projection_params
 from femo_amd.fea.utils_hip import get_context
 
 _FILTER_PARAMS = (('nel', {}), ('beta', dict(default=2.)), ('coordinates', {}), ('h_avg', {}))
@@ -108,3 +110,167 @@ class GeneralFilterOperation(CustomExplicitOperation):
                                                            self._product(d_outputs['density'], True))
         else:
             raise ValueError(f"unknown mode {mode!r}")
+
+
+# ---------------------------------------------------------------------------------- filter + Heaviside projection ----
+_PROJECTION_PARAMS = _FILTER_PARAMS + (('projection_beta', dict(default=0.)), ('eta', dict(default=0.5)),
+                                       ('volumes', dict(default=None)), ('solid', dict(default=None)),
+                                       ('void', dict(default=None)), ('void_value', dict(default=1e-4)))
+
+
+def check_projection_parameters(nel, projection_beta=0., eta=0.5, volumes=None, solid=None, void=None, void_value=1e-4):
+    """The refusals of ProjectedFilterModel's parameters, without a device: a negative or non-finite ``projection_beta``,
+    ``eta`` outside [0, 1] and not ``"volume"``, indices outside 0..nel-1, a cell both solid and void, ``void_value`` outside
+    (0, 1], volumes of the wrong length or not positive and finite, ``"volume"`` with no active cell.  Returns the checked
+    (beta, eta, mode, volumes, solid, void, void_value)."""
+    return check_projection_params(nel, projection_beta, eta, volumes, () if solid is None else solid,
+                                   () if void is None else void, void_value)
+
+
+class ProjectedFilterModel(Model):
+    """``density_unfiltered`` -> ``density`` through the filter and the Heaviside projection (three-field SIMP):
+    density = P(W density_unfiltered), P as include/femo_hip.h, "Heaviside projection", states it.  The general filter's
+    parameters, plus ``projection_beta`` (0: the identity), ``eta`` (a number in [0, 1] or ``"volume"``), ``volumes``
+    (cell volumes; None: ones), ``solid`` / ``void`` (passive cell indices) and ``void_value``.  ``operation`` is the
+    ProjectedFilterOperation (a BetaContinuation takes it)."""
+
+    def initialize(self):
+        for name, kw in _PROJECTION_PARAMS:
+            self.parameters.declare(name, **kw)
+
+    def define(self):
+        P = self.parameters
+        nel = P['nel']
+        density_unfiltered = self.declare_variable('density_unfiltered', shape=(nel,), val=1.0)
+        self.operation = ProjectedFilterOperation(**{name: P[name] for name, _ in _PROJECTION_PARAMS})
+        self.register_output('density', custom(density_unfiltered, op=self.operation))
+
+
+class ProjectedFilterOperation(CustomExplicitOperation):
+    """input: unfiltered density (DG0), output: filtered and projected density.  The Jacobian is not constant, so no sparse
+    partials are declared: ``compute_jacvec_product`` is the interface.  ``beta`` and ``eta`` may be set between runs;
+    ``last`` is the info record of the last ``compute`` (eta, flat, vol_in, vol_out, ...)."""
+
+    def initialize(self):
+        for name, kw in _PROJECTION_PARAMS:
+            self.parameters.declare(name, **kw)
+
+    def define(self):
+        P = self.parameters
+        self.nel = int(P['nel'])
+        coords = np.asarray(P['coordinates'], dtype=np.float64)
+        if coords.shape[0] != self.nel:
+            raise ValueError(f"ProjectedFilterOperation: {coords.shape[0]} coordinates for nel = {self.nel}")
+        if coords.shape[1] == 3 and np.all(coords[:, 2] == 0.0):
+            coords = coords[:, :2]                     # dolfinx tabulates 3 coordinates for a 2-D mesh
+        check_projection_parameters(self.nel, P['projection_beta'], P['eta'], P['volumes'], P['solid'], P['void'], P['void_value'])
+        self.radius = float(P['beta']) * float(P['h_avg'])
+        self.add_input('density_unfiltered', shape=(self.nel,), val=0.0)
+        self.add_output('density', shape=(self.nel,))
+        ctx = get_context()
+        self.filter = DeviceFilter(ctx, coords, self.radius)
+        self.projection = DeviceProjection(ctx, self.nel, P['projection_beta'], P['eta'], P['volumes'],
+                                           () if P['solid'] is None else P['solid'], () if P['void'] is None else P['void'],
+                                           P['void_value'])
+        self._x = self._a = None
+        self._xt, self._rho, self._t, self._y = (Vec(ctx, self.nel) for _ in range(4))
+        self._seen = None             # the input x-tilde belongs to: a host copy, or the device vector itself
+        self.last = None
+        self.time_ms = dict(compute=0.0, jacvec=0.0, calls=0)      # host time spent in compute / in the products, accumulated
+        self.sync_timers = False      # True: wait for the device before and after each call, so that the times are the
+                                      # projection's own and not those of work queued before it (measurements)
+        self.declare_derivatives('density', 'density_unfiltered')
+
+    # -- settings ----------------------------------------------------------------------------
+    @property
+    def beta(self) -> float:
+        return self.projection.beta
+
+    @beta.setter
+    def beta(self, value) -> None:
+        self.projection.set(beta=value)
+        self._seen = None
+
+    @property
+    def eta(self):
+        return self.projection.eta
+
+    @eta.setter
+    def eta(self, value) -> None:
+        self.projection.set(eta=value)
+        self._seen = None
+
+    def grayness(self, density=None) -> float:
+        """M_nd = 4 sum v rho (1 - rho) / sum v of ``density`` (default: the last computed one)."""
+        if density is None:
+            if self._seen is None:
+                raise ValueError("ProjectedFilterOperation.grayness: nothing computed yet")
+            return self.projection.grayness(self._rho)
+        if isinstance(density, DeviceArray):
+            return self.projection.grayness(density.vec)
+        return self.projection.grayness(self._t.set(np.ascontiguousarray(E.host_wait(np.asarray(density, dtype=np.float64))).ravel()))
+
+    # -- helpers -----------------------------------------------------------------------------
+    def _upload(self, slot: str, value) -> Vec:
+        if isinstance(value, DeviceArray):
+            return value.vec
+        v = getattr(self, slot)
+        if v is None:
+            v = Vec(get_context(), self.nel)
+            setattr(self, slot, v)
+        return v.set(np.ascontiguousarray(E.host_wait(np.asarray(value, dtype=np.float64))).ravel())
+
+    def _forward(self, x) -> None:
+        """x-tilde and the projected density of ``x`` into the operation's own vectors; remembers the input."""
+        self.last = self.projection.filter_forward(self.filter, self._upload('_x', x), self._xt, self._rho)
+        self._seen = x.vec if isinstance(x, DeviceArray) else np.array(E.host_wait(np.asarray(x, dtype=np.float64)), copy=True).ravel()
+
+    def _ensure(self, x) -> None:
+        """Recompute x-tilde unless ``x`` is the input the last forward pass saw (a device vector: the same vector; a host
+        array: the same values)."""
+        if isinstance(x, DeviceArray):
+            same = self._seen is x.vec
+        else:
+            same = isinstance(self._seen, np.ndarray) and np.array_equal(self._seen, np.asarray(E.host_wait(np.asarray(x))).ravel())
+        if not same:
+            self._forward(x)
+
+    # -- protocol ----------------------------------------------------------------------------
+    def compute(self, inputs, outputs):
+        if self.sync_timers:
+            get_context().sync()
+        t0 = time.perf_counter()
+        x = inputs['density_unfiltered']
+        self._forward(x)
+        if isinstance(x, DeviceArray):
+            out = Vec(get_context(), self.nel)
+            out.copy_from(self._rho)
+            outputs['density'] = DeviceArray(out)
+        else:
+            outputs['density'] = self._rho.get()
+        if self.sync_timers:
+            get_context().sync()
+        self.time_ms['compute'] += (time.perf_counter() - t0) * 1e3
+        self.time_ms['calls'] += 1
+
+    def compute_jacvec_product(self, inputs, d_inputs, d_outputs, mode):
+        """fwd: d_outputs[density] += J_P W d_inputs[density_unfiltered];  rev: d_inputs[...] += W^T J_P^T d_outputs[density]."""
+        if mode not in ('fwd', 'rev'):
+            raise ValueError(f"unknown mode {mode!r}")
+        if not ('density_unfiltered' in d_inputs and 'density' in d_outputs):
+            return
+        if self.sync_timers:
+            get_context().sync()
+        t0 = time.perf_counter()
+        self._ensure(inputs['density_unfiltered'])
+        if mode == 'fwd':
+            self.filter.apply(self._upload('_a', d_inputs['density_unfiltered']), self._t)
+            self.projection.tangent(self._xt, self._t, self._y)
+            d_outputs['density'] = GeneralFilterOperation._add(d_outputs['density'], self._y)
+        else:
+            self.projection.reverse(self._xt, self._upload('_a', d_outputs['density']), self._t)
+            self.filter.apply(self._t, self._y, transpose=True)
+            d_inputs['density_unfiltered'] = GeneralFilterOperation._add(d_inputs['density_unfiltered'], self._y)
+        if self.sync_timers:
+            get_context().sync()
+        self.time_ms['jacvec'] += (time.perf_counter() - t0) * 1e3

@@ -71,6 +71,16 @@ struct femo_elast {
                                      // pointer: the caller may have destroyed it); uid 0 = wrapped memory, built at once
 };
 
+// the density filter (elasticity.hip builds and applies it; project.hip gathers with it)
+struct femo_filter {
+  femo_ctx* ctx = nullptr;
+  int64_t n = 0, nnz = 0;
+  int64_t* d_rowptr = nullptr;
+  int32_t* d_col = nullptr;
+  double* d_val = nullptr;      // W
+  double* d_valT = nullptr;     // W^T on the same (symmetric) pattern
+};
+
 constexpr int EB = 256;              // threads per block of the row kernels
 constexpr int PCG_GRID = 512;        // blocks of the PCG reductions (one partial each)
 

@@ -17,15 +17,6 @@
 #include <algorithm>
 #include <cmath>
 
-struct femo_filter {
-  femo_ctx* ctx = nullptr;
-  int64_t n = 0, nnz = 0;
-  int64_t* d_rowptr = nullptr;
-  int32_t* d_col = nullptr;
-  double* d_val = nullptr;      // W
-  double* d_valT = nullptr;     // W^T on the same (symmetric) pattern
-};
-
 namespace {
 
 // ----------------------------------------------------------------------------------------------- assembly ----

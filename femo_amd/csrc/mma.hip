@@ -15,7 +15,8 @@
 // eta positive) -> k_mma_trial (residual at the trial point; once more per halving) -> k_mma_trial<WRITE> (commit).
 // Bytes per Newton step: see DESIGN.md section 10, "Optimiser".
 //
-// Out of scope: GCMMA's inner conservative loop, equality constraints, passive or frozen cells, m > 8, partitioned meshes.
+// Out of scope: GCMMA's inner conservative loop, equality constraints, m > 8, partitioned meshes.  xmax = xmin is refused:
+// passive cells go through the projection (project.hip), which also carries the Heaviside step of the continuation.
 #include <chrono>
 #include <cmath>
 

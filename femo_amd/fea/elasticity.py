@@ -660,6 +660,129 @@ class DeviceFilter:
             pass
 
 
+def check_projection_params(n: int, beta, eta, volumes=None, solid=(), void=(), void_value: float = 1e-4):
+    """Validates the parameters of the projection without a device and returns them as
+    (beta, eta, mode, volumes or None, solid, void, void_value); ``eta`` is a float in [0, 1] or ``"volume"``."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"projection: n = {n}, need at least one cell")
+    beta = float(beta)
+    if not (np.isfinite(beta) and beta >= 0.0):
+        raise ValueError(f"projection: beta = {beta}, must be finite and >= 0")
+    if isinstance(eta, str):
+        if eta != "volume":
+            raise ValueError(f"projection: eta = {eta!r}, must be a number in [0, 1] or 'volume'")
+        mode, eta = _lib.PROJECT_VOLUME, 0.5
+    else:
+        mode, eta = _lib.PROJECT_FIXED, float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"projection: eta = {eta}, must lie in [0, 1]")
+    void_value = float(void_value)
+    if not 0.0 < void_value <= 1.0:
+        raise ValueError(f"projection: void_value = {void_value}, must lie in (0, 1]")
+    sets = []
+    for name, idx in (("solid", solid), ("void", void)):
+        raw = np.asarray(() if idx is None else idx).ravel()
+        if raw.size and not np.issubdtype(raw.dtype, np.integer):
+            raise ValueError(f"projection: {name} must hold integer cell indices")
+        a = np.ascontiguousarray(raw, dtype=np.int64)
+        if a.size and (a.min() < 0 or a.max() >= n):
+            raise ValueError(f"projection: a {name} cell lies outside 0..{n - 1}")
+        sets.append(a)
+    if np.intersect1d(sets[0], sets[1]).size:
+        raise ValueError("projection: a cell is both solid and void")
+    if volumes is not None:
+        volumes = np.ascontiguousarray(volumes, dtype=np.float64).ravel()
+        if volumes.size != n:
+            raise ValueError(f"projection: {volumes.size} volumes for n = {n}")
+        if not (np.all(np.isfinite(volumes)) and np.all(volumes > 0.0)):
+            raise ValueError("projection: the volumes must be positive and finite")
+    if mode == _lib.PROJECT_VOLUME and np.union1d(sets[0], sets[1]).size >= n:
+        raise ValueError("projection: the volume-preserving threshold needs an active cell")
+    return beta, eta, mode, volumes, sets[0], sets[1], void_value
+
+
+def _check_rc2(rc: int) -> None:
+    """The library's error path; an input it refused (rc 2) is a ValueError."""
+    if rc == 0:
+        return
+    msg = _lib.load().femo_last_error()
+    msg = msg.decode() if msg else f"libfemo_hip error {rc}"
+    if rc == 2:
+        raise ValueError(msg)
+    raise _lib.FemoError(msg)
+
+
+class DeviceProjection:
+    """femo_project (csrc/project.hip): rho = H(xt; beta, eta) on the active cells, 1 on ``solid``, ``void_value`` on ``void``;
+    ``eta`` a number in [0, 1] or ``"volume"`` (the volume-preserving threshold, 53 bisection steps on the device)."""
+
+    def __init__(self, ctx, n: int, beta: float = 0.0, eta=0.5, volumes=None, solid=(), void=(), void_value: float = 1e-4):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.n = int(n)
+        beta, eta_, mode, v, s, w, vv = check_projection_params(n, beta, eta, volumes, solid, void, void_value)
+        self._beta, self._eta = beta, ("volume" if mode == _lib.PROJECT_VOLUME else eta_)
+        self.n_passive = int(s.size + w.size)
+        h = _lib.H()
+        _check_rc2(self.lib.femo_project_create(ctx.handle, self.n, None if v is None else _ptr(v), s.size, _ptr(s) if s.size else None,
+                                                w.size, _ptr(w) if w.size else None, vv, beta, eta_, mode, C.byref(h)))
+        self.handle = h
+
+    @property
+    def beta(self) -> float:
+        return self._beta
+
+    @property
+    def eta(self):
+        return self._eta
+
+    def set(self, beta=None, eta=None) -> None:
+        beta = self._beta if beta is None else beta
+        eta = self._eta if eta is None else eta
+        volume = isinstance(eta, str)
+        if volume and eta != "volume":
+            raise ValueError(f"projection: eta = {eta!r}, must be a number in [0, 1] or 'volume'")
+        _check_rc2(self.lib.femo_project_set(self.handle, float(beta), 0.5 if volume else float(eta),
+                                             _lib.PROJECT_VOLUME if volume else _lib.PROJECT_FIXED))
+        self._beta, self._eta = float(beta), (eta if volume else float(eta))
+
+    @staticmethod
+    def _info(info: "_lib.ProjectInfo") -> dict:
+        return {k: getattr(info, k) for k, _ in _lib.ProjectInfo._fields_ if k != "reserved"}
+
+    def forward(self, xt: Vec, rho: Vec, info: bool = True) -> Optional[dict]:
+        rec = _lib.ProjectInfo()
+        _check_rc2(self.lib.femo_project_forward(self.handle, xt.handle, rho.handle, C.byref(rec) if info else None))
+        return self._info(rec) if info else None
+
+    def filter_forward(self, filt: "DeviceFilter", x: Vec, xt: Vec, rho: Vec, info: bool = True) -> Optional[dict]:
+        """xt = W x and rho = P(xt) (fixed threshold: one launch)."""
+        rec = _lib.ProjectInfo()
+        _check_rc2(self.lib.femo_filter_project(filt.handle, self.handle, x.handle, xt.handle, rho.handle, C.byref(rec) if info else None))
+        return self._info(rec) if info else None
+
+    def reverse(self, xt: Vec, a: Vec, out: Vec) -> Vec:
+        _check_rc2(self.lib.femo_project_reverse(self.handle, xt.handle, a.handle, out.handle))
+        return out
+
+    def tangent(self, xt: Vec, d: Vec, out: Vec) -> Vec:
+        _check_rc2(self.lib.femo_project_tangent(self.handle, xt.handle, d.handle, out.handle))
+        return out
+
+    def grayness(self, rho: Vec) -> float:
+        m = C.c_double(0.0)
+        _check_rc2(self.lib.femo_project_grayness(self.handle, rho.handle, C.byref(m)))
+        return float(m.value)
+
+    def __del__(self):
+        try:
+            h, self.handle = getattr(self, "handle", None), None
+            if h and getattr(self.ctx, "handle", None):
+                self.lib.femo_project_destroy(h)
+        except Exception:
+            pass
+
+
 # ----------------------------------------------------------------------------------------- boundary data / UFL ----
 class Constant:
     """dolfinx.fem.Constant(mesh, value) [ext]: a spatially constant scalar or vector (run_topo_opt_cantilever_beam.py:73)."""

@@ -5,8 +5,9 @@
     optimizer = MMA(prob, max_iter=100, move=0.5, tol=1e-3, sub_tol=1e-7, normalize=True)
     optimizer.solve(); optimizer.print_results()
 
-``MMA`` is the Method of Moving Asymptotes (include/femo_hip.h; csrc/mma.hip), ``DeviceMMA`` the bare handle."""
-from .mma import MMA, DeviceMMA
+``MMA`` is the Method of Moving Asymptotes (include/femo_hip.h; csrc/mma.hip), ``DeviceMMA`` the bare handle,
+``BetaContinuation`` the schedule on the Heaviside projection's sharpness (``MMA(..., continuation=...)``)."""
+from .mma import MMA, BetaContinuation, DeviceMMA
 from .problem import CSDLProblem
 
-__all__ = ["CSDLProblem", "MMA", "DeviceMMA"]
+__all__ = ["CSDLProblem", "MMA", "DeviceMMA", "BetaContinuation"]

@@ -1,8 +1,12 @@
 """Method of Moving Asymptotes on the device: ``DeviceMMA`` binds the handle of csrc/mma.hip (include/femo_hip.h states the
 formulation), ``MMA`` drives a ``CSDLProblem`` with it -- ``Simulator.run``, one ``compute_totals`` per output, one update.
 
-Out of scope: GCMMA's inner conservative loop, equality constraints, passive or frozen cells, several design-variable
-vectors, more than 8 rows, partitioned meshes, Heaviside projection and continuation schedules, an OC update."""
+``BetaContinuation`` is the continuation schedule on the sharpness of the Heaviside projection
+(csdl_opt/filter_model.py: ProjectedFilterOperation, csrc/project.hip), which is also where passive cells enter the loop: the
+projection fixes their density and zeroes their Jacobian rows, while ``CSDLProblem`` and the handle still refuse xmax = xmin.
+
+Out of scope: GCMMA's inner conservative loop, equality constraints, several design-variable vectors, more than 8 rows,
+partitioned meshes, continuation on the SIMP exponent or the filter radius, an OC update."""
 from __future__ import annotations
 
 import ctypes as C
@@ -104,6 +108,45 @@ class DeviceMMA:
             pass
 
 
+class BetaContinuation:
+    """Continuation on the projection's sharpness: stage s runs with ``op.beta = betas[s]`` and ends after ``every`` design
+    steps, or earlier when the driver's ``tol > 0`` and the step's max_dx_rel <= tol.  At a stage's end ``op.beta`` takes the
+    next value and the driver restarts the asymptote history (``handle.reset()``); the loop may stop on ``tol`` only in the
+    last stage.  ``op`` is anything with a settable ``beta`` (a ProjectedFilterOperation)."""
+
+    def __init__(self, op, betas, every: int):
+        self.op = op
+        self.betas = [float(b) for b in betas]
+        self.every = int(every)
+        if not self.betas or any(not (np.isfinite(b) and b >= 0.0) for b in self.betas):
+            raise ValueError(f"BetaContinuation: betas = {betas}, need at least one finite value >= 0")
+        if self.every < 1:
+            raise ValueError(f"BetaContinuation: every = {every}, must be at least 1")
+        self.stage, self.steps_in_stage = 0, 0
+
+    @property
+    def last_stage(self) -> bool:
+        return self.stage == len(self.betas) - 1
+
+    def start(self) -> None:
+        self.stage, self.steps_in_stage = 0, 0
+        self.op.beta = self.betas[0]
+
+    def after_step(self, max_dx_rel: float, tol: float) -> str:
+        """Called once per design step: ``'stop'`` (tol met in the last stage), ``'advance'`` (beta took its next value: the
+        caller resets the optimiser's history) or ``'go'``."""
+        self.steps_in_stage += 1
+        small = tol > 0.0 and max_dx_rel <= tol
+        if self.last_stage:
+            return 'stop' if small else 'go'
+        if small or self.steps_in_stage >= self.every:
+            self.stage += 1
+            self.steps_in_stage = 0
+            self.op.beta = self.betas[self.stage]
+            return 'advance'
+        return 'go'
+
+
 class MMA:
     """Minimise the problem's objective under its rows with the device-resident MMA update.
 
@@ -112,10 +155,14 @@ class MMA:
     a constraint cheaper than it should be.  Each step runs ``sim.run()``, one ``sim.compute_totals`` for the objective and
     one per constrained output, and one update; with ``Simulator(device=True)`` the design and the gradients stay in HBM
     (only function values and the sums of the subproblem's m x m system cross the link), in host mode they are uploaded.
-    Stops after ``max_iter`` steps or when max_j |x^{k+1} - x^k| / range_j <= tol.  ``results`` holds the history."""
+    Stops after ``max_iter`` steps or when max_j |x^{k+1} - x^k| / range_j <= tol.  ``results`` holds the history.
+    ``continuation`` (a BetaContinuation) runs its schedule inside the loop: ``results['beta']``, ``['eta']`` and
+    ``['grayness']`` then hold the projection's sharpness, threshold and M_nd of the design each step was taken from,
+    ``results['reset']`` the steps (from 1) that began with a fresh asymptote history."""
 
     def __init__(self, prob: CSDLProblem, max_iter: int = 100, move: float = 0.5, tol: float = 1e-3, sub_tol: float = 1e-7,
-                 normalize: bool = True, c: float = 1000.0, d: float = 1.0):
+                 normalize: bool = True, c: float = 1000.0, d: float = 1.0,
+                 continuation: Optional[BetaContinuation] = None):
         if not isinstance(prob, CSDLProblem):
             raise ValueError("MMA needs a CSDLProblem")
         _check_params(prob.m, move, sub_tol)
@@ -123,6 +170,9 @@ class MMA:
             raise ValueError(f"MMA: max_iter = {max_iter}")
         self.prob, self.max_iter, self.move, self.tol, self.sub_tol = prob, int(max_iter), float(move), float(tol), float(sub_tol)
         self.normalize, self.c, self.d = bool(normalize), c, d
+        if continuation is not None and not isinstance(continuation, BetaContinuation):
+            raise ValueError("MMA: continuation must be a BetaContinuation")
+        self.continuation = continuation
         self.results: Dict[str, List] = {}
         self.handle: Optional[DeviceMMA] = None
         self.callback = None          # called as callback(x, f0, df0, f, df) with the update's arguments just before it
@@ -154,8 +204,12 @@ class MMA:
         names = list(dict.fromkeys(r.name for r in prob.rows))
         res = self.results = dict(objective=[], constraints=[], max_dx=[], inner=[], halvings=[], stages=[], converged=[],
                                   update_ms=[], cycle_ms=[])
+        cont = self.continuation
+        if cont is not None:
+            res.update(beta=[], eta=[], grayness=[], reset=[1])
+            cont.start()
         scale0 = None
-        for _ in range(self.max_iter):
+        for step in range(1, self.max_iter + 1):
             t0 = time.perf_counter()
             sim.run()
             J = prob.objective_scaler * float(np.asarray(sim[prob.objective]).ravel()[0])
@@ -183,7 +237,17 @@ class MMA:
             res["inner"].append(info["newton_steps"]); res["halvings"].append(info["halvings"]); res["stages"].append(info["stages"])
             res["converged"].append(info["converged"])
             res["update_ms"].append((t2 - t1) * 1e3); res["cycle_ms"].append((tc - t0) * 1e3)
-            if info["max_dx_rel"] <= self.tol:
+            if cont is not None:
+                last = getattr(cont.op, "last", None) or {}
+                res["beta"].append(cont.betas[cont.stage]); res["eta"].append(last.get("eta", float("nan")))
+                res["grayness"].append(cont.op.grayness() if hasattr(cont.op, "grayness") else float("nan"))
+                what = cont.after_step(info["max_dx_rel"], self.tol)
+                if what == 'stop':
+                    break
+                if what == 'advance' and step < self.max_iter:
+                    self.handle.reset()
+                    res["reset"].append(step + 1)
+            elif info["max_dx_rel"] <= self.tol:
                 break
         self.x = x
         return res

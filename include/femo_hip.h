@@ -976,7 +976,8 @@ int femo_filter_export_csr(const femo_filter* f, int transpose, int64_t* rowptr,
  * recomputed in registers from the m values of delta lambda.  The m x m Newton system is folded from per-block partial sums
  * in a fixed order and solved on the host inside the call (small_solve.h); three blocking copies of at most 64 doubles per
  * Newton step.  No float atomics: the same inputs give the same bits.  One rank.  Out of scope: GCMMA's inner conservative
- * loop, equality constraints, passive cells (xmax = xmin), m > FEMO_MMA_MAX_M.                                            */
+ * loop, equality constraints, m > FEMO_MMA_MAX_M.  xmax = xmin is refused: passive cells enter through the projection
+ * below, which fixes their density and zeroes their Jacobian rows.                                                        */
 #define FEMO_MMA_MAX_M 8
 typedef struct femo_mma femo_mma;
 typedef struct femo_mma_params {
@@ -1011,6 +1012,59 @@ int femo_mma_update(femo_mma* h, femo_vec* x, double f0, const femo_vec* df0, co
 /* Forget the history: the next update is step 1 again.                                                                   */
 int femo_mma_reset(femo_mma* h);
 int femo_mma_destroy(femo_mma* h);
+
+/* ---- Heaviside projection of the filtered density (csrc/project.hip) ------------------------------------------------------
+ * The third field of the three-field formulation (Wang, Lazarov, Sigmund 2011): xt = W x (the filter above), and on the
+ * active cells
+ *   rho_i = H(xt_i) = (tanh(beta eta) + tanh(beta (xt_i - eta))) / D,   D = tanh(beta eta) + tanh(beta (1 - eta)),
+ *   H_x   = beta (1 - tanh^2(beta (xt - eta))) / D,
+ *   H_eta = (N_eta D - N D_eta) / D^2,  N = tanh(beta eta) + tanh(beta (xt - eta)),
+ *           N_eta = beta (tanh^2(beta (xt - eta)) - tanh^2(beta eta)),  D_eta = beta (tanh^2(beta (1 - eta)) - tanh^2(beta eta)).
+ * beta = 0 is the identity (rho = xt, a copy; H_x = 1, H_eta = 0).  Passive cells: rho_i = 1 on `solid`, rho_i = void_value on
+ * `void`; their Jacobian rows are zero in both products and they take no part in any sum below.
+ * FEMO_PROJECT_FIXED: eta as set.  FEMO_PROJECT_VOLUME (Xu, Cai, Cheng 2010): eta is the root of
+ *   g(eta) = sum_active v_i H(xt_i; beta, eta) - sum_active v_i xt_i,
+ * found by 53 bisection steps on [0, 1] (mid = (lo + hi) / 2; g(mid) > 0: lo = mid, else hi = mid; eta = (lo + hi) / 2), all on
+ * the device: per step one reduction launch (wave shuffle -> LDS -> one partial per block into the handle's own buffer) and one
+ * fold in the order of femo_fold_partials that also moves lo / hi in the handle's device record {lo, hi, eta, target, S_a, S_v,
+ * vol_out}; one blocking copy of that record at the end.  The Jacobian then has a rank-one term,
+ *   (J^T a)_j = a_j H_x,j + (S_a / S_v) v_j (1 - H_x,j),   (J d)_i = H_x,i d_i + H_eta,i sum_j v_j (1 - H_x,j) d_j / S_v,
+ *   S_a = sum_active a_i H_eta,i,  S_v = sum_active v_i H_eta,i,
+ * dropped when S_v == 0 exactly (every active cell saturated, or beta = 0; info->flat = 1).  No float atomics: the same inputs
+ * give the same bits.  fp64, one rank, the context's stream.                                                              */
+#define FEMO_PROJECT_FIXED 0
+#define FEMO_PROJECT_VOLUME 1
+typedef struct femo_project femo_project;
+typedef struct femo_project_info {
+  double eta;                    /* the threshold used (volume mode: the root)                                   */
+  double vol_in;                 /* sum_active v_i xt_i                                                          */
+  double vol_out;                /* sum_active v_i rho_i                                                         */
+  double s_v;                    /* S_v at eta (volume mode; 0 in fixed mode)                                    */
+  double ms;                     /* host time of the call, its one blocking copy included                        */
+  int32_t flat;                  /* volume mode: S_v == 0, the rank-one term is dropped                          */
+  int32_t mode;
+  int32_t launches;              /* kernels of the call                                                          */
+  int32_t reserved;
+} femo_project_info;
+/* v: n cell volumes on the host, copied (NULL: ones).  solid / void_: n_solid / n_void cell indices on the host.  Refused
+ * before any launch: beta < 0 or not finite, eta outside [0, 1], an unknown mode, an index outside 0..n-1, a cell in both
+ * sets, void_value outside (0, 1], an entry of v that is not positive and finite, volume mode without an active cell.      */
+int femo_project_create(femo_ctx* ctx, int64_t n, const double* v, int64_t n_solid, const int64_t* solid, int64_t n_void,
+                        const int64_t* void_, double void_value, double beta, double eta, int mode, femo_project** out);
+int femo_project_destroy(femo_project* p);
+int femo_project_set(femo_project* p, double beta, double eta, int mode);
+/* rho = P(xt).  info may be NULL in fixed mode (then nothing is copied back).  Refused: vectors shorter than n, xt
+ * overlapping rho.                                                                                                      */
+int femo_project_forward(femo_project* p, const femo_vec* xt, femo_vec* rho, femo_project_info* info);
+/* xt = W x and rho = P(xt).  Fixed mode: one gather launch (the row loop of femo_filter_apply, then H in registers).  Volume
+ * mode: the gather also leaves the partials of sum v xt; the bisection; one element-wise launch for rho.  Refused as above,
+ * and x overlapping xt or rho.                                                                                           */
+int femo_filter_project(femo_filter* f, femo_project* p, const femo_vec* x, femo_vec* xt, femo_vec* rho, femo_project_info* info);
+/* out = J^T a and out = J d at xt, with the threshold of the last forward call (volume mode).  out may be a / d itself.    */
+int femo_project_reverse(femo_project* p, const femo_vec* xt, const femo_vec* a, femo_vec* out);
+int femo_project_tangent(femo_project* p, const femo_vec* xt, const femo_vec* d, femo_vec* out);
+/* M_nd = 4 sum v rho (1 - rho) / sum v over all cells                                                                    */
+int femo_project_grayness(femo_project* p, const femo_vec* rho, double* mnd);
 
 #ifdef __cplusplus
 }

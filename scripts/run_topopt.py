@@ -6,13 +6,19 @@ loop with the device-resident MMA update in the place of modopt's SLSQP / SNOPT.
   ... --stress        a second constraint: the p-norm von Mises stress at most 0.9 times its value at the start design
   ... --host          Simulator(device=False): NumPy arrays at the operator boundary, uploaded for the update
   ... --host-update   also run the NumPy restatement's update (tests/mma_ref.py) on the same data, step by step
+  ... --betas 1,2,4,8 --every 5   Heaviside projection between filter and state (ProjectedFilterModel) with continuation on
+                      its sharpness: --every design steps per value (BetaContinuation); without --betas: today's model
+  ... --eta 0.5|volume            the projection's threshold: a number in [0, 1] or the volume-preserving one
+  ... --solid-frame W             a passive solid strip of W cells along the loaded edge (needs --betas; --betas 0 projects nothing else)
 
 Minimises the compliance under avg_density <= 0.40 from x = 0.4.  Prints one JSON line: per step the objective, the
 constraint values and the inner (Newton) iterations; the ms of the MMA update against the ms of the design cycle (the first
 step is the warm-up and left out of the statistics: median, minimum, maximum over the others); the bytes a Newton step moves
 by the count of DESIGN.md section 10 and the GB/s that gives; with --host-update the restatement's ms beside the device's,
 alternating with it step by step, and the largest difference between the two updates.  Writes the final filtered density
-to --out (XDMF)."""
+to --out (XDMF).  With --betas the line also holds beta, eta and the grayness M_nd per step, the ms the projection takes per
+step (its operation's own timers: compute, both products, synchronised) and its share of the cycle, and the ms of the 53-step
+bisection alone (a volume-mode forward call minus a fixed-mode one on the final design, median of 10)."""
 import argparse
 import json
 import os
@@ -28,7 +34,7 @@ sys.path.insert(0, ROOT)
 
 def build(args):
     from femo_amd.csdl_opt.fea_model import FEAModel
-    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel, ProjectedFilterModel
     from femo_amd.csdl_opt.simulator import Simulator
     from femo_amd.fea.elasticity import averageFunc, compliance, pdeRes
     from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, Measure, VectorFunctionSpace,
@@ -67,8 +73,22 @@ def build(args):
     fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), lambda x: np.isclose(x[0], 0.0, atol=1e-6))], V)
     model = FEAModel(fea=[fea])
     h = meshSize(mesh)
-    model.add(GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
-              name="general_filter_model")
+    betas = getattr(args, "betas", None)
+    if betas:
+        from femo_amd.fea.elasticity import cell_volumes
+        frame, solid = int(getattr(args, "solid_frame", 0) or 0), None
+        if frame > 0:
+            if args.n3:
+                raise SystemExit("--solid-frame is for the rectangle")
+            solid = np.nonzero(mesh.centroids()[:, 0] >= LX - frame * LX / args.nelx - 1e-9)[0]
+        eta = getattr(args, "eta", "0.5")
+        filt = ProjectedFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2,
+                                    projection_beta=betas[0], eta=eta if eta == "volume" else float(eta),
+                                    volumes=cell_volumes(mesh), solid=solid)
+        args.projection = filt
+    else:
+        filt = GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2)
+    model.add(filt, name="general_filter_model")
     model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.full(mesh.n_cell, 0.4))
     model.add_design_variable("density_unfiltered", upper=1.0, lower=1e-4)
     model.add_objective("compliance")
@@ -100,13 +120,19 @@ def main():
     mode.add_argument("--host", dest="device", action="store_false")
     ap.add_argument("--stress", action="store_true")
     ap.add_argument("--host-update", action="store_true")
+    ap.add_argument("--betas", type=lambda t: [float(b) for b in t.split(",")], default=None)
+    ap.add_argument("--every", type=int, default=5)
+    ap.add_argument("--eta", default="0.5")
+    ap.add_argument("--solid-frame", type=int, default=0)
     ap.add_argument("--out", default=os.path.join("topopt_out", "density.xdmf"))
     args = ap.parse_args()
+    if args.solid_frame and not args.betas:
+        raise SystemExit("--solid-frame needs --betas (passive cells go through the projection)")
     from femo_amd import _lib
     from femo_amd.engine import Context, Vec
     from femo_amd.fea import utils_hip
     from femo_amd.fea.io import XDMFRecorder
-    from femo_amd.opt import MMA, CSDLProblem
+    from femo_amd.opt import MMA, BetaContinuation, CSDLProblem
     if _lib.device_count() < 1:
         raise SystemExit("run_topopt needs a HIP device")
     ctx = Context(0)
@@ -121,8 +147,18 @@ def main():
         sim.run()
         model.add_constraint("stress", upper=0.9 * float(np.asarray(sim["stress"]).ravel()[0]))
     prob = CSDLProblem(problem_name="beam_topo_opt", simulator=sim)
-    optimizer = MMA(prob, max_iter=args.iters, move=0.5, tol=0.0, sub_tol=1e-7, normalize=True).setup()
+    op = args.projection.operation if args.betas else None
+    cont = BetaContinuation(op, args.betas, args.every) if args.betas else None
+    optimizer = MMA(prob, max_iter=args.iters, move=0.5, tol=0.0, sub_tol=1e-7, normalize=True, continuation=cont).setup()
     host = dict(ms=[], dx=[], newton=[])
+    proj_ms = []
+    if op is not None:
+        op.sync_timers = True
+
+        def on_projection(*_):                 # once per step, after run() and the totals: what the operation took since the last call
+            total = op.time_ms["compute"] + op.time_ms["jacvec"]
+            proj_ms.append(total - sum(proj_ms))
+        optimizer.callback = on_projection
     if args.host_update:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import mma_ref
@@ -138,6 +174,8 @@ def main():
             host["newton"].append(ref.last["rec"]["newton"])
             # the restatement keeps its own history; it is handed the device's iterate every step, so that both update the same data
             pending.append((x, xn))
+            if op is not None:
+                on_projection()
         optimizer.callback = on_update
     res = optimizer.solve()
     if args.host_update:
@@ -166,6 +204,21 @@ def main():
                newton_per_update=float(np.mean(inner)), newton_step_bytes=step_bytes,
                update_GBps=stats(list(gbps)), density_file=args.out,
                avg_density=float(np.asarray(sim["avg_density"]).ravel()[0]), final_compliance=float(np.asarray(sim["compliance"]).ravel()[0]))
+    if op is not None:
+        pm = stats(proj_ms)
+        compute_ms, products_ms = op.time_ms["compute"], op.time_ms["jacvec"]       # of the loop: taken before the calls below
+        xt, r1 = op._xt, Vec(ctx, n)
+        calls = {}
+        for eta in ("volume", 0.5):
+            op.projection.set(eta=eta)
+            op.projection.forward(xt, r1)
+            calls[eta] = float(np.median([op.projection.forward(xt, r1)["ms"] for _ in range(10)]))
+        op.eta = args.eta if args.eta == "volume" else float(args.eta)
+        steps = max(len(proj_ms), 1)
+        out.update(beta=res["beta"], eta=res["eta"], grayness=res["grayness"], reset=res["reset"], projection_ms=pm,
+                   projection_compute_ms_mean=compute_ms / max(op.time_ms["calls"], 1), projection_products_ms_mean=products_ms / steps,
+                   projection_share=pm["median"] / (upd["median"] + cyc["median"]), bisection_ms=calls["volume"] - calls[0.5],
+                   forward_volume_ms=calls["volume"], forward_fixed_ms=calls[0.5])
     if args.host_update:
         out.update(host_update_ms=stats(host["ms"]), host_newton=host["newton"], host_vs_device_last_dx=host["dx"])
     print(json.dumps(out))
