@@ -12,7 +12,9 @@
 //
 // The product k_elast_cdyn_spmv_multi is k_elast_dyn_spmv_multi with four accumulators per complex column and component
 // -- K x_re, M x_re, K x_im, M x_im -- from ONE read of the block, its column index, the fixed bytes and the mass scalar of
-// an entry.  Two complex columns per thread are the registers of the real kernel at four.  Each part is formed as the real
+// an entry.  Two complex columns per thread (ELAST_CHUNK / 2) are the registers of the real kernel at four.  It keeps a row
+// walk of its own, in the order of elast_row_walk (elast_internal.h) over the real columns 2 c + h: through the shared walk
+// its <2, false, 2> instantiation changes occupancy (DESIGN_LOG.md R24).  Each part is formed as the real
 // kernel forms it, (K x - sigma M x), and the damping term is subtracted (added) last: with cK = cM = 0 both parts have the
 // bits of femo_elast_dyn_apply_multi.  conj = 1 gives conj(Z), the transpose of the real 2L-column operator.
 //
@@ -56,8 +58,6 @@ struct CplxScalars { double v[CMC]; };
 enum { CS_RHO_R = 0, CS_RHO_I, CS_ALPHA_R, CS_ALPHA_I, CS_BETA_R, CS_BETA_I, CS_BETA1, CS_TOL, CS_RES };
 constexpr int CS_STRIDE = 16;
 static_assert(CS_STRIDE * CMC <= FEMO_ELAST_HARM_SCALARS * EMC, "the COCR scalars live in the MINRES scalars");
-
-__device__ __forceinline__ bool is_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
 
 // ------------------------------------------------------------------------------------------- complex product ----
 // y_l = a Z_l x_l + b f_l (conj(Z_l) with cj = -1) for the complex columns c0 = MC * blockIdx.y ... min(c0 + MC, n_cols)
@@ -374,24 +374,6 @@ __global__ __launch_bounds__(1024) void k_cocr_scalar(int mode, const double* __
   }
 }
 
-// ----------------------------------------------------------------------------------------------- launches ----
-template <int D, bool MASKED, int MC>
-void cdyn_launch(femo_elast* e, int nc, const CplxScalars& sig, const CplxScalars& ck, const CplxScalars& cm, double cj, double a,
-                 const double* x, double b, const double* f, double* y, double* part, int64_t ps, const int32_t* done) {
-  femo_mesh* m = e->mesh;
-  hipLaunchKernelGGL((k_elast_cdyn_spmv_multi<D, MASKED, MC>), dim3(grid_of(m->n_rows), (unsigned)((nc + MC - 1) / MC)), dim3(EB),
-                     0, m->ctx->stream, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_mvals, e->d_mdiag,
-                     e->d_fixed, nc, m->n_rows * D, sig, ck, cm, cj, a, x, b, f, y, part, ps, done);
-}
-
-// one complex column: the MC = 1 instantiation; otherwise two per thread
-template <int D, bool MASKED>
-void cdyn_chunk(femo_elast* e, int nc, const CplxScalars& sig, const CplxScalars& ck, const CplxScalars& cm, double cj, double a,
-                const double* x, double b, const double* f, double* y, double* part, int64_t ps, const int32_t* done) {
-  if (nc == 1) cdyn_launch<D, MASKED, 1>(e, nc, sig, ck, cm, cj, a, x, b, f, y, part, ps, done);
-  else cdyn_launch<D, MASKED, 2>(e, nc, sig, ck, cm, cj, a, x, b, f, y, part, ps, done);
-}
-
 struct Damping {
   CplxScalars sig, ck, cm;
   double cj;          // +1: Z, -1: conj(Z)
@@ -400,13 +382,17 @@ struct Damping {
 // y_l = a Z_l x_l + b f_l on raw pointers
 int cdyn_spmv(femo_elast* e, bool masked, int n_cols, const Damping& z, double a, const double* x, double b, const double* f,
               double* y, double* part, int64_t ps, const int32_t* done) {
-  if (e->d == 2) {
-    if (masked) cdyn_chunk<2, true>(e, n_cols, z.sig, z.ck, z.cm, z.cj, a, x, b, f, y, part, ps, done);
-    else cdyn_chunk<2, false>(e, n_cols, z.sig, z.ck, z.cm, z.cj, a, x, b, f, y, part, ps, done);
-  } else {
-    if (masked) cdyn_chunk<3, true>(e, n_cols, z.sig, z.ck, z.cm, z.cj, a, x, b, f, y, part, ps, done);
-    else cdyn_chunk<3, false>(e, n_cols, z.sig, z.ck, z.cm, z.cj, a, x, b, f, y, part, ps, done);
-  }
+  femo_mesh* m = e->mesh;
+  // one complex column: the MC = 1 instantiation; otherwise two per thread
+  const int mc = n_cols == 1 ? 1 : ELAST_CHUNK / 2;
+  elast_dispatch(e->d, masked, [&](auto dim, auto mask) {
+    constexpr int D = decltype(dim)::value;
+    constexpr bool MASKED = decltype(mask)::value;
+    auto* kernel = n_cols == 1 ? k_elast_cdyn_spmv_multi<D, MASKED, 1> : k_elast_cdyn_spmv_multi<D, MASKED, ELAST_CHUNK / 2>;
+    hipLaunchKernelGGL(kernel, dim3(grid_of(m->n_rows), (unsigned)((n_cols + mc - 1) / mc)), dim3(EB), 0, m->ctx->stream, m->n_rows,
+                       m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_mvals, e->d_mdiag, e->d_fixed, n_cols,
+                       m->n_rows * D, z.sig, z.ck, z.cm, z.cj, a, x, b, f, y, part, ps, done);
+  });
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -430,90 +416,59 @@ int cocr_solve(femo_elast* e, int n_cols, const Damping& zd, const femo_vec* b, 
   const int64_t n = m->n_vert * e->d;
   const int nr = 2 * n_cols;          // real columns
   const bool ml = opts->pc == FEMO_ELAST_PC_MULTILEVEL;
-  FEMO_REQUIRE(!ml || e->pc, "%s: pc = multilevel without femo_elast_pc_setup", who);
-  FEMO_TRY(femo_vec_await(b));
-  femo_vec_touch(x);
   hipStream_t st = m->ctx->stream;
   const bool masked = e->has_fixed;
-  if (ml) FEMO_TRY(femo_elast_pc_ensure(e));
-  FEMO_TRY(femo_elast_work_reserve(e, nr, who));
-  FEMO_TRY(femo_elast_harm_reserve(e, nr, who));
-  const int check = opts->check_every > 0 ? opts->check_every : (ml ? 8 : 32);
-  const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
   const int nps = (int)grid_of(m->n_rows);
-  const int64_t ps = e->w_pstride;
   const unsigned L = (unsigned)n_cols, gp = (unsigned)PCG_GRID;
-  // r, z, p, q in the PCG's work vectors; w = Z z and mq = M^-1 q in the first two of the MINRES loop's three
-  double *r = e->w_r, *z = e->w_z, *p = e->w_p, *q = e->w_q;
-  double *w = e->w_harm, *mq = e->w_harm + n * e->w_harm_cols;
-  double* cs = e->w_ms;
-  hipEvent_t e0 = m->ctx->ev0, e1 = m->ctx->ev1;
-  FEMO_HIP_CHECK(hipEventRecord(e0, st));
-  FEMO_TRY(femo_elast_start_x(e, nr, opts->zero_guess, b->d, x->d));
-  FEMO_TRY(cdyn_spmv(e, masked, n_cols, zd, -1.0, x->d, 1.0, b->d, r, nullptr, 0, nullptr));                     // r = b - Z x
+  // r, z, p, q are the PCG's work vectors w_r, w_z, w_p, w_q; w = Z z and mq = M^-1 q are the first two of the MINRES loop's
+  // three in w_harm, the scalars those of the MINRES (w_ms).  The loop reserves them before start(), so every launch reads
+  // them from the handle when it runs
+  auto mq = [&]() { return e->w_harm + n * e->w_harm_cols; };
 #define FEMO_COCR_DIR(D, S, J, SRC, OUT) hipLaunchKernelGGL((k_cocr_dir<D, S, J>), dim3(gp, L), dim3(EB), 0, st, m->n_rows, e->d_dinv, \
-                                                            SRC, w, p, q, OUT, cs, e->w_part, ps, e->w_flag)
+                                                            SRC, e->w_harm, e->w_p, e->w_q, OUT, e->w_ms, e->w_part, e->w_pstride, e->w_flag)
   // start: z = M^-1 r and the partials of Re(r^H z).  step: p, q, mq = M^-1 q and the partials of q^T mq
   auto precond = [&](bool step) -> int {
     if (ml) {
-      if (step) { if (e->d == 2) FEMO_COCR_DIR(2, true, false, z, mq); else FEMO_COCR_DIR(3, true, false, z, mq); }
-      FEMO_TRY(femo_elast_pc_step(e, false, nr, nullptr, step ? q : r, nullptr, nullptr, step ? mq : z, nullptr, e->w_s, e->w_part,
-                                  ps, e->w_flag, e->d_dinv));
-      if (step) hipLaunchKernelGGL(k_cocr_dot<false>, dim3(gp, L), dim3(EB), 0, st, n, q, mq, e->w_part, ps, e->w_flag);
-      else hipLaunchKernelGGL(k_cocr_dot<true>, dim3(gp, L), dim3(EB), 0, st, n, r, z, e->w_part, ps, e->w_flag);
+      if (step) { if (e->d == 2) FEMO_COCR_DIR(2, true, false, e->w_z, mq()); else FEMO_COCR_DIR(3, true, false, e->w_z, mq()); }
+      FEMO_TRY(femo_elast_pc_step(e, false, nr, nullptr, step ? e->w_q : e->w_r, nullptr, nullptr, step ? mq() : e->w_z, nullptr,
+                                  e->w_s, e->w_part, e->w_pstride, e->w_flag, e->d_dinv));
+      if (step) hipLaunchKernelGGL(k_cocr_dot<false>, dim3(gp, L), dim3(EB), 0, st, n, e->w_q, mq(), e->w_part, e->w_pstride,
+                                   e->w_flag);
+      else hipLaunchKernelGGL(k_cocr_dot<true>, dim3(gp, L), dim3(EB), 0, st, n, e->w_r, e->w_z, e->w_part, e->w_pstride,
+                              e->w_flag);
       return 0;
     }
-    if (e->d == 2) { if (step) FEMO_COCR_DIR(2, true, true, z, mq); else FEMO_COCR_DIR(2, false, true, r, z); }
-    else { if (step) FEMO_COCR_DIR(3, true, true, z, mq); else FEMO_COCR_DIR(3, false, true, r, z); }
+    if (e->d == 2) { if (step) FEMO_COCR_DIR(2, true, true, e->w_z, mq()); else FEMO_COCR_DIR(2, false, true, e->w_r, e->w_z); }
+    else { if (step) FEMO_COCR_DIR(3, true, true, e->w_z, mq()); else FEMO_COCR_DIR(3, false, true, e->w_r, e->w_z); }
     return 0;
   };
-#define FEMO_COCR_SCALAR(MODE, NP) hipLaunchKernelGGL(k_cocr_scalar, dim3(L), dim3(1024), 0, st, MODE, e->w_part, ps, NP, opts->rtol, \
-                                                      opts->atol, max_it, cs, e->w_flag)
-  // the flags of the last solve may freeze a column before mode 0 has run: clear them first
-  FEMO_HIP_CHECK(hipMemsetAsync(e->w_flag, 0, (size_t)nr * EMF_STRIDE * sizeof(int32_t), st));
-  FEMO_TRY(precond(false));
-  FEMO_COCR_SCALAR(0, PCG_GRID);
-  FEMO_HIP_CHECK(hipGetLastError());
-  int it_issued = 0;
-  for (;;) {
-    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_flag, e->w_flag, (size_t)nr * EMF_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    FEMO_HIP_CHECK(hipStreamSynchronize(st));
-    bool all_done = true;
-    for (int l = 0; l < n_cols; ++l) all_done = all_done && e->h_flag[2 * l * EMF_STRIDE] != 0;
-    if (all_done || it_issued >= max_it) break;
-    for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) {
-      FEMO_TRY(cdyn_spmv(e, masked, n_cols, zd, 1.0, z, 0.0, nullptr, w, e->w_part, ps, e->w_flag));              // w = Z z, z^T w
-      FEMO_COCR_SCALAR(1, nps);
-      FEMO_TRY(precond(true));
-      FEMO_COCR_SCALAR(2, PCG_GRID);
-      hipLaunchKernelGGL(k_cocr_update, dim3(gp, L), dim3(EB), 0, st, n, x->d, r, z, p, q, mq, cs, e->w_part, ps, e->w_flag);
-      FEMO_COCR_SCALAR(3, PCG_GRID);
-    }
-    FEMO_HIP_CHECK(hipGetLastError());
-  }
 #undef FEMO_COCR_DIR
+#define FEMO_COCR_SCALAR(MODE, NP) hipLaunchKernelGGL(k_cocr_scalar, dim3(L), dim3(1024), 0, st, MODE, e->w_part, e->w_pstride, NP, \
+                                                      opts->rtol, opts->atol, max_it, e->w_ms, e->w_flag)
+  femo_elast_krylov loop = {who, nr, n_cols, 2, true};
+  loop.start = [&](int max_it) -> int {
+    FEMO_TRY(femo_elast_start_x(e, nr, opts->zero_guess, b->d, x->d));
+    FEMO_TRY(cdyn_spmv(e, masked, n_cols, zd, -1.0, x->d, 1.0, b->d, e->w_r, nullptr, 0, nullptr));              // r = b - Z x
+    // the flags of the last solve may freeze a column before mode 0 has run: clear them first
+    FEMO_HIP_CHECK(hipMemsetAsync(e->w_flag, 0, (size_t)nr * EMF_STRIDE * sizeof(int32_t), st));
+    FEMO_TRY(precond(false));
+    FEMO_COCR_SCALAR(0, PCG_GRID);
+    return 0;
+  };
+  loop.iterate = [&](int, int max_it) -> int {
+    FEMO_TRY(cdyn_spmv(e, masked, n_cols, zd, 1.0, e->w_z, 0.0, nullptr, e->w_harm, e->w_part, e->w_pstride, e->w_flag));   // w = Z z, z^T w
+    FEMO_COCR_SCALAR(1, nps);
+    FEMO_TRY(precond(true));
+    FEMO_COCR_SCALAR(2, PCG_GRID);
+    hipLaunchKernelGGL(k_cocr_update, dim3(gp, L), dim3(EB), 0, st, n, x->d, e->w_r, e->w_z, e->w_p, e->w_q, mq(), e->w_ms,
+                       e->w_part, e->w_pstride, e->w_flag);
+    FEMO_COCR_SCALAR(3, PCG_GRID);
+    return 0;
+  };
 #undef FEMO_COCR_SCALAR
-  FEMO_HIP_CHECK(hipEventRecord(e1, st));
-  FEMO_HIP_CHECK(hipMemcpyAsync(e->h_ms, cs, (size_t)n_cols * CS_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
-  FEMO_HIP_CHECK(hipStreamSynchronize(st));
-  if (info) {
-    float ms = 0.0f;
-    const bool timed = hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-    for (int l = 0; l < n_cols; ++l) {
-      const int32_t* fl = e->h_flag + 2 * l * EMF_STRIDE;
-      const double* s = e->h_ms + l * CS_STRIDE;
-      femo_solve_info* o = info + l;
-      std::memset(o, 0, sizeof(*o));
-      o->iterations = fl[1];
-      o->converged = fl[2] ? -1 : (fl[3] ? 1 : 0);
-      o->residual_norm = s[CS_RES];
-      o->rhs_norm = s[CS_BETA1];
-      o->pc_residual_norm = o->residual_norm;
-      o->pc_rhs_norm = o->rhs_norm;
-      if (timed) o->solve_ms = ms;
-    }
-  }
-  return 0;
+  loop.d_scal = &femo_elast::w_ms; loop.h_scal = &femo_elast::h_ms; loop.scal_stride = CS_STRIDE;
+  loop.s_res = CS_RES; loop.s_rhs = CS_BETA1; loop.squared = false;
+  return femo_elast_krylov_loop(e, b, x, opts, info, loop);
 }
 
 }  // namespace

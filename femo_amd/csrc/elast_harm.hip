@@ -14,7 +14,9 @@
 //
 // The product k_elast_dyn_spmv_multi is k_elast_spmv_multi with a second accumulator per column and component for M x: the
 // block, its column index, the fixed bytes AND the mass scalar of an entry are read once for the columns of a chunk, and
-// y_l = a (K x_l - sigma_l M x_l) + b f_l.  With sigma_l = 0 it gives the bits of k_elast_spmv_multi.
+// y_l = a (K x_l - sigma_l M x_l) + b f_l.  With sigma_l = 0 it gives the bits of k_elast_spmv_multi.  It keeps a row walk of
+// its own, in the order of elast_row_walk (elast_internal.h) with MASS: through the shared walk the MINRES iteration at four
+// columns measured 1 to 2 % slower (70.2 to 71.2 against 69.8 us, DESIGN_LOG.md R24).
 //
 // The solve is Paige & Saunders' MINRES with the SPD preconditioners of the static solve (block-Jacobi or multilevel, both
 // built from the masked, UNSHIFTED K): above the first resonance K - sigma M is indefinite, where PCG breaks down.  One
@@ -49,21 +51,10 @@ namespace {
 
 constexpr int EMC = FEMO_ELAST_MAX_COLS;
 
-// one value per column: the shifts of the product, the scales of dR/drho
-struct ColScalars { double v[EMC]; };
-
-// columns per thread of the shifted product
-template <int D>
-struct DynChunk { static constexpr int value = 4; };
-
 // MINRES device scalars of a column
 enum { MS_BETA1 = 0, MS_BETA, MS_OLDB, MS_ALFA, MS_DBAR, MS_EPSLN, MS_OLDEPS, MS_DELTA, MS_GAMMA, MS_CS, MS_SN, MS_PHI,
        MS_PHIBAR, MS_TOL };
 constexpr int MS_STRIDE = FEMO_ELAST_HARM_SCALARS;
-
-// neither NaN nor infinite.  (x - x == 0 would do as well, were it not that with x = a * b the compiler contracts x - x into
-// fma(a, b, -x), the rounding error of the product.)
-__device__ __forceinline__ bool is_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
 
 // ---------------------------------------------------------------------------------------------- mass assembly ----
 // One thread per vertex row, the visit walk of k_elast_assemble.  A visit of cell c as its vertex a adds
@@ -439,33 +430,20 @@ __global__ __launch_bounds__(EB) void k_elast_mass_drho_N(
 }
 
 // ----------------------------------------------------------------------------------------------- launches ----
-template <int D, bool MASKED, int MC>
-void dyn_launch(femo_elast* e, int nc, const ColScalars& sig, double a, const double* x, double b, const double* f, double* y,
-                double* part, int64_t ps, const int32_t* done) {
-  femo_mesh* m = e->mesh;
-  hipLaunchKernelGGL((k_elast_dyn_spmv_multi<D, MASKED, MC>), dim3(grid_of(m->n_rows), (unsigned)((nc + MC - 1) / MC)), dim3(EB),
-                     0, m->ctx->stream, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_mvals, e->d_mdiag,
-                     e->d_fixed, nc, m->n_rows * D, sig, a, x, b, f, y, part, ps, done);
-}
-
-// one column: the MC = 1 instantiation, which carries no accumulators of absent columns
-template <int D, bool MASKED>
-void dyn_chunk(femo_elast* e, int nc, const ColScalars& sig, double a, const double* x, double b, const double* f, double* y,
-               double* part, int64_t ps, const int32_t* done) {
-  if (nc == 1) dyn_launch<D, MASKED, 1>(e, nc, sig, a, x, b, f, y, part, ps, done);
-  else dyn_launch<D, MASKED, DynChunk<D>::value>(e, nc, sig, a, x, b, f, y, part, ps, done);
-}
-
 // y_l = a (Op - sig_l M) x_l + b f_l on raw pointers, as femo_elast_spmv
 int dyn_spmv(femo_elast* e, bool masked, int n_cols, const ColScalars& sig, double a, const double* x, double b, const double* f,
              double* y, double* part, int64_t ps, const int32_t* done) {
-  if (e->d == 2) {
-    if (masked) dyn_chunk<2, true>(e, n_cols, sig, a, x, b, f, y, part, ps, done);
-    else dyn_chunk<2, false>(e, n_cols, sig, a, x, b, f, y, part, ps, done);
-  } else {
-    if (masked) dyn_chunk<3, true>(e, n_cols, sig, a, x, b, f, y, part, ps, done);
-    else dyn_chunk<3, false>(e, n_cols, sig, a, x, b, f, y, part, ps, done);
-  }
+  femo_mesh* m = e->mesh;
+  // one column: the MC = 1 instantiation, which carries no accumulators of absent columns
+  const int mc = n_cols == 1 ? 1 : ELAST_CHUNK;
+  elast_dispatch(e->d, masked, [&](auto dim, auto mask) {
+    constexpr int D = decltype(dim)::value;
+    constexpr bool MASKED = decltype(mask)::value;
+    auto* kernel = n_cols == 1 ? k_elast_dyn_spmv_multi<D, MASKED, 1> : k_elast_dyn_spmv_multi<D, MASKED, ELAST_CHUNK>;
+    hipLaunchKernelGGL(kernel, dim3(grid_of(m->n_rows), (unsigned)((n_cols + mc - 1) / mc)), dim3(EB), 0, m->ctx->stream, m->n_rows,
+                       m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_mvals, e->d_mdiag, e->d_fixed, n_cols,
+                       m->n_rows * D, sig, a, x, b, f, y, part, ps, done);
+  });
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -484,84 +462,51 @@ int minres_solve(femo_elast* e, int n_cols, const ColScalars& sig, const femo_ve
   femo_mesh* m = e->mesh;
   const int64_t n = m->n_vert * e->d;
   const bool ml = opts->pc == FEMO_ELAST_PC_MULTILEVEL;
-  FEMO_REQUIRE(!ml || e->pc, "%s: pc = multilevel without femo_elast_pc_setup", who);
-  FEMO_TRY(femo_vec_await(b));
-  femo_vec_touch(x);
   hipStream_t st = m->ctx->stream;
-  const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
-  if (ml) FEMO_TRY(femo_elast_pc_ensure(e));
-  FEMO_TRY(femo_elast_work_reserve(e, n_cols, who));
-  FEMO_TRY(femo_elast_harm_reserve(e, n_cols, who));
-  const int check = opts->check_every > 0 ? opts->check_every : (ml ? 8 : 32);
-  const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
+  const bool masked = e->has_fixed;
   const int nps = (int)grid_of(m->n_rows);
-  const int64_t ps = e->w_pstride;
   const unsigned L = (unsigned)n_cols, gp = (unsigned)PCG_GRID;
-  // r2, z, v, q in the PCG's work vectors; r1, w1, w2 behind one another in w_harm
-  double *r2 = e->w_r, *z = e->w_z, *v = e->w_p, *q = e->w_q;
-  double *r1 = e->w_harm, *w1 = e->w_harm + n * n_cols, *w2 = e->w_harm + 2 * n * n_cols;
-  hipEvent_t e0 = m->ctx->ev0, e1 = m->ctx->ev1;
-  FEMO_HIP_CHECK(hipEventRecord(e0, st));
-  FEMO_TRY(femo_elast_start_x(e, n_cols, opts->zero_guess, b->d, x->d));
-  FEMO_TRY(dyn_spmv(e, fx != nullptr, n_cols, sig, -1.0, x->d, 1.0, b->d, r2, nullptr, 0, nullptr));           // r2 = b - S x
+  // r2, z, v, q are the PCG's work vectors w_r, w_z, w_p, w_q; r1, w1, w2 lie behind one another in w_harm.  The loop
+  // reserves them before start(), so every launch reads them from the handle when it runs
+  auto harm = [&](int k) { return e->w_harm + k * n * n_cols; };
 #define FEMO_LANCZOS(D, S, J) hipLaunchKernelGGL((k_minres_lanczos<D, S, J>), dim3(gp, L), dim3(EB), 0, st, m->n_rows, e->d_dinv, \
-                                                 r1, r2, q, z, e->w_ms, e->w_part, ps, e->w_flag)
+                                                 harm(0), e->w_r, e->w_q, e->w_z, e->w_ms, e->w_part, e->w_pstride, e->w_flag)
   // z = M^-1 r2 and the partials of r2.z: update = false reads neither s nor (for a frozen column) anything it may not
   auto precond = [&](bool step) -> int {
     if (ml) {
       if (step) { if (e->d == 2) FEMO_LANCZOS(2, true, false); else FEMO_LANCZOS(3, true, false); }
-      return femo_elast_pc_step(e, false, n_cols, nullptr, r2, nullptr, nullptr, z, nullptr, e->w_s, e->w_part, ps, e->w_flag,
+      return femo_elast_pc_step(e, false, n_cols, nullptr, e->w_r, nullptr, nullptr, e->w_z, nullptr, e->w_s, e->w_part, e->w_pstride,
+                                e->w_flag,
                                 e->d_dinv);
     }
     if (e->d == 2) { if (step) FEMO_LANCZOS(2, true, true); else FEMO_LANCZOS(2, false, true); }
     else { if (step) FEMO_LANCZOS(3, true, true); else FEMO_LANCZOS(3, false, true); }
     return 0;
   };
-  FEMO_TRY(precond(false));
-  hipLaunchKernelGGL(k_minres_scalar, dim3(L), dim3(1024), 0, st, 0, e->w_part, ps, PCG_GRID, opts->rtol, opts->atol, max_it, e->w_ms,
-                     e->w_flag);
-  hipLaunchKernelGGL(k_minres_x<false>, dim3(gp, L), dim3(EB), 0, st, n, 0, x->d, v, z, w1, w2, e->w_ms, e->w_flag);
-  FEMO_HIP_CHECK(hipGetLastError());
-  int it_issued = 0;
-  for (;;) {
-    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_flag, e->w_flag, (size_t)n_cols * EMF_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    FEMO_HIP_CHECK(hipStreamSynchronize(st));
-    bool all_done = true;
-    for (int l = 0; l < n_cols; ++l) all_done = all_done && e->h_flag[l * EMF_STRIDE] != 0;
-    if (all_done || it_issued >= max_it) break;
-    for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) {
-      FEMO_TRY(dyn_spmv(e, fx != nullptr, n_cols, sig, 1.0, v, 0.0, nullptr, q, e->w_part, ps, e->w_flag));     // q = S v, v.q
-      hipLaunchKernelGGL(k_minres_scalar, dim3(L), dim3(1024), 0, st, 1, e->w_part, ps, nps, opts->rtol, opts->atol, max_it, e->w_ms,
-                         e->w_flag);
-      FEMO_TRY(precond(true));
-      hipLaunchKernelGGL(k_minres_scalar, dim3(L), dim3(1024), 0, st, 2, e->w_part, ps, PCG_GRID, opts->rtol, opts->atol, max_it,
-                         e->w_ms, e->w_flag);
-      hipLaunchKernelGGL(k_minres_x<true>, dim3(gp, L), dim3(EB), 0, st, n, it_issued + 1, x->d, v, z, w1, w2, e->w_ms, e->w_flag);
-    }
-    FEMO_HIP_CHECK(hipGetLastError());
-  }
 #undef FEMO_LANCZOS
-  FEMO_HIP_CHECK(hipEventRecord(e1, st));
-  FEMO_HIP_CHECK(hipMemcpyAsync(e->h_ms, e->w_ms, (size_t)n_cols * MS_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
-  FEMO_HIP_CHECK(hipStreamSynchronize(st));
-  if (info) {
-    float ms = 0.0f;
-    const bool timed = hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-    for (int l = 0; l < n_cols; ++l) {
-      const int32_t* fl = e->h_flag + l * EMF_STRIDE;
-      const double* s = e->h_ms + l * MS_STRIDE;
-      femo_solve_info* o = info + l;
-      std::memset(o, 0, sizeof(*o));
-      o->iterations = fl[1];
-      o->converged = fl[2] ? -1 : (fl[3] ? 1 : 0);
-      o->residual_norm = s[MS_PHIBAR];
-      o->rhs_norm = s[MS_BETA1];
-      o->pc_residual_norm = o->residual_norm;
-      o->pc_rhs_norm = o->rhs_norm;
-      if (timed) o->solve_ms = ms;
-    }
-  }
-  return 0;
+#define FEMO_MINRES_SCALAR(MODE, NP) hipLaunchKernelGGL(k_minres_scalar, dim3(L), dim3(1024), 0, st, MODE, e->w_part, e->w_pstride, NP, \
+                                                        opts->rtol, opts->atol, max_it, e->w_ms, e->w_flag)
+  femo_elast_krylov loop = {who, n_cols, n_cols, 1, true};
+  loop.start = [&](int max_it) -> int {
+    FEMO_TRY(femo_elast_start_x(e, n_cols, opts->zero_guess, b->d, x->d));
+    FEMO_TRY(dyn_spmv(e, masked, n_cols, sig, -1.0, x->d, 1.0, b->d, e->w_r, nullptr, 0, nullptr));             // r2 = b - S x
+    FEMO_TRY(precond(false));
+    FEMO_MINRES_SCALAR(0, PCG_GRID);
+    hipLaunchKernelGGL(k_minres_x<false>, dim3(gp, L), dim3(EB), 0, st, n, 0, x->d, e->w_p, e->w_z, harm(1), harm(2), e->w_ms, e->w_flag);
+    return 0;
+  };
+  loop.iterate = [&](int it, int max_it) -> int {
+    FEMO_TRY(dyn_spmv(e, masked, n_cols, sig, 1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, e->w_pstride, e->w_flag));   // q = S v, v.q
+    FEMO_MINRES_SCALAR(1, nps);
+    FEMO_TRY(precond(true));
+    FEMO_MINRES_SCALAR(2, PCG_GRID);
+    hipLaunchKernelGGL(k_minres_x<true>, dim3(gp, L), dim3(EB), 0, st, n, it + 1, x->d, e->w_p, e->w_z, harm(1), harm(2), e->w_ms, e->w_flag);
+    return 0;
+  };
+#undef FEMO_MINRES_SCALAR
+  loop.d_scal = &femo_elast::w_ms; loop.h_scal = &femo_elast::h_ms; loop.scal_stride = MS_STRIDE;
+  loop.s_res = MS_PHIBAR; loop.s_rhs = MS_BETA1; loop.squared = false;
+  return femo_elast_krylov_loop(e, b, x, opts, info, loop);
 }
 
 }  // namespace

@@ -1,14 +1,17 @@
-// Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product and PCG), elast_pc.hip
-// (multilevel preconditioner), elast_stress.hip (stress aggregate), each for one or several load cases, elast_block.hip
-// (block linear algebra and the block iteration of the eigen solves), elast_eig.hip (mass product and the eigenfrequency
-// pencil), elast_buckle.hip (geometric stiffness and the buckling pencil), elast_harm.hip (assembled mass, shifted
-// product and MINRES of the harmonic response), elast_damp.hip (complex product and COCR of the damped response) and
-// elast_transient.hip (Newmark march, its banded product and dR/drho).  Not part of the ABI.
+// Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product, PCG and the poll loop
+// of every batched Krylov solve), elast_pc.hip (multilevel preconditioner), elast_stress.hip (stress aggregate), each for
+// one or several load cases, elast_block.hip (block linear algebra and the block iteration of the eigen solves),
+// elast_eig.hip (mass product and the eigenfrequency pencil), elast_buckle.hip (geometric stiffness and the buckling
+// pencil), elast_harm.hip (assembled mass, shifted product and MINRES of the harmonic response), elast_damp.hip (complex
+// product and COCR of the damped response) and elast_transient.hip (Newmark march, its banded product and dR/drho).  The
+// static and the banded SELL product of these units are prologues and epilogues around one row walk, elast_row_walk below;
+// all four products choose their instantiation through elast_dispatch.  Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
 
 #include <functional>
+#include <type_traits>
 
 struct femo_elast_pc;   // lattice hierarchy of the multilevel preconditioner (elast_pc.hip)
 
@@ -89,6 +92,27 @@ enum { S_RZ = 0, S_ALPHA = 1, S_BETA = 2, S_TOL2 = 3, S_RZ0 = 4 };
 // Column l keeps its own s[] at s + l * EMS_STRIDE and its own flag[] at flag + l * EMF_STRIDE.
 constexpr int EMS_STRIDE = 8, EMF_STRIDE = 4;
 
+// columns per thread of the batched products (complex columns: half as many); one column runs the instantiation for 1
+constexpr int ELAST_CHUNK = 4;
+
+// One value per column, by value into a kernel: shifts, scales, weights.  In an unnamed namespace like the kernels that take
+// it, whose symbols carry its name.
+namespace {
+struct ColScalars { double v[FEMO_ELAST_MAX_COLS]; };
+}  // namespace
+
+// fn(std::integral_constant<int, D>, std::bool_constant<MASKED>) for d = 2 or 3: the run-time pair as template arguments
+template <typename F>
+inline void elast_dispatch(int d, bool masked, F&& fn) {
+  if (d == 2) {
+    if (masked) fn(std::integral_constant<int, 2>(), std::true_type());
+    else fn(std::integral_constant<int, 2>(), std::false_type());
+  } else {
+    if (masked) fn(std::integral_constant<int, 3>(), std::true_type());
+    else fn(std::integral_constant<int, 3>(), std::false_type());
+  }
+}
+
 // blocks of EB threads for n items
 inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
   int64_t g = (n + EB - 1) / EB;
@@ -139,6 +163,28 @@ struct femo_elast_op {
 // march): info: n_cols records, or null.  op == null: K.
 int femo_elast_pcg(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
                    const char* who, const femo_elast_op* op = nullptr);
+// What a batched Krylov solve (PCG, MINRES, COCR) hands to femo_elast_krylov_loop.  Its launches read the work vectors from
+// the handle when they run: the loop reserves them before start().
+struct femo_elast_krylov {
+  const char* who;          // the entry point, for the error texts
+  int real_cols;            // columns of work to reserve; the flags of as many columns are copied at every poll
+  int n_cols;               // solver columns: column l reads the flags of real column l * flag_stride
+  int flag_stride;          // 1, or 2 where a complex column owns a pair of real ones
+  bool harm;                // reserves the harmonic work (w_harm, w_ms) as well
+  std::function<int(int max_it)> start;              // everything up to and including the scalar kernel of iteration 0
+  std::function<int(int it, int max_it)> iterate;    // the launches of iteration `it` (from 0)
+  double* femo_elast::*d_scal;                       // the scalars of the columns on the device ...
+  double* femo_elast::*h_scal;                       // ... their pinned mirror ...
+  int scal_stride;                                   // ... and the stride between two columns
+  int s_res, s_rhs;         // residual_norm and rhs_norm among a column's scalars ...
+  bool squared;             // ... or their squares (possibly rounded below zero)
+};
+// The host side every batched Krylov solve shares: the multilevel refusal, await b / touch x, the preconditioner and work on
+// demand, the defaults of check_every (multilevel 8, else 32) and max_it (100000), start(), then bursts of check_every
+// iterations -- never beyond max_it -- between polls of the flags, until every column is done; the scalars' read-back and
+// one femo_solve_info per column (info may be null).
+int femo_elast_krylov_loop(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
+                           const femo_elast_krylov& loop);
 
 // elast_harm.hip ----------------------------------------------------------------------------------------------------
 // scalars per column in w_ms / h_ms, always for FEMO_ELAST_MAX_COLS columns
@@ -194,6 +240,102 @@ int block_iteration(femo_elast* e, const Pencil& pencil, int n_modes, int block,
 }  // namespace elast_block
 
 #if defined(__HIPCC__)
+// neither NaN nor infinite.  (x - x == 0 would do as well, were it not that with x = a * b the compiler contracts x - x into
+// fma(a, b, -x), the rounding error of the product.)
+__device__ __forceinline__ bool is_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// One SELL row of K x_i, and with MASS of M x_i (one scalar per entry in the slots of K, times I_d), for NV vectors: the walk
+// under the static and the banded product (the shifted and the complex product keep copies of it, DESIGN_LOG.md R24).  The
+// kernels differ before it (which columns the x_i are, which are on) and after it (how the sums combine, the right-hand
+// side, the dot partials).  Both structs travel by value: behind a reference the arrays would be reached through generic
+// pointers, and the kernels would not compile to what they were.
+template <int NV>
+struct ElastRowIn {
+  const double* x[NV];      // column i; read only where on[i]
+  bool on[NV];              // uniform over the block
+};
+template <int D, int NV, bool MASS>
+struct ElastRow {
+  uint8_t fo[D];            // the row's fixed bytes (0 without MASKED)
+  double xo[NV][D];         // the row's own entries of x_i as stored, 0 where off
+  double acc[NV][D];        // (K x_i)[row]; MASKED: fixed entries of x_i read as 0
+  double accm[NV][D];       // (M x_i)[row] likewise
+};
+template <int D, int NV>
+struct ElastRow<D, NV, false> {       // without MASS there is no mass accumulator
+  uint8_t fo[D];
+  double xo[NV][D];
+  double acc[NV][D];
+};
+// The fixed bytes and the diagonal block, then per slot the block, its column index, the fixed bytes and the mass scalar
+// are read ONCE for all vectors.  Every sum is seeded from the diagonal block and takes the slots in ascending order, the
+// columns of a block in ascending order: one order of additions under every product, so that their bits agree.  A vector
+// that is off is never read and keeps the seed of zeros.  Without MASS no mass array is touched.
+template <int D, bool MASKED, int NV, bool MASS>
+__device__ __forceinline__ ElastRow<D, NV, MASS> elast_row_walk(int64_t row, const int64_t* mptr, const int32_t* cols,
+                                                                const int32_t* rowlen, const double* vals, const double* diag,
+                                                                const uint8_t* fixed, const double* mvals, const double* mdiag,
+                                                                ElastRowIn<NV> in) {
+  constexpr int DD = D * D;
+  ElastRow<D, NV, MASS> R;
+  const int64_t slice = row >> 6;
+  const int lane = (int)(row & 63);
+  const int64_t mb = mptr[slice];
+  const int len = rowlen[row];
+#pragma unroll
+  for (int r = 0; r < D; ++r) R.fo[r] = MASKED ? fixed[row * D + r] : 0;
+#pragma unroll
+  for (int i = 0; i < NV; ++i)
+#pragma unroll
+    for (int r = 0; r < D; ++r) R.xo[i][r] = in.on[i] ? in.x[i][row * D + r] : 0.0;
+  {
+    double dg[DD];
+#pragma unroll
+    for (int q = 0; q < DD; ++q) dg[q] = diag[row * DD + q];
+    double md = 0.0;
+    if constexpr (MASS) md = mdiag[row];
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int r = 0; r < D; ++r) {
+        double s = 0.0;
+#pragma unroll
+        for (int cc = 0; cc < D; ++cc) s += dg[r * D + cc] * (R.fo[cc] ? 0.0 : R.xo[i][cc]);
+        R.acc[i][r] = s;
+        if constexpr (MASS) R.accm[i][r] = md * (R.fo[r] ? 0.0 : R.xo[i][r]);
+      }
+  }
+  for (int k = 0; k < len; ++k) {
+    const int64_t e = femo_sell_index(mb, k, lane);
+    const int64_t col = cols[e];
+    double blk[DD];
+#pragma unroll
+    for (int q = 0; q < DD; ++q) blk[q] = vals[e * DD + q];
+    double mv = 0.0;
+    if constexpr (MASS) mv = mvals[e];
+    uint8_t fc[D];
+#pragma unroll
+    for (int cc = 0; cc < D; ++cc) fc[cc] = MASKED ? fixed[col * D + cc] : 0;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      if (!in.on[i]) continue;
+      double xc[D];
+#pragma unroll
+      for (int cc = 0; cc < D; ++cc) {
+        xc[cc] = in.x[i][col * D + cc];
+        if (MASKED && fc[cc]) xc[cc] = 0.0;
+      }
+#pragma unroll
+      for (int r = 0; r < D; ++r) {
+#pragma unroll
+        for (int cc = 0; cc < D; ++cc) R.acc[i][r] += blk[r * D + cc] * xc[cc];
+        if constexpr (MASS) R.accm[i][r] += mv * xc[r];
+      }
+    }
+  }
+  return R;
+}
+
 // gradients of the barycentric coordinates and the volume of a P1 simplex, from the vertices in `conn` order
 template <int D>
 __device__ __forceinline__ void simplex_grads(const double (&p)[D + 1][D], double (&g)[D + 1][D], double& vol) {

@@ -8,9 +8,9 @@
 // An iteration issues these launches, each with a column dimension in its grid:
 //
 //   q_l = A p_l, partial p_l.q_l       k_elast_spmv_multi   up to MC columns per thread: a d x d block, its column index
-//                                                           and the fixed bytes are read once for them; pass blockIdx.y
-//                                                           covers columns MC * blockIdx.y ...  One column runs the MC = 1
-//                                                           instantiation, several run MultiChunk<D>::value
+//                                                           and the fixed bytes are read once for them (elast_row_walk);
+//                                                           pass blockIdx.y covers columns MC * blockIdx.y ...  One column
+//                                                           runs the MC = 1 instantiation, several run ELAST_CHUNK
 //   alpha_l                            k_pcg_scalar         one workgroup per column
 //   x, r update, z_l = M^-1 r_l        k_pcg_precond, or the four launches of femo_elast_pc_step
 //   beta_l, convergence of column l    k_pcg_scalar
@@ -20,6 +20,9 @@
 // a column is set (converged, breakdown, or the stopping test met at iteration 0) every block of that column returns
 // early, so its x, r and p are never written again and a stale alpha does no harm.  Within a column every sum runs in the
 // same order whatever L is: no float atomics, the same bits on every call.
+//
+// The host side of the loop -- reserve, start, bursts of iterations between polls of the flags, read-back -- is
+// femo_elast_krylov_loop, which the MINRES of elast_harm.hip and the COCR of elast_damp.hip run as well.
 #include "elast_internal.h"
 
 #include <algorithm>
@@ -30,10 +33,6 @@ namespace {
 
 constexpr int EMC = FEMO_ELAST_MAX_COLS;
 
-// columns per thread of the batched product
-template <int D>
-struct MultiChunk { static constexpr int value = 4; };
-
 // y_l = a Op x_l + b f_l (+ partial dot(x_l, y_l) per block and column when part != null) for the columns
 // c0 = MC * blockIdx.y ... min(c0 + MC, n_cols) - 1.  done != null: a column whose done[l * EMF_STRIDE] is set is skipped.
 // vs: column stride of the vectors, ps: of the partials.
@@ -43,7 +42,6 @@ __global__ __launch_bounds__(EB) void k_elast_spmv_multi(
     const double* __restrict__ vals, const double* __restrict__ diag, const uint8_t* __restrict__ fixed, int n_cols, int64_t vs,
     double a, const double* __restrict__ x, double b, const double* __restrict__ f, double* __restrict__ y,
     double* __restrict__ part, int64_t ps, const int32_t* __restrict__ done) {
-  constexpr int DD = D * D;
   __shared__ double lds[EB / 64];
   const int c0 = (int)blockIdx.y * MC;
   bool on[MC];          // uniform over the block
@@ -59,66 +57,23 @@ __global__ __launch_bounds__(EB) void k_elast_spmv_multi(
 #pragma unroll
   for (int c = 0; c < MC; ++c) dotv[c] = 0.0;
   if (row < n_rows) {
-    const int64_t slice = row >> 6;
-    const int lane = (int)(row & 63);
-    const int64_t mb = mptr[slice];
-    const int len = rowlen[row];
-    double acc[MC][D], xo[MC][D];
-    uint8_t fo[D];
+    ElastRowIn<MC> in;
 #pragma unroll
-    for (int r = 0; r < D; ++r) fo[r] = MASKED ? fixed[row * D + r] : 0;
-#pragma unroll
-    for (int c = 0; c < MC; ++c)
-#pragma unroll
-      for (int r = 0; r < D; ++r) xo[c][r] = on[c] ? x[(c0 + c) * vs + row * D + r] : 0.0;
-    {
-      double dg[DD];
-#pragma unroll
-      for (int q = 0; q < DD; ++q) dg[q] = diag[row * DD + q];
-#pragma unroll
-      for (int c = 0; c < MC; ++c)
-#pragma unroll
-        for (int r = 0; r < D; ++r) {
-          double s = 0.0;
-#pragma unroll
-          for (int cc = 0; cc < D; ++cc) s += dg[r * D + cc] * (fo[cc] ? 0.0 : xo[c][cc]);
-          acc[c][r] = s;
-        }
+    for (int c = 0; c < MC; ++c) {
+      in.x[c] = x + (c0 + c) * vs;
+      in.on[c] = on[c];
     }
-    for (int k = 0; k < len; ++k) {
-      const int64_t e = femo_sell_index(mb, k, lane);
-      const int64_t col = cols[e];
-      double blk[DD];
-#pragma unroll
-      for (int q = 0; q < DD; ++q) blk[q] = vals[e * DD + q];
-      uint8_t fc[D];
-#pragma unroll
-      for (int cc = 0; cc < D; ++cc) fc[cc] = MASKED ? fixed[col * D + cc] : 0;
-#pragma unroll
-      for (int c = 0; c < MC; ++c) {
-        if (!on[c]) continue;
-        double xc[D];
-#pragma unroll
-        for (int cc = 0; cc < D; ++cc) {
-          xc[cc] = x[(c0 + c) * vs + col * D + cc];
-          if (MASKED && fc[cc]) xc[cc] = 0.0;
-        }
-#pragma unroll
-        for (int r = 0; r < D; ++r)
-#pragma unroll
-          for (int cc = 0; cc < D; ++cc) acc[c][r] += blk[r * D + cc] * xc[cc];
-      }
-    }
+    const auto w = elast_row_walk<D, MASKED, MC, false>(row, mptr, cols, rowlen, vals, diag, fixed, nullptr, nullptr, in);
 #pragma unroll
     for (int c = 0; c < MC; ++c) {
       if (!on[c]) continue;
 #pragma unroll
       for (int r = 0; r < D; ++r) {
-        double o = MASKED && fo[r] ? xo[c][r] : acc[c][r];
+        double o = MASKED && w.fo[r] ? w.xo[c][r] : w.acc[c][r];
         o = a * o;
         if (f) o += b * f[(c0 + c) * vs + row * D + r];
         y[(c0 + c) * vs + row * D + r] = o;
-        dotv[c] += xo[c][r] * o;
+        dotv[c] += w.xo[c][r] * o;
       }
     }
   }
@@ -227,23 +182,6 @@ __global__ void k_pcg_p(int64_t n, const double* __restrict__ z, double* __restr
   for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) p[i] = z[i] + beta * p[i];
 }
 
-template <int D, bool MASKED, int MC>
-void spmv_launch(femo_elast* e, int nc, double a, const double* x, double b, const double* f, double* y, double* part,
-                 int64_t ps, const int32_t* done) {
-  femo_mesh* m = e->mesh;
-  hipLaunchKernelGGL((k_elast_spmv_multi<D, MASKED, MC>), dim3(grid_of(m->n_rows), (unsigned)((nc + MC - 1) / MC)), dim3(EB), 0,
-                     m->ctx->stream, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_fixed, nc,
-                     m->n_rows * D, a, x, b, f, y, part, ps, done);
-}
-
-// one column: the MC = 1 instantiation, which carries no accumulators of absent columns
-template <int D, bool MASKED>
-void spmv_chunk(femo_elast* e, int nc, double a, const double* x, double b, const double* f, double* y, double* part,
-                int64_t ps, const int32_t* done) {
-  if (nc == 1) spmv_launch<D, MASKED, 1>(e, nc, a, x, b, f, y, part, ps, done);
-  else spmv_launch<D, MASKED, MultiChunk<D>::value>(e, nc, a, x, b, f, y, part, ps, done);
-}
-
 // the PCG of femo_elast_solve (one column) and femo_elast_solve_multi, which have checked their arguments; who: the entry
 // point, for the error texts.  info: n_cols records, or null.
 // op: K (null), or K + sigma M with its own inverse diagonal blocks for the Jacobi term.
@@ -252,74 +190,44 @@ int pcg_solve(femo_elast* e, int n_cols, const femo_vec* b, femo_vec* x, const f
   femo_mesh* m = e->mesh;
   const int64_t n = m->n_vert * e->d;
   const bool ml = opts->pc == FEMO_ELAST_PC_MULTILEVEL;
-  FEMO_REQUIRE(!ml || e->pc, "%s: pc = multilevel without femo_elast_pc_setup", who);
-  FEMO_TRY(femo_vec_await(b));
-  femo_vec_touch(x);
   hipStream_t st = m->ctx->stream;
   const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
-  if (ml) FEMO_TRY(femo_elast_pc_ensure(e));
-  FEMO_TRY(femo_elast_work_reserve(e, n_cols, who));
-  const int check = opts->check_every > 0 ? opts->check_every : (ml ? 8 : 32);
-  const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
   const double rtol2 = opts->rtol * opts->rtol, atol2 = opts->atol * opts->atol;
   const int nps = (int)grid_of(m->n_rows);
-  const int64_t ps = e->w_pstride;
   const unsigned L = (unsigned)n_cols, gp = (unsigned)PCG_GRID;
-  hipEvent_t e0 = m->ctx->ev0, e1 = m->ctx->ev1;
   const double* dinv = op ? op->dinv : e->d_dinv;
   // y = a A x + b f of the chosen operator: the block product of K, or the shifted product with the shift -sigma
   auto product = [&](double a, const double* xx, double bb, const double* f, double* y, double* part, const int32_t* done) -> int {
-    if (op) return femo_elast_dyn_spmv(e, fx != nullptr, n_cols, -op->sigma, a, xx, bb, f, y, part, ps, done);
-    return femo_elast_spmv(e, fx != nullptr, n_cols, a, xx, bb, f, y, part, ps, done);
+    if (op) return femo_elast_dyn_spmv(e, fx != nullptr, n_cols, -op->sigma, a, xx, bb, f, y, part, e->w_pstride, done);
+    return femo_elast_spmv(e, fx != nullptr, n_cols, a, xx, bb, f, y, part, e->w_pstride, done);
   };
-  FEMO_HIP_CHECK(hipEventRecord(e0, st));
-  hipLaunchKernelGGL(k_pcg_start_x, dim3(grid_of(n), L), dim3(EB), 0, st, n, opts->zero_guess, fx, b->d, x->d);
-  FEMO_TRY(product(-1.0, x->d, 1.0, b->d, e->w_r, nullptr, nullptr));                                           // r = b - A x
-#define FEMO_PRECOND(D, U, I) hipLaunchKernelGGL((k_pcg_precond<D, U, I>), dim3(gp, L), dim3(EB), 0, st, m->n_rows, dinv, \
-                                                 x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, ps, e->w_flag)
-  if (ml) FEMO_TRY(femo_elast_pc_step(e, false, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, ps, e->w_flag, dinv));
-  else if (e->d == 2) FEMO_PRECOND(2, false, true); else FEMO_PRECOND(3, false, true);
-  hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 0, e->w_part, ps, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
-  FEMO_HIP_CHECK(hipGetLastError());
-  int it_issued = 0;
-  for (;;) {
-    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_flag, e->w_flag, (size_t)n_cols * EMF_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    FEMO_HIP_CHECK(hipStreamSynchronize(st));
-    bool all_done = true;
-    for (int l = 0; l < n_cols; ++l) all_done = all_done && e->h_flag[l * EMF_STRIDE] != 0;
-    if (all_done || it_issued >= max_it) break;
-    for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) {
-      FEMO_TRY(product(1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, e->w_flag));                               // q = A p, p.q
-      hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 1, e->w_part, ps, nps, rtol2, atol2, max_it, e->w_s, e->w_flag);
-      if (ml) FEMO_TRY(femo_elast_pc_step(e, true, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, nullptr, e->w_s, e->w_part, ps, e->w_flag, dinv));
-      else if (e->d == 2) FEMO_PRECOND(2, true, false); else FEMO_PRECOND(3, true, false);
-      hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, 2, e->w_part, ps, PCG_GRID, rtol2, atol2, max_it, e->w_s, e->w_flag);
-      hipLaunchKernelGGL(k_pcg_p, dim3(gp, L), dim3(EB), 0, st, n, e->w_z, e->w_p, e->w_s, e->w_flag);
-    }
-    FEMO_HIP_CHECK(hipGetLastError());
-  }
+#define FEMO_PRECOND(D, U, I) hipLaunchKernelGGL((k_pcg_precond<D, U, I>), dim3(gp, L), dim3(EB), 0, st, m->n_rows, dinv, x->d, \
+                                                 e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, e->w_pstride, e->w_flag)
+#define FEMO_PCG_SCALAR(MODE, NP) hipLaunchKernelGGL(k_pcg_scalar, dim3(L), dim3(1024), 0, st, MODE, e->w_part, e->w_pstride, NP, \
+                                                     rtol2, atol2, max_it, e->w_s, e->w_flag)
+  femo_elast_krylov loop = {who, n_cols, n_cols, 1, false};
+  loop.start = [&](int max_it) -> int {
+    hipLaunchKernelGGL(k_pcg_start_x, dim3(grid_of(n), L), dim3(EB), 0, st, n, opts->zero_guess, fx, b->d, x->d);
+    FEMO_TRY(product(-1.0, x->d, 1.0, b->d, e->w_r, nullptr, nullptr));                                         // r = b - A x
+    if (ml) FEMO_TRY(femo_elast_pc_step(e, false, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, e->w_p, e->w_s, e->w_part, e->w_pstride, e->w_flag, dinv));
+    else if (e->d == 2) FEMO_PRECOND(2, false, true); else FEMO_PRECOND(3, false, true);
+    FEMO_PCG_SCALAR(0, PCG_GRID);
+    return 0;
+  };
+  loop.iterate = [&](int, int max_it) -> int {
+    FEMO_TRY(product(1.0, e->w_p, 0.0, nullptr, e->w_q, e->w_part, e->w_flag));                                 // q = A p, p.q
+    FEMO_PCG_SCALAR(1, nps);
+    if (ml) FEMO_TRY(femo_elast_pc_step(e, true, n_cols, x->d, e->w_r, e->w_p, e->w_q, e->w_z, nullptr, e->w_s, e->w_part, e->w_pstride, e->w_flag, dinv));
+    else if (e->d == 2) FEMO_PRECOND(2, true, false); else FEMO_PRECOND(3, true, false);
+    FEMO_PCG_SCALAR(2, PCG_GRID);
+    hipLaunchKernelGGL(k_pcg_p, dim3(gp, L), dim3(EB), 0, st, n, e->w_z, e->w_p, e->w_s, e->w_flag);
+    return 0;
+  };
 #undef FEMO_PRECOND
-  FEMO_HIP_CHECK(hipEventRecord(e1, st));
-  FEMO_HIP_CHECK(hipMemcpyAsync(e->h_s, e->w_s, (size_t)n_cols * EMS_STRIDE * sizeof(double), hipMemcpyDeviceToHost, st));
-  FEMO_HIP_CHECK(hipStreamSynchronize(st));
-  if (info) {
-    float ms = 0.0f;
-    const bool timed = hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-    for (int l = 0; l < n_cols; ++l) {
-      const int32_t* fl = e->h_flag + l * EMF_STRIDE;
-      const double* s = e->h_s + l * EMS_STRIDE;
-      femo_solve_info* o = info + l;
-      std::memset(o, 0, sizeof(*o));
-      o->iterations = fl[1];
-      o->converged = fl[2] ? -1 : (fl[3] ? 1 : 0);
-      o->residual_norm = std::sqrt(std::fabs(s[S_RZ]));
-      o->rhs_norm = std::sqrt(std::fabs(s[S_RZ0]));
-      o->pc_residual_norm = o->residual_norm;
-      o->pc_rhs_norm = o->rhs_norm;
-      if (timed) o->solve_ms = ms;
-    }
-  }
-  return 0;
+#undef FEMO_PCG_SCALAR
+  loop.d_scal = &femo_elast::w_s; loop.h_scal = &femo_elast::h_s; loop.scal_stride = EMS_STRIDE;
+  loop.s_res = S_RZ; loop.s_rhs = S_RZ0; loop.squared = true;                                                   // r.z of the last and the first residual
+  return femo_elast_krylov_loop(e, b, x, opts, info, loop);
 }
 
 // the product of femo_elast_apply (one column) and femo_elast_apply_multi, which have checked their arguments
@@ -334,14 +242,69 @@ int apply_cols(femo_elast* e, int masked, int n_cols, double a, const femo_vec* 
 
 int femo_elast_spmv(femo_elast* e, bool masked, int n_cols, double a, const double* x, double b, const double* f, double* y,
                     double* part, int64_t part_stride, const int32_t* done) {
-  if (e->d == 2) {
-    if (masked) spmv_chunk<2, true>(e, n_cols, a, x, b, f, y, part, part_stride, done);
-    else spmv_chunk<2, false>(e, n_cols, a, x, b, f, y, part, part_stride, done);
-  } else {
-    if (masked) spmv_chunk<3, true>(e, n_cols, a, x, b, f, y, part, part_stride, done);
-    else spmv_chunk<3, false>(e, n_cols, a, x, b, f, y, part, part_stride, done);
-  }
+  femo_mesh* m = e->mesh;
+  // one column: the MC = 1 instantiation, which carries no accumulators of absent columns
+  const int mc = n_cols == 1 ? 1 : ELAST_CHUNK;
+  elast_dispatch(e->d, masked, [&](auto dim, auto mask) {
+    constexpr int D = decltype(dim)::value;
+    constexpr bool MASKED = decltype(mask)::value;
+    auto* kernel = n_cols == 1 ? k_elast_spmv_multi<D, MASKED, 1> : k_elast_spmv_multi<D, MASKED, ELAST_CHUNK>;
+    hipLaunchKernelGGL(kernel, dim3(grid_of(m->n_rows), (unsigned)((n_cols + mc - 1) / mc)), dim3(EB), 0, m->ctx->stream, m->n_rows,
+                       m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_fixed, n_cols, m->n_rows * D, a, x, b, f, y,
+                       part, part_stride, done);
+  });
   FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int femo_elast_krylov_loop(femo_elast* e, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info,
+                           const femo_elast_krylov& loop) {
+  femo_mesh* m = e->mesh;
+  const bool ml = opts->pc == FEMO_ELAST_PC_MULTILEVEL;
+  FEMO_REQUIRE(!ml || e->pc, "%s: pc = multilevel without femo_elast_pc_setup", loop.who);
+  FEMO_TRY(femo_vec_await(b));
+  femo_vec_touch(x);
+  hipStream_t st = m->ctx->stream;
+  if (ml) FEMO_TRY(femo_elast_pc_ensure(e));
+  FEMO_TRY(femo_elast_work_reserve(e, loop.real_cols, loop.who));
+  if (loop.harm) FEMO_TRY(femo_elast_harm_reserve(e, loop.real_cols, loop.who));
+  const int check = opts->check_every > 0 ? opts->check_every : (ml ? 8 : 32);
+  const int max_it = opts->max_it > 0 ? opts->max_it : 100000;
+  hipEvent_t e0 = m->ctx->ev0, e1 = m->ctx->ev1;
+  FEMO_HIP_CHECK(hipEventRecord(e0, st));
+  FEMO_TRY(loop.start(max_it));
+  FEMO_HIP_CHECK(hipGetLastError());
+  int it_issued = 0;
+  for (;;) {
+    FEMO_HIP_CHECK(hipMemcpyAsync(e->h_flag, e->w_flag, (size_t)loop.real_cols * EMF_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FEMO_HIP_CHECK(hipStreamSynchronize(st));
+    bool all_done = true;
+    for (int l = 0; l < loop.n_cols; ++l) all_done = all_done && e->h_flag[loop.flag_stride * l * EMF_STRIDE] != 0;
+    if (all_done || it_issued >= max_it) break;
+    for (int k = 0; k < check && it_issued < max_it; ++k, ++it_issued) FEMO_TRY(loop.iterate(it_issued, max_it));
+    FEMO_HIP_CHECK(hipGetLastError());
+  }
+  FEMO_HIP_CHECK(hipEventRecord(e1, st));
+  FEMO_HIP_CHECK(hipMemcpyAsync(e->*loop.h_scal, e->*loop.d_scal, (size_t)loop.n_cols * loop.scal_stride * sizeof(double),
+                                hipMemcpyDeviceToHost, st));
+  FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  if (info) {
+    float ms = 0.0f;
+    const bool timed = hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+    for (int l = 0; l < loop.n_cols; ++l) {
+      const int32_t* fl = e->h_flag + loop.flag_stride * l * EMF_STRIDE;
+      const double* s = e->*loop.h_scal + l * loop.scal_stride;
+      femo_solve_info* o = info + l;
+      std::memset(o, 0, sizeof(*o));
+      o->iterations = fl[1];
+      o->converged = fl[2] ? -1 : (fl[3] ? 1 : 0);
+      o->residual_norm = loop.squared ? std::sqrt(std::fabs(s[loop.s_res])) : s[loop.s_res];
+      o->rhs_norm = loop.squared ? std::sqrt(std::fabs(s[loop.s_rhs])) : s[loop.s_rhs];
+      o->pc_residual_norm = o->residual_norm;
+      o->pc_rhs_norm = o->rhs_norm;
+      if (timed) o->solve_ms = ms;
+    }
+  }
   return 0;
 }
 

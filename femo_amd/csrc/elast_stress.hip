@@ -18,8 +18,6 @@ namespace {
 
 constexpr int EMC = FEMO_ELAST_MAX_COLS;
 
-struct ColScalars { double v[EMC]; };
-
 // columns per thread of the dJ/du kernel: D accumulators and one deviator per column in registers
 template <int D>
 struct StressChunk { static constexpr int value = 4; };

@@ -72,95 +72,39 @@ struct BandArgs {
 
 // Column col0 + blockIdx.y of
 //   y = cr rhs + sum_{i < NV} (m_i M + k_i K) x_i
-// over the SELL rows: each d x d block of K, each scalar of M and each column index is read once for the NV vectors.
-// MASKED: the fixed entries of every x read as 0; a fixed row gives crf rhs + idc x_0.  rhs may be null.  rhs and y are
-// those of the launch's first column, their columns rs and vs apart.
+// over the SELL rows (elast_row_walk): each d x d block of K, each scalar of M and each column index is read once for the NV
+// vectors.  MASKED: the fixed entries of every x read as 0; a fixed row gives crf rhs + idc x_0.  rhs may be null.  rhs and
+// y are those of the launch's first column, their columns rs and vs apart.
 template <int D, bool MASKED, int NV>
 __global__ __launch_bounds__(EB) void k_newmark_band(
     int64_t n_rows, const int64_t* __restrict__ mptr, const int32_t* __restrict__ cols, const int32_t* __restrict__ rowlen,
     const double* __restrict__ vals, const double* __restrict__ diag, const double* __restrict__ mvals,
     const double* __restrict__ mdiag, const uint8_t* __restrict__ fixed, BandArgs A, int n_steps, int col0, int64_t vs,
     const double* __restrict__ X, const double* __restrict__ rhs, int64_t rs, double* __restrict__ y) {
-  constexpr int DD = D * D;
   const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (row >= n_rows) return;
   const int col = col0 + (int)blockIdx.y;
-  const double* __restrict__ xin[NV];
-  bool on[NV];          // uniform over the block
+  ElastRowIn<NV> in;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int t = col + A.off[i];
-    on[i] = t >= 0 && t < n_steps;
-    xin[i] = on[i] ? X + (int64_t)t * vs : nullptr;
+    in.on[i] = t >= 0 && t < n_steps;
+    in.x[i] = in.on[i] ? X + (int64_t)t * vs : nullptr;
   }
   if (rhs) rhs += (int64_t)blockIdx.y * rs;
   y += (int64_t)blockIdx.y * vs;
-  const int64_t slice = row >> 6;
-  const int lane = (int)(row & 63);
-  const int64_t mb = mptr[slice];
-  const int len = rowlen[row];
-  double ak[NV][D], am[NV][D], xo[NV][D];
-  uint8_t fo[D];
-#pragma unroll
-  for (int r = 0; r < D; ++r) fo[r] = MASKED ? fixed[row * D + r] : 0;
-#pragma unroll
-  for (int i = 0; i < NV; ++i)
-#pragma unroll
-    for (int r = 0; r < D; ++r) xo[i][r] = on[i] ? xin[i][row * D + r] : 0.0;
-  {
-    double dg[DD];
-#pragma unroll
-    for (int q = 0; q < DD; ++q) dg[q] = diag[row * DD + q];
-    const double md = mdiag[row];
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-      for (int r = 0; r < D; ++r) {
-        double s = 0.0;
-#pragma unroll
-        for (int cc = 0; cc < D; ++cc) s += dg[r * D + cc] * (fo[cc] ? 0.0 : xo[i][cc]);
-        ak[i][r] = s;
-        am[i][r] = md * (fo[r] ? 0.0 : xo[i][r]);
-      }
-  }
-  for (int k = 0; k < len; ++k) {
-    const int64_t e = femo_sell_index(mb, k, lane);
-    const int64_t c = cols[e];
-    double blk[DD];
-#pragma unroll
-    for (int q = 0; q < DD; ++q) blk[q] = vals[e * DD + q];
-    const double mv = mvals[e];
-    uint8_t fc[D];
-#pragma unroll
-    for (int cc = 0; cc < D; ++cc) fc[cc] = MASKED ? fixed[c * D + cc] : 0;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      if (!on[i]) continue;
-      double xc[D];
-#pragma unroll
-      for (int cc = 0; cc < D; ++cc) {
-        xc[cc] = xin[i][c * D + cc];
-        if (MASKED && fc[cc]) xc[cc] = 0.0;
-      }
-#pragma unroll
-      for (int r = 0; r < D; ++r) {
-#pragma unroll
-        for (int cc = 0; cc < D; ++cc) ak[i][r] += blk[r * D + cc] * xc[cc];
-        am[i][r] += mv * xc[r];
-      }
-    }
-  }
+  const auto w = elast_row_walk<D, MASKED, NV, true>(row, mptr, cols, rowlen, vals, diag, fixed, mvals, mdiag, in);
 #pragma unroll
   for (int r = 0; r < D; ++r) {
     const double f = rhs ? rhs[row * D + r] : 0.0;
     double o;
-    if (MASKED && fo[r]) {
-      o = A.crf * f + A.idc * xo[0][r];
+    if (MASKED && w.fo[r]) {
+      o = A.crf * f + A.idc * w.xo[0][r];
     } else {
       o = A.cr * f;
 #pragma unroll
       for (int i = 0; i < NV; ++i)
-        if (on[i]) o += A.k[i] * ak[i][r] + A.m[i] * am[i][r];
+        if (in.on[i]) o += A.k[i] * w.acc[i][r] + A.m[i] * w.accm[i][r];
     }
     y[row * D + r] = o;
   }
@@ -210,8 +154,6 @@ __global__ __launch_bounds__(EB) void k_newmark_combine(int64_t n, int col0, NmB
   outM[(int64_t)blockIdx.y * n + i] = c.m[0] * u1 + c.m[1] * u0 + c.m[2] * um;
 }
 
-struct ColScalars { double v[EMC]; };
-
 // column blockIdx.y: y = a_c f
 __global__ __launch_bounds__(EB) void k_newmark_outer(int64_t n, ColScalars a, const double* __restrict__ f, double* __restrict__ y) {
   const int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x;
@@ -219,25 +161,17 @@ __global__ __launch_bounds__(EB) void k_newmark_outer(int64_t n, ColScalars a, c
   y[(int64_t)blockIdx.y * n + i] = a.v[blockIdx.y] * f[i];
 }
 
-template <int D, bool MASKED, int NV>
-void band_launch(femo_elast* e, const BandArgs& A, int n_steps, int col0, int n_cols, const double* X, const double* rhs,
-                 int64_t rs, double* y) {
-  femo_mesh* m = e->mesh;
-  hipLaunchKernelGGL((k_newmark_band<D, MASKED, NV>), dim3(grid_of(m->n_rows), (unsigned)n_cols), dim3(EB), 0, m->ctx->stream,
-                     m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_mvals, e->d_mdiag, e->d_fixed, A,
-                     n_steps, col0, m->n_rows * D, X, rhs, rs, y);
-}
-
 template <int NV>
 int band(femo_elast* e, bool masked, const BandArgs& A, int n_steps, int col0, int n_cols, const double* X, const double* rhs,
          int64_t rs, double* y) {
-  if (e->d == 2) {
-    if (masked) band_launch<2, true, NV>(e, A, n_steps, col0, n_cols, X, rhs, rs, y);
-    else band_launch<2, false, NV>(e, A, n_steps, col0, n_cols, X, rhs, rs, y);
-  } else {
-    if (masked) band_launch<3, true, NV>(e, A, n_steps, col0, n_cols, X, rhs, rs, y);
-    else band_launch<3, false, NV>(e, A, n_steps, col0, n_cols, X, rhs, rs, y);
-  }
+  femo_mesh* m = e->mesh;
+  elast_dispatch(e->d, masked, [&](auto dim, auto mask) {
+    constexpr int D = decltype(dim)::value;
+    constexpr bool MASKED = decltype(mask)::value;
+    hipLaunchKernelGGL((k_newmark_band<D, MASKED, NV>), dim3(grid_of(m->n_rows), (unsigned)n_cols), dim3(EB), 0, m->ctx->stream,
+                       m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, e->d_vals, e->d_diag, e->d_mvals, e->d_mdiag, e->d_fixed, A,
+                       n_steps, col0, m->n_rows * D, X, rhs, rs, y);
+  });
   FEMO_HIP_CHECK(hipGetLastError());
   return 0;
 }
