@@ -27,8 +27,10 @@ struct StressChunk { static constexpr int value = 4; };
 //   drho[c] (+)= sum_l w_l p q / rho_c J_{l,c}, summed in ascending l
 //   field[c] = max_l s_l rho_c^q sigma_vm(u_l) (column < 0: the envelope), or s_column rho_c^q sigma_vm(u_column)
 // rho == null reads as q = 0.  A (cell, column) with sigma_vm = 0 gives 0 everywhere (pow(0, p) = 0 for p >= 1; no division
-// by it).  ONE: the one-column instantiation (n_cols = 1, column 0, known at compile time), which keeps no geometry alive
-// across a column loop and writes the field as it is, so that a non-finite state shows as a non-finite stress.
+// by it); the guard is a test for == 0, so a non-finite stress is no zero: it shows in the value, in drho and in the field
+// (the envelope's maximum keeps a NaN).  A column with w_l = 0 takes no part in drho.  ONE: the one-column instantiation
+// (n_cols = 1, column 0, known at compile time), which keeps no geometry alive across a column loop and writes the field as
+// it is.
 template <int D, bool ONE>
 __global__ __launch_bounds__(EB) void k_elast_stress_cell_multi(
     int64_t n_cell, const int32_t* __restrict__ conn, const double* __restrict__ xv, const double* __restrict__ rho,
@@ -65,9 +67,12 @@ __global__ __launch_bounds__(EB) void k_elast_stress_cell_multi(
       const double vm = cell_von_mises<D>(g, v, u + l * vs, mu, s);
       const double relaxed = rq * vm;
       if (ONE) fmax_ = sc.v[0] * relaxed;
-      else if (field && (column < 0 || column == l)) fmax_ = fmax(fmax_, sc.v[l] * relaxed);
+      else if (field && (column < 0 || column == l)) {
+        const double f = sc.v[l] * relaxed;
+        fmax_ = f > fmax_ || f != f ? f : fmax_;          // a sticky maximum: fmax would drop a NaN
+      }
       if (sums) {
-        Jc = vm > 0.0 ? vol * inv_alpha * pow(m.v[l] * relaxed, p) : 0.0;
+        Jc = vm == 0.0 ? 0.0 : vol * inv_alpha * pow(m.v[l] * relaxed, p);
         if (drho && q != 0.0 && Jc != 0.0 && w.v[l] != 0.0) dsum += w.v[l] * (p * q / r * Jc);
       }
     }
@@ -140,7 +145,7 @@ __global__ __launch_bounds__(EB) void k_elast_stress_du_multi(
         if (!act[cc]) continue;
         double s[D][D];
         const double vm = cell_von_mises<D>(g, v, u + (c0 + cc) * vs, mu, s);
-        if (!(vm > 0.0)) continue;
+        if (vm == 0.0) continue;                          // exactly zero only: a NaN stress goes on and shows in y
         if (MC == 1) rq = q != 0.0 ? pow(rho[c], q) : 1.0;
         const double mr = mm[cc] * rq;
         const double wt = ww[cc] * (base * mr * pow(mr * vm, p - 1.0));

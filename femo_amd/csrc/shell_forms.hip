@@ -409,7 +409,7 @@ __global__ __launch_bounds__(SH_BLOCK) void k_shell_pnorm_stress(femo_shell_view
       const double e0 = sw[0] + z * sw[3], e1 = sw[1] + z * sw[4], e2 = sw[2] + z * sw[5];
       const double s0 = mt.c11 * e0 + mt.c12 * e1, s1 = mt.c12 * e0 + mt.c11 * e1, s2 = mt.c33 * e2;
       const double vm = sqrt(s0 * s0 - s0 * s1 + s1 * s1 + 3.0 * s2 * s2);
-      if (!(vm > 0.0)) continue;
+      if (vm == 0.0) continue;                 // exactly zero only: a non-finite stress shows in the value and both gradients
       const double pw = pow(mscale * vm, rho - 1.0);
       val += wq * pw * mscale * vm * inv_alpha;
       if (grad_w == nullptr && grad_h == nullptr) continue;

@@ -848,6 +848,9 @@ class DeviceShell:
         E.pointwise_divide(z, r, ml, nv)
         p.copy_from(z)
         g = g0 = dot(r, z)
+        if not np.isfinite(g0):
+            # g <= rtol^2 g0 holds at once for g0 = inf (the zero field would be returned) and never for NaN: refuse both
+            raise E.FemoError("the von Mises stress to project is not finite")
         for _ in range(max_it):
             if g <= (rtol * rtol) * g0 or g0 == 0.0:
                 return refresh(out) if part is not None else out

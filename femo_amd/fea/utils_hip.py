@@ -711,7 +711,10 @@ class _NewtonBase:
         use_flag = (reuse and ctx.nranks == 1 and os.environ.get("FEMO_NEWTON_FLAG", "1") != "0" and E.has_newton_flag())
         while not converged and it < self.max_it:
             if it > 0:
-                opts["atol"] = max(KSP_OPTIONS["atol"], KSP_OPTIONS["rtol"] * z0, self.NOISE_FACTOR * eps * unorm)
+                # (a NaN ||u|| gives no noise floor -- max() would drop it without a word -- and, below, no skip either: the
+                # pass goes to the solver, whose own rule says -1 for the residual of such a state)
+                noise = self.NOISE_FACTOR * eps * unorm
+                opts["atol"] = max(KSP_OPTIONS["atol"], KSP_OPTIONS["rtol"] * z0, noise if noise == noise else 0.0)
                 if bpx_energy:
                     # Later corrections are solved to the accuracy the first solve aims at, measured against the
                     # STATE: sqrt(r^T M^-1 r) ~ energy norm of the error, threshold rtol_bpx * sqrt(u^T A u) (interior
@@ -745,7 +748,10 @@ class _NewtonBase:
             # assembled residual (Newton's passes 2 and 3 of a linear form) costs one small launch instead of a solver
             # set-up, a first application and a host round trip.  Same numbers, same rule, same result (identity rows solved,
             # zero elsewhere); the solve is still reported (0 iterations).
+            # A rho_0 that is NaN is not "nothing to iterate on": the solver's rule reports it as converged = -1, so it is the
+            # solver that gets it (the record of the path without the probe), never the identity solve's converged = 1.
             skip = (rho_b is not None and A.symmetric and not hasattr(A, "backend_solve")
+                    and rho_b == rho_b and (it == 0 or unorm == unorm)
                     and (rho_b == 0.0 or not (np.sqrt(rho_b) > opts["atol"])))
             if skip:
                 A.mat.identity_solve(b, dx, flagged=use_flag)

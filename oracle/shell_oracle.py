@@ -276,9 +276,10 @@ def pnorm_stress(V: ShellSpace, w: np.ndarray, h_nodal, E: float, nu: float, m: 
         vm = np.sqrt(sig[:, 0] ** 2 - sig[:, 0] * sig[:, 1] + sig[:, 1] ** 2 + 3.0 * sig[:, 2] ** 2)
         J += float(np.sum(wq * area * (m * vm) ** rho)) / alpha
         if grad:
-            safe = np.where(vm > 0.0, vm, 1.0)
+            zero = vm == 0.0                          # exactly zero only: a non-finite stress is no zero and shows in both gradients
+            safe = np.where(zero, 1.0, vm)
             dvm = np.stack([2 * sig[:, 0] - sig[:, 1], 2 * sig[:, 1] - sig[:, 0], 6 * sig[:, 2]], axis=1) / (2.0 * safe[:, None])
-            fac = np.where(vm > 0.0, wq * area * rho * m * (m * safe) ** (rho - 1.0) / alpha, 0.0)      # dJ / d vm
+            fac = np.where(zero, 0.0, wq * area * rho * m * (m * safe) ** (rho - 1.0) / alpha)      # dJ / d vm
             ds = fac[:, None] * np.einsum("ci,ij->cj", dvm, C)                                          # dJ / d (eps + z kappa)
             np.add.at(gw, V.cell_dofs.ravel(), (np.einsum("ci,cia->ca", ds, Bm) + z[:, None] * np.einsum("ci,cia->ca", ds, Bb)).ravel())
             np.add.at(gh, V.conn.ravel(), (0.5 * surface * np.einsum("ci,ci->c", ds, kap)[:, None] * lam[None, :]).ravel())

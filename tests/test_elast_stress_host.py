@@ -49,6 +49,38 @@ def test_zero_displacement(name):
         assert np.all(np.isfinite(R["du"])) and np.all(np.isfinite(R["drho"]))
 
 
+@pytest.mark.parametrize("name", MESHES)
+def test_zero_guard_is_exact_and_hides_no_non_finite_state(name):
+    """The guard sigma_vm == 0 and the earlier sigma_vm > 0 give the same bits on finite inputs (random, all zero, and a
+    state with some cells at exactly zero stress).  With one entry of the state at NaN, +Inf or -Inf the value is not
+    finite and neither are the partials of the cells and vertices around it, where the earlier guard returned finite numbers."""
+    mesh = _meshes()[name]()
+    x, conn, d = mesh.x, mesh.conn, mesh.tdim
+    u, rho, m = sref.random_inputs(x, conn, seed=5)
+    some_zero = u.copy().reshape(-1, d)
+    some_zero[np.unique(conn[: mesh.n_cell // 3])] = 0.0                # whole cells without displacement
+    assert 0 < (sref.von_mises(x, conn, some_zero.ravel()) == 0.0).sum() < mesh.n_cell
+    for state in (u, np.zeros_like(u), some_zero.ravel()):
+        for p, q in sref.PQ_CASES:
+            new = sref.pnorm_stress(x, conn, rho, state, m, p, q)
+            old = sref.pnorm_stress(x, conn, rho, state, m, p, q, positive_guard=True)
+            assert new["value"] == old["value"] and np.isfinite(new["value"])
+            assert np.array_equal(new["du"], old["du"]) and np.array_equal(new["drho"], old["drho"])
+    vertex = mesh.n_vert // 2
+    touching = np.any(conn == vertex, axis=1)
+    for bad in (np.nan, np.inf, -np.inf):
+        state = u.copy()
+        state[vertex * d + 1] = bad
+        with np.errstate(all="ignore"):
+            new = sref.pnorm_stress(x, conn, rho, state, m, 8.0, 0.5)
+            old = sref.pnorm_stress(x, conn, rho, state, m, 8.0, 0.5, positive_guard=True)
+        assert not np.isfinite(new["value"])
+        assert not np.isfinite(new["drho"][touching]).any() and np.isfinite(new["drho"][~touching]).all()
+        assert not np.isfinite(new["du"].reshape(-1, d)[np.unique(conn[touching])]).any()
+        if bad != bad:
+            assert np.isfinite(old["value"]) and np.isfinite(old["drho"]).all()      # what the earlier guard hid
+
+
 def test_hydrostatic_is_finite():
     mesh = _meshes()["cube4j"]()
     rho = np.random.default_rng(2).uniform(1e-3, 1.0, mesh.n_cell)

@@ -104,6 +104,60 @@ def test_newton_probe_takes_the_solvers_decision(ctx):
     assert np.abs(u1 - ref['u']).max() < 1e-10 * np.abs(ref['u']).max()
 
 
+def test_newton_probe_leaves_a_nan_to_the_solver(ctx, monkeypatch):
+    """The NaN case of the comparison above: the state picks up a NaN right after Newton's first update, so the next pass's
+    right-hand side, ||u|| and rho_0 are NaN.  `not (sqrt(rho_0) > atol)` is true for a NaN as well, but it is not "nothing to
+    iterate on": with the probe and without it the pass goes to the solver, whose rule (k_pcg_setup) records converged = -1
+    and whose error ends the solve; no pass is recorded as converged = 1, skipped_by_newton."""
+    from bench import build_problem, source_fields
+    from femo_amd import engine as E
+    from femo_amd.fea import utils_hip
+    from femo_amd.fea.mesh import createUnitCubeMesh
+    utils_hip.set_context(ctx)
+    mesh = createUnitCubeMesh(12, jitter=0.2)
+    f = source_fields(mesh, 1)[0]
+    plain_axpy = E.Vec.axpy
+    out = {}
+    try:
+        for probe in (True, False):
+            monkeypatch.setattr(utils_hip._NewtonBase, "newton_probe", probe)
+            sim, fea = build_problem(mesh, device=False)
+            state = fea.states_dict['u']['function'].vec
+            updates = []
+
+            def axpy(self, a, x, flagged=False, state=state, updates=updates):
+                plain_axpy(self, a, x, flagged=flagged)
+                if self is state:
+                    updates.append(flagged)
+                    if len(updates) == 1:                               # Newton's first update of the state: poison one entry
+                        u = np.empty(self.n)
+                        self.get(out=u)
+                        u[self.n // 2] = np.nan
+                        self.set(u)
+                return self
+
+            monkeypatch.setattr(E.Vec, "axpy", axpy)
+            sim['f'] = E.pinned_array(f)
+            sim['u'] = np.zeros(mesh.n_vert)
+            del utils_hip.LAST_KSP_INFO[:]
+            raised = None
+            try:
+                sim.run()
+            except Exception as e:                                      # the solver's "did not converge", through the operator
+                raised = str(e)
+            monkeypatch.setattr(E.Vec, "axpy", plain_axpy)
+            infos = list(utils_hip.LAST_KSP_INFO)
+            out[probe] = ([i["converged"] for i in infos], [bool(i.get("skipped_by_newton")) for i in infos], raised is not None,
+                          len(updates))
+            print(f"probe={probe}: converged {out[probe][0]}, skipped {out[probe][1]}, raised: {raised}")
+            utils_hip.clear_workspaces()
+    finally:
+        monkeypatch.setattr(E.Vec, "axpy", plain_axpy)
+    assert out[True] == out[False]
+    conv, skipped, raised, n_updates = out[True]
+    assert conv == [1, -1] and skipped == [False, False] and raised and n_updates == 1
+
+
 def test_host_sync_counter_counts(ctx):
     from femo_amd import engine as E
     E.host_syncs(reset=True)
