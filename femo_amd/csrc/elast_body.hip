@@ -18,7 +18,7 @@ constexpr int EMC = FEMO_ELAST_MAX_COLS;
 
 struct BodyForces { double v[EMC][3]; };
 
-// N: one thread per vertex row, the visit walk of k_elast_drho_N.  s_v once, then every column and component:
+// N: one thread per vertex row on the shared visit walk (elast_visits).  s_v once, then every column and component:
 //   y = [accumulate ? y : (base ? base : 0)] + a s_v b_l[i],   or 0 on a fixed dof (fixed != null: the same set per column)
 template <int D>
 __global__ __launch_bounds__(EB) void k_elast_body_N(
@@ -27,19 +27,12 @@ __global__ __launch_bounds__(EB) void k_elast_body_N(
     const double* __restrict__ base, const uint8_t* __restrict__ fixed, double* __restrict__ y, int accumulate) {
   const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (row >= n_rows) return;
-  const int64_t slice = row >> 6;
-  const int lane = (int)(row & 63);
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
   double sv = 0.0;
-  for (int s = 0; s < nvis; ++s) {
-    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
-    if (ca < 0) continue;
-    const int64_t c = ca >> 2;
-    int32_t v[D + 1];
-    double p[D + 1][D];
-    load_cell<D>(conn, xv, c, v, p);
-    sv += w[c] * (simplex_volume<D>(p) * (1.0 / (D + 1)));
+  const ElastVisits V = elast_visits(row, vptr);
+  for (int s = 0; s < V.n; ++s) {
+    const ElastVisit t = elast_visit(V, visit_cell, s);
+    if (!t.live) continue;
+    sv += w[t.c] * (elast_cell_volume<D>(conn, xv, t.c).vol * (1.0 / (D + 1)));
   }
   const double asv = a * sv;
   const int64_t n_dof = n_rows * D;
@@ -61,10 +54,8 @@ __global__ __launch_bounds__(EB) void k_elast_body_T(int64_t n_cell, int64_t n_d
                                                      BodyForces bf, double a, double* __restrict__ y, int accumulate) {
   const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (c >= n_cell) return;
-  int32_t v[D + 1];
-  double p[D + 1][D];
-  load_cell<D>(conn, xv, c, v, p);
-  const double vol = simplex_volume<D>(p) * (1.0 / (D + 1));
+  const ElastCellVolume<D> K = elast_cell_volume<D>(conn, xv, c);
+  const double vol = K.vol * (1.0 / (D + 1));
   double acc = 0.0;
   for (int l = 0; l < n_cols; ++l) {
     const double* __restrict__ xl = x + (int64_t)l * n_dof;
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(EB) void k_elast_body_T(int64_t n_cell, int64_t n_d
     for (int i = 0; i < D; ++i) {
       double sx = 0.0;
 #pragma unroll
-      for (int b = 0; b <= D; ++b) sx += xl[(int64_t)v[b] * D + i];
+      for (int b = 0; b <= D; ++b) sx += xl[(int64_t)K.v[b] * D + i];
       t += bf.v[l][i] * sx;
     }
     acc += t;
@@ -82,19 +73,15 @@ __global__ __launch_bounds__(EB) void k_elast_body_T(int64_t n_cell, int64_t n_d
   y[c] = accumulate ? y[c] + val : val;
 }
 
-template <int D>
 int body_launch(femo_elast* e, int n_cols, const BodyForces& bf, int transpose, double a, const double* x, const double* base,
                 const uint8_t* fixed, double* y, int accumulate) {
   femo_mesh* m = e->mesh;
-  hipStream_t st = m->ctx->stream;
-  if (transpose)
-    hipLaunchKernelGGL(k_elast_body_T<D>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->n_vert * D, m->d_conn, m->d_x,
-                       x, n_cols, bf, a, y, accumulate);
-  else
-    hipLaunchKernelGGL(k_elast_body_N<D>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell,
-                       m->d_conn, m->d_x, x, n_cols, bf, a, base, fixed, y, accumulate);
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  return elast_dispatch_d(e->d, [&](auto dim) {
+    constexpr int D = decltype(dim)::value;
+    if (transpose) return elast_launch_cells(e, k_elast_body_T<D>, m->n_vert * D, m->d_conn, m->d_x, x, n_cols, bf, a, y, accumulate);
+    return elast_launch_rows(e, k_elast_body_N<D>, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, x, n_cols, bf, a, base, fixed, y,
+                             accumulate);
+  });
 }
 
 }  // namespace
@@ -120,6 +107,5 @@ extern "C" int femo_elast_body_apply(femo_elast* e, int n_cols, const double* b,
   femo_vec_touch(y);
   const uint8_t* fx = zero_fixed ? e->d_fixed : nullptr;
   const double* bs = base ? base->d : nullptr;
-  return e->d == 2 ? body_launch<2>(e, n_cols, bf, transpose, a, x->d, bs, fx, y->d, accumulate)
-                   : body_launch<3>(e, n_cols, bf, transpose, a, x->d, bs, fx, y->d, accumulate);
+  return body_launch(e, n_cols, bf, transpose, a, x->d, bs, fx, y->d, accumulate);
 }

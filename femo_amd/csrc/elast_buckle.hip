@@ -6,8 +6,9 @@
 //   K_G,e[(a,i),(b,j)] = delta_ij |T_e| g_a . sigma_e g_b,   g_a the barycentric gradients
 //
 // Layout as in elast_solve.hip: column l at l * n_dof.  K_G is never stored: the product walks the cells around a vertex row
-// like k_elast_mass, and reads the cell stress from a buffer of the handle that femo_elast_geom_stress fills once per
-// solve, so the product touches neither u nor rho.  No float atomics: one writer per dof and per cell; the cells around a
+// like k_elast_mass (the shared visit walk), and reads the cell stress from a buffer of the handle that
+// femo_elast_geom_stress fills once per solve, so the product touches neither u nor rho.  No float atomics: one writer per
+// dof and per cell; the cells around a
 // vertex, the columns and the modes are summed in a fixed order, so every call gives the same bits, and a column of the
 // product does not depend on how many columns travel with it.
 //
@@ -34,24 +35,6 @@ struct ModeWeights { double w1[EMC], w2[EMC]; };
 template <int D>
 __device__ __forceinline__ constexpr int sym_at(int i, int k) {
   return i == k ? i : (D == 2 ? 2 : (i + k + 2));
-}
-
-// Gu[i][k] = d x_i / d x_k of the P1 field x in a cell
-template <int D>
-__device__ __forceinline__ void cell_gradient(const double (&g)[D + 1][D], const int32_t (&v)[D + 1],
-                                              const double* __restrict__ x, double (&Gu)[D][D]) {
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int k = 0; k < D; ++k) Gu[i][k] = 0.0;
-#pragma unroll
-  for (int b = 0; b <= D; ++b)
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      const double xb = x[(int64_t)v[b] * D + i];
-#pragma unroll
-      for (int k = 0; k < D; ++k) Gu[i][k] += xb * g[b][k];
-    }
 }
 
 // sigma_0 = lam tr(eps) I + 2 mu eps of the gradient Gu
@@ -89,11 +72,9 @@ __global__ __launch_bounds__(EB) void k_elast_cell_stress(int64_t n_cell, const 
                                                           double* __restrict__ sig) {
   const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (c >= n_cell) return;
-  int32_t v[D + 1];
-  double p[D + 1][D], g[D + 1][D], vol, Gu[D][D], s[D][D];
-  load_cell<D>(conn, xv, c, v, p);
-  simplex_grads<D>(p, g, vol);
-  cell_gradient<D>(g, v, u, Gu);
+  const ElastCell<D> K = elast_cell<D>(conn, xv, c);
+  double Gu[D][D], s[D][D];
+  cell_gradient<D>(K.g, K.v, u, Gu);
   solid_stress<D>(Gu, lam, mu, s);
   const double C = penal(method, rho[c]);
 #pragma unroll
@@ -103,7 +84,7 @@ __global__ __launch_bounds__(EB) void k_elast_cell_stress(int64_t n_cell, const 
 }
 
 // ------------------------------------------------------------------------------------- geometric stiffness ----
-// One thread per vertex row, the visit walk of k_elast_mass.  A visit of cell c as its vertex a adds, per column and
+// One thread per vertex row on the shared visit walk (elast_visits).  A visit of cell c as its vertex a adds, per column and
 // component i, |T_c| sum_k (sigma_c g_a)_k d_k x_i = sum_b w_b x_i[v_b] with w_b = |T_c| (sigma_c g_a) . g_b; y = a * that.
 // MASKED: fixed entries of x read as 0 and fixed entries of y are 0.  The geometry, the stress, the weights and the fixed
 // bytes of a visit (one bit per dof of the cell) serve all columns.
@@ -114,46 +95,40 @@ __global__ __launch_bounds__(EB) void k_elast_geom(
     const uint8_t* __restrict__ fixed, int n_cols, double a, const double* __restrict__ x, double* __restrict__ y) {
   const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (row >= n_rows) return;
-  const int64_t slice = row >> 6;
-  const int lane = (int)(row & 63);
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
   const int64_t n_dof = n_rows * D;
   double acc[EMC][D];
 #pragma unroll
   for (int l = 0; l < EMC; ++l)
 #pragma unroll
     for (int i = 0; i < D; ++i) acc[l][i] = 0.0;
-  for (int s = 0; s < nvis; ++s) {
-    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
-    if (ca < 0) continue;
-    const int64_t c = ca >> 2;
-    const int va = ca & 3;
-    int32_t v[D + 1];
+  const ElastVisits V = elast_visits(row, vptr);
+  for (int s = 0; s < V.n; ++s) {
+    const ElastVisit vis = elast_visit(V, visit_cell, s);
+    if (!vis.live) continue;
+    const int64_t c = vis.c;
+    const int va = vis.a;
+    const ElastCell<D> K = elast_cell<D>(conn, xv, c);
     double w[D + 1];
     {
-      double p[D + 1][D], g[D + 1][D], vol, t[D];
-      load_cell<D>(conn, xv, c, v, p);
-      simplex_grads<D>(p, g, vol);
-      double ga[D];
+      double t[D], ga[D];
 #pragma unroll
       for (int k = 0; k < D; ++k) {
         ga[k] = 0.0;
 #pragma unroll
-        for (int b = 0; b <= D; ++b) ga[k] = b == va ? g[b][k] : ga[k];
+        for (int b = 0; b <= D; ++b) ga[k] = b == va ? K.g[b][k] : ga[k];
       }
 #pragma unroll
       for (int k = 0; k < D; ++k) {
         double tk = 0.0;
 #pragma unroll
         for (int m = 0; m < D; ++m) tk += sig[(int64_t)sym_at<D>(k < m ? k : m, k < m ? m : k) * n_cell + c] * ga[m];
-        t[k] = vol * tk;
+        t[k] = K.vol * tk;
       }
 #pragma unroll
       for (int b = 0; b <= D; ++b) {
         double wb = 0.0;
 #pragma unroll
-        for (int k = 0; k < D; ++k) wb += t[k] * g[b][k];
+        for (int k = 0; k < D; ++k) wb += t[k] * K.g[b][k];
         w[b] = wb;
       }
     }
@@ -162,7 +137,7 @@ __global__ __launch_bounds__(EB) void k_elast_geom(
 #pragma unroll
       for (int b = 0; b <= D; ++b)
 #pragma unroll
-        for (int i = 0; i < D; ++i) fx |= fixed[(int64_t)v[b] * D + i] ? 1u << (b * D + i) : 0u;
+        for (int i = 0; i < D; ++i) fx |= fixed[(int64_t)K.v[b] * D + i] ? 1u << (b * D + i) : 0u;
     }
 #pragma unroll
     for (int l = 0; l < EMC; ++l) {
@@ -173,7 +148,7 @@ __global__ __launch_bounds__(EB) void k_elast_geom(
         double sx = 0.0;
 #pragma unroll
         for (int b = 0; b <= D; ++b) {
-          const double t = xl[(int64_t)v[b] * D + i];                 // loaded whatever the mask says: a select, no branch
+          const double t = xl[(int64_t)K.v[b] * D + i];               // loaded whatever the mask says: a select, no branch
           sx += w[b] * ((fx >> (b * D + i)) & 1u ? 0.0 : t);
         }
         acc[l][i] += sx;
@@ -201,23 +176,18 @@ __global__ __launch_bounds__(EB) void k_elast_buckle_du(
     ModeWeights mw, const double* __restrict__ phi, double* __restrict__ out) {
   const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (row >= n_rows) return;
-  const int64_t slice = row >> 6;
-  const int lane = (int)(row & 63);
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
   const int64_t n_dof = n_rows * D;
   double acc[D];
 #pragma unroll
   for (int j = 0; j < D; ++j) acc[j] = 0.0;
-  for (int s = 0; s < nvis; ++s) {
-    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
-    if (ca < 0) continue;
-    const int64_t c = ca >> 2;
-    const int va = ca & 3;
-    int32_t v[D + 1];
-    double p[D + 1][D], g[D + 1][D], vol, H[D][D];
-    load_cell<D>(conn, xv, c, v, p);
-    simplex_grads<D>(p, g, vol);
+  const ElastVisits V = elast_visits(row, vptr);
+  for (int s = 0; s < V.n; ++s) {
+    const ElastVisit vis = elast_visit(V, visit_cell, s);
+    if (!vis.live) continue;
+    const int64_t c = vis.c;
+    const int va = vis.a;
+    const ElastCell<D> K = elast_cell<D>(conn, xv, c);
+    double H[D][D];
 #pragma unroll
     for (int k = 0; k < D; ++k)
 #pragma unroll
@@ -225,13 +195,13 @@ __global__ __launch_bounds__(EB) void k_elast_buckle_du(
 #pragma unroll 1
     for (int k = 0; k < n_modes; ++k) {
       double G[D][D];
-      cell_gradient<D>(g, v, phi + (int64_t)k * n_dof, G);
+      cell_gradient<D>(K.g, K.v, phi + (int64_t)k * n_dof, G);
       add_gram<D>(G, mw.w1[k], H);
     }
     double tr = 0.0;
 #pragma unroll
     for (int k = 0; k < D; ++k) tr += H[k][k];
-    const double cw = penal(method, rho[c]) * vol;
+    const double cw = penal(method, rho[c]) * K.vol;
 #pragma unroll
     for (int j = 0; j < D; ++j) {
       double t = 0.0;
@@ -239,7 +209,7 @@ __global__ __launch_bounds__(EB) void k_elast_buckle_du(
       for (int m = 0; m < D; ++m) {
         double gam = 0.0;
 #pragma unroll
-        for (int b = 0; b <= D; ++b) gam = b == va ? g[b][m] : gam;
+        for (int b = 0; b <= D; ++b) gam = b == va ? K.g[b][m] : gam;
         t += (2.0 * mu * H[j][m] + (j == m ? lam * tr : 0.0)) * gam;
       }
       acc[j] += cw * t;
@@ -252,7 +222,8 @@ __global__ __launch_bounds__(EB) void k_elast_buckle_du(
 // ------------------------------------------------------------------------------------- d lambda / d rho ----
 // One thread per cell, the modes in ascending order:
 //   y_c (+)= C'(rho_c) |T_c| sum_k [ w1_k (lam0 (div phi_k)^2 + 2 mu0 eps(phi_k) : eps(phi_k)) + w2_k sigma_0(u_c) : H_c(phi_k) ]
-// The first bracket is the arithmetic of k_elast_eig_drho.
+// The first bracket is the arithmetic of elastic_form (elast_internal.h) in a text of its own: through the helper the 3-D
+// kernel goes from 94 to 78 registers and from 5 to 6 waves, which is not the code object it was (DESIGN_LOG.md R26).
 template <int D>
 __global__ __launch_bounds__(EB) void k_elast_buckle_drho(int64_t n_cell, int64_t n_dof, const int32_t* __restrict__ conn,
                                                           const double* __restrict__ xv, const double* __restrict__ rho,
@@ -261,18 +232,16 @@ __global__ __launch_bounds__(EB) void k_elast_buckle_drho(int64_t n_cell, int64_
                                                           double* __restrict__ y, int accumulate) {
   const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (c >= n_cell) return;
-  int32_t v[D + 1];
-  double p[D + 1][D], g[D + 1][D], vol, Gu[D][D], s0[D][D];
-  load_cell<D>(conn, xv, c, v, p);
-  simplex_grads<D>(p, g, vol);
-  cell_gradient<D>(g, v, u, Gu);
+  const ElastCell<D> K = elast_cell<D>(conn, xv, c);
+  double Gu[D][D], s0[D][D];
+  cell_gradient<D>(K.g, K.v, u, Gu);
   solid_stress<D>(Gu, lam, mu, s0);
-  const double dC = penal_d(method, rho[c]) * vol;
+  const double dC = penal_d(method, rho[c]) * K.vol;
   double acc = 0.0;
 #pragma unroll 1
   for (int k = 0; k < n_modes; ++k) {
     double G[D][D];
-    cell_gradient<D>(g, v, phi + (int64_t)k * n_dof, G);
+    cell_gradient<D>(K.g, K.v, phi + (int64_t)k * n_dof, G);
     double div = 0.0, ee = 0.0, sh = 0.0;
 #pragma unroll
     for (int i = 0; i < D; ++i) div += G[i][i];
@@ -298,28 +267,22 @@ __global__ __launch_bounds__(EB) void k_elast_buckle_drho(int64_t n_cell, int64_
 int stress_launch(femo_elast* e, int method, const double* rho, const double* u) {
   femo_mesh* m = e->mesh;
   if (!e->w_gstress) FEMO_TRY(dalloc(&e->w_gstress, (int64_t)(e->d * (e->d + 1) / 2) * m->n_cell));
-  hipStream_t st = m->ctx->stream;
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_elast_cell_stress<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho, method,
-                       e->lam0, e->mu0, u, e->w_gstress);
-  else
-    hipLaunchKernelGGL(k_elast_cell_stress<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho, method,
-                       e->lam0, e->mu0, u, e->w_gstress);
-  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_TRY(elast_dispatch_d(e->d, [&](auto dim) {
+    return elast_launch_cells(e, k_elast_cell_stress<decltype(dim)::value>, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u,
+                              e->w_gstress);
+  }));
   e->has_gstress = true;
   return 0;
 }
 
 int geom_launch(femo_elast* e, bool masked, int n_cols, double a, const double* x, double* y) {
   femo_mesh* m = e->mesh;
-  hipStream_t st = m->ctx->stream;
-#define FEMO_GEOM(D, MK) hipLaunchKernelGGL((k_elast_geom<D, MK>), dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->n_cell, \
-                                            m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, e->w_gstress, e->d_fixed, n_cols, a, x, y)
-  if (e->d == 2) { if (masked) FEMO_GEOM(2, true); else FEMO_GEOM(2, false); }
-  else { if (masked) FEMO_GEOM(3, true); else FEMO_GEOM(3, false); }
-#undef FEMO_GEOM
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  int rc = 0;
+  elast_dispatch(e->d, masked, [&](auto dim, auto mask) {
+    rc = elast_launch_rows(e, k_elast_geom<decltype(dim)::value, decltype(mask)::value>, m->n_cell, m->d_vptr, m->d_visit_cell,
+                           m->d_conn, m->d_x, e->w_gstress, e->d_fixed, n_cols, a, x, y);
+  });
+  return rc;
 }
 
 }  // namespace
@@ -375,15 +338,10 @@ int femo_elast_buckle_du(femo_elast* e, int method, int n_modes, const femo_vec*
   for (int k = 0; k < EMC; ++k) { mw.w1[k] = k < n_modes ? w[k] : 0.0; mw.w2[k] = 0.0; }
   FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(phi));
   femo_vec_touch(out);
-  hipStream_t st = m->ctx->stream;
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_elast_buckle_du<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn,
-                       m->d_x, rho->d, method, e->lam0, e->mu0, n_modes, mw, phi->d, out->d);
-  else
-    hipLaunchKernelGGL(k_elast_buckle_du<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn,
-                       m->d_x, rho->d, method, e->lam0, e->mu0, n_modes, mw, phi->d, out->d);
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  return elast_dispatch_d(e->d, [&](auto dim) {
+    return elast_launch_rows(e, k_elast_buckle_du<decltype(dim)::value>, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho->d,
+                             method, e->lam0, e->mu0, n_modes, mw, phi->d, out->d);
+  });
 }
 
 int femo_elast_buckle_drho(femo_elast* e, int method, int n_modes, const femo_vec* rho, const femo_vec* u, const femo_vec* phi,
@@ -400,15 +358,10 @@ int femo_elast_buckle_drho(femo_elast* e, int method, int n_modes, const femo_ve
   for (int k = 0; k < EMC; ++k) { mw.w1[k] = k < n_modes ? w1[k] : 0.0; mw.w2[k] = k < n_modes ? w2[k] : 0.0; }
   FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(phi));
   femo_vec_touch(y);
-  hipStream_t st = m->ctx->stream;
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_elast_buckle_drho<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, n, m->d_conn, m->d_x, rho->d, method,
-                       e->lam0, e->mu0, n_modes, mw, u->d, phi->d, y->d, accumulate);
-  else
-    hipLaunchKernelGGL(k_elast_buckle_drho<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, n, m->d_conn, m->d_x, rho->d, method,
-                       e->lam0, e->mu0, n_modes, mw, u->d, phi->d, y->d, accumulate);
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  return elast_dispatch_d(e->d, [&](auto dim) {
+    return elast_launch_cells(e, k_elast_buckle_drho<decltype(dim)::value>, n, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0,
+                              n_modes, mw, u->d, phi->d, y->d, accumulate);
+  });
 }
 
 int femo_elast_buckle(femo_elast* e, int method, const femo_vec* rho, const femo_vec* u, int n_modes, int block, femo_vec* X,

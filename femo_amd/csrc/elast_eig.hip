@@ -5,9 +5,9 @@
 //   m = rho (linear) or Du & Olhoff's law: rho for rho >= 0.1, 6e5 rho^6 - 5e6 rho^7 below (C^1 at 0.1)
 //
 // Layout as in elast_solve.hip: column l at l * n_dof.  The mass matrix is never stored: the product walks the cells around
-// a vertex row like k_elast_body_N.  No float atomics: one writer per dof and per cell; the cells around a vertex and the
-// columns are summed in a fixed order, so every call gives the same bits, and a column of the mass product does not depend
-// on how many columns travel with it.
+// a vertex row on the shared visit walk (elast_internal.h).  No float atomics: one writer per dof and per cell; the cells
+// around a vertex and the columns are summed in a fixed order, so every call gives the same bits, and a column of the mass
+// product does not depend on how many columns travel with it.
 //
 // femo_elast_eigs is the block iteration of elast_block.hip on the pencil K phi = lambda M phi: the operator product is
 // M_ff (k_elast_mass, one launch for the block), which is also the positive definite side, so the modes come back
@@ -26,9 +26,10 @@ constexpr int EMC = FEMO_ELAST_MAX_COLS;
 struct ModeScalars { double lam[EMC], c[EMC]; };
 
 // ------------------------------------------------------------------------------------------- mass product ----
-// One thread per vertex row, the visit walk of k_elast_body_N.  A visit of cell c as its vertex a adds, per column and
-// component, w_c (sum_b x[v_b] + x[v_a]) with w_c = rho0 m(rho_c) |T_c| / ((d+1)(d+2)); y = a * that.  MASKED: fixed entries
-// of x read as 0 and fixed entries of y are 0.  The geometry and the fixed bytes of a visit serve all columns.
+// One thread per vertex row on the shared visit walk (elast_visits).  A visit of cell c as its vertex a adds, per column and
+// component, w_c (sum_b x[v_b] + x[v_a]) with w_c = rho0 m(rho_c) |T_c| / ((d+1)(d+2)) (mass_row_add, mass_weight);
+// y = a * that.  MASKED: fixed entries of x read as 0 and fixed entries of y are 0.  The geometry and the fixed bytes of a
+// visit serve all columns.
 template <int D, bool MASKED>
 __global__ __launch_bounds__(EB) void k_elast_mass(
     int64_t n_rows, const int64_t* __restrict__ vptr, const int32_t* __restrict__ visit_cell, const int32_t* __restrict__ conn,
@@ -36,46 +37,18 @@ __global__ __launch_bounds__(EB) void k_elast_mass(
     int n_cols, double a, const double* __restrict__ x, double* __restrict__ y) {
   const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (row >= n_rows) return;
-  const int64_t slice = row >> 6;
-  const int lane = (int)(row & 63);
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
   const int64_t n_dof = n_rows * D;
   double acc[EMC][D];
 #pragma unroll
   for (int l = 0; l < EMC; ++l)
 #pragma unroll
     for (int i = 0; i < D; ++i) acc[l][i] = 0.0;
-  for (int s = 0; s < nvis; ++s) {
-    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
-    if (ca < 0) continue;
-    const int64_t c = ca >> 2;
-    const int va = ca & 3;
-    int32_t v[D + 1];
-    double p[D + 1][D];
-    load_cell<D>(conn, xv, c, v, p);
-    const double w = rho0 * mass_law(law, rho[c]) * (simplex_volume<D>(p) * (1.0 / ((D + 1) * (D + 2))));
-    bool fx[D + 1][D];
-#pragma unroll
-    for (int b = 0; b <= D; ++b)
-#pragma unroll
-      for (int i = 0; i < D; ++i) fx[b][i] = MASKED && fixed[(int64_t)v[b] * D + i];
-#pragma unroll
-    for (int l = 0; l < EMC; ++l) {
-      if (l >= n_cols) break;
-      const double* __restrict__ xl = x + (int64_t)l * n_dof;
-#pragma unroll
-      for (int i = 0; i < D; ++i) {
-        double sx = 0.0, own = 0.0;
-#pragma unroll
-        for (int b = 0; b <= D; ++b) {
-          const double t = fx[b][i] ? 0.0 : xl[(int64_t)v[b] * D + i];
-          sx += t;
-          if (b == va) own = t;
-        }
-        acc[l][i] += w * (sx + own);
-      }
-    }
+  const ElastVisits V = elast_visits(row, vptr);
+  for (int s = 0; s < V.n; ++s) {
+    const ElastVisit t = elast_visit(V, visit_cell, s);
+    if (!t.live) continue;
+    const ElastCellVolume<D> K = elast_cell_volume<D>(conn, xv, t.c);
+    mass_row_add<D, MASKED>(K.v, t.a, mass_weight<D>(rho0 * mass_law(law, rho[t.c]), K.vol), fixed, n_cols, n_dof, x, acc);
   }
 #pragma unroll
   for (int l = 0; l < EMC; ++l) {
@@ -98,43 +71,32 @@ __global__ __launch_bounds__(EB) void k_elast_eig_drho(int64_t n_cell, int64_t n
                                                        const double* __restrict__ phi, double* __restrict__ y, int accumulate) {
   const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (c >= n_cell) return;
-  int32_t v[D + 1];
-  double p[D + 1][D], g[D + 1][D], vol;
-  load_cell<D>(conn, xv, c, v, p);
-  simplex_grads<D>(p, g, vol);
+  const ElastCell<D> K = elast_cell<D>(conn, xv, c);
   const double r = rho[c];
-  const double dC = penal_d(method, r) * vol;
-  const double dM = rho0 * mass_law_d(law, r) * (vol * (1.0 / ((D + 1) * (D + 2))));
+  const double dC = penal_d(method, r) * K.vol;
+  const double dM = mass_weight<D>(rho0 * mass_law_d(law, r), K.vol);
   double acc = 0.0;
 #pragma unroll
   for (int k = 0; k < EMC; ++k) {
     if (k >= n_modes) break;
     const double* __restrict__ u = phi + (int64_t)k * n_dof;
     double Gu[D][D], su[D], qu = 0.0;
+    cell_gradient<D>(K.g, K.v, u, Gu);
+    // the mass part sums qu + sum_i su_i^2: not the order of k_elast_mass_drho_T
 #pragma unroll
-    for (int i = 0; i < D; ++i) {
-      su[i] = 0.0;
-#pragma unroll
-      for (int j = 0; j < D; ++j) Gu[i][j] = 0.0;
-    }
+    for (int i = 0; i < D; ++i) su[i] = 0.0;
 #pragma unroll
     for (int b = 0; b <= D; ++b)
 #pragma unroll
       for (int i = 0; i < D; ++i) {
-        const double ub = u[(int64_t)v[b] * D + i];
+        const double ub = u[(int64_t)K.v[b] * D + i];
         su[i] += ub;
         qu += ub * ub;
-#pragma unroll
-        for (int j = 0; j < D; ++j) Gu[i][j] += ub * g[b][j];
       }
-    double div = 0.0, ee = 0.0, mm = qu;
+    double mm = qu;
 #pragma unroll
-    for (int i = 0; i < D; ++i) { div += Gu[i][i]; mm += su[i] * su[i]; }
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-      for (int j = 0; j < D; ++j) { const double t = Gu[i][j] + Gu[j][i]; ee += 0.25 * t * t; }
-    acc += ms.c[k] * (dC * (lam * div * div + 2.0 * mu * ee) - ms.lam[k] * (dM * mm));
+    for (int i = 0; i < D; ++i) mm += su[i] * su[i];
+    acc += ms.c[k] * (dC * elastic_form<D>(Gu, Gu, lam, mu) - ms.lam[k] * (dM * mm));
   }
   y[c] = accumulate ? y[c] + acc : acc;
 }
@@ -143,14 +105,12 @@ __global__ __launch_bounds__(EB) void k_elast_eig_drho(int64_t n_cell, int64_t n
 int mass_launch(femo_elast* e, int law, double rho0, bool masked, int n_cols, double a, const double* rho, const double* x,
                 double* y) {
   femo_mesh* m = e->mesh;
-  hipStream_t st = m->ctx->stream;
-#define FEMO_MASS(D, MK) hipLaunchKernelGGL((k_elast_mass<D, MK>), dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, \
-                                            m->d_visit_cell, m->d_conn, m->d_x, rho, law, rho0, e->d_fixed, n_cols, a, x, y)
-  if (e->d == 2) { if (masked) FEMO_MASS(2, true); else FEMO_MASS(2, false); }
-  else { if (masked) FEMO_MASS(3, true); else FEMO_MASS(3, false); }
-#undef FEMO_MASS
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  int rc = 0;
+  elast_dispatch(e->d, masked, [&](auto dim, auto mask) {
+    rc = elast_launch_rows(e, k_elast_mass<decltype(dim)::value, decltype(mask)::value>, m->d_vptr, m->d_visit_cell, m->d_conn,
+                           m->d_x, rho, law, rho0, e->d_fixed, n_cols, a, x, y);
+  });
+  return rc;
 }
 
 }  // namespace
@@ -189,15 +149,10 @@ int femo_elast_eig_drho(femo_elast* e, int method, int mass_law, double density,
   for (int k = 0; k < EMC; ++k) { ms.lam[k] = k < n_modes ? lambda[k] : 0.0; ms.c[k] = k < n_modes ? c[k] : 0.0; }
   FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(phi));
   femo_vec_touch(y);
-  hipStream_t st = m->ctx->stream;
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_elast_eig_drho<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, n, m->d_conn, m->d_x, rho->d, method,
-                       mass_law, density, e->lam0, e->mu0, n_modes, ms, phi->d, y->d, accumulate);
-  else
-    hipLaunchKernelGGL(k_elast_eig_drho<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, n, m->d_conn, m->d_x, rho->d, method,
-                       mass_law, density, e->lam0, e->mu0, n_modes, ms, phi->d, y->d, accumulate);
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  return elast_dispatch_d(e->d, [&](auto dim) {
+    return elast_launch_cells(e, k_elast_eig_drho<decltype(dim)::value>, n, m->d_conn, m->d_x, rho->d, method, mass_law, density,
+                              e->lam0, e->mu0, n_modes, ms, phi->d, y->d, accumulate);
+  });
 }
 
 int femo_elast_eigs(femo_elast* e, int mass_law, double density, const femo_vec* rho, int n_modes, int block, femo_vec* X,

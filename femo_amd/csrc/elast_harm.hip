@@ -57,7 +57,7 @@ enum { MS_BETA1 = 0, MS_BETA, MS_OLDB, MS_ALFA, MS_DBAR, MS_EPSLN, MS_OLDEPS, MS
 constexpr int MS_STRIDE = FEMO_ELAST_HARM_SCALARS;
 
 // ---------------------------------------------------------------------------------------------- mass assembly ----
-// One thread per vertex row, the visit walk of k_elast_assemble.  A visit of cell c as its vertex a adds
+// One thread per vertex row on the shared visit walk (elast_visits), as k_elast_assemble.  A visit of cell c as its vertex a adds
 // w_c = rho0 m(rho_c) |T_c| / ((d+1)(d+2)) to the entries (a, b), b != a, and 2 w_c to the diagonal.
 template <int D>
 __global__ __launch_bounds__(EB) void k_elast_mass_assemble(
@@ -73,23 +73,16 @@ __global__ __launch_bounds__(EB) void k_elast_mass_assemble(
   const int len = rowlen[row];
   for (int k = 0; k < len; ++k) mvals[femo_sell_index(mb, k, lane)] = 0.0;
   double dg = 0.0;
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
-  for (int s = 0; s < nvis; ++s) {
-    const int64_t vi = vb + (int64_t)s * 64 + lane;
-    const int32_t ca = visit_cell[vi];
-    if (ca < 0) continue;
-    const uint32_t sl = visit_slots[vi];
-    const int64_t c = ca >> 2;
-    const int a = ca & 3;
-    int32_t v[D + 1];
-    double p[D + 1][D];
-    load_cell<D>(conn, x, c, v, p);
-    const double w = rho0 * mass_law(law, rho[c]) * (simplex_volume<D>(p) * (1.0 / ((D + 1) * (D + 2))));
+  const ElastVisits V = elast_visits(row, vptr);
+  for (int s = 0; s < V.n; ++s) {
+    const ElastVisit t = elast_visit(V, visit_cell, s);
+    if (!t.live) continue;
+    const uint32_t sl = visit_slots[t.vi];
+    const double w = mass_weight<D>(rho0 * mass_law(law, rho[t.c]), elast_cell_volume<D>(conn, x, t.c).vol);
 #pragma unroll
     for (int b = 0; b <= D; ++b) {
-      if (b == a) dg += w + w;
-      else mvals[femo_sell_index(mb, slot_pos(sl, a, b), lane)] += w;
+      if (b == t.a) dg += w + w;
+      else mvals[femo_sell_index(mb, slot_pos(sl, t.a, b), lane)] += w;
     }
   }
   mdiag[row] = dg;
@@ -348,21 +341,19 @@ __global__ __launch_bounds__(EB) void k_elast_mass_drho_T(int64_t n_cell, int64_
                                                           const double* __restrict__ x, double* __restrict__ y, int accumulate) {
   const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (c >= n_cell) return;
-  int32_t v[D + 1];
-  double p[D + 1][D];
-  load_cell<D>(conn, xv, c, v, p);
-  const double dM = rho0 * mass_law_d(law, rho[c]) * (simplex_volume<D>(p) * (1.0 / ((D + 1) * (D + 2))));
+  const ElastCellVolume<D> K = elast_cell_volume<D>(conn, xv, c);
+  const double dM = mass_weight<D>(rho0 * mass_law_d(law, rho[c]), K.vol);
   double acc = 0.0;
   for (int l = 0; l < n_cols; ++l) {
     const double* __restrict__ ul = u + (int64_t)l * n_dof;
     const double* __restrict__ xl = x + (int64_t)l * n_dof;
-    double mm = 0.0;
+    double mm = 0.0;         // sum_i (sx su + xu): not the order of the mass part of k_elast_eig_drho
 #pragma unroll
     for (int i = 0; i < D; ++i) {
       double su = 0.0, sx = 0.0, xu = 0.0;
 #pragma unroll
       for (int b = 0; b <= D; ++b) {
-        const double ub = ul[(int64_t)v[b] * D + i], xb = xl[(int64_t)v[b] * D + i];
+        const double ub = ul[(int64_t)K.v[b] * D + i], xb = xl[(int64_t)K.v[b] * D + i];
         su += ub; sx += xb; xu += xb * ub;
       }
       mm += sx * su + xu;
@@ -373,7 +364,8 @@ __global__ __launch_bounds__(EB) void k_elast_mass_drho_T(int64_t n_cell, int64_
 }
 
 // fwd: y_l[(v, i)] (+)= s_l sum over the cells c around v of rho0 m'(rho_c) dr_c (M0_c u_{l,c})[(v, i)]; one thread per vertex
-// row, the visit walk of k_elast_body_N, the geometry of a visit serving all columns
+// row on the shared visit walk (elast_visits) with the mass row of k_elast_mass (mass_row_add), the geometry of a visit
+// serving all columns
 template <int D>
 __global__ __launch_bounds__(EB) void k_elast_mass_drho_N(
     int64_t n_rows, const int64_t* __restrict__ vptr, const int32_t* __restrict__ visit_cell, const int32_t* __restrict__ conn,
@@ -381,41 +373,19 @@ __global__ __launch_bounds__(EB) void k_elast_mass_drho_N(
     const double* __restrict__ u, const double* __restrict__ dr, double* __restrict__ y, int accumulate) {
   const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (row >= n_rows) return;
-  const int64_t slice = row >> 6;
-  const int lane = (int)(row & 63);
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
   const int64_t n_dof = n_rows * D;
   double acc[EMC][D];
 #pragma unroll
   for (int l = 0; l < EMC; ++l)
 #pragma unroll
     for (int i = 0; i < D; ++i) acc[l][i] = 0.0;
-  for (int s = 0; s < nvis; ++s) {
-    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
-    if (ca < 0) continue;
-    const int64_t c = ca >> 2;
-    const int va = ca & 3;
-    int32_t v[D + 1];
-    double p[D + 1][D];
-    load_cell<D>(conn, xv, c, v, p);
-    const double w = rho0 * mass_law_d(law, rho[c]) * dr[c] * (simplex_volume<D>(p) * (1.0 / ((D + 1) * (D + 2))));
-#pragma unroll
-    for (int l = 0; l < EMC; ++l) {
-      if (l >= n_cols) break;
-      const double* __restrict__ ul = u + (int64_t)l * n_dof;
-#pragma unroll
-      for (int i = 0; i < D; ++i) {
-        double su = 0.0, own = 0.0;
-#pragma unroll
-        for (int b = 0; b <= D; ++b) {
-          const double t = ul[(int64_t)v[b] * D + i];
-          su += t;
-          if (b == va) own = t;
-        }
-        acc[l][i] += w * (su + own);
-      }
-    }
+  const ElastVisits V = elast_visits(row, vptr);
+  for (int s = 0; s < V.n; ++s) {
+    const ElastVisit t = elast_visit(V, visit_cell, s);
+    if (!t.live) continue;
+    const ElastCellVolume<D> K = elast_cell_volume<D>(conn, xv, t.c);
+    mass_row_add<D, false>(K.v, t.a, mass_weight<D>(rho0 * mass_law_d(law, rho[t.c]) * dr[t.c], K.vol), nullptr, n_cols, n_dof, u,
+                           acc);
   }
 #pragma unroll
   for (int l = 0; l < EMC; ++l) {
@@ -555,13 +525,10 @@ int femo_elast_mass_assemble(femo_elast* e, int mass_law, double density, const 
     e->d_mvals = mv; e->d_mdiag = md;
   }
   FEMO_TRY(femo_vec_await(rho));
-  hipStream_t st = m->ctx->stream;
-#define FEMO_MASS_ASM(D) hipLaunchKernelGGL(k_elast_mass_assemble<D>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, \
-                                            m->d_visit_cell, m->d_visit_slots, m->d_mptr, m->d_rowlen, m->d_conn, m->d_x, rho->d,      \
-                                            mass_law, density, e->d_mvals, e->d_mdiag)
-  if (e->d == 2) FEMO_MASS_ASM(2); else FEMO_MASS_ASM(3);
-#undef FEMO_MASS_ASM
-  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_TRY(elast_dispatch_d(e->d, [&](auto dim) {
+    return elast_launch_rows(e, k_elast_mass_assemble<decltype(dim)::value>, m->d_vptr, m->d_visit_cell, m->d_visit_slots, m->d_mptr,
+                             m->d_rowlen, m->d_conn, m->d_x, rho->d, mass_law, density, e->d_mvals, e->d_mdiag);
+  }));
   e->mass_assembled = true;
   return 0;
 }
@@ -614,21 +581,14 @@ int femo_elast_mass_drho_multi(femo_elast* e, int mass_law, double density, int 
   for (int l = 0; l < EMC; ++l) sc.v[l] = l < n_cols ? scales[l] : 0.0;
   FEMO_TRY(femo_vec_await(rho)); FEMO_TRY(femo_vec_await(u)); FEMO_TRY(femo_vec_await(x));
   femo_vec_touch(y);
-  hipStream_t st = m->ctx->stream;
-  if (transpose) {
-#define FEMO_MDRHO_T(D) hipLaunchKernelGGL(k_elast_mass_drho_T<D>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, n, m->d_conn, \
-                                           m->d_x, rho->d, mass_law, density, n_cols, sc, u->d, x->d, y->d, accumulate)
-    if (e->d == 2) FEMO_MDRHO_T(2); else FEMO_MDRHO_T(3);
-#undef FEMO_MDRHO_T
-  } else {
-#define FEMO_MDRHO_N(D) hipLaunchKernelGGL(k_elast_mass_drho_N<D>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr,    \
-                                           m->d_visit_cell, m->d_conn, m->d_x, rho->d, mass_law, density, n_cols, sc, u->d, x->d, y->d, \
-                                           accumulate)
-    if (e->d == 2) FEMO_MDRHO_N(2); else FEMO_MDRHO_N(3);
-#undef FEMO_MDRHO_N
-  }
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  return elast_dispatch_d(e->d, [&](auto dim) {
+    constexpr int D = decltype(dim)::value;
+    if (transpose)
+      return elast_launch_cells(e, k_elast_mass_drho_T<D>, n, m->d_conn, m->d_x, rho->d, mass_law, density, n_cols, sc, u->d, x->d,
+                                y->d, accumulate);
+    return elast_launch_rows(e, k_elast_mass_drho_N<D>, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho->d, mass_law, density,
+                             n_cols, sc, u->d, x->d, y->d, accumulate);
+  });
 }
 
 }  // extern "C"

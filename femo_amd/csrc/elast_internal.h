@@ -5,7 +5,11 @@
 // pencil), elast_harm.hip (assembled mass, shifted product and MINRES of the harmonic response), elast_damp.hip (complex
 // product and COCR of the damped response) and elast_transient.hip (Newmark march, its banded product and dR/drho).  The
 // static and the banded SELL product of these units are prologues and epilogues around one row walk, elast_row_walk below;
-// all four products choose their instantiation through elast_dispatch.  Not part of the ABI.
+// all four products choose their instantiation through elast_dispatch.  The kernels that work on cells, or on the vertex ->
+// cell incidence, share their cell prologue (elast_cell, elast_cell_volume), the visit walk (for_each_visit), the
+// displacement gradient, the energy density and the consistent-mass weight and row (cell_gradient, elastic_form,
+// mass_weight, mass_row_add) and their launch path (elast_dispatch_d, elast_launch_cells, elast_launch_rows), all below.
+// Not part of the ABI.
 #pragma once
 
 #include "femo_internal.h"
@@ -113,6 +117,12 @@ inline void elast_dispatch(int d, bool masked, F&& fn) {
   }
 }
 
+// fn(std::integral_constant<int, D>) for d = 2 or 3; returns what fn returns
+template <typename F>
+inline auto elast_dispatch_d(int d, F&& fn) {
+  return d == 2 ? fn(std::integral_constant<int, 2>()) : fn(std::integral_constant<int, 3>());
+}
+
 // blocks of EB threads for n items
 inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
   int64_t g = (n + EB - 1) / EB;
@@ -120,6 +130,26 @@ inline unsigned grid_of(int64_t n, int64_t cap = 1 << 20) {
   if (g > cap) g = cap;
   return (unsigned)g;
 }
+
+#if defined(__HIPCC__)
+// kernel(n, args...) with one thread per item on the context's stream, ny blocks in the grid's second dimension
+template <typename K, typename... A>
+int elast_launch(const femo_elast* e, int64_t n, unsigned ny, K kernel, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid_of(n), ny), dim3(EB), 0, e->mesh->ctx->stream, n, args...);
+  FEMO_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+// one thread per cell: kernel(n_cell, args...)
+template <typename K, typename... A>
+int elast_launch_cells(const femo_elast* e, K kernel, A... args) {
+  return elast_launch(e, e->mesh->n_cell, 1u, kernel, args...);
+}
+// one thread per vertex row: kernel(n_rows, args...)
+template <typename K, typename... A>
+int elast_launch_rows(const femo_elast* e, K kernel, A... args) {
+  return elast_launch(e, e->mesh->n_rows, 1u, kernel, args...);
+}
+#endif
 
 // device array of n entries (at least one)
 template <typename T>
@@ -412,13 +442,76 @@ __device__ __forceinline__ void load_cell(const int32_t* __restrict__ conn, cons
   }
 }
 
-// Solid-material stress sigma_0(u) of a P1 cell as a 3 x 3 tensor (plane strain in 2-D: sigma_zz = lam tr eps, no
-// out-of-plane shear).  Its deviator does not see lam: s = 2 mu (eps - tr(eps) / 3 I), so s_zz = -2 mu tr(eps) / 3 in
-// 2-D.  Returns sigma_vm = sqrt(3/2 s : s); s holds the d x d block of the deviator.
+// A P1 cell BY VALUE (DESIGN_LOG.md R24: behind a reference the arrays would be reached through generic pointers): its
+// vertices in `conn` order, the gradients of the barycentric coordinates and |T| ...  Index g with constants only: a
+// run-time index into a member keeps the whole record from being split into registers (R26), so a kernel that reads
+// g[a] of the visit's vertex a calls load_cell and simplex_grads on arrays of its own.
 template <int D>
-__device__ __forceinline__ double cell_von_mises(const double (&g)[D + 1][D], const int32_t (&v)[D + 1],
-                                                 const double* __restrict__ u, double mu, double (&s)[D][D]) {
-  double Gu[D][D];      // Gu[i][k] = du_i/dx_k
+struct ElastCell {
+  int32_t v[D + 1];
+  double g[D + 1][D];
+  double vol;
+};
+template <int D>
+__device__ __forceinline__ ElastCell<D> elast_cell(const int32_t* __restrict__ conn, const double* __restrict__ x, int64_t c) {
+  ElastCell<D> K;
+  double p[D + 1][D];
+  load_cell<D>(conn, x, c, K.v, p);
+  simplex_grads<D>(p, K.g, K.vol);
+  return K;
+}
+// ... or its vertices and |T| alone
+template <int D>
+struct ElastCellVolume {
+  int32_t v[D + 1];
+  double vol;
+};
+template <int D>
+__device__ __forceinline__ ElastCellVolume<D> elast_cell_volume(const int32_t* __restrict__ conn, const double* __restrict__ x,
+                                                                int64_t c) {
+  ElastCellVolume<D> K;
+  double p[D + 1][D];
+  load_cell<D>(conn, x, c, K.v, p);
+  K.vol = simplex_volume<D>(p);
+  return K;
+}
+
+// The visit walk of the vertex-row kernels: the cells around vertex `row` in ascending cell order.  Visit s < n of the walk
+// is cell c as its vertex a, at index vi of visit_cell and visit_slots; the padding of a slice is not live and is skipped:
+//   const ElastVisits V = elast_visits(row, vptr);
+//   for (int s = 0; s < V.n; ++s) { const ElastVisit t = elast_visit(V, visit_cell, s); if (!t.live) continue; ... }
+// Both structs travel by value (DESIGN_LOG.md R24, R26).
+struct ElastVisits {
+  int64_t vb;
+  int lane, n;
+};
+struct ElastVisit {
+  int64_t vi, c;
+  int a;
+  bool live;
+};
+__device__ __forceinline__ ElastVisits elast_visits(int64_t row, const int64_t* __restrict__ vptr) {
+  const int64_t slice = row >> 6;
+  ElastVisits V;
+  V.lane = (int)(row & 63);
+  V.vb = vptr[slice];
+  V.n = (int)((vptr[slice + 1] - V.vb) >> 6);
+  return V;
+}
+__device__ __forceinline__ ElastVisit elast_visit(ElastVisits V, const int32_t* __restrict__ visit_cell, int s) {
+  ElastVisit t;
+  t.vi = V.vb + (int64_t)s * 64 + V.lane;
+  const int32_t ca = visit_cell[t.vi];
+  t.live = ca >= 0;
+  t.c = (int64_t)((uint32_t)ca >> 2);       // of a live visit: without the sign, as the compiler sees it behind `ca >= 0`
+  t.a = (int)(ca & 3);
+  return t;
+}
+
+// Gu[i][k] = d u_i / d x_k of the P1 field u in a cell
+template <int D>
+__device__ __forceinline__ void cell_gradient(const double (&g)[D + 1][D], const int32_t (&v)[D + 1],
+                                              const double* __restrict__ u, double (&Gu)[D][D]) {
 #pragma unroll
   for (int i = 0; i < D; ++i)
 #pragma unroll
@@ -431,6 +524,30 @@ __device__ __forceinline__ double cell_von_mises(const double (&g)[D + 1][D], co
 #pragma unroll
       for (int k = 0; k < D; ++k) Gu[i][k] += ub * g[b][k];
     }
+}
+
+// lam div(u) div(w) + 2 mu eps(u) : eps(w) of two gradients: the solid energy density, bilinear; the quadratic sites pass the
+// same gradient twice
+template <int D>
+__device__ __forceinline__ double elastic_form(const double (&Gu)[D][D], const double (&Gw)[D][D], double lam, double mu) {
+  double divu = 0.0, divw = 0.0, ee = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) { divu += Gu[i][i]; divw += Gw[i][i]; }
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) ee += 0.25 * (Gu[i][k] + Gu[k][i]) * (Gw[i][k] + Gw[k][i]);
+  return lam * divu * divw + 2.0 * mu * ee;
+}
+
+// Solid-material stress sigma_0(u) of a P1 cell as a 3 x 3 tensor (plane strain in 2-D: sigma_zz = lam tr eps, no
+// out-of-plane shear).  Its deviator does not see lam: s = 2 mu (eps - tr(eps) / 3 I), so s_zz = -2 mu tr(eps) / 3 in
+// 2-D.  Returns sigma_vm = sqrt(3/2 s : s); s holds the d x d block of the deviator.
+template <int D>
+__device__ __forceinline__ double cell_von_mises(const double (&g)[D + 1][D], const int32_t (&v)[D + 1],
+                                                 const double* __restrict__ u, double mu, double (&s)[D][D]) {
+  double Gu[D][D];
+  cell_gradient<D>(g, v, u, Gu);
   double tr = 0.0;
 #pragma unroll
   for (int i = 0; i < D; ++i) tr += Gu[i][i];
@@ -473,6 +590,41 @@ __device__ __forceinline__ double mass_law_d(int law, double r) {
   if (law == FEMO_ELAST_MASS_LINEAR || r >= 0.1) return 1.0;
   const double r2 = r * r, r5 = r2 * r2 * r;
   return 36e5 * r5 - 35e6 * (r5 * r);
+}
+
+// The weight of a cell in the consistent P1 mass: m |T| / ((d+1)(d+2)), m = rho0 m(rho) or its derivative's factors
+template <int D>
+__device__ __forceinline__ double mass_weight(double m, double vol) {
+  return m * (vol * (1.0 / ((D + 1) * (D + 2))));
+}
+
+// The P1 mass row of a visit of the cell with vertices v as its vertex va, for the n_cols first columns of x (n_dof apart):
+// acc[l][i] += w (sum_b x_l[v_b, i] + x_l[v_va, i]).  MASKED: fixed entries of x read as 0.  The fixed bytes serve all columns.
+template <int D, bool MASKED>
+__device__ __forceinline__ void mass_row_add(const int32_t (&v)[D + 1], int va, double w, const uint8_t* __restrict__ fixed,
+                                             int n_cols, int64_t n_dof, const double* __restrict__ x,
+                                             double (&acc)[FEMO_ELAST_MAX_COLS][D]) {
+  bool fx[D + 1][D];
+#pragma unroll
+  for (int b = 0; b <= D; ++b)
+#pragma unroll
+    for (int i = 0; i < D; ++i) fx[b][i] = MASKED && fixed[(int64_t)v[b] * D + i];
+#pragma unroll
+  for (int l = 0; l < FEMO_ELAST_MAX_COLS; ++l) {
+    if (l >= n_cols) break;
+    const double* __restrict__ xl = x + (int64_t)l * n_dof;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      double sx = 0.0, own = 0.0;
+#pragma unroll
+      for (int b = 0; b <= D; ++b) {
+        const double t = fx[b][i] ? 0.0 : xl[(int64_t)v[b] * D + i];
+        sx += t;
+        if (b == va) own = t;
+      }
+      acc[l][i] += w * (sx + own);
+    }
+  }
 }
 
 // block (a, b) of the element matrix without the factor C |T|; written symmetrically in (a, r) <-> (b, c)

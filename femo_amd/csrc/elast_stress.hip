@@ -40,21 +40,12 @@ __global__ __launch_bounds__(EB) void k_elast_stress_cell_multi(
   __shared__ double lds[EB / 64];
   const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
   const bool live = c < n_cell;
-  int32_t v[D + 1];
-  double g[D + 1][D], vol = 0.0, r = 1.0, rq = 1.0;
+  ElastCell<D> K = {};           // a thread past the last cell stays for the block sums, on a cell of zeros
+  double r = 1.0, rq = 1.0;
   if (live) {
-    double pt[D + 1][D];
-    load_cell<D>(conn, xv, c, v, pt);
-    simplex_grads<D>(pt, g, vol);
+    K = elast_cell<D>(conn, xv, c);
     r = rho ? rho[c] : 1.0;
     rq = rho && q != 0.0 ? pow(r, q) : 1.0;
-  } else {
-#pragma unroll
-    for (int b = 0; b <= D; ++b) {
-      v[b] = 0;
-#pragma unroll
-      for (int i = 0; i < D; ++i) g[b][i] = 0.0;
-    }
   }
   const bool sums = part || drho;
   const int l0 = !ONE && field && !sums && column >= 0 ? column : 0;          // a single field: that column only
@@ -64,7 +55,7 @@ __global__ __launch_bounds__(EB) void k_elast_stress_cell_multi(
     double Jc = 0.0;
     if (live) {
       double s[D][D];
-      const double vm = cell_von_mises<D>(g, v, u + l * vs, mu, s);
+      const double vm = cell_von_mises<D>(K.g, K.v, u + l * vs, mu, s);
       const double relaxed = rq * vm;
       if (ONE) fmax_ = sc.v[0] * relaxed;
       else if (field && (column < 0 || column == l)) {
@@ -72,7 +63,7 @@ __global__ __launch_bounds__(EB) void k_elast_stress_cell_multi(
         fmax_ = f > fmax_ || f != f ? f : fmax_;          // a sticky maximum: fmax would drop a NaN
       }
       if (sums) {
-        Jc = vm == 0.0 ? 0.0 : vol * inv_alpha * pow(m.v[l] * relaxed, p);
+        Jc = vm == 0.0 ? 0.0 : K.vol * inv_alpha * pow(m.v[l] * relaxed, p);
         if (drho && q != 0.0 && Jc != 0.0 && w.v[l] != 0.0) dsum += w.v[l] * (p * q / r * Jc);
       }
     }
@@ -87,7 +78,7 @@ __global__ __launch_bounds__(EB) void k_elast_stress_cell_multi(
   }
 }
 
-// dJ/du: one thread per vertex row with the visit walk of k_elast_drho_N, for the columns c0 = MC * blockIdx.y ...
+// dJ/du: one thread per vertex row on the shared visit walk (elast_visits), for the columns c0 = MC * blockIdx.y ...
 // min(c0 + MC, n_cols) - 1.  Column l of y (+)= w_l dJ_l/du_l:
 //   y_(v, r) (+)= sum over the cells c around v of (tau_c grad phi_v)_r, tau = 2 mu S + lam tr(S) I,
 //   S = dJ_c/dsigma = |T| / alpha p (m rho^q)^p sigma_vm^(p-2) 3/2 s.
@@ -120,16 +111,13 @@ __global__ __launch_bounds__(EB) void k_elast_stress_du_multi(
 #pragma unroll
     for (int i = 0; i < D; ++i) acc[cc][i] = 0.0;
   if (any) {
-    const int64_t slice = row >> 6;
-    const int lane = (int)(row & 63);
-    const int64_t vb = vptr[slice];
-    const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
-    for (int k = 0; k < nvis; ++k) {
-      const int32_t ca = visit_cell[vb + (int64_t)k * 64 + lane];
-      if (ca < 0) continue;
-      const int64_t c = ca >> 2;
-      const int a = ca & 3;
-      int32_t v[D + 1];
+    const ElastVisits V = elast_visits(row, vptr);
+    for (int k = 0; k < V.n; ++k) {
+      const ElastVisit t = elast_visit(V, visit_cell, k);
+      if (!t.live) continue;
+      const int64_t c = t.c;
+      const int a = t.a;
+      int32_t v[D + 1];          // g[a]: an array of its own, as in k_elast_assemble
       double pt[D + 1][D], g[D + 1][D], vol;
       load_cell<D>(conn, xv, c, v, pt);
       simplex_grads<D>(pt, g, vol);
@@ -171,43 +159,31 @@ __global__ __launch_bounds__(EB) void k_elast_stress_du_multi(
   }
 }
 
-template <int D, bool ONE>
-void cell_launch_d(femo_elast* e, unsigned g, int nc, const double* rho, const double* u, const ColScalars& m, const ColScalars& w,
-                   const ColScalars& sc, double p, double q, double inv_alpha, int column, double* field, double* part,
-                   int64_t ps, double* drho, int accumulate) {
-  femo_mesh* mh = e->mesh;
-  hipLaunchKernelGGL((k_elast_stress_cell_multi<D, ONE>), dim3(g), dim3(EB), 0, mh->ctx->stream, mh->n_cell, mh->d_conn, mh->d_x,
-                     rho, u, mh->n_vert * D, nc, e->mu0, m, w, sc, p, q, inv_alpha, column, field, part, ps, drho, accumulate);
-}
-
-// one column: the ONE instantiation (as spmv_chunk in elast_solve.hip picks MC = 1)
+// one column: the ONE instantiation (as femo_elast_spmv in elast_solve.hip picks MC = 1)
 int cell_launch(femo_elast* e, int nc, const double* rho, const double* u, const ColScalars& m, const ColScalars& w,
                 const ColScalars& sc, double p, double q, double inv_alpha, int column, double* field, double* part, int64_t ps,
                 double* drho, int accumulate) {
-  const unsigned g = grid_of(e->mesh->n_cell);
-  FEMO_REQUIRE((int64_t)g * EB >= e->mesh->n_cell, "too many cells for one launch");
-#define FEMO_CELL(D, ONE) cell_launch_d<D, ONE>(e, g, nc, rho, u, m, w, sc, p, q, inv_alpha, column, field, part, ps, drho, accumulate)
-  if (e->d == 2) { if (nc == 1) FEMO_CELL(2, true); else FEMO_CELL(2, false); }
-  else { if (nc == 1) FEMO_CELL(3, true); else FEMO_CELL(3, false); }
-#undef FEMO_CELL
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-template <int D, int MC>
-void du_launch(femo_elast* e, int nc, const double* rho, const double* u, const ColScalars& m, const ColScalars& w, double p,
-               double q, double inv_alpha, double* y, int accumulate) {
   femo_mesh* mh = e->mesh;
-  hipLaunchKernelGGL((k_elast_stress_du_multi<D, MC>), dim3(grid_of(mh->n_rows), (unsigned)((nc + MC - 1) / MC)), dim3(EB), 0,
-                     mh->ctx->stream, mh->n_rows, mh->d_vptr, mh->d_visit_cell, mh->d_conn, mh->d_x, rho, u, mh->n_vert * D, nc,
-                     e->mu0, m, w, p, q, inv_alpha, y, accumulate);
+  FEMO_REQUIRE((int64_t)grid_of(mh->n_cell) * EB >= mh->n_cell, "too many cells for one launch");
+  return elast_dispatch_d(e->d, [&](auto dim) {
+    constexpr int D = decltype(dim)::value;
+    auto* kernel = nc == 1 ? k_elast_stress_cell_multi<D, true> : k_elast_stress_cell_multi<D, false>;
+    return elast_launch_cells(e, kernel, mh->d_conn, mh->d_x, rho, u, mh->n_vert * D, nc, e->mu0, m, w, sc, p, q, inv_alpha, column,
+                              field, part, ps, drho, accumulate);
+  });
 }
 
-template <int D>
-void du_chunk(femo_elast* e, int nc, const double* rho, const double* u, const ColScalars& m, const ColScalars& w, double p,
+// one column: the MC = 1 instantiation; the columns of a chunk in the grid's second dimension
+int du_launch(femo_elast* e, int nc, const double* rho, const double* u, const ColScalars& m, const ColScalars& w, double p,
               double q, double inv_alpha, double* y, int accumulate) {
-  if (nc == 1) du_launch<D, 1>(e, nc, rho, u, m, w, p, q, inv_alpha, y, accumulate);
-  else du_launch<D, StressChunk<D>::value>(e, nc, rho, u, m, w, p, q, inv_alpha, y, accumulate);
+  femo_mesh* mh = e->mesh;
+  return elast_dispatch_d(e->d, [&](auto dim) {
+    constexpr int D = decltype(dim)::value;
+    const int mc = nc == 1 ? 1 : StressChunk<D>::value;
+    auto* kernel = nc == 1 ? k_elast_stress_du_multi<D, 1> : k_elast_stress_du_multi<D, StressChunk<D>::value>;
+    return elast_launch(e, mh->n_rows, (unsigned)((nc + mc - 1) / mc), kernel, mh->d_vptr, mh->d_visit_cell, mh->d_conn, mh->d_x, rho,
+                        u, mh->n_vert * D, nc, e->mu0, m, w, p, q, inv_alpha, y, accumulate);
+  });
 }
 
 // m and w of n_cols load cases as kernel arguments (w == null: ones), checked; the absent columns read m = 1, w = 0
@@ -245,9 +221,7 @@ int pnorm_stress(femo_elast* e, int n_cols, const femo_vec* rho, const femo_vec*
                          grad_rho ? grad_rho->d : nullptr, accumulate));
   if (grad_u) {
     femo_vec_touch(grad_u);
-    if (e->d == 2) du_chunk<2>(e, n_cols, rho->d, u->d, ms, ws, p, q, inv_alpha, grad_u->d, accumulate);
-    else du_chunk<3>(e, n_cols, rho->d, u->d, ms, ws, p, q, inv_alpha, grad_u->d, accumulate);
-    FEMO_HIP_CHECK(hipGetLastError());
+    FEMO_TRY(du_launch(e, n_cols, rho->d, u->d, ms, ws, p, q, inv_alpha, grad_u->d, accumulate));
   }
   if (values) {
     double* out = e->w_smpart + ps * EMC;

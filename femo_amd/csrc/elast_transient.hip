@@ -240,11 +240,9 @@ int femo_elast_newmark_march(femo_elast* e, const femo_newmark_params* p, int n_
   femo_vec_touch(U);
   hipStream_t st = m->ctx->stream;
   const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_newmark_dinv<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, e->d_diag, e->d_mdiag, fx, sigma, e->d_nm_dinv);
-  else
-    hipLaunchKernelGGL(k_newmark_dinv<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, e->d_diag, e->d_mdiag, fx, sigma, e->d_nm_dinv);
-  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_TRY(elast_dispatch_d(e->d, [&](auto dim) {
+    return elast_launch_rows(e, k_newmark_dinv<decltype(dim)::value>, e->d_diag, e->d_mdiag, fx, sigma, e->d_nm_dinv);
+  }));
   const femo_elast_op op = {sigma, e->d_nm_dinv};
   femo_solver_opts so = *opts;
   so.zero_guess = extrapolate ? 0 : 1;

@@ -42,15 +42,14 @@ __global__ __launch_bounds__(EB) void k_elast_assemble(
   double dg[DD];
 #pragma unroll
   for (int q = 0; q < DD; ++q) dg[q] = 0.0;
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
-  for (int s = 0; s < nvis; ++s) {
-    const int64_t vi = vb + (int64_t)s * 64 + lane;
-    const int32_t ca = visit_cell[vi];
-    if (ca < 0) continue;
-    const uint32_t sl = visit_slots[vi];
-    const int64_t c = ca >> 2;
-    const int a = ca & 3;
+  const ElastVisits V = elast_visits(row, vptr);
+  for (int s = 0; s < V.n; ++s) {
+    const ElastVisit t = elast_visit(V, visit_cell, s);
+    if (!t.live) continue;
+    const uint32_t sl = visit_slots[t.vi];
+    const int64_t c = t.c;
+    const int a = t.a;
+    // g is indexed by the run-time a: an array of its own, which a member of the cell record could not be split into
     int32_t v[D + 1];
     double p[D + 1][D], g[D + 1][D], vol;
     load_cell<D>(conn, x, c, v, p);
@@ -93,31 +92,11 @@ __global__ __launch_bounds__(EB) void k_elast_drho_T(int64_t n_cell, const int32
                                                      const double* __restrict__ w, double* __restrict__ y, int accumulate) {
   const int64_t c = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (c >= n_cell) return;
-  int32_t v[D + 1];
-  double p[D + 1][D], g[D + 1][D], vol;
-  load_cell<D>(conn, xv, c, v, p);
-  simplex_grads<D>(p, g, vol);
-  double Gu[D][D], Gw[D][D];      // G[i][k] = d(field_i)/dx_k
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int k = 0; k < D; ++k) { Gu[i][k] = 0.0; Gw[i][k] = 0.0; }
-#pragma unroll
-  for (int b = 0; b <= D; ++b)
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      const double ub = u[(int64_t)v[b] * D + i], wb = w[(int64_t)v[b] * D + i];
-#pragma unroll
-      for (int k = 0; k < D; ++k) { Gu[i][k] += ub * g[b][k]; Gw[i][k] += wb * g[b][k]; }
-    }
-  double divu = 0.0, divw = 0.0, ee = 0.0;
-#pragma unroll
-  for (int i = 0; i < D; ++i) { divu += Gu[i][i]; divw += Gw[i][i]; }
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int k = 0; k < D; ++k) ee += 0.25 * (Gu[i][k] + Gu[k][i]) * (Gw[i][k] + Gw[k][i]);
-  const double val = penal_d(method, rho[c]) * vol * (lam * divu * divw + 2.0 * mu * ee);
+  const ElastCell<D> K = elast_cell<D>(conn, xv, c);
+  double Gu[D][D], Gw[D][D];
+  cell_gradient<D>(K.g, K.v, u, Gu);
+  cell_gradient<D>(K.g, K.v, w, Gw);
+  const double val = penal_d(method, rho[c]) * K.vol * elastic_form<D>(Gu, Gw, lam, mu);
   y[c] = accumulate ? y[c] + val : val;
 }
 
@@ -129,39 +108,25 @@ __global__ __launch_bounds__(EB) void k_elast_drho_N(
     const double* __restrict__ u, const double* __restrict__ dr, double* __restrict__ y, int accumulate) {
   const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
   if (row >= n_rows) return;
-  const int64_t slice = row >> 6;
-  const int lane = (int)(row & 63);
-  const int64_t vb = vptr[slice];
-  const int nvis = (int)((vptr[slice + 1] - vb) >> 6);
   double acc[D];
 #pragma unroll
   for (int r = 0; r < D; ++r) acc[r] = 0.0;
-  for (int s = 0; s < nvis; ++s) {
-    const int32_t ca = visit_cell[vb + (int64_t)s * 64 + lane];
-    if (ca < 0) continue;
-    const int64_t c = ca >> 2;
-    const int a = ca & 3;
-    int32_t v[D + 1];
-    double p[D + 1][D], g[D + 1][D], vol;
+  const ElastVisits V = elast_visits(row, vptr);
+  for (int s = 0; s < V.n; ++s) {
+    const ElastVisit t = elast_visit(V, visit_cell, s);
+    if (!t.live) continue;
+    const int64_t c = t.c;
+    const int a = t.a;
+    int32_t v[D + 1];        // g[a]: an array of its own, as in k_elast_assemble
+    double p[D + 1][D], g[D + 1][D], vol, Gu[D][D];
     load_cell<D>(conn, xv, c, v, p);
     simplex_grads<D>(p, g, vol);
-    double Gu[D][D];
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-      for (int k = 0; k < D; ++k) Gu[i][k] = 0.0;
-#pragma unroll
-    for (int b = 0; b <= D; ++b)
-#pragma unroll
-      for (int i = 0; i < D; ++i) {
-        const double ub = u[(int64_t)v[b] * D + i];
-#pragma unroll
-        for (int k = 0; k < D; ++k) Gu[i][k] += ub * g[b][k];
-      }
+    cell_gradient<D>(g, v, u, Gu);
     double divu = 0.0;
 #pragma unroll
     for (int i = 0; i < D; ++i) divu += Gu[i][i];
     const double coef = penal_d(method, rho[c]) * dr[c] * vol;
+    // lam div g_a first, then the shear terms in ascending k: not the order of a stress tensor times g_a
 #pragma unroll
     for (int r = 0; r < D; ++r) {
       double sg = lam * divu * g[a][r];
@@ -396,20 +361,13 @@ __global__ void k_f_apply(int64_t n, const int64_t* __restrict__ rowptr, const i
 int drho_launch(femo_elast* e, int method, int transpose, const double* rho, const double* u, const double* x, double* y,
                 int accumulate) {
   femo_mesh* m = e->mesh;
-  hipStream_t st = m->ctx->stream;
-  if (transpose) {
-    if (e->d == 2)
-      hipLaunchKernelGGL(k_elast_drho_T<2>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
-    else
-      hipLaunchKernelGGL(k_elast_drho_T<3>, dim3(grid_of(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
-  } else {
-    if (e->d == 2)
-      hipLaunchKernelGGL(k_elast_drho_N<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
-    else
-      hipLaunchKernelGGL(k_elast_drho_N<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
-  }
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  return elast_dispatch_d(e->d, [&](auto dim) {
+    constexpr int D = decltype(dim)::value;
+    if (transpose)
+      return elast_launch_cells(e, k_elast_drho_T<D>, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u, x, y, accumulate);
+    return elast_launch_rows(e, k_elast_drho_N<D>, m->d_vptr, m->d_visit_cell, m->d_conn, m->d_x, rho, method, e->lam0, e->mu0, u,
+                             x, y, accumulate);
+  });
 }
 
 // dR/drho of femo_elast_drho (one column) and femo_elast_drho_multi, which have checked their sizes; who: the entry point,
@@ -536,17 +494,11 @@ int femo_elast_assemble(femo_elast* e, int method, const femo_vec* rho) {
   femo_mesh* m = e->mesh;
   FEMO_REQUIRE(rho->n >= m->n_cell, "density vector too small");
   FEMO_TRY(femo_vec_await(rho));
-  hipStream_t st = m->ctx->stream;
   const uint8_t* fx = e->has_fixed ? e->d_fixed : nullptr;
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_elast_assemble<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell,
-                       m->d_visit_slots, m->d_mptr, m->d_rowlen, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, fx,
-                       e->d_vals, e->d_diag, e->d_dinv);
-  else
-    hipLaunchKernelGGL(k_elast_assemble<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_vptr, m->d_visit_cell,
-                       m->d_visit_slots, m->d_mptr, m->d_rowlen, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, fx,
-                       e->d_vals, e->d_diag, e->d_dinv);
-  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_TRY(elast_dispatch_d(e->d, [&](auto dim) {
+    return elast_launch_rows(e, k_elast_assemble<decltype(dim)::value>, m->d_vptr, m->d_visit_cell, m->d_visit_slots, m->d_mptr,
+                             m->d_rowlen, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, fx, e->d_vals, e->d_diag, e->d_dinv);
+  }));
   e->assembled = true;
   e->pc_dirty = true;
   e->method = method;
@@ -563,14 +515,10 @@ int femo_elast_load(femo_elast* e, const double* t, femo_vec* F) {
   FEMO_REQUIRE(F->n >= m->n_vert * e->d, "load vector too small");
   FEMO_REQUIRE(e->d_fptr, "femo_elast_load: no tagged facets (femo_elast_set_facets)");
   femo_vec_touch(F);
-  hipStream_t st = m->ctx->stream;
   const double t2 = e->d == 3 ? t[2] : 0.0;
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_elast_load<2>, dim3(grid_of(m->n_vert)), dim3(EB), 0, st, m->n_vert, e->d_fptr, e->d_flist, e->d_fverts, m->d_x, t[0], t[1], t2, F->d);
-  else
-    hipLaunchKernelGGL(k_elast_load<3>, dim3(grid_of(m->n_vert)), dim3(EB), 0, st, m->n_vert, e->d_fptr, e->d_flist, e->d_fverts, m->d_x, t[0], t[1], t2, F->d);
-  FEMO_HIP_CHECK(hipGetLastError());
-  return 0;
+  return elast_dispatch_d(e->d, [&](auto dim) {      // n_vert = n_rows on the one GPU the elasticity runs on
+    return elast_launch_rows(e, k_elast_load<decltype(dim)::value>, e->d_fptr, e->d_flist, e->d_fverts, m->d_x, t[0], t[1], t2, F->d);
+  });
 }
 
 int femo_elast_drho(femo_elast* e, int method, int transpose, const femo_vec* rho, const femo_vec* u, const femo_vec* x,
@@ -608,11 +556,10 @@ int femo_elast_export_csr(const femo_elast* e, int64_t* rowptr, int32_t* col, do
   FEMO_TRY(dalloc(&d_col, m->nnz));
   FEMO_TRY(dalloc(&d_val, m->nnz * dd));
   FEMO_HIP_CHECK(hipMemcpyAsync(d_rp, rowptr, (m->n_rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  if (e->d == 2)
-    hipLaunchKernelGGL(k_elast_export<2>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, m->d_rowreal, e->d_diag, e->d_vals, d_rp, d_col, d_val);
-  else
-    hipLaunchKernelGGL(k_elast_export<3>, dim3(grid_of(m->n_rows)), dim3(EB), 0, st, m->n_rows, m->d_mptr, m->d_cols, m->d_rowlen, m->d_rowreal, e->d_diag, e->d_vals, d_rp, d_col, d_val);
-  FEMO_HIP_CHECK(hipGetLastError());
+  FEMO_TRY(elast_dispatch_d(e->d, [&](auto dim) {
+    return elast_launch_rows(e, k_elast_export<decltype(dim)::value>, m->d_mptr, m->d_cols, m->d_rowlen, m->d_rowreal, e->d_diag,
+                             e->d_vals, d_rp, d_col, d_val);
+  }));
   FEMO_HIP_CHECK(hipMemcpyAsync(col, d_col, m->nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   FEMO_HIP_CHECK(hipMemcpyAsync(val, d_val, m->nnz * dd * sizeof(double), hipMemcpyDeviceToHost, st));
   FEMO_HIP_CHECK(hipStreamSynchronize(st));
