@@ -304,6 +304,14 @@ PROTOTYPES = {
     "femo_filter_nnz": (C.c_int, [H, c_i64p]),
     "femo_filter_apply": (C.c_int, [H, C.c_int, H, H]),
     "femo_filter_export_csr": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # Helmholtz (PDE) density filter (csrc/pde_filter.hip)
+    "femo_pde_filter_create": (C.c_int, [H, C.c_double, C.c_int, C.POINTER(H)]),
+    "femo_pde_filter_destroy": (C.c_int, [H]),
+    "femo_pde_filter_apply": (C.c_int, [H, C.c_int, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
+    "femo_pde_filter_set": (C.c_int, [H, C.c_double, C.c_int]),
+    "femo_pde_filter_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "femo_pde_filter_bytes": (C.c_int, [H, c_i64p]),
+    "femo_pde_filter_project": (C.c_int, [H, H, H, H, H, C.POINTER(ProjectInfo)]),
     # Method of Moving Asymptotes (csrc/mma.hip)
     "femo_mma_create": (C.c_int, [H, c_i64, C.c_int, H, H, C.POINTER(MmaParams), C.POINTER(H)]),
     "femo_mma_update": (C.c_int, [H, H, C.c_double, H, c_f64p, H, C.POINTER(MmaInfo)]),

@@ -8,6 +8,11 @@
 W and W^T are built once on the device (csrc/elasticity.hip: hash grid, count / scan / fill); ``compute`` and both
 Jacobian-vector products are gathers on the GPU.  Values may be NumPy arrays or ``DeviceArray``.  With the real
 ``csdl`` the sparse partials (rows, cols, val) are declared as a CSDL backend expects, exported once from the device.
+
+``HelmholtzFilterModel`` / ``HelmholtzFilterOperation`` are the same variables through the PDE filter of Lazarov & Sigmund
+(csrc/pde_filter.hip): parameters ``mesh``, ``radius`` (or ``beta`` and ``h_avg``, radius = beta h_avg) and ``mass``; W is
+dense, so no sparse partials are declared and ``compute_jacvec_product`` is the interface.  ``ProjectedFilterModel`` takes
+either filter (``filter="neighbours"``, the default, or ``"helmholtz"`` with ``mesh``).
 """
 import time
 
@@ -16,7 +21,7 @@ import numpy as np
 from femo_amd import engine as E
 from femo_amd.csdl_opt._csdl_compat import HAVE_CSDL, CustomExplicitOperation, Model, custom
 from femo_amd.engine import DeviceArray, Vec
-from femo_amd.fea.elasticity import DeviceFilter, DeviceProjection, check_projection_params
+from femo_amd.fea.elasticity import DeviceFilter, DevicePdeFilter, DeviceProjection, check_projection_params
 from femo_amd.fea.utils_hip import get_context
 
 _FILTER_PARAMS = (('nel', {}), ('beta', dict(default=2.)), ('coordinates', {}), ('h_avg', {}))
@@ -112,8 +117,58 @@ class GeneralFilterOperation(CustomExplicitOperation):
             raise ValueError(f"unknown mode {mode!r}")
 
 
+# ------------------------------------------------------------------------------------------- Helmholtz filter ----
+_HELMHOLTZ_PARAMS = (('mesh', {}), ('radius', dict(default=None)), ('beta', dict(default=2.)), ('h_avg', dict(default=None)),
+                     ('mass', dict(default='lumped')))
+
+
+def helmholtz_radius(radius=None, beta=2., h_avg=None) -> float:
+    """``radius``, or ``beta * h_avg`` when it is None (the neighbour filter's convention)."""
+    if radius is None:
+        if h_avg is None:
+            raise ValueError("Helmholtz filter: give radius, or beta and h_avg")
+        radius = float(beta) * float(h_avg)
+    return float(radius)
+
+
+class HelmholtzFilterModel(Model):
+    """Declares ``density_unfiltered`` and registers ``density`` as the output of a HelmholtzFilterOperation."""
+
+    def initialize(self):
+        for name, kw in _HELMHOLTZ_PARAMS:
+            self.parameters.declare(name, **kw)
+
+    def define(self):
+        P = self.parameters
+        nel = int(P['mesh'].n_cell)
+        density_unfiltered = self.declare_variable('density_unfiltered', shape=(nel,), val=1.0)
+        self.operation = HelmholtzFilterOperation(**{name: P[name] for name, _ in _HELMHOLTZ_PARAMS})
+        self.register_output('density', custom(density_unfiltered, op=self.operation))
+
+
+class HelmholtzFilterOperation(GeneralFilterOperation):
+    """input: unfiltered density (DG0), output: density = W density_unfiltered with the Helmholtz filter; the products are
+    those of GeneralFilterOperation with ``self.filter`` a DevicePdeFilter (one solve each)."""
+
+    def initialize(self):
+        for name, kw in _HELMHOLTZ_PARAMS:
+            self.parameters.declare(name, **kw)
+
+    def define(self):
+        P = self.parameters
+        self.nel = int(P['mesh'].n_cell)
+        self.radius = helmholtz_radius(P['radius'], P['beta'], P['h_avg'])
+        self.add_input('density_unfiltered', shape=(self.nel,), val=0.0)
+        self.add_output('density', shape=(self.nel,))
+        self.filter = DevicePdeFilter(get_context(), P['mesh'], self.radius, mass=P['mass'])
+        self._x = self._y = None
+        self.declare_derivatives('density', 'density_unfiltered')
+
+
 # ---------------------------------------------------------------------------------- filter + Heaviside projection ----
-_PROJECTION_PARAMS = _FILTER_PARAMS + (('projection_beta', dict(default=0.)), ('eta', dict(default=0.5)),
+_PROJECTION_PARAMS = _FILTER_PARAMS + (('filter', dict(default='neighbours')), ('mesh', dict(default=None)),
+                                       ('mass', dict(default='lumped')), ('projection_beta', dict(default=0.)),
+                                       ('eta', dict(default=0.5)),
                                        ('volumes', dict(default=None)), ('solid', dict(default=None)),
                                        ('void', dict(default=None)), ('void_value', dict(default=1e-4)))
 
@@ -130,7 +185,8 @@ def check_projection_parameters(nel, projection_beta=0., eta=0.5, volumes=None, 
 class ProjectedFilterModel(Model):
     """``density_unfiltered`` -> ``density`` through the filter and the Heaviside projection (three-field SIMP):
     density = P(W density_unfiltered), P as include/femo_hip.h, "Heaviside projection", states it.  The general filter's
-    parameters, plus ``projection_beta`` (0: the identity), ``eta`` (a number in [0, 1] or ``"volume"``), ``volumes``
+    parameters, plus ``filter`` (``"neighbours"``: the general filter, or ``"helmholtz"`` with ``mesh`` and ``mass``: the PDE
+    filter, for which ``coordinates`` may be None), ``projection_beta`` (0: the identity), ``eta`` (a number in [0, 1] or ``"volume"``), ``volumes``
     (cell volumes; None: ones), ``solid`` / ``void`` (passive cell indices) and ``void_value``.  ``operation`` is the
     ProjectedFilterOperation (a BetaContinuation takes it)."""
 
@@ -158,17 +214,24 @@ class ProjectedFilterOperation(CustomExplicitOperation):
     def define(self):
         P = self.parameters
         self.nel = int(P['nel'])
-        coords = np.asarray(P['coordinates'], dtype=np.float64)
-        if coords.shape[0] != self.nel:
-            raise ValueError(f"ProjectedFilterOperation: {coords.shape[0]} coordinates for nel = {self.nel}")
-        if coords.shape[1] == 3 and np.all(coords[:, 2] == 0.0):
-            coords = coords[:, :2]                     # dolfinx tabulates 3 coordinates for a 2-D mesh
+        if P['filter'] not in ('neighbours', 'helmholtz'):
+            raise ValueError(f"ProjectedFilterOperation: filter = {P['filter']!r}, must be 'neighbours' or 'helmholtz'")
+        helmholtz = P['filter'] == 'helmholtz'
+        if helmholtz:
+            if P['mesh'] is None or int(P['mesh'].n_cell) != self.nel:
+                raise ValueError("ProjectedFilterOperation: filter = 'helmholtz' needs the mesh of the nel cells")
+        else:
+            coords = np.asarray(P['coordinates'], dtype=np.float64)
+            if coords.shape[0] != self.nel:
+                raise ValueError(f"ProjectedFilterOperation: {coords.shape[0]} coordinates for nel = {self.nel}")
+            if coords.shape[1] == 3 and np.all(coords[:, 2] == 0.0):
+                coords = coords[:, :2]                     # dolfinx tabulates 3 coordinates for a 2-D mesh
         check_projection_parameters(self.nel, P['projection_beta'], P['eta'], P['volumes'], P['solid'], P['void'], P['void_value'])
         self.radius = float(P['beta']) * float(P['h_avg'])
         self.add_input('density_unfiltered', shape=(self.nel,), val=0.0)
         self.add_output('density', shape=(self.nel,))
         ctx = get_context()
-        self.filter = DeviceFilter(ctx, coords, self.radius)
+        self.filter = DevicePdeFilter(ctx, P['mesh'], self.radius, mass=P['mass']) if helmholtz else DeviceFilter(ctx, coords, self.radius)
         self.projection = DeviceProjection(ctx, self.nel, P['projection_beta'], P['eta'], P['volumes'],
                                            () if P['solid'] is None else P['solid'], () if P['void'] is None else P['void'],
                                            P['void_value'])

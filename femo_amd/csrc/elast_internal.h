@@ -88,6 +88,26 @@ struct femo_filter {
   double* d_valT = nullptr;     // W^T on the same (symmetric) pattern
 };
 
+// Helmholtz (PDE) density filter W = V^-1 T^T A^-1 T (csrc/pde_filter.hip; include/femo_hip.h states it)
+struct femo_pde_filter {
+  femo_ctx* ctx = nullptr;
+  femo_mesh* mesh = nullptr;
+  int64_t n = 0;                // cells
+  double radius = 0.0, rtol = 1e-13;   // rtol: of the solves that are not handed options of their own
+  bool lumped = true, warm_start = false;
+  bool have_guess = false;      // p holds the nodal field of the last forward application that converged
+  femo_mat* A = nullptr;        // rt^2 L + M on the mesh pattern
+  femo_vec* cv_vol = nullptr;   // n: |T_c| / (d+1), the transfer T and the transposed pipeline's way out
+  femo_vec* cv_one = nullptr;   // n: 1 / (d+1), the mean and the transposed pipeline's way in
+  femo_vec* b = nullptr;        // n_rows: the load
+  femo_vec* p = nullptr;        // n_vert: nodal field of the forward pipeline (kept for warm_start)
+  femo_vec* pT = nullptr;       // n_vert: ... of the transposed one
+  femo_solve_info last = {};
+};
+// b = T (s x), p = A^-1 b: the two first steps of femo_pde_filter_apply.  *nodal is the solution; the caller applies the mean.
+int femo_pde_filter_nodal(femo_pde_filter* f, int transpose, const femo_vec* x, const femo_solver_opts* opts,
+                          femo_solve_info* info, const femo_vec** nodal);
+
 constexpr int EB = 256;              // threads per block of the row kernels
 constexpr int PCG_GRID = 512;        // blocks of the PCG reductions (one partial each)
 

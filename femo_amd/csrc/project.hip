@@ -9,6 +9,8 @@
 //
 // Fixed threshold: tanh(beta eta) and D are formed once on the host and travel as kernel arguments, so a cell costs one tanh.
 // femo_filter_project is then one launch: the row loop of k_f_apply (elasticity.hip), then p_cell on the sum in registers.
+// femo_pde_filter_project: load and solve of the Helmholtz filter (pde_filter.hip), then k_p_mean in the gather's place: the
+// cell means of the nodal field, and p_cell on each in registers.
 // Volume-preserving threshold: k_p_gsum / k_p_fold<STEP> 53 times -- no host round trip -- then k_p_forward, which reads the
 // root from the record, and one blocking copy of the record.  Bytes per launch: DESIGN.md section 10, "Projection".
 //
@@ -171,6 +173,27 @@ __global__ __launch_bounds__(P_BLOCK) void k_p_gather(int64_t n, const int64_t* 
   for (int64_t i = (int64_t)blockIdx.x * P_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * P_BLOCK) {
     double a = 0.0;
     for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) a += val[e] * x[col[e]];
+    xt[i] = a;
+    if (PROJECT) rho[i] = p_rho(c, fl[i], a, v[i], void_value, s);
+    else if (fl[i] == 0) s[0] += v[i] * a;
+  }
+  p_block_reduce<3>(s, lds, part, nb);
+}
+
+// xt = the mean of the nodal field p over the vertices of the cell, scaled by cv (the last step of femo_pde_filter_apply: the sum
+// in `conn` order, then one product, as k_dRdf_cell_apply_T has it), then -- PROJECT -- rho = P(xt) from the register
+template <int D, bool PROJECT>
+__global__ __launch_bounds__(P_BLOCK) void k_p_mean(int64_t n, const int32_t* __restrict__ conn, const double* __restrict__ cv,
+                                                    const double* __restrict__ p, PCoef c, double void_value,
+                                                    const double* __restrict__ v, const int8_t* __restrict__ fl,
+                                                    double* __restrict__ xt, double* __restrict__ rho, double* __restrict__ part, int nb) {
+  __shared__ double lds[P_WAVES * 3];
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = (int64_t)blockIdx.x * P_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * P_BLOCK) {
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k <= D; ++k) a += p[conn[i * (D + 1) + k]];
+    a *= cv[i];
     xt[i] = a;
     if (PROJECT) rho[i] = p_rho(c, fl[i], a, v[i], void_value, s);
     else if (fl[i] == 0) s[0] += v[i] * a;
@@ -449,6 +472,33 @@ extern "C" int femo_filter_project(femo_filter* f, femo_project* p, const femo_v
   else
     hipLaunchKernelGGL(k_p_gather<false>, dim3(p->nb), dim3(P_BLOCK), 0, st, n, f->d_rowptr, f->d_col, f->d_val, x->d, p_coef(p->beta, 0.5),
                        p->void_value, p->d_v, p->d_flag, xt->d, rho->d, p->d_part, p->nb);
+  return p_finish(p, xt->d, rho->d, fixed, 1, info, t0);
+}
+
+extern "C" int femo_pde_filter_project(femo_pde_filter* f, femo_project* p, const femo_vec* x, femo_vec* xt, femo_vec* rho,
+                                       femo_project_info* info) {
+  FEMO_REQUIRE(f && p && x && xt && rho, "null argument");
+  const int64_t n = p->n;
+  FEMO_REQUIRE(f->n == n && f->ctx == p->ctx, "project: the filter has %lld cells, the projection %lld", (long long)f->n, (long long)n);
+  FEMO_REQUIRE(x->n >= n && xt->n >= n && rho->n >= n, "project: a vector is shorter than n = %lld", (long long)n);
+  FEMO_REQUIRE(!p_overlap(xt, rho, n) && !p_overlap(x, xt, n) && !p_overlap(x, rho, n), "project: x, xt and rho must not overlap");
+  FEMO_REQUIRE(info || p->mode == FEMO_PROJECT_FIXED, "project: volume mode needs an info record");
+  const auto t0 = std::chrono::steady_clock::now();
+  const femo_vec* nodal = nullptr;
+  FEMO_TRY(femo_pde_filter_nodal(f, 0, x, nullptr, nullptr, &nodal));
+  femo_vec_touch(xt);
+  femo_vec_touch(rho);
+  const femo_mesh* m = f->mesh;
+  hipStream_t st = p->ctx->stream;
+  const bool fixed = p->mode == FEMO_PROJECT_FIXED;
+  const PCoef c = p_coef(p->beta, fixed ? p->eta : 0.5);
+  const dim3 g(p->nb), b(P_BLOCK);
+#define P_MEAN(DIM, PROJECT)                                                                                                     \
+  hipLaunchKernelGGL((k_p_mean<DIM, PROJECT>), g, b, 0, st, n, m->d_conn, f->cv_one->d, nodal->d, c, p->void_value, p->d_v, p->d_flag, \
+                     xt->d, rho->d, p->d_part, p->nb)
+  if (m->tdim == 2) { if (fixed) P_MEAN(2, true); else P_MEAN(2, false); }
+  else { if (fixed) P_MEAN(3, true); else P_MEAN(3, false); }
+#undef P_MEAN
   return p_finish(p, xt->d, rho->d, fixed, 1, info, t0);
 }
 

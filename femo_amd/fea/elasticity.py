@@ -660,6 +660,61 @@ class DeviceFilter:
             pass
 
 
+class DevicePdeFilter:
+    """femo_pde_filter (csrc/pde_filter.hip): the Helmholtz filter W = V^-1 T^T A^-1 T, A = rt^2 L + M, rt = r / (2 sqrt 3), on
+    ``mesh`` (a fea mesh); ``mass`` is ``"lumped"`` (default: no undershoot on meshes without obtuse cells) or
+    ``"consistent"``.  One scalar operator on the mesh pattern whatever the radius; ``apply`` is one Jacobi-PCG solve to
+    ``rtol`` from the zero guess -- with ``warm_start`` from the nodal field of the last forward application.  ``last_info`` is
+    the solve record of the last application (iterations, converged, residual_norm, rhs_norm, solve_ms, ...)."""
+
+    MASS = {"lumped": 1, "consistent": 0}
+
+    def __init__(self, ctx, mesh, radius: float, mass: str = "lumped", rtol: float = 1e-13, warm_start: bool = False):
+        if mass not in self.MASS:
+            raise ValueError(f"pde filter: mass = {mass!r}, must be 'lumped' or 'consistent'")
+        self.ctx, self.lib, self.mesh = ctx, ctx.lib, mesh
+        self.dm = mesh.device(ctx)
+        self.n, self.radius, self.mass = int(self.dm.n_cell), float(radius), mass
+        self.rtol, self.warm_start = float(rtol), bool(warm_start)
+        h = _lib.H()
+        _check_rc2(self.lib.femo_pde_filter_create(self.dm.handle, self.radius, self.MASS[mass], C.byref(h)))
+        self.handle = h
+        _check_rc2(self.lib.femo_pde_filter_set(self.handle, self.rtol, int(self.warm_start)))
+        self.nnz = int(self.dm.info["nnz"])
+        self.last_info = None
+
+    def apply(self, x: Vec, y: Vec, transpose: bool = False) -> Vec:
+        info = _lib.SolveInfo()
+        try:
+            _check_rc2(self.lib.femo_pde_filter_apply(self.handle, int(bool(transpose)), x.handle, y.handle, None, C.byref(info)))
+        finally:
+            self.last_info = {k: getattr(info, k) for k, _ in _lib.SolveInfo._fields_}
+        return y
+
+    def export_csr(self):
+        """(rowptr, col, val) of A on the mesh pattern, rows sorted by column."""
+        rowptr = np.zeros(self.dm.n_rows + 1, np.int64)
+        col = np.zeros(self.nnz, np.int32)
+        val = np.zeros(self.nnz)
+        check(self.lib.femo_pde_filter_export_csr(self.handle, _ptr(rowptr), _ptr(col), _ptr(val)))
+        return rowptr, col, val
+
+    @property
+    def bytes(self) -> int:
+        """Device bytes the handle holds now (the scaled copy of A appears with the first solve)."""
+        b = C.c_int64(0)
+        check(self.lib.femo_pde_filter_bytes(self.handle, C.byref(b)))
+        return int(b.value)
+
+    def __del__(self):
+        try:
+            h, self.handle = getattr(self, "handle", None), None
+            if h and getattr(self.ctx, "handle", None) and getattr(self.dm, "handle", None):
+                self.lib.femo_pde_filter_destroy(h)
+        except Exception:
+            pass
+
+
 def check_projection_params(n: int, beta, eta, volumes=None, solid=(), void=(), void_value: float = 1e-4):
     """Validates the parameters of the projection without a device and returns them as
     (beta, eta, mode, volumes or None, solid, void, void_value); ``eta`` is a float in [0, 1] or ``"volume"``."""
@@ -755,10 +810,12 @@ class DeviceProjection:
         _check_rc2(self.lib.femo_project_forward(self.handle, xt.handle, rho.handle, C.byref(rec) if info else None))
         return self._info(rec) if info else None
 
-    def filter_forward(self, filt: "DeviceFilter", x: Vec, xt: Vec, rho: Vec, info: bool = True) -> Optional[dict]:
-        """xt = W x and rho = P(xt) (fixed threshold: one launch)."""
+    def filter_forward(self, filt, x: Vec, xt: Vec, rho: Vec, info: bool = True) -> Optional[dict]:
+        """xt = W x and rho = P(xt) with a DeviceFilter (fixed threshold: one launch) or a DevicePdeFilter (load, solve, and
+        one launch for the cell means and the projection)."""
         rec = _lib.ProjectInfo()
-        _check_rc2(self.lib.femo_filter_project(filt.handle, self.handle, x.handle, xt.handle, rho.handle, C.byref(rec) if info else None))
+        entry = self.lib.femo_pde_filter_project if isinstance(filt, DevicePdeFilter) else self.lib.femo_filter_project
+        _check_rc2(entry(filt.handle, self.handle, x.handle, xt.handle, rho.handle, C.byref(rec) if info else None))
         return self._info(rec) if info else None
 
     def reverse(self, xt: Vec, a: Vec, out: Vec) -> Vec:

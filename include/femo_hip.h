@@ -953,6 +953,41 @@ int femo_filter_apply(femo_filter* f, int transpose, const femo_vec* x, femo_vec
 /* the rows / cols / val that declare_derivatives('density', 'density_unfiltered', ...) is given (CSR of W or W^T)     */
 int femo_filter_export_csr(const femo_filter* f, int transpose, int64_t* rowptr, int32_t* col, double* val);
 
+/* ---- Helmholtz (PDE) density filter (csrc/pde_filter.hip) ----------------------------------------------------------------
+ * The filter of Lazarov & Sigmund (2011), (-rt^2 Laplace + 1) xt = x with natural boundary conditions and rt = r / (2 sqrt 3),
+ * r the radius of the neighbour filter above whose length scale it matches.  For a DG0 field x on a mesh of d-simplices
+ *   xt = W x,   W = V^-1 T^T A^-1 T,   A = rt^2 L + M,
+ *   L_vw = sum_c |T_c| grad phi_v . grad phi_w,   T[v,c] = |T_c| / (d+1),   V = diag |T_c|,
+ *   M lumped:     M_vv = sum_{c around v} |T_c| / (d+1)                       (the default)
+ *   M consistent: |T_c| (1 + delta_ab) / ((d+1)(d+2)) per cell,
+ * so xt_c is the mean of the nodal solution over the vertices of c.  W^T = V W V^-1: the same pipeline with 1 / |T_c| on the way
+ * in and |T_c| on the way out; there is no second operator and no second solve path.  The memory is that of one scalar
+ * operator on the mesh pattern, whatever r is; an application is one Jacobi-preconditioned CG solve, whose iteration count
+ * grows with r / h and not with the mesh.
+ * A 1 = T 1 for both mass choices, hence W 1 = 1 and v^T W x = v^T x (v = the cell volumes) up to the solve's tolerance.
+ * Why lumped is the default: the consistent mass has positive off-diagonal entries, and A^-1 then undershoots -- the indicator of
+ * one cell of a 24 x 12 rectangle goes to -1.2e-2 at r = h and -7.9e-4 at r = 2 h, which SIMP turns into negative stiffness.
+ * With the lumped mass the off-diagonal entries of A are those of rt^2 L: non-positive on a mesh without obtuse cells, A is
+ * then an M-matrix and W x >= 0 for x >= 0.  On obtuse cells positivity is not guaranteed with either mass.
+ * create: d = 2, 3; refused: a partitioned mesh (one rank, as the rest of the SIMP track), a radius that is not finite or <= 0.
+ * apply: y = W x (transpose = 0) or W^T x.  opts NULL: the handle's rtol (1e-13) from the zero guess, so that apply is a pure
+ *   function of its input; opts->zero_guess is ignored and opts->pc must be FEMO_PC_JACOBI.  info may be NULL.  Refused (and the next call works):
+ *   vectors shorter than n_cell, x overlapping y, an input with a NaN or an infinity (found as the load's non-finite norm; y may
+ *   have been written).  A solve that does not converge is an error that names the iteration count.
+ * set(rtol, warm_start): the tolerance of the solves that get no options of their own (finite, > 0), and, with warm_start = 1,
+ *   the nodal field of the last converged forward application is the first guess of the next forward one
+ *   (results then depend on the history within the tolerance).  The transpose never warm-starts.
+ * export_csr: A in the layout of femo_mat_export_csr (pattern: femo_mesh_pattern_csr).  bytes: device bytes the handle holds.
+ * No float atomics: A is symmetric bit for bit and has the same bits on every build; an application has the same bits every time. */
+typedef struct femo_pde_filter femo_pde_filter;
+int femo_pde_filter_create(femo_mesh* mesh, double radius, int lumped, femo_pde_filter** out);
+int femo_pde_filter_destroy(femo_pde_filter* f);
+int femo_pde_filter_apply(femo_pde_filter* f, int transpose, const femo_vec* x, femo_vec* y, const femo_solver_opts* opts,
+                          femo_solve_info* info);
+int femo_pde_filter_set(femo_pde_filter* f, double rtol, int warm_start);
+int femo_pde_filter_export_csr(const femo_pde_filter* f, int64_t* rowptr, int32_t* col, double* val);
+int femo_pde_filter_bytes(const femo_pde_filter* f, int64_t* bytes);
+
 /* ---- Method of Moving Asymptotes (csrc/mma.hip) -------------------------------------------------------------------------
  * What the reference's drivers hand to modopt (run_topo_opt_cantilever_beam.py: modopt.CSDLProblem + SLSQP / SNOPT), as a
  * device-resident update: minimise f_0(x) subject to f_i(x) <= 0, i = 1..m, xmin <= x <= xmax (Svanberg 1987; Svanberg 2007,
@@ -1060,6 +1095,11 @@ int femo_project_forward(femo_project* p, const femo_vec* xt, femo_vec* rho, fem
  * mode: the gather also leaves the partials of sum v xt; the bisection; one element-wise launch for rho.  Refused as above,
  * and x overlapping xt or rho.                                                                                           */
 int femo_filter_project(femo_filter* f, femo_project* p, const femo_vec* x, femo_vec* xt, femo_vec* rho, femo_project_info* info);
+/* The same with the Helmholtz filter: load, solve (the handle's defaults), then ONE launch that forms the cell means and, in
+ * fixed mode, applies H in registers, so that xt and rho leave one launch; volume mode: the mean launch also leaves the partials
+ * of sum v xt, then the bisection and the element-wise launch as above.  Refusals of both entry points apply.              */
+int femo_pde_filter_project(femo_pde_filter* f, femo_project* p, const femo_vec* x, femo_vec* xt, femo_vec* rho,
+                            femo_project_info* info);
 /* out = J^T a and out = J d at xt, with the threshold of the last forward call (volume mode).  out may be a / d itself.    */
 int femo_project_reverse(femo_project* p, const femo_vec* xt, const femo_vec* a, femo_vec* out);
 int femo_project_tangent(femo_project* p, const femo_vec* xt, const femo_vec* d, femo_vec* out);

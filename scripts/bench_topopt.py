@@ -58,7 +58,7 @@ PEAK_BYTES_PER_S = 8.0e12
 
 def build(args):
     from femo_amd.csdl_opt.fea_model import FEAModel
-    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel, HelmholtzFilterModel
     from femo_amd.csdl_opt.simulator import Simulator
     from femo_amd.fea.elasticity import averageFunc, compliance, pdeRes
     from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, Measure, VectorFunctionSpace,
@@ -98,7 +98,11 @@ def build(args):
     model = FEAModel(fea=[fea])
     h = meshSize(mesh)
     t0 = time.perf_counter()
-    fm = GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2)
+    h_avg = (h.max() + h.min()) / 2
+    if args.filter == "helmholtz":
+        fm = HelmholtzFilterModel(mesh=mesh, beta=args.radius_h, h_avg=h_avg)
+    else:
+        fm = GeneralFilterModel(nel=mesh.n_cell, beta=args.radius_h, coordinates=Q.tabulate_dof_coordinates(), h_avg=h_avg)
     model.add(fm, name="general_filter_model")
     model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.random.default_rng(0).random(mesh.n_cell) * 0.86)
     sim = Simulator(model)                                      # defines the filter operation: W, W^T built here
@@ -512,7 +516,14 @@ def main():
     ap.add_argument("--harmonic", type=int, default=0,
                     help="N harmonic responses of the tip load, 1 to 8, at frequencies below and between the first eigenfrequencies "
                          "of the start design: every solve one batched MINRES; prints the iterations per column and the cycle time")
+    ap.add_argument("--filter", choices=("neighbours", "helmholtz"), default="neighbours",
+                    help="the explicit neighbour list (default) or the Helmholtz PDE filter; single load case, no --harmonic")
+    ap.add_argument("--radius-h", type=float, default=2.0, help="filter radius in units of the mean cell size (default 2)")
     args = ap.parse_args()
+    if (args.filter != "neighbours" or args.radius_h != 2.0) and (args.load_cases > 1 or args.harmonic):
+        ap.error("--filter / --radius-h: with the single load case only")
+    if not args.no_scipy and (args.filter != "neighbours" or args.radius_h != 2.0):
+        ap.error("the SciPy cycle restates the neighbour filter at 2 h: add --no-scipy")
     if not 1 <= args.load_cases <= 8:
         ap.error("--load-cases: 1 to 8")
     if args.loss_factor is not None and not (1 <= args.harmonic <= 4 and np.isfinite(args.loss_factor) and args.loss_factor >= 0.0):
@@ -568,6 +579,7 @@ def main():
     if args.pc == "multilevel":
         pci = dev.pc_info()
         out.update(pc_levels=pci["levels"], pc_build_ms=pci["build_ms"], pc_nodes=pci["nodes"], pc_lattice_bytes=pci["bytes"])
+    out.update(filter=args.filter, filter_radius_h=args.radius_h)
     if not args.no_scipy:
         h = np.asarray(__import__("femo_amd.fea.mesh", fromlist=["meshSize"]).meshSize(mesh))
         sc_ms, sc_J, sc_g = scipy_cycle(mesh, facets, t, np.array(sim["density_unfiltered"]), 2.0 * (h.max() + h.min()) / 2)

@@ -10,6 +10,8 @@ loop with the device-resident MMA update in the place of modopt's SLSQP / SNOPT.
                       its sharpness: --every design steps per value (BetaContinuation); without --betas: today's model
   ... --eta 0.5|volume            the projection's threshold: a number in [0, 1] or the volume-preserving one
   ... --solid-frame W             a passive solid strip of W cells along the loaded edge (needs --betas; --betas 0 projects nothing else)
+  ... --filter helmholtz          the Helmholtz PDE filter (HelmholtzFilterModel, or ProjectedFilterModel(filter="helmholtz") with
+                      --betas) in the neighbour list's place: one scalar solve per product, memory independent of the radius
 
 Minimises the compliance under avg_density <= 0.40 from x = 0.4.  Prints one JSON line: per step the objective, the
 constraint values and the inner (Newton) iterations; the ms of the MMA update against the ms of the design cycle (the first
@@ -34,7 +36,7 @@ sys.path.insert(0, ROOT)
 
 def build(args):
     from femo_amd.csdl_opt.fea_model import FEAModel
-    from femo_amd.csdl_opt.filter_model import GeneralFilterModel, ProjectedFilterModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel, HelmholtzFilterModel, ProjectedFilterModel
     from femo_amd.csdl_opt.simulator import Simulator
     from femo_amd.fea.elasticity import averageFunc, compliance, pdeRes
     from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, Measure, VectorFunctionSpace,
@@ -74,6 +76,7 @@ def build(args):
     model = FEAModel(fea=[fea])
     h = meshSize(mesh)
     betas = getattr(args, "betas", None)
+    helmholtz = getattr(args, "filter", "neighbours") == "helmholtz"
     if betas:
         from femo_amd.fea.elasticity import cell_volumes
         frame, solid = int(getattr(args, "solid_frame", 0) or 0), None
@@ -82,10 +85,12 @@ def build(args):
                 raise SystemExit("--solid-frame is for the rectangle")
             solid = np.nonzero(mesh.centroids()[:, 0] >= LX - frame * LX / args.nelx - 1e-9)[0]
         eta = getattr(args, "eta", "0.5")
-        filt = ProjectedFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2,
-                                    projection_beta=betas[0], eta=eta if eta == "volume" else float(eta),
-                                    volumes=cell_volumes(mesh), solid=solid)
+        which = dict(filter="helmholtz", mesh=mesh) if helmholtz else dict(coordinates=Q.tabulate_dof_coordinates())
+        filt = ProjectedFilterModel(nel=mesh.n_cell, h_avg=(h.max() + h.min()) / 2, projection_beta=betas[0],
+                                    eta=eta if eta == "volume" else float(eta), volumes=cell_volumes(mesh), solid=solid, **which)
         args.projection = filt
+    elif helmholtz:
+        filt = HelmholtzFilterModel(mesh=mesh, beta=2.0, h_avg=(h.max() + h.min()) / 2)
     else:
         filt = GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2)
     model.add(filt, name="general_filter_model")
@@ -124,6 +129,8 @@ def main():
     ap.add_argument("--every", type=int, default=5)
     ap.add_argument("--eta", default="0.5")
     ap.add_argument("--solid-frame", type=int, default=0)
+    ap.add_argument("--filter", choices=("neighbours", "helmholtz"), default="neighbours",
+                    help="the explicit neighbour list (default) or the Helmholtz PDE filter (memory independent of the radius)")
     ap.add_argument("--out", default=os.path.join("topopt_out", "density.xdmf"))
     args = ap.parse_args()
     if args.solid_frame and not args.betas:
