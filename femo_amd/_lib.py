@@ -251,6 +251,7 @@ PROTOTYPES = {
     "femo_elast_destroy": (C.c_int, [H]),
     "femo_elast_info": (C.c_int, [H, c_i64p]),
     "femo_elast_set_fixed": (C.c_int, [H, C.c_void_p]),
+    "femo_elast_set_springs": (C.c_int, [H, C.c_void_p]),
     "femo_elast_set_facets": (C.c_int, [H, c_i64, C.c_void_p]),
     "femo_elast_assemble": (C.c_int, [H, C.c_int, H]),
     "femo_elast_apply": (C.c_int, [H, C.c_int, C.c_double, H, C.c_double, H, H]),
@@ -265,6 +266,7 @@ PROTOTYPES = {
     "femo_elast_pnorm_stress_multi": (C.c_int, [H, C.c_int, H, H, c_f64p, c_f64p, C.c_double, C.c_double, C.c_double, c_f64p,
                                                 H, H, C.c_int]),
     "femo_elast_von_mises_multi": (C.c_int, [H, C.c_int, H, H, c_f64p, C.c_double, C.c_int, H]),
+    "femo_elast_pnorm_disp_multi": (C.c_int, [H, C.c_int, H, H, c_f64p, c_f64p, C.c_double, C.c_double, c_f64p, H, C.c_int]),
     "femo_elast_body_apply": (C.c_int, [H, C.c_int, c_f64p, C.c_int, C.c_double, H, H, C.c_int, H, C.c_int]),
     "femo_elast_mass_apply_multi": (C.c_int, [H, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, H, H, H]),
     "femo_elast_block_gram": (C.c_int, [H, C.c_int, H, C.c_int, H, c_f64p]),

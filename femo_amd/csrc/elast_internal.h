@@ -1,7 +1,7 @@
 // Shared by elasticity.hip (assembly, dR/drho, load, export, filter), elast_solve.hip (block product, PCG and the poll loop
 // of every batched Krylov solve), elast_pc.hip (multilevel preconditioner), elast_stress.hip (stress aggregate), each for
-// one or several load cases, elast_block.hip (block linear algebra and the block iteration of the eigen solves),
-// elast_eig.hip (mass product and the eigenfrequency pencil), elast_buckle.hip (geometric stiffness and the buckling
+// one or several load cases, elast_disp.hip (displacement aggregate), elast_block.hip (block linear algebra and the block
+// iteration of the eigen solves), elast_eig.hip (mass product and the eigenfrequency pencil), elast_buckle.hip (geometric stiffness and the buckling
 // pencil), elast_harm.hip (assembled mass, shifted product and MINRES of the harmonic response), elast_damp.hip (complex
 // product and COCR of the damped response) and elast_transient.hip (Newmark march, its banded product and dR/drho).  The
 // static and the banded SELL product of these units are prologues and epilogues around one row walk, elast_row_walk below;
@@ -28,6 +28,10 @@ struct femo_elast {
   double* d_dinv = nullptr;     // n_rows * d^2: inverse of the (masked) diagonal blocks
   uint8_t* d_fixed = nullptr;   // n_dof, optional
   bool has_fixed = false;
+  // elastic supports (femo_elast_set_springs): one stiffness per dof; the operator is K(rho) + diag(springs) from the next
+  // assembly on (k_elast_springs after k_elast_assemble; the lattice blocks take them in k_pc_springs)
+  double* d_springs = nullptr;  // n_dof, optional
+  bool has_springs = false;
   bool assembled = false;
   // tagged facets: vertex -> facet CSR (vertex ids of the facets, d per facet)
   int64_t n_facets = 0;
@@ -46,6 +50,8 @@ struct femo_elast {
   // stress aggregate (femo_elast_pnorm_stress, femo_elast_pnorm_stress_multi): FEMO_ELAST_MAX_COLS slabs of partials, one per
   // column, and the folded values behind them, on first use
   double* w_smpart = nullptr;
+  // displacement aggregate (femo_elast_pnorm_disp_multi, elast_disp.hip): the same layout over the blocks of the vertices
+  double* w_dpart = nullptr;
   // block iteration (elast_block.hip), on first use: the right-hand sides B = Op X of w_eig_cols columns; the Gram partials
   // and their folded values, with their pinned mirror
   double* w_eig = nullptr;
@@ -66,7 +72,7 @@ struct femo_elast {
   int w_harm_cols = 0;
   double* w_ms = nullptr;
   double* h_ms = nullptr;       // pinned
-  // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set) through pc_dirty
+  // multilevel preconditioner (femo_elast_pc_setup); its Galerkin blocks follow (K, fixed set, springs) through pc_dirty
   // Newmark march (elast_transient.hip), on first use: the step's right-hand side, the two windows of FEMO_ELAST_MAX_COLS
   // combined columns of dR/drho (w_nm: 1 + 2 FEMO_ELAST_MAX_COLS vectors) and the inverse diagonal blocks of K + sigma M
   double* w_nm = nullptr;

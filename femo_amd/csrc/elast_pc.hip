@@ -22,7 +22,8 @@
 // follow exactly (bin >> 1, (frac + (bin & 1)) / 2).  The restriction CSR carries the products of the same fractions, so
 // the restriction is the exact transpose of the gather.
 //
-// Galerkin blocks (k_pc_blocks, once per assembled K or fixed set).  With g_r = sum_a w_aI m_ar grad(lambda_a) -- w_aI the
+// Galerkin blocks (k_pc_blocks, once per assembled K, fixed set or set of springs; with elastic supports k_pc_springs adds
+// P_l^T diag(k) P_l behind it).  With g_r = sum_a w_aI m_ar grad(lambda_a) -- w_aI the
 // hat of node I at vertex a, m_ar = 0 on a fixed dof -- cell e adds C(rho_e) |T_e| (lam0 g_r[r] g_c[c] + mu0 (g_r[c] g_c[r]
 // + delta_rc g_r . g_c)) to entry (r, c) of the block of node I.  The hats are evaluated at the nodes of the cell's bin
 // range, so a cell that straddles bins needs no de-duplication.  Fine levels add with fp64 atomics straight into the
@@ -174,6 +175,66 @@ __global__ __launch_bounds__(EB) void k_pc_blocks(int64_t n_cell, const int32_t*
               if (val != 0.0) atomicAdd(&dst[node * DD + r * D + cc], val);
             }
         }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int64_t i = threadIdx.x; i < nacc; i += EB) {
+      const double a = acc[i];
+      if (a != 0.0) atomicAdd(&G[i], a);
+    }
+  }
+}
+
+// Elastic supports in the blocks: P_l^T diag(k) P_l adds w_vI^2 k[d v + r] to entry (r, r) of the block of every node I under
+// whose hat vertex v lies (fixed dofs skipped: their row of P_l is zero).  One thread per vertex; the bin and fraction on
+// level L - shift follow from the finest ones as in k_pc_final, one halving per level, so P_l is that of the apply.  fp64
+// atomics like k_pc_blocks, behind its launches on the same stream: straight into the lattice on fine levels, per workgroup in
+// LDS with one flush on the levels that fit (a foundation under every vertex would otherwise send n_vert 2^d d atomics to the
+// handful of addresses of the coarsest levels).
+template <int D, bool LDS>
+__global__ __launch_bounds__(EB) void k_pc_springs(int64_t n_vert, const double* __restrict__ k, const uint8_t* __restrict__ fixed,
+                                                   const int32_t* __restrict__ vbin, const double* __restrict__ vfrac, PcLat L,
+                                                   int shift, double* __restrict__ G) {
+  constexpr int DD = D * D;
+  extern __shared__ double acc[];
+  const int64_t nacc = L.nodes * DD;
+  if (LDS) {
+    for (int64_t i = threadIdx.x; i < nacc; i += EB) acc[i] = 0.0;
+    __syncthreads();
+  }
+  double* dst = LDS ? acc : G;
+  for (int64_t v = (int64_t)blockIdx.x * EB + threadIdx.x; v < n_vert; v += (int64_t)gridDim.x * EB) {
+    double kr[D];
+    bool any = false;
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      kr[r] = (fixed && fixed[v * D + r]) ? 0.0 : k[v * D + r];
+      any = any || kr[r] != 0.0;
+    }
+    if (!any) continue;
+    int b[D];
+    double f[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) { b[i] = vbin[v * D + i]; f[i] = vfrac[v * D + i]; }
+    for (int s = 0; s < shift; ++s) {
+#pragma unroll
+      for (int i = 0; i < D; ++i) { f[i] = 0.5 * (f[i] + (double)(b[i] & 1)); b[i] >>= 1; }
+    }
+    for (int corner = 0; corner < (1 << D); ++corner) {
+      int ijk[3] = {0, 0, 0};
+      double w = 1.0;
+#pragma unroll
+      for (int i = 0; i < D; ++i) {
+        const int up = (corner >> i) & 1;
+        ijk[i] = b[i] + up;
+        w *= up ? f[i] : 1.0 - f[i];
+      }
+      if (w == 0.0) continue;
+      const int64_t node = pc_node(L, ijk[0], ijk[1], ijk[2]);
+#pragma unroll
+      for (int r = 0; r < D; ++r)
+        if (kr[r] != 0.0) atomicAdd(&dst[node * DD + r * D + r], w * w * kr[r]);
+    }
   }
   if (LDS) {
     __syncthreads();
@@ -463,6 +524,18 @@ int pc_build_blocks(femo_elast* e, const double* rho) {
       hipLaunchKernelGGL((k_pc_blocks<D, false>), dim3(pc_grid(m->n_cell)), dim3(EB), 0, st, m->n_cell, m->d_conn, m->d_x,
                          rho, e->method, e->lam0, e->mu0, fx, P.lat[l], F, to_level, P.lo[0], P.lo[1], P.lo[2], G);
   }
+  if (e->has_springs)
+    for (int l = 0; l < P.n_levels; ++l) {
+      double* G = pc->d_G + P.off[l] * DD;
+      const int shift = P.n_levels - 1 - l;
+      if (P.lat[l].nodes * DD <= PC_LDS_DOUBLES)
+        hipLaunchKernelGGL((k_pc_springs<D, true>), dim3(std::min<unsigned>(pc_grid(m->n_vert), PC_LDS_GRID)), dim3(EB),
+                           (size_t)P.lat[l].nodes * DD * sizeof(double), st, m->n_vert, e->d_springs, fx, pc->d_vbin, pc->d_vfrac,
+                           P.lat[l], shift, G);
+      else
+        hipLaunchKernelGGL((k_pc_springs<D, false>), dim3(pc_grid(m->n_vert)), dim3(EB), 0, st, m->n_vert, e->d_springs, fx,
+                           pc->d_vbin, pc->d_vfrac, P.lat[l], shift, G);
+    }
   hipLaunchKernelGGL(k_pc_invert<D>, dim3(pc_grid(total)), dim3(EB), 0, st, total, pc->d_G, pc->d_C);
   FEMO_HIP_CHECK(hipGetLastError());
   FEMO_HIP_CHECK(hipEventRecord(pc->ev1, st));

@@ -83,6 +83,38 @@ __global__ __launch_bounds__(EB) void k_elast_assemble(
   for (int q = 0; q < DD; ++q) dinv[row * DD + q] = Bi[q];
 }
 
+// Elastic supports: K_s = K + diag(k).  After k_elast_assemble, and only when springs are set: the thread of a row with a
+// non-zero spring adds k[d row + r] to entry (r, r) of its diagonal block and recomputes the block's inverse (the fixed byte
+// first, as in the assembly: a spring on a fixed dof stays in the unmasked operator and out of the masked one).  One writer
+// per entry, no atomics.  A row without springs is not touched.
+template <int D>
+__global__ __launch_bounds__(EB) void k_elast_springs(int64_t n_rows, const double* __restrict__ k,
+                                                      const uint8_t* __restrict__ fixed, double* __restrict__ diag,
+                                                      double* __restrict__ dinv) {
+  constexpr int DD = D * D;
+  const int64_t row = (int64_t)blockIdx.x * EB + threadIdx.x;
+  if (row >= n_rows) return;
+  double kr[D];
+  bool any = false;
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    kr[r] = k[row * D + r];
+    any = any || kr[r] != 0.0;
+  }
+  if (!any) return;
+  double B[DD], Bi[DD];
+#pragma unroll
+  for (int q = 0; q < DD; ++q) B[q] = diag[row * DD + q];
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    B[r * D + r] += kr[r];
+    diag[row * DD + r * D + r] = B[r * D + r];
+  }
+  block_inverse_fixed<D>(B, fixed ? fixed + row * D : nullptr, Bi);
+#pragma unroll
+  for (int q = 0; q < DD; ++q) dinv[row * DD + q] = Bi[q];
+}
+
 // ---------------------------------------------------------------------------------------------- dR/drho ----
 // rev: y_c (+)= C'(rho_c) |T| (lam div w div u + 2 mu eps(w) : eps(u)) = C'(rho_c) w_c^T K0_c u_c
 template <int D>
@@ -420,9 +452,9 @@ int femo_elast_create(femo_mesh* m, double E, double nu, femo_elast** out) {
 int femo_elast_destroy(femo_elast* e) {
   if (!e) return 0;                    // hipFree waits for the device; the mesh may already be gone
   femo_elast_pc_free(e);
-  hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed);
+  hipFree(e->d_vals); hipFree(e->d_diag); hipFree(e->d_dinv); hipFree(e->d_fixed); hipFree(e->d_springs);
   hipFree(e->d_fverts); hipFree(e->d_fptr); hipFree(e->d_flist);
-  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_smpart);
+  hipFree(e->w_r); hipFree(e->w_z); hipFree(e->w_p); hipFree(e->w_q); hipFree(e->w_part); hipFree(e->w_s); hipFree(e->w_flag); hipFree(e->w_smpart); hipFree(e->w_dpart);
   hipFree(e->w_eig); hipFree(e->w_gram); hipFree(e->w_gstress);
   hipFree(e->d_mvals); hipFree(e->d_mdiag); hipFree(e->w_harm); hipFree(e->w_ms);
   hipFree(e->w_nm); hipFree(e->d_nm_dinv);
@@ -456,6 +488,27 @@ int femo_elast_set_fixed(femo_elast* e, const uint8_t* mask) {
   FEMO_HIP_CHECK(hipMemcpyAsync(e->d_fixed, mask, n, hipMemcpyHostToDevice, st));
   FEMO_HIP_CHECK(hipStreamSynchronize(st));
   e->has_fixed = true;
+  return 0;
+}
+
+int femo_elast_set_springs(femo_elast* e, const double* k) {
+  FEMO_REQUIRE(e, "null argument");
+  const int64_t n = e->mesh->n_vert * e->d;
+  bool any = false;
+  for (int64_t i = 0; k && i < n; ++i) {
+    FEMO_REQUIRE(std::isfinite(k[i]) && k[i] >= 0.0, "femo_elast_set_springs: the stiffness of dof %lld is %g (need finite, >= 0)",
+                 (long long)i, k[i]);
+    any = any || k[i] != 0.0;
+  }
+  if (any) {
+    hipStream_t st = e->mesh->ctx->stream;
+    if (!e->d_springs) FEMO_TRY(dalloc(&e->d_springs, n));
+    FEMO_HIP_CHECK(hipMemcpyAsync(e->d_springs, k, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    FEMO_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  e->has_springs = any;
+  e->assembled = false;            // the stored operator is that of the old supports: no product before the next assembly
+  e->pc_dirty = true;
   return 0;
 }
 
@@ -499,6 +552,10 @@ int femo_elast_assemble(femo_elast* e, int method, const femo_vec* rho) {
     return elast_launch_rows(e, k_elast_assemble<decltype(dim)::value>, m->d_vptr, m->d_visit_cell, m->d_visit_slots, m->d_mptr,
                              m->d_rowlen, m->d_conn, m->d_x, rho->d, method, e->lam0, e->mu0, fx, e->d_vals, e->d_diag, e->d_dinv);
   }));
+  if (e->has_springs)
+    FEMO_TRY(elast_dispatch_d(e->d, [&](auto dim) {
+      return elast_launch_rows(e, k_elast_springs<decltype(dim)::value>, e->d_springs, fx, e->d_diag, e->d_dinv);
+    }));
   e->assembled = true;
   e->pc_dirty = true;
   e->method = method;

@@ -1,6 +1,6 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
-product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip,
+product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, the displacement aggregate in csrc/elast_disp.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip,
 buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip, the harmonic response in csrc/elast_harm.hip, its damped form in csrc/elast_damp.hip, the transient response in csrc/elast_transient.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
@@ -20,6 +20,14 @@ are used unchanged.
                        reference's script.  RAMP is the usual stiffness law here (SIMP's rho^3 against the linear mass gives
                        large displacements at low density), and the exact reduced gradient needs
                        ``fea.consistent_bc_partials = True``: F(rho) is non-zero on clamped vertices
+  elastic supports     ``springs`` of the static residuals: K_s(rho) = K(rho) + diag(k), one stiffness k >= 0 per dof from
+                       `point_springs` (a workpiece, an input or output port) and `facet_springs` (a Winkler foundation, lumped
+                       like the traction).  The handle carries them into the product, block-Jacobi and the lattice blocks of
+                       the multilevel preconditioner; they do not depend on rho.  Not in the reference's script
+  ElasticityDisplacement  J = sum_l w_l l_l . u_l: the displacement of a port (`port_displacement`) or the mean displacement
+                       of a boundary (`mean_displacement`); with two port springs the objective of a compliant mechanism
+  ElasticityPnormDisplacement  J = (1/alpha) sum_v a_v (m |u_v|)^p over a vertex list, a tagged boundary or the whole mesh:
+                       "no vertex of this region moves more than delta" as one smooth output (csrc/elast_disp.hip)
   averageFunc          (1/|Omega|) int rho dx as a LinearFunctional with the DG0 coefficient |T_e| / |Omega| (:103-106)
   ElasticityPnormStress  J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p, the aggregated von Mises stress of the solid
                        material: sigma_vm = sqrt(3/2 s : s), s the deviator of sigma_0(u) as a 3 x 3 tensor (plane strain in
@@ -117,6 +125,7 @@ class DeviceElasticity:
         self.info = dict(zip(_lib.ELAST_INFO_KEYS, (int(v) for v in buf)))
         self.d, self.n_dof = self.info["dim"], self.info["n_dof"]
         self.fixed_key = None
+        self.springs_key = None
         self.facets_key = None
         self.pc_plan = None                # set by pc_setup: dict(levels, bytes, nodes)
         self._rho = None
@@ -130,6 +139,20 @@ class DeviceElasticity:
         assert m.size == self.n_dof
         check(self.lib.femo_elast_set_fixed(self.handle, _ptr(m)))
         self.fixed_key = hash(m.tobytes())
+
+    def set_springs(self, k: Optional[np.ndarray]) -> None:
+        """Elastic supports: one stiffness >= 0 per dof (None or all zeros: none).  The operator is K(rho) + diag(k) from the
+        next `assemble` on; until then products and solves are refused."""
+        if k is None:
+            check(self.lib.femo_elast_set_springs(self.handle, None))
+            self.springs_key = None
+        else:
+            a = np.ascontiguousarray(k, dtype=np.float64).ravel()
+            if a.size != self.n_dof:
+                raise _lib.FemoError(f"set_springs: {self.n_dof} dofs need as many stiffnesses, got {a.size}")
+            check(self.lib.femo_elast_set_springs(self.handle, _ptr(a)))
+            self.springs_key = hash(a.tobytes()) if a.any() else None
+        self._owner = None                 # whoever assembled last: K is gone
 
     def set_facets(self, facets: np.ndarray) -> None:
         f = np.ascontiguousarray(facets, dtype=np.int32).reshape(-1, self.d)
@@ -575,6 +598,26 @@ class DeviceElasticity:
                                                      None if grad_rho is None else grad_rho.handle, int(bool(accumulate))))
         return vals[:n_cols] if value else None
 
+    def pnorm_disp_multi(self, n_cols: int, u: Vec, a: Vec, m, p: float, alpha: float = 0.0, weights=None, value: bool = True,
+                         grad_u: Optional[Vec] = None, accumulate: bool = False):
+        """J_l = (1/alpha) sum_v a_v (m_l |u_{l,v}|)^p with the nodal weights ``a`` (n_vert, >= 0) for every column (the array
+        of the ``n_cols`` unweighted values is returned when ``value``), column l of ``grad_u`` (+)= w_l dJ_l/du_l.
+        ``alpha`` <= 0: sum_v a_v.  ``m``: a scalar or one scale per column; ``weights``: one per column, 1 without."""
+        n_cols = self._cols(n_cols, u, grad_u)
+        mv = np.ascontiguousarray(m, dtype=np.float64).ravel()
+        if np.ndim(m) == 0:
+            mv = np.full(max(n_cols, 0), float(m))
+        wv = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        if mv.size != n_cols or (wv is not None and wv.size != n_cols):
+            raise _lib.FemoError(f"pnorm_disp_multi: {n_cols} columns need as many scales and weights")
+        vals = np.zeros(max(n_cols, 1))
+        f64 = lambda a: a.ctypes.data_as(_lib.c_f64p)
+        check(self.lib.femo_elast_pnorm_disp_multi(self.handle, n_cols, u.handle, a.handle, f64(mv),
+                                                   None if wv is None else f64(wv), float(p), float(alpha),
+                                                   f64(vals) if value else None, None if grad_u is None else grad_u.handle,
+                                                   int(bool(accumulate))))
+        return vals[:n_cols] if value else None
+
     def von_mises_multi(self, n_cols: int, u: Vec, out: Vec, rho: Optional[Vec] = None, q: float = 0.0, scales=None,
                         column: Optional[int] = None) -> Vec:
         """out[n_cell] = max_l s_l rho_e^q sigma_vm,e(u_l), or s_column rho_e^q sigma_vm,e(u_column) with ``column``."""
@@ -933,15 +976,113 @@ def _load_vec(mesh, facets: np.ndarray, t: np.ndarray) -> Vec:
     return F
 
 
+def _check_springs(name: str, springs, n_dof: int) -> Optional[np.ndarray]:
+    """The per-dof stiffnesses as a contiguous float array, or None for none (None, or all zeros)."""
+    if springs is None:
+        return None
+    k = np.ascontiguousarray(springs, dtype=np.float64).ravel()
+    if k.size != n_dof:
+        raise ValueError(f"{name}: {n_dof} dofs need as many spring stiffnesses, got {k.size}")
+    if not (np.all(np.isfinite(k)) and np.all(k >= 0.0)):
+        raise ValueError(f"{name}: spring stiffnesses must be finite and >= 0")
+    return k.copy() if k.any() else None
+
+
+def _one_space(name: str, V) -> VectorFunctionSpace:
+    """The space of one displacement field: V itself, or the base of a LoadCaseSpace."""
+    V = V.base if isinstance(V, LoadCaseSpace) else V
+    if not isinstance(V, VectorFunctionSpace):
+        raise NotImplementedError(f"{name} needs a VectorFunctionSpace(mesh, ('CG', 1))")
+    return V
+
+
+def facet_measures(mesh, facets: np.ndarray) -> np.ndarray:
+    """|f| of every facet (rows of tdim vertex ids): edge lengths in 2-D, triangle areas in 3-D."""
+    f = np.asarray(facets, dtype=np.int64).reshape(-1, mesh.tdim)
+    p = mesh.x[f][:, :, :mesh.tdim]
+    if mesh.tdim == 2:
+        return np.linalg.norm(p[:, 1] - p[:, 0], axis=1)
+    return 0.5 * np.linalg.norm(np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), axis=1)
+
+
+def lumped_facet_measure(mesh, facets: np.ndarray) -> np.ndarray:
+    """(n_vert,) sum_{f around v} |f| / d: the lumping of the traction load (femo_elast_load)."""
+    f = np.asarray(facets, dtype=np.int64).reshape(-1, mesh.tdim)
+    out = np.zeros(mesh.n_vert)
+    np.add.at(out, f.ravel(), np.repeat(facet_measures(mesh, f) / mesh.tdim, mesh.tdim))
+    return out
+
+
+def lumped_cell_volume(mesh) -> np.ndarray:
+    """(n_vert,) sum_{e around v} |T_e| / (d + 1)."""
+    out = np.zeros(mesh.n_vert)
+    np.add.at(out, mesh.conn.ravel(), np.repeat(cell_volumes(mesh) / (mesh.tdim + 1), mesh.tdim + 1))
+    return out
+
+
+def point_springs(V, dofs, k) -> np.ndarray:
+    """Per-dof stiffnesses of springs ``k`` (a scalar or one per entry) on the dofs ``dofs`` of V (a workpiece, an input or
+    output port); repeated dofs add up, and so do the arrays of several supports."""
+    V = _one_space("point_springs", V)
+    dofs = np.atleast_1d(np.asarray(dofs, dtype=np.int64)).ravel()
+    kv = np.broadcast_to(np.asarray(k, dtype=np.float64), dofs.shape)
+    if dofs.size and (dofs.min() < 0 or dofs.max() >= V.dim):
+        raise ValueError(f"point_springs: dof out of range (0 to {V.dim - 1})")
+    if not (np.all(np.isfinite(kv)) and np.all(kv >= 0.0)):
+        raise ValueError("point_springs: spring stiffnesses must be finite and >= 0")
+    out = np.zeros(V.dim)
+    np.add.at(out, dofs, kv)
+    return out
+
+
+def facet_springs(V, ds: "Measure", kappa) -> np.ndarray:
+    """Per-dof stiffnesses of a Winkler foundation of stiffness per area ``kappa`` (a scalar or a d-vector) on the facets of
+    ``ds``, lumped like the traction load: k_{v,i} = kappa_i sum_{f around v} |f| / d."""
+    V = _one_space("facet_springs", V)
+    d = V.mesh.tdim
+    kap = np.asarray(kappa, dtype=np.float64).ravel()
+    kap = np.full(d, kap[0]) if kap.size == 1 else kap
+    if kap.size != d or not (np.all(np.isfinite(kap)) and np.all(kap >= 0.0)):
+        raise ValueError(f"facet_springs: kappa is a scalar or {d} components, finite and >= 0")
+    return (lumped_facet_measure(V.mesh, ds.facets())[:, None] * kap[None, :]).ravel()
+
+
+def port_displacement(V, dofs, coeffs=1.0) -> np.ndarray:
+    """The vector l of a point output u_out = l . u: ``coeffs`` (a scalar or one per entry) on the dofs ``dofs`` of V."""
+    V = _one_space("port_displacement", V)
+    dofs = np.atleast_1d(np.asarray(dofs, dtype=np.int64)).ravel()
+    cv = np.broadcast_to(np.asarray(coeffs, dtype=np.float64), dofs.shape)
+    if dofs.size == 0 or dofs.min() < 0 or dofs.max() >= V.dim:
+        raise ValueError(f"port_displacement: needs dofs in 0 to {V.dim - 1}")
+    out = np.zeros(V.dim)
+    np.add.at(out, dofs, cv)
+    return out
+
+
+def mean_displacement(V, direction, ds: "Measure") -> np.ndarray:
+    """The vector l of the mean displacement of the facets of ``ds`` along ``direction``: the traction load of ``direction``
+    (femo_elast_load) over |Gamma|."""
+    V = _one_space("mean_displacement", V)
+    t = _traction(direction, V.mesh)
+    w = lumped_facet_measure(V.mesh, ds.facets())
+    if not w.sum() > 0.0:
+        raise ValueError("mean_displacement: the measure has no facets")
+    return (w[:, None] * t[None, :]).ravel() / w.sum()
+
+
 def _owned_stiffness(owner, mask: Optional[np.ndarray]) -> DeviceElasticity:
     """The handle of ``owner`` (its ``device()``, ``rho``, ``method_id``, ``preconditioner``) with K(rho) of the current density
-    and the fixed set ``mask``: reassembled when the density (its version or its vector), the fixed set, the method or the
-    owner changed since the last assembly on this handle."""
+    and the fixed set ``mask``, and with the owner's elastic supports (its ``springs``, none without the attribute):
+    reassembled when the density (its version or its vector), the fixed set, the springs, the method or the owner changed
+    since the last assembly on this handle."""
     dev = owner.device()
     want = None if mask is None else hash(mask.tobytes())
     if dev.fixed_key != want:
         dev.set_fixed(mask)
-    key = (owner.rho.version, id(owner.rho.vec), dev.fixed_key, owner.method_id, id(owner))
+    springs = getattr(owner, "springs", None)     # the handle is shared per mesh: an owner without springs clears them
+    if dev.springs_key != (None if springs is None else hash(springs.tobytes())):
+        dev.set_springs(springs)
+    key = (owner.rho.version, id(owner.rho.vec), dev.fixed_key, dev.springs_key, owner.method_id, id(owner))
     if getattr(dev, "_owner", None) != key:
         dev.assemble(owner.method_id, owner.rho.vec)
         dev._owner = key
@@ -1121,7 +1262,10 @@ def _multi_arguments(name: str, u: Function, tractions, measures, body_forces=No
 
 
 class ElasticityResidual(BackendForm):
-    """R(u; rho) = K(rho) u - F(rho) with F = the tagged traction ``ds`` (see the module docstring) plus, with
+    """R(u; rho) = K_s(rho) u - F(rho), K_s = K(rho) + diag(springs) with the elastic supports ``springs`` (one stiffness >= 0
+    per dof, from `point_springs` / `facet_springs`; None: K itself; they do not depend on rho, so dR/drho is unchanged), and
+    F = the tagged traction ``ds`` (see the module docstring) plus the nodal forces ``point_load`` (one value per dof, the
+    input force of a mechanism's port; ``traction`` may then be None) plus, with
     ``body_force`` b (mass density times acceleration, constant), the self-weight G_b rho: rho_e |T_e| b / (d + 1) at every
     vertex of cell e.  ``traction`` may be None with a body force.  ``n_cases`` columns (one here), ``n_dof`` dofs per
     column; every product and solve is the batched one over all columns.
@@ -1137,19 +1281,26 @@ class ElasticityResidual(BackendForm):
     matrix_class = ElasticityMatrix
 
     def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, E: float = 1.0,
-                 nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None):
+                 nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None, springs=None,
+                 point_load=None):
         V = u.function_space
         if not isinstance(V, VectorFunctionSpace):
             raise NotImplementedError("ElasticityResidual needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
         self.t = _traction(traction, V.mesh)
         self.ds = ds if ds is not None else Measure("ds", domain=V.mesh)
         body = _body_forces("ElasticityResidual", None if body_force is None else [body_force], 1, V.mesh)
-        if self.t is None and body is None:
-            raise ValueError("ElasticityResidual: without a traction the load needs a body force")
-        self._setup(u, rho, V, 1, [self.t], [self.ds], E, nu, method, preconditioner, body)
+        if point_load is not None:
+            point_load = np.ascontiguousarray(point_load, dtype=np.float64).ravel().copy()
+            if point_load.size != V.dim or not np.all(np.isfinite(point_load)):
+                raise ValueError(f"ElasticityResidual: the point load needs {V.dim} finite entries")
+        if self.t is None and body is None and point_load is None:
+            raise ValueError("ElasticityResidual: without a traction the load needs a body force or a point load")
+        self._setup(u, rho, V, 1, [self.t], [self.ds], E, nu, method, preconditioner, body, springs)
+        self.point_load = point_load
 
-    def _setup(self, u, rho, V, n_cases, tractions, measures, E, nu, method, preconditioner, body=None) -> None:
-        """``V``: the space of one column (the numbering of the bcs); ``body``: (n_cases, tdim) body forces or None."""
+    def _setup(self, u, rho, V, n_cases, tractions, measures, E, nu, method, preconditioner, body=None, springs=None) -> None:
+        """``V``: the space of one column (the numbering of the bcs and of the springs); ``body``: (n_cases, tdim) body forces
+        or None; ``springs``: one stiffness per dof of V or None."""
         if rho.function_space.family != "DG" or rho.function_space.mesh is not V.mesh:
             raise NotImplementedError(f"{type(self).__name__} needs a DG0 density on the state's mesh")
         if method not in METHODS:
@@ -1162,6 +1313,8 @@ class ElasticityResidual(BackendForm):
         self.n_cases, self.n_dof = n_cases, V.dim
         self.tractions, self.measures = tractions, measures
         self.body = body
+        self.springs = _check_springs(type(self).__name__, springs, V.dim)
+        self.point_load, self._point_vec = None, None
         self._body_load = self._body_rhs = None
         if body is not None:
             self._body_load, self._body_rhs = _BodyLoad(V.mesh, rho, body), _BodyLoad(V.mesh, rho, body)
@@ -1180,7 +1333,14 @@ class ElasticityResidual(BackendForm):
         return elasticity_handle(self.mesh, self.E, self.nu)
 
     def _traction_load(self) -> Optional[Vec]:
-        return _loads_vec(self.mesh, _facets_of(self.measures, self.tractions), self.tractions)
+        """The part of the load that does not depend on the density: the tractions plus the nodal forces ``point_load``."""
+        T = _loads_vec(self.mesh, _facets_of(self.measures, self.tractions), self.tractions)
+        if self.point_load is None:
+            return T
+        if self._point_vec is None or self._point_vec[0] is not T:
+            host = self.point_load if T is None else np.array(T.get(), dtype=np.float64) + self.point_load
+            self._point_vec = (T, Vec(_ctx(), host.size).set(host))
+        return self._point_vec[1]
 
     def load(self) -> Vec:
         """Column l: the total load F_l(rho)."""
@@ -1299,9 +1459,9 @@ class MultiLoadElasticityResidual(ElasticityResidual):
     matrix_class = MultiLoadElasticityMatrix
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, E: float = 1.0, nu: float = 0.3,
-                 method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None):
+                 method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None, springs=None):
         V, ts, dss, body = _multi_arguments("MultiLoadElasticityResidual", u, tractions, measures, body_forces)
-        self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner, body)
+        self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner, body, springs)
         self.solve_counts = {"state": 0, "adjoint": 0}
 
     def _record(self, infos, kind: str):
@@ -1390,6 +1550,128 @@ class MultiLoadCompliance(Compliance):
             raise ValueError(f"MultiLoadCompliance: {V.n_cases} load cases need as many weights")
         self._set_body("MultiLoadCompliance", body, rho)
         self._grad = {}
+
+
+class ElasticityDisplacement(BackendForm):
+    """J = sum_l w_l l_l . u_l for host vectors l_l in the numbering of the base space (`port_displacement`,
+    `mean_displacement`): the displacement of a port, the mean displacement of a boundary.  dJ/du = w l: `Compliance` with
+    another vector.  ``ell``: one vector (used for every column) or one per column."""
+    rank = 0
+
+    def __init__(self, u: Function, ell, weights=None):
+        V = u.function_space
+        base = _one_space("ElasticityDisplacement", V)
+        L = V.n_cases if isinstance(V, LoadCaseSpace) else 1
+        ell = np.asarray(ell, dtype=np.float64)
+        if ell.ndim == 1:
+            ell = np.tile(ell, (L, 1))
+        if ell.shape != (L, base.dim):
+            raise ValueError(f"ElasticityDisplacement: {L} columns need vectors of {base.dim} entries")
+        if not np.all(np.isfinite(ell)):
+            raise ValueError("ElasticityDisplacement: the vectors must be finite")
+        self.weights = np.ones(L) if weights is None else _per_case("ElasticityDisplacement", "weights", weights, L)
+        self.u, self.mesh, self.n_cases, self.ell = u, V.mesh, L, ell
+        self._vec = None
+        self._grad = {}
+
+    def functions(self):
+        return (self.u,)
+
+    def load(self) -> Vec:
+        """Column l = w_l l_l on the device (uploaded once)."""
+        if self._vec is None:
+            self._vec = Vec(_ctx(), self.ell.size).set((self.weights[:, None] * self.ell).ravel())
+        return self._vec
+
+    def values(self) -> np.ndarray:
+        """The unweighted l_l . u_l of the current state (host)."""
+        return np.einsum("ln,ln->l", self.ell, np.asarray(self.u.vec.get(), dtype=np.float64).reshape(self.n_cases, -1))
+
+    def assemble_scalar(self) -> float:
+        return self.load().dot(self.u.vec, self.u.function_space.dim)
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        return out.copy_from(self.load()) if wrt is self.u else out.fill(0.0)
+
+
+class ElasticityPnormDisplacement(BackendForm):
+    """J = sum_l w_l J_l, J_l = (1/alpha) sum_v a_v (m |u_{l,v}|)^p with alpha = sum_v a_v: the aggregated nodal displacement
+    of a region, the smooth form of "no vertex of this region moves more than delta" (`max_estimate` <= delta).  ``region``:
+    a vertex index array (a_v = 1), a ``ds(tag)`` (a_v = the lumped facet measure) or None (all vertices with their lumped
+    cell volume).  On a plain state or a LoadCaseSpace state; value and dJ/du are one pass over the vertices for all columns
+    (`DeviceElasticity.pnorm_disp_multi`, csrc/elast_disp.hip).  dJ/du is non-zero on clamped dofs of the region: the exact
+    reduced gradient needs ``fea.consistent_bc_partials = True``."""
+    rank = 0
+
+    def __init__(self, u: Function, region=None, m=1.0, p: float = 8.0, weights=None, E: float = 1.0, nu: float = 0.3):
+        V = u.function_space
+        base = _one_space("ElasticityPnormDisplacement", V)
+        mesh = base.mesh
+        L = V.n_cases if isinstance(V, LoadCaseSpace) else 1
+        if region is None:
+            a = lumped_cell_volume(mesh)
+        elif isinstance(region, Measure):
+            a = lumped_facet_measure(mesh, region.facets())
+        else:
+            idx = np.unique(np.asarray(region, dtype=np.int64).ravel())
+            if idx.size == 0 or idx.min() < 0 or idx.max() >= mesh.n_vert:
+                raise ValueError(f"ElasticityPnormDisplacement: the region needs vertices in 0 to {mesh.n_vert - 1}")
+            a = np.zeros(mesh.n_vert)
+            a[idx] = 1.0
+        if not a.sum() > 0.0:
+            raise ValueError("ElasticityPnormDisplacement: the region is empty")
+        self.m = _per_case("ElasticityPnormDisplacement", "scales m", m, L)
+        self.weights = np.ones(L) if weights is None else _per_case("ElasticityPnormDisplacement", "weights", weights, L)
+        if not (np.all(self.m > 0.0) and np.all(np.isfinite(self.m)) and p >= 1.0 and np.isfinite(p)):
+            raise ValueError("the displacement aggregate needs m > 0 and a finite p >= 1")
+        if not np.all(self.weights >= 0.0):
+            raise ValueError("the displacement aggregate needs weights >= 0")
+        self.u, self.mesh, self.n_cases, self.a, self.p = u, mesh, L, a, float(p)
+        self.alpha = float(a.sum())
+        self.E, self.nu = float(E), float(nu)
+        self._a_vec = None
+        self._grad = {}
+        self._values = None
+
+    def functions(self):
+        return (self.u,)
+
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
+
+    def _call(self, **kw):
+        if self._a_vec is None:
+            self._a_vec = Vec(_ctx(), self.a.size).set(self.a)
+        return self.device().pnorm_disp_multi(self.n_cases, self.u.vec, self._a_vec, self.m, self.p, self.alpha,
+                                              weights=self.weights, **kw)
+
+    def values(self) -> Optional[np.ndarray]:
+        """The J_l of the last `assemble_scalar` (unweighted), or None before the first."""
+        return None if self._values is None else self._values.copy()
+
+    def max_estimate(self) -> np.ndarray:
+        """J_l^(1/p) / m_l per column, from the current state: the p-mean of |u_v| over the region, which tends to the
+        maximum from below as p grows."""
+        return self._call() ** (1.0 / self.p) / self.m
+
+    def assemble_scalar(self) -> float:
+        self._values = self._call()
+        return float(self.weights @ self._values)
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        if out is None:
+            out = self._grad.get(id(wrt))
+            if out is None:
+                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        if wrt is self.u:
+            self._call(value=False, grad_u=out)
+        else:
+            out.fill(0.0)
+        return out
 
 
 def cell_volumes(mesh) -> np.ndarray:
@@ -2617,11 +2899,13 @@ def averageFunc(func: Function) -> LinearFunctional:
 
 # ---------------------------------------------------------------------------- builders of the run script (:85-109) ----
 def pdeRes(u, v, rho_e, f, E: float = 1.0, dss: Optional[Measure] = None, method: str = "SIMP",
-           preconditioner: str = "jacobi", body_force=None) -> ElasticityResidual:
+           preconditioner: str = "jacobi", body_force=None, springs=None, point_load=None) -> ElasticityResidual:
     """run_topo_opt_cantilever_beam.py:85-101 (nu = 0.3 as there); ``v`` is implied by the catalogue.  ``body_force``: the
-    self-weight rho b dx (not in the reference's script); ``f`` may then be None."""
+    self-weight rho b dx (not in the reference's script); ``f`` may then be None.  ``springs``: elastic supports, one
+    stiffness per dof (`point_springs`, `facet_springs`), and ``point_load``: nodal forces, one value per dof (a port's input
+    force, built like `port_displacement`); neither is in the reference's script."""
     return ElasticityResidual(u, rho_e, f, dss, E=E, nu=0.3, method=method, preconditioner=preconditioner,
-                              body_force=body_force)
+                              body_force=body_force, springs=springs, point_load=point_load)
 
 
 def compliance(u, f, dss: Optional[Measure] = None, body_force=None, rho_e=None) -> Compliance:
@@ -2630,11 +2914,21 @@ def compliance(u, f, dss: Optional[Measure] = None, body_force=None, rho_e=None)
 
 
 def pdeRes_multiload(u, v, rho_e, fs, dss_list=None, E: float = 1.0, method: str = "SIMP",
-                     preconditioner: str = "jacobi", body_forces=None) -> MultiLoadElasticityResidual:
-    """`pdeRes` for the load cases ``fs[l]`` on ``dss_list[l]`` with the body forces ``body_forces[l]`` (None = none);
-    ``u`` is a Function(LoadCaseSpace(V, len(fs)))."""
+                     preconditioner: str = "jacobi", body_forces=None, springs=None) -> MultiLoadElasticityResidual:
+    """`pdeRes` for the load cases ``fs[l]`` on ``dss_list[l]`` with the body forces ``body_forces[l]`` (None = none) and
+    the elastic supports ``springs`` (the same for every load case); ``u`` is a Function(LoadCaseSpace(V, len(fs)))."""
     return MultiLoadElasticityResidual(u, rho_e, fs, dss_list, E=E, nu=0.3, method=method, preconditioner=preconditioner,
-                                       body_forces=body_forces)
+                                       body_forces=body_forces, springs=springs)
+
+
+def displacement(u, ell, weights=None) -> ElasticityDisplacement:
+    """sum_l w_l l_l . u_l as a scalar output (`port_displacement`, `mean_displacement` build l)."""
+    return ElasticityDisplacement(u, ell, weights=weights)
+
+
+def pnorm_displacement(u, region=None, m=1.0, p: float = 8.0, weights=None) -> ElasticityPnormDisplacement:
+    """The aggregated nodal displacement of a region as a scalar output."""
+    return ElasticityPnormDisplacement(u, region, m=m, p=p, weights=weights)
 
 
 def compliance_multiload(u, fs, dss_list=None, weights=None, body_forces=None, rho_e=None) -> MultiLoadCompliance:

@@ -26,7 +26,8 @@ from .io import XDMFRecorder
 from .mesh import (BeamMesh, Mesh, createIntervalMesh, createRectangleMesh, createUnitCubeMesh, createUnitSquareMesh,
                    findNodeIndices, locate_dofs_geometrical, locate_entities_boundary, meshSize)
 from .elasticity import (Constant, Measure, TransientCompliance, TransientElasticityResidual, buckling_aggregate,
-                         compliance_multiload, dynamic_compliance, dynamic_compliance_damped, eigenvalue_aggregate, meshtags,
+                         compliance_multiload, displacement, dynamic_compliance, dynamic_compliance_damped, eigenvalue_aggregate,
+                         facet_springs, mean_displacement, meshtags, pnorm_displacement, point_springs, port_displacement,
                          pdeRes_harmonic, pdeRes_harmonic_damped, pdeRes_multiload, pdeRes_transient, pnorm_stress,
                          pnorm_stress_multiload, transient_compliance, von_Mises_stress, von_Mises_stress_multiload)
 from ..opt import CSDLProblem, MMA          # noqa: F401  the drivers' last lines (modopt.CSDLProblem + an optimiser)

@@ -632,6 +632,15 @@ int femo_elast_info(const femo_elast* e, int64_t info[FEMO_ELAST_INFO_COUNT]);
 /* Strong Dirichlet dofs (fea.add_strong_bc, :152-156): mask[n_dof] = 1 on fixed dofs; NULL clears.  Used by the masked
  * products (identity rows and columns) and by the block-Jacobi inverse of the next femo_elast_assemble.                  */
 int femo_elast_set_fixed(femo_elast* e, const uint8_t* mask);
+/* Elastic supports (a workpiece or port spring, a Winkler foundation, a structure held by springs alone): k[n_dof] >= 0, one
+ * stiffness per dof, host memory; NULL or all zeros clears them.  A NaN, an infinity or a negative entry is refused and
+ * leaves the handle as it was.  From the next femo_elast_assemble on the handle's operator is K_s(rho) = K(rho) + diag(k):
+ * products, residual, export, block-Jacobi, the shifted and banded operators of the dynamic paths, the eigen and buckling
+ * pencils and the lattice blocks of the multilevel preconditioner (P_l^T diag(k) P_l) all follow.  The call invalidates the
+ * assembled operator: products and solves are refused until the next femo_elast_assemble.  A spring on a fixed dof is
+ * legal: the masked operator keeps its identity row and column there, the unmasked one (and the lifting F - K_s g) carries
+ * it.  The springs do not depend on rho: dR/drho is unchanged.                                                           */
+int femo_elast_set_springs(femo_elast* e, const double* k /* [n_dof] or NULL */);
 /* Tagged boundary facets of ds_(100) (locate_entities_boundary + meshtags, :44-52): d vertex ids per facet.             */
 int femo_elast_set_facets(femo_elast* e, int64_t n_facets, const int32_t* facet_verts);
 /* K(rho) (dolfinx assemble_matrix of derivative(pdeRes, u), fea_dolfinx.py / state_model.py:117-158) and the inverted
@@ -708,6 +717,21 @@ int femo_elast_pnorm_stress_multi(femo_elast* e, int n_cols, const femo_vec* rho
                                   const double* m /* [n_cols] */, const double* w /* [n_cols] or NULL */, double p, double q,
                                   double alpha, double* values /* [n_cols] or NULL */, femo_vec* grad_u, femo_vec* grad_rho,
                                   int accumulate);
+/* Aggregated nodal displacement of n_cols states u_l in one pass (csrc/elast_disp.hip): "no vertex of this region moves more
+ * than delta" as one smooth output,
+ *   J_l = 1/alpha sum_v a_v (m_l |u_{l,v}|)^p,     J = sum_l w_l J_l,     |u_v| = the Euclidean norm of the d components
+ * with nodal weights a[n_vert] >= 0 (a device vector: 1 on a vertex list, the lumped facet or cell measure of a region), one
+ * scale m_l > 0 per load case, weights w_l >= 0 (NULL = 1), p >= 1, and alpha = sum_v a_v when alpha <= 0 is passed.  Either
+ * output may be NULL:
+ *   values[n_cols]          the UNWEIGHTED J_l, folded on the device in a fixed order (the call waits for them)
+ *   grad_u[n_cols * n_dof]  column l (+)= w_l dJ_l/du_l, dJ_l/du_{l,v,i} = p/alpha a_v m_l^p |u_v|^(p-2) u_{v,i}; without
+ *                           accumulate a column with w_l = 0 is written as zeros
+ * A vertex with |u_v| == 0 contributes exact zeros (never a NaN); a vertex with a_v == 0 is skipped without reading u.  A
+ * non-finite entry of u shows in J_l of its column and in the d gradient entries of its vertex, nowhere else.  No float
+ * atomics: the same bits every call, and column l does not depend on n_cols.                                              */
+int femo_elast_pnorm_disp_multi(femo_elast* e, int n_cols, const femo_vec* u, const femo_vec* a /* [n_vert] */,
+                                const double* m /* [n_cols] */, const double* w /* [n_cols] or NULL */, double p, double alpha,
+                                double* values /* [n_cols] or NULL */, femo_vec* grad_u, int accumulate);
 /* out_cells[n_cell] = max_l scale_l rho_e^q sigma_vm,e(u_l), the envelope over the load cases (column = -1), or
  * scale_column rho_e^q sigma_vm,e(u_column) (0 <= column < n_cols).  scale > 0 per load case, NULL = 1; rho may be NULL
  * when q == 0.  With n_cols > 1 a NaN stress reads as 0 in the maximum; one column is written as it is.                */
@@ -919,8 +943,9 @@ int femo_elast_newmark_outer(femo_elast* e, int n_steps, const double* a /* [n_s
  * (the same weights for all d components, zero rows on fixed dofs).  The coarsest lattice has one bin along the shortest
  * axis of the box; every finer one halves the spacing; there are 1 + round(log2(shortest extent / (spacing_factor * mean
  * edge length))) of them (spacing_factor 0 = the default, 2).  The plan is built once per mesh; the d x d blocks are rebuilt
- * inside femo_elast_solve / femo_elast_pc_apply / femo_elast_pc_export_level whenever femo_elast_assemble or
- * femo_elast_set_fixed ran since the last build.  The rebuild reads the density vector of the last femo_elast_assemble,
+ * inside femo_elast_solve / femo_elast_pc_apply / femo_elast_pc_export_level whenever femo_elast_assemble,
+ * femo_elast_set_fixed or femo_elast_set_springs ran since the last build (with springs the blocks are those of
+ * K + diag(k): P_l^T diag(k) P_l is added level by level).  The rebuild reads the density vector of the last femo_elast_assemble,
  * which must still exist and be unchanged (an error otherwise: assemble again); a wrapped vector (femo_vec_wrap) cannot be
  * recognised later, so its blocks are built inside femo_elast_assemble when the plan exists.  femo_elast_pc_setup refuses a
  * mesh whose second-finest lattice exceeds 2^18 nodes: the lattices below the finest are swept by one workgroup.        */

@@ -10,10 +10,15 @@ loop with the device-resident MMA update in the place of modopt's SLSQP / SNOPT.
                       its sharpness: --every design steps per value (BetaContinuation); without --betas: today's model
   ... --eta 0.5|volume            the projection's threshold: a number in [0, 1] or the volume-preserving one
   ... --solid-frame W             a passive solid strip of W cells along the loaded edge (needs --betas; --betas 0 projects nothing else)
+  ... --problem inverter [--kin 0.1 --kout 0.1 --volume 0.3 --move 0.2]   the half model of the force inverter on the 2 x 1
+                      rectangle: input spring and unit input force at the top-left corner, output spring and the objective
+                      u_out (port_displacement) at the top-right corner, a roller on the top (symmetry) edge, a clamp on
+                      x = 0, y <= 0.1; minimises u_out under avg_density <= volume from x = volume
   ... --filter helmholtz          the Helmholtz PDE filter (HelmholtzFilterModel, or ProjectedFilterModel(filter="helmholtz") with
                       --betas) in the neighbour list's place: one scalar solve per product, memory independent of the radius
 
-Minimises the compliance under avg_density <= 0.40 from x = 0.4.  Prints one JSON line: per step the objective, the
+Minimises the compliance under avg_density <= 0.40 from x = 0.4 (--problem cantilever, the default).  Prints one JSON line
+(with --problem inverter also u_out per step and final_u_out): per step the objective, the
 constraint values and the inner (Newton) iterations; the ms of the MMA update against the ms of the design cycle (the first
 step is the warm-up and left out of the statistics: median, minimum, maximum over the others); the bytes a Newton step moves
 by the count of DESIGN.md section 10 and the GB/s that gives; with --host-update the restatement's ms beside the device's,
@@ -102,6 +107,45 @@ def build(args):
     return sim, model, mesh, stress
 
 
+def build_inverter(args):
+    """The compliant-mechanism problem: elastic supports at the two ports and a displacement output as the objective."""
+    from femo_amd.csdl_opt.fea_model import FEAModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.simulator import Simulator
+    from femo_amd.fea.elasticity import averageFunc, pdeRes
+    from femo_amd.fea.fea_hip import (FEA, Function, FunctionSpace, VectorFunctionSpace, createRectangleMesh, displacement,
+                                      locate_dofs_geometrical, meshSize, point_springs, port_displacement)
+    if args.n3:
+        raise SystemExit("--problem inverter is for the rectangle")
+    LX, LY = 2.0, 1.0
+    mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([LX, LY]), args.nelx, args.nely)
+    fea = FEA(mesh)
+    fea.REPORT = False
+    Q, V = FunctionSpace(mesh, ("DG", 0)), VectorFunctionSpace(mesh, ("CG", 1))
+    rho, u = Function(Q), Function(V)
+    corner = lambda cx: int(np.nonzero(np.isclose(mesh.x[:, 0], cx) & np.isclose(mesh.x[:, 1], LY))[0][0])
+    dof_in, dof_out = 2 * corner(0.0), 2 * corner(LX)
+    springs = point_springs(V, [dof_in, dof_out], [args.kin, args.kout])
+    res = pdeRes(u, None, rho, None, preconditioner=args.pc, springs=springs, point_load=port_displacement(V, [dof_in]))
+    fea.add_input("density", rho)
+    fea.add_state(name="displacements", function=u, residual_form=res, arguments=["density"])
+    fea.add_output(name="avg_density", type="scalar", form=averageFunc(rho), arguments=["density"])
+    fea.add_output(name="u_out", type="scalar", form=displacement(u, port_displacement(V, [dof_out])), arguments=["displacements"])
+    ubc = Function(V)
+    ubc.vector.set(0.0)
+    fea.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), lambda x: np.logical_and(np.isclose(x[0], 0.0), x[1] <= 0.1 * LY + 1e-9)),
+                            locate_dofs_geometrical(V.sub(1), lambda x: np.isclose(x[1], LY))], V)
+    model = FEAModel(fea=[fea])
+    h = meshSize(mesh)
+    model.add(GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
+              name="general_filter_model")
+    model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.full(mesh.n_cell, args.volume))
+    model.add_design_variable("density_unfiltered", upper=1.0, lower=1e-3)
+    model.add_objective("u_out")
+    model.add_constraint("avg_density", upper=args.volume)
+    return Simulator(model, device=args.device), model, mesh, None
+
+
 def newton_step_bytes(n, m):
     """Bytes one Newton step without halvings moves ("Optimiser"): the three reading passes and the
     commit each read x, xi, eta, L, U, alpha, beta and p, q of the m + 1 functions; the commit writes x, xi, eta."""
@@ -132,7 +176,15 @@ def main():
     ap.add_argument("--filter", choices=("neighbours", "helmholtz"), default="neighbours",
                     help="the explicit neighbour list (default) or the Helmholtz PDE filter (memory independent of the radius)")
     ap.add_argument("--out", default=os.path.join("topopt_out", "density.xdmf"))
+    ap.add_argument("--problem", choices=("cantilever", "inverter"), default="cantilever")
+    ap.add_argument("--kin", type=float, default=0.1, help="inverter: the input spring")
+    ap.add_argument("--kout", type=float, default=0.1, help="inverter: the output (workpiece) spring")
+    ap.add_argument("--volume", type=float, default=0.3, help="inverter: the volume bound and the start density")
+    ap.add_argument("--move", type=float, default=None, help="the move limit of MMA (cantilever 0.5, inverter 0.2)")
     args = ap.parse_args()
+    inverter = args.problem == "inverter"
+    if inverter and (args.stress or args.betas or args.filter != "neighbours"):
+        raise SystemExit("--problem inverter runs the plain neighbour filter without --stress")
     if args.solid_frame and not args.betas:
         raise SystemExit("--solid-frame needs --betas (passive cells go through the projection)")
     from femo_amd import _lib
@@ -144,7 +196,8 @@ def main():
         raise SystemExit("run_topopt needs a HIP device")
     ctx = Context(0)
     utils_hip.set_context(ctx)
-    sim, model, mesh, stress = build(args)
+    sim, model, mesh, stress = build_inverter(args) if inverter else build(args)
+    utils_hip.LAST_KSP_INFO.clear()          # a complete record of this run's solves
     n = mesh.n_cell
     if stress is not None:
         # the aggregate's scale from the start design, and its bound: 0.9 times its value there
@@ -156,7 +209,8 @@ def main():
     prob = CSDLProblem(problem_name="beam_topo_opt", simulator=sim)
     op = args.projection.operation if args.betas else None
     cont = BetaContinuation(op, args.betas, args.every) if args.betas else None
-    optimizer = MMA(prob, max_iter=args.iters, move=0.5, tol=0.0, sub_tol=1e-7, normalize=True, continuation=cont).setup()
+    move = args.move if args.move is not None else (0.2 if inverter else 0.5)
+    optimizer = MMA(prob, max_iter=args.iters, move=move, tol=0.0, sub_tol=1e-7, normalize=True, continuation=cont).setup()
     host = dict(ms=[], dx=[], newton=[])
     proj_ms = []
     if op is not None:
@@ -210,7 +264,15 @@ def main():
                max_dx=res["max_dx"], update_ms=upd, cycle_ms=cyc, update_share=upd["median"] / (upd["median"] + cyc["median"]),
                newton_per_update=float(np.mean(inner)), newton_step_bytes=step_bytes,
                update_GBps=stats(list(gbps)), density_file=args.out,
-               avg_density=float(np.asarray(sim["avg_density"]).ravel()[0]), final_compliance=float(np.asarray(sim["compliance"]).ravel()[0]))
+               avg_density=float(np.asarray(sim["avg_density"]).ravel()[0]))
+    if inverter:
+        # state and adjoint PCG of every design cycle, in the order they ran
+        pcg_log = [r for r in utils_hip.LAST_KSP_INFO if str(r.get("kind", "")).startswith("elasticity_")]
+        out.update(metric="topopt_mma_inverter", u_out=res["objective"], final_u_out=float(np.asarray(sim["u_out"]).ravel()[0]),
+                   kin=args.kin, kout=args.kout, volume=args.volume, move=move,
+                   pcg_iterations=[[r["kind"].split("_")[-1], r["iterations"]] for r in pcg_log])
+    else:
+        out["final_compliance"] = float(np.asarray(sim["compliance"]).ravel()[0])
     if op is not None:
         pm = stats(proj_ms)
         compute_ms, products_ms = op.time_ms["compute"], op.time_ms["jacvec"]       # of the loop: taken before the calls below
