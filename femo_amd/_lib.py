@@ -35,7 +35,8 @@ ELAST_INFO_KEYS = ("dim", "n_dof", "nnz", "sell_entries", "spmv_bytes")
 ELAST_PC = {"jacobi": 0, "multilevel": 1}
 ELAST_MAX_COLS = 8                # FEMO_ELAST_MAX_COLS: load cases of one batched product / solve
 ELAST_MASS_LAWS = {"linear": 0, "du_olhoff": 1}    # FEMO_ELAST_MASS_LINEAR, FEMO_ELAST_MASS_DU_OLHOFF
-ELAST_PC_INFO_COUNT = 16           # [levels, lattice bytes, block builds, last build us, nodes per level ...]
+ELAST_THERMAL_PRODUCTS = {"N": 0, "T_rho": 1, "T_temp": 2}    # FEMO_ELAST_THERMAL_N, _T_RHO, _T_TEMP
+ELAST_PC_INFO_COUNT = 16          # [levels, lattice bytes, block builds, last build us, nodes per level ...]
 
 
 class SolverOpts(C.Structure):
@@ -268,6 +269,8 @@ PROTOTYPES = {
     "femo_elast_von_mises_multi": (C.c_int, [H, C.c_int, H, H, c_f64p, C.c_double, C.c_int, H]),
     "femo_elast_pnorm_disp_multi": (C.c_int, [H, C.c_int, H, H, c_f64p, c_f64p, C.c_double, C.c_double, c_f64p, H, C.c_int]),
     "femo_elast_body_apply": (C.c_int, [H, C.c_int, c_f64p, C.c_int, C.c_double, H, H, C.c_int, H, C.c_int]),
+    "femo_elast_thermal_apply": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_f64p, C.c_double, H, H, C.c_double, C.c_double,
+                                           C.c_double, H, H, C.c_int, H, C.c_int]),
     "femo_elast_mass_apply_multi": (C.c_int, [H, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, H, H, H]),
     "femo_elast_block_gram": (C.c_int, [H, C.c_int, H, C.c_int, H, c_f64p]),
     "femo_elast_block_rotate": (C.c_int, [H, C.c_int, c_f64p, H, H]),
@@ -314,6 +317,15 @@ PROTOTYPES = {
     "femo_pde_filter_export_csr": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "femo_pde_filter_bytes": (C.c_int, [H, c_i64p]),
     "femo_pde_filter_project": (C.c_int, [H, H, H, H, H, C.POINTER(ProjectInfo)]),
+    # heat conduction with a penalised conductivity (csrc/conduction.hip)
+    "femo_cond_create": (C.c_int, [H, C.POINTER(H)]),
+    "femo_cond_destroy": (C.c_int, [H]),
+    "femo_cond_assemble": (C.c_int, [H, C.c_int, C.c_double, C.c_double, H, H]),
+    "femo_cond_apply": (C.c_int, [H, C.c_int, H, H]),
+    "femo_cond_lift": (C.c_int, [H, H, H, H, H]),
+    "femo_cond_solve": (C.c_int, [H, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
+    "femo_cond_drho": (C.c_int, [H, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, H, H, H, H, C.c_int]),
+    "femo_cond_export_csr": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # Method of Moving Asymptotes (csrc/mma.hip)
     "femo_mma_create": (C.c_int, [H, c_i64, C.c_int, H, H, C.POINTER(MmaParams), C.POINTER(H)]),
     "femo_mma_update": (C.c_int, [H, H, C.c_double, H, c_f64p, H, C.POINTER(MmaInfo)]),

@@ -1,6 +1,6 @@
 """SIMP topology optimisation on the HIP engine: the linear-elasticity state, its loads and outputs, and the device
 handles of the density filter (examples/beam_topo_opt/run_topo_opt_cantilever_beam.py; kernels in csrc/elasticity.hip,
-product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, the displacement aggregate in csrc/elast_disp.hip, body loads in csrc/elast_body.hip, eigenfrequencies in csrc/elast_eig.hip,
+product and PCG in csrc/elast_solve.hip, stress in csrc/elast_stress.hip, the displacement aggregate in csrc/elast_disp.hip, body loads in csrc/elast_body.hip, thermal loads in csrc/elast_thermal.hip, eigenfrequencies in csrc/elast_eig.hip,
 buckling in csrc/elast_buckle.hip, the block iteration of both in csrc/elast_block.hip, the harmonic response in csrc/elast_harm.hip, its damped form in csrc/elast_damp.hip, the transient response in csrc/elast_transient.hip).  One load case is the L = 1 case of several:
 each form is written once, and the MultiLoad... names adapt the constructor arguments and the presentation.
 
@@ -20,6 +20,19 @@ are used unchanged.
                        reference's script.  RAMP is the usual stiffness law here (SIMP's rho^3 against the linear mass gives
                        large displacements at low density), and the exact reduced gradient needs
                        ``fea.consistent_bc_partials = True``: F(rho) is non-zero on clamped vertices
+  thermal loads        ``thermal=ThermalExpansion(alpha, temperature, T_ref, scales)`` of the static residuals and compliances:
+                       sigma = C(rho) (sigma_0(u) - beta_0 theta I) on the 3 x 3 tensor, beta_0 = (3 lambda_0 + 2 mu_0) alpha (the
+                       same constant in plane strain and in 3-D), theta = T - T_ref a number or a CG1 Function.  The load is
+                       F_th = s_l H(C(rho); theta), H(w; theta)[d v + i] = sum_{e around v} w_e beta_0 thetabar_e |T_e| d_i phi_v,
+                       thetabar_e the cell mean (exact for P1): it scales with the stiffness law, not with the mass.  dR/drho
+                       gains -s_l H(C'(rho) . ; theta), and with a temperature Function the form depends on (u, rho, T) with
+                       dR/dT = -s_l H(C(rho); .): one operator, three contractions, one launch each for all load cases
+                       (csrc/elast_thermal.hip).  The temperature may be the state of a `ConductionResidual` (fea/conduction.py)
+                       in another FEA of the same FEAModel: the thermoelastic chain rho -> T -> u -> J, two adjoint solves.
+                       F_th is non-zero on clamped vertices: the exact reduced gradient needs
+                       ``fea.consistent_bc_partials = True``.  The thermal stress is hydrostatic on the 3 x 3 tensor, so the von
+                       Mises outputs below are already the thermoelastic ones.  Not in the harmonic, damped, transient, eigen
+                       and buckling forms (refused); one temperature for all load cases.  Not in the reference's script
   elastic supports     ``springs`` of the static residuals: K_s(rho) = K(rho) + diag(k), one stiffness k >= 0 per dof from
                        `point_springs` (a workpiece, an input or output port) and `facet_springs` (a Winkler foundation, lumped
                        like the traction).  The handle carries them into the product, block-Jacobi and the lattice blocks of
@@ -287,6 +300,34 @@ class DeviceElasticity:
         check(self.lib.femo_elast_body_apply(self.handle, n_cols, b3.ctypes.data_as(_lib.c_f64p), int(bool(transpose)),
                                              float(a), x.handle, None if base is None else base.handle,
                                              int(bool(zero_fixed)), y.handle, int(bool(accumulate))))
+        return y
+
+    def thermal_apply(self, method: int, product: str, n_cols: int, scales, alpha: float, rho: Vec, temperature, y: Vec,
+                      T_ref: float = 0.0, x: Optional[Vec] = None, a: float = 1.0, base: Optional[Vec] = None,
+                      zero_fixed: bool = False, accumulate: bool = False) -> Vec:
+        """The thermal-expansion operator H(w; theta)[d v + i] = sum_{c around v} w_c beta_0 thetabar_c |T_c| d_i phi_v^c in one
+        launch for ``n_cols`` columns with the scales ``scales`` (csrc/elast_thermal.hip); beta_0 = (3 lambda_0 + 2 mu_0)
+        ``alpha``, theta = ``temperature`` - ``T_ref`` with the temperature a Vec of nodal values or a number (uniform).
+        ``product`` "N": column l of y = [y if ``accumulate``, else ``base`` or 0] + a s_l H(w; theta), w = C(rho), or
+        C'(rho) x with the cell vector ``x``; 0 on the dofs of the fixed set when ``zero_fixed``.  "T_rho": y[n_cell] (+)= a
+        C'(rho_c) beta_0 thetabar_c |T_c| sum_l s_l div(x_l)_c and "T_temp": y[n_vert] (+)= a sum_{c around v} C(rho_c) beta_0
+        |T_c| / (d + 1) sum_l s_l div(x_l)_c from the n_cols columns of ``x``: the transposes in w and in theta."""
+        if product not in _lib.ELAST_THERMAL_PRODUCTS:
+            raise _lib.FemoError(f"thermal_apply: unknown product {product!r} (N, T_rho or T_temp)")
+        fwd = product == "N"
+        n_cols = self._cols(n_cols, y if fwd else x, base)
+        s = np.ascontiguousarray(scales, dtype=np.float64).ravel()
+        if s.size != n_cols:
+            raise _lib.FemoError(f"thermal_apply: {n_cols} columns need as many scales")
+        s8 = np.zeros(max(n_cols, 1))
+        s8[:n_cols] = s
+        uniform = not isinstance(temperature, Vec)
+        check(self.lib.femo_elast_thermal_apply(self.handle, int(method), _lib.ELAST_THERMAL_PRODUCTS[product], n_cols,
+                                                s8.ctypes.data_as(_lib.c_f64p), float(alpha), rho.handle,
+                                                None if uniform else temperature.handle, float(temperature) if uniform else 0.0,
+                                                float(T_ref), float(a), None if x is None else x.handle,
+                                                None if base is None else base.handle, int(bool(zero_fixed)), y.handle,
+                                                int(bool(accumulate))))
         return y
 
     # ---- eigenfrequencies: K phi = lambda M(rho) phi on the free dofs (csrc/elast_eig.hip, csrc/elast_block.hip) ----
@@ -957,6 +998,84 @@ def _body_forces(name: str, body_forces, n_cases: int, mesh) -> Optional[np.ndar
     return B
 
 
+class ThermalExpansion:
+    """The thermal strain alpha (T - T_ref) I of the static residuals and compliances (``thermal=``): ``alpha`` the linear
+    expansion coefficient, ``temperature`` a number (uniform) or a Function(FunctionSpace(mesh, ("CG", 1))) -- an input of
+    the form then, e.g. the state of a `ConductionResidual`'s FEA --, ``scales`` one factor per load case (default 1 for
+    every case; 0 switches a case off).  One temperature serves all load cases."""
+
+    def __init__(self, alpha: float, temperature, T_ref: float = 0.0, scales=None):
+        self.alpha, self.T_ref = float(alpha), float(T_ref)
+        if not (np.isfinite(self.alpha) and np.isfinite(self.T_ref)):
+            raise ValueError("ThermalExpansion: alpha and T_ref must be finite")
+        if isinstance(temperature, Function):
+            Q = temperature.function_space
+            if not isinstance(Q, FunctionSpace) or Q.family != "CG":
+                raise NotImplementedError("ThermalExpansion: the temperature needs a FunctionSpace(mesh, ('CG', 1))")
+            self.temperature = temperature
+        else:
+            self.temperature = float(temperature)
+        self.scales = None if scales is None else np.array(scales, dtype=np.float64).ravel()
+        if self.scales is not None and not np.all(np.isfinite(self.scales)):
+            raise ValueError("ThermalExpansion: the scales must be finite")
+
+    @property
+    def function(self) -> Optional[Function]:
+        """The temperature Function, or None for a uniform temperature."""
+        return self.temperature if isinstance(self.temperature, Function) else None
+
+
+class _ThermalTerm:
+    """A `ThermalExpansion` bound to a form: its density, stiffness law and handle (E, nu), and the scales of the form's
+    load cases (the weights of a compliance folded in).  The three products of csrc/elast_thermal.hip for that form."""
+
+    def __init__(self, name: str, thermal: ThermalExpansion, mesh, rho: Function, n_cases: int, E: float, nu: float,
+                 method_id: int, weights=None):
+        if not isinstance(thermal, ThermalExpansion):
+            raise TypeError(f"{name}: thermal= takes a ThermalExpansion")
+        T = thermal.function
+        if T is not None and T.function_space.mesh is not mesh:
+            raise NotImplementedError(f"{name}: the temperature needs a CG1 space on the state's mesh")
+        s = np.ones(n_cases) if thermal.scales is None else thermal.scales
+        if s.size != n_cases:
+            raise ValueError(f"{name}: {n_cases} load cases need as many thermal scales")
+        self.thermal, self.mesh, self.rho, self.method_id = thermal, mesh, rho, method_id
+        self.E, self.nu, self.n_cases = float(E), float(nu), n_cases
+        self.scales = s.copy() if weights is None else s * np.asarray(weights, dtype=np.float64)
+
+    def device(self) -> DeviceElasticity:
+        return elasticity_handle(self.mesh, self.E, self.nu)
+
+    def key(self) -> tuple:
+        T = self.thermal.function
+        return (None, self.thermal.temperature) if T is None else (T.version, id(T.vec))
+
+    def _temperature(self):
+        T = self.thermal.function
+        return self.thermal.temperature if T is None else T.vec
+
+    def load(self, y: Vec, **kw) -> Vec:
+        """y_l = [...] + a s_l H(C(rho); theta)"""
+        th = self.thermal
+        return self.device().thermal_apply(self.method_id, "N", self.n_cases, self.scales, th.alpha, self.rho.vec,
+                                           self._temperature(), y, T_ref=th.T_ref, **kw)
+
+    def drho(self, transpose: bool, x: Vec, y: Vec, a: float, accumulate: bool = True) -> Vec:
+        """forward: y_l (+)= a s_l H(C'(rho) x; theta); transposed: y[n_cell] (+)= a sum_l s_l (T_rho product of x_l)"""
+        th = self.thermal
+        return self.device().thermal_apply(self.method_id, "T_rho" if transpose else "N", self.n_cases, self.scales, th.alpha,
+                                           self.rho.vec, self._temperature(), y, T_ref=th.T_ref, x=x, a=a, accumulate=accumulate)
+
+    def dtemp(self, transpose: bool, x: Vec, y: Vec, a: float, accumulate: bool = False) -> Vec:
+        """forward: y_l (+)= a s_l H(C(rho); x) for the nodal field x; transposed: y[n_vert] (+)= a sum_l s_l (T_T product of x_l)"""
+        dev = self.device()
+        if transpose:
+            return dev.thermal_apply(self.method_id, "T_temp", self.n_cases, self.scales, self.thermal.alpha, self.rho.vec, 0.0, y,
+                                     x=x, a=a, accumulate=accumulate)
+        return dev.thermal_apply(self.method_id, "N", self.n_cases, self.scales, self.thermal.alpha, self.rho.vec, x, y, a=a,
+                                 accumulate=accumulate)
+
+
 def _facets_of(measures, tractions) -> list:
     """The tagged facets of every load case that has a traction (None for the others: they need none)."""
     return [None if t is None else ds.facets() for ds, t in zip(measures, tractions)]
@@ -1167,7 +1286,8 @@ class MultiLoadElasticityMatrix(ElasticityMatrix):
 
 class _ElasticityDrho:
     """dR/drho ((n_cases n_dof) x n_cell), matrix free: block l of column e = C'(rho_e) K0_e u_{l,e}, minus the body-load
-    operator G_B of a form with body forces (F depends on the density there), added onto the stiffness term."""
+    operator G_B of a form with body forces and minus s_l H(C'(rho) . ; theta) of a form with a thermal load (F depends on
+    the density there), added onto the stiffness term."""
 
     def __init__(self, form: "ElasticityResidual"):
         self.form, self.mesh = form, form.mesh
@@ -1181,6 +1301,8 @@ class _ElasticityDrho:
         F.device().drho_multi(F.method_id, False, F.n_cases, F.rho.vec, F.u.vec, x, y)
         if F.body is not None:
             F.device().body_apply(F.n_cases, F.body, x, y, a=-1.0, accumulate=True)
+        if F.thermal is not None:
+            F.thermal.drho(False, x, y, a=-1.0)
         return y
 
     def multTranspose(self, x: Vec, y: Vec) -> Vec:
@@ -1188,6 +1310,8 @@ class _ElasticityDrho:
         F.device().drho_multi(F.method_id, True, F.n_cases, F.rho.vec, F.u.vec, x, y)
         if F.body is not None:
             F.device().body_apply(F.n_cases, F.body, x, y, transpose=True, a=-1.0, accumulate=True)
+        if F.thermal is not None:
+            F.thermal.drho(True, x, y, a=-1.0)
         return y
 
     def new_row_vec(self) -> Vec:
@@ -1198,6 +1322,34 @@ class _ElasticityDrho:
     def new_col_vec(self) -> Vec:
         if self._col is None:
             self._col = Vec(_ctx(), self.mesh.n_cell)
+        return self._col
+
+
+class _ElasticityDtemp:
+    """dR/dT ((n_cases n_dof) x n_vert) of a form whose thermal load reads a temperature Function, matrix free: block l =
+    -s_l H(C(rho); .), the thermal load as a linear map of the nodal temperatures (csrc/elast_thermal.hip)."""
+
+    def __init__(self, form: "ElasticityResidual"):
+        self.form, self.mesh = form, form.mesh
+        self._row = self._col = None
+
+    def getSizes(self):
+        return (self.form.n_cases * self.form.n_dof, self.mesh.n_vert)
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        return self.form.thermal.dtemp(False, x, y, a=-1.0)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        return self.form.thermal.dtemp(True, x, y, a=-1.0)
+
+    def new_row_vec(self) -> Vec:
+        if self._row is None:
+            self._row = Vec(_ctx(), self.getSizes()[0])
+        return self._row
+
+    def new_col_vec(self) -> Vec:
+        if self._col is None:
+            self._col = Vec(_ctx(), self.mesh.n_vert)
         return self._col
 
 
@@ -1226,25 +1378,33 @@ def _loads_vec(mesh, facets_list, tractions, weights=None) -> Optional[Vec]:
 
 class _BodyLoad:
     """The total load T + G_B rho of a form with body forces, in a Vec of the form's own: rebuilt by one G_B launch whenever
-    the density (its version or its vector) or the traction columns changed.  ``B``: (n_cases, tdim), weights included."""
+    the density (its version or its vector) or the traction columns changed.  ``B``: (n_cases, tdim), weights included.
+    With ``thermal`` (a `_ThermalTerm`) the total is T + G_B rho + s_l H(C(rho); theta), the thermal load one launch of its
+    own onto the first (``B`` may then be None: that launch alone), rebuilt when the temperature changed as well."""
 
-    def __init__(self, mesh, rho: Function, B: np.ndarray):
-        self.mesh, self.rho, self.B = mesh, rho, B
+    def __init__(self, mesh, rho: Function, B: Optional[np.ndarray], thermal: Optional["_ThermalTerm"] = None):
+        self.mesh, self.rho, self.B, self.thermal = mesh, rho, B, thermal
         self.vec = None
         self.key = None
 
     def total(self, dev: "DeviceElasticity", traction: Optional[Vec], zero_fixed: bool = False) -> Vec:
         key = (self.rho.version, id(self.rho.vec), id(traction), dev.fixed_key if zero_fixed else None)
+        if self.thermal is not None:
+            key += self.thermal.key()
         if key != self.key:
-            L = self.B.shape[0]
+            L = self.B.shape[0] if self.B is not None else self.thermal.n_cases
             if self.vec is None:
                 self.vec = Vec(_ctx(), L * dev.n_dof)
-            dev.body_apply(L, self.B, self.rho.vec, self.vec, base=traction, zero_fixed=zero_fixed)
+            if self.B is not None:
+                dev.body_apply(L, self.B, self.rho.vec, self.vec, base=traction, zero_fixed=zero_fixed)
+            if self.thermal is not None:
+                self.thermal.load(self.vec, base=None if self.B is not None else traction, zero_fixed=zero_fixed,
+                                  accumulate=self.B is not None)
             self.key = key
         return self.vec
 
 
-def _multi_arguments(name: str, u: Function, tractions, measures, body_forces=None):
+def _multi_arguments(name: str, u: Function, tractions, measures, body_forces=None, thermal=None):
     V = u.function_space
     if not isinstance(V, LoadCaseSpace):
         raise NotImplementedError(f"{name} needs a Function(LoadCaseSpace(V, n_cases)) state")
@@ -1254,7 +1414,7 @@ def _multi_arguments(name: str, u: Function, tractions, measures, body_forces=No
     measures = [None] * len(tractions) if measures is None else list(measures)
     if len(tractions) != V.n_cases or len(measures) != V.n_cases:
         raise ValueError(f"{name}: {V.n_cases} load cases need as many tractions and measures")
-    if any(t is None for t in tractions) and _body_forces(name, body_forces, V.n_cases, V.mesh) is None:
+    if any(t is None for t in tractions) and _body_forces(name, body_forces, V.n_cases, V.mesh) is None and thermal is None:
         raise ValueError(f"{name}: a load case without a traction needs a body force")
     ts = [_traction(t, V.mesh) for t in tractions]
     dss = [ds if ds is not None else Measure("ds", domain=V.mesh) for ds in measures]
@@ -1273,7 +1433,12 @@ class ElasticityResidual(BackendForm):
     With a body force `load` is the total F(rho), rebuilt in one launch when the density changes, and dR/drho gains
     -G_b.  RAMP is the usual stiffness law with self-weight: SIMP's rho^3 against the linear mass gives large displacements
     at low density.  F(rho) is non-zero on clamped vertices, so the adjoint is non-zero on fixed dofs: the exact reduced
-    gradient needs ``fea.consistent_bc_partials = True``, as for `MultiLoadPnormStress`."""
+    gradient needs ``fea.consistent_bc_partials = True``, as for `MultiLoadPnormStress`.
+
+    With ``thermal`` (a `ThermalExpansion`) F gains the thermal expansion load s_l H(C(rho); theta) (module docstring): `load`
+    is rebuilt when the density or the temperature changed, dR/drho gains -s_l H(C'(rho) . ; theta), and with a temperature
+    Function T the form depends on (u, rho, T), `partial_matrix(T)` being the matrix-free -s_l H(C(rho); .).  ``traction`` may
+    be None with a thermal load.  It is non-zero on clamped vertices as well: ``consistent_bc_partials`` as above."""
     rank = 1
     is_linear = True
     is_symmetric = True
@@ -1282,7 +1447,7 @@ class ElasticityResidual(BackendForm):
 
     def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, E: float = 1.0,
                  nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None, springs=None,
-                 point_load=None):
+                 point_load=None, thermal: Optional[ThermalExpansion] = None):
         V = u.function_space
         if not isinstance(V, VectorFunctionSpace):
             raise NotImplementedError("ElasticityResidual needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
@@ -1293,14 +1458,15 @@ class ElasticityResidual(BackendForm):
             point_load = np.ascontiguousarray(point_load, dtype=np.float64).ravel().copy()
             if point_load.size != V.dim or not np.all(np.isfinite(point_load)):
                 raise ValueError(f"ElasticityResidual: the point load needs {V.dim} finite entries")
-        if self.t is None and body is None and point_load is None:
-            raise ValueError("ElasticityResidual: without a traction the load needs a body force or a point load")
-        self._setup(u, rho, V, 1, [self.t], [self.ds], E, nu, method, preconditioner, body, springs)
+        if self.t is None and body is None and point_load is None and thermal is None:
+            raise ValueError("ElasticityResidual: without a traction the load needs a body force, a point load or a thermal load")
+        self._setup(u, rho, V, 1, [self.t], [self.ds], E, nu, method, preconditioner, body, springs, thermal)
         self.point_load = point_load
 
-    def _setup(self, u, rho, V, n_cases, tractions, measures, E, nu, method, preconditioner, body=None, springs=None) -> None:
+    def _setup(self, u, rho, V, n_cases, tractions, measures, E, nu, method, preconditioner, body=None, springs=None,
+               thermal=None) -> None:
         """``V``: the space of one column (the numbering of the bcs and of the springs); ``body``: (n_cases, tdim) body forces
-        or None; ``springs``: one stiffness per dof of V or None."""
+        or None; ``springs``: one stiffness per dof of V or None; ``thermal``: a `ThermalExpansion` or None."""
         if rho.function_space.family != "DG" or rho.function_space.mesh is not V.mesh:
             raise NotImplementedError(f"{type(self).__name__} needs a DG0 density on the state's mesh")
         if method not in METHODS:
@@ -1315,9 +1481,12 @@ class ElasticityResidual(BackendForm):
         self.body = body
         self.springs = _check_springs(type(self).__name__, springs, V.dim)
         self.point_load, self._point_vec = None, None
+        self.thermal = None if thermal is None else _ThermalTerm(type(self).__name__, thermal, V.mesh, rho, n_cases, E, nu,
+                                                                  self.method_id)
         self._body_load = self._body_rhs = None
-        if body is not None:
-            self._body_load, self._body_rhs = _BodyLoad(V.mesh, rho, body), _BodyLoad(V.mesh, rho, body)
+        if body is not None or thermal is not None:
+            self._body_load, self._body_rhs = (_BodyLoad(V.mesh, rho, body, self.thermal),
+                                               _BodyLoad(V.mesh, rho, body, self.thermal))
         self.rtol = 1e-15
         self._key = None
         self._mask = None
@@ -1327,7 +1496,8 @@ class ElasticityResidual(BackendForm):
         self.last_info = {}
 
     def functions(self):
-        return (self.u, self.rho)
+        T = None if self.thermal is None else self.thermal.thermal.function
+        return (self.u, self.rho) if T is None else (self.u, self.rho, T)
 
     def device(self) -> DeviceElasticity:
         return elasticity_handle(self.mesh, self.E, self.nu)
@@ -1345,7 +1515,7 @@ class ElasticityResidual(BackendForm):
     def load(self) -> Vec:
         """Column l: the total load F_l(rho)."""
         T = self._traction_load()
-        return T if self.body is None else self._body_load.total(self.device(), T)
+        return T if self._body_load is None else self._body_load.total(self.device(), T)
 
     def _set_bcs(self, bcs) -> None:
         mask, self._vals = _fixed_data(self.n_dof, bcs)
@@ -1388,6 +1558,8 @@ class ElasticityResidual(BackendForm):
             return out if isinstance(out, self.matrix_class) and not out.masked else self.matrix_class(self)
         if wrt is self.rho:
             return out if isinstance(out, _ElasticityDrho) else _ElasticityDrho(self)
+        if self.thermal is not None and wrt is self.thermal.thermal.function:
+            return out if isinstance(out, _ElasticityDtemp) else _ElasticityDtemp(self)
         raise ValueError("the elasticity residual does not depend on that Function")
 
     def assemble_system(self, bcs, rhs: bool, out, out_nobc):
@@ -1409,7 +1581,7 @@ class ElasticityResidual(BackendForm):
             return self.load()
         fixed = self._mask == 1
         nonzero = bool(np.any(self._vals[fixed] != 0.0))
-        if self.body is not None and not nonzero:
+        if self._body_rhs is not None and not nonzero:
             return self._body_rhs.total(dev, self._traction_load(), zero_fixed=True)
         F = self.load()
         key = (id(F), hash(self._mask.tobytes()))
@@ -1459,9 +1631,10 @@ class MultiLoadElasticityResidual(ElasticityResidual):
     matrix_class = MultiLoadElasticityMatrix
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, E: float = 1.0, nu: float = 0.3,
-                 method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None, springs=None):
-        V, ts, dss, body = _multi_arguments("MultiLoadElasticityResidual", u, tractions, measures, body_forces)
-        self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner, body, springs)
+                 method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None, springs=None,
+                 thermal: Optional[ThermalExpansion] = None):
+        V, ts, dss, body = _multi_arguments("MultiLoadElasticityResidual", u, tractions, measures, body_forces, thermal)
+        self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner, body, springs, thermal)
         self.solve_counts = {"state": 0, "adjoint": 0}
 
     def _record(self, infos, kind: str):
@@ -1488,40 +1661,55 @@ class MultiLoadElasticityResidual(ElasticityResidual):
 class Compliance(BackendForm):
     """J = int_ds t . u ds = F^T u (compliance, run_topo_opt_cantilever_beam.py:108-109); over several columns
     J = sum_l w_l F_l . u_l.  With ``body_force`` the load is the total F(rho) = T + G_b rho of `ElasticityResidual`: the
-    density ``rho`` is then required, the form depends on (u, rho), and dJ/drho = G_{wB}^T u (one launch)."""
+    density ``rho`` is then required, the form depends on (u, rho), and dJ/drho = G_{wB}^T u (one launch).  With ``thermal``
+    (a `ThermalExpansion`; ``rho`` required, ``E``, ``nu`` and ``method`` those of the residual) the load carries s_l H(C(rho);
+    theta) as well: the work of the total load, with dJ/drho += sum_l w_l s_l (T_rho product of u_l) and, for a temperature
+    Function T (an argument of the form then), dJ/dT = sum_l w_l s_l (T_T product of u_l), one launch each."""
     rank = 0
 
-    def __init__(self, u: Function, traction, ds: Optional[Measure] = None, body_force=None, rho: Optional[Function] = None):
+    def __init__(self, u: Function, traction, ds: Optional[Measure] = None, body_force=None, rho: Optional[Function] = None,
+                 thermal: Optional[ThermalExpansion] = None, E: float = 1.0, nu: float = 0.3, method: str = "SIMP"):
         if not isinstance(u.function_space, VectorFunctionSpace):
             raise NotImplementedError("Compliance needs a VectorFunctionSpace(mesh, ('CG', 1)) state")
         self.u, self.mesh = u, u.function_space.mesh
         self.t = _traction(traction, self.mesh)
         self.ds = ds if ds is not None else Measure("ds", domain=self.mesh)
         self.tractions, self.measures, self.weights = [self.t], [self.ds], None
-        self._set_body("Compliance", _body_forces("Compliance", None if body_force is None else [body_force], 1, self.mesh), rho)
+        self._set_body("Compliance", _body_forces("Compliance", None if body_force is None else [body_force], 1, self.mesh), rho,
+                       thermal, E, nu, method)
         self._grad = {}
 
-    def _set_body(self, name: str, body: Optional[np.ndarray], rho: Optional[Function]) -> None:
-        """``body``: (n_cases, tdim) or None; kept with the weights folded in (column l = w_l b_l)."""
-        if body is None and any(t is None for t in self.tractions):
+    def _set_body(self, name: str, body: Optional[np.ndarray], rho: Optional[Function], thermal=None, E: float = 1.0,
+                  nu: float = 0.3, method: str = "SIMP") -> None:
+        """``body``: (n_cases, tdim) or None; kept with the weights folded in (column l = w_l b_l), as are the scales of
+        ``thermal``."""
+        if body is None and thermal is None and any(t is None for t in self.tractions):
             raise ValueError(f"{name}: a load case without a traction needs a body force")
-        if body is not None:
+        if body is not None or thermal is not None:
             if rho is None:
-                raise ValueError(f"{name}: the load of a body force depends on the density: pass rho")
+                raise ValueError(f"{name}: the load of a body force or a thermal expansion depends on the density: pass rho")
             if rho.function_space.family != "DG" or rho.function_space.mesh is not self.mesh:
                 raise NotImplementedError(f"{name} needs a DG0 density on the state's mesh")
-            if self.weights is not None:
+            if body is not None and self.weights is not None:
                 body = body * np.asarray(self.weights, dtype=np.float64)[:, None]
-        self.body, self.rho = body, rho if body is not None else None
-        self._body_load = None if body is None else _BodyLoad(self.mesh, rho, body)
+        self.thermal = None
+        if thermal is not None:
+            if method not in METHODS:
+                raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
+            self.thermal = _ThermalTerm(name, thermal, self.mesh, rho, len(self.tractions), E, nu, METHODS[method], self.weights)
+        self.body, self.rho = body, rho if (body is not None or thermal is not None) else None
+        self._body_load = None if self.rho is None else _BodyLoad(self.mesh, rho, body, self.thermal)
 
     def functions(self):
-        return (self.u,) if self.body is None else (self.u, self.rho)
+        if self.rho is None:
+            return (self.u,)
+        T = None if self.thermal is None else self.thermal.thermal.function
+        return (self.u, self.rho) if T is None else (self.u, self.rho, T)
 
     def load(self) -> Vec:
-        """Column l = w_l F_l, the total load with body forces."""
+        """Column l = w_l F_l, the total load with body forces and the thermal load."""
         T = _loads_vec(self.mesh, _facets_of(self.measures, self.tractions), self.tractions, self.weights)
-        return T if self.body is None else self._body_load.total(elasticity_handle(self.mesh), T)
+        return T if self._body_load is None else self._body_load.total(elasticity_handle(self.mesh), T)
 
     def assemble_scalar(self) -> float:
         return self.load().dot(self.u.vec, self.u.function_space.dim)
@@ -1533,22 +1721,30 @@ class Compliance(BackendForm):
                 out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
         if wrt is self.u:
             return out.copy_from(self.load())
-        if self.body is not None and wrt is self.rho:
-            return elasticity_handle(self.mesh).body_apply(self.body.shape[0], self.body, self.u.vec, out, transpose=True)
+        if self.rho is not None and wrt is self.rho:
+            if self.body is not None:
+                elasticity_handle(self.mesh).body_apply(self.body.shape[0], self.body, self.u.vec, out, transpose=True)
+            if self.thermal is not None:
+                self.thermal.drho(True, self.u.vec, out, a=1.0, accumulate=self.body is not None)
+            return out
+        if self.thermal is not None and wrt is self.thermal.thermal.function:
+            return self.thermal.dtemp(True, self.u.vec, out, a=1.0)
         return out.fill(0.0)
 
 
 class MultiLoadCompliance(Compliance):
     """J = sum_l w_l F_l . u_l over the load cases of a Function(LoadCaseSpace(V, L)) (w = 1 without ``weights``); with
-    ``body_forces`` (and the density ``rho``) F_l is the total load of `MultiLoadElasticityResidual`."""
+    ``body_forces`` and ``thermal`` (and the density ``rho``) F_l is the total load of `MultiLoadElasticityResidual`."""
 
-    def __init__(self, u: Function, tractions, measures=None, weights=None, body_forces=None, rho: Optional[Function] = None):
-        V, self.tractions, self.measures, body = _multi_arguments("MultiLoadCompliance", u, tractions, measures, body_forces)
+    def __init__(self, u: Function, tractions, measures=None, weights=None, body_forces=None, rho: Optional[Function] = None,
+                 thermal: Optional[ThermalExpansion] = None, E: float = 1.0, nu: float = 0.3, method: str = "SIMP"):
+        V, self.tractions, self.measures, body = _multi_arguments("MultiLoadCompliance", u, tractions, measures, body_forces,
+                                                                  thermal)
         self.u, self.mesh = u, V.mesh
         self.weights = np.ones(V.n_cases) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
         if self.weights.size != V.n_cases:
             raise ValueError(f"MultiLoadCompliance: {V.n_cases} load cases need as many weights")
-        self._set_body("MultiLoadCompliance", body, rho)
+        self._set_body("MultiLoadCompliance", body, rho, thermal, E, nu, method)
         self._grad = {}
 
 
@@ -1717,7 +1913,9 @@ class ElasticityPnormStress(BackendForm):
     """J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p with the solid-material von Mises stress (module docstring);
     alpha = |Omega| unless given.  dJ/du is not a multiple of the load: its adjoint solve is a solve of its own.  Over
     several columns J = sum_l w_l J_l; value, dJ/du (column l = w_l dJ_l/du_l) and dJ/drho each take one pass over the mesh
-    for all of them (`DeviceElasticity.pnorm_stress_multi`).  ``m`` is a float here and may be assigned to."""
+    for all of them (`DeviceElasticity.pnorm_stress_multi`).  ``m`` is a float here and may be assigned to.  With a thermal
+    load (`ThermalExpansion`) the stress gains -C beta_0 theta I, hydrostatic on the 3 x 3 tensor in plane strain too: its
+    deviator, and with it sigma_vm, is unchanged, so this output is the thermoelastic one as it stands."""
     rank = 0
 
     def __init__(self, u: Function, rho: Function, E: float = 1.0, nu: float = 0.3, m: float = 1.0, p: float = 8.0,
@@ -1799,7 +1997,8 @@ class MultiLoadPnormStress(ElasticityPnormStress):
 class ElasticityVonMises(BackendForm):
     """The cell field rho_e^q sigma_vm,e (q = 0: the stress of the solid material, no density needed); over several columns
     max_l s_l rho_e^q sigma_vm,e(u_l), or the field of one of them.  `project` hands the projection over: onto a DG0 target
-    the cell values themselves, onto CG1 the L2 projection of a cell-wise constant."""
+    the cell values themselves, onto CG1 the L2 projection of a cell-wise constant.  The thermal stress of a `ThermalExpansion`
+    is hydrostatic (see `ElasticityPnormStress`): the field of a thermoelastic state needs no change."""
     rank = 0
 
     def __init__(self, u: Function, rho: Optional[Function] = None, E: float = 1.0, nu: float = 0.3, q: float = 0.0):
@@ -2035,6 +2234,8 @@ class ElasticityBuckling(_BlockModes):
             raise NotImplementedError(f"{name} needs the ElasticityResidual whose state carries the load")
         if isinstance(residual, MultiLoadElasticityResidual) or residual.n_cases != 1:
             raise NotImplementedError(f"{name}: several load cases are out of scope (one ElasticityResidual, one load)")
+        if residual.thermal is not None:                              # the pre-stress would need -C beta_0 theta I as well
+            raise NotImplementedError(f"{name}: thermal loads are out of scope")
         if getattr(residual.mesh, "local", None) is not None and residual.mesh.local.nranks > 1:
             raise NotImplementedError(f"{name}: partitioned meshes are out of scope")
         n_modes = int(n_modes)
@@ -2194,10 +2395,12 @@ class HarmonicElasticityResidual(MultiLoadElasticityResidual):
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, omegas=None, density: float = 1.0,
                  mass_law: str = "linear", E: float = 1.0, nu: float = 0.3, method: str = "SIMP",
-                 preconditioner: str = "jacobi", body_forces=None):
+                 preconditioner: str = "jacobi", body_forces=None, thermal=None):
         name = "HarmonicElasticityResidual"
         if body_forces is not None:
             raise NotImplementedError(f"{name}: body forces are out of scope")
+        if thermal is not None:
+            raise NotImplementedError(f"{name}: thermal loads are out of scope")
         if any(t is None for t in list(tractions)):
             raise ValueError(f"{name}: every column needs a traction (body forces are out of scope)")
         V, ts, dss, _ = _multi_arguments(name, u, tractions, measures)
@@ -2468,10 +2671,12 @@ class DampedHarmonicElasticityResidual(HarmonicElasticityResidual):
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, omegas=None, loss_factor: float = 0.0,
                  rayleigh=(0.0, 0.0), density: float = 1.0, mass_law: str = "linear", E: float = 1.0, nu: float = 0.3,
-                 method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None):
+                 method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None, thermal=None):
         name = "DampedHarmonicElasticityResidual"
         if body_forces is not None:
             raise NotImplementedError(f"{name}: body forces are out of scope")
+        if thermal is not None:
+            raise NotImplementedError(f"{name}: thermal loads are out of scope")
         V, L, ts, dss = _damped_arguments(name, u, tractions, measures)
         if omegas is None:
             raise ValueError(f"{name}: one angular frequency per column (omegas)")
@@ -2715,10 +2920,13 @@ class TransientElasticityResidual(ElasticityResidual):
 
     def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, signal=None, dt: float = None,
                  beta: float = 0.25, gamma: float = 0.5, rayleigh=(0.0, 0.0), density: float = 1.0, mass_law: str = "linear",
-                 E: float = 1.0, nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None):
+                 E: float = 1.0, nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None,
+                 thermal=None):
         name = "TransientElasticityResidual"
         if body_force is not None:
             raise NotImplementedError(f"{name}: body forces are out of scope")
+        if thermal is not None:
+            raise NotImplementedError(f"{name}: thermal loads are out of scope")
         V = _transient_space(name, u)
         if traction is None:
             raise ValueError(f"{name}: the load pattern needs a traction (body forces are out of scope)")
@@ -2899,26 +3107,32 @@ def averageFunc(func: Function) -> LinearFunctional:
 
 # ---------------------------------------------------------------------------- builders of the run script (:85-109) ----
 def pdeRes(u, v, rho_e, f, E: float = 1.0, dss: Optional[Measure] = None, method: str = "SIMP",
-           preconditioner: str = "jacobi", body_force=None, springs=None, point_load=None) -> ElasticityResidual:
+           preconditioner: str = "jacobi", body_force=None, springs=None, point_load=None,
+           thermal: Optional[ThermalExpansion] = None) -> ElasticityResidual:
     """run_topo_opt_cantilever_beam.py:85-101 (nu = 0.3 as there); ``v`` is implied by the catalogue.  ``body_force``: the
     self-weight rho b dx (not in the reference's script); ``f`` may then be None.  ``springs``: elastic supports, one
     stiffness per dof (`point_springs`, `facet_springs`), and ``point_load``: nodal forces, one value per dof (a port's input
-    force, built like `port_displacement`); neither is in the reference's script."""
+    force, built like `port_displacement`); neither is in the reference's script.  ``thermal``: the thermal expansion load
+    of a `ThermalExpansion`; ``f`` may then be None."""
     return ElasticityResidual(u, rho_e, f, dss, E=E, nu=0.3, method=method, preconditioner=preconditioner,
-                              body_force=body_force, springs=springs, point_load=point_load)
+                              body_force=body_force, springs=springs, point_load=point_load, thermal=thermal)
 
 
-def compliance(u, f, dss: Optional[Measure] = None, body_force=None, rho_e=None) -> Compliance:
-    """run_topo_opt_cantilever_beam.py:108-109; with ``body_force`` (and the density ``rho_e``) the work of the total load."""
-    return Compliance(u, f, dss, body_force=body_force, rho=rho_e)
+def compliance(u, f, dss: Optional[Measure] = None, body_force=None, rho_e=None, thermal: Optional[ThermalExpansion] = None,
+               E: float = 1.0, method: str = "SIMP") -> Compliance:
+    """run_topo_opt_cantilever_beam.py:108-109; with ``body_force`` or ``thermal`` (and the density ``rho_e``) the work of the
+    total load; ``E`` and ``method`` are those of `pdeRes` (read by the thermal load alone)."""
+    return Compliance(u, f, dss, body_force=body_force, rho=rho_e, thermal=thermal, E=E, nu=0.3, method=method)
 
 
 def pdeRes_multiload(u, v, rho_e, fs, dss_list=None, E: float = 1.0, method: str = "SIMP",
-                     preconditioner: str = "jacobi", body_forces=None, springs=None) -> MultiLoadElasticityResidual:
+                     preconditioner: str = "jacobi", body_forces=None, springs=None,
+                     thermal: Optional[ThermalExpansion] = None) -> MultiLoadElasticityResidual:
     """`pdeRes` for the load cases ``fs[l]`` on ``dss_list[l]`` with the body forces ``body_forces[l]`` (None = none) and
-    the elastic supports ``springs`` (the same for every load case); ``u`` is a Function(LoadCaseSpace(V, len(fs)))."""
+    the elastic supports ``springs`` (the same for every load case) and the thermal load ``thermal`` (one temperature, one
+    scale per load case); ``u`` is a Function(LoadCaseSpace(V, len(fs)))."""
     return MultiLoadElasticityResidual(u, rho_e, fs, dss_list, E=E, nu=0.3, method=method, preconditioner=preconditioner,
-                                       body_forces=body_forces, springs=springs)
+                                       body_forces=body_forces, springs=springs, thermal=thermal)
 
 
 def displacement(u, ell, weights=None) -> ElasticityDisplacement:
@@ -2931,9 +3145,12 @@ def pnorm_displacement(u, region=None, m=1.0, p: float = 8.0, weights=None) -> E
     return ElasticityPnormDisplacement(u, region, m=m, p=p, weights=weights)
 
 
-def compliance_multiload(u, fs, dss_list=None, weights=None, body_forces=None, rho_e=None) -> MultiLoadCompliance:
-    """sum_l w_l F_l . u_l with F_l = int_ds(l) f_l . v ds + the body load of ``body_forces[l]`` (needs ``rho_e``)"""
-    return MultiLoadCompliance(u, fs, dss_list, weights, body_forces=body_forces, rho=rho_e)
+def compliance_multiload(u, fs, dss_list=None, weights=None, body_forces=None, rho_e=None,
+                         thermal: Optional[ThermalExpansion] = None, E: float = 1.0, method: str = "SIMP") -> MultiLoadCompliance:
+    """sum_l w_l F_l . u_l with F_l = int_ds(l) f_l . v ds + the body load of ``body_forces[l]`` + the thermal load of
+    ``thermal`` (either needs ``rho_e``; ``E`` and ``method`` as for `compliance`)"""
+    return MultiLoadCompliance(u, fs, dss_list, weights, body_forces=body_forces, rho=rho_e, thermal=thermal, E=E, nu=0.3,
+                               method=method)
 
 
 def pdeRes_harmonic(u, v, rho_e, fs, dss_list=None, omegas=None, density: float = 1.0, mass_law: str = "linear", E: float = 1.0,

@@ -25,12 +25,14 @@ from .function import Function, FunctionSpace, LoadCaseSpace, TimeHistorySpace, 
 from .io import XDMFRecorder
 from .mesh import (BeamMesh, Mesh, createIntervalMesh, createRectangleMesh, createUnitCubeMesh, createUnitSquareMesh,
                    findNodeIndices, locate_dofs_geometrical, locate_entities_boundary, meshSize)
-from .elasticity import (Constant, Measure, TransientCompliance, TransientElasticityResidual, buckling_aggregate,
+from .elasticity import (Constant, Measure, ThermalExpansion, TransientCompliance, TransientElasticityResidual, buckling_aggregate,
                          compliance_multiload, displacement, dynamic_compliance, dynamic_compliance_damped, eigenvalue_aggregate,
                          facet_springs, mean_displacement, meshtags, pnorm_displacement, point_springs, port_displacement,
                          pdeRes_harmonic, pdeRes_harmonic_damped, pdeRes_multiload, pdeRes_transient, pnorm_stress,
                          pnorm_stress_multiload, transient_compliance, von_Mises_stress, von_Mises_stress_multiload)
-from ..opt import CSDLProblem, MMA          # noqa: F401  the drivers' last lines (modopt.CSDLProblem + an optimiser)
+from .conduction import (ConductionResidual, DeviceConduction, ThermalCompliance, pdeRes_conduction,    # noqa: F401
+                         thermal_compliance)
+from ..opt import CSDLProblem, MMA         # noqa: F401  the drivers' last lines (modopt.CSDLProblem + an optimiser)
 
 
 class AbstractFEA(object):

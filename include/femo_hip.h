@@ -751,6 +751,27 @@ int femo_elast_von_mises_multi(femo_elast* e, int n_cols, const femo_vec* rho, c
  * atomics: the same bits every call, and column l does not depend on n_cols.                                             */
 int femo_elast_body_apply(femo_elast* e, int n_cols, const double* b /* [n_cols * 3] */, int transpose, double a,
                           const femo_vec* x, const femo_vec* base /* or NULL */, int zero_fixed, femo_vec* y, int accumulate);
+/* Thermal expansion load (csrc/elast_thermal.hip).  sigma = C(rho) (sigma_0(u) - beta_0 theta I) on the 3 x 3 tensor, with
+ * beta_0 = (3 lambda_0 + 2 mu_0) alpha from the handle's lambda_0, mu_0 (the same constant in plane strain and in 3-D) and
+ * theta = T - t_ref, T the P1 field `temp` (n_vert nodal values) or, with temp = NULL, the uniform value t_uniform.  The load
+ * of load case l is s_l H(C(rho); theta) with
+ *   H(w; theta)[d v + i] = sum_{c around v} w_c beta_0 thetabar_c |T_c| d_i phi_v^c,   thetabar_c = the mean of theta over c
+ * (exact for P1 theta: div v is constant per cell).  C and C' are those of `method`; column l at l * n_dof; s: n_cols scales.
+ *   FEMO_ELAST_THERMAL_N:       y_l = [accumulate ? y_l : (base ? base_l : 0)] + a s_l H(w; theta), w = C(rho) with x = NULL
+ *                               and w_c = C'(rho_c) x_c with the cell vector x (dR/drho forward; dR/dT forward is the call
+ *                               with temp = dT and t_ref = 0).  y and base: n_cols * n_dof.  zero_fixed = 1 writes 0 on the dofs
+ *                               of the fixed set of every column instead (needs femo_elast_set_fixed).
+ *   FEMO_ELAST_THERMAL_T_RHO:   y[c] = (accumulate ? y[c] : 0) + a C'(rho_c) beta_0 thetabar_c |T_c| sum_l s_l div(x_l)_c
+ *   FEMO_ELAST_THERMAL_T_TEMP:  y[v] = (accumulate ? y[v] : 0) + a sum_{c around v} C(rho_c) beta_0 |T_c| / (d+1) sum_l s_l div(x_l)_c
+ *                               (x: n_cols * n_dof; y: n_cell resp. n_vert; base NULL and zero_fixed 0; div(x)_c = sum_a
+ *                               grad phi_a . x[a]; summed in ascending l; temp and t_uniform are not read by T_TEMP).
+ * They are the transposes of w -> N and of theta -> N.  One launch for all columns; no float atomics: the same bits every
+ * call, and column l does not depend on n_cols.  A non-finite density or temperature reaches y.  One rank only.           */
+enum { FEMO_ELAST_THERMAL_N = 0, FEMO_ELAST_THERMAL_T_RHO = 1, FEMO_ELAST_THERMAL_T_TEMP = 2 };
+int femo_elast_thermal_apply(femo_elast* e, int method, int product, int n_cols, const double* s /* [n_cols] */, double alpha,
+                             const femo_vec* rho, const femo_vec* temp /* or NULL */, double t_uniform, double t_ref, double a,
+                             const femo_vec* x /* or NULL (N) */, const femo_vec* base /* or NULL */, int zero_fixed,
+                             femo_vec* y, int accumulate);
 /* Lowest eigenfrequencies (csrc/elast_eig.hip): K(rho) phi = lambda M(rho) phi on the free dofs, with the consistent P1 mass
  *   M(rho) = density sum_e m(rho_e) M0_e,   M0_e[(a,i),(b,j)] = delta_ij |T_e| (1 + delta_ab) / ((d+1)(d+2)),
  *   m = rho (FEMO_ELAST_MASS_LINEAR) or rho for rho >= 0.1 and 6e5 rho^6 - 5e6 rho^7 below (FEMO_ELAST_MASS_DU_OLHOFF, C^1 at
@@ -1012,6 +1033,36 @@ int femo_pde_filter_apply(femo_pde_filter* f, int transpose, const femo_vec* x, 
 int femo_pde_filter_set(femo_pde_filter* f, double rtol, int warm_start);
 int femo_pde_filter_export_csr(const femo_pde_filter* f, int64_t* rowptr, int32_t* col, double* val);
 int femo_pde_filter_bytes(const femo_pde_filter* f, int64_t* bytes);
+
+/* ---- Heat conduction with a penalised conductivity (csrc/conduction.hip) ------------------------------------------------
+ * The second physics of the SIMP track, the heat-sink problem: on a mesh of P1 triangles or tetrahedra on one rank,
+ *   K_theta(rho) = sum_c k(rho_c) |T_c| grad phi_a . grad phi_b,   k(rho) = k_min + (k_0 - k_min) C(rho),
+ * C = rho^3 (FEMO_ELAST_SIMP) or rho / (1 + 8 (1 - rho)) (FEMO_ELAST_RAMP), 0 <= k_min < k_0, in femo_mat on the mesh pattern.
+ * assemble: K_theta of the DG0 density rho and, with a Dirichlet set bc, the eliminated matrix beside it in the same launch
+ *   (zero rows and columns and a unit diagonal on the set; it keeps its identity rows, which femo_solve_cg solves up front).
+ *   No float atomics: both are symmetric bit for bit and have the same bits on every build.
+ * apply: y = K_theta x, or with eliminated = 1 the eliminated matrix.
+ * lift: the right-hand side for Dirichlet values g (NULL: zero): b = g on the set, b = q - K_theta g elsewhere; g holds the
+ *   values on the set and zeros elsewhere; work: n_rows scratch entries (needed with g).
+ * solve: Jacobi-scaled femo_solve_cg with the eliminated matrix (the plain one without a set); opts NULL: rtol 1e-13 from the
+ *   zero guess; opts->pc must be FEMO_PC_JACOBI.  A non-finite density or right-hand side is found as the non-finite Jacobi
+ *   norm of the right-hand side and refused (x may have been written; the next call works).  Whether the solve converged is
+ *   in info.  No multilevel preconditioner for this operator.
+ * drho: the density products of R = K_theta(rho) T - Q at the temperature T, k' = (k_0 - k_min) C',
+ *   transpose = 0:  y[v] = (accumulate ? y[v] : 0) + a sum_{c around v} k'(rho_c) x_c |T_c| grad phi_v . grad T_c   (x: n_cell)
+ *   transpose = 1:  y[c] = (accumulate ? y[c] : 0) + a k'(rho_c) |T_c| grad x_c . grad T_c                         (x: n_vert)
+ *   exact transposes in exact arithmetic; one writer per entry, the cells around a vertex in ascending order.
+ * export_csr: either matrix in the layout of femo_mat_export_csr.                                                        */
+typedef struct femo_cond femo_cond;
+int femo_cond_create(femo_mesh* mesh, femo_cond** out);
+int femo_cond_destroy(femo_cond* c);
+int femo_cond_assemble(femo_cond* c, int method, double k0, double k_min, const femo_vec* rho, const femo_bc* bc /* or NULL */);
+int femo_cond_apply(femo_cond* c, int eliminated, const femo_vec* x, femo_vec* y);
+int femo_cond_lift(femo_cond* c, const femo_vec* q, const femo_vec* g /* or NULL */, femo_vec* work /* or NULL */, femo_vec* b);
+int femo_cond_solve(femo_cond* c, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info);
+int femo_cond_drho(femo_cond* c, int method, double k0, double k_min, int transpose, double a, const femo_vec* rho,
+                   const femo_vec* T, const femo_vec* x, femo_vec* y, int accumulate);
+int femo_cond_export_csr(const femo_cond* c, int eliminated, int64_t* rowptr, int32_t* col, double* val);
 
 /* ---- Method of Moving Asymptotes (csrc/mma.hip) -------------------------------------------------------------------------
  * What the reference's drivers hand to modopt (run_topo_opt_cantilever_beam.py: modopt.CSDLProblem + SLSQP / SNOPT), as a

@@ -39,6 +39,13 @@ and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the
                                                                  the COCR iterations and ms per column, and the time per iteration
                                                                  of the COCR and the MINRES state solves, alternated: a warm-up of
                                                                  both, then 5 pairs, medians)
+  ... --thermal [--counts]                                      (the thermoelastic chain rho -> T(rho) -> u(rho, T) -> J -- a conduction
+                                                                 state with the sink on the clamped edge, its temperature as the
+                                                                 thermal expansion load beside the tip load, two adjoint solves --
+                                                                 alternated cycle by cycle with the mechanical-only cycle of the same
+                                                                 build; the three launches of the thermal-load operator and the
+                                                                 conduction assembly in windows of 200 launches; --counts adds the
+                                                                 Jacobi-PCG iterations of the conduction solves at three sizes)
 """
 from __future__ import annotations
 
@@ -463,6 +470,147 @@ def damped_solves(ctx, res, u, fs, dss, bcs, loss_factor, repeats=5):
                 damped_dynamic_compliance=float(J.assemble_scalar()), damped_responses_abs=[float(abs(c)) for c in J.responses()])
 
 
+def build_thermoelastic(args, thermal: bool):
+    """The cantilever of `build` as the thermoelastic chain rho -> T(rho) -> u(rho, T) -> J (two FEA objects: uniform heating
+    with the sink on the clamped edge, the tip traction plus the thermal load of the computed temperature, J the work of the
+    total load), or with ``thermal`` False the mechanical cycle alone in the same set-up."""
+    from femo_amd.csdl_opt.fea_model import FEAModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.simulator import Simulator
+    from femo_amd.fea.elasticity import compliance, pdeRes
+    from femo_amd.fea.fea_hip import (FEA, Constant, Function, FunctionSpace, Measure, ThermalExpansion, VectorFunctionSpace,
+                                      createRectangleMesh, locate_dofs_geometrical, locate_entities_boundary, meshSize, meshtags,
+                                      pdeRes_conduction)
+    LX, LY = 160.0, 80.0
+    mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([LX, LY]), args.nelx, args.nely)
+    marker, t = load_cases(2, 1, args.nely)[0]
+    facets = locate_entities_boundary(mesh, 1, marker)
+    ds = Measure("ds", domain=mesh, subdomain_data=meshtags(mesh, 1, facets, np.full(len(facets), 100, dtype=np.int32)))(100)
+    Q, P, V = FunctionSpace(mesh, ("DG", 0)), FunctionSpace(mesh, ("CG", 1)), VectorFunctionSpace(mesh, ("CG", 1))
+    clamp = lambda x: np.isclose(x[0], 0.0, atol=1e-6)
+    feas, res_t, th = [], None, None
+    if thermal:
+        ft = FEA(mesh)
+        ft.REPORT = False
+        ft.consistent_bc_partials = True
+        rho_t, T = Function(Q), Function(P)
+        res_t = pdeRes_conduction(T, None, rho_t, source=1e-2, k0=1.0, k_min=1e-3)
+        ft.add_input("density", rho_t)
+        ft.add_state(name="temperature", function=T, residual_form=res_t, arguments=["density"])
+        Tbc = Function(P)
+        Tbc.vector.set(0.0)
+        ft.add_strong_bc(Tbc, [locate_dofs_geometrical((P, P), clamp)], P)
+        feas.append(ft)
+    fe = FEA(mesh)
+    fe.REPORT = False
+    fe.consistent_bc_partials = True
+    rho, u, f = Function(Q), Function(V), Constant(mesh, t)
+    fe.add_input("density", rho)
+    args_u = ["density"]
+    if thermal:
+        T_in = Function(P)
+        th = ThermalExpansion(1e-2, T_in)
+        fe.add_input("temperature", T_in)
+        args_u.append("temperature")
+    res = pdeRes(u, None, rho, f, dss=ds, preconditioner=args.pc, thermal=th)
+    fe.add_state(name="displacements", function=u, residual_form=res, arguments=args_u)
+    fe.add_output(name="compliance", type="scalar", form=compliance(u, f, dss=ds, rho_e=rho if thermal else None, thermal=th),
+                  arguments=["displacements"] + (args_u if thermal else []))
+    ubc = Function(V)
+    ubc.vector.set(0.0)
+    fe.add_strong_bc(ubc, [locate_dofs_geometrical((V, V), clamp)], V)
+    feas.append(fe)
+    model = FEAModel(fea=feas)
+    h = meshSize(mesh)
+    model.add(GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
+              name="general_filter_model")
+    model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.random.default_rng(0).random(mesh.n_cell) * 0.86)
+    return Simulator(model), mesh, res, res_t
+
+
+def conduction_counts(ctx, sizes=((80, 40), (320, 160), (640, 320))):
+    """Jacobi-PCG iterations of the conduction state (uniform source) and of an adjoint-like solve (right-hand side: the state)
+    at rho = 0.5 and on the black / white truss pattern, k_min = 1e-3, the sink on x = 0, rtol 1e-13: the baseline a later
+    preconditioner is judged against."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import elast_pc_ref as pr
+    from femo_amd.fea.conduction import ConductionResidual
+    from femo_amd.fea.fea_hip import Function, FunctionSpace, createRectangleMesh, dirichletbc, locate_dofs_geometrical
+    out = []
+    for nelx, nely in sizes:
+        mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([160.0, 80.0]), nelx, nely)
+        Q, P = FunctionSpace(mesh, ("DG", 0)), FunctionSpace(mesh, ("CG", 1))
+        T, rho = Function(P), Function(Q)
+        form = ConductionResidual(T, rho, source=1e-2, k0=1.0, k_min=1e-3)
+        bcs = [dirichletbc(0.0, locate_dofs_geometrical((P, P), lambda x: np.isclose(x[0], 0.0, atol=1e-6)), P)]
+        for kind in ("uniform", "truss"):
+            rho.vector[:] = pr.count_density(kind, mesh.centroids(), 80.0)
+            form.solve_state(T, bcs)
+            st = dict(form.last_info["state"])
+            A, _ = form.assemble_system(bcs, False, None, None)
+            lam = Function(P)
+            A.backend_solve(T.vec, lam.vec)
+            ad = form.last_info["adjoint"]
+            out.append(dict(mesh=f"rect {nelx}x{nely}", density=kind, n_vert=mesh.n_vert, state_iterations=st["iterations"],
+                            state_ms=st["solve_ms"], adjoint_iterations=ad["iterations"], adjoint_ms=ad["solve_ms"]))
+    return out
+
+
+def main_thermal(args, ctx):
+    """The thermoelastic cycle and the mechanical-only cycle of the same build in alternation, the three launches of the
+    thermal-load operator and the conduction assembly timed in windows of launches, and the conduction iteration counts."""
+    from femo_amd import _lib
+    from femo_amd.engine import Vec
+    legs = {name: build_thermoelastic(args, name == "thermoelastic") for name in ("thermoelastic", "mechanical")}
+    x0 = np.array(legs["mechanical"][0]["density_unfiltered"])
+    times = {name: [] for name in legs}
+    for k in range(args.cycles + 1):
+        for name, (sim, *_rest) in legs.items():
+            sim["density_unfiltered"] = x0 * (1.0 - 1e-3 * k)
+            ctx.sync()
+            t0 = time.perf_counter()
+            sim.run()
+            np.asarray(sim.compute_totals("compliance", "density_unfiltered"))
+            ctx.sync()
+            if k > 0:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+    sim, mesh, res, res_t = legs["thermoelastic"]
+    dev, n, nc, nv = res.device(), res.n_dof, mesh.n_cell, mesh.n_vert
+    rho, T = res.rho.vec, res.thermal.thermal.function.vec
+    y, yc, yv, one = Vec(ctx, n), Vec(ctx, nc), Vec(ctx, nv), np.ones(1)
+
+    def timed(body, reps=200):
+        body()
+        ctx.sync()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            body()
+        ctx.sync()
+        return (time.perf_counter() - t0) * 1e6 / reps
+
+    cond = res_t.device()
+    launches = dict(
+        thermal_N_us=timed(lambda: dev.thermal_apply(_lib.ELAST_SIMP, "N", 1, one, 1e-2, rho, T, y)),
+        thermal_T_rho_us=timed(lambda: dev.thermal_apply(_lib.ELAST_SIMP, "T_rho", 1, one, 1e-2, rho, T, yc, x=res.u.vec)),
+        thermal_T_temp_us=timed(lambda: dev.thermal_apply(_lib.ELAST_SIMP, "T_temp", 1, one, 1e-2, rho, 0.0, yv, x=res.u.vec)),
+        conduction_assemble_us=timed(lambda: cond.assemble(_lib.ELAST_SIMP, 1.0, 1e-3, res_t.rho.vec, res_t._bc)))
+    it, ie, im = res_t.last_info, res.last_info, legs["mechanical"][2].last_info
+    out = dict(metric="topopt_cycle_thermoelastic", mesh=f"rect {args.nelx}x{args.nely}", n_dof=n, n_cell=nc, pc=args.pc,
+               cycle_ms_thermoelastic=float(np.median(times["thermoelastic"])), cycle_ms_mechanical=float(np.median(times["mechanical"])),
+               cycle_ms_thermoelastic_all=[float(v) for v in times["thermoelastic"]],
+               cycle_ms_mechanical_all=[float(v) for v in times["mechanical"]],
+               conduction_iterations=[it["state"]["iterations"], it["adjoint"]["iterations"]],
+               conduction_solve_ms=[it["state"]["solve_ms"], it["adjoint"]["solve_ms"]],
+               elasticity_iterations=[ie["state"]["iterations"], ie["adjoint"]["iterations"]],
+               elasticity_solve_ms=[ie["state"]["solve_ms"], ie["adjoint"]["solve_ms"]],
+               mechanical_iterations=[im["state"]["iterations"], im["adjoint"]["iterations"]],
+               compliance_thermoelastic=float(sim["compliance"][0]), compliance_mechanical=float(legs["mechanical"][0]["compliance"][0]),
+               **launches)
+    if args.counts:
+        out["conduction_counts"] = conduction_counts(ctx)
+    print(json.dumps(out))
+
+
 def scipy_cycle(mesh, facets, t, x0, radius):
     """The same cycle with SciPy: KD-tree filter, element-by-element assembly, spsolve forward and adjoint."""
     import scipy.sparse as sp
@@ -519,7 +667,14 @@ def main():
     ap.add_argument("--filter", choices=("neighbours", "helmholtz"), default="neighbours",
                     help="the explicit neighbour list (default) or the Helmholtz PDE filter; single load case, no --harmonic")
     ap.add_argument("--radius-h", type=float, default=2.0, help="filter radius in units of the mean cell size (default 2)")
+    ap.add_argument("--thermal", action="store_true",
+                    help="the thermoelastic cycle (conduction state, thermal expansion load, two adjoint solves) alternated with the "
+                         "mechanical-only cycle of the same build; 2-D, single load case")
+    ap.add_argument("--counts", action="store_true",
+                    help="with --thermal: the Jacobi-PCG iteration counts of the conduction solves at 80x40, 320x160 and 640x320")
     args = ap.parse_args()
+    if args.thermal and (args.n3 or args.load_cases > 1 or args.harmonic or args.stress or args.filter != "neighbours"):
+        ap.error("--thermal: the 2-D cantilever with one load case and the neighbour filter")
     if (args.filter != "neighbours" or args.radius_h != 2.0) and (args.load_cases > 1 or args.harmonic):
         ap.error("--filter / --radius-h: with the single load case only")
     if not args.no_scipy and (args.filter != "neighbours" or args.radius_h != 2.0):
@@ -541,6 +696,8 @@ def main():
         return main_multi(args, ctx)
     if args.harmonic:
         return main_harmonic(args, ctx)
+    if args.thermal:
+        return main_thermal(args, ctx)
     sim, mesh, res, facets, t, filter_build_ms, stress = build(args)
     x0 = np.array(sim["density_unfiltered"])
     times = []

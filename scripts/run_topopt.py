@@ -14,7 +14,10 @@ loop with the device-resident MMA update in the place of modopt's SLSQP / SNOPT.
                       rectangle: input spring and unit input force at the top-left corner, output spring and the objective
                       u_out (port_displacement) at the top-right corner, a roller on the top (symmetry) edge, a clamp on
                       x = 0, y <= 0.1; minimises u_out under avg_density <= volume from x = volume
-  ... --filter helmholtz          the Helmholtz PDE filter (HelmholtzFilterModel, or ProjectedFilterModel(filter="helmholtz") with
+  ... --problem heatsink [--volume 0.3 --move 0.2]   the heat-sink problem on the 2 x 1 rectangle: uniform heating, a sink T = 0
+                      over the middle fifth of the left edge, conductivity k_min + (1 - k_min) rho^3 with k_min = 1e-3
+                      (ConductionResidual); minimises the thermal compliance under avg_density <= volume from x = volume
+  ... --filter helmholtz        the Helmholtz PDE filter (HelmholtzFilterModel, or ProjectedFilterModel(filter="helmholtz") with
                       --betas) in the neighbour list's place: one scalar solve per product, memory independent of the radius
 
 Minimises the compliance under avg_density <= 0.40 from x = 0.4 (--problem cantilever, the default).  Prints one JSON line
@@ -146,6 +149,45 @@ def build_inverter(args):
     return Simulator(model, device=args.device), model, mesh, None
 
 
+def build_heatsink(args):
+    """The heat-sink problem: uniform heating of the 2 x 1 rectangle, a sink T = 0 over the middle fifth of the left edge,
+    conductivity k_min + (1 - k_min) rho^3 with k_min = 1e-3; minimises the thermal compliance Q^T T under
+    avg_density <= volume from x = volume."""
+    from femo_amd.csdl_opt.fea_model import FEAModel
+    from femo_amd.csdl_opt.filter_model import GeneralFilterModel
+    from femo_amd.csdl_opt.simulator import Simulator
+    from femo_amd.fea.elasticity import averageFunc
+    from femo_amd.fea.fea_hip import (FEA, Function, FunctionSpace, createRectangleMesh, locate_dofs_geometrical, meshSize,
+                                      pdeRes_conduction, thermal_compliance)
+    if args.n3:
+        raise SystemExit("--problem heatsink is for the rectangle")
+    LX, LY = 2.0, 1.0
+    mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([LX, LY]), args.nelx, args.nely)
+    fea = FEA(mesh)
+    fea.REPORT = False
+    fea.consistent_bc_partials = True          # the load Q is non-zero on the sink, and so is the multiplier
+    Q, P = FunctionSpace(mesh, ("DG", 0)), FunctionSpace(mesh, ("CG", 1))
+    rho, T = Function(Q), Function(P)
+    res = pdeRes_conduction(T, None, rho, source=1.0, k0=1.0, k_min=1e-3)
+    fea.add_input("density", rho)
+    fea.add_state(name="temperature", function=T, residual_form=res, arguments=["density"])
+    fea.add_output(name="avg_density", type="scalar", form=averageFunc(rho), arguments=["density"])
+    fea.add_output(name="thermal_compliance", type="scalar", form=thermal_compliance(T, source=1.0), arguments=["temperature"])
+    Tbc = Function(P)
+    Tbc.vector.set(0.0)
+    sink = lambda x: np.logical_and(np.isclose(x[0], 0.0), abs(x[1] - LY / 2) <= 0.1 * LY + 1e-9)
+    fea.add_strong_bc(Tbc, [locate_dofs_geometrical((P, P), sink)], P)
+    model = FEAModel(fea=[fea])
+    h = meshSize(mesh)
+    model.add(GeneralFilterModel(nel=mesh.n_cell, coordinates=Q.tabulate_dof_coordinates(), h_avg=(h.max() + h.min()) / 2),
+              name="general_filter_model")
+    model.create_input("density_unfiltered", shape=mesh.n_cell, val=np.full(mesh.n_cell, args.volume))
+    model.add_design_variable("density_unfiltered", upper=1.0, lower=1e-3)
+    model.add_objective("thermal_compliance")
+    model.add_constraint("avg_density", upper=args.volume)
+    return Simulator(model, device=args.device), model, mesh, None
+
+
 def newton_step_bytes(n, m):
     """Bytes one Newton step without halvings moves ("Optimiser"): the three reading passes and the
     commit each read x, xi, eta, L, U, alpha, beta and p, q of the m + 1 functions; the commit writes x, xi, eta."""
@@ -176,15 +218,15 @@ def main():
     ap.add_argument("--filter", choices=("neighbours", "helmholtz"), default="neighbours",
                     help="the explicit neighbour list (default) or the Helmholtz PDE filter (memory independent of the radius)")
     ap.add_argument("--out", default=os.path.join("topopt_out", "density.xdmf"))
-    ap.add_argument("--problem", choices=("cantilever", "inverter"), default="cantilever")
+    ap.add_argument("--problem", choices=("cantilever", "inverter", "heatsink"), default="cantilever")
     ap.add_argument("--kin", type=float, default=0.1, help="inverter: the input spring")
     ap.add_argument("--kout", type=float, default=0.1, help="inverter: the output (workpiece) spring")
-    ap.add_argument("--volume", type=float, default=0.3, help="inverter: the volume bound and the start density")
-    ap.add_argument("--move", type=float, default=None, help="the move limit of MMA (cantilever 0.5, inverter 0.2)")
+    ap.add_argument("--volume", type=float, default=0.3, help="inverter, heatsink: the volume bound and the start density")
+    ap.add_argument("--move", type=float, default=None, help="the move limit of MMA (cantilever 0.5, inverter and heatsink 0.2)")
     args = ap.parse_args()
-    inverter = args.problem == "inverter"
-    if inverter and (args.stress or args.betas or args.filter != "neighbours"):
-        raise SystemExit("--problem inverter runs the plain neighbour filter without --stress")
+    inverter, heatsink = args.problem == "inverter", args.problem == "heatsink"
+    if (inverter or heatsink) and (args.stress or args.betas or args.filter != "neighbours"):
+        raise SystemExit(f"--problem {args.problem} runs the plain neighbour filter without --stress")
     if args.solid_frame and not args.betas:
         raise SystemExit("--solid-frame needs --betas (passive cells go through the projection)")
     from femo_amd import _lib
@@ -196,7 +238,7 @@ def main():
         raise SystemExit("run_topopt needs a HIP device")
     ctx = Context(0)
     utils_hip.set_context(ctx)
-    sim, model, mesh, stress = build_inverter(args) if inverter else build(args)
+    sim, model, mesh, stress = build_inverter(args) if inverter else build_heatsink(args) if heatsink else build(args)
     utils_hip.LAST_KSP_INFO.clear()          # a complete record of this run's solves
     n = mesh.n_cell
     if stress is not None:
@@ -209,7 +251,7 @@ def main():
     prob = CSDLProblem(problem_name="beam_topo_opt", simulator=sim)
     op = args.projection.operation if args.betas else None
     cont = BetaContinuation(op, args.betas, args.every) if args.betas else None
-    move = args.move if args.move is not None else (0.2 if inverter else 0.5)
+    move = args.move if args.move is not None else (0.2 if inverter or heatsink else 0.5)
     optimizer = MMA(prob, max_iter=args.iters, move=move, tol=0.0, sub_tol=1e-7, normalize=True, continuation=cont).setup()
     host = dict(ms=[], dx=[], newton=[])
     proj_ms = []
@@ -270,6 +312,12 @@ def main():
         pcg_log = [r for r in utils_hip.LAST_KSP_INFO if str(r.get("kind", "")).startswith("elasticity_")]
         out.update(metric="topopt_mma_inverter", u_out=res["objective"], final_u_out=float(np.asarray(sim["u_out"]).ravel()[0]),
                    kin=args.kin, kout=args.kout, volume=args.volume, move=move,
+                   pcg_iterations=[[r["kind"].split("_")[-1], r["iterations"]] for r in pcg_log])
+    elif heatsink:
+        # state and adjoint Jacobi-PCG of every design cycle, in the order they ran
+        pcg_log = [r for r in utils_hip.LAST_KSP_INFO if str(r.get("kind", "")).startswith("conduction_")]
+        out.update(metric="topopt_mma_heatsink", final_thermal_compliance=float(np.asarray(sim["thermal_compliance"]).ravel()[0]),
+                   volume=args.volume, move=move, k_min=1e-3,
                    pcg_iterations=[[r["kind"].split("_")[-1], r["iterations"]] for r in pcg_log])
     else:
         out["final_compliance"] = float(np.asarray(sim["compliance"]).ravel()[0])
