@@ -95,7 +95,10 @@ class HostStats(C.Structure):
                                          "h2d_deferred", "h2d_deferred_bytes",
                                          # appended with femo_mesh_head_info: a build without it leaves the field at 0 (the
                                          # library fills the struct it knows; engine.host_stats reports the field only when bound)
-                                         "h2d_chunks")]
+                                         "h2d_chunks",
+                                         # appended with femo_vec_get_host_promised_ex: the pool's own bookkeeping
+                                         "pool_fresh", "pool_fresh_us", "pool_free_deferred", "pool_free_waited",
+                                         "pool_free_waited_us")]
 
 
 # name -> (restype, argtypes); every symbol include/femo_hip.h declares
@@ -119,7 +122,9 @@ PROTOTYPES = {
     "femo_vec_add_to_host": (C.c_int, [H, C.c_void_p, c_i64]),
     "femo_vec_get_host_async": (C.c_int, [H, C.c_void_p, c_i64]),
     "femo_vec_get_host_promised": (C.c_int, [H, C.c_void_p, c_i64]),
+    "femo_vec_get_host_promised_ex": (C.c_int, [H, C.c_void_p, c_i64, C.c_int]),
     "femo_host_forget": (C.c_int, [C.c_void_p]),
+    "femo_range_plan_host": (C.c_int, [c_i64, c_i64, C.c_int, c_i64, c_i64, c_i64, C.POINTER(c_i64), c_i64]),
     "femo_vec_set_host_deferred": (C.c_int, [H, C.c_void_p, c_i64]),
     "femo_vec_await_upload": (C.c_int, [H]),
     "femo_host_wait": (C.c_int, [C.c_void_p]),
@@ -353,6 +358,7 @@ PROTOTYPES = {
 OPTIONAL = frozenset({"femo_mesh_pcg_info", "femo_mesh_head_info", "femo_mat_identity_solve_flag", "femo_vec_axpy_if",
                       "femo_newton_rhs_linear_if", "femo_ctx_newton_flag_info", "femo_mesh_tail_info",
                       "femo_dRdf_cell_apply_T_add_to_host", "femo_vec_get_host_promised", "femo_host_forget",
+                      "femo_vec_get_host_promised_ex", "femo_range_plan_host",
                       "femo_mat_compact_info", "femo_mat_spmv_scaled", "femo_mat_import_csr"})
 
 

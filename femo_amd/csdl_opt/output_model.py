@@ -59,8 +59,10 @@ class OutputOperation(_OutputOperationBase):
         dev = stays_on_device(inputs)
         form = self.output['form']
         # smallest first: with asynchronous results the copies leave in this order, and the adjoint seed (dJ/du)
-        # is what the backend needs next
-        with lazy_results(self.fea.async_results):
+        # is what the backend needs next.  From 1 MiB on they are only promised: a reverse sweep hands dJ/du back to the
+        # library as the adjoint's right-hand side and lets the library overwrite the explicit dJ/df from the device, so
+        # neither has to cross the link unless somebody reads it (host_wait / host_sync keep the promise).
+        with lazy_results(self.fea.async_results, on_demand=True, outputs=True):
             for name, entry in sorted(self.args_dict.items(), key=lambda kv: kv[1]['shape']):
                 derivatives[self.output_name, name] = assemble(computePartials(form, entry['function']),
                                                                dim=self.output_dim + 1, device=dev)

@@ -266,6 +266,11 @@ class Simulator:
                         d_outputs = {state: _readonly(seed)}
                         d_residuals = {state: np.zeros(0)}          # assigned by the operation
                         op.apply_inverse_jacobian(d_outputs, d_residuals, 'rev')
+                        # the solve took its right-hand side from the device where rhs was only promised (and seed with it:
+                        # -1 x a promised array is a promise): neither is read here again, so neither has to travel
+                        E.host_forget(seed)
+                        if isinstance(rhs, np.ndarray):
+                            E.host_forget(rhs)
                         d_inputs = {}
                         for k in op.input_meta:
                             if k in adj:

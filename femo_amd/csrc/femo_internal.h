@@ -204,12 +204,11 @@ struct femo_vec {
   // assembly pass, S A S and the preconditioner weights run under the upload of f)
   hipEvent_t h2d_ev = nullptr;
   bool h2d_pending = false;
-  // the upload in flight travels as h2d_chunks copies of h2d_chunk_n entries, the last one of what remains:
-  // h2d_chunk_ev[k] follows copy k < h2d_chunks - 1, h2d_ev the last.  The events stay with the vector from
-  // upload to upload.  h2d_chunks <= 1: one copy, no prefix to wait for (femo_vec_await_prefix)
-  // (the last chunk takes the remainder: the copies end at k * h2d_chunk_n, a multiple of 256 entries, and at n)
+  // the upload in flight travels as h2d_chunks copies, copy k ending at entry h2d_ends[k] (range_plan.h: multiples of
+  // 256 entries, the last one n): h2d_chunk_ev[k] follows copy k < h2d_chunks - 1, h2d_ev the last.  The events stay
+  // with the vector from upload to upload.  h2d_chunks <= 1: one copy, no prefix to wait for (femo_vec_await_prefix)
   std::vector<hipEvent_t> h2d_chunk_ev;
-  int64_t h2d_chunk_n = 0;
+  std::vector<int64_t> h2d_ends;
   int h2d_chunks = 0;
 };
 void femo_vec_wait_readers(femo_vec* v);   // hostmem.cpp

@@ -5,7 +5,8 @@
 // (the DG0 source of the 10 M-DOF cube) per call.  Three mechanisms:
 //
 //  1. Pinned host blocks (femo_host_alloc / femo_host_register).  A transfer from or to a pinned
-//     block is one DMA at PCIe rate.  The library hands its own results out in such blocks.
+//     block is one DMA at PCIe rate.  The library hands its own results out in such blocks.  Released blocks are recycled;
+//     one released while a DMA still owns it is parked and recycled by a later pool call, never waited for (g_limbo).
 //  2. Pageable user memory goes through a ring of pinned staging slots: a pool of host threads
 //     copies chunk i+1 into (out of) a slot while the DMA engine moves chunk i, instead of the HIP
 //     runtime's single-threaded pageable path (measured 3-5 GB/s in round 1).
@@ -31,16 +32,20 @@
 //     chunks arrive (same bits: one IEEE addition per entry either way).
 //  6. The streamed tail (femo_dRdf_cell_apply_T_add_to_host).  The last statement of a reverse sweep, dJ/df += (dR/df)^T psi
 //     into such a block, forms the sum range by range -- product and addition in one kernel, no round trip of the product
-//     through HBM -- and sends each range down on the copy stream while the next one is computed.
+//     through HBM -- and sends each range down on the copy stream while the next one is computed.  Its ranges grow from a
+//     short first one, the pieces of the chunked upload of f shrink to a short last one (range_plan.h).
 //  7. Promised results (femo_vec_get_host_promised).  A block is recorded as the copy of a vector and marked pending, but
 //     nothing travels until somebody asks for the bytes (femo_host_wait, femo_host_sync, any entry that reads the block) or
 //     the vector is about to change.  Handed back to femo_vec_set_host it is elided like any mirror; femo_host_forget drops
 //     it.  The multiplier of the adjoint solve is consumed on the device and never read on the host: its 8 n_vert bytes
-//     stay off the link that carries the gradient.
+//     stay off the link that carries the gradient.  So do the partials of an output operator (FEMO_PROMISE_OUTPUT): dJ/du
+//     goes back into the adjoint solve -- femo_host_axpby(-1, x, 0, y) from a promised x promises y the product -- and the
+//     explicit dJ/df is the block the streamed tail overwrites from the device.
 #include <sched.h>
 #include <unistd.h>
 
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdlib>
 #include <fstream>
@@ -52,6 +57,7 @@
 #include <unordered_map>
 
 #include "femo_internal.h"
+#include "range_plan.h"
 
 namespace {
 
@@ -255,6 +261,31 @@ int64_t d2h_chunk_entries() {
   return std::max<int64_t>(n, 256);
 }
 
+// The taper of both plans (range_plan.h), read once per transfer.  FEMO_RANGE_FLOOR_MB: the size of the upload's last and of
+// the download's first piece in MiB (fractions allowed; 0, or at least the chunk size: equal pieces as before);
+// FEMO_RANGE_FACTOR: the ratio of neighbouring pieces inside the taper (below 2: equal pieces); FEMO_D2H_MAX_CHUNK_MB: up to
+// where the download's ranges grow beyond FEMO_D2H_CHUNK_MB once they taper.  Defaults: DESIGN_LOG.md R30.
+constexpr double RANGE_FLOOR_MB_DEFAULT = 8.0, D2H_MAX_CHUNK_MB_DEFAULT = 128.0;
+constexpr int64_t RANGE_FACTOR_DEFAULT = 4;
+struct RangeTaper { int64_t floor, factor, d2h_cap; };
+int64_t mb_entries(const char* name, double mb) {
+  if (const char* e = getenv(name)) {
+    char* end = nullptr;
+    const double v = strtod(e, &end);
+    if (end != e && v >= 0.0 && v <= 65536.0) mb = v;
+  }
+  return (int64_t)(mb * 1048576.0 / sizeof(double));
+}
+RangeTaper range_taper() {
+  RangeTaper t;
+  t.floor = mb_entries("FEMO_RANGE_FLOOR_MB", RANGE_FLOOR_MB_DEFAULT);
+  if (t.floor <= 0) t.floor = INT64_MAX / 2;             // no taper
+  t.factor = RANGE_FACTOR_DEFAULT;
+  if (const char* e = getenv("FEMO_RANGE_FACTOR")) t.factor = std::max(0, atoi(e));
+  t.d2h_cap = mb_entries("FEMO_D2H_MAX_CHUNK_MB", D2H_MAX_CHUNK_MB_DEFAULT);
+  return t;
+}
+
 // A copy-out is promised only from this size on.  Below it the copy costs no more than its own launch (1 MiB takes 19 us at
 // the link's 56 GB/s), so keeping it off the link saves nothing, while a promise that has to be kept in front of a writer
 // would put the copy and a wait of the compute stream where the eager copy had long landed; and a small result keeps
@@ -267,8 +298,42 @@ bool on_demand_enabled() {
   return e == nullptr || strcmp(e, "0") != 0;
 }
 
+// The switch of the promises an output operator asks for (FEMO_PROMISE_OUTPUT: dJ/du, which goes straight back into the adjoint
+// solve, and the explicit dJ/df, which the streamed tail overwrites from the device).  Its own switch, so that
+// FEMO_D2H_ON_DEMAND=0 still measures the multiplier's copy alone.
+bool promise_outputs_enabled() {
+  const char* e = getenv("FEMO_D2H_PROMISE_OUTPUTS");
+  return e == nullptr || strcmp(e, "0") != 0;
+}
+
 // events of blocks that left the registry, kept for the next block that needs one
 std::vector<hipEvent_t> g_ev_free;
+
+// Blocks released while a DMA still owned them (an array dropped with its copy-out or upload in flight).  femo_host_free
+// does not wait for the transfer -- it would hold up the interpreter thread, and under g_mu every other caller of the
+// pool: the block waits here, out of the registry, and the next pool call whose query finds the event complete recycles
+// it.  A block never reaches g_free, and so never a new owner, before its last DMA is over.
+struct LimboBlock { void* p; size_t bytes; hipEvent_t ready; };
+std::vector<LimboBlock> g_limbo;
+
+int64_t now_us() {
+  return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// Return block p to the recycled ones, making room under the cap first.  g_mu held; what has to be hipHostFree'd (outside the
+// lock) goes to `evict`.
+void recycle_block(void* p, size_t bytes, std::vector<void*>& evict);
+
+void sweep_limbo(std::vector<void*>& evict) {            // g_mu held
+  for (size_t i = 0; i < g_limbo.size();) {
+    if (hipEventQuery(g_limbo[i].ready) != hipSuccess) { ++i; continue; }
+    const LimboBlock lb = g_limbo[i];
+    g_limbo[i] = g_limbo.back();
+    g_limbo.pop_back();
+    g_ev_free.push_back(lb.ready);
+    recycle_block(lb.p, lb.bytes, evict);
+  }
+}
 
 hipEvent_t take_event() {                                // g_mu held
   if (!g_ev_free.empty()) { hipEvent_t e = g_ev_free.back(); g_ev_free.pop_back(); return e; }
@@ -285,7 +350,15 @@ int ensure_copy_stream(femo_ctx* c) {
 }
 
 // promised copy-outs ------------------------------------------------------------------
-struct PromisedCopy { double* host; femo_vec* v; int64_t n; hipEvent_t ready; };
+// (scale: the block was promised scale * v, femo_host_axpby(a, x, 0, y) from a promised x: the factor is applied on the host
+// behind the copy, as it would have been had x travelled)
+struct PromisedCopy { double* host; femo_vec* v; int64_t n; hipEvent_t ready; double scale; };
+struct DeferredScale { double* y; const double* x; int64_t n; double a; };
+void run_deferred_scale(void* p) {                       // hipLaunchHostFunc callback: host work only, no HIP calls
+  DeferredScale* d = static_cast<DeferredScale*>(p);
+  par_stream(d->y, d->x, d->n, 2, d->a, 0.0);
+  delete d;
+}
 
 // The promise leaves block b: its copy is about to be enqueued (out != null) or will never be.  g_mu held.
 bool take_promise(HostBlock& b, PromisedCopy* out) {
@@ -294,7 +367,7 @@ bool take_promise(HostBlock& b, PromisedCopy* out) {
   auto it = g_live.find(b.src_uid);
   femo_vec* v = it != g_live.end() ? it->second : nullptr;
   if (v != nullptr && v->promises > 0) --v->promises;
-  if (out != nullptr) *out = PromisedCopy{reinterpret_cast<double*>(b.base), v, b.src_n, b.ready};
+  if (out != nullptr) *out = PromisedCopy{reinterpret_cast<double*>(b.base), v, b.src_n, b.ready, b.src_scale};
   return true;
 }
 
@@ -319,8 +392,10 @@ int send_promised(const PromisedCopy& pc) {
   FEMO_HIP_CHECK(hipEventRecord(c->ev_copy, c->stream));
   FEMO_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, c->ev_copy, 0));
   FEMO_HIP_CHECK(hipMemcpyAsync(pc.host, v->d, pc.n * sizeof(double), hipMemcpyDeviceToHost, c->copy_stream));
-  FEMO_HIP_CHECK(hipEventRecord(pc.ready, c->copy_stream));
   FEMO_HIP_CHECK(hipEventRecord(v->d2h_ev, c->copy_stream));
+  // (in place on the block, y == x: every entry is read and written once by the same thread of par_stream's op 2 with b = 0)
+  if (pc.scale != 1.0) FEMO_HIP_CHECK(hipLaunchHostFunc(c->copy_stream, run_deferred_scale, new DeferredScale{pc.host, pc.host, pc.n, pc.scale}));
+  FEMO_HIP_CHECK(hipEventRecord(pc.ready, c->copy_stream));
   v->d2h_pending = true;
   std::lock_guard<std::mutex> lk(g_mu);
   ++g_stats.d2h_async; g_stats.d2h_async_bytes += pc.n * 8;
@@ -472,8 +547,10 @@ int femo_host_alloc(int64_t bytes, void** out) {
   FEMO_REQUIRE(out != nullptr && bytes >= 0, "bad argument");
   *out = nullptr;
   const size_t need = (size_t)std::max<int64_t>(bytes, 8);
+  std::vector<void*> evict;
   {
     std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_limbo.empty()) sweep_limbo(evict);
     auto it = g_free.find(need);
     if (it != g_free.end()) {
       *out = it->second;
@@ -482,56 +559,70 @@ int femo_host_alloc(int64_t bytes, void** out) {
       HostBlock b;
       b.base = static_cast<char*>(*out); b.bytes = need; b.pooled = true;
       g_blocks[reinterpret_cast<uintptr_t>(*out)] = b;
-      return 0;
     }
   }
+  for (void* q : evict) (void)hipHostFree(q);
+  if (*out != nullptr) return 0;
   void* p = nullptr;
+  const int64_t t0 = now_us();
   FEMO_HIP_CHECK(hipHostMalloc(&p, need, hipHostMallocDefault));
+  const int64_t dt = now_us() - t0;
   HostBlock b;
   b.base = static_cast<char*>(p); b.bytes = need; b.pooled = true;
   std::lock_guard<std::mutex> lk(g_mu);
+  ++g_stats.pool_fresh; g_stats.pool_fresh_us += dt;
   g_blocks[reinterpret_cast<uintptr_t>(p)] = b;
   *out = p;
   return 0;
 }
 
+namespace {
+void recycle_block(void* p, size_t bytes, std::vector<void*>& evict) {
+  // Over the cap: make room by dropping recycled blocks of OTHER sizes, largest first -- the size being freed now is the
+  // one the running workload allocates again.  (Round 3 dropped the freed block itself: after a 10 M-DOF run had filled
+  // the pool with 477 MB blocks, every result block of a smaller problem was hipHostMalloc'ed and hipHostFree'd again,
+  // 50 ms per cycle of the 5 M-DOF configuration in bench.py.)
+  while (g_free_bytes + bytes > FREE_CAP && !g_free.empty()) {
+    auto victim = g_free.end();
+    for (auto jt = g_free.rbegin(); jt != g_free.rend(); ++jt)
+      if (jt->first != bytes) { victim = std::next(jt).base(); break; }
+    if (victim == g_free.end()) break;
+    evict.push_back(victim->second);
+    g_free_bytes -= victim->first;
+    g_free.erase(victim);
+  }
+  if (g_free_bytes + bytes <= FREE_CAP) {
+    g_free.emplace(bytes, p);
+    g_free_bytes += bytes;
+  } else {
+    evict.push_back(p);
+  }
+}
+}  // namespace
+
 int femo_host_free(void* p) {
   if (!p) return 0;
-  size_t bytes = 0;
-  bool keep = false;
   std::vector<void*> evict;
   {
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_blocks.find(reinterpret_cast<uintptr_t>(p));
     FEMO_REQUIRE(it != g_blocks.end() && it->second.pooled, "femo_host_free: not a block of femo_host_alloc");
-    bytes = it->second.bytes;
+    const size_t bytes = it->second.bytes;
     if (take_promise(it->second, nullptr)) it->second.pending = false;   // nobody can read the block any more
-    if (it->second.ready != nullptr) {
-      if (it->second.pending) (void)hipEventSynchronize(it->second.ready);   // the DMA still owns the block
-      g_ev_free.push_back(it->second.ready);
-    }
+    const hipEvent_t ready = it->second.ready;
+    // the DMA still owns the block: it comes back through g_limbo, never by waiting here under the lock
+    const bool in_flight = ready != nullptr && it->second.pending && hipEventQuery(ready) != hipSuccess;
     g_blocks.erase(it);
-    // Over the cap: make room by dropping recycled blocks of OTHER sizes, largest first -- the size being freed now is the
-    // one the running workload allocates again.  (Round 3 dropped the freed block itself: after a 10 M-DOF run had filled
-    // the pool with 477 MB blocks, every result block of a smaller problem was hipHostMalloc'ed and hipHostFree'd again,
-    // 50 ms per cycle of the 5 M-DOF configuration in bench.py.)
-    while (g_free_bytes + bytes > FREE_CAP && !g_free.empty()) {
-      auto victim = g_free.end();
-      for (auto jt = g_free.rbegin(); jt != g_free.rend(); ++jt)
-        if (jt->first != bytes) { victim = std::next(jt).base(); break; }
-      if (victim == g_free.end()) break;
-      evict.push_back(victim->second);
-      g_free_bytes -= victim->first;
-      g_free.erase(victim);
-    }
-    if (g_free_bytes + bytes <= FREE_CAP) {
-      g_free.emplace(bytes, p);
-      g_free_bytes += bytes;
-      keep = true;
+    if (!g_limbo.empty()) sweep_limbo(evict);
+    if (in_flight) {
+      g_limbo.push_back(LimboBlock{p, bytes, ready});
+      ++g_stats.pool_free_deferred;
+    } else {
+      if (ready != nullptr) g_ev_free.push_back(ready);
+      recycle_block(p, bytes, evict);
     }
   }
   for (void* q : evict) (void)hipHostFree(q);
-  if (!keep) FEMO_HIP_CHECK(hipHostFree(p));
   return 0;
 }
 
@@ -539,6 +630,7 @@ int femo_host_trim(void) {
   std::vector<void*> drop;
   {
     std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_limbo.empty()) sweep_limbo(drop);             // (blocks still in flight stay: their DMA owns them)
     for (auto& kv : g_free) drop.push_back(kv.second);
     g_free.clear();
     g_free_bytes = 0;
@@ -562,11 +654,20 @@ int femo_host_register(void* p, int64_t bytes) {
 }
 
 int femo_host_unregister(void* p) {
+  hipEvent_t in_flight = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_mu);
     auto it = g_blocks.find(reinterpret_cast<uintptr_t>(p));
     FEMO_REQUIRE(it != g_blocks.end() && !it->second.pooled, "femo_host_unregister: not a registered range");
-    if (it->second.ready != nullptr && it->second.pending) (void)hipEventSynchronize(it->second.ready);
+    if (it->second.ready != nullptr && it->second.pending) in_flight = it->second.ready;
+  }
+  if (in_flight != nullptr) {
+    // not under the lock: the range's owner is the one who waits (caller memory cannot be parked: it is about to be freed)
+    const int64_t t0 = now_us();
+    (void)hipEventSynchronize(in_flight);
+    const int64_t dt = now_us() - t0;
+    std::lock_guard<std::mutex> lk(g_mu);
+    ++g_stats.pool_free_waited; g_stats.pool_free_waited_us += dt;
   }
   // The record goes only once the runtime has let go of the range: if it refuses, the range is still pinned for it, and a
   // registry that had forgotten it would hand the next array at this address to the staged path as if it were pageable.
@@ -623,19 +724,29 @@ int femo_host_copy(double* dst, const double* src, int64_t n) {
   return 0;
 }
 
-namespace {
-struct DeferredScale { double* y; const double* x; int64_t n; double a; };
-void run_deferred_scale(void* p) {                       // hipLaunchHostFunc callback: host work only, no HIP calls
-  DeferredScale* d = static_cast<DeferredScale*>(p);
-  par_stream(d->y, d->x, d->n, 2, d->a, 0.0);
-  delete d;
-}
-}  // namespace
-
 int femo_host_axpby(int64_t n, double a, const double* x, double b, double* y) {
   FEMO_REQUIRE((x && y) || n == 0, "null argument");
   if (n == 0) return 0;
+  if (b == 0.0 && x != y) drop_promise(y);               // overwritten whole: what it was promised need not travel
   FEMO_TRY(wait_block(y));
+  // y = a x with x a block that was only PROMISED the content of a live vector: y is promised a times that vector, and
+  // nothing is read or sent.  (The reverse sweep negates dJ/du this way; the adjoint solve takes the seed from the device.)
+  if (b == 0.0 && a != 0.0 && x != y) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    HostBlock* bx = find_block(x, (size_t)n * sizeof(double));
+    HostBlock* by = find_block(y, (size_t)n * sizeof(double));
+    if (bx && by && bx != by && by->pooled && bx->promised && !by->pending && reinterpret_cast<const char*>(x) == bx->base &&
+        reinterpret_cast<char*>(y) == by->base && bx->src_uid != 0 && bx->src_n == n) {
+      auto it = g_live.find(bx->src_uid);
+      if (it != g_live.end() && it->second->gen == bx->src_gen && by->ready == nullptr) by->ready = take_event();
+      if (it != g_live.end() && it->second->gen == bx->src_gen && by->ready != nullptr) {
+        by->src_uid = bx->src_uid; by->src_gen = bx->src_gen; by->src_n = n; by->src_scale = a * bx->src_scale; by->const_n = 0;
+        by->pending = true; by->pend_ctx = bx->pend_ctx; by->promised = true;
+        ++it->second->promises;
+        return 0;
+      }
+    }
+  }
   FEMO_TRY(resolve_block(x));                            // x is read below, at once or behind its copy
   // y = a x with x a block that mirrors a device vector: y is then known to be a * that vector without its bytes
   // (femo_vec_set_host from y becomes a device-side scale).  If x is still on its way down the host pass is queued
@@ -806,9 +917,10 @@ int femo_vec_set_host_deferred(femo_vec* v, const double* host, int64_t n) {
   // The copy travels in chunks, each followed by an event of its own, so that a reader which needs only a prefix of v can
   // start on it (femo_vec_await_prefix: the streamed head of femo_newton_rhs_linear).  The last chunk's event is h2d_ev:
   // femo_vec_await, the block's `ready` event and the provenance below see one upload that is over when all of it is.
-  int64_t chunk_n = h2d_chunk_entries();
-  if (chunk_n > 0) chunk_n = std::max(chunk_n, ((n + 1023) / 1024 + 255) / 256 * 256);   // at most 1024 chunks
-  const int n_chunks = chunk_n > 0 ? (int)((n + chunk_n - 1) / chunk_n) : 1;
+  // ... and the pieces shrink towards the end (range_plan.h): only the last one's kernels stand behind the last byte.
+  const RangeTaper tp = range_taper();
+  const auto plan = femo_range_plan(n, h2d_chunk_entries(), FEMO_TAPER_HEAD, tp.floor, tp.factor, 0);
+  const int n_chunks = (int)plan.size();
   while ((int)v->h2d_chunk_ev.size() < n_chunks - 1) {   // kept with the vector: none is created in a warmed-up cycle
     hipEvent_t e = nullptr;
     FEMO_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -824,14 +936,16 @@ int femo_vec_set_host_deferred(femo_vec* v, const double* host, int64_t n) {
   FEMO_REQUIRE(ready != nullptr, "could not create an event");
   FEMO_HIP_CHECK(hipEventRecord(c->ev_copy, c->stream));           // kernels enqueued so far may still read v
   FEMO_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, c->ev_copy, 0));
+  v->h2d_ends.clear();
   for (int k = 0; k < n_chunks; ++k) {
-    const int64_t lo = k * chunk_n, hi = k == n_chunks - 1 ? n : lo + chunk_n;
+    const int64_t lo = plan[(size_t)k].first, hi = plan[(size_t)k].second;
     FEMO_HIP_CHECK(hipMemcpyAsync(v->d + lo, host + lo, (hi - lo) * sizeof(double), hipMemcpyHostToDevice, c->copy_stream));
     if (k < n_chunks - 1) FEMO_HIP_CHECK(hipEventRecord(v->h2d_chunk_ev[k], c->copy_stream));
+    v->h2d_ends.push_back(hi);
   }
   FEMO_HIP_CHECK(hipEventRecord(ready, c->copy_stream));
   FEMO_HIP_CHECK(hipEventRecord(v->h2d_ev, c->copy_stream));
-  v->h2d_chunks = n_chunks; v->h2d_chunk_n = n_chunks > 1 ? chunk_n : 0;
+  v->h2d_chunks = n_chunks;
   v->h2d_pending = true;
   std::lock_guard<std::mutex> lk(g_mu);
   ++g_stats.h2d_pinned; g_stats.h2d_pinned_bytes += n * 8;
@@ -855,7 +969,8 @@ int femo_vec_await(const femo_vec* v_) {
 int femo_vec_await_prefix(const femo_vec* v_, int64_t n_entries) {
   femo_vec* v = const_cast<femo_vec*>(v_);
   if (!v || !v->h2d_pending || n_entries <= 0) return 0;
-  const int64_t k = v->h2d_chunks > 1 ? (n_entries - 1) / v->h2d_chunk_n : 0;
+  // the first chunk that ends at or behind entry n_entries
+  const int64_t k = v->h2d_chunks > 1 ? std::lower_bound(v->h2d_ends.begin(), v->h2d_ends.end(), n_entries) - v->h2d_ends.begin() : 0;
   if (k >= v->h2d_chunks - 1) return femo_vec_await(v);  // the last chunk, or a single copy: all of it
   FEMO_HIP_CHECK(hipStreamWaitEvent(v->ctx->stream, v->h2d_chunk_ev[(size_t)k], 0));
   return 0;
@@ -874,7 +989,18 @@ static int get_host_impl(const femo_vec* v, double* host, int64_t n, int op, boo
   femo_ctx* c = v->ctx;
   FEMO_HIP_CHECK(hipSetDevice(c->device));
   FEMO_TRY(femo_vec_await(v));                           // a deferred upload of v must have landed before it is read back
-  if (op == 0) drop_promise(host);                       // overwritten whole: what it was promised need not travel
+  if (op == 0) {
+    drop_promise(host);                                  // overwritten whole: what it was promised need not travel
+  } else if (!verify_enabled()) {                        // (the verifier compares the block's bytes: it keeps the promise)
+    // accumulate into a block that was only promised the unscaled content of a live vector of this context: the sum below is
+    // formed from that vector on the device, so the promise is dropped, not kept (the record stays for the mirror test below)
+    std::lock_guard<std::mutex> lk(g_mu);
+    HostBlock* b = find_block(host, (size_t)n * sizeof(double));
+    if (b != nullptr && b->promised && b->pooled && reinterpret_cast<char*>(host) == b->base && b->src_n >= n && b->src_scale == 1.0) {
+      auto it = g_live.find(b->src_uid);
+      if (it != g_live.end() && it->second->gen == b->src_gen && it->second->ctx == c && take_promise(*b, nullptr)) b->pending = false;
+    }
+  }
   FEMO_TRY(wait_block(host));                            // an earlier copy-out into the block must not land after this one
   bool pinned = false, exact_base = false;
   femo_vec* mirror = nullptr;                            // live vector the block is an exact copy of (op 1)
@@ -964,11 +1090,12 @@ int femo_vec_add_to_host(const femo_vec* v, double* host, int64_t n) { return ge
 // copy itself is enqueued by whoever first needs the bytes (wait_block, femo_host_sync) or is about to change v
 // (femo_vec_touch, femo_vec_destroy).  Only into a whole pooled block from an owned vector, from PROMISE_MIN_BYTES on; anything
 // else, and FEMO_D2H_ON_DEMAND=0, is femo_vec_get_host_async.
-int femo_vec_get_host_promised(const femo_vec* v, double* host, int64_t n) {
+static int get_host_promised_impl(const femo_vec* v, double* host, int64_t n, int flags) {
   FEMO_REQUIRE(v && host, "null argument");
   FEMO_REQUIRE(n <= v->n, "size mismatch: vector has %lld entries, host array %lld", (long long)v->n, (long long)n);
   if (n == 0) return 0;
-  bool ok = v->uid != 0 && on_demand_enabled() && n * (int64_t)sizeof(double) >= PROMISE_MIN_BYTES;
+  const bool enabled = (flags & FEMO_PROMISE_OUTPUT) ? promise_outputs_enabled() : on_demand_enabled();
+  bool ok = v->uid != 0 && enabled && n * (int64_t)sizeof(double) >= PROMISE_MIN_BYTES;
   if (ok) {
     std::lock_guard<std::mutex> lk(g_mu);
     HostBlock* b = find_block(host, (size_t)n * sizeof(double));
@@ -987,6 +1114,13 @@ int femo_vec_get_host_promised(const femo_vec* v, double* host, int64_t n) {
   b->pending = true; b->pend_ctx = v->ctx; b->promised = true;
   ++vv->promises;
   return 0;
+}
+
+int femo_vec_get_host_promised(const femo_vec* v, double* host, int64_t n) { return get_host_promised_impl(v, host, n, 0); }
+
+int femo_vec_get_host_promised_ex(const femo_vec* v, double* host, int64_t n, int flags) {
+  FEMO_REQUIRE((flags & ~FEMO_PROMISE_OUTPUT) == 0, "femo_vec_get_host_promised_ex: unknown flag");
+  return get_host_promised_impl(v, host, n, flags);
 }
 
 int femo_host_forget(const void* p) {
@@ -1025,7 +1159,7 @@ int femo_dRdf_cell_apply_T_add_to_host(femo_mesh* m, const femo_vec* cvals, cons
   FEMO_TRY(femo_vec_await(cvals));
   FEMO_TRY(femo_vec_await(x));
   FEMO_TRY(femo_vec_await(mirror));
-  drop_promise(host);                                    // its content is read from the vector it mirrors, never from the block
+  if (!verify_enabled()) drop_promise(host);             // its content is read from the vector it mirrors, never from the block
   FEMO_TRY(wait_block(host));                            // an earlier copy-out into the block must not land after this one
   {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -1046,15 +1180,17 @@ int femo_dRdf_cell_apply_T_add_to_host(femo_mesh* m, const femo_vec* cvals, cons
     c->accum_n = n;
   }
   FEMO_TRY(ensure_copy_stream(c));
-  const int64_t chunk_n = std::max(chunk_env, ((n + 1023) / 1024 + 255) / 256 * 256);   // at most 1024 ranges
-  const int n_ranges = (int)((n + chunk_n - 1) / chunk_n);
+  // short ranges first, so that the first byte leaves early, then longer ones than a chunk: fewer gaps (range_plan.h)
+  const RangeTaper tp = range_taper();
+  const auto plan = femo_range_plan(n, chunk_env, FEMO_TAPER_TAIL, tp.floor, tp.factor, tp.d2h_cap);
+  const int n_ranges = (int)plan.size();
   while ((int)c->d2h_chunk_ev.size() < n_ranges) {       // kept with the context: none is created in a warmed-up cycle
     hipEvent_t e = nullptr;
     FEMO_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     c->d2h_chunk_ev.push_back(e);
   }
   for (int k = 0; k < n_ranges; ++k) {
-    const int64_t lo = k * chunk_n, hi = std::min(n, lo + chunk_n);
+    const int64_t lo = plan[(size_t)k].first, hi = plan[(size_t)k].second;
     FEMO_TRY(femo_launch_dRdf_cell_apply_T_sum(m, cvals->d, x->d, mirror->d, c->d_accum, lo, hi));
     FEMO_HIP_CHECK(hipEventRecord(c->d2h_chunk_ev[(size_t)k], c->stream));
     FEMO_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, c->d2h_chunk_ev[(size_t)k], 0));
@@ -1091,9 +1227,17 @@ int femo_host_sync(void) {
 
 }  // extern "C"
 
+extern "C" int femo_range_plan_host(int64_t n, int64_t chunk, int taper, int64_t floor, int64_t factor, int64_t cap, int64_t* bounds,
+                                    int64_t room) {
+  FEMO_REQUIRE(bounds != nullptr || room == 0, "null argument");
+  const auto plan = femo_range_plan(n, chunk, taper, floor, factor, cap);
+  for (size_t k = 0; k < plan.size() && (int64_t)(2 * k + 1) < room; ++k) { bounds[2 * k] = plan[k].first; bounds[2 * k + 1] = plan[k].second; }
+  return (int)plan.size();
+}
+
 int femo_vec_upload_chunks(const femo_vec* v, std::vector<int64_t>& ends) {
   ends.clear();
   if (!v || !v->h2d_pending || v->h2d_chunks <= 1) return 0;
-  for (int k = 0; k < v->h2d_chunks; ++k) ends.push_back(k == v->h2d_chunks - 1 ? v->n : (k + 1) * v->h2d_chunk_n);
+  ends = v->h2d_ends;
   return v->h2d_chunks;
 }

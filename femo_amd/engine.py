@@ -249,10 +249,11 @@ def register(a: np.ndarray) -> bool:
 
 
 _LAZY = threading.local()
+PROMISE_OUTPUT = 1                  # FEMO_PROMISE_OUTPUT (include/femo_hip.h)
 
 
 @contextlib.contextmanager
-def lazy_results(enabled: bool = True, on_demand: bool = False):
+def lazy_results(enabled: bool = True, on_demand: bool = False, outputs: bool = False):
     """Inside the block ``Vec.get()`` (without ``out``) returns its pinned array before the bytes have landed:
     the copy runs on the context's copy stream while later kernels execute.  The caller promises that whoever
     reads the array with code of its own calls ``host_wait`` / ``host_sync`` first (the operator classes hand
@@ -261,14 +262,19 @@ def lazy_results(enabled: bool = True, on_demand: bool = False):
     ``on_demand``: the copy is only promised (femo_vec_get_host_promised).  It leaves at the first ``host_wait`` /
     ``host_sync`` / library call that reads the array, or in front of the next write of the vector; handed back to
     ``Vec.set`` the array is elided without being read, and ``host_forget`` drops the promise.  For results that are
-    usually consumed on the device (the multiplier of an adjoint solve).  Results below 1 MiB leave at once all the same."""
-    prev, prev_od = getattr(_LAZY, "on", False), getattr(_LAZY, "on_demand", False)
+    usually consumed on the device (the multiplier of an adjoint solve).  Results below 1 MiB leave at once all the same.
+
+    ``outputs`` (with ``on_demand``): the results are the partials of an output operator (FEMO_PROMISE_OUTPUT) -- dJ/du goes
+    back into the adjoint solve and the explicit dJ/df is overwritten by the streamed tail.  Their switch is
+    FEMO_D2H_PROMISE_OUTPUTS, not FEMO_D2H_ON_DEMAND; a library without the entry point copies them out eagerly."""
+    prev, prev_od, prev_out = getattr(_LAZY, "on", False), getattr(_LAZY, "on_demand", False), getattr(_LAZY, "outputs", False)
     _LAZY.on = bool(enabled) or prev
     _LAZY.on_demand = bool(enabled) and bool(on_demand)
+    _LAZY.outputs = _LAZY.on_demand and bool(outputs)
     try:
         yield
     finally:
-        _LAZY.on, _LAZY.on_demand = prev, prev_od
+        _LAZY.on, _LAZY.on_demand, _LAZY.outputs = prev, prev_od, prev_out
 
 
 _DEFER = threading.local()
@@ -332,6 +338,9 @@ def host_stats(reset: bool = False) -> Dict[str, int]:
     out = {k: int(getattr(st, k)) for k, _ in _lib.HostStats._fields_}
     if not hasattr(lib, "femo_mesh_head_info"):        # a build from before the chunked upload: its struct ends earlier
         del out["h2d_chunks"]
+    if not hasattr(lib, "femo_vec_get_host_promised_ex"):   # ... and one from before the pool's counters
+        for k in ("pool_fresh", "pool_fresh_us", "pool_free_waited", "pool_free_waited_us", "pool_free_deferred"):
+            del out[k]
     return out
 
 
@@ -473,8 +482,14 @@ class Vec:
             return out
         out = pinned_empty(n)
         if getattr(_LAZY, "on", False):
-            promised = getattr(_LAZY, "on_demand", False) and hasattr(self.lib, "femo_vec_get_host_promised")
-            check((self.lib.femo_vec_get_host_promised if promised else self.lib.femo_vec_get_host_async)(self.handle, _ptr(out), n))
+            if getattr(_LAZY, "outputs", False):
+                if hasattr(self.lib, "femo_vec_get_host_promised_ex"):
+                    check(self.lib.femo_vec_get_host_promised_ex(self.handle, _ptr(out), n, PROMISE_OUTPUT))
+                else:
+                    check(self.lib.femo_vec_get_host_async(self.handle, _ptr(out), n))
+            else:
+                promised = getattr(_LAZY, "on_demand", False) and hasattr(self.lib, "femo_vec_get_host_promised")
+                check((self.lib.femo_vec_get_host_promised if promised else self.lib.femo_vec_get_host_async)(self.handle, _ptr(out), n))
         else:
             check(self.lib.femo_vec_get_host(self.handle, _ptr(out), n))
         out.flags.writeable = False

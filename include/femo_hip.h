@@ -202,6 +202,12 @@ typedef struct femo_host_stats {
   int64_t d2h_device_sum, d2h_device_sum_bytes; /* accumulate formed on the device      */
   int64_t h2d_deferred, h2d_deferred_bytes; /* of the h2d_pinned ones: femo_vec_set_host_deferred, on the copy stream */
   int64_t h2d_chunks;                       /* copies those travelled as (FEMO_H2D_CHUNK_MB; one per upload when it is 0) */
+  /* the pool of pinned blocks: what a steady cycle must not do */
+  int64_t pool_fresh, pool_fresh_us;        /* femo_host_alloc found no recycled block: hipHostMalloc, and the time it took */
+  int64_t pool_free_deferred;               /* femo_host_free of a block with a DMA in flight: parked, recycled by a later pool
+                                             * call; femo_host_free itself never waits                                      */
+  int64_t pool_free_waited, pool_free_waited_us; /* releases that did wait for a DMA, and for how long: femo_host_unregister of
+                                             * a caller's range with a transfer in flight (it cannot be parked)            */
 } femo_host_stats;
 int femo_host_alloc(int64_t bytes, void** out);
 int femo_host_free(void* p);
@@ -227,6 +233,12 @@ int femo_host_sync(void);
  * never read the block under p -- a copy it was promised is dropped.  Any other `host`, a wrapped vector, less than 1 MiB, or
  * FEMO_D2H_ON_DEMAND=0 in the environment: femo_vec_get_host_async.                                                   */
 int femo_vec_get_host_promised(const femo_vec* v, double* host, int64_t n);
+/* The same with flags.  FEMO_PROMISE_OUTPUT: the result of an output operator (dJ/du, which goes back into the adjoint solve as
+ * its right-hand side, and the explicit dJ/df, which the streamed tail overwrites from the device).  Such a promise is governed
+ * by FEMO_D2H_PROMISE_OUTPUTS (default on; 0: femo_vec_get_host_async) and not by FEMO_D2H_ON_DEMAND.  femo_host_axpby(a, x, 0, y)
+ * from a promised x promises y the product a x instead of sending x.                                                      */
+#define FEMO_PROMISE_OUTPUT 1
+int femo_vec_get_host_promised_ex(const femo_vec* v, double* host, int64_t n, int flags);
 int femo_host_forget(const void* p);
 int femo_host_get_stats(femo_host_stats* out);
 int femo_host_reset_stats(void);

@@ -59,6 +59,15 @@ int femo_mesh_head_info(femo_mesh* mesh, int64_t* out, int count);
  * Entries beyond `count` are not written.                                                                   */
 int femo_mesh_tail_info(femo_mesh* mesh, int64_t* out, int count);
 
+/* ---- the ranges of the streamed head and tail (host only, no GPU touched; csrc/range_plan.h) -------------------------------
+ * The plan both streamed transfers cut their n entries by: bounds[2 k], bounds[2 k + 1] = begin and end of range k, written
+ * while 2 k + 1 < room; returns the number of ranges.  taper 0: pieces of `chunk` entries; 1: the chunked upload's plan (pieces
+ * shrink by `factor` down to `floor` at the end); 2: the streamed tail's (they grow by `factor` from `floor`, on to `cap`).
+ * The library calls it with FEMO_H2D_CHUNK_MB / FEMO_D2H_CHUNK_MB, FEMO_RANGE_FLOOR_MB, FEMO_RANGE_FACTOR and
+ * FEMO_D2H_MAX_CHUNK_MB in entries.                                                                            */
+int femo_range_plan_host(int64_t n, int64_t chunk, int taper, int64_t floor, int64_t factor, int64_t cap, int64_t* bounds,
+                         int64_t room);
+
 /* ---- Newton's flagged passes: what the launches that were handed the flag did (tests) -----------------------
  * Synchronises the context's stream, then
  * out[0] / out[1] = flagged launches of the axpy that left early / that ran (a device counter, bumped by workgroup 0);
