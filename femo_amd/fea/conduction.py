@@ -370,7 +370,6 @@ class ThermalCompliance(BackendForm):
         self.mesh = _check_scalar_space("ThermalCompliance", T)
         self.u = self.T = T
         self._load = _HeatLoad("ThermalCompliance", self.mesh, source, flux, ds)
-        self._grad = {}
 
     def functions(self):
         return (self.u,)
@@ -382,13 +381,8 @@ class ThermalCompliance(BackendForm):
         return self.load().dot(self.u.vec, self.mesh.n_vert)
 
     def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
-        if wrt is self.u:
-            return out.copy_from(self.load())
-        return out.fill(0.0)
+        out = self._gradient_buffer(wrt, out)
+        return out.copy_from(self.load()) if wrt is self.u else out.fill(0.0)
 
 
 def pdeRes_conduction(T, v, rho_e, source=None, flux=None, dss: Optional[Measure] = None, k0: float = 1.0, k_min: float = 0.0,

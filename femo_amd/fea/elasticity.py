@@ -123,6 +123,26 @@ def _ctx():
     return get_context()
 
 
+def _n_values(who: str, what: str, values, n: int, noun: str = "load cases", scalar: bool = True, error=ValueError) -> np.ndarray:
+    """``values`` as a float array of its own of length ``n``: one value per load case (column, mode), or with ``scalar`` one
+    number for all of them."""
+    a = np.array(values, dtype=np.float64).ravel()
+    if scalar and a.size == 1 and np.ndim(values) == 0:
+        a = np.full(n, float(a[0]))
+    if a.size != n:
+        raise error(f"{who}: {n} {noun} need as many {what}")
+    return a
+
+
+def _one_per_column(who: str, what: str, values, n_cols: int, noun: str = "columns") -> np.ndarray:
+    """`_n_values` as the device calls want it: exactly one value per column (or mode), a FemoError otherwise."""
+    return _n_values(who, what, values, n_cols, noun, scalar=False, error=_lib.FemoError)
+
+
+def _f64(a: np.ndarray):
+    return a.ctypes.data_as(_lib.c_f64p)
+
+
 # ------------------------------------------------------------------------------------------------ device handles ----
 class DeviceElasticity:
     """femo_elast: K(rho) as d x d blocks on the mesh's scalar pattern, its products, the traction load, dR/drho and PCG."""
@@ -254,11 +274,12 @@ class DeviceElasticity:
         return info
 
     # ---- several load cases in one vector: column l at l * n_dof (csrc/elast_solve.hip) ----
-    def _cols(self, n_cols: int, *vecs: Vec) -> int:
+    def _cols(self, n_cols: int, *vecs: Vec, what: str = "load cases") -> int:
+        """``n_cols`` as an int, once every vector given holds that many columns (``what``: what the error calls them)."""
         n_cols = int(n_cols)
         for v in vecs:
             if v is not None and v.n < n_cols * self.n_dof:
-                raise _lib.FemoError(f"{n_cols} load cases need vectors of {n_cols * self.n_dof} entries, got {v.n}")
+                raise _lib.FemoError(f"{n_cols} {what} need vectors of {n_cols * self.n_dof} entries, got {v.n}")
         return n_cols
 
     def apply_multi(self, n_cols: int, x: Vec, y: Vec, masked: bool = False, a: float = 1.0, b: float = 0.0,
@@ -369,9 +390,8 @@ class DeviceElasticity:
         lv, cv = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (lam, c))
         if lv.size != n_modes or cv.size != n_modes:
             raise _lib.FemoError(f"eig_drho: {n_modes} modes need as many eigenvalues and weights")
-        f64 = lambda a: a.ctypes.data_as(_lib.c_f64p)
         check(self.lib.femo_elast_eig_drho(self.handle, int(method), self._mass_law(mass_law), float(density), n_modes,
-                                           rho.handle, phi.handle, f64(lv), f64(cv), y.handle, int(bool(accumulate))))
+                                           rho.handle, phi.handle, _f64(lv), _f64(cv), y.handle, int(bool(accumulate))))
         return y
 
     def eigs(self, n_modes: int, rho: Vec, X: Vec, block: Optional[int] = None, density: float = 1.0,
@@ -418,20 +438,13 @@ class DeviceElasticity:
                                                    y.handle))
         return y
 
-    def _mode_weights(self, who: str, n_modes: int, *weights):
-        ws = [np.ascontiguousarray(w, dtype=np.float64).ravel() for w in weights]
-        if any(w.size != n_modes for w in ws):
-            raise _lib.FemoError(f"{who}: {n_modes} modes need as many weights")
-        return ws
-
     def buckle_du(self, method: int, n_modes: int, rho: Vec, phi: Vec, w, out: Vec) -> Vec:
         """out[(v, j)] = sum_{e around v} C(rho_e) |T_e| (Sigma_H g_v)_j with Sigma_H = lam0 tr(H) I + 2 mu0 H and
         H = sum_k w_k (grad phi_k)^T (grad phi_k), in one launch: with K-orthonormal modes and w_k = lambda_k^2 it is
         d lambda_k / du."""
         n_modes = self._cols(n_modes, phi)
-        (wv,) = self._mode_weights("buckle_du", n_modes, w)
-        check(self.lib.femo_elast_buckle_du(self.handle, int(method), n_modes, rho.handle, phi.handle,
-                                            wv.ctypes.data_as(_lib.c_f64p), out.handle))
+        wv = _one_per_column("buckle_du", "weights", w, n_modes, "modes")
+        check(self.lib.femo_elast_buckle_du(self.handle, int(method), n_modes, rho.handle, phi.handle, _f64(wv), out.handle))
         return out
 
     def buckle_drho(self, method: int, n_modes: int, rho: Vec, u: Vec, phi: Vec, w1, w2, y: Vec,
@@ -440,10 +453,9 @@ class DeviceElasticity:
         H_e(phi_k)] in one launch: with K-orthonormal modes, w1_k = lambda_k and w2_k = lambda_k^2 it is d lambda_k / d rho at
         fixed u."""
         n_modes = self._cols(n_modes, phi)
-        w1v, w2v = self._mode_weights("buckle_drho", n_modes, w1, w2)
-        f64 = lambda a: a.ctypes.data_as(_lib.c_f64p)
-        check(self.lib.femo_elast_buckle_drho(self.handle, int(method), n_modes, rho.handle, u.handle, phi.handle, f64(w1v),
-                                              f64(w2v), y.handle, int(bool(accumulate))))
+        w1v, w2v = (_one_per_column("buckle_drho", "weights", w, n_modes, "modes") for w in (w1, w2))
+        check(self.lib.femo_elast_buckle_drho(self.handle, int(method), n_modes, rho.handle, u.handle, phi.handle, _f64(w1v),
+                                              _f64(w2v), y.handle, int(bool(accumulate))))
         return y
 
     def buckle(self, n_modes: int, rho: Vec, u: Vec, X: Vec, block: Optional[int] = None, method: int = _lib.ELAST_SIMP,
@@ -460,12 +472,6 @@ class DeviceElasticity:
                                  n_modes, block, X, rtol, max_outer, pcg_rtol, pcg_max_it, pc)
 
     # ---- harmonic response: (K - sigma_l M(rho)) u_l = F_l, sigma_l = omega_l^2 (csrc/elast_harm.hip) ----
-    def _per_column(self, who: str, what: str, n_cols: int, values) -> np.ndarray:
-        a = np.ascontiguousarray(values, dtype=np.float64).ravel()
-        if a.size != n_cols:
-            raise _lib.FemoError(f"{who}: {n_cols} columns need as many {what}")
-        return a
-
     def mass_assemble(self, rho: Vec, density: float = 1.0, mass_law: str = "linear") -> None:
         """M(rho) = density sum_e m(rho_e) M0_e as a scalar matrix on the pattern of K (one double per entry, one per row);
         `dyn_apply_multi` and `dyn_solve_multi` read it."""
@@ -476,9 +482,9 @@ class DeviceElasticity:
         """y_l = a (K - shifts[l] M) x_l + b f_l with the assembled K and M in one pass over the pattern (or with identity rows
         and columns on the fixed dofs when ``masked``); shifts[l] = 0 gives the bits of `apply_multi`."""
         n_cols = self._cols(n_cols, x, y, f)
-        sv = self._per_column("dyn_apply_multi", "shifts", n_cols, shifts)
-        check(self.lib.femo_elast_dyn_apply_multi(self.handle, int(bool(masked)), n_cols, sv.ctypes.data_as(_lib.c_f64p),
-                                                  float(a), x.handle, float(b), None if f is None else f.handle, y.handle))
+        sv = _one_per_column("dyn_apply_multi", "shifts", shifts, n_cols)
+        check(self.lib.femo_elast_dyn_apply_multi(self.handle, int(bool(masked)), n_cols, _f64(sv), float(a), x.handle,
+                                                  float(b), None if f is None else f.handle, y.handle))
         return y
 
     def dyn_solve_multi(self, n_cols: int, shifts, b: Vec, x: Vec, rtol: float = 1e-12, atol: float = 0.0,
@@ -490,10 +496,9 @@ class DeviceElasticity:
         residual.  A finished column is frozen while the others go on."""
         opts = self._solver_opts(rtol, atol, max_it, check_every, zero_guess, pc)
         n_cols = self._cols(n_cols, b, x)
-        sv = self._per_column("dyn_solve_multi", "shifts", n_cols, shifts)
+        sv = _one_per_column("dyn_solve_multi", "shifts", shifts, n_cols)
         info = (_lib.SolveInfo * _lib.ELAST_MAX_COLS)()
-        check(self.lib.femo_elast_dyn_solve_multi(self.handle, n_cols, sv.ctypes.data_as(_lib.c_f64p), b.handle, x.handle,
-                                                  C.byref(opts), info))
+        check(self.lib.femo_elast_dyn_solve_multi(self.handle, n_cols, _f64(sv), b.handle, x.handle, C.byref(opts), info))
         return [info[l] for l in range(n_cols)]
 
     # ---- damped harmonic response: Z_l = (K - sigma_l M) + i (ck_l K + cm_l M); complex column l = real columns 2 l, 2 l + 1
@@ -503,8 +508,8 @@ class DeviceElasticity:
         if not 1 <= n_cols <= _lib.ELAST_MAX_COLS // 2:
             raise _lib.FemoError(f"{who}: {n_cols} complex columns (1 to {_lib.ELAST_MAX_COLS // 2})")
         self._cols(2 * n_cols, *vecs)
-        arrays = [self._per_column(who, what, n_cols, v) for what, v in (("shifts", shifts), ("ck", ck), ("cm", cm))]
-        return n_cols, [a.ctypes.data_as(_lib.c_f64p) for a in arrays], arrays
+        arrays = [_one_per_column(who, what, v, n_cols) for what, v in (("shifts", shifts), ("ck", ck), ("cm", cm))]
+        return n_cols, [_f64(a) for a in arrays], arrays
 
     def cdyn_apply_multi(self, n_cols: int, shifts, ck, cm, x: Vec, y: Vec, masked: bool = False, conj: bool = False,
                          a: float = 1.0, b: float = 0.0, f: Optional[Vec] = None) -> Vec:
@@ -536,10 +541,10 @@ class DeviceElasticity:
         the forward product of the cell vector x with u_l.  With scales = -shifts and ``accumulate`` on top of `drho_multi` it
         is dR/drho of the harmonic residual."""
         n_cols = self._cols(n_cols, u, x if transpose else y)
-        sv = self._per_column("mass_drho_multi", "scales", n_cols, scales)
+        sv = _one_per_column("mass_drho_multi", "scales", scales, n_cols)
         check(self.lib.femo_elast_mass_drho_multi(self.handle, self._mass_law(mass_law), float(density), int(bool(transpose)),
-                                                  n_cols, sv.ctypes.data_as(_lib.c_f64p), rho.handle, u.handle, x.handle,
-                                                  y.handle, int(bool(accumulate))))
+                                                  n_cols, _f64(sv), rho.handle, u.handle, x.handle, y.handle,
+                                                  int(bool(accumulate))))
         return y
 
     # ---- transient response: Newmark march on a history of n_steps columns, column t = u_{t+1} (csrc/elast_transient.hip) ----
@@ -547,13 +552,6 @@ class DeviceElasticity:
     def _newmark(params) -> _lib.NewmarkParams:
         dt, beta, gamma, c_m, c_k = (float(v) for v in params)
         return _lib.NewmarkParams(dt=dt, beta=beta, gamma=gamma, c_m=c_m, c_k=c_k)
-
-    def _steps(self, n_steps: int, *vecs: Vec) -> int:
-        n_steps = int(n_steps)
-        for v in vecs:
-            if v is not None and v.n < n_steps * self.n_dof:
-                raise _lib.FemoError(f"{n_steps} steps need vectors of {n_steps * self.n_dof} entries, got {v.n}")
-        return n_steps
 
     def newmark_rhs(self, u: Vec, y: Vec, m0: float, k0: float, mm: float, km: float, rhs: Optional[Vec] = None,
                     cr: float = 1.0, crf: float = 1.0, masked: bool = False) -> Vec:
@@ -569,7 +567,7 @@ class DeviceElasticity:
         """All ``n_steps`` steps of L U = B (L^T U = B with ``reverse``) in one call: B is the history ``rhs`` or comes from the
         load pattern ``F`` and the n_steps + 1 samples ``signal``.  ``params`` = (dt, beta, gamma, c_m, c_k).  Returns (one
         `SolveInfo` per step, the column the march stopped at or -1)."""
-        n_steps = self._steps(n_steps, U, rhs)
+        n_steps = self._cols(n_steps, U, rhs, what="steps")
         opts = self._solver_opts(rtol, atol, max_it, check_every, False, pc)
         g = None
         if signal is not None:
@@ -588,8 +586,8 @@ class DeviceElasticity:
     def newmark_apply(self, params, n_steps: int, X: Vec, Y: Vec, transpose: bool = False, masked: bool = False) -> Vec:
         """Y = L X, or L^T X, for a history; FEMO_ELAST_MAX_COLS time steps per launch."""
         par = self._newmark(params)
-        check(self.lib.femo_elast_newmark_apply(self.handle, C.byref(par), self._steps(n_steps, X, Y), int(bool(transpose)),
-                                                int(bool(masked)), X.handle, Y.handle))
+        check(self.lib.femo_elast_newmark_apply(self.handle, C.byref(par), self._cols(n_steps, X, Y, what="steps"),
+                                                int(bool(transpose)), int(bool(masked)), X.handle, Y.handle))
         return Y
 
     def newmark_drho(self, params, method: int, transpose: bool, n_steps: int, rho: Vec, U: Vec, x: Vec, y: Vec,
@@ -598,7 +596,7 @@ class DeviceElasticity:
         """dR/drho of the march's residual for the columns first ... first + count - 1 (all by default).  transpose:
         y[n_cell] (+)= sum_t (dR_t/drho)^T x_t; otherwise column t of y (+)= dR_t/drho x.  Windows of FEMO_ELAST_MAX_COLS columns
         in ascending order."""
-        n_steps = self._steps(n_steps, U, x if transpose else y)
+        n_steps = self._cols(n_steps, U, x if transpose else y, what="steps")
         par = self._newmark(params)
         check(self.lib.femo_elast_newmark_drho(self.handle, C.byref(par), int(method), self._mass_law(mass_law), float(density),
                                                int(bool(transpose)), n_steps, int(first),
@@ -608,14 +606,14 @@ class DeviceElasticity:
 
     def newmark_dots(self, n_steps: int, f: Vec, U: Vec) -> np.ndarray:
         """(n_steps,): f . U_t for every column, through the Gram kernel in windows."""
-        out = np.zeros(self._steps(n_steps, U))
-        check(self.lib.femo_elast_newmark_dots(self.handle, int(n_steps), f.handle, U.handle, out.ctypes.data_as(_lib.c_f64p)))
+        out = np.zeros(self._cols(n_steps, U, what="steps"))
+        check(self.lib.femo_elast_newmark_dots(self.handle, int(n_steps), f.handle, U.handle, _f64(out)))
         return out
 
     def newmark_outer(self, n_steps: int, a, f: Vec, Y: Vec) -> Vec:
         """Y_t = a[t] f for every column."""
-        av = self._per_column("newmark_outer", "coefficients", self._steps(n_steps, Y), a)
-        check(self.lib.femo_elast_newmark_outer(self.handle, int(n_steps), av.ctypes.data_as(_lib.c_f64p), f.handle, Y.handle))
+        av = _one_per_column("newmark_outer", "coefficients", a, self._cols(n_steps, Y, what="steps"))
+        check(self.lib.femo_elast_newmark_outer(self.handle, int(n_steps), _f64(av), f.handle, Y.handle))
         return Y
 
     def pnorm_stress_multi(self, n_cols: int, rho: Vec, u: Vec, m, p: float, q: float, alpha: float, weights=None,
@@ -625,19 +623,24 @@ class DeviceElasticity:
         values is returned when ``value``), column l of ``grad_u`` (+)= w_l dJ_l/du_l, ``grad_rho`` (+)= sum_l w_l dJ_l/drho.
         ``m``: a scalar or one scale per column; ``weights``: one per column, 1 without."""
         n_cols = self._cols(n_cols, u, grad_u)
+        mv, wv, vals = self._scales_and_weights("pnorm_stress_multi", n_cols, m, weights)
+        check(self.lib.femo_elast_pnorm_stress_multi(self.handle, n_cols, rho.handle, u.handle, _f64(mv),
+                                                     None if wv is None else _f64(wv), float(p), float(q), float(alpha),
+                                                     _f64(vals) if value else None, None if grad_u is None else grad_u.handle,
+                                                     None if grad_rho is None else grad_rho.handle, int(bool(accumulate))))
+        return vals[:n_cols] if value else None
+
+    @staticmethod
+    def _scales_and_weights(who: str, n_cols: int, m, weights):
+        """The scales ``m`` (a scalar or one per column) and the weights (one per column, or None) of an aggregate as arrays,
+        and the array its ``n_cols`` values are written to."""
         mv = np.ascontiguousarray(m, dtype=np.float64).ravel()
         if np.ndim(m) == 0:
             mv = np.full(max(n_cols, 0), float(m))
         wv = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).ravel()
         if mv.size != n_cols or (wv is not None and wv.size != n_cols):
-            raise _lib.FemoError(f"pnorm_stress_multi: {n_cols} columns need as many scales and weights")
-        vals = np.zeros(max(n_cols, 1))
-        f64 = lambda a: a.ctypes.data_as(_lib.c_f64p)
-        check(self.lib.femo_elast_pnorm_stress_multi(self.handle, n_cols, rho.handle, u.handle, f64(mv),
-                                                     None if wv is None else f64(wv), float(p), float(q), float(alpha),
-                                                     f64(vals) if value else None, None if grad_u is None else grad_u.handle,
-                                                     None if grad_rho is None else grad_rho.handle, int(bool(accumulate))))
-        return vals[:n_cols] if value else None
+            raise _lib.FemoError(f"{who}: {n_cols} columns need as many scales and weights")
+        return mv, wv, np.zeros(max(n_cols, 1))
 
     def pnorm_disp_multi(self, n_cols: int, u: Vec, a: Vec, m, p: float, alpha: float = 0.0, weights=None, value: bool = True,
                          grad_u: Optional[Vec] = None, accumulate: bool = False):
@@ -645,17 +648,10 @@ class DeviceElasticity:
         of the ``n_cols`` unweighted values is returned when ``value``), column l of ``grad_u`` (+)= w_l dJ_l/du_l.
         ``alpha`` <= 0: sum_v a_v.  ``m``: a scalar or one scale per column; ``weights``: one per column, 1 without."""
         n_cols = self._cols(n_cols, u, grad_u)
-        mv = np.ascontiguousarray(m, dtype=np.float64).ravel()
-        if np.ndim(m) == 0:
-            mv = np.full(max(n_cols, 0), float(m))
-        wv = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).ravel()
-        if mv.size != n_cols or (wv is not None and wv.size != n_cols):
-            raise _lib.FemoError(f"pnorm_disp_multi: {n_cols} columns need as many scales and weights")
-        vals = np.zeros(max(n_cols, 1))
-        f64 = lambda a: a.ctypes.data_as(_lib.c_f64p)
-        check(self.lib.femo_elast_pnorm_disp_multi(self.handle, n_cols, u.handle, a.handle, f64(mv),
-                                                   None if wv is None else f64(wv), float(p), float(alpha),
-                                                   f64(vals) if value else None, None if grad_u is None else grad_u.handle,
+        mv, wv, vals = self._scales_and_weights("pnorm_disp_multi", n_cols, m, weights)
+        check(self.lib.femo_elast_pnorm_disp_multi(self.handle, n_cols, u.handle, a.handle, _f64(mv),
+                                                   None if wv is None else _f64(wv), float(p), float(alpha),
+                                                   _f64(vals) if value else None, None if grad_u is None else grad_u.handle,
                                                    int(bool(accumulate))))
         return vals[:n_cols] if value else None
 
@@ -667,7 +663,7 @@ class DeviceElasticity:
         if sv is not None and sv.size != n_cols:
             raise _lib.FemoError(f"von_mises_multi: {n_cols} columns need as many scales")
         check(self.lib.femo_elast_von_mises_multi(self.handle, n_cols, None if rho is None else rho.handle, u.handle,
-                                                  None if sv is None else sv.ctypes.data_as(_lib.c_f64p), float(q),
+                                                  None if sv is None else _f64(sv), float(q),
                                                   -1 if column is None else int(column), out.handle))
         return out
 
@@ -1230,10 +1226,18 @@ def _fixed_data(n_dof: int, bcs):
     return mask, vals
 
 
+def _mask_host(S, mask: Optional[np.ndarray], identity: bool = True):
+    """The host copy of a masked operator: ``S`` with zero rows and columns on the fixed dofs of ``mask`` and, with
+    ``identity``, ones on their diagonal; ``S`` itself without a mask."""
+    if mask is None:
+        return S
+    import scipy.sparse as sp
+    free = sp.diags((mask == 0).astype(np.float64))
+    S = free @ S @ free
+    return (S + sp.diags(mask.astype(np.float64)) if identity else S).tocsr()
+
+
 # ------------------------------------------------------------------------------------------------------ operators ----
-# One load case is the L = 1 case: every form below is written once for the ``n_cases`` columns of its state (1 for a plain
-# VectorFunctionSpace state) and calls the batched entry points.  The ``MultiLoad...`` names adapt the constructor
-# arguments and how the solves are recorded and reported.
 class ElasticityMatrix:
     """dR/du = K(rho) on every column; with ``masked`` the A of state_model.py:149 (identity rows / columns on the fixed
     dofs).  One `mult` is one batched product, one `backend_solve` one batched PCG over all columns."""
@@ -1265,18 +1269,15 @@ class ElasticityMatrix:
     new_col_vec = new_row_vec
 
     def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
-        o = options or {}
-        F = self.form
-        infos = F.stiffness().solve_multi(F.n_cases, b, x, rtol=o.get("elast_rtol", F.rtol),
-                                          max_it=o.get("elast_max_it", 1_000_000), pc=F.preconditioner)
-        self.info = F._record(infos, "adjoint")
+        self.info = self.form._matrix_solve(b, x, "adjoint", options)
+
+    def _host_mask(self) -> Optional[np.ndarray]:
+        """The fixed set a host copy of this matrix carries: the form's when ``masked``."""
+        return self.form._mask if self.masked else None
 
     def to_scipy(self):
         import scipy.sparse as sp
-        K = self.form.stiffness().export_csr()
-        if self.masked and self.form._mask is not None:
-            free = sp.diags((self.form._mask == 0).astype(np.float64))
-            K = (free @ K @ free + sp.diags(self.form._mask.astype(np.float64))).tocsr()
+        K = _mask_host(self.form.stiffness().export_csr(), self._host_mask())
         return K if self.form.n_cases == 1 else sp.block_diag([K] * self.form.n_cases, format="csr")
 
 
@@ -1284,73 +1285,77 @@ class MultiLoadElasticityMatrix(ElasticityMatrix):
     """`ElasticityMatrix` of a `MultiLoadElasticityResidual`."""
 
 
-class _ElasticityDrho:
+class _UnsymmetricMatrix(ElasticityMatrix):
+    """A dR/du that is not symmetric: the transposed product and the transposed solve are calls of their own.  A subclass
+    gives ``_apply(flag, x, y)`` and ``_solve(flag, kind, b, x, options)``, ``flag`` False for the matrix (`mult`, and
+    `backend_solve`: the forward mode) and True for its transpose (`multTranspose`, and `backend_solve_transpose`: the
+    adjoint); `_solve` leaves what the form's `_record` returns in ``info``."""
+    symmetric = False
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        return self._apply(False, x, y)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        return self._apply(True, x, y)
+
+    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        self._solve(False, "forward", b, x, options)
+
+    def backend_solve_transpose(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
+        self._solve(True, "adjoint", b, x, options)
+
+
+class _MatrixFree:
+    """A partial of a residual that is never formed, (n_cases n_dof) x the mesh's ``cols`` ("n_cell" or "n_vert"): `mult` and
+    `multTranspose` are the subclass's ``_product(transpose, x, y)``."""
+
+    def __init__(self, form: "ElasticityResidual"):
+        self.form, self.mesh = form, form.mesh
+        self._row = self._col = None
+
+    def getSizes(self):
+        return (self.form.n_cases * self.form.n_dof, getattr(self.mesh, self.cols))
+
+    def mult(self, x: Vec, y: Vec) -> Vec:
+        return self._product(False, x, y)
+
+    def multTranspose(self, x: Vec, y: Vec) -> Vec:
+        return self._product(True, x, y)
+
+    def new_row_vec(self) -> Vec:
+        if self._row is None:
+            self._row = Vec(_ctx(), self.getSizes()[0])
+        return self._row
+
+    def new_col_vec(self) -> Vec:
+        if self._col is None:
+            self._col = Vec(_ctx(), self.getSizes()[1])
+        return self._col
+
+
+class _ElasticityDrho(_MatrixFree):
     """dR/drho ((n_cases n_dof) x n_cell), matrix free: block l of column e = C'(rho_e) K0_e u_{l,e}, minus the body-load
     operator G_B of a form with body forces and minus s_l H(C'(rho) . ; theta) of a form with a thermal load (F depends on
     the density there), added onto the stiffness term."""
+    cols = "n_cell"
 
-    def __init__(self, form: "ElasticityResidual"):
-        self.form, self.mesh = form, form.mesh
-        self._row = self._col = None
-
-    def getSizes(self):
-        return (self.form.n_cases * self.form.n_dof, self.mesh.n_cell)
-
-    def mult(self, x: Vec, y: Vec) -> Vec:
+    def _product(self, transpose: bool, x: Vec, y: Vec) -> Vec:
         F = self.form
-        F.device().drho_multi(F.method_id, False, F.n_cases, F.rho.vec, F.u.vec, x, y)
+        F.device().drho_multi(F.method_id, transpose, F.n_cases, F.rho.vec, F.u.vec, x, y)
         if F.body is not None:
-            F.device().body_apply(F.n_cases, F.body, x, y, a=-1.0, accumulate=True)
+            F.device().body_apply(F.n_cases, F.body, x, y, transpose=transpose, a=-1.0, accumulate=True)
         if F.thermal is not None:
-            F.thermal.drho(False, x, y, a=-1.0)
+            F.thermal.drho(transpose, x, y, a=-1.0)
         return y
 
-    def multTranspose(self, x: Vec, y: Vec) -> Vec:
-        F = self.form
-        F.device().drho_multi(F.method_id, True, F.n_cases, F.rho.vec, F.u.vec, x, y)
-        if F.body is not None:
-            F.device().body_apply(F.n_cases, F.body, x, y, transpose=True, a=-1.0, accumulate=True)
-        if F.thermal is not None:
-            F.thermal.drho(True, x, y, a=-1.0)
-        return y
 
-    def new_row_vec(self) -> Vec:
-        if self._row is None:
-            self._row = Vec(_ctx(), self.getSizes()[0])
-        return self._row
-
-    def new_col_vec(self) -> Vec:
-        if self._col is None:
-            self._col = Vec(_ctx(), self.mesh.n_cell)
-        return self._col
-
-
-class _ElasticityDtemp:
+class _ElasticityDtemp(_MatrixFree):
     """dR/dT ((n_cases n_dof) x n_vert) of a form whose thermal load reads a temperature Function, matrix free: block l =
     -s_l H(C(rho); .), the thermal load as a linear map of the nodal temperatures (csrc/elast_thermal.hip)."""
+    cols = "n_vert"
 
-    def __init__(self, form: "ElasticityResidual"):
-        self.form, self.mesh = form, form.mesh
-        self._row = self._col = None
-
-    def getSizes(self):
-        return (self.form.n_cases * self.form.n_dof, self.mesh.n_vert)
-
-    def mult(self, x: Vec, y: Vec) -> Vec:
-        return self.form.thermal.dtemp(False, x, y, a=-1.0)
-
-    def multTranspose(self, x: Vec, y: Vec) -> Vec:
-        return self.form.thermal.dtemp(True, x, y, a=-1.0)
-
-    def new_row_vec(self) -> Vec:
-        if self._row is None:
-            self._row = Vec(_ctx(), self.getSizes()[0])
-        return self._row
-
-    def new_col_vec(self) -> Vec:
-        if self._col is None:
-            self._col = Vec(_ctx(), self.mesh.n_vert)
-        return self._col
+    def _product(self, transpose: bool, x: Vec, y: Vec) -> Vec:
+        return self.form.thermal.dtemp(transpose, x, y, a=-1.0)
 
 
 # ---------------------------------------------------------------------------------------------------------- forms ----
@@ -1444,6 +1449,7 @@ class ElasticityResidual(BackendForm):
     is_symmetric = True
     constant_partials = False
     matrix_class = ElasticityMatrix
+    max_it = 1_000_000            # the bound on the iterations of a solve (assign to an instance to change it)
 
     def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, E: float = 1.0,
                  nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None, springs=None,
@@ -1527,7 +1533,7 @@ class ElasticityResidual(BackendForm):
 
     def _record(self, infos, kind: str):
         """Keeps the record of a solve (``infos``: one per column) and raises when it did not converge; returns what
-        the matrix shows as its ``info``."""
+        the matrix shows as its ``info``.  One column, one flat record; several columns: `MultiLoadElasticityResidual`."""
         from .utils_hip import LAST_KSP_INFO
         info = infos[0]
         self.last_info[kind] = dict(iterations=info.iterations, converged=info.converged, solve_ms=info.solve_ms,
@@ -1545,12 +1551,18 @@ class ElasticityResidual(BackendForm):
     def new_matrix(self) -> ElasticityMatrix:
         return self.matrix_class(self)
 
-    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
-        """Column l: K u_l - F_l; one launch for all columns (femo_elast_apply_multi)."""
+    def _residual_buffer(self, out: Optional[Vec], n: Optional[int] = None) -> Vec:
+        """``out``, or without one the form's own residual vector, allocated on first use (``n`` entries, all columns by
+        default)."""
         if out is None:
             if self._res is None:
-                self._res = Vec(_ctx(), self.n_cases * self.n_dof)
+                self._res = Vec(_ctx(), self.n_cases * self.n_dof if n is None else n)
             out = self._res
+        return out
+
+    def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
+        """Column l: K u_l - F_l; one launch for all columns (femo_elast_apply_multi)."""
+        out = self._residual_buffer(out)
         return self.stiffness().apply_multi(self.n_cases, self.u.vec, out, a=1.0, b=-1.0, f=self.load())
 
     def partial_matrix(self, wrt: Function, out=None):
@@ -1601,11 +1613,27 @@ class ElasticityResidual(BackendForm):
             self._rhs_cache = (key, bv)
         return bv
 
+    def _operator(self) -> DeviceElasticity:
+        """The handle with everything this form's products and solves read: K(rho) here, M(rho) as well under `_MassCarrying`."""
+        return self.stiffness()
+
+    def _solve_columns(self, dev: DeviceElasticity, b: Vec, x: Vec, transpose: bool, **opts) -> list:
+        """This form's batched solve for all columns on the handle of `_operator` (``transpose``: with the transposed
+        matrix, which is the matrix itself here): K(rho) x_l = b_l, one PCG."""
+        return dev.solve_multi(self.n_cases, b, x, pc=self.preconditioner, **opts)
+
+    def _matrix_solve(self, b: Vec, x: Vec, kind: str, options: Optional[dict], transpose: bool = False):
+        """`backend_solve` of this form's matrix: the solve under the caller's options, recorded as ``kind``."""
+        o = options or {}
+        infos = self._solve_columns(self._operator(), b, x, transpose, rtol=o.get("elast_rtol", self.rtol),
+                                    max_it=o.get("elast_max_it", self.max_it))
+        return self._record(infos, kind)
+
     def solve_state(self, func: Function, bcs, report: bool = False) -> None:
-        """K(rho) u_l = F_l for every column with the strongly imposed dofs: ONE batched PCG solve (the form is linear)."""
+        """The state of every column with the strongly imposed dofs: ONE batched solve (the form is linear)."""
         self._set_bcs(bcs)
-        dev = self.stiffness()
-        infos = dev.solve_multi(self.n_cases, self._rhs(dev), func.vec, rtol=self.rtol, pc=self.preconditioner)
+        dev = self._operator()
+        infos = self._solve_columns(dev, self._rhs(dev), func.vec, False, rtol=self.rtol, max_it=self.max_it)
         func.version += 1
         self._record(infos, "state")
         if report:
@@ -1637,25 +1665,40 @@ class MultiLoadElasticityResidual(ElasticityResidual):
         self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner, body, springs, thermal)
         self.solve_counts = {"state": 0, "adjoint": 0}
 
+    # How the column-wise solves of this form and of its subclasses are recorded and reported; a subclass changes the data.
+    _title, _solver = "elasticity", "PCG"                       # "<title> <solver> did not converge", "<title> solve, ..."
+    _kind = "elasticity_multiload_"                             # + the kind of solve: ``kind`` of the LAST_KSP_INFO record
+    _residual = "sqrt(r.M^-1 r)"                                # what the solver's residual_norm measures
+    _column, _plural = "load case", "load cases"                # what a column is called in the error and in the report
+    _count = "n_cases"                                          # the attribute with the number of columns solved for
+    _per_column = {}                                            # attribute -> its name in the error: arrays with one value per
+    #                                                             column, copied into the record; the error gives the value of
+    #                                                             the column that failed
+
     def _record(self, infos, kind: str):
+        """`ElasticityResidual._record` for a column-wise solve: one entry per column under ``columns``, the solve counted in
+        ``solve_counts[kind]``; raises on the first column that did not converge and returns ``infos``."""
         from .utils_hip import LAST_KSP_INFO
+        n = getattr(self, self._count)
         cols = [dict(iterations=i.iterations, converged=i.converged, residual_norm=i.residual_norm, rhs_norm=i.rhs_norm)
                 for i in infos]
         self.solve_counts[kind] = self.solve_counts.get(kind, 0) + 1
-        self.last_info[kind] = dict(columns=cols, n_cases=self.n_cases, iterations=[c["iterations"] for c in cols],
+        self.last_info[kind] = dict(columns=cols, n_cases=n, iterations=[c["iterations"] for c in cols],
                                     converged=[c["converged"] for c in cols], solve_ms=infos[0].solve_ms,
-                                    preconditioner=self.preconditioner)
-        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_multiload_" + kind))
+                                    preconditioner=self.preconditioner,
+                                    **{k: getattr(self, k).copy() for k in self._per_column})
+        LAST_KSP_INFO.append(dict(self.last_info[kind], kind=self._kind + kind))
         for l, c in enumerate(cols):
             if c["converged"] != 1:
-                raise RuntimeError(f"elasticity PCG did not converge ({kind}, load case {l} of {self.n_cases}): "
-                                   f"{c['iterations']} iterations, sqrt(r.M^-1 r) = {c['residual_norm']:.3e} of "
+                its = "".join(f", {name} = {getattr(self, k)[l]:.6g}" for k, name in self._per_column.items())
+                raise RuntimeError(f"{self._title} {self._solver} did not converge ({kind}, {self._column} {l} of {n}{its}): "
+                                   f"{c['iterations']} iterations, {self._residual} = {c['residual_norm']:.3e} of "
                                    f"{c['rhs_norm']:.3e}")
         return infos
 
     def _report(self, infos) -> str:
-        return (f"elasticity solve, {self.n_cases} load cases: {[i.iterations for i in infos]} PCG iterations, "
-                f"{infos[0].solve_ms:.1f} ms")
+        return (f"{self._title} solve, {getattr(self, self._count)} {self._plural}: {[i.iterations for i in infos]} "
+                f"{self._solver} iterations, {infos[0].solve_ms:.1f} ms")
 
 
 class Compliance(BackendForm):
@@ -1677,7 +1720,6 @@ class Compliance(BackendForm):
         self.tractions, self.measures, self.weights = [self.t], [self.ds], None
         self._set_body("Compliance", _body_forces("Compliance", None if body_force is None else [body_force], 1, self.mesh), rho,
                        thermal, E, nu, method)
-        self._grad = {}
 
     def _set_body(self, name: str, body: Optional[np.ndarray], rho: Optional[Function], thermal=None, E: float = 1.0,
                   nu: float = 0.3, method: str = "SIMP") -> None:
@@ -1715,10 +1757,7 @@ class Compliance(BackendForm):
         return self.load().dot(self.u.vec, self.u.function_space.dim)
 
     def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:                                            # one buffer per argument: both partials may be pending
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        out = self._gradient_buffer(wrt, out)
         if wrt is self.u:
             return out.copy_from(self.load())
         if self.rho is not None and wrt is self.rho:
@@ -1745,14 +1784,25 @@ class MultiLoadCompliance(Compliance):
         if self.weights.size != V.n_cases:
             raise ValueError(f"MultiLoadCompliance: {V.n_cases} load cases need as many weights")
         self._set_body("MultiLoadCompliance", body, rho, thermal, E, nu, method)
-        self._grad = {}
 
 
-class ElasticityDisplacement(BackendForm):
+class _StateOutput(BackendForm):
+    """A scalar output of the state ``u`` alone: its partial in ``u`` is the subclass's ``_state_gradient(out)``, that in any
+    other Function zero."""
+    rank = 0
+
+    def functions(self):
+        return (self.u,)
+
+    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
+        out = self._gradient_buffer(wrt, out)
+        return self._state_gradient(out) if wrt is self.u else out.fill(0.0)
+
+
+class ElasticityDisplacement(_StateOutput):
     """J = sum_l w_l l_l . u_l for host vectors l_l in the numbering of the base space (`port_displacement`,
     `mean_displacement`): the displacement of a port, the mean displacement of a boundary.  dJ/du = w l: `Compliance` with
     another vector.  ``ell``: one vector (used for every column) or one per column."""
-    rank = 0
 
     def __init__(self, u: Function, ell, weights=None):
         V = u.function_space
@@ -1765,13 +1815,9 @@ class ElasticityDisplacement(BackendForm):
             raise ValueError(f"ElasticityDisplacement: {L} columns need vectors of {base.dim} entries")
         if not np.all(np.isfinite(ell)):
             raise ValueError("ElasticityDisplacement: the vectors must be finite")
-        self.weights = np.ones(L) if weights is None else _per_case("ElasticityDisplacement", "weights", weights, L)
+        self.weights = np.ones(L) if weights is None else _n_values("ElasticityDisplacement", "weights", weights, L)
         self.u, self.mesh, self.n_cases, self.ell = u, V.mesh, L, ell
         self._vec = None
-        self._grad = {}
-
-    def functions(self):
-        return (self.u,)
 
     def load(self) -> Vec:
         """Column l = w_l l_l on the device (uploaded once)."""
@@ -1786,22 +1832,17 @@ class ElasticityDisplacement(BackendForm):
     def assemble_scalar(self) -> float:
         return self.load().dot(self.u.vec, self.u.function_space.dim)
 
-    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
-        return out.copy_from(self.load()) if wrt is self.u else out.fill(0.0)
+    def _state_gradient(self, out: Vec) -> Vec:
+        return out.copy_from(self.load())
 
 
-class ElasticityPnormDisplacement(BackendForm):
+class ElasticityPnormDisplacement(_StateOutput):
     """J = sum_l w_l J_l, J_l = (1/alpha) sum_v a_v (m |u_{l,v}|)^p with alpha = sum_v a_v: the aggregated nodal displacement
     of a region, the smooth form of "no vertex of this region moves more than delta" (`max_estimate` <= delta).  ``region``:
     a vertex index array (a_v = 1), a ``ds(tag)`` (a_v = the lumped facet measure) or None (all vertices with their lumped
     cell volume).  On a plain state or a LoadCaseSpace state; value and dJ/du are one pass over the vertices for all columns
     (`DeviceElasticity.pnorm_disp_multi`, csrc/elast_disp.hip).  dJ/du is non-zero on clamped dofs of the region: the exact
     reduced gradient needs ``fea.consistent_bc_partials = True``."""
-    rank = 0
 
     def __init__(self, u: Function, region=None, m=1.0, p: float = 8.0, weights=None, E: float = 1.0, nu: float = 0.3):
         V = u.function_space
@@ -1820,8 +1861,8 @@ class ElasticityPnormDisplacement(BackendForm):
             a[idx] = 1.0
         if not a.sum() > 0.0:
             raise ValueError("ElasticityPnormDisplacement: the region is empty")
-        self.m = _per_case("ElasticityPnormDisplacement", "scales m", m, L)
-        self.weights = np.ones(L) if weights is None else _per_case("ElasticityPnormDisplacement", "weights", weights, L)
+        self.m = _n_values("ElasticityPnormDisplacement", "scales m", m, L)
+        self.weights = np.ones(L) if weights is None else _n_values("ElasticityPnormDisplacement", "weights", weights, L)
         if not (np.all(self.m > 0.0) and np.all(np.isfinite(self.m)) and p >= 1.0 and np.isfinite(p)):
             raise ValueError("the displacement aggregate needs m > 0 and a finite p >= 1")
         if not np.all(self.weights >= 0.0):
@@ -1830,11 +1871,7 @@ class ElasticityPnormDisplacement(BackendForm):
         self.alpha = float(a.sum())
         self.E, self.nu = float(E), float(nu)
         self._a_vec = None
-        self._grad = {}
         self._values = None
-
-    def functions(self):
-        return (self.u,)
 
     def device(self) -> DeviceElasticity:
         return elasticity_handle(self.mesh, self.E, self.nu)
@@ -1858,15 +1895,8 @@ class ElasticityPnormDisplacement(BackendForm):
         self._values = self._call()
         return float(self.weights @ self._values)
 
-    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
-        if wrt is self.u:
-            self._call(value=False, grad_u=out)
-        else:
-            out.fill(0.0)
+    def _state_gradient(self, out: Vec) -> Vec:
+        self._call(value=False, grad_u=out)
         return out
 
 
@@ -1899,16 +1929,6 @@ def _check_multi_stress_spaces(name: str, u: Function, rho: Optional[Function]) 
     return V
 
 
-def _per_case(name: str, what: str, values, n_cases: int) -> np.ndarray:
-    """A scalar (the same for every load case) or one value per load case, as a float array of length n_cases."""
-    a = np.asarray(values, dtype=np.float64).ravel()
-    if a.size == 1 and np.ndim(values) == 0:
-        a = np.full(n_cases, float(a[0]))
-    if a.size != n_cases:
-        raise ValueError(f"{name}: {n_cases} load cases need as many {what}")
-    return a.copy()
-
-
 class ElasticityPnormStress(BackendForm):
     """J = (1/alpha) sum_e |T_e| (m rho_e^q sigma_vm,e)^p with the solid-material von Mises stress (module docstring);
     alpha = |Omega| unless given.  dJ/du is not a multiple of the load: its adjoint solve is a solve of its own.  Over
@@ -1933,7 +1953,6 @@ class ElasticityPnormStress(BackendForm):
         self.m, self.weights = m, weights
         self.E, self.nu, self.p, self.q = float(E), float(nu), float(p), float(q)
         self.alpha = float(cell_volumes(self.mesh).sum() if alpha is None else alpha)
-        self._grad = {}
         self._values = None
 
     def functions(self):
@@ -1955,10 +1974,7 @@ class ElasticityPnormStress(BackendForm):
         return float(self.weights @ self._values)
 
     def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:                                            # one buffer per argument: both partials may be pending
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        out = self._gradient_buffer(wrt, out)
         if wrt is self.u:
             self._call(value=False, grad_u=out)
         elif wrt is self.rho:
@@ -1978,8 +1994,8 @@ class MultiLoadPnormStress(ElasticityPnormStress):
     def __init__(self, u: Function, rho: Function, E: float = 1.0, nu: float = 0.3, m=1.0, p: float = 8.0, q: float = 0.5,
                  alpha: Optional[float] = None, weights=None):
         V = _check_multi_stress_spaces("MultiLoadPnormStress", u, rho)
-        m = _per_case("MultiLoadPnormStress", "scales m", m, V.n_cases)
-        weights = np.ones(V.n_cases) if weights is None else _per_case("MultiLoadPnormStress", "weights", weights, V.n_cases)
+        m = _n_values("MultiLoadPnormStress", "scales m", m, V.n_cases)
+        weights = np.ones(V.n_cases) if weights is None else _n_values("MultiLoadPnormStress", "weights", weights, V.n_cases)
         self._setup(u, rho, V.mesh, V.n_cases, m, weights, E, nu, p, q, alpha)
 
     def set_scales_from_state(self) -> np.ndarray:
@@ -2050,7 +2066,7 @@ class MultiLoadVonMises(ElasticityVonMises):
         V = _check_multi_stress_spaces("MultiLoadVonMises", u, rho)
         if load_case is not None and not 0 <= int(load_case) < V.n_cases:
             raise ValueError(f"MultiLoadVonMises: load case {load_case} of {V.n_cases}")
-        scales = None if scales is None else _per_case("MultiLoadVonMises", "scales", scales, V.n_cases)
+        scales = None if scales is None else _n_values("MultiLoadVonMises", "scales", scales, V.n_cases)
         if scales is not None and not np.all(scales > 0.0):
             raise ValueError("MultiLoadVonMises needs scales > 0")
         self._setup(u, rho, V.mesh, V.n_cases, scales, None if load_case is None else int(load_case), E, nu, q)
@@ -2178,7 +2194,7 @@ class EigenvalueAggregate(BackendForm):
         if not p >= 1.0:
             raise ValueError("EigenvalueAggregate needs p >= 1")
         self.eigen, self.rho, self.mesh, self.p = eigen, eigen.rho, eigen.mesh, float(p)
-        self._grad = None
+        self._grad_rho = None                      # one buffer of n_cell entries whatever the argument, not `_gradient_buffer`
 
     def functions(self):
         return (self.rho,)
@@ -2192,9 +2208,9 @@ class EigenvalueAggregate(BackendForm):
 
     def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
         if out is None:
-            if self._grad is None:
-                self._grad = Vec(_ctx(), self.mesh.n_cell)
-            out = self._grad
+            if self._grad_rho is None:
+                self._grad_rho = Vec(_ctx(), self.mesh.n_cell)
+            out = self._grad_rho
         if wrt is not self.rho:
             return out.fill(0.0)
         lam = self.eigen.eigenvalues()
@@ -2287,7 +2303,6 @@ class BucklingAggregate(BackendForm):
         if not p >= 1.0:
             raise ValueError("BucklingAggregate needs p >= 1")
         self.buckling, self.u, self.rho, self.mesh, self.p = buckling, buckling.u, buckling.rho, buckling.mesh, float(p)
-        self._grad = {}
 
     def functions(self):
         return (self.u, self.rho)
@@ -2296,10 +2311,7 @@ class BucklingAggregate(BackendForm):
         return float(_reciprocal_power_mean(self.buckling.load_factors(), self.p)[0])
 
     def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:                                            # one buffer per argument: both partials may be pending
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
+        out = self._gradient_buffer(wrt, out)
         if wrt is not self.u and wrt is not self.rho:
             return out.fill(0.0)
         b = self.buckling
@@ -2336,45 +2348,68 @@ class HarmonicElasticityMatrix(MultiLoadElasticityMatrix):
 
     multTranspose = mult
 
-    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
-        o = options or {}
-        F = self.form
-        infos = F.dynamic().dyn_solve_multi(F.n_cases, F.shifts, b, x, rtol=o.get("elast_rtol", F.rtol),
-                                            max_it=o.get("elast_max_it", F.max_it), pc=F.preconditioner)
-        self.info = F._record(infos, "adjoint")
-
     def to_scipy(self):
         import scipy.sparse as sp
         F = self.form
         K = F.dynamic().export_csr()
         M = _host_mass(F.mesh, np.array(F.rho.vec.get(), dtype=np.float64), F.mass_law, F.density)
-        blocks = []
-        for sg in F.shifts:
-            S = (K - sg * M).tocsr()
-            if self.masked and F._mask is not None:
-                free = sp.diags((F._mask == 0).astype(np.float64))
-                S = (free @ S @ free + sp.diags(F._mask.astype(np.float64))).tocsr()
-            blocks.append(S)
-        return sp.block_diag(blocks, format="csr")
+        return sp.block_diag([_mask_host((K - sg * M).tocsr(), self._host_mask()) for sg in F.shifts], format="csr")
 
 
 class _HarmonicDrho(_ElasticityDrho):
     """dR/drho of a `HarmonicElasticityResidual`: block l of column e = C'(rho_e) K0_e u_{l,e} - omega_l^2 density m'(rho_e)
     M0_e u_{l,e}; the mass term is one launch for all columns, added onto the stiffness term."""
 
-    def _mass(self, transpose: bool, x: Vec, y: Vec) -> Vec:
+    def _product(self, transpose: bool, x: Vec, y: Vec) -> Vec:
         F = self.form
+        super()._product(transpose, x, y)
         return F.device().mass_drho_multi(transpose, F.n_cases, -F.shifts, F.rho.vec, F.u.vec, x, y, density=F.density,
                                           mass_law=F.mass_law, accumulate=True)
 
-    def mult(self, x: Vec, y: Vec) -> Vec:
-        return self._mass(False, x, super().mult(x, y))
 
-    def multTranspose(self, x: Vec, y: Vec) -> Vec:
-        return self._mass(True, x, super().multTranspose(x, y))
+class _MassCarrying:
+    """What the residuals with a mass matrix share, mixed in ahead of their static base: M(rho) beside K(rho) on the handle,
+    the ``density`` / ``mass_law`` arguments and their solver's tolerance, and what none of them takes: body forces, thermal
+    loads, inhomogeneous supports."""
+
+    @staticmethod
+    def _refuse_loads(name: str, body, thermal) -> None:
+        if body is not None:
+            raise NotImplementedError(f"{name}: body forces are out of scope")
+        if thermal is not None:
+            raise NotImplementedError(f"{name}: thermal loads are out of scope")
+
+    @staticmethod
+    def _check_mass(name: str, density: float, mass_law: str) -> None:
+        if mass_law not in MASS_LAWS:
+            raise ValueError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
+        if not (np.isfinite(density) and density >= 0.0):
+            raise ValueError(f"{name}: the mass density must be finite and >= 0")
+
+    def _set_mass(self, density: float, mass_law: str, rtol: float) -> None:
+        """After `_setup`: the checked mass arguments, and the tolerance of this form's solver in place of the PCG's 1e-15."""
+        self.density, self.mass_law = float(density), mass_law
+        self.rtol = rtol
+
+    def _set_bcs(self, bcs) -> None:
+        super()._set_bcs(bcs)
+        if self._mask is not None and np.any(self._vals[self._mask == 1] != 0.0):
+            raise NotImplementedError(f"{self._supports_name}: inhomogeneous supports are out of scope")
+
+    def dynamic(self) -> DeviceElasticity:
+        """`stiffness()` with M(rho) of the current density as well: reassembled when the density (its version or its
+        vector), the mass density or the mass law changed since the last mass assembly on this handle."""
+        dev = self.stiffness()
+        key = (self.rho.version, id(self.rho.vec), self.density, self.mass_law)
+        if getattr(dev, "_mass_owner", None) != key:
+            dev.mass_assemble(self.rho.vec, density=self.density, mass_law=self.mass_law)
+            dev._mass_owner = key
+        return dev
+
+    _operator = dynamic
 
 
-class HarmonicElasticityResidual(MultiLoadElasticityResidual):
+class HarmonicElasticityResidual(_MassCarrying, MultiLoadElasticityResidual):
     """Column l of the residual is (K(rho) - omega_l^2 M(rho)) u_l - F_l: the undamped response to the time-harmonic load
     F_l cos(omega_l t), in real arithmetic.  ``u`` is a Function(LoadCaseSpace(V, L)); ``omegas``: one angular frequency
     >= 0 per column (a frequency sweep under one load repeats the traction); M = ``density`` sum_e m(rho_e) M0_e is the
@@ -2392,54 +2427,37 @@ class HarmonicElasticityResidual(MultiLoadElasticityResidual):
     Damping: `DampedHarmonicElasticityResidual`.  Out of scope: shifted or deflated preconditioners, frequency-band integrals,
     viscous dampers at points, body forces, inhomogeneous supports, partitioned meshes."""
     matrix_class = HarmonicElasticityMatrix
+    _supports_name = "HarmonicElasticityResidual"
+    _title, _solver, _kind, _residual = "harmonic elasticity", "MINRES", "elasticity_harmonic_", "estimated sqrt(r.M^-1 r)"
+    _column, _plural, _per_column = "column", "frequencies", {"omegas": "omega"}
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, omegas=None, density: float = 1.0,
                  mass_law: str = "linear", E: float = 1.0, nu: float = 0.3, method: str = "SIMP",
                  preconditioner: str = "jacobi", body_forces=None, thermal=None):
         name = "HarmonicElasticityResidual"
-        if body_forces is not None:
-            raise NotImplementedError(f"{name}: body forces are out of scope")
-        if thermal is not None:
-            raise NotImplementedError(f"{name}: thermal loads are out of scope")
+        self._refuse_loads(name, body_forces, thermal)
         if any(t is None for t in list(tractions)):
             raise ValueError(f"{name}: every column needs a traction (body forces are out of scope)")
         V, ts, dss, _ = _multi_arguments(name, u, tractions, measures)
-        if omegas is None:
-            raise ValueError(f"{name}: one angular frequency per column (omegas)")
-        om = _per_case(name, "frequencies omega", omegas, V.n_cases)
-        if not np.all(np.isfinite(om)) or np.any(om < 0.0):
-            raise ValueError(f"{name}: the frequencies omega must be finite and >= 0")
-        if mass_law not in MASS_LAWS:
-            raise ValueError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
-        if not (np.isfinite(density) and density >= 0.0):
-            raise ValueError(f"{name}: the mass density must be finite and >= 0")
+        om = self._check_omegas(name, omegas, V.n_cases)
+        self._check_mass(name, density, mass_law)
         self._setup(u, rho, V.base, V.n_cases, ts, dss, E, nu, method, preconditioner, None)
         self.omegas, self.shifts = om, om * om
-        self.density, self.mass_law = float(density), mass_law
-        self.rtol, self.max_it = 1e-12, 1_000_000
+        self._set_mass(density, mass_law, rtol=1e-12)
         self.solve_counts = {"state": 0, "adjoint": 0}
 
-    def _set_bcs(self, bcs) -> None:
-        super()._set_bcs(bcs)
-        if self._mask is not None and np.any(self._vals[self._mask == 1] != 0.0):
-            raise NotImplementedError("HarmonicElasticityResidual: inhomogeneous supports are out of scope")
-
-    def dynamic(self) -> DeviceElasticity:
-        """`stiffness()` with M(rho) of the current density as well: reassembled when the density (its version or its
-        vector), the mass density or the mass law changed since the last mass assembly on this handle."""
-        dev = self.stiffness()
-        key = (self.rho.version, id(self.rho.vec), self.density, self.mass_law)
-        if getattr(dev, "_mass_owner", None) != key:
-            dev.mass_assemble(self.rho.vec, density=self.density, mass_law=self.mass_law)
-            dev._mass_owner = key
-        return dev
+    @staticmethod
+    def _check_omegas(name: str, omegas, n: int) -> np.ndarray:
+        if omegas is None:
+            raise ValueError(f"{name}: one angular frequency per column (omegas)")
+        om = _n_values(name, "frequencies omega", omegas, n)
+        if not np.all(np.isfinite(om)) or np.any(om < 0.0):
+            raise ValueError(f"{name}: the frequencies omega must be finite and >= 0")
+        return om
 
     def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
         """Column l: (K - omega_l^2 M) u_l - F_l; one launch for all columns (femo_elast_dyn_apply_multi)."""
-        if out is None:
-            if self._res is None:
-                self._res = Vec(_ctx(), self.n_cases * self.n_dof)
-            out = self._res
+        out = self._residual_buffer(out)
         return self.dynamic().dyn_apply_multi(self.n_cases, self.shifts, self.u.vec, out, a=1.0, b=-1.0, f=self.load())
 
     def partial_matrix(self, wrt: Function, out=None):
@@ -2447,45 +2465,17 @@ class HarmonicElasticityResidual(MultiLoadElasticityResidual):
             return out if isinstance(out, _HarmonicDrho) else _HarmonicDrho(self)
         return super().partial_matrix(wrt, out)
 
-    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
-        """(K - omega_l^2 M) u_l = F_l for every column with the clamped dofs: ONE batched MINRES (the form is linear)."""
-        self._set_bcs(bcs)
-        dev = self.dynamic()
-        infos = dev.dyn_solve_multi(self.n_cases, self.shifts, self._rhs(dev), func.vec, rtol=self.rtol, max_it=self.max_it,
-                                    pc=self.preconditioner)
-        func.version += 1
-        self._record(infos, "state")
-        if report:
-            print(self._report(infos))
-
-    def _record(self, infos, kind: str):
-        from .utils_hip import LAST_KSP_INFO
-        cols = [dict(iterations=i.iterations, converged=i.converged, residual_norm=i.residual_norm, rhs_norm=i.rhs_norm)
-                for i in infos]
-        self.solve_counts[kind] = self.solve_counts.get(kind, 0) + 1
-        self.last_info[kind] = dict(columns=cols, n_cases=self.n_cases, iterations=[c["iterations"] for c in cols],
-                                    converged=[c["converged"] for c in cols], solve_ms=infos[0].solve_ms,
-                                    preconditioner=self.preconditioner, omegas=self.omegas.copy())
-        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_harmonic_" + kind))
-        for l, c in enumerate(cols):
-            if c["converged"] != 1:
-                raise RuntimeError(f"harmonic elasticity MINRES did not converge ({kind}, column {l} of {self.n_cases}, "
-                                   f"omega = {self.omegas[l]:.6g}): {c['iterations']} iterations, estimated sqrt(r.M^-1 r) = "
-                                   f"{c['residual_norm']:.3e} of {c['rhs_norm']:.3e}")
-        return infos
-
-    def _report(self, infos) -> str:
-        return (f"harmonic elasticity solve, {self.n_cases} frequencies: {[i.iterations for i in infos]} MINRES iterations, "
-                f"{infos[0].solve_ms:.1f} ms")
+    def _solve_columns(self, dev: DeviceElasticity, b: Vec, x: Vec, transpose: bool, **opts) -> list:
+        """(K - omega_l^2 M) x_l = b_l for every column: ONE batched MINRES (the matrix is symmetric)."""
+        return dev.dyn_solve_multi(self.n_cases, self.shifts, b, x, pc=self.preconditioner, **opts)
 
 
-class DynamicCompliance(BackendForm):
+class DynamicCompliance(_StateOutput):
     """J = sum_l w_l |c_l|, or sum_l w_l c_l^2 with ``squared``, over the columns of a harmonic state, c_l = F_l . u_l the
     dynamic compliance of column l (w = 1 without ``weights``).  Below the first resonance c_l > 0; above it the response
     may be in antiphase with the load and c_l < 0, hence the absolute value (Ma, Kikuchi & Cheng 1995) or the square, which
     is smooth where c_l changes sign.  dJ/du_l = w_l sgn(c_l) F_l, or 2 w_l c_l F_l; the form has no partial in the density --
     the framework's adjoint solve (one batched MINRES) and dR/drho of `HarmonicElasticityResidual` give the total."""
-    rank = 0
 
     def __init__(self, u: Function, tractions, measures=None, weights=None, squared: bool = False):
         name = "DynamicCompliance"
@@ -2493,12 +2483,8 @@ class DynamicCompliance(BackendForm):
             raise ValueError(f"{name}: every column needs a traction")
         V, self.tractions, self.measures, _ = _multi_arguments(name, u, tractions, measures)
         self.u, self.mesh, self.n_cases = u, V.mesh, V.n_cases
-        self.weights = np.ones(V.n_cases) if weights is None else _per_case(name, "weights", weights, V.n_cases)
+        self.weights = np.ones(V.n_cases) if weights is None else _n_values(name, "weights", weights, V.n_cases)
         self.squared = bool(squared)
-        self._grad = {}
-
-    def functions(self):
-        return (self.u,)
 
     def load(self) -> Vec:
         """Column l = F_l, unweighted."""
@@ -2513,25 +2499,18 @@ class DynamicCompliance(BackendForm):
         c = self.responses()
         return float(self.weights @ (c * c if self.squared else np.abs(c)))
 
-    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
-        if wrt is not self.u:
-            return out.fill(0.0)
+    def _state_gradient(self, out: Vec) -> Vec:
         c = self.responses()
         coef = self.weights * (2.0 * c if self.squared else np.sign(c))
         return elasticity_handle(self.mesh).block_rotate(self.n_cases, np.diag(coef), self.load(), out)
 
 
 # ------------------------------------------------------------------------------------ damped harmonic response ----
-class DampedHarmonicElasticityMatrix(MultiLoadElasticityMatrix):
+class DampedHarmonicElasticityMatrix(_UnsymmetricMatrix, MultiLoadElasticityMatrix):
     """dR/du of a `DampedHarmonicElasticityResidual` as the real operator on the 2L columns: [[A_l, -B_l], [B_l, A_l]] on
     the pair (2 l, 2 l + 1), A = K - omega^2 M, B = c_K K + c_M M -- not symmetric.  `mult` is Z, `multTranspose` conj(Z) (the
     transpose of the real operator); `backend_solve` is one batched COCR with Z (forward mode), `backend_solve_transpose`
     one with conj(Z) (the adjoint)."""
-    symmetric = False
 
     def _apply(self, conj: bool, x: Vec, y: Vec) -> Vec:
         F = self.form
@@ -2539,37 +2518,18 @@ class DampedHarmonicElasticityMatrix(MultiLoadElasticityMatrix):
         return dev.cdyn_apply_multi(F.n_freq, F.shifts, F.ck, F.cm, x, y, conj=conj,
                                     masked=self.masked and dev.fixed_key is not None)
 
-    def mult(self, x: Vec, y: Vec) -> Vec:
-        return self._apply(False, x, y)
-
-    def multTranspose(self, x: Vec, y: Vec) -> Vec:
-        return self._apply(True, x, y)
-
     def _solve(self, conj: bool, kind: str, b: Vec, x: Vec, options: Optional[dict]) -> None:
-        o = options or {}
-        F = self.form
-        infos = F.dynamic().cdyn_solve_multi(F.n_freq, F.shifts, F.ck, F.cm, b, x, conj=conj, rtol=o.get("elast_rtol", F.rtol),
-                                             max_it=o.get("elast_max_it", F.max_it), pc=F.preconditioner)
-        self.info = F._record(infos, kind)
-
-    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
-        self._solve(False, "forward", b, x, options)
-
-    def backend_solve_transpose(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
-        self._solve(True, "adjoint", b, x, options)
+        self.info = self.form._matrix_solve(b, x, kind, options, transpose=conj)
 
     def to_scipy(self):
         import scipy.sparse as sp
         F = self.form
         K = F.dynamic().export_csr()
         M = _host_mass(F.mesh, np.array(F.rho.vec.get(), dtype=np.float64), F.mass_law, F.density)
-        blocks = []
+        blocks, mask = [], self._host_mask()
         for sg, ck, cm in zip(F.shifts, F.ck, F.cm):
-            A, B = (K - sg * M).tocsr(), (ck * K + cm * M).tocsr()
-            if self.masked and F._mask is not None:
-                free = sp.diags((F._mask == 0).astype(np.float64))
-                A = (free @ A @ free + sp.diags(F._mask.astype(np.float64))).tocsr()
-                B = (free @ B @ free).tocsr()
+            A = _mask_host((K - sg * M).tocsr(), mask)
+            B = _mask_host((ck * K + cm * M).tocsr(), mask, identity=False)
             blocks.append(sp.bmat([[A, -B], [B, A]], format="csr"))
         return sp.block_diag(blocks, format="csr")
 
@@ -2604,19 +2564,13 @@ class _DampedHarmonicDrho(_ElasticityDrho):
             self._key = key
         return self._uk, self._um
 
-    def _both(self, transpose: bool, x: Vec, y: Vec) -> Vec:
+    def _product(self, transpose: bool, x: Vec, y: Vec) -> Vec:
         F = self.form
         uk, um = self._states()
         dev = F.device()
         dev.drho_multi(F.method_id, transpose, F.n_cases, F.rho.vec, uk, x, y)
         return dev.mass_drho_multi(transpose, F.n_cases, -np.ones(F.n_cases), F.rho.vec, um, x, y, density=F.density,
                                    mass_law=F.mass_law, accumulate=True)
-
-    def mult(self, x: Vec, y: Vec) -> Vec:
-        return self._both(False, x, y)
-
-    def multTranspose(self, x: Vec, y: Vec) -> Vec:
-        return self._both(True, x, y)
 
 
 def _damped_arguments(name: str, u: Function, tractions, measures):
@@ -2668,34 +2622,25 @@ class DampedHarmonicElasticityResidual(HarmonicElasticityResidual):
     supports, partitioned meshes."""
     matrix_class = DampedHarmonicElasticityMatrix
     is_symmetric = False
+    _title, _solver, _kind = "damped harmonic elasticity", "COCR", "elasticity_damped_harmonic_"
+    _residual, _count = "sqrt(Re(r^H M^-1 r))", "n_freq"
 
     def __init__(self, u: Function, rho: Function, tractions, measures=None, omegas=None, loss_factor: float = 0.0,
                  rayleigh=(0.0, 0.0), density: float = 1.0, mass_law: str = "linear", E: float = 1.0, nu: float = 0.3,
                  method: str = "SIMP", preconditioner: str = "jacobi", body_forces=None, thermal=None):
         name = "DampedHarmonicElasticityResidual"
-        if body_forces is not None:
-            raise NotImplementedError(f"{name}: body forces are out of scope")
-        if thermal is not None:
-            raise NotImplementedError(f"{name}: thermal loads are out of scope")
+        self._refuse_loads(name, body_forces, thermal)
         V, L, ts, dss = _damped_arguments(name, u, tractions, measures)
-        if omegas is None:
-            raise ValueError(f"{name}: one angular frequency per column (omegas)")
-        om = _per_case(name, "frequencies omega", omegas, L)
-        if not np.all(np.isfinite(om)) or np.any(om < 0.0):
-            raise ValueError(f"{name}: the frequencies omega must be finite and >= 0")
+        om = self._check_omegas(name, omegas, L)
         damping = np.array([float(loss_factor)] + [float(v) for v in np.ravel(rayleigh)])
         if damping.size != 3 or not np.all(np.isfinite(damping)) or np.any(damping < 0.0):
             raise ValueError(f"{name}: the damping (loss_factor, rayleigh = (alpha, beta)) must be finite and >= 0")
-        if mass_law not in MASS_LAWS:
-            raise ValueError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
-        if not (np.isfinite(density) and density >= 0.0):
-            raise ValueError(f"{name}: the mass density must be finite and >= 0")
+        self._check_mass(name, density, mass_law)
         self._setup(u, rho, V.base, 2 * L, ts, dss, E, nu, method, preconditioner, None)
         self.n_freq = L
         self.loss_factor, self.rayleigh = float(damping[0]), (float(damping[1]), float(damping[2]))
         self.omegas = om
-        self.density, self.mass_law = float(density), mass_law
-        self.rtol, self.max_it = 1e-12, 1_000_000
+        self._set_mass(density, mass_law, rtol=1e-12)
         self.solve_counts = {"state": 0, "adjoint": 0, "forward": 0}
 
     @property
@@ -2712,10 +2657,7 @@ class DampedHarmonicElasticityResidual(HarmonicElasticityResidual):
 
     def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
         """Columns 2 l, 2 l + 1: Re and Im of Z_l u_l - F_l; one launch (femo_elast_cdyn_apply_multi)."""
-        if out is None:
-            if self._res is None:
-                self._res = Vec(_ctx(), self.n_cases * self.n_dof)
-            out = self._res
+        out = self._residual_buffer(out)
         return self.dynamic().cdyn_apply_multi(self.n_freq, self.shifts, self.ck, self.cm, self.u.vec, out, a=1.0, b=-1.0,
                                                f=self.load())
 
@@ -2724,39 +2666,13 @@ class DampedHarmonicElasticityResidual(HarmonicElasticityResidual):
             return out if isinstance(out, _DampedHarmonicDrho) else _DampedHarmonicDrho(self)
         return MultiLoadElasticityResidual.partial_matrix(self, wrt, out)
 
-    def solve_state(self, func: Function, bcs, report: bool = False) -> None:
-        """Z_l u_l = F_l for every frequency with the clamped dofs: ONE batched COCR (the form is linear)."""
-        self._set_bcs(bcs)
-        dev = self.dynamic()
-        infos = dev.cdyn_solve_multi(self.n_freq, self.shifts, self.ck, self.cm, self._rhs(dev), func.vec, rtol=self.rtol,
-                                     max_it=self.max_it, pc=self.preconditioner)
-        func.version += 1
-        self._record(infos, "state")
-        if report:
-            print(self._report(infos))
-
-    def _record(self, infos, kind: str):
-        from .utils_hip import LAST_KSP_INFO
-        cols = [dict(iterations=i.iterations, converged=i.converged, residual_norm=i.residual_norm, rhs_norm=i.rhs_norm)
-                for i in infos]
-        self.solve_counts[kind] = self.solve_counts.get(kind, 0) + 1
-        self.last_info[kind] = dict(columns=cols, n_cases=self.n_freq, iterations=[c["iterations"] for c in cols],
-                                    converged=[c["converged"] for c in cols], solve_ms=infos[0].solve_ms,
-                                    preconditioner=self.preconditioner, omegas=self.omegas.copy())
-        LAST_KSP_INFO.append(dict(self.last_info[kind], kind="elasticity_damped_harmonic_" + kind))
-        for l, c in enumerate(cols):
-            if c["converged"] != 1:
-                raise RuntimeError(f"damped harmonic elasticity COCR did not converge ({kind}, column {l} of {self.n_freq}, "
-                                   f"omega = {self.omegas[l]:.6g}): {c['iterations']} iterations, sqrt(Re(r^H M^-1 r)) = "
-                                   f"{c['residual_norm']:.3e} of {c['rhs_norm']:.3e}")
-        return infos
-
-    def _report(self, infos) -> str:
-        return (f"damped harmonic elasticity solve, {self.n_freq} frequencies: {[i.iterations for i in infos]} COCR iterations, "
-                f"{infos[0].solve_ms:.1f} ms")
+    def _solve_columns(self, dev: DeviceElasticity, b: Vec, x: Vec, transpose: bool, **opts) -> list:
+        """Z_l x_l = b_l for every frequency, or with ``transpose`` conj(Z_l) x_l = b_l: ONE batched COCR."""
+        return dev.cdyn_solve_multi(self.n_freq, self.shifts, self.ck, self.cm, b, x, conj=transpose, pc=self.preconditioner,
+                                    **opts)
 
 
-class DampedDynamicCompliance(BackendForm):
+class DampedDynamicCompliance(_StateOutput):
     """J = sum_l w_l |c_l|, or sum_l w_l |c_l|^2 with ``squared``, over the frequencies of a damped harmonic state, c_l =
     F_l . u_l the complex dynamic compliance (unconjugated; the load is real).  dJ/du: the real column of frequency l is
     w_l (Re c_l / |c_l|) F_l and the imaginary one w_l (Im c_l / |c_l|) F_l; 2 w_l Re c_l F_l and 2 w_l Im c_l F_l for the square.
@@ -2764,18 +2680,13 @@ class DampedDynamicCompliance(BackendForm):
     `DampedHarmonicElasticityResidual` give the total,
     dJ/drho = sum_l w_l Re(conj(c_l) / |c_l| dc_l/drho), dc_l/drho_e = -u_e^T [C'(rho_e) K0_e (1 + i c_K) - density m'(rho_e) M0_e
     (omega_l^2 - i c_M)] u_e."""
-    rank = 0
 
     def __init__(self, u: Function, tractions, measures=None, weights=None, squared: bool = False):
         name = "DampedDynamicCompliance"
         V, L, self.tractions, self.measures = _damped_arguments(name, u, tractions, measures)
         self.u, self.mesh, self.n_cases, self.n_freq = u, V.mesh, V.n_cases, L
-        self.weights = np.ones(L) if weights is None else _per_case(name, "weights", weights, L)
+        self.weights = np.ones(L) if weights is None else _n_values(name, "weights", weights, L)
         self.squared = bool(squared)
-        self._grad = {}
-
-    def functions(self):
-        return (self.u,)
 
     def load(self) -> Vec:
         """Column 2 l = F_l, unweighted; column 2 l + 1 = 0."""
@@ -2792,13 +2703,7 @@ class DampedDynamicCompliance(BackendForm):
         a = np.abs(self.responses())
         return float(self.weights @ (a * a if self.squared else a))
 
-    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
-        if wrt is not self.u:
-            return out.fill(0.0)
+    def _state_gradient(self, out: Vec) -> Vec:
         c = self.responses()
         a = np.abs(c)
         coef = self.weights * (2.0 * c if self.squared else np.where(a > 0.0, c / np.where(a > 0.0, a, 1.0), 0.0))
@@ -2809,13 +2714,12 @@ class DampedDynamicCompliance(BackendForm):
 
 
 # ------------------------------------------------------------------------------------------ transient response ----
-class TransientElasticityMatrix(ElasticityMatrix):
+class TransientElasticityMatrix(_UnsymmetricMatrix):
     """dR/dU of a `TransientElasticityResidual`: the block lower-banded, block-Toeplitz L of the Newmark recurrence on the
     history -- not symmetric, but with symmetric blocks, so `backend_solve_transpose` (the adjoint) is the march of
     `backend_solve` (forward mode) run from the last step to the first.  With ``masked`` the diagonal blocks carry identity
     rows / columns on the fixed dofs and the sub-diagonal blocks zero ones.  `mult` / `multTranspose` are the banded product,
     8 time steps per launch."""
-    symmetric = False
 
     def getSizes(self):
         n = self.form.n_steps * self.form.n_dof
@@ -2829,12 +2733,6 @@ class TransientElasticityMatrix(ElasticityMatrix):
         return dev.newmark_apply(F.params, F.n_steps, x, y, transpose=transpose,
                                  masked=self.masked and dev.fixed_key is not None)
 
-    def mult(self, x: Vec, y: Vec) -> Vec:
-        return self._apply(False, x, y)
-
-    def multTranspose(self, x: Vec, y: Vec) -> Vec:
-        return self._apply(True, x, y)
-
     def _solve(self, reverse: bool, kind: str, b: Vec, x: Vec, options: Optional[dict]) -> None:
         o = options or {}
         F = self.form
@@ -2843,22 +2741,13 @@ class TransientElasticityMatrix(ElasticityMatrix):
                                                    pc=F.preconditioner)
         self.info = F._record((infos, stopped), kind)
 
-    def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
-        self._solve(False, "forward", b, x, options)
-
-    def backend_solve_transpose(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
-        self._solve(True, "adjoint", b, x, options)
-
     def to_scipy(self):
         import scipy.sparse as sp
         F = self.form
         K = F.dynamic().export_csr()
         M = _host_mass(F.mesh, np.array(F.rho.vec.get(), dtype=np.float64), F.mass_law, F.density)
-        A = [(m * M + k * K).tocsr() for m, k in zip(F.blocks["m"], F.blocks["k"])]
-        if self.masked and F._mask is not None:
-            free = sp.diags((F._mask == 0).astype(np.float64))
-            A = [(free @ A[0] @ free + sp.diags(F._mask.astype(np.float64))).tocsr(), (free @ A[1] @ free).tocsr(),
-                 (free @ A[2] @ free).tocsr()]
+        A = [_mask_host((m * M + k * K).tocsr(), self._host_mask(), identity=j == 0)        # ones on the diagonal blocks only
+             for j, (m, k) in enumerate(zip(F.blocks["m"], F.blocks["k"]))]
         N = F.n_steps
         sub = lambda k: sp.csr_matrix((np.ones(max(N - k, 0)), (np.arange(k, N), np.arange(0, max(N - k, 0)))), shape=(N, N))
         return (sp.kron(sp.identity(N), A[0]) + sp.kron(sub(1), A[1]) + sp.kron(sub(2), A[2])).tocsr()
@@ -2872,16 +2761,10 @@ class _TransientDrho(_ElasticityDrho):
     def getSizes(self):
         return (self.form.n_steps * self.form.n_dof, self.mesh.n_cell)
 
-    def _both(self, transpose: bool, x: Vec, y: Vec) -> Vec:
+    def _product(self, transpose: bool, x: Vec, y: Vec) -> Vec:
         F = self.form
         return F.device().newmark_drho(F.params, F.method_id, transpose, F.n_steps, F.rho.vec, F.u.vec, x, y, density=F.density,
                                        mass_law=F.mass_law)
-
-    def mult(self, x: Vec, y: Vec) -> Vec:
-        return self._both(False, x, y)
-
-    def multTranspose(self, x: Vec, y: Vec) -> Vec:
-        return self._both(True, x, y)
 
 
 def _transient_space(name: str, u: Function) -> TimeHistorySpace:
@@ -2893,7 +2776,7 @@ def _transient_space(name: str, u: Function) -> TimeHistorySpace:
     return V
 
 
-class TransientElasticityResidual(ElasticityResidual):
+class TransientElasticityResidual(_MassCarrying, ElasticityResidual):
     """The time-domain response M u'' + C u' + K(rho) u = g(t) F from rest, C = c_m M + c_k K (``rayleigh`` = (c_m, c_k)), by
     Newmark(``beta``, ``gamma``) with the step ``dt``, written as its two-step recurrence in the displacements:
 
@@ -2917,16 +2800,14 @@ class TransientElasticityResidual(ElasticityResidual):
     conditions, checkpointing, HHT-alpha and generalised-alpha, point dampers."""
     matrix_class = TransientElasticityMatrix
     is_symmetric = False
+    _supports_name = "TransientElasticityResidual"
 
     def __init__(self, u: Function, rho: Function, traction, ds: Optional[Measure] = None, signal=None, dt: float = None,
                  beta: float = 0.25, gamma: float = 0.5, rayleigh=(0.0, 0.0), density: float = 1.0, mass_law: str = "linear",
                  E: float = 1.0, nu: float = 0.3, method: str = "SIMP", preconditioner: str = "jacobi", body_force=None,
                  thermal=None):
         name = "TransientElasticityResidual"
-        if body_force is not None:
-            raise NotImplementedError(f"{name}: body forces are out of scope")
-        if thermal is not None:
-            raise NotImplementedError(f"{name}: thermal loads are out of scope")
+        self._refuse_loads(name, body_force, thermal)
         V = _transient_space(name, u)
         if traction is None:
             raise ValueError(f"{name}: the load pattern needs a traction (body forces are out of scope)")
@@ -2948,10 +2829,7 @@ class TransientElasticityResidual(ElasticityResidual):
         ray = np.array(rayleigh, dtype=np.float64).ravel()
         if ray.size != 2 or not np.all(np.isfinite(ray)) or np.any(ray < 0.0):
             raise ValueError(f"{name}: rayleigh = (c_m, c_k) must be two finite values >= 0")
-        if mass_law not in MASS_LAWS:
-            raise ValueError(f"unknown mass law {mass_law!r} (linear or du_olhoff)")
-        if not (np.isfinite(density) and density >= 0.0):
-            raise ValueError(f"{name}: the mass density must be finite and >= 0")
+        self._check_mass(name, density, mass_law)
         self._setup(u, rho, V.base, 1, [self.t], [self.ds], E, nu, method, preconditioner, None)
         self.n_steps, self.signal = V.n_steps, g
         self.dt, self.beta, self.gamma, self.rayleigh = float(dt), float(beta), float(gamma), (float(ray[0]), float(ray[1]))
@@ -2963,8 +2841,8 @@ class TransientElasticityResidual(ElasticityResidual):
                               1.0 - (1.0 - self.gamma) * self.dt * cm),
                            k=(self.gamma * self.dt * ck + self.beta * dt2, (1.0 - 2.0 * self.gamma) * self.dt * ck + b0 * dt2,
                               -(1.0 - self.gamma) * self.dt * ck + bm * dt2), b0=b0, bm=bm)
-        self.density, self.mass_law = float(density), mass_law
-        self.rtol, self.max_it, self.extrapolate = 1e-13, 1_000_000, True
+        self._set_mass(density, mass_law, rtol=1e-13)
+        self.extrapolate = True
         self.solve_counts = {"state": 0, "adjoint": 0, "forward": 0}
         self._B = None
 
@@ -2974,28 +2852,10 @@ class TransientElasticityResidual(ElasticityResidual):
         gm = np.concatenate([[0.0], g[:-2]])
         return self.dt ** 2 * (self.beta * g[1:] + self.blocks["b0"] * g[:-1] + self.blocks["bm"] * gm)
 
-    def _set_bcs(self, bcs) -> None:
-        super()._set_bcs(bcs)
-        if self._mask is not None and np.any(self._vals[self._mask == 1] != 0.0):
-            raise NotImplementedError("TransientElasticityResidual: inhomogeneous supports are out of scope")
-
-    def dynamic(self) -> DeviceElasticity:
-        """`stiffness()` with M(rho) of the current density as well, under the key rule of
-        `HarmonicElasticityResidual.dynamic`."""
-        dev = self.stiffness()
-        key = (self.rho.version, id(self.rho.vec), self.density, self.mass_law)
-        if getattr(dev, "_mass_owner", None) != key:
-            dev.mass_assemble(self.rho.vec, density=self.density, mass_law=self.mass_law)
-            dev._mass_owner = key
-        return dev
-
     def assemble_vector(self, out: Optional[Vec] = None) -> Vec:
         """R = L U - B of the whole history, without any Dirichlet treatment: the banded product and one launch for B."""
         n = self.n_steps * self.n_dof
-        if out is None:
-            if self._res is None:
-                self._res = Vec(_ctx(), n)
-            out = self._res
+        out = self._residual_buffer(out, n)
         dev = self.dynamic()
         if self._B is None:
             self._B = Vec(_ctx(), n)
@@ -3020,6 +2880,7 @@ class TransientElasticityResidual(ElasticityResidual):
             print(self._report(out))
 
     def _record(self, out, kind: str):
+        """`ElasticityResidual._record` for a march: ``out`` = (one record per step, the step it stopped at or -1)."""
         from .utils_hip import LAST_KSP_INFO
         infos, stopped = out
         taken = [i for i in infos if i.iterations > 0 or i.converged != 0]
@@ -3042,12 +2903,11 @@ class TransientElasticityResidual(ElasticityResidual):
                 f"{sum(i.solve_ms for i in infos):.1f} ms in the solves")
 
 
-class TransientCompliance(BackendForm):
+class TransientCompliance(_StateOutput):
     """J = sum_n w_n c_n, or sum_n w_n c_n^2 with ``squared``, over the steps of a transient state, c_n = F . u_n the work of
     the load pattern on step n (n = 1 ... N).  Without ``weights`` they are ``dt`` each -- the rectangle rule of int F . u dt --
     and ``dt``, the time step of the residual, must be given: the state's space does not know it.  dJ/du_n = w_n F or 2 w_n c_n F; the form has no partial in the density -- the reversed
     march of `TransientElasticityResidual` and its dR/drho give the total."""
-    rank = 0
 
     def __init__(self, u: Function, traction, ds: Optional[Measure] = None, weights=None, squared: bool = False,
                  dt: Optional[float] = None):
@@ -3067,10 +2927,6 @@ class TransientCompliance(BackendForm):
             if self.weights.size != V.n_steps or not np.all(np.isfinite(self.weights)):
                 raise ValueError(f"{name}: {V.n_steps} steps need as many finite weights")
         self.squared = bool(squared)
-        self._grad = {}
-
-    def functions(self):
-        return (self.u,)
 
     def load(self) -> Vec:
         return _load_vec(self.mesh, self.ds.facets(), self.t)
@@ -3083,13 +2939,7 @@ class TransientCompliance(BackendForm):
         c = self.responses()
         return float(self.weights @ (c * c if self.squared else c))
 
-    def assemble_derivative(self, wrt: Function, out: Optional[Vec] = None) -> Vec:
-        if out is None:
-            out = self._grad.get(id(wrt))
-            if out is None:
-                out = self._grad[id(wrt)] = Vec(_ctx(), wrt.function_space.dim)
-        if wrt is not self.u:
-            return out.fill(0.0)
+    def _state_gradient(self, out: Vec) -> Vec:
         coef = self.weights * (2.0 * self.responses() if self.squared else 1.0)
         return elasticity_handle(self.mesh).newmark_outer(self.n_steps, coef, self.load(), out)
 

@@ -32,6 +32,20 @@ class BackendForm(Form):
               assemble_system(bcs, rhs, out, out_nobc) -> (A, b);  solve_state(func, bcs, report);  new_matrix()
     and ``mesh``."""
     mesh = None
+    _grad = None          # id(argument) -> gradient vector, filled by `_gradient_buffer`
+
+    def _gradient_buffer(self, wrt: Function, out=None):
+        """``out``, or without one the form's own vector for the gradient in ``wrt``, allocated on first use: one buffer per
+        argument, since the partials in several arguments may be pending at once."""
+        if out is None:
+            if self._grad is None:
+                self._grad = {}
+            out = self._grad.get(id(wrt))
+            if out is None:
+                from ..engine import Vec
+                from .utils_hip import get_context
+                out = self._grad[id(wrt)] = Vec(get_context(), wrt.function_space.dim)
+        return out
 
 
 class PoissonResidual(Form):
