@@ -329,6 +329,9 @@ PROTOTYPES = {
     "femo_cond_apply": (C.c_int, [H, C.c_int, H, H]),
     "femo_cond_lift": (C.c_int, [H, H, H, H, H]),
     "femo_cond_solve": (C.c_int, [H, H, H, C.POINTER(SolverOpts), C.POINTER(SolveInfo)]),
+    "femo_cond_pc_apply": (C.c_int, [H, H, H]),
+    "femo_cond_pc_info": (C.c_int, [H, C.c_void_p, C.c_int]),
+    "femo_cond_pc_export_level": (C.c_int, [H, C.c_int, C.c_void_p]),
     "femo_cond_drho": (C.c_int, [H, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, H, H, H, H, C.c_int]),
     "femo_cond_export_csr": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # Method of Moving Asymptotes (csrc/mma.hip)

@@ -73,6 +73,10 @@ struct femo_pc {
   double lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
   std::vector<LatticeLevel> L;
   uint64_t built_key = 0;   // identity of the Dirichlet mask the coef arrays were built for
+  // ... and of the operator whose Galerkin diagonals weight them (FemoPcWeighted::gen; 0: the stock weights).  wt: what the
+  // begin of the current solve handed over, read by pc_prepare
+  uint64_t built_wgen = 0;
+  FemoPcWeighted wt;
   double* g_all = nullptr;  // the g arrays of all levels, coarsest first, contiguous
   // The levels the brick kernel accumulates into (the finest n_fused + 1) exist twice; applies alternate between
   // the two copies.  The fused prolongation reads the second-finest level from several workgroups, so it cannot
@@ -1792,6 +1796,15 @@ __global__ void k_lattice_coef_inject(int nc0, int nc1, int nc2, int nf0, int nf
   }
 }
 
+// operator-aware weights (FemoPcWeighted): the stock arrays hold keep * c_l with c_l > 0, so their zeros are the keep rule;
+// a kept node gets theta / G, a node no free vertex reaches (G == 0) nothing.  All levels in one launch.
+__global__ void k_lattice_coef_weighted(int64_t nodes, double theta, const double* __restrict__ G, double* __restrict__ coef) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nodes; i += (int64_t)gridDim.x * blockDim.x) {
+    const double g = G[i];
+    coef[i] = (coef[i] != 0.0 && g != 0.0) ? theta / g : 0.0;
+  }
+}
+
 inline unsigned lat_grid(int64_t n) {
   int64_t g = (n + 255) / 256;
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(g, 2048));
@@ -2245,10 +2258,12 @@ static int pc_setup_shared(femo_mesh* m) {
   return 0;
 }
 
-// coef arrays for the Dirichlet mask identified by `key` (mask == nullptr: no Dirichlet vertices)
+// coef arrays for the Dirichlet mask identified by `key` (mask == nullptr: no Dirichlet vertices) and the operator of the
+// current solve (femo_pc::wt).  An operator without weights of its own has wt.gen == 0 and built_wgen stays 0 between such
+// solves: the test below and everything behind it are then what they were before weighted operators existed.
 static int pc_prepare(femo_mesh* m, const uint8_t* mask, uint64_t key) {
   femo_pc* pc = m->pc;
-  if (pc->coef_valid && pc->built_key == key) return 0;
+  if (pc->coef_valid && pc->built_key == key && pc->built_wgen == pc->wt.gen) return 0;
   femo_ctx* ctx = m->ctx;
   hipStream_t st = ctx->stream;
   const int gv = (int)lat_grid(m->n_rows);
@@ -2277,9 +2292,14 @@ static int pc_prepare(femo_mesh* m, const uint8_t* mask, uint64_t key) {
     const LatticeLevel& Fi = pc->L[l + 1];
     hipLaunchKernelGGL(k_lattice_coef_inject, dim3(lat_grid(C.nodes)), dim3(256), 0, st, C.n[0], C.n[1], C.n[2], Fi.n[0], Fi.n[1], Fi.n[2], pc->dim, level_c(C), Fi.coef, C.coef);
   }
+  if (pc->wt.G != nullptr) {
+    const int64_t total = (pc->L[nl - 1].coef + pc->L[nl - 1].nodes) - pc->coef_all;
+    hipLaunchKernelGGL(k_lattice_coef_weighted, dim3(lat_grid(total)), dim3(256), 0, st, total, THETA, pc->wt.G, pc->coef_all);
+  }
   FEMO_HIP_CHECK(hipGetLastError());
   FEMO_HIP_CHECK(hipMemsetAsync(F.g, 0, F.nodes * sizeof(double), st));   // the restriction expects clean accumulators
   pc->built_key = key;
+  pc->built_wgen = pc->wt.gen;
   pc->coef_valid = true;
   return 0;
 }
@@ -2387,8 +2407,9 @@ int femo_pc_weights_early(femo_mesh* m, const double* s, const uint8_t* mask, ui
 }
 
 // start of a solve: per-vertex weights of the current operator; the atomically accumulated g arrays must be zero
-int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey) {
+int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey, const FemoPcWeighted* wt) {
   femo_pc* pc = m->pc;
+  pc->wt = wt != nullptr ? *wt : FemoPcWeighted{};
   if (m->ctx->nranks > 1 && getenv("FEMO_BPX_DENSE_ALLREDUCE") == nullptr) FEMO_TRY(pc_setup_shared(m));   // once; uses d_w_sorted as scratch
   FEMO_TRY(pc_weights(m, s, mask, wkey));
   const int nl = pc->n_levels;
@@ -2411,8 +2432,10 @@ bool femo_pc_merged_ok(femo_mesh* m) {
 int femo_pc_merged_collectives(const femo_mesh* m) { return m->ctx->nranks > 1 ? 1 : 0; }
 
 // start of a solve with the merged loop: weights of the current operator, clean accumulators, zero state
-int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra, uint64_t wkey) {
+int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra, uint64_t wkey,
+                         const FemoPcWeighted* wt) {
   femo_pc* pc = m->pc;
+  pc->wt = wt != nullptr ? *wt : FemoPcWeighted{};
   femo_ctx* ctx = m->ctx;
   const hipStream_t st = ctx->stream;
   if (ctx->nranks > 1) FEMO_TRY(pc_setup_shared(m));   // once; collective
@@ -2581,5 +2604,27 @@ int femo_pc_levels(const femo_mesh* m, int* n_levels, int64_t* finest_nodes) {
   if (!m->pc) { *n_levels = 0; *finest_nodes = 0; return 0; }
   *n_levels = m->pc->n_levels;
   *finest_nodes = m->pc->L.back().nodes;
+  return 0;
+}
+
+int femo_pc_lattice(const femo_mesh* m, int level, FemoLattice* out) {
+  FEMO_REQUIRE(m->pc != nullptr && out != nullptr, "femo_pc_lattice: the hierarchy is not built");
+  const femo_pc* pc = m->pc;
+  FEMO_REQUIRE(level >= 0 && level < pc->n_levels, "femo_pc_lattice: level %d of %d", level, pc->n_levels);
+  const LatticeLevel& L = pc->L[level];
+  const Lat a = make_lat(pc, L);
+  for (int k = 0; k < 3; ++k) { out->n[k] = a.n[k]; out->lo[k] = a.lo[k]; out->inv_h[k] = a.inv_h[k]; }
+  out->nodes = L.nodes;
+  out->offset = L.coef - pc->coef_all;
+  out->total = (pc->L.back().coef + pc->L.back().nodes) - pc->coef_all;
+  return 0;
+}
+
+int femo_pc_level_coef(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, int level, const double** coef, int64_t* nodes) {
+  FEMO_REQUIRE(m->pc != nullptr && coef != nullptr && nodes != nullptr, "femo_pc_level_coef: the hierarchy is not built");
+  FEMO_REQUIRE(level >= 0 && level < m->pc->n_levels, "femo_pc_level_coef: level %d of %d", level, m->pc->n_levels);
+  FEMO_TRY(pc_prepare(m, mask, mask_key));
+  *coef = m->pc->L[level].coef;
+  *nodes = m->pc->L[level].nodes;
   return 0;
 }

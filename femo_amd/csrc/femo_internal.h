@@ -443,6 +443,15 @@ struct femo_bc {
   uint64_t uid = 0;           // process-unique, never reused (keys cached preconditioner data)
 };
 
+// Operator-aware level weights of the BPX preconditioner: G holds diag(P_l^T A P_l) of every lattice level, coarsest first, in
+// the layout of the hierarchy's coefficient arrays (femo_pc_lattice: offset), and the coefficients become keep * theta / G
+// instead of the unit Laplacian's.  gen names the content of G (the generation of the matrix it was formed from, process-unique);
+// G == nullptr: the stock weights.  The buffer belongs to whoever formed it (conduction.hip).
+struct FemoPcWeighted {
+  const double* G = nullptr;
+  uint64_t gen = 0;
+};
+
 struct femo_mat {
   femo_mesh* mesh = nullptr;
   double* d_diag = nullptr;   // n_slices*64
@@ -475,6 +484,7 @@ struct femo_mat {
   uint8_t* d_pcmask = nullptr;  // n_vert bytes, valid when pc_key != 0 and pc_has_mask
   bool pc_has_mask = false;
   uint64_t pc_key = 0;
+  FemoPcWeighted pc_wt;         // level weights taken from the operator (the conduction matrices); default: the stock ones
   // content generation: process-unique, renewed by every assembly into this matrix (femo_mat_touch); 0 = never assembled
   uint64_t gen = 0;
 };
@@ -692,7 +702,9 @@ struct FemoMergedVecs {
 bool femo_pc_merged_ok(femo_mesh* m);                 // the fused lattice cycle with two brick-fused levels runs on this mesh
 struct FemoZeroExtra { double* p[3]; int64_t n[3]; int count; };     // small regions the caller wants cleared by the same launch
 // (wkey: see femo_pc_begin)
-int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra = nullptr, uint64_t wkey = 0);
+// (wt: see femo_pc_begin)
+int femo_pc_merged_begin(femo_mesh* m, const double* s, const uint8_t* mask, const FemoZeroExtra* extra = nullptr, uint64_t wkey = 0,
+                         const FemoPcWeighted* wt = nullptr);
 int femo_pc_merged_apply(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, const FemoMergedVecs& V, double* S,
                          const int32_t* done, const FemoPcgStop* stop);
 // N > 1: does femo_pc_merged_apply start the halo exchange of the direction it produces (interface vertices first, send buffer
@@ -720,7 +732,10 @@ bool femo_pc_can_piggyback(const femo_mesh* m);
 // wkey != 0: the operator content (femo_mat::gen) the weights are formed from -- a begin that finds the weights of the same
 // key, s and mask in place does not form them again (one rank; bpx.hip: pc_weights).  femo_pc_weights_early forms them ahead
 // of the solve, with the prescale, on a mesh whose hierarchy exists.
-int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey = 0);
+// wt: the level weights of the operator this solve is for (null or wt->G == nullptr: the stock weights).  The applies up to the
+// next begin use them; the coefficient arrays are cached under (mask key, wt->gen), so operators solved alternately on one mesh
+// each see their own.
+int femo_pc_begin(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey = 0, const FemoPcWeighted* wt = nullptr);
 int femo_pc_weights_early(femo_mesh* m, const double* s, const uint8_t* mask, uint64_t wkey);
 // the key a solve or a prescale of A passes: A's content generation on one rank with Newton's flag switched on, else 0
 // (FEMO_NEWTON_FLAG=0: the weights at every solve; read once per solve / prescale)
@@ -731,4 +746,14 @@ inline uint64_t femo_pc_weights_key(const femo_mat* A) {
   return (e != nullptr && e[0] == '0' && e[1] == 0) ? 0 : A->gen;
 }
 int femo_pc_levels(const femo_mesh* m, int* n_levels, int64_t* finest_nodes);
+// one level of a built hierarchy (coarsest = 0): its bins, the map x -> lattice coordinate (x - lo) * inv_h, its node count
+// and where it starts in the concatenated per-level arrays
+struct FemoLattice {
+  int n[3];
+  double lo[3], inv_h[3];
+  int64_t nodes, offset, total;
+};
+int femo_pc_lattice(const femo_mesh* m, int level, FemoLattice* out);
+// the coefficient array of one level as the applies after the last begin read it (built if need be); device pointer
+int femo_pc_level_coef(femo_mesh* m, const uint8_t* mask, uint64_t mask_key, int level, const double** coef, int64_t* nodes);
 int femo_reduce_to_host(femo_ctx* ctx, int nblocks, int nsums, double* host_out);

@@ -910,7 +910,7 @@ static int solve_pcg_bpx_merged(femo_mat* A, const femo_vec* b, femo_vec* x, con
     ze.p[ze.count] = w.r + n; ze.n[ze.count++] = tail;
   }
   if (opts->zero_guess && x->n > n) { ze.p[ze.count] = x->d + n; ze.n[ze.count++] = x->n - n; }   // ghost tail of the solution, as the classic loop leaves it
-  FEMO_TRY(femo_pc_merged_begin(m, A->d_s, mask, &ze, femo_pc_weights_key(A)));
+  FEMO_TRY(femo_pc_merged_begin(m, A->d_s, mask, &ze, femo_pc_weights_key(A), &A->pc_wt));
   const double* q0;
   FEMO_TRY(initial_guess(A, A->d_vals, x, opts->zero_guess, /*clear_x=*/false, w.q, &q0));
   double* const p0 = R ? slot(0) : w.p;
@@ -1071,7 +1071,7 @@ static int solve_pcg_bpx(femo_mat* A, int transpose, const femo_vec* b, femo_vec
   double* P = ctx->d_partials;
   double* S = ctx->d_scal;
   const uint8_t* mask = A->pc_has_mask ? A->d_pcmask : nullptr;
-  FEMO_TRY(femo_pc_begin(m, A->d_s, mask, femo_pc_weights_key(A)));
+  FEMO_TRY(femo_pc_begin(m, A->d_s, mask, femo_pc_weights_key(A), &A->pc_wt));
   auto allreduce1 = [&](double* d) -> int {
     if (multi) FEMO_TRY(femo_coll_allreduce(ctx, d, 1, st));
     return 0;
@@ -1224,7 +1224,7 @@ extern "C" int femo_mat_pc_apply(const femo_mat* A_, const femo_vec* r, femo_vec
   CgWork w;
   FEMO_TRY(ensure_work(ctx, n, m->n_vert, w, 1));
   const uint8_t* mask = A->pc_has_mask ? A->d_pcmask : nullptr;
-  FEMO_TRY(femo_pc_begin(m, A->d_s, mask, femo_pc_weights_key(A)));
+  FEMO_TRY(femo_pc_begin(m, A->d_s, mask, femo_pc_weights_key(A), &A->pc_wt));
   const int gv = vec_grid(ctx, n);
   FEMO_HIP_CHECK(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int32_t), st));
   if (n == 0) return 0;

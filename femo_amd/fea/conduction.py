@@ -11,12 +11,17 @@ is named ``temperature`` feeds an elastic `FEA` with an input of that name (`The
                        every vertex of c) plus a facet flux on ``ds`` lumped like the traction (|f| / d at every vertex of f);
                        it does not depend on rho.  dR/drho = k'(rho) |T_c| grad phi_v . grad T_c, matrix free, forward and
                        reverse one launch each.  Dirichlet values may be non-zero (a sink temperature): the right-hand side
-                       is the lifting b = Q - K_theta g, b = g on the fixed set.  The state and adjoint solves are the
-                       Jacobi-scaled `femo_solve_cg` to ``rtol`` (1e-13); a solve that does not converge raises
+                       is the lifting b = Q - K_theta g, b = g on the fixed set.  The state and adjoint solves are
+                       `femo_solve_cg` to ``rtol`` (1e-13), Jacobi-scaled by default; ``preconditioner="multilevel"`` adds
+                       the auxiliary-lattice BPX of csrc/bpx.hip with level weights theta / diag(P_l^T K_theta P_l) formed
+                       on the device once per assembly (tests/cond_pc_ref.py restates them), whose iteration count does not
+                       grow with the mesh; its stopping norm is that of the preconditioner, sqrt(r^T M^-1 r) <= rtol
+                       sqrt(b^T M^-1 b).  A solve that does not converge raises
   ThermalCompliance    J = Q^T T, dJ/dT = Q, nothing with respect to rho
 
-Out of scope: a multilevel preconditioner for K_theta (the iteration counts of the Jacobi-PCG are recorded in DESIGN.md),
-convection (Robin) boundaries, design-dependent sources, temperature-dependent material data, partitioned meshes.
+Out of scope: the lattice preconditioner as the default, a V-cycle or off-diagonal Galerkin operators on the lattices (the
+weights are diagonals), convection (Robin) boundaries, design-dependent sources, temperature-dependent material data,
+partitioned meshes.
 """
 from __future__ import annotations
 
@@ -27,15 +32,15 @@ import numpy as np
 
 from .. import _lib
 from .._lib import check
-from ..engine import Vec, _ptr
-from .elasticity import METHODS, Measure, _ctx, _fixed_data, lumped_facet_measure, cell_volumes
+from ..engine import PC_KINDS, Vec, _ptr
+from .elasticity import METHODS, PRECONDITIONERS, Measure, _ctx, _fixed_data, lumped_facet_measure, cell_volumes
 from .forms import BackendForm
 from .function import Function, FunctionSpace
 
 
 class DeviceConduction:
-    """femo_cond: K_theta(rho) and its eliminated form on the mesh's scalar pattern, the lifting, the Jacobi-PCG solve and the
-    two density products."""
+    """femo_cond: K_theta(rho) and its eliminated form on the mesh's scalar pattern, the lifting, the PCG solve (Jacobi or the
+    lattice preconditioner) and the two density products."""
 
     def __init__(self, ctx, mesh):
         self.ctx, self.lib, self.mesh = ctx, ctx.lib, mesh
@@ -46,13 +51,14 @@ class DeviceConduction:
         self.n_vert, self.n_cell = int(self.dm.n_vert), int(self.dm.n_cell)
         self.nnz = int(self.dm.info["nnz"])
         self._bc = None                     # the DirichletSet of the last assembly, kept alive with it
+        self._rho = None                    # ... and its density: the lattice weights are formed from it at the first solve
         self._work = None
 
     def assemble(self, method: int, k0: float, k_min: float, rho: Vec, bc=None) -> None:
         """K_theta(rho), and with the `engine.DirichletSet` ``bc`` the eliminated matrix beside it (one launch)."""
         check(self.lib.femo_cond_assemble(self.handle, int(method), float(k0), float(k_min), rho.handle,
                                           None if bc is None else bc.handle))
-        self._bc = bc
+        self._bc, self._rho = bc, rho
 
     def apply(self, x: Vec, y: Vec, eliminated: bool = False) -> Vec:
         check(self.lib.femo_cond_apply(self.handle, int(bool(eliminated)), x.handle, y.handle))
@@ -67,11 +73,37 @@ class DeviceConduction:
         return b
 
     def solve(self, b: Vec, x: Vec, rtol: float = 1e-13, atol: float = 0.0, max_it: int = 1_000_000, check_every: int = 8,
-              zero_guess: bool = True) -> "_lib.SolveInfo":
-        opts = _lib.SolverOpts(float(rtol), float(atol), int(max_it), int(bool(zero_guess)), int(check_every), 0, 0.0)
+              zero_guess: bool = True, pc: str = "jacobi") -> "_lib.SolveInfo":
+        """PCG; ``pc`` = "jacobi" or "multilevel" (the lattice preconditioner weighted with this operator's Galerkin
+        diagonals; ``rtol`` is then relative in the norm of the preconditioner)."""
+        if pc not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {pc!r} (jacobi or multilevel)")
+        opts = _lib.SolverOpts(float(rtol), float(atol), int(max_it), int(bool(zero_guess)), int(check_every),
+                               PC_KINDS["bpx" if pc == "multilevel" else "jacobi"], 0.0)
         info = _lib.SolveInfo()
         check(self.lib.femo_cond_solve(self.handle, b.handle, x.handle, C.byref(opts), C.byref(info)))
         return info
+
+    def pc_apply(self, r: Vec, z: Vec) -> Vec:
+        """z = M^-1 r with the lattice preconditioner of the current assembly, in unscaled variables."""
+        check(self.lib.femo_cond_pc_apply(self.handle, r.handle, z.handle))
+        return z
+
+    def pc_info(self) -> dict:
+        """Lattice levels, nodes per level (coarsest first) and how often the Galerkin diagonals were formed."""
+        out = np.zeros(34, np.int64)
+        check(self.lib.femo_cond_pc_info(self.handle, _ptr(out), len(out)))
+        nl = int(out[0])
+        return dict(levels=nl, builds=int(out[1]), nodes=[int(v) for v in out[2:2 + nl]])
+
+    def pc_level_weights(self, level: int) -> np.ndarray:
+        """C_level = keep theta / diag(P_l^T A P_l) of the current assembly."""
+        nodes = self.pc_info()["nodes"]
+        if not 0 <= level < len(nodes):
+            raise ValueError(f"level {level} of {len(nodes)}")
+        out = np.zeros(nodes[level])
+        check(self.lib.femo_cond_pc_export_level(self.handle, int(level), _ptr(out)))
+        return out
 
     def drho(self, method: int, k0: float, k_min: float, transpose: bool, rho: Vec, T: Vec, x: Vec, y: Vec, a: float = 1.0,
              accumulate: bool = False) -> Vec:
@@ -165,7 +197,7 @@ class _HeatLoad:
 
 class ConductionMatrix:
     """dR/dT = K_theta(rho); with ``masked`` the eliminated matrix (identity rows / columns on the fixed vertices).
-    `backend_solve` is the Jacobi-PCG of the form."""
+    `backend_solve` is the PCG of the form, with its preconditioner."""
     symmetric = True
     pde_kind = None
 
@@ -195,7 +227,8 @@ class ConductionMatrix:
     def backend_solve(self, b: Vec, x: Vec, options: Optional[dict] = None) -> None:
         o = options or {}
         F = self.form
-        info = F.operator().solve(b, x, rtol=o.get("cond_rtol", F.rtol), max_it=o.get("cond_max_it", 1_000_000))
+        info = F.operator().solve(b, x, rtol=o.get("cond_rtol", F.rtol), max_it=o.get("cond_max_it", 1_000_000),
+                                  pc=F.preconditioner)
         self.info = F._record(info, "adjoint")
 
     def to_scipy(self):
@@ -235,8 +268,8 @@ class _ConductionDrho:
 
 class ConductionResidual(BackendForm):
     """R(T; rho) = K_theta(rho) T - Q (see the module docstring).  ``source``: a number or a DG0 Function; ``flux``: a number on
-    the facets of ``ds``.  ``rtol`` (1e-13, the stopping level of the PDE filter) is that of the state and adjoint solves;
-    ``last_info[kind]`` keeps the record of the last solve of each kind ("state", "adjoint").  Q is non-zero on the fixed
+    the facets of ``ds``.  ``rtol`` (1e-13, the stopping level of the PDE filter) is that of the state and adjoint solves,
+    ``preconditioner`` ("jacobi", the default, or "multilevel": see the module docstring) theirs; ``last_info[kind]`` keeps the record of the last solve of each kind ("state", "adjoint").  Q is non-zero on the fixed
     vertices, and so is the multiplier of an output such as `ThermalCompliance`: the exact reduced gradient needs
     ``fea.consistent_bc_partials = True``, as for the body and thermal loads of the elasticity."""
     rank = 1
@@ -246,13 +279,16 @@ class ConductionResidual(BackendForm):
     matrix_class = ConductionMatrix
 
     def __init__(self, T: Function, rho: Function, source=None, flux=None, ds: Optional[Measure] = None, k0: float = 1.0,
-                 k_min: float = 0.0, method: str = "SIMP"):
+                 k_min: float = 0.0, method: str = "SIMP", preconditioner: str = "jacobi"):
         name = "ConductionResidual"
         mesh = _check_scalar_space(name, T)
         if rho.function_space.family != "DG" or rho.function_space.mesh is not mesh:
             raise NotImplementedError(f"{name} needs a DG0 density on the temperature's mesh")
         if method not in METHODS:
             raise ValueError(f"unknown penalisation method {method!r} (SIMP or RAMP)")
+        if preconditioner not in PRECONDITIONERS:
+            raise ValueError(f"unknown preconditioner {preconditioner!r} (jacobi or multilevel)")
+        self.preconditioner = preconditioner
         k0, k_min = float(k0), float(k_min)
         if not (np.isfinite(k0) and np.isfinite(k_min) and 0.0 <= k_min < k0):
             raise ValueError(f"{name}: finite conductivities with 0 <= k_min < k0 are needed")
@@ -299,10 +335,11 @@ class ConductionResidual(BackendForm):
     def _record(self, info, kind: str):
         from .utils_hip import LAST_KSP_INFO
         self.last_info[kind] = dict(iterations=info.iterations, converged=info.converged, solve_ms=info.solve_ms,
-                                    residual_norm=info.residual_norm, rhs_norm=info.rhs_norm, preconditioner="jacobi")
+                                    residual_norm=info.residual_norm, rhs_norm=info.rhs_norm,
+                                    preconditioner=self.preconditioner)
         LAST_KSP_INFO.append(dict(self.last_info[kind], kind="conduction_" + kind))
         if info.converged != 1:
-            raise RuntimeError(f"conduction PCG did not converge ({kind}): {info.iterations} iterations, "
+            raise RuntimeError(f"conduction PCG ({self.preconditioner}) did not converge ({kind}): {info.iterations} iterations, "
                                f"sqrt(r.D^-1 r) = {info.residual_norm:.3e} of {info.rhs_norm:.3e}")
         return info
 
@@ -351,10 +388,10 @@ class ConductionResidual(BackendForm):
         return dev.lift(Q, self._b, g)
 
     def solve_state(self, func: Function, bcs, report: bool = False) -> None:
-        """K_theta(rho) T = Q with the strongly imposed temperatures: one Jacobi-PCG solve (the form is linear)."""
+        """K_theta(rho) T = Q with the strongly imposed temperatures: one PCG solve (the form is linear)."""
         self._set_bcs(bcs)
         dev = self.operator()
-        info = dev.solve(self._rhs(dev), func.vec, rtol=self.rtol)
+        info = dev.solve(self._rhs(dev), func.vec, rtol=self.rtol, pc=self.preconditioner)
         func.version += 1
         self._record(info, "state")
         if report:
@@ -386,9 +423,10 @@ class ThermalCompliance(BackendForm):
 
 
 def pdeRes_conduction(T, v, rho_e, source=None, flux=None, dss: Optional[Measure] = None, k0: float = 1.0, k_min: float = 0.0,
-                      method: str = "SIMP") -> ConductionResidual:
+                      method: str = "SIMP", preconditioner: str = "jacobi") -> ConductionResidual:
     """The conduction residual in the style of `pdeRes`; ``v`` is implied by the catalogue."""
-    return ConductionResidual(T, rho_e, source=source, flux=flux, ds=dss, k0=k0, k_min=k_min, method=method)
+    return ConductionResidual(T, rho_e, source=source, flux=flux, ds=dss, k0=k0, k_min=k_min, method=method,
+                              preconditioner=preconditioner)
 
 
 def thermal_compliance(T, source=None, flux=None, dss: Optional[Measure] = None) -> ThermalCompliance:

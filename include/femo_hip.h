@@ -1056,10 +1056,22 @@ int femo_pde_filter_bytes(const femo_pde_filter* f, int64_t* bytes);
  * apply: y = K_theta x, or with eliminated = 1 the eliminated matrix.
  * lift: the right-hand side for Dirichlet values g (NULL: zero): b = g on the set, b = q - K_theta g elsewhere; g holds the
  *   values on the set and zeros elsewhere; work: n_rows scratch entries (needed with g).
- * solve: Jacobi-scaled femo_solve_cg with the eliminated matrix (the plain one without a set); opts NULL: rtol 1e-13 from the
- *   zero guess; opts->pc must be FEMO_PC_JACOBI.  A non-finite density or right-hand side is found as the non-finite Jacobi
- *   norm of the right-hand side and refused (x may have been written; the next call works).  Whether the solve converged is
- *   in info.  No multilevel preconditioner for this operator.
+ * solve: femo_solve_cg with the eliminated matrix (the plain one without a set); opts NULL: Jacobi, rtol 1e-13 from the zero
+ *   guess.  opts->pc selects the preconditioner and with it the stopping rule, as femo_solver_opts defines them:
+ *     FEMO_PC_JACOBI (default)  sqrt(r^T D^-1 r) <= max(rtol sqrt(b^T D^-1 b), atol)
+ *     FEMO_PC_BPX               sqrt(r^T M^-1 r) <= max(rtol sqrt(b^T M^-1 b), atol_pc)   or   sqrt(r^T D^-1 r) <= atol (if > 0)
+ *   FEMO_PC_BPX is the auxiliary-lattice preconditioner of csrc/bpx.hip with level weights taken from this operator,
+ *     M^-1 = D^-1 + sum_l P_l C_l P_l^T,   C_l[I] = keep_l[I] 0.6 / G_l[I],   G_l[I] = (Pt_l^T A Pt_l)_II
+ *   (Pt_l: multilinear interpolation from lattice l to the free vertices, A the matrix that is solved; tests/cond_pc_ref.py).
+ *   G is formed on the device by the first such solve after an assembly and shared by the later ones; it reads the density
+ *   handed to femo_cond_assemble again, which must still be alive and unchanged then.  The sums of G are fp64 atomics: a BPX
+ *   solve repeats to rounding, not bit for bit; the Jacobi path is untouched by all of this.  A non-finite density or
+ *   right-hand side is found as the non-finite Jacobi norm of the right-hand side, or as the breakdown of the first iteration,
+ *   and refused with either preconditioner (x may have been written; the next call works).  Whether the solve converged is
+ *   in info.
+ * pc_apply: z = M^-1 r with the FEMO_PC_BPX operator above in unscaled variables, as femo_mat_pc_apply (tests).
+ * pc_info: out[0] lattice levels, out[1] builds of G so far, out[2 + l] nodes of level l (coarsest first), count entries at most.
+ * pc_export_level: the count of pc_info's out[2 + level] weights C_level of the current assembly, to host memory.
  * drho: the density products of R = K_theta(rho) T - Q at the temperature T, k' = (k_0 - k_min) C',
  *   transpose = 0:  y[v] = (accumulate ? y[v] : 0) + a sum_{c around v} k'(rho_c) x_c |T_c| grad phi_v . grad T_c   (x: n_cell)
  *   transpose = 1:  y[c] = (accumulate ? y[c] : 0) + a k'(rho_c) |T_c| grad x_c . grad T_c                         (x: n_vert)
@@ -1072,6 +1084,9 @@ int femo_cond_assemble(femo_cond* c, int method, double k0, double k_min, const 
 int femo_cond_apply(femo_cond* c, int eliminated, const femo_vec* x, femo_vec* y);
 int femo_cond_lift(femo_cond* c, const femo_vec* q, const femo_vec* g /* or NULL */, femo_vec* work /* or NULL */, femo_vec* b);
 int femo_cond_solve(femo_cond* c, const femo_vec* b, femo_vec* x, const femo_solver_opts* opts, femo_solve_info* info);
+int femo_cond_pc_apply(femo_cond* c, const femo_vec* r, femo_vec* z);
+int femo_cond_pc_info(femo_cond* c, int64_t* out, int count);
+int femo_cond_pc_export_level(femo_cond* c, int level, double* coef);
 int femo_cond_drho(femo_cond* c, int method, double k0, double k_min, int transpose, double a, const femo_vec* rho,
                    const femo_vec* T, const femo_vec* x, femo_vec* y, int accumulate);
 int femo_cond_export_csr(const femo_cond* c, int eliminated, int64_t* rowptr, int32_t* col, double* val);

@@ -45,7 +45,11 @@ and its share of 8 TB/s, the filter build time, and a SciPy spsolve cycle of the
                                                                  alternated cycle by cycle with the mechanical-only cycle of the same
                                                                  build; the three launches of the thermal-load operator and the
                                                                  conduction assembly in windows of 200 launches; --counts adds the
-                                                                 Jacobi-PCG iterations of the conduction solves at three sizes)
+                                                                 PCG iterations of the conduction solves at three sizes, Jacobi and
+                                                                 the lattice preconditioner side by side; with --pc multilevel the
+                                                                 conduction form takes the lattice preconditioner too, and a third
+                                                                 leg, the same cycle with the conduction form on Jacobi, is alternated
+                                                                 with the other two)
 """
 from __future__ import annotations
 
@@ -470,10 +474,11 @@ def damped_solves(ctx, res, u, fs, dss, bcs, loss_factor, repeats=5):
                 damped_dynamic_compliance=float(J.assemble_scalar()), damped_responses_abs=[float(abs(c)) for c in J.responses()])
 
 
-def build_thermoelastic(args, thermal: bool):
+def build_thermoelastic(args, thermal: bool, cond_pc=None):
     """The cantilever of `build` as the thermoelastic chain rho -> T(rho) -> u(rho, T) -> J (two FEA objects: uniform heating
     with the sink on the clamped edge, the tip traction plus the thermal load of the computed temperature, J the work of the
-    total load), or with ``thermal`` False the mechanical cycle alone in the same set-up."""
+    total load), or with ``thermal`` False the mechanical cycle alone in the same set-up.  ``cond_pc``: the preconditioner of
+    the conduction form (default: --pc, like the elasticity)."""
     from femo_amd.csdl_opt.fea_model import FEAModel
     from femo_amd.csdl_opt.filter_model import GeneralFilterModel
     from femo_amd.csdl_opt.simulator import Simulator
@@ -494,7 +499,7 @@ def build_thermoelastic(args, thermal: bool):
         ft.REPORT = False
         ft.consistent_bc_partials = True
         rho_t, T = Function(Q), Function(P)
-        res_t = pdeRes_conduction(T, None, rho_t, source=1e-2, k0=1.0, k_min=1e-3)
+        res_t = pdeRes_conduction(T, None, rho_t, source=1e-2, k0=1.0, k_min=1e-3, preconditioner=cond_pc or args.pc)
         ft.add_input("density", rho_t)
         ft.add_state(name="temperature", function=T, residual_form=res_t, arguments=["density"])
         Tbc = Function(P)
@@ -529,9 +534,10 @@ def build_thermoelastic(args, thermal: bool):
 
 
 def conduction_counts(ctx, sizes=((80, 40), (320, 160), (640, 320))):
-    """Jacobi-PCG iterations of the conduction state (uniform source) and of an adjoint-like solve (right-hand side: the state)
-    at rho = 0.5 and on the black / white truss pattern, k_min = 1e-3, the sink on x = 0, rtol 1e-13: the baseline a later
-    preconditioner is judged against."""
+    """PCG iterations of the conduction state (uniform source) and of an adjoint-like solve (right-hand side: the state) at
+    rho = 0.5 and on the black / white truss pattern, k_min = 1e-3, the sink on x = 0, rtol 1e-13, with both preconditioners
+    side by side: Jacobi (relative in the Jacobi norm) and the lattice preconditioner weighted by the operator's Galerkin
+    diagonals (relative in its own norm)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import elast_pc_ref as pr
     from femo_amd.fea.conduction import ConductionResidual
@@ -541,18 +547,23 @@ def conduction_counts(ctx, sizes=((80, 40), (320, 160), (640, 320))):
         mesh = createRectangleMesh(np.array([0.0, 0.0]), np.array([160.0, 80.0]), nelx, nely)
         Q, P = FunctionSpace(mesh, ("DG", 0)), FunctionSpace(mesh, ("CG", 1))
         T, rho = Function(P), Function(Q)
-        form = ConductionResidual(T, rho, source=1e-2, k0=1.0, k_min=1e-3)
+        forms = {pc: ConductionResidual(T, rho, source=1e-2, k0=1.0, k_min=1e-3, preconditioner=pc) for pc in ("jacobi", "multilevel")}
         bcs = [dirichletbc(0.0, locate_dofs_geometrical((P, P), lambda x: np.isclose(x[0], 0.0, atol=1e-6)), P)]
         for kind in ("uniform", "truss"):
             rho.vector[:] = pr.count_density(kind, mesh.centroids(), 80.0)
-            form.solve_state(T, bcs)
-            st = dict(form.last_info["state"])
-            A, _ = form.assemble_system(bcs, False, None, None)
-            lam = Function(P)
-            A.backend_solve(T.vec, lam.vec)
-            ad = form.last_info["adjoint"]
-            out.append(dict(mesh=f"rect {nelx}x{nely}", density=kind, n_vert=mesh.n_vert, state_iterations=st["iterations"],
-                            state_ms=st["solve_ms"], adjoint_iterations=ad["iterations"], adjoint_ms=ad["solve_ms"]))
+            row = dict(mesh=f"rect {nelx}x{nely}", density=kind, n_vert=mesh.n_vert)
+            for pc, form in forms.items():
+                form.solve_state(T, bcs)
+                form.solve_state(T, bcs)                       # the second solve: hierarchy, weights and work vectors exist
+                st = dict(form.last_info["state"])
+                A, _ = form.assemble_system(bcs, False, None, None)
+                lam = Function(P)
+                A.backend_solve(T.vec, lam.vec)
+                ad = form.last_info["adjoint"]
+                tag = "" if pc == "jacobi" else "multilevel_"
+                row.update({tag + "state_iterations": st["iterations"], tag + "state_ms": st["solve_ms"],
+                            tag + "adjoint_iterations": ad["iterations"], tag + "adjoint_ms": ad["solve_ms"]})
+            out.append(row)
     return out
 
 
@@ -562,6 +573,9 @@ def main_thermal(args, ctx):
     from femo_amd import _lib
     from femo_amd.engine import Vec
     legs = {name: build_thermoelastic(args, name == "thermoelastic") for name in ("thermoelastic", "mechanical")}
+    if args.pc == "multilevel":
+        # the same cycle with the conduction form on Jacobi, alternated with the other two: what the lattice path is judged against
+        legs["thermoelastic_cond_jacobi"] = build_thermoelastic(args, True, cond_pc="jacobi")
     x0 = np.array(legs["mechanical"][0]["density_unfiltered"])
     times = {name: [] for name in legs}
     for k in range(args.cycles + 1):
@@ -606,6 +620,24 @@ def main_thermal(args, ctx):
                mechanical_iterations=[im["state"]["iterations"], im["adjoint"]["iterations"]],
                compliance_thermoelastic=float(sim["compliance"][0]), compliance_mechanical=float(legs["mechanical"][0]["compliance"][0]),
                **launches)
+    spread = lambda v: float(np.percentile(v, 75) - np.percentile(v, 25))
+    out.update(conduction_pc=res_t.preconditioner, cycle_ms_thermoelastic_iqr=spread(times["thermoelastic"]),
+               cycle_ms_mechanical_iqr=spread(times["mechanical"]))
+    if "thermoelastic_cond_jacobi" in legs:
+        tj, ij = times["thermoelastic_cond_jacobi"], legs["thermoelastic_cond_jacobi"][3].last_info
+        out.update(cycle_ms_thermoelastic_cond_jacobi=float(np.median(tj)), cycle_ms_thermoelastic_cond_jacobi_iqr=spread(tj),
+                   cycle_ms_thermoelastic_cond_jacobi_all=[float(v) for v in tj],
+                   conduction_jacobi_iterations=[ij["state"]["iterations"], ij["adjoint"]["iterations"]],
+                   conduction_jacobi_solve_ms=[ij["state"]["solve_ms"], ij["adjoint"]["solve_ms"]])
+        # the Galerkin diagonals of the lattice weights: ms per assembly, assembly + build against the assembly alone
+        one_rhs = Vec(ctx, nv).fill(1.0)
+        zz = Vec(ctx, nv)
+        both = timed(lambda: (cond.assemble(_lib.ELAST_SIMP, 1.0, 1e-3, res_t.rho.vec, res_t._bc), cond.pc_apply(one_rhs, zz)), reps=50)
+        cond.pc_apply(one_rhs, zz)
+        apply_only = timed(lambda: cond.pc_apply(one_rhs, zz), reps=50)
+        out.update(conduction_pc_build_us=both - apply_only - launches["conduction_assemble_us"], conduction_pc_apply_us=apply_only,
+                   conduction_ms_per_iteration=[it[k]["solve_ms"] / max(it[k]["iterations"], 1) for k in ("state", "adjoint")],
+                   conduction_jacobi_ms_per_iteration=[ij[k]["solve_ms"] / max(ij[k]["iterations"], 1) for k in ("state", "adjoint")])
     if args.counts:
         out["conduction_counts"] = conduction_counts(ctx)
     print(json.dumps(out))
@@ -671,7 +703,8 @@ def main():
                     help="the thermoelastic cycle (conduction state, thermal expansion load, two adjoint solves) alternated with the "
                          "mechanical-only cycle of the same build; 2-D, single load case")
     ap.add_argument("--counts", action="store_true",
-                    help="with --thermal: the Jacobi-PCG iteration counts of the conduction solves at 80x40, 320x160 and 640x320")
+                    help="with --thermal: the PCG iteration counts of the conduction solves at 80x40, 320x160 and 640x320, Jacobi and the "
+                         "lattice preconditioner side by side")
     args = ap.parse_args()
     if args.thermal and (args.n3 or args.load_cases > 1 or args.harmonic or args.stress or args.filter != "neighbours"):
         ap.error("--thermal: the 2-D cantilever with one load case and the neighbour filter")

@@ -16,7 +16,8 @@ loop with the device-resident MMA update in the place of modopt's SLSQP / SNOPT.
                       x = 0, y <= 0.1; minimises u_out under avg_density <= volume from x = volume
   ... --problem heatsink [--volume 0.3 --move 0.2]   the heat-sink problem on the 2 x 1 rectangle: uniform heating, a sink T = 0
                       over the middle fifth of the left edge, conductivity k_min + (1 - k_min) rho^3 with k_min = 1e-3
-                      (ConductionResidual); minimises the thermal compliance under avg_density <= volume from x = volume
+                      (ConductionResidual); minimises the thermal compliance under avg_density <= volume from x = volume;
+                      --pc multilevel: the conduction solves with the lattice preconditioner weighted by K_theta's diagonals
   ... --filter helmholtz        the Helmholtz PDE filter (HelmholtzFilterModel, or ProjectedFilterModel(filter="helmholtz") with
                       --betas) in the neighbour list's place: one scalar solve per product, memory independent of the radius
 
@@ -168,7 +169,7 @@ def build_heatsink(args):
     fea.consistent_bc_partials = True          # the load Q is non-zero on the sink, and so is the multiplier
     Q, P = FunctionSpace(mesh, ("DG", 0)), FunctionSpace(mesh, ("CG", 1))
     rho, T = Function(Q), Function(P)
-    res = pdeRes_conduction(T, None, rho, source=1.0, k0=1.0, k_min=1e-3)
+    res = pdeRes_conduction(T, None, rho, source=1.0, k0=1.0, k_min=1e-3, preconditioner=args.pc)
     fea.add_input("density", rho)
     fea.add_state(name="temperature", function=T, residual_form=res, arguments=["density"])
     fea.add_output(name="avg_density", type="scalar", form=averageFunc(rho), arguments=["density"])
@@ -314,7 +315,7 @@ def main():
                    kin=args.kin, kout=args.kout, volume=args.volume, move=move,
                    pcg_iterations=[[r["kind"].split("_")[-1], r["iterations"]] for r in pcg_log])
     elif heatsink:
-        # state and adjoint Jacobi-PCG of every design cycle, in the order they ran
+        # state and adjoint PCG of every design cycle (--pc: Jacobi or the lattice preconditioner), in the order they ran
         pcg_log = [r for r in utils_hip.LAST_KSP_INFO if str(r.get("kind", "")).startswith("conduction_")]
         out.update(metric="topopt_mma_heatsink", final_thermal_compliance=float(np.asarray(sim["thermal_compliance"]).ravel()[0]),
                    volume=args.volume, move=move, k_min=1e-3,
